@@ -49,6 +49,7 @@ OPS_PER_PAIR = 3         # xor, popcount, compare: the ideal N-free one-word for
 OPS_PER_PAIR_REAL = 5    # ... with 64-bit xor and popcount as two 32-bit ops each
 PROFILE_JSON = os.path.join(ROOT, "profiles", "r03_counters.json")
 KERNEL_NAMES = {0: None, 1: "small_bucket_kernel", 2: "seg_pair_kernel"}
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: everything written together
 
 
 def stamped_sources():
@@ -403,6 +404,7 @@ def measure(res, steps, warmup, profile=True):
         res.step()
     res.drain_gathers()
     dt, stats_plain = res.timed(steps)
+    kept_last = res.d_kept[:res.n].cpu().numpy()  # what the last timed step returned (--dump-outputs)
     kept_n = int(res.d_kept[:res.n].sum().item())
     assert kept_n == stats_plain[-1]["n_kept"]
     res.check_gathered(kept_n)
@@ -433,7 +435,21 @@ def measure(res, steps, warmup, profile=True):
                      "pairs_evaluated": s0["n_pairs_evaluated"]},
         "roofline": roofline_of(wl, res.n, stats, ms_step),
     }
-    return out, dt, stats, kept_n
+    return out, dt, stats, kept_n, kept_last
+
+
+def dump_outputs(out_dir, kept):
+    """--dump-outputs: the kept mask of the last timed step as out_dir/kept.npy (float32, 1 = kept, in the
+    order of the workload's unique UMIs).  A mask larger than DUMP_MAX_BYTES is cut to the same seeded
+    sample of entries on every run, their indices beside it (kept_index.npy, float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    kept = kept.astype(np.float32)
+    if kept.nbytes > DUMP_MAX_BYTES:
+        n_sample = (DUMP_MAX_BYTES - 4096) // (4 + 8)  # float32 mask + float64 index per entry, .npy headers
+        idx = np.sort(np.random.default_rng(0).choice(len(kept), n_sample, replace=False))
+        np.save(os.path.join(out_dir, "kept_index.npy"), idx.astype(np.float64))
+        kept = kept[idx]
+    np.save(os.path.join(out_dir, "kept.npy"), kept)
 
 
 def main():
@@ -468,7 +484,13 @@ def main():
     ap.add_argument("--also", default=None,
                     help="comma list of the configs measured after the top-level one, under \"configs\" "
                          "(default: 3,5,2m at N=1; 5,2 at N>1; 'none')")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the top-level workload's kept mask of the last timed step "
+                         "(rank 0's) as DIR/kept.npy (float32); the inputs are seeded, so two builds run with the "
+                         "same arguments can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -517,7 +539,10 @@ def main():
     # ---- the top-level workload
     wl = make_workload(cfg, 0 if split else rank, args.reads or None)
     res = Resident(wl, ctx, dev, world, rank, dist, args.p, split, coll)
-    block, dt, stats, kept_n = measure(res, args.steps, args.warmup, not args.no_profile)
+    block, dt, stats, kept_n, kept_last = measure(res, args.steps, args.warmup, not args.no_profile)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, kept_last)
+    del kept_last
     kept_ref = res.d_kept.clone()
     n, st = res.n, wl["st"]
     ms_step = block["ms_per_step"]
@@ -602,7 +627,7 @@ def main():
     for c in also:
         w2 = make_workload(c, rank)
         r2 = Resident(w2, ctx, dev, world, rank, dist, args.p, False, coll)
-        b2, _, _, _ = measure(r2, args.steps, args.warmup, not args.no_profile)
+        b2, _, _, _, _ = measure(r2, args.steps, args.warmup, not args.no_profile)
         if rank == 0 and world == 1 and not args.no_cpu_baseline:
             # (a prefix of buckets / a 40,000-UMI cut that the oracle finishes in about a second)
             b2["cpu_baseline"] = cpu_baseline(w2, 40_000 if w2["one_position"] else 5_000, args.p, all_cores=False)

@@ -19,10 +19,12 @@ def test_library_exports_every_declared_symbol():
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     declared = set(re.findall(r"\b(umi_[a-z_]+)\s*\(", hdr))
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
-    L = C.CDLL(_lib.LIB_PATH)
+    # (opened through the package's loader, never by a bare CDLL: the loader maps torch's HIP runtime
+    # before the library's own, and a process with both mapped sees no GPU -- the suite shares one)
+    L = umi.load()
     for name in declared:
         assert getattr(L, name) is not None
-    assert umi.load().umi_abi_version() == 2
+    assert L.umi_abi_version() == 2
 
 
 def test_encode_matches_oracle_and_kat(kat):
