@@ -39,6 +39,7 @@ extern "C" {
 
 #define UMI_MAX_UMI_LEN 21 /* one 64-bit word per key (3 bits per base) */
 #define UMI_MAX_WIDE_UMI_LEN 85 /* the _wide entry points: up to 4 words per key */
+#define UMI_MAX_SEQ_LEN 256     /* whole reads (umi_dedup_seqs): up to 12 words per key */
 
 typedef struct umi_ctx umi_ctx;   /* one per process/GPU; not re-entrant (the reference calls
                                      apply strictly sequentially, deduplicate_sam.rs:207) */
@@ -72,6 +73,7 @@ typedef struct umi_stats {
 #define UMI_KERNEL_NONE 0
 #define UMI_KERNEL_FUSED 1     /* small_bucket_kernel: one wave per position of <= 128 UMIs */
 #define UMI_KERNEL_SEG_PAIRS 2 /* seg_pair_kernel: all pairs inside the n-gram sub-buckets of deep positions */
+#define UMI_KERNEL_SEQ_PAIRS 3 /* seq_pair_kernel: the whole-read keys of umi_dedup_seqs */
 
 /* ---- context ----------------------------------------------------------- */
 int umi_ctx_create(int device_id, umi_ctx **out);
@@ -159,6 +161,29 @@ int umi_dedup_batch_wide_device(umi_ctx *ctx, const uint64_t *d_keys, const uint
                                 uint64_t n_buckets, int umi_len, int k, float percentage, int algo,
                                 int32_t adj_max_freq, uint8_t *d_kept, uint32_t *d_root,
                                 void *hip_stream, umi_stats *stats);
+
+/* ---- whole reads as keys (FASTQ mode: the reference's src/main.rs:49-50 is a TODO; this build defines
+ *      it, see host/umicollapse_main.cpp).  One bucket per read length, several lengths in one call.
+ *      keys / nmask: n_words words per entry, entry-major (nmask may be NULL); 1 <= n_words <= 12 and
+ *      n_words >= ceil(3 * bucket_len[b] / 64) for every bucket.  Bucket b uses the first
+ *      ceil(3 * bucket_len[b] / 64) words of its keys (bucket_len[b] in 0..UMI_MAX_SEQ_LEN), the words
+ *      behind them are zero.  Everything else -- rank order inside a bucket, kept / root, stats, any
+ *      k >= 0, UMI_ERR_* -- as in umi_dedup_batch_wide; the distance is the reference's per-word
+ *      arithmetic (src/utils/bitset.rs:77-91), straddling bases included.  Deep buckets are cut into
+ *      k + 1 parts of the whole read and only pairs that agree exactly on one part are evaluated
+ *      (n_pairs_evaluated counts them; kernel_id UMI_KERNEL_SEQ_PAIRS).  A multi-device context is
+ *      UMI_ERR_ARG.  umi_encode_seqs is to_bitset (src/utils/mod.rs:63-83) per read, read i being the
+ *      bytes [seq_off[i], seq_off[i + 1]) of ascii; host code, no GPU; UMI_ERR_CHAR outside ATCGN. */
+int umi_encode_seqs(const uint8_t *ascii, const uint64_t *seq_off, uint64_t n, int n_words, uint64_t *keys,
+                    uint64_t *nmask);
+int umi_dedup_seqs(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask, int n_words, const int32_t *freq,
+                   const uint64_t *bucket_off, const int32_t *bucket_len, uint64_t n_buckets, int k,
+                   float percentage, int algo, int32_t adj_max_freq, uint8_t *kept, uint32_t *root,
+                   umi_stats *stats);
+int umi_dedup_seqs_device(umi_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_nmask, int n_words,
+                          const int32_t *d_freq, const uint64_t *bucket_off, const int32_t *bucket_len,
+                          uint64_t n_buckets, int k, float percentage, int algo, int32_t adj_max_freq,
+                          uint8_t *d_kept, uint32_t *d_root, void *hip_stream, umi_stats *stats);
 
 /* ---- read staging on the device: the per-read part of
  *      DeduplicateSAM::deduplicate_and_merge, src/deduplicate_sam.rs:148-176

@@ -1,0 +1,103 @@
+"""Fastq mode's long-key path on shapes F1-F3: umi_dedup_seqs timed with device events (call and pair
+kernel), pairs evaluated against W = sum n(n-1)/2, and the umicollapse CLI end to end with its phase
+split.  One JSON line per shape and measurement on stdout.
+
+  F1: 1 M reads, 150 bp, ~300 k molecules, 0.5 % substitutions, k = 1
+  F2: F1 with the last 75 bases constant (one heavy bin: part 1 is shared by most of the bucket)
+  F3: 1 M reads, lengths 18-150, 1 % N
+
+usage: python tools/fastq_bench.py [--shapes F1,F2,F3] [--reps 5] [--out DIR]"""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from umi_collapse_rs_amd import Context, synth, to_bitset_seq  # noqa: E402
+
+CLI = os.path.join(ROOT, "umi_collapse_rs_amd", "bin", "umicollapse")
+SHAPES = {
+    "F1": dict(n_reads=1_000_000, n_molecules=300_000, length=150, err=0.005),
+    "F2": dict(n_reads=1_000_000, n_molecules=300_000, length=150, err=0.005, const_suffix=75),
+    "F3": dict(n_reads=1_000_000, n_molecules=300_000, lengths=list(range(18, 151)), err=0.005, n_frac=0.01),
+}
+
+
+def stage(seqs):
+    buckets = {}
+    for s in seqs:
+        d = buckets.setdefault(len(s), {})
+        d[s] = d.get(s, 0) + 1
+    ent, off, blen = [], [0], []
+    for L, d in buckets.items():
+        items = sorted(d.items(), key=lambda kv: -kv[1])
+        ent += items
+        off.append(len(ent))
+        blen.append(L)
+    return ent, off, blen
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="F1,F2,F3")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out", default=None, help="also keep the FASTQ files here (default: a temp dir)")
+    a = ap.parse_args()
+    out = a.out or os.path.join(ROOT, "build", "fastq_bench")
+    os.makedirs(out, exist_ok=True)
+    ctx = Context(0, profile=True)
+    for name in a.shapes.split(","):
+        t0 = time.time()
+        seqs, quals = synth.fastq_reads(hash(name) & 0xFFFF, **SHAPES[name])
+        ent, off, blen = stage(seqs)
+        w = max(1, max((3 * L + 63) // 64 for L in blen))
+        keys, nm = to_bitset_seq([e[0] for e in ent], w)
+        freq = np.array([e[1] for e in ent], np.int32)
+        nmask = nm if nm.any() else None
+        gen_s = time.time() - t0
+        runs = []
+        for r in range(a.reps + 1):
+            t = time.perf_counter()
+            kept, _, st = ctx.dedup_seqs(keys, nmask, freq, off, blen, k=1)
+            wall = (time.perf_counter() - t) * 1e3
+            if r:  # (the first call grows the workspace)
+                runs.append((wall, st))
+        st = runs[-1][1]
+        print(json.dumps({
+            "shape": name, "what": "umi_dedup_seqs", "reads": len(seqs), "entries": len(ent), "buckets": len(blen),
+            "max_bucket": int(st["max_bucket"]), "W": int(st["n_pairs"]), "pairs_evaluated": int(st["n_pairs_evaluated"]),
+            "candidates": int(st["n_candidates"]), "edges": int(st["n_edges"]), "kept": int(st["n_kept"]),
+            "ms_call_wall_median": float(np.median([x[0] for x in runs])),
+            "ms_total_median": float(np.median([x[1]["ms_total"] for x in runs])),
+            "ms_prep_median": float(np.median([x[1]["ms_prep"] for x in runs])),
+            "ms_kernel_median": float(np.median([x[1]["ms_kernel"] for x in runs])),
+            "ms_collapse_median": float(np.median([x[1]["ms_collapse"] for x in runs])),
+            "kernel_id": int(st["kernel_id"]), "gen_s": round(gen_s, 1)}), flush=True)
+        path = os.path.join(out, name + ".fq")
+        with open(path, "wb") as f:
+            f.write(synth.fastq_text(seqs, quals))
+        for r in range(3):
+            t = time.perf_counter()
+            p = subprocess.run([CLI, "-m", "fastq", "-i", path, "-o", os.path.join(out, name + ".out.fq"), "-k", "1"],
+                               capture_output=True, text=True, timeout=600)
+            wall = time.perf_counter() - t
+            if p.returncode != 0:
+                print(p.stderr, file=sys.stderr)
+                sys.exit(p.returncode)
+        m = re.search(r"phases: read\+parse ([0-9.]+) s, staging \(host\) ([0-9.]+) s, gpu init ([0-9.]+) s, "
+                      r"hot path \(H2D\+GPU\+D2H\) ([0-9.]+) s .*write ([0-9.]+) s", p.stderr)
+        print(json.dumps({"shape": name, "what": "cli", "wall_s": round(wall, 3),
+                          "read_parse_s": float(m.group(1)), "staging_s": float(m.group(2)),
+                          "gpu_init_s": float(m.group(3)), "gpu_call_s": float(m.group(4)),
+                          "write_s": float(m.group(5))}), flush=True)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -48,6 +48,23 @@ def to_bitset_wide(umis, umi_len):
     return keys, nm
 
 
+def to_bitset_seq(seqs, n_words=None):
+    """to_bitset (src/utils/mod.rs:63-83) per read for whole reads of up to 256 bases and of any
+    lengths: list of str/bytes -> (keys, nmask) uint64 [n, n_words], n_words = ceil(3 * longest / 64)
+    unless given; the words behind a read's own are zero (umi_encode_seqs)."""
+    bs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    off = np.zeros(len(bs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(b) for b in bs], dtype=np.uint64)
+    if n_words is None:
+        n_words = max(1, (3 * max([len(b) for b in bs] or [0]) + 63) // 64)
+    buf = np.frombuffer(b"".join(bs) or b"\0", dtype=np.uint8)
+    keys = np.zeros((len(bs), n_words), dtype=np.uint64)
+    nm = np.zeros((len(bs), n_words), dtype=np.uint64)
+    check(load().umi_encode_seqs(ptr(buf, C.c_uint8), ptr(off, C.c_uint64), len(bs), n_words,
+                                 ptr(keys, C.c_uint64), ptr(nm, C.c_uint64)))
+    return keys, nm
+
+
 def partition_buckets(bucket_off, n_ranks):
     """umi_partition_buckets: owner rank of every bucket (uint32[n_buckets]), the assignment the
     multi-device context uses -- for hosts that run one process per GPU."""
@@ -125,6 +142,34 @@ class Context:
                                           ptr(freq, C.c_int32), ptr(bucket_off, C.c_uint64), len(bucket_off) - 1,
                                           umi_len, k, percentage, algo, adj_max_freq, ptr(kept, C.c_uint8),
                                           ptr(root, C.c_uint32), C.byref(st)))
+        return kept[:n], (root[:n] if want_root else None), st.as_dict()
+
+    def dedup_seqs(self, keys, nmask, freq, bucket_off, bucket_len, k=1, percentage=0.5,
+                   algo=UMI_ALGO_DIRECTIONAL, adj_max_freq=0, want_root=True):
+        """Whole reads as keys (umi_dedup_seqs): keys / nmask uint64 [N, n_words], bucket b of
+        bucket_len[b] bases owns entries [bucket_off[b], bucket_off[b + 1]), several lengths in one call.
+        Returns (kept u8[N], root u32[N] or None, stats dict)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        if keys.ndim != 2:
+            raise ValueError("keys must be [N, n_words]")
+        n, w = keys.shape
+        nm = None if nmask is None else np.ascontiguousarray(nmask, dtype=np.uint64)
+        if nm is not None and nm.shape != keys.shape:
+            raise ValueError("nmask must have the shape of keys")
+        freq = np.ascontiguousarray(freq, dtype=np.int32)
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        bucket_len = np.ascontiguousarray(bucket_len, dtype=np.int32)
+        if len(freq) != n or len(bucket_len) != len(bucket_off) - 1:
+            raise ValueError("freq / bucket_len lengths differ from keys / bucket_off")
+        if len(bucket_off) < 1 or (len(bucket_off) > 1 and int(bucket_off[-1]) != n):
+            raise ValueError("bucket_off[-1] must equal len(keys)")
+        kept = np.zeros(max(1, n), dtype=np.uint8)
+        root = np.zeros(max(1, n), dtype=np.uint32) if want_root else None
+        st = Stats()
+        check(load().umi_dedup_seqs(self._h, ptr(keys, C.c_uint64), ptr(nm, C.c_uint64), w, ptr(freq, C.c_int32),
+                                    ptr(bucket_off, C.c_uint64), ptr(bucket_len, C.c_int32), len(bucket_off) - 1, k,
+                                    percentage, algo, adj_max_freq, ptr(kept, C.c_uint8), ptr(root, C.c_uint32),
+                                    C.byref(st)))
         return kept[:n], (root[:n] if want_root else None), st.as_dict()
 
     def stage_reads(self, align_key, umi_bytes, score, umi_len, merge=1, align_key_bits=64):

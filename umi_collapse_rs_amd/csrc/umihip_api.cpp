@@ -227,6 +227,8 @@ struct umi_ctx {
     DevBuf in_keys, in_nmask, in_freq, out_kept, out_root;
     // read staging (umi_stage_reads*): workspace; device copies of the host-buffer form
     DevBuf stage_ws, st_align, st_umi, st_score, st_keys, st_nmask, st_freq, st_rep, st_boff;
+    // whole-read keys (umi_dedup_seqs*): group table, records and their sort, runs, tile tasks
+    DevBuf seq_groups, seq_ka, seq_kb, seq_va, seq_vb, seq_flag, seq_runid, seq_rs, seq_tend, seq_tmp;
     uint64_t *h_boff = nullptr;               // pinned staging of the bucket table
     size_t h_boff_cap = 0;
     PinnedBuf h_tasks;                        // pinned staging of the bit-sliced tile-task lists
@@ -1810,7 +1812,9 @@ void umi_ctx_destroy(umi_ctx *ctx)
                       &ctx->boff,    &ctx->status,   &ctx->blocked,  &ctx->in_keys,
                       &ctx->in_nmask, &ctx->in_freq, &ctx->out_kept, &ctx->out_root,
                       &ctx->stage_ws, &ctx->st_align, &ctx->st_umi, &ctx->st_score, &ctx->st_keys, &ctx->st_nmask,
-                      &ctx->st_freq, &ctx->st_rep, &ctx->st_boff};
+                      &ctx->st_freq, &ctx->st_rep, &ctx->st_boff,
+                      &ctx->seq_groups, &ctx->seq_ka, &ctx->seq_kb, &ctx->seq_va, &ctx->seq_vb, &ctx->seq_flag,
+                      &ctx->seq_runid, &ctx->seq_rs, &ctx->seq_tend, &ctx->seq_tmp};
     for (DevBuf *b : bufs) b->release();
     if (ctx->h_boff) (void)hipHostFree(ctx->h_boff);
     ctx->h_tasks.release();
@@ -2449,6 +2453,301 @@ int umi_collapse_edges_device(umi_ctx *ctx, uint64_t n, const uint64_t *d_edges,
                         algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY, d_kept,
                         d_root, (hipStream_t)hip_stream)
         .run(stats);
+}
+
+} // extern "C"
+
+// ---- whole-read keys (FASTQ mode): umi_dedup_seqs* ----------------------------------------------
+namespace {
+
+constexpr uint32_t SEQ_PART_MIN = 512;      // buckets from this many entries up go through the partition ...
+constexpr uint32_t SEQ_MIN_PART_BASES = 8; // ... where their k + 1 parts are at least this many bases
+constexpr int SEQ_MAX_K = 400;             // a key of 12 words has at most 384 units of distance
+
+int seq_words(uint32_t len) { return (int)((3 * len + 63) / 64); } // bitset.rs:17-18
+
+int seq_check(umi_ctx *ctx, int n_words, const uint64_t *bucket_off, const int32_t *bucket_len, uint64_t n_buckets,
+              int k, int algo, uint64_t *n_out)
+{
+    if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
+    if (!ctx->subs.empty() && ctx->subs.size() > 1)
+        return fail(UMI_ERR_ARG, "umi_dedup_seqs takes a single-device context");
+    if (!bucket_off || (n_buckets && !bucket_len)) return fail(UMI_ERR_ARG, "bucket_off/bucket_len is NULL");
+    if (n_words < 1 || n_words > SEQ_MAX_WORDS) return fail(UMI_ERR_ARG, "n_words %d outside 1..%d", n_words, SEQ_MAX_WORDS);
+    if (k < 0) return fail(UMI_ERR_ARG, "k must be >= 0 (got %d)", k);
+    if (algo != UMI_ALGO_DIRECTIONAL && algo != UMI_ALGO_ADJACENCY) return fail(UMI_ERR_ARG, "unknown algo %d", algo);
+    if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
+    for (uint64_t b = 0; b < n_buckets; b++) {
+        if (bucket_off[b + 1] < bucket_off[b])
+            return fail(UMI_ERR_ARG, "bucket_off not monotone at bucket %llu", (unsigned long long)b);
+        if (bucket_len[b] < 0 || bucket_len[b] > UMI_MAX_SEQ_LEN)
+            return fail(UMI_ERR_ARG, "bucket_len[%llu] = %d outside 0..%d", (unsigned long long)b, bucket_len[b],
+                        UMI_MAX_SEQ_LEN);
+        if (seq_words((uint32_t)bucket_len[b]) > n_words)
+            return fail(UMI_ERR_ARG, "bucket_len[%llu] = %d needs %d words, n_words is %d", (unsigned long long)b,
+                        bucket_len[b], seq_words((uint32_t)bucket_len[b]), n_words);
+    }
+    const uint64_t n = n_buckets ? bucket_off[n_buckets] : 0;
+    if (n >= 0x7FFFFFF0ull) // bit 31 of an edge endpoint is a flag
+        return fail(UMI_ERR_ARG, "%llu entries exceed the 31-bit index space of one call", (unsigned long long)n);
+    *n_out = n;
+    return UMI_OK;
+}
+
+int seq_pipeline(umi_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_nmask, int n_words, const int32_t *d_freq,
+                 const uint64_t *bucket_off, const int32_t *bucket_len, uint64_t n_buckets, uint32_t n, int k,
+                 float percentage, int algo, int32_t adj_max_freq, uint8_t *d_kept, uint32_t *d_root, hipStream_t s,
+                 umi_stats *stats)
+{
+    settle(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc;
+    umi_stats st;
+    memset(&st, 0, sizeof(st));
+    st.n_umis = n;
+    st.n_buckets = n_buckets;
+    const int mode = algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY;
+    const int kk = std::min(k, SEQ_MAX_K);
+    // groups: k + 1 parts of a deep bucket with parts of SEQ_MIN_PART_BASES bases or more, else one
+    std::vector<SeqGroup> groups;
+    uint64_t n_rec = 0;
+    for (uint64_t b = 0; b < n_buckets; b++) {
+        const uint64_t nb = bucket_off[b + 1] - bucket_off[b];
+        st.max_bucket = std::max(st.max_bucket, nb);
+        st.n_pairs += nb * (nb - (nb > 0)) / 2;
+        if (nb < 2) continue;
+        const uint32_t len = (uint32_t)bucket_len[b], parts = (uint32_t)kk + 1;
+        const bool split = nb >= SEQ_PART_MIN && len / parts >= SEQ_MIN_PART_BASES;
+        for (uint32_t j = 0; j < (split ? parts : 1u); j++) {
+            SeqGroup g;
+            g.rec_off = (uint32_t)std::min<uint64_t>(n_rec, 0xFFFFFFFFull);
+            g.bstart = (uint32_t)bucket_off[b];
+            g.n = (uint32_t)nb;
+            g.len = len;
+            g.nw = (uint32_t)seq_words(len);
+            g.part = split ? j : SEQ_ALL_PAIRS;
+            g.n_parts = split ? parts : 1u;
+            g.pad = 0;
+            groups.push_back(g);
+            n_rec += nb;
+        }
+    }
+    if (n_rec >= (1ull << 30))
+        return fail(UMI_ERR_ARG, "%llu partition records exceed the 2^30 of one call", (unsigned long long)n_rec);
+    const uint32_t R = (uint32_t)n_rec, G = (uint32_t)groups.size();
+    unsigned long long *d_cnt;
+    if ((rc = ctx->counters.reserve(CTRL_BYTES)) || (rc = ctx->thr.reserve((size_t)n * 4))) return rc;
+    d_cnt = ctx->counters.as<unsigned long long>();
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, CNT_COUNT * sizeof(unsigned long long), s));
+    if (ctx->profile) HIP_TRY(hipEventRecord(ctx->ev[0], s));
+    const bool need_pairs = !(mode == MODE_ADJACENCY && adj_max_freq < 1); // reference adj: only the query goes
+    uint64_t n_edges = 0;
+    if (R && need_pairs) {
+        const size_t tmp = std::max(radix_sort_temp_bytes(R), scan_temp_bytes(R));
+        if ((rc = ctx->seq_groups.reserve(G * sizeof(SeqGroup))) || (rc = ctx->seq_ka.reserve((size_t)R * 8)) ||
+            (rc = ctx->seq_kb.reserve((size_t)R * 8)) || (rc = ctx->seq_va.reserve((size_t)R * 4)) ||
+            (rc = ctx->seq_vb.reserve((size_t)R * 4)) || (rc = ctx->seq_flag.reserve((size_t)R * 8)) ||
+            (rc = ctx->seq_runid.reserve((size_t)R * 8)) || (rc = ctx->seq_rs.reserve((size_t)(R + 1) * 4)) ||
+            (rc = ctx->seq_tend.reserve((size_t)R * 8)) || (rc = ctx->seq_tmp.reserve(tmp)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->seq_groups.p, groups.data(), G * sizeof(SeqGroup), hipMemcpyHostToDevice, s));
+        HIP_TRY(launch_seq_records(ctx->seq_groups.as<SeqGroup>(), G, R, d_keys, d_nmask, n_words, d_freq, percentage,
+                                   ctx->thr.as<int32_t>(), ctx->seq_ka.as<uint64_t>(), ctx->seq_va.as<uint32_t>(), d_cnt, s));
+        int gbits = 1;
+        while ((1u << gbits) < G) gbits++;
+        bool in_b = false;
+        HIP_TRY(radix_sort_pairs_u64(ctx->seq_ka.as<uint64_t>(), ctx->seq_kb.as<uint64_t>(), ctx->seq_va.as<uint32_t>(),
+                                     ctx->seq_vb.as<uint32_t>(), R, 0, 32 + gbits, ctx->seq_tmp.p, ctx->seq_tmp.cap, &in_b, s));
+        const uint64_t *rkey = in_b ? ctx->seq_kb.as<uint64_t>() : ctx->seq_ka.as<uint64_t>();
+        const uint32_t *rval = in_b ? ctx->seq_vb.as<uint32_t>() : ctx->seq_va.as<uint32_t>();
+        HIP_TRY(launch_seq_runs(rkey, R, ctx->seq_flag.as<uint64_t>(), ctx->seq_runid.as<uint64_t>(),
+                                ctx->seq_rs.as<uint32_t>(), ctx->seq_tend.as<uint64_t>(), ctx->seq_tmp.p, ctx->seq_tmp.cap,
+                                d_cnt, s));
+        if (ctx->profile) HIP_TRY(hipEventRecord(ctx->ev[1], s));
+        SeqPairArgs a;
+        a.groups = ctx->seq_groups.as<SeqGroup>();
+        a.rkey = rkey;
+        a.rval = rval;
+        a.n_rec = R;
+        a.run_id = ctx->seq_runid.as<uint64_t>();
+        a.run_start = ctx->seq_rs.as<uint32_t>();
+        a.task_end = ctx->seq_tend.as<uint64_t>();
+        a.keys = d_keys;
+        a.nmask = d_nmask;
+        a.stride = n_words;
+        a.freq = d_freq;
+        a.thr = ctx->thr.as<int32_t>();
+        a.counters = d_cnt;
+        a.k = kk;
+        a.mode = mode;
+        a.adj_max_freq = adj_max_freq;
+        const uint32_t blocks = (uint32_t)ctx->n_cus * 16; // persistent: every resident wave deals itself tiles
+        for (int attempt = 0;; attempt++) { // an edge list that overflowed is grown and the pair work redone
+            if ((rc = ctx->edges.reserve(std::max<uint64_t>(ctx->edge_capacity, 1) * sizeof(uint2)))) return rc;
+            a.edges = ctx->edges.as<uint2>();
+            a.edge_cap = (uint32_t)std::min<size_t>(ctx->edges.cap / sizeof(uint2), 0xFFFFFFF0u);
+            if (ctx->profile) HIP_TRY(hipEventRecord(ctx->ev[7], s));
+            HIP_TRY(launch_seq_pairs(a, blocks, s));
+            if (ctx->profile) HIP_TRY(hipEventRecord(ctx->ev[8], s));
+            st.n_pair_launches++;
+            HIP_TRY(hipMemcpyAsync(ctx->h_counters, d_cnt, CNT_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (ctx->h_counters[CNT_ERROR]) break;
+            n_edges = ctx->h_counters[CNT_EDGES];
+            if (n_edges <= a.edge_cap) break;
+            if (n_edges >= 0x7FFFFFF0ull || attempt > 4)
+                return fail(UMI_ERR_NOMEM, "%llu edges exceed the list of one call", (unsigned long long)n_edges);
+            ctx->edge_capacity = n_edges + n_edges / 4;
+            HIP_TRY(hipMemsetAsync(&d_cnt[CNT_EDGES], 0, 2 * sizeof(unsigned long long), s)); // edges, candidates
+        }
+        st.n_pairs_evaluated = ctx->h_counters[CNT_SEG_PAIRS];
+        st.n_candidates = ctx->h_counters[CNT_CANDIDATES];
+    } else if (R) { // adjacency with adj_max_freq < 1: the contract check and nothing else
+        if ((rc = ctx->seq_groups.reserve(G * sizeof(SeqGroup))) || (rc = ctx->seq_ka.reserve((size_t)R * 8)) ||
+            (rc = ctx->seq_va.reserve((size_t)R * 4)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->seq_groups.p, groups.data(), G * sizeof(SeqGroup), hipMemcpyHostToDevice, s));
+        HIP_TRY(launch_seq_records(ctx->seq_groups.as<SeqGroup>(), G, R, d_keys, d_nmask, n_words, d_freq, percentage,
+                                   ctx->thr.as<int32_t>(), ctx->seq_ka.as<uint64_t>(), ctx->seq_va.as<uint32_t>(), d_cnt, s));
+        HIP_TRY(hipMemcpyAsync(ctx->h_counters, d_cnt, CNT_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (R && ctx->h_counters[CNT_ERROR])
+        return fail(UMI_ERR_ORDER,
+                    "%llu entries break the input contract (freq < 1, not in freq-descending rank order inside a "
+                    "bucket, or an N base without nmask)",
+                    (unsigned long long)ctx->h_counters[CNT_ERROR]);
+    // a bucket of one entry, or whole buckets of entries ruled out above, need no record: every entry
+    // starts as its own root
+    umi_stats cst;
+    if ((rc = EdgeCollapse(ctx, n, ctx->edges.as<uint2>(), (uint32_t)n_edges, mode, d_kept, d_root, s).run(&cst)))
+        return rc;
+    if (ctx->profile) {
+        HIP_TRY(hipEventRecord(ctx->ev[4], s));
+        HIP_TRY(hipEventSynchronize(ctx->ev[4]));
+        if (R && need_pairs) {
+            HIP_TRY(hipEventElapsedTime(&st.ms_prep, ctx->ev[0], ctx->ev[1]));
+            HIP_TRY(hipEventElapsedTime(&st.ms_pairs, ctx->ev[7], ctx->ev[8]));
+            HIP_TRY(hipEventElapsedTime(&st.ms_collapse, ctx->ev[8], ctx->ev[4]));
+            st.ms_kernel = st.ms_pairs;
+            st.kernel_id = UMI_KERNEL_SEQ_PAIRS;
+        }
+        HIP_TRY(hipEventElapsedTime(&st.ms_total, ctx->ev[0], ctx->ev[4]));
+    } else if (R && need_pairs) {
+        st.kernel_id = UMI_KERNEL_SEQ_PAIRS;
+    }
+    st.n_edges = n_edges;
+    st.n_rounds = cst.n_rounds;
+    st.n_kept = cst.n_kept;
+    if (stats) *stats = st;
+    return UMI_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int umi_encode_seqs(const uint8_t *ascii, const uint64_t *seq_off, uint64_t n, int n_words, uint64_t *keys,
+                    uint64_t *nmask)
+{ // src/utils/mod.rs:63-83 per read: base i at bits 3i .. 3i+2 of the word string, the words behind it zero
+    if (n && (!ascii || !seq_off || !keys)) return fail(UMI_ERR_ARG, "ascii/seq_off/keys is NULL");
+    if (n_words < 1 || n_words > SEQ_MAX_WORDS) return fail(UMI_ERR_ARG, "n_words %d outside 1..%d", n_words, SEQ_MAX_WORDS);
+    for (uint64_t i = 0; i < n; i++) {
+        if (seq_off[i + 1] < seq_off[i]) return fail(UMI_ERR_ARG, "seq_off not monotone at read %llu", (unsigned long long)i);
+        const uint64_t len = seq_off[i + 1] - seq_off[i];
+        if (len > UMI_MAX_SEQ_LEN)
+            return fail(UMI_ERR_ARG, "read %llu has %llu bases, more than %d", (unsigned long long)i,
+                        (unsigned long long)len, UMI_MAX_SEQ_LEN);
+        if (seq_words((uint32_t)len) > n_words)
+            return fail(UMI_ERR_ARG, "read %llu of %llu bases needs %d words, n_words is %d", (unsigned long long)i,
+                        (unsigned long long)len, seq_words((uint32_t)len), n_words);
+        uint64_t *kw = keys + i * (uint64_t)n_words, *m = nmask ? nmask + i * (uint64_t)n_words : nullptr;
+        for (int w = 0; w < n_words; w++) {
+            kw[w] = 0;
+            if (m) m[w] = 0;
+        }
+        const uint8_t *p = ascii + seq_off[i];
+        for (uint64_t b = 0; b < len; b++) {
+            uint64_t c;
+            switch (p[b]) { // read.rs:23-31
+            case 'A': c = 0; break;
+            case 'T': c = 5; break;
+            case 'C': c = 6; break;
+            case 'G': c = 3; break;
+            case 'N': c = 4; break;
+            default: return fail(UMI_ERR_CHAR, "Unknown character in sequence: %u (read %llu)", (unsigned)p[b],
+                                 (unsigned long long)i);
+            }
+            for (int j = 0; j < 3; j++) { // bit by bit: a base may straddle two words (bitset.rs:52-61)
+                const uint64_t bit = 3 * b + j;
+                if ((c >> j) & 1) kw[bit >> 6] |= 1ull << (bit & 63);
+                if (c == 4 && m) m[bit >> 6] |= 1ull << (bit & 63); // set_n_bit, bitset.rs:63-75
+            }
+        }
+    }
+    return UMI_OK;
+}
+
+int umi_dedup_seqs_device(umi_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_nmask, int n_words,
+                          const int32_t *d_freq, const uint64_t *bucket_off, const int32_t *bucket_len,
+                          uint64_t n_buckets, int k, float percentage, int algo, int32_t adj_max_freq, uint8_t *d_kept,
+                          uint32_t *d_root, void *hip_stream, umi_stats *stats)
+{
+    uint64_t n = 0;
+    int rc = seq_check(ctx, n_words, bucket_off, bucket_len, n_buckets, k, algo, &n);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    if (n && (!d_keys || !d_freq || !d_kept)) return fail(UMI_ERR_ARG, "keys/freq/kept is NULL");
+    if (n == 0) {
+        if (stats) {
+            memset(stats, 0, sizeof(*stats));
+            stats->n_buckets = n_buckets;
+        }
+        return UMI_OK;
+    }
+    return seq_pipeline(ctx, d_keys, d_nmask, n_words, d_freq, bucket_off, bucket_len, n_buckets, (uint32_t)n, k,
+                        percentage, algo, adj_max_freq, d_kept, d_root, (hipStream_t)hip_stream, stats);
+}
+
+int umi_dedup_seqs(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask, int n_words, const int32_t *freq,
+                   const uint64_t *bucket_off, const int32_t *bucket_len, uint64_t n_buckets, int k, float percentage,
+                   int algo, int32_t adj_max_freq, uint8_t *kept, uint32_t *root, umi_stats *stats)
+{
+    uint64_t n = 0;
+    int rc = seq_check(ctx, n_words, bucket_off, bucket_len, n_buckets, k, algo, &n);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    if (n && (!keys || !freq || !kept)) return fail(UMI_ERR_ARG, "keys/freq/kept is NULL");
+    if (n == 0) {
+        if (stats) {
+            memset(stats, 0, sizeof(*stats));
+            stats->n_buckets = n_buckets;
+        }
+        return UMI_OK;
+    }
+    settle(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t kb = (size_t)n * 8 * (size_t)n_words;
+    if ((rc = ctx->in_keys.reserve(kb)) || (rc = ctx->in_freq.reserve(n * 4)) || (rc = ctx->out_kept.reserve(n)) ||
+        (rc = ctx->out_root.reserve(n * 4)))
+        return rc;
+    if (nmask && (rc = ctx->in_nmask.reserve(kb))) return rc;
+    hipStream_t s = ctx->own_stream;
+    HIP_TRY(hipMemcpyAsync(ctx->in_keys.p, keys, kb, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ctx->in_freq.p, freq, n * 4, hipMemcpyHostToDevice, s));
+    if (nmask) HIP_TRY(hipMemcpyAsync(ctx->in_nmask.p, nmask, kb, hipMemcpyHostToDevice, s));
+    rc = seq_pipeline(ctx, ctx->in_keys.as<uint64_t>(), nmask ? ctx->in_nmask.as<uint64_t>() : nullptr, n_words,
+                      ctx->in_freq.as<int32_t>(), bucket_off, bucket_len, n_buckets, (uint32_t)n, k, percentage, algo,
+                      adj_max_freq, ctx->out_kept.as<uint8_t>(), root ? ctx->out_root.as<uint32_t>() : nullptr, s,
+                      stats);
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(kept, ctx->out_kept.p, n, hipMemcpyDeviceToHost, s));
+    if (root) HIP_TRY(hipMemcpyAsync(root, ctx->out_root.p, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return UMI_OK;
 }
 
 } // extern "C"

@@ -276,6 +276,44 @@ hipError_t launch_seg_edge_append(const PairArgs &a, const SegArgs &g, uint32_t 
 // a.tasks: rows [row0, row0 + 64) x columns [col0, col1) of one bucket; exact distance from all words
 hipError_t launch_wide_pairs(const PairArgs &a, uint32_t n_tasks, int n_words, hipStream_t s);
 
+// ---- whole-read keys (umihip_seq.hip): reads of up to 256 bases, 1..12 words per key, stride words apart
+constexpr int SEQ_MAX_WORDS = 12;
+constexpr uint32_t SEQ_TILE = 64;           // rows / columns of a pair task
+constexpr uint32_t SEQ_ALL_PAIRS = 0xFFFFFFFFu; // SeqGroup::part of a bucket evaluated without the partition
+// one part of one bucket: its records are [rec_off, rec_off + n), entry bstart + (r - rec_off)
+struct SeqGroup {
+    uint32_t rec_off, bstart, n;
+    uint32_t len, nw;     // read length (bases) and words of the bucket's keys
+    uint32_t part, n_parts; // part j of k + 1 (bases [j len / P, (j + 1) len / P)), or SEQ_ALL_PAIRS
+    uint32_t pad;
+};
+struct SeqPairArgs {
+    const SeqGroup *groups;
+    const uint64_t *rkey;   // sorted records: group << 32 | hash of the part
+    const uint32_t *rval;   // ... their entries
+    uint32_t n_rec;
+    const uint64_t *run_id; // inclusive scan of the run starts (run_id[n_rec - 1] = runs)
+    const uint32_t *run_start; // [runs + 1]
+    const uint64_t *task_end;  // inclusive scan of the tiles per run
+    const uint64_t *keys, *nmask; // nmask may be null
+    int stride;
+    const int32_t *freq, *thr;
+    uint2 *edges;
+    unsigned long long *counters;
+    uint32_t edge_cap;
+    int k, mode;
+    int32_t adj_max_freq;
+};
+hipError_t launch_seq_records(const SeqGroup *groups, uint32_t n_groups, uint32_t n_rec, const uint64_t *keys,
+                              const uint64_t *nmask, int stride, const int32_t *freq, float percentage, int32_t *thr,
+                              uint64_t *rkey, uint32_t *rval, unsigned long long *counters, hipStream_t s);
+// runs of equal sorted records -> run_start, task_end; flag is scratch of n_rec words;
+// counters[CNT_SEG_PAIRS] += the pairs inside the runs
+hipError_t launch_seq_runs(const uint64_t *rkey, uint32_t n_rec, uint64_t *flag, uint64_t *run_id,
+                           uint32_t *run_start, uint64_t *task_end, void *scan_temp, size_t scan_temp_size,
+                           unsigned long long *counters, hipStream_t s);
+hipError_t launch_seq_pairs(const SeqPairArgs &a, uint32_t n_blocks, hipStream_t s);
+
 // ---- read staging on the device (umihip_stage.hip) ----
 size_t stage_workspace_bytes(uint32_t n_reads, int n_words);
 // reads (alignment key, UMI text, score) -> entries in canonical order + bucket table, all device

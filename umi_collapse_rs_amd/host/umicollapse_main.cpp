@@ -13,7 +13,24 @@
 // read is written, in file order, with MI:i = cluster id (offset + index of the cluster's root
 // among the survivors), cs:i = reads in the cluster, su:i = reads with the same UMI at the same
 // position.  Nothing in the reference to be in parity with: tests/bamio.py defines it.
-// Not implemented, as in the reference: --mode fastq (main.rs:49-50), --two-pass, --algo cc.
+// --mode fastq: a TODO in the reference (main.rs:49-50), defined by this build after UMICollapse's
+// fastq mode (run_fastq).  Input: one FASTQ file, plain or gzip (detected by its magic bytes; several
+// members, BGZF included), records of four lines (@header, sequence, +line, quality).  The whole
+// sequence (<= 256 bases, ATCGN) is the key, to_bitset'd into ceil(3L/64) words; distance is the
+// reference's per-word bit_count_xor.  One bucket per read length (first appearance), one entry per
+// distinct sequence (freq = reads; rep = the first read with --merge any, the highest average quality
+// -- (int)(sum(q - 33) as f32 / len as f32) -- first on ties, with avgqual, the default; mapqual is
+// refused), entries in rank order (freq descending, first appearance), dir / adj per bucket as for
+// BAM.  Output: the rep reads of the survivors in file order, header and + lines byte for byte,
+// -u N trimming N bases and quality characters (a read shorter than N is an error); gzip (BGZF at
+// --compress-level) when -o ends in .gz.  --tag writes every read with " cluster_id=<i>" (index of
+// its cluster's root among the survivors in output order), " cluster_size=<reads>" on the root's
+// rep read and " same_umi=<freq>" on every sequence's rep read.  A truncated record, a missing @ or
+// +, sequence and quality of different lengths, a base outside ATCGN ("Unknown character"), a read
+// over 256 bases end the run with status 101.  Refused with it: --paired, --remove-unpaired,
+// --remove-chimeric, --keep-unmapped, --two-pass, --stage gpu, several --devices; --umi_sep and
+// --data are accepted and ignored.
+// Not implemented, as in the reference: --two-pass, --algo cc.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -30,6 +47,7 @@
 #include "../../include/umihip.h"
 #include "bam.hpp"
 #include "bgzf.hpp"
+#include "fastq.hpp"
 
 namespace {
 
@@ -75,6 +93,8 @@ struct HipLib {
                        uint64_t *, uint64_t *, int32_t *, uint64_t *, uint64_t *, uint64_t *, uint64_t *) = nullptr;
     int (*dedup_batch)(umi_ctx *, const uint64_t *, const uint64_t *, int, const int32_t *, const uint64_t *, uint64_t,
                        int, int, float, int, int32_t, uint8_t *, uint32_t *, umi_stats *) = nullptr;
+    int (*dedup_seqs)(umi_ctx *, const uint64_t *, const uint64_t *, int, const int32_t *, const uint64_t *,
+                      const int32_t *, uint64_t, int, float, int, int32_t, uint8_t *, uint32_t *, umi_stats *) = nullptr;
     std::string error;
     bool load()
     {
@@ -99,6 +119,7 @@ struct HipLib {
         last_error = (decltype(last_error))sym("umi_last_error");
         stage_reads = (decltype(stage_reads))sym("umi_stage_reads_wide");
         dedup_batch = (decltype(dedup_batch))sym("umi_dedup_batch_wide");
+        dedup_seqs = (decltype(dedup_seqs))sym("umi_dedup_seqs");
         return error.empty();
     }
 };
@@ -149,14 +170,16 @@ bool encode_umi(const uint8_t *u, size_t len, UmiKey *key, UmiKey *nmask)
 void usage()
 {
     std::puts("Usage: umicollapse [OPTIONS] -i <INPUT_FILE> -o <OUITPUT_FILE>\n"
-              "  -m, --mode <MODE>        Either fastq or SAM/BAM mode [default: bam]\n"
+              "  -m, --mode <MODE>        Either fastq or SAM/BAM mode [default: bam]; fastq: whole reads\n"
+              "                           (<= 256 bases) are the key, one bucket per read length\n"
               "  -k <K>                   Number of substitution edits to allow [default: 1]\n"
-              "  -u <UMI_LENGTH>          The UMI length [default: 0 = autodetect]\n"
+              "  -u <UMI_LENGTH>          The UMI length [default: 0 = autodetect]; fastq: bases trimmed\n"
+              "                           from the start of every written read\n"
               "  -p <PERCENTAGE>          Directional threshold percentage [default: 0.5]\n"
               "      --num-threads <N>    Threads used in reader/writer [default: 1]\n"
               "      --umi_sep <BYTE>     Separator byte value between UMI and read name [default: 95]\n"
               "      --algo <ALGO>        adj or dir [default: dir]\n"
-              "      --merge <MERGE>      any, avgqual or mapqual [default: mapqual in bam mode]\n"
+              "      --merge <MERGE>      any, avgqual or mapqual [default: mapqual in bam mode, avgqual in fastq mode]\n"
               "      --data <DATA>        accepted; every value gives Naive's result (as in the reference)\n"
               "      --keep-unmapped      Keep unmapped reads\n"
               "      --paired             Paired-end mode: template length joins the alignment key,\n"
@@ -287,6 +310,232 @@ double now_s()
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// ---- FASTQ mode (-m fastq).  The reference leaves it a TODO (src/main.rs:49-50); this build defines it
+// after UMICollapse's fastq mode: the whole read sequence is the key.  One bucket per read length
+// (first appearance), one entry per distinct sequence (freq, rep: the first read with --merge any, the
+// highest average quality -- first on ties -- with avgqual), rank order inside, ONE umi_dedup_seqs call,
+// survivors' rep reads written in file order (-u N trims N bases and quality characters from each).
+int run_fastq(const Cli &args, int algo, int merge, HipLib &lib)
+{
+    const double t_start = now_s();
+    if (args.paired || args.remove_unpaired || args.remove_chimeric || args.keep_unmapped || args.two_pass)
+        die("--paired, --remove-unpaired, --remove-chimeric, --keep-unmapped and --two-pass do not go with fastq mode");
+    if (args.stage == "gpu") die("--stage gpu does not go with fastq mode (its reads are staged on the host)");
+    if (args.devices.size() > 1) die("fastq mode runs on one GPU: --devices takes one id here");
+    if (merge == 2) die("Invalid algorithm combination: " + args.algo + " , " + args.merge + " and " + args.data);
+    umi::bgzf::Bytes text = umi::fastq::read_all(args.input, args.num_threads);
+    std::vector<umi::fastq::Record> recs;
+    const std::string perr = umi::fastq::parse(text.data(), text.size(), recs);
+    if (!perr.empty()) die(perr);
+    const double t_read = now_s();
+    const uint8_t *d = text.data();
+    const size_t n_reads = recs.size();
+    // staging: per read length a map sequence -> entry, entries in first appearance
+    struct Entry {
+        uint32_t freq, rep;
+        int32_t score;
+    };
+    struct Bucket {
+        uint32_t len;
+        std::vector<Entry> entries;
+        std::unordered_map<std::string, uint32_t> index;
+    };
+    std::vector<Bucket> buckets;
+    std::vector<int32_t> bucket_of_len(UMI_MAX_SEQ_LEN + 1, -1);
+    for (size_t i = 0; i < n_reads; i++) {
+        const umi::fastq::Record &r = recs[i];
+        if (r.len > UMI_MAX_SEQ_LEN)
+            die("FASTQ record " + std::to_string(i + 1) + ": " + std::to_string(r.len) + " bases, more than " +
+                std::to_string(UMI_MAX_SEQ_LEN));
+        if (r.len < args.umi_length)
+            die("FASTQ record " + std::to_string(i + 1) + ": " + std::to_string(r.len) + " bases, shorter than -u " +
+                std::to_string(args.umi_length));
+        for (size_t b = 0; b < r.len; b++) {
+            const uint8_t c = d[r.seq + b];
+            if (c != 'A' && c != 'T' && c != 'C' && c != 'G' && c != 'N')
+                die("Unknown character in sequence: " + std::to_string((unsigned)c) + " (FASTQ record " +
+                    std::to_string(i + 1) + ")"); // utils/mod.rs:77-79
+        }
+        int32_t &bi = bucket_of_len[r.len];
+        if (bi < 0) {
+            bi = (int32_t)buckets.size();
+            buckets.push_back(Bucket{(uint32_t)r.len, {}, {}});
+        }
+        Bucket &bk = buckets[bi];
+        const int32_t score = merge == 1 ? umi::fastq::avg_qual(d + r.qual, r.len) : 0;
+        auto it = bk.index.emplace(std::string((const char *)d + r.seq, r.len), (uint32_t)bk.entries.size());
+        if (it.second) {
+            bk.entries.push_back(Entry{1, (uint32_t)i, score});
+        } else {
+            Entry &e = bk.entries[it.first->second];
+            e.freq++;
+            if (merge == 1 && !(e.score >= score)) { // merge/mod.rs:35: the kept read stays on ties
+                e.rep = (uint32_t)i;
+                e.score = score;
+            }
+        }
+    }
+    // entries in canonical order: bucket by bucket, freq descending, first appearance on ties
+    size_t n = 0;
+    int n_words = 1;
+    for (const Bucket &bk : buckets) {
+        n += bk.entries.size();
+        n_words = std::max(n_words, (int)((3 * bk.len + 63) / 64));
+    }
+    const size_t nb = buckets.size();
+    std::vector<uint64_t> keys(n * n_words + 1, 0), nmask(n * n_words + 1, 0), off(nb + 1, 0);
+    std::vector<int32_t> freq(n + 1), blen(nb + 1);
+    std::vector<uint32_t> rep(n + 1);
+    bool any_n = false;
+    {
+        size_t e = 0;
+        for (size_t b = 0; b < nb; b++) {
+            Bucket &bk = buckets[b];
+            std::vector<uint32_t> order(bk.entries.size());
+            for (uint32_t j = 0; j < order.size(); j++) order[j] = j;
+            std::stable_sort(order.begin(), order.end(),
+                             [&](uint32_t x, uint32_t y) { return bk.entries[x].freq > bk.entries[y].freq; });
+            off[b] = e;
+            blen[b] = (int32_t)bk.len;
+            for (uint32_t j : order) {
+                const Entry &en = bk.entries[j];
+                const umi::fastq::Record &r = recs[en.rep];
+                freq[e] = (int32_t)en.freq;
+                rep[e] = en.rep;
+                uint64_t *kw = &keys[e * n_words], *mw = &nmask[e * n_words];
+                for (size_t p = 0; p < r.len; p++) { // to_bitset, utils/mod.rs:63-83; read.rs:23-31
+                    uint64_t c = 0;
+                    switch (d[r.seq + p]) {
+                    case 'T': c = 5; break;
+                    case 'C': c = 6; break;
+                    case 'G': c = 3; break;
+                    case 'N': c = 4; any_n = true; break;
+                    default: break;
+                    }
+                    for (int q = 0; q < 3; q++) { // a base may straddle two words (bitset.rs:52-75)
+                        const size_t bit = 3 * p + q;
+                        if ((c >> q) & 1) kw[bit >> 6] |= 1ull << (bit & 63);
+                        if (c == 4) mw[bit >> 6] |= 1ull << (bit & 63);
+                    }
+                }
+                e++;
+            }
+            bk.index.clear();
+        }
+        off[nb] = e;
+    }
+    const double t_stage = now_s();
+    std::fprintf(stderr, "UMI collapsing reading finished in %.3f seconds\n", t_stage - t_start);
+    if (!args.dump_staging.empty()) { // test hook: staged hot-path input, no GPU touched
+        FILE *f = std::fopen(args.dump_staging.c_str(), "wb");
+        if (!f) die("cannot open " + args.dump_staging);
+        const uint64_t hdr[4] = {n, nb, 0, (uint64_t)n_words};
+        std::fwrite(hdr, 8, 4, f);
+        std::fwrite(keys.data(), 8, n * n_words, f);
+        std::fwrite(nmask.data(), 8, n * n_words, f);
+        std::fwrite(freq.data(), 4, n, f);
+        std::fwrite(rep.data(), 4, n, f);
+        std::fwrite(off.data(), 8, nb + 1, f);
+        std::fwrite(blen.data(), 4, nb, f);
+        std::fclose(f);
+        return 0;
+    }
+    std::vector<uint8_t> kept(n + 1, 0);
+    std::vector<uint32_t> root(n + 1, 0);
+    umi_stats st;
+    std::memset(&st, 0, sizeof(st));
+    double t_gpu0 = now_s(), t_gpu1 = t_gpu0;
+    if (n) {
+        if (!lib.load()) die(lib.error);
+        if (!lib.dedup_seqs) die("libumihip.so lacks umi_dedup_seqs");
+        umi_ctx *ctx = nullptr;
+        if (lib.ctx_create_multi(args.devices.data(), 1, &ctx) != UMI_OK) die(lib.last_error());
+        t_gpu0 = now_s();
+        if (lib.dedup_seqs(ctx, keys.data(), any_n ? nmask.data() : nullptr, n_words, freq.data(), off.data(),
+                           blen.data(), nb, args.k, args.percentage, algo, 0 /* adjacency.rs:56 */, kept.data(),
+                           root.data(), &st) != UMI_OK)
+            die(lib.last_error());
+        t_gpu1 = now_s();
+    }
+    // survivors in output order: their rep reads in file order
+    std::vector<uint32_t> entry_of_rep(n_reads, UINT32_MAX);
+    for (size_t e = 0; e < n; e++) entry_of_rep[rep[e]] = (uint32_t)e;
+    const size_t trim = args.umi_length;
+    std::string out;
+    out.reserve(text.size() + (args.track_clusters ? n_reads * 48 : 0));
+    auto put = [&](size_t p, size_t len) { out.append((const char *)d + p, len); };
+    auto put_record = [&](const umi::fastq::Record &r, const std::string &extra) {
+        put(r.head, r.head_len);
+        out += extra;
+        out += '\n';
+        put(r.seq + trim, r.len - trim);
+        out += '\n';
+        put(r.plus, r.plus_len);
+        out += '\n';
+        put(r.qual + trim, r.len - trim);
+        out += '\n';
+    };
+    size_t n_out = 0;
+    if (!args.track_clusters) {
+        for (size_t i = 0; i < n_reads; i++) {
+            const uint32_t e = entry_of_rep[i];
+            if (e == UINT32_MAX || !kept[e]) continue;
+            put_record(recs[i], "");
+            n_out++;
+        }
+    } else {
+        // --tag: cluster_id = index of the cluster's root among the survivors in output order,
+        // cluster_size = reads of the cluster (on the root's rep read), same_umi = reads of the sequence
+        // (on every sequence's rep read)
+        std::vector<uint32_t> cluster_id(n + 1, 0), cluster_reads(n + 1, 0);
+        for (size_t i = 0; i < n_reads; i++) {
+            const uint32_t e = entry_of_rep[i];
+            if (e != UINT32_MAX && kept[e]) cluster_id[e] = (uint32_t)n_out++;
+        }
+        for (size_t e = 0; e < n; e++) cluster_reads[root[e]] += (uint32_t)freq[e];
+        // entry of every read: its sequence's, looked up again per bucket
+        std::vector<std::unordered_map<std::string, uint32_t>> index(nb);
+        for (size_t b = 0; b < nb; b++)
+            for (uint64_t e = off[b]; e < off[b + 1]; e++)
+                index[b].emplace(std::string((const char *)d + recs[rep[e]].seq, recs[rep[e]].len), (uint32_t)e);
+        for (size_t i = 0; i < n_reads; i++) {
+            const umi::fastq::Record &r = recs[i];
+            const uint32_t e = index[bucket_of_len[r.len]].at(std::string((const char *)d + r.seq, r.len));
+            const uint32_t rt = root[e];
+            std::string extra = " cluster_id=" + std::to_string(cluster_id[rt]);
+            if (rep[rt] == i) extra += " cluster_size=" + std::to_string(cluster_reads[rt]);
+            if (rep[e] == i) extra += " same_umi=" + std::to_string(freq[e]);
+            put_record(r, extra);
+        }
+    }
+    const std::string &o = args.output;
+    if (o.size() >= 3 && o.compare(o.size() - 3, 3, ".gz") == 0) {
+        umi::bgzf::compress_to_file(o, (const uint8_t *)out.data(), out.size(), args.num_threads, args.compress_level);
+    } else {
+        FILE *f = std::fopen(o.c_str(), "wb");
+        if (!f) die("cannot open " + o);
+        if (!out.empty() && std::fwrite(out.data(), 1, out.size(), f) != out.size()) die("cannot write " + o);
+        if (std::fclose(f) != 0) die("cannot write " + o);
+    }
+    const double t_end = now_s();
+    size_t max_bucket = 0;
+    for (size_t b = 0; b < nb; b++) max_bucket = std::max<size_t>(max_bucket, off[b + 1] - off[b]);
+    std::fprintf(stderr, "Number of input reads: %zu\n", n_reads);
+    std::fprintf(stderr, "Number of read lengths: %zu\n", nb);
+    std::fprintf(stderr, "Number of distinct sequences: %zu\n", n);
+    std::fprintf(stderr, "Max number of distinct sequences of one length: %zu\n", max_bucket);
+    std::fprintf(stderr, args.track_clusters ? "Number of groups of reads: %llu\n" : "Number of reads after deduplicating: %llu\n",
+                 (unsigned long long)st.n_kept);
+    std::fprintf(stderr,
+                 "phases: read+parse %.3f s, staging (host) %.3f s, gpu init %.3f s, hot path (H2D+GPU+D2H) %.3f s "
+                 "[%llu pairs, %llu evaluated], write %.3f s\n",
+                 t_read - t_start, t_stage - t_read, t_gpu0 - t_stage, t_gpu1 - t_gpu0, (unsigned long long)st.n_pairs,
+                 (unsigned long long)st.n_pairs_evaluated, t_end - t_gpu1);
+    std::fprintf(stderr, "UMI collapsing finished in %.3f seconds\n", t_end - t_start); // main.rs:97-102
+    std::fflush(stderr);
+    std::_Exit(0); // (no static destructors: as the BAM path, the process ends without tearing HIP down)
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -297,8 +546,7 @@ int main(int argc, char **argv)
     if (args.merge.empty()) args.merge = args.mode == "fastq" ? "avgqual" : "mapqual"; // main.rs:33-39
     if (args.track_clusters && args.two_pass) die("Cannot track clusters with the two pass algorithm!");
     if (args.paired && args.keep_unmapped) die("Cannot keep unmapped reads with paired-end reads!");
-    if (args.mode == "fastq") die("fastq mode is not implemented (nor in the reference: main.rs:49-50)");
-    if (args.mode != "bam" && args.mode != "sam") return 0; // main.rs:49-95: nothing happens
+    if (args.mode != "bam" && args.mode != "sam" && args.mode != "fastq") return 0; // main.rs:49-95: nothing happens
     if (args.track_clusters && args.paired) die("--tag with --paired is not implemented (the reference never reaches its tagging pass)");
     int algo, merge;
     if (args.algo == "dir") algo = UMI_ALGO_DIRECTIONAL;
@@ -308,6 +556,14 @@ int main(int argc, char **argv)
     else if (args.merge == "avgqual") merge = 1;
     else if (args.merge == "mapqual") merge = 2;
     else die("Invalid algorithm combination: " + args.algo + " , " + args.merge + " and " + args.data);
+    if (args.mode == "fastq") { // (this build's definition, see run_fastq)
+        HipLib fq_lib;
+        try {
+            return run_fastq(args, algo, merge, fq_lib);
+        } catch (const std::exception &e) {
+            die(e.what());
+        }
+    }
 
     // The GPU is woken while the file is read: context creation and the first launch of the
     // library's kernels (their code objects are loaded then) take ~0.1 s of a process that lives

@@ -177,3 +177,55 @@ def config2m(seed=22, n_reads=1_000_000, umi_len=12, n_molecules=100_000, err=0.
     st["n_reads"] = n_reads
     st["n_molecules"] = int(mol_of.max()) + 1
     return st
+
+
+def fastq_reads(seed, n_reads, n_molecules, length=150, err=0.005, n_frac=0.0, const_prefix=0, const_suffix=0,
+                lengths=None, mean_copies=None):
+    """Seeded FASTQ workload of whole-read keys (fastq mode): n_molecules random molecules, each of one
+    length (length, or drawn from the list `lengths`), read a Poisson number of times (mean n_reads /
+    n_molecules, at least once; reads stop at n_reads), every base substituted with probability err and
+    made N with probability n_frac; const_prefix / const_suffix bases of every molecule are one fixed
+    string (a linker, an amplicon's constant half).  Returns (seqs, quals): lists of ASCII bytes, in
+    file order (the copies of all molecules shuffled)."""
+    rng = np.random.default_rng(seed)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    maxlen = max(lengths) if lengths is not None else length
+    fixed = rng.choice(acgt, maxlen)
+    lam = mean_copies if mean_copies is not None else n_reads / max(1, n_molecules)
+    copies = np.maximum(1, rng.poisson(lam, n_molecules))
+    mol_len = (rng.choice(np.asarray(lengths), n_molecules) if lengths is not None
+               else np.full(n_molecules, length))
+    which = np.repeat(np.arange(n_molecules), copies)[:n_reads]
+    rng.shuffle(which)
+    seqs, quals = [], []
+    mols = {}
+    for m in which:
+        L = int(mol_len[m])
+        mol = mols.get(m)
+        if mol is None:
+            mol = rng.choice(acgt, L)
+            p = min(const_prefix, L)
+            mol[:p] = fixed[:p]
+            s = min(const_suffix, L)
+            if s:
+                mol[L - s:] = fixed[maxlen - s:maxlen][:s] if L >= s else mol[L - s:]
+            mols[m] = mol
+        r = mol.copy()
+        if err:
+            hit = np.nonzero(rng.random(L) < err)[0]
+            for i in hit:
+                r[i] = rng.choice(acgt[acgt != r[i]])
+        if n_frac:
+            r[rng.random(L) < n_frac] = ord("N")
+        seqs.append(r.tobytes())
+        quals.append((rng.integers(2, 41, L) + 33).astype(np.uint8).tobytes())
+    return seqs, quals
+
+
+def fastq_text(seqs, quals, names=None):
+    """The four-line records of (seqs, quals) as one bytes object."""
+    out = []
+    for i, (s, q) in enumerate(zip(seqs, quals)):
+        name = names[i] if names is not None else b"read%d" % i
+        out.append(b"@" + name + b"\n" + s + b"\n+\n" + q + b"\n")
+    return b"".join(out)
