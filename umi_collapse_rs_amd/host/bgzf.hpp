@@ -251,6 +251,29 @@ inline Bytes decompress(const Bytes &in, unsigned threads)
     return std::move(inf.out);
 }
 
+// One BGZF block: `n` payload bytes deflated by `zs` (initialised raw, or reset) into `b` (room for
+// `cap` bytes), header and trailer included; returns the block's size.
+inline uint32_t deflate_block(z_stream &zs, const uint8_t *payload, size_t n, uint8_t *b, size_t cap)
+{
+    zs.next_in = const_cast<Bytef *>(payload);
+    zs.avail_in = (uInt)n;
+    zs.next_out = b + 18;
+    zs.avail_out = (uInt)(cap - 18 - 8);
+    const int rc = deflate(&zs, Z_FINISH);
+    const size_t clen = zs.total_out;
+    if (rc != Z_STREAM_END) throw IoError("deflate failed");
+    const uint32_t bsize = (uint32_t)(18 + clen + 8 - 1);
+    if (bsize > 0xffff) throw IoError("BGZF block overflow");
+    const uint8_t hdr[18] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0,
+                             (uint8_t)(bsize & 0xff), (uint8_t)(bsize >> 8)};
+    std::memcpy(b, hdr, 18);
+    const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), payload, (uInt)n);
+    uint8_t *t = b + 18 + clen;
+    for (int k = 0; k < 4; k++) t[k] = (uint8_t)(crc >> (8 * k));
+    for (int k = 0; k < 4; k++) t[4 + k] = (uint8_t)((uint32_t)n >> (8 * k));
+    return (uint32_t)(18 + clen + 8);
+}
+
 // BGZF compression of a stream given as pieces (the header, runs of surviving records: nothing is
 // copied together first): 0xff00-byte payloads, parallel deflate -- a run of blocks per task, one
 // deflate state per run, a block's payload gathered into a buffer that stays in the core's cache --
@@ -313,31 +336,13 @@ inline void compress_pieces_to_file(const std::string &path, const std::vector<P
                     std::memcpy(payload.get() + got, pieces[piece].p + at, take);
                     got += take;
                 }
-                uint8_t *b = slots + i * SLOT;
                 if (i != r * RUN) deflateReset(&zs);
-                zs.next_in = payload.get();
-                zs.avail_in = (uInt)n;
-                zs.next_out = b + 18;
-                zs.avail_out = (uInt)(SLOT - 18 - 8);
-                const int rc = deflate(&zs, Z_FINISH);
-                const size_t clen = zs.total_out;
-                if (rc != Z_STREAM_END) {
+                try {
+                    size_of[i] = deflate_block(zs, payload.get(), n, slots + i * SLOT, SLOT);
+                } catch (...) {
                     deflateEnd(&zs);
-                    throw IoError("deflate failed");
+                    throw;
                 }
-                const uint32_t bsize = (uint32_t)(18 + clen + 8 - 1);
-                if (bsize > 0xffff) {
-                    deflateEnd(&zs);
-                    throw IoError("BGZF block overflow");
-                }
-                const uint8_t hdr[18] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0,
-                                         (uint8_t)(bsize & 0xff), (uint8_t)(bsize >> 8)};
-                std::memcpy(b, hdr, 18);
-                const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), payload.get(), (uInt)n);
-                uint8_t *t = b + 18 + clen;
-                for (int k = 0; k < 4; k++) t[k] = (uint8_t)(crc >> (8 * k));
-                for (int k = 0; k < 4; k++) t[4 + k] = (uint8_t)((uint32_t)n >> (8 * k));
-                size_of[i] = (uint32_t)(18 + clen + 8);
             }
             deflateEnd(&zs);
             flag.v = 1;
@@ -359,6 +364,189 @@ inline void compress_to_file(const std::string &path, const uint8_t *data, size_
 {
     compress_pieces_to_file(path, std::vector<Piece>{{data, len}}, threads, level);
 }
+
+// Chunked BGZF decompression for inputs read more than once or too large to hold (--two-pass):
+// the file is read `chunk` compressed bytes at a time, the complete blocks of a chunk are inflated
+// in parallel and appended to the caller's buffer; a block cut by the chunk's end waits for the next.
+class ChunkReader
+{
+  public:
+    ChunkReader(const std::string &path, unsigned threads, size_t chunk = 16u << 20) : threads_(threads), chunk_(chunk)
+    {
+        fd_ = ::open(path.c_str(), O_RDONLY);
+        if (fd_ < 0) throw IoError("Invalid input path: " + path);
+    }
+    ~ChunkReader()
+    {
+        if (fd_ >= 0) ::close(fd_);
+    }
+    ChunkReader(const ChunkReader &) = delete;
+    ChunkReader &operator=(const ChunkReader &) = delete;
+
+    // appends the next chunk's bytes to `out`; false once the file is done
+    bool next(Bytes &out)
+    {
+        while (true) {
+            if (eof_ && pending_.empty()) return false;
+            if (!eof_) {
+                const size_t have = pending_.size();
+                pending_.resize(have + chunk_);
+                size_t got = 0;
+                while (got < chunk_) {
+                    const ssize_t r = ::read(fd_, pending_.data() + have + got, chunk_ - got);
+                    if (r < 0) throw IoError("short read on the input");
+                    if (r == 0) {
+                        eof_ = true;
+                        break;
+                    }
+                    got += (size_t)r;
+                }
+                pending_.resize(have + got);
+            }
+            // the complete blocks at the front of pending_
+            std::vector<BlockRef> blocks;
+            size_t off = 0, total = 0;
+            const uint8_t *in = pending_.data();
+            const size_t n = pending_.size();
+            while (n - off >= 18) {
+                if (in[off] != 0x1f || in[off + 1] != 0x8b || in[off + 2] != 8 || !(in[off + 3] & 4))
+                    throw IoError("not a BGZF block");
+                const uint32_t xlen = in[off + 10] | (in[off + 11] << 8);
+                const size_t xend = off + 12 + xlen;
+                if (xend > n) break;
+                uint32_t bsize = 0;
+                for (size_t x = off + 12; x + 4 <= xend;) {
+                    const uint32_t slen = in[x + 2] | (in[x + 3] << 8);
+                    if (in[x] == 'B' && in[x + 1] == 'C' && slen == 2 && x + 6 <= xend) bsize = (in[x + 4] | (in[x + 5] << 8)) + 1u;
+                    x += 4 + (size_t)slen;
+                }
+                if (!bsize || (size_t)bsize < (xend - off) + 8) throw IoError("truncated BGZF block");
+                if (bsize > n - off) break; // (the rest of it comes with the next chunk)
+                const size_t tail = off + bsize - 8;
+                const uint32_t isize = in[tail + 4] | (in[tail + 5] << 8) | (in[tail + 6] << 16) | ((uint32_t)in[tail + 7] << 24);
+                if (isize > 0x10000u) throw IoError("Failed to parse record: corrupt BGZF block");
+                blocks.push_back({xend, (uint32_t)(tail - xend), isize, total});
+                total += isize;
+                off += bsize;
+            }
+            if (blocks.empty()) {
+                if (eof_) throw IoError("truncated BGZF block");
+                continue;
+            }
+            const size_t base = out.size();
+            out.resize(base + total);
+            uint8_t *dst = out.data() + base;
+            constexpr size_t RUN = 16;
+            parallel_for((blocks.size() + RUN - 1) / RUN, threads_, [&](size_t r) {
+                z_stream zs;
+                std::memset(&zs, 0, sizeof(zs));
+                if (inflateInit2(&zs, -15) != Z_OK) throw IoError("inflateInit2 failed");
+                for (size_t i = r * RUN; i < std::min(blocks.size(), (r + 1) * RUN); i++) {
+                    const BlockRef &b = blocks[i];
+                    if (b.out_len == 0) continue;
+                    inflateReset2(&zs, -15);
+                    zs.next_in = const_cast<Bytef *>(in + b.in_off);
+                    zs.avail_in = b.in_len;
+                    zs.next_out = dst + b.out_off;
+                    zs.avail_out = b.out_len;
+                    if (inflate(&zs, Z_FINISH) != Z_STREAM_END || zs.avail_out != 0) {
+                        inflateEnd(&zs);
+                        throw IoError("Failed to parse record: corrupt BGZF block");
+                    }
+                }
+                inflateEnd(&zs);
+            });
+            pending_.erase(pending_.begin(), pending_.begin() + (ptrdiff_t)off);
+            if (total) return true;
+        }
+    }
+
+  private:
+    int fd_ = -1;
+    unsigned threads_;
+    size_t chunk_;
+    bool eof_ = false;
+    Bytes pending_; // compressed bytes not inflated yet
+};
+
+// Incremental BGZF output: bytes are appended as they become final; every `batch` bytes the full
+// 0xff00-byte blocks are deflated in parallel (one deflate state per run of blocks) and written in
+// order.  close() writes the rest and the EOF block.  The block cut follows the appends, so the file
+// may differ from compress_pieces_to_file's; the decompressed stream is the same.
+class ChunkWriter
+{
+  public:
+    ChunkWriter(const std::string &path, unsigned threads, int level, size_t batch = 8u << 20)
+        : threads_(threads), level_(level), batch_(std::max<size_t>(batch, PAYLOAD))
+    {
+        fd_ = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd_ < 0) throw IoError("cannot open output " + path);
+    }
+    ~ChunkWriter()
+    {
+        if (fd_ >= 0) ::close(fd_);
+    }
+    ChunkWriter(const ChunkWriter &) = delete;
+    ChunkWriter &operator=(const ChunkWriter &) = delete;
+
+    void write(const uint8_t *p, size_t n)
+    {
+        buf_.insert(buf_.end(), p, p + n);
+        if (buf_.size() >= batch_) flush(false);
+    }
+    void close()
+    {
+        flush(true);
+        static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0,
+                                        0, 0, 0, 0, 0, 0, 0, 0};
+        write_all(eof, sizeof(eof));
+        if (::close(fd_) != 0) throw IoError("Failed to write the record");
+        fd_ = -1;
+    }
+
+  private:
+    static constexpr size_t PAYLOAD = 0xff00, RUN = 16, SLOT = 18 + 0x10000 + 1024 + 8;
+    void flush(bool all)
+    {
+        const size_t nblk = all ? (buf_.size() + PAYLOAD - 1) / PAYLOAD : buf_.size() / PAYLOAD;
+        if (!nblk) return;
+        const size_t len = std::min(buf_.size(), nblk * PAYLOAD);
+        if (slots_.size() < nblk * SLOT) slots_.resize(nblk * SLOT);
+        std::vector<uint32_t> size_of(nblk, 0);
+        parallel_for((nblk + RUN - 1) / RUN, threads_, [&](size_t r) {
+            z_stream zs;
+            std::memset(&zs, 0, sizeof(zs));
+            if (deflateInit2(&zs, level_, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw IoError("deflateInit2 failed");
+            for (size_t i = r * RUN; i < std::min(nblk, (r + 1) * RUN); i++) {
+                if (i != r * RUN) deflateReset(&zs);
+                try {
+                    size_of[i] = deflate_block(zs, buf_.data() + i * PAYLOAD, std::min(PAYLOAD, len - i * PAYLOAD),
+                                               slots_.data() + i * SLOT, SLOT);
+                } catch (...) {
+                    deflateEnd(&zs);
+                    throw;
+                }
+            }
+            deflateEnd(&zs);
+        });
+        for (size_t i = 0; i < nblk; i++) write_all(slots_.data() + i * SLOT, size_of[i]);
+        buf_.erase(buf_.begin(), buf_.begin() + (ptrdiff_t)len);
+    }
+    void write_all(const uint8_t *p, size_t n)
+    {
+        while (n) {
+            const ssize_t w = ::write(fd_, p, n);
+            if (w <= 0) throw IoError("Failed to write the record");
+            p += w;
+            n -= (size_t)w;
+        }
+    }
+    int fd_ = -1;
+    unsigned threads_;
+    int level_;
+    size_t batch_;
+    Bytes buf_, slots_;
+};
 
 } // namespace bgzf
 } // namespace umi

@@ -30,14 +30,23 @@
 // over 256 bases end the run with status 101.  Refused with it: --paired, --remove-unpaired,
 // --remove-chimeric, --keep-unmapped, --two-pass, --stage gpu, several --devices; --umi_sep and
 // --data are accepted and ignored.
-// Not implemented, as in the reference: --two-pass, --algo cc.
+// --two-pass (the reference parses it and ignores it; UMICollapse's meaning): the input is read twice and
+// never held.  Pass 1 counts, writes the kept unmapped reads and notes the last read of every alignment
+// key; pass 2 holds a position's reads until its last one, deduplicates closed positions in windows of
+// --two-pass-window reads (one batched library call each) and writes the survivors through a reorder
+// buffer in the one-pass order.  Same decompressed output and summary lines as one pass, plus
+// "two-pass: <W> windows, at most <R> reads held" (run_two_pass).  --dump-staging and
+// --passthrough keep their one-pass behaviour with it.
+// Not implemented, as in the reference: --algo cc.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
+#include <functional>
 #include <future>
+#include <sys/stat.h>
 #include <string>
 #include <unistd.h>
 #include <unordered_map>
@@ -67,6 +76,7 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     int compress_level = 1;      // --compress-level 0..9: deflate level of the output's BGZF blocks.  Parity is
                                  // defined on the decompressed stream (htslib's own level and backend are
                                  // not reproducible here), and level 1 deflates a third of level 6's time
+    uint64_t two_pass_window = 1u << 21; // --two-pass-window <N>: reads per GPU call of --two-pass (see run_two_pass)
     std::string stage = "auto";  // --stage gpu|host|auto: where the reads are merged per (position, UMI) and
                                  // put in rank order (auto: on the GPU unless --paired or --tag need the
                                  // host's per-read bookkeeping)
@@ -188,7 +198,10 @@ void usage()
               "      --remove-chimeric    Remove chimeric pairs (paired-end mode)\n"
               "      --tag                Write every read tagged with its cluster (MI, cs, su) instead of\n"
               "                           removing duplicates\n"
-              "      --two-pass           accepted and rejected (see header)\n"
+              "      --two-pass           Read the input twice and hold only the open positions: peak memory\n"
+              "                           bounded for coordinate-sorted input, output identical to one pass\n"
+              "                           (-i must be a regular file; not with --tag or fastq mode)\n"
+              "      --two-pass-window <N> reads per GPU call with --two-pass [default: 2097152]\n"
               "      --compress-level <N> deflate level of the output BAM, 0..9 [default: 1]\n"
               "      --stage <WHERE>      gpu, host or auto: where reads are merged per (position, UMI) [default: auto]\n"
               "      --device <ID>        GPU to use [default: 0]\n"
@@ -225,6 +238,13 @@ Cli parse(int argc, char **argv)
         else if (a == "--merge") c.merge = need(i);
         else if (a == "--data") c.data = need(i);
         else if (a == "--two-pass") c.two_pass = true;
+        else if (a == "--two-pass-window") {
+            const char *v = need(i);
+            char *end = nullptr;
+            const long long w = std::strtoll(v, &end, 10);
+            if (end == v || *end != '\0' || w < 1) die("--two-pass-window wants a number of reads, 1 or more");
+            c.two_pass_window = (uint64_t)w;
+        }
         else if (a == "--paired") c.paired = true;
         else if (a == "--remove-unpaired") c.remove_unpaired = true;
         else if (a == "--remove-chimeric") c.remove_chimeric = true;
@@ -303,6 +323,56 @@ size_t detect_umi_length(const uint8_t *q, size_t n, uint8_t sep)
             return j - i - 1;
         }
     die("No UMI group found in pattern match");
+}
+
+// The filters of the read loop (deduplicate_sam.rs:95-129), shared by the one-pass staging and both
+// passes of --two-pass.  Returns the read's state: 0 staged, 1 unmapped, 3 second mate (not counted),
+// 4 mate unmapped, 5 filtered (--remove-unpaired / --remove-chimeric); 2 (error) is set by the caller.
+uint8_t read_state(const Cli &args, const umi::bam::Record &r, uint8_t &is_unpaired, uint8_t &is_chimeric)
+{
+    is_unpaired = is_chimeric = 0;
+    if (args.paired && r.is_paired() && r.is_last_in_template()) return 3; // :95-97
+    if (r.is_unmapped()) return 1;                                         // :102-108
+    if (args.paired && !args.passthrough) {                                // :110-129
+        if (!r.is_paired()) {
+            is_unpaired = 1;
+            if (args.remove_unpaired) return 5;
+        }
+        if (r.is_paired() && r.is_mate_unmapped()) return 4;
+        if (r.is_paired() && r.tid() != r.mtid()) {
+            is_chimeric = 1;
+            if (args.remove_chimeric) return 5;
+        }
+    }
+    return 0;
+}
+
+// Alignment{strand, coord, ref} (:141-145) or, with --paired, PairedAlignment (:138, :547-553) of a
+// staged read; equality on tid == equality on the reference name
+AlignKey align_key(const umi::bam::Record &r, bool paired)
+{
+    return AlignKey{(uint64_t)r.unclipped_pos(), ((uint64_t)(uint32_t)r.tid() << 1) | (r.is_reverse() ? 1u : 0u),
+                    paired ? (uint64_t)(int64_t)r.tlen() : 0};
+}
+
+// where a staged read's UMI starts in its name (read.rs:100), or the reference's message
+const char *find_umi(const umi::bam::Record &r, uint8_t sep, size_t umi_length, size_t &at)
+{
+    const uint8_t *q = r.qname();
+    const size_t qn = r.qname_len();
+    const uint8_t *sp = (const uint8_t *)std::memchr(q, sep, qn);
+    at = sp ? (size_t)(sp - q) + 1 : 0;
+    if (!sp) return "failed to get the umi";
+    if (umi_length == 0) return "Empty UMI sequence extracted";
+    if (umi_length > UMI_MAX_WIDE_UMI_LEN) return "UMIs of more than 85 bases are not handled";
+    if (at + umi_length > qn) return "UMI runs past the end of the read name";
+    return nullptr;
+}
+
+// a second mate the paired writer may look for (:425-429)
+bool mate_candidate(const umi::bam::Record &r)
+{
+    return !r.is_unmapped() && r.is_paired() && r.is_last_in_template() && !r.is_mate_unmapped();
 }
 
 double now_s()
@@ -536,6 +606,446 @@ int run_fastq(const Cli &args, int algo, int merge, HipLib &lib)
     std::_Exit(0); // (no static destructors: as the BAM path, the process ends without tearing HIP down)
 }
 
+
+// ---- --two-pass: the file is read twice and never held.  Pass 1 (census) walks the
+// records without keeping them: counters, the kept unmapped reads (written at once: they come first), the
+// UMI length, and per alignment key the index of its last read (UMICollapse's `latest`).  Pass 2 reads
+// the file again; a position's reads are held until its last one has been read, closed positions gather
+// in a window that goes to the library as one batched call once it holds --two-pass-window reads, and a
+// reorder buffer writes the survivors in the one-pass order (positions by first appearance).  Output and
+// summary lines are those of the one-pass run; only the decompressed stream is equal, the BGZF block cut
+// differs.
+
+// Records of a BGZF-compressed BAM, one at a time (the checks of umi::bam::File::parse_behind); only
+// the chunk being parsed and a record cut by its end are held.
+class RecordStream
+{
+  public:
+    RecordStream(const std::string &path, unsigned threads) : in_(path, threads) {}
+    // the header (magic .. end of the reference list), verbatim
+    umi::bgzf::Bytes header()
+    {
+        size_t q;
+        while (!(q = header_len()))
+            if (!more()) {
+                if (buf_.size() >= 4 && std::memcmp(buf_.data(), "BAM\1", 4) != 0)
+                    throw umi::bam::FormatError("Invalid input path: not a BAM file");
+                throw umi::bam::FormatError("truncated BAM header");
+            }
+        umi::bgzf::Bytes h(buf_.begin(), buf_.begin() + (ptrdiff_t)q);
+        pos_ = q;
+        return h;
+    }
+    // the next record, valid until the next call; false at the end of the file
+    bool next(umi::bam::Record &r)
+    {
+        while (true) {
+            const size_t avail = buf_.size() - pos_;
+            if (avail >= 4) {
+                const uint8_t *p = buf_.data() + pos_;
+                const int32_t bs = umi::bam::rd_i32(p);
+                if (bs < 32) throw umi::bam::FormatError("Failed to parse record");
+                if (avail - 4 >= (size_t)bs) {
+                    const umi::bam::Record rec{p, p + 4 + (size_t)bs};
+                    const int32_t l_seq = rec.l_seq();
+                    if (l_seq < 0 || 32ull + rec.l_read_name() + 4ull * rec.n_cigar() + ((uint64_t)l_seq + 1) / 2 +
+                                             (uint64_t)l_seq > (uint64_t)bs)
+                        throw umi::bam::FormatError("Failed to parse record");
+                    pos_ += 4 + (size_t)bs;
+                    r = rec;
+                    return true;
+                }
+            }
+            if (!more()) {
+                if (avail) throw umi::bam::FormatError("Failed to parse record");
+                return false;
+            }
+        }
+    }
+
+  private:
+    bool more()
+    {
+        buf_.erase(buf_.begin(), buf_.begin() + (ptrdiff_t)pos_);
+        pos_ = 0;
+        return in_.next(buf_);
+    }
+    // bytes of the header once they are all there, else 0
+    size_t header_len() const
+    {
+        const uint8_t *p = buf_.data();
+        const size_t size = buf_.size();
+        if (size < 12) return 0;
+        if (std::memcmp(p, "BAM\1", 4) != 0) throw umi::bam::FormatError("Invalid input path: not a BAM file");
+        const int32_t l_text = umi::bam::rd_i32(p + 4);
+        if (l_text < 0) throw umi::bam::FormatError("truncated BAM header");
+        size_t q = 8 + (size_t)l_text;
+        if (size < q + 4) return 0;
+        const int32_t n_ref = umi::bam::rd_i32(p + q);
+        if (n_ref < 0) throw umi::bam::FormatError("truncated BAM header");
+        q += 4;
+        for (int32_t r = 0; r < n_ref; r++) {
+            if (size < q + 4) return 0;
+            const int32_t l_name = umi::bam::rd_i32(p + q);
+            if (l_name < 0) throw umi::bam::FormatError("truncated BAM header");
+            q += 4 + (size_t)l_name + 4;
+            if (size < q) return 0;
+        }
+        return q;
+    }
+    umi::bgzf::ChunkReader in_;
+    umi::bgzf::Bytes buf_;
+    size_t pos_ = 0;
+};
+
+void run_two_pass(const Cli &args, int algo, int merge, HipLib &lib, const std::function<umi_ctx *()> &get_ctx,
+                  const std::function<void(const char *)> &lap, double t_start)
+{
+    struct stat sb;
+    if (::stat(args.input.c_str(), &sb) != 0) die("Invalid input path: " + args.input);
+    if (!S_ISREG(sb.st_mode)) die("--two-pass reads the input twice: -i must be a regular file (" + args.input + ")");
+    if (args.stage != "auto" && args.stage != "gpu" && args.stage != "host") die("--stage wants gpu, host or auto");
+    const unsigned T = std::max(1u, args.num_threads);
+    auto reg_hash = [](const std::string &key) { return (uint64_t)std::hash<std::string>()(key); };
+
+    // ---- pass 1: census
+    umi::bgzf::ChunkWriter out(args.output, T, args.compress_level);
+    size_t umi_length = args.umi_length;
+    size_t total_read_count = 0, unmapped = 0, unpaired = 0, chimeric = 0;
+    std::unordered_map<AlignKey, uint64_t, KeyHash> latest; // alignment key -> index of its last read
+    std::unordered_map<int32_t, uint64_t> last_mate_on;     // --paired: reference -> index of its last candidate second mate
+    std::unordered_map<uint64_t, uint32_t> reg_count;       // --paired: hash of the (qname, mate ref, mate pos) a staged
+                                                            // first mate registers -> first mates not yet written or dropped
+    bool bad_char = false;
+    uint64_t n_records = 0;
+    {
+        RecordStream rs(args.input, T);
+        const umi::bgzf::Bytes h = rs.header();
+        out.write(h.data(), h.size());
+        umi::bam::Record r;
+        UmiKey k, nm;
+        for (uint64_t ri = 0; rs.next(r); ri++, n_records++) {
+            uint8_t up, ch;
+            const uint8_t state = read_state(args, r, up, ch);
+            if (state != 3) total_read_count++;
+            unpaired += up;
+            chimeric += ch;
+            if (args.paired && mate_candidate(r)) last_mate_on[r.tid()] = ri;
+            if (state == 4) unmapped++;
+            if (state == 1) {
+                unmapped++;
+                if (args.keep_unmapped) out.write(r.begin, (size_t)(r.end - r.begin)); // :104-106, ahead of every position
+            }
+            if (state != 0) continue;
+            if (umi_length == 0) umi_length = detect_umi_length(r.qname(), r.qname_len(), args.umi_sep); // :154-156
+            size_t at;
+            if (const char *err = find_umi(r, args.umi_sep, umi_length, at)) die(err);
+            if (!bad_char && !encode_umi(r.qname() + at, umi_length, &k, &nm)) bad_char = true;
+            latest[align_key(r, args.paired)] = ri;
+            if (args.paired && r.is_paired()) reg_count[reg_hash(mate_key(r.qname(), r.qname_len(), r.mtid(), r.mpos()))]++;
+        }
+    }
+    if (bad_char) die("Unknown character in UMI sequence");
+    lap("census");
+    const double t_census = now_s();
+
+    const bool gpu_stage = args.stage != "host" && !args.paired && umi_length >= 1;
+    if (args.stage == "gpu" && !gpu_stage) die("--stage gpu does not go with --paired, --tag or --dump-staging");
+    const int n_words = umi_length ? (int)((3 * umi_length + 63) / 64) : 1;
+
+    // ---- pass 2
+    struct ReadRef {
+        uint64_t off;    // of the record in its position's bytes
+        uint32_t umi_at; // of the UMI in the read name
+        int32_t score;
+    };
+    struct Bucket {
+        uint64_t seq = 0, last = 0; // first-appearance rank; index of the last read
+        std::vector<uint8_t> bytes;
+        std::vector<ReadRef> reads;
+    };
+    struct Survivors { // a deduplicated position's written records, in rank order
+        std::vector<uint8_t> bytes;
+        uint64_t count = 0;
+    };
+    struct Mate {
+        uint64_t ri;
+        std::string key;
+        std::vector<uint8_t> rec;
+    };
+    auto rec_at = [](const uint8_t *p) {
+        return umi::bam::Record{p, p + 4 + (size_t)umi::bam::rd_i32(p)};
+    };
+    std::unordered_map<AlignKey, Bucket, KeyHash> open;
+    std::vector<Bucket> window;
+    std::unordered_map<uint64_t, Survivors> pending; // the reorder buffer
+    std::unordered_map<int32_t, std::vector<Mate>> mates; // --paired: second mates by reference, file order
+    std::unordered_set<std::string> waiting;
+    uint64_t next_seq = 0, next_out = 0, n_windows = 0, done_upto = 0; // done_upto: records of pass 2 read so far
+    bool pass2_done = false, have_ref = false, stalled = false;
+    int32_t cur_ref = 0;
+    uint64_t held_open = 0, held_window = 0, held_pending = 0, held_mates = 0, peak = 0;
+    auto note_peak = [&]() { peak = std::max(peak, held_open + held_window + held_pending + held_mates); };
+    size_t n_total = 0, nb_total = 0, max_umi = 0;
+    uint64_t n_kept = 0, n_pairs = 0;
+    double t_hot = 0.0;
+    umi_ctx *ctx = nullptr;
+
+    auto release = [&](const umi::bam::Record &r) { // a staged first mate written or dropped
+        if (!args.paired || !r.is_paired()) return;
+        auto it = reg_count.find(reg_hash(mate_key(r.qname(), r.qname_len(), r.mtid(), r.mpos())));
+        if (it != reg_count.end() && --it->second == 0) reg_count.erase(it);
+    };
+    // UcWriter::write_reversed (:382-459) over the held second mates of one reference (or all of them, at
+    // the end) in file order; a mate no staged first mate can still register is let go
+    auto flush_mates = [&](int32_t tid, bool all) {
+        std::vector<Mate> cands;
+        if (all) {
+            for (auto &m : mates)
+                for (Mate &x : m.second) cands.push_back(std::move(x));
+            mates.clear();
+            std::sort(cands.begin(), cands.end(), [](const Mate &a, const Mate &b) { return a.ri < b.ri; });
+        } else {
+            auto it = mates.find(tid);
+            if (it == mates.end()) return;
+            cands.swap(it->second);
+            mates.erase(it);
+        }
+        std::vector<Mate> keep;
+        for (Mate &m : cands) {
+            auto w = waiting.find(m.key);
+            if (w != waiting.end()) {
+                out.write(m.rec.data(), m.rec.size());
+                waiting.erase(w);
+            } else if (!all && reg_count.count(reg_hash(m.key))) {
+                keep.push_back(std::move(m));
+            }
+        }
+        held_mates -= cands.size() - keep.size();
+        if (!keep.empty()) mates[tid] = std::move(keep);
+    };
+    // write the deduplicated positions that are next in first-appearance order
+    auto pump = [&]() {
+        stalled = false;
+        for (auto it = pending.find(next_out); it != pending.end(); it = pending.find(++next_out)) {
+            Survivors &sv = it->second;
+            if (args.paired && sv.count) {
+                const int32_t tid = rec_at(sv.bytes.data()).tid();
+                if (have_ref && cur_ref != tid) {
+                    auto lm = last_mate_on.find(cur_ref); // (every second mate of the reference must have been read)
+                    if (!pass2_done && lm != last_mate_on.end() && lm->second >= done_upto) {
+                        stalled = true;
+                        return;
+                    }
+                    flush_mates(cur_ref, false);
+                }
+            }
+            for (size_t o = 0; o < sv.bytes.size();) {
+                const umi::bam::Record r = rec_at(sv.bytes.data() + o);
+                const size_t len = (size_t)(r.end - r.begin);
+                if (args.paired) {
+                    have_ref = true;
+                    cur_ref = r.tid();
+                    if (r.is_paired()) waiting.insert(mate_key(r.qname(), r.qname_len(), r.mtid(), r.mpos())); // :395-401
+                    release(r);
+                }
+                out.write(r.begin, len);
+                o += len;
+            }
+            held_pending -= sv.count;
+            pending.erase(it);
+        }
+    };
+    // one batched library call for the closed positions of the window, in first-appearance order
+    auto run_window = [&]() {
+        if (window.empty()) return;
+        std::sort(window.begin(), window.end(), [](const Bucket &a, const Bucket &b) { return a.seq < b.seq; });
+        const size_t nb = window.size();
+        std::vector<uint64_t> read_base(nb + 1, 0);
+        for (size_t b = 0; b < nb; b++) read_base[b + 1] = read_base[b] + window[b].reads.size();
+        const size_t nr = read_base[nb];
+        std::vector<uint64_t, umi::bgzf::default_init_allocator<uint64_t>> keys(nr * n_words), nmask(nr * n_words),
+            off(nr + 1), rep(nr);
+        std::vector<int32_t, umi::bgzf::default_init_allocator<int32_t>> freq(nr);
+        auto umi_of = [&](const Bucket &bk, const ReadRef &rr) { return bk.bytes.data() + rr.off + 4 + 32 + rr.umi_at; };
+        uint64_t ne = 0, nbk = 0;
+        if (!ctx) ctx = get_ctx();
+        const double t0 = now_s();
+        if (gpu_stage) {
+            // (the window's position rank is the alignment key: the reads go in position by position, file order inside)
+            std::vector<uint64_t, umi::bgzf::default_init_allocator<uint64_t>> akey(nr);
+            umi::bgzf::Bytes umis(nr * umi_length);
+            std::vector<int32_t, umi::bgzf::default_init_allocator<int32_t>> sc(nr);
+            for (size_t b = 0; b < nb; b++)
+                for (size_t j = 0; j < window[b].reads.size(); j++) {
+                    const size_t g = read_base[b] + j;
+                    akey[g] = b;
+                    std::memcpy(&umis[g * umi_length], umi_of(window[b], window[b].reads[j]), umi_length);
+                    sc[g] = window[b].reads[j].score;
+                }
+            int bits = 1;
+            while (bits < 64 && (nb >> bits)) bits++;
+            if (lib.stage_reads(ctx, akey.data(), bits, umis.data(), sc.data(), nr, (int)umi_length, n_words, merge != 0 ? 1 : 0,
+                                keys.data(), nmask.data(), freq.data(), rep.data(), off.data(), &ne, &nbk) != UMI_OK)
+                die(lib.last_error());
+            if (nbk != nb) die("device staging returned " + std::to_string(nbk) + " positions for " + std::to_string(nb));
+        } else {
+            // deduplicate_sam.rs:148-176 per position, then the stable freq-descending rank order
+            std::unordered_map<UmiKey, uint32_t, UmiKeyHash> idx;
+            std::vector<Entry> ents;
+            std::vector<uint32_t> order;
+            off[0] = 0;
+            for (size_t b = 0; b < nb; b++) {
+                const Bucket &bk = window[b];
+                idx.clear();
+                ents.clear();
+                for (uint32_t j = 0; j < bk.reads.size(); j++) {
+                    const ReadRef &rr = bk.reads[j];
+                    UmiKey k, nm;
+                    encode_umi(umi_of(bk, rr), umi_length, &k, &nm); // (checked by the census)
+                    auto e = idx.find(k);
+                    if (e == idx.end()) {
+                        idx.emplace(k, (uint32_t)ents.size());
+                        ents.push_back({k, nm, 1, rr.score, j, (uint32_t)b});
+                    } else {
+                        Entry &en = ents[e->second];
+                        en.freq += 1;
+                        if (merge != 0 && !(en.score >= rr.score)) { en.rep = j; en.score = rr.score; } // merge/mod.rs:21,35,49
+                    }
+                }
+                order.resize(ents.size());
+                for (uint32_t j = 0; j < order.size(); j++) order[j] = j;
+                std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return ents[y].freq < ents[x].freq; });
+                for (uint32_t j : order) {
+                    const Entry &en = ents[j];
+                    for (int q = 0; q < n_words; q++) {
+                        keys[ne * n_words + q] = en.key.w[q];
+                        nmask[ne * n_words + q] = en.nmask.w[q];
+                    }
+                    freq[ne] = en.freq;
+                    rep[ne] = read_base[b] + en.rep;
+                    ne++;
+                }
+                off[b + 1] = ne;
+            }
+        }
+        bool any_n = false;
+        for (size_t i = 0; i < ne * n_words; i++) any_n |= nmask[i] != 0;
+        std::vector<uint8_t> kept(ne + 1, 0);
+        umi_stats st;
+        std::memset(&st, 0, sizeof(st));
+        if (lib.dedup_batch(ctx, keys.data(), any_n ? nmask.data() : nullptr, n_words, freq.data(), off.data(), nb,
+                            (int)umi_length, args.k, args.percentage, algo, 0 /* adjacency.rs:56 */, kept.data(), nullptr,
+                            &st) != UMI_OK)
+            die(lib.last_error());
+        t_hot += now_s() - t0;
+        n_total += ne;
+        nb_total += nb;
+        n_kept += st.n_kept;
+        n_pairs += st.n_pairs;
+        std::vector<uint8_t> survivor;
+        for (size_t b = 0; b < nb; b++) {
+            Bucket &bk = window[b];
+            max_umi = std::max<size_t>(max_umi, off[b + 1] - off[b]);
+            Survivors sv;
+            if (args.paired) survivor.assign(bk.reads.size(), 0);
+            for (uint64_t e = off[b]; e < off[b + 1]; e++) {
+                if (!kept[e]) continue;
+                const uint64_t j = rep[e] - read_base[b];
+                const umi::bam::Record r = rec_at(bk.bytes.data() + bk.reads[j].off);
+                sv.bytes.insert(sv.bytes.end(), r.begin, r.end);
+                sv.count++;
+                if (args.paired) survivor[j] = 1;
+            }
+            if (args.paired) // the merged-away and removed first mates register nothing
+                for (size_t j = 0; j < bk.reads.size(); j++)
+                    if (!survivor[j]) release(rec_at(bk.bytes.data() + bk.reads[j].off));
+            held_pending += sv.count;
+            pending.emplace(bk.seq, std::move(sv));
+        }
+        note_peak();
+        held_window = 0;
+        window.clear();
+        n_windows++;
+        pump();
+    };
+
+    {
+        RecordStream rs(args.input, T);
+        (void)rs.header();
+        umi::bam::Record r;
+        for (uint64_t ri = 0; rs.next(r); ri++) {
+            done_upto = ri + 1;
+            uint8_t up, ch;
+            const uint8_t state = read_state(args, r, up, ch);
+            if (args.paired && mate_candidate(r)) {
+                std::string key = mate_key(r.qname(), r.qname_len(), r.tid(), r.pos());
+                if (waiting.count(key) || reg_count.count(reg_hash(key))) { // (else no first mate can ask for it)
+                    mates[r.tid()].push_back(Mate{ri, std::move(key), std::vector<uint8_t>(r.begin, r.end)});
+                    held_mates++;
+                    note_peak();
+                }
+            }
+            if (state == 0) {
+                const AlignKey key = align_key(r, args.paired);
+                auto it = open.find(key);
+                if (it == open.end()) {
+                    it = open.emplace(key, Bucket()).first;
+                    it->second.seq = next_seq++;
+                    auto l = latest.find(key);
+                    it->second.last = l->second;
+                    latest.erase(l);
+                }
+                Bucket &bk = it->second;
+                size_t at;
+                find_umi(r, args.umi_sep, umi_length, at);
+                bk.reads.push_back({bk.bytes.size(), (uint32_t)at, merge == 2 ? (int32_t)r.mapq() : r.avg_qual()});
+                bk.bytes.insert(bk.bytes.end(), r.begin, r.end);
+                held_open++;
+                note_peak();
+                if (ri == bk.last) { // the position is closed
+                    held_open -= bk.reads.size();
+                    held_window += bk.reads.size();
+                    window.push_back(std::move(bk));
+                    open.erase(it);
+                    if (held_window >= args.two_pass_window) run_window();
+                }
+            }
+            if (stalled) pump();
+        }
+    }
+    pass2_done = true;
+    if (!open.empty()) die("two-pass: the input changed between the passes");
+    run_window();
+    pump();
+    if (have_ref) flush_mates(0, true); // close(), :411-415
+    lap("pass-2");
+    const double t_pass2 = now_s();
+    out.close();
+    lap("write");
+    const double t_end = now_s();
+
+    std::fprintf(stderr, "UMI collapsing reading finished in %.3f seconds\n", t_census - t_start);
+    std::fprintf(stderr, "Number of input reads: %zu\n", total_read_count);
+    std::fprintf(stderr, "Number of removed unmapped reads: %zu\n", unmapped);
+    if (args.paired) {
+        std::fprintf(stderr, "Number of unpaired reads: %zu\n", unpaired);
+        std::fprintf(stderr, "Number of chimeric reads: %zu\n", chimeric);
+    }
+    std::fprintf(stderr, "Number of unique alignment positions: %zu\n", nb_total);
+    std::fprintf(stderr, "Number of UMIs: %zu\n", n_total);
+    std::fprintf(stderr, "Average number of UMIs per alignment position: %g\n", nb_total ? (double)n_total / (double)nb_total : 0.0);
+    std::fprintf(stderr, "Max number of UMIs over all alignment positions: %zu\n", max_umi);
+    std::fprintf(stderr, "Number of reads after deduplicating: %llu\n", (unsigned long long)n_kept);
+    std::fprintf(stderr, "two-pass: %llu windows, at most %llu reads held\n", (unsigned long long)n_windows,
+                 (unsigned long long)peak);
+    std::fprintf(stderr,
+                 "phases: census %.3f s, pass 2 (staging %s) %.3f s, hot path (H2D+GPU+D2H) %.3f s [%llu pairs], write %.3f s\n",
+                 t_census - t_start, gpu_stage ? "gpu" : "host", t_pass2 - t_census, t_hot, (unsigned long long)n_pairs,
+                 t_end - t_pass2);
+    std::fprintf(stderr, "UMI collapsing finished in %.3f seconds\n", t_end - t_start);
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -614,6 +1124,18 @@ int main(int argc, char **argv)
         std::fflush(nullptr);
         std::_Exit(0); // the output file is closed; device memory and the runtime go with the process
     };
+    if (args.two_pass && !args.passthrough && args.dump_staging.empty()) { // (those two keep the one-pass behaviour)
+        try {
+            run_two_pass(args, algo, merge, lib, [&]() -> umi_ctx * {
+                umi_ctx *c = warm.get();
+                if (!c) die(warm_error);
+                return c;
+            }, lap, t_start);
+        } catch (const std::exception &e) {
+            die(e.what());
+        }
+        leave();
+    }
     try {
         // ---- read: BGZF inflate (threaded) + BAM parse
         umi::bam::File in;
@@ -640,21 +1162,7 @@ int main(int argc, char **argv)
         size_t umi_length = args.umi_length;
         // the filters of the read loop (:95-129); returns ReadInfo::state
         auto classify = [&](const umi::bam::Record &r, uint8_t &is_unpaired, uint8_t &is_chimeric) -> uint8_t {
-            is_unpaired = is_chimeric = 0;
-            if (args.paired && r.is_paired() && r.is_last_in_template()) return 3; // :95-97
-            if (r.is_unmapped()) return 1;                                         // :102-108
-            if (args.paired && !args.passthrough) {                                // :110-129
-                if (!r.is_paired()) {
-                    is_unpaired = 1;
-                    if (args.remove_unpaired) return 5;
-                }
-                if (r.is_paired() && r.is_mate_unmapped()) return 4;
-                if (r.is_paired() && r.tid() != r.mtid()) {
-                    is_chimeric = 1;
-                    if (args.remove_chimeric) return 5;
-                }
-            }
-            return 0;
+            return read_state(args, r, is_unpaired, is_chimeric);
         };
         if (umi_length == 0 && !args.passthrough) // autodetect on the first staged read (:154-156)
             for (uint32_t ri = 0; ri < n_rec; ri++) {
@@ -725,19 +1233,13 @@ int main(int argc, char **argv)
                 ii.tlen = 0;
                 ii.state = classify(r, ii.unpaired, ii.chimeric);
                 if (ii.state != 0 || args.passthrough) continue;
-                if (args.paired) ii.tlen = (uint64_t)(int64_t)r.tlen(); // record.insert_size(), :138
-                // Alignment{strand, coord, ref} (:141-145); equality on tid == equality on the name
-                ii.coord = (uint64_t)r.unclipped_pos();
-                ii.ref_strand = ((uint64_t)(uint32_t)r.tid() << 1) | (r.is_reverse() ? 1u : 0u);
+                const AlignKey ak = align_key(r, args.paired);
+                ii.coord = ak.coord;
+                ii.ref_strand = ak.ref_strand;
+                ii.tlen = ak.tlen;
                 const uint8_t *q = r.qname();
-                const size_t qn = r.qname_len();
-                const uint8_t *sp = (const uint8_t *)std::memchr(q, args.umi_sep, qn); // read.rs:100
-                const char *err = nullptr;
-                const size_t at = sp ? (size_t)(sp - q) + 1 : 0;
-                if (!sp) err = "failed to get the umi";
-                else if (umi_length == 0) err = "Empty UMI sequence extracted";
-                else if (umi_length > UMI_MAX_WIDE_UMI_LEN) err = "UMIs of more than 85 bases are not handled";
-                else if (at + umi_length > qn) err = "UMI runs past the end of the read name";
+                size_t at;
+                const char *err = find_umi(r, args.umi_sep, umi_length, at);
                 if (err) {
                     ii.state = 2;
                     if (first_error[t] == UINT32_MAX) { first_error[t] = ri; errors[t] = err; }
@@ -1017,7 +1519,7 @@ int main(int argc, char **argv)
             std::vector<uint32_t> mates_all;
             for (uint32_t ri = 0; ri < n_rec; ri++) {
                 const umi::bam::Record &r = in.records[ri];
-                if (!r.is_unmapped() && r.is_paired() && r.is_last_in_template() && !r.is_mate_unmapped()) { // :425-429
+                if (mate_candidate(r)) { // :425-429
                     mates_on[r.tid()].push_back(ri);
                     mates_all.push_back(ri);
                 }
