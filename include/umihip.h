@@ -116,6 +116,11 @@ const char *umi_last_error(void);
  *                    per entry)
  *   "seg_unite"      0/1 (default 1): symmetric pairs united where the pair kernel finds them (0: through
  *                    the list)
+ *   "seg_local"      0/1 (default 1): on the batched directional path with "seg_unite" and 32-bit compare
+ *                    keys, the part-0 sub-buckets of at most "seg_local_cap" entries are evaluated and
+ *                    their symmetric pairs united in LDS by a kernel of their own, ahead of the pair kernel
+ *                    (0: every sub-bucket through the pair kernel); same result and statistics
+ *   "seg_local_cap"  2..2048 (default 512): largest part-0 sub-bucket that kernel takes (LDS: 16 bytes per entry)
  *   "seg_ckey"       0/1 (default 1): the pair kernel compares 3-bit-per-base compare keys where the bases
  *                    outside a bin fit 32 bits (0: the 2-bit filter keys)
  *   "seg_sliced"     0/1 (default 1): ... 64 columns of a tile at a time, from wave ballots of the columns'

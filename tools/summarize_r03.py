@@ -25,7 +25,7 @@ STEPS = 13  # --steps 5 --warmup 2: 2 + 5 plain steps, then 1 + 5 with the event
 OUT = os.path.join(ROOT, "profiles", "r03_counters.json")
 
 PHASES = (("prep", ("prep_kernel", "bucket_rise", "seg_scan", "seg_scatter", "seg_count", "seg_hist", "iota", "rocprim")),
-          ("pairs", ("seg_pair", "seg_edge", "pair_kernel", "small_bucket", "wide_")),
+          ("pairs", ("seg_pair", "seg_local", "seg_edge", "pair_kernel", "small_bucket", "wide_")),
           ("collapse", ("uf_", "dag_", "jump_kernel", "map_label", "adj_mark", "adj_promote")),
           ("finalize", ("map_finalize", "finalize_kernel", "adj_finalize")))
 

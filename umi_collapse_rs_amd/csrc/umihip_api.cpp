@@ -207,13 +207,17 @@ struct umi_ctx {
     bool seg_lds = true;     // counting sort of the partition through per-block LDS histograms (where
                              // every part has at most SEG_LDS_BINS bins), else one atomic per entry
     int seg_occ[2][2][2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};
+    bool seg_local = true;   // part-0 sub-buckets of at most seg_local_cap entries united in LDS by a kernel
+    uint32_t seg_local_cap = SEG_LOCAL_CAP; // of their own, ahead of the pair kernel (batched directional path)
+    int seg_local_occ[2] = {0, 0}; // its resident blocks per CU (without / with N) at seg_local_occ_cap
+    uint32_t seg_local_occ_cap = 0;
     uint32_t seg_blocks = 0; // one-wave blocks of its pair kernel (0: all resident at once -- 24 per CU by
                              // registers, 28 by LDS with the compare keys' leaner loop)
     // workspace
     DevBuf fkey, thr, label, lab, edges, edge_dist, ovf, counters, boff, status, blocked;
     DevBuf plan_tables; // ranges, segment descriptors, scan chunks, popcount tile tasks: one upload
     DevBuf bs_tasks, plane_tasks, planes, tab_rows, tab_items;
-    DevBuf seg_bin_cnt, seg_bin_start, seg_tasks, seg_sub_rec, seg_priv_edges, seg_priv_dist, seg_priv_cnt;
+    DevBuf seg_bin_cnt, seg_bin_start, seg_tasks, seg_sub_rec, seg_priv_edges, seg_priv_dist, seg_priv_cnt, seg_priv_stat;
     PinnedBuf h_plan_alt[2]; // staging of the plan's tables, in turn; [plan_flip ^ 1] = what plan_tables holds
     int plan_flip = 0;
     size_t plan_uploaded = 0;
@@ -413,8 +417,9 @@ class Pipeline {
     bool prune = false, drained = false, fused_ran = false, seg_timed = false;
     bool may_defer = false; // umi_dedup_batch_device_begin: the end of the call may be left on the stream
     size_t zero_behind_control = 0; // bytes of the segment index's counters that sit behind the control block
-    uint32_t priv_blocks_for_collapse = 0; // blocks of the segment index's pair kernel whose private edge slots the
-                                           // collapse's flatten launch appends to the list (0: appended already)
+    uint32_t priv_blocks_for_collapse = 0; // blocks of the segment index's local and pair kernels whose private edge
+                                           // slots the collapse's flatten launch appends to the list (0: appended already)
+    uint64_t seg_local_bins = 0; // part-0 bins of the call's segments (the local kernel's grid at most)
     umi_stats st;
     unsigned long long *d_cnt = nullptr;
     size_t n_tasks = 0;              // tile tasks of the pair kernels (fused buckets excluded)
@@ -677,6 +682,13 @@ class Pipeline {
             seg.full_umi_len = umi_len;
             seg.use_ckey = key32 && ctx->seg_ckey && pl.seg_max_rest <= 10 ? 1u : 0u;
             seg.col_sliced = ctx->seg_sliced ? 1u : 0u;
+            // part 0 in LDS: where the pair kernel would unite symmetric pairs on the spot (the batched
+            // directional path, one device's whole call) and compares 32-bit compare keys
+            if (ctx->seg_local && ctx->seg_unite && mode == MODE_DIRECTIONAL && one_sync() && seg.use_ckey) {
+                seg.local_cap = ctx->seg_local_cap;
+                seg_local_bins = 0;
+                for (const SegDesc &sd : pl.segs) seg_local_bins += 1ull << (2 * sd.nb[0]);
+            }
             if (ctx->seg_lds && pl.seg_max_bins <= SEG_LDS_BINS && !pl.seg_blocks.empty()) {
                 seg.blocks = d_seg_blocks;
                 seg.n_blocks = (uint32_t)pl.seg_blocks.size();
@@ -954,6 +966,16 @@ class Pipeline {
         if (!slot) slot = seg_pair_blocks_per_cu(key32, has_n, ck);
         return (uint32_t)slot;
     }
+    uint32_t seg_local_occupancy()
+    {
+        if (ctx->seg_local_occ_cap != seg.local_cap) {
+            ctx->seg_local_occ[0] = ctx->seg_local_occ[1] = 0;
+            ctx->seg_local_occ_cap = seg.local_cap;
+        }
+        int &slot = ctx->seg_local_occ[d_nmask != nullptr ? 1 : 0];
+        if (!slot) slot = seg_local_blocks_per_cu(d_nmask != nullptr, seg.local_cap);
+        return (uint32_t)slot;
+    }
 
     // all pair kernels of the call, largest work first (nothing waits on the host in here)
     int enqueue_pairs(uint64_t ovf_cap)
@@ -981,24 +1003,41 @@ class Pipeline {
         if (pl.seg_parts) { // the large buckets' sub-buckets: persistent one-wave blocks
             const uint32_t blocks = std::max(1u, (uint32_t)std::min<uint64_t>(
                 pl.seg_task_cap, ctx->seg_blocks ? ctx->seg_blocks : (uint64_t)ctx->n_cus * std::min(16u, seg_occupancy())));
+            // the local kernel's blocks (resident all at once, no more than there are part-0 bins) take
+            // the first private slots, the pair kernel's the ones behind them
+            const uint32_t local_blocks = seg.local_cap ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(
+                                                              seg_local_bins, (uint64_t)ctx->n_cus * seg_local_occupancy()))
+                                                        : 0u;
+            const size_t slots = (size_t)local_blocks + blocks;
             int rc;
-            if ((rc = ctx->seg_priv_edges.reserve((size_t)blocks * SEG_PRIV_CAP * sizeof(uint2))) ||
-                (rc = ctx->seg_priv_cnt.reserve((size_t)blocks * 4)) ||
+            if ((rc = ctx->seg_priv_edges.reserve(slots * SEG_PRIV_CAP * sizeof(uint2))) ||
+                (rc = ctx->seg_priv_cnt.reserve(slots * 4)) || (rc = ctx->seg_priv_stat.reserve(slots * sizeof(uint2))) ||
                 (mode == MODE_NEIGHBOURS && (rc = ctx->seg_priv_dist.reserve((size_t)blocks * SEG_PRIV_CAP))))
                 return rc;
             seg.priv_edges = ctx->seg_priv_edges.as<uint2>();
             seg.priv_dist = ctx->seg_priv_dist.as<uint8_t>();
             seg.priv_cnt = ctx->seg_priv_cnt.as<uint32_t>();
             seg.uf_parent = one_sync() && ctx->seg_unite ? ctx->label.as<uint32_t>() : nullptr;
+            // the slots go to the collapse's flatten launch, which adds up the blocks' counts as well
+            const bool slots_to_collapse = seg.uf_parent && mode == MODE_DIRECTIONAL;
+            seg.priv_stat = slots_to_collapse ? ctx->seg_priv_stat.as<uint2>() : nullptr;
+            if (seg.local_cap && !seg.uf_parent) // (the scan has left the local bins without tasks)
+                return fail(UMI_ERR_HIP, "internal: part-0 sub-buckets planned for the local kernel without unions");
+            SegArgs pair_seg = seg;
+            pair_seg.priv_edges += (size_t)local_blocks * SEG_PRIV_CAP;
+            pair_seg.priv_cnt += local_blocks;
+            if (pair_seg.priv_stat) pair_seg.priv_stat += local_blocks;
 
             if (prof) HIP_TRY(hipEventRecord(ctx->ev[7], s));
-            HIP_TRY(launch_seg_pairs(a, seg, key32, percentage, part, n_parts, blocks, s));
+            // (part 0's plain label stores all land before the pair kernel's first union: stream order)
+            if (local_blocks) HIP_TRY(launch_seg_local(a, seg, percentage, local_blocks, s));
+            HIP_TRY(launch_seg_pairs(a, pair_seg, key32, percentage, part, n_parts, blocks, s));
             if (prof) HIP_TRY(hipEventRecord(ctx->ev[8], s));
             seg_timed = true;
             // what the blocks still hold in their private slots: one-way pairs only when the symmetric
             // ones were united where they were found, and then the collapse's flatten launch moves them
             // to the list (collapse_desc); else two small launches here, ahead of the list's unions
-            priv_blocks_for_collapse = seg.uf_parent && mode == MODE_DIRECTIONAL ? blocks : 0u;
+            priv_blocks_for_collapse = slots_to_collapse ? (uint32_t)slots : 0u;
             if (!priv_blocks_for_collapse) HIP_TRY(launch_seg_edge_append(a, seg, blocks, s));
             st.n_pair_launches += 1;
         }
@@ -1138,6 +1177,7 @@ class Pipeline {
         if (priv_blocks_for_collapse) {
             d.priv_edges = seg.priv_edges;
             d.priv_cnt = seg.priv_cnt;
+            d.priv_stat = seg.priv_stat;
             d.priv_blocks = priv_blocks_for_collapse;
         }
         return d;
@@ -1805,7 +1845,7 @@ void umi_ctx_destroy(umi_ctx *ctx)
     ctx->sh_out.release();
     DevBuf *bufs[] = {&ctx->tab_rows, &ctx->tab_items, &ctx->bs_tasks, &ctx->plane_tasks, &ctx->planes, &ctx->plan_tables, &ctx->fkey_sorted, &ctx->perm,
                       &ctx->seg_bin_cnt, &ctx->seg_bin_start, &ctx->seg_tasks,
-                      &ctx->seg_sub_rec, &ctx->seg_priv_edges, &ctx->seg_priv_dist, &ctx->seg_priv_cnt,
+                      &ctx->seg_sub_rec, &ctx->seg_priv_edges, &ctx->seg_priv_dist, &ctx->seg_priv_cnt, &ctx->seg_priv_stat,
                       &ctx->iota, &ctx->sort_tmp, &ctx->sample_pos, &ctx->sample_out,
                       &ctx->fkey,    &ctx->thr,      &ctx->label,    &ctx->lab,      &ctx->edges,    &ctx->ovf,
                       &ctx->edge_dist, &ctx->counters,
@@ -1894,6 +1934,11 @@ int umi_ctx_set_option(umi_ctx *ctx, const char *name, int64_t value)
         ctx->seg_unite = value != 0;
     } else if (!strcmp(name, "seg_lds")) {
         ctx->seg_lds = value != 0;
+    } else if (!strcmp(name, "seg_local")) {
+        ctx->seg_local = value != 0;
+    } else if (!strcmp(name, "seg_local_cap")) {
+        if (value < 2 || value > SEG_LOCAL_MAX_CAP) return fail(UMI_ERR_ARG, "seg_local_cap must be in 2..%u", SEG_LOCAL_MAX_CAP);
+        ctx->seg_local_cap = (uint32_t)value;
     } else if (!strcmp(name, "seg_blocks")) {
         if (value < 0 || value > (1 << 22)) return fail(UMI_ERR_ARG, "seg_blocks must be in 0..2^22");
         ctx->seg_blocks = (uint32_t)value;

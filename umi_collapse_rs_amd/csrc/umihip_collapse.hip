@@ -49,6 +49,7 @@ struct CollapseArgs {
     uint32_t *changed;       // [MAX_ROUNDS_PER_SYNC] round r moved a label
     const uint2 *priv_edges; // the pair kernel's private slots (may be null), priv_blocks of SEG_PRIV_CAP edges
     const uint32_t *priv_cnt;
+    const uint2 *priv_stat;  // (candidates, united pairs) of each slot's block, to the counters here (may be null)
     uint32_t priv_blocks;
 };
 
@@ -182,6 +183,16 @@ __device__ __forceinline__ void gather_private_edges(const CollapseArgs &a, uint
         }
         pre[threadIdx.x] = incl - c;
         if (threadIdx.x == 63) pre[GATHER_SLOTS] = incl;
+        if (a.priv_stat) { // the blocks' counts: two atomics per group instead of two per block
+            const uint2 st = s0 + threadIdx.x < s1 ? a.priv_stat[s0 + threadIdx.x] : make_uint2(0u, 0u);
+            unsigned long long cand = st.x, direct = st.y;
+            for (int o = 32; o > 0; o >>= 1) {
+                cand += __shfl_down(cand, o);
+                direct += __shfl_down(direct, o);
+            }
+            if (threadIdx.x == 0 && cand) atomicAdd(&a.counters[CNT_CANDIDATES], cand);
+            if (threadIdx.x == 0 && direct) atomicAdd(&a.counters[CNT_UF_DIRECT], direct);
+        }
     }
     __syncthreads();
     const unsigned long long first = a.counters[CNT_EDGES] + wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -275,6 +286,7 @@ CollapseArgs collapse_args(const CollapseDesc &d)
     a.changed = d.changed;
     a.priv_edges = d.priv_edges;
     a.priv_cnt = d.priv_cnt;
+    a.priv_stat = d.priv_stat;
     a.priv_blocks = d.priv_blocks;
     return a;
 }

@@ -241,6 +241,10 @@ struct SegArgs {
     uint2 *priv_edges;      // [n_blocks * SEG_PRIV_CAP]
     uint8_t *priv_dist;     // ... their distances (DataStruct mode), else null
     uint32_t *priv_cnt;     // [n_blocks] entries in each slot, then (after the scan) their offsets
+    // (candidates, symmetric pairs united) of each block, which the collapse's flatten launch adds to the
+    // counters when it gathers the slots (null: every block adds its own with two atomics at its end --
+    // ~90 per microsecond on one word, a queue when thousands of blocks end together)
+    uint2 *priv_stat;       // [n_blocks]
     // directional batched path: parent array of the union-find (= label[]).  A pair permitted in both
     // directions is united where it is found instead of going through the edge list (null: listed)
     uint32_t *uf_parent;
@@ -259,6 +263,9 @@ struct SegArgs {
     uint32_t use_ckey; // 32-bit keys: the pair kernel compares the records' compare keys (every part of
                        // every segment leaves at most 10 bases outside its bins)
     uint32_t col_sliced; // ... 64 columns at a time, bit-sliced (columns64_sliced), where k <= 3; 0: a broadcast per column
+    // part-0 sub-buckets of 2..local_cap entries are seg_local_kernel's (united in LDS, launched ahead of
+    // the pair kernel): the scan gives them no tile tasks.  0: every sub-bucket is the pair kernel's.
+    uint32_t local_cap;
 };
 // exclusive scan of the bin counts -> bin_start, task list, counters[CNT_SEG_TASKS / _PAIRS];
 // then every entry of a segment is copied to its position in each part's sub-bucket order
@@ -271,6 +278,16 @@ int seg_pair_blocks_per_cu(bool key32, bool has_n, bool ckey);
 hipError_t launch_seg_pairs(const PairArgs &a, const SegArgs &g, bool key32, float percentage,
                             uint32_t part, uint32_t n_parts, uint32_t n_blocks, hipStream_t s);
 hipError_t launch_seg_edge_append(const PairArgs &a, const SegArgs &g, uint32_t n_blocks, hipStream_t s);
+// The part-0 sub-buckets of at most g.local_cap entries (batched directional path, 32-bit compare keys):
+// every pair inside them evaluated by one wave out of LDS, the symmetric ones united in an LDS forest
+// that is written to g.uf_parent as root = smallest entry index of the set (depth <= 1), the one-way
+// ones left in the blocks' private slots (g.priv_edges / priv_cnt, n_blocks of them).  Must finish
+// before any kernel unites through g.uf_parent: a launch of its own, ahead of the pair kernel.
+constexpr uint32_t SEG_LOCAL_MAX_CAP = 2048;
+constexpr uint32_t SEG_LOCAL_CAP = 512; // default cap (LDS: 16 bytes per entry + the hit queue)
+size_t seg_local_lds_bytes(uint32_t cap);
+int seg_local_blocks_per_cu(bool has_n, uint32_t cap);
+hipError_t launch_seg_local(const PairArgs &a, const SegArgs &g, float percentage, uint32_t n_blocks, hipStream_t s);
 
 // ---- multi-word keys (umihip_wide.hip): umi_len 22..85, n_words = 2..4 words per key, entry-major
 // a.tasks: rows [row0, row0 + 64) x columns [col0, col1) of one bucket; exact distance from all words
@@ -374,6 +391,7 @@ struct CollapseDesc {
     // symmetric ones were united where they were found); the flatten launch appends them to the list
     const uint2 *priv_edges = nullptr; // [priv_blocks * SEG_PRIV_CAP]
     const uint32_t *priv_cnt = nullptr;
+    const uint2 *priv_stat = nullptr; // (candidates, united pairs) of each such block (null: counted already)
     uint32_t priv_blocks = 0;
 };
 // bytes (a multiple of 8) of the control block to its pinned, device-visible host mirror

@@ -22,7 +22,12 @@ namespace {
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_PER_THREAD = SEG_SCAN_CHUNK / SCAN_THREADS; // 16 bins per thread
 
-__device__ __forceinline__ uint32_t tasks_of_bin(uint32_t c) { return seg_tasks_of_bin(c); }
+// (a part-0 sub-bucket the local kernel takes has no tile tasks)
+__device__ __forceinline__ bool local_bin(const SegArgs &g, uint32_t part, uint32_t c) { return part == 0 && c <= g.local_cap; }
+__device__ __forceinline__ uint32_t tasks_of_bin(const SegArgs &g, uint32_t part, uint32_t c)
+{
+    return local_bin(g, part, c) ? 0u : seg_tasks_of_bin(c);
+}
 
 // Exclusive scan of the bin counts -> bin_start, the task list, the pair count: ONE launch, the
 // chunks chained by a decoupled look-back.  A block draws its chunk from a ticket counter (so that
@@ -52,7 +57,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void seg_scan_kernel(SegArgs g, unsig
         const uint32_t b = b_first + q;
         c[q] = b < ch.nbins ? g.bin_cnt[ch.bin0 + b] : 0u;
         mine.x += c[q];
-        mine.y += tasks_of_bin(c[q]);
+        mine.y += tasks_of_bin(g, ch.part, c[q]);
     }
     uint2 incl = mine;
     for (int d = 1; d < 64; d <<= 1) {
@@ -119,7 +124,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void seg_scan_kernel(SegArgs g, unsig
         if (b < ch.nbins) {
             g.bin_start[ch.bin0 + b] = off.x;
             g.bin_cnt[ch.bin0 + b] = 0;
-            const uint32_t nt = seg_chunks_of(c[q]), e = seg_span_log2(nt), span = 1u << e;
+            const uint32_t nt = local_bin(g, ch.part, c[q]) ? 0u : seg_chunks_of(c[q]), e = seg_span_log2(nt), span = 1u << e;
             const uint32_t where = ch.seg | (ch.part << 24) | (e << 28);
             uint32_t ti = off.y;
             for (uint32_t t = 0; t < nt; t++) {
@@ -555,6 +560,9 @@ __device__ __forceinline__ void uf_union_multi(uint32_t *parent, uint32_t (&u)[I
     uint32_t pu[ILP], pv[ILP];
     // (u < v.)  First a direct try, as in uf_union: v, if it is still the root it started as, goes
     // under u with one access; otherwise the swap has returned v's parent and the walk starts with it.
+    // (Behind seg_local_kernel about half the entries are children of depth-1 trees, and the try fails
+    // more often; loading u's parent in the same trip as the swap was measured there: 0.305 ms per
+    // config-2 step against 0.300 -- the extra load costs more than the trip it saves.)
     uint32_t seen[ILP];
 #pragma unroll
     for (int s = 0; s < ILP; s++) seen[s] = act[s] ? atomicCAS(&parent[v[s]], v[s], u[s]) : 0u;
@@ -825,9 +833,203 @@ __global__ __launch_bounds__(64) void seg_pair_kernel(PairArgs a, SegArgs g, flo
         if (lane == 0) g.priv_cnt[blockIdx.x] = left;
     }
     for (int off = 32; off > 0; off >>= 1) n_cand += __shfl_down(n_cand, off);
-    if (lane == 0 && n_cand) atomicAdd(&a.counters[CNT_CANDIDATES], (unsigned long long)n_cand);
     for (int off = 32; off > 0; off >>= 1) n_direct += __shfl_down(n_direct, off);
-    if (lane == 0 && n_direct) atomicAdd(&a.counters[CNT_UF_DIRECT], (unsigned long long)n_direct);
+    if (g.priv_stat) {
+        if (lane == 0) g.priv_stat[blockIdx.x] = make_uint2(n_cand, n_direct);
+    } else {
+        if (lane == 0 && n_cand) atomicAdd(&a.counters[CNT_CANDIDATES], (unsigned long long)n_cand);
+        if (lane == 0 && n_direct) atomicAdd(&a.counters[CNT_UF_DIRECT], (unsigned long long)n_direct);
+    }
+}
+
+// ---- part 0 in LDS ------------------------------------------------------------------------------
+// The k + 1 parts each partition a segment's entries, so every pair found in a part-0 sub-bucket joins
+// two entries of that sub-bucket: its symmetric pairs can be united in a forest local to the bin,
+// without a global atomic.  One wave per block, persistent, dealt whole part-0 bins statically (bin
+// ids in scan-chunk order: those of part 0 come first in a segment).  A bin's records go to LDS once
+// (structure of arrays: compare key, entry index, freq; the filter key is not needed -- part 0 has no
+// dedupe rule, and without N the compare keys give the distance); its upper triangle is walked with
+// the pair kernel's 64 x 64 tiles and hit queue; a symmetric pair is united in the LDS forest over
+// positions in the bin, a one-way pair goes to the block's private slot.  The bin's forest is then
+// written out canonically: label[idx] = the smallest entry index of idx's set, for every entry of the
+// bin, with plain stores -- depth <= 1, every root the minimum of its set, which is what the global
+// union keeps as well.  (The smallest position would not do: positions come from the scatter's atomics.)
+// Plain stores would race the pair kernel's compare-and-swaps on the same words: this kernel is a
+// launch of its own, and stream order puts all of it ahead of every global union.
+constexpr uint32_t LOCAL_DRAIN_AT = 64;
+constexpr uint32_t LOCAL_HITQ = LOCAL_DRAIN_AT + 64;
+
+__device__ __forceinline__ uint32_t lds_ld(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+// uf_union over positions in LDS (u < v; par[p] <= p)
+__device__ __forceinline__ void lds_union(uint32_t *par, uint32_t u, uint32_t v)
+{
+    const uint32_t seen = atomicCAS(&par[v], v, u);
+    if (seen == v || seen == u) return;
+    uint32_t pu = lds_ld(&par[u]), pv = seen;
+    while (pu != pv) {
+        if (pu < pv) {
+            uint32_t t = u; u = v; v = t;
+            t = pu; pu = pv; pv = t;
+        }
+        if (u == pu) {
+            const uint32_t old = atomicCAS(&par[u], u, pv);
+            if (old == u) return;
+            pu = old;
+        } else {
+            u = pu;
+            pu = lds_ld(&par[u]);
+        }
+    }
+}
+
+template <bool HAS_N>
+__global__ __launch_bounds__(64) void seg_local_kernel(PairArgs a, SegArgs g, float percentage)
+{
+    extern __shared__ uint32_t lds[];
+    const uint32_t cap = g.local_cap;
+    uint32_t *ck = lds, *ix = lds + cap, *fr = lds + 2 * cap, *par = lds + 3 * cap;
+    uint32_t *hitq = lds + 4 * cap; // row position | column position << 16
+    const int lane = threadIdx.x;
+    const SegRec32 *__restrict__ sub = (const SegRec32 *)g.sub_rec;
+    const bool sliced = a.k <= 3 && g.col_sliced != 0;
+    const uint32_t lim2 = (uint32_t)__builtin_amdgcn_readfirstlane(2 * a.k);
+    unsigned int n_cand = 0, n_direct = 0;
+    // one-way pairs: to this block's private slot, wave-uniform fill level; a slot that is full sends
+    // the rest to the list, one atomic per wave and batch
+    uint32_t n_out = 0;
+    uint2 *__restrict__ slot = g.priv_edges + (size_t)blockIdx.x * SEG_PRIV_CAP;
+    auto emit = [&](bool has, uint32_t u, uint32_t v) {
+        const unsigned long long bal = __ballot(has);
+        if (!bal) return;
+        const uint32_t cnt = (uint32_t)__builtin_popcountll(bal);
+        const uint32_t pos = n_out + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1ull));
+        unsigned long long base = 0;
+        if (n_out + cnt > SEG_PRIV_CAP) {
+            const uint32_t first_over = max(n_out, SEG_PRIV_CAP);
+            const int leader = __builtin_ctzll(bal);
+            if (lane == leader) base = atomicAdd(&a.counters[CNT_EDGES], (unsigned long long)(n_out + cnt - first_over));
+            base = __shfl(base, leader);
+            base -= first_over;
+        }
+        if (has) {
+            if (pos < SEG_PRIV_CAP) slot[pos] = make_uint2(u, v);
+            else if (base + pos < a.edge_cap) a.edges[base + pos] = make_uint2(u, v);
+        }
+        n_out += cnt;
+    };
+    uint32_t nq = 0;
+    auto drain = [&]() {
+        __syncthreads();
+        for (uint32_t q0 = 0; q0 < nq; q0 += 64) {
+            const uint32_t q = q0 + (uint32_t)lane;
+            const bool live = q < nq;
+            const uint32_t h = live ? hitq[q] : 0u;
+            const uint32_t pa = h & 0xFFFFu, pb = h >> 16;
+            const uint32_t ia = ix[pa], ib = ix[pb];
+            const int32_t fa = (int32_t)fr[pa], fb = (int32_t)fr[pb];
+            // entry indices in rank order (src/algo/directional.rs:67-72)
+            const bool sw = ib < ia;
+            const uint32_t gi = sw ? ib : ia, gj = sw ? ia : ib;
+            const int32_t fi = sw ? fb : fa, fj = sw ? fa : fb;
+            int dist = 0;
+            if (live) {
+                if (HAS_N) { // bitset.rs:85-87 (one word) and utils/mod.rs:25
+                    const uint64_t ka = a.keys[gi], kb = a.keys[gj];
+                    const uint64_t xn = a.nmask[gi] ^ a.nmask[gj];
+                    dist = (__builtin_popcountll(xn | (ka ^ kb)) - __builtin_popcountll(xn) / 3) / 2;
+                } else { // no N in the call: the bases outside the bin differ in two code bits each
+                    dist = __builtin_popcount(ck[pa] ^ ck[pb]) / 2;
+                }
+                n_cand++;
+            }
+            const bool near = live && dist <= a.k;
+            // naive.rs:31 under directional.rs:38-39
+            const bool fwd = near && fj <= threshold_of(percentage, fi);
+            const bool bwd = near && fi <= threshold_of(percentage, fj);
+            if (fwd && bwd) { // reachability inside such a set is symmetric: one set
+                n_direct++;
+                lds_union(par, min(pa, pb), max(pa, pb));
+            }
+            emit(fwd != bwd, fwd ? gi : gj, fwd ? gj : gi);
+        }
+        nq = 0;
+        __syncthreads();
+    };
+
+    const uint32_t n_ids = g.n_chunks * SEG_SCAN_CHUNK;
+    for (uint32_t id = blockIdx.x; id < n_ids; id += gridDim.x) {
+        const SegScanChunk ch = g.chunks[id / SEG_SCAN_CHUNK];
+        const uint32_t bi = id % SEG_SCAN_CHUNK;
+        if (ch.part != 0 || bi >= ch.nbins) continue;
+        const uint32_t b = ch.bin0 + bi;
+        const uint32_t c = __builtin_amdgcn_readfirstlane(g.bin_cnt[b]); // (the scatter's cursor: the count again)
+        if (c < 2 || c > cap) continue;
+        const uint32_t start = __builtin_amdgcn_readfirstlane(g.bin_start[b]);
+        const int ck_bases = __builtin_amdgcn_readfirstlane(g.umi_len - (int)g.segs[ch.seg].nb[0]);
+        for (uint32_t p = lane; p < c; p += 64) {
+            const SegRec32 r = sub[start + p];
+            ck[p] = r.ckey;
+            ix[p] = r.idx;
+            fr[p] = (uint32_t)r.freq;
+            par[p] = p;
+        }
+        __syncthreads();
+        // the upper triangle: 64-row chunks against the columns behind their first row
+        for (uint32_t row0 = 0; row0 < c; row0 += 64) {
+            const uint32_t r = row0 + (uint32_t)lane;
+            const uint32_t n_rows = min(64u, c - row0);
+            const uint32_t x = r < c ? ck[r] : pad_row<uint32_t>();
+            for (uint32_t c0 = row0 + 1; c0 < c; c0 += 64) {
+                const uint32_t ky = c0 + (uint32_t)lane < c ? ck[c0 + lane] : pad_col<uint32_t>();
+                const uint32_t nc = min(64u, c - c0);
+                unsigned long long h; // bit j: this lane's row is within k of column j of the tile
+                if (sliced) {
+                    h = columns64_sliced_k(x, ky, a.k, ck_bases);
+                } else {
+                    uint32_t hlo = 0, hhi = 0;
+                    hlo = columns32<true, 0>(x, ky, a.k, lim2);
+                    if (nc > 32) hhi = columns32<true, 32>(x, ky, a.k, lim2);
+                    h = ((unsigned long long)hhi << 32) | hlo;
+                }
+                const int j_min = lane + 1 - (int)(c0 - row0);
+                if (nc < 64) h &= (1ull << nc) - 1ull;
+                if (j_min > 0) h = j_min >= 64 ? 0ull : h & ~((1ull << j_min) - 1ull);
+                if ((uint32_t)lane >= n_rows) h = 0ull;
+                while (__any(h != 0ull)) { // one hit per lane and round
+                    const unsigned long long bal = __ballot(h != 0ull);
+                    if (h) {
+                        const int j = __builtin_ctzll(h);
+                        h &= h - 1ull;
+                        hitq[nq + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1ull))] = r | ((c0 + (uint32_t)j) << 16);
+                    }
+                    nq += (uint32_t)__builtin_popcountll(bal);
+                    if (nq >= LOCAL_DRAIN_AT) drain();
+                }
+            }
+        }
+        if (nq) drain();
+        // the bin's sets out: root position of every entry (into ck[], free now), the smallest entry
+        // index of every set (fr[] of its root), label[] of every entry
+        for (uint32_t p = lane; p < c; p += 64) {
+            uint32_t q = lds_ld(&par[p]);
+            for (;;) {
+                const uint32_t up = lds_ld(&par[q]);
+                if (up == q) break;
+                q = up;
+            }
+            ck[p] = q;
+            fr[p] = 0xFFFFFFFFu;
+        }
+        __syncthreads();
+        for (uint32_t p = lane; p < c; p += 64) atomicMin(&fr[ck[p]], ix[p]);
+        __syncthreads();
+        for (uint32_t p = lane; p < c; p += 64) g.uf_parent[ix[p]] = fr[ck[p]];
+        __syncthreads(); // (the next bin's records overwrite these arrays)
+    }
+    if (lane == 0) g.priv_cnt[blockIdx.x] = min(n_out, SEG_PRIV_CAP);
+    for (int off = 32; off > 0; off >>= 1) n_cand += __shfl_down(n_cand, off);
+    for (int off = 32; off > 0; off >>= 1) n_direct += __shfl_down(n_direct, off);
+    if (lane == 0) g.priv_stat[blockIdx.x] = make_uint2(n_cand, n_direct); // (the flatten launch adds them up)
 }
 
 // offsets of the blocks' slots behind what the list holds already (one block), the new total
@@ -945,6 +1147,27 @@ hipError_t launch_seg_pairs(const PairArgs &a, const SegArgs &g, bool key32, flo
         }
 #undef UMI_SEG_WIDE
     }
+    return hipGetLastError();
+}
+
+size_t seg_local_lds_bytes(uint32_t cap) { return ((size_t)4 * cap + LOCAL_HITQ) * sizeof(uint32_t); }
+
+int seg_local_blocks_per_cu(bool has_n, uint32_t cap)
+{
+    int nb = 0;
+    const hipError_t e = has_n ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, seg_local_kernel<true>, 64, seg_local_lds_bytes(cap))
+                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, seg_local_kernel<false>, 64, seg_local_lds_bytes(cap));
+    return e == hipSuccess && nb > 0 ? nb : 8;
+}
+
+hipError_t launch_seg_local(const PairArgs &a, const SegArgs &g, float percentage, uint32_t n_blocks, hipStream_t s)
+{
+    if (g.n_chunks == 0 || n_blocks == 0 || g.local_cap == 0) return hipSuccess;
+    if (g.local_cap > SEG_LOCAL_MAX_CAP || !g.uf_parent || !g.priv_stat || !g.use_ckey || a.mode != MODE_DIRECTIONAL)
+        return hipErrorInvalidValue;
+    const size_t lds = seg_local_lds_bytes(g.local_cap);
+    if (a.nmask) seg_local_kernel<true><<<n_blocks, 64, lds, s>>>(a, g, percentage);
+    else seg_local_kernel<false><<<n_blocks, 64, lds, s>>>(a, g, percentage);
     return hipGetLastError();
 }
 
