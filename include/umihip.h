@@ -232,6 +232,35 @@ int umi_stage_reads_wide(umi_ctx *ctx, const uint64_t *align_key, int align_key_
                          uint64_t *nmask, int32_t *freq, uint64_t *rep, uint64_t *bucket_off, uint64_t *n_entries,
                          uint64_t *n_buckets);
 
+/* ---- read staging of whole reads (FASTQ mode): the staging of run_fastq on the device.
+ * in : read i is len[i] bases at text + seq_pos[i]; its quality, as long, at text + qual_pos[i]
+ *      (qual_pos may be NULL with merge 0), so one buffer may hold the whole FASTQ file.
+ *      merge: 0 = the first read represents a sequence (any), 1 = the read of the highest average
+ *      quality, (int)(sum(q - 33) as f32 / len as f32), the first on ties.
+ * out: the input of umi_dedup_seqs: buckets are read lengths in order of first appearance, entries
+ *      of a bucket by freq descending, first appearance on ties; keys / nmask (may be NULL) n_words
+ *      words per entry, zero behind the read's own ceil(3L/64); freq; rep = file index of the
+ *      representative read; entry_of_read[i] (may be NULL) = read i's entry.  Capacity n_reads.
+ *      bucket_off [*n_buckets + 1] and bucket_len [*n_buckets] are HOST arrays in both forms (at most
+ *      UMI_MAX_SEQ_LEN + 1 lengths); *any_n = whether any N occurred (else nmask is all zero and
+ *      umi_dedup_seqs may take NULL for it).
+ * UMI_ERR_ARG: n_reads >= 2^30, a read over UMI_MAX_SEQ_LEN bases, n_words outside 1..12 or below
+ * what the longest read needs, merge 1 without qualities.  UMI_ERR_CHAR: a byte outside ATCGN;
+ * umi_last_error() names the smallest such read and its first bad byte:
+ * "Unknown character in sequence: <byte> (read <index>)".
+ * The _device form takes and leaves the per-read and per-entry arrays in device memory (it
+ * synchronises the stream); the plain form copies host arrays in and out around it. */
+int umi_stage_seqs_device(umi_ctx *ctx, const uint8_t *d_text, const uint64_t *d_seq_pos,
+                          const uint64_t *d_qual_pos, const uint32_t *d_len, uint64_t n_reads, int n_words,
+                          int merge, uint64_t *d_keys, uint64_t *d_nmask, int32_t *d_freq, uint64_t *d_rep,
+                          uint32_t *d_entry_of_read, uint64_t *bucket_off, int32_t *bucket_len,
+                          uint64_t *n_entries, uint64_t *n_buckets, int *any_n, void *hip_stream);
+int umi_stage_seqs(umi_ctx *ctx, const uint8_t *text, const uint64_t *seq_pos, const uint64_t *qual_pos,
+                   const uint32_t *len, uint64_t n_reads, int n_words, int merge, uint64_t *keys,
+                   uint64_t *nmask, int32_t *freq, uint64_t *rep, uint32_t *entry_of_read,
+                   uint64_t *bucket_off, int32_t *bucket_len, uint64_t *n_entries, uint64_t *n_buckets,
+                   int *any_n);
+
 /* ---- batched path: replaces the whole bucket loop
  *      src/deduplicate_sam.rs:207-233 (apply::<UcSAMRead,Naive> per bucket,
  *      counters :217-219) = Directional/Adjacency::apply

@@ -1,6 +1,7 @@
 """Fastq mode's long-key path on shapes F1-F3: umi_dedup_seqs timed with device events (call and pair
-kernel), pairs evaluated against W = sum n(n-1)/2, and the umicollapse CLI end to end with its phase
-split.  One JSON line per shape and measurement on stdout.
+kernel), pairs evaluated against W = sum n(n-1)/2, umi_stage_seqs_device on resident data timed with
+device events, and the umicollapse CLI end to end with its phase split, --stage host and --stage gpu
+alternating.  One JSON line per shape and measurement on stdout.
 
   F1: 1 M reads, 150 bp, ~300 k molecules, 0.5 % substitutions, k = 1
   F2: F1 with the last 75 bases constant (one heavy bin: part 1 is shared by most of the bucket)
@@ -43,6 +44,39 @@ def stage(seqs):
     return ent, off, blen
 
 
+def stage_leg(ctx, name, seqs, quals, reps):
+    """umi_stage_seqs_device (merge avgqual, entry_of_read on) on data already on the device, timed with
+    device events around the call (which synchronises inside)"""
+    import torch
+    n = len(seqs)
+    lens = np.array([len(s) for s in seqs], np.uint32)
+    pos = np.zeros(n, np.uint64)
+    pos[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    pos = np.concatenate([pos, pos + np.uint64(int(lens.sum()))])
+    w = max(1, (3 * int(lens.max()) + 63) // 64)
+    dev = torch.device("cuda", 0)
+    d_text = torch.from_numpy(np.frombuffer(b"".join(seqs) + b"".join(quals), np.uint8).copy()).to(dev)
+    d_pos = torch.from_numpy(pos.view(np.int64)).to(dev)
+    d_len = torch.from_numpy(lens.view(np.int32)).to(dev)
+    d_keys, d_nm = (torch.empty(n * w, dtype=torch.int64, device=dev) for _ in range(2))
+    d_freq, d_eor = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+    d_rep = torch.empty(n, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()
+    ms = []
+    for r in range(reps + 1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _, blen, ne, any_n = ctx.stage_seqs_device(d_text.data_ptr(), d_pos.data_ptr(), d_pos.data_ptr() + 8 * n,
+                                                   d_len.data_ptr(), n, w, d_keys.data_ptr(), d_nm.data_ptr(),
+                                                   d_freq.data_ptr(), d_rep.data_ptr(), d_eor.data_ptr(), merge=1)
+        e1.record()
+        torch.cuda.synchronize()
+        if r:  # (the first call grows the workspace)
+            ms.append(e0.elapsed_time(e1))
+    return {"shape": name, "what": "umi_stage_seqs_device", "reads": n, "n_words": w, "entries": ne,
+            "buckets": len(blen), "any_n": any_n, "ms_median": float(np.median(ms)), "ms_min": float(np.min(ms))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="F1,F2,F3")
@@ -79,23 +113,25 @@ def main():
             "ms_kernel_median": float(np.median([x[1]["ms_kernel"] for x in runs])),
             "ms_collapse_median": float(np.median([x[1]["ms_collapse"] for x in runs])),
             "kernel_id": int(st["kernel_id"]), "gen_s": round(gen_s, 1)}), flush=True)
+        print(json.dumps(stage_leg(ctx, name, seqs, quals, a.reps)), flush=True)
         path = os.path.join(out, name + ".fq")
         with open(path, "wb") as f:
             f.write(synth.fastq_text(seqs, quals))
         for r in range(3):
-            t = time.perf_counter()
-            p = subprocess.run([CLI, "-m", "fastq", "-i", path, "-o", os.path.join(out, name + ".out.fq"), "-k", "1"],
-                               capture_output=True, text=True, timeout=600)
-            wall = time.perf_counter() - t
-            if p.returncode != 0:
-                print(p.stderr, file=sys.stderr)
-                sys.exit(p.returncode)
-        m = re.search(r"phases: read\+parse ([0-9.]+) s, staging \(host\) ([0-9.]+) s, gpu init ([0-9.]+) s, "
-                      r"hot path \(H2D\+GPU\+D2H\) ([0-9.]+) s .*write ([0-9.]+) s", p.stderr)
-        print(json.dumps({"shape": name, "what": "cli", "wall_s": round(wall, 3),
-                          "read_parse_s": float(m.group(1)), "staging_s": float(m.group(2)),
-                          "gpu_init_s": float(m.group(3)), "gpu_call_s": float(m.group(4)),
-                          "write_s": float(m.group(5))}), flush=True)
+            for side in ("host", "gpu"):  # (alternating: the two sides see the same machine state)
+                t = time.perf_counter()
+                p = subprocess.run([CLI, "-m", "fastq", "-i", path, "-o", os.path.join(out, name + ".out.fq"), "-k", "1",
+                                    "--stage", side], capture_output=True, text=True, timeout=600)
+                wall = time.perf_counter() - t
+                if p.returncode != 0:
+                    print(p.stderr, file=sys.stderr)
+                    sys.exit(p.returncode)
+                m = re.search(r"phases: read\+parse ([0-9.]+) s, staging \((host|gpu)\) ([0-9.]+) s, gpu init ([0-9.]+) s, "
+                              r"hot path \(H2D\+GPU\+D2H\) ([0-9.]+) s .*write ([0-9.]+) s", p.stderr)
+                print(json.dumps({"shape": name, "what": "cli", "stage": m.group(2), "run": r, "wall_s": round(wall, 3),
+                                  "read_parse_s": float(m.group(1)), "staging_s": float(m.group(3)),
+                                  "gpu_init_s": float(m.group(4)), "gpu_call_s": float(m.group(5)),
+                                  "write_s": float(m.group(6))}), flush=True)
     ctx.close()
 
 

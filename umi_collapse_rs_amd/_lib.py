@@ -63,6 +63,11 @@ SIGNATURES = {
                                               C.c_void_p, _u64p, _u64p, C.c_void_p]),
     "umi_stage_reads_wide": (C.c_int, [C.c_void_p, _u64p, C.c_int, _u8p, _i32p, C.c_uint64, C.c_int, C.c_int, C.c_int,
                                        _u64p, _u64p, _i32p, _u64p, _u64p, _u64p, _u64p]),
+    "umi_stage_seqs_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
+                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p,
+                                        _i32p, _u64p, _u64p, C.POINTER(C.c_int), C.c_void_p]),
+    "umi_stage_seqs": (C.c_int, [C.c_void_p, _u8p, _u64p, _u64p, _u32p, C.c_uint64, C.c_int, C.c_int, _u64p, _u64p,
+                                 _i32p, _u64p, _u32p, _u64p, _i32p, _u64p, _u64p, C.POINTER(C.c_int)]),
     "umi_encode_seqs": (C.c_int, [_u8p, _u64p, C.c_uint64, C.c_int, _u64p, _u64p]),
     "umi_dedup_seqs": (C.c_int, [C.c_void_p, _u64p, _u64p, C.c_int, _i32p, _u64p, _i32p, C.c_uint64, C.c_int,
                                  C.c_float, C.c_int, C.c_int32, _u8p, _u32p, C.POINTER(Stats)]),

@@ -172,6 +172,56 @@ class Context:
                                     C.byref(st)))
         return kept[:n], (root[:n] if want_root else None), st.as_dict()
 
+    def stage_seqs(self, seqs, quals=None, merge=1, n_words=None):
+        """Staging of whole reads on the device (umi_stage_seqs): lists of bytes (reads, and their
+        qualities for merge 1) in file order -> dict(keys, nmask [n_entries, n_words], freq, rep,
+        entry_of_read, bucket_off, bucket_len, any_n), the input of dedup_seqs.  n_words =
+        ceil(3 * longest / 64) unless given."""
+        bs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        n = len(bs)
+        if quals is not None:
+            qs = [q.encode() if isinstance(q, str) else bytes(q) for q in quals]
+            if len(qs) != n or any(len(a) != len(b) for a, b in zip(bs, qs)):
+                raise ValueError("quals must match seqs read by read")
+        elif merge:
+            raise ValueError("merge 1 needs quals")
+        lens = np.array([len(b) for b in bs], dtype=np.uint32)
+        if n_words is None:
+            n_words = max(1, (3 * int(lens.max() if n else 0) + 63) // 64)
+        text = b"".join(bs) + (b"".join(qs) if quals is not None else b"")
+        seq_pos = np.zeros(n, dtype=np.uint64)
+        if n:
+            seq_pos[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+        qual_pos = seq_pos + np.uint64(sum(map(len, bs))) if quals is not None else None
+        buf = np.frombuffer(text or b"\0", dtype=np.uint8)
+        m = max(1, n)
+        keys, nm = np.zeros((m, n_words), np.uint64), np.zeros((m, n_words), np.uint64)
+        freq, rep, eor = np.zeros(m, np.int32), np.zeros(m, np.uint64), np.zeros(m, np.uint32)
+        boff, blen = np.zeros(m + 1, np.uint64), np.zeros(m, np.int32)
+        ne, nb, any_n = C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+        check(load().umi_stage_seqs(self._h, ptr(buf, C.c_uint8), ptr(seq_pos, C.c_uint64), ptr(qual_pos, C.c_uint64),
+                                    ptr(lens, C.c_uint32), n, n_words, merge, ptr(keys, C.c_uint64), ptr(nm, C.c_uint64),
+                                    ptr(freq, C.c_int32), ptr(rep, C.c_uint64), ptr(eor, C.c_uint32),
+                                    ptr(boff, C.c_uint64), ptr(blen, C.c_int32), C.byref(ne), C.byref(nb),
+                                    C.byref(any_n)))
+        e, b = int(ne.value), int(nb.value)
+        return dict(keys=keys[:e], nmask=nm[:e], freq=freq[:e], rep=rep[:e], entry_of_read=eor[:n],
+                    bucket_off=boff[:b + 1], bucket_len=blen[:b], any_n=bool(any_n.value))
+
+    def stage_seqs_device(self, d_text, d_seq_pos, d_qual_pos, d_len, n_reads, n_words, d_keys, d_nmask, d_freq,
+                          d_rep, d_entry_of_read=0, merge=1, stream=0):
+        """The same with the per-read and per-entry arrays in device memory (raw pointers); returns
+        (bucket_off, bucket_len, n_entries, any_n), the bucket table on the host."""
+        m = max(1, min(int(n_reads), 257))
+        boff, blen = np.zeros(m + 1, np.uint64), np.zeros(m, np.int32)
+        ne, nb, any_n = C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+        check(load().umi_stage_seqs_device(self._h, d_text, d_seq_pos, d_qual_pos or None, d_len, n_reads, n_words,
+                                           merge, d_keys, d_nmask or None, d_freq, d_rep, d_entry_of_read or None,
+                                           ptr(boff, C.c_uint64), ptr(blen, C.c_int32), C.byref(ne), C.byref(nb),
+                                           C.byref(any_n), stream or None))
+        b = int(nb.value)
+        return boff[:b + 1], blen[:b], int(ne.value), bool(any_n.value)
+
     def stage_reads(self, align_key, umi_bytes, score, umi_len, merge=1, align_key_bits=64):
         """Read staging on the device (host arrays in and out): reads in file order ->
         dict(keys, nmask, freq, rep, bucket_off) in canonical order, the batched path's input

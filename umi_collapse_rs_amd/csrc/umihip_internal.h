@@ -342,6 +342,21 @@ int stage_reads_on_device(void *workspace, const uint64_t *d_align, int align_bi
                           uint64_t *n_entries_out, uint64_t *n_buckets_out, unsigned long long *h_pinned4,
                           hipStream_t s);
 
+// whole reads (umi_stage_seqs): read i is len[i] bases at text + seq_pos[i], its quality at text +
+// qual_pos[i] (may be null with merge 0); keys / nmask (may be null): n_words words per entry.  The
+// bucket table (bucket_off [n_buckets + 1], bucket_len [n_buckets]) comes back to the host; eor (may be
+// null): every read's entry.  0 ok; 1 a character outside ATCGN (fault: read, byte); 2 a read longer
+// than UMI_MAX_SEQ_LEN, 3 longer than n_words hold (fault: value = the longest); negative: -(hipError_t)
+struct SeqFault {
+    uint64_t read = 0, value = 0;
+};
+size_t stage_seqs_workspace_bytes(uint32_t n_reads, int n_words);
+int stage_seqs_on_device(void *workspace, const uint8_t *d_text, const uint64_t *d_seq_pos, const uint64_t *d_qual_pos,
+                         const uint32_t *d_len, uint32_t n, int n_words, int merge, uint64_t *d_keys, uint64_t *d_nmask,
+                         int32_t *d_freq, uint64_t *d_rep, uint32_t *d_eor, uint64_t *h_bucket_off, int32_t *h_bucket_len,
+                         uint64_t *n_entries_out, uint64_t *n_buckets_out, int *any_n, SeqFault *fault,
+                         unsigned long long *h_pinned4, hipStream_t s);
+
 // ---- sort and scan primitives of the staging (umihip_radix.hip) ----
 constexpr int RADIX_BINS = 256, RADIX_MAX_PASSES = 8; // 8-bit digits; a 64-bit key has at most eight
 constexpr int RADIX_HIST_PARTS = 2048;                // blocks of a kernel that counts digits, at most

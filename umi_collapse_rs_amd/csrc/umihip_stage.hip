@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "../../include/umihip.h"
 #include "umihip_internal.h"
 
 namespace umihip {
@@ -598,7 +599,7 @@ __global__ __launch_bounds__(256) void stage_emit_kernel(const uint32_t *__restr
                                                          const unsigned long long *__restrict__ best,
                                                          uint64_t *__restrict__ keys, uint64_t *__restrict__ nmask,
                                                          int32_t *__restrict__ freq, uint64_t *__restrict__ rep,
-                                                         uint64_t *__restrict__ bucket_off)
+                                                         uint64_t *__restrict__ bucket_off, uint32_t *__restrict__ slot)
 {
     const uint32_t n_round = (n_entries + 63u) & ~63u; // (whole waves: the neighbour's rank comes by DPP)
     for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n_round; j += gridDim.x * blockDim.x) {
@@ -648,6 +649,7 @@ __global__ __launch_bounds__(256) void stage_emit_kernel(const uint32_t *__restr
         freq[j] = (int32_t)f;
         rep[j] = merge ? (uint64_t)(0xFFFFFFFFu - (uint32_t)best[e]) : (uint64_t)first;
         if (j == 0 || br_before != br) bucket_off[br] = j;
+        if (slot) slot[e] = j;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) bucket_off[n_buckets] = n_entries;
 }
@@ -682,7 +684,7 @@ __global__ __launch_bounds__(256) void stage_emit_local_kernel(const uint32_t *_
                                                                const unsigned long long *__restrict__ best,
                                                                uint64_t *__restrict__ keys, uint64_t *__restrict__ nmask,
                                                                int32_t *__restrict__ freq, uint64_t *__restrict__ rep,
-                                                               uint64_t *__restrict__ bucket_off)
+                                                               uint64_t *__restrict__ bucket_off, uint32_t *__restrict__ slot)
 {
     constexpr bool NARROW = sizeof(OrdT) == 4;
     constexpr uint32_t PER_READ = 16 / sizeof(OrdT); // keys per 16-byte LDS read
@@ -761,10 +763,166 @@ __global__ __launch_bounds__(256) void stage_emit_local_kernel(const uint32_t *_
             }
             freq[out] = (int32_t)(fmax - (uint32_t)(NARROW ? (uint64_t)k >> first_bits : (uint64_t)k >> 32));
             rep[out] = merge ? (uint64_t)(0xFFFFFFFFu - (uint32_t)best[e]) : (uint64_t)((uint32_t)k & first_mask);
+            if (slot) slot[e] = (uint32_t)out;
         }
         __builtin_amdgcn_wave_barrier();
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) bucket_off[n_buckets] = n_entries;
+}
+
+// ---- 4. whole reads (fastq mode): the kernels of their own -------------------------------------------
+// what the encode leaves for the host: the first bad byte (read << 9 | position, a minimum), whether
+// any N occurred, the longest read, and per key word (slot SI_LEN: the length) the OR and the AND of
+// that word over all reads -- a bit where they differ takes a sort pass
+constexpr int SI_SLOTS = 13, SI_LEN = 12;
+enum SeqInfo : int { SI_BAD = 0, SI_ANY_N = 1, SI_MAXLEN = 2, SI_OR = 3, SI_AND = SI_OR + SI_SLOTS, SI_COUNT = SI_AND + SI_SLOTS };
+
+// the four bytes at [at, at + 4), bytes from `end` on replaced by those of `pad`: only aligned words
+// that hold a byte of [at, end) are loaded (memory is mapped in whole pages, so none of them faults)
+__device__ __forceinline__ uint32_t load4(const uint8_t *p, uint64_t at, uint64_t end, uint32_t pad)
+{
+    const uintptr_t addr = (uintptr_t)(p + at), a = addr & ~(uintptr_t)3;
+    const int sh = (int)(addr & 3);
+    const uint32_t lo = *(const uint32_t *)a;
+    uint32_t w = lo;
+    if (sh) {
+        const uint32_t hi = a + 4 < (uintptr_t)(p + end) ? *(const uint32_t *)(a + 4) : 0u;
+        w = (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * sh));
+    }
+    const uint64_t have = end - at;
+    if (have < 4) {
+        const uint32_t keep = (1u << (8 * have)) - 1u;
+        w = (w & keep) | (pad & ~keep);
+    }
+    return w;
+}
+
+// One wave per read: lane l takes bases 4l .. 4l+3 (a read has at most 256), encodes them (encode4),
+// and lane t < W gathers word t of the key from the lanes whose twelve bits fall in it (a base may
+// straddle two words, bitset.rs:52-75).  Bytes are checked as they are encoded.  score (may be null):
+// the average quality, sum(q - 33) / len truncated (the f32 quotient of fastq::avg_qual, which equals
+// the integer one for len <= 256: a quotient that is no integer lies >= 1/256 from one).
+template <int W>
+__global__ __launch_bounds__(256) void seq_encode_kernel(const uint8_t *__restrict__ text, const uint64_t *__restrict__ seq_pos,
+                                                         const uint64_t *__restrict__ qual_pos, const uint32_t *__restrict__ len,
+                                                         uint32_t n, uint64_t *__restrict__ k3, uint32_t *__restrict__ idx,
+                                                         uint64_t *__restrict__ len64, int32_t *__restrict__ score,
+                                                         unsigned long long *__restrict__ info)
+{
+    __shared__ unsigned long long s_or[SI_SLOTS], s_and[SI_SLOTS];
+    const int lane = threadIdx.x & 63;
+    if (threadIdx.x < SI_SLOTS) {
+        s_or[threadIdx.x] = 0;
+        s_and[threadIdx.x] = ~0ull;
+    }
+    __syncthreads();
+    const int slot = lane < W ? lane : lane == 63 ? SI_LEN : -1; // (lane 63: the length)
+    unsigned long long acc_or = 0, acc_and = ~0ull;
+    uint32_t has_n = 0, max_len = 0;
+    const int first_src = (64 * lane) / 12; // the lowest lane whose bits reach word `lane`
+    for (uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += gridDim.x * 4) {
+        const uint32_t L = len[r], Lc = min(L, 256u);
+        const uint32_t b0 = 4u * lane;
+        uint32_t word = 0x41414141u; // ('A': code 0, behind the read's end)
+        uint32_t bad = 0;
+        if (b0 < Lc) {
+            const uint64_t sp = seq_pos[r];
+            word = load4(text, sp + b0, sp + Lc, 0x41414141u);
+        }
+        const uint32_t twelve = encode4(word, &bad);
+        const uint32_t vn = word ^ 0x4E4E4E4Eu; // a zero byte where the base is N
+        has_n |= (vn - 0x01010101u) & ~vn & 0x80808080u;
+        const unsigned long long bad_lanes = __ballot(bad != 0);
+        if (bad_lanes) {
+            const int fl = __builtin_ctzll(bad_lanes);
+            if (lane == fl)
+                atomicMin(&info[SI_BAD], ((unsigned long long)r << 9) | (unsigned long long)(b0 + __builtin_ctz(bad) / 8));
+        }
+        uint64_t key = 0;
+#pragma unroll
+        for (int j = 0; j < 7; j++) {
+            const int src = first_src + j;
+            const uint64_t v = (uint32_t)__shfl((int)twelve, src & 63);
+            const int d = 12 * src - 64 * lane;
+            if (src < 64) key |= d >= 0 ? (d < 64 ? v << d : 0ull) : v >> (-d);
+        }
+        if (lane < W) k3[(size_t)r * W + lane] = key;
+        const uint64_t mine = lane == 63 ? (uint64_t)L : key;
+        acc_or |= mine;
+        acc_and &= mine;
+        if (score && qual_pos) { // (both or neither, wave-uniform)
+            uint32_t qs = 0;
+            if (b0 < Lc) {
+                const uint64_t qp = qual_pos[r];
+                const uint32_t qw = load4(text, qp + b0, qp + Lc, 0u);
+                qs = (qw & 0xFFu) + ((qw >> 8) & 0xFFu) + ((qw >> 16) & 0xFFu) + (qw >> 24);
+            }
+            for (int off = 32; off > 0; off >>= 1) qs += (uint32_t)__shfl_xor((int)qs, off);
+            if (lane == 0) score[r] = L ? ((int32_t)qs - 33 * (int32_t)Lc) / (int32_t)Lc : 0;
+        }
+        if (lane == 0) {
+            idx[r] = r;
+            len64[r] = L;
+            max_len = max(max_len, L);
+        }
+    }
+    if (slot >= 0) {
+        atomicOr(&s_or[slot], acc_or);
+        atomicAnd(&s_and[slot], acc_and);
+    }
+    if (__any(has_n != 0) && lane == 0) atomicOr(&info[SI_ANY_N], 1ull);
+    if (lane == 0 && max_len) atomicMax(&info[SI_MAXLEN], (unsigned long long)max_len);
+    __syncthreads();
+    if (threadIdx.x < SI_SLOTS) {
+        atomicOr(&info[SI_OR + threadIdx.x], s_or[threadIdx.x]);
+        atomicAnd(&info[SI_AND + threadIdx.x], s_and[threadIdx.x]);
+    }
+}
+
+// nmask of the staged keys (set_n_bit, bitset.rs:63-75), word by word: an N is a base whose bit 2 is
+// set and bits 0, 1 clear; in word w base boundaries sit at the bits o with (64w + o) % 3 == 0, and a
+// base's low bits may lie in the word before
+template <int W>
+__global__ __launch_bounds__(256) void seq_nmask_kernel(const uint64_t *__restrict__ keys, uint32_t n_entries,
+                                                        uint64_t *__restrict__ nmask)
+{
+    const uint64_t top_bit[3] = {0x4924924924924924ull, 0x2492492492492492ull, 0x9249249249249249ull}; // o % 3 == 2, 1, 0
+    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n_entries; e += gridDim.x * blockDim.x) {
+        uint64_t m[W];
+        uint64_t prev = 0;
+#pragma unroll
+        for (int w = 0; w < W; w++) {
+            const uint64_t x = keys[(size_t)e * W + w];
+            const uint64_t b1 = (x << 1) | (prev >> 63), b0 = (x << 2) | (prev >> 62);
+            const uint64_t nb = x & ~b1 & ~b0 & top_bit[w % 3]; // (64w + o) % 3 == 2 <=> o % 3 == (2 - w % 3) % 3
+            m[w] = nb | (nb >> 1) | (nb >> 2);
+            if (w > 0) m[w - 1] |= (nb << 63) | (nb << 62);
+            prev = x;
+        }
+#pragma unroll
+        for (int w = 0; w < W; w++) nmask[(size_t)e * W + w] = m[w];
+    }
+}
+
+// bucket_len by rank: the length of every position's first read
+__global__ __launch_bounds__(256) void seq_bucket_len_kernel(const uint32_t *__restrict__ bfirst, const uint32_t *__restrict__ brank_of,
+                                                             const uint64_t *__restrict__ len64, uint32_t n_buckets,
+                                                             int32_t *__restrict__ blen)
+{
+    for (uint32_t b = blockIdx.x * blockDim.x + threadIdx.x; b < n_buckets; b += gridDim.x * blockDim.x)
+        blen[brank_of[b]] = (int32_t)len64[bfirst[b]];
+}
+
+// entry_of_read: first every read's entry number of the heads pass, by file index ...
+__global__ __launch_bounds__(256) void seq_read_entry_kernel(const uint32_t *__restrict__ numbers, const uint32_t *__restrict__ perm,
+                                                             uint32_t n, uint32_t *__restrict__ eor)
+{
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) eor[perm[i]] = numbers[i];
+}
+// ... then, once the emit has placed every entry, its place in the output
+__global__ __launch_bounds__(256) void seq_entry_slot_kernel(const uint32_t *__restrict__ slot, uint32_t n, uint32_t *__restrict__ eor)
+{
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) eor[r] = slot[eor[r]];
 }
 
 inline int bits_for(uint64_t v)
@@ -832,6 +990,105 @@ StageBufs carve(void *ws, uint32_t n, int n_words)
         if (e_ != hipSuccess) return -(int)e_;         \
     } while (0)
 
+// ---- 2'-3'. from the sorted reads to the output (both staging forms) -----------------------------------
+// va: the reads' file indices in sorted order; composed: the sorted composed keys (or null).  Leaves the
+// output on the stream, unsynchronised.  d_eor (may be null): every read's place in the output,
+// entry_of_read; it takes the entry numbers of the heads pass, which the order sort below overwrites,
+// and va (free by then) holds the place of every entry.
+template <int W>
+int stage_finish(StageBufs &b, uint32_t *va, const uint64_t *composed, Pack5 p5, const uint64_t *d_align, int align_bits,
+                 const int32_t *d_score, uint32_t n, int umi_len, int merge, uint64_t *d_keys, uint64_t *d_nmask,
+                 int32_t *d_freq, uint64_t *d_rep, uint64_t *d_bucket_off, uint32_t *d_eor, uint64_t *n_entries_out,
+                 uint64_t *n_buckets_out, unsigned long long *h_pinned4, hipStream_t s)
+{
+    const bool use_score = merge != 0 && d_score != nullptr;
+    const bool one_key = composed != nullptr;
+    // ---- 2. entries and positions
+    SortedReads sr;
+    sr.composed = composed;
+    sr.p5 = p5;
+    sr.umi_bits = p5.bits;
+    sr.align = d_align;
+    sr.align_bits = align_bits;
+    sr.k3 = b.k3;
+    sr.perm = va;
+    sr.n = n;
+    const uint32_t tiles = (n + HT_TILE - 1) / HT_TILE;
+    stage_head_sums_kernel<W><<<tiles, 256, 0, s>>>(sr, b.tile_sums);
+    STAGE_TRY(scan_spine_u64(b.tile_sums, tiles, s));
+    stage_head_apply_kernel<W><<<tiles, 256, 0, s>>>(sr, b.tile_sums, b.head_pos, b.ent_first, b.ent_bseq, b.ent_key, b.bfirst,
+                                                    use_score || d_eor ? b.numbers : nullptr, b.pos_start, b.counters);
+    if (d_eor) seq_read_entry_kernel<<<grid_for(n), 256, 0, s>>>(b.numbers, va, n, d_eor);
+    stage_fmax_kernel<<<grid_for(n, 256 * 16, 512), 256, 0, s>>>(b.head_pos, b.pos_start, b.counters);
+    // the host needs the counts to size what follows (and the verdict on the characters)
+    STAGE_TRY(hipMemcpyAsync(h_pinned4, b.counters, SC_COUNT * 8, hipMemcpyDeviceToHost, s));
+    STAGE_TRY(hipStreamSynchronize(s));
+    if (h_pinned4[SC_BAD]) return 1;
+    const uint32_t E = (uint32_t)h_pinned4[SC_ENTRIES], B = (uint32_t)h_pinned4[SC_BUCKETS];
+    const uint32_t fmax = (uint32_t)h_pinned4[SC_FMAX], pmax = (uint32_t)h_pinned4[SC_PMAX];
+    if (use_score) {
+        STAGE_TRY(hipMemsetAsync(b.best, 0, (size_t)E * 8, s));
+        stage_best_kernel<<<grid_for(n), 256, 0, s>>>(b.numbers, va, d_score, n, b.best);
+    }
+    uint32_t *slot = d_eor ? va : nullptr; // (the read order is not looked at again)
+    // ---- 3. the canonical order: first appearance by flag bytes in file order, counted and scanned ...
+    const uint32_t n_groups = (n + 63u) / 64u, n_blocks = (n_groups + 255u) / 256u;
+    STAGE_TRY(hipMemsetAsync(b.file_flags, 0, (size_t)n_groups * 64, s));
+    stage_mark_kernel<<<grid_for(E), 256, 0, s>>>(b.ent_first, b.ent_bseq, b.bfirst, E, (uint8_t *)b.file_flags);
+    stage_rank_sums_kernel<<<n_blocks, 256, 0, s>>>(b.file_flags, n_groups, b.rank_rec, b.tile_sums);
+    STAGE_TRY(scan_spine_u64(b.tile_sums, n_blocks, s));
+    stage_position_rank_kernel<<<grid_for(B), 256, 0, s>>>(b.bfirst, B, b.rank_rec, b.tile_sums, b.brank_of);
+    // ---- 3'. every position fits a wave's LDS: ordered where it lies, no sort.  (A wave per position pays
+    // where positions hold some tens of entries; a file of singletons -- shallow sequencing -- is 10^7
+    // positions of one entry each, a trip to memory per wave and position: the sort below does not care.)
+    if (pmax <= LOCAL_MAX && (uint64_t)E >= 16ull * B) {
+        uint64_t *size_by_rank = b.keyA, *end_by_rank = b.keyB; // (the read sort's buffers are free)
+        stage_rank_sizes_kernel<<<grid_for(B), 256, 0, s>>>(b.pos_start, b.brank_of, B, size_by_rank);
+        STAGE_TRY(scan_inclusive_u64(size_by_rank, end_by_rank, B, b.tmp, b.tmp_bytes, s));
+        const int first_bits = bits_for(n - 1);
+        // (UMIHIP_STAGE_WIDE_ORDER: the tests' way to the 64-bit form, which otherwise needs 2^24 reads and a freq to match)
+        static const bool force_wide = getenv("UMIHIP_STAGE_WIDE_ORDER") != nullptr;
+        if (first_bits + bits_for(fmax) <= 32 && !force_wide)
+            stage_emit_local_kernel<W, uint32_t><<<grid_for((uint64_t)B, 4, 8192), 256, 0, s>>>(
+                b.pos_start, b.brank_of, end_by_rank, E, B, use_score ? 1 : 0, umi_len, fmax, first_bits, p5, one_key ? 1 : 0,
+                b.ent_key, b.ent_first, b.head_pos, b.best, d_keys, d_nmask, d_freq, d_rep, d_bucket_off, slot);
+        else
+            stage_emit_local_kernel<W, uint64_t><<<grid_for((uint64_t)B, 4, 4096), 256, 0, s>>>(
+                b.pos_start, b.brank_of, end_by_rank, E, B, use_score ? 1 : 0, umi_len, fmax, 32, p5, one_key ? 1 : 0,
+                b.ent_key, b.ent_first, b.head_pos, b.best, d_keys, d_nmask, d_freq, d_rep, d_bucket_off, slot);
+    } else {
+        // ... and one stable sort of the entries, taken in that order, by (position rank, max freq - freq).
+        // (Everything of the read sort but its order, va, is free by now -- and va's twin and the entry
+        // numbers too, in stream order.)
+        const int freq_bits = bits_for(fmax), rank_bits = bits_for(B ? B - 1 : 0), order_bits = std::min(64, freq_bits + rank_bits);
+        uint32_t *ova = va == b.idxA ? b.idxB : b.idxA, *ovb = b.numbers;
+        uint32_t *hist = nullptr;
+        STAGE_TRY(radix_sort_prepare(b.tmp, b.tmp_bytes, E, 0, order_bits, &hist, s));
+        bool ob = false;
+        const uint32_t order_blocks = grid_for(E, 256, RADIX_HIST_PARTS);
+        if (order_bits <= 32) {
+            uint32_t *oka = (uint32_t *)b.keyA, *okb = (uint32_t *)b.keyB;
+            stage_order_kernel<uint32_t><<<order_blocks, 256, 0, s>>>(b.rank_rec, b.tile_sums, b.ent_first, b.ent_bseq, b.brank_of,
+                                                                     b.head_pos, b.ent_key, W, E, fmax, freq_bits, oka, ova, b.rec,
+                                                                     hist, order_bits, p5, one_key ? 1 : 0);
+            STAGE_TRY(radix_sort_pairs_u32(oka, okb, ova, ovb, E, 0, order_bits, b.tmp, b.tmp_bytes, &ob, s, order_blocks));
+        } else {
+            stage_order_kernel<uint64_t><<<order_blocks, 256, 0, s>>>(b.rank_rec, b.tile_sums, b.ent_first, b.ent_bseq, b.brank_of,
+                                                                     b.head_pos, b.ent_key, W, E, fmax, freq_bits, b.keyA, ova, b.rec,
+                                                                     hist, order_bits, p5, one_key ? 1 : 0);
+            STAGE_TRY(radix_sort_pairs_u64(b.keyA, b.keyB, ova, ovb, E, 0, order_bits, b.tmp, b.tmp_bytes, &ob, s, order_blocks));
+        }
+        const uint32_t *perm_final = ob ? ovb : ova;
+        stage_emit_kernel<W><<<grid_for(E), 256, 0, s>>>(perm_final, E, B, use_score ? 1 : 0, umi_len, b.rec, b.ent_key, b.best,
+                                                         d_keys, d_nmask, d_freq, d_rep, d_bucket_off, slot);
+    }
+    if (d_eor) seq_entry_slot_kernel<<<grid_for(n), 256, 0, s>>>(slot, n, d_eor);
+    STAGE_TRY(hipGetLastError());
+    *n_entries_out = E;
+    *n_buckets_out = B;
+    return 0;
+}
+
 template <int W>
 int stage_impl(void *workspace, const uint64_t *d_align, int align_bits, const uint8_t *d_umi, const int32_t *d_score,
                uint32_t n, int umi_len, int merge, uint64_t *d_keys, uint64_t *d_nmask, int32_t *d_freq, uint64_t *d_rep,
@@ -839,7 +1096,6 @@ int stage_impl(void *workspace, const uint64_t *d_align, int align_bits, const u
                hipStream_t s)
 {
     StageBufs b = carve(workspace, n, W);
-    const bool use_score = merge != 0 && d_score != nullptr;
     const int umi_bits = 3 * umi_len;
     const Pack5 p5 = pack5_of(W == 1 ? umi_len : 1);
     const bool one_key = W == 1 && align_bits + p5.bits <= 64; // the composed sort key fits a word
@@ -875,87 +1131,119 @@ int stage_impl(void *workspace, const uint64_t *d_align, int align_bits, const u
         STAGE_TRY(sort_by(0, align_bits, 0));
     }
     // (va: the reads' file indices in order; ka: the composed keys in order where there is one)
-    // ---- 2. entries and positions
-    SortedReads sr;
-    sr.composed = one_key ? ka : nullptr;
-    sr.p5 = p5;
-    sr.umi_bits = p5.bits;
-    sr.align = d_align;
-    sr.align_bits = align_bits;
-    sr.k3 = b.k3;
-    sr.perm = va;
-    sr.n = n;
-    const uint32_t tiles = (n + HT_TILE - 1) / HT_TILE;
-    stage_head_sums_kernel<W><<<tiles, 256, 0, s>>>(sr, b.tile_sums);
-    STAGE_TRY(scan_spine_u64(b.tile_sums, tiles, s));
-    stage_head_apply_kernel<W><<<tiles, 256, 0, s>>>(sr, b.tile_sums, b.head_pos, b.ent_first, b.ent_bseq, b.ent_key, b.bfirst,
-                                                    use_score ? b.numbers : nullptr, b.pos_start, b.counters);
-    stage_fmax_kernel<<<grid_for(n, 256 * 16, 512), 256, 0, s>>>(b.head_pos, b.pos_start, b.counters);
-    // the host needs the counts to size what follows (and the verdict on the characters)
-    STAGE_TRY(hipMemcpyAsync(h_pinned4, b.counters, SC_COUNT * 8, hipMemcpyDeviceToHost, s));
+    const int r = stage_finish<W>(b, va, one_key ? ka : nullptr, p5, d_align, align_bits, d_score, n, umi_len, merge, d_keys,
+                                  d_nmask, d_freq, d_rep, d_bucket_off, nullptr, n_entries_out, n_buckets_out, h_pinned4, s);
+    if (r) return r;
     STAGE_TRY(hipStreamSynchronize(s));
-    if (h_pinned4[SC_BAD]) return 1;
-    const uint32_t E = (uint32_t)h_pinned4[SC_ENTRIES], B = (uint32_t)h_pinned4[SC_BUCKETS];
-    const uint32_t fmax = (uint32_t)h_pinned4[SC_FMAX], pmax = (uint32_t)h_pinned4[SC_PMAX];
-    if (use_score) {
-        STAGE_TRY(hipMemsetAsync(b.best, 0, (size_t)E * 8, s));
-        stage_best_kernel<<<grid_for(n), 256, 0, s>>>(b.numbers, va, d_score, n, b.best);
+    return 0;
+}
+
+// ---- 4. whole reads (fastq mode, umi_stage_seqs): the read length is the position, the whole read a key
+// of W <= 12 words.  One wave per read encodes it straight from the file's text; a stable sort per
+// key word (and one by length) brings equal reads together -- exact, no hashes -- and sections 2-3 do
+// the rest as for UMIs.  Sort passes over a byte that is the same in every read (the zero high words
+// of short reads, a constant linker) are left out: the encode ORs and ANDs every word over the reads.
+struct SeqBufs {
+    uint64_t *len64, *boff;
+    int32_t *score, *blen;
+    unsigned long long *info;
+    size_t total;
+};
+SeqBufs seq_carve(void *ws, uint32_t n, int n_words)
+{
+    Carver c{(char *)ws};
+    c.off = carve(nullptr, n, n_words).total;
+    SeqBufs q;
+    const size_t m = (size_t)n + 2;
+    q.len64 = c.take<uint64_t>(m);
+    q.score = c.take<int32_t>(m);
+    q.info = c.take<unsigned long long>(SI_COUNT);
+    q.boff = c.take<uint64_t>(UMI_MAX_SEQ_LEN + 2);
+    q.blen = c.take<int32_t>(UMI_MAX_SEQ_LEN + 1);
+    q.total = c.off;
+    return q;
+}
+
+template <int W>
+int seq_impl(void *workspace, const uint8_t *d_text, const uint64_t *d_seq_pos, const uint64_t *d_qual_pos,
+             const uint32_t *d_len, uint32_t n, int merge, uint64_t *d_keys, uint64_t *d_nmask, int32_t *d_freq,
+             uint64_t *d_rep, uint32_t *d_eor, uint64_t *h_bucket_off, int32_t *h_bucket_len, uint64_t *n_entries_out,
+             uint64_t *n_buckets_out, int *any_n, SeqFault *fault, unsigned long long *h_pinned4, hipStream_t s)
+{
+    StageBufs b = carve(workspace, n, W);
+    SeqBufs q = seq_carve(workspace, n, W);
+    STAGE_TRY(hipMemsetAsync(b.counters, 0, SC_COUNT * 8, s));
+    STAGE_TRY(hipMemsetAsync(b.bfirst, 0xFF, (size_t)n * 4, s));
+    STAGE_TRY(hipMemsetAsync(q.info, 0, SI_COUNT * 8, s));
+    STAGE_TRY(hipMemsetAsync(q.info + SI_BAD, 0xFF, 8, s));
+    STAGE_TRY(hipMemsetAsync(q.info + SI_AND, 0xFF, SI_SLOTS * 8, s));
+    const bool use_score = merge != 0 && d_qual_pos != nullptr; // (the API refuses merge 1 without qualities)
+    seq_encode_kernel<W><<<grid_for(n, 4, 4096), 256, 0, s>>>(d_text, d_seq_pos, use_score ? d_qual_pos : nullptr, d_len, n,
+                                                              b.k3, b.idxA, q.len64, use_score ? q.score : nullptr, q.info);
+    unsigned long long info[SI_COUNT];
+    STAGE_TRY(hipMemcpyAsync(info, q.info, sizeof(info), hipMemcpyDeviceToHost, s));
+    STAGE_TRY(hipStreamSynchronize(s));
+    const uint32_t max_len = (uint32_t)info[SI_MAXLEN];
+    if (max_len > UMI_MAX_SEQ_LEN) {
+        fault->value = max_len;
+        return 2;
     }
-    // ---- 3. the canonical order: first appearance by flag bytes in file order, counted and scanned ...
-    const uint32_t n_groups = (n + 63u) / 64u, n_blocks = (n_groups + 255u) / 256u;
-    STAGE_TRY(hipMemsetAsync(b.file_flags, 0, (size_t)n_groups * 64, s));
-    stage_mark_kernel<<<grid_for(E), 256, 0, s>>>(b.ent_first, b.ent_bseq, b.bfirst, E, (uint8_t *)b.file_flags);
-    stage_rank_sums_kernel<<<n_blocks, 256, 0, s>>>(b.file_flags, n_groups, b.rank_rec, b.tile_sums);
-    STAGE_TRY(scan_spine_u64(b.tile_sums, n_blocks, s));
-    stage_position_rank_kernel<<<grid_for(B), 256, 0, s>>>(b.bfirst, B, b.rank_rec, b.tile_sums, b.brank_of);
-    // ---- 3'. every position fits a wave's LDS: ordered where it lies, no sort.  (A wave per position pays
-    // where positions hold some tens of entries; a file of singletons -- shallow sequencing -- is 10^7
-    // positions of one entry each, a trip to memory per wave and position: the sort below does not care.)
-    if (pmax <= LOCAL_MAX && (uint64_t)E >= 16ull * B) {
-        uint64_t *size_by_rank = b.keyA, *end_by_rank = b.keyB; // (the read sort's buffers are free)
-        stage_rank_sizes_kernel<<<grid_for(B), 256, 0, s>>>(b.pos_start, b.brank_of, B, size_by_rank);
-        STAGE_TRY(scan_inclusive_u64(size_by_rank, end_by_rank, B, b.tmp, b.tmp_bytes, s));
-        const int first_bits = bits_for(n - 1);
-        // (UMIHIP_STAGE_WIDE_ORDER: the tests' way to the 64-bit form, which otherwise needs 2^24 reads and a freq to match)
-        static const bool force_wide = getenv("UMIHIP_STAGE_WIDE_ORDER") != nullptr;
-        if (first_bits + bits_for(fmax) <= 32 && !force_wide)
-            stage_emit_local_kernel<W, uint32_t><<<grid_for((uint64_t)B, 4, 8192), 256, 0, s>>>(
-                b.pos_start, b.brank_of, end_by_rank, E, B, use_score ? 1 : 0, umi_len, fmax, first_bits, p5, one_key ? 1 : 0,
-                b.ent_key, b.ent_first, b.head_pos, b.best, d_keys, d_nmask, d_freq, d_rep, d_bucket_off);
-        else
-            stage_emit_local_kernel<W, uint64_t><<<grid_for((uint64_t)B, 4, 4096), 256, 0, s>>>(
-                b.pos_start, b.brank_of, end_by_rank, E, B, use_score ? 1 : 0, umi_len, fmax, 32, p5, one_key ? 1 : 0,
-                b.ent_key, b.ent_first, b.head_pos, b.best, d_keys, d_nmask, d_freq, d_rep, d_bucket_off);
-        STAGE_TRY(hipGetLastError());
+    if ((int)((3 * max_len + 63) / 64) > W) {
+        fault->value = max_len;
+        return 3;
+    }
+    if (info[SI_BAD] != ~0ull) { // the first bad byte of the first read that has one
+        const uint64_t r = info[SI_BAD] >> 9, at = info[SI_BAD] & 511u;
+        uint64_t pos = 0;
+        uint8_t byte = 0;
+        STAGE_TRY(hipMemcpyAsync(&pos, d_seq_pos + r, 8, hipMemcpyDeviceToHost, s));
         STAGE_TRY(hipStreamSynchronize(s));
-        *n_entries_out = E;
-        *n_buckets_out = B;
-        return 0;
+        STAGE_TRY(hipMemcpyAsync(&byte, d_text + pos + at, 1, hipMemcpyDeviceToHost, s));
+        STAGE_TRY(hipStreamSynchronize(s));
+        fault->read = r;
+        fault->value = byte;
+        return 1;
     }
-    // ... and one stable sort of the entries, taken in that order, by (position rank, max freq - freq).
-    // (Everything of the read sort but its order, va, is free by now -- and va's twin and the entry
-    // numbers too, in stream order.)
-    const int freq_bits = bits_for(fmax), rank_bits = bits_for(B ? B - 1 : 0), order_bits = std::min(64, freq_bits + rank_bits);
-    uint32_t *ova = va == b.idxA ? b.idxB : b.idxA, *ovb = b.numbers;
-    STAGE_TRY(radix_sort_prepare(b.tmp, b.tmp_bytes, E, 0, order_bits, &hist, s));
-    bool ob = false;
-    const uint32_t order_blocks = grid_for(E, 256, RADIX_HIST_PARTS);
-    if (order_bits <= 32) {
-        uint32_t *oka = (uint32_t *)b.keyA, *okb = (uint32_t *)b.keyB;
-        stage_order_kernel<uint32_t><<<order_blocks, 256, 0, s>>>(b.rank_rec, b.tile_sums, b.ent_first, b.ent_bseq, b.brank_of,
-                                                                 b.head_pos, b.ent_key, W, E, fmax, freq_bits, oka, ova, b.rec,
-                                                                 hist, order_bits, p5, one_key ? 1 : 0);
-        STAGE_TRY(radix_sort_pairs_u32(oka, okb, ova, ovb, E, 0, order_bits, b.tmp, b.tmp_bytes, &ob, s, order_blocks));
-    } else {
-        stage_order_kernel<uint64_t><<<order_blocks, 256, 0, s>>>(b.rank_rec, b.tile_sums, b.ent_first, b.ent_bseq, b.brank_of,
-                                                                 b.head_pos, b.ent_key, W, E, fmax, freq_bits, b.keyA, ova, b.rec,
-                                                                 hist, order_bits, p5, one_key ? 1 : 0);
-        STAGE_TRY(radix_sort_pairs_u64(b.keyA, b.keyB, ova, ovb, E, 0, order_bits, b.tmp, b.tmp_bytes, &ob, s, order_blocks));
+    *any_n = info[SI_ANY_N] ? 1 : 0;
+    // ---- 1. reads by (length, whole read, file index): the words, least significant first, then the length
+    uint64_t *ka = b.keyA, *kb = b.keyB;
+    uint32_t *va = b.idxA, *vb = b.idxB;
+    bool in_b = false;
+    auto sort_word = [&](const uint64_t *src, int stride, int w, uint64_t varying) -> hipError_t {
+        if (!varying) return hipSuccess;
+        stage_gather_u64_kernel<<<grid_for(n), 256, 0, s>>>(src, stride, w, va, n, ka);
+        for (int p = 0; p < 8;) { // one sort per run of bytes that differ between reads
+            if (!((varying >> (8 * p)) & 0xFFu)) {
+                p++;
+                continue;
+            }
+            int e = p;
+            while (e < 8 && ((varying >> (8 * e)) & 0xFFu)) e++;
+            const hipError_t err = radix_sort_pairs_u64(ka, kb, va, vb, n, 8 * p, 8 * e, b.tmp, b.tmp_bytes, &in_b, s, 0);
+            if (err != hipSuccess) return err;
+            if (in_b) {
+                std::swap(ka, kb);
+                std::swap(va, vb);
+            }
+            p = e;
+        }
+        return hipSuccess;
+    };
+    for (int w = 0; w < W; w++) STAGE_TRY(sort_word(b.k3, W, w, info[SI_OR + w] ^ info[SI_AND + w]));
+    STAGE_TRY(sort_word(q.len64, 1, 0, info[SI_OR + SI_LEN] ^ info[SI_AND + SI_LEN]));
+    // ---- 2-3. as for UMIs, the length as the alignment key (9 bits: 0..256)
+    uint64_t E = 0, B = 0;
+    const int r = stage_finish<W>(b, va, nullptr, pack5_of(1), q.len64, 9, use_score ? q.score : nullptr, n, 0, merge, d_keys,
+                                  nullptr, d_freq, d_rep, q.boff, d_eor, &E, &B, h_pinned4, s);
+    if (r) return r;
+    if (d_nmask) {
+        if (*any_n) seq_nmask_kernel<W><<<grid_for(E), 256, 0, s>>>(d_keys, (uint32_t)E, d_nmask);
+        else STAGE_TRY(hipMemsetAsync(d_nmask, 0, (size_t)E * W * 8, s));
     }
-    const uint32_t *perm_final = ob ? ovb : ova;
-    stage_emit_kernel<W><<<grid_for(E), 256, 0, s>>>(perm_final, E, B, use_score ? 1 : 0, umi_len, b.rec, b.ent_key, b.best,
-                                                     d_keys, d_nmask, d_freq, d_rep, d_bucket_off);
+    seq_bucket_len_kernel<<<grid_for(B), 256, 0, s>>>(b.bfirst, b.brank_of, q.len64, (uint32_t)B, q.blen);
     STAGE_TRY(hipGetLastError());
+    STAGE_TRY(hipMemcpyAsync(h_bucket_off, q.boff, (B + 1) * 8, hipMemcpyDeviceToHost, s));
+    STAGE_TRY(hipMemcpyAsync(h_bucket_len, q.blen, B * 4, hipMemcpyDeviceToHost, s));
     STAGE_TRY(hipStreamSynchronize(s));
     *n_entries_out = E;
     *n_buckets_out = B;
@@ -965,6 +1253,7 @@ int stage_impl(void *workspace, const uint64_t *d_align, int align_bits, const u
 } // namespace
 
 size_t stage_workspace_bytes(uint32_t n_reads, int n_words) { return carve(nullptr, n_reads, n_words).total; }
+size_t stage_seqs_workspace_bytes(uint32_t n_reads, int n_words) { return seq_carve(nullptr, n_reads, n_words).total; }
 
 // 0 ok; 1 a character outside ATCGN; negative: -(hipError_t)
 int stage_reads_on_device(void *workspace, const uint64_t *d_align, int align_bits, const uint8_t *d_umi,
@@ -990,6 +1279,37 @@ int stage_reads_on_device(void *workspace, const uint64_t *d_align, int align_bi
     default: return -(int)hipErrorInvalidValue;
     }
 #undef STAGE_W
+}
+
+int stage_seqs_on_device(void *workspace, const uint8_t *d_text, const uint64_t *d_seq_pos, const uint64_t *d_qual_pos,
+                         const uint32_t *d_len, uint32_t n, int n_words, int merge, uint64_t *d_keys, uint64_t *d_nmask,
+                         int32_t *d_freq, uint64_t *d_rep, uint32_t *d_eor, uint64_t *h_bucket_off, int32_t *h_bucket_len,
+                         uint64_t *n_entries_out, uint64_t *n_buckets_out, int *any_n, SeqFault *fault,
+                         unsigned long long *h_pinned4, hipStream_t s)
+{
+    *n_entries_out = *n_buckets_out = 0;
+    *any_n = 0;
+    h_bucket_off[0] = 0;
+    if (n == 0) return 0;
+#define SEQ_W(WN)                                                                                                  \
+    return seq_impl<WN>(workspace, d_text, d_seq_pos, d_qual_pos, d_len, n, merge, d_keys, d_nmask, d_freq, d_rep, \
+                        d_eor, h_bucket_off, h_bucket_len, n_entries_out, n_buckets_out, any_n, fault, h_pinned4, s)
+    switch (n_words) {
+    case 1: SEQ_W(1);
+    case 2: SEQ_W(2);
+    case 3: SEQ_W(3);
+    case 4: SEQ_W(4);
+    case 5: SEQ_W(5);
+    case 6: SEQ_W(6);
+    case 7: SEQ_W(7);
+    case 8: SEQ_W(8);
+    case 9: SEQ_W(9);
+    case 10: SEQ_W(10);
+    case 11: SEQ_W(11);
+    case 12: SEQ_W(12);
+    default: return -(int)hipErrorInvalidValue;
+    }
+#undef SEQ_W
 }
 
 #undef STAGE_TRY

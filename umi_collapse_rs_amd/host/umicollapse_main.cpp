@@ -28,8 +28,10 @@
 // rep read and " same_umi=<freq>" on every sequence's rep read.  A truncated record, a missing @ or
 // +, sequence and quality of different lengths, a base outside ATCGN ("Unknown character"), a read
 // over 256 bases end the run with status 101.  Refused with it: --paired, --remove-unpaired,
-// --remove-chimeric, --keep-unmapped, --two-pass, --stage gpu, several --devices; --umi_sep and
-// --data are accepted and ignored.
+// --remove-chimeric, --keep-unmapped, --two-pass, several --devices, --stage gpu with --dump-staging;
+// --umi_sep and --data are accepted and ignored.  --stage gpu / auto stage the reads on the device
+// (umi_stage_seqs_device; auto means host only with --dump-staging or 2^30 reads or more), --stage host
+// on the host; same output and messages either way.
 // --two-pass (the reference parses it and ignores it; UMICollapse's meaning): the input is read twice and
 // never held.  Pass 1 counts, writes the kept unmapped reads and notes the last read of every alignment
 // key; pass 2 holds a position's reads until its last one, deduplicates closed positions in windows of
@@ -105,6 +107,20 @@ struct HipLib {
                        int, int, float, int, int32_t, uint8_t *, uint32_t *, umi_stats *) = nullptr;
     int (*dedup_seqs)(umi_ctx *, const uint64_t *, const uint64_t *, int, const int32_t *, const uint64_t *,
                       const int32_t *, uint64_t, int, float, int, int32_t, uint8_t *, uint32_t *, umi_stats *) = nullptr;
+    // fastq mode's device staging: its arrays stay on the device between the two calls
+    int (*stage_seqs)(umi_ctx *, const uint8_t *, const uint64_t *, const uint64_t *, const uint32_t *, uint64_t, int, int,
+                      uint64_t *, uint64_t *, int32_t *, uint64_t *, uint32_t *, uint64_t *, int32_t *, uint64_t *,
+                      uint64_t *, int *) = nullptr;
+    int (*stage_seqs_device)(umi_ctx *, const uint8_t *, const uint64_t *, const uint64_t *, const uint32_t *, uint64_t, int,
+                             int, uint64_t *, uint64_t *, int32_t *, uint64_t *, uint32_t *, uint64_t *, int32_t *,
+                             uint64_t *, uint64_t *, int *, void *) = nullptr;
+    int (*dedup_seqs_device)(umi_ctx *, const uint64_t *, const uint64_t *, int, const int32_t *, const uint64_t *,
+                             const int32_t *, uint64_t, int, float, int, int32_t, uint8_t *, uint32_t *, void *,
+                             umi_stats *) = nullptr;
+    // (the HIP runtime the library brings along: device buffers for the arrays above)
+    int (*hip_set_device)(int) = nullptr; // (the current device is per thread: the context was made on another)
+    int (*hip_malloc)(void **, size_t) = nullptr;
+    int (*hip_memcpy)(void *, const void *, size_t, int) = nullptr; // kind: 1 host to device, 2 device to host
     std::string error;
     bool load()
     {
@@ -130,6 +146,12 @@ struct HipLib {
         stage_reads = (decltype(stage_reads))sym("umi_stage_reads_wide");
         dedup_batch = (decltype(dedup_batch))sym("umi_dedup_batch_wide");
         dedup_seqs = (decltype(dedup_seqs))sym("umi_dedup_seqs");
+        stage_seqs = (decltype(stage_seqs))sym("umi_stage_seqs");
+        stage_seqs_device = (decltype(stage_seqs_device))sym("umi_stage_seqs_device");
+        dedup_seqs_device = (decltype(dedup_seqs_device))sym("umi_dedup_seqs_device");
+        hip_set_device = (decltype(hip_set_device))sym("hipSetDevice");
+        hip_malloc = (decltype(hip_malloc))sym("hipMalloc");
+        hip_memcpy = (decltype(hip_memcpy))sym("hipMemcpy");
         return error.empty();
     }
 };
@@ -380,19 +402,190 @@ double now_s()
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// What the writer of fastq mode takes from either staging side: entries in canonical order (n of them
+// in nb buckets), the collapse's kept / root, and with --tag every read's entry.
+struct FastqResult {
+    size_t n, nb;
+    std::vector<uint64_t> off;
+    std::vector<int32_t> freq;
+    std::vector<uint32_t> rep;
+    std::vector<uint8_t> kept;
+    std::vector<uint32_t> root;
+    std::vector<uint32_t> entry_of_read;
+    umi_stats st;
+    double t_staging, t_init, t_hot;
+    bool gpu_staged;
+};
+[[noreturn]] void write_fastq(const Cli &args, const umi::bgzf::Bytes &text, const std::vector<umi::fastq::Record> &recs,
+                              const FastqResult &res, double t_start, double t_read, double t_gpu1);
+
+// fastq mode with the staging on the device.  The checks of the host staging come in the same order and
+// with the same messages: per record in file order its length (over 256, under -u), then its characters.
+// A file with a length problem is an error either way: the reads before it are checked for characters
+// on the host and the earlier problem is named, no GPU needed.  Otherwise the device checks the
+// characters and reports the first bad read.
+[[noreturn]] void run_fastq_gpu_stage(const Cli &args, int algo, int merge, HipLib &lib, const umi::bgzf::Bytes &text,
+                                      const std::vector<umi::fastq::Record> &recs, std::future<umi_ctx *> &warm,
+                                      const std::string &warm_error, double t_start, double t_read)
+{
+    const size_t n_reads = recs.size();
+    size_t n_ok = n_reads; // reads before the first length problem
+    std::string len_problem;
+    for (size_t i = 0; i < n_reads && n_ok == n_reads; i++) {
+        const umi::fastq::Record &r = recs[i];
+        if (r.len > UMI_MAX_SEQ_LEN)
+            len_problem = "FASTQ record " + std::to_string(i + 1) + ": " + std::to_string(r.len) + " bases, more than " +
+                          std::to_string(UMI_MAX_SEQ_LEN);
+        else if (r.len < args.umi_length)
+            len_problem = "FASTQ record " + std::to_string(i + 1) + ": " + std::to_string(r.len) +
+                          " bases, shorter than -u " + std::to_string(args.umi_length);
+        if (!len_problem.empty()) n_ok = i;
+    }
+    if (!len_problem.empty()) {
+        for (size_t i = 0; i < n_ok; i++)
+            for (size_t b = 0; b < recs[i].len; b++) {
+                const uint8_t c = text[recs[i].seq + b];
+                if (c != 'A' && c != 'T' && c != 'C' && c != 'G' && c != 'N')
+                    die("Unknown character in sequence: " + std::to_string((unsigned)c) + " (FASTQ record " +
+                        std::to_string(i + 1) + ")"); // utils/mod.rs:77-79
+            }
+        die(len_problem);
+    }
+    std::vector<uint64_t> pos(2 * n_ok + 1);
+    std::vector<uint32_t> len(n_ok + 1);
+    int n_words = 1;
+    for (size_t i = 0; i < n_ok; i++) {
+        pos[i] = recs[i].seq;
+        pos[n_ok + i] = recs[i].qual;
+        len[i] = (uint32_t)recs[i].len;
+        n_words = std::max(n_words, (int)((3 * recs[i].len + 63) / 64));
+    }
+    umi_ctx *ctx = warm.get();
+    if (!ctx) die(warm_error);
+    // the buffers below go to the context's device: this thread's current device is 0 until it is set
+    if (lib.hip_set_device(args.devices[0]) != 0) die("hipSetDevice(" + std::to_string(args.devices[0]) + ") failed");
+    const double t_init = now_s();
+    auto dev = [&](size_t bytes) -> void * {
+        void *p = nullptr;
+        if (lib.hip_malloc(&p, std::max<size_t>(bytes, 8)) != 0) die("hipMalloc of " + std::to_string(bytes) + " bytes failed");
+        return p;
+    };
+    auto up = [&](void *dst, const void *src, size_t bytes) {
+        if (bytes && lib.hip_memcpy(dst, src, bytes, 1) != 0) die("hipMemcpy to the device failed");
+    };
+    auto down = [&](void *dst, const void *src, size_t bytes) {
+        if (bytes && lib.hip_memcpy(dst, src, bytes, 2) != 0) die("hipMemcpy from the device failed");
+    };
+    const size_t m = std::max<size_t>(n_ok, 1);
+    uint8_t *d_text = (uint8_t *)dev(text.size());
+    uint64_t *d_pos = (uint64_t *)dev(16 * m);
+    uint32_t *d_len = (uint32_t *)dev(4 * m);
+    uint64_t *d_keys = (uint64_t *)dev(8 * m * n_words), *d_nmask = (uint64_t *)dev(8 * m * n_words);
+    int32_t *d_freq = (int32_t *)dev(4 * m);
+    uint64_t *d_rep = (uint64_t *)dev(8 * m);
+    uint32_t *d_eor = args.track_clusters ? (uint32_t *)dev(4 * m) : nullptr;
+    up(d_text, text.data(), text.size());
+    up(d_pos, pos.data(), 8 * n_ok);
+    up(d_pos + n_ok, pos.data() + n_ok, 8 * n_ok);
+    up(d_len, len.data(), 4 * n_ok);
+    FastqResult res;
+    res.off.assign(UMI_MAX_SEQ_LEN + 2, 0);
+    std::vector<int32_t> blen(UMI_MAX_SEQ_LEN + 1, 0);
+    uint64_t n = 0, nb = 0;
+    int any_n = 0;
+    if (lib.stage_seqs_device(ctx, d_text, d_pos, merge == 1 ? d_pos + n_ok : nullptr, d_len, n_ok, n_words, merge, d_keys,
+                              d_nmask, d_freq, d_rep, d_eor, res.off.data(), blen.data(), &n, &nb, &any_n, nullptr) != UMI_OK) {
+        const std::string msg = lib.last_error();
+        unsigned byte = 0;
+        unsigned long long read = 0;
+        if (std::sscanf(msg.c_str(), "Unknown character in sequence: %u (read %llu)", &byte, &read) == 2)
+            die("Unknown character in sequence: " + std::to_string(byte) + " (FASTQ record " + std::to_string(read + 1) +
+                ")"); // utils/mod.rs:77-79
+        die(msg);
+    }
+    const double t_stage = now_s();
+    std::fprintf(stderr, "UMI collapsing reading finished in %.3f seconds\n", t_stage - t_start);
+    res.n = n;
+    res.nb = nb;
+    res.off.resize(nb + 1);
+    res.kept.assign(n + 1, 0);
+    res.root.assign(n + 1, 0);
+    res.freq.resize(n + 1);
+    res.rep.resize(n + 1);
+    std::memset(&res.st, 0, sizeof(res.st));
+    if (n) {
+        uint8_t *d_kept = (uint8_t *)dev(n);
+        uint32_t *d_root = (uint32_t *)dev(4 * n);
+        if (lib.dedup_seqs_device(ctx, d_keys, any_n ? d_nmask : nullptr, n_words, d_freq, res.off.data(), blen.data(), nb,
+                                  args.k, args.percentage, algo, 0 /* adjacency.rs:56 */, d_kept, d_root, nullptr,
+                                  &res.st) != UMI_OK)
+            die(lib.last_error());
+        down(res.kept.data(), d_kept, n);
+        down(res.root.data(), d_root, 4 * n);
+        down(res.freq.data(), d_freq, 4 * n);
+        std::vector<uint64_t> rep64(n);
+        down(rep64.data(), d_rep, 8 * n);
+        for (size_t e = 0; e < n; e++) res.rep[e] = (uint32_t)rep64[e];
+        if (d_eor) {
+            res.entry_of_read.resize(n_reads);
+            down(res.entry_of_read.data(), d_eor, 4 * n_reads);
+        }
+    }
+    const double t_gpu1 = now_s();
+    res.t_staging = t_stage - t_init;
+    res.t_init = t_init - t_read;
+    res.t_hot = t_gpu1 - t_stage;
+    res.gpu_staged = true;
+    write_fastq(args, text, recs, res, t_start, t_read, t_gpu1);
+}
+
 // ---- FASTQ mode (-m fastq).  The reference leaves it a TODO (src/main.rs:49-50); this build defines it
 // after UMICollapse's fastq mode: the whole read sequence is the key.  One bucket per read length
 // (first appearance), one entry per distinct sequence (freq, rep: the first read with --merge any, the
 // highest average quality -- first on ties -- with avgqual), rank order inside, ONE umi_dedup_seqs call,
 // survivors' rep reads written in file order (-u N trims N bases and quality characters from each).
+// Staging on the device (--stage gpu, or auto): the inflated text goes up as it is, with every read's
+// offsets and length; umi_stage_seqs_device leaves its output on the device for umi_dedup_seqs_device,
+// and only what the writer needs comes back.  --stage host (and auto with --dump-staging or 2^30
+// reads or more): the per-length hash maps below.
 int run_fastq(const Cli &args, int algo, int merge, HipLib &lib)
 {
     const double t_start = now_s();
     if (args.paired || args.remove_unpaired || args.remove_chimeric || args.keep_unmapped || args.two_pass)
         die("--paired, --remove-unpaired, --remove-chimeric, --keep-unmapped and --two-pass do not go with fastq mode");
-    if (args.stage == "gpu") die("--stage gpu does not go with fastq mode (its reads are staged on the host)");
+    if (args.stage != "auto" && args.stage != "gpu" && args.stage != "host") die("--stage wants gpu, host or auto");
+    if (args.stage == "gpu" && !args.dump_staging.empty()) die("--stage gpu does not go with --dump-staging");
     if (args.devices.size() > 1) die("fastq mode runs on one GPU: --devices takes one id here");
     if (merge == 2) die("Invalid algorithm combination: " + args.algo + " , " + args.merge + " and " + args.data);
+    // the GPU is woken while the file is read (as in BAM mode: a tiny staging call and a tiny dedup call
+    // load the library's code objects)
+    const bool want_gpu_stage = args.stage != "host" && args.dump_staging.empty();
+    std::future<umi_ctx *> warm;
+    std::string warm_error;
+    if (want_gpu_stage)
+        warm = std::async(std::launch::async, [&]() -> umi_ctx * {
+            umi_ctx *c = nullptr;
+            if (!lib.load()) {
+                warm_error = lib.error;
+                return nullptr;
+            }
+            if (lib.ctx_create_multi(args.devices.data(), 1, &c) != UMI_OK) {
+                warm_error = lib.last_error();
+                return nullptr;
+            }
+            const uint8_t txt[8] = {'A', 'C', 'G', 'T', 'A', 'C', 'G', 'A'};
+            const uint64_t pos[2] = {0, 4};
+            const uint32_t len[2] = {4, 4};
+            uint64_t k[2], nm[2], rp[2], off[3], ne = 0, nbk = 0;
+            int32_t fr[2], bl[2];
+            int an = 0;
+            uint8_t kept[2];
+            umi_stats wst;
+            if (lib.stage_seqs(c, txt, pos, pos, len, 2, 1, merge, k, nm, fr, rp, nullptr, off, bl, &ne, &nbk, &an) != UMI_OK ||
+                lib.dedup_seqs(c, k, nullptr, 1, fr, off, bl, nbk, 1, 0.5f, UMI_ALGO_DIRECTIONAL, 0, kept, nullptr, &wst) != UMI_OK)
+                warm_error = lib.last_error(); // (reported when the real call fails the same way)
+            return c;
+        });
     umi::bgzf::Bytes text = umi::fastq::read_all(args.input, args.num_threads);
     std::vector<umi::fastq::Record> recs;
     const std::string perr = umi::fastq::parse(text.data(), text.size(), recs);
@@ -400,6 +593,8 @@ int run_fastq(const Cli &args, int algo, int merge, HipLib &lib)
     const double t_read = now_s();
     const uint8_t *d = text.data();
     const size_t n_reads = recs.size();
+    if (want_gpu_stage && n_reads < (1ull << 30))
+        run_fastq_gpu_stage(args, algo, merge, lib, text, recs, warm, warm_error, t_start, t_read);
     // staging: per read length a map sequence -> entry, entries in first appearance
     struct Entry {
         uint32_t freq, rep;
@@ -516,10 +711,15 @@ int run_fastq(const Cli &args, int algo, int merge, HipLib &lib)
     std::memset(&st, 0, sizeof(st));
     double t_gpu0 = now_s(), t_gpu1 = t_gpu0;
     if (n) {
-        if (!lib.load()) die(lib.error);
-        if (!lib.dedup_seqs) die("libumihip.so lacks umi_dedup_seqs");
         umi_ctx *ctx = nullptr;
-        if (lib.ctx_create_multi(args.devices.data(), 1, &ctx) != UMI_OK) die(lib.last_error());
+        if (warm.valid()) { // (--stage auto with 2^30 reads or more: the context the start-up thread made)
+            ctx = warm.get();
+            if (!ctx) die(warm_error);
+        } else {
+            if (!lib.load()) die(lib.error);
+            if (!lib.dedup_seqs) die("libumihip.so lacks umi_dedup_seqs");
+            if (lib.ctx_create_multi(args.devices.data(), 1, &ctx) != UMI_OK) die(lib.last_error());
+        }
         t_gpu0 = now_s();
         if (lib.dedup_seqs(ctx, keys.data(), any_n ? nmask.data() : nullptr, n_words, freq.data(), off.data(),
                            blen.data(), nb, args.k, args.percentage, algo, 0 /* adjacency.rs:56 */, kept.data(),
@@ -527,6 +727,34 @@ int run_fastq(const Cli &args, int algo, int merge, HipLib &lib)
             die(lib.last_error());
         t_gpu1 = now_s();
     }
+    FastqResult res{n, nb, std::move(off), std::move(freq), std::move(rep), std::move(kept), std::move(root), {}, st,
+                    t_stage - t_read, t_gpu0 - t_stage, t_gpu1 - t_gpu0, false};
+    // entry of every read (--tag): its sequence's, looked up again per bucket
+    if (args.track_clusters) {
+        res.entry_of_read.resize(n_reads);
+        std::vector<std::unordered_map<std::string, uint32_t>> index(nb);
+        for (size_t b = 0; b < nb; b++)
+            for (uint64_t e = res.off[b]; e < res.off[b + 1]; e++)
+                index[b].emplace(std::string((const char *)d + recs[res.rep[e]].seq, recs[res.rep[e]].len), (uint32_t)e);
+        for (size_t i = 0; i < n_reads; i++) {
+            const umi::fastq::Record &r = recs[i];
+            res.entry_of_read[i] = index[bucket_of_len[r.len]].at(std::string((const char *)d + r.seq, r.len));
+        }
+    }
+    write_fastq(args, text, recs, res, t_start, t_read, t_gpu1);
+}
+
+// the survivors (or with --tag every read) written, the summary printed; the process ends here
+[[noreturn]] void write_fastq(const Cli &args, const umi::bgzf::Bytes &text, const std::vector<umi::fastq::Record> &recs,
+                              const FastqResult &res, double t_start, double t_read, double t_gpu1)
+{
+    const uint8_t *d = text.data();
+    const size_t n_reads = recs.size(), n = res.n, nb = res.nb;
+    const std::vector<uint64_t> &off = res.off;
+    const std::vector<int32_t> &freq = res.freq;
+    const std::vector<uint32_t> &rep = res.rep, &root = res.root;
+    const std::vector<uint8_t> &kept = res.kept;
+    const umi_stats &st = res.st;
     // survivors in output order: their rep reads in file order
     std::vector<uint32_t> entry_of_rep(n_reads, UINT32_MAX);
     for (size_t e = 0; e < n; e++) entry_of_rep[rep[e]] = (uint32_t)e;
@@ -563,14 +791,9 @@ int run_fastq(const Cli &args, int algo, int merge, HipLib &lib)
             if (e != UINT32_MAX && kept[e]) cluster_id[e] = (uint32_t)n_out++;
         }
         for (size_t e = 0; e < n; e++) cluster_reads[root[e]] += (uint32_t)freq[e];
-        // entry of every read: its sequence's, looked up again per bucket
-        std::vector<std::unordered_map<std::string, uint32_t>> index(nb);
-        for (size_t b = 0; b < nb; b++)
-            for (uint64_t e = off[b]; e < off[b + 1]; e++)
-                index[b].emplace(std::string((const char *)d + recs[rep[e]].seq, recs[rep[e]].len), (uint32_t)e);
         for (size_t i = 0; i < n_reads; i++) {
             const umi::fastq::Record &r = recs[i];
-            const uint32_t e = index[bucket_of_len[r.len]].at(std::string((const char *)d + r.seq, r.len));
+            const uint32_t e = res.entry_of_read[i];
             const uint32_t rt = root[e];
             std::string extra = " cluster_id=" + std::to_string(cluster_id[rt]);
             if (rep[rt] == i) extra += " cluster_size=" + std::to_string(cluster_reads[rt]);
@@ -597,10 +820,10 @@ int run_fastq(const Cli &args, int algo, int merge, HipLib &lib)
     std::fprintf(stderr, args.track_clusters ? "Number of groups of reads: %llu\n" : "Number of reads after deduplicating: %llu\n",
                  (unsigned long long)st.n_kept);
     std::fprintf(stderr,
-                 "phases: read+parse %.3f s, staging (host) %.3f s, gpu init %.3f s, hot path (H2D+GPU+D2H) %.3f s "
+                 "phases: read+parse %.3f s, staging (%s) %.3f s, gpu init %.3f s, hot path (H2D+GPU+D2H) %.3f s "
                  "[%llu pairs, %llu evaluated], write %.3f s\n",
-                 t_read - t_start, t_stage - t_read, t_gpu0 - t_stage, t_gpu1 - t_gpu0, (unsigned long long)st.n_pairs,
-                 (unsigned long long)st.n_pairs_evaluated, t_end - t_gpu1);
+                 t_read - t_start, res.gpu_staged ? "gpu" : "host", res.t_staging, res.t_init, res.t_hot,
+                 (unsigned long long)st.n_pairs, (unsigned long long)st.n_pairs_evaluated, t_end - t_gpu1);
     std::fprintf(stderr, "UMI collapsing finished in %.3f seconds\n", t_end - t_start); // main.rs:97-102
     std::fflush(stderr);
     std::_Exit(0); // (no static destructors: as the BAM path, the process ends without tearing HIP down)
