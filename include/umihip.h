@@ -231,6 +231,33 @@ int umi_stage_reads_wide(umi_ctx *ctx, const uint64_t *align_key, int align_key_
                          const int32_t *score, uint64_t n_reads, int umi_len, int n_words, int merge, uint64_t *keys,
                          uint64_t *nmask, int32_t *freq, uint64_t *rep, uint64_t *bucket_off, uint64_t *n_entries,
                          uint64_t *n_buckets);
+/* Grouped staging: the four calls above with a second per-read key, group_key (the low group_key_bits
+ * bits looked at; 0 = none, group_key may then be NULL, and the call is the plain one).  A position is
+ * then the pair (align_key, group_key): reads of different groups never share a bucket -- a cell barcode's
+ * dense id puts every cell of a single-cell file in buckets of its own.  Buckets are ranked by first
+ * appearance of the pair; merge, rank order, rep, outputs and errors as above.  The device sort takes the
+ * group bits as more key bits: where align_key_bits + group_key_bits fit 64 bits the two are one word
+ * (and with the UMI's 7 bits per 3 bases still one composed sort key where that fits 64 bits), else the
+ * group word is sorted in passes of its own behind the alignment key's, and bucket boundaries look at
+ * both words.  group_key_bits in 0..64, else UMI_ERR_ARG.  The plain calls are these with 0. */
+int umi_stage_reads_grouped_device(umi_ctx *ctx, const uint64_t *d_align_key, int align_key_bits,
+                                   const uint64_t *d_group_key, int group_key_bits, const uint8_t *d_umi_ascii,
+                                   const int32_t *d_score, uint64_t n_reads, int umi_len, int merge, uint64_t *d_keys,
+                                   uint64_t *d_nmask, int32_t *d_freq, uint64_t *d_rep, uint64_t *d_bucket_off,
+                                   uint64_t *n_entries, uint64_t *n_buckets, void *hip_stream);
+int umi_stage_reads_grouped(umi_ctx *ctx, const uint64_t *align_key, int align_key_bits, const uint64_t *group_key,
+                            int group_key_bits, const uint8_t *umi_ascii, const int32_t *score, uint64_t n_reads, int umi_len,
+                            int merge, uint64_t *keys, uint64_t *nmask, int32_t *freq, uint64_t *rep, uint64_t *bucket_off,
+                            uint64_t *n_entries, uint64_t *n_buckets);
+int umi_stage_reads_grouped_wide_device(umi_ctx *ctx, const uint64_t *d_align_key, int align_key_bits,
+                                        const uint64_t *d_group_key, int group_key_bits, const uint8_t *d_umi_ascii,
+                                        const int32_t *d_score, uint64_t n_reads, int umi_len, int n_words, int merge,
+                                        uint64_t *d_keys, uint64_t *d_nmask, int32_t *d_freq, uint64_t *d_rep,
+                                        uint64_t *d_bucket_off, uint64_t *n_entries, uint64_t *n_buckets, void *hip_stream);
+int umi_stage_reads_grouped_wide(umi_ctx *ctx, const uint64_t *align_key, int align_key_bits, const uint64_t *group_key,
+                                 int group_key_bits, const uint8_t *umi_ascii, const int32_t *score, uint64_t n_reads,
+                                 int umi_len, int n_words, int merge, uint64_t *keys, uint64_t *nmask, int32_t *freq,
+                                 uint64_t *rep, uint64_t *bucket_off, uint64_t *n_entries, uint64_t *n_buckets);
 
 /* ---- read staging of whole reads (FASTQ mode): the staging of run_fastq on the device.
  * in : read i is len[i] bases at text + seq_pos[i]; its quality, as long, at text + qual_pos[i]

@@ -1,0 +1,246 @@
+"""Test-side model of --umi-tag / --per-cell (umicollapse_main.cpp): the read loop of
+src/deduplicate_sam.rs:93-177 with the UMI taken from an aux tag and the position keyed by
+(alignment, cell barcode), restated in plain Python over tests/bamio.py's record helpers.  Expected
+survivors come from the oracle's staging and batched dedup, --paired through bamio.paired_writer.
+Also: a synthetic BAM writer with RX / UB / CB tags and aux fields of every type in front of them."""
+import struct
+
+import numpy as np
+
+import bamio
+import oracle as orc
+
+AUX_SIZES = {"A": 1, "c": 1, "C": 1, "s": 2, "S": 2, "i": 4, "I": 4, "f": 4}
+
+
+def aux_z(tag, text):
+    return tag.encode() + b"Z" + (text.encode() if isinstance(text, str) else text) + b"\0"
+
+
+def aux_fields_before(rng):
+    """a few fields of the other types, a B array among them, to walk past before the wanted tag"""
+    out = b"NMc" + struct.pack("<b", int(rng.integers(-3, 4)))
+    out += b"ASi" + struct.pack("<i", int(rng.integers(0, 200)))
+    out += b"XSs" + struct.pack("<h", -7)
+    out += b"XAA" + b"Q"
+    out += b"XFf" + struct.pack("<f", 0.25)
+    out += b"XHH" + b"1AE301" + b"\0"
+    sub = "cCsSiIf"[int(rng.integers(0, 7))]
+    cnt = int(rng.integers(0, 5))
+    fmt = {"c": "b", "C": "B", "s": "h", "S": "H", "i": "i", "I": "I", "f": "f"}[sub]
+    out += b"XBB" + sub.encode() + struct.pack("<I", cnt) + struct.pack("<%d%s" % (cnt, fmt), *range(cnt))
+    out += b"MDZ" + b"50\0"
+    return out
+
+
+def parse_aux(rec):
+    """{tag: (type, value bytes)} of a record's aux block (the first of a repeated tag wins)"""
+    l_rn, n_cig, l_seq = rec[4 + 8], struct.unpack_from("<H", rec, 4 + 12)[0], struct.unpack_from("<i", rec, 4 + 16)[0]
+    o = 4 + 32 + l_rn + 4 * n_cig + (l_seq + 1) // 2 + l_seq
+    out = {}
+    while o < len(rec):
+        tag, ty = rec[o:o + 2].decode(), chr(rec[o + 2])
+        o += 3
+        if ty in "ZH":
+            e = rec.index(b"\0", o)
+            val, o = rec[o:e], e + 1
+        elif ty == "B":
+            sub, cnt = chr(rec[o]), struct.unpack_from("<I", rec, o + 1)[0]
+            n = 5 + cnt * AUX_SIZES[sub]
+            val, o = rec[o:o + n], o + n
+        else:
+            n = AUX_SIZES[ty]
+            val, o = rec[o:o + n], o + n
+        out.setdefault(tag, (ty, val))
+    return out
+
+
+def tagged_bam(seed, n_positions, reads_per_position, umi_len=12, n_cells=6, err=0.02, miss_umi=0.04,
+               miss_cell=0.04, umi_in_name=True, paired=False):
+    """Coordinate-ordered BAM whose reads carry their UMI in RX and UB (and, unless umi_in_name is
+    False, after '_' in the name too) and a 10x-style barcode "<16 bases>-1" in CB, behind fields of
+    every other type.  A share of the reads lacks RX+UB or CB; the same (position, UMI) occurs in
+    several cells.  With `paired`, first mates (which carry the tags) and their second mates."""
+    from umi_collapse_rs_amd import synth
+    rng = np.random.default_rng(seed)
+    pos, bases = synth.molecule_reads(seed, n_positions, reads_per_position, umi_len, err=err)
+    cells = ["".join("ACGT"[x] for x in rng.integers(0, 4, 16)) + "-1" for _ in range(n_cells)]
+    refs = [("chr1", 10_000_000), ("chr2", 5_000_000)]
+    items = []
+    for i in range(len(pos)):
+        umi = synth.BASES[bases[i]].tobytes().decode()
+        if rng.random() < 0.02:
+            umi = umi[:3] + "N" + umi[4:]
+        name = "r%d_%s" % (i, umi) if umi_in_name else "r%d" % i
+        tid = 0 if pos[i] % 5 else 1
+        p0 = 1000 + 10 * int(pos[i])
+        flag = 0x10 if rng.random() < 0.1 else 0
+        if rng.random() < 0.02:
+            flag |= 0x4
+        tags = aux_fields_before(rng)
+        if rng.random() >= miss_umi:
+            tags += aux_z("RX", umi) + aux_z("UB", umi)
+        if rng.random() >= miss_cell:
+            # (cells drawn per read, so one molecule's UMI lands in several cells)
+            tags += aux_z("CB", cells[int(rng.integers(0, n_cells))])
+        tags += b"xxi" + struct.pack("<i", i)  # (a field behind the wanted ones)
+        quals = rng.integers(20, 41, 50).astype(np.uint8).tobytes()
+        mapq = int(rng.integers(0, 61))
+        if paired:
+            tl = int(rng.choice([180, 200]))
+            mp = p0 + tl - 50
+            items.append((tid, p0, i, bamio.make_record(name, 0x1 | 0x2 | 0x40 | 0x20 | (flag & 0x4), tid, p0, mapq,
+                                                        [("M", 50)], 50, quals, tags=tags, mtid=tid, mpos=mp,
+                                                        tlen=tl)))
+            items.append((tid, mp, i, bamio.make_record(name, 0x1 | 0x2 | 0x80 | 0x10, tid, mp, mapq, [("M", 50)],
+                                                        50, quals, mtid=tid, mpos=p0, tlen=-tl)))
+        else:
+            items.append((tid, p0, i, bamio.make_record(name, flag, tid, p0, mapq, [("M", 50)], 50, quals,
+                                                        tags=tags)))
+    items.sort(key=lambda t: (t[0], t[1], t[2]))
+    return bamio.make_header(refs), [t[3] for t in items]
+
+
+def stage(recs, umi_tag=None, per_cell=False, cell_tag="CB", merge="mapqual", umi_len=0, sep=95,
+          keep_unmapped=False, paired=False):
+    """The staging of umicollapse with --umi-tag / --per-cell: returns (staged dict with keys, nmask,
+    freq, rep (record indices), bucket_off, bucket_cell, umi_len, counters, reads), pre-written
+    record indices)."""
+    rows, pre = [], []  # rows: (record index, alignment key, cell, UMI bytes, score)
+    counters = dict(total=0, unmapped=0, no_umi=0, no_cell=0)
+    for i, rec in enumerate(recs):
+        r = bamio.parse_record(rec)
+        if paired and r["flag"] & 0x1 and r["flag"] & 0x80:
+            continue
+        counters["total"] += 1
+        if r["flag"] & 0x4:
+            counters["unmapped"] += 1
+            if keep_unmapped:
+                pre.append(i)
+            continue
+        if paired and r["flag"] & 0x1 and r["flag"] & 0x8:
+            counters["unmapped"] += 1
+            continue
+        aux = parse_aux(rec)
+        miss = False
+        umi = None
+        if umi_tag:
+            if umi_tag in aux:
+                assert aux[umi_tag][0] == "Z"
+                umi = aux[umi_tag][1]
+            else:
+                counters["no_umi"] += 1
+                miss = True
+        cell = b""
+        if per_cell:
+            if cell_tag in aux:
+                cell = aux[cell_tag][1]
+            else:
+                counters["no_cell"] += 1
+                miss = True
+        if miss:
+            continue
+        if umi is None:
+            if umi_len == 0:
+                umi_len = bamio.detect_umi_length(r["qname"], sep)
+            at = r["qname"].index(bytes([sep])) + 1
+            umi = r["qname"][at:at + umi_len]
+        elif umi_len == 0:
+            umi_len = len(umi)
+        assert len(umi) == umi_len
+        akey = (bool(r["flag"] & 0x10), bamio.unclipped_pos(r), r["tid"])
+        if paired:
+            akey += (r["tlen"],)
+        score = r["mapq"] if merge == "mapqual" else orc.avg_qual(list(r["qual"]))
+        rows.append((i, akey, cell, umi, score))
+    cell_id, group_id, positions = {}, {}, set()
+    bucket_ids, bucket_cell = [], []
+    for _, akey, cell, _, _ in rows:
+        c = cell_id.setdefault(cell, len(cell_id))
+        g = group_id.get((akey, c))
+        if g is None:
+            g = group_id[(akey, c)] = len(group_id)
+            bucket_cell.append(c)
+        positions.add(akey)
+        bucket_ids.append(g)
+    umis = [u for _, _, _, u, _ in rows]
+    scores = [s for _, _, _, _, s in rows]
+    m = 0 if merge == "any" else 1
+    if umi_len > 21:
+        from helpers import stage_model
+        w_umis, freq, rep, off = stage_model(bucket_ids, [u.decode() for u in umis], scores, m)
+        keys, nmask = orc.encode_keys_wide(w_umis)
+        st = dict(keys=keys, nmask=nmask, freq=freq, rep=rep, bucket_off=off)
+    else:
+        ub = np.frombuffer(b"".join(umis), dtype=np.uint8) if umis else np.zeros(0, np.uint8)
+        st = orc.stage_reads(bucket_ids, ub, scores, max(umi_len, 1), merge=m)
+    rec_idx = np.array([i for i, _, _, _, _ in rows], dtype=np.int64)
+    st["rep"] = rec_idx[st["rep"].astype(np.int64)] if len(rows) else np.zeros(0, np.int64)
+    st["bucket_cell"] = np.array(bucket_cell, np.uint32)
+    st["umi_len"] = umi_len
+    counters["positions"] = len(positions)
+    counters["groups"] = len(group_id)
+    st["counters"] = counters
+    st["reads"] = [(i, g, u) for (i, _, _, u, _), g in zip(rows, bucket_ids)]
+    return st, pre
+
+
+def expected_output(recs, k=1, p=0.5, algo="dir", **kw):
+    """(expected records in output order, staged dict, reads kept)"""
+    st, pre = stage(recs, **kw)
+    dedup = orc.dedup_batch_wide if st["keys"].ndim == 2 else orc.dedup_batch
+    kept, _, _ = dedup(st["keys"], st["nmask"], st["freq"], st["bucket_off"], max(st["umi_len"], 1), k, p,
+                       0 if algo == "dir" else 1)
+    out = list(pre) + [int(st["rep"][i]) for i in np.nonzero(kept)[0]]
+    if kw.get("paired"):
+        out = bamio.paired_writer(recs, out)
+    return [recs[i] for i in out], st, int(kept.sum())
+
+
+def expected_tagged_output(recs, k=1, p=0.5, algo="dir", **kw):
+    """--tag: every staged read in file order with MI / cs / su of its (position, cell) cluster
+    (the definition of bamio.expected_tagged_output, buckets per (position, cell))."""
+    st, pre = stage(recs, **kw)
+    kept, root, _ = orc.dedup_batch(st["keys"], st["nmask"], st["freq"], st["bucket_off"], st["umi_len"], k, p,
+                                    0 if algo == "dir" else 1)
+    cluster_id = np.cumsum(kept) - 1
+    cluster_reads = np.zeros(len(kept), np.int64)
+    np.add.at(cluster_reads, root.astype(np.int64), st["freq"])
+    index = {}
+    off = st["bucket_off"].astype(np.int64)
+    for b in range(len(off) - 1):
+        for e in range(off[b], off[b + 1]):
+            index[(b, int(st["keys"][e]))] = e
+    out = [recs[i] for i in pre]
+    for ri, b, umi in st["reads"]:
+        key, _ = orc.encode_keys([umi.decode()])
+        e = index[(b, int(key[0]))]
+        r = int(root[e])
+        tags = b"".join(t + b"i" + struct.pack("<i", int(v)) for t, v in
+                        ((b"MI", cluster_id[r]), (b"cs", cluster_reads[r]), (b"su", st["freq"][e])))
+        body = recs[ri][4:] + tags
+        out.append(struct.pack("<i", len(body)) + body)
+    return out, st, int(kept.sum())
+
+
+def read_staging(path, per_cell=False):
+    """the --dump-staging file: header (n, nb, umi_len, n_words), keys, nmask, freq, rep, bucket_off,
+    and with --per-cell every bucket's cell id"""
+    with open(path, "rb") as f:
+        n, nb, umi_len, w = struct.unpack("<4Q", f.read(32))
+        keys = np.frombuffer(f.read(8 * n * w), np.uint64).reshape(n, w)
+        nmask = np.frombuffer(f.read(8 * n * w), np.uint64).reshape(n, w)
+        freq = np.frombuffer(f.read(4 * n), np.int32)
+        rep = np.frombuffer(f.read(4 * n), np.uint32)
+        off = np.frombuffer(f.read(8 * (nb + 1)), np.uint64)
+        cell = np.frombuffer(f.read(4 * nb), np.uint32) if per_cell else None
+        rest = f.read()
+    assert rest == b""
+    if w == 1:
+        keys, nmask = keys[:, 0], nmask[:, 0]
+    return dict(keys=keys, nmask=nmask, freq=freq, rep=rep, bucket_off=off, bucket_cell=cell, umi_len=umi_len)
+
+
+def write_bam(path, header, recs):
+    with open(path, "wb") as f:
+        f.write(bamio.bgzf_compress(header + b"".join(recs)))

@@ -63,6 +63,18 @@ SIGNATURES = {
                                               C.c_void_p, _u64p, _u64p, C.c_void_p]),
     "umi_stage_reads_wide": (C.c_int, [C.c_void_p, _u64p, C.c_int, _u8p, _i32p, C.c_uint64, C.c_int, C.c_int, C.c_int,
                                        _u64p, _u64p, _i32p, _u64p, _u64p, _u64p, _u64p]),
+    "umi_stage_reads_grouped_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, _u64p, _u64p, C.c_void_p]),
+    "umi_stage_reads_grouped_wide_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                      C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      _u64p, _u64p, C.c_void_p]),
+    "umi_stage_reads_grouped": (C.c_int, [C.c_void_p, _u64p, C.c_int, _u64p, C.c_int, _u8p, _i32p, C.c_uint64, C.c_int,
+                                          C.c_int, _u64p, _u64p, _i32p, _u64p, _u64p, _u64p, _u64p]),
+    "umi_stage_reads_grouped_wide": (C.c_int, [C.c_void_p, _u64p, C.c_int, _u64p, C.c_int, _u8p, _i32p, C.c_uint64,
+                                               C.c_int, C.c_int, C.c_int, _u64p, _u64p, _i32p, _u64p, _u64p, _u64p,
+                                               _u64p]),
     "umi_stage_seqs_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p,
                                         _i32p, _u64p, _u64p, C.POINTER(C.c_int), C.c_void_p]),

@@ -262,6 +262,54 @@ class Context:
         e, b = int(ne.value), int(nb.value)
         return dict(keys=keys[:e], nmask=nm[:e], freq=freq[:e], rep=rep[:e], bucket_off=boff[:b + 1])
 
+    def stage_reads_grouped(self, align_key, group_key, umi_bytes, score, umi_len, merge=1, align_key_bits=64,
+                            group_key_bits=64):
+        """stage_reads with a second per-read key (umi_stage_reads_grouped): positions are
+        (align_key, group_key) pairs, e.g. (alignment, cell barcode id); group_key_bits=0 is stage_reads."""
+        return self._stage_grouped(align_key, group_key, umi_bytes, score, umi_len, merge, align_key_bits,
+                                   group_key_bits, wide=False)
+
+    def stage_reads_grouped_wide(self, align_key, group_key, umi_bytes, score, umi_len, merge=1, align_key_bits=64,
+                                 group_key_bits=64):
+        """stage_reads_wide with a second per-read key (umi_stage_reads_grouped_wide): keys / nmask
+        come back as uint64 [n_entries, n_words]."""
+        return self._stage_grouped(align_key, group_key, umi_bytes, score, umi_len, merge, align_key_bits,
+                                   group_key_bits, wide=True)
+
+    def _stage_grouped(self, align_key, group_key, umi_bytes, score, umi_len, merge, align_key_bits, group_key_bits,
+                       wide):
+        align_key = np.ascontiguousarray(align_key, dtype=np.uint64)
+        group_key = np.ascontiguousarray(group_key, dtype=np.uint64)
+        umi_bytes = np.ascontiguousarray(umi_bytes, dtype=np.uint8)
+        sc = None if score is None else np.ascontiguousarray(score, dtype=np.int32)
+        n, w = len(align_key), (3 * umi_len + 63) // 64
+        assert len(group_key) == n and len(umi_bytes) == n * umi_len
+        m = max(1, n)
+        shape = (m, w) if wide else m
+        keys, nm = np.zeros(shape, np.uint64), np.zeros(shape, np.uint64)
+        rep, freq, boff = np.zeros(m, np.uint64), np.zeros(m, np.int32), np.zeros(m + 1, np.uint64)
+        ne, nb = C.c_uint64(0), C.c_uint64(0)
+        head = (self._h, ptr(align_key, C.c_uint64), align_key_bits, ptr(group_key, C.c_uint64), group_key_bits,
+                ptr(umi_bytes, C.c_uint8), ptr(sc, C.c_int32), n, umi_len)
+        tail = (merge, ptr(keys, C.c_uint64), ptr(nm, C.c_uint64), ptr(freq, C.c_int32), ptr(rep, C.c_uint64),
+                ptr(boff, C.c_uint64), C.byref(ne), C.byref(nb))
+        if wide:
+            check(load().umi_stage_reads_grouped_wide(*head, w, *tail))
+        else:
+            check(load().umi_stage_reads_grouped(*head, *tail))
+        e, b = int(ne.value), int(nb.value)
+        return dict(keys=keys[:e], nmask=nm[:e], freq=freq[:e], rep=rep[:e], bucket_off=boff[:b + 1])
+
+    def stage_reads_grouped_device(self, d_align_key, d_group_key, d_umi, d_score, n_reads, umi_len, d_keys, d_nmask,
+                                   d_freq, d_rep, d_bucket_off, merge=1, align_key_bits=64, group_key_bits=64, stream=0):
+        """umi_stage_reads_grouped_device (raw device pointers); returns (n_entries, n_buckets)."""
+        ne, nb = C.c_uint64(0), C.c_uint64(0)
+        check(load().umi_stage_reads_grouped_device(self._h, d_align_key, align_key_bits, d_group_key or None,
+                                                    group_key_bits, d_umi, d_score or None, n_reads, umi_len, merge,
+                                                    d_keys, d_nmask or None, d_freq, d_rep, d_bucket_off, C.byref(ne),
+                                                    C.byref(nb), stream or None))
+        return int(ne.value), int(nb.value)
+
     def stage_reads_device(self, d_align_key, d_umi, d_score, n_reads, umi_len, d_keys, d_nmask, d_freq,
                            d_rep, d_bucket_off, merge=1, align_key_bits=64, stream=0):
         """The same with everything in device memory (raw pointers); returns (n_entries, n_buckets)."""

@@ -230,7 +230,7 @@ struct umi_ctx {
     // staging for the host-buffer entry point
     DevBuf in_keys, in_nmask, in_freq, out_kept, out_root;
     // read staging (umi_stage_reads*): workspace; device copies of the host-buffer form
-    DevBuf stage_ws, st_align, st_umi, st_score, st_keys, st_nmask, st_freq, st_rep, st_boff;
+    DevBuf stage_ws, st_align, st_group, st_umi, st_score, st_keys, st_nmask, st_freq, st_rep, st_boff;
     // ... and of umi_stage_seqs: the text, seq_pos then qual_pos, the lengths, entry_of_read
     DevBuf sq_text, sq_pos, sq_len, sq_eor;
     // whole-read keys (umi_dedup_seqs*): group table, records and their sort, runs, tile tasks
@@ -1853,7 +1853,7 @@ void umi_ctx_destroy(umi_ctx *ctx)
                       &ctx->edge_dist, &ctx->counters,
                       &ctx->boff,    &ctx->status,   &ctx->blocked,  &ctx->in_keys,
                       &ctx->in_nmask, &ctx->in_freq, &ctx->out_kept, &ctx->out_root,
-                      &ctx->stage_ws, &ctx->st_align, &ctx->st_umi, &ctx->st_score, &ctx->st_keys, &ctx->st_nmask,
+                      &ctx->stage_ws, &ctx->st_align, &ctx->st_group, &ctx->st_umi, &ctx->st_score, &ctx->st_keys, &ctx->st_nmask,
                       &ctx->st_freq, &ctx->st_rep, &ctx->st_boff, &ctx->sq_text, &ctx->sq_pos, &ctx->sq_len, &ctx->sq_eor,
                       &ctx->seq_groups, &ctx->seq_ka, &ctx->seq_kb, &ctx->seq_va, &ctx->seq_vb, &ctx->seq_flag,
                       &ctx->seq_runid, &ctx->seq_rs, &ctx->seq_tend, &ctx->seq_tmp};
@@ -2144,10 +2144,11 @@ int umi_dedup_batch_wide(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nma
                               percentage, algo, adj_max_freq, kept, root, stats, n_words);
 }
 
-int umi_stage_reads_wide_device(umi_ctx *ctx, const uint64_t *d_align_key, int align_key_bits, const uint8_t *d_umi_ascii,
-                                const int32_t *d_score, uint64_t n_reads, int umi_len, int n_words, int merge,
-                                uint64_t *d_keys, uint64_t *d_nmask, int32_t *d_freq, uint64_t *d_rep,
-                                uint64_t *d_bucket_off, uint64_t *n_entries, uint64_t *n_buckets, void *hip_stream)
+int umi_stage_reads_grouped_wide_device(umi_ctx *ctx, const uint64_t *d_align_key, int align_key_bits,
+                                        const uint64_t *d_group_key, int group_key_bits, const uint8_t *d_umi_ascii,
+                                        const int32_t *d_score, uint64_t n_reads, int umi_len, int n_words, int merge,
+                                        uint64_t *d_keys, uint64_t *d_nmask, int32_t *d_freq, uint64_t *d_rep,
+                                        uint64_t *d_bucket_off, uint64_t *n_entries, uint64_t *n_buckets, void *hip_stream)
 {
     if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
     if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (staging runs on the first device of a multi-device context)
@@ -2157,19 +2158,43 @@ int umi_stage_reads_wide_device(umi_ctx *ctx, const uint64_t *d_align_key, int a
     if (umi_len < 1 || umi_len > UMI_MAX_WIDE_UMI_LEN) return fail(UMI_ERR_ARG, "umi_len %d outside 1..%d", umi_len, UMI_MAX_WIDE_UMI_LEN);
     if (n_words != wide_words(umi_len)) return fail(UMI_ERR_ARG, "n_words must be %d for umi_len %d", wide_words(umi_len), umi_len);
     if (align_key_bits < 1 || align_key_bits > 64) return fail(UMI_ERR_ARG, "align_key_bits must be in 1..64");
+    if (group_key_bits < 0 || group_key_bits > 64) return fail(UMI_ERR_ARG, "group_key_bits must be in 0..64");
+    if (group_key_bits && n_reads && !d_group_key) return fail(UMI_ERR_ARG, "d_group_key is NULL with group_key_bits %d", group_key_bits);
     if (merge != 0 && merge != 1) return fail(UMI_ERR_ARG, "merge must be 0 (any) or 1 (highest score, first on ties)");
     if (n_reads >= (1ull << 30)) return fail(UMI_ERR_ARG, "%llu reads exceed the 30-bit index space of one staging call", (unsigned long long)n_reads);
     HIP_TRY(hipSetDevice(ctx->device));
     settle(ctx);
     int rc;
-    if ((rc = ctx->stage_ws.reserve(stage_workspace_bytes((uint32_t)n_reads, n_words)))) return rc;
+    if ((rc = ctx->stage_ws.reserve(stage_workspace_bytes((uint32_t)n_reads, n_words, group_key_bits > 0)))) return rc;
     hipStream_t s = (hipStream_t)hip_stream; // (NULL = the default stream, as in every device-pointer call)
-    const int r = stage_reads_on_device(ctx->stage_ws.p, d_align_key, align_key_bits, d_umi_ascii, d_score,
-                                        (uint32_t)n_reads, umi_len, n_words, merge, d_keys, d_nmask, d_freq, d_rep,
-                                        d_bucket_off, n_entries, n_buckets, ctx->h_counters, s);
+    const int r = stage_reads_on_device(ctx->stage_ws.p, d_align_key, align_key_bits, group_key_bits ? d_group_key : nullptr,
+                                        group_key_bits, d_umi_ascii, d_score, (uint32_t)n_reads, umi_len, n_words, merge,
+                                        d_keys, d_nmask, d_freq, d_rep, d_bucket_off, n_entries, n_buckets, ctx->h_counters, s);
     if (r == 1) return fail(UMI_ERR_CHAR, "Unknown character in UMI sequence");
     if (r < 0) return fail(UMI_ERR_HIP, "staging: %s", hipGetErrorString((hipError_t)(-r)));
     return UMI_OK;
+}
+
+int umi_stage_reads_wide_device(umi_ctx *ctx, const uint64_t *d_align_key, int align_key_bits, const uint8_t *d_umi_ascii,
+                                const int32_t *d_score, uint64_t n_reads, int umi_len, int n_words, int merge,
+                                uint64_t *d_keys, uint64_t *d_nmask, int32_t *d_freq, uint64_t *d_rep,
+                                uint64_t *d_bucket_off, uint64_t *n_entries, uint64_t *n_buckets, void *hip_stream)
+{
+    return umi_stage_reads_grouped_wide_device(ctx, d_align_key, align_key_bits, nullptr, 0, d_umi_ascii, d_score, n_reads,
+                                               umi_len, n_words, merge, d_keys, d_nmask, d_freq, d_rep, d_bucket_off,
+                                               n_entries, n_buckets, hip_stream);
+}
+
+int umi_stage_reads_grouped_device(umi_ctx *ctx, const uint64_t *d_align_key, int align_key_bits,
+                                   const uint64_t *d_group_key, int group_key_bits, const uint8_t *d_umi_ascii,
+                                   const int32_t *d_score, uint64_t n_reads, int umi_len, int merge, uint64_t *d_keys,
+                                   uint64_t *d_nmask, int32_t *d_freq, uint64_t *d_rep, uint64_t *d_bucket_off,
+                                   uint64_t *n_entries, uint64_t *n_buckets, void *hip_stream)
+{
+    if (umi_len < 1 || umi_len > UMI_MAX_UMI_LEN) return fail(UMI_ERR_ARG, "umi_len %d outside 1..%d", umi_len, UMI_MAX_UMI_LEN);
+    return umi_stage_reads_grouped_wide_device(ctx, d_align_key, align_key_bits, d_group_key, group_key_bits, d_umi_ascii,
+                                               d_score, n_reads, umi_len, 1, merge, d_keys, d_nmask, d_freq, d_rep,
+                                               d_bucket_off, n_entries, n_buckets, hip_stream);
 }
 
 int umi_stage_reads_device(umi_ctx *ctx, const uint64_t *d_align_key, int align_key_bits, const uint8_t *d_umi_ascii,
@@ -2177,15 +2202,15 @@ int umi_stage_reads_device(umi_ctx *ctx, const uint64_t *d_align_key, int align_
                            uint64_t *d_nmask, int32_t *d_freq, uint64_t *d_rep, uint64_t *d_bucket_off,
                            uint64_t *n_entries, uint64_t *n_buckets, void *hip_stream)
 {
-    if (umi_len < 1 || umi_len > UMI_MAX_UMI_LEN) return fail(UMI_ERR_ARG, "umi_len %d outside 1..%d", umi_len, UMI_MAX_UMI_LEN);
-    return umi_stage_reads_wide_device(ctx, d_align_key, align_key_bits, d_umi_ascii, d_score, n_reads, umi_len, 1, merge,
-                                       d_keys, d_nmask, d_freq, d_rep, d_bucket_off, n_entries, n_buckets, hip_stream);
+    return umi_stage_reads_grouped_device(ctx, d_align_key, align_key_bits, nullptr, 0, d_umi_ascii, d_score, n_reads, umi_len,
+                                          merge, d_keys, d_nmask, d_freq, d_rep, d_bucket_off, n_entries, n_buckets,
+                                          hip_stream);
 }
 
-int umi_stage_reads_wide(umi_ctx *ctx, const uint64_t *align_key, int align_key_bits, const uint8_t *umi_ascii,
-                         const int32_t *score, uint64_t n_reads, int umi_len, int n_words, int merge, uint64_t *keys,
-                         uint64_t *nmask, int32_t *freq, uint64_t *rep, uint64_t *bucket_off, uint64_t *n_entries,
-                         uint64_t *n_buckets)
+int umi_stage_reads_grouped_wide(umi_ctx *ctx, const uint64_t *align_key, int align_key_bits, const uint64_t *group_key,
+                                 int group_key_bits, const uint8_t *umi_ascii, const int32_t *score, uint64_t n_reads,
+                                 int umi_len, int n_words, int merge, uint64_t *keys, uint64_t *nmask, int32_t *freq,
+                                 uint64_t *rep, uint64_t *bucket_off, uint64_t *n_entries, uint64_t *n_buckets)
 {
     if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
     if (!ctx->subs.empty()) ctx = ctx->subs[0];
@@ -2193,25 +2218,31 @@ int umi_stage_reads_wide(umi_ctx *ctx, const uint64_t *align_key, int align_key_
     if (n_reads && (!align_key || !umi_ascii || !keys || !freq || !rep)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
     if (umi_len < 1 || umi_len > UMI_MAX_WIDE_UMI_LEN) return fail(UMI_ERR_ARG, "umi_len %d outside 1..%d", umi_len, UMI_MAX_WIDE_UMI_LEN);
     if (n_words != wide_words(umi_len)) return fail(UMI_ERR_ARG, "n_words must be %d for umi_len %d", wide_words(umi_len), umi_len);
+    if (group_key_bits < 0 || group_key_bits > 64) return fail(UMI_ERR_ARG, "group_key_bits must be in 0..64");
+    if (group_key_bits && n_reads && !group_key) return fail(UMI_ERR_ARG, "group_key is NULL with group_key_bits %d", group_key_bits);
     if (n_reads >= (1ull << 30)) return fail(UMI_ERR_ARG, "%llu reads exceed the 30-bit index space of one staging call", (unsigned long long)n_reads);
     HIP_TRY(hipSetDevice(ctx->device));
     int rc;
     const size_t n = (size_t)n_reads, m = std::max<size_t>(n, 1), kw = 8 * (size_t)n_words;
     if ((rc = ctx->st_align.reserve(m * 8)) || (rc = ctx->st_umi.reserve(m * (size_t)umi_len)) ||
         (rc = ctx->st_score.reserve(m * 4)) || (rc = ctx->st_keys.reserve(m * kw)) || (rc = ctx->st_nmask.reserve(m * kw)) ||
-        (rc = ctx->st_freq.reserve(m * 4)) || (rc = ctx->st_rep.reserve(m * 8)) || (rc = ctx->st_boff.reserve((m + 1) * 8)))
+        (rc = ctx->st_freq.reserve(m * 4)) || (rc = ctx->st_rep.reserve(m * 8)) || (rc = ctx->st_boff.reserve((m + 1) * 8)) ||
+        (group_key_bits && (rc = ctx->st_group.reserve(m * 8))))
         return rc;
     hipStream_t s = ctx->own_stream;
     if (n) {
         HIP_TRY(hipMemcpyAsync(ctx->st_align.p, align_key, n * 8, hipMemcpyHostToDevice, s));
+        if (group_key_bits) HIP_TRY(hipMemcpyAsync(ctx->st_group.p, group_key, n * 8, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(ctx->st_umi.p, umi_ascii, n * (size_t)umi_len, hipMemcpyHostToDevice, s));
         if (score) HIP_TRY(hipMemcpyAsync(ctx->st_score.p, score, n * 4, hipMemcpyHostToDevice, s));
     }
-    if ((rc = umi_stage_reads_wide_device(ctx, ctx->st_align.as<uint64_t>(), align_key_bits, ctx->st_umi.as<uint8_t>(),
-                                          score ? ctx->st_score.as<int32_t>() : nullptr, n_reads, umi_len, n_words, merge,
-                                          ctx->st_keys.as<uint64_t>(), ctx->st_nmask.as<uint64_t>(),
-                                          ctx->st_freq.as<int32_t>(), ctx->st_rep.as<uint64_t>(),
-                                          ctx->st_boff.as<uint64_t>(), n_entries, n_buckets, s)))
+    if ((rc = umi_stage_reads_grouped_wide_device(ctx, ctx->st_align.as<uint64_t>(), align_key_bits,
+                                                  group_key_bits ? ctx->st_group.as<uint64_t>() : nullptr, group_key_bits,
+                                                  ctx->st_umi.as<uint8_t>(), score ? ctx->st_score.as<int32_t>() : nullptr,
+                                                  n_reads, umi_len, n_words, merge, ctx->st_keys.as<uint64_t>(),
+                                                  ctx->st_nmask.as<uint64_t>(), ctx->st_freq.as<int32_t>(),
+                                                  ctx->st_rep.as<uint64_t>(), ctx->st_boff.as<uint64_t>(), n_entries,
+                                                  n_buckets, s)))
         return rc;
     const size_t e = (size_t)*n_entries, b = (size_t)*n_buckets;
     if (e) {
@@ -2225,13 +2256,31 @@ int umi_stage_reads_wide(umi_ctx *ctx, const uint64_t *align_key, int align_key_
     return UMI_OK;
 }
 
+int umi_stage_reads_wide(umi_ctx *ctx, const uint64_t *align_key, int align_key_bits, const uint8_t *umi_ascii,
+                         const int32_t *score, uint64_t n_reads, int umi_len, int n_words, int merge, uint64_t *keys,
+                         uint64_t *nmask, int32_t *freq, uint64_t *rep, uint64_t *bucket_off, uint64_t *n_entries,
+                         uint64_t *n_buckets)
+{
+    return umi_stage_reads_grouped_wide(ctx, align_key, align_key_bits, nullptr, 0, umi_ascii, score, n_reads, umi_len, n_words,
+                                        merge, keys, nmask, freq, rep, bucket_off, n_entries, n_buckets);
+}
+
+int umi_stage_reads_grouped(umi_ctx *ctx, const uint64_t *align_key, int align_key_bits, const uint64_t *group_key,
+                            int group_key_bits, const uint8_t *umi_ascii, const int32_t *score, uint64_t n_reads, int umi_len,
+                            int merge, uint64_t *keys, uint64_t *nmask, int32_t *freq, uint64_t *rep, uint64_t *bucket_off,
+                            uint64_t *n_entries, uint64_t *n_buckets)
+{
+    if (umi_len < 1 || umi_len > UMI_MAX_UMI_LEN) return fail(UMI_ERR_ARG, "umi_len %d outside 1..%d", umi_len, UMI_MAX_UMI_LEN);
+    return umi_stage_reads_grouped_wide(ctx, align_key, align_key_bits, group_key, group_key_bits, umi_ascii, score, n_reads,
+                                        umi_len, 1, merge, keys, nmask, freq, rep, bucket_off, n_entries, n_buckets);
+}
+
 int umi_stage_reads(umi_ctx *ctx, const uint64_t *align_key, int align_key_bits, const uint8_t *umi_ascii,
                     const int32_t *score, uint64_t n_reads, int umi_len, int merge, uint64_t *keys, uint64_t *nmask,
                     int32_t *freq, uint64_t *rep, uint64_t *bucket_off, uint64_t *n_entries, uint64_t *n_buckets)
 {
-    if (umi_len < 1 || umi_len > UMI_MAX_UMI_LEN) return fail(UMI_ERR_ARG, "umi_len %d outside 1..%d", umi_len, UMI_MAX_UMI_LEN);
-    return umi_stage_reads_wide(ctx, align_key, align_key_bits, umi_ascii, score, n_reads, umi_len, 1, merge, keys, nmask,
-                                freq, rep, bucket_off, n_entries, n_buckets);
+    return umi_stage_reads_grouped(ctx, align_key, align_key_bits, nullptr, 0, umi_ascii, score, n_reads, umi_len, merge, keys,
+                                   nmask, freq, rep, bucket_off, n_entries, n_buckets);
 }
 
 int umi_stage_seqs_device(umi_ctx *ctx, const uint8_t *d_text, const uint64_t *d_seq_pos, const uint64_t *d_qual_pos,

@@ -332,11 +332,14 @@ hipError_t launch_seq_runs(const uint64_t *rkey, uint32_t n_rec, uint64_t *flag,
 hipError_t launch_seq_pairs(const SeqPairArgs &a, uint32_t n_blocks, hipStream_t s);
 
 // ---- read staging on the device (umihip_stage.hip) ----
-size_t stage_workspace_bytes(uint32_t n_reads, int n_words);
+size_t stage_workspace_bytes(uint32_t n_reads, int n_words, bool grouped = false);
 // reads (alignment key, UMI text, score) -> entries in canonical order + bucket table, all device
 // memory (keys / nmask: n_words words per entry); h_pinned4: four pinned 64-bit words for the counts
-// the host needs on the way.  0 ok; 1 a character outside ATCGN; negative: -(hipError_t)
-int stage_reads_on_device(void *workspace, const uint64_t *d_align, int align_bits, const uint8_t *d_umi,
+// the host needs on the way.  d_group / group_bits (null / 0: none): a second per-read key, positions
+// are (alignment, group); the workspace must then be the grouped size.  0 ok; 1 a character outside
+// ATCGN; negative: -(hipError_t)
+int stage_reads_on_device(void *workspace, const uint64_t *d_align, int align_bits, const uint64_t *d_group,
+                          int group_bits, const uint8_t *d_umi,
                           const int32_t *d_score, uint32_t n, int umi_len, int n_words, int merge, uint64_t *d_keys,
                           uint64_t *d_nmask, int32_t *d_freq, uint64_t *d_rep, uint64_t *d_bucket_off,
                           uint64_t *n_entries_out, uint64_t *n_buckets_out, unsigned long long *h_pinned4,

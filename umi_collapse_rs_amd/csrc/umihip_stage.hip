@@ -216,6 +216,19 @@ __global__ __launch_bounds__(256) void stage_encode_kernel(const uint8_t *__rest
     if (__any(bad != 0) && (threadIdx.x & 63) == 0) atomicAdd(&counters[SC_BAD], 1ull);
 }
 
+// The grouped staging's key where alignment and group bits fit one word together:
+// out[i] = group[i] (its low group_bits) above align[i] (its low align_bits).  Everything after it sees
+// one alignment key of align_bits + group_bits bits -- the composed sort key included, where that still
+// fits 64 bits with the UMI.
+__global__ __launch_bounds__(256) void stage_group_combine_kernel(const uint64_t *__restrict__ align, int align_bits,
+                                                                  const uint64_t *__restrict__ group, int group_bits,
+                                                                  uint32_t n, uint64_t *__restrict__ out)
+{
+    const uint64_t am = (1ull << align_bits) - 1ull, gm = group_bits >= 64 ? ~0ull : (1ull << group_bits) - 1ull;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+        out[i] = ((group[i] & gm) << align_bits) | (align[i] & am); // (align_bits < 64 here)
+}
+
 // out[i] = src[pos[i] * stride + word]
 __global__ __launch_bounds__(256) void stage_gather_u64_kernel(const uint64_t *__restrict__ src, int stride, int word,
                                                                const uint32_t *__restrict__ pos, uint32_t n,
@@ -235,6 +248,8 @@ struct SortedReads {
     int umi_bits; // (of the composed key: p5.bits)
     const uint64_t *align;
     int align_bits;
+    const uint64_t *group; // (grouped staging whose alignment and group keys do not fit one word: the
+    int group_bits;        // second word of the position; else null)
     const uint64_t *k3;
     const uint32_t *perm;
     uint32_t n;
@@ -249,7 +264,11 @@ template <int W> __device__ __forceinline__ uint32_t head_bits(const SortedReads
     }
     const uint32_t r = s.perm[i], q = s.perm[i - 1];
     const uint64_t am = s.align_bits >= 64 ? ~0ull : (1ull << s.align_bits) - 1ull;
-    const bool bh = (s.align[r] & am) != (s.align[q] & am);
+    bool bh = (s.align[r] & am) != (s.align[q] & am);
+    if (s.group) {
+        const uint64_t gm = s.group_bits >= 64 ? ~0ull : (1ull << s.group_bits) - 1ull;
+        bh = bh || (s.group[r] & gm) != (s.group[q] & gm);
+    }
     bool h = bh;
 #pragma unroll
     for (int w = 0; w < W; w++) h = h || s.k3[(size_t)r * W + w] != s.k3[(size_t)q * W + w]; // BitSet equality is on the
@@ -944,7 +963,7 @@ struct Carver {
 };
 
 struct StageBufs {
-    uint64_t *k3, *keyA, *keyB, *ent_key, *file_flags;
+    uint64_t *k3, *keyA, *keyB, *ent_key, *file_flags, *gkey;
     unsigned long long *best, *tile_sums;
     uint32_t *idxA, *idxB, *ent_first, *ent_bseq, *head_pos, *bfirst, *numbers, *brank_of, *pos_start;
     EntryRec *rec;
@@ -954,7 +973,8 @@ struct StageBufs {
     size_t tmp_bytes, total;
 };
 
-StageBufs carve(void *ws, uint32_t n, int n_words)
+// grouped: room behind everything else for the combined (group, alignment) keys
+StageBufs carve(void *ws, uint32_t n, int n_words, bool grouped = false)
 {
     Carver c{(char *)ws};
     StageBufs b;
@@ -980,6 +1000,7 @@ StageBufs carve(void *ws, uint32_t n, int n_words)
     b.counters = c.take<unsigned long long>(SC_COUNT);
     b.tmp_bytes = std::max(radix_sort_temp_bytes(n), scan_temp_bytes(n)) + 256;
     b.tmp = c.take<char>(b.tmp_bytes);
+    b.gkey = grouped ? c.take<uint64_t>(m) : nullptr;
     b.total = c.off;
     return b;
 }
@@ -997,7 +1018,7 @@ StageBufs carve(void *ws, uint32_t n, int n_words)
 // and va (free by then) holds the place of every entry.
 template <int W>
 int stage_finish(StageBufs &b, uint32_t *va, const uint64_t *composed, Pack5 p5, const uint64_t *d_align, int align_bits,
-                 const int32_t *d_score, uint32_t n, int umi_len, int merge, uint64_t *d_keys, uint64_t *d_nmask,
+                 const uint64_t *d_group, int group_bits, const int32_t *d_score, uint32_t n, int umi_len, int merge, uint64_t *d_keys, uint64_t *d_nmask,
                  int32_t *d_freq, uint64_t *d_rep, uint64_t *d_bucket_off, uint32_t *d_eor, uint64_t *n_entries_out,
                  uint64_t *n_buckets_out, unsigned long long *h_pinned4, hipStream_t s)
 {
@@ -1010,6 +1031,8 @@ int stage_finish(StageBufs &b, uint32_t *va, const uint64_t *composed, Pack5 p5,
     sr.umi_bits = p5.bits;
     sr.align = d_align;
     sr.align_bits = align_bits;
+    sr.group = d_group;
+    sr.group_bits = group_bits;
     sr.k3 = b.k3;
     sr.perm = va;
     sr.n = n;
@@ -1090,15 +1113,23 @@ int stage_finish(StageBufs &b, uint32_t *va, const uint64_t *composed, Pack5 p5,
 }
 
 template <int W>
-int stage_impl(void *workspace, const uint64_t *d_align, int align_bits, const uint8_t *d_umi, const int32_t *d_score,
-               uint32_t n, int umi_len, int merge, uint64_t *d_keys, uint64_t *d_nmask, int32_t *d_freq, uint64_t *d_rep,
-               uint64_t *d_bucket_off, uint64_t *n_entries_out, uint64_t *n_buckets_out, unsigned long long *h_pinned4,
-               hipStream_t s)
+int stage_impl(void *workspace, const uint64_t *d_align, int align_bits, const uint64_t *d_group, int group_bits,
+               const uint8_t *d_umi, const int32_t *d_score, uint32_t n, int umi_len, int merge, uint64_t *d_keys,
+               uint64_t *d_nmask, int32_t *d_freq, uint64_t *d_rep, uint64_t *d_bucket_off, uint64_t *n_entries_out,
+               uint64_t *n_buckets_out, unsigned long long *h_pinned4, hipStream_t s)
 {
-    StageBufs b = carve(workspace, n, W);
+    StageBufs b = carve(workspace, n, W, group_bits > 0);
+    if (group_bits > 0 && align_bits + group_bits <= 64) {
+        // (alignment and group in one word: from here on the ordinary staging of a wider alignment key)
+        stage_group_combine_kernel<<<grid_for(n), 256, 0, s>>>(d_align, align_bits, d_group, group_bits, n, b.gkey);
+        d_align = b.gkey;
+        align_bits += group_bits;
+        group_bits = 0;
+    }
+    if (group_bits <= 0) d_group = nullptr;
     const int umi_bits = 3 * umi_len;
     const Pack5 p5 = pack5_of(W == 1 ? umi_len : 1);
-    const bool one_key = W == 1 && align_bits + p5.bits <= 64; // the composed sort key fits a word
+    const bool one_key = W == 1 && !d_group && align_bits + p5.bits <= 64; // the composed sort key fits a word
     const int composed_bits = align_bits + p5.bits;
     STAGE_TRY(hipMemsetAsync(b.counters, 0, SC_COUNT * 8, s));
     STAGE_TRY(hipMemsetAsync(b.bfirst, 0xFF, (size_t)n * 4, s)); // (a position per read at most)
@@ -1129,10 +1160,15 @@ int stage_impl(void *workspace, const uint64_t *d_align, int align_bits, const u
         }
         stage_gather_u64_kernel<<<grid_for(n), 256, 0, s>>>(d_align, 1, 0, va, n, ka);
         STAGE_TRY(sort_by(0, align_bits, 0));
+        if (d_group) { // (alignment and group keys over 64 bits together: the group word, most significant, last)
+            stage_gather_u64_kernel<<<grid_for(n), 256, 0, s>>>(d_group, 1, 0, va, n, ka);
+            STAGE_TRY(sort_by(0, group_bits, 0));
+        }
     }
     // (va: the reads' file indices in order; ka: the composed keys in order where there is one)
-    const int r = stage_finish<W>(b, va, one_key ? ka : nullptr, p5, d_align, align_bits, d_score, n, umi_len, merge, d_keys,
-                                  d_nmask, d_freq, d_rep, d_bucket_off, nullptr, n_entries_out, n_buckets_out, h_pinned4, s);
+    const int r = stage_finish<W>(b, va, one_key ? ka : nullptr, p5, d_align, align_bits, d_group, group_bits, d_score, n,
+                                  umi_len, merge, d_keys, d_nmask, d_freq, d_rep, d_bucket_off, nullptr, n_entries_out,
+                                  n_buckets_out, h_pinned4, s);
     if (r) return r;
     STAGE_TRY(hipStreamSynchronize(s));
     return 0;
@@ -1233,8 +1269,8 @@ int seq_impl(void *workspace, const uint8_t *d_text, const uint64_t *d_seq_pos, 
     STAGE_TRY(sort_word(q.len64, 1, 0, info[SI_OR + SI_LEN] ^ info[SI_AND + SI_LEN]));
     // ---- 2-3. as for UMIs, the length as the alignment key (9 bits: 0..256)
     uint64_t E = 0, B = 0;
-    const int r = stage_finish<W>(b, va, nullptr, pack5_of(1), q.len64, 9, use_score ? q.score : nullptr, n, 0, merge, d_keys,
-                                  nullptr, d_freq, d_rep, q.boff, d_eor, &E, &B, h_pinned4, s);
+    const int r = stage_finish<W>(b, va, nullptr, pack5_of(1), q.len64, 9, nullptr, 0, use_score ? q.score : nullptr, n, 0,
+                                  merge, d_keys, nullptr, d_freq, d_rep, q.boff, d_eor, &E, &B, h_pinned4, s);
     if (r) return r;
     if (d_nmask) {
         if (*any_n) seq_nmask_kernel<W><<<grid_for(E), 256, 0, s>>>(d_keys, (uint32_t)E, d_nmask);
@@ -1252,12 +1288,15 @@ int seq_impl(void *workspace, const uint8_t *d_text, const uint64_t *d_seq_pos, 
 
 } // namespace
 
-size_t stage_workspace_bytes(uint32_t n_reads, int n_words) { return carve(nullptr, n_reads, n_words).total; }
+size_t stage_workspace_bytes(uint32_t n_reads, int n_words, bool grouped)
+{
+    return carve(nullptr, n_reads, n_words, grouped).total;
+}
 size_t stage_seqs_workspace_bytes(uint32_t n_reads, int n_words) { return seq_carve(nullptr, n_reads, n_words).total; }
 
 // 0 ok; 1 a character outside ATCGN; negative: -(hipError_t)
-int stage_reads_on_device(void *workspace, const uint64_t *d_align, int align_bits, const uint8_t *d_umi,
-                          const int32_t *d_score, uint32_t n, int umi_len, int n_words, int merge, uint64_t *d_keys,
+int stage_reads_on_device(void *workspace, const uint64_t *d_align, int align_bits, const uint64_t *d_group,
+                          int group_bits, const uint8_t *d_umi, const int32_t *d_score, uint32_t n, int umi_len, int n_words, int merge, uint64_t *d_keys,
                           uint64_t *d_nmask, int32_t *d_freq, uint64_t *d_rep, uint64_t *d_bucket_off,
                           uint64_t *n_entries_out, uint64_t *n_buckets_out, unsigned long long *h_pinned4,
                           hipStream_t s)
@@ -1269,8 +1308,8 @@ int stage_reads_on_device(void *workspace, const uint64_t *d_align, int align_bi
         return 0;
     }
 #define STAGE_W(WN)                                                                                               \
-    return stage_impl<WN>(workspace, d_align, align_bits, d_umi, d_score, n, umi_len, merge, d_keys, d_nmask, d_freq, \
-                          d_rep, d_bucket_off, n_entries_out, n_buckets_out, h_pinned4, s)
+    return stage_impl<WN>(workspace, d_align, align_bits, d_group, group_bits, d_umi, d_score, n, umi_len, merge, d_keys, \
+                          d_nmask, d_freq, d_rep, d_bucket_off, n_entries_out, n_buckets_out, h_pinned4, s)
     switch (n_words) {
     case 1: STAGE_W(1);
     case 2: STAGE_W(2);

@@ -117,7 +117,71 @@ struct Record {
         if (v <= -2147483648.0f) return INT32_MIN;
         return (int32_t)v;
     }
+
+    // The aux block: what follows the qualities up to the end of the record (parse() checked that the
+    // fixed and variable-length fields fit, so this start lies inside the record).
+    const uint8_t *aux() const { return qual() + (size_t)l_seq(); }
 };
+
+// One aux field (SAM spec 4.2.4): its type letter and value bytes.  For Z and H the value is the text
+// without its NUL; for B it is the subtype byte, the count and the elements.
+struct AuxField {
+    char type = 0;
+    const uint8_t *value = nullptr;
+    size_t len = 0;
+};
+enum class AuxFind { absent, found, malformed };
+
+// bytes of one element of an aux field of type t (A c C s S i I f, the B subtypes), 0 for anything else
+inline size_t aux_elem_bytes(uint8_t t)
+{
+    switch (t) {
+    case 'A': case 'c': case 'C': return 1;
+    case 's': case 'S': return 2;
+    case 'i': case 'I': case 'f': return 4;
+    default: return 0;
+    }
+}
+
+// The field `tag` of a record's aux block, every field before it walked and bounds-checked: a field
+// that runs past the record, a Z / H text without its NUL or an unknown type is `malformed`.  The
+// fields after the wanted one are not looked at.
+inline AuxFind find_aux(const Record &r, const char tag[2], AuxField *out)
+{
+    const uint8_t *p = r.aux(), *const end = r.end;
+    while (p < end) {
+        if (end - p < 3) return AuxFind::malformed;
+        const uint8_t t0 = p[0], t1 = p[1], type = p[2];
+        const uint8_t *v = p + 3;
+        size_t len;
+        if (type == 'Z' || type == 'H') {
+            const uint8_t *nul = (const uint8_t *)std::memchr(v, 0, (size_t)(end - v));
+            if (!nul) return AuxFind::malformed;
+            len = (size_t)(nul - v);
+            p = nul + 1;
+        } else if (type == 'B') {
+            if (end - v < 5) return AuxFind::malformed;
+            const size_t eb = aux_elem_bytes(v[0]);
+            if (!eb || v[0] == 'A') return AuxFind::malformed;
+            uint32_t count;
+            std::memcpy(&count, v + 1, 4);
+            if ((uint64_t)count * eb > (uint64_t)(end - v - 5)) return AuxFind::malformed;
+            len = 5 + (size_t)count * eb;
+            p = v + len;
+        } else {
+            len = aux_elem_bytes(type);
+            if (!len || (size_t)(end - v) < len) return AuxFind::malformed;
+            p = v + len;
+        }
+        if (t0 == (uint8_t)tag[0] && t1 == (uint8_t)tag[1]) {
+            out->type = (char)type;
+            out->value = v;
+            out->len = len;
+            return AuxFind::found;
+        }
+    }
+    return AuxFind::absent;
+}
 
 struct File {
     umi::bgzf::Bytes data;     // whole decompressed stream

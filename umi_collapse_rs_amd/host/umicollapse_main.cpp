@@ -39,6 +39,18 @@
 // buffer in the one-pass order.  Same decompressed output and summary lines as one pass, plus
 // "two-pass: <W> windows, at most <R> reads held" (run_two_pass).  --dump-staging and
 // --passthrough keep their one-pass behaviour with it.
+// --umi-tag XX (bam/sam mode; fgbio / umi_tools / single-cell convention, not the reference's): the UMI of a
+// staged read is the value of its aux tag XX (type Z; -u N or the first staged read's length; another length
+// ends the run naming the read, a byte outside ATCGN -- a duplex "-" included -- is "Unknown character";
+// --umi_sep is ignored).  --per-cell: a position is (alignment, cell barcode) -- the value of --cell-tag
+// (default CB, type Z), compared byte for byte -- so UMIs of different cells are never compared.  A staged
+// read without its tags is dropped, not written, and counted ("Number of reads without a UMI tag / a cell
+// barcode", each tag counted by itself); "Number of unique alignment positions" still counts alignments,
+// "Number of (position, cell) groups" the buckets, which the average and maximum lines are over.  A
+// barcode's id is the rank of its first appearance (per-thread tables made global); the device staging takes
+// it as the group key of umi_stage_reads_grouped_wide.  Everything else -- merge, --paired (the first
+// mate's tags), --tag, --two-pass, --devices, --stage -- as without the flags; --dump-staging appends every
+// bucket's cell id.  A malformed aux block or a tag of another type ends the run with status 101.
 // Not implemented, as in the reference: --algo cc.
 #include <algorithm>
 #include <chrono>
@@ -50,6 +62,7 @@
 #include <future>
 #include <sys/stat.h>
 #include <string>
+#include <string_view>
 #include <unistd.h>
 #include <unordered_map>
 #include <unordered_set>
@@ -82,6 +95,9 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     std::string stage = "auto";  // --stage gpu|host|auto: where the reads are merged per (position, UMI) and
                                  // put in rank order (auto: on the GPU unless --paired or --tag need the
                                  // host's per-read bookkeeping)
+    std::string umi_tag;         // --umi-tag XX: the UMI is the value of this aux tag, not the name's suffix
+    std::string cell_tag = "CB"; // --cell-tag XX: the cell barcode's tag (--per-cell)
+    bool per_cell = false, cell_tag_given = false; // --per-cell: positions are (alignment, cell barcode)
 };
 
 [[noreturn]] void die(const std::string &msg)
@@ -103,6 +119,10 @@ struct HipLib {
     // (the forms for keys of any number of words: one word is the ordinary call behind them)
     int (*stage_reads)(umi_ctx *, const uint64_t *, int, const uint8_t *, const int32_t *, uint64_t, int, int, int,
                        uint64_t *, uint64_t *, int32_t *, uint64_t *, uint64_t *, uint64_t *, uint64_t *) = nullptr;
+    // --per-cell: positions are (alignment, cell id) pairs
+    int (*stage_reads_grouped)(umi_ctx *, const uint64_t *, int, const uint64_t *, int, const uint8_t *, const int32_t *,
+                               uint64_t, int, int, int, uint64_t *, uint64_t *, int32_t *, uint64_t *, uint64_t *, uint64_t *,
+                               uint64_t *) = nullptr;
     int (*dedup_batch)(umi_ctx *, const uint64_t *, const uint64_t *, int, const int32_t *, const uint64_t *, uint64_t,
                        int, int, float, int, int32_t, uint8_t *, uint32_t *, umi_stats *) = nullptr;
     int (*dedup_seqs)(umi_ctx *, const uint64_t *, const uint64_t *, int, const int32_t *, const uint64_t *,
@@ -144,6 +164,8 @@ struct HipLib {
         ctx_set_option = (decltype(ctx_set_option))sym("umi_ctx_set_option");
         last_error = (decltype(last_error))sym("umi_last_error");
         stage_reads = (decltype(stage_reads))sym("umi_stage_reads_wide");
+        // (looked up without a verdict: only --per-cell's GPU staging needs it, and says so if it is missing)
+        stage_reads_grouped = (decltype(stage_reads_grouped))dlsym(handle, "umi_stage_reads_grouped_wide");
         dedup_batch = (decltype(dedup_batch))sym("umi_dedup_batch_wide");
         dedup_seqs = (decltype(dedup_seqs))sym("umi_dedup_seqs");
         stage_seqs = (decltype(stage_seqs))sym("umi_stage_seqs");
@@ -226,6 +248,11 @@ void usage()
               "      --two-pass-window <N> reads per GPU call with --two-pass [default: 2097152]\n"
               "      --compress-level <N> deflate level of the output BAM, 0..9 [default: 1]\n"
               "      --stage <WHERE>      gpu, host or auto: where reads are merged per (position, UMI) [default: auto]\n"
+              "      --umi-tag <XX>       the UMI is the value of aux tag XX (type Z, e.g. RX or UB) instead of the\n"
+              "                           read name's suffix; reads without it are dropped (bam/sam mode)\n"
+              "      --per-cell           deduplicate per cell: positions are (alignment, cell barcode); reads\n"
+              "                           without a barcode are dropped (bam/sam mode)\n"
+              "      --cell-tag <XX>      aux tag of the cell barcode, type Z [default: CB]\n"
               "      --device <ID>        GPU to use [default: 0]\n"
               "      --devices <ID,..>    several GPUs of the node: alignment positions are sharded over them");
 }
@@ -275,6 +302,15 @@ Cli parse(int argc, char **argv)
         else if (a == "--dump-staging") c.dump_staging = need(i);
         else if (a == "--passthrough") c.passthrough = true;
         else if (a == "--stage") c.stage = need(i);
+        else if (a == "--umi-tag" || a == "--cell-tag") {
+            const std::string t = need(i);
+            auto alpha = [](char ch) { return (ch >= 'A' && ch <= 'Z') || (ch >= 'a' && ch <= 'z'); };
+            if (t.size() != 2 || !alpha(t[0]) || !(alpha(t[1]) || (t[1] >= '0' && t[1] <= '9'))) // SAM spec
+                die(a + " wants a tag name of two characters, [A-Za-z][A-Za-z0-9]: '" + t + "'");
+            if (a == "--umi-tag") c.umi_tag = t;
+            else { c.cell_tag = t; c.cell_tag_given = true; }
+        }
+        else if (a == "--per-cell") c.per_cell = true;
         else if (a == "--compress-level") {
             c.compress_level = std::atoi(need(i));
             if (c.compress_level < 0 || c.compress_level > 9) die("--compress-level wants 0..9");
@@ -309,13 +345,18 @@ struct Entry { // one (alignment key, UMI): ReadFreq of src/utils/read_freq.rs +
 // PairedAlignment{strand, coord, ref, tlen} (:547-553); ref as tid (equal names <=> equal tid)
 struct AlignKey {
     uint64_t coord, ref_strand, tlen;
-    bool operator==(const AlignKey &o) const { return coord == o.coord && ref_strand == o.ref_strand && tlen == o.tlen; }
+    uint64_t cell = 0; // --per-cell: the barcode's dense id (first-appearance rank); 0 otherwise
+    bool operator==(const AlignKey &o) const
+    {
+        return coord == o.coord && ref_strand == o.ref_strand && tlen == o.tlen && cell == o.cell;
+    }
 };
 
 struct KeyHash {
     size_t operator()(const AlignKey &k) const
     {
-        uint64_t x = k.coord * 0x9E3779B97F4A7C15ull ^ (k.ref_strand + 0x7F4A7C15u) ^ (k.tlen * 0xD6E8FEB86659FD93ull);
+        uint64_t x = k.coord * 0x9E3779B97F4A7C15ull ^ (k.ref_strand + 0x7F4A7C15u) ^ (k.tlen * 0xD6E8FEB86659FD93ull) ^
+                     (k.cell * 0x94D049BB133111EBull);
         x ^= x >> 29;
         x *= 0xBF58476D1CE4E5B9ull;
         return (size_t)(x ^ (x >> 32));
@@ -389,6 +430,74 @@ const char *find_umi(const umi::bam::Record &r, uint8_t sep, size_t umi_length, 
     if (umi_length > UMI_MAX_WIDE_UMI_LEN) return "UMIs of more than 85 bases are not handled";
     if (at + umi_length > qn) return "UMI runs past the end of the read name";
     return nullptr;
+}
+
+// --umi-tag / --per-cell: the aux tags a staged read is looked up by.  Returns the bits of the ones it
+// lacks (MISS_UMI, MISS_CELL: the read is dropped, not written, and counted); err: the message that ends
+// the run (a malformed aux block, a tag that is not of type Z).
+enum : uint8_t { MISS_UMI = 1, MISS_CELL = 2 };
+struct ReadTags {
+    const uint8_t *umi = nullptr; // --umi-tag: the value
+    size_t umi_len = 0;
+    std::string_view cell;        // --per-cell: the barcode, an opaque byte string
+};
+uint8_t read_tags(const Cli &args, const umi::bam::Record &r, ReadTags &t, std::string &err)
+{
+    auto look = [&](const std::string &tag, umi::bam::AuxField &f) -> bool {
+        const umi::bam::AuxFind got = umi::bam::find_aux(r, tag.c_str(), &f);
+        const std::string name((const char *)r.qname(), r.qname_len());
+        if (got == umi::bam::AuxFind::malformed) err = "malformed aux block in read " + name;
+        else if (got == umi::bam::AuxFind::found && f.type != 'Z')
+            err = "tag " + tag + " of read " + name + " is of type " + std::string(1, f.type) + ", not Z";
+        return got == umi::bam::AuxFind::found && err.empty();
+    };
+    uint8_t miss = 0;
+    umi::bam::AuxField f;
+    if (!args.umi_tag.empty()) {
+        if (look(args.umi_tag, f)) {
+            t.umi = f.value;
+            t.umi_len = f.len;
+        } else {
+            miss |= MISS_UMI;
+        }
+        if (!err.empty()) return 0;
+    }
+    if (args.per_cell) {
+        if (look(args.cell_tag, f)) t.cell = std::string_view((const char *)f.value, f.len);
+        else miss |= MISS_CELL;
+    }
+    return miss;
+}
+
+// where the UMI of a read with all its tags starts, as an offset from its name: after --umi_sep in the
+// name (find_umi), or the --umi-tag value, which must be umi_length bases; empty, or the message that
+// ends the run
+std::string umi_offset(const Cli &args, const umi::bam::Record &r, const ReadTags &t, size_t umi_length, size_t &at)
+{
+    if (args.umi_tag.empty()) {
+        const char *err = find_umi(r, args.umi_sep, umi_length, at);
+        return err ? err : "";
+    }
+    at = (size_t)(t.umi - r.qname());
+    if (umi_length == 0) return "Empty UMI sequence extracted";
+    if (umi_length > UMI_MAX_WIDE_UMI_LEN) return "UMIs of more than 85 bases are not handled";
+    if (t.umi_len != umi_length)
+        return "UMI tag " + args.umi_tag + " of read " + std::string((const char *)r.qname(), r.qname_len()) + " holds " +
+               std::to_string(t.umi_len) + " bases, not " + std::to_string(umi_length);
+    return "";
+}
+
+// the UMI length of the first staged read (src: :154-156): the name's UMI group, or the --umi-tag value's length
+size_t detect_length(const Cli &args, const umi::bam::Record &r, const ReadTags &t)
+{
+    return args.umi_tag.empty() ? detect_umi_length(r.qname(), r.qname_len(), args.umi_sep) : t.umi_len;
+}
+
+int bits_of(uint64_t v)
+{
+    int b = 1;
+    while (b < 64 && (v >> b)) b++;
+    return b;
 }
 
 // a second mate the paired writer may look for (:425-429)
@@ -553,6 +662,8 @@ int run_fastq(const Cli &args, int algo, int merge, HipLib &lib)
     const double t_start = now_s();
     if (args.paired || args.remove_unpaired || args.remove_chimeric || args.keep_unmapped || args.two_pass)
         die("--paired, --remove-unpaired, --remove-chimeric, --keep-unmapped and --two-pass do not go with fastq mode");
+    if (!args.umi_tag.empty() || args.cell_tag_given || args.per_cell)
+        die("--umi-tag, --cell-tag and --per-cell do not go with fastq mode");
     if (args.stage != "auto" && args.stage != "gpu" && args.stage != "host") die("--stage wants gpu, host or auto");
     if (args.stage == "gpu" && !args.dump_staging.empty()) die("--stage gpu does not go with --dump-staging");
     if (args.devices.size() > 1) die("fastq mode runs on one GPU: --devices takes one id here");
@@ -941,6 +1052,33 @@ void run_two_pass(const Cli &args, int algo, int merge, HipLib &lib, const std::
                                                             // first mate registers -> first mates not yet written or dropped
     bool bad_char = false;
     uint64_t n_records = 0;
+    // --umi-tag / --per-cell: reads without their tags are dropped in both passes; a barcode's id is its rank
+    // of first appearance, as in one pass, and the positions are counted apart from the (position, cell) groups
+    const bool by_tags = !args.umi_tag.empty() || args.per_cell;
+    size_t no_umi_tag = 0, no_cell = 0;
+    std::unordered_map<std::string, uint64_t> cell_ids;
+    std::unordered_set<AlignKey, KeyHash> positions;
+    // the (alignment, cell) key of a staged read, false if it lacks a tag (census: counted; err ends the run)
+    auto staged_key = [&](const umi::bam::Record &r, ReadTags &tg, AlignKey &key, bool census) -> bool {
+        key = align_key(r, args.paired);
+        if (!by_tags) return true;
+        std::string err;
+        const uint8_t miss = read_tags(args, r, tg, err);
+        if (!err.empty()) die(err);
+        if (miss) {
+            if (census) {
+                no_umi_tag += (miss & MISS_UMI) ? 1 : 0;
+                no_cell += (miss & MISS_CELL) ? 1 : 0;
+            }
+            return false;
+        }
+        if (args.per_cell) {
+            if (census) positions.insert(key);
+            key.cell = census ? cell_ids.emplace(std::string(tg.cell), cell_ids.size()).first->second
+                              : cell_ids.at(std::string(tg.cell));
+        }
+        return true;
+    };
     {
         RecordStream rs(args.input, T);
         const umi::bgzf::Bytes h = rs.header();
@@ -960,11 +1098,15 @@ void run_two_pass(const Cli &args, int algo, int merge, HipLib &lib, const std::
                 if (args.keep_unmapped) out.write(r.begin, (size_t)(r.end - r.begin)); // :104-106, ahead of every position
             }
             if (state != 0) continue;
-            if (umi_length == 0) umi_length = detect_umi_length(r.qname(), r.qname_len(), args.umi_sep); // :154-156
+            ReadTags tg;
+            AlignKey key;
+            if (!staged_key(r, tg, key, true)) continue;
+            if (umi_length == 0) umi_length = detect_length(args, r, tg); // :154-156
             size_t at;
-            if (const char *err = find_umi(r, args.umi_sep, umi_length, at)) die(err);
+            const std::string err = umi_offset(args, r, tg, umi_length, at);
+            if (!err.empty()) die(err);
             if (!bad_char && !encode_umi(r.qname() + at, umi_length, &k, &nm)) bad_char = true;
-            latest[align_key(r, args.paired)] = ri;
+            latest[key] = ri;
             if (args.paired && r.is_paired()) reg_count[reg_hash(mate_key(r.qname(), r.qname_len(), r.mtid(), r.mpos()))]++;
         }
     }
@@ -1209,8 +1351,9 @@ void run_two_pass(const Cli &args, int algo, int merge, HipLib &lib, const std::
                     note_peak();
                 }
             }
-            if (state == 0) {
-                const AlignKey key = align_key(r, args.paired);
+            ReadTags tg;
+            AlignKey key;
+            if (state == 0 && staged_key(r, tg, key, false)) {
                 auto it = open.find(key);
                 if (it == open.end()) {
                     it = open.emplace(key, Bucket()).first;
@@ -1221,7 +1364,7 @@ void run_two_pass(const Cli &args, int algo, int merge, HipLib &lib, const std::
                 }
                 Bucket &bk = it->second;
                 size_t at;
-                find_umi(r, args.umi_sep, umi_length, at);
+                (void)umi_offset(args, r, tg, umi_length, at); // (checked by the census)
                 bk.reads.push_back({bk.bytes.size(), (uint32_t)at, merge == 2 ? (int32_t)r.mapq() : r.avg_qual()});
                 bk.bytes.insert(bk.bytes.end(), r.begin, r.end);
                 held_open++;
@@ -1255,7 +1398,10 @@ void run_two_pass(const Cli &args, int algo, int merge, HipLib &lib, const std::
         std::fprintf(stderr, "Number of unpaired reads: %zu\n", unpaired);
         std::fprintf(stderr, "Number of chimeric reads: %zu\n", chimeric);
     }
-    std::fprintf(stderr, "Number of unique alignment positions: %zu\n", nb_total);
+    if (!args.umi_tag.empty()) std::fprintf(stderr, "Number of reads without a UMI tag: %zu\n", no_umi_tag);
+    if (args.per_cell) std::fprintf(stderr, "Number of reads without a cell barcode: %zu\n", no_cell);
+    std::fprintf(stderr, "Number of unique alignment positions: %zu\n", args.per_cell ? positions.size() : nb_total);
+    if (args.per_cell) std::fprintf(stderr, "Number of (position, cell) groups: %zu\n", nb_total);
     std::fprintf(stderr, "Number of UMIs: %zu\n", n_total);
     std::fprintf(stderr, "Average number of UMIs per alignment position: %g\n", nb_total ? (double)n_total / (double)nb_total : 0.0);
     std::fprintf(stderr, "Max number of UMIs over all alignment positions: %zu\n", max_umi);
@@ -1391,7 +1537,12 @@ int main(int argc, char **argv)
             for (uint32_t ri = 0; ri < n_rec; ri++) {
                 uint8_t u, c;
                 if (classify(in.records[ri], u, c) == 0) {
-                    umi_length = detect_umi_length(in.records[ri].qname(), in.records[ri].qname_len(), args.umi_sep);
+                    ReadTags tg;
+                    std::string err;
+                    const uint8_t miss = read_tags(args, in.records[ri], tg, err); // (a read without its tags is not staged)
+                    if (!err.empty()) die(err);
+                    if (miss) continue;
+                    umi_length = detect_length(args, in.records[ri], tg);
                     break;
                 }
             }
@@ -1405,9 +1556,11 @@ int main(int argc, char **argv)
             uint64_t coord, ref_strand, tlen;
             int32_t score;
             uint8_t state; // 0 staged, 1 unmapped, 2 error, 3 second mate (not counted),
-                           // 4 mate unmapped, 5 filtered (--remove-unpaired / --remove-chimeric)
-            uint8_t unpaired, chimeric;
-            uint32_t umi_at; // offset of the UMI in the read name
+                           // 4 mate unmapped, 5 filtered (--remove-unpaired / --remove-chimeric),
+                           // 6 dropped: it lacks a tag of --umi-tag / --per-cell (`missing` says which)
+            uint8_t unpaired, chimeric, missing;
+            uint32_t umi_at; // offset of the UMI from the read name (a --umi-tag value lies behind it)
+            uint32_t cell;   // --per-cell: the barcode's id, the thread's own during the per-read pass
         };
         std::vector<ReadInfo> info(n_rec);
         std::vector<UmiKey> rkey, rnm; // per read: its UMI key and N mask (host staging only: the device encodes its own)
@@ -1444,6 +1597,13 @@ int main(int argc, char **argv)
         std::vector<std::string> errors(T);
         std::vector<uint32_t> first_error(T, UINT32_MAX);
         const uint32_t chunk = (n_rec + T - 1) / T;
+        // --per-cell: every thread numbers the barcodes of its reads in order of appearance; the numbers are
+        // made global (first appearance in the file) below.  A few thousand to 10^5 barcodes: the tables stay
+        // in cache.
+        std::vector<std::unordered_map<std::string_view, uint32_t>> cell_ids(args.per_cell ? T : 0);
+        std::vector<std::vector<std::string_view>> cell_seen(args.per_cell ? T : 0);
+        U64s gkey; // GPU staging with --per-cell: every read's cell id, the group key
+        if (gpu_stage && args.per_cell) gkey.resize(n_rec);
         umi::bgzf::parallel_for(T, T, [&](size_t t) {
             const uint32_t lo = (uint32_t)t * chunk, hi = std::min(n_rec, lo + chunk);
             // (the thread's extremes in locals: sixteen threads updating neighbours of one cache line
@@ -1454,6 +1614,8 @@ int main(int argc, char **argv)
                 const umi::bam::Record &r = in.records[ri];
                 ReadInfo &ii = info[ri];
                 ii.tlen = 0;
+                ii.missing = 0;
+                ii.cell = 0;
                 ii.state = classify(r, ii.unpaired, ii.chimeric);
                 if (ii.state != 0 || args.passthrough) continue;
                 const AlignKey ak = align_key(r, args.paired);
@@ -1461,12 +1623,26 @@ int main(int argc, char **argv)
                 ii.ref_strand = ak.ref_strand;
                 ii.tlen = ak.tlen;
                 const uint8_t *q = r.qname();
-                size_t at;
-                const char *err = find_umi(r, args.umi_sep, umi_length, at);
-                if (err) {
+                size_t at = 0;
+                std::string err;
+                ReadTags tg;
+                if (!args.umi_tag.empty() || args.per_cell) {
+                    ii.missing = read_tags(args, r, tg, err);
+                    if (ii.missing && err.empty()) {
+                        ii.state = 6;
+                        continue;
+                    }
+                }
+                if (err.empty()) err = umi_offset(args, r, tg, umi_length, at);
+                if (!err.empty()) {
                     ii.state = 2;
                     if (first_error[t] == UINT32_MAX) { first_error[t] = ri; errors[t] = err; }
                     continue;
+                }
+                if (args.per_cell) {
+                    const auto id = cell_ids[t].emplace(tg.cell, (uint32_t)cell_seen[t].size());
+                    if (id.second) cell_seen[t].push_back(tg.cell);
+                    ii.cell = id.first->second;
                 }
                 ii.score = merge == 2 ? (int32_t)r.mapq() : r.avg_qual();
                 ii.umi_at = (uint32_t)at;
@@ -1488,13 +1664,34 @@ int main(int argc, char **argv)
         });
         for (unsigned t = 0; t < T; t++) // the reference panics at the first offending read
             if (first_error[t] != UINT32_MAX) die(errors[t]);
+        size_t n_cells = 0;
+        if (args.per_cell) { // the threads' barcode numbers -> ranks of first appearance in the file
+            std::unordered_map<std::string_view, uint32_t> global;
+            std::vector<std::vector<uint32_t>> to_global(T);
+            for (unsigned t = 0; t < T; t++)
+                for (const std::string_view &bc : cell_seen[t])
+                    to_global[t].push_back(global.emplace(bc, (uint32_t)global.size()).first->second);
+            n_cells = global.size();
+            umi::bgzf::parallel_for(T, T, [&](size_t t) {
+                const uint32_t lo = (uint32_t)t * chunk, hi = std::min(n_rec, lo + chunk);
+                for (uint32_t ri = lo; ri < hi; ri++)
+                    if (info[ri].state == 0) {
+                        info[ri].cell = to_global[t][info[ri].cell];
+                        if (gpu_stage) gkey[ri] = info[ri].cell;
+                    }
+            });
+        }
         lap("per-read");
         if (!gpu_stage && !args.passthrough) encode_all();
 
-        size_t total_read_count = 0, unmapped = 0, unpaired = 0, chimeric = 0;
+        size_t total_read_count = 0, unmapped = 0, unpaired = 0, chimeric = 0, no_umi_tag = 0, no_cell = 0;
         std::vector<uint32_t> out_records; // records written before dedup (--keep-unmapped, :104-106)
         for (uint32_t ri = 0; ri < n_rec; ri++) {
             if (info[ri].state != 3) total_read_count++; // :99
+            if (info[ri].state == 6) {
+                no_umi_tag += (info[ri].missing & MISS_UMI) ? 1 : 0;
+                no_cell += (info[ri].missing & MISS_CELL) ? 1 : 0;
+            }
             unpaired += info[ri].unpaired;
             chimeric += info[ri].chimeric;
             if (info[ri].state == 4) unmapped++; // :118-121
@@ -1550,6 +1747,7 @@ int main(int argc, char **argv)
                 }
                 if (moved) {
                     akey[ns] = akey[ri];
+                    if (!gkey.empty()) gkey[ns] = gkey[ri];
                     std::memmove(&umis[ns * umi_length], &umis[(size_t)ri * umi_length], umi_length);
                     sc[ns] = sc[ri];
                     staged.push_back(ri);
@@ -1585,9 +1783,16 @@ int main(int argc, char **argv)
                 lap("wait-gpu");
                 keys.resize(ns * n_words); nmask.resize(ns * n_words); freq.resize(ns); off.resize(ns + 1);
                 uint64_t ne = 0, nbk = 0;
-                if (lib.stage_reads(ctx, akey.data(), akey_bits, umis.data(), sc.data(), ns, (int)umi_length, n_words, merge != 0 ? 1 : 0,
-                                    keys.data(), nmask.data(), freq.data(), rep64.data(), off.data(), &ne, &nbk) != UMI_OK)
-                    die(lib.last_error());
+                if (args.per_cell && !lib.stage_reads_grouped) die("libumihip.so lacks umi_stage_reads_grouped_wide");
+                const int rc = args.per_cell
+                                   ? lib.stage_reads_grouped(ctx, akey.data(), akey_bits, gkey.data(), bits_of(n_cells), umis.data(),
+                                                             sc.data(), ns, (int)umi_length, n_words, merge != 0 ? 1 : 0,
+                                                             keys.data(), nmask.data(), freq.data(), rep64.data(), off.data(),
+                                                             &ne, &nbk)
+                                   : lib.stage_reads(ctx, akey.data(), akey_bits, umis.data(), sc.data(), ns, (int)umi_length,
+                                                     n_words, merge != 0 ? 1 : 0, keys.data(), nmask.data(), freq.data(),
+                                                     rep64.data(), off.data(), &ne, &nbk);
+                if (rc != UMI_OK) die(lib.last_error());
                 lap("stage-call");
                 n = (size_t)ne;
                 nb = (size_t)nbk;
@@ -1614,7 +1819,7 @@ int main(int argc, char **argv)
             for (uint32_t ri = 0; ri < n_rec; ri++) {
                 const ReadInfo &ii = info[ri];
                 if (ii.state != 0) continue;
-                const AlignKey akey{ii.coord, ii.ref_strand, ii.tlen};
+                const AlignKey akey{ii.coord, ii.ref_strand, ii.tlen, ii.cell};
                 if (hasher(akey) % T != t) continue;
                 auto it = sh.bucket_of.find(akey);
                 uint32_t b;
@@ -1679,6 +1884,20 @@ int main(int argc, char **argv)
             max_umi = std::max(max_umi, v.size());
         }
         }
+        // --per-cell: a bucket is a (position, cell) group; the positions are counted as ever, and every
+        // group's cell id (the rank of the barcode's first appearance) is what --dump-staging adds
+        size_t n_positions = nb;
+        std::vector<uint32_t> bucket_cell;
+        if (args.per_cell && !args.passthrough) {
+            std::unordered_set<AlignKey, KeyHash> positions;
+            bucket_cell.resize(nb);
+            for (size_t b = 0; b < nb; b++) {
+                const ReadInfo &ii = info[rep[off[b]]];
+                positions.insert(AlignKey{ii.coord, ii.ref_strand, ii.tlen});
+                bucket_cell[b] = ii.cell;
+            }
+            n_positions = positions.size();
+        }
         const double t_stage0 = now_s();
         std::fprintf(stderr, "UMI collapsing reading finished in %.3f seconds\n", t_stage0 - t_start); // :178-183
         if (!args.dump_staging.empty()) { // test hook: staged hot-path input, no GPU touched
@@ -1689,7 +1908,14 @@ int main(int argc, char **argv)
             std::fwrite(keys.data(), 8, n * n_words, f); std::fwrite(nmask.data(), 8, n * n_words, f);
             std::fwrite(freq.data(), 4, n, f); std::fwrite(rep.data(), 4, n, f);
             std::fwrite(off.data(), 8, nb + 1, f);
+            if (args.per_cell) std::fwrite(bucket_cell.data(), 4, nb, f); // (--per-cell: every bucket's cell id)
             std::fclose(f);
+            if (!args.umi_tag.empty()) std::fprintf(stderr, "Number of reads without a UMI tag: %zu\n", no_umi_tag);
+            if (args.per_cell) {
+                std::fprintf(stderr, "Number of reads without a cell barcode: %zu\n", no_cell);
+                std::fprintf(stderr, "Number of unique alignment positions: %zu\n", n_positions);
+                std::fprintf(stderr, "Number of (position, cell) groups: %zu\n", nb);
+            }
             return 0;
         }
 
@@ -1811,7 +2037,7 @@ int main(int argc, char **argv)
             const int32_t block_size = (int32_t)(len - 4 + TAG_BYTES);
             std::memcpy(out.data() + o, &block_size, 4);
             o += len;
-            const AlignKey akey{info[ri].coord, info[ri].ref_strand, info[ri].tlen};
+            const AlignKey akey{info[ri].coord, info[ri].ref_strand, info[ri].tlen, info[ri].cell};
             const uint32_t e = global_of[hasher(akey) % T][entry_of[ri]];
             const uint32_t r = root[e];
             const struct { const char *tag; int32_t v; } aux[3] = {
@@ -1836,7 +2062,10 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "Number of unpaired reads: %zu\n", unpaired);
             std::fprintf(stderr, "Number of chimeric reads: %zu\n", chimeric);
         }
-        std::fprintf(stderr, "Number of unique alignment positions: %zu\n", nb);
+        if (!args.umi_tag.empty()) std::fprintf(stderr, "Number of reads without a UMI tag: %zu\n", no_umi_tag);
+        if (args.per_cell) std::fprintf(stderr, "Number of reads without a cell barcode: %zu\n", no_cell);
+        std::fprintf(stderr, "Number of unique alignment positions: %zu\n", n_positions);
+        if (args.per_cell) std::fprintf(stderr, "Number of (position, cell) groups: %zu\n", nb);
         std::fprintf(stderr, "Number of UMIs: %zu\n", n);
         std::fprintf(stderr, "Average number of UMIs per alignment position: %g\n", nb ? (double)n / (double)nb : 0.0);
         std::fprintf(stderr, "Max number of UMIs over all alignment positions: %zu\n", max_umi);
