@@ -7,16 +7,22 @@ batch of synthetic input resident in HBM.
 
 N = 1 (the judged line): BASELINE config 2 -- 1,000,000 reads, 12-bp UMIs, ONE alignment position
 (uniform UMIs, ~9.7e5 unique -> W ~ 4.7e11 unordered pairs), --data naive --algo dir -k 1 -p 0.5.
-The other single-GPU shapes ride along under "configs": config 3 (10 M reads in 100,000 positions),
-one GPU's share of config 5 (6.25 M reads, 20-bp, k = 2) and 2m (one deep position from the
-molecule model), each with its own roofline and CPU baseline.
+With --full the other single-GPU shapes ride along under "configs": config 3 (10 M reads in 100,000
+positions), one GPU's share of config 5 (6.25 M reads, 20-bp, k = 2), 2m (one deep position from the
+molecule model) and wide24, each with its own roofline and CPU baseline.
 
 N > 1: BASELINE config 4 -- 100 M reads in 10^6 positions over 8 GPUs, i.e. 12.5 M reads in 125,000
 positions per rank (weak scaling in N), buckets sharded by rank with no data-path collective, the
-kept mask packed to bits and all-gathered over RCCL/xGMI every step.  Config 5's per-rank share and
-config 2 (one deep position per rank) follow in the same run under "configs".  `--config 2` makes
-config 2 the top-level workload again; `--split` is strong scaling of ONE deep position (pair work
-split over the ranks, edge lists all-gathered, collapse replicated).
+kept mask packed to bits and all-gathered over RCCL/xGMI every step.  With --full, config 5's
+per-rank share and config 2 (one deep position per rank) follow in the same run under "configs".
+`--config 2` makes config 2 the top-level workload again; `--split` is strong scaling of ONE deep
+position (pair work split over the ranks, edge lists all-gathered, collapse replicated).
+
+A plain run sets up the top-level workload, warms up, times --steps steps, writes --dump-outputs and
+prints the line; the fields it does not measure are null.  --full adds everything else: the phase
+split and the roofline (a second block of steps with event records), a sustained block, the
+brute-force step, device staging, the host-buffer call, CPU baselines, the other configs and the
+end-to-end CLI run.
 
 `value` is an EFFECTIVE rate: W / t, the unordered pairs of the positions per second of hot-path
 time.  A deep position is not walked pair by pair: it is cut into n-gram sub-buckets (two UMIs
@@ -397,7 +403,8 @@ def measure(res, steps, warmup, profile=True):
     The timed steps run with the library's event records off: a hipEventRecord between two kernels
     costs the stream ~5 us, and a call records up to nine -- 0.04 ms of a 0.14 ms step.  The phase
     times and the duration of the kernel the roofline is quoted on come from a second block of the
-    same `steps` steps, on the same stream, with the records on (`ms_per_step_with_events`)."""
+    same `steps` steps, on the same stream, with the records on (`ms_per_step_with_events`); without that
+    block (profile=False) they are null."""
     import torch
     res.ctx.set_option("profile", 0)
     for _ in range(warmup):
@@ -429,11 +436,12 @@ def measure(res, steps, warmup, profile=True):
         "reads_per_s": res.reads_total * steps / dt,
         "unique_umis_rank0": res.n, "positions_rank0": len(res.boff) - 1, "pairs_W_total": res.w_total,
         "kept_rank0": kept_n,
-        "phases_ms": {"prep": mean("ms_prep"), "pairs": mean("ms_pairs"), "collapse": mean("ms_collapse"),
-                      "finalize": mean("ms_finalize")},
+        "phases_ms": None if not profile else {
+            "prep": mean("ms_prep"), "pairs": mean("ms_pairs"), "collapse": mean("ms_collapse"),
+            "finalize": mean("ms_finalize")},
         "counters": {"n_edges": s0["n_edges"], "n_candidates": s0["n_candidates"], "n_rounds": s0["n_rounds"],
                      "pairs_evaluated": s0["n_pairs_evaluated"]},
-        "roofline": roofline_of(wl, res.n, stats, ms_step),
+        "roofline": roofline_of(wl, res.n, stats, ms_step) if profile else None,
     }
     return out, dt, stats, kept_n, kept_last
 
@@ -460,11 +468,16 @@ def main():
     ap.add_argument("--reads", type=int, default=0, help="reads per rank of the top-level workload (0: the config's)")
     ap.add_argument("-p", type=float, default=0.5)
     ap.add_argument("--cpu-sample", type=int, default=80_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline: the phase split and the roofline (a second block "
+                         "of steps with event records), a sustained block, the brute-force step, device staging, "
+                         "the host-buffer call, CPU baselines, the other configs and the end-to-end CLI run; "
+                         "without it only the top-level workload's timed steps run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the timed block of the top-level workload (profiling runs): no sustained block, "
-                         "no brute-force step, no host-buffer call, no CPU baseline, no end-to-end run, no "
-                         "other configs")
+                    help="with --full: only the timed block and the event-record block of the top-level workload "
+                         "(profiling runs): no sustained block, no brute-force step, no host-buffer call, no CPU "
+                         "baseline, no end-to-end run, no other configs")
     ap.add_argument("--opt", action="append", default=[], help="ctx option name=value (tuning)")
     ap.add_argument("--split", action="store_true",
                     help="N>1 only: strong scaling -- ONE giant position (config 2), its pair work split over "
@@ -476,14 +489,14 @@ def main():
                          "one GPU's share of 50M reads with 20-bp UMIs, k=2, wide24 = one deep position of 24-base "
                          "(dual 12 + 12) UMIs")
     ap.add_argument("--no-profile", action="store_true",
-                    help="no HIP events inside the library's calls (phases_ms and the roofline's kernel time are then "
+                    help="with --full: no HIP events inside the library's calls (phases_ms and the roofline are then "
                          "missing): what the event records cost the step")
     ap.add_argument("--force-collective", action="store_true",
                     help="N=1 rehearsal of the N>1 step: a process group of one rank is formed (RCCL unless "
                          "BENCH_BACKEND says otherwise) and every step packs and all-gathers its mask")
     ap.add_argument("--also", default=None,
                     help="comma list of the configs measured after the top-level one, under \"configs\" "
-                         "(default: 3,5,2m at N=1; 5,2 at N>1; 'none')")
+                         "(default: 3,5,2m,wide24 at N=1 and 5,2 at N>1 with --full, none without; 'none')")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the top-level workload's kept mask of the last timed step "
                          "(rank 0's) as DIR/kept.npy (float32); the inputs are seeded, so two builds run with the "
@@ -522,7 +535,8 @@ def main():
 
     split = args.split and world > 1
     cfg = args.config or ("2" if (world == 1 or split) else "4")
-    extras = not args.no_extras
+    extras = args.full and not args.no_extras
+    profile = args.full and not args.no_profile
     if args.also is None:
         also = [] if (not extras or split) else ([c for c in ("3", "5", "2m", "wide24") if c != cfg] if world == 1
                                                  else [c for c in ("5", "2") if c != cfg])
@@ -539,7 +553,7 @@ def main():
     # ---- the top-level workload
     wl = make_workload(cfg, 0 if split else rank, args.reads or None)
     res = Resident(wl, ctx, dev, world, rank, dist, args.p, split, coll)
-    block, dt, stats, kept_n, kept_last = measure(res, args.steps, args.warmup, not args.no_profile)
+    block, dt, stats, kept_n, kept_last = measure(res, args.steps, args.warmup, profile)
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, kept_last)
     del kept_last
@@ -627,8 +641,8 @@ def main():
     for c in also:
         w2 = make_workload(c, rank)
         r2 = Resident(w2, ctx, dev, world, rank, dist, args.p, False, coll)
-        b2, _, _, _, _ = measure(r2, args.steps, args.warmup, not args.no_profile)
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        b2, _, _, _, _ = measure(r2, args.steps, args.warmup, profile)
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
             # (a prefix of buckets / a 40,000-UMI cut that the oracle finishes in about a second)
             b2["cpu_baseline"] = cpu_baseline(w2, 40_000 if w2["one_position"] else 5_000, args.p, all_cores=False)
         others[c] = b2
@@ -644,7 +658,7 @@ def main():
             "metric": metric,
             "value": block["value"],
             "unit": "UMI-pair comparisons/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": ms_step, "ms_per_step_with_events": block["ms_per_step_with_events"], "higher_is_better": True,
             "scaling": "strong" if split else "weak",
             "vs_baseline": None, "dtype": "u32" if wl["umi_len"] <= 16 else "u64", "data": "synthetic",

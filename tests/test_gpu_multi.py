@@ -249,7 +249,7 @@ def test_bench_rehearsal_two_ranks_over_gloo_and_one_rank_over_rccl(tmp_path):
     env = dict(os.environ, BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--steps", "3", "--warmup", "1", "--reads", "500000", "--also", "2"]
+           "--steps", "3", "--warmup", "1", "--reads", "500000", "--also", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -87,7 +87,7 @@ for P in sorted(glob.glob(os.path.join(BASE, "c*"))):
     doc["configs"][cfg] = {
         "tag": tag, "workload": lines["bench_line"]["config"]["workload"],
         "command": "bash tools/profile_r03.sh %s  (rocprofv3 --kernel-trace --stats, then one --pmc pass per counter "
-                   "set, each over `python3 bench.py --config %s --steps 5 --warmup 2 --no-extras`)" % (cfg, cfg),
+                   "set, each over `python3 bench.py --full --config %s --steps 5 --warmup 2 --no-extras`)" % (cfg, cfg),
         "source_sha256": bench.source_sha256() if mine == sha_file else "sources differ from the box's",
         "ms_per_step_plain": lines["bench_line"]["ms_per_step"],
         "ms_per_step_under_rocprof": lines["bench_under_rocprof"]["ms_per_step"],

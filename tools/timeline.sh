@@ -3,7 +3,7 @@
 # with its start offset, duration and the idle gap before it (run on the GPU box)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/timeline; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/trace -o t -- python3 $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-extras "$@" > $O/bench.log 2>&1 || { tail -5 $O/bench.log; exit 1; }
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/trace -o t -- python3 $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-extras "$@" > $O/bench.log 2>&1 || { tail -5 $O/bench.log; exit 1; }
 python3 - <<PY
 import csv,glob
 rows=[]
