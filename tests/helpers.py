@@ -149,3 +149,21 @@ def stage_model(pos, umis, score, merge):
         rep += [e[1] for _, e in items]
         off.append(len(out_umis))
     return out_umis, np.array(freq, np.int32), np.array(rep, np.uint64), np.array(off, np.uint64)
+
+
+def grouped_stage_model(align, group, umis, score, umi_len, merge, gbits):
+    """umi_stage_reads_grouped[_wide]: buckets = (align, group & mask) by first appearance, then the
+    oracle's staging (stage_model above for UMIs of more than one key word)"""
+    import oracle as orc
+    gm = np.uint64((1 << gbits) - 1) if gbits < 64 else np.uint64(0xFFFFFFFFFFFFFFFF)
+    pairs = np.stack([align, group & gm if gbits else np.zeros_like(group)], axis=1)
+    _, first, inv = np.unique(pairs, axis=0, return_index=True, return_inverse=True)
+    rank = np.empty(len(first), np.int64)
+    rank[np.argsort(first, kind="stable")] = np.arange(len(first))
+    bucket = rank[inv.reshape(-1)]
+    if umi_len <= 21:
+        return orc.stage_reads(bucket, umis, score, umi_len, merge=merge)
+    u = [bytes(umis[i * umi_len:(i + 1) * umi_len]).decode() for i in range(len(align))]
+    w_umis, freq, rep, off = stage_model(bucket, u, score, merge)
+    keys, nmask = orc.encode_keys_wide(w_umis)
+    return dict(keys=keys, nmask=nmask, freq=freq, rep=rep, bucket_off=off)

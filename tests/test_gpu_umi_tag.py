@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 import bamio
-import oracle as orc
 import tag_model
+from helpers import grouped_stage_model as model
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -143,23 +143,6 @@ def reads(seed, n, n_align, n_groups, umi_len, abits, gbits):
     umis = np.frombuffer(b"ACGTN", np.uint8)[bases].reshape(-1)
     score = rng.integers(0, 60, n).astype(np.int32)
     return align, group, umis, score
-
-
-def model(align, group, umis, score, umi_len, merge, gbits):
-    """buckets = (align, group & mask) by first appearance, then the oracle's staging"""
-    gm = np.uint64((1 << gbits) - 1) if gbits < 64 else np.uint64(0xFFFFFFFFFFFFFFFF)
-    pairs = np.stack([align, group & gm if gbits else np.zeros_like(group)], axis=1)
-    _, first, inv = np.unique(pairs, axis=0, return_index=True, return_inverse=True)
-    rank = np.empty(len(first), np.int64)
-    rank[np.argsort(first, kind="stable")] = np.arange(len(first))
-    bucket = rank[inv.reshape(-1)]
-    if umi_len <= 21:
-        return orc.stage_reads(bucket, umis, score, umi_len, merge=merge)
-    from helpers import stage_model
-    u = [bytes(umis[i * umi_len:(i + 1) * umi_len]).decode() for i in range(len(align))]
-    w_umis, freq, rep, off = stage_model(bucket, u, score, merge)
-    keys, nmask = orc.encode_keys_wide(w_umis)
-    return dict(keys=keys, nmask=nmask, freq=freq, rep=rep, bucket_off=off)
 
 
 def same(got, exp):

@@ -250,6 +250,7 @@ struct umi_ctx {
         unsigned long long seq = 0;
         hipStream_t stream = nullptr;
         int rc = UMI_OK;
+        std::string err; // the text of a non-OK rc, told again when the result is handed out
         umi_stats st;
     } pending;
     bool spin_wait = true;                    // watch that number instead of hipStreamSynchronize (option "spin_wait")
@@ -543,7 +544,7 @@ class Pipeline {
             const auto t0 = std::chrono::steady_clock::now();
             bool there = false;
             for (unsigned spins = 0; !there; spins++) {
-                there = __atomic_load_n(ctx->h_seq(), __ATOMIC_ACQUIRE) == seq;
+                there = __atomic_load_n(ctx->h_seq(), __ATOMIC_ACQUIRE) >= seq; // (numbers only grow)
                 if (!there && (spins & 1023u) == 1023u &&
                     std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2))
                     break;
@@ -1462,30 +1463,34 @@ int finish_pending(umi_ctx *ctx, umi_stats *stats)
     umi_ctx::PendingCall &pc = ctx->pending;
     if (pc.deferred) {
         pc.deferred = false;
-        HIP_TRY(hipSetDevice(ctx->device));
+        pc.have_result = true; // (a failure to see the end is the call's result as well)
+        hipError_t e = hipSetDevice(ctx->device);
         const auto t0 = std::chrono::steady_clock::now();
         bool there = false;
-        for (unsigned spins = 0; !there; spins++) {
-            there = __atomic_load_n(ctx->h_seq(), __ATOMIC_ACQUIRE) == pc.seq;
+        for (unsigned spins = 0; !there && e == hipSuccess; spins++) {
+            there = __atomic_load_n(ctx->h_seq(), __ATOMIC_ACQUIRE) >= pc.seq; // (numbers only grow)
             if (!there && (spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
         }
-        if (!there) HIP_TRY(hipStreamSynchronize(pc.stream));
+        if (!there && e == hipSuccess) e = hipStreamSynchronize(pc.stream);
         const unsigned long long bad =
             ctx->h_counters[CNT_ERROR] + (ctx->h_counters[CNT_RISES] - ctx->h_counters[CNT_START_RISES]);
         pc.rc = UMI_OK;
-        if (bad)
+        if (e != hipSuccess)
+            pc.rc = fail(UMI_ERR_HIP, "the end of the pending call: %s", hipGetErrorString(e));
+        else if (bad)
             pc.rc = fail(UMI_ERR_ORDER,
                          "%llu entries break the input contract (freq < 1, not in freq-descending rank "
                          "order inside a bucket, or an N base without nmask)",
                          bad);
+        pc.err = pc.rc ? g_err : std::string(); // (told again at the hand-out: calls in between set texts of their own)
         pc.st.n_candidates = ctx->h_counters[CNT_CANDIDATES];
         pc.st.n_kept = ctx->h_counters[CNT_KEPT] + ctx->h_counters[CNT_KEPT_FUSED];
-        pc.have_result = true;
     }
     if (!pc.have_result) return fail(UMI_ERR_ARG, "umi_dedup_batch_end without umi_dedup_batch_device_begin");
     pc.have_result = false;
-    if (pc.rc == UMI_OK && stats) *stats = pc.st;
-    return pc.rc;
+    if (pc.rc != UMI_OK) return fail(pc.rc, "%s", pc.err.c_str());
+    if (stats) *stats = pc.st;
+    return UMI_OK;
 }
 // every other entry point that touches the context's workspace first lets a deferred call end (its
 // result keeps waiting for umi_dedup_batch_end)
@@ -1628,6 +1633,7 @@ int dedup_batch_split(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask,
                 out.err = "hipSetDevice failed on a worker thread";
                 return;
             }
+            settle(sub); // (a deferred call owns the workspace until its end has been seen)
             int rc;
             if ((rc = sub->in_keys.reserve(n * 8)) || (rc = sub->in_freq.reserve(n * 4)) ||
                 (nmask && (rc = sub->in_nmask.reserve(n * 8))))
@@ -2544,8 +2550,17 @@ int umi_dedup_batch_device_multi(umi_ctx *ctx, const uint64_t *const *d_keys, co
             }
         });
     for (auto &t : pool) t.join();
+    // an error return lets every device's stream run dry first: the healthy shards' packing may still be
+    // writing the caller's buffers
+    auto drain = [&] {
+        for (umi_ctx *sub : ctx->subs)
+            if (hipSetDevice(sub->device) == hipSuccess) (void)hipStreamSynchronize(sub->own_stream);
+    };
     for (uint32_t r = 0; r < n_dev; r++)
-        if (res[r].rc) return fail(res[r].rc, "device %d: %s", ctx->subs[r]->device, res[r].err.c_str());
+        if (res[r].rc) {
+            drain();
+            return fail(res[r].rc, "device %d: %s", ctx->subs[r]->device, res[r].err.c_str());
+        }
     // the all-gatherv of the kept mask: every device's slice to every device over RCCL / xGMI, as
     // padded slices in place (a device's send buffer is its own slot of its receive buffer) --
     // <= 1 bit per unique UMI, latency-bound; one group, so the ranks of this one process progress together
@@ -2555,12 +2570,17 @@ int umi_dedup_batch_device_multi(umi_ctx *ctx, const uint64_t *const *d_keys, co
             e = ctx->rccl.AllGather(d_mask_bits_all[r] + (size_t)r * slice_bytes, d_mask_bits_all[r], slice_bytes, ncclUint8,
                                     ctx->comms[r], ctx->subs[r]->own_stream);
         const ncclResult_t e2 = ctx->rccl.GroupEnd();
-        if (e != ncclSuccess || e2 != ncclSuccess)
+        if (e != ncclSuccess || e2 != ncclSuccess) {
+            drain();
             return fail(UMI_ERR_HIP, "ncclAllGather: %s", ctx->rccl.GetErrorString(e != ncclSuccess ? e : e2));
-        for (uint32_t r = 0; r < n_dev; r++) {
-            HIP_TRY(hipSetDevice(ctx->subs[r]->device));
-            HIP_TRY(hipStreamSynchronize(ctx->subs[r]->own_stream));
         }
+        hipError_t he = hipSuccess;
+        for (uint32_t r = 0; r < n_dev; r++) { // (every device's, whatever one of them reports)
+            hipError_t hr = hipSetDevice(ctx->subs[r]->device);
+            if (hr == hipSuccess) hr = hipStreamSynchronize(ctx->subs[r]->own_stream);
+            if (he == hipSuccess) he = hr;
+        }
+        if (he != hipSuccess) return fail(UMI_ERR_HIP, "the gather's end: %s", hipGetErrorString(he));
     }
     if (stats) {
         umi_stats total = res[0].st;
@@ -2600,6 +2620,7 @@ int umi_pairs_partial_device(umi_ctx *ctx, const uint64_t *d_keys, const uint64_
     if (!d_keys || !d_freq) return fail(UMI_ERR_ARG, "keys/freq is NULL");
     const int mode = algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY;
     hipStream_t s = (hipStream_t)hip_stream;
+    settle(ctx); // (a deferred call owns the workspace until its end has been seen)
     Pipeline p(ctx, d_keys, d_nmask, d_freq, bucket_off, n_buckets, (uint32_t)n, umi_len, k,
                percentage, mode, adj_max_freq, nullptr, nullptr, s, part, n_parts);
     if ((rc = p.run(stats))) return rc;
