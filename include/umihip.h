@@ -130,6 +130,9 @@ const char *umi_last_error(void);
  *   "table_pieces"   1..64 (default 1): a bucket table of more than 4096 positions is walked, uploaded
  *                    and handed to the fused kernel in this many pieces
  *   "split_min"      multi-device contexts, see umi_ctx_create_multi
+ *   "cons_split"     2..2^30 (default 512): umi_consensus_seqs sums a cluster of at least this many reads in
+ *                    pieces over the whole grid instead of by one wave (raised by itself where the deep
+ *                    clusters' accumulators, 12 KB each, would pass 512 MB)
  * The round-1 tile kernels (bit-sliced masks, key-sorted scan + item walk, range pruning, hook/jump
  * collapse) and their options ("bitslice", "bs_*", "prune", "two_phase", "ovf_capacity") exist in the
  * development build only (make dev: libumihip_dev.so, -DUMIHIP_DEV), as cross-checks. */
@@ -287,6 +290,44 @@ int umi_stage_seqs(umi_ctx *ctx, const uint8_t *text, const uint64_t *seq_pos, c
                    uint64_t *nmask, int32_t *freq, uint64_t *rep, uint32_t *entry_of_read,
                    uint64_t *bucket_off, int32_t *bucket_len, uint64_t *n_entries, uint64_t *n_buckets,
                    int *any_n);
+
+/* ---- consensus of the clusters of whole reads (FASTQ mode's --consensus): one read per cluster, voted
+ *      column by column from all its members.  No counterpart in the reference (its fastq mode is a TODO,
+ *      src/main.rs:49-50); the vote is the quality-weighted majority that consensus callers of UMI families
+ *      start from, in integers.
+ * in : what umi_stage_seqs[_device] and umi_dedup_seqs[_device] leave behind -- the text with every read's
+ *      seq_pos / qual_pos / len, entry_of_read, freq, kept, root, the bucket table (HOST arrays in both
+ *      forms, bucket_off[n_buckets] = n_entries).
+ *      A cluster is a kept entry r (kept[r] != 0) with every entry e whose root[e] == r; its members are
+ *      the reads i with root[entry_of_read[i]] == r, all of the bucket's length L.
+ *      Column c, base b of A, C, G, T: S_b = sum of max(0, quality byte - 33) over the members with b at c,
+ *      n_b = their number (an N votes for nothing).  Called: the b with the greatest (S_b, n_b), S first;
+ *      the first of A, C, G, T on a tie.  n_b == 0 (every member has N): 'N' with quality '!'.  Else the
+ *      quality byte is 33 + min(93, max(0, S_win - (sum of the other three S))).  The sums are 64-bit.
+ * out: cons_seq / cons_qual (capacity: the sum of len over all reads): the consensus of the kept entries
+ *      back to back in ascending entry order, *cons_bytes of them; cons_off[r] (defined where kept): where
+ *      entry r's begins, its length being its bucket's; cluster_reads[r] (defined where kept; may be
+ *      NULL): its members.
+ * UMI_ERR_ARG: a multi-device context, n_reads >= 2^30, a NULL among the required pointers, no qual_pos,
+ * a bucket table that does not end at n_entries.  UMI_ERR_ORDER, found on the device before anything is
+ * written (nothing is read out of bounds): an entry_of_read or a root outside [0, n_entries), a root that
+ * is not kept, a read that is not as long as its entry's bucket, a kept entry without a member, freq not
+ * summing to n_reads.  A deferred call (umi_dedup_batch_device_begin) that is out on the context ends
+ * first; its result keeps waiting for umi_dedup_batch_end.
+ * The _device form takes and leaves the per-read and per-entry arrays in device memory and synchronises
+ * the stream (twice: after the checks, at the end); the plain form copies host arrays in and out around it. */
+int umi_consensus_seqs_device(umi_ctx *ctx, const uint8_t *d_text, const uint64_t *d_seq_pos,
+                              const uint64_t *d_qual_pos, const uint32_t *d_len, uint64_t n_reads,
+                              const uint32_t *d_entry_of_read, const int32_t *d_freq, const uint8_t *d_kept,
+                              const uint32_t *d_root, uint64_t n_entries, const uint64_t *bucket_off,
+                              const int32_t *bucket_len, uint64_t n_buckets, uint8_t *d_cons_seq,
+                              uint8_t *d_cons_qual, uint64_t *d_cons_off, uint32_t *d_cluster_reads,
+                              uint64_t *cons_bytes, void *hip_stream);
+int umi_consensus_seqs(umi_ctx *ctx, const uint8_t *text, const uint64_t *seq_pos, const uint64_t *qual_pos,
+                       const uint32_t *len, uint64_t n_reads, const uint32_t *entry_of_read, const int32_t *freq,
+                       const uint8_t *kept, const uint32_t *root, uint64_t n_entries, const uint64_t *bucket_off,
+                       const int32_t *bucket_len, uint64_t n_buckets, uint8_t *cons_seq, uint8_t *cons_qual,
+                       uint64_t *cons_off, uint32_t *cluster_reads, uint64_t *cons_bytes);
 
 /* ---- batched path: replaces the whole bucket loop
  *      src/deduplicate_sam.rs:207-233 (apply::<UcSAMRead,Naive> per bucket,

@@ -7,7 +7,11 @@ alternating.  One JSON line per shape and measurement on stdout.
   F2: F1 with the last 75 bases constant (one heavy bin: part 1 is shared by most of the bucket)
   F3: 1 M reads, lengths 18-150, 1 % N
 
-usage: python tools/fastq_bench.py [--shapes F1,F2,F3] [--reps 5] [--out DIR]"""
+--consensus: instead, per shape, umi_consensus_seqs_device on resident data (staged and collapsed on the
+device just before), timed with device events, next to the stage and collapse calls of the same data, with
+the bytes the call must move at the least and that traffic over the time as a share of the HBM rate.
+
+usage: python tools/fastq_bench.py [--shapes F1,F2,F3] [--reps 5] [--out DIR] [--consensus]"""
 import argparse
 import json
 import os
@@ -77,11 +81,72 @@ def stage_leg(ctx, name, seqs, quals, reps):
             "buckets": len(blen), "any_n": any_n, "ms_median": float(np.median(ms)), "ms_min": float(np.min(ms))}
 
 
+HBM_MEASURED = 6.29e12  # bytes per second, a float4 copy on the MI355X
+
+
+def consensus_leg(ctx, name, seqs, quals, reps):
+    """stage -> collapse -> consensus, all on device pointers; device events around each call (each
+    synchronises inside)"""
+    import ctypes as C
+    import torch
+    from umi_collapse_rs_amd._lib import Stats, check, load, ptr
+    n = len(seqs)
+    lens = np.array([len(s) for s in seqs], np.uint32)
+    total = int(lens.sum())
+    pos = np.zeros(n, np.uint64)
+    pos[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    pos = np.concatenate([pos, pos + np.uint64(total)])
+    w = max(1, (3 * int(lens.max()) + 63) // 64)
+    dev = torch.device("cuda", 0)
+    d_text = torch.from_numpy(np.frombuffer(b"".join(seqs) + b"".join(quals), np.uint8).copy()).to(dev)
+    d_pos = torch.from_numpy(pos.view(np.int64)).to(dev)
+    d_len = torch.from_numpy(lens.view(np.int32)).to(dev)
+    d_keys, d_nm = (torch.empty(n * w, dtype=torch.int64, device=dev) for _ in range(2))
+    d_freq, d_eor, d_root, d_cr = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4))
+    d_rep, d_coff = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(2))
+    d_kept = torch.empty(n, dtype=torch.uint8, device=dev)
+    d_cs, d_cq = (torch.empty(total + 8, dtype=torch.uint8, device=dev) for _ in range(2))
+    torch.cuda.synchronize()
+    ms = {"stage": [], "dedup": [], "consensus": []}
+    for r in range(reps + 1):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        ev[0].record()
+        boff, blen, ne, any_n = ctx.stage_seqs_device(d_text.data_ptr(), d_pos.data_ptr(), d_pos.data_ptr() + 8 * n,
+                                                      d_len.data_ptr(), n, w, d_keys.data_ptr(), d_nm.data_ptr(),
+                                                      d_freq.data_ptr(), d_rep.data_ptr(), d_eor.data_ptr(), merge=1)
+        ev[1].record()
+        st = Stats()
+        check(load().umi_dedup_seqs_device(ctx._h, d_keys.data_ptr(), d_nm.data_ptr() if any_n else None, w,
+                                           d_freq.data_ptr(), ptr(boff, C.c_uint64), ptr(blen, C.c_int32), len(blen), 1,
+                                           0.5, 0, 0, d_kept.data_ptr(), d_root.data_ptr(), None, C.byref(st)))
+        ev[2].record()
+        cons_bytes = ctx.consensus_seqs_device(d_text.data_ptr(), d_pos.data_ptr(), d_pos.data_ptr() + 8 * n,
+                                               d_len.data_ptr(), n, d_eor.data_ptr(), d_freq.data_ptr(), d_kept.data_ptr(),
+                                               d_root.data_ptr(), ne, boff, blen, d_cs.data_ptr(), d_cq.data_ptr(),
+                                               d_coff.data_ptr(), d_cr.data_ptr())
+        ev[3].record()
+        torch.cuda.synchronize()
+        if r:  # (the first round grows the workspaces)
+            for j, k in enumerate(("stage", "dedup", "consensus")):
+                ms[k].append(ev[j].elapsed_time(ev[j + 1]))
+    kept = int(st.n_kept)
+    # the least the call moves: base and quality of every read once, the consensus written, per read its two
+    # offsets, length and entry, per entry freq, kept, root, per kept entry its offset and count
+    min_bytes = 2 * total + 2 * cons_bytes + n * (8 + 8 + 4 + 4) + ne * (4 + 1 + 4) + kept * (8 + 4)
+    med = float(np.median(ms["consensus"]))
+    return {"shape": name, "what": "umi_consensus_seqs_device", "reads": n, "entries": ne, "clusters": kept,
+            "largest_cluster": int(d_cr[:ne][d_kept[:ne].bool()].max()), "bases": total, "cons_bytes": cons_bytes,
+            "ms_median": med, "ms_min": float(np.min(ms["consensus"])), "min_bytes": int(min_bytes),
+            "gb_per_s": round(min_bytes / med / 1e6, 1), "share_of_hbm_measured": round(min_bytes / (med * 1e-3) / HBM_MEASURED, 4),
+            "ms_stage_median": float(np.median(ms["stage"])), "ms_dedup_median": float(np.median(ms["dedup"]))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="F1,F2,F3")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None, help="also keep the FASTQ files here (default: a temp dir)")
+    ap.add_argument("--consensus", action="store_true", help="time umi_consensus_seqs_device on the shapes instead")
     a = ap.parse_args()
     out = a.out or os.path.join(ROOT, "build", "fastq_bench")
     os.makedirs(out, exist_ok=True)
@@ -89,6 +154,9 @@ def main():
     for name in a.shapes.split(","):
         t0 = time.time()
         seqs, quals = synth.fastq_reads(hash(name) & 0xFFFF, **SHAPES[name])
+        if a.consensus:
+            print(json.dumps(consensus_leg(ctx, name, seqs, quals, a.reps)), flush=True)
+            continue
         ent, off, blen = stage(seqs)
         w = max(1, max((3 * L + 63) // 64 for L in blen))
         keys, nm = to_bitset_seq([e[0] for e in ent], w)

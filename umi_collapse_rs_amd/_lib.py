@@ -86,6 +86,12 @@ SIGNATURES = {
     "umi_dedup_seqs_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _u64p, _i32p,
                                         C.c_uint64, C.c_int, C.c_float, C.c_int, C.c_int32, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.POINTER(Stats)]),
+    "umi_consensus_seqs_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u64p, _i32p,
+                                            C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p,
+                                            C.c_void_p]),
+    "umi_consensus_seqs": (C.c_int, [C.c_void_p, _u8p, _u64p, _u64p, _u32p, C.c_uint64, _u32p, _i32p, _u8p, _u32p,
+                                     C.c_uint64, _u64p, _i32p, C.c_uint64, _u8p, _u8p, _u64p, _u32p, _u64p]),
     "umi_dedup_batch": (C.c_int, [C.c_void_p, _u64p, _u64p, _i32p, _u64p, C.c_uint64, C.c_int,
                                   C.c_int, C.c_float, C.c_int, C.c_int32, _u8p, _u32p,
                                   C.POINTER(Stats)]),

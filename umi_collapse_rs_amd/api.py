@@ -222,6 +222,64 @@ class Context:
         b = int(nb.value)
         return boff[:b + 1], blen[:b], int(ne.value), bool(any_n.value)
 
+    def consensus_seqs(self, seqs, quals, staged, kept, root):
+        """One consensus read per cluster (umi_consensus_seqs): seqs / quals as given to stage_seqs,
+        staged the dict it returned, kept / root from dedup_seqs.  Returns (cons_seqs, cons_quals,
+        cluster_reads): lists of bytes and a uint32 array over the kept entries in ascending entry order."""
+        bs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        qs = [q.encode() if isinstance(q, str) else bytes(q) for q in quals]
+        n = len(bs)
+        if len(qs) != n or any(len(a) != len(b) for a, b in zip(bs, qs)):
+            raise ValueError("quals must match seqs read by read")
+        lens = np.array([len(b) for b in bs], dtype=np.uint32)
+        total = int(lens.sum(dtype=np.uint64)) if n else 0
+        seq_pos = np.zeros(max(1, n), dtype=np.uint64)
+        if n:
+            seq_pos[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+        qual_pos = seq_pos + np.uint64(total)
+        buf = np.frombuffer((b"".join(bs) + b"".join(qs)) or b"\0", dtype=np.uint8)
+        eor = np.ascontiguousarray(staged["entry_of_read"], dtype=np.uint32)
+        freq = np.ascontiguousarray(staged["freq"], dtype=np.int32)
+        boff = np.ascontiguousarray(staged["bucket_off"], dtype=np.uint64)
+        blen = np.ascontiguousarray(staged["bucket_len"], dtype=np.int32)
+        kept = np.ascontiguousarray(kept, dtype=np.uint8)
+        root = np.ascontiguousarray(root, dtype=np.uint32)
+        ne = len(freq)
+        if len(eor) != n or len(kept) != ne or len(root) != ne or len(blen) != len(boff) - 1:
+            raise ValueError("entry_of_read / kept / root / bucket table do not match the reads and entries")
+        cons_seq, cons_qual = np.zeros(max(1, total), np.uint8), np.zeros(max(1, total), np.uint8)
+        cons_off, cr = np.zeros(max(1, ne), np.uint64), np.zeros(max(1, ne), np.uint32)
+        nbytes = C.c_uint64(0)
+        check(load().umi_consensus_seqs(self._h, ptr(buf, C.c_uint8), ptr(seq_pos, C.c_uint64), ptr(qual_pos, C.c_uint64),
+                                        ptr(lens, C.c_uint32), n, ptr(eor, C.c_uint32), ptr(freq, C.c_int32),
+                                        ptr(kept, C.c_uint8), ptr(root, C.c_uint32), ne, ptr(boff, C.c_uint64),
+                                        ptr(blen, C.c_int32), len(boff) - 1, ptr(cons_seq, C.c_uint8),
+                                        ptr(cons_qual, C.c_uint8), ptr(cons_off, C.c_uint64), ptr(cr, C.c_uint32),
+                                        C.byref(nbytes)))
+        ks = np.flatnonzero(kept[:ne])
+        bucket_of = np.searchsorted(boff, ks, side="right") - 1
+        sb, qb = cons_seq.tobytes(), cons_qual.tobytes()
+        out_s, out_q = [], []
+        for r, b in zip(ks, bucket_of):
+            o, L = int(cons_off[r]), int(blen[b])
+            out_s.append(sb[o:o + L])
+            out_q.append(qb[o:o + L])
+        return out_s, out_q, cr[ks]
+
+    def consensus_seqs_device(self, d_text, d_seq_pos, d_qual_pos, d_len, n_reads, d_entry_of_read, d_freq, d_kept,
+                              d_root, n_entries, bucket_off, bucket_len, d_cons_seq, d_cons_qual, d_cons_off,
+                              d_cluster_reads=0, stream=0):
+        """The same on raw device pointers (umi_consensus_seqs_device; the bucket table stays on the host):
+        fills d_cons_seq / d_cons_qual / d_cons_off / d_cluster_reads and returns the consensus bytes written."""
+        boff = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        blen = np.ascontiguousarray(bucket_len, dtype=np.int32)
+        nbytes = C.c_uint64(0)
+        check(load().umi_consensus_seqs_device(self._h, d_text, d_seq_pos, d_qual_pos or None, d_len, n_reads,
+                                               d_entry_of_read, d_freq, d_kept, d_root, n_entries, ptr(boff, C.c_uint64),
+                                               ptr(blen, C.c_int32), len(boff) - 1, d_cons_seq, d_cons_qual, d_cons_off,
+                                               d_cluster_reads or None, C.byref(nbytes), stream or None))
+        return int(nbytes.value)
+
     def stage_reads(self, align_key, umi_bytes, score, umi_len, merge=1, align_key_bits=64):
         """Read staging on the device (host arrays in and out): reads in file order ->
         dict(keys, nmask, freq, rep, bucket_off) in canonical order, the batched path's input

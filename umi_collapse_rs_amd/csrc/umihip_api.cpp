@@ -235,6 +235,9 @@ struct umi_ctx {
     DevBuf sq_text, sq_pos, sq_len, sq_eor;
     // whole-read keys (umi_dedup_seqs*): group table, records and their sort, runs, tile tasks
     DevBuf seq_groups, seq_ka, seq_kb, seq_va, seq_vb, seq_flag, seq_runid, seq_rs, seq_tend, seq_tmp;
+    // consensus of their clusters (umi_consensus_seqs*): workspace; the host-buffer form's outputs
+    DevBuf cons_ws, cons_seq, cons_qual, cons_off, cons_cr;
+    uint32_t cons_split = 512; // clusters of at least this many reads are summed in pieces by the whole grid
     uint64_t *h_boff = nullptr;               // pinned staging of the bucket table
     size_t h_boff_cap = 0;
     PinnedBuf h_tasks;                        // pinned staging of the bit-sliced tile-task lists
@@ -1862,7 +1865,8 @@ void umi_ctx_destroy(umi_ctx *ctx)
                       &ctx->stage_ws, &ctx->st_align, &ctx->st_group, &ctx->st_umi, &ctx->st_score, &ctx->st_keys, &ctx->st_nmask,
                       &ctx->st_freq, &ctx->st_rep, &ctx->st_boff, &ctx->sq_text, &ctx->sq_pos, &ctx->sq_len, &ctx->sq_eor,
                       &ctx->seq_groups, &ctx->seq_ka, &ctx->seq_kb, &ctx->seq_va, &ctx->seq_vb, &ctx->seq_flag,
-                      &ctx->seq_runid, &ctx->seq_rs, &ctx->seq_tend, &ctx->seq_tmp};
+                      &ctx->seq_runid, &ctx->seq_rs, &ctx->seq_tend, &ctx->seq_tmp,
+                      &ctx->cons_ws, &ctx->cons_seq, &ctx->cons_qual, &ctx->cons_off, &ctx->cons_cr};
     for (DevBuf *b : bufs) b->release();
     if (ctx->h_boff) (void)hipHostFree(ctx->h_boff);
     ctx->h_tasks.release();
@@ -1953,6 +1957,9 @@ int umi_ctx_set_option(umi_ctx *ctx, const char *name, int64_t value)
     } else if (!strcmp(name, "seg_min")) {
         if (value < 2 || value > (1ll << 31)) return fail(UMI_ERR_ARG, "seg_min must be in 2..2^31");
         ctx->seg_min = (uint32_t)value;
+    } else if (!strcmp(name, "cons_split")) {
+        if (value < 2 || value > (1ll << 30)) return fail(UMI_ERR_ARG, "cons_split must be in 2..2^30");
+        ctx->cons_split = (uint32_t)value;
     } else if (!strcmp(name, "fused_sliced")) {
         ctx->fused_sliced = value != 0;
     } else if (!strcmp(name, "fused_blocks")) {
@@ -2951,6 +2958,157 @@ int umi_dedup_seqs(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask, in
     HIP_TRY(hipMemcpyAsync(kept, ctx->out_kept.p, n, hipMemcpyDeviceToHost, s));
     if (root) HIP_TRY(hipMemcpyAsync(root, ctx->out_root.p, n * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return UMI_OK;
+}
+
+} // extern "C"
+
+// ---- consensus of the clusters of whole reads ---------------------------------------------------
+namespace {
+int cons_check(umi_ctx *ctx, uint64_t n_reads, uint64_t n_entries, const uint64_t *bucket_off, const int32_t *bucket_len,
+               uint64_t n_buckets)
+{
+    if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
+    if (ctx->subs.size() > 1) return fail(UMI_ERR_ARG, "umi_consensus_seqs takes a single-device context");
+    if (n_reads >= (1ull << 30))
+        return fail(UMI_ERR_ARG, "%llu reads exceed the 30-bit index space of one call", (unsigned long long)n_reads);
+    if (!bucket_off || (n_buckets && !bucket_len)) return fail(UMI_ERR_ARG, "bucket_off/bucket_len is NULL");
+    if (n_buckets >= (1ull << 31)) return fail(UMI_ERR_ARG, "too many buckets");
+    if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
+    for (uint64_t b = 0; b < n_buckets; b++) {
+        if (bucket_off[b + 1] < bucket_off[b])
+            return fail(UMI_ERR_ARG, "bucket_off not monotone at bucket %llu", (unsigned long long)b);
+        if (bucket_len[b] < 0 || bucket_len[b] > UMI_MAX_SEQ_LEN)
+            return fail(UMI_ERR_ARG, "bucket_len[%llu] = %d outside 0..%d", (unsigned long long)b, bucket_len[b],
+                        UMI_MAX_SEQ_LEN);
+    }
+    if ((n_buckets ? bucket_off[n_buckets] : 0) != n_entries)
+        return fail(UMI_ERR_ARG, "bucket_off ends at %llu, n_entries is %llu",
+                    (unsigned long long)(n_buckets ? bucket_off[n_buckets] : 0), (unsigned long long)n_entries);
+    if (n_entries > n_reads)
+        return fail(UMI_ERR_ARG, "%llu entries for %llu reads", (unsigned long long)n_entries, (unsigned long long)n_reads);
+    return UMI_OK;
+}
+} // namespace
+
+extern "C" {
+
+int umi_consensus_seqs_device(umi_ctx *ctx, const uint8_t *d_text, const uint64_t *d_seq_pos, const uint64_t *d_qual_pos,
+                              const uint32_t *d_len, uint64_t n_reads, const uint32_t *d_entry_of_read,
+                              const int32_t *d_freq, const uint8_t *d_kept, const uint32_t *d_root, uint64_t n_entries,
+                              const uint64_t *bucket_off, const int32_t *bucket_len, uint64_t n_buckets,
+                              uint8_t *d_cons_seq, uint8_t *d_cons_qual, uint64_t *d_cons_off, uint32_t *d_cluster_reads,
+                              uint64_t *cons_bytes, void *hip_stream)
+{
+    int rc = cons_check(ctx, n_reads, n_entries, bucket_off, bucket_len, n_buckets);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    if (!cons_bytes) return fail(UMI_ERR_ARG, "cons_bytes is NULL");
+    if (n_reads && !d_qual_pos) return fail(UMI_ERR_ARG, "d_qual_pos is NULL: a consensus needs the qualities");
+    if (n_reads && (!d_text || !d_seq_pos || !d_len || !d_entry_of_read || !d_freq || !d_kept || !d_root || !d_cons_seq ||
+                    !d_cons_qual || !d_cons_off))
+        return fail(UMI_ERR_ARG, "a required device pointer is NULL");
+    *cons_bytes = 0;
+    if (n_reads == 0) return UMI_OK; // (and no entry: there are at most as many as reads)
+    if (n_entries == 0)
+        return fail(UMI_ERR_ORDER, "%llu reads break the input contract (entry_of_read outside the 0 entries)",
+                    (unsigned long long)n_reads);
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
+    if ((rc = ctx->cons_ws.reserve(consensus_workspace_bytes((uint32_t)n_reads, (uint32_t)n_entries, (uint32_t)n_buckets,
+                                                             ctx->cons_split))))
+        return rc;
+    ConsFault f;
+    const int r = consensus_on_device(ctx->cons_ws.p, d_text, d_seq_pos, d_qual_pos, d_len, (uint32_t)n_reads, d_entry_of_read,
+                                      d_freq, d_kept, d_root, (uint32_t)n_entries, bucket_off, bucket_len, (uint32_t)n_buckets,
+                                      ctx->cons_split, (uint32_t)ctx->n_cus, d_cons_seq, d_cons_qual, d_cons_off,
+                                      d_cluster_reads, cons_bytes, &f, ctx->h_counters, (hipStream_t)hip_stream);
+    if (r == 1) {
+        if (f.bad_read)
+            return fail(UMI_ERR_ORDER, "%llu reads break the input contract (entry_of_read outside the %llu entries)",
+                        f.bad_read, (unsigned long long)n_entries);
+        if (f.bad_root)
+            return fail(UMI_ERR_ORDER, "%llu entries break the input contract (root outside the entries, or not a kept entry)",
+                        f.bad_root);
+        if (f.bad_len)
+            return fail(UMI_ERR_ORDER, "%llu reads break the input contract (not as long as the bucket of their entry)",
+                        f.bad_len);
+        if (f.empty)
+            return fail(UMI_ERR_ORDER, "%llu kept entries break the input contract (no read belongs to their cluster)", f.empty);
+        return fail(UMI_ERR_ORDER, "freq sums to %lld over the entries, there are %llu reads", (long long)f.freq_sum,
+                    (unsigned long long)n_reads);
+    }
+    if (r < 0) return fail(UMI_ERR_HIP, "consensus: %s", hipGetErrorString((hipError_t)(-r)));
+    return UMI_OK;
+}
+
+int umi_consensus_seqs(umi_ctx *ctx, const uint8_t *text, const uint64_t *seq_pos, const uint64_t *qual_pos,
+                       const uint32_t *len, uint64_t n_reads, const uint32_t *entry_of_read, const int32_t *freq,
+                       const uint8_t *kept, const uint32_t *root, uint64_t n_entries, const uint64_t *bucket_off,
+                       const int32_t *bucket_len, uint64_t n_buckets, uint8_t *cons_seq, uint8_t *cons_qual,
+                       uint64_t *cons_off, uint32_t *cluster_reads, uint64_t *cons_bytes)
+{
+    int rc = cons_check(ctx, n_reads, n_entries, bucket_off, bucket_len, n_buckets);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    if (!cons_bytes) return fail(UMI_ERR_ARG, "cons_bytes is NULL");
+    if (n_reads && !qual_pos) return fail(UMI_ERR_ARG, "qual_pos is NULL: a consensus needs the qualities");
+    if (n_reads && (!text || !seq_pos || !len || !entry_of_read || !freq || !kept || !root || !cons_seq || !cons_qual || !cons_off))
+        return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    *cons_bytes = 0;
+    if (n_reads == 0) return UMI_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx);
+    // the text that is looked at, and what the consensus may fill: the caller's capacity
+    size_t text_bytes = 1, cap = 0;
+    for (uint64_t i = 0; i < n_reads; i++) {
+        if (len[i] > UMI_MAX_SEQ_LEN)
+            return fail(UMI_ERR_ARG, "read %llu has %u bases, more than %d", (unsigned long long)i, len[i], UMI_MAX_SEQ_LEN);
+        text_bytes = std::max<size_t>(text_bytes, std::max(seq_pos[i], qual_pos[i]) + len[i]);
+        cap += len[i];
+    }
+    const size_t n = (size_t)n_reads, ne = std::max<size_t>((size_t)n_entries, 1);
+    if ((rc = ctx->sq_text.reserve(text_bytes)) || (rc = ctx->sq_pos.reserve(n * 16)) || (rc = ctx->sq_len.reserve(n * 4)) ||
+        (rc = ctx->sq_eor.reserve(n * 4)) || (rc = ctx->in_freq.reserve(ne * 4)) || (rc = ctx->out_kept.reserve(ne)) ||
+        (rc = ctx->out_root.reserve(ne * 4)) || (rc = ctx->cons_seq.reserve(cap + 8)) || (rc = ctx->cons_qual.reserve(cap + 8)) ||
+        (rc = ctx->cons_off.reserve(ne * 8)) || (rc = ctx->cons_cr.reserve(ne * 4)))
+        return rc;
+    hipStream_t s = ctx->own_stream;
+    uint64_t *d_pos = ctx->sq_pos.as<uint64_t>(); // (seq_pos, then qual_pos)
+    HIP_TRY(hipMemcpyAsync(ctx->sq_text.p, text, text_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_pos, seq_pos, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_pos + n, qual_pos, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ctx->sq_len.p, len, n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ctx->sq_eor.p, entry_of_read, n * 4, hipMemcpyHostToDevice, s));
+    if (n_entries) {
+        HIP_TRY(hipMemcpyAsync(ctx->in_freq.p, freq, n_entries * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(ctx->out_kept.p, kept, n_entries, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(ctx->out_root.p, root, n_entries * 4, hipMemcpyHostToDevice, s));
+    }
+    rc = umi_consensus_seqs_device(ctx, ctx->sq_text.as<uint8_t>(), d_pos, d_pos + n, ctx->sq_len.as<uint32_t>(), n_reads,
+                                   ctx->sq_eor.as<uint32_t>(), ctx->in_freq.as<int32_t>(), ctx->out_kept.as<uint8_t>(),
+                                   ctx->out_root.as<uint32_t>(), n_entries, bucket_off, bucket_len, n_buckets,
+                                   ctx->cons_seq.as<uint8_t>(), ctx->cons_qual.as<uint8_t>(), ctx->cons_off.as<uint64_t>(),
+                                   ctx->cons_cr.as<uint32_t>(), cons_bytes, s);
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    // what came out, where it is defined: the kept entries' offsets and counts, the bytes in front of cons_bytes
+    std::vector<uint64_t> off_all((size_t)n_entries);
+    std::vector<uint32_t> cr_all((size_t)n_entries);
+    if (*cons_bytes) {
+        HIP_TRY(hipMemcpyAsync(cons_seq, ctx->cons_seq.p, (size_t)*cons_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(cons_qual, ctx->cons_qual.p, (size_t)*cons_bytes, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipMemcpyAsync(off_all.data(), ctx->cons_off.p, (size_t)n_entries * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(cr_all.data(), ctx->cons_cr.p, (size_t)n_entries * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (uint64_t e = 0; e < n_entries; e++)
+        if (kept[e]) {
+            cons_off[e] = off_all[e];
+            if (cluster_reads) cluster_reads[e] = cr_all[e];
+        }
     return UMI_OK;
 }
 

@@ -360,6 +360,25 @@ int stage_seqs_on_device(void *workspace, const uint8_t *d_text, const uint64_t 
                          uint64_t *n_entries_out, uint64_t *n_buckets_out, int *any_n, SeqFault *fault,
                          unsigned long long *h_pinned4, hipStream_t s);
 
+// ---- consensus of the clusters of whole reads (umihip_consensus.hip: umi_consensus_seqs) ----
+// The inputs are what stage_seqs_on_device and the whole-read collapse leave on the device (n_entries >= 1,
+// the bucket table on the host); cons_seq / cons_qual take the kept entries' consensus back to back in
+// entry order, cons_off [n_entries] where each starts, cluster_reads (may be null) its members.  split:
+// clusters of at least this many reads are summed in pieces by the whole grid.  h_pinned: 16 pinned
+// words.  0 ok; 1 the inputs break the contract (fault says how, nothing was written); negative:
+// -(hipError_t)
+struct ConsFault {
+    unsigned long long bad_root = 0, bad_read = 0, bad_len = 0, empty = 0, freq_sum = 0;
+};
+uint32_t consensus_effective_split(uint32_t n_reads, uint32_t split);
+size_t consensus_workspace_bytes(uint32_t n_reads, uint32_t n_entries, uint32_t n_buckets, uint32_t split);
+int consensus_on_device(void *workspace, const uint8_t *d_text, const uint64_t *d_seq_pos, const uint64_t *d_qual_pos,
+                        const uint32_t *d_len, uint32_t n_reads, const uint32_t *d_eor, const int32_t *d_freq,
+                        const uint8_t *d_kept, const uint32_t *d_root, uint32_t n_entries, const uint64_t *h_bucket_off,
+                        const int32_t *h_bucket_len, uint32_t n_buckets, uint32_t split, uint32_t n_cus, uint8_t *d_cons_seq,
+                        uint8_t *d_cons_qual, uint64_t *d_cons_off, uint32_t *d_cluster_reads, uint64_t *cons_bytes,
+                        ConsFault *fault, unsigned long long *h_pinned, hipStream_t s);
+
 // ---- sort and scan primitives of the staging (umihip_radix.hip) ----
 constexpr int RADIX_BINS = 256, RADIX_MAX_PASSES = 8; // 8-bit digits; a 64-bit key has at most eight
 constexpr int RADIX_HIST_PARTS = 2048;                // blocks of a kernel that counts digits, at most

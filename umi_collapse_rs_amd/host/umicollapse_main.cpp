@@ -32,6 +32,16 @@
 // --umi_sep and --data are accepted and ignored.  --stage gpu / auto stage the reads on the device
 // (umi_stage_seqs_device; auto means host only with --dump-staging or 2^30 reads or more), --stage host
 // on the host; same output and messages either way.
+// --consensus (fastq mode; not the reference's, tests/consensus_model.py defines it): the same records in
+// the same order, but of each the sequence and quality lines are its cluster's consensus -- per column the
+// base with the greatest sum of (quality - 33) over all the cluster's reads, ties by the number of reads and
+// then the order ACGT, quality min(93, winner's sum - the others'), N and '!' where every read has N
+// (umi_consensus_seqs, include/umihip.h) -- trimmed by -u N like any read, and the header gets
+// " cluster_size=<reads>" appended.  --consensus-min-reads M (default 1) leaves out the clusters of fewer
+// than M reads; the summary gains "Number of clusters below --consensus-min-reads: <n>".  With the device
+// staging nothing more goes up (text, offsets, entry of every read and the collapse's result are resident);
+// with --stage host the text and the offsets go up for the one call.  Refused with status 101: --consensus
+// outside fastq mode, with --tag or --dump-staging; --consensus-min-reads without it or not a number >= 1.
 // --two-pass (the reference parses it and ignores it; UMICollapse's meaning): the input is read twice and
 // never held.  Pass 1 counts, writes the kept unmapped reads and notes the last read of every alignment
 // key; pass 2 holds a position's reads until its last one, deduplicates closed positions in windows of
@@ -98,6 +108,9 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     std::string umi_tag;         // --umi-tag XX: the UMI is the value of this aux tag, not the name's suffix
     std::string cell_tag = "CB"; // --cell-tag XX: the cell barcode's tag (--per-cell)
     bool per_cell = false, cell_tag_given = false; // --per-cell: positions are (alignment, cell barcode)
+    bool consensus = false;           // --consensus (fastq mode): every cluster written as its consensus read
+    uint64_t consensus_min_reads = 1; // --consensus-min-reads M: clusters of fewer members are left out
+    bool consensus_min_given = false;
 };
 
 [[noreturn]] void die(const std::string &msg)
@@ -137,6 +150,15 @@ struct HipLib {
     int (*dedup_seqs_device)(umi_ctx *, const uint64_t *, const uint64_t *, int, const int32_t *, const uint64_t *,
                              const int32_t *, uint64_t, int, float, int, int32_t, uint8_t *, uint32_t *, void *,
                              umi_stats *) = nullptr;
+    // --consensus: resolved only when the flag is given, so that a library without them serves every other run
+    bool want_consensus = false;
+    int (*consensus_seqs)(umi_ctx *, const uint8_t *, const uint64_t *, const uint64_t *, const uint32_t *, uint64_t,
+                          const uint32_t *, const int32_t *, const uint8_t *, const uint32_t *, uint64_t, const uint64_t *,
+                          const int32_t *, uint64_t, uint8_t *, uint8_t *, uint64_t *, uint32_t *, uint64_t *) = nullptr;
+    int (*consensus_seqs_device)(umi_ctx *, const uint8_t *, const uint64_t *, const uint64_t *, const uint32_t *, uint64_t,
+                                 const uint32_t *, const int32_t *, const uint8_t *, const uint32_t *, uint64_t,
+                                 const uint64_t *, const int32_t *, uint64_t, uint8_t *, uint8_t *, uint64_t *, uint32_t *,
+                                 uint64_t *, void *) = nullptr;
     // (the HIP runtime the library brings along: device buffers for the arrays above)
     int (*hip_set_device)(int) = nullptr; // (the current device is per thread: the context was made on another)
     int (*hip_malloc)(void **, size_t) = nullptr;
@@ -171,6 +193,10 @@ struct HipLib {
         stage_seqs = (decltype(stage_seqs))sym("umi_stage_seqs");
         stage_seqs_device = (decltype(stage_seqs_device))sym("umi_stage_seqs_device");
         dedup_seqs_device = (decltype(dedup_seqs_device))sym("umi_dedup_seqs_device");
+        if (want_consensus) {
+            consensus_seqs = (decltype(consensus_seqs))sym("umi_consensus_seqs");
+            consensus_seqs_device = (decltype(consensus_seqs_device))sym("umi_consensus_seqs_device");
+        }
         hip_set_device = (decltype(hip_set_device))sym("hipSetDevice");
         hip_malloc = (decltype(hip_malloc))sym("hipMalloc");
         hip_memcpy = (decltype(hip_memcpy))sym("hipMemcpy");
@@ -247,6 +273,10 @@ void usage()
               "                           (-i must be a regular file; not with --tag or fastq mode)\n"
               "      --two-pass-window <N> reads per GPU call with --two-pass [default: 2097152]\n"
               "      --compress-level <N> deflate level of the output BAM, 0..9 [default: 1]\n"
+              "      --consensus          fastq mode: write every cluster as its consensus read -- each column the\n"
+              "                           quality-weighted majority of all the cluster's reads -- in place of the kept\n"
+              "                           read, the header with cluster_size=<reads> appended (not with --tag)\n"
+              "      --consensus-min-reads <M> with --consensus: leave out clusters of fewer than M reads [default: 1]\n"
               "      --stage <WHERE>      gpu, host or auto: where reads are merged per (position, UMI) [default: auto]\n"
               "      --umi-tag <XX>       the UMI is the value of aux tag XX (type Z, e.g. RX or UB) instead of the\n"
               "                           read name's suffix; reads without it are dropped (bam/sam mode)\n"
@@ -311,6 +341,15 @@ Cli parse(int argc, char **argv)
             else { c.cell_tag = t; c.cell_tag_given = true; }
         }
         else if (a == "--per-cell") c.per_cell = true;
+        else if (a == "--consensus") c.consensus = true;
+        else if (a == "--consensus-min-reads") {
+            const char *v = need(i);
+            char *end = nullptr;
+            const long long m = std::strtoll(v, &end, 10);
+            if (end == v || *end != '\0' || m < 1) die("--consensus-min-reads wants a number of reads, 1 or more");
+            c.consensus_min_reads = (uint64_t)m;
+            c.consensus_min_given = true;
+        }
         else if (a == "--compress-level") {
             c.compress_level = std::atoi(need(i));
             if (c.compress_level < 0 || c.compress_level > 9) die("--compress-level wants 0..9");
@@ -521,6 +560,11 @@ struct FastqResult {
     std::vector<uint8_t> kept;
     std::vector<uint32_t> root;
     std::vector<uint32_t> entry_of_read;
+    // --consensus: the kept entries' consensus back to back (entry e's at cons_off[e], its bucket's length) and
+    // the reads of their clusters
+    std::vector<uint8_t> cons_seq, cons_qual;
+    std::vector<uint64_t> cons_off;
+    std::vector<uint32_t> cluster_reads;
     umi_stats st;
     double t_staging, t_init, t_hot;
     bool gpu_staged;
@@ -592,7 +636,7 @@ struct FastqResult {
     uint64_t *d_keys = (uint64_t *)dev(8 * m * n_words), *d_nmask = (uint64_t *)dev(8 * m * n_words);
     int32_t *d_freq = (int32_t *)dev(4 * m);
     uint64_t *d_rep = (uint64_t *)dev(8 * m);
-    uint32_t *d_eor = args.track_clusters ? (uint32_t *)dev(4 * m) : nullptr;
+    uint32_t *d_eor = args.track_clusters || args.consensus ? (uint32_t *)dev(4 * m) : nullptr;
     up(d_text, text.data(), text.size());
     up(d_pos, pos.data(), 8 * n_ok);
     up(d_pos + n_ok, pos.data() + n_ok, 8 * n_ok);
@@ -635,9 +679,29 @@ struct FastqResult {
         std::vector<uint64_t> rep64(n);
         down(rep64.data(), d_rep, 8 * n);
         for (size_t e = 0; e < n; e++) res.rep[e] = (uint32_t)rep64[e];
-        if (d_eor) {
+        if (args.track_clusters) {
             res.entry_of_read.resize(n_reads);
             down(res.entry_of_read.data(), d_eor, 4 * n_reads);
+        }
+        if (args.consensus) { // everything it reads is resident; the consensus, its offsets and the counts come back
+            size_t cap = 0;
+            for (size_t i = 0; i < n_ok; i++) cap += len[i];
+            uint8_t *d_cs = (uint8_t *)dev(cap), *d_cq = (uint8_t *)dev(cap);
+            uint64_t *d_coff = (uint64_t *)dev(8 * n);
+            uint32_t *d_cr = (uint32_t *)dev(4 * n);
+            uint64_t cons_bytes = 0;
+            if (lib.consensus_seqs_device(ctx, d_text, d_pos, d_pos + n_ok, d_len, n_ok, d_eor, d_freq, d_kept, d_root, n,
+                                          res.off.data(), blen.data(), nb, d_cs, d_cq, d_coff, d_cr, &cons_bytes,
+                                          nullptr) != UMI_OK)
+                die(lib.last_error());
+            res.cons_seq.resize(cons_bytes);
+            res.cons_qual.resize(cons_bytes);
+            res.cons_off.resize(n);
+            res.cluster_reads.resize(n);
+            down(res.cons_seq.data(), d_cs, cons_bytes);
+            down(res.cons_qual.data(), d_cq, cons_bytes);
+            down(res.cons_off.data(), d_coff, 8 * n);
+            down(res.cluster_reads.data(), d_cr, 4 * n);
         }
     }
     const double t_gpu1 = now_s();
@@ -667,6 +731,9 @@ int run_fastq(const Cli &args, int algo, int merge, HipLib &lib)
     if (args.stage != "auto" && args.stage != "gpu" && args.stage != "host") die("--stage wants gpu, host or auto");
     if (args.stage == "gpu" && !args.dump_staging.empty()) die("--stage gpu does not go with --dump-staging");
     if (args.devices.size() > 1) die("fastq mode runs on one GPU: --devices takes one id here");
+    if (args.consensus && args.track_clusters) die("--consensus does not go with --tag (which writes every read as it is)");
+    if (args.consensus && !args.dump_staging.empty()) die("--consensus does not go with --dump-staging (which stops before the GPU)");
+    lib.want_consensus = args.consensus;
     if (merge == 2) die("Invalid algorithm combination: " + args.algo + " , " + args.merge + " and " + args.data);
     // the GPU is woken while the file is read (as in BAM mode: a tiny staging call and a tiny dedup call
     // load the library's code objects)
@@ -821,8 +888,8 @@ int run_fastq(const Cli &args, int algo, int merge, HipLib &lib)
     umi_stats st;
     std::memset(&st, 0, sizeof(st));
     double t_gpu0 = now_s(), t_gpu1 = t_gpu0;
+    umi_ctx *ctx = nullptr;
     if (n) {
-        umi_ctx *ctx = nullptr;
         if (warm.valid()) { // (--stage auto with 2^30 reads or more: the context the start-up thread made)
             ctx = warm.get();
             if (!ctx) die(warm_error);
@@ -838,10 +905,10 @@ int run_fastq(const Cli &args, int algo, int merge, HipLib &lib)
             die(lib.last_error());
         t_gpu1 = now_s();
     }
-    FastqResult res{n, nb, std::move(off), std::move(freq), std::move(rep), std::move(kept), std::move(root), {}, st,
+    FastqResult res{n, nb, std::move(off), std::move(freq), std::move(rep), std::move(kept), std::move(root), {}, {}, {}, {}, {}, st,
                     t_stage - t_read, t_gpu0 - t_stage, t_gpu1 - t_gpu0, false};
-    // entry of every read (--tag): its sequence's, looked up again per bucket
-    if (args.track_clusters) {
+    // entry of every read (--tag, --consensus): its sequence's, looked up again per bucket
+    if (args.track_clusters || args.consensus) {
         res.entry_of_read.resize(n_reads);
         std::vector<std::unordered_map<std::string, uint32_t>> index(nb);
         for (size_t b = 0; b < nb; b++)
@@ -851,6 +918,30 @@ int run_fastq(const Cli &args, int algo, int merge, HipLib &lib)
             const umi::fastq::Record &r = recs[i];
             res.entry_of_read[i] = index[bucket_of_len[r.len]].at(std::string((const char *)d + r.seq, r.len));
         }
+    }
+    if (args.consensus && n) { // the text and the reads' offsets go up for this one call
+        if (!lib.consensus_seqs) die("libumihip.so lacks umi_consensus_seqs");
+        std::vector<uint64_t> pos(2 * n_reads);
+        std::vector<uint32_t> len(n_reads);
+        size_t cap = 0;
+        for (size_t i = 0; i < n_reads; i++) {
+            pos[i] = recs[i].seq;
+            pos[n_reads + i] = recs[i].qual;
+            len[i] = (uint32_t)recs[i].len;
+            cap += recs[i].len;
+        }
+        res.cons_seq.resize(cap + 1);
+        res.cons_qual.resize(cap + 1);
+        res.cons_off.assign(n, 0);
+        res.cluster_reads.assign(n, 0);
+        uint64_t cons_bytes = 0;
+        if (lib.consensus_seqs(ctx, d, pos.data(), pos.data() + n_reads, len.data(), n_reads, res.entry_of_read.data(),
+                               res.freq.data(), res.kept.data(), res.root.data(), n, res.off.data(), blen.data(), nb,
+                               res.cons_seq.data(), res.cons_qual.data(), res.cons_off.data(), res.cluster_reads.data(),
+                               &cons_bytes) != UMI_OK)
+            die(lib.last_error());
+        t_gpu1 = now_s();
+        res.t_hot = t_gpu1 - t_gpu0;
     }
     write_fastq(args, text, recs, res, t_start, t_read, t_gpu1);
 }
@@ -884,8 +975,33 @@ int run_fastq(const Cli &args, int algo, int merge, HipLib &lib)
         put(r.qual + trim, r.len - trim);
         out += '\n';
     };
-    size_t n_out = 0;
-    if (!args.track_clusters) {
+    size_t n_out = 0, n_below = 0;
+    if (args.consensus) {
+        // the same records in the same order, each with its cluster's consensus for sequence and quality
+        std::vector<uint32_t> len_of(n + 1, 0);
+        for (size_t b = 0; b < nb; b++)
+            for (uint64_t e = off[b]; e < off[b + 1]; e++) len_of[e] = (uint32_t)recs[rep[e]].len;
+        for (size_t i = 0; i < n_reads; i++) {
+            const uint32_t e = entry_of_rep[i];
+            if (e == UINT32_MAX || !kept[e]) continue;
+            if (res.cluster_reads[e] < args.consensus_min_reads) {
+                n_below++;
+                continue;
+            }
+            const umi::fastq::Record &r = recs[i];
+            const size_t at = res.cons_off[e], L = len_of[e];
+            put(r.head, r.head_len);
+            out += " cluster_size=" + std::to_string(res.cluster_reads[e]);
+            out += '\n';
+            out.append((const char *)res.cons_seq.data() + at + trim, L - trim);
+            out += '\n';
+            put(r.plus, r.plus_len);
+            out += '\n';
+            out.append((const char *)res.cons_qual.data() + at + trim, L - trim);
+            out += '\n';
+            n_out++;
+        }
+    } else if (!args.track_clusters) {
         for (size_t i = 0; i < n_reads; i++) {
             const uint32_t e = entry_of_rep[i];
             if (e == UINT32_MAX || !kept[e]) continue;
@@ -930,6 +1046,7 @@ int run_fastq(const Cli &args, int algo, int merge, HipLib &lib)
     std::fprintf(stderr, "Max number of distinct sequences of one length: %zu\n", max_bucket);
     std::fprintf(stderr, args.track_clusters ? "Number of groups of reads: %llu\n" : "Number of reads after deduplicating: %llu\n",
                  (unsigned long long)st.n_kept);
+    if (args.consensus) std::fprintf(stderr, "Number of clusters below --consensus-min-reads: %zu\n", n_below);
     std::fprintf(stderr,
                  "phases: read+parse %.3f s, staging (%s) %.3f s, gpu init %.3f s, hot path (H2D+GPU+D2H) %.3f s "
                  "[%llu pairs, %llu evaluated], write %.3f s\n",
@@ -1425,6 +1542,8 @@ int main(int argc, char **argv)
     if (args.merge.empty()) args.merge = args.mode == "fastq" ? "avgqual" : "mapqual"; // main.rs:33-39
     if (args.track_clusters && args.two_pass) die("Cannot track clusters with the two pass algorithm!");
     if (args.paired && args.keep_unmapped) die("Cannot keep unmapped reads with paired-end reads!");
+    if (args.consensus_min_given && !args.consensus) die("--consensus-min-reads goes with --consensus only");
+    if (args.consensus && args.mode != "fastq") die("--consensus is defined in fastq mode only (-m fastq)");
     if (args.mode != "bam" && args.mode != "sam" && args.mode != "fastq") return 0; // main.rs:49-95: nothing happens
     if (args.track_clusters && args.paired) die("--tag with --paired is not implemented (the reference never reaches its tagging pass)");
     int algo, merge;
