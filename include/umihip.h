@@ -338,7 +338,9 @@ int umi_consensus_seqs(umi_ctx *ctx, const uint8_t *text, const uint64_t *seq_po
  * [bucket_off[b], bucket_off[b+1]).  Inside a bucket entries MUST already be in
  * rank order: freq descending (directional.rs:72), ties in first-appearance
  * order (canonical determinisation); freq >= 1.
- * percentage = Cli.percentage (src/cli.rs:25-26), k = Cli.k (src/cli.rs:18-19).
+ * percentage = Cli.percentage (src/cli.rs:25-26), k = Cli.k (src/cli.rs:18-19):
+ * any k >= 0 up to INT_MAX; a k no distance can reach (128 and more: umi_dist is at most 32 per
+ * key word) means every pair of a bucket, in every entry point that takes a k.
  * adj_max_freq: third argument of remove_near in adjacency.rs:56 (reference: 0).
  * kept[i] = 1 iff entry i survives; survivors in ascending index order are the
  * reference's output order (deduplicate_sam.rs:227-231).  root (may be NULL):

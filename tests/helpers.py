@@ -167,3 +167,231 @@ def grouped_stage_model(align, group, umis, score, umi_len, merge, gbits):
     w_umis, freq, rep, off = stage_model(bucket, u, score, merge)
     keys, nmask = orc.encode_keys_wide(w_umis)
     return dict(keys=keys, nmask=nmask, freq=freq, rep=rep, bucket_off=off)
+
+
+# ---- inputs where k is the limit that decides (tests of k > 3) -------------------------------------
+# Random UMIs sit ~0.75 L substitutions apart: a random bucket has no pair anywhere near k = 6.  These
+# buckets are built from centres with copies at planted distances k-1 .. k+2, their substitution sites
+# chosen against the pigeonhole partition [j L / P, (j + 1) L / P), P = k + 1, that the segment index
+# and the whole-read partition use.
+
+def part_bounds(L, P):
+    return [j * L // P for j in range(P + 1)]
+
+
+def _planted_sites(rng, L, d, P, style, part_len):
+    """d distinct substitution sites.  "last": one per part, parts 0, 1, ... first (d = k leaves only
+    the last part equal: the tightest case of the pigeonhole; d = k + 1 leaves none); "first": parts
+    P-1, P-2, ... (d = k leaves only part 0 equal); "rand": anywhere.  Parts are cut from the first
+    part_len bases; sites beyond the parts' count are random."""
+    d = min(d, L)
+    if style == "rand" or P > part_len:
+        return sorted(rng.choice(L, d, replace=False).tolist())
+    b = part_bounds(part_len, P)
+    order = list(range(P)) if style == "last" else list(range(P - 1, -1, -1))
+    sites = []
+    for j in order[:d]:
+        lo, hi = b[j], b[j + 1]
+        sites.append(int(rng.choice([lo, hi - 1, int(rng.integers(lo, hi))])))  # part edges too
+    rest = [i for i in range(L) if i not in sites]
+    sites += rng.choice(rest, d - len(sites), replace=False).tolist() if d > len(sites) else []
+    return sorted(sites)
+
+
+def planted_bucket(rng, n, L, k, n_frac=0.0, n_sites=(), part_len=None):
+    """n distinct UMIs (fewer when 5^L runs out) in rank order with their freq: centres, and per
+    centre copies at distance exactly k, k+1, k-1, k+2 (clipped to 1..L) in the styles of
+    _planted_sites; with n_frac some copies carry an N at one of their substituted sites, at one of
+    n_sites (the bases that straddle key words) when given.  Frequencies: centres from {1, 3, 5, 9, 20},
+    copies from {1, 1, 2, 3, 5}, so that at p = 0.5 a centre-copy pair is symmetric (1, 1), one-way
+    (5, 2) or no edge at all (3, 3)."""
+    part_len = min(part_len or L, L)
+    P = min(k, 4 * L) + 1  # (k beyond every distance: the parts no longer matter)
+    out = {}
+    tries = 0
+    while len(out) < n and tries < 20 * n + 100:
+        tries += 1
+        c = rng.choice(ALPHA, L)
+        # (the first centre and its first copy, at exactly k, are a one-way pair: a bucket of two entries
+        # already has a removal that only a distance-k edge makes)
+        out.setdefault(c.tobytes(), 9 if not out else int(rng.choice([1, 3, 5, 9, 20])))
+        for d in (k, k + 1, k - 1, k + 2):
+            if d < 1:
+                continue
+            for style in ("last", "first", "rand"):
+                if len(out) >= n:
+                    break
+                u = c.copy()
+                sites = _planted_sites(rng, L, d, P, style, part_len)
+                for i in sites:
+                    u[i] = rng.choice(ALPHA[ALPHA != c[i]])
+                if n_frac and rng.random() < 12 * n_frac:  # (a copy, not a base: ~1 % of the bases of a 12-mer)
+                    at = [i for i in n_sites if i < L]
+                    i = int(rng.choice(at)) if at and rng.random() < 0.5 else int(rng.choice(sites))
+                    if i not in sites:  # keep the planted distance: an N where a substitution was
+                        u[sites[0]] = c[sites[0]]
+                    u[i] = ord("N")
+                out.setdefault(u.tobytes(), 1 if len(out) == 1 else int(rng.choice([1, 1, 2, 3, 5])))
+    umis = [u.decode() for u in out]
+    umis, freq, _ = canonical(umis, list(out.values()))
+    return umis[:n], freq[:n]
+
+
+def dist_blocks(keys, nm, rows=256):
+    """The reference's distance (bitset.rs:77-91 per word, summed, halved) of every pair of one bucket,
+    as (first row, int64 [rows, n]) blocks.  keys / nm: uint64 [n] or [n, w]."""
+    keys = keys.reshape(len(keys), -1)
+    nm = nm.reshape(len(nm), -1)
+    for r0 in range(0, len(keys), rows):
+        x = nm[r0:r0 + rows, None, :] ^ nm[None, :, :]
+        v = np.bitwise_count(x | (keys[r0:r0 + rows, None, :] ^ keys[None, :, :])).astype(np.int64) \
+            - np.bitwise_count(x).astype(np.int64) // 3
+        yield r0, v.sum(-1) // 2
+
+
+SIZE_CLASSES = ((2, 128), (129, 1024), (1025, 1 << 31))  # fused kernel / chunk kernel / deep
+
+
+def limit_census(keys, nm, freq, off, k, p=0.5):
+    """Per size class that the batch contains: pairs at distance exactly k and exactly k + 1, and of
+    the former the symmetric / one-way / no-edge ones under the directional test.  dict class -> counts."""
+    freq = np.asarray(freq, np.int64)
+    out = {}
+    for b in range(len(off) - 1):
+        s, e = int(off[b]), int(off[b + 1])
+        if e - s < 2:
+            continue
+        cls = next(c for c in SIZE_CLASSES if c[0] <= e - s <= c[1])
+        c = out.setdefault(cls, dict(at_k=0, at_k1=0, sym=0, one_way=0, neither=0))
+        f = freq[s:e]
+        thr = np.array([thr_f32(p, int(x)) for x in f])
+        for r0, d in dist_blocks(keys[s:e], nm[s:e]):
+            upper = np.arange(e - s)[None, :] > (r0 + np.arange(len(d)))[:, None]
+            at = (d == k) & upper
+            c["at_k"] += int(at.sum())
+            c["at_k1"] += int(((d == k + 1) & upper).sum())
+            fwd = f[None, :] <= thr[r0:r0 + len(d), None]
+            bwd = f[r0:r0 + len(d), None] <= thr[None, :]
+            c["sym"] += int((at & fwd & bwd).sum())
+            c["one_way"] += int((at & (fwd ^ bwd)).sum())
+            c["neither"] += int((at & ~fwd & ~bwd).sum())
+    return out
+
+
+def assert_k_decides(census, umi_len, k, kept_k, kept_km1):
+    """The two conditions a large-k case meets before the library is called: every size class has a
+    pair at exactly k and one at exactly k + 1 (where the length allows such a distance at all), and
+    the reference removes something through a distance-k edge (its result at k - 1 differs).  For
+    k above the length the largest distance, umi_len, stands in for k."""
+    kk = min(k, umi_len)
+    assert census, "no bucket of two or more entries"
+    for cls, c in census.items():
+        assert c["at_k"] > 0, (cls, c)
+        if kk + 1 <= umi_len:
+            assert c["at_k1"] > 0, (cls, c)
+    assert sum(c["sym"] for c in census.values()) and sum(c["one_way"] for c in census.values()) \
+        and sum(c["neither"] for c in census.values()), census
+    assert not np.array_equal(kept_k, kept_km1), "no removal goes through a distance-k edge"
+
+
+# one-word cases of tests/test_gpu_large_k.py (checked on the CPU in tests/test_large_k_inputs_cpu.py)
+ONE_WORD_BOUNDARY = [(21, 6), (21, 7), (20, 6), (18, 5), (17, 5), (15, 4), (14, 4), (12, 3), (11, 3)]
+ONE_WORD_HUGE = [(L, k) for L in (6, 12, 21) for k in (L - 1, L, L + 1, 2 ** 30 - 1, 2 ** 30, 2 ** 31 - 1)]
+ONE_WORD_SIZES = [0, 1, 2, 63, 64, 65, 127, 128, 129, 511, 512, 513, 1023, 1025, 3000]
+# k >= L - 1 makes (nearly) every pair of a bucket an edge candidate: one bucket per kernel boundary there
+ONE_WORD_SIZES_HUGE = [0, 1, 2, 63, 64, 65, 127, 128, 129, 511, 1025]
+
+
+def seg_index_applies(umi_len, k):
+    """The planner's rule (umihip_plan.hpp), restated: k + 1 parts, 8 at most, of 3 bases or more."""
+    return k + 1 <= 8 and umi_len // (k + 1) >= 3
+
+
+def one_word_batch(L, k, n_frac, seed=0):
+    """The buckets of one one-word case: every size of ONE_WORD_SIZES in one call (of ONE_WORD_SIZES_HUGE
+    where k >= L - 1; fewer entries where 4^L runs out)."""
+    rng = np.random.default_rng(100000 + 1000 * L + min(k, 99) + seed)
+    import oracle as orc
+    keys, nm, fr, off = [], [], [], [0]
+    for n in (ONE_WORD_SIZES_HUGE if k >= L - 1 else ONE_WORD_SIZES):
+        n = min(n, 4 ** L // 3)
+        umis, freq = planted_bucket(rng, n, L, min(k, L), n_frac) if n else ([], [])
+        kk, mm = orc.encode_keys(umis)
+        keys.append(kk); nm.append(mm); fr.extend(freq); off.append(off[-1] + len(umis))
+    return np.concatenate(keys), np.concatenate(nm), np.array(fr, np.int32), np.array(off, np.uint64)
+
+
+WIDE_CASES = [(L, k) for L in (22, 24, 43, 64, 85) for k in (4, 5, 6, 7, 8, L, 2 ** 31 - 1)]
+WIDE_STRADDLE = (21, 42)
+
+
+def wide_batch(L, k, n_frac=0.01, seed=0):
+    """Buckets of one wide case: fused-range sizes, one for the chunk kernel, one deep (2,000 entries).  The parts are cut from the first word's 21 bases, where the segment
+    index looks; N also at the straddling bases 21 and 42."""
+    import oracle as orc
+    rng = np.random.default_rng(200000 + 1000 * L + min(k, 99) + seed)
+    keys, nm, fr, off = [], [], [], [0]
+    for n in (2, 64, 128, 400, 2000):
+        umis, freq = planted_bucket(rng, n, L, min(k, L), n_frac, WIDE_STRADDLE, part_len=21)
+        kk, mm = orc.encode_keys_wide(umis)
+        keys.append(kk); nm.append(mm); fr.extend(freq); off.append(off[-1] + len(umis))
+    return np.concatenate(keys), np.concatenate(nm), np.array(fr, np.int32), np.array(off, np.uint64)
+
+
+SEQ_CASES = sorted({(L, k) for L in (64, 100, 150, 256) for k in (4, 7, 8, 16, L, 400, 401, 2 ** 31 - 1)}
+                   | {(150, 17), (150, 18), (256, 31), (256, 32)})
+SEQ_STRADDLE = (21, 42, 85, 106, 149, 170, 213, 234)
+
+
+def seq_partitioned(L, k):
+    """umi_dedup_seqs cuts a bucket of 512 entries or more into k + 1 parts while a part has 8 bases
+    (k clamped to 400 first)."""
+    return L // (min(k, 400) + 1) >= 8
+
+
+def seq_buckets(L, k, n_frac=0.01, seed=0, sizes=(2, 200, 600)):
+    """[(seqs as bytes, freq)] of one whole-read case: a pair, a bucket below 512 entries (all pairs) and one above
+    (partitioned where seq_partitioned)."""
+    rng = np.random.default_rng(300000 + 1000 * L + min(k, 999) + seed)
+    out = []
+    for n in sizes:
+        umis, freq = planted_bucket(rng, n, L, min(k, L), n_frac, SEQ_STRADDLE)
+        out.append(([u.encode() for u in umis], freq))
+    return out
+
+
+def dense_clusters(rng, n_centres, copies, L, d_max):
+    """Centres with many copies within d_max / 2 substitutions each (any two copies of a centre are within
+    d_max): buckets whose edge lists run to a few 10^5 entries.  Rank order, freq."""
+    out = {}
+    for _ in range(n_centres):
+        c = rng.choice(ALPHA, L)
+        out.setdefault(c.tobytes(), int(rng.choice([3, 5, 9])))
+        for _ in range(copies):
+            u = c.copy()
+            for i in rng.choice(L, int(rng.integers(1, d_max // 2 + 1)), replace=False):
+                u[i] = rng.choice(ALPHA[ALPHA != c[i]])
+            out.setdefault(u.tobytes(), int(rng.choice([1, 1, 2, 3])))
+    umis, freq, _ = canonical([u.decode() for u in out], list(out.values()))
+    return umis, freq
+
+
+def equal_parts_of_pairs(seqs, pairs, P):
+    """For every pair (i, j) of one bucket of equal-length reads: the set of parts [j L / P, (j + 1) L / P)
+    on which the two reads agree exactly, as a frozenset."""
+    L = len(seqs[0])
+    arr = np.frombuffer(b"".join(seqs), np.uint8).reshape(len(seqs), L)
+    b = part_bounds(L, P)
+    out = []
+    for i, j in pairs:
+        ne = arr[i] != arr[j]
+        out.append(frozenset(p for p in range(P) if not ne[b[p]:b[p + 1]].any()))
+    return out
+
+
+def assert_tight_pigeonhole(seqs, pairs, P):
+    """A partitioned bucket holds a pair within k that agrees on the last part only and one that agrees on
+    part 0 only: the two ends of the exactly-once masks (bits 0 and P - 1)."""
+    eq = equal_parts_of_pairs(seqs, pairs, P)
+    assert frozenset([P - 1]) in eq, "no pair within k equal in part %d only" % (P - 1)
+    assert frozenset([0]) in eq, "no pair within k equal in part 0 only"

@@ -66,3 +66,18 @@ def test_cli_fastq_empty_reads_and_one_length(tmp_path):
     assert r.returncode == 0, r.stderr
     assert dst.read_bytes() == expected(seqs, quals, names, 1, 0, 1)
     assert dst.read_bytes().count(b"@e0\n\n+\n\n") == 1  # one length-0 read survives
+
+
+@pytest.mark.parametrize("k", [8, 31])
+def test_cli_fastq_large_k(tmp_path, k):
+    """-k 8 and -k 31 (reads of 256 bases are cut into 9 and 32 parts) against the model's output."""
+    seqs, quals = synth.fastq_reads(43 + k, 5000, 600, lengths=[60, 150, 256], err=0.03, n_frac=0.002)
+    names = [b"r%d" % i for i in range(len(seqs))]
+    src = tmp_path / "in.fq"
+    src.write_bytes(synth.fastq_text(seqs, quals, names))
+    dst = tmp_path / "out.fq"
+    r = run(["-m", "fastq", "-i", str(src), "-o", str(dst), "-k", str(k)])
+    assert r.returncode == 0, r.stderr
+    want = expected(seqs, quals, names, k, 0, 1)
+    assert 0 < want.count(b"\n") // 4 < len({s for s in seqs})  # something collapses, something stays
+    assert dst.read_bytes() == want

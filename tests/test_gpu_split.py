@@ -69,3 +69,23 @@ def test_split_equals_single_call_and_oracle(n_parts):
         assert e.value.code == _lib.UMI_ERR_NOMEM
     finally:
         ctx.close()
+
+
+@pytest.mark.parametrize("L,k", [(18, 5), (12, 2 ** 31 - 1)])
+def test_split_at_large_k(L, k):
+    """The split path at k = 5 (segment index on, pairs planted at exactly k and k + 1) and at k = 2^31 - 1
+    (every pair of a bucket), against the oracle."""
+    import umi_collapse_rs_amd as umi
+    from helpers import assert_k_decides, limit_census, one_word_batch
+    keys, nm, fr, off = one_word_batch(L, k, 0.01)
+    kk = min(k, L)
+    okept, oroot, _ = orc.dedup_batch(keys, nm, fr, off, L, k)
+    assert_k_decides(limit_census(keys, nm, fr, off, kk), L, k, okept, orc.dedup_batch(keys, nm, fr, off, L, kk - 1)[0])
+    ctx = umi.Context(0)
+    try:
+        for n_parts in (2, 3):
+            kept, root, counts, st = run_split(ctx, keys, nm, fr, off, L, k, 0.5, 0, 0, n_parts, cap=1 << 22)
+            assert (kept == okept).all() and (root == oroot).all()
+            assert st["n_kept"] == int(okept.sum()) and sum(counts) > 0
+    finally:
+        ctx.close()

@@ -141,3 +141,57 @@ def test_straddling_bases_quirk_of_the_reference():
     assert orc.lib().orc_bit_count_xor(ba, bb) == 5 and orc.lib().orc_umi_dist(ba, bb) == 2
     one = orc.to_bitset("A" * 21 + "N" + "A" * 22)
     assert orc.lib().orc_bit_count_xor(one, bb) == 3 and orc.lib().orc_umi_dist(one, bb) == 1
+
+
+# ---- k > 3: the reference of tests/test_gpu_large_k.py, pinned before anything is compared with it ----
+
+@pytest.mark.parametrize("n_frac", [0.0, 0.02])
+@pytest.mark.parametrize("L", [8, 12, 18, 21])
+def test_batched_oracle_matches_bruteforce_at_large_k(L, n_frac):
+    """oracle.dedup_batch against the character-level brute force at k = 4 .. 8, L-1, L, L+5 and 2^31-1,
+    both algorithms, on buckets with pairs planted at exactly k and k + 1."""
+    from helpers import planted_bucket
+    rng = np.random.default_rng(31 * L + int(100 * n_frac))
+    for k in (4, 5, 6, 7, 8, L - 1, L, L + 5, 2 ** 31 - 1):
+        buckets = [planted_bucket(rng, n, L, min(k, L), n_frac) for n in (2, 40, 90)]
+        buckets.append(canonical(*random_bucket(rng, 30, L, err=0.3, n_frac=n_frac))[:2])
+        keys = np.concatenate([orc.encode_keys(u)[0] for u, _ in buckets])
+        nm = np.concatenate([orc.encode_keys(u)[1] for u, _ in buckets])
+        fr = [f for _, fs in buckets for f in fs]
+        off = np.cumsum([0] + [len(u) for u, _ in buckets])
+        for algo, amf in ((0, 0), (1, 0), (1, 2)):
+            kept, root, _ = orc.dedup_batch(keys, nm, fr, off, L, k, 0.5, algo, amf)
+            for b, (u, f) in enumerate(buckets):
+                surv, root_of = brute_directional(u, f, k, 0.5) if algo == 0 else brute_adjacency(u, f, k, amf)
+                s = int(off[b])
+                assert np.nonzero(kept[s:s + len(u)])[0].tolist() == sorted(surv), (L, k, algo, amf, b)
+                assert (root[s:s + len(u)] - s).tolist() == root_of, (L, k, algo, amf, b)
+
+
+@pytest.mark.parametrize("L", [22, 43, 85])
+def test_wide_oracle_matches_the_word_model_at_large_k(L):
+    """oracle.dedup_batch_wide against seq_model (per-word distance, collapse from neighbour lists) at
+    k = 4, 6, 8, L and 2^31-1, with N at the straddling bases 21 and 42."""
+    import seq_model as sm
+    from helpers import planted_bucket
+    rng = np.random.default_rng(17 * L)
+    for k in (4, 6, 8, L, 2 ** 31 - 1):
+        for n in (2, 120):
+            umis, freq = planted_bucket(rng, n, L, min(k, L), 0.03, (21, 42))
+            for i in (1, n // 2):  # N at the straddlers whatever the generator drew
+                for b in (21, 42):
+                    if b < L:
+                        umis[i] = umis[i][:b] + "N" + umis[i][b + 1:]
+            if len(set(umis)) != len(umis):  # an N forced onto a copy made it equal to another: keep the first
+                first = {}
+                for u, f in zip(umis, freq):
+                    first.setdefault(u, f)
+                umis, freq, _ = canonical(list(first), list(first.values()))
+            keys, nm = orc.encode_keys_wide(umis)
+            mk, mn = sm.encode([u.encode() for u in umis], sm.words(L))
+            assert (keys == mk).all() and (nm == mn).all()
+            pairs = sm.pairs_brute(mk, mn, k)
+            for algo, amf in ((0, 0), (1, 0), (1, 2)):
+                kept, root, _ = orc.dedup_batch_wide(keys, nm, freq, [0, len(umis)], L, k, 0.5, algo, amf)
+                ek, er = sm.collapse(len(umis), pairs, freq, algo, k, 0.5, amf)
+                assert np.array_equal(kept.astype(bool), ek) and np.array_equal(root, er), (L, k, algo, amf)

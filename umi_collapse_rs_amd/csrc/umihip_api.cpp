@@ -266,6 +266,11 @@ struct umi_ctx {
 
 namespace {
 
+// No distance exceeds this: bit_count_xor is at most 64 per word, umi_dist halves it, and a batched key has at
+// most 4 words (85 bases).  Every k from here up means "all pairs", and the clamped value is what the planner and
+// the kernels see, so that their 2 k and 2 k + 1 stay far inside an int.
+constexpr int BATCH_MAX_K = 32 * 4;
+
 int check_common(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, int k,
                  int algo, uint64_t *n_out, int max_len = UMI_MAX_UMI_LEN)
 {
@@ -357,7 +362,7 @@ class Pipeline {
              float percentage, int mode, int32_t adj_max_freq, uint8_t *d_kept, uint32_t *d_root,
              hipStream_t s, uint32_t part = 0, uint32_t n_parts = 1)
         : ctx(ctx), d_keys(d_keys), d_nmask(d_nmask), d_freq(d_freq), bucket_off(bucket_off),
-          n_buckets(n_buckets), n(n), umi_len(umi_len), k(k), percentage(percentage), mode(mode),
+          n_buckets(n_buckets), n(n), umi_len(umi_len), k(std::min(k, BATCH_MAX_K)), percentage(percentage), mode(mode),
           adj_max_freq(adj_max_freq), d_kept(d_kept), d_root(d_root), s(s), pl(ctx->plan),
           key32(umi_len <= 16),
           need_pairs(!(mode == MODE_ADJACENCY && adj_max_freq < 1)), // reference adj: only the query goes
