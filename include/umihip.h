@@ -329,6 +329,39 @@ int umi_consensus_seqs(umi_ctx *ctx, const uint8_t *text, const uint64_t *seq_po
                        const int32_t *bucket_len, uint64_t n_buckets, uint8_t *cons_seq, uint8_t *cons_qual,
                        uint64_t *cons_off, uint32_t *cluster_reads, uint64_t *cons_bytes);
 
+/* ---- correction of UMIs to a fixed list (the program's --umi-whitelist): every read's UMI against every
+ *      listed one, on the GPU.  No counterpart in the reference; the two conditions are those of fgbio
+ *      CorrectUmis, and the distance is the reference's umi_dist (src/utils/bitset.rs:77-91) on the encoded keys.
+ * in : n_reads UMIs of umi_len bytes each, back to back, every byte one of ATCGN (the pointer needs no
+ *      alignment); whitelist_ascii: n_wl UMIs of the same length, every byte one of ACGT, a HOST array in
+ *      both forms.  d(u, w) = the positions whose bytes differ: an N of a read differs from every listed base.
+ *      Per read: best = the smallest d over the list, idx = the smallest index that reaches it, second =
+ *      the smallest d over every entry other than idx (umi_len + 1 with n_wl == 1; a listed UMI that
+ *      occurs twice makes second == best).  The read is matched iff best <= max_mismatches and
+ *      second - best >= min_distance; a max_mismatches of umi_len or more lets every distance pass.
+ * out: match[i] = idx where read i is matched, else -1; best[i] / second[i] (each may be NULL) for every
+ *      read, matched or not; out_ascii (may be NULL, may be the input itself): the listed UMI's bytes for
+ *      a matched read, the input bytes for any other; counts (host): reads matched at distance 0, matched
+ *      at a distance above 0, not matched.
+ * n_reads == 0: UMI_OK, counts all zero, nothing else touched.  A multi-device context uses its first
+ * device, as umi_data_new does.  A deferred call (umi_dedup_batch_device_begin) that is out on the context
+ * ends first; its result keeps waiting for umi_dedup_batch_end.
+ * UMI_ERR_ARG: n_wl == 0 or above 2^24, a NULL among ctx, the UMIs, the list, match and counts, a negative
+ * max_mismatches or min_distance, umi_len outside 1..UMI_MAX_WIDE_UMI_LEN, n_reads >= 2^30.  UMI_ERR_CHAR:
+ * a listed byte outside ACGT ("Unknown character in whitelist: <byte> (entry <index>)", found on the host
+ * before anything is launched), or a read byte outside ATCGN -- a pass of its own over the reads finds
+ * the smallest such read before anything is written, the outputs stay as they were, and umi_last_error()
+ * names it and its first bad byte: "Unknown character in UMI sequence: <byte> (read <index>)".
+ * The _device form takes and leaves the per-read arrays in device memory and synchronises the stream
+ * (twice: after the check, at the end); the plain form copies host arrays in and out around it. */
+int umi_correct_umis_device(umi_ctx *ctx, const uint8_t *d_umi_ascii, uint64_t n_reads, int umi_len,
+                            const uint8_t *whitelist_ascii, uint32_t n_wl, int max_mismatches, int min_distance,
+                            uint8_t *d_out_ascii, int32_t *d_match, uint8_t *d_best, uint8_t *d_second,
+                            uint64_t counts[3], void *hip_stream);
+int umi_correct_umis(umi_ctx *ctx, const uint8_t *umi_ascii, uint64_t n_reads, int umi_len,
+                     const uint8_t *whitelist_ascii, uint32_t n_wl, int max_mismatches, int min_distance,
+                     uint8_t *out_ascii, int32_t *match, uint8_t *best, uint8_t *second, uint64_t counts[3]);
+
 /* ---- batched path: replaces the whole bucket loop
  *      src/deduplicate_sam.rs:207-233 (apply::<UcSAMRead,Naive> per bucket,
  *      counters :217-219) = Directional/Adjacency::apply

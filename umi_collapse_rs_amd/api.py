@@ -280,6 +280,50 @@ class Context:
                                                d_cluster_reads or None, C.byref(nbytes), stream or None))
         return int(nbytes.value)
 
+    @staticmethod
+    def _whitelist_bytes(whitelist, umi_len):
+        """A list of str/bytes, or a uint8 array [n_wl * umi_len] -> (uint8 array, n_wl)."""
+        if isinstance(whitelist, np.ndarray):
+            wl = np.ascontiguousarray(whitelist, dtype=np.uint8).reshape(-1)
+        else:
+            bs = [w.encode() if isinstance(w, str) else bytes(w) for w in whitelist]
+            if any(len(b) != umi_len for b in bs):
+                raise ValueError("every listed UMI has umi_len bases")
+            wl = np.frombuffer(b"".join(bs), dtype=np.uint8)
+        if wl.size % umi_len:
+            raise ValueError("the whitelist is not a whole number of UMIs")
+        return wl, wl.size // umi_len
+
+    def correct_umis(self, umi_bytes, umi_len, whitelist, max_mismatches=1, min_distance=1):
+        """UMIs snapped to a fixed list (umi_correct_umis): umi_bytes uint8 [n * umi_len], whitelist a list of
+        str/bytes or a uint8 array.  Returns dict(out uint8 [n * umi_len], match int32 [n] (-1: not matched),
+        best, second uint8 [n], counts uint64 [3]: exact, corrected, unmatched)."""
+        umi_bytes = np.ascontiguousarray(umi_bytes, dtype=np.uint8).reshape(-1)
+        if umi_len < 1 or umi_bytes.size % umi_len:
+            raise ValueError("umi_bytes is not a whole number of UMIs")
+        n = umi_bytes.size // umi_len
+        wl, n_wl = self._whitelist_bytes(whitelist, umi_len)
+        m = max(1, n)
+        out = np.zeros(m * umi_len, np.uint8)
+        match = np.zeros(m, np.int32)
+        best, second = np.zeros(m, np.uint8), np.zeros(m, np.uint8)
+        counts = np.zeros(3, np.uint64)
+        check(load().umi_correct_umis(self._h, ptr(umi_bytes, C.c_uint8), n, umi_len, ptr(wl, C.c_uint8), n_wl,
+                                      max_mismatches, min_distance, ptr(out, C.c_uint8), ptr(match, C.c_int32),
+                                      ptr(best, C.c_uint8), ptr(second, C.c_uint8), ptr(counts, C.c_uint64)))
+        return {"out": out[:n * umi_len], "match": match[:n], "best": best[:n], "second": second[:n], "counts": counts}
+
+    def correct_umis_device(self, d_umi, n_reads, umi_len, whitelist, max_mismatches, min_distance, d_out, d_match,
+                            d_best=0, d_second=0, stream=0):
+        """The same on raw device pointers (umi_correct_umis_device; the whitelist stays on the host): fills
+        d_match and, where given, d_out (may be d_umi) / d_best / d_second; returns counts uint64 [3]."""
+        wl, n_wl = self._whitelist_bytes(whitelist, umi_len)
+        counts = np.zeros(3, np.uint64)
+        check(load().umi_correct_umis_device(self._h, d_umi or None, n_reads, umi_len, ptr(wl, C.c_uint8), n_wl,
+                                             max_mismatches, min_distance, d_out or None, d_match or None,
+                                             d_best or None, d_second or None, ptr(counts, C.c_uint64), stream or None))
+        return counts
+
     def stage_reads(self, align_key, umi_bytes, score, umi_len, merge=1, align_key_bits=64):
         """Read staging on the device (host arrays in and out): reads in file order ->
         dict(keys, nmask, freq, rep, bucket_off) in canonical order, the batched path's input

@@ -379,6 +379,22 @@ int consensus_on_device(void *workspace, const uint8_t *d_text, const uint64_t *
                         uint8_t *d_cons_qual, uint64_t *d_cons_off, uint32_t *d_cluster_reads, uint64_t *cons_bytes,
                         ConsFault *fault, unsigned long long *h_pinned, hipStream_t s);
 
+// ---- correction of UMIs to a fixed list (umihip_correct.hip: umi_correct_umis) ----
+// The list is packed on the host, 2 bits per base (A 0, C 1, G 2, T 3), correct_words(umi_len) 32-bit
+// words per entry (correct_pack_list: 1 and *bad_entry at a byte outside ACGT), and walked on the
+// device in tiles of CORR_TILE entries.  d_out, d_best, d_second may be null; d_out may be d_umi.
+// h_pinned: 4 pinned words.  0 ok; 1 a read byte outside ATCGN (*bad_read: the smallest such read;
+// nothing was written); negative: -(hipError_t)
+constexpr uint32_t CORR_TILE = 1024;          // entries of the list in LDS at a time
+constexpr uint32_t CORR_MAX_LIST = 1u << 24;  // entries of a list, at most (an index is 24 bits of a compare key)
+int correct_words(int umi_len);
+int correct_pack_list(const uint8_t *ascii, uint32_t n_wl, int umi_len, uint32_t *packed, uint64_t *bad_entry);
+size_t correct_workspace_bytes(uint32_t n_wl, int umi_len);
+int correct_on_device(void *workspace, const uint8_t *d_umi, uint32_t n_reads, int umi_len, const uint32_t *h_packed,
+                      uint32_t n_wl, int max_mismatches, int min_distance, uint8_t *d_out, int32_t *d_match, uint8_t *d_best,
+                      uint8_t *d_second, uint64_t counts[3], uint64_t *bad_read, uint32_t n_cus, unsigned long long *h_pinned,
+                      hipStream_t s);
+
 // ---- sort and scan primitives of the staging (umihip_radix.hip) ----
 constexpr int RADIX_BINS = 256, RADIX_MAX_PASSES = 8; // 8-bit digits; a 64-bit key has at most eight
 constexpr int RADIX_HIST_PARTS = 2048;                // blocks of a kernel that counts digits, at most

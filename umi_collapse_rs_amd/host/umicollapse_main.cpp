@@ -61,6 +61,16 @@
 // it as the group key of umi_stage_reads_grouped_wide.  Everything else -- merge, --paired (the first
 // mate's tags), --tag, --two-pass, --devices, --stage -- as without the flags; --dump-staging appends every
 // bucket's cell id.  A malformed aux block or a tag of another type ends the run with status 101.
+// --umi-whitelist FILE (bam/sam mode, one pass; fgbio CorrectUmis / umi_tools whitelist, not the reference's):
+// the UMIs of the reads that would be staged go through umi_correct_umis in one call, between the per-read
+// pass and the staging.  A read whose UMI matches a listed one (at most --whitelist-max-mismatches away, the
+// next best listed UMI at least --whitelist-min-distance further; both default 1) is staged with the listed
+// UMI's bytes; any other is dropped like a read without its tag, not written, and counted ("Number of reads
+// with a corrected UMI / an uncorrectable UMI", printed with the flag only).  Written records are the
+// input's bytes.  The UMI length is the list's.  --whitelist-metrics FILE: umi, reads, exact, corrected per
+// listed UMI.  Refused before the GPU is woken: fastq mode, --two-pass, --dump-staging, --passthrough, another
+// -u, the other three flags alone, a list that is empty, of mixed lengths, with a byte outside ACGT, with a
+// duplicate, or of more than 85 bases.
 // Not implemented, as in the reference: --algo cc.
 #include <algorithm>
 #include <chrono>
@@ -111,6 +121,10 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     bool consensus = false;           // --consensus (fastq mode): every cluster written as its consensus read
     uint64_t consensus_min_reads = 1; // --consensus-min-reads M: clusters of fewer members are left out
     bool consensus_min_given = false;
+    std::string umi_whitelist;     // --umi-whitelist FILE: every UMI is snapped to the nearest listed one first
+    std::string whitelist_metrics; // --whitelist-metrics FILE: reads, exact, corrected per listed UMI
+    int wl_max_mismatches = 1, wl_min_distance = 1; // --whitelist-max-mismatches, --whitelist-min-distance
+    bool wl_max_given = false, wl_min_given = false;
 };
 
 [[noreturn]] void die(const std::string &msg)
@@ -159,6 +173,10 @@ struct HipLib {
                                  const uint32_t *, const int32_t *, const uint8_t *, const uint32_t *, uint64_t,
                                  const uint64_t *, const int32_t *, uint64_t, uint8_t *, uint8_t *, uint64_t *, uint32_t *,
                                  uint64_t *, void *) = nullptr;
+    // --umi-whitelist: resolved only when the flag is given, like --consensus
+    bool want_correct = false;
+    int (*correct_umis)(umi_ctx *, const uint8_t *, uint64_t, int, const uint8_t *, uint32_t, int, int, uint8_t *, int32_t *,
+                        uint8_t *, uint8_t *, uint64_t *) = nullptr;
     // (the HIP runtime the library brings along: device buffers for the arrays above)
     int (*hip_set_device)(int) = nullptr; // (the current device is per thread: the context was made on another)
     int (*hip_malloc)(void **, size_t) = nullptr;
@@ -197,6 +215,7 @@ struct HipLib {
             consensus_seqs = (decltype(consensus_seqs))sym("umi_consensus_seqs");
             consensus_seqs_device = (decltype(consensus_seqs_device))sym("umi_consensus_seqs_device");
         }
+        if (want_correct) correct_umis = (decltype(correct_umis))sym("umi_correct_umis");
         hip_set_device = (decltype(hip_set_device))sym("hipSetDevice");
         hip_malloc = (decltype(hip_malloc))sym("hipMalloc");
         hip_memcpy = (decltype(hip_memcpy))sym("hipMemcpy");
@@ -283,6 +302,13 @@ void usage()
               "      --per-cell           deduplicate per cell: positions are (alignment, cell barcode); reads\n"
               "                           without a barcode are dropped (bam/sam mode)\n"
               "      --cell-tag <XX>      aux tag of the cell barcode, type Z [default: CB]\n"
+              "      --umi-whitelist <FILE> the kit's UMIs, one per line (ACGT, all of one length; blank lines and\n"
+              "                           lines starting with # skipped): every read's UMI is replaced, on the GPU, by\n"
+              "                           the nearest listed one before the reads are grouped; reads that match none\n"
+              "                           are dropped; written records keep their own bytes (bam/sam mode, one pass)\n"
+              "      --whitelist-max-mismatches <M> a UMI matches a listed one at up to M mismatches [default: 1]\n"
+              "      --whitelist-min-distance <D> ... if the next best listed UMI is at least D further away [default: 1]\n"
+              "      --whitelist-metrics <FILE> write a table: umi, reads, exact, corrected per listed UMI, in list order\n"
               "      --device <ID>        GPU to use [default: 0]\n"
               "      --devices <ID,..>    several GPUs of the node: alignment positions are sharded over them");
 }
@@ -341,6 +367,16 @@ Cli parse(int argc, char **argv)
             else { c.cell_tag = t; c.cell_tag_given = true; }
         }
         else if (a == "--per-cell") c.per_cell = true;
+        else if (a == "--umi-whitelist") c.umi_whitelist = need(i);
+        else if (a == "--whitelist-metrics") c.whitelist_metrics = need(i);
+        else if (a == "--whitelist-max-mismatches" || a == "--whitelist-min-distance") {
+            const char *v = need(i);
+            char *end = nullptr;
+            const long long m = std::strtoll(v, &end, 10);
+            if (end == v || *end != '\0' || m < 0 || m > INT32_MAX) die(a + " wants a number, 0 or more");
+            if (a == "--whitelist-max-mismatches") { c.wl_max_mismatches = (int)m; c.wl_max_given = true; }
+            else { c.wl_min_distance = (int)m; c.wl_min_given = true; }
+        }
         else if (a == "--consensus") c.consensus = true;
         else if (a == "--consensus-min-reads") {
             const char *v = need(i);
@@ -530,6 +566,44 @@ std::string umi_offset(const Cli &args, const umi::bam::Record &r, const ReadTag
 size_t detect_length(const Cli &args, const umi::bam::Record &r, const ReadTags &t)
 {
     return args.umi_tag.empty() ? detect_umi_length(r.qname(), r.qname_len(), args.umi_sep) : t.umi_len;
+}
+
+// --umi-whitelist: the listed UMIs back to back; their length in umi_len.  One UMI per line, blank lines and
+// lines that start with # skipped; anything a kit's list cannot be ends the run.
+std::vector<uint8_t> read_whitelist(const std::string &path, size_t &umi_len)
+{
+    FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) die("cannot open the UMI whitelist " + path);
+    std::string text;
+    char buf[1 << 16];
+    for (size_t got; (got = std::fread(buf, 1, sizeof(buf), f)) > 0;) text.append(buf, got);
+    std::fclose(f);
+    std::vector<uint8_t> list;
+    std::unordered_set<std::string> seen;
+    umi_len = 0;
+    size_t line_no = 0;
+    for (size_t p = 0; p < text.size();) {
+        size_t q = text.find('\n', p);
+        if (q == std::string::npos) q = text.size();
+        std::string line = text.substr(p, q - p);
+        p = q + 1;
+        line_no++;
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        const std::string where = "UMI whitelist " + path + ", line " + std::to_string(line_no) + ": ";
+        if (line.size() > UMI_MAX_WIDE_UMI_LEN)
+            die(where + std::to_string(line.size()) + " bases, more than " + std::to_string(UMI_MAX_WIDE_UMI_LEN));
+        for (char ch : line)
+            if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T')
+                die(where + "a character outside ACGT: " + std::to_string((unsigned)(uint8_t)ch));
+        if (umi_len && line.size() != umi_len)
+            die(where + std::to_string(line.size()) + " bases, the UMIs before it have " + std::to_string(umi_len));
+        if (!seen.insert(line).second) die(where + "duplicate entry " + line);
+        umi_len = line.size();
+        list.insert(list.end(), line.begin(), line.end());
+    }
+    if (list.empty()) die("the UMI whitelist " + path + " holds no UMI");
+    return list;
 }
 
 int bits_of(uint64_t v)
@@ -1544,7 +1618,22 @@ int main(int argc, char **argv)
     if (args.paired && args.keep_unmapped) die("Cannot keep unmapped reads with paired-end reads!");
     if (args.consensus_min_given && !args.consensus) die("--consensus-min-reads goes with --consensus only");
     if (args.consensus && args.mode != "fastq") die("--consensus is defined in fastq mode only (-m fastq)");
+    if (args.umi_whitelist.empty() && (args.wl_max_given || args.wl_min_given || !args.whitelist_metrics.empty()))
+        die("--whitelist-max-mismatches, --whitelist-min-distance and --whitelist-metrics go with --umi-whitelist only");
     if (args.mode != "bam" && args.mode != "sam" && args.mode != "fastq") return 0; // main.rs:49-95: nothing happens
+    // --umi-whitelist: everything about it that can be refused is, before the GPU is woken
+    std::vector<uint8_t> whitelist;
+    if (!args.umi_whitelist.empty()) {
+        if (args.mode == "fastq") die("--umi-whitelist does not go with fastq mode (whole reads are the key there)");
+        if (args.two_pass) die("--umi-whitelist does not go with --two-pass (its census would need the correction too)");
+        if (!args.dump_staging.empty() || args.passthrough) die("--umi-whitelist does not go with --dump-staging or --passthrough");
+        size_t wl_len = 0;
+        whitelist = read_whitelist(args.umi_whitelist, wl_len);
+        if (args.umi_length != 0 && args.umi_length != wl_len)
+            die("-u " + std::to_string(args.umi_length) + " does not go with a whitelist of UMIs of " + std::to_string(wl_len) +
+                " bases");
+        args.umi_length = wl_len; // (a read whose UMI is of another length ends the run, as with -u)
+    }
     if (args.track_clusters && args.paired) die("--tag with --paired is not implemented (the reference never reaches its tagging pass)");
     int algo, merge;
     if (args.algo == "dir") algo = UMI_ALGO_DIRECTIONAL;
@@ -1568,6 +1657,7 @@ int main(int argc, char **argv)
     // half a second, none of it on the device.  A tiny staging call and a tiny batch go through;
     // whoever needs the context first waits for this thread.
     HipLib lib;
+    lib.want_correct = !whitelist.empty();
     std::future<umi_ctx *> warm;
     std::string warm_error;
     if (!args.passthrough && args.dump_staging.empty())
@@ -1677,11 +1767,13 @@ int main(int argc, char **argv)
             uint8_t state; // 0 staged, 1 unmapped, 2 error, 3 second mate (not counted),
                            // 4 mate unmapped, 5 filtered (--remove-unpaired / --remove-chimeric),
                            // 6 dropped: it lacks a tag of --umi-tag / --per-cell (`missing` says which)
+                           // 7 dropped: its UMI matches no listed one (--umi-whitelist)
             uint8_t unpaired, chimeric, missing;
             uint32_t umi_at; // offset of the UMI from the read name (a --umi-tag value lies behind it)
             uint32_t cell;   // --per-cell: the barcode's id, the thread's own during the per-read pass
         };
         std::vector<ReadInfo> info(n_rec);
+        umi::bgzf::Bytes wl_umis;      // --umi-whitelist: per record, the listed UMI a staged read was snapped to
         std::vector<UmiKey> rkey, rnm; // per read: its UMI key and N mask (host staging only: the device encodes its own)
         auto encode_all = [&]() {       // utils/mod.rs:63-83 for every staged read; the first bad character ends the run
             rkey.resize(n_rec);
@@ -1691,7 +1783,8 @@ int main(int argc, char **argv)
             umi::bgzf::parallel_for(T, T, [&](size_t t) {
                 for (uint32_t ri = (uint32_t)t * per; ri < std::min(n_rec, ((uint32_t)t + 1) * per); ri++)
                     if (info[ri].state == 0 && !args.passthrough &&
-                        !encode_umi(in.records[ri].qname() + info[ri].umi_at, umi_length, &rkey[ri], &rnm[ri]) &&
+                        !encode_umi(wl_umis.empty() ? in.records[ri].qname() + info[ri].umi_at : &wl_umis[(size_t)ri * umi_length],
+                                    umi_length, &rkey[ri], &rnm[ri]) &&
                         bad[t] == UINT32_MAX)
                         bad[t] = ri;
             });
@@ -1800,6 +1893,73 @@ int main(int argc, char **argv)
                     }
             });
         }
+        umi_ctx *ctx = nullptr;
+        double t_init = 0.0;
+        auto need_ctx = [&]() { // (t_init: what of the GPU's start-up was left to wait for)
+            if (ctx) return;
+            const double t0 = now_s();
+            if (warm.valid()) {
+                ctx = warm.get();
+                if (!ctx) die(warm_error);
+            } else {
+                if (!lib.load()) die(lib.error);
+                if (lib.ctx_create_multi(args.devices.data(), (int)args.devices.size(), &ctx) != UMI_OK) die(lib.last_error());
+            }
+            t_init += now_s() - t0;
+        };
+        // --umi-whitelist: the UMIs of the reads that would be staged, snapped to the list in one call; a read
+        // that matches no listed UMI is dropped like one without its tag, the others go on with the listed
+        // UMI's bytes in place of their own (either staging below sees only those)
+        uint64_t wl_counts[3] = {0, 0, 0};
+        std::vector<int32_t> wl_match;    // per staged read, in file order
+        if (!whitelist.empty()) {
+            std::vector<uint32_t> cand;
+            for (uint32_t ri = 0; ri < n_rec; ri++)
+                if (info[ri].state == 0) cand.push_back(ri);
+            const size_t nc = cand.size(), L = umi_length;
+            umi::bgzf::Bytes raw_umis(nc * L), fixed(nc * L);
+            const size_t per = (nc + T - 1) / T;
+            umi::bgzf::parallel_for(T, T, [&](size_t t) {
+                for (size_t j = t * per; j < std::min(nc, (t + 1) * per); j++)
+                    std::memcpy(&raw_umis[j * L], in.records[cand[j]].qname() + info[cand[j]].umi_at, L);
+            });
+            wl_match.resize(nc);
+            std::vector<uint8_t> wl_best(args.whitelist_metrics.empty() ? 0 : nc);
+            if (nc) {
+                need_ctx();
+                if (lib.correct_umis(ctx, raw_umis.data(), nc, (int)L, whitelist.data(), (uint32_t)(whitelist.size() / L),
+                                     args.wl_max_mismatches, args.wl_min_distance, fixed.data(), wl_match.data(),
+                                     wl_best.empty() ? nullptr : wl_best.data(), nullptr, wl_counts) != UMI_OK)
+                    die(lib.last_error());
+                wl_umis.resize((size_t)n_rec * L);
+                umi::bgzf::parallel_for(T, T, [&](size_t t) {
+                    for (size_t j = t * per; j < std::min(nc, (t + 1) * per); j++) {
+                        const uint32_t ri = cand[j];
+                        if (wl_match[j] < 0) {
+                            info[ri].state = 7;
+                            continue;
+                        }
+                        std::memcpy(&wl_umis[(size_t)ri * L], &fixed[j * L], L);
+                        if (gpu_stage) std::memcpy(&umis[(size_t)ri * L], &fixed[j * L], L);
+                    }
+                });
+            }
+            if (!args.whitelist_metrics.empty()) { // per listed UMI, in list order: the reads it took, exact and corrected
+                const size_t n_wl = whitelist.size() / L;
+                std::vector<uint64_t> exact(n_wl, 0), corrected(n_wl, 0);
+                for (size_t j = 0; j < nc; j++)
+                    if (wl_match[j] >= 0) (wl_best[j] == 0 ? exact : corrected)[(size_t)wl_match[j]]++;
+                FILE *f = std::fopen(args.whitelist_metrics.c_str(), "wb");
+                if (!f) die("cannot open " + args.whitelist_metrics);
+                std::fprintf(f, "umi\treads\texact\tcorrected\n");
+                for (size_t w = 0; w < n_wl; w++)
+                    std::fprintf(f, "%.*s\t%llu\t%llu\t%llu\n", (int)L, (const char *)&whitelist[w * L],
+                                 (unsigned long long)(exact[w] + corrected[w]), (unsigned long long)exact[w],
+                                 (unsigned long long)corrected[w]);
+                if (std::fclose(f) != 0) die("cannot write " + args.whitelist_metrics);
+            }
+            lap("whitelist");
+        }
         lap("per-read");
         if (!gpu_stage && !args.passthrough) encode_all();
 
@@ -1836,20 +1996,6 @@ int main(int argc, char **argv)
         std::vector<std::vector<uint32_t>> global_of;
         std::vector<uint32_t> entry_of;
         KeyHash hasher;
-        umi_ctx *ctx = nullptr;
-        double t_init = 0.0;
-        auto need_ctx = [&]() { // (t_init: what of the GPU's start-up was left to wait for)
-            if (ctx) return;
-            const double t0 = now_s();
-            if (warm.valid()) {
-                ctx = warm.get();
-                if (!ctx) die(warm_error);
-            } else {
-                if (!lib.load()) die(lib.error);
-                if (lib.ctx_create_multi(args.devices.data(), (int)args.devices.size(), &ctx) != UMI_OK) die(lib.last_error());
-            }
-            t_init += now_s() - t0;
-        };
         if (gpu_stage) {
             // the staged reads closed up (nothing moves while every read so far is staged)
             std::vector<uint32_t> staged; // staged[j] = record of the j-th staged read, once a read has been left out
@@ -2183,6 +2329,10 @@ int main(int argc, char **argv)
         }
         if (!args.umi_tag.empty()) std::fprintf(stderr, "Number of reads without a UMI tag: %zu\n", no_umi_tag);
         if (args.per_cell) std::fprintf(stderr, "Number of reads without a cell barcode: %zu\n", no_cell);
+        if (!whitelist.empty()) {
+            std::fprintf(stderr, "Number of reads with a corrected UMI: %llu\n", (unsigned long long)wl_counts[1]);
+            std::fprintf(stderr, "Number of reads with an uncorrectable UMI: %llu\n", (unsigned long long)wl_counts[2]);
+        }
         std::fprintf(stderr, "Number of unique alignment positions: %zu\n", n_positions);
         if (args.per_cell) std::fprintf(stderr, "Number of (position, cell) groups: %zu\n", nb);
         std::fprintf(stderr, "Number of UMIs: %zu\n", n);
