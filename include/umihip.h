@@ -130,7 +130,7 @@ const char *umi_last_error(void);
  *   "table_pieces"   1..64 (default 1): a bucket table of more than 4096 positions is walked, uploaded
  *                    and handed to the fused kernel in this many pieces
  *   "split_min"      multi-device contexts, see umi_ctx_create_multi
- *   "cons_split"     2..2^30 (default 512): umi_consensus_seqs sums a cluster of at least this many reads in
+ *   "cons_split"     2..2^30 (default 512): umi_consensus_seqs / umi_consensus_bam sum a cluster of at least this many reads in
  *                    pieces over the whole grid instead of by one wave (raised by itself where the deep
  *                    clusters' accumulators, 12 KB each, would pass 512 MB)
  * The round-1 tile kernels (bit-sliced masks, key-sorted scan + item walk, range pruning, hook/jump
@@ -328,6 +328,48 @@ int umi_consensus_seqs(umi_ctx *ctx, const uint8_t *text, const uint64_t *seq_po
                        const uint8_t *kept, const uint32_t *root, uint64_t n_entries, const uint64_t *bucket_off,
                        const int32_t *bucket_len, uint64_t n_buckets, uint8_t *cons_seq, uint8_t *cons_qual,
                        uint64_t *cons_off, uint32_t *cluster_reads, uint64_t *cons_bytes);
+
+/* ---- consensus of the clusters of aligned reads (BAM mode's --call-consensus): one sequence and quality
+ *      string per cluster, voted column by column over BAM's own encodings.  No counterpart in the reference;
+ *      the caller says which reads vote where (the program: the reads of a cluster whose length and CIGAR
+ *      are the representative's, host/umicollapse_main.cpp).
+ * in : read i is len[i] bases, packed two per byte, high nibble first, at data + seq_pos[i]; its qualities,
+ *      raw Phred bytes, at data + qual_pos[i].  No offset needs any alignment: one buffer may be the whole
+ *      inflated BAM.  cluster[i] in [0, n_clusters) makes read i a voter of that cluster, UMI_NO_CLUSTER
+ *      leaves it out (nothing of such a read is looked at).  cluster_len[c] <= UMI_MAX_CONS_LEN: the length
+ *      of cluster c, and of every voter of it.
+ *      Column c: nibble 1, 2, 4, 8 votes for A, C, G, T, every other nibble (=, N, the ambiguity codes) for
+ *      nothing, with weight w = min(quality byte, 93).  S_b = sum of w over the voters that show b, n_b =
+ *      their number.  Called: the b with the greatest (S_b, n_b), S first; the first of A, C, G, T on a tie;
+ *      quality min(93, max(0, S_win - (sum of the other three S))).  A column nobody voted on is nibble 15
+ *      with quality 0.  The unused low nibble of the last byte of an odd length is 0.  The sums are 64-bit.
+ * out: cons_seq (capacity: the sum of ceil(cluster_len / 2)) / cons_qual (the sum of cluster_len): the
+ *      clusters' consensus back to back in ascending order, *seq_bytes / *qual_bytes of them, nothing
+ *      written behind; seq_off[c] / qual_off[c]: where cluster c's begins; depth[c]: its voters;
+ *      disagree[c] (may be NULL): the sum over its columns of (sum of n_b) - n_win, the base votes that
+ *      lost.  A cluster without a voter is all nibble 15 with quality 0 and depth 0.
+ * UMI_ERR_ARG: a multi-device context, n_reads or n_clusters >= 2^30, a NULL among the required pointers.
+ * UMI_ERR_ORDER, found on the device before anything is written (nothing is read out of bounds): a
+ * cluster_len above UMI_MAX_CONS_LEN, a cluster id that is neither in range nor UMI_NO_CLUSTER, a voter
+ * whose len differs from its cluster's.  A deferred call (umi_dedup_batch_device_begin) that is out on the
+ * context ends first; its result keeps waiting for umi_dedup_batch_end.  "cons_split" applies as to
+ * umi_consensus_seqs (an accumulator slot is 48 KB here; a cluster of 2^24 voters or more always takes
+ * that path).
+ * The _device form takes and leaves every array in device memory and synchronises the stream (twice:
+ * after the checks, at the end); the plain form copies host arrays in and out around it. */
+#define UMI_MAX_CONS_LEN 1024
+#define UMI_NO_CLUSTER 0xFFFFFFFFu
+int umi_consensus_bam_device(umi_ctx *ctx, const uint8_t *d_data, const uint64_t *d_seq_pos,
+                             const uint64_t *d_qual_pos, const uint32_t *d_len, const uint32_t *d_cluster,
+                             uint64_t n_reads, const uint32_t *d_cluster_len, uint64_t n_clusters,
+                             uint8_t *d_cons_seq, uint8_t *d_cons_qual, uint64_t *d_seq_off, uint64_t *d_qual_off,
+                             uint32_t *d_depth, uint32_t *d_disagree, uint64_t *seq_bytes, uint64_t *qual_bytes,
+                             void *hip_stream);
+int umi_consensus_bam(umi_ctx *ctx, const uint8_t *data, const uint64_t *seq_pos, const uint64_t *qual_pos,
+                      const uint32_t *len, const uint32_t *cluster, uint64_t n_reads, const uint32_t *cluster_len,
+                      uint64_t n_clusters, uint8_t *cons_seq, uint8_t *cons_qual, uint64_t *seq_off,
+                      uint64_t *qual_off, uint32_t *depth, uint32_t *disagree, uint64_t *seq_bytes,
+                      uint64_t *qual_bytes);
 
 /* ---- correction of UMIs to a fixed list (the program's --umi-whitelist): every read's UMI against every
  *      listed one, on the GPU.  No counterpart in the reference; the two conditions are those of fgbio

@@ -12,6 +12,8 @@ UMI_ERR_ARG, UMI_ERR_HIP, UMI_ERR_ORDER, UMI_ERR_NOMEM, UMI_ERR_NODEV, UMI_ERR_C
     -1, -2, -3, -4, -5, -6)
 UMI_ALGO_DIRECTIONAL, UMI_ALGO_ADJACENCY = 0, 1
 UMI_MAX_UMI_LEN = 21
+UMI_MAX_CONS_LEN = 1024       # umi_consensus_bam: bases of a cluster, at most
+UMI_NO_CLUSTER = 0xFFFFFFFF   # ... a read that votes nowhere
 
 
 class UmiHipError(RuntimeError):
@@ -92,6 +94,11 @@ SIGNATURES = {
                                             C.c_void_p]),
     "umi_consensus_seqs": (C.c_int, [C.c_void_p, _u8p, _u64p, _u64p, _u32p, C.c_uint64, _u32p, _i32p, _u8p, _u32p,
                                      C.c_uint64, _u64p, _i32p, C.c_uint64, _u8p, _u8p, _u64p, _u32p, _u64p]),
+    "umi_consensus_bam_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, _u64p, _u64p, C.c_void_p]),
+    "umi_consensus_bam": (C.c_int, [C.c_void_p, _u8p, _u64p, _u64p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint64, _u8p,
+                                    _u8p, _u64p, _u64p, _u32p, _u32p, _u64p, _u64p]),
     "umi_correct_umis_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, _u8p, C.c_uint32, C.c_int, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_void_p]),
     "umi_correct_umis": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, C.c_int, _u8p, C.c_uint32, C.c_int, C.c_int, _u8p,

@@ -280,6 +280,49 @@ class Context:
                                                d_cluster_reads or None, C.byref(nbytes), stream or None))
         return int(nbytes.value)
 
+    def consensus_bam(self, data, seq_pos, qual_pos, lens, cluster, cluster_len, want_disagree=True):
+        """One consensus per cluster of aligned reads (umi_consensus_bam): read i is lens[i] bases packed two per
+        byte at data[seq_pos[i]:], its Phred bytes at data[qual_pos[i]:]; cluster[i] is its cluster or
+        UMI_NO_CLUSTER; cluster_len the clusters' lengths.  Returns (cons_seqs, cons_quals, depth, disagree):
+        lists of bytes (packed sequence, qualities) and uint32 arrays over the clusters (disagree None if not
+        wanted)."""
+        buf = np.frombuffer(bytes(data) or b"\0", dtype=np.uint8)
+        seq_pos = np.ascontiguousarray(seq_pos, dtype=np.uint64)
+        qual_pos = np.ascontiguousarray(qual_pos, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        cluster = np.ascontiguousarray(cluster, dtype=np.uint32)
+        clen = np.ascontiguousarray(cluster_len, dtype=np.uint32)
+        n, nc = len(lens), len(clen)
+        if len(seq_pos) != n or len(qual_pos) != n or len(cluster) != n:
+            raise ValueError("seq_pos / qual_pos / lens / cluster lengths differ")
+        fit = np.minimum(clen, _lib.UMI_MAX_CONS_LEN).astype(np.uint64)
+        cons_seq = np.zeros(max(1, int(((fit + 1) // 2).sum())), np.uint8)
+        cons_qual = np.zeros(max(1, int(fit.sum())), np.uint8)
+        seq_off, qual_off = np.zeros(max(1, nc), np.uint64), np.zeros(max(1, nc), np.uint64)
+        depth = np.zeros(max(1, nc), np.uint32)
+        disagree = np.zeros(max(1, nc), np.uint32) if want_disagree else None
+        sb, qb = C.c_uint64(0), C.c_uint64(0)
+        check(load().umi_consensus_bam(self._h, ptr(buf, C.c_uint8), ptr(seq_pos, C.c_uint64), ptr(qual_pos, C.c_uint64),
+                                       ptr(lens, C.c_uint32), ptr(cluster, C.c_uint32), n, ptr(clen, C.c_uint32), nc,
+                                       ptr(cons_seq, C.c_uint8), ptr(cons_qual, C.c_uint8), ptr(seq_off, C.c_uint64),
+                                       ptr(qual_off, C.c_uint64), ptr(depth, C.c_uint32), ptr(disagree, C.c_uint32),
+                                       C.byref(sb), C.byref(qb)))
+        s, q = cons_seq.tobytes(), cons_qual.tobytes()
+        out_s = [s[int(seq_off[c]):int(seq_off[c]) + (int(clen[c]) + 1) // 2] for c in range(nc)]
+        out_q = [q[int(qual_off[c]):int(qual_off[c]) + int(clen[c])] for c in range(nc)]
+        return out_s, out_q, depth[:nc], (disagree[:nc] if want_disagree else None)
+
+    def consensus_bam_device(self, d_data, d_seq_pos, d_qual_pos, d_len, d_cluster, n_reads, d_cluster_len, n_clusters,
+                             d_cons_seq, d_cons_qual, d_seq_off, d_qual_off, d_depth, d_disagree=0, stream=0):
+        """The same on raw device pointers (umi_consensus_bam_device): fills d_cons_seq / d_cons_qual / d_seq_off /
+        d_qual_off / d_depth / d_disagree and returns (sequence bytes, quality bytes) written."""
+        sb, qb = C.c_uint64(0), C.c_uint64(0)
+        check(load().umi_consensus_bam_device(self._h, d_data or None, d_seq_pos or None, d_qual_pos or None, d_len or None,
+                                              d_cluster or None, n_reads, d_cluster_len or None, n_clusters,
+                                              d_cons_seq or None, d_cons_qual or None, d_seq_off or None, d_qual_off or None,
+                                              d_depth or None, d_disagree or None, C.byref(sb), C.byref(qb), stream or None))
+        return int(sb.value), int(qb.value)
+
     @staticmethod
     def _whitelist_bytes(whitelist, umi_len):
         """A list of str/bytes, or a uint8 array [n_wl * umi_len] -> (uint8 array, n_wl)."""

@@ -237,6 +237,8 @@ struct umi_ctx {
     DevBuf seq_groups, seq_ka, seq_kb, seq_va, seq_vb, seq_flag, seq_runid, seq_rs, seq_tend, seq_tmp;
     // consensus of their clusters (umi_consensus_seqs*): workspace; the host-buffer form's outputs
     DevBuf cons_ws, cons_seq, cons_qual, cons_off, cons_cr;
+    // ... of aligned reads (umi_consensus_bam): the host-buffer form's inputs and its other outputs
+    DevBuf cb_cluster, cb_clen, cb_qoff, cb_disagree;
     // correction of UMIs to a fixed list (umi_correct_umis*): workspace; the host-buffer form's arrays
     DevBuf corr_ws, corr_umi, corr_out, corr_match, corr_best, corr_second;
     uint32_t cons_split = 512; // clusters of at least this many reads are summed in pieces by the whole grid
@@ -3117,6 +3119,128 @@ int umi_consensus_seqs(umi_ctx *ctx, const uint8_t *text, const uint64_t *seq_po
             cons_off[e] = off_all[e];
             if (cluster_reads) cluster_reads[e] = cr_all[e];
         }
+    return UMI_OK;
+}
+
+} // extern "C"
+
+// ---- consensus of the clusters of aligned reads ---------------------------------------------------
+namespace {
+int cons_bam_check(umi_ctx *ctx, uint64_t n_reads, uint64_t n_clusters, const uint64_t *seq_bytes, const uint64_t *qual_bytes)
+{
+    if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
+    if (ctx->subs.size() > 1) return fail(UMI_ERR_ARG, "umi_consensus_bam takes a single-device context");
+    if (n_reads >= (1ull << 30))
+        return fail(UMI_ERR_ARG, "%llu reads exceed the 30-bit index space of one call", (unsigned long long)n_reads);
+    if (n_clusters >= (1ull << 30))
+        return fail(UMI_ERR_ARG, "%llu clusters exceed the 30-bit index space of one call", (unsigned long long)n_clusters);
+    if (!seq_bytes || !qual_bytes) return fail(UMI_ERR_ARG, "seq_bytes / qual_bytes is NULL");
+    return UMI_OK;
+}
+} // namespace
+
+extern "C" {
+
+int umi_consensus_bam_device(umi_ctx *ctx, const uint8_t *d_data, const uint64_t *d_seq_pos, const uint64_t *d_qual_pos,
+                             const uint32_t *d_len, const uint32_t *d_cluster, uint64_t n_reads,
+                             const uint32_t *d_cluster_len, uint64_t n_clusters, uint8_t *d_cons_seq, uint8_t *d_cons_qual,
+                             uint64_t *d_seq_off, uint64_t *d_qual_off, uint32_t *d_depth, uint32_t *d_disagree,
+                             uint64_t *seq_bytes, uint64_t *qual_bytes, void *hip_stream)
+{
+    int rc = cons_bam_check(ctx, n_reads, n_clusters, seq_bytes, qual_bytes);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    if (n_reads && (!d_data || !d_seq_pos || !d_qual_pos || !d_len || !d_cluster))
+        return fail(UMI_ERR_ARG, "a required device pointer is NULL");
+    if (n_clusters && (!d_cluster_len || !d_cons_seq || !d_cons_qual || !d_seq_off || !d_qual_off || !d_depth))
+        return fail(UMI_ERR_ARG, "a required device pointer is NULL");
+    *seq_bytes = *qual_bytes = 0;
+    if (n_reads == 0 && n_clusters == 0) return UMI_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
+    if ((rc = ctx->cons_ws.reserve(consensus_bam_workspace_bytes((uint32_t)n_reads, (uint32_t)n_clusters, ctx->cons_split))))
+        return rc;
+    ConsBamFault f;
+    uint64_t sb = 0, qb = 0;
+    const int r = consensus_bam_on_device(ctx->cons_ws.p, d_data, d_seq_pos, d_qual_pos, d_len, d_cluster, (uint32_t)n_reads,
+                                          d_cluster_len, (uint32_t)n_clusters, ctx->cons_split, (uint32_t)ctx->n_cus, d_cons_seq,
+                                          d_cons_qual, d_seq_off, d_qual_off, d_depth, d_disagree, &sb, &qb, &f,
+                                          ctx->h_counters, (hipStream_t)hip_stream);
+    if (r == 1) {
+        if (f.bad_cluster_len)
+            return fail(UMI_ERR_ORDER, "%llu clusters break the input contract (cluster_len above %d)", f.bad_cluster_len,
+                        UMI_MAX_CONS_LEN);
+        if (f.bad_id)
+            return fail(UMI_ERR_ORDER, "%llu reads break the input contract (cluster outside the %llu clusters)", f.bad_id,
+                        (unsigned long long)n_clusters);
+        return fail(UMI_ERR_ORDER, "%llu voters break the input contract (not as long as their cluster)", f.bad_len);
+    }
+    if (r < 0) return fail(UMI_ERR_HIP, "consensus: %s", hipGetErrorString((hipError_t)(-r)));
+    *seq_bytes = sb;
+    *qual_bytes = qb;
+    return UMI_OK;
+}
+
+int umi_consensus_bam(umi_ctx *ctx, const uint8_t *data, const uint64_t *seq_pos, const uint64_t *qual_pos, const uint32_t *len,
+                      const uint32_t *cluster, uint64_t n_reads, const uint32_t *cluster_len, uint64_t n_clusters,
+                      uint8_t *cons_seq, uint8_t *cons_qual, uint64_t *seq_off, uint64_t *qual_off, uint32_t *depth,
+                      uint32_t *disagree, uint64_t *seq_bytes, uint64_t *qual_bytes)
+{
+    int rc = cons_bam_check(ctx, n_reads, n_clusters, seq_bytes, qual_bytes);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    if (n_reads && (!data || !seq_pos || !qual_pos || !len || !cluster)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (n_clusters && (!cluster_len || !cons_seq || !cons_qual || !seq_off || !qual_off || !depth))
+        return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    *seq_bytes = *qual_bytes = 0;
+    if (n_reads == 0 && n_clusters == 0) return UMI_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx);
+    // what of the data is looked at: the voters' bytes (a voter of a length the device refuses adds nothing);
+    // what the consensus may fill (likewise for a cluster that is too long)
+    size_t data_bytes = 1, cap_s = 0, cap_q = 0;
+    for (uint64_t i = 0; i < n_reads; i++)
+        if (cluster[i] != UMI_NO_CLUSTER && len[i] <= UMI_MAX_CONS_LEN)
+            data_bytes = std::max<size_t>(data_bytes, std::max(seq_pos[i] + (len[i] + 1) / 2, qual_pos[i] + len[i]));
+    for (uint64_t c = 0; c < n_clusters; c++) {
+        const size_t L = std::min<uint32_t>(cluster_len[c], UMI_MAX_CONS_LEN);
+        cap_s += (L + 1) / 2;
+        cap_q += L;
+    }
+    const size_t n = std::max<size_t>((size_t)n_reads, 1), nc = std::max<size_t>((size_t)n_clusters, 1);
+    if ((rc = ctx->sq_text.reserve(data_bytes)) || (rc = ctx->sq_pos.reserve(n * 16)) || (rc = ctx->sq_len.reserve(n * 4)) ||
+        (rc = ctx->cb_cluster.reserve(n * 4)) || (rc = ctx->cb_clen.reserve(nc * 4)) || (rc = ctx->cons_seq.reserve(cap_s + 8)) ||
+        (rc = ctx->cons_qual.reserve(cap_q + 8)) || (rc = ctx->cons_off.reserve(nc * 8)) || (rc = ctx->cb_qoff.reserve(nc * 8)) ||
+        (rc = ctx->cons_cr.reserve(nc * 4)) || (rc = ctx->cb_disagree.reserve(nc * 4)))
+        return rc;
+    hipStream_t s = ctx->own_stream;
+    uint64_t *d_pos = ctx->sq_pos.as<uint64_t>(); // (seq_pos, then qual_pos)
+    if (n_reads) {
+        HIP_TRY(hipMemcpyAsync(ctx->sq_text.p, data, data_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_pos, seq_pos, n_reads * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_pos + n, qual_pos, n_reads * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(ctx->sq_len.p, len, n_reads * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(ctx->cb_cluster.p, cluster, n_reads * 4, hipMemcpyHostToDevice, s));
+    }
+    if (n_clusters) HIP_TRY(hipMemcpyAsync(ctx->cb_clen.p, cluster_len, n_clusters * 4, hipMemcpyHostToDevice, s));
+    rc = umi_consensus_bam_device(ctx, ctx->sq_text.as<uint8_t>(), d_pos, d_pos + n, ctx->sq_len.as<uint32_t>(),
+                                  ctx->cb_cluster.as<uint32_t>(), n_reads, ctx->cb_clen.as<uint32_t>(), n_clusters,
+                                  ctx->cons_seq.as<uint8_t>(), ctx->cons_qual.as<uint8_t>(), ctx->cons_off.as<uint64_t>(),
+                                  ctx->cb_qoff.as<uint64_t>(), ctx->cons_cr.as<uint32_t>(),
+                                  disagree ? ctx->cb_disagree.as<uint32_t>() : nullptr, seq_bytes, qual_bytes, s);
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    if (*seq_bytes) HIP_TRY(hipMemcpyAsync(cons_seq, ctx->cons_seq.p, (size_t)*seq_bytes, hipMemcpyDeviceToHost, s));
+    if (*qual_bytes) HIP_TRY(hipMemcpyAsync(cons_qual, ctx->cons_qual.p, (size_t)*qual_bytes, hipMemcpyDeviceToHost, s));
+    if (n_clusters) {
+        HIP_TRY(hipMemcpyAsync(seq_off, ctx->cons_off.p, (size_t)n_clusters * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(qual_off, ctx->cb_qoff.p, (size_t)n_clusters * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(depth, ctx->cons_cr.p, (size_t)n_clusters * 4, hipMemcpyDeviceToHost, s));
+        if (disagree) HIP_TRY(hipMemcpyAsync(disagree, ctx->cb_disagree.p, (size_t)n_clusters * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
     return UMI_OK;
 }
 

@@ -379,6 +379,23 @@ int consensus_on_device(void *workspace, const uint8_t *d_text, const uint64_t *
                         uint8_t *d_cons_qual, uint64_t *d_cons_off, uint32_t *d_cluster_reads, uint64_t *cons_bytes,
                         ConsFault *fault, unsigned long long *h_pinned, hipStream_t s);
 
+// ---- consensus of the clusters of aligned reads (umihip_consensus_bam.hip: umi_consensus_bam) ----
+// Everything in device memory; the clusters are given (cluster [n_reads], cluster_len [n_clusters]).
+// cons_seq / cons_qual take the clusters' consensus back to back, seq_off / qual_off where each starts,
+// depth its voters, disagree (may be null) its base votes that lost.  split: as for consensus_on_device
+// (never above 2^24 here: one wave sums in 32 bits).  h_pinned: 16 pinned words.  0 ok; 1 the inputs
+// break the contract (fault says how, nothing was written); negative: -(hipError_t)
+struct ConsBamFault {
+    unsigned long long bad_cluster_len = 0, bad_id = 0, bad_len = 0;
+};
+size_t consensus_bam_workspace_bytes(uint32_t n_reads, uint32_t n_clusters, uint32_t split);
+int consensus_bam_on_device(void *workspace, const uint8_t *d_data, const uint64_t *d_seq_pos, const uint64_t *d_qual_pos,
+                            const uint32_t *d_len, const uint32_t *d_cluster, uint32_t n_reads, const uint32_t *d_cluster_len,
+                            uint32_t n_clusters, uint32_t split, uint32_t n_cus, uint8_t *d_cons_seq, uint8_t *d_cons_qual,
+                            uint64_t *d_seq_off, uint64_t *d_qual_off, uint32_t *d_depth, uint32_t *d_disagree,
+                            uint64_t *seq_bytes, uint64_t *qual_bytes, ConsBamFault *fault, unsigned long long *h_pinned,
+                            hipStream_t s);
+
 // ---- correction of UMIs to a fixed list (umihip_correct.hip: umi_correct_umis) ----
 // The list is packed on the host, 2 bits per base (A 0, C 1, G 2, T 3), correct_words(umi_len) 32-bit
 // words per entry (correct_pack_list: 1 and *bad_entry at a byte outside ACGT), and walked on the

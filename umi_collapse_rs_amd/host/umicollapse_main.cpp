@@ -71,6 +71,22 @@
 // listed UMI.  Refused before the GPU is woken: fastq mode, --two-pass, --dump-staging, --passthrough, another
 // -u, the other three flags alone, a list that is empty, of mixed lengths, with a byte outside ACGT, with a
 // duplicate, or of more than 85 bases.
+// --call-consensus (bam/sam mode, one pass; not the reference's, tests/bam_consensus_model.py defines it): the
+// same records in the same order, but of each kept record the sequence and the qualities are its cluster's
+// consensus.  A cluster is a kept entry with every entry it removed, as for --tag; its voters are its reads
+// whose l_seq and CIGAR (n_cigar_op and the op words) are the representative's and that have qualities (the
+// reads of a position share strand and unclipped 5' end, so these line up column by column).  Per column the
+// base (nibble 1, 2, 4, 8) with the greatest sum of min(quality, 93) over the voters, ties by their number and
+// then the order ACGT, quality min(93, winner's sum - the others'), nibble 15 and quality 0 where nobody voted
+// (umi_consensus_bam, include/umihip.h: one call, the inflated file and the voters' offsets go up for it).
+// The record keeps everything else -- MAPQ, flags, its aux fields (an NM or MD may now be stale) -- and gets
+// cD:i = voters, cs:i = reads of the cluster (--tag's cs), ce:i = base votes that lost, appended.  A cluster
+// whose representative has no bases or no qualities is written unchanged, without the tags ("Number of
+// clusters without a consensus").  --call-consensus-min-reads M (default 1) leaves out the clusters with a
+// consensus of fewer than M voters ("Number of clusters below --call-consensus-min-reads").  Host staging,
+// as --tag.  Refused with status 101: with fastq mode, --tag, --two-pass, --paired, --dump-staging or
+// --passthrough; the second flag without the first or not a number >= 1; a staged read of more than 1024
+// bases.
 // Not implemented, as in the reference: --algo cc.
 #include <algorithm>
 #include <chrono>
@@ -121,6 +137,9 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     bool consensus = false;           // --consensus (fastq mode): every cluster written as its consensus read
     uint64_t consensus_min_reads = 1; // --consensus-min-reads M: clusters of fewer members are left out
     bool consensus_min_given = false;
+    bool call_consensus = false;           // --call-consensus (bam/sam mode): kept records carry their cluster's consensus
+    uint64_t call_consensus_min_reads = 1; // --call-consensus-min-reads M: clusters of fewer voters are left out
+    bool call_consensus_min_given = false;
     std::string umi_whitelist;     // --umi-whitelist FILE: every UMI is snapped to the nearest listed one first
     std::string whitelist_metrics; // --whitelist-metrics FILE: reads, exact, corrected per listed UMI
     int wl_max_mismatches = 1, wl_min_distance = 1; // --whitelist-max-mismatches, --whitelist-min-distance
@@ -173,6 +192,11 @@ struct HipLib {
                                  const uint32_t *, const int32_t *, const uint8_t *, const uint32_t *, uint64_t,
                                  const uint64_t *, const int32_t *, uint64_t, uint8_t *, uint8_t *, uint64_t *, uint32_t *,
                                  uint64_t *, void *) = nullptr;
+    // --call-consensus: likewise
+    bool want_consensus_bam = false;
+    int (*consensus_bam)(umi_ctx *, const uint8_t *, const uint64_t *, const uint64_t *, const uint32_t *, const uint32_t *,
+                         uint64_t, const uint32_t *, uint64_t, uint8_t *, uint8_t *, uint64_t *, uint64_t *, uint32_t *,
+                         uint32_t *, uint64_t *, uint64_t *) = nullptr;
     // --umi-whitelist: resolved only when the flag is given, like --consensus
     bool want_correct = false;
     int (*correct_umis)(umi_ctx *, const uint8_t *, uint64_t, int, const uint8_t *, uint32_t, int, int, uint8_t *, int32_t *,
@@ -215,6 +239,7 @@ struct HipLib {
             consensus_seqs = (decltype(consensus_seqs))sym("umi_consensus_seqs");
             consensus_seqs_device = (decltype(consensus_seqs_device))sym("umi_consensus_seqs_device");
         }
+        if (want_consensus_bam) consensus_bam = (decltype(consensus_bam))sym("umi_consensus_bam");
         if (want_correct) correct_umis = (decltype(correct_umis))sym("umi_correct_umis");
         hip_set_device = (decltype(hip_set_device))sym("hipSetDevice");
         hip_malloc = (decltype(hip_malloc))sym("hipMalloc");
@@ -296,6 +321,13 @@ void usage()
               "                           quality-weighted majority of all the cluster's reads -- in place of the kept\n"
               "                           read, the header with cluster_size=<reads> appended (not with --tag)\n"
               "      --consensus-min-reads <M> with --consensus: leave out clusters of fewer than M reads [default: 1]\n"
+              "      --call-consensus     bam/sam mode: every kept record carries its cluster's consensus -- each column the\n"
+              "                           quality-weighted majority of the cluster's reads with the kept read's length\n"
+              "                           and CIGAR -- for sequence and qualities, with cD:i (voters), cs:i (reads of the\n"
+              "                           cluster) and ce:i (base votes that lost) appended; everything else of the\n"
+              "                           record stays (not with --tag, --paired, --two-pass)\n"
+              "      --call-consensus-min-reads <M> with --call-consensus: leave out clusters of fewer than M voters\n"
+              "                           [default: 1]\n"
               "      --stage <WHERE>      gpu, host or auto: where reads are merged per (position, UMI) [default: auto]\n"
               "      --umi-tag <XX>       the UMI is the value of aux tag XX (type Z, e.g. RX or UB) instead of the\n"
               "                           read name's suffix; reads without it are dropped (bam/sam mode)\n"
@@ -385,6 +417,15 @@ Cli parse(int argc, char **argv)
             if (end == v || *end != '\0' || m < 1) die("--consensus-min-reads wants a number of reads, 1 or more");
             c.consensus_min_reads = (uint64_t)m;
             c.consensus_min_given = true;
+        }
+        else if (a == "--call-consensus") c.call_consensus = true;
+        else if (a == "--call-consensus-min-reads") {
+            const char *v = need(i);
+            char *end = nullptr;
+            const long long m = std::strtoll(v, &end, 10);
+            if (end == v || *end != '\0' || m < 1) die("--call-consensus-min-reads wants a number of reads, 1 or more");
+            c.call_consensus_min_reads = (uint64_t)m;
+            c.call_consensus_min_given = true;
         }
         else if (a == "--compress-level") {
             c.compress_level = std::atoi(need(i));
@@ -1614,6 +1655,15 @@ int main(int argc, char **argv)
     Cli args = parse(argc, argv);
     const double t_start = now_s();
     if (args.merge.empty()) args.merge = args.mode == "fastq" ? "avgqual" : "mapqual"; // main.rs:33-39
+    // --call-consensus: everything about it that can be refused is, before the GPU is woken
+    if (args.call_consensus_min_given && !args.call_consensus) die("--call-consensus-min-reads goes with --call-consensus only");
+    if (args.call_consensus) {
+        if (args.mode == "fastq") die("--call-consensus is defined in bam/sam mode only (fastq mode has --consensus)");
+        if (args.track_clusters) die("--call-consensus does not go with --tag (which writes every read as it is)");
+        if (args.two_pass) die("--call-consensus does not go with --two-pass (a cluster's reads are not held there)");
+        if (args.paired) die("--call-consensus does not go with --paired");
+        if (!args.dump_staging.empty() || args.passthrough) die("--call-consensus does not go with --dump-staging or --passthrough");
+    }
     if (args.track_clusters && args.two_pass) die("Cannot track clusters with the two pass algorithm!");
     if (args.paired && args.keep_unmapped) die("Cannot keep unmapped reads with paired-end reads!");
     if (args.consensus_min_given && !args.consensus) die("--consensus-min-reads goes with --consensus only");
@@ -1658,6 +1708,7 @@ int main(int argc, char **argv)
     // whoever needs the context first waits for this thread.
     HipLib lib;
     lib.want_correct = !whitelist.empty();
+    lib.want_consensus_bam = args.call_consensus;
     std::future<umi_ctx *> warm;
     std::string warm_error;
     if (!args.passthrough && args.dump_staging.empty())
@@ -1758,9 +1809,11 @@ int main(int argc, char **argv)
         // (where the reads are merged per (position, UMI): on the GPU unless something needs the host's
         // per-read bookkeeping -- decided here because the per-read pass only encodes UMIs for the host path)
         if (args.stage != "auto" && args.stage != "gpu" && args.stage != "host") die("--stage wants gpu, host or auto");
-        bool gpu_stage = args.stage != "host" && !args.passthrough && !args.paired && !args.track_clusters &&
+        const bool need_clusters = args.track_clusters || args.call_consensus; // every read's entry, every entry's root
+        bool gpu_stage = args.stage != "host" && !args.passthrough && !args.paired && !need_clusters &&
                          args.dump_staging.empty() && umi_length >= 1;
-        if (args.stage == "gpu" && !gpu_stage) die("--stage gpu does not go with --paired, --tag or --dump-staging");
+        if (args.stage == "gpu" && !gpu_stage)
+            die("--stage gpu does not go with --paired, --tag, --call-consensus or --dump-staging");
         struct ReadInfo {
             uint64_t coord, ref_strand, tlen;
             int32_t score;
@@ -2078,7 +2131,7 @@ int main(int argc, char **argv)
             std::vector<Entry> entries;
         };
         std::vector<Shard> shards(args.passthrough ? 0 : T);
-        entry_of.assign(args.track_clusters ? n_rec : 0, 0); // read -> entry of its shard (--tag)
+        entry_of.assign(need_clusters ? n_rec : 0, 0); // read -> entry of its shard (--tag, --call-consensus)
         umi::bgzf::parallel_for(shards.size(), T, [&](size_t t) {
             Shard &sh = shards[t];
             for (uint32_t ri = 0; ri < n_rec; ri++) {
@@ -2099,7 +2152,7 @@ int main(int argc, char **argv)
                 }
                 auto &idx = sh.umi_index[b];
                 auto e = idx.find(rkey[ri]);
-                if (args.track_clusters) entry_of[ri] = e == idx.end() ? (uint32_t)sh.entries.size() : e->second;
+                if (need_clusters) entry_of[ri] = e == idx.end() ? (uint32_t)sh.entries.size() : e->second;
                 if (e == idx.end()) { // Vacant :161-163
                     idx.emplace(rkey[ri], (uint32_t)sh.entries.size());
                     sh.bucket_entries[b].push_back((uint32_t)sh.entries.size());
@@ -2128,7 +2181,7 @@ int main(int argc, char **argv)
         freq.assign(n, 0);
         rep.assign(n, 0);
         size_t w = 0;
-        global_of.assign(args.track_clusters ? shards.size() : 0, {}); // (shard, entry) -> index
+        global_of.assign(need_clusters ? shards.size() : 0, {}); // (shard, entry) -> index
         for (size_t t = 0; t < global_of.size(); t++) global_of[t].resize(shards[t].entries.size());
         for (size_t b = 0; b < nb; b++) {
             Shard &sh = shards[order[b].shard];
@@ -2136,7 +2189,7 @@ int main(int argc, char **argv)
             std::stable_sort(v.begin(), v.end(), [&](uint32_t x, uint32_t y) { return sh.entries[y].freq < sh.entries[x].freq; });
             for (uint32_t ei : v) {
                 const Entry &en = sh.entries[ei];
-                if (args.track_clusters) global_of[order[b].shard][ei] = (uint32_t)w;
+                if (need_clusters) global_of[order[b].shard][ei] = (uint32_t)w;
                 for (int q = 0; q < n_words; q++) {
                     keys[w * n_words + q] = en.key.w[q];
                     nmask[w * n_words + q] = en.nmask.w[q];
@@ -2187,7 +2240,7 @@ int main(int argc, char **argv)
         // ---- the hot path: one batched call replaces the bucket loop :207-233
         lap("to-hot-path");
         std::vector<uint8_t> kept(n + 1, 0);
-        std::vector<uint32_t> root(args.track_clusters ? n + 1 : 0);
+        std::vector<uint32_t> root(need_clusters ? n + 1 : 0);
         umi_stats st;
         std::memset(&st, 0, sizeof(st));
         double t_gpu0 = now_s(), t_gpu1 = t_gpu0;
@@ -2198,7 +2251,7 @@ int main(int argc, char **argv)
             t_gpu0 = now_s();
             if (lib.dedup_batch(ctx, keys.data(), any_n ? nmask.data() : nullptr, n_words, freq.data(), off.data(), nb,
                                 (int)umi_length, args.k, args.percentage, algo, 0 /* adjacency.rs:56 */,
-                                kept.data(), args.track_clusters ? root.data() : nullptr, &st) != UMI_OK)
+                                kept.data(), need_clusters ? root.data() : nullptr, &st) != UMI_OK)
                 die(lib.last_error());
             t_gpu1 = now_s();
         }
@@ -2268,10 +2321,136 @@ int main(int argc, char **argv)
             if (have_ref) write_reversed(mates_all); // close(), :411-415
         }
 
+        // --call-consensus: the clusters numbered in order of kept entry (as cluster_id above), every staged read a
+        // voter of its cluster or of none, one call, then the kept records rebuilt around what came back
+        struct ConsensusOut {
+            std::vector<uint32_t> entry_of_out; // per written record: its kept entry, UINT32_MAX for the others
+            std::vector<uint32_t> cluster_id, cluster_reads, clen, depth, disagree;
+            std::vector<uint64_t> seq_off, qual_off;
+            umi::bgzf::Bytes seq, qual;
+            size_t n_below = 0, n_without = 0;
+        } cons;
+        if (args.call_consensus) {
+            cons.entry_of_out.assign(out_records.size(), UINT32_MAX);
+            cons.cluster_id.assign(n, 0);
+            cons.cluster_reads.assign(n, 0);
+            uint32_t nc = 0;
+            {
+                size_t o = out_records.size();
+                for (size_t i = n; i-- > 0;)
+                    if (kept[i]) cons.entry_of_out[--o] = (uint32_t)i; // (the kept entries are the last records written)
+            }
+            for (size_t i = 0; i < n; i++)
+                if (kept[i]) cons.cluster_id[i] = nc++;
+            for (size_t i = 0; i < n; i++) cons.cluster_reads[root[i]] += (uint32_t)freq[i];
+            cons.clen.assign(nc, 0);
+            for (size_t i = 0; i < n; i++) {
+                if (!kept[i]) continue;
+                const umi::bam::Record &rr = in.records[rep[i]];
+                const bool can = rr.l_seq() > 0 && rr.qual()[0] != 0xFF;
+                cons.clen[cons.cluster_id[i]] = can ? (uint32_t)rr.l_seq() : 0u;
+                if (!can) cons.n_without++;
+            }
+            std::vector<uint64_t> pos;   // seq_pos, then qual_pos, of the staged reads
+            std::vector<uint32_t> rlen, rcluster;
+            std::vector<uint32_t> staged_reads;
+            for (uint32_t ri = 0; ri < n_rec; ri++)
+                if (info[ri].state == 0) staged_reads.push_back(ri);
+            const size_t ns = staged_reads.size();
+            pos.resize(2 * ns);
+            rlen.resize(ns);
+            rcluster.resize(ns);
+            const uint8_t *base = in.data.data();
+            for (size_t j = 0; j < ns; j++) {
+                const uint32_t ri = staged_reads[j];
+                const umi::bam::Record &r = in.records[ri];
+                if (r.l_seq() > UMI_MAX_CONS_LEN)
+                    die("--call-consensus: read " + std::string((const char *)r.qname(), r.qname_len()) + " has " +
+                        std::to_string(r.l_seq()) + " bases, more than " + std::to_string(UMI_MAX_CONS_LEN));
+                const AlignKey akey{info[ri].coord, info[ri].ref_strand, info[ri].tlen, info[ri].cell};
+                const uint32_t e = global_of[hasher(akey) % T][entry_of[ri]];
+                const uint32_t rt = root[e];
+                const umi::bam::Record &rr = in.records[rep[rt]];
+                const uint32_t c = cons.cluster_id[rt];
+                const bool votes = cons.clen[c] != 0 && r.l_seq() == rr.l_seq() && r.n_cigar() == rr.n_cigar() &&
+                                   std::memcmp(r.cigar(), rr.cigar(), 4 * (size_t)r.n_cigar()) == 0 && r.qual()[0] != 0xFF;
+                pos[j] = (uint64_t)(r.seq() - base);
+                pos[ns + j] = (uint64_t)(r.qual() - base);
+                rlen[j] = (uint32_t)r.l_seq();
+                rcluster[j] = votes ? c : UMI_NO_CLUSTER;
+            }
+            size_t cap_s = 0, cap_q = 0;
+            for (uint32_t L : cons.clen) {
+                cap_s += (L + 1) / 2;
+                cap_q += L;
+            }
+            cons.seq.resize(cap_s + 1);
+            cons.qual.resize(cap_q + 1);
+            cons.seq_off.assign(nc + 1, 0);
+            cons.qual_off.assign(nc + 1, 0);
+            cons.depth.assign(nc + 1, 0);
+            cons.disagree.assign(nc + 1, 0);
+            if (nc) {
+                need_ctx();
+                if (!lib.consensus_bam) die("libumihip.so lacks umi_consensus_bam");
+                // (a --devices context shards positions; the vote is one device's work: the first one's)
+                umi_ctx *cctx = ctx;
+                if (args.devices.size() > 1 &&
+                    lib.ctx_create_multi(args.devices.data(), 1, &cctx) != UMI_OK)
+                    die(lib.last_error());
+                uint64_t sb = 0, qb = 0;
+                if (lib.consensus_bam(cctx, base, pos.data(), pos.data() + ns, rlen.data(), rcluster.data(), ns, cons.clen.data(),
+                                      nc, cons.seq.data(), cons.qual.data(), cons.seq_off.data(), cons.qual_off.data(),
+                                      cons.depth.data(), cons.disagree.data(), &sb, &qb) != UMI_OK)
+                    die(lib.last_error());
+            }
+            lap("consensus");
+        }
+
         // ---- write: header verbatim (Header::from_template :357-362) + surviving records verbatim
         constexpr size_t TAG_BYTES = 3 * 7; // three int32 aux fields
         lap("hot-path+select");
-        if (tagged.empty()) {
+        if (args.call_consensus) {
+            size_t out_len = in.header_len;
+            for (uint32_t ri : out_records) out_len += (size_t)(in.records[ri].end - in.records[ri].begin) + TAG_BYTES;
+            umi::bgzf::Bytes out(out_len);
+            std::memcpy(out.data(), in.data.data(), in.header_len);
+            size_t o = in.header_len;
+            for (size_t j = 0; j < out_records.size(); j++) {
+                const umi::bam::Record &r = in.records[out_records[j]];
+                const size_t len = (size_t)(r.end - r.begin);
+                const uint32_t e = cons.entry_of_out[j];
+                const uint32_t c = e == UINT32_MAX ? 0u : cons.cluster_id[e];
+                if (e == UINT32_MAX || cons.clen[c] == 0) { // (a kept unmapped read; a cluster without a consensus)
+                    std::memcpy(out.data() + o, r.begin, len);
+                    o += len;
+                    continue;
+                }
+                if (cons.depth[c] < args.call_consensus_min_reads) {
+                    cons.n_below++;
+                    continue;
+                }
+                const size_t head = (size_t)(r.seq() - r.begin), ls = (size_t)r.l_seq(), sbytes = (ls + 1) / 2;
+                const size_t aux_len = (size_t)(r.end - r.aux());
+                std::memcpy(out.data() + o, r.begin, head);
+                const int32_t block_size = (int32_t)(len - 4 + TAG_BYTES);
+                std::memcpy(out.data() + o, &block_size, 4);
+                std::memcpy(out.data() + o + head, cons.seq.data() + cons.seq_off[c], sbytes);
+                std::memcpy(out.data() + o + head + sbytes, cons.qual.data() + cons.qual_off[c], ls);
+                std::memcpy(out.data() + o + head + sbytes + ls, r.aux(), aux_len);
+                o += len;
+                const struct { const char *tag; int32_t v; } aux[3] = {
+                    {"cD", (int32_t)cons.depth[c]}, {"cs", (int32_t)cons.cluster_reads[e]}, {"ce", (int32_t)cons.disagree[c]}};
+                for (const auto &a : aux) {
+                    out[o++] = (uint8_t)a.tag[0];
+                    out[o++] = (uint8_t)a.tag[1];
+                    out[o++] = 'i';
+                    std::memcpy(out.data() + o, &a.v, 4);
+                    o += 4;
+                }
+            }
+            umi::bgzf::compress_to_file(args.output, out.data(), o, args.num_threads, args.compress_level);
+        } else if (tagged.empty()) {
             // the stream as pieces of the input (neighbouring survivors are one piece): the compressor
             // gathers each block's 64 KB itself, nothing is copied together first
             std::vector<umi::bgzf::Piece> pieces;
@@ -2340,6 +2519,10 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "Max number of UMIs over all alignment positions: %zu\n", max_umi);
         std::fprintf(stderr, args.track_clusters ? "Number of groups of reads: %llu\n" : "Number of reads after deduplicating: %llu\n",
                      (unsigned long long)st.n_kept); // :259-266
+        if (args.call_consensus) {
+            std::fprintf(stderr, "Number of clusters below --call-consensus-min-reads: %zu\n", cons.n_below);
+            std::fprintf(stderr, "Number of clusters without a consensus: %zu\n", cons.n_without);
+        }
         std::fprintf(stderr,
                      "phases: read+inflate %.3f s, staging (%s) %.3f s, gpu init %.3f s, hot path (H2D+GPU+D2H) %.3f s [%llu pairs], write %.3f s\n",
                      t_read - t_start, gpu_stage ? "gpu" : "host", t_stage0 - t_read - (gpu_stage ? t_init : 0.0), t_init,
