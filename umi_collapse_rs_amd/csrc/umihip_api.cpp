@@ -350,7 +350,8 @@ int directional_labels(umi_ctx *ctx, const uint2 *d_edges, unsigned long long *d
     if ((rc = run_rounds(ctx, s, [&](uint32_t *d_changed, int r) {
              return launch_dag_round(d_edges, d_cnt, edge_cap, d_label, d_lab, n, d_changed, r,
                                      (uint32_t)n_edges, s);
-         }, rounds, 3))) // freq at least halves along a one-way pair at p <= 0.5
+         }, rounds, 3))) // (the common depth: freq at least halves along a one-way pair at p <= 0.5; a deeper
+                         // chain -- 255 pairs in tests/test_gpu_deep_chains.py -- goes on in batches of 6, 12, 16)
         return rc;
     HIP_TRY(launch_map_labels(d_label, d_lab, n, s));
     return UMI_OK;

@@ -90,9 +90,12 @@ __device__ __forceinline__ void flatten_entry(uint32_t *parent, uint32_t *lab, u
 // One round along the one-way pairs over the flattened sets: lab[set of v] = min(.., lab[set of u])
 // for every pair u -> v of the list (directional.rs:38-39: v falls to whatever
 // removes u).  No pointer jump over lab[] behind it: a chain of one-way pairs is as deep as the freq
-// ladder it descends, two or three steps, and a pass over all of lab[] per round costs more than the
-// round it might save.  Only as many blocks walk the list as it needs (the count is on the
-// device): the fewer waves, the more of a hot word's hooks meet in one wave's registers.
+// ladder it descends -- two or three steps in sequencing data, where a pass over all of lab[] per
+// round costs more than the round it might save; nothing bounds it (at p = 1.0 a ladder 2n, 2n - 2,
+// ..., 2 is n - 1 one-way pairs in a row), and a deeper chain only takes more rounds: ladders of up
+// to 768 pairs are in tests/test_gpu_deep_chains.py.  Only as many blocks walk the list as it needs
+// (the count is on the device): the fewer waves, the more of a hot word's hooks meet in one wave's
+// registers.
 // Returns whether this thread saw a label to move.  Every lane of a wave makes the same trips.
 __device__ __forceinline__ bool one_way_round(const CollapseArgs &a)
 {
