@@ -74,6 +74,7 @@ typedef struct umi_stats {
 #define UMI_KERNEL_FUSED 1     /* small_bucket_kernel: one wave per position of <= 128 UMIs */
 #define UMI_KERNEL_SEG_PAIRS 2 /* seg_pair_kernel: all pairs inside the n-gram sub-buckets of deep positions */
 #define UMI_KERNEL_SEQ_PAIRS 3 /* seq_pair_kernel: the whole-read keys of umi_dedup_seqs */
+#define UMI_KERNEL_EDIT_PAIRS 4 /* edit_pair_kernel: the Levenshtein distance of umi_dedup_batch_edit */
 
 /* ---- context ----------------------------------------------------------- */
 int umi_ctx_create(int device_id, umi_ctx **out);
@@ -448,6 +449,34 @@ int umi_dedup_batch_device_table(umi_ctx *ctx, const uint64_t *d_keys, const uin
                                  const uint64_t *d_bucket_off, uint64_t n_buckets, int umi_len, int k,
                                  float percentage, int algo, int32_t adj_max_freq, uint8_t *d_kept,
                                  uint32_t *d_root, void *hip_stream, umi_stats *stats);
+
+/* ---- the batched call by Levenshtein (edit) distance: umi_dedup_batch's contract with d_E in place of
+ *      umi_dist (src/utils/mod.rs:24-26).  No counterpart in the reference; the distance is the one
+ *      starcode and the long-read UMI pipelines cluster by, because a base lost or gained in synthesis
+ *      shifts the rest of a fixed-length UMI window: ACGTACGTACGT without its first base is read as
+ *      CGTACGTACGTx, Hamming distance ~9, edit distance 2.
+ *      d_E(a, b): substitution, insertion and deletion cost 1 each, over the umi_len letters of A T C G N;
+ *      two letters match iff they are the same letter (N matches N and nothing else, as in umi_dist).
+ *      For equal lengths d_E <= d_H, and d_E == d_H wherever either is at most 1 -- one indel alone changes
+ *      the length, so an indel costs 2 and k <= 1 gives umi_dedup_batch's result bit for bit; the two differ
+ *      from k = 2 on.  Rank order inside a bucket, the f32 threshold, algo, adj_max_freq, kept / root, stats,
+ *      UMI_ERR_ORDER: as umi_dedup_batch.  Any k >= 0 up to INT_MAX; min(k, umi_len) is what is computed
+ *      with (no distance is larger), k >= umi_len means every pair of a bucket.
+ *      Keys are one word, umi_len 1..UMI_MAX_UMI_LEN; code 100 in a key is N, so nmask may be NULL whatever
+ *      the keys hold.  Where it is given, a key with code 100 at a base it does not cover is UMI_ERR_ORDER.
+ *      UMI_ERR_ARG: umi_len above 21, a multi-device context, 2^31 entries or more.
+ *      Every bucket goes through edit_pair_kernel (kernel_id UMI_KERNEL_EDIT_PAIRS), all pairs behind a
+ *      filter on the keys' letter counts: n_pairs_evaluated = n_pairs = W, n_candidates = the pairs that
+ *      passed the filter and had their exact distance taken.  A deferred call
+ *      (umi_dedup_batch_device_begin) that is out on the context ends first; its result keeps waiting for
+ *      umi_dedup_batch_end. */
+int umi_dedup_batch_edit(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask, const int32_t *freq,
+                         const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, int k, float percentage,
+                         int algo, int32_t adj_max_freq, uint8_t *kept, uint32_t *root, umi_stats *stats);
+int umi_dedup_batch_edit_device(umi_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_nmask,
+                                const int32_t *d_freq, const uint64_t *bucket_off, uint64_t n_buckets,
+                                int umi_len, int k, float percentage, int algo, int32_t adj_max_freq,
+                                uint8_t *d_kept, uint32_t *d_root, void *hip_stream, umi_stats *stats);
 
 /* The kept mask as one bit per entry (bit i % 8 of byte i / 8; ceil(n / 8) bytes at d_bits), packed
  * on the device and enqueued on hip_stream: what a one-process-per-GPU host all-gathers over RCCL

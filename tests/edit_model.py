@@ -1,0 +1,246 @@
+"""Model of the collapse by Levenshtein distance (umi_dedup_batch_edit, --distance edit), independent of the
+library: the distance by full dynamic programming on the characters, the collapse from its definition
+(helpers.brute_directional / brute_adjacency with the distance matrix swapped), and the inputs of the GPU
+tests -- UMIs that differ by a shift, which is what the Hamming distance misses."""
+import numpy as np
+
+from helpers import ALPHA, canonical, thr_f32
+
+CODE_OF = {"A": 0, "T": 5, "C": 6, "G": 3, "N": 4}  # src/utils/read.rs:23-31
+LETTER_OF = {v: k for k, v in CODE_OF.items()}
+
+
+def levenshtein(a, b):
+    """Substitution, insertion, deletion at cost 1 each; two letters match iff they are the same letter."""
+    prev = list(range(len(b) + 1))
+    for i, ca in enumerate(a, 1):
+        cur = [i]
+        for j, cb in enumerate(b, 1):
+            cur.append(min(prev[j] + 1, cur[j - 1] + 1, prev[j - 1] + (ca != cb)))
+        prev = cur
+    return prev[-1]
+
+
+def hamming(a, b):
+    return sum(x != y for x, y in zip(a, b))
+
+
+def edit_matrix(umis):
+    """levenshtein() of every pair of equal-length UMIs: the same recurrence, one DP cell at a time for all
+    pairs at once."""
+    n = len(umis)
+    if n == 0:
+        return np.zeros((0, 0), np.int64)
+    a = np.array([np.frombuffer(u.encode(), dtype=np.uint8) for u in umis])
+    L = a.shape[1]
+    prev = np.broadcast_to(np.arange(L + 1, dtype=np.int16), (n, n, L + 1)).copy()  # DP row 0: d(0, j) = j
+    for i in range(1, L + 1):
+        cur = np.empty_like(prev)
+        cur[:, :, 0] = i
+        for j in range(1, L + 1):
+            cur[:, :, j] = np.minimum(np.minimum(prev[:, :, j] + 1, cur[:, :, j - 1] + 1),
+                                      prev[:, :, j - 1] + (a[:, None, i - 1] != a[None, :, j - 1]))
+        prev = cur
+    return prev[:, :, L].astype(np.int64)
+
+
+def hamming_matrix(umis):
+    a = np.array([np.frombuffer(u.encode(), dtype=np.uint8) for u in umis])
+    return (a[:, None, :] != a[None, :, :]).sum(-1)
+
+
+def letter_counts(u):
+    return [u.count(c) for c in "ACGT"]
+
+
+def count_l1(a, b):
+    """The shipped filter's quantity: L1 distance of the counts of A, C, G, T (N counts for nothing)."""
+    return sum(abs(x - y) for x, y in zip(letter_counts(a), letter_counts(b)))
+
+
+def myers_global(a, b):
+    """The kernel's recurrence (umihip_edit.hip: edit_distance) in plain Python: Myers' bit vectors, Hyyro's
+    formulation, global distance.  Bit i of a vector is letter i of a; 32-bit registers; score starts at
+    len(a), Ph is shifted in as (Ph << 1) | 1, the score moves on bit len(a) - 1."""
+    M = 0xFFFFFFFF
+    L = len(a)
+    assert L == len(b) and 1 <= L <= 21
+    pv, mv, score = M, 0, L
+    for cb in b:
+        eq = 0
+        for i, ca in enumerate(a):
+            eq |= (ca == cb) << i
+        # (the kernel's eq has garbage above bit L - 1 where the letter's code is 000: it never moves down)
+        xv = eq | mv
+        xh = ((((eq & pv) + pv) & M) ^ pv) | eq
+        ph = (mv | ~(xh | pv)) & M
+        mh = pv & xh
+        score += ((ph >> (L - 1)) & 1) - ((mh >> (L - 1)) & 1)
+        ph = ((ph << 1) | 1) & M
+        mh = (mh << 1) & M
+        pv = (mh | ~(xv | ph)) & M
+        mv = ph & xv
+    return score
+
+
+def _collapse_directional(d, freq, k, p):
+    n = len(freq)
+    order = sorted(range(n), key=lambda i: (-freq[i], i))
+    if n == 0:
+        return [], []
+    thr = np.array([thr_f32(p, f) for f in freq])
+    fr = np.array(freq)
+    adj = (d <= k) & (fr[None, :] <= thr[:, None])
+    np.fill_diagonal(adj, False)
+    present = np.ones(n, bool)
+    root_of = list(range(n))
+    surv = []
+    for r in order:
+        if not present[r]:
+            continue
+        surv.append(r)
+        present[r] = False
+        frontier = [r]
+        while frontier:
+            nxt = []
+            for u in frontier:
+                vs = np.nonzero(adj[u] & present)[0]
+                present[vs] = False
+                for v in vs:
+                    root_of[v] = r
+                nxt.extend(vs.tolist())
+            frontier = nxt
+    return surv, root_of
+
+
+def _collapse_adjacency(d, freq, k, max_freq):
+    n = len(freq)
+    order = sorted(range(n), key=lambda i: (-freq[i], i))
+    if n == 0:
+        return [], []
+    fr = np.array(freq)
+    present = np.ones(n, bool)
+    root_of = list(range(n))
+    surv = []
+    for r in order:
+        if not present[r]:
+            continue
+        surv.append(r)
+        present[r] = False
+        vs = np.nonzero((d[r] <= k) & (fr <= max_freq) & present)[0]
+        present[vs] = False
+        for v in vs:
+            root_of[v] = r
+    return surv, root_of
+
+
+def brute_directional_edit(umis, freq, k, p, d=None):
+    """helpers.brute_directional with d_E for the distance (d: the bucket's edit_matrix, if at hand)."""
+    return _collapse_directional(edit_matrix(umis) if d is None else d, freq, k, p)
+
+
+def brute_adjacency_edit(umis, freq, k, max_freq, d=None):
+    return _collapse_adjacency(edit_matrix(umis) if d is None else d, freq, k, max_freq)
+
+
+def model_batch(buckets, k, p=0.5, algo=0, adj_max_freq=0, mats=None):
+    """kept u8 [N] / root u32 [N] of a batch of (umis, freq) buckets in rank order, global indices."""
+    kept, root, at = [], [], 0
+    for b, (umis, freq) in enumerate(buckets):
+        d = mats[b] if mats is not None else None
+        surv, root_of = (brute_directional_edit(umis, freq, k, p, d) if algo == 0
+                         else brute_adjacency_edit(umis, freq, k, adj_max_freq, d))
+        m = np.zeros(len(umis), np.uint8)
+        m[surv] = 1
+        kept.append(m)
+        root.append(np.array(root_of, np.int64) + at)
+        at += len(umis)
+    if not kept:
+        return np.zeros(0, np.uint8), np.zeros(0, np.uint32)
+    return np.concatenate(kept), np.concatenate(root).astype(np.uint32)
+
+
+def encode(umis):
+    """Keys and N masks of the batched ABI (src/utils/mod.rs:63-83), straight from the code table."""
+    keys = np.zeros(len(umis), np.uint64)
+    nm = np.zeros(len(umis), np.uint64)
+    for i, u in enumerate(umis):
+        kk = mm = 0
+        for b, ch in enumerate(u):
+            kk |= CODE_OF[ch] << (3 * b)
+            if ch == "N":
+                mm |= 7 << (3 * b)
+        keys[i], nm[i] = kk, mm
+    return keys, nm
+
+
+def decode(keys, umi_len):
+    return ["".join(LETTER_OF[(int(k) >> (3 * b)) & 7] for b in range(umi_len)) for k in keys]
+
+
+def pack(buckets):
+    """(keys, nmask, freq, bucket_off) of a list of (umis, freq) buckets."""
+    keys, nm, fr, off = [np.zeros(0, np.uint64)], [np.zeros(0, np.uint64)], [], [0]
+    for umis, freq in buckets:
+        kk, mm = encode(umis)
+        keys.append(kk); nm.append(mm); fr.extend(freq); off.append(off[-1] + len(umis))
+    return np.concatenate(keys), np.concatenate(nm), np.array(fr, np.int32), np.array(off, np.uint64)
+
+
+# ---- inputs ---------------------------------------------------------------------------------------
+
+def shifted_reads(rng, n_mol, L, mean_copies=4.0, sub=0.03, indel=0.25, n_frac=0.0):
+    """Molecule model with synthesis errors, read by read: n_mol true UMIs, geometric copy counts; a copy
+    has per-base substitutions (sub) and, with probability indel, one of the two shifts of a fixed-length
+    window -- base i deleted and a random base appended, or a random base inserted at i and the last base
+    dropped.  Returns the reads' UMIs as strings, in order."""
+    out = []
+    for _ in range(n_mol):
+        true = rng.choice(ALPHA, L)
+        for _ in range(int(rng.geometric(1.0 / mean_copies))):
+            u = true.copy()
+            for i in np.nonzero(rng.random(L) < sub)[0]:
+                u[i] = rng.choice(ALPHA[ALPHA != u[i]])
+            if rng.random() < indel:
+                i = int(rng.integers(0, L))
+                if rng.random() < 0.5:  # deletion: the rest moves up, the next base of the read comes in
+                    u = np.concatenate([u[:i], u[i + 1:], rng.choice(ALPHA, 1)])
+                else:                   # insertion: the rest moves down, the last base falls out
+                    u = np.concatenate([u[:i], rng.choice(ALPHA, 1), u[i:L - 1]])
+            if n_frac:
+                u[rng.random(L) < n_frac] = ord("N")
+            out.append(u.tobytes().decode())
+    return out
+
+
+def shifted_bucket(rng, n_mol, L, mean_copies=4.0, sub=0.03, indel=0.25, n_frac=0.0, n_max=None):
+    """One position of shifted_reads in rank order: (umis, freq); at most n_max distinct UMIs, the first to
+    appear (molecules with their copies, not the most frequent ones)."""
+    seen = {}
+    for s in shifted_reads(rng, n_mol, L, mean_copies, sub, indel, n_frac):
+        seen[s] = seen.get(s, 0) + 1
+    umis = list(seen)[:n_max]
+    umis, freq, _ = canonical(umis, [seen[u] for u in umis])
+    return umis, freq
+
+
+def same_composition_bucket(L, n, seed=0):
+    """n distinct arrangements of one multiset of letters (L // 2 times A, the rest C: 924 of them at
+    L = 12): every pair has the same letter counts and passes the count filter.  Rank order, freq."""
+    import itertools
+    rng = np.random.default_rng(seed)
+    every = ["".join("A" if i in at else "C" for i in range(L)) for at in
+             (set(c) for c in itertools.combinations(range(L), L // 2))]
+    assert n <= len(every)
+    pick = sorted(rng.choice(len(every), n, replace=False).tolist())
+    umis = [every[i] for i in pick]
+    freq = [int(f) for f in rng.choice([1, 1, 2, 3, 5, 9, 20], n)]
+    umis, freq, _ = canonical(umis, freq)
+    return umis, freq
+
+
+def shift_only_pairs(umis, k, d_e=None):
+    """Pairs (i < j) with d_E <= k < d_H: what a Hamming run cannot see."""
+    d_e = edit_matrix(umis) if d_e is None else d_e
+    d_h = hamming_matrix(umis)
+    return int((np.triu((d_e <= k) & (d_h > k), 1)).sum())

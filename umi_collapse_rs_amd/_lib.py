@@ -12,6 +12,7 @@ UMI_ERR_ARG, UMI_ERR_HIP, UMI_ERR_ORDER, UMI_ERR_NOMEM, UMI_ERR_NODEV, UMI_ERR_C
     -1, -2, -3, -4, -5, -6)
 UMI_ALGO_DIRECTIONAL, UMI_ALGO_ADJACENCY = 0, 1
 UMI_MAX_UMI_LEN = 21
+UMI_KERNEL_EDIT_PAIRS = 4     # Stats.kernel_id of umi_dedup_batch_edit (with "profile")
 UMI_MAX_CONS_LEN = 1024       # umi_consensus_bam: bases of a cluster, at most
 UMI_NO_CLUSTER = 0xFFFFFFFF   # ... a read that votes nowhere
 
@@ -110,6 +111,13 @@ SIGNATURES = {
                                          C.c_uint64, C.c_int, C.c_int, C.c_float, C.c_int,
                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(Stats)]),
+    "umi_dedup_batch_edit": (C.c_int, [C.c_void_p, _u64p, _u64p, _i32p, _u64p, C.c_uint64, C.c_int,
+                                       C.c_int, C.c_float, C.c_int, C.c_int32, _u8p, _u32p,
+                                       C.POINTER(Stats)]),
+    "umi_dedup_batch_edit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p,
+                                              C.c_uint64, C.c_int, C.c_int, C.c_float, C.c_int,
+                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(Stats)]),
     "umi_dedup_batch_device_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_void_p,
                                                C.c_uint64, C.c_int, C.c_int, C.c_float, C.c_int,
                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

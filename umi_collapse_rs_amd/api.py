@@ -127,6 +127,30 @@ class Context:
                                      C.byref(st)))
         return kept, root, st.as_dict()
 
+    def dedup_batch_edit(self, keys, nmask, freq, bucket_off, umi_len, k=1, percentage=0.5,
+                         algo=UMI_ALGO_DIRECTIONAL, adj_max_freq=0, want_root=True):
+        """dedup_batch by Levenshtein distance (umi_dedup_batch_edit): one-word keys, umi_len <= 21; nmask may
+        be None whatever the keys hold.  An indel costs 2 between UMIs of one length, so the result differs
+        from dedup_batch's from k = 2 on.  Returns (kept u8[N], root u32[N] or None, stats dict)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        freq = np.ascontiguousarray(freq, dtype=np.int32)
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        nm = None if nmask is None else np.ascontiguousarray(nmask, dtype=np.uint64)
+        n = len(keys)
+        if len(freq) != n or (nm is not None and len(nm) != n):
+            raise ValueError("keys/nmask/freq lengths differ")
+        if len(bucket_off) < 1 or (len(bucket_off) > 1 and int(bucket_off[-1]) != n):
+            raise ValueError("bucket_off[-1] must equal len(keys)")
+        kept = np.zeros(n, dtype=np.uint8)
+        root = np.zeros(n, dtype=np.uint32) if want_root else None
+        st = Stats()
+        check(load().umi_dedup_batch_edit(self._h, ptr(keys, C.c_uint64), ptr(nm, C.c_uint64),
+                                          ptr(freq, C.c_int32), ptr(bucket_off, C.c_uint64),
+                                          len(bucket_off) - 1, umi_len, k, percentage, algo,
+                                          adj_max_freq, ptr(kept, C.c_uint8), ptr(root, C.c_uint32),
+                                          C.byref(st)))
+        return kept, root, st.as_dict()
+
     def dedup_batch_wide(self, keys, nmask, freq, bucket_off, umi_len, k=1, percentage=0.5,
                          algo=UMI_ALGO_DIRECTIONAL, adj_max_freq=0, want_root=True):
         """Batched call for keys of several words (umi_len > 21): keys / nmask uint64 [N, n_words]."""
@@ -476,6 +500,17 @@ class Context:
                                                   len(bucket_off) - 1, umi_len, k, percentage, algo,
                                                   adj_max_freq, d_kept, d_root or None, stream or None,
                                                   C.byref(st)))
+        return st.as_dict()
+
+    def dedup_batch_edit_device(self, d_keys, d_nmask, d_freq, bucket_off, umi_len, d_kept, d_root=0,
+                                k=1, percentage=0.5, algo=UMI_ALGO_DIRECTIONAL, adj_max_freq=0, stream=0):
+        """umi_dedup_batch_edit_device: dedup_batch_device by Levenshtein distance."""
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        st = Stats()
+        check(load().umi_dedup_batch_edit_device(self._h, d_keys, d_nmask or None, d_freq,
+                                                 ptr(bucket_off, C.c_uint64), len(bucket_off) - 1, umi_len, k,
+                                                 percentage, algo, adj_max_freq, d_kept, d_root or None,
+                                                 stream or None, C.byref(st)))
         return st.as_dict()
 
 

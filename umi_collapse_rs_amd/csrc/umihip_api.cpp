@@ -403,6 +403,16 @@ class Pipeline {
     // all-pairs kernel of umihip_wide.hip.
     void use_wide_keys(int words) { n_words = words; }
     void allow_deferred_end() { may_defer = true; }
+    // Levenshtein distance between one-word keys (umi_dedup_batch_edit): every bucket as 64-row chunks
+    // against its later entries through the kernel of umihip_edit.hip -- no fused kernel, no segment
+    // index (two UMIs within k edits need not agree on any fixed base range).  No distance exceeds
+    // umi_len, and the clamped k is what the kernel sees.
+    void use_edit_distance()
+    {
+        edit = true;
+        k = std::min(k, umi_len);
+        fused_max = 0;
+    }
 
   private:
     umi_ctx *ctx;
@@ -411,6 +421,7 @@ class Pipeline {
     const uint64_t *bucket_off;
     const uint64_t *d_boff_caller = nullptr;
     int n_words = 1;
+    bool edit = false;
     bool wide() const { return n_words > 1; }
     int plan_umi_len() const { return wide() ? 21 : umi_len; } // bases the filter keys hold
     const uint64_t *d_boff() const { return d_boff_caller ? d_boff_caller : ctx->boff.as<uint64_t>(); }
@@ -430,7 +441,7 @@ class Pipeline {
     const uint32_t part, n_parts; // n_parts > 1: evaluate only every n_parts-th tile task, stop
                                   // after the pair kernels (multi-GPU split of one call's pairs)
     uint64_t task_counter = 0;    // running index over all tile tasks, for that split
-    bool prune = false, drained = false, fused_ran = false, seg_timed = false;
+    bool prune = false, drained = false, fused_ran = false, seg_timed = false, edit_timed = false;
     bool may_defer = false; // umi_dedup_batch_device_begin: the end of the call may be left on the stream
     size_t zero_behind_control = 0; // bytes of the segment index's counters that sit behind the control block
     uint32_t priv_blocks_for_collapse = 0; // blocks of the segment index's local and pair kernels whose private edge
@@ -588,6 +599,7 @@ class Pipeline {
             return rc;
         if (mode == MODE_ADJACENCY && need_pairs)
             if ((rc = ctx->status.reserve(n)) || (rc = ctx->blocked.reserve(n))) return rc;
+        if (edit && (rc = ctx->planes.reserve((size_t)n * 4))) return rc; // (the keys' letter counts; fkey: their bit planes)
         d_cnt = ctx->counters.as<unsigned long long>();
         bs_fkey = ctx->fkey.p;
         return UMI_OK;
@@ -598,12 +610,12 @@ class Pipeline {
     {
         // (the table is monotone: upload_table has looked)
         scan_table_range(bucket_off, 0, n_buckets, fused_max, nullptr, ctx->table_pass);
-        const bool seg_on = ctx->seg_index && need_pairs && !ctx->prune;
-        build_plan(bucket_off, n_buckets, wide() ? 0x7FFFFFFFu : ctx->small_max, ctx->use_bitslice && k <= BS_MAX_K && !wide(),
+        const bool seg_on = ctx->seg_index && need_pairs && !ctx->prune && !edit;
+        build_plan(bucket_off, n_buckets, wide() || edit ? 0x7FFFFFFFu : ctx->small_max, ctx->use_bitslice && k <= BS_MAX_K && !wide() && !edit,
                    plan_umi_len(), fused_max, ctx->prune, ctx->bs_sorted && ctx->bs_unit == 2 && need_pairs,
                    ctx->bs_tables && key32, ctx->bs_tab_min_run, seg_on ? std::max(ctx->seg_min, 1u) : 0u, k, key32, pl,
                    &ctx->table_pass);
-        prune = ctx->prune && need_pairs && !pl.bs_buckets.empty() && !wide();
+        prune = ctx->prune && need_pairs && !pl.bs_buckets.empty() && !wide() && !edit;
         keep_my_share(pl.small_tasks);
         keep_my_share(pl.big_tasks);
         st.max_bucket = pl.max_bucket;
@@ -805,6 +817,12 @@ class Pipeline {
     // the entries of a segment also count themselves into the bins of its parts
     int prep_stage()
     {
+        if (edit) {
+            HIP_TRY(launch_edit_prep(d_keys, d_nmask, d_freq, d_boff(), n_buckets, n, umi_len, percentage,
+                                     ctx->fkey.as<uint64_t>(), ctx->planes.as<uint32_t>(), ctx->thr.as<int32_t>(),
+                                     ctx->label.as<uint32_t>(), d_cnt, s));
+            return UMI_OK;
+        }
         // With the LDS counting sort the segments' entries are prepared by its count kernel; the
         // entry kernel keeps the other buckets' ranges (none at all for a call of deep positions:
         // only the rises at bucket starts are left to count)
@@ -917,7 +935,7 @@ class Pipeline {
     {
         n_tasks = pl.small_tasks.size() + pl.big_tasks.size() + pl.n_bs() + pl.tab_rows.size() +
                   (pl.seg_parts ? 1 : 0);
-        if (need_pairs) st.n_pairs_evaluated = pl.n_pairs_eval;
+        if (need_pairs) st.n_pairs_evaluated = edit ? pl.n_pairs : pl.n_pairs_eval; // (edit: no tile padding counted)
 #ifdef UMIHIP_DEV
         if (need_pairs && legacy_tiles()) {
             int rc;
@@ -1077,6 +1095,14 @@ class Pipeline {
                                     ctx->bs_unit, li == 2 ? 3 : (li == 3 ? 4 : 0), s));
         }
 #endif
+        if (edit) { // every bucket as 64-row chunks against its later entries, by edit distance
+            if (prof) HIP_TRY(hipEventRecord(ctx->ev[7], s));
+            HIP_TRY(launch_edit_pairs(a, ctx->planes.as<uint32_t>(), (uint32_t)pl.small_tasks.size(), umi_len, s));
+            if (prof) HIP_TRY(hipEventRecord(ctx->ev[8], s));
+            edit_timed = true;
+            st.n_pair_launches += pl.small_tasks.empty() ? 0 : 1;
+            return UMI_OK;
+        }
         if (wide()) { // every bucket as 64-row chunks against its later entries
             HIP_TRY(launch_wide_pairs(a, (uint32_t)pl.small_tasks.size(), n_words, s));
             st.n_pair_launches += pl.small_tasks.empty() ? 0 : 1;
@@ -1098,7 +1124,7 @@ class Pipeline {
         n_direct = ctx->h_counters[CNT_UF_DIRECT];
         seg_tasks_made = ctx->h_counters[CNT_SEG_TASKS];
         st.n_candidates = ctx->h_counters[CNT_CANDIDATES];
-        st.n_pairs_evaluated = pl.n_pairs_eval + ctx->h_counters[CNT_SEG_PAIRS];
+        st.n_pairs_evaluated = edit ? pl.n_pairs : pl.n_pairs_eval + ctx->h_counters[CNT_SEG_PAIRS];
         if (!pl.tab_rows.empty()) // the table kernel walks only the column tiles its scan kept
             st.n_pairs_evaluated = st.n_pairs_evaluated - pl.n_pairs_eval_tab +
                                    (ctx->h_counters[CNT_ITEMS] + ctx->h_counters[CNT_DIAG_ITEMS]) *
@@ -1360,7 +1386,10 @@ class Pipeline {
             HIP_TRY(hipEventElapsedTime(&st.ms_total, ev[0], ev[4]));
             // the kernel that does the call's pair work, by itself: the segment index's pair kernel
             // where a deep position is in the call, else the fused small-bucket kernel
-            if (seg_timed) {
+            if (edit_timed) {
+                HIP_TRY(hipEventElapsedTime(&st.ms_kernel, ev[7], ev[8]));
+                st.kernel_id = UMI_KERNEL_EDIT_PAIRS;
+            } else if (seg_timed) {
                 HIP_TRY(hipEventElapsedTime(&st.ms_kernel, ev[7], ev[8]));
                 st.kernel_id = UMI_KERNEL_SEG_PAIRS;
             } else if (fused_ran) {
@@ -1458,13 +1487,14 @@ int run_pipeline(umi_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_nmask,
                  const int32_t *d_freq, const uint64_t *bucket_off, uint64_t n_buckets, uint32_t n,
                  int umi_len, int k, float percentage, int mode, int32_t adj_max_freq,
                  uint8_t *d_kept, uint32_t *d_root, hipStream_t s, umi_stats *stats,
-                 const uint64_t *d_bucket_off = nullptr, int n_words = 1, bool may_defer = false)
+                 const uint64_t *d_bucket_off = nullptr, int n_words = 1, bool may_defer = false, bool edit = false)
 {
     settle(ctx); // (a deferred call owns the workspace until its end has been seen)
     Pipeline p(ctx, d_keys, d_nmask, d_freq, bucket_off, n_buckets, n, umi_len, k, percentage, mode, adj_max_freq,
                d_kept, d_root, s);
     p.use_device_table(d_bucket_off);
     p.use_wide_keys(n_words);
+    if (edit) p.use_edit_distance();
     if (may_defer) p.allow_deferred_end();
     return p.run(stats);
 }
@@ -2455,6 +2485,75 @@ int umi_dedup_batch_device_table(umi_ctx *ctx, const uint64_t *d_keys, const uin
                         k, percentage,
                         algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY,
                         adj_max_freq, d_kept, d_root, (hipStream_t)hip_stream, stats, d_bucket_off);
+}
+
+// ---- Levenshtein distance between one-word keys (umihip_edit.hip) ----------------------------------
+int umi_dedup_batch_edit_device(umi_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_nmask, const int32_t *d_freq,
+                                const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, int k, float percentage,
+                                int algo, int32_t adj_max_freq, uint8_t *d_kept, uint32_t *d_root, void *hip_stream,
+                                umi_stats *stats)
+{
+    if (ctx && !ctx->subs.empty()) {
+        if (ctx->subs.size() > 1) return fail(UMI_ERR_ARG, "edit distance takes a single-device context");
+        ctx = ctx->subs[0];
+    }
+    uint64_t n = 0;
+    int rc = check_common(ctx, bucket_off, n_buckets, umi_len, k, algo, &n);
+    if (rc) return rc;
+    if (n && (!d_keys || !d_freq || !d_kept)) return fail(UMI_ERR_ARG, "keys/freq/kept is NULL");
+    if (n == 0) {
+        if (stats) {
+            memset(stats, 0, sizeof(*stats));
+            stats->n_buckets = n_buckets;
+        }
+        return UMI_OK;
+    }
+    return run_pipeline(ctx, d_keys, d_nmask, d_freq, bucket_off, n_buckets, (uint32_t)n, umi_len, k, percentage,
+                        algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY, adj_max_freq, d_kept, d_root,
+                        (hipStream_t)hip_stream, stats, nullptr, 1, false, true);
+}
+
+int umi_dedup_batch_edit(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask, const int32_t *freq,
+                         const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, int k, float percentage, int algo,
+                         int32_t adj_max_freq, uint8_t *kept, uint32_t *root, umi_stats *stats)
+{
+    if (ctx && !ctx->subs.empty()) {
+        if (ctx->subs.size() > 1) return fail(UMI_ERR_ARG, "edit distance takes a single-device context");
+        ctx = ctx->subs[0];
+    }
+    uint64_t n = 0;
+    int rc = check_common(ctx, bucket_off, n_buckets, umi_len, k, algo, &n);
+    if (rc) return rc;
+    if (n && (!keys || !freq || !kept)) return fail(UMI_ERR_ARG, "keys/freq/kept is NULL");
+    for (uint64_t b = 0; b < n_buckets; b++)
+        if (bucket_off[b + 1] < bucket_off[b])
+            return fail(UMI_ERR_ARG, "bucket_off not monotone at bucket %llu", (unsigned long long)b);
+    if (n == 0) {
+        if (stats) {
+            memset(stats, 0, sizeof(*stats));
+            stats->n_buckets = n_buckets;
+        }
+        return UMI_OK;
+    }
+    settle(ctx); // (the staging buffers below are the deferred call's as well)
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = ctx->in_keys.reserve(n * 8)) || (rc = ctx->in_freq.reserve(n * 4)) || (rc = ctx->out_kept.reserve(n)) ||
+        (rc = ctx->out_root.reserve(n * 4)) || (nmask && (rc = ctx->in_nmask.reserve(n * 8))))
+        return rc;
+    hipStream_t s = ctx->own_stream;
+    HIP_TRY(hipMemcpyAsync(ctx->in_keys.p, keys, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ctx->in_freq.p, freq, n * 4, hipMemcpyHostToDevice, s));
+    if (nmask) HIP_TRY(hipMemcpyAsync(ctx->in_nmask.p, nmask, n * 8, hipMemcpyHostToDevice, s));
+    rc = run_pipeline(ctx, ctx->in_keys.as<uint64_t>(), nmask ? ctx->in_nmask.as<uint64_t>() : nullptr,
+                      ctx->in_freq.as<int32_t>(), bucket_off, n_buckets, (uint32_t)n, umi_len, k, percentage,
+                      algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY, adj_max_freq,
+                      ctx->out_kept.as<uint8_t>(), root ? ctx->out_root.as<uint32_t>() : nullptr, s, stats, nullptr, 1,
+                      false, true);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(kept, ctx->out_kept.p, n, hipMemcpyDeviceToHost, s));
+    if (root) HIP_TRY(hipMemcpyAsync(root, ctx->out_root.p, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return UMI_OK;
 }
 
 int umi_dedup_batch_device_begin(umi_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_nmask, const int32_t *d_freq,

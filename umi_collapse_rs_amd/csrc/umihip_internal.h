@@ -293,6 +293,17 @@ hipError_t launch_seg_local(const PairArgs &a, const SegArgs &g, float percentag
 // a.tasks: rows [row0, row0 + 64) x columns [col0, col1) of one bucket; exact distance from all words
 hipError_t launch_wide_pairs(const PairArgs &a, uint32_t n_tasks, int n_words, hipStream_t s);
 
+// ---- edit distance between one-word keys (umihip_edit.hip): umi_len 1..21, k <= umi_len
+// the entry pass of such a call (every entry: threshold, label, contract check as launch_prep) with the two
+// forms of a key its pair kernel reads: planes[i] = bit b of base j's code at bit 21 b + j, counts[i] = the
+// key's A, C, G, T in bytes 0..3
+hipError_t launch_edit_prep(const uint64_t *keys, const uint64_t *nmask, const int32_t *freq, const uint64_t *bucket_off,
+                            uint64_t n_buckets, uint32_t n, int umi_len, float percentage, uint64_t *planes,
+                            uint32_t *counts, int32_t *thr, uint32_t *label, unsigned long long *counters, hipStream_t s);
+// a.tasks: rows [row0, row0 + 64) x columns [col0, col1) of one bucket; a.fkey: the planes.  Count filter,
+// LDS queue of its hits, exact Levenshtein distance of each; permitted pairs to the edge list
+hipError_t launch_edit_pairs(const PairArgs &a, const uint32_t *counts, uint32_t n_tasks, int umi_len, hipStream_t s);
+
 // ---- whole-read keys (umihip_seq.hip): reads of up to 256 bases, 1..12 words per key, stride words apart
 constexpr int SEQ_MAX_WORDS = 12;
 constexpr uint32_t SEQ_TILE = 64;           // rows / columns of a pair task

@@ -87,6 +87,17 @@
 // as --tag.  Refused with status 101: with fastq mode, --tag, --two-pass, --paired, --dump-staging or
 // --passthrough; the second flag without the first or not a number >= 1; a staged read of more than 1024
 // bases.
+// --distance hamming|edit (bam/sam mode; not the reference's, tests/edit_model.py defines it): which distance -k
+// bounds.  hamming, the default, is the reference's umi_dist and changes nothing.  edit is the Levenshtein
+// distance over the UMI's letters -- substitution, insertion and deletion cost 1 each, N matches N only -- which
+// sees the shift that a base lost or gained in synthesis leaves in a fixed-length UMI window: ACGTACGTACGT
+// without its first base reads CGTACGTACGTx, Hamming distance ~9, edit distance 2.  Between UMIs of one length
+// an indel costs 2 (one insertion and one deletion), the two distances agree wherever either is at most 1, and
+// -k 0 / -k 1 therefore give the Hamming result: the flag matters from -k 2.  Only the batched library call
+// differs (umi_dedup_batch_edit, include/umihip.h): -k, -p, --algo, --merge, --keep-unmapped, --paired, --tag,
+// --umi-tag, --per-cell, --umi-whitelist, --call-consensus, --two-pass and both --stage values work as before;
+// the summary gains "UMI distance: edit".  Refused with status 101: any other value, fastq mode, several
+// --devices, a UMI length above 21 (-u, the whitelist's, or the first staged read's).
 // Not implemented, as in the reference: --algo cc.
 #include <algorithm>
 #include <chrono>
@@ -144,6 +155,7 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     std::string whitelist_metrics; // --whitelist-metrics FILE: reads, exact, corrected per listed UMI
     int wl_max_mismatches = 1, wl_min_distance = 1; // --whitelist-max-mismatches, --whitelist-min-distance
     bool wl_max_given = false, wl_min_given = false;
+    bool edit_distance = false; // --distance edit: -k bounds the Levenshtein distance (umi_dedup_batch_edit)
 };
 
 [[noreturn]] void die(const std::string &msg)
@@ -183,6 +195,19 @@ struct HipLib {
     int (*dedup_seqs_device)(umi_ctx *, const uint64_t *, const uint64_t *, int, const int32_t *, const uint64_t *,
                              const int32_t *, uint64_t, int, float, int, int32_t, uint8_t *, uint32_t *, void *,
                              umi_stats *) = nullptr;
+    // --distance edit: resolved only when the flag is given, like --consensus below; one-word keys only
+    bool want_edit = false;
+    int (*dedup_batch_edit)(umi_ctx *, const uint64_t *, const uint64_t *, const int32_t *, const uint64_t *, uint64_t, int, int,
+                            float, int, int32_t, uint8_t *, uint32_t *, umi_stats *) = nullptr;
+    // the batched call of the run: by the distance --distance names
+    int dedup(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask, int n_words, const int32_t *freq, const uint64_t *off,
+              uint64_t nb, int umi_len, int k, float percentage, int algo, int32_t adj_max_freq, uint8_t *kept, uint32_t *root,
+              umi_stats *st) const
+    {
+        if (want_edit) // (n_words is 1: a UMI length above 21 has been refused)
+            return dedup_batch_edit(ctx, keys, nmask, freq, off, nb, umi_len, k, percentage, algo, adj_max_freq, kept, root, st);
+        return dedup_batch(ctx, keys, nmask, n_words, freq, off, nb, umi_len, k, percentage, algo, adj_max_freq, kept, root, st);
+    }
     // --consensus: resolved only when the flag is given, so that a library without them serves every other run
     bool want_consensus = false;
     int (*consensus_seqs)(umi_ctx *, const uint8_t *, const uint64_t *, const uint64_t *, const uint32_t *, uint64_t,
@@ -235,6 +260,7 @@ struct HipLib {
         stage_seqs = (decltype(stage_seqs))sym("umi_stage_seqs");
         stage_seqs_device = (decltype(stage_seqs_device))sym("umi_stage_seqs_device");
         dedup_seqs_device = (decltype(dedup_seqs_device))sym("umi_dedup_seqs_device");
+        if (want_edit) dedup_batch_edit = (decltype(dedup_batch_edit))sym("umi_dedup_batch_edit");
         if (want_consensus) {
             consensus_seqs = (decltype(consensus_seqs))sym("umi_consensus_seqs");
             consensus_seqs_device = (decltype(consensus_seqs_device))sym("umi_consensus_seqs_device");
@@ -297,6 +323,11 @@ void usage()
               "  -m, --mode <MODE>        Either fastq or SAM/BAM mode [default: bam]; fastq: whole reads\n"
               "                           (<= 256 bases) are the key, one bucket per read length\n"
               "  -k <K>                   Number of substitution edits to allow [default: 1]\n"
+              "      --distance <D>       hamming or edit [default: hamming]: the distance -k bounds.  edit is the\n"
+              "                           Levenshtein distance (substitution, insertion, deletion cost 1 each), which\n"
+              "                           sees a UMI shifted by a lost or gained base; between UMIs of one length an\n"
+              "                           indel costs 2, so -k 0 and -k 1 give the hamming result and the flag matters\n"
+              "                           from -k 2 (bam/sam mode, one GPU, UMIs of at most 21 bases)\n"
               "  -u <UMI_LENGTH>          The UMI length [default: 0 = autodetect]; fastq: bases trimmed\n"
               "                           from the start of every written read\n"
               "  -p <PERCENTAGE>          Directional threshold percentage [default: 0.5]\n"
@@ -372,6 +403,11 @@ Cli parse(int argc, char **argv)
         else if (a == "--num-threads") c.num_threads = (unsigned)std::atoi(need(i));
         else if (a == "--umi_sep") c.umi_sep = (uint8_t)std::atoi(need(i)); // a number, cli.rs:31-32
         else if (a == "--algo") c.algo = need(i);
+        else if (a == "--distance") {
+            const std::string d = need(i);
+            if (d != "hamming" && d != "edit") die("--distance wants hamming or edit: '" + d + "'");
+            c.edit_distance = d == "edit";
+        }
         else if (a == "--merge") c.merge = need(i);
         else if (a == "--data") c.data = need(i);
         else if (a == "--two-pass") c.two_pass = true;
@@ -1349,6 +1385,8 @@ void run_two_pass(const Cli &args, int algo, int merge, HipLib &lib, const std::
     const bool gpu_stage = args.stage != "host" && !args.paired && umi_length >= 1;
     if (args.stage == "gpu" && !gpu_stage) die("--stage gpu does not go with --paired, --tag or --dump-staging");
     const int n_words = umi_length ? (int)((3 * umi_length + 63) / 64) : 1;
+    if (args.edit_distance && umi_length > UMI_MAX_UMI_LEN)
+        die("--distance edit takes UMIs of at most 21 bases (this file's have " + std::to_string(umi_length) + ")");
 
     // ---- pass 2
     struct ReadRef {
@@ -1531,9 +1569,9 @@ void run_two_pass(const Cli &args, int algo, int merge, HipLib &lib, const std::
         std::vector<uint8_t> kept(ne + 1, 0);
         umi_stats st;
         std::memset(&st, 0, sizeof(st));
-        if (lib.dedup_batch(ctx, keys.data(), any_n ? nmask.data() : nullptr, n_words, freq.data(), off.data(), nb,
-                            (int)umi_length, args.k, args.percentage, algo, 0 /* adjacency.rs:56 */, kept.data(), nullptr,
-                            &st) != UMI_OK)
+        if (lib.dedup(ctx, keys.data(), any_n ? nmask.data() : nullptr, n_words, freq.data(), off.data(), nb,
+                      (int)umi_length, args.k, args.percentage, algo, 0 /* adjacency.rs:56 */, kept.data(), nullptr,
+                      &st) != UMI_OK)
             die(lib.last_error());
         t_hot += now_s() - t0;
         n_total += ne;
@@ -1638,6 +1676,7 @@ void run_two_pass(const Cli &args, int algo, int merge, HipLib &lib, const std::
     std::fprintf(stderr, "Average number of UMIs per alignment position: %g\n", nb_total ? (double)n_total / (double)nb_total : 0.0);
     std::fprintf(stderr, "Max number of UMIs over all alignment positions: %zu\n", max_umi);
     std::fprintf(stderr, "Number of reads after deduplicating: %llu\n", (unsigned long long)n_kept);
+    if (args.edit_distance) std::fprintf(stderr, "UMI distance: edit\n");
     std::fprintf(stderr, "two-pass: %llu windows, at most %llu reads held\n", (unsigned long long)n_windows,
                  (unsigned long long)peak);
     std::fprintf(stderr,
@@ -1671,6 +1710,12 @@ int main(int argc, char **argv)
     if (args.umi_whitelist.empty() && (args.wl_max_given || args.wl_min_given || !args.whitelist_metrics.empty()))
         die("--whitelist-max-mismatches, --whitelist-min-distance and --whitelist-metrics go with --umi-whitelist only");
     if (args.mode != "bam" && args.mode != "sam" && args.mode != "fastq") return 0; // main.rs:49-95: nothing happens
+    // --distance edit: everything about it that can be refused is, before the GPU is woken
+    if (args.edit_distance) {
+        if (args.mode == "fastq") die("--distance edit is defined in bam/sam mode only (whole reads are the key in fastq mode)");
+        if (args.devices.size() > 1) die("--distance edit runs on one GPU: --devices takes one id with it");
+        if (args.umi_length > UMI_MAX_UMI_LEN) die("--distance edit takes UMIs of at most 21 bases (-u " + std::to_string(args.umi_length) + ")");
+    }
     // --umi-whitelist: everything about it that can be refused is, before the GPU is woken
     std::vector<uint8_t> whitelist;
     if (!args.umi_whitelist.empty()) {
@@ -1682,6 +1727,8 @@ int main(int argc, char **argv)
         if (args.umi_length != 0 && args.umi_length != wl_len)
             die("-u " + std::to_string(args.umi_length) + " does not go with a whitelist of UMIs of " + std::to_string(wl_len) +
                 " bases");
+        if (args.edit_distance && wl_len > UMI_MAX_UMI_LEN)
+            die("--distance edit takes UMIs of at most 21 bases (the whitelist's have " + std::to_string(wl_len) + ")");
         args.umi_length = wl_len; // (a read whose UMI is of another length ends the run, as with -u)
     }
     if (args.track_clusters && args.paired) die("--tag with --paired is not implemented (the reference never reaches its tagging pass)");
@@ -1709,6 +1756,7 @@ int main(int argc, char **argv)
     HipLib lib;
     lib.want_correct = !whitelist.empty();
     lib.want_consensus_bam = args.call_consensus;
+    lib.want_edit = args.edit_distance;
     std::future<umi_ctx *> warm;
     std::string warm_error;
     if (!args.passthrough && args.dump_staging.empty())
@@ -2042,6 +2090,8 @@ int main(int argc, char **argv)
         size_t n = 0, nb = 0, max_umi = 0;
         bool any_n = false;
         const int n_words = umi_length ? (int)((3 * umi_length + 63) / 64) : 1; // words per key (bitset.rs:17-18)
+        if (args.edit_distance && umi_length > UMI_MAX_UMI_LEN)
+            die("--distance edit takes UMIs of at most 21 bases (this file's have " + std::to_string(umi_length) + ")");
         // (not zeroed when sized: the staging call writes them)
         std::vector<uint64_t, umi::bgzf::default_init_allocator<uint64_t>> keys, nmask, off; // keys / nmask: n_words words per entry
         std::vector<int32_t, umi::bgzf::default_init_allocator<int32_t>> freq;
@@ -2249,9 +2299,9 @@ int main(int argc, char **argv)
             // The reference accepts every --data value and always runs Naive
             // (deduplicate_sam.rs:210-213): the result -- and here the path -- is the same for all of them.
             t_gpu0 = now_s();
-            if (lib.dedup_batch(ctx, keys.data(), any_n ? nmask.data() : nullptr, n_words, freq.data(), off.data(), nb,
-                                (int)umi_length, args.k, args.percentage, algo, 0 /* adjacency.rs:56 */,
-                                kept.data(), need_clusters ? root.data() : nullptr, &st) != UMI_OK)
+            if (lib.dedup(ctx, keys.data(), any_n ? nmask.data() : nullptr, n_words, freq.data(), off.data(), nb,
+                          (int)umi_length, args.k, args.percentage, algo, 0 /* adjacency.rs:56 */,
+                          kept.data(), need_clusters ? root.data() : nullptr, &st) != UMI_OK)
                 die(lib.last_error());
             t_gpu1 = now_s();
         }
@@ -2519,6 +2569,7 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "Max number of UMIs over all alignment positions: %zu\n", max_umi);
         std::fprintf(stderr, args.track_clusters ? "Number of groups of reads: %llu\n" : "Number of reads after deduplicating: %llu\n",
                      (unsigned long long)st.n_kept); // :259-266
+        if (args.edit_distance) std::fprintf(stderr, "UMI distance: edit\n");
         if (args.call_consensus) {
             std::fprintf(stderr, "Number of clusters below --call-consensus-min-reads: %zu\n", cons.n_below);
             std::fprintf(stderr, "Number of clusters without a consensus: %zu\n", cons.n_without);
