@@ -405,6 +405,47 @@ int umi_correct_umis(umi_ctx *ctx, const uint8_t *umi_ascii, uint64_t n_reads, i
                      const uint8_t *whitelist_ascii, uint32_t n_wl, int max_mismatches, int min_distance,
                      uint8_t *out_ascii, int32_t *match, uint8_t *best, uint8_t *second, uint64_t counts[3]);
 
+/* ---- correction of cell barcodes to a kit's list (the program's --cell-whitelist): every read's barcode and
+ *      its single substitutions looked up in an index of the list, on the GPU.  No counterpart in the
+ *      reference; the rule is STARsolo's 1MM.  Where umi_correct_umis compares every read with every entry
+ *      (right for 10^2 to 10^5 UMIs), this call costs a read one probe when its barcode is listed and
+ *      3 bc_len otherwise, whatever the list's size (10x lists: 737,280 and 6,794,880 barcodes).
+ * in : n_reads barcodes of bc_len bytes each, back to back, every byte one of ACGTN (the pointer needs no
+ *      alignment); whitelist_ascii: n_wl different barcodes of the same length, every byte one of ACGT, a
+ *      HOST array in both forms.  max_mismatches is 0 or 1.  An N of a read differs from every listed base.
+ * out: per read status[i] (may be NULL) and match[i]:
+ *        UMI_BARCODE_EXACT      the barcode is listed; match = its index
+ *        UMI_BARCODE_CORRECTED  not exact, max_mismatches 1, exactly one listed barcode differs in exactly
+ *                               one position; match = its index
+ *        UMI_BARCODE_NONE       no listed barcode within max_mismatches; match = -1
+ *        UMI_BARCODE_AMBIGUOUS  not exact, max_mismatches 1, two or more listed barcodes differ in exactly
+ *                               one position; match = -1
+ *      counts (host): the reads of each status, counts[status].  match is what umi_correct_umis gives with
+ *      the same max_mismatches and min_distance 1.
+ * n_reads == 0: UMI_OK, counts all zero, nothing else touched.  A multi-device context uses its first
+ * device.  A deferred call (umi_dedup_batch_device_begin) that is out on the context ends first; its result
+ * keeps waiting for umi_dedup_batch_end.
+ * UMI_ERR_ARG: n_wl == 0 or above 2^24, a NULL among ctx, the barcodes, the list, match and counts,
+ * max_mismatches outside 0..1, bc_len outside 1..32, n_reads >= 2^30, a listed barcode that occurs twice
+ * ("duplicate entry in the barcode whitelist: entry <index> equals an earlier one", the smallest such index,
+ * found on the device while the index is built).  UMI_ERR_CHAR: a listed byte outside ACGT ("Unknown
+ * character in whitelist: <byte> (entry <index>)", found on the host before anything is launched), or a
+ * read byte outside ACGTN -- a pass of its own over the reads finds the smallest such read before anything
+ * is written: "Unknown character in cell barcode: <byte> (read <index>)".  After any refusal the outputs
+ * are as they were.  The _device form takes and leaves the per-read arrays in device memory and
+ * synchronises the stream (twice: after the index and the check, at the end); the plain form copies host
+ * arrays in and out around it. */
+#define UMI_BARCODE_EXACT 0
+#define UMI_BARCODE_CORRECTED 1
+#define UMI_BARCODE_NONE 2
+#define UMI_BARCODE_AMBIGUOUS 3
+int umi_correct_barcodes_device(umi_ctx *ctx, const uint8_t *d_bc_ascii, uint64_t n_reads, int bc_len,
+                                const uint8_t *whitelist_ascii, uint32_t n_wl, int max_mismatches, int32_t *d_match,
+                                uint8_t *d_status, uint64_t counts[4], void *hip_stream);
+int umi_correct_barcodes(umi_ctx *ctx, const uint8_t *bc_ascii, uint64_t n_reads, int bc_len,
+                         const uint8_t *whitelist_ascii, uint32_t n_wl, int max_mismatches, int32_t *match,
+                         uint8_t *status, uint64_t counts[4]);
+
 /* ---- batched path: replaces the whole bucket loop
  *      src/deduplicate_sam.rs:207-233 (apply::<UcSAMRead,Naive> per bucket,
  *      counters :217-219) = Directional/Adjacency::apply

@@ -104,6 +104,10 @@ SIGNATURES = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_void_p]),
     "umi_correct_umis": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, C.c_int, _u8p, C.c_uint32, C.c_int, C.c_int, _u8p,
                                    _i32p, _u8p, _u8p, _u64p]),
+    "umi_correct_barcodes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, _u8p, C.c_uint32, C.c_int,
+                                              C.c_void_p, C.c_void_p, _u64p, C.c_void_p]),
+    "umi_correct_barcodes": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, C.c_int, _u8p, C.c_uint32, C.c_int, _i32p, _u8p,
+                                       _u64p]),
     "umi_dedup_batch": (C.c_int, [C.c_void_p, _u64p, _u64p, _i32p, _u64p, C.c_uint64, C.c_int,
                                   C.c_int, C.c_float, C.c_int, C.c_int32, _u8p, _u32p,
                                   C.POINTER(Stats)]),

@@ -391,6 +391,34 @@ class Context:
                                              d_best or None, d_second or None, ptr(counts, C.c_uint64), stream or None))
         return counts
 
+    def correct_barcodes(self, bc_bytes, bc_len, whitelist, max_mismatches=1):
+        """Cell barcodes snapped to a kit's list by an indexed lookup (umi_correct_barcodes): bc_bytes uint8
+        [n * bc_len], whitelist a list of str/bytes or a uint8 array, without duplicates.  Returns dict(match
+        int32 [n] (-1: none or ambiguous), status uint8 [n] (0 exact, 1 corrected, 2 none, 3 ambiguous), counts
+        uint64 [4], by status)."""
+        bc_bytes = np.ascontiguousarray(bc_bytes, dtype=np.uint8).reshape(-1)
+        if bc_len < 1 or bc_bytes.size % bc_len:
+            raise ValueError("bc_bytes is not a whole number of barcodes")
+        n = bc_bytes.size // bc_len
+        wl, n_wl = self._whitelist_bytes(whitelist, bc_len)
+        m = max(1, n)
+        match, status = np.zeros(m, np.int32), np.zeros(m, np.uint8)
+        counts = np.zeros(4, np.uint64)
+        check(load().umi_correct_barcodes(self._h, ptr(bc_bytes, C.c_uint8), n, bc_len, ptr(wl, C.c_uint8), n_wl,
+                                          max_mismatches, ptr(match, C.c_int32), ptr(status, C.c_uint8),
+                                          ptr(counts, C.c_uint64)))
+        return {"match": match[:n], "status": status[:n], "counts": counts}
+
+    def correct_barcodes_device(self, d_bc, n_reads, bc_len, whitelist, max_mismatches, d_match, d_status=0, stream=0):
+        """The same on raw device pointers (umi_correct_barcodes_device; the whitelist stays on the host): fills
+        d_match and, where given, d_status; returns counts uint64 [4]."""
+        wl, n_wl = self._whitelist_bytes(whitelist, bc_len)
+        counts = np.zeros(4, np.uint64)
+        check(load().umi_correct_barcodes_device(self._h, d_bc or None, n_reads, bc_len, ptr(wl, C.c_uint8), n_wl,
+                                                 max_mismatches, d_match or None, d_status or None,
+                                                 ptr(counts, C.c_uint64), stream or None))
+        return counts
+
     def stage_reads(self, align_key, umi_bytes, score, umi_len, merge=1, align_key_bits=64):
         """Read staging on the device (host arrays in and out): reads in file order ->
         dict(keys, nmask, freq, rep, bucket_off) in canonical order, the batched path's input

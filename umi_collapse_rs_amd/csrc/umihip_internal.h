@@ -423,6 +423,21 @@ int correct_on_device(void *workspace, const uint8_t *d_umi, uint32_t n_reads, i
                       uint8_t *d_second, uint64_t counts[3], uint64_t *bad_read, uint32_t n_cus, unsigned long long *h_pinned,
                       hipStream_t s);
 
+// ---- correction of cell barcodes to a kit's list (umihip_barcode.hip: umi_correct_barcodes) ----
+// The list is packed on the host, 2 bits per base in one 64-bit word per entry (barcode_pack_list: 1 and
+// *bad_entry at a byte outside ACGT), indexed on the device (a table of barcode_table_slots(n_wl) slots)
+// and looked up by every read and its single substitutions.  d_status may be null.  h_pinned: 8 pinned
+// words.  0 ok; 1 a read byte outside ACGTN (*bad: the smallest such read); 2 a listed barcode that occurs
+// twice (*bad: the smallest entry that equals an earlier one) -- nothing was written in either case;
+// negative: -(hipError_t)
+constexpr int BARCODE_MAX_LEN = 32;
+int barcode_pack_list(const uint8_t *ascii, uint32_t n_wl, int bc_len, uint64_t *packed, uint64_t *bad_entry);
+uint32_t barcode_table_slots(uint32_t n_wl);
+size_t barcode_workspace_bytes(uint32_t n_wl);
+int barcode_on_device(void *workspace, const uint8_t *d_bc, uint32_t n_reads, int bc_len, const uint64_t *h_packed, uint32_t n_wl,
+                      int max_mismatches, int32_t *d_match, uint8_t *d_status, uint64_t counts[4], uint64_t *bad, uint32_t n_cus,
+                      unsigned long long *h_pinned, hipStream_t s);
+
 // ---- sort and scan primitives of the staging (umihip_radix.hip) ----
 constexpr int RADIX_BINS = 256, RADIX_MAX_PASSES = 8; // 8-bit digits; a 64-bit key has at most eight
 constexpr int RADIX_HIST_PARTS = 2048;                // blocks of a kernel that counts digits, at most

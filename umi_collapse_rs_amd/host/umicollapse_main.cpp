@@ -71,6 +71,21 @@
 // listed UMI.  Refused before the GPU is woken: fastq mode, --two-pass, --dump-staging, --passthrough, another
 // -u, the other three flags alone, a list that is empty, of mixed lengths, with a byte outside ACGT, with a
 // duplicate, or of more than 85 bases.
+// --cell-whitelist FILE (with --per-cell; STARsolo's 1MM rule, not the reference's, tests/barcode_model.py defines
+// it): the kit's cell barcodes, one per line, for files whose barcode tag is raw (--cell-tag CR).  The barcodes
+// of the reads that would be staged go through umi_correct_barcodes in one call -- an indexed lookup of the
+// barcode and its single substitutions, not a comparison with every entry -- after the per-read pass and
+// before the barcodes are numbered: a listed barcode stands for itself, an unlisted one with exactly one
+// listed barcode one substitution away (--cell-whitelist-max-mismatches 1, the default; 0: none) for that
+// one, and a cell's id is the rank of first appearance of the corrected barcode.  Reads whose barcode is
+// unlisted or ambiguous are dropped like reads without a barcode, not written, and counted ("Number of reads
+// with a corrected / an unlisted / an ambiguous cell barcode", printed with the flag only).  The tag's value
+// must have the list's length and bytes from ACGTN, else the run ends with status 101.  Written records are
+// the input's bytes.  --cell-whitelist-metrics FILE: barcode, reads, exact, corrected per listed barcode that
+// took a read.  Refused before the GPU is woken: without --per-cell, fastq mode, --two-pass, --dump-staging,
+// --passthrough, the two other flags alone, a mismatch bound other than 0 or 1, a list that is empty, of mixed
+// lengths, with a byte outside ACGT (Cell Ranger's "-1" suffix included), with a duplicate, or of more than 32
+// bases.
 // --call-consensus (bam/sam mode, one pass; not the reference's, tests/bam_consensus_model.py defines it): the
 // same records in the same order, but of each kept record the sequence and the qualities are its cluster's
 // consensus.  A cluster is a kept entry with every entry it removed, as for --tag; its voters are its reads
@@ -154,6 +169,10 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     std::string umi_whitelist;     // --umi-whitelist FILE: every UMI is snapped to the nearest listed one first
     std::string whitelist_metrics; // --whitelist-metrics FILE: reads, exact, corrected per listed UMI
     int wl_max_mismatches = 1, wl_min_distance = 1; // --whitelist-max-mismatches, --whitelist-min-distance
+    std::string cell_whitelist;         // --cell-whitelist FILE: cell barcodes are snapped to the kit's list first
+    std::string cell_whitelist_metrics; // --cell-whitelist-metrics FILE: reads, exact, corrected per listed barcode
+    int cell_wl_max_mismatches = 1;     // --cell-whitelist-max-mismatches: 0 or 1
+    bool cell_wl_max_given = false;
     bool wl_max_given = false, wl_min_given = false;
     bool edit_distance = false; // --distance edit: -k bounds the Levenshtein distance (umi_dedup_batch_edit)
 };
@@ -226,6 +245,10 @@ struct HipLib {
     bool want_correct = false;
     int (*correct_umis)(umi_ctx *, const uint8_t *, uint64_t, int, const uint8_t *, uint32_t, int, int, uint8_t *, int32_t *,
                         uint8_t *, uint8_t *, uint64_t *) = nullptr;
+    // --cell-whitelist: likewise
+    bool want_barcodes = false;
+    int (*correct_barcodes)(umi_ctx *, const uint8_t *, uint64_t, int, const uint8_t *, uint32_t, int, int32_t *, uint8_t *,
+                            uint64_t *) = nullptr;
     // (the HIP runtime the library brings along: device buffers for the arrays above)
     int (*hip_set_device)(int) = nullptr; // (the current device is per thread: the context was made on another)
     int (*hip_malloc)(void **, size_t) = nullptr;
@@ -267,6 +290,7 @@ struct HipLib {
         }
         if (want_consensus_bam) consensus_bam = (decltype(consensus_bam))sym("umi_consensus_bam");
         if (want_correct) correct_umis = (decltype(correct_umis))sym("umi_correct_umis");
+        if (want_barcodes) correct_barcodes = (decltype(correct_barcodes))sym("umi_correct_barcodes");
         hip_set_device = (decltype(hip_set_device))sym("hipSetDevice");
         hip_malloc = (decltype(hip_malloc))sym("hipMalloc");
         hip_memcpy = (decltype(hip_memcpy))sym("hipMemcpy");
@@ -372,6 +396,15 @@ void usage()
               "      --whitelist-max-mismatches <M> a UMI matches a listed one at up to M mismatches [default: 1]\n"
               "      --whitelist-min-distance <D> ... if the next best listed UMI is at least D further away [default: 1]\n"
               "      --whitelist-metrics <FILE> write a table: umi, reads, exact, corrected per listed UMI, in list order\n"
+              "      --cell-whitelist <FILE> with --per-cell: the kit's cell barcodes, one per line (ACGT, all of one\n"
+              "                           length, at most 32 bases, no -1 suffix; blank lines and lines starting with #\n"
+              "                           skipped): every read's barcode (--cell-tag CR for raw ones) is looked up in an\n"
+              "                           index of the list on the GPU; an unlisted barcode one substitution from exactly\n"
+              "                           one listed barcode counts as that one; reads with an unlisted or ambiguous\n"
+              "                           barcode are dropped; written records keep their own bytes (bam/sam mode, one pass)\n"
+              "      --cell-whitelist-max-mismatches <M> 0: listed barcodes only; 1: one substitution allowed [default: 1]\n"
+              "      --cell-whitelist-metrics <FILE> write a table: barcode, reads, exact, corrected per listed barcode\n"
+              "                           that took a read, in list order\n"
               "      --device <ID>        GPU to use [default: 0]\n"
               "      --devices <ID,..>    several GPUs of the node: alignment positions are sharded over them");
 }
@@ -444,6 +477,14 @@ Cli parse(int argc, char **argv)
             if (end == v || *end != '\0' || m < 0 || m > INT32_MAX) die(a + " wants a number, 0 or more");
             if (a == "--whitelist-max-mismatches") { c.wl_max_mismatches = (int)m; c.wl_max_given = true; }
             else { c.wl_min_distance = (int)m; c.wl_min_given = true; }
+        }
+        else if (a == "--cell-whitelist") c.cell_whitelist = need(i);
+        else if (a == "--cell-whitelist-metrics") c.cell_whitelist_metrics = need(i);
+        else if (a == "--cell-whitelist-max-mismatches") {
+            const std::string v = need(i);
+            if (v != "0" && v != "1") die(a + " wants 0 or 1: '" + v + "'");
+            c.cell_wl_max_mismatches = v == "1";
+            c.cell_wl_max_given = true;
         }
         else if (a == "--consensus") c.consensus = true;
         else if (a == "--consensus-min-reads") {
@@ -647,10 +688,12 @@ size_t detect_length(const Cli &args, const umi::bam::Record &r, const ReadTags 
 
 // --umi-whitelist: the listed UMIs back to back; their length in umi_len.  One UMI per line, blank lines and
 // lines that start with # skipped; anything a kit's list cannot be ends the run.
-std::vector<uint8_t> read_whitelist(const std::string &path, size_t &umi_len)
+// (--cell-whitelist reads its list the same way: `list_name` and `item` are what the messages call them)
+std::vector<uint8_t> read_whitelist(const std::string &path, size_t &umi_len, const std::string &list_name = "UMI whitelist",
+                                    const std::string &item = "UMI", size_t max_len = UMI_MAX_WIDE_UMI_LEN)
 {
     FILE *f = std::fopen(path.c_str(), "rb");
-    if (!f) die("cannot open the UMI whitelist " + path);
+    if (!f) die("cannot open the " + list_name + " " + path);
     std::string text;
     char buf[1 << 16];
     for (size_t got; (got = std::fread(buf, 1, sizeof(buf), f)) > 0;) text.append(buf, got);
@@ -667,19 +710,18 @@ std::vector<uint8_t> read_whitelist(const std::string &path, size_t &umi_len)
         line_no++;
         while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
         if (line.empty() || line[0] == '#') continue;
-        const std::string where = "UMI whitelist " + path + ", line " + std::to_string(line_no) + ": ";
-        if (line.size() > UMI_MAX_WIDE_UMI_LEN)
-            die(where + std::to_string(line.size()) + " bases, more than " + std::to_string(UMI_MAX_WIDE_UMI_LEN));
+        const std::string where = list_name + " " + path + ", line " + std::to_string(line_no) + ": ";
+        if (line.size() > max_len) die(where + std::to_string(line.size()) + " bases, more than " + std::to_string(max_len));
         for (char ch : line)
             if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T')
                 die(where + "a character outside ACGT: " + std::to_string((unsigned)(uint8_t)ch));
         if (umi_len && line.size() != umi_len)
-            die(where + std::to_string(line.size()) + " bases, the UMIs before it have " + std::to_string(umi_len));
+            die(where + std::to_string(line.size()) + " bases, the " + item + "s before it have " + std::to_string(umi_len));
         if (!seen.insert(line).second) die(where + "duplicate entry " + line);
         umi_len = line.size();
         list.insert(list.end(), line.begin(), line.end());
     }
-    if (list.empty()) die("the UMI whitelist " + path + " holds no UMI");
+    if (list.empty()) die("the " + list_name + " " + path + " holds no " + item);
     return list;
 }
 
@@ -1731,6 +1773,18 @@ int main(int argc, char **argv)
             die("--distance edit takes UMIs of at most 21 bases (the whitelist's have " + std::to_string(wl_len) + ")");
         args.umi_length = wl_len; // (a read whose UMI is of another length ends the run, as with -u)
     }
+    // --cell-whitelist: likewise
+    if (args.cell_whitelist.empty() && (args.cell_wl_max_given || !args.cell_whitelist_metrics.empty()))
+        die("--cell-whitelist-max-mismatches and --cell-whitelist-metrics go with --cell-whitelist only");
+    std::vector<uint8_t> cell_list;
+    size_t cell_len = 0;
+    if (!args.cell_whitelist.empty()) {
+        if (args.mode == "fastq") die("--cell-whitelist does not go with fastq mode (there are no tags there)");
+        if (!args.per_cell) die("--cell-whitelist goes with --per-cell only");
+        if (args.two_pass) die("--cell-whitelist does not go with --two-pass (its census would need the correction too)");
+        if (!args.dump_staging.empty() || args.passthrough) die("--cell-whitelist does not go with --dump-staging or --passthrough");
+        cell_list = read_whitelist(args.cell_whitelist, cell_len, "cell barcode whitelist", "barcode", 32);
+    }
     if (args.track_clusters && args.paired) die("--tag with --paired is not implemented (the reference never reaches its tagging pass)");
     int algo, merge;
     if (args.algo == "dir") algo = UMI_ALGO_DIRECTIONAL;
@@ -1755,6 +1809,7 @@ int main(int argc, char **argv)
     // whoever needs the context first waits for this thread.
     HipLib lib;
     lib.want_correct = !whitelist.empty();
+    lib.want_barcodes = !cell_list.empty();
     lib.want_consensus_bam = args.call_consensus;
     lib.want_edit = args.edit_distance;
     std::future<umi_ctx *> warm;
@@ -1869,6 +1924,7 @@ int main(int argc, char **argv)
                            // 4 mate unmapped, 5 filtered (--remove-unpaired / --remove-chimeric),
                            // 6 dropped: it lacks a tag of --umi-tag / --per-cell (`missing` says which)
                            // 7 dropped: its UMI matches no listed one (--umi-whitelist)
+                           // 8 dropped: its cell barcode is unlisted or ambiguous (--cell-whitelist)
             uint8_t unpaired, chimeric, missing;
             uint32_t umi_at; // offset of the UMI from the read name (a --umi-tag value lies behind it)
             uint32_t cell;   // --per-cell: the barcode's id, the thread's own during the per-read pass
@@ -1913,6 +1969,8 @@ int main(int argc, char **argv)
         // --per-cell: every thread numbers the barcodes of its reads in order of appearance; the numbers are
         // made global (first appearance in the file) below.  A few thousand to 10^5 barcodes: the tables stay
         // in cache.
+        umi::bgzf::Bytes cell_raw; // --cell-whitelist: per record, a staged read's barcode as the tag has it
+        if (!cell_list.empty()) cell_raw.resize((size_t)n_rec * cell_len);
         std::vector<std::unordered_map<std::string_view, uint32_t>> cell_ids(args.per_cell ? T : 0);
         std::vector<std::vector<std::string_view>> cell_seen(args.per_cell ? T : 0);
         U64s gkey; // GPU staging with --per-cell: every read's cell id, the group key
@@ -1952,7 +2010,23 @@ int main(int argc, char **argv)
                     if (first_error[t] == UINT32_MAX) { first_error[t] = ri; errors[t] = err; }
                     continue;
                 }
-                if (args.per_cell) {
+                if (!cell_list.empty()) { // (numbered after the correction, below)
+                    bool acgtn = tg.cell.size() == cell_len;
+                    for (const char ch : tg.cell) acgtn = acgtn && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T' || ch == 'N');
+                    if (!acgtn) {
+                        ii.state = 2;
+                        if (first_error[t] == UINT32_MAX) {
+                            first_error[t] = ri;
+                            const std::string name((const char *)r.qname(), r.qname_len());
+                            errors[t] = tg.cell.size() != cell_len
+                                            ? "cell barcode tag " + args.cell_tag + " of read " + name + " holds " +
+                                                  std::to_string(tg.cell.size()) + " bases, not " + std::to_string(cell_len)
+                                            : "Unknown character in cell barcode tag " + args.cell_tag + " of read " + name;
+                        }
+                        continue;
+                    }
+                    std::memcpy(&cell_raw[(size_t)ri * cell_len], tg.cell.data(), cell_len);
+                } else if (args.per_cell) {
                     const auto id = cell_ids[t].emplace(tg.cell, (uint32_t)cell_seen[t].size());
                     if (id.second) cell_seen[t].push_back(tg.cell);
                     ii.cell = id.first->second;
@@ -1978,7 +2052,74 @@ int main(int argc, char **argv)
         for (unsigned t = 0; t < T; t++) // the reference panics at the first offending read
             if (first_error[t] != UINT32_MAX) die(errors[t]);
         size_t n_cells = 0;
-        if (args.per_cell) { // the threads' barcode numbers -> ranks of first appearance in the file
+        umi_ctx *ctx = nullptr;
+        double t_init = 0.0;
+        auto need_ctx = [&]() { // (t_init: what of the GPU's start-up was left to wait for)
+            if (ctx) return;
+            const double t0 = now_s();
+            if (warm.valid()) {
+                ctx = warm.get();
+                if (!ctx) die(warm_error);
+            } else {
+                if (!lib.load()) die(lib.error);
+                if (lib.ctx_create_multi(args.devices.data(), (int)args.devices.size(), &ctx) != UMI_OK) die(lib.last_error());
+            }
+            t_init += now_s() - t0;
+        };
+        // --cell-whitelist: the barcodes of the reads that would be staged, looked up in the list's index in one
+        // call; a read whose barcode is unlisted or ambiguous is dropped like one without the tag, and the
+        // others are numbered by their corrected barcode (rank of first appearance in the file)
+        uint64_t cb_counts[4] = {0, 0, 0, 0};
+        if (!cell_list.empty()) {
+            std::vector<uint32_t> cand;
+            for (uint32_t ri = 0; ri < n_rec; ri++)
+                if (info[ri].state == 0) cand.push_back(ri);
+            const size_t nc = cand.size(), L = cell_len, n_wl = cell_list.size() / L;
+            umi::bgzf::Bytes raw(nc * L);
+            const size_t per = (nc + T - 1) / T;
+            umi::bgzf::parallel_for(T, T, [&](size_t t) {
+                for (size_t j = t * per; j < std::min(nc, (t + 1) * per); j++)
+                    std::memcpy(&raw[j * L], &cell_raw[(size_t)cand[j] * L], L);
+            });
+            std::vector<int32_t> cb_match(nc);
+            std::vector<uint8_t> cb_status(nc);
+            if (nc) {
+                need_ctx();
+                if (lib.correct_barcodes(ctx, raw.data(), nc, (int)L, cell_list.data(), (uint32_t)n_wl, args.cell_wl_max_mismatches,
+                                         cb_match.data(), cb_status.data(), cb_counts) != UMI_OK)
+                    die(lib.last_error());
+            }
+            std::vector<uint32_t> id_of(n_wl, UINT32_MAX); // listed barcode -> cell id
+            uint32_t next_id = 0;
+            for (size_t j = 0; j < nc; j++) {
+                ReadInfo &ii = info[cand[j]];
+                if (cb_match[j] < 0) {
+                    ii.state = 8;
+                    continue;
+                }
+                uint32_t &id = id_of[(size_t)cb_match[j]];
+                if (id == UINT32_MAX) id = next_id++;
+                ii.cell = id;
+                if (gpu_stage) gkey[cand[j]] = id;
+            }
+            n_cells = next_id;
+            if (!args.cell_whitelist_metrics.empty()) { // per listed barcode that took a read, in list order
+                std::vector<uint64_t> exact(n_wl, 0), corrected(n_wl, 0);
+                for (size_t j = 0; j < nc; j++)
+                    if (cb_match[j] >= 0) (cb_status[j] == 0 ? exact : corrected)[(size_t)cb_match[j]]++;
+                FILE *f = std::fopen(args.cell_whitelist_metrics.c_str(), "wb");
+                if (!f) die("cannot open " + args.cell_whitelist_metrics);
+                std::fprintf(f, "barcode\treads\texact\tcorrected\n");
+                for (size_t w = 0; w < n_wl; w++)
+                    if (exact[w] + corrected[w])
+                        std::fprintf(f, "%.*s\t%llu\t%llu\t%llu\n", (int)L, (const char *)&cell_list[w * L],
+                                     (unsigned long long)(exact[w] + corrected[w]), (unsigned long long)exact[w],
+                                     (unsigned long long)corrected[w]);
+                if (std::fclose(f) != 0) die("cannot write " + args.cell_whitelist_metrics);
+            }
+            lap("cell whitelist");
+        }
+        if (args.per_cell && cell_list.empty()) { // the threads' barcode numbers -> ranks of first appearance in the file
             std::unordered_map<std::string_view, uint32_t> global;
             std::vector<std::vector<uint32_t>> to_global(T);
             for (unsigned t = 0; t < T; t++)
@@ -1994,20 +2135,6 @@ int main(int argc, char **argv)
                     }
             });
         }
-        umi_ctx *ctx = nullptr;
-        double t_init = 0.0;
-        auto need_ctx = [&]() { // (t_init: what of the GPU's start-up was left to wait for)
-            if (ctx) return;
-            const double t0 = now_s();
-            if (warm.valid()) {
-                ctx = warm.get();
-                if (!ctx) die(warm_error);
-            } else {
-                if (!lib.load()) die(lib.error);
-                if (lib.ctx_create_multi(args.devices.data(), (int)args.devices.size(), &ctx) != UMI_OK) die(lib.last_error());
-            }
-            t_init += now_s() - t0;
-        };
         // --umi-whitelist: the UMIs of the reads that would be staged, snapped to the list in one call; a read
         // that matches no listed UMI is dropped like one without its tag, the others go on with the listed
         // UMI's bytes in place of their own (either staging below sees only those)
@@ -2558,6 +2685,11 @@ int main(int argc, char **argv)
         }
         if (!args.umi_tag.empty()) std::fprintf(stderr, "Number of reads without a UMI tag: %zu\n", no_umi_tag);
         if (args.per_cell) std::fprintf(stderr, "Number of reads without a cell barcode: %zu\n", no_cell);
+        if (!cell_list.empty()) {
+            std::fprintf(stderr, "Number of reads with a corrected cell barcode: %llu\n", (unsigned long long)cb_counts[1]);
+            std::fprintf(stderr, "Number of reads with an unlisted cell barcode: %llu\n", (unsigned long long)cb_counts[2]);
+            std::fprintf(stderr, "Number of reads with an ambiguous cell barcode: %llu\n", (unsigned long long)cb_counts[3]);
+        }
         if (!whitelist.empty()) {
             std::fprintf(stderr, "Number of reads with a corrected UMI: %llu\n", (unsigned long long)wl_counts[1]);
             std::fprintf(stderr, "Number of reads with an uncorrectable UMI: %llu\n", (unsigned long long)wl_counts[2]);
