@@ -122,6 +122,9 @@ const char *umi_last_error(void);
  *                    their symmetric pairs united in LDS by a kernel of their own, ahead of the pair kernel
  *                    (0: every sub-bucket through the pair kernel); same result and statistics
  *   "seg_local_cap"  2..2048 (default 512): largest part-0 sub-bucket that kernel takes (LDS: 16 bytes per entry)
+ *   "collapse_kept_only" 0/1 (default 1): a batched directional call without d_root leaves the union-find
+ *                    forest unflattened: only the endpoints of the one-way pairs are followed to their
+ *                    roots, and the mask is read off parent[] and lab[] (0: flatten as a call with d_root does)
  *   "seg_ckey"       0/1 (default 1): the pair kernel compares 3-bit-per-base compare keys where the bases
  *                    outside a bin fit 32 bits (0: the 2-bit filter keys)
  *   "seg_sliced"     0/1 (default 1): ... 64 columns of a tile at a time, from wave ballots of the columns'

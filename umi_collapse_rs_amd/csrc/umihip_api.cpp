@@ -211,6 +211,7 @@ struct umi_ctx {
     uint32_t seg_local_cap = SEG_LOCAL_CAP; // of their own, ahead of the pair kernel (batched directional path)
     int seg_local_occ[2] = {0, 0}; // its resident blocks per CU (without / with N) at seg_local_occ_cap
     uint32_t seg_local_occ_cap = 0;
+    bool collapse_kept_only = true; // a batched directional call without root[] skips the forest flatten (umihip_collapse.hip)
     uint32_t seg_blocks = 0; // one-wave blocks of its pair kernel (0: all resident at once -- 24 per CU by
                              // registers, 28 by LDS with the compare keys' leaner loop)
     // workspace
@@ -1216,6 +1217,9 @@ class Pipeline {
         d.n = n;
         d.kept = d_kept;
         d.root = d_root;
+        // (label[] then holds the unflattened forest when the call ends: nobody reads it across calls, every
+        // call's prep / launch_iota writes its entries afresh)
+        d.kept_only = d_root == nullptr && ctx->collapse_kept_only;
         d.counters = d_cnt;
         d.changed = ctx->d_changed();
         if (priv_blocks_for_collapse) {
@@ -1254,7 +1258,9 @@ class Pipeline {
                 HIP_TRY(launch_collapse_flatten(cd, s));
                 // (the last of them as a check beside the finalize pass: in the common case it would change
                 // nothing, and the kept mask stands)
-                for (int r = 0; r < ahead - 1; r++) HIP_TRY(launch_collapse_round(cd, r, s));
+                // (kept_only: round 0 resolves the one-way pairs' endpoints for the rounds and the check behind it)
+                static_assert(DAG_ROUNDS >= 2, "the check beside finalize needs a resolving round ahead of it");
+                for (int r = 0; r < ahead - 1; r++) HIP_TRY(launch_collapse_round(cd, r, s, r == 0));
                 HIP_TRY(launch_collapse_finalize(cd, s, ahead - 1));
             } else { // no pair of this call reaches the edge list: every entry outside the fused buckets survives
                 HIP_TRY(launch_finalize(d_label, d_ranges, (uint32_t)pl.ranges.size(), n, d_kept, d_root, d_cnt, s));
@@ -1289,7 +1295,8 @@ class Pipeline {
         for (int r = 0; have_pairs && r < ahead; r++) rounds += (r == 0 || ctx->h_changed()[r - 1]) ? 1 : 0;
         const int rounds_first = rounds;
         if (have_pairs && ctx->h_changed()[ahead - 1]) { // a deeper chain of one-way pairs than that
-            // (comp[] is flat and lab[] only ever falls: the rounds go on where the first ones stopped)
+            // (comp[] is flat -- kept_only: the list holds roots -- and lab[] only ever falls: the rounds go on
+            // where the first ones stopped; their index restarts at 0 here, and none of them resolves again)
             const CollapseDesc cd = collapse_desc();
             if ((rc = run_rounds(ctx, s, [&](uint32_t *, int r) { return launch_collapse_round(cd, r, s); }, rounds, 4)))
                 return rc;
@@ -1992,6 +1999,8 @@ int umi_ctx_set_option(umi_ctx *ctx, const char *name, int64_t value)
         ctx->seg_lds = value != 0;
     } else if (!strcmp(name, "seg_local")) {
         ctx->seg_local = value != 0;
+    } else if (!strcmp(name, "collapse_kept_only")) {
+        ctx->collapse_kept_only = value != 0;
     } else if (!strcmp(name, "seg_local_cap")) {
         if (value < 2 || value > SEG_LOCAL_MAX_CAP) return fail(UMI_ERR_ARG, "seg_local_cap must be in 2..%u", SEG_LOCAL_MAX_CAP);
         ctx->seg_local_cap = (uint32_t)value;

@@ -36,15 +36,26 @@ __global__ __launch_bounds__(256) void uf_union_kernel(const uint2 *__restrict__
 // blocks leave them, 4,096 private slots, instead of moving them to the list first saved two small
 // launches and cost the first round 47 us instead of 13: a slot per wave means 2,000 waves, and every
 // one of them sends its own atomic for the giant component's word.)
+//
+// kept_only (the caller wants the mask and no root[]): the flatten is only there for root[].  lab[c] <= c
+// (identity, then atomicMin) and comp[i] <= i (parents are smaller than children), so an entry that
+// is not the root of its set has lab[comp[i]] <= comp[i] < i and is not kept whatever its root is,
+// and a root is kept iff lab[i] == i: kept[i] = parent[i] == i && lab[i] == i, two streams over the
+// forest as the unions left it.  Only the endpoints of the one-way pairs need their roots: the first
+// round finds them by climbing (read only: no union runs behind the pair kernels in stream order) and
+// writes each pair back to its slot as (root of u, root of v); the rounds after it, the check and the
+// host's continuation read lab[] at the stored endpoints.
 struct CollapseArgs {
-    uint32_t *parent;       // in: the forest; out: comp[v] = root of v's set (flat)
+    uint32_t *parent;       // in: the forest; out: comp[v] = root of v's set (flat; kept_only: left as it is)
     uint32_t *lab;          // lab[c] = smallest set that reaches set c along one-way pairs
-    const uint2 *edges;     // the list (one-way pairs and, flagged, symmetric ones: skipped here)
+    const uint2 *edges;     // the list (one-way pairs and, flagged, symmetric ones: skipped here);
+                            // kept_only: the resolving round rewrites the one-way pairs in place
     uint32_t edge_cap;
     const RangeTask *ranges; // the entries the collapse covers (the fused kernel finished the others); null: all n
     uint32_t n_ranges, n;
     uint8_t *kept;
     uint32_t *root;          // may be null
+    bool kept_only;          // only kept[] is asked for (root is null): the forest is never flattened, see above
     unsigned long long *counters;
     uint32_t *changed;       // [MAX_ROUNDS_PER_SYNC] round r moved a label
     const uint2 *priv_edges; // the pair kernel's private slots (may be null), priv_blocks of SEG_PRIV_CAP edges
@@ -60,15 +71,16 @@ __device__ __forceinline__ uint32_t list_length(const CollapseArgs &a)
     return ne < a.edge_cap ? (uint32_t)ne : a.edge_cap;
 }
 
-template <class F> __device__ __forceinline__ void collapse_entries(const CollapseArgs &a, F f)
+// f(i) for the entries of ranges (null: all n), by the first n_blocks blocks of the grid
+template <class F> __device__ __forceinline__ void collapse_entries(const CollapseArgs &a, uint32_t n_blocks, F f)
 {
     if (a.ranges) {
-        for (uint32_t r = blockIdx.x; r < a.n_ranges; r += gridDim.x) {
+        for (uint32_t r = blockIdx.x; r < a.n_ranges; r += n_blocks) {
             const RangeTask rt = a.ranges[r];
             for (uint32_t i = rt.start + threadIdx.x; i < rt.end; i += blockDim.x) f(i);
         }
     } else {
-        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += gridDim.x * blockDim.x) f(i);
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += n_blocks * blockDim.x) f(i);
     }
 }
 
@@ -97,19 +109,49 @@ __device__ __forceinline__ void flatten_entry(uint32_t *parent, uint32_t *lab, u
 // (the count is on the device): the fewer waves, the more of a hot word's hooks meet in one wave's
 // registers.
 // Returns whether this thread saw a label to move.  Every lane of a wave makes the same trips.
+//
+// RESOLVE (kept_only's first round): the pair's endpoints are climbed to their roots in the unflattened
+// forest -- both climbs in one loop, two loads in flight per step; plain loads: the forest does not
+// change any more -- and the pair goes back to its own slot as (cu, cv) with one 8-byte store.  Flagged
+// entries and whatever lies at or beyond edge_cap are left alone.  A pair that is resolved a second time
+// stays what it is (a root is its own root).  PER_THREAD: the trips a thread makes when the list is
+// at least as long as the grid covers; each is a chain of dependent loads, and the climbs make it
+// long, so the resolving round spreads the list over more waves than the others.
+template <bool RESOLVE, uint32_t PER_THREAD>
 __device__ __forceinline__ bool one_way_round(const CollapseArgs &a)
 {
     const uint32_t E = list_length(a);
-    constexpr uint32_t PER_BLOCK = 256 * 8;
+    constexpr uint32_t PER_BLOCK = 256 * PER_THREAD;
     const uint32_t active = min(gridDim.x, (E + PER_BLOCK - 1) / PER_BLOCK);
     bool any = false;
     HotMin hot;
-    auto pair = [&](uint2 uv) {
+    auto pair = [&](uint32_t e, uint2 uv) {
         bool todo = false;
         uint32_t cv = 0, lu = 0;
         if (!(uv.x & SYM_FLAG)) {
-            const uint32_t cu = a.parent[uv.x];
-            cv = a.parent[uv.y];
+            uint32_t cu;
+            if (RESOLVE) {
+                cu = uv.x;
+                cv = uv.y;
+                uint32_t pu = a.parent[cu], pv = a.parent[cv];
+                while (pu != cu || pv != cv) {
+                    if (pu != cu) {
+                        cu = pu;
+                        pu = a.parent[cu];
+                    }
+                    if (pv != cv) {
+                        cv = pv;
+                        pv = a.parent[cv];
+                    }
+                }
+                const_cast<uint2 *>(a.edges)[e] = make_uint2(cu, cv);
+            } else if (a.kept_only) { // resolved by the round before
+                cu = uv.x;
+                cv = uv.y;
+            } else {
+                cu = a.parent[uv.x];
+                cv = a.parent[uv.y];
+            }
             lu = a.lab[cu];
             todo = lu < a.lab[cv];
         }
@@ -119,7 +161,7 @@ __device__ __forceinline__ bool one_way_round(const CollapseArgs &a)
     if (blockIdx.x < active)
         for (uint32_t e0 = blockIdx.x * blockDim.x; e0 < E; e0 += active * blockDim.x) {
             const uint32_t e = e0 + threadIdx.x;
-            pair(e < E ? a.edges[e] : make_uint2(SYM_FLAG, 0u));
+            pair(e, e < E ? a.edges[e] : make_uint2(SYM_FLAG, 0u));
         }
     hot_flush(a.lab, hot);
     return any;
@@ -134,13 +176,20 @@ __device__ __forceinline__ bool one_way_check(const CollapseArgs &a, uint32_t fi
     bool any = false;
     for (uint32_t e = me * blockDim.x + threadIdx.x; e < E; e += n_blocks * blockDim.x) {
         const uint2 uv = a.edges[e];
-        if (!(uv.x & SYM_FLAG)) any |= a.lab[a.parent[uv.x]] < a.lab[a.parent[uv.y]];
+        if (uv.x & SYM_FLAG) continue;
+        any |= a.kept_only ? a.lab[uv.x] < a.lab[uv.y] // (resolved: a resolving round always runs ahead of the check)
+                           : a.lab[a.parent[uv.x]] < a.lab[a.parent[uv.y]];
     }
     return any;
 }
 
 __device__ __forceinline__ unsigned int finalize_entry(const CollapseArgs &a, uint32_t i)
 {
+    if (a.kept_only) { // no gather: an entry below its root is not kept, a root is if nothing reaches it
+        const bool kp = a.parent[i] == i && a.lab[i] == i;
+        a.kept[i] = kp ? 1 : 0;
+        return kp ? 1u : 0u;
+    }
     const uint32_t l = a.lab[a.parent[i]]; // label[v] = lab[comp[v]] (directional.rs:30-54,78-88)
     const bool kp = l == i;                // (deduplicate_sam.rs:217-231)
     a.kept[i] = kp ? 1 : 0;
@@ -160,7 +209,14 @@ __device__ __forceinline__ unsigned int finalize_entry(const CollapseArgs &a, ui
 __global__ __launch_bounds__(256) void dag_flat_hook_kernel(CollapseArgs a, int round)
 {
     if (round > 0 && a.changed[round - 1] == 0) return;
-    if (one_way_round(a)) a.changed[round] = 1;
+    if (one_way_round<false, 8>(a)) a.changed[round] = 1;
+}
+
+// kept_only's first round (always runs: the rounds and the check behind it read what it stores)
+constexpr uint32_t RESOLVE_PER_THREAD = 2;
+__global__ __launch_bounds__(256) void dag_resolve_hook_kernel(CollapseArgs a, int round)
+{
+    if (one_way_round<true, RESOLVE_PER_THREAD>(a)) a.changed[round] = 1;
 }
 
 // The private slots to the list, 64 slots per block (blocks behind the flatten pass's own, in the same
@@ -200,13 +256,18 @@ __device__ __forceinline__ void gather_private_edges(const CollapseArgs &a, uint
     __syncthreads();
     const unsigned long long first = a.counters[CNT_EDGES] + wsum[0] + wsum[1] + wsum[2] + wsum[3];
     uint2 *list = const_cast<uint2 *>(a.edges);
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (uint32_t j = wave; s0 + j < s1; j += blockDim.x >> 6) {
-        const uint32_t cnt = pre[j + 1] - pre[j];
-        for (uint32_t i = lane; i < cnt; i += 64) {
-            const unsigned long long pos = first + pre[j] + i;
-            if (pos < a.edge_cap) list[pos] = a.priv_edges[(size_t)(s0 + j) * SEG_PRIV_CAP + i];
+    // a thread per edge of the group, its slot by bisection of pre[]: a slot holds a handful of edges, and a
+    // wave that walks its sixteen slots one after the other makes sixteen dependent trips to memory (with
+    // the flatten's entry part gone from the launch, kept_only, it took 21 us that way and takes 16 so)
+    for (uint32_t t = threadIdx.x; t < pre[GATHER_SLOTS]; t += blockDim.x) {
+        uint32_t lo = 0, hi = GATHER_SLOTS; // pre[lo] <= t < pre[hi]
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (pre[mid] <= t) lo = mid;
+            else hi = mid;
         }
+        const unsigned long long pos = first + t;
+        if (pos < a.edge_cap) list[pos] = a.priv_edges[(size_t)(s0 + lo) * SEG_PRIV_CAP + (t - pre[lo])];
     }
     if (s1 == a.priv_blocks && threadIdx.x == 0) a.counters[CNT_EDGES_MOVED] = first + pre[GATHER_SLOTS] - a.counters[CNT_EDGES];
 }
@@ -215,6 +276,10 @@ __global__ __launch_bounds__(256) void uf_flatten_kernel(CollapseArgs a, uint32_
 {
     if (blockIdx.x >= entry_blocks) {
         gather_private_edges(a, blockIdx.x - entry_blocks);
+        return;
+    }
+    if (a.kept_only) { // lab[] = identity and nothing else: parent[] is neither read nor written
+        collapse_entries(a, entry_blocks, [&](uint32_t i) { a.lab[i] = i; });
         return;
     }
     if (a.ranges) {
@@ -241,7 +306,31 @@ __global__ __launch_bounds__(256) void map_finalize_kernel(CollapseArgs a, uint3
         return;
     }
     unsigned int cnt = 0;
-    if (a.ranges) {
+    if (a.kept_only && !a.ranges) {
+        // two streams in, one out: a quarter of the other path's blocks (one add to CNT_KEPT each), a thread's
+        // four entries loaded before the first byte is stored (kept[] may alias anything for the compiler).
+        // Measured at config 2: 11.6 us, where the entry-by-entry loop over 2,048 blocks took 11.4 and the
+        // path with the gather 12.2 -- neither the gather nor the adds are what this pass waits for
+        const uint32_t stride = entry_blocks * blockDim.x;
+        for (uint32_t i0 = blockIdx.x * blockDim.x + threadIdx.x; i0 < a.n; i0 += 4 * stride) {
+            uint32_t p[4], l[4];
+#pragma unroll
+            for (uint32_t u = 0; u < 4; u++) {
+                const uint32_t i = i0 + u * stride;
+                p[u] = i < a.n ? a.parent[i] : 0xFFFFFFFFu;
+                l[u] = i < a.n ? a.lab[i] : 0xFFFFFFFFu;
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < 4; u++) {
+                const uint32_t i = i0 + u * stride;
+                if (i < a.n) {
+                    const bool kp = p[u] == i && l[u] == i;
+                    a.kept[i] = kp ? 1 : 0;
+                    cnt += kp ? 1u : 0u;
+                }
+            }
+        }
+    } else if (a.ranges) {
         for (uint32_t r = blockIdx.x; r < a.n_ranges; r += entry_blocks) {
             const RangeTask rt = a.ranges[r];
             for (uint32_t i = rt.start + threadIdx.x; i < rt.end; i += blockDim.x) cnt += finalize_entry(a, i);
@@ -285,6 +374,7 @@ CollapseArgs collapse_args(const CollapseDesc &d)
     a.n = d.n;
     a.kept = d.kept;
     a.root = d.root;
+    a.kept_only = d.kept_only;
     a.counters = d.counters;
     a.changed = d.changed;
     a.priv_edges = d.priv_edges;
@@ -336,16 +426,20 @@ hipError_t launch_collapse_flatten(const CollapseDesc &d, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_collapse_round(const CollapseDesc &d, int round, hipStream_t s)
+hipError_t launch_collapse_round(const CollapseDesc &d, int round, hipStream_t s, bool resolve)
 {
-    dag_flat_hook_kernel<<<grid_of(d.edge_cap, 256 * 8, 512), 256, 0, s>>>(collapse_args(d), round);
+    if (resolve && d.kept_only)
+        dag_resolve_hook_kernel<<<grid_of(d.edge_cap, 256 * RESOLVE_PER_THREAD, 4096 / RESOLVE_PER_THREAD), 256, 0, s>>>(
+            collapse_args(d), round);
+    else
+        dag_flat_hook_kernel<<<grid_of(d.edge_cap, 256 * 8, 512), 256, 0, s>>>(collapse_args(d), round);
     return hipGetLastError();
 }
 
 hipError_t launch_collapse_finalize(const CollapseDesc &d, hipStream_t s, int check_round)
 {
     if (d.n == 0 || (d.ranges && d.n_ranges == 0)) return hipSuccess;
-    const uint32_t entry_blocks = entries_grid(d, 2048);
+    const uint32_t entry_blocks = entries_grid(d, d.kept_only && !d.ranges ? 512 : 2048);
     const uint32_t check_blocks = check_round >= 0 ? grid_of(d.edge_cap, 256 * 8, 256) : 0u;
     map_finalize_kernel<<<entry_blocks + check_blocks, 256, 0, s>>>(collapse_args(d), entry_blocks, check_round);
     return hipGetLastError();

@@ -481,6 +481,8 @@ struct CollapseDesc {
     uint32_t n_ranges, n;
     uint8_t *kept;
     uint32_t *root;
+    bool kept_only = false;  // root is null and only kept[] is wanted: no flatten; the first round resolves the one-way
+                             // pairs' endpoints to roots in place, finalize reads parent[i] and lab[i] only
     unsigned long long *counters;
     uint32_t *changed;       // the rounds' flags in the control block
     // what the segment index's pair kernel left in its blocks' private slots (one-way pairs only: the
@@ -494,10 +496,12 @@ struct CollapseDesc {
 // h_seq (pinned, may be null): set to seq once the block has arrived
 hipError_t launch_control_to_host(const void *d_ctrl, void *h_ctrl, size_t bytes, hipStream_t s,
                                   unsigned long long *h_seq = nullptr, unsigned long long seq = 0);
-// ... phase by phase: comp[v] = root of v in place and lab[v] = v; round `round` along the
-// one-way pairs (a no-op once round - 1 was quiet); label = lab[comp[v]], kept, root, survivors
+// ... phase by phase: comp[v] = root of v in place and lab[v] = v (kept_only: lab[v] = v alone); round `round`
+// along the one-way pairs (a no-op once round - 1 was quiet); label = lab[comp[v]], kept, root, survivors
 hipError_t launch_collapse_flatten(const CollapseDesc &d, hipStream_t s);
-hipError_t launch_collapse_round(const CollapseDesc &d, int round, hipStream_t s);
+// resolve (kept_only; ignored otherwise): this round also rewrites the one-way pairs as (root, root).  The first
+// round behind launch_collapse_flatten must; a later one that does is harmless (a root resolves to itself)
+hipError_t launch_collapse_round(const CollapseDesc &d, int round, hipStream_t s, bool resolve = false);
 // check_round >= 0: blocks of their own look, without a store, whether round check_round would still
 // move a label (changed[check_round])
 hipError_t launch_collapse_finalize(const CollapseDesc &d, hipStream_t s, int check_round = -1);
