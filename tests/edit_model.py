@@ -244,3 +244,22 @@ def shift_only_pairs(umis, k, d_e=None):
     d_e = edit_matrix(umis) if d_e is None else d_e
     d_h = hamming_matrix(umis)
     return int((np.triu((d_e <= k) & (d_h > k), 1)).sum())
+
+
+SIZES = (1, 2, 63, 64, 65, 129, 600)
+_batches = {}
+
+
+def batch(L, n_frac):
+    """One call's buckets -- every size of SIZES (fewer entries where the alphabet runs out), empty buckets in
+    between -- with their distance matrices, made once per (L, n_frac)."""
+    key = (L, n_frac)
+    if key not in _batches:
+        rng = np.random.default_rng(7000 + 100 * L + int(1000 * n_frac))
+        buckets = []
+        for n in SIZES:
+            buckets.append(shifted_bucket(rng, n, L, n_frac=n_frac, n_max=n))
+            buckets.append(([], []))
+        mats = [edit_matrix(u) for u, _ in buckets]
+        _batches[key] = (buckets, mats, pack(buckets))
+    return _batches[key]

@@ -5,10 +5,11 @@ import numpy as np
 import pytest
 
 import edit_model as em
+from edit_model import batch
 
 pytestmark = pytest.mark.gpu
 
-SIZES = (1, 2, 63, 64, 65, 129, 600)
+SIZES = em.SIZES
 LENGTHS = (1, 2, 6, 12, 20, 21)
 
 
@@ -18,24 +19,6 @@ def ctx():
     c = umi.Context(0)
     yield c
     c.close()
-
-
-_batches = {}
-
-
-def batch(L, n_frac):
-    """One call's buckets -- every size of SIZES (fewer entries where the alphabet runs out), empty buckets in
-    between -- with their distance matrices, made once per (L, n_frac)."""
-    key = (L, n_frac)
-    if key not in _batches:
-        rng = np.random.default_rng(7000 + 100 * L + int(1000 * n_frac))
-        buckets = []
-        for n in SIZES:
-            buckets.append(em.shifted_bucket(rng, n, L, n_frac=n_frac, n_max=n))
-            buckets.append(([], []))
-        mats = [em.edit_matrix(u) for u, _ in buckets]
-        _batches[key] = (buckets, mats, em.pack(buckets))
-    return _batches[key]
 
 
 def dev(a):

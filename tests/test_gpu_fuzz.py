@@ -5,33 +5,9 @@ import numpy as np
 import pytest
 
 import oracle as orc
-from helpers import usable
+from helpers import clustered_bucket, usable
 
 pytestmark = pytest.mark.gpu
-ALPHA = np.frombuffer(b"ACGT", dtype=np.uint8)
-
-
-def clustered_bucket(rng, n_target, L, n_frac):
-    """~n_target distinct UMIs: a few centres with many 1-2 error neighbours + random ones."""
-    out = {}
-    centres = rng.choice(ALPHA, (max(1, n_target // 40), L))
-    while len(out) < n_target:
-        if rng.random() < 0.7:
-            u = centres[rng.integers(len(centres))].copy()
-            for _ in range(int(rng.integers(0, 3))):
-                u[rng.integers(L)] = rng.choice(ALPHA)
-        else:
-            u = rng.choice(ALPHA, L)
-        if n_frac and rng.random() < n_frac:
-            u[rng.integers(L)] = ord("N")
-        s = u.tobytes()
-        out[s] = out.get(s, 0) + int(rng.geometric(0.4))
-        if len(out) >= 4 ** L - 1 and L < 6:
-            break
-    umis = list(out.keys())
-    freq = np.array([out[u] for u in umis])
-    order = np.lexsort((np.arange(len(umis)), -freq))
-    return [umis[i].decode() for i in order], freq[order].tolist()
 
 
 @pytest.mark.parametrize("seed", range(30))

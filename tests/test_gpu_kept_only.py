@@ -3,10 +3,12 @@
 With option collapse_kept_only (default 1) such a call skips the flatten of the union-find forest: the
 first round follows the endpoints of the one-way pairs to their roots and rewrites the pairs in place, the
 rounds after it, the check beside finalize and the host's continuation read the rewritten pairs, and the
-mask is parent[i] == i && lab[i] == i.  Every other GPU test asks for root and so runs the flattening
-path; this file runs the other one.  Every case asserts that kept and n_kept equal the CPU oracle's, the
-same context's call with want_root = True, and a context with collapse_kept_only = 0, which must also
-report the same n_edges and n_candidates.  Inputs: tests/kept_only_inputs.py (checked on the CPU in
+mask is parent[i] == i && lab[i] == i.  This file runs that path on hand-made chains and a few small
+buckets; tests/test_gpu_kept_only_matrix.py takes it through the other entry points, options and kinds
+of input with the same assertions (the rest of the suite asks for root and runs the flattening path).
+Every case asserts that kept and n_kept equal the CPU oracle's, the same context's call with
+want_root = True, and a context with collapse_kept_only = 0; all three calls must report the same
+n_edges and n_candidates.  Inputs: tests/kept_only_inputs.py (checked on the CPU in
 tests/test_kept_only_inputs_cpu.py)."""
 import contextlib
 
@@ -38,23 +40,29 @@ def same_mask(what, got, n_kept, exp):
     assert n_kept == int(exp.sum()), (what, n_kept, int(exp.sum()))
 
 
+def check_mask(run, ref, what, ctx, old):
+    """The common assertions on run(ctx, want_root) -> (kept, root or None, stats) against the reference mask ref;
+    ctx / old: contexts with collapse_kept_only on / off.  Returns the stats of the want_root = False call."""
+    kept, root, st = run(ctx, False)
+    assert root is None
+    same_mask(what + ": against the reference", kept, st["n_kept"], ref)
+    kept_r, root_r, st_r = run(ctx, True)
+    assert root_r is not None
+    same_mask(what + ": the call with root", kept_r, st_r["n_kept"], kept)
+    kept_o, _, st_o = run(old, False)
+    same_mask(what + ": collapse_kept_only=0", kept_o, st_o["n_kept"], kept)
+    for other in (st_r, st_o):
+        assert other["n_edges"] == st["n_edges"] and other["n_candidates"] == st["n_candidates"], (what, st, other)
+    return st
+
+
 def check(batch, opts, what, ctx=None, old=None):
-    """The common assertions; returns the stats of the want_root = False call.  ctx / old: contexts to go on
-    with (kept-only on / off); made and closed here otherwise."""
+    """check_mask on a Batch against the oracle.  ctx / old: contexts to go on with (kept-only on / off); made and
+    closed here otherwise."""
     with contextlib.ExitStack() as es:
         ctx = ctx or es.enter_context(context(opts))
         old = old or es.enter_context(context(dict(opts, collapse_kept_only=0)))
-        okept = batch.reference()
-        kept, root, st = batch.run(ctx, want_root=False)
-        assert root is None
-        same_mask(what + ": against the oracle", kept, st["n_kept"], okept)
-        kept_r, root_r, st_r = batch.run(ctx, want_root=True)
-        assert root_r is not None
-        same_mask(what + ": the call with root", kept_r, st_r["n_kept"], kept)
-        kept_o, _, st_o = batch.run(old, want_root=False)
-        same_mask(what + ": collapse_kept_only=0", kept_o, st_o["n_kept"], kept)
-        assert st_o["n_edges"] == st["n_edges"] and st_o["n_candidates"] == st["n_candidates"], (what, st, st_o)
-        return st
+        return check_mask(batch.run, batch.reference(), what, ctx, old)
 
 
 LIST_OPTS = [dict(fused_max=0)] + [dict(fused_max=0, seg_min=2, seg_unite=a, seg_local=b) for a in (0, 1) for b in (0, 1)]
