@@ -122,6 +122,11 @@ const char *umi_last_error(void);
  *                    their symmetric pairs united in LDS by a kernel of their own, ahead of the pair kernel
  *                    (0: every sub-bucket through the pair kernel); same result and statistics
  *   "seg_local_cap"  2..2048 (default 512): largest part-0 sub-bucket that kernel takes (LDS: 16 bytes per entry)
+ *   "seg_probe"      0/1 (default 1): k = 1 without N: in the sub-buckets that kernel takes, where at most six
+ *                    bases lie outside the bins, the pairs are decided by lookups in a bitmap of the
+ *                    sub-bucket instead of being compared one by one (0: the tile walk); same result and
+ *                    statistics
+ *   "seg_probe_min"  2..2048 (default 129): smallest sub-bucket decided by lookups
  *   "collapse_kept_only" 0/1 (default 1): a batched directional call without d_root leaves the union-find
  *                    forest unflattened: only the endpoints of the one-way pairs are followed to their
  *                    roots, and the mask is read off parent[] and lab[] (0: flatten as a call with d_root does)

@@ -209,6 +209,9 @@ struct umi_ctx {
     int seg_occ[2][2][2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};
     bool seg_local = true;   // part-0 sub-buckets of at most seg_local_cap entries united in LDS by a kernel
     uint32_t seg_local_cap = SEG_LOCAL_CAP; // of their own, ahead of the pair kernel (batched directional path)
+    bool seg_probe = true;   // ... k = 1 without N: their pairs decided by bitmap lookups where at most
+                             // SEG_PROBE_MAX_REST bases lie outside the bins (0: the tile walk)
+    uint32_t seg_probe_min = SEG_PROBE_MIN; // smallest sub-bucket decided by lookups
     int seg_local_occ[2] = {0, 0}; // its resident blocks per CU (without / with N) at seg_local_occ_cap
     uint32_t seg_local_occ_cap = 0;
     bool collapse_kept_only = true; // a batched directional call without root[] skips the forest flatten (umihip_collapse.hip)
@@ -719,6 +722,12 @@ class Pipeline {
                 seg.local_cap = ctx->seg_local_cap;
                 seg_local_bins = 0;
                 for (const SegDesc &sd : pl.segs) seg_local_bins += 1ull << (2 * sd.nb[0]);
+                // k = 1 without N: inside a bin every pair within k differs in one base outside the bin's own,
+                // and no two entries agree there (with N folded onto A they could)
+                if (ctx->seg_probe && k == 1 && !d_nmask) {
+                    seg.probe_rest = SEG_PROBE_MAX_REST;
+                    seg.probe_min = ctx->seg_probe_min;
+                }
             }
             if (ctx->seg_lds && pl.seg_max_bins <= SEG_LDS_BINS && !pl.seg_blocks.empty()) {
                 seg.blocks = d_seg_blocks;
@@ -1999,6 +2008,12 @@ int umi_ctx_set_option(umi_ctx *ctx, const char *name, int64_t value)
         ctx->seg_lds = value != 0;
     } else if (!strcmp(name, "seg_local")) {
         ctx->seg_local = value != 0;
+    } else if (!strcmp(name, "seg_probe")) {
+        if (value != 0 && value != 1) return fail(UMI_ERR_ARG, "seg_probe must be 0 or 1");
+        ctx->seg_probe = value != 0;
+    } else if (!strcmp(name, "seg_probe_min")) {
+        if (value < 2 || value > SEG_LOCAL_MAX_CAP) return fail(UMI_ERR_ARG, "seg_probe_min must be in 2..%u", SEG_LOCAL_MAX_CAP);
+        ctx->seg_probe_min = (uint32_t)value;
     } else if (!strcmp(name, "collapse_kept_only")) {
         ctx->collapse_kept_only = value != 0;
     } else if (!strcmp(name, "seg_local_cap")) {

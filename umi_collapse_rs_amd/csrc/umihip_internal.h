@@ -266,6 +266,10 @@ struct SegArgs {
     // part-0 sub-buckets of 2..local_cap entries are seg_local_kernel's (united in LDS, launched ahead of
     // the pair kernel): the scan gives them no tile tasks.  0: every sub-bucket is the pair kernel's.
     uint32_t local_cap;
+    // k = 1, no N in the call: where part 0 leaves at most probe_rest bases outside its bins, the local
+    // kernel decides its sub-buckets of at least probe_min entries by bitmap lookups instead of the tile walk
+    // (SEG_PROBE_MAX_REST, or 0: every sub-bucket is walked)
+    uint32_t probe_rest, probe_min;
 };
 // exclusive scan of the bin counts -> bin_start, task list, counters[CNT_SEG_TASKS / _PAIRS];
 // then every entry of a segment is copied to its position in each part's sub-bucket order
@@ -285,6 +289,12 @@ hipError_t launch_seg_edge_append(const PairArgs &a, const SegArgs &g, uint32_t 
 // before any kernel unites through g.uf_parent: a launch of its own, ahead of the pair kernel.
 constexpr uint32_t SEG_LOCAL_MAX_CAP = 2048;
 constexpr uint32_t SEG_LOCAL_CAP = 512; // default cap (LDS: 16 bytes per entry + the hit queue)
+// Lookups instead of pairs (k = 1, no N): inside a sub-bucket whose part leaves rest <= SEG_PROBE_MAX_REST
+// bases outside its bins an entry is the 2 * rest bits of those bases, the sub-bucket a bitmap of 4^rest
+// bits in LDS, and an entry's partners within one substitution are 3 * rest single-bit tests.
+constexpr int SEG_PROBE_MAX_REST = 6;                                       // 4,096 bits: 512 bytes
+constexpr uint32_t SEG_PROBE_WORDS = (1u << (2 * SEG_PROBE_MAX_REST)) / 32; // words of the bitmap
+constexpr uint32_t SEG_PROBE_MIN = 129; // smallest sub-bucket decided by lookups (up to three tiles: the tile walk)
 size_t seg_local_lds_bytes(uint32_t cap);
 int seg_local_blocks_per_cu(bool has_n, uint32_t cap);
 hipError_t launch_seg_local(const PairArgs &a, const SegArgs &g, float percentage, uint32_t n_blocks, hipStream_t s);

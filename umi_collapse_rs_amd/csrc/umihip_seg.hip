@@ -22,6 +22,11 @@ namespace {
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_PER_THREAD = SEG_SCAN_CHUNK / SCAN_THREADS; // 16 bins per thread
 
+// a part whose bins are indexed by nb bases has its sub-buckets decided by lookups (seg_local_kernel)
+__device__ __forceinline__ bool probe_part(const SegArgs &g, uint32_t nb)
+{
+    return g.probe_rest != 0u && g.umi_len - (int)nb <= (int)g.probe_rest;
+}
 // (a part-0 sub-bucket the local kernel takes has no tile tasks)
 __device__ __forceinline__ bool local_bin(const SegArgs &g, uint32_t part, uint32_t c) { return part == 0 && c <= g.local_cap; }
 __device__ __forceinline__ uint32_t tasks_of_bin(const SegArgs &g, uint32_t part, uint32_t c)
@@ -882,6 +887,25 @@ __device__ __forceinline__ void lds_union(uint32_t *par, uint32_t u, uint32_t v)
     }
 }
 
+// ---- lookups instead of pairs (k = 1, no N in the call) ------------------------------------------------
+// A part that leaves rest <= SEG_PROBE_MAX_REST bases outside its bins: inside a sub-bucket an entry is the
+// 2 * rest bits of those bases (its rest-code s, the low two bits of every 3-bit group of the compare key,
+// in base order), two entries are within one substitution exactly when their rest-codes differ in one
+// base, and so an entry has 3 * rest possible partners, s ^ (d << 2 b) for b < rest, d = 1..3, each one bit
+// of a 4^rest-bit map of the sub-bucket.  The bin's records are put in the order of their rest-codes (the
+// rank of a code in the bitmap: a prefix of the words' popcounts plus the popcount of the bits below it),
+// so that the position of a partner follows from its code and a pair is found once, at its smaller
+// position.  The hits go through the same queue and drain as those of the tile walk.  Two entries with one
+// rest-code -- a key twice in the input -- show when the map is built (a returning OR): that bin is walked
+// by tiles, where such a pair is a hit of distance 0.
+__device__ __forceinline__ uint32_t rest_code(uint32_t ck)
+{
+    uint32_t s = 0;
+#pragma unroll
+    for (int b = 0; b < SEG_PROBE_MAX_REST; b++) s |= ((ck >> (3 * b)) & 3u) << (2 * b);
+    return s;
+}
+
 template <bool HAS_N>
 __global__ __launch_bounds__(64) void seg_local_kernel(PairArgs a, SegArgs g, float percentage)
 {
@@ -889,6 +913,7 @@ __global__ __launch_bounds__(64) void seg_local_kernel(PairArgs a, SegArgs g, fl
     const uint32_t cap = g.local_cap;
     uint32_t *ck = lds, *ix = lds + cap, *fr = lds + 2 * cap, *par = lds + 3 * cap;
     uint32_t *hitq = lds + 4 * cap; // row position | column position << 16
+    uint32_t *bm = hitq + LOCAL_HITQ, *pre = bm + SEG_PROBE_WORDS; // the bin's bitmap, set bits before each word
     const int lane = threadIdx.x;
     const SegRec32 *__restrict__ sub = (const SegRec32 *)g.sub_rec;
     const bool sliced = a.k <= 3 && g.col_sliced != 0;
@@ -955,17 +980,25 @@ __global__ __launch_bounds__(64) void seg_local_kernel(PairArgs a, SegArgs g, fl
         nq = 0;
         __syncthreads();
     };
+    // one hit per lane and round into the queue
+    auto push = [&](bool has, uint32_t h) {
+        const unsigned long long bal = __ballot(has);
+        if (has) hitq[nq + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1ull))] = h;
+        nq += (uint32_t)__builtin_popcountll(bal);
+        if (nq >= LOCAL_DRAIN_AT) drain();
+    };
 
     const uint32_t n_ids = g.n_chunks * SEG_SCAN_CHUNK;
     for (uint32_t id = blockIdx.x; id < n_ids; id += gridDim.x) {
         const SegScanChunk ch = g.chunks[id / SEG_SCAN_CHUNK];
         const uint32_t bi = id % SEG_SCAN_CHUNK;
         if (ch.part != 0 || bi >= ch.nbins) continue;
+        const uint32_t nb = g.segs[ch.seg].nb[0];
         const uint32_t b = ch.bin0 + bi;
         const uint32_t c = __builtin_amdgcn_readfirstlane(g.bin_cnt[b]); // (the scatter's cursor: the count again)
         if (c < 2 || c > cap) continue;
         const uint32_t start = __builtin_amdgcn_readfirstlane(g.bin_start[b]);
-        const int ck_bases = __builtin_amdgcn_readfirstlane(g.umi_len - (int)g.segs[ch.seg].nb[0]);
+        const int ck_bases = __builtin_amdgcn_readfirstlane(g.umi_len - (int)nb);
         for (uint32_t p = lane; p < c; p += 64) {
             const SegRec32 r = sub[start + p];
             ck[p] = r.ckey;
@@ -974,36 +1007,100 @@ __global__ __launch_bounds__(64) void seg_local_kernel(PairArgs a, SegArgs g, fl
             par[p] = p;
         }
         __syncthreads();
-        // the upper triangle: 64-row chunks against the columns behind their first row
-        for (uint32_t row0 = 0; row0 < c; row0 += 64) {
-            const uint32_t r = row0 + (uint32_t)lane;
-            const uint32_t n_rows = min(64u, c - row0);
-            const uint32_t x = r < c ? ck[r] : pad_row<uint32_t>();
-            for (uint32_t c0 = row0 + 1; c0 < c; c0 += 64) {
-                const uint32_t ky = c0 + (uint32_t)lane < c ? ck[c0 + lane] : pad_col<uint32_t>();
-                const uint32_t nc = min(64u, c - c0);
-                unsigned long long h; // bit j: this lane's row is within k of column j of the tile
-                if (sliced) {
-                    h = columns64_sliced_k(x, ky, a.k, ck_bases);
-                } else {
-                    uint32_t hlo = 0, hhi = 0;
-                    hlo = columns32<true, 0>(x, ky, a.k, lim2);
-                    if (nc > 32) hhi = columns32<true, 32>(x, ky, a.k, lim2);
-                    h = ((unsigned long long)hhi << 32) | hlo;
+        bool probed = false;
+        if (!HAS_N && a.k == 1 && probe_part(g, nb) && c >= g.probe_min) { // (wave-uniform)
+            for (uint32_t w = lane; w < SEG_PROBE_WORDS; w += 64) bm[w] = 0u;
+            __syncthreads();
+            bool twice = false;
+            for (uint32_t p = lane; p < c; p += 64) {
+                const uint32_t sc = rest_code(ck[p]), bit = 1u << (sc & 31u);
+                twice = twice || (atomicOr(&bm[sc >> 5], bit) & bit) != 0u;
+            }
+            __syncthreads();
+            probed = !__any(twice);
+        }
+        if (probed) {
+            { // set bits before every word: a lane sums two words, the wave scans the sums
+                static_assert(SEG_PROBE_WORDS == 128, "two words per lane");
+                const uint32_t n0 = (uint32_t)__builtin_popcount(bm[2 * lane]), n1 = (uint32_t)__builtin_popcount(bm[2 * lane + 1]);
+                uint32_t incl = n0 + n1;
+                for (int d = 1; d < 64; d <<= 1) {
+                    const uint32_t up = __shfl_up(incl, d);
+                    if (lane >= d) incl += up;
                 }
-                const int j_min = lane + 1 - (int)(c0 - row0);
-                if (nc < 64) h &= (1ull << nc) - 1ull;
-                if (j_min > 0) h = j_min >= 64 ? 0ull : h & ~((1ull << j_min) - 1ull);
-                if ((uint32_t)lane >= n_rows) h = 0ull;
-                while (__any(h != 0ull)) { // one hit per lane and round
-                    const unsigned long long bal = __ballot(h != 0ull);
-                    if (h) {
-                        const int j = __builtin_ctzll(h);
-                        h &= h - 1ull;
-                        hitq[nq + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1ull))] = r | ((c0 + (uint32_t)j) << 16);
+                pre[2 * lane] = incl - n0 - n1;
+                pre[2 * lane + 1] = incl - n1;
+            }
+            __syncthreads();
+            auto rank_of = [&](uint32_t sc) { // entries of the bin with a smaller rest-code = the position of sc's
+                return pre[sc >> 5] + (uint32_t)__builtin_popcount(bm[sc >> 5] & ((1u << (sc & 31u)) - 1u));
+            };
+            // the records again (L2), to the order of their rest-codes
+            for (uint32_t p = lane; p < c; p += 64) {
+                const SegRec32 r = sub[start + p];
+                const uint32_t q = rank_of(rest_code(r.ckey));
+                ck[q] = r.ckey;
+                ix[q] = r.idx;
+                fr[q] = (uint32_t)r.freq;
+            }
+            __syncthreads();
+            for (uint32_t row0 = 0; row0 < c; row0 += 64) {
+                const uint32_t r = row0 + (uint32_t)lane;
+                const uint32_t sc = r < c ? rest_code(ck[r]) : 0u;
+                uint32_t m = 0; // bit 3 b + d - 1: the entry with base b changed by d is there, behind this one
+#pragma unroll
+                for (int bb = 0; bb < SEG_PROBE_MAX_REST; bb++) {
+#pragma unroll
+                    for (int d = 1; d <= 3; d++) {
+                        const uint32_t t = sc ^ ((uint32_t)d << (2 * bb));
+                        const uint32_t there = (bm[t >> 5] >> (t & 31u)) & 1u;
+                        if (bb < ck_bases && t > sc) m |= there << (3 * bb + d - 1);
                     }
-                    nq += (uint32_t)__builtin_popcountll(bal);
-                    if (nq >= LOCAL_DRAIN_AT) drain();
+                }
+                if (r >= c) m = 0u;
+                while (__any(m != 0u)) {
+                    uint32_t h = 0;
+                    const bool has = m != 0u;
+                    if (has) {
+                        const int j = __builtin_ctz(m), bb = j / 3;
+                        m &= m - 1u;
+                        h = r | (rank_of(sc ^ ((uint32_t)(j - 3 * bb + 1) << (2 * bb))) << 16);
+                    }
+                    push(has, h);
+                }
+            }
+        } else {
+            // the upper triangle: 64-row chunks against the columns behind their first row
+            for (uint32_t row0 = 0; row0 < c; row0 += 64) {
+                const uint32_t r = row0 + (uint32_t)lane;
+                const uint32_t n_rows = min(64u, c - row0);
+                const uint32_t x = r < c ? ck[r] : pad_row<uint32_t>();
+                for (uint32_t c0 = row0 + 1; c0 < c; c0 += 64) {
+                    const uint32_t ky = c0 + (uint32_t)lane < c ? ck[c0 + lane] : pad_col<uint32_t>();
+                    const uint32_t nc = min(64u, c - c0);
+                    unsigned long long h; // bit j: this lane's row is within k of column j of the tile
+                    if (sliced) {
+                        h = columns64_sliced_k(x, ky, a.k, ck_bases);
+                    } else {
+                        uint32_t hlo = 0, hhi = 0;
+                        hlo = columns32<true, 0>(x, ky, a.k, lim2);
+                        if (nc > 32) hhi = columns32<true, 32>(x, ky, a.k, lim2);
+                        h = ((unsigned long long)hhi << 32) | hlo;
+                    }
+                    const int j_min = lane + 1 - (int)(c0 - row0);
+                    if (nc < 64) h &= (1ull << nc) - 1ull;
+                    if (j_min > 0) h = j_min >= 64 ? 0ull : h & ~((1ull << j_min) - 1ull);
+                    if ((uint32_t)lane >= n_rows) h = 0ull;
+                    while (__any(h != 0ull)) { // one hit per lane and round
+                        uint32_t hit = 0;
+                        const bool has = h != 0ull;
+                        if (has) {
+                            const int j = __builtin_ctzll(h);
+                            h &= h - 1ull;
+                            hit = r | ((c0 + (uint32_t)j) << 16);
+                        }
+                        push(has, hit);
+                    }
                 }
             }
         }
@@ -1150,13 +1247,16 @@ hipError_t launch_seg_pairs(const PairArgs &a, const SegArgs &g, bool key32, flo
     return hipGetLastError();
 }
 
-size_t seg_local_lds_bytes(uint32_t cap) { return ((size_t)4 * cap + LOCAL_HITQ) * sizeof(uint32_t); }
+// (the records, the forest, the hit queue, the bitmap and its prefix: 9,728 bytes at the default cap, 16
+// blocks to a CU's 160 KB)
+size_t seg_local_lds_bytes(uint32_t cap) { return ((size_t)4 * cap + LOCAL_HITQ + 2 * SEG_PROBE_WORDS) * sizeof(uint32_t); }
 
 int seg_local_blocks_per_cu(bool has_n, uint32_t cap)
 {
     int nb = 0;
-    const hipError_t e = has_n ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, seg_local_kernel<true>, 64, seg_local_lds_bytes(cap))
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, seg_local_kernel<false>, 64, seg_local_lds_bytes(cap));
+    const size_t lds = seg_local_lds_bytes(cap);
+    const hipError_t e = has_n ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, seg_local_kernel<true>, 64, lds)
+                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, seg_local_kernel<false>, 64, lds);
     return e == hipSuccess && nb > 0 ? nb : 8;
 }
 
