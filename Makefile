@@ -43,7 +43,8 @@ $(DEVLIB): $(DEVOBJS)
 
 dev: $(DEVLIB)
 
-$(CLI): $(LIB) $(PKG)/host/umicollapse_main.cpp $(PKG)/host/bam.hpp $(PKG)/host/bgzf.hpp $(PKG)/host/fastq.hpp include/umihip.h
+$(CLI): $(LIB) $(PKG)/host/umicollapse_main.cpp $(PKG)/host/cli.hpp $(PKG)/host/hiplib.hpp $(PKG)/host/staging.hpp \
+        $(PKG)/host/two_pass.hpp $(PKG)/host/fastq_mode.hpp $(PKG)/host/bam.hpp $(PKG)/host/bgzf.hpp $(PKG)/host/fastq.hpp include/umihip.h
 	mkdir -p $(PKG)/bin
 	g++ -O2 -std=c++17 -Wall -Wextra -o $@ $(PKG)/host/umicollapse_main.cpp -lz -lpthread -ldl
 

@@ -1,4 +1,4 @@
-"""Test-side model of --umi-tag / --per-cell (umicollapse_main.cpp): the read loop of
+"""Test-side model of --umi-tag / --per-cell (host/staging.hpp, umicollapse_main.cpp): the read loop of
 src/deduplicate_sam.rs:93-177 with the UMI taken from an aux tag and the position keyed by
 (alignment, cell barcode), restated in plain Python over tests/bamio.py's record helpers.  Expected
 survivors come from the oracle's staging and batched dedup, --paired through bamio.paired_writer.

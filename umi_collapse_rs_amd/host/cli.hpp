@@ -1,0 +1,358 @@
+// `umicollapse`'s command line: the flags (Cli, parse, usage), the refusals that need no input file
+// (validate) and the lists the flags name (read_whitelist).
+#pragma once
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <unordered_set>
+#include <vector>
+
+#include "../../include/umihip.h"
+
+namespace {
+
+struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
+    std::string mode = "bam", input, output, algo = "dir", merge, data = "ngrambktree";
+    int k = 1;
+    size_t umi_length = 0;
+    float percentage = 0.5f;
+    unsigned num_threads = 1;
+    uint8_t umi_sep = '_';
+    bool two_pass = false, paired = false, remove_unpaired = false, remove_chimeric = false,
+         keep_unmapped = false, track_clusters = false;
+    // development switches (not in the reference)
+    std::string dump_staging; // write the staged hot-path input here and stop before the GPU
+    bool passthrough = false; // write every mapped record back (codec round trip), no dedup
+    std::vector<int> devices{0}; // --device <ID> or --devices <ID,ID,...>
+    int compress_level = 1;      // --compress-level 0..9: deflate level of the output's BGZF blocks.  Parity is
+                                 // defined on the decompressed stream (htslib's own level and backend are
+                                 // not reproducible here), and level 1 deflates a third of level 6's time
+    uint64_t two_pass_window = 1u << 21; // --two-pass-window <N>: reads per GPU call of --two-pass (see run_two_pass)
+    std::string stage = "auto";  // --stage gpu|host|auto: where the reads are merged per (position, UMI) and
+                                 // put in rank order (auto: on the GPU unless --paired or --tag need the
+                                 // host's per-read bookkeeping)
+    std::string umi_tag;         // --umi-tag XX: the UMI is the value of this aux tag, not the name's suffix
+    std::string cell_tag = "CB"; // --cell-tag XX: the cell barcode's tag (--per-cell)
+    bool per_cell = false, cell_tag_given = false; // --per-cell: positions are (alignment, cell barcode)
+    bool consensus = false;           // --consensus (fastq mode): every cluster written as its consensus read
+    uint64_t consensus_min_reads = 1; // --consensus-min-reads M: clusters of fewer members are left out
+    bool consensus_min_given = false;
+    bool call_consensus = false;           // --call-consensus (bam/sam mode): kept records carry their cluster's consensus
+    uint64_t call_consensus_min_reads = 1; // --call-consensus-min-reads M: clusters of fewer voters are left out
+    bool call_consensus_min_given = false;
+    std::string umi_whitelist;     // --umi-whitelist FILE: every UMI is snapped to the nearest listed one first
+    std::string whitelist_metrics; // --whitelist-metrics FILE: reads, exact, corrected per listed UMI
+    int wl_max_mismatches = 1, wl_min_distance = 1; // --whitelist-max-mismatches, --whitelist-min-distance
+    std::string cell_whitelist;         // --cell-whitelist FILE: cell barcodes are snapped to the kit's list first
+    std::string cell_whitelist_metrics; // --cell-whitelist-metrics FILE: reads, exact, corrected per listed barcode
+    int cell_wl_max_mismatches = 1;     // --cell-whitelist-max-mismatches: 0 or 1
+    bool cell_wl_max_given = false;
+    bool wl_max_given = false, wl_min_given = false;
+    bool edit_distance = false; // --distance edit: -k bounds the Levenshtein distance (umi_dedup_batch_edit)
+    // filled in by validate(): --algo as UMI_ALGO_*, --merge as 0 any, 1 avgqual, 2 mapqual, and the two lists
+    int algo_id = 0, merge_id = 0;
+    std::vector<uint8_t> whitelist, cell_list; // the listed UMIs / barcodes back to back
+    size_t cell_len = 0;
+};
+
+[[noreturn]] void die(const std::string &msg)
+{ // the reference panics (panic = "abort")
+    std::fprintf(stderr, "umicollapse: %s\n", msg.c_str());
+    std::fflush(stderr);
+    std::_Exit(101); // (no static destructors: the GPU's start-up thread may still be running)
+}
+
+void usage()
+{
+    std::puts("Usage: umicollapse [OPTIONS] -i <INPUT_FILE> -o <OUITPUT_FILE>\n"
+              "  -m, --mode <MODE>        Either fastq or SAM/BAM mode [default: bam]; fastq: whole reads\n"
+              "                           (<= 256 bases) are the key, one bucket per read length\n"
+              "  -k <K>                   Number of substitution edits to allow [default: 1]\n"
+              "      --distance <D>       hamming or edit [default: hamming]: the distance -k bounds.  edit is the\n"
+              "                           Levenshtein distance (substitution, insertion, deletion cost 1 each), which\n"
+              "                           sees a UMI shifted by a lost or gained base; between UMIs of one length an\n"
+              "                           indel costs 2, so -k 0 and -k 1 give the hamming result and the flag matters\n"
+              "                           from -k 2 (bam/sam mode, one GPU, UMIs of at most 21 bases)\n"
+              "  -u <UMI_LENGTH>          The UMI length [default: 0 = autodetect]; fastq: bases trimmed\n"
+              "                           from the start of every written read\n"
+              "  -p <PERCENTAGE>          Directional threshold percentage [default: 0.5]\n"
+              "      --num-threads <N>    Threads used in reader/writer [default: 1]\n"
+              "      --umi_sep <BYTE>     Separator byte value between UMI and read name [default: 95]\n"
+              "      --algo <ALGO>        adj or dir [default: dir]\n"
+              "      --merge <MERGE>      any, avgqual or mapqual [default: mapqual in bam mode, avgqual in fastq mode]\n"
+              "      --data <DATA>        accepted; every value gives Naive's result (as in the reference)\n"
+              "      --keep-unmapped      Keep unmapped reads\n"
+              "      --paired             Paired-end mode: template length joins the alignment key,\n"
+              "                           second mates follow their surviving first mates\n"
+              "      --remove-unpaired    Remove unpaired reads (paired-end mode)\n"
+              "      --remove-chimeric    Remove chimeric pairs (paired-end mode)\n"
+              "      --tag                Write every read tagged with its cluster (MI, cs, su) instead of\n"
+              "                           removing duplicates\n"
+              "      --two-pass           Read the input twice and hold only the open positions: peak memory\n"
+              "                           bounded for coordinate-sorted input, output identical to one pass\n"
+              "                           (-i must be a regular file; not with --tag or fastq mode)\n"
+              "      --two-pass-window <N> reads per GPU call with --two-pass [default: 2097152]\n"
+              "      --compress-level <N> deflate level of the output BAM, 0..9 [default: 1]\n"
+              "      --consensus          fastq mode: write every cluster as its consensus read -- each column the\n"
+              "                           quality-weighted majority of all the cluster's reads -- in place of the kept\n"
+              "                           read, the header with cluster_size=<reads> appended (not with --tag)\n"
+              "      --consensus-min-reads <M> with --consensus: leave out clusters of fewer than M reads [default: 1]\n"
+              "      --call-consensus     bam/sam mode: every kept record carries its cluster's consensus -- each column the\n"
+              "                           quality-weighted majority of the cluster's reads with the kept read's length\n"
+              "                           and CIGAR -- for sequence and qualities, with cD:i (voters), cs:i (reads of the\n"
+              "                           cluster) and ce:i (base votes that lost) appended; everything else of the\n"
+              "                           record stays (not with --tag, --paired, --two-pass)\n"
+              "      --call-consensus-min-reads <M> with --call-consensus: leave out clusters of fewer than M voters\n"
+              "                           [default: 1]\n"
+              "      --stage <WHERE>      gpu, host or auto: where reads are merged per (position, UMI) [default: auto]\n"
+              "      --umi-tag <XX>       the UMI is the value of aux tag XX (type Z, e.g. RX or UB) instead of the\n"
+              "                           read name's suffix; reads without it are dropped (bam/sam mode)\n"
+              "      --per-cell           deduplicate per cell: positions are (alignment, cell barcode); reads\n"
+              "                           without a barcode are dropped (bam/sam mode)\n"
+              "      --cell-tag <XX>      aux tag of the cell barcode, type Z [default: CB]\n"
+              "      --umi-whitelist <FILE> the kit's UMIs, one per line (ACGT, all of one length; blank lines and\n"
+              "                           lines starting with # skipped): every read's UMI is replaced, on the GPU, by\n"
+              "                           the nearest listed one before the reads are grouped; reads that match none\n"
+              "                           are dropped; written records keep their own bytes (bam/sam mode, one pass)\n"
+              "      --whitelist-max-mismatches <M> a UMI matches a listed one at up to M mismatches [default: 1]\n"
+              "      --whitelist-min-distance <D> ... if the next best listed UMI is at least D further away [default: 1]\n"
+              "      --whitelist-metrics <FILE> write a table: umi, reads, exact, corrected per listed UMI, in list order\n"
+              "      --cell-whitelist <FILE> with --per-cell: the kit's cell barcodes, one per line (ACGT, all of one\n"
+              "                           length, at most 32 bases, no -1 suffix; blank lines and lines starting with #\n"
+              "                           skipped): every read's barcode (--cell-tag CR for raw ones) is looked up in an\n"
+              "                           index of the list on the GPU; an unlisted barcode one substitution from exactly\n"
+              "                           one listed barcode counts as that one; reads with an unlisted or ambiguous\n"
+              "                           barcode are dropped; written records keep their own bytes (bam/sam mode, one pass)\n"
+              "      --cell-whitelist-max-mismatches <M> 0: listed barcodes only; 1: one substitution allowed [default: 1]\n"
+              "      --cell-whitelist-metrics <FILE> write a table: barcode, reads, exact, corrected per listed barcode\n"
+              "                           that took a read, in list order\n"
+              "      --device <ID>        GPU to use [default: 0]\n"
+              "      --devices <ID,..>    several GPUs of the node: alignment positions are sharded over them");
+}
+
+// a GPU id: decimal digits only (atoi would take "x" for device 0)
+int device_id(const char *text)
+{
+    char *end = nullptr;
+    const long v = std::strtol(text, &end, 10);
+    if (end == text || *end != '\0' || v < 0 || v > 1023) die(std::string("not a GPU id: '") + text + "'");
+    return (int)v;
+}
+
+Cli parse(int argc, char **argv)
+{
+    Cli c;
+    auto need = [&](int &i) -> const char * {
+        if (i + 1 >= argc) die(std::string("a value is required for '") + argv[i] + "'");
+        return argv[++i];
+    };
+    // a flag's value as a whole decimal number from `least` to `most`, or the flag's message
+    auto number = [&](int &i, const std::string &msg, long long least, long long most = INT64_MAX) -> long long {
+        const char *v = need(i);
+        char *end = nullptr;
+        const long long w = std::strtoll(v, &end, 10);
+        if (end == v || *end != '\0' || w < least || w > most) die(msg);
+        return w;
+    };
+    for (int i = 1; i < argc; i++) {
+        const std::string a = argv[i];
+        if (a == "-m" || a == "--mode") c.mode = need(i);
+        else if (a == "-i") c.input = need(i);
+        else if (a == "-o") c.output = need(i);
+        else if (a == "-k") c.k = std::atoi(need(i));
+        else if (a == "-u") c.umi_length = (size_t)std::atol(need(i));
+        else if (a == "-p") c.percentage = std::strtof(need(i), nullptr);
+        else if (a == "--num-threads") c.num_threads = (unsigned)std::atoi(need(i));
+        else if (a == "--umi_sep") c.umi_sep = (uint8_t)std::atoi(need(i)); // a number, cli.rs:31-32
+        else if (a == "--algo") c.algo = need(i);
+        else if (a == "--distance") {
+            const std::string d = need(i);
+            if (d != "hamming" && d != "edit") die("--distance wants hamming or edit: '" + d + "'");
+            c.edit_distance = d == "edit";
+        }
+        else if (a == "--merge") c.merge = need(i);
+        else if (a == "--data") c.data = need(i);
+        else if (a == "--two-pass") c.two_pass = true;
+        else if (a == "--two-pass-window")
+            c.two_pass_window = (uint64_t)number(i, "--two-pass-window wants a number of reads, 1 or more", 1);
+        else if (a == "--paired") c.paired = true;
+        else if (a == "--remove-unpaired") c.remove_unpaired = true;
+        else if (a == "--remove-chimeric") c.remove_chimeric = true;
+        else if (a == "--keep-unmapped") c.keep_unmapped = true;
+        else if (a == "--tag") c.track_clusters = true;
+        else if (a == "--dump-staging") c.dump_staging = need(i);
+        else if (a == "--passthrough") c.passthrough = true;
+        else if (a == "--stage") c.stage = need(i);
+        else if (a == "--umi-tag" || a == "--cell-tag") {
+            const std::string t = need(i);
+            auto alpha = [](char ch) { return (ch >= 'A' && ch <= 'Z') || (ch >= 'a' && ch <= 'z'); };
+            if (t.size() != 2 || !alpha(t[0]) || !(alpha(t[1]) || (t[1] >= '0' && t[1] <= '9'))) // SAM spec
+                die(a + " wants a tag name of two characters, [A-Za-z][A-Za-z0-9]: '" + t + "'");
+            if (a == "--umi-tag") c.umi_tag = t;
+            else { c.cell_tag = t; c.cell_tag_given = true; }
+        }
+        else if (a == "--per-cell") c.per_cell = true;
+        else if (a == "--umi-whitelist") c.umi_whitelist = need(i);
+        else if (a == "--whitelist-metrics") c.whitelist_metrics = need(i);
+        else if (a == "--whitelist-max-mismatches" || a == "--whitelist-min-distance") {
+            const long long m = number(i, a + " wants a number, 0 or more", 0, INT32_MAX);
+            if (a == "--whitelist-max-mismatches") { c.wl_max_mismatches = (int)m; c.wl_max_given = true; }
+            else { c.wl_min_distance = (int)m; c.wl_min_given = true; }
+        }
+        else if (a == "--cell-whitelist") c.cell_whitelist = need(i);
+        else if (a == "--cell-whitelist-metrics") c.cell_whitelist_metrics = need(i);
+        else if (a == "--cell-whitelist-max-mismatches") {
+            const std::string v = need(i);
+            if (v != "0" && v != "1") die(a + " wants 0 or 1: '" + v + "'");
+            c.cell_wl_max_mismatches = v == "1";
+            c.cell_wl_max_given = true;
+        }
+        else if (a == "--consensus") c.consensus = true;
+        else if (a == "--consensus-min-reads") {
+            c.consensus_min_reads = (uint64_t)number(i, "--consensus-min-reads wants a number of reads, 1 or more", 1);
+            c.consensus_min_given = true;
+        }
+        else if (a == "--call-consensus") c.call_consensus = true;
+        else if (a == "--call-consensus-min-reads") {
+            c.call_consensus_min_reads = (uint64_t)number(i, "--call-consensus-min-reads wants a number of reads, 1 or more", 1);
+            c.call_consensus_min_given = true;
+        }
+        else if (a == "--compress-level") {
+            c.compress_level = std::atoi(need(i));
+            if (c.compress_level < 0 || c.compress_level > 9) die("--compress-level wants 0..9");
+        }
+        else if (a == "--device") c.devices.assign(1, device_id(need(i)));
+        else if (a == "--devices") { // the GPUs of the node the position buckets are sharded over
+            c.devices.clear();
+            std::string list = need(i);
+            for (size_t p = 0; p <= list.size();) {
+                const size_t q = std::min(list.find(',', p), list.size());
+                if (q == p) die("--devices wants a comma separated list of GPU ids");
+                c.devices.push_back(device_id(list.substr(p, q - p).c_str()));
+                p = q + 1;
+            }
+        }
+        else if (a == "-h" || a == "--help") { usage(); std::exit(0); }
+        else die("unexpected argument '" + a + "'");
+    }
+    if (c.input.empty() || c.output.empty()) { usage(); die("-i and -o are required"); }
+    return c;
+}
+
+// --umi-whitelist: the listed UMIs back to back; their length in umi_len.  One UMI per line, blank lines and
+// lines that start with # skipped; anything a kit's list cannot be ends the run.
+// (--cell-whitelist reads its list the same way: `list_name` and `item` are what the messages call them)
+std::vector<uint8_t> read_whitelist(const std::string &path, size_t &umi_len, const std::string &list_name = "UMI whitelist",
+                                    const std::string &item = "UMI", size_t max_len = UMI_MAX_WIDE_UMI_LEN)
+{
+    FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) die("cannot open the " + list_name + " " + path);
+    std::string text;
+    char buf[1 << 16];
+    for (size_t got; (got = std::fread(buf, 1, sizeof(buf), f)) > 0;) text.append(buf, got);
+    std::fclose(f);
+    std::vector<uint8_t> list;
+    std::unordered_set<std::string> seen;
+    umi_len = 0;
+    size_t line_no = 0;
+    for (size_t p = 0; p < text.size();) {
+        size_t q = text.find('\n', p);
+        if (q == std::string::npos) q = text.size();
+        std::string line = text.substr(p, q - p);
+        p = q + 1;
+        line_no++;
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        const std::string where = list_name + " " + path + ", line " + std::to_string(line_no) + ": ";
+        if (line.size() > max_len) die(where + std::to_string(line.size()) + " bases, more than " + std::to_string(max_len));
+        for (char ch : line)
+            if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T')
+                die(where + "a character outside ACGT: " + std::to_string((unsigned)(uint8_t)ch));
+        if (umi_len && line.size() != umi_len)
+            die(where + std::to_string(line.size()) + " bases, the " + item + "s before it have " + std::to_string(umi_len));
+        if (!seen.insert(line).second) die(where + "duplicate entry " + line);
+        umi_len = line.size();
+        list.insert(list.end(), line.begin(), line.end());
+    }
+    if (list.empty()) die("the " + list_name + " " + path + " holds no " + item);
+    return list;
+}
+
+// the one spelling of --stage's values (each mode asks at its own place among its refusals)
+void check_stage(const Cli &args)
+{
+    if (args.stage != "auto" && args.stage != "gpu" && args.stage != "host") die("--stage wants gpu, host or auto");
+}
+
+// --distance edit: one-word keys only; `whose` says where the length came from
+void check_edit_length(const Cli &args, size_t umi_length, const std::string &whose)
+{
+    if (args.edit_distance && umi_length > UMI_MAX_UMI_LEN)
+        die("--distance edit takes UMIs of at most 21 bases (" + whose + " " + std::to_string(umi_length) + ")");
+}
+
+// The refusals that need nothing but the command line and the lists it names, in the order that decides
+// which message wins when two apply; fills in the defaults and the decoded --algo / --merge.  False: a
+// --mode that is none of bam, sam, fastq, for which nothing happens.
+bool validate(Cli &args)
+{
+    if (args.merge.empty()) args.merge = args.mode == "fastq" ? "avgqual" : "mapqual"; // main.rs:33-39
+    // --call-consensus: everything about it that can be refused is, before the GPU is woken
+    if (args.call_consensus_min_given && !args.call_consensus) die("--call-consensus-min-reads goes with --call-consensus only");
+    if (args.call_consensus) {
+        if (args.mode == "fastq") die("--call-consensus is defined in bam/sam mode only (fastq mode has --consensus)");
+        if (args.track_clusters) die("--call-consensus does not go with --tag (which writes every read as it is)");
+        if (args.two_pass) die("--call-consensus does not go with --two-pass (a cluster's reads are not held there)");
+        if (args.paired) die("--call-consensus does not go with --paired");
+        if (!args.dump_staging.empty() || args.passthrough) die("--call-consensus does not go with --dump-staging or --passthrough");
+    }
+    if (args.track_clusters && args.two_pass) die("Cannot track clusters with the two pass algorithm!");
+    if (args.paired && args.keep_unmapped) die("Cannot keep unmapped reads with paired-end reads!");
+    if (args.consensus_min_given && !args.consensus) die("--consensus-min-reads goes with --consensus only");
+    if (args.consensus && args.mode != "fastq") die("--consensus is defined in fastq mode only (-m fastq)");
+    if (args.umi_whitelist.empty() && (args.wl_max_given || args.wl_min_given || !args.whitelist_metrics.empty()))
+        die("--whitelist-max-mismatches, --whitelist-min-distance and --whitelist-metrics go with --umi-whitelist only");
+    if (args.mode != "bam" && args.mode != "sam" && args.mode != "fastq") return false; // main.rs:49-95: nothing happens
+    // --distance edit: everything about it that can be refused is, before the GPU is woken
+    if (args.edit_distance) {
+        if (args.mode == "fastq") die("--distance edit is defined in bam/sam mode only (whole reads are the key in fastq mode)");
+        if (args.devices.size() > 1) die("--distance edit runs on one GPU: --devices takes one id with it");
+        check_edit_length(args, args.umi_length, "-u");
+    }
+    // --umi-whitelist: everything about it that can be refused is, before the GPU is woken
+    if (!args.umi_whitelist.empty()) {
+        if (args.mode == "fastq") die("--umi-whitelist does not go with fastq mode (whole reads are the key there)");
+        if (args.two_pass) die("--umi-whitelist does not go with --two-pass (its census would need the correction too)");
+        if (!args.dump_staging.empty() || args.passthrough) die("--umi-whitelist does not go with --dump-staging or --passthrough");
+        size_t wl_len = 0;
+        args.whitelist = read_whitelist(args.umi_whitelist, wl_len);
+        if (args.umi_length != 0 && args.umi_length != wl_len)
+            die("-u " + std::to_string(args.umi_length) + " does not go with a whitelist of UMIs of " + std::to_string(wl_len) +
+                " bases");
+        check_edit_length(args, wl_len, "the whitelist's have");
+        args.umi_length = wl_len; // (a read whose UMI is of another length ends the run, as with -u)
+    }
+    // --cell-whitelist: likewise
+    if (args.cell_whitelist.empty() && (args.cell_wl_max_given || !args.cell_whitelist_metrics.empty()))
+        die("--cell-whitelist-max-mismatches and --cell-whitelist-metrics go with --cell-whitelist only");
+    if (!args.cell_whitelist.empty()) {
+        if (args.mode == "fastq") die("--cell-whitelist does not go with fastq mode (there are no tags there)");
+        if (!args.per_cell) die("--cell-whitelist goes with --per-cell only");
+        if (args.two_pass) die("--cell-whitelist does not go with --two-pass (its census would need the correction too)");
+        if (!args.dump_staging.empty() || args.passthrough) die("--cell-whitelist does not go with --dump-staging or --passthrough");
+        args.cell_list = read_whitelist(args.cell_whitelist, args.cell_len, "cell barcode whitelist", "barcode", 32);
+    }
+    if (args.track_clusters && args.paired) die("--tag with --paired is not implemented (the reference never reaches its tagging pass)");
+    if (args.algo == "dir") args.algo_id = UMI_ALGO_DIRECTIONAL;
+    else if (args.algo == "adj") args.algo_id = UMI_ALGO_ADJACENCY;
+    else die("Invalid algorithm combination: " + args.algo + " , " + args.merge + " and " + args.data); // main.rs:86-91
+    if (args.merge == "any") args.merge_id = 0;
+    else if (args.merge == "avgqual") args.merge_id = 1;
+    else if (args.merge == "mapqual") args.merge_id = 2;
+    else die("Invalid algorithm combination: " + args.algo + " , " + args.merge + " and " + args.data);
+    return true;
+}
+
+} // namespace

@@ -1,0 +1,353 @@
+// What BAM mode's staging is made of, shared by the one-pass pipeline and --two-pass: UMI and alignment keys,
+// the filters of the read loop, the tags a read is looked up by, the host staging of one position and the
+// summary lines.
+//
+// --umi-tag XX (bam/sam mode; fgbio / umi_tools / single-cell convention, not the reference's): the UMI of a
+// staged read is the value of its aux tag XX (type Z; -u N or the first staged read's length; another length
+// ends the run naming the read, a byte outside ATCGN -- a duplex "-" included -- is "Unknown character";
+// --umi_sep is ignored).  --per-cell: a position is (alignment, cell barcode) -- the value of --cell-tag
+// (default CB, type Z), compared byte for byte -- so UMIs of different cells are never compared.  A staged
+// read without its tags is dropped, not written, and counted ("Number of reads without a UMI tag / a cell
+// barcode", each tag counted by itself); "Number of unique alignment positions" still counts alignments,
+// "Number of (position, cell) groups" the buckets, which the average and maximum lines are over.  A
+// barcode's id is the rank of its first appearance (per-thread tables made global); the device staging takes
+// it as the group key of umi_stage_reads_grouped_wide.  Everything else -- merge, --paired (the first
+// mate's tags), --tag, --two-pass, --devices, --stage -- as without the flags; --dump-staging appends every
+// bucket's cell id.  A malformed aux block or a tag of another type ends the run with status 101.
+#pragma once
+#include <string_view>
+#include <unordered_map>
+
+#include "bam.hpp"
+#include "bgzf.hpp"
+#include "cli.hpp"
+
+namespace {
+
+// A UMI key: BitSet.bits of the reference (src/utils/bitset.rs:9-27), up to 85 bases in four words
+constexpr int MAX_WORDS = 4;
+struct UmiKey {
+    uint64_t w[MAX_WORDS];
+    bool operator==(const UmiKey &o) const { return w[0] == o.w[0] && w[1] == o.w[1] && w[2] == o.w[2] && w[3] == o.w[3]; }
+};
+struct UmiKeyHash {
+    size_t operator()(const UmiKey &k) const
+    {
+        uint64_t x = k.w[0] * 0x9E3779B97F4A7C15ull ^ (k.w[1] + 0x7F4A7C15u) * 0xD6E8FEB86659FD93ull ^ (k.w[2] << 7) ^ (k.w[3] >> 3);
+        x ^= x >> 31;
+        x *= 0xBF58476D1CE4E5B9ull;
+        return (size_t)(x ^ (x >> 29));
+    }
+};
+
+// src/utils/mod.rs:63-83 with the codes of src/utils/read.rs:23-31 (the library's umi_encode_umis[_wide],
+// restated here so that the staging of the host path needs no library call); base b at bits
+// 3b .. 3b+2 of the word string, bit by bit: a base may sit across two words (bitset.rs:52-75)
+bool encode_umi(const uint8_t *u, size_t len, UmiKey *key, UmiKey *nmask)
+{
+    UmiKey k{{0, 0, 0, 0}}, nm{{0, 0, 0, 0}};
+    for (size_t b = 0; b < len; b++) {
+        uint64_t c;
+        switch (u[b]) {
+        case 'A': c = 0; break;
+        case 'T': c = 5; break;
+        case 'C': c = 6; break;
+        case 'G': c = 3; break;
+        case 'N': c = 4; break;
+        default: return false;
+        }
+        for (int j = 0; j < 3; j++) {
+            const size_t bit = 3 * b + j;
+            if ((c >> j) & 1) k.w[bit >> 6] |= 1ull << (bit & 63);
+            if (c == 4) nm.w[bit >> 6] |= 1ull << (bit & 63);
+        }
+    }
+    *key = k;
+    *nmask = nm;
+    return true;
+}
+
+struct Entry { // one (alignment key, UMI): ReadFreq of src/utils/read_freq.rs + its key
+    UmiKey key, nmask;
+    int32_t freq;
+    int32_t score;  // avg qual or mapq of the representative
+    uint32_t rep;   // record index of the representative read
+    uint32_t index; // its place in the canonical order, once its position has been emitted
+};
+
+// Align (deduplicate_sam.rs:478-481): Alignment{strand, coord, ref} or, with --paired,
+// PairedAlignment{strand, coord, ref, tlen} (:547-553); ref as tid (equal names <=> equal tid)
+struct AlignKey {
+    uint64_t coord, ref_strand, tlen;
+    uint64_t cell = 0; // --per-cell: the barcode's dense id (first-appearance rank); 0 otherwise
+    bool operator==(const AlignKey &o) const
+    {
+        return coord == o.coord && ref_strand == o.ref_strand && tlen == o.tlen && cell == o.cell;
+    }
+};
+
+struct KeyHash {
+    size_t operator()(const AlignKey &k) const
+    {
+        uint64_t x = k.coord * 0x9E3779B97F4A7C15ull ^ (k.ref_strand + 0x7F4A7C15u) ^ (k.tlen * 0xD6E8FEB86659FD93ull) ^
+                     (k.cell * 0x94D049BB133111EBull);
+        x ^= x >> 29;
+        x *= 0xBF58476D1CE4E5B9ull;
+        return (size_t)(x ^ (x >> 32));
+    }
+};
+
+// ReverseRead (deduplicate_sam.rs:272-286): the mate a written paired record is waiting for
+std::string mate_key(const uint8_t *qname, size_t n, int32_t tid, int32_t pos)
+{
+    std::string s((const char *)qname, n);
+    s.append((const char *)&tid, 4);
+    s.append((const char *)&pos, 4);
+    return s;
+}
+
+// UcSAMRead::get_umi_length (read.rs:65-75,87-94): first separator followed by a base
+// (caseless [ATCGN]), length of that run.
+size_t detect_umi_length(const uint8_t *q, size_t n, uint8_t sep)
+{
+    auto is_base = [](uint8_t ch) {
+        switch (ch | 0x20) { case 'a': case 't': case 'c': case 'g': case 'n': return true; default: return false; }
+    };
+    for (size_t i = 0; i + 1 < n; i++)
+        if (q[i] == sep && is_base(q[i + 1])) {
+            size_t j = i + 1;
+            while (j < n && is_base(q[j])) j++;
+            return j - i - 1;
+        }
+    die("No UMI group found in pattern match");
+}
+
+// The filters of the read loop (deduplicate_sam.rs:95-129), shared by the one-pass staging and both
+// passes of --two-pass.  Returns the read's state: 0 staged, 1 unmapped, 3 second mate (not counted),
+// 4 mate unmapped, 5 filtered (--remove-unpaired / --remove-chimeric); 2 (error) is set by the caller.
+uint8_t read_state(const Cli &args, const umi::bam::Record &r, uint8_t &is_unpaired, uint8_t &is_chimeric)
+{
+    is_unpaired = is_chimeric = 0;
+    if (args.paired && r.is_paired() && r.is_last_in_template()) return 3; // :95-97
+    if (r.is_unmapped()) return 1;                                         // :102-108
+    if (args.paired && !args.passthrough) {                                // :110-129
+        if (!r.is_paired()) {
+            is_unpaired = 1;
+            if (args.remove_unpaired) return 5;
+        }
+        if (r.is_paired() && r.is_mate_unmapped()) return 4;
+        if (r.is_paired() && r.tid() != r.mtid()) {
+            is_chimeric = 1;
+            if (args.remove_chimeric) return 5;
+        }
+    }
+    return 0;
+}
+
+// Alignment{strand, coord, ref} (:141-145) or, with --paired, PairedAlignment (:138, :547-553) of a
+// staged read; equality on tid == equality on the reference name
+AlignKey align_key(const umi::bam::Record &r, bool paired)
+{
+    return AlignKey{(uint64_t)r.unclipped_pos(), ((uint64_t)(uint32_t)r.tid() << 1) | (r.is_reverse() ? 1u : 0u),
+                    paired ? (uint64_t)(int64_t)r.tlen() : 0};
+}
+
+// where a staged read's UMI starts in its name (read.rs:100), or the reference's message
+const char *find_umi(const umi::bam::Record &r, uint8_t sep, size_t umi_length, size_t &at)
+{
+    const uint8_t *q = r.qname();
+    const size_t qn = r.qname_len();
+    const uint8_t *sp = (const uint8_t *)std::memchr(q, sep, qn);
+    at = sp ? (size_t)(sp - q) + 1 : 0;
+    if (!sp) return "failed to get the umi";
+    if (umi_length == 0) return "Empty UMI sequence extracted";
+    if (umi_length > UMI_MAX_WIDE_UMI_LEN) return "UMIs of more than 85 bases are not handled";
+    if (at + umi_length > qn) return "UMI runs past the end of the read name";
+    return nullptr;
+}
+
+// --umi-tag / --per-cell: the aux tags a staged read is looked up by.  Returns the bits of the ones it
+// lacks (MISS_UMI, MISS_CELL: the read is dropped, not written, and counted); err: the message that ends
+// the run (a malformed aux block, a tag that is not of type Z).
+enum : uint8_t { MISS_UMI = 1, MISS_CELL = 2 };
+struct ReadTags {
+    const uint8_t *umi = nullptr; // --umi-tag: the value
+    size_t umi_len = 0;
+    std::string_view cell;        // --per-cell: the barcode, an opaque byte string
+};
+uint8_t read_tags(const Cli &args, const umi::bam::Record &r, ReadTags &t, std::string &err)
+{
+    auto look = [&](const std::string &tag, umi::bam::AuxField &f) -> bool {
+        const umi::bam::AuxFind got = umi::bam::find_aux(r, tag.c_str(), &f);
+        const std::string name((const char *)r.qname(), r.qname_len());
+        if (got == umi::bam::AuxFind::malformed) err = "malformed aux block in read " + name;
+        else if (got == umi::bam::AuxFind::found && f.type != 'Z')
+            err = "tag " + tag + " of read " + name + " is of type " + std::string(1, f.type) + ", not Z";
+        return got == umi::bam::AuxFind::found && err.empty();
+    };
+    uint8_t miss = 0;
+    umi::bam::AuxField f;
+    if (!args.umi_tag.empty()) {
+        if (look(args.umi_tag, f)) {
+            t.umi = f.value;
+            t.umi_len = f.len;
+        } else {
+            miss |= MISS_UMI;
+        }
+        if (!err.empty()) return 0;
+    }
+    if (args.per_cell) {
+        if (look(args.cell_tag, f)) t.cell = std::string_view((const char *)f.value, f.len);
+        else miss |= MISS_CELL;
+    }
+    return miss;
+}
+
+// where the UMI of a read with all its tags starts, as an offset from its name: after --umi_sep in the
+// name (find_umi), or the --umi-tag value, which must be umi_length bases; empty, or the message that
+// ends the run
+std::string umi_offset(const Cli &args, const umi::bam::Record &r, const ReadTags &t, size_t umi_length, size_t &at)
+{
+    if (args.umi_tag.empty()) {
+        const char *err = find_umi(r, args.umi_sep, umi_length, at);
+        return err ? err : "";
+    }
+    at = (size_t)(t.umi - r.qname());
+    if (umi_length == 0) return "Empty UMI sequence extracted";
+    if (umi_length > UMI_MAX_WIDE_UMI_LEN) return "UMIs of more than 85 bases are not handled";
+    if (t.umi_len != umi_length)
+        return "UMI tag " + args.umi_tag + " of read " + std::string((const char *)r.qname(), r.qname_len()) + " holds " +
+               std::to_string(t.umi_len) + " bases, not " + std::to_string(umi_length);
+    return "";
+}
+
+// the UMI length of the first staged read (src: :154-156): the name's UMI group, or the --umi-tag value's length
+size_t detect_length(const Cli &args, const umi::bam::Record &r, const ReadTags &t)
+{
+    return args.umi_tag.empty() ? detect_umi_length(r.qname(), r.qname_len(), args.umi_sep) : t.umi_len;
+}
+
+int bits_of(uint64_t v)
+{
+    int b = 1;
+    while (b < 64 && (v >> b)) b++;
+    return b;
+}
+
+// a second mate the paired writer may look for (:425-429)
+bool mate_candidate(const umi::bam::Record &r)
+{
+    return !r.is_unmapped() && r.is_paired() && r.is_last_in_template() && !r.is_mate_unmapped();
+}
+
+// ---- the host staging of one position (deduplicate_sam.rs:148-176), shared by the one-pass shards and the
+// windows of --two-pass.  `index` maps the position's UMIs to their entries in `entries` (which may hold other
+// positions' too), `members` lists the position's entries in order of first appearance.
+using UmiIndex = std::unordered_map<UmiKey, uint32_t, UmiKeyHash>;
+using U64s = std::vector<uint64_t, umi::bgzf::default_init_allocator<uint64_t>>; // (not zeroed when sized)
+using I32s = std::vector<int32_t, umi::bgzf::default_init_allocator<int32_t>>;
+
+// a read joins its position: a new entry, or one more read of an entry that keeps the better representative.
+// Returns the entry.
+uint32_t add_read(UmiIndex &index, std::vector<Entry> &entries, std::vector<uint32_t> &members, const UmiKey &key,
+                  const UmiKey &nmask, int32_t score, uint32_t read, int merge)
+{
+    const auto e = index.find(key);
+    if (e == index.end()) { // Vacant :161-163
+        const uint32_t ei = (uint32_t)entries.size();
+        index.emplace(key, ei);
+        members.push_back(ei);
+        entries.push_back({key, nmask, 1, score, read, 0});
+        return ei;
+    }
+    Entry &en = entries[e->second]; // Occupied :164-175
+    const bool keep_existing = merge == 0 ? true : en.score >= score; // merge/mod.rs:21,35,49
+    en.freq += 1;
+    if (!keep_existing) { en.rep = read; en.score = score; }
+    return e->second;
+}
+
+// a position's entries go out in the stable freq-descending order of directional.rs:67-72 (creation order of
+// a position's entries = first appearance): n_words key and mask words and the frequency of each, from entry
+// `w` of the arrays on; every entry learns its index, `members` is left in that order
+void emit_position(std::vector<Entry> &entries, std::vector<uint32_t> &members, int n_words, uint64_t *keys, uint64_t *nmask,
+                   int32_t *freq, size_t &w)
+{
+    std::stable_sort(members.begin(), members.end(), [&](uint32_t x, uint32_t y) { return entries[y].freq < entries[x].freq; });
+    for (uint32_t ei : members) {
+        Entry &en = entries[ei];
+        for (int q = 0; q < n_words; q++) {
+            keys[w * n_words + q] = en.key.w[q];
+            nmask[w * n_words + q] = en.nmask.w[q];
+        }
+        freq[w] = en.freq;
+        en.index = (uint32_t)w++;
+    }
+}
+
+// --whitelist-metrics / --cell-whitelist-metrics: per listed item, in list order, the reads it took, exact and
+// corrected (status 0: exact); `used_only` leaves out the items that took none
+void write_list_metrics(const std::string &path, const char *item, const std::vector<uint8_t> &list, size_t L,
+                        const std::vector<int32_t> &match, const std::vector<uint8_t> &status, bool used_only)
+{
+    const size_t n_wl = list.size() / L;
+    std::vector<uint64_t> exact(n_wl, 0), corrected(n_wl, 0);
+    for (size_t j = 0; j < match.size(); j++)
+        if (match[j] >= 0) (status[j] == 0 ? exact : corrected)[(size_t)match[j]]++;
+    FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) die("cannot open " + path);
+    std::fprintf(f, "%s\treads\texact\tcorrected\n", item);
+    for (size_t w = 0; w < n_wl; w++)
+        if (!used_only || exact[w] + corrected[w])
+            std::fprintf(f, "%.*s\t%llu\t%llu\t%llu\n", (int)L, (const char *)&list[w * L],
+                         (unsigned long long)(exact[w] + corrected[w]), (unsigned long long)exact[w],
+                         (unsigned long long)corrected[w]);
+    if (std::fclose(f) != 0) die("cannot write " + path);
+}
+
+// counters of deduplicate_sam.rs:243-268 and this build's own, printed by one pass, --two-pass and (the lines
+// about tags and cells only) the --dump-staging exit
+struct Summary {
+    size_t total_read_count = 0, unmapped = 0, unpaired = 0, chimeric = 0, no_umi_tag = 0, no_cell = 0;
+    uint64_t cb_counts[4] = {0, 0, 0, 0}; // --cell-whitelist: exact, corrected, unlisted, ambiguous
+    uint64_t wl_counts[3] = {0, 0, 0};    // --umi-whitelist: exact, corrected, uncorrectable
+    size_t n_positions = 0, nb = 0, n = 0, max_umi = 0;
+    uint64_t n_kept = 0;
+    size_t n_below = 0, n_without = 0; // --call-consensus
+    void print(const Cli &args, bool dump_exit = false) const
+    {
+        if (!dump_exit) {
+            std::fprintf(stderr, "Number of input reads: %zu\n", total_read_count);
+            std::fprintf(stderr, "Number of removed unmapped reads: %zu\n", unmapped);
+            if (args.paired) {
+                std::fprintf(stderr, "Number of unpaired reads: %zu\n", unpaired);
+                std::fprintf(stderr, "Number of chimeric reads: %zu\n", chimeric);
+            }
+        }
+        if (!args.umi_tag.empty()) std::fprintf(stderr, "Number of reads without a UMI tag: %zu\n", no_umi_tag);
+        if (args.per_cell) std::fprintf(stderr, "Number of reads without a cell barcode: %zu\n", no_cell);
+        if (!args.cell_list.empty()) {
+            std::fprintf(stderr, "Number of reads with a corrected cell barcode: %llu\n", (unsigned long long)cb_counts[1]);
+            std::fprintf(stderr, "Number of reads with an unlisted cell barcode: %llu\n", (unsigned long long)cb_counts[2]);
+            std::fprintf(stderr, "Number of reads with an ambiguous cell barcode: %llu\n", (unsigned long long)cb_counts[3]);
+        }
+        if (!args.whitelist.empty()) {
+            std::fprintf(stderr, "Number of reads with a corrected UMI: %llu\n", (unsigned long long)wl_counts[1]);
+            std::fprintf(stderr, "Number of reads with an uncorrectable UMI: %llu\n", (unsigned long long)wl_counts[2]);
+        }
+        if (!dump_exit || args.per_cell) std::fprintf(stderr, "Number of unique alignment positions: %zu\n", n_positions);
+        if (args.per_cell) std::fprintf(stderr, "Number of (position, cell) groups: %zu\n", nb);
+        if (dump_exit) return;
+        std::fprintf(stderr, "Number of UMIs: %zu\n", n);
+        std::fprintf(stderr, "Average number of UMIs per alignment position: %g\n", nb ? (double)n / (double)nb : 0.0);
+        std::fprintf(stderr, "Max number of UMIs over all alignment positions: %zu\n", max_umi);
+        std::fprintf(stderr, args.track_clusters ? "Number of groups of reads: %llu\n" : "Number of reads after deduplicating: %llu\n",
+                     (unsigned long long)n_kept); // :259-266
+        if (args.edit_distance) std::fprintf(stderr, "UMI distance: edit\n");
+        if (args.call_consensus) {
+            std::fprintf(stderr, "Number of clusters below --call-consensus-min-reads: %zu\n", n_below);
+            std::fprintf(stderr, "Number of clusters without a consensus: %zu\n", n_without);
+        }
+    }
+};
+} // namespace
