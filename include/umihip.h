@@ -454,6 +454,36 @@ int umi_correct_barcodes(umi_ctx *ctx, const uint8_t *bc_ascii, uint64_t n_reads
                          const uint8_t *whitelist_ascii, uint32_t n_wl, int max_mismatches, int32_t *match,
                          uint8_t *status, uint64_t counts[4]);
 
+/* ---- molecules and reads per (column, row) pair (the program's --count-matrix): what a batched call kept,
+ *      summed over its buckets into the triplets of a sparse matrix, on the GPU.  No counterpart in the
+ *      reference; the counting is umi_tools count --per-gene --per-cell's, tests/gene_model.py (count_model)
+ *      defines it.
+ * in : kept / freq: the N = bucket_off[n_buckets] entries of a batched call (kept as that call wrote it: any
+ *      byte other than 0 counts as kept); bucket_off: a HOST array in both forms, [n_buckets + 1], starting
+ *      at 0 and never falling; row[b] / col[b]: the row id (gene) and column id (cell) of bucket b.  A bucket
+ *      is non-empty when bucket_off[b] < bucket_off[b + 1]; several buckets may carry the same pair.
+ * out: one triplet for every distinct (col, row) among the non-empty buckets, sorted by col, then by row:
+ *      out_row / out_col the pair, out_molecules the entries with kept != 0 and out_reads the sum of freq
+ *      (64 bits) over all buckets that carry it; *nnz their number.  Empty buckets contribute nothing, and
+ *      their ids are not looked at; a triplet may have 0 molecules.  The four arrays have room for
+ *      n_buckets triplets; what lies behind the first *nnz is not defined.
+ * n_buckets == 0 or every bucket empty: UMI_OK, *nnz = 0, nothing launched, nothing else touched.  A
+ * multi-device context uses its first device.  A deferred call (umi_dedup_batch_device_begin) that is out on
+ * the context ends first; its result keeps waiting for umi_dedup_batch_end.
+ * UMI_ERR_ARG: a NULL among ctx, nnz and the arrays the call would touch, n_buckets >= 2^30, a bucket_off
+ * that does not start at 0 or that falls (found on the host before anything is launched), n_rows == 0 or
+ * n_cols == 0 with a non-empty bucket, a non-empty bucket whose row >= n_rows or col >= n_cols (counted on the
+ * device, told after the call's synchronisation: *nnz is 0 and the outputs are not defined).
+ * The _device form takes and leaves everything but bucket_off and nnz in device memory and synchronises the
+ * stream once, at the end; the plain form copies host arrays in and out around it. */
+int umi_count_matrix_device(umi_ctx *ctx, const uint8_t *d_kept, const int32_t *d_freq, const uint64_t *bucket_off,
+                            uint64_t n_buckets, const uint32_t *d_row, const uint32_t *d_col, uint32_t n_rows,
+                            uint32_t n_cols, uint32_t *d_out_row, uint32_t *d_out_col, uint32_t *d_out_molecules,
+                            uint64_t *d_out_reads, uint64_t *nnz, void *hip_stream);
+int umi_count_matrix(umi_ctx *ctx, const uint8_t *kept, const int32_t *freq, const uint64_t *bucket_off,
+                     uint64_t n_buckets, const uint32_t *row, const uint32_t *col, uint32_t n_rows, uint32_t n_cols,
+                     uint32_t *out_row, uint32_t *out_col, uint32_t *out_molecules, uint64_t *out_reads, uint64_t *nnz);
+
 /* ---- batched path: replaces the whole bucket loop
  *      src/deduplicate_sam.rs:207-233 (apply::<UcSAMRead,Naive> per bucket,
  *      counters :217-219) = Directional/Adjacency::apply

@@ -419,6 +419,44 @@ class Context:
                                                  ptr(counts, C.c_uint64), stream or None))
         return counts
 
+    def count_matrix(self, kept, freq, bucket_off, row, col, n_rows, n_cols):
+        """Molecules and reads per (column, row) pair (umi_count_matrix): kept uint8 [N] and freq int32 [N] of a
+        batched call, bucket_off uint64 [n_buckets + 1], row / col uint32 [n_buckets] the row (gene) and column
+        (cell) of every bucket.  Returns (out_row, out_col, molecules uint32, reads uint64), one element per
+        distinct pair among the non-empty buckets, sorted by column, then row."""
+        kept = np.ascontiguousarray(kept, dtype=np.uint8)
+        freq = np.ascontiguousarray(freq, dtype=np.int32)
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        row = np.ascontiguousarray(row, dtype=np.uint32)
+        col = np.ascontiguousarray(col, dtype=np.uint32)
+        nb = len(bucket_off) - 1
+        if nb < 0 or len(row) != nb or len(col) != nb:
+            raise ValueError("row / col want one element per bucket")
+        if len(kept) != len(freq) or (nb and int(bucket_off.max()) > len(kept)):
+            raise ValueError("kept / freq lengths differ, or bucket_off runs past them")
+        m = max(1, nb)
+        o_row, o_col, o_mol = (np.zeros(m, np.uint32) for _ in range(3))
+        o_reads = np.zeros(m, np.uint64)
+        nnz = C.c_uint64(0)
+        check(load().umi_count_matrix(self._h, ptr(kept, C.c_uint8), ptr(freq, C.c_int32), ptr(bucket_off, C.c_uint64), nb,
+                                      ptr(row, C.c_uint32), ptr(col, C.c_uint32), n_rows, n_cols, ptr(o_row, C.c_uint32),
+                                      ptr(o_col, C.c_uint32), ptr(o_mol, C.c_uint32), ptr(o_reads, C.c_uint64),
+                                      C.byref(nnz)))
+        z = int(nnz.value)
+        return o_row[:z], o_col[:z], o_mol[:z], o_reads[:z]
+
+    def count_matrix_device(self, d_kept, d_freq, bucket_off, d_row, d_col, n_rows, n_cols, d_out_row, d_out_col,
+                            d_out_molecules, d_out_reads, stream=0):
+        """The same on raw device pointers (umi_count_matrix_device; bucket_off stays on the host): fills the
+        four output arrays (room for n_buckets elements each) and returns nnz."""
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        nnz = C.c_uint64(0)
+        check(load().umi_count_matrix_device(self._h, d_kept or None, d_freq or None, ptr(bucket_off, C.c_uint64),
+                                             len(bucket_off) - 1, d_row or None, d_col or None, n_rows, n_cols,
+                                             d_out_row or None, d_out_col or None, d_out_molecules or None,
+                                             d_out_reads or None, C.byref(nnz), stream or None))
+        return int(nnz.value)
+
     def stage_reads(self, align_key, umi_bytes, score, umi_len, merge=1, align_key_bits=64):
         """Read staging on the device (host arrays in and out): reads in file order ->
         dict(keys, nmask, freq, rep, bucket_off) in canonical order, the batched path's input

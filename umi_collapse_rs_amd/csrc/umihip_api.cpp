@@ -247,6 +247,10 @@ struct umi_ctx {
     DevBuf corr_ws, corr_umi, corr_out, corr_match, corr_best, corr_second;
     // correction of cell barcodes (umi_correct_barcodes*): packed list and index; the host-buffer form's arrays
     DevBuf bc_ws, bc_in, bc_match, bc_status;
+    // molecules per (column, row) pair (umi_count_matrix*): workspace; the host-buffer form's arrays in one block;
+    // pinned staging of the non-empty buckets' offsets and numbers
+    DevBuf cm_ws, cm_io;
+    PinnedBuf cm_h;
     uint32_t cons_split = 512; // clusters of at least this many reads are summed in pieces by the whole grid
     uint64_t *h_boff = nullptr;               // pinned staging of the bucket table
     size_t h_boff_cap = 0;
@@ -1926,8 +1930,10 @@ void umi_ctx_destroy(umi_ctx *ctx)
                       &ctx->seq_runid, &ctx->seq_rs, &ctx->seq_tend, &ctx->seq_tmp,
                       &ctx->cons_ws, &ctx->cons_seq, &ctx->cons_qual, &ctx->cons_off, &ctx->cons_cr,
                       &ctx->corr_ws, &ctx->corr_umi, &ctx->corr_out, &ctx->corr_match, &ctx->corr_best, &ctx->corr_second,
-                      &ctx->bc_ws, &ctx->bc_in, &ctx->bc_match, &ctx->bc_status};
+                      &ctx->bc_ws, &ctx->bc_in, &ctx->bc_match, &ctx->bc_status,
+                      &ctx->cm_ws, &ctx->cm_io};
     for (DevBuf *b : bufs) b->release();
+    ctx->cm_h.release();
     if (ctx->h_boff) (void)hipHostFree(ctx->h_boff);
     ctx->h_tasks.release();
     ctx->h_plan_alt[0].release();
@@ -3581,6 +3587,144 @@ int umi_correct_barcodes(umi_ctx *ctx, const uint8_t *bc_ascii, uint64_t n_reads
     HIP_TRY(hipMemcpyAsync(match, ctx->bc_match.p, n * 4, hipMemcpyDeviceToHost, s));
     if (status) HIP_TRY(hipMemcpyAsync(status, ctx->bc_status.p, n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return UMI_OK;
+}
+
+} // extern "C"
+
+// ---- molecules and reads per (column, row) pair ---------------------------------------------------
+namespace {
+// what both forms check before a device is looked at (the context last)
+int cm_check(umi_ctx *ctx, const void *kept, const void *freq, const uint64_t *bucket_off, uint64_t n_buckets, const void *row,
+             const void *col, const void *out_row, const void *out_col, const void *out_molecules, const void *out_reads,
+             const uint64_t *nnz)
+{
+    if (!nnz) return fail(UMI_ERR_ARG, "nnz is NULL");
+    if (n_buckets >= (1ull << 30))
+        return fail(UMI_ERR_ARG, "%llu buckets exceed the 30-bit index space of one call", (unsigned long long)n_buckets);
+    if (n_buckets && !bucket_off) return fail(UMI_ERR_ARG, "bucket_off is NULL");
+    if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
+    if (n_buckets && (!row || !col || !out_row || !out_col || !out_molecules || !out_reads))
+        return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (n_buckets && bucket_off[n_buckets] && (!kept || !freq)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
+    return UMI_OK;
+}
+
+// The table walked once into the pinned staging: its non-empty buckets' offsets (a run of equal offsets is
+// one) and, from the first empty bucket on, their numbers.  *m: the non-empty buckets; *idx: null where
+// nothing was left out.
+int cm_walk(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, uint32_t *m, const uint64_t **off, const uint32_t **idx)
+{
+    int rc;
+    const size_t off_bytes = ((size_t)n_buckets + 1) * 8;
+    if ((rc = ctx->cm_h.reserve(off_bytes + (size_t)n_buckets * 4))) return rc;
+    uint64_t *o = (uint64_t *)ctx->cm_h.p;
+    uint32_t *x = (uint32_t *)(ctx->cm_h.p + off_bytes);
+    uint32_t k = 0;
+    o[0] = 0;
+    for (uint64_t b = 0; b < n_buckets; b++) {
+        const uint64_t lo = bucket_off[b], hi = bucket_off[b + 1];
+        if (hi < lo) return fail(UMI_ERR_ARG, "bucket_off is not monotone at bucket %llu", (unsigned long long)b);
+        if (hi == lo) continue;
+        x[k] = (uint32_t)b;
+        o[++k] = hi;
+    }
+    *m = k;
+    *off = o;
+    *idx = k == n_buckets ? nullptr : x;
+    return UMI_OK;
+}
+
+int cm_run(umi_ctx *ctx, const uint8_t *d_kept, const int32_t *d_freq, uint32_t m, const uint64_t *h_off, const uint32_t *h_idx,
+           const uint32_t *d_row, const uint32_t *d_col, uint32_t n_rows, uint32_t n_cols, uint32_t *d_out_row, uint32_t *d_out_col,
+           uint32_t *d_out_molecules, uint64_t *d_out_reads, uint64_t *nnz, hipStream_t s)
+{
+    int rc;
+    if ((rc = ctx->cm_ws.reserve(count_workspace_bytes(m, h_idx != nullptr)))) return rc;
+    uint64_t bad = 0;
+    const int r = count_matrix_on_device(ctx->cm_ws.p, d_kept, d_freq, h_off, h_idx, m, d_row, d_col, n_rows, n_cols, d_out_row,
+                                         d_out_col, d_out_molecules, d_out_reads, nnz, &bad, (uint32_t)ctx->n_cus, ctx->h_counters, s);
+    if (r < 0) return fail(UMI_ERR_HIP, "count matrix: %s", hipGetErrorString((hipError_t)(-r)));
+    if (bad) {
+        *nnz = 0;
+        return fail(UMI_ERR_ARG, "%llu non-empty buckets have a row id of %u or more, or a column id of %u or more",
+                    (unsigned long long)bad, n_rows, n_cols);
+    }
+    return UMI_OK;
+}
+} // namespace
+
+extern "C" {
+
+int umi_count_matrix_device(umi_ctx *ctx, const uint8_t *d_kept, const int32_t *d_freq, const uint64_t *bucket_off,
+                            uint64_t n_buckets, const uint32_t *d_row, const uint32_t *d_col, uint32_t n_rows, uint32_t n_cols,
+                            uint32_t *d_out_row, uint32_t *d_out_col, uint32_t *d_out_molecules, uint64_t *d_out_reads,
+                            uint64_t *nnz, void *hip_stream)
+{
+    int rc = cm_check(ctx, d_kept, d_freq, bucket_off, n_buckets, d_row, d_col, d_out_row, d_out_col, d_out_molecules, d_out_reads, nnz);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_correct_barcodes)
+    *nnz = 0;
+    if (n_buckets == 0) return UMI_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
+    uint32_t m = 0;
+    const uint64_t *h_off = nullptr;
+    const uint32_t *h_idx = nullptr;
+    if ((rc = cm_walk(ctx, bucket_off, n_buckets, &m, &h_off, &h_idx))) return rc;
+    if (m == 0) return UMI_OK;
+    if (n_rows == 0 || n_cols == 0) return fail(UMI_ERR_ARG, "a matrix of %u rows and %u columns with a non-empty bucket", n_rows, n_cols);
+    return cm_run(ctx, d_kept, d_freq, m, h_off, h_idx, d_row, d_col, n_rows, n_cols, d_out_row, d_out_col, d_out_molecules,
+                  d_out_reads, nnz, (hipStream_t)hip_stream);
+}
+
+int umi_count_matrix(umi_ctx *ctx, const uint8_t *kept, const int32_t *freq, const uint64_t *bucket_off, uint64_t n_buckets,
+                     const uint32_t *row, const uint32_t *col, uint32_t n_rows, uint32_t n_cols, uint32_t *out_row,
+                     uint32_t *out_col, uint32_t *out_molecules, uint64_t *out_reads, uint64_t *nnz)
+{
+    int rc = cm_check(ctx, kept, freq, bucket_off, n_buckets, row, col, out_row, out_col, out_molecules, out_reads, nnz);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    *nnz = 0;
+    if (n_buckets == 0) return UMI_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx);
+    uint32_t m = 0;
+    const uint64_t *h_off = nullptr;
+    const uint32_t *h_idx = nullptr;
+    if ((rc = cm_walk(ctx, bucket_off, n_buckets, &m, &h_off, &h_idx))) return rc;
+    if (m == 0) return UMI_OK;
+    if (n_rows == 0 || n_cols == 0) return fail(UMI_ERR_ARG, "a matrix of %u rows and %u columns with a non-empty bucket", n_rows, n_cols);
+    // the host arrays' device copies in one block: freq | row | col | the four outputs | kept
+    const size_t n = (size_t)bucket_off[n_buckets], nb = (size_t)n_buckets, cap = (size_t)m;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_freq = 0, o_row = o_freq + up(n * 4), o_col = o_row + up(nb * 4), o_orow = o_col + up(nb * 4),
+                 o_ocol = o_orow + up(cap * 4), o_omol = o_ocol + up(cap * 4), o_oreads = o_omol + up(cap * 4),
+                 o_kept = o_oreads + up(cap * 8), total = o_kept + up(n);
+    if ((rc = ctx->cm_io.reserve(total))) return rc;
+    char *d = ctx->cm_io.as<char>();
+    hipStream_t s = ctx->own_stream;
+    HIP_TRY(hipMemcpyAsync(d + o_kept, kept, n, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_freq, freq, n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_row, row, nb * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_col, col, nb * 4, hipMemcpyHostToDevice, s));
+    uint64_t got = 0;
+    rc = cm_run(ctx, (const uint8_t *)(d + o_kept), (const int32_t *)(d + o_freq), m, h_off, h_idx, (const uint32_t *)(d + o_row),
+                (const uint32_t *)(d + o_col), n_rows, n_cols, (uint32_t *)(d + o_orow), (uint32_t *)(d + o_ocol),
+                (uint32_t *)(d + o_omol), (uint64_t *)(d + o_oreads), &got, s);
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    if (got) {
+        HIP_TRY(hipMemcpyAsync(out_row, d + o_orow, (size_t)got * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_col, d + o_ocol, (size_t)got * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_molecules, d + o_omol, (size_t)got * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_reads, d + o_oreads, (size_t)got * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    *nnz = got;
     return UMI_OK;
 }
 

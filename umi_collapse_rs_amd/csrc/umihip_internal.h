@@ -448,6 +448,18 @@ int barcode_on_device(void *workspace, const uint8_t *d_bc, uint32_t n_reads, in
                       int max_mismatches, int32_t *d_match, uint8_t *d_status, uint64_t counts[4], uint64_t *bad, uint32_t n_cus,
                       unsigned long long *h_pinned, hipStream_t s);
 
+// ---- molecules and reads per (column, row) pair (umihip_count.hip: umi_count_matrix) ----
+// h_off (pinned): the m + 1 offsets of the m >= 1 non-empty buckets; h_idx (pinned, null: nothing was left out):
+// their numbers in d_row / d_col.  The outputs take the triplets sorted by column, then row (capacity m);
+// *bad_ids: non-empty buckets with a row or column out of range (the outputs are then worthless).  One
+// synchronisation, at the end.  h_pinned: 2 pinned words.  0 ok; negative: -(hipError_t)
+size_t count_workspace_bytes(uint32_t m, bool has_idx);
+int count_matrix_on_device(void *workspace, const uint8_t *d_kept, const int32_t *d_freq, const uint64_t *h_off,
+                           const uint32_t *h_idx, uint32_t m, const uint32_t *d_row, const uint32_t *d_col, uint32_t n_rows,
+                           uint32_t n_cols, uint32_t *d_out_row, uint32_t *d_out_col, uint32_t *d_out_molecules,
+                           uint64_t *d_out_reads, uint64_t *nnz, uint64_t *bad_ids, uint32_t n_cus, unsigned long long *h_pinned,
+                           hipStream_t s);
+
 // ---- sort and scan primitives of the staging (umihip_radix.hip) ----
 constexpr int RADIX_BINS = 256, RADIX_MAX_PASSES = 8; // 8-bit digits; a 64-bit key has at most eight
 constexpr int RADIX_HIST_PARTS = 2048;                // blocks of a kernel that counts digits, at most

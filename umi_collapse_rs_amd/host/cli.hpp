@@ -1,5 +1,15 @@
 // `umicollapse`'s command line: the flags (Cli, parse, usage), the refusals that need no input file
 // (validate) and the lists the flags name (read_whitelist).
+//
+// --per-gene [--gene-tag XX] (bam/sam mode, one pass; umi_tools --per-gene / STARsolo's grouping, not the
+// reference's, tests/gene_model.py defines it): reads are grouped by gene -- with --per-cell by (cell, gene) --
+// and not by alignment position (staging.hpp has the rule, umicollapse_main.cpp the pipeline).
+// --count-matrix DIR (with --per-gene): the molecules per cell and gene, written to DIR as features.tsv,
+// barcodes.tsv, matrix.mtx and reads.mtx.  DIR is made here, while the flags are looked at (its parent must be
+// there; a directory that is there is used).  Refused with status 101 before the GPU is woken, each with a
+// message of its own: --per-gene with fastq mode, --two-pass, --paired, --keep-unmapped, --tag, --call-consensus
+// or --passthrough; --gene-tag without --per-gene, or not a tag name of two characters; --count-matrix without
+// --per-gene, with --dump-staging, or a DIR that cannot be made.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -8,6 +18,9 @@
 #include <string>
 #include <unordered_set>
 #include <vector>
+
+#include <cerrno>
+#include <sys/stat.h>
 
 #include "../../include/umihip.h"
 
@@ -50,6 +63,9 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     int cell_wl_max_mismatches = 1;     // --cell-whitelist-max-mismatches: 0 or 1
     bool cell_wl_max_given = false;
     bool wl_max_given = false, wl_min_given = false;
+    bool per_gene = false, gene_tag_given = false; // --per-gene: a bucket is a gene, with --per-cell a (cell, gene) pair
+    std::string gene_tag = "GX";                   // --gene-tag XX: the gene's tag
+    std::string count_matrix;                      // --count-matrix DIR: molecules per cell and gene, MatrixMarket files
     bool edit_distance = false; // --distance edit: -k bounds the Levenshtein distance (umi_dedup_batch_edit)
     // filled in by validate(): --algo as UMI_ALGO_*, --merge as 0 any, 1 avgqual, 2 mapqual, and the two lists
     int algo_id = 0, merge_id = 0;
@@ -128,6 +144,16 @@ void usage()
               "      --cell-whitelist-max-mismatches <M> 0: listed barcodes only; 1: one substitution allowed [default: 1]\n"
               "      --cell-whitelist-metrics <FILE> write a table: barcode, reads, exact, corrected per listed barcode\n"
               "                           that took a read, in list order\n"
+              "      --per-gene           deduplicate per gene: reads are grouped by gene (with --per-cell by cell and\n"
+              "                           gene) and not by alignment position, so a molecule fragmented at two places\n"
+              "                           is kept once; reads without a gene, or assigned to several, are dropped\n"
+              "                           (bam/sam mode, one pass; not with --paired, --tag, --keep-unmapped,\n"
+              "                           --call-consensus)\n"
+              "      --gene-tag <XX>      aux tag of the gene, type Z [default: GX]; no tag, an empty value, -, or a value\n"
+              "                           starting with __ or Unassigned: no gene; a value with ; or , : several genes\n"
+              "      --count-matrix <DIR> with --per-gene: write the molecules per cell and gene to DIR (made if it is\n"
+              "                           not there) as features.tsv, barcodes.tsv, matrix.mtx (molecules) and reads.mtx\n"
+              "                           (reads), MatrixMarket coordinate files sorted by cell, then gene, counted on the GPU\n"
               "      --device <ID>        GPU to use [default: 0]\n"
               "      --devices <ID,..>    several GPUs of the node: alignment positions are sharded over them");
 }
@@ -194,6 +220,9 @@ Cli parse(int argc, char **argv)
             else { c.cell_tag = t; c.cell_tag_given = true; }
         }
         else if (a == "--per-cell") c.per_cell = true;
+        else if (a == "--per-gene") c.per_gene = true;
+        else if (a == "--gene-tag") { c.gene_tag = need(i); c.gene_tag_given = true; } // (looked at by validate)
+        else if (a == "--count-matrix") c.count_matrix = need(i);
         else if (a == "--umi-whitelist") c.umi_whitelist = need(i);
         else if (a == "--whitelist-metrics") c.whitelist_metrics = need(i);
         else if (a == "--whitelist-max-mismatches" || a == "--whitelist-min-distance") {
@@ -315,6 +344,23 @@ bool validate(Cli &args)
     if (args.umi_whitelist.empty() && (args.wl_max_given || args.wl_min_given || !args.whitelist_metrics.empty()))
         die("--whitelist-max-mismatches, --whitelist-min-distance and --whitelist-metrics go with --umi-whitelist only");
     if (args.mode != "bam" && args.mode != "sam" && args.mode != "fastq") return false; // main.rs:49-95: nothing happens
+    // --per-gene, --count-matrix: likewise (the directory is made last, once nothing else refuses the run)
+    if (args.gene_tag_given && !args.per_gene) die("--gene-tag goes with --per-gene only");
+    if (!args.count_matrix.empty() && !args.per_gene) die("--count-matrix goes with --per-gene only");
+    if (args.per_gene) {
+        if (args.mode == "fastq") die("--per-gene is defined in bam/sam mode only (there are no tags in fastq mode)");
+        if (args.two_pass) die("--per-gene does not go with --two-pass (its census is by position)");
+        if (args.paired) die("--per-gene does not go with --paired");
+        if (args.keep_unmapped) die("--per-gene does not go with --keep-unmapped (an unmapped read has no gene)");
+        if (args.track_clusters) die("--per-gene does not go with --tag");
+        if (args.call_consensus) die("--per-gene does not go with --call-consensus (the reads of a gene do not line up)");
+        if (args.passthrough) die("--per-gene does not go with --passthrough");
+        const std::string &t = args.gene_tag;
+        auto alpha = [](char ch) { return (ch >= 'A' && ch <= 'Z') || (ch >= 'a' && ch <= 'z'); };
+        if (t.size() != 2 || !alpha(t[0]) || !(alpha(t[1]) || (t[1] >= '0' && t[1] <= '9')))
+            die("--gene-tag wants a tag name of two characters, [A-Za-z][A-Za-z0-9]: '" + t + "'");
+        if (!args.count_matrix.empty() && !args.dump_staging.empty()) die("--count-matrix does not go with --dump-staging");
+    }
     // --distance edit: everything about it that can be refused is, before the GPU is woken
     if (args.edit_distance) {
         if (args.mode == "fastq") die("--distance edit is defined in bam/sam mode only (whole reads are the key in fastq mode)");
@@ -352,6 +398,12 @@ bool validate(Cli &args)
     else if (args.merge == "avgqual") args.merge_id = 1;
     else if (args.merge == "mapqual") args.merge_id = 2;
     else die("Invalid algorithm combination: " + args.algo + " , " + args.merge + " and " + args.data);
+    if (!args.count_matrix.empty() && mkdir(args.count_matrix.c_str(), 0777) != 0) {
+        const int why = errno;
+        struct stat sb;
+        if (why != EEXIST || stat(args.count_matrix.c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode))
+            die("cannot make the directory " + args.count_matrix + " for --count-matrix: " + std::strerror(why));
+    }
     return true;
 }
 

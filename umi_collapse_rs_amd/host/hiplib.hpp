@@ -12,6 +12,9 @@
 // --umi-tag, --per-cell, --umi-whitelist, --call-consensus, --two-pass and both --stage values work as before;
 // the summary gains "UMI distance: edit".  Refused with status 101: any other value, fastq mode, several
 // --devices, a UMI length above 21 (-u, the whitelist's, or the first staged read's).
+//
+// --count-matrix DIR (with --per-gene): umi_count_matrix, the one library call behind the flag, is resolved only
+// when the flag is given, so that a library without it serves every other run.
 #pragma once
 #include <chrono>
 #include <dlfcn.h>
@@ -71,6 +74,9 @@ struct HipLib {
     // --cell-whitelist: likewise
     bool want_barcodes = false;
     decltype(&umi_correct_barcodes) correct_barcodes = nullptr;
+    // --count-matrix: likewise
+    bool want_count = false;
+    decltype(&umi_count_matrix) count_matrix = nullptr;
     // (the HIP runtime the library brings along: device buffers for the arrays above)
     int (*hip_set_device)(int) = nullptr; // (the current device is per thread: the context was made on another)
     int (*hip_malloc)(void **, size_t) = nullptr;
@@ -78,7 +84,8 @@ struct HipLib {
     std::string error;
     explicit HipLib(const Cli &args)
         : want_edit(args.edit_distance), want_consensus(args.consensus), want_consensus_bam(args.call_consensus),
-          want_correct(!args.whitelist.empty()), want_barcodes(!args.cell_list.empty())
+          want_correct(!args.whitelist.empty()), want_barcodes(!args.cell_list.empty()),
+          want_count(!args.count_matrix.empty())
     {
     }
     bool load()
@@ -118,6 +125,7 @@ struct HipLib {
         if (want_consensus_bam) consensus_bam = (decltype(consensus_bam))sym("umi_consensus_bam");
         if (want_correct) correct_umis = (decltype(correct_umis))sym("umi_correct_umis");
         if (want_barcodes) correct_barcodes = (decltype(correct_barcodes))sym("umi_correct_barcodes");
+        if (want_count) count_matrix = (decltype(count_matrix))sym("umi_count_matrix");
         hip_set_device = (decltype(hip_set_device))sym("hipSetDevice");
         hip_malloc = (decltype(hip_malloc))sym("hipMalloc");
         hip_memcpy = (decltype(hip_memcpy))sym("hipMemcpy");

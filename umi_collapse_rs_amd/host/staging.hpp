@@ -14,6 +14,21 @@
 // it as the group key of umi_stage_reads_grouped_wide.  Everything else -- merge, --paired (the first
 // mate's tags), --tag, --two-pass, --devices, --stage -- as without the flags; --dump-staging appends every
 // bucket's cell id.  A malformed aux block or a tag of another type ends the run with status 101.
+//
+// --per-gene (bam/sam mode, one pass; umi_tools --per-gene, Cell Ranger, STARsolo; tests/gene_model.py defines it):
+// a staged read's gene is the value of --gene-tag (default GX, type Z), compared byte for byte, and a bucket is
+// (gene) -- with --per-cell (cell, gene) -- whatever the alignment: strand, unclipped position, reference and
+// template length play no part, so one molecule fragmented at two places is one entry.  A tag of another type, a
+// malformed aux block or a value with a byte below 0x21 or above 0x7e ends the run with status 101.  A read
+// without the tag, with an empty value, the value "-", or a value that starts with "__" or "Unassigned" has no
+// gene (MISS_GENE: dropped like a read without its UMI tag, "Number of reads without a gene tag"); one whose
+// value holds ';' or ',' is assigned to several and dropped too ("Number of reads assigned to several genes").
+// A gene's id is the rank of its first appearance among the staged reads in file order.  In the host staging
+// the key's coord / ref_strand / tlen are zero and `gene` tells the buckets apart; the device staging gets a
+// constant alignment key of one bit and cell | gene << bits_of(n_cells) as the group key.  Bucket and entry
+// order, the merge rule and what is written are as ever.  The summary gains the two lines, "Number of genes"
+// and "Number of (cell, gene) groups" ("Number of gene groups" without --per-cell) and loses "Number of unique
+// alignment positions"; --dump-staging appends every bucket's gene id behind the cell ids.
 #pragma once
 #include <string_view>
 #include <unordered_map>
@@ -80,9 +95,10 @@ struct Entry { // one (alignment key, UMI): ReadFreq of src/utils/read_freq.rs +
 struct AlignKey {
     uint64_t coord, ref_strand, tlen;
     uint64_t cell = 0; // --per-cell: the barcode's dense id (first-appearance rank); 0 otherwise
+    uint64_t gene = 0; // --per-gene: the gene's dense id (the three alignment fields are then 0); 0 otherwise
     bool operator==(const AlignKey &o) const
     {
-        return coord == o.coord && ref_strand == o.ref_strand && tlen == o.tlen && cell == o.cell;
+        return coord == o.coord && ref_strand == o.ref_strand && tlen == o.tlen && cell == o.cell && gene == o.gene;
     }
 };
 
@@ -90,7 +106,7 @@ struct KeyHash {
     size_t operator()(const AlignKey &k) const
     {
         uint64_t x = k.coord * 0x9E3779B97F4A7C15ull ^ (k.ref_strand + 0x7F4A7C15u) ^ (k.tlen * 0xD6E8FEB86659FD93ull) ^
-                     (k.cell * 0x94D049BB133111EBull);
+                     (k.cell * 0x94D049BB133111EBull) ^ (k.gene * 0xC2B2AE3D27D4EB4Full);
         x ^= x >> 29;
         x *= 0xBF58476D1CE4E5B9ull;
         return (size_t)(x ^ (x >> 32));
@@ -166,14 +182,17 @@ const char *find_umi(const umi::bam::Record &r, uint8_t sep, size_t umi_length, 
     return nullptr;
 }
 
-// --umi-tag / --per-cell: the aux tags a staged read is looked up by.  Returns the bits of the ones it
-// lacks (MISS_UMI, MISS_CELL: the read is dropped, not written, and counted); err: the message that ends
-// the run (a malformed aux block, a tag that is not of type Z).
-enum : uint8_t { MISS_UMI = 1, MISS_CELL = 2 };
+// --umi-tag / --per-cell / --per-gene: the aux tags a staged read is looked up by.  Returns the bits of the ones
+// it lacks (MISS_UMI, MISS_CELL, MISS_GENE: the read is dropped, not written, and counted); err: the message
+// that ends the run (a malformed aux block, a tag that is not of type Z, a gene with a byte that is not a
+// printable character).
+enum : uint8_t { MISS_UMI = 1, MISS_CELL = 2, MISS_GENE = 4 };
 struct ReadTags {
     const uint8_t *umi = nullptr; // --umi-tag: the value
     size_t umi_len = 0;
     std::string_view cell;        // --per-cell: the barcode, an opaque byte string
+    std::string_view gene;        // --per-gene: the gene, likewise
+    bool several_genes = false;   // ... its value lists more than one (';' or ','): the read is dropped
 };
 uint8_t read_tags(const Cli &args, const umi::bam::Record &r, ReadTags &t, std::string &err)
 {
@@ -199,6 +218,21 @@ uint8_t read_tags(const Cli &args, const umi::bam::Record &r, ReadTags &t, std::
     if (args.per_cell) {
         if (look(args.cell_tag, f)) t.cell = std::string_view((const char *)f.value, f.len);
         else miss |= MISS_CELL;
+        if (!err.empty()) return 0;
+    }
+    if (args.per_gene) {
+        std::string_view g;
+        if (look(args.gene_tag, f)) g = std::string_view((const char *)f.value, f.len);
+        if (!err.empty()) return 0;
+        for (const char ch : g)
+            if ((uint8_t)ch < 0x21 || (uint8_t)ch > 0x7e) {
+                err = "tag " + args.gene_tag + " of read " + std::string((const char *)r.qname(), r.qname_len()) +
+                      " holds a byte that is not a printable character: " + std::to_string((unsigned)(uint8_t)ch);
+                return 0;
+            }
+        if (g.empty() || g == "-" || g.substr(0, 2) == "__" || g.substr(0, 10) == "Unassigned") miss |= MISS_GENE;
+        t.gene = g;
+        t.several_genes = g.find_first_of(";,") != std::string_view::npos;
     }
     return miss;
 }
@@ -309,6 +343,7 @@ void write_list_metrics(const std::string &path, const char *item, const std::ve
 // about tags and cells only) the --dump-staging exit
 struct Summary {
     size_t total_read_count = 0, unmapped = 0, unpaired = 0, chimeric = 0, no_umi_tag = 0, no_cell = 0;
+    size_t no_gene = 0, several_genes = 0, n_genes = 0; // --per-gene
     uint64_t cb_counts[4] = {0, 0, 0, 0}; // --cell-whitelist: exact, corrected, unlisted, ambiguous
     uint64_t wl_counts[3] = {0, 0, 0};    // --umi-whitelist: exact, corrected, uncorrectable
     size_t n_positions = 0, nb = 0, n = 0, max_umi = 0;
@@ -326,6 +361,10 @@ struct Summary {
         }
         if (!args.umi_tag.empty()) std::fprintf(stderr, "Number of reads without a UMI tag: %zu\n", no_umi_tag);
         if (args.per_cell) std::fprintf(stderr, "Number of reads without a cell barcode: %zu\n", no_cell);
+        if (args.per_gene) {
+            std::fprintf(stderr, "Number of reads without a gene tag: %zu\n", no_gene);
+            std::fprintf(stderr, "Number of reads assigned to several genes: %zu\n", several_genes);
+        }
         if (!args.cell_list.empty()) {
             std::fprintf(stderr, "Number of reads with a corrected cell barcode: %llu\n", (unsigned long long)cb_counts[1]);
             std::fprintf(stderr, "Number of reads with an unlisted cell barcode: %llu\n", (unsigned long long)cb_counts[2]);
@@ -335,8 +374,13 @@ struct Summary {
             std::fprintf(stderr, "Number of reads with a corrected UMI: %llu\n", (unsigned long long)wl_counts[1]);
             std::fprintf(stderr, "Number of reads with an uncorrectable UMI: %llu\n", (unsigned long long)wl_counts[2]);
         }
-        if (!dump_exit || args.per_cell) std::fprintf(stderr, "Number of unique alignment positions: %zu\n", n_positions);
-        if (args.per_cell) std::fprintf(stderr, "Number of (position, cell) groups: %zu\n", nb);
+        if (args.per_gene) { // (positions play no part)
+            std::fprintf(stderr, "Number of genes: %zu\n", n_genes);
+            std::fprintf(stderr, args.per_cell ? "Number of (cell, gene) groups: %zu\n" : "Number of gene groups: %zu\n", nb);
+        } else {
+            if (!dump_exit || args.per_cell) std::fprintf(stderr, "Number of unique alignment positions: %zu\n", n_positions);
+            if (args.per_cell) std::fprintf(stderr, "Number of (position, cell) groups: %zu\n", nb);
+        }
         if (dump_exit) return;
         std::fprintf(stderr, "Number of UMIs: %zu\n", n);
         std::fprintf(stderr, "Average number of UMIs per alignment position: %g\n", nb ? (double)n / (double)nb : 0.0);

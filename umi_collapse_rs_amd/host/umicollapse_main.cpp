@@ -54,6 +54,21 @@
 // as --tag.  Refused with status 101: with fastq mode, --tag, --two-pass, --paired, --dump-staging or
 // --passthrough; the second flag without the first or not a number >= 1; a staged read of more than 1024
 // bases.
+// --per-gene [--gene-tag XX] (bam/sam mode, one pass; not the reference's, tests/gene_model.py defines it): the
+// reads are grouped by gene -- with --per-cell by (cell, gene) -- and not by alignment position (staging.hpp has
+// the rule for a read's gene and for the reads that are dropped).  The genes are numbered after the two
+// whitelists have dropped their reads, by first appearance among the reads that are staged (number_genes); both
+// stagings, the collapse and the records written are as without the flag.  Goes with --umi-tag, --per-cell /
+// --cell-tag, --cell-whitelist, --umi-whitelist, -k, -p, --algo, --merge, --distance edit, --num-threads,
+// --devices and every --stage; refused with status 101: see cli.hpp.
+// --count-matrix DIR (with --per-gene): after the collapse one call to umi_count_matrix (include/umihip.h) sums
+// kept[] and freq[] over the buckets, row = the bucket's gene, column = its cell (one column without
+// --per-cell), and four files are written to DIR, uncompressed, lines ended by \n: features.tsv, a line
+// "<gene>\t<gene>\tGene Expression" per gene in id order; barcodes.tsv, a line per cell in id order -- the tag's
+// bytes, with --cell-whitelist the listed barcode, without --per-cell the one line "all"; matrix.mtx,
+// "%%MatrixMarket matrix coordinate integer general", then "G C NNZ", then NNZ lines "row col molecules", counted
+// from 1, by column and then row; reads.mtx, the same with the reads.  The molecules add up to "Number of reads
+// after deduplicating".
 // Not implemented, as in the reference: --algo cc.
 #include "fastq_mode.hpp"
 #include "hiplib.hpp"
@@ -70,9 +85,11 @@ struct ReadInfo {
                    // 6 dropped: it lacks a tag of --umi-tag / --per-cell (`missing` says which)
                    // 7 dropped: its UMI matches no listed one (--umi-whitelist)
                    // 8 dropped: its cell barcode is unlisted or ambiguous (--cell-whitelist)
+                   // 9 dropped: its gene tag names several genes (--per-gene)
     uint8_t unpaired, chimeric, missing;
     uint32_t umi_at; // offset of the UMI from the read name (a --umi-tag value lies behind it)
     uint32_t cell;   // --per-cell: the barcode's id, the thread's own during the per-read pass
+    uint32_t gene;   // --per-gene: the gene's id, likewise (until number_genes)
 };
 
 // three int32 aux fields appended to a record that has been copied to `out` and ends at o; returns the new end
@@ -129,6 +146,9 @@ struct OnePass {
     std::vector<std::vector<std::string_view>> cell_seen; // --per-cell: per thread, its barcodes in order of appearance
     U64s gkey; // GPU staging with --per-cell: every read's cell id, the group key
     size_t n_cells = 0;
+    std::vector<std::string_view> cell_names; // --count-matrix: what barcodes.tsv calls every cell, in id order
+    std::vector<std::vector<std::string_view>> gene_seen; // --per-gene: per thread, its genes in order of appearance
+    std::vector<std::string_view> gene_names;             // ... and all of them in id order
     std::vector<uint32_t> out_records; // the records to write, in order; first those written before dedup (--keep-unmapped, :104-106)
 
     // the staged arrays: unique (position, UMI) entries in canonical order
@@ -140,6 +160,7 @@ struct OnePass {
     std::vector<uint32_t> rep;
     std::vector<uint32_t> entry_of;    // host staging, --tag / --call-consensus: every staged read's entry
     std::vector<uint32_t> bucket_cell; // --per-cell: every bucket's cell id
+    std::vector<uint32_t> bucket_gene; // --per-gene: every bucket's gene id
 
     // the collapse and what is made of it
     std::vector<uint8_t> kept;
@@ -187,6 +208,7 @@ struct OnePass {
         if (!args.cell_list.empty()) correct_cells();
         else if (args.per_cell && !args.passthrough) number_cells(); // (--passthrough reads no tags)
         if (!args.whitelist.empty()) correct_umis();
+        if (args.per_gene) number_genes();
         lap("per-read");
         if (!gpu_stage && !args.passthrough) encode_all();
         count_reads();
@@ -200,6 +222,7 @@ struct OnePass {
             return 0;
         }
         collapse();
+        if (!args.count_matrix.empty()) count_matrix();
         if (need_clusters) number_clusters();
         select_records();
         if (args.call_consensus) call_consensus();
@@ -238,7 +261,7 @@ struct OnePass {
                     std::string err;
                     const uint8_t miss = read_tags(args, in.records[ri], tg, err); // (a read without its tags is not staged)
                     if (!err.empty()) die(err);
-                    if (miss) continue;
+                    if (miss || tg.several_genes) continue;
                     umi_length = detect_length(args, in.records[ri], tg);
                     break;
                 }
@@ -296,7 +319,9 @@ struct OnePass {
         // in cache.
         std::vector<std::unordered_map<std::string_view, uint32_t>> cell_ids(args.per_cell ? T : 0);
         cell_seen.assign(args.per_cell ? T : 0, {});
-        if (gpu_stage && args.per_cell) gkey.resize(n_rec);
+        std::vector<std::unordered_map<std::string_view, uint32_t>> gene_ids(args.per_gene ? T : 0); // --per-gene: likewise
+        gene_seen.assign(args.per_gene ? T : 0, {});
+        if (gpu_stage && (args.per_cell || args.per_gene)) gkey.resize(n_rec);
         umi::bgzf::parallel_for(T, T, [&](size_t t) {
             const uint32_t lo = (uint32_t)t * chunk, hi = std::min(n_rec, lo + chunk);
             // (the thread's extremes in locals: sixteen threads updating neighbours of one cache line
@@ -309,9 +334,10 @@ struct OnePass {
                 ii.tlen = 0;
                 ii.missing = 0;
                 ii.cell = 0;
+                ii.gene = 0;
                 ii.state = read_state(args, r, ii.unpaired, ii.chimeric);
                 if (ii.state != 0 || args.passthrough) continue;
-                const AlignKey ak = align_key(r, args.paired);
+                const AlignKey ak = args.per_gene ? AlignKey{0, 0, 0} : align_key(r, args.paired); // (--per-gene: no part)
                 ii.coord = ak.coord;
                 ii.ref_strand = ak.ref_strand;
                 ii.tlen = ak.tlen;
@@ -319,10 +345,14 @@ struct OnePass {
                 size_t at = 0;
                 std::string err;
                 ReadTags tg;
-                if (!args.umi_tag.empty() || args.per_cell) {
+                if (!args.umi_tag.empty() || args.per_cell || args.per_gene) {
                     ii.missing = read_tags(args, r, tg, err);
                     if (ii.missing && err.empty()) {
                         ii.state = 6;
+                        continue;
+                    }
+                    if (tg.several_genes && err.empty()) {
+                        ii.state = 9;
                         continue;
                     }
                 }
@@ -352,6 +382,11 @@ struct OnePass {
                     const auto id = cell_ids[t].emplace(tg.cell, (uint32_t)cell_seen[t].size());
                     if (id.second) cell_seen[t].push_back(tg.cell);
                     ii.cell = id.first->second;
+                }
+                if (args.per_gene) {
+                    const auto id = gene_ids[t].emplace(tg.gene, (uint32_t)gene_seen[t].size());
+                    if (id.second) gene_seen[t].push_back(tg.gene);
+                    ii.gene = id.first->second;
                 }
                 ii.score = merge == 2 ? (int32_t)r.mapq() : r.avg_qual();
                 ii.umi_at = (uint32_t)at;
@@ -400,7 +435,10 @@ struct OnePass {
                 continue;
             }
             uint32_t &id = id_of[(size_t)cb_match[j]];
-            if (id == UINT32_MAX) id = next_id++;
+            if (id == UINT32_MAX) {
+                id = next_id++;
+                cell_names.emplace_back((const char *)&args.cell_list[(size_t)cb_match[j] * L], L); // (the listed barcode)
+            }
             ii.cell = id;
             if (gpu_stage) gkey[cand[j]] = id;
         }
@@ -419,6 +457,8 @@ struct OnePass {
             for (const std::string_view &bc : cell_seen[t])
                 to_global[t].push_back(global.emplace(bc, (uint32_t)global.size()).first->second);
         n_cells = global.size();
+        cell_names.resize(n_cells);
+        for (const auto &g : global) cell_names[g.second] = g.first;
         umi::bgzf::parallel_for(T, T, [&](size_t t) {
             const uint32_t lo = (uint32_t)t * chunk, hi = std::min(n_rec, lo + chunk);
             for (uint32_t ri = lo; ri < hi; ri++)
@@ -427,6 +467,32 @@ struct OnePass {
                     if (gpu_stage) gkey[ri] = info[ri].cell;
                 }
         });
+    }
+
+    // --per-gene: the threads' gene numbers -> ranks of first appearance among the reads that are staged (the
+    // whitelists have dropped theirs), the threads' reads walked in file order; the device staging's group key is
+    // cell | gene << bits_of(n_cells)
+    void number_genes()
+    {
+        std::unordered_map<std::string_view, uint32_t> global;
+        const int cell_bits = bits_of(n_cells);
+        for (unsigned t = 0; t < T; t++) {
+            std::vector<uint32_t> to_global(gene_seen[t].size(), UINT32_MAX);
+            const uint32_t lo = t * chunk, hi = std::min(n_rec, lo + chunk);
+            for (uint32_t ri = lo; ri < hi; ri++) {
+                ReadInfo &ii = info[ri];
+                if (ii.state != 0) continue;
+                uint32_t &g = to_global[ii.gene];
+                if (g == UINT32_MAX) {
+                    const auto id = global.emplace(gene_seen[t][ii.gene], (uint32_t)gene_names.size());
+                    if (id.second) gene_names.push_back(id.first->first);
+                    g = id.first->second;
+                }
+                ii.gene = g;
+                if (gpu_stage) gkey[ri] = (uint64_t)ii.cell | ((uint64_t)g << cell_bits);
+            }
+        }
+        sum.n_genes = gene_names.size();
     }
 
     // --umi-whitelist: the UMIs of the reads that would be staged, snapped to the list in one call; a read
@@ -472,7 +538,9 @@ struct OnePass {
             if (info[ri].state == 6) {
                 sum.no_umi_tag += (info[ri].missing & MISS_UMI) ? 1 : 0;
                 sum.no_cell += (info[ri].missing & MISS_CELL) ? 1 : 0;
+                sum.no_gene += (info[ri].missing & MISS_GENE) ? 1 : 0;
             }
+            if (info[ri].state == 9) sum.several_genes++;
             sum.unpaired += info[ri].unpaired;
             sum.chimeric += info[ri].chimeric;
             if (info[ri].state == 4) sum.unmapped++; // :118-121
@@ -518,8 +586,8 @@ struct OnePass {
         // The alignment key in as few bits as the file needs -- (ref, strand) code above the coordinate
         // counted from the smallest one -- so that with the UMI it fits the device sort's one 64-bit key
         // (a human genome: 6 + 28 bits, and 28 more for 12 bases)
-        int akey_bits = 64;
-        if (gpu_stage && ns) {
+        int akey_bits = args.per_gene ? 1 : 64; // (--per-gene: the alignment key is the constant 0, and the call refuses 0 bits)
+        if (gpu_stage && ns && !args.per_gene) {
             const int64_t lo = *std::min_element(c_min.begin(), c_min.end()), hi = *std::max_element(c_max.begin(), c_max.end());
             const uint64_t rs_hi = *std::max_element(rs_max.begin(), rs_max.end());
             const int cbits = bits_of((uint64_t)(hi - lo)), rbits = bits_of(rs_hi);
@@ -543,9 +611,11 @@ struct OnePass {
         lap("wait-gpu");
         keys.resize(ns * n_words); nmask.resize(ns * n_words); freq.resize(ns); off.resize(ns + 1);
         uint64_t ne = 0, nbk = 0;
-        if (args.per_cell && !lib.stage_reads_grouped) die("libumihip.so lacks umi_stage_reads_grouped_wide");
-        const int rc = args.per_cell
-                           ? lib.stage_reads_grouped(ctx, akey.data(), akey_bits, gkey.data(), bits_of(n_cells), umis.data(),
+        const bool grouped = args.per_cell || args.per_gene;
+        if (grouped && !lib.stage_reads_grouped) die("libumihip.so lacks umi_stage_reads_grouped_wide");
+        const int group_bits = bits_of(n_cells) + (args.per_gene ? bits_of(sum.n_genes) : 0);
+        const int rc = grouped
+                           ? lib.stage_reads_grouped(ctx, akey.data(), akey_bits, gkey.data(), group_bits, umis.data(),
                                                      sc.data(), ns, (int)umi_length, n_words, merge != 0 ? 1 : 0,
                                                      keys.data(), nmask.data(), freq.data(), rep64.data(), off.data(),
                                                      &ne, &nbk)
@@ -576,7 +646,7 @@ struct OnePass {
         std::vector<Shard> shards(args.passthrough ? 0 : T);
         entry_of.assign(need_clusters ? n_rec : 0, 0); // read -> its entry (--tag, --call-consensus): its shard's number first
         const KeyHash hasher;
-        auto key_of = [&](const ReadInfo &ii) { return AlignKey{ii.coord, ii.ref_strand, ii.tlen, ii.cell}; };
+        auto key_of = [&](const ReadInfo &ii) { return AlignKey{ii.coord, ii.ref_strand, ii.tlen, ii.cell, ii.gene}; };
         umi::bgzf::parallel_for(shards.size(), T, [&](size_t t) {
             Shard &sh = shards[t];
             for (uint32_t ri = 0; ri < n_rec; ri++) {
@@ -649,6 +719,10 @@ struct OnePass {
             }
             sum.n_positions = positions.size();
         }
+        if (args.per_gene) {
+            bucket_gene.resize(nb);
+            for (size_t b = 0; b < nb; b++) bucket_gene[b] = info[rep[off[b]]].gene;
+        }
         t_stage0 = now_s();
         std::fprintf(stderr, "UMI collapsing reading finished in %.3f seconds\n", t_stage0 - t_start); // :178-183
     }
@@ -666,6 +740,7 @@ struct OnePass {
         }
         std::fwrite(off.data(), 8, nb + 1, f);
         if (args.per_cell) std::fwrite(bucket_cell.data(), 4, nb, f); // (--per-cell: every bucket's cell id)
+        if (args.per_gene) std::fwrite(bucket_gene.data(), 4, nb, f); // (--per-gene: every bucket's gene id)
         std::fclose(f);
         sum.print(args, true);
     }
@@ -691,6 +766,50 @@ struct OnePass {
         }
         // (the context is not put away: tearing the HIP runtime down costs a process that lives half
         // a second another 0.1 s, and the process ends below without running destructors)
+    }
+
+    // --count-matrix: molecules and reads per (cell, gene) in one call over the collapse's kept[] and the staged
+    // freq[], then the four files
+    void count_matrix()
+    {
+        const uint32_t n_rows = (uint32_t)sum.n_genes, n_cols = args.per_cell ? (uint32_t)n_cells : 1u;
+        std::vector<uint32_t> out_row(nb + 1), out_col(nb + 1), molecules(nb + 1);
+        std::vector<uint64_t> reads(nb + 1);
+        uint64_t nnz = 0;
+        if (nb) {
+            need_ctx();
+            if (!lib.count_matrix) die("libumihip.so lacks umi_count_matrix");
+            const std::vector<uint32_t> one_column(args.per_cell ? 0 : nb, 0u);
+            if (lib.count_matrix(ctx, kept.data(), freq.data(), off.data(), nb, bucket_gene.data(),
+                                 args.per_cell ? bucket_cell.data() : one_column.data(), n_rows, n_cols, out_row.data(),
+                                 out_col.data(), molecules.data(), reads.data(), &nnz) != UMI_OK)
+                die(lib.last_error());
+        }
+        auto write = [&](const char *name, const std::string &text) {
+            const std::string path = args.count_matrix + "/" + name;
+            FILE *f = std::fopen(path.c_str(), "wb");
+            if (!f) die("cannot open " + path);
+            const bool ok = std::fwrite(text.data(), 1, text.size(), f) == text.size();
+            if (std::fclose(f) != 0 || !ok) die("cannot write " + path);
+        };
+        std::string text;
+        for (const std::string_view &g : gene_names) text.append(g).append("\t").append(g).append("\tGene Expression\n");
+        write("features.tsv", text);
+        text.clear();
+        if (!args.per_cell) text = "all\n";
+        for (size_t c = 0; c < n_cols && args.per_cell; c++) text.append(cell_names[c]).append("\n");
+        write("barcodes.tsv", text);
+        const std::string head = "%%MatrixMarket matrix coordinate integer general\n" + std::to_string(n_rows) + " " +
+                                 std::to_string(n_cols) + " " + std::to_string(nnz) + "\n";
+        std::string mol = head, rd = head;
+        for (uint64_t i = 0; i < nnz; i++) {
+            const std::string at = std::to_string(out_row[i] + 1) + " " + std::to_string(out_col[i] + 1) + " ";
+            mol.append(at).append(std::to_string(molecules[i])).append("\n");
+            rd.append(at).append(std::to_string(reads[i])).append("\n");
+        }
+        write("matrix.mtx", mol);
+        write("reads.mtx", rd);
+        lap("count matrix");
     }
 
     // --tag, --call-consensus: cluster id / size per entry from the root of every entry.  Survivors in index
