@@ -36,6 +36,7 @@ extern "C" {
 
 #define UMI_ALGO_DIRECTIONAL 0 /* src/algo/directional.rs */
 #define UMI_ALGO_ADJACENCY 1   /* src/algo/adjacency.rs  */
+#define UMI_ALGO_CLUSTER 2     /* connected components of "within k" (the reference's unimplemented `cc`) */
 
 #define UMI_MAX_UMI_LEN 21 /* one 64-bit word per key (3 bits per base) */
 #define UMI_MAX_WIDE_UMI_LEN 85 /* the _wide entry points: up to 4 words per key */
@@ -166,6 +167,8 @@ int umi_encode_umis(const uint8_t *ascii, uint64_t n, int umi_len, uint64_t *key
  *      (two UMIs within k overall are within k there) with every candidate pair decided on all words,
  *      the ones in between through an exact all-pairs kernel; a multi-device context shards the
  *      positions as for one-word keys.  Dual 12 + 12 UMIs are the 24-base, two-word case.
+ *      algo = UMI_ALGO_CLUSTER: the connected components of that distance <= k (no fused kernel for these
+ *      keys in that mode: the positions of up to 128 UMIs go through the all-pairs kernel as well).
  *      umi_encode_umis_wide is to_bitset (src/utils/mod.rs:63-83) for these lengths, host code. */
 int umi_encode_umis_wide(const uint8_t *ascii, uint64_t n, int umi_len, int n_words, uint64_t *keys,
                          uint64_t *nmask);
@@ -185,7 +188,7 @@ int umi_dedup_batch_wide_device(umi_ctx *ctx, const uint64_t *d_keys, const uint
  *      n_words >= ceil(3 * bucket_len[b] / 64) for every bucket.  Bucket b uses the first
  *      ceil(3 * bucket_len[b] / 64) words of its keys (bucket_len[b] in 0..UMI_MAX_SEQ_LEN), the words
  *      behind them are zero.  Everything else -- rank order inside a bucket, kept / root, stats, any
- *      k >= 0, UMI_ERR_* -- as in umi_dedup_batch_wide; the distance is the reference's per-word
+ *      k >= 0, algo (UMI_ALGO_CLUSTER included), UMI_ERR_* -- as in umi_dedup_batch_wide; the distance is the reference's per-word
  *      arithmetic (src/utils/bitset.rs:77-91), straddling bases included.  Deep buckets are cut into
  *      k + 1 parts of the whole read and only pairs that agree exactly on one part are evaluated
  *      (n_pairs_evaluated counts them; kernel_id UMI_KERNEL_SEQ_PAIRS).  A multi-device context is
@@ -501,6 +504,20 @@ int umi_count_matrix(umi_ctx *ctx, const uint8_t *kept, const int32_t *freq, con
  * reference's output order (deduplicate_sam.rs:227-231).  root (may be NULL):
  * global index of the root that removed entry i (ClusterTracker::add_all,
  * directional.rs:42-44).  stats may be NULL.
+ * algo = UMI_ALGO_CLUSTER: connected components.  Per bucket, the graph on its entries with an edge
+ * i ~ j iff dist(i, j) <= k (the distance of the entry point: umi_dist here, the per-word arithmetic in
+ * the _wide and _seqs forms, d_E in umi_dedup_batch_edit; N semantics and any k as for the other two).
+ * kept[i] = 1 iff i is the smallest index of its connected component, root[i] = that smallest index --
+ * in rank order the entry the root loop reaches first.  Frequencies take no part in the result:
+ * percentage is accepted with any bit pattern (NaN, negative, inf) and ignored, and so is adj_max_freq.
+ * The bucket contract holds and is checked all the same (freq >= 1 and non-increasing inside a bucket,
+ * nmask covering every N code: UMI_ERR_ORDER); freq = INT32_MAX is legal, there is no threshold to wrap.
+ * It is the `cc` the reference's help names and its main() refuses (src/cli.rs:33-36,
+ * src/main.rs:86-91), umi_tools' `--method cluster`, with k = 1 STARsolo's `--soloUMIdedup 1MM_All`, and
+ * -- while freq < 2^31 - 1 -- the directional result at percentage = +inf.  umi_stats: n_edges = the pairs
+ * within k found outside the fused buckets, each once; n_rounds <= 1 (the union pass; no round along
+ * one-way pairs exists); the other counters as for a directional call on the same path.  Any other algo
+ * value is UMI_ERR_ARG.
  * Buffers are caller-owned host memory; the library never frees them. */
 int umi_dedup_batch(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask,
                     const int32_t *freq, const uint64_t *bucket_off, uint64_t n_buckets,
@@ -538,7 +555,8 @@ int umi_dedup_batch_device_table(umi_ctx *ctx, const uint64_t *d_keys, const uin
  *      two letters match iff they are the same letter (N matches N and nothing else, as in umi_dist).
  *      For equal lengths d_E <= d_H, and d_E == d_H wherever either is at most 1 -- one indel alone changes
  *      the length, so an indel costs 2 and k <= 1 gives umi_dedup_batch's result bit for bit; the two differ
- *      from k = 2 on.  Rank order inside a bucket, the f32 threshold, algo, adj_max_freq, kept / root, stats,
+ *      from k = 2 on.  Rank order inside a bucket, the f32 threshold, algo (UMI_ALGO_CLUSTER: the connected
+ *      components of d_E <= k), adj_max_freq, kept / root, stats,
  *      UMI_ERR_ORDER: as umi_dedup_batch.  Any k >= 0 up to INT_MAX; min(k, umi_len) is what is computed
  *      with (no distance is larger), k >= umi_len means every pair of a bucket.
  *      Keys are one word, umi_len 1..UMI_MAX_UMI_LEN; code 100 in a key is N, so nmask may be NULL whatever
@@ -605,7 +623,8 @@ int umi_dedup_batch_device_multi(umi_ctx *ctx, const uint64_t *const *d_keys, co
  *      device); the result equals umi_dedup_batch_device on the same inputs. ------------ */
 /* part in [0, n_parts), n_parts >= 2.  d_edges: caller's device buffer of edge_capacity
  * entries; *n_edges_out = entries produced (if it exceeds edge_capacity: UMI_ERR_NOMEM,
- * nothing copied, call again with a larger buffer). */
+ * nothing copied, call again with a larger buffer).  algo = UMI_ALGO_CLUSTER: every pair within k,
+ * each once and every one flagged. */
 int umi_pairs_partial_device(umi_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_nmask,
                              const int32_t *d_freq, const uint64_t *bucket_off,
                              uint64_t n_buckets, int umi_len, int k, float percentage, int algo,
@@ -613,7 +632,9 @@ int umi_pairs_partial_device(umi_ctx *ctx, const uint64_t *d_keys, const uint64_
                              uint64_t *d_edges, uint64_t edge_capacity, uint64_t *n_edges_out,
                              void *hip_stream, umi_stats *stats);
 /* Collapse of a gathered edge list over n entries (same index space as the calls that
- * produced it): kept / root as in umi_dedup_batch_device. */
+ * produced it): kept / root as in umi_dedup_batch_device.  algo = UMI_ALGO_CLUSTER: the unions of the
+ * flagged entries and one write-out (the lists of a cluster call hold no other; an entry without the flag
+ * is the caller's error and is not looked at). */
 int umi_collapse_edges_device(umi_ctx *ctx, uint64_t n, const uint64_t *d_edges, uint64_t n_edges,
                               int algo, uint8_t *d_kept, uint32_t *d_root, void *hip_stream,
                               umi_stats *stats);

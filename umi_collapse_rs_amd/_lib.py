@@ -10,7 +10,7 @@ LIB_PATH = os.environ.get("UMIHIP_LIB") or os.path.join(_HERE, "libumihip.so")
 UMI_OK = 0
 UMI_ERR_ARG, UMI_ERR_HIP, UMI_ERR_ORDER, UMI_ERR_NOMEM, UMI_ERR_NODEV, UMI_ERR_CHAR = (
     -1, -2, -3, -4, -5, -6)
-UMI_ALGO_DIRECTIONAL, UMI_ALGO_ADJACENCY = 0, 1
+UMI_ALGO_DIRECTIONAL, UMI_ALGO_ADJACENCY, UMI_ALGO_CLUSTER = 0, 1, 2
 UMI_MAX_UMI_LEN = 21
 UMI_KERNEL_EDIT_PAIRS = 4     # Stats.kernel_id of umi_dedup_batch_edit (with "profile")
 UMI_MAX_CONS_LEN = 1024       # umi_consensus_bam: bases of a cluster, at most

@@ -2,7 +2,7 @@
 of the C ABI (include/umihip.h):
 
     trait DataStruct  (src/data/mod.rs:11-17)   -> HipNaive
-    trait Algorithm   (src/algo/mod.rs:13-20)    -> Directional, Adjacency
+    trait Algorithm   (src/algo/mod.rs:13-20)    -> Directional, Adjacency, Cluster
     bucket loop       (src/deduplicate_sam.rs:207-233) -> Context.dedup_batch
 
 Same names, argument meaning and error behaviour as the reference (where the
@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (UMI_ALGO_ADJACENCY, UMI_ALGO_DIRECTIONAL, Stats, UmiHipError, check, load, ptr)
+from ._lib import (UMI_ALGO_ADJACENCY, UMI_ALGO_CLUSTER, UMI_ALGO_DIRECTIONAL, Stats, UmiHipError, check, load, ptr)
 
 
 def to_bitset(umis, umi_len=None):
@@ -800,5 +800,36 @@ class Adjacency:
                 near = data.remove_near(umi, self.k, self.max_freq)
                 if tracker is not None:
                     tracker[umi] = sorted(near)
+                res.append(rf.read)
+        return res
+
+
+class Cluster:
+    """Connected components of "within k" (UMI_ALGO_CLUSTER; umi_tools' `cluster`, UMICollapse's `cc`,
+    STARsolo's 1MM_All at k = 1): the root loop of Directional with every neighbour admitted whatever its
+    freq -- remove_near(u, k, INT32_MAX), followed transitively -- so a root takes its whole component
+    and the survivor is the component's first UMI in rank order.  percentage is accepted and plays no part."""
+
+    def __init__(self, k=1, percentage=0.5, track_cluster=False):
+        self.k, self.percentage, self.track_cluster = k, percentage, track_cluster
+
+    def apply(self, reads, tracker, umi_length, data_struct=HipNaive):
+        """reads: dict umi -> ReadFreq in first-appearance order.  Returns list of reads."""
+        data_member = {umi: rf.freq for umi, rf in reads.items()}
+        umi_freqs = sorted(reads.items(), key=lambda kv: -kv[1].freq)  # stable
+        data = data_struct.new(data_member, umi_length, self.k)
+        res = []
+        for umi, rf in umi_freqs:
+            if data.contains(umi):
+                cluster = [] if (self.track_cluster and tracker is not None) else None
+                stack = [umi]
+                while stack:
+                    u = stack.pop()
+                    near = data.remove_near(u, self.k, 2 ** 31 - 1)
+                    if cluster is not None:
+                        cluster.extend(near)
+                    stack.extend(v for v in near if v != u)
+                if cluster is not None:
+                    tracker[umi] = cluster
                 res.append(rf.read)
         return res

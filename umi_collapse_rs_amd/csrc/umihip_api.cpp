@@ -285,6 +285,13 @@ namespace {
 // the kernels see, so that their 2 k and 2 k + 1 stay far inside an int.
 constexpr int BATCH_MAX_K = 32 * 4;
 
+// the one place an `algo` of the interface becomes a mode of the pipeline
+bool known_algo(int algo) { return algo == UMI_ALGO_DIRECTIONAL || algo == UMI_ALGO_ADJACENCY || algo == UMI_ALGO_CLUSTER; }
+int mode_of(int algo)
+{
+    return algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : algo == UMI_ALGO_CLUSTER ? MODE_CLUSTER : MODE_ADJACENCY;
+}
+
 int check_common(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, int k,
                  int algo, uint64_t *n_out, int max_len = UMI_MAX_UMI_LEN)
 {
@@ -293,7 +300,7 @@ int check_common(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, i
     if (umi_len < 1 || umi_len > max_len)
         return fail(UMI_ERR_ARG, "umi_len %d outside 1..%d", umi_len, max_len);
     if (k < 0) return fail(UMI_ERR_ARG, "k must be >= 0 (got %d)", k);
-    if (algo != UMI_ALGO_DIRECTIONAL && algo != UMI_ALGO_ADJACENCY)
+    if (!known_algo(algo))
         return fail(UMI_ERR_ARG, "unknown algo %d", algo);
     // (that the table is monotone is checked while it is copied to its pinned staging buffer,
     // before anything is launched: Pipeline::upload_and_prep)
@@ -486,8 +493,11 @@ class Pipeline {
     // directional path (and the reference's adjacency, which needs no pairs) without those tiles.
     bool one_sync() const
     {
-        return (mode == MODE_DIRECTIONAL || !need_pairs) && n_parts == 1 && ctx->two_phase == 2 && !legacy_tiles();
+        return (mode == MODE_DIRECTIONAL || mode == MODE_CLUSTER || !need_pairs) && n_parts == 1 && ctx->two_phase == 2 &&
+               !legacy_tiles();
     }
+    // the forest of the unions is the result (MODE_CLUSTER) or the first phase of it (MODE_DIRECTIONAL)
+    bool unions_collapse() const { return mode == MODE_DIRECTIONAL || mode == MODE_CLUSTER; }
 
     int run_stages()
     {
@@ -531,7 +541,10 @@ class Pipeline {
         if (need_pairs && pl.seg_parts)
             HIP_TRY(launch_seg_build(seg, ctx->fkey.p, d_freq, key32, d_cnt, s));
         if ((rc = upload_bitsliced())) return rc;
-        if (one_sync()) return run_one_sync();
+        if (one_sync()) return mode == MODE_CLUSTER ? run_cluster() : run_one_sync();
+        // (connected components have the one collapse path: what keeps a call off it are development options)
+        if (mode == MODE_CLUSTER && n_parts == 1)
+            return fail(UMI_ERR_ARG, "algo cluster does not run with the development option two_phase below 2");
         if ((rc = pair_stage())) return rc;
         if (mode == MODE_NEIGHBOURS || n_parts > 1) return finish_neighbours();
         if (mode == MODE_DIRECTIONAL || !need_pairs)
@@ -620,12 +633,16 @@ class Pipeline {
     {
         // (the table is monotone: upload_table has looked)
         scan_table_range(bucket_off, 0, n_buckets, fused_max, nullptr, ctx->table_pass);
-        const bool seg_on = ctx->seg_index && need_pairs && !ctx->prune && !edit;
-        build_plan(bucket_off, n_buckets, wide() || edit ? 0x7FFFFFFFu : ctx->small_max, ctx->use_bitslice && k <= BS_MAX_K && !wide() && !edit,
-                   plan_umi_len(), fused_max, ctx->prune, ctx->bs_sorted && ctx->bs_unit == 2 && need_pairs,
-                   ctx->bs_tables && key32, ctx->bs_tab_min_run, seg_on ? std::max(ctx->seg_min, 1u) : 0u, k, key32, pl,
+        // (connected components: the popcount tiles and the segment index only -- the development build's
+        // bit-sliced tiles keep an overflow list of their own, which that mode's one collapse path does not read)
+        const bool dev_tiles = mode != MODE_CLUSTER;
+        const bool seg_on = ctx->seg_index && need_pairs && !(ctx->prune && dev_tiles) && !edit;
+        build_plan(bucket_off, n_buckets, wide() || edit ? 0x7FFFFFFFu : ctx->small_max,
+                   ctx->use_bitslice && k <= BS_MAX_K && !wide() && !edit && dev_tiles,
+                   plan_umi_len(), fused_max, ctx->prune && dev_tiles, ctx->bs_sorted && ctx->bs_unit == 2 && need_pairs && dev_tiles,
+                   ctx->bs_tables && key32 && dev_tiles, ctx->bs_tab_min_run, seg_on ? std::max(ctx->seg_min, 1u) : 0u, k, key32, pl,
                    &ctx->table_pass);
-        prune = ctx->prune && need_pairs && !pl.bs_buckets.empty() && !wide() && !edit;
+        prune = ctx->prune && dev_tiles && need_pairs && !pl.bs_buckets.empty() && !wide() && !edit;
         keep_my_share(pl.small_tasks);
         keep_my_share(pl.big_tasks);
         st.max_bucket = pl.max_bucket;
@@ -722,7 +739,7 @@ class Pipeline {
             seg.col_sliced = ctx->seg_sliced ? 1u : 0u;
             // part 0 in LDS: where the pair kernel would unite symmetric pairs on the spot (the batched
             // directional path, one device's whole call) and compares 32-bit compare keys
-            if (ctx->seg_local && ctx->seg_unite && mode == MODE_DIRECTIONAL && one_sync() && seg.use_ckey) {
+            if (ctx->seg_local && ctx->seg_unite && unions_collapse() && one_sync() && seg.use_ckey) {
                 seg.local_cap = ctx->seg_local_cap;
                 seg_local_bins = 0;
                 for (const SegDesc &sd : pl.segs) seg_local_bins += 1ull << (2 * sd.nb[0]);
@@ -812,7 +829,7 @@ class Pipeline {
 #ifdef UMIHIP_DEV
         const bool need_label = true; // (the tile kernels' collapse variants walk label[] of every entry)
 #else
-        const bool need_label = !((mode == MODE_DIRECTIONAL || !need_pairs) && n_parts == 1);
+        const bool need_label = !((unions_collapse() || !need_pairs) && n_parts == 1);
 #endif
         if (wide())
             HIP_TRY(launch_small_buckets_wide(d_keys, d_nmask, n_words, d_freq, percentage, d_boff() + b0, (uint32_t)(b1 - b0),
@@ -1069,7 +1086,7 @@ class Pipeline {
             seg.priv_cnt = ctx->seg_priv_cnt.as<uint32_t>();
             seg.uf_parent = one_sync() && ctx->seg_unite ? ctx->label.as<uint32_t>() : nullptr;
             // the slots go to the collapse's flatten launch, which adds up the blocks' counts as well
-            const bool slots_to_collapse = seg.uf_parent && mode == MODE_DIRECTIONAL;
+            const bool slots_to_collapse = seg.uf_parent && unions_collapse();
             seg.priv_stat = slots_to_collapse ? ctx->seg_priv_stat.as<uint2>() : nullptr;
             if (seg.local_cap && !seg.uf_parent) // (the scan has left the local bins without tasks)
                 return fail(UMI_ERR_HIP, "internal: part-0 sub-buckets planned for the local kernel without unions");
@@ -1323,6 +1340,59 @@ class Pipeline {
         return finish_stats();
     }
 
+    // Connected components (MODE_CLUSTER), a sibling of run_one_sync: pair kernels, the unions of whatever
+    // reached the list, one write-out, the control block read once.  Every pair within k is a union -- united
+    // where it was found or listed flagged -- so there is no one-way pair, no lab[], no round and no check
+    // beside the write-out, and dag_rounds_ahead stays what the directional calls made it.  What the host may
+    // find: the edge list ran over (longer list, pairs and write-out again).
+    int run_cluster()
+    {
+        int rc;
+        uint32_t *d_label = ctx->label.as<uint32_t>();
+        const bool have_pairs = need_pairs && n_tasks;
+        uint64_t cap = std::max<uint64_t>(ctx->edge_capacity, 1024);
+        for (int attempt = 0;; attempt++) {
+            if (have_pairs) {
+                uint64_t ovf_cap = 0;
+                if ((rc = reserve_lists(cap, ovf_cap))) return rc;
+                if ((rc = enqueue_pairs(ovf_cap))) return rc;
+            }
+            if (prof) HIP_TRY(hipEventRecord(ctx->ev[2], s));
+            if (have_pairs) {
+                // pairs in the list: those of the tile kernels, and the segment index's when it does not
+                // unite them itself
+                if (!seg.uf_parent || legacy_tiles() || !pl.small_tasks.empty() || !pl.big_tasks.empty())
+                    HIP_TRY(launch_uf_union_list(ctx->edges.as<uint2>(), d_cnt, cap_used, d_label, cap_used, s));
+                if (prof) HIP_TRY(hipEventRecord(ctx->ev[3], s));
+                HIP_TRY(launch_cluster_write(collapse_desc(), s));
+            } else { // no pair of this call reaches the edge list: every entry outside the fused buckets survives
+                if (prof) HIP_TRY(hipEventRecord(ctx->ev[3], s));
+                HIP_TRY(launch_finalize(d_label, d_ranges, (uint32_t)pl.ranges.size(), n, d_kept, d_root, d_cnt, s));
+            }
+            if (prof) HIP_TRY(hipEventRecord(ctx->ev[4], s));
+            if (may_defer && !have_pairs && !prof && ctx->spin_wait) {
+                st.n_pairs_evaluated = pl.n_pairs_eval;
+                return defer_control();
+            }
+            if ((rc = read_control())) return rc;
+            note_pair_counters();
+            if (pl.seg_parts && seg_tasks_made > seg.task_cap)
+                return fail(UMI_ERR_HIP, "internal: %llu segment tasks for a list of %u", (unsigned long long)seg_tasks_made, seg.task_cap);
+            if (n_edges <= cap || !have_pairs) break;
+            if (attempt >= 3) return fail(UMI_ERR_HIP, "edge list overflow persists");
+            // the list was too short: the exact count is known now
+            cap = n_edges + n_edges / 16 + 1024;
+            ctx->edge_capacity = cap;
+            HIP_TRY(hipMemsetAsync(&d_cnt[CNT_EDGES], 0, 2 * sizeof(unsigned long long), s));
+            HIP_TRY(hipMemsetAsync(&d_cnt[CNT_KEPT], 0, sizeof(unsigned long long), s));
+            HIP_TRY(hipMemsetAsync(&d_cnt[CNT_UF_DIRECT], 0, 2 * sizeof(unsigned long long), s));
+            HIP_TRY(launch_iota(d_label, n, s)); // (the fused buckets' entries are finished: their labels are free)
+        }
+        st.n_edges = n_edges + n_direct;
+        st.n_rounds = have_pairs && st.n_edges ? 1u : 0u; // (the union pass)
+        return finish_stats();
+    }
+
     int finish_neighbours()
     {
         if (!(need_pairs && n_tasks)) { // pair_stage did not read the counters back
@@ -1469,7 +1539,20 @@ class EdgeCollapse {
         memset(&st, 0, sizeof(st));
         st.n_umis = n;
         st.n_edges = n_edges;
-        if (mode == MODE_DIRECTIONAL) {
+        if (mode == MODE_CLUSTER) { // every listed pair is a union (flagged: one without the flag is not looked at)
+            if (n_edges) {
+                HIP_TRY(launch_uf_union_list(d_edges, d_cnt, n_edges, ctx->label.as<uint32_t>(), n_edges, s));
+                st.n_rounds = 1;
+            }
+            CollapseDesc cd{};
+            cd.parent = ctx->label.as<uint32_t>();
+            cd.n = n;
+            cd.kept = d_kept;
+            cd.root = d_root;
+            cd.kept_only = d_root == nullptr && ctx->collapse_kept_only;
+            cd.counters = d_cnt;
+            HIP_TRY(launch_cluster_write(cd, s));
+        } else if (mode == MODE_DIRECTIONAL) {
             if (n_edges) {
                 int rounds = 0;
                 if ((rc = directional_labels(ctx, d_edges, d_cnt, n_edges, n_edges, n, s, rounds))) return rc;
@@ -1680,7 +1763,7 @@ int dedup_batch_split(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask,
                       umi_stats *stats)
 {
     const uint32_t n_dev = (uint32_t)ctx->subs.size();
-    const int mode = algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY;
+    const int mode = mode_of(algo);
     std::vector<ShardResult> res(n_dev);
     std::vector<uint64_t> n_edges(n_dev, 0);
     std::vector<std::thread> pool;
@@ -1736,8 +1819,11 @@ int dedup_batch_split(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask,
     hipError_t e = hipSuccess;
     for (uint32_t r = 0; r < n_dev && e == hipSuccess; r++) {
         if (!n_edges[r]) continue;
-        e = hipMemcpy((char *)gathered.p + at * sizeof(uint2), ctx->subs[r]->edges.p, n_edges[r] * sizeof(uint2),
-                      hipMemcpyDefault);
+        // (on the stream the collapse runs on: a device-to-device hipMemcpy may return before the copy has landed,
+        // and that stream -- non-blocking -- would not wait for it.  The lists themselves are finished: every
+        // device's pipeline has seen its end.)
+        e = hipMemcpyAsync((char *)gathered.p + at * sizeof(uint2), ctx->subs[r]->edges.p, n_edges[r] * sizeof(uint2),
+                           hipMemcpyDefault, c0->own_stream);
         at += n_edges[r];
     }
     if (e != hipSuccess) {
@@ -1848,7 +1934,7 @@ int dedup_batch_single(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask
     rc = run_pipeline(ctx, ctx->in_keys.as<uint64_t>(),
                       nmask ? ctx->in_nmask.as<uint64_t>() : nullptr, ctx->in_freq.as<int32_t>(),
                       bucket_off, n_buckets, (uint32_t)n, umi_len, k, percentage,
-                      algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY,
+                      mode_of(algo),
                       adj_max_freq, ctx->out_kept.as<uint8_t>(),
                       root ? ctx->out_root.as<uint32_t>() : nullptr, s, stats, nullptr, n_words);
     if (rc) return rc;
@@ -2197,7 +2283,7 @@ int umi_dedup_batch_wide_device(umi_ctx *ctx, const uint64_t *d_keys, const uint
         return UMI_OK;
     }
     return run_pipeline(ctx, d_keys, d_nmask, d_freq, bucket_off, n_buckets, (uint32_t)n, umi_len, k, percentage,
-                        algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY, adj_max_freq, d_kept, d_root,
+                        mode_of(algo), adj_max_freq, d_kept, d_root,
                         (hipStream_t)hip_stream, stats, nullptr, n_words);
 }
 
@@ -2516,7 +2602,7 @@ int umi_dedup_batch_device_table(umi_ctx *ctx, const uint64_t *d_keys, const uin
     }
     return run_pipeline(ctx, d_keys, d_nmask, d_freq, bucket_off, n_buckets, (uint32_t)n, umi_len,
                         k, percentage,
-                        algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY,
+                        mode_of(algo),
                         adj_max_freq, d_kept, d_root, (hipStream_t)hip_stream, stats, d_bucket_off);
 }
 
@@ -2542,7 +2628,7 @@ int umi_dedup_batch_edit_device(umi_ctx *ctx, const uint64_t *d_keys, const uint
         return UMI_OK;
     }
     return run_pipeline(ctx, d_keys, d_nmask, d_freq, bucket_off, n_buckets, (uint32_t)n, umi_len, k, percentage,
-                        algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY, adj_max_freq, d_kept, d_root,
+                        mode_of(algo), adj_max_freq, d_kept, d_root,
                         (hipStream_t)hip_stream, stats, nullptr, 1, false, true);
 }
 
@@ -2579,7 +2665,7 @@ int umi_dedup_batch_edit(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nma
     if (nmask) HIP_TRY(hipMemcpyAsync(ctx->in_nmask.p, nmask, n * 8, hipMemcpyHostToDevice, s));
     rc = run_pipeline(ctx, ctx->in_keys.as<uint64_t>(), nmask ? ctx->in_nmask.as<uint64_t>() : nullptr,
                       ctx->in_freq.as<int32_t>(), bucket_off, n_buckets, (uint32_t)n, umi_len, k, percentage,
-                      algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY, adj_max_freq,
+                      mode_of(algo), adj_max_freq,
                       ctx->out_kept.as<uint8_t>(), root ? ctx->out_root.as<uint32_t>() : nullptr, s, stats, nullptr, 1,
                       false, true);
     if (rc) return rc;
@@ -2616,7 +2702,7 @@ int umi_dedup_batch_device_begin(umi_ctx *ctx, const uint64_t *d_keys, const uin
     umi_stats st;
     memset(&st, 0, sizeof(st));
     rc = run_pipeline(ctx, d_keys, d_nmask, d_freq, bucket_off, n_buckets, (uint32_t)n, umi_len, k, percentage,
-                      algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY, adj_max_freq, d_kept, d_root,
+                      mode_of(algo), adj_max_freq, d_kept, d_root,
                       (hipStream_t)hip_stream, &st, d_bucket_off, 1, true);
     if (rc) return rc; // (nothing is pending: the call failed where a plain call would have)
     if (!pc.deferred) { // the call had decisions to take on the host and has run to its end
@@ -2671,7 +2757,7 @@ int umi_dedup_batch_device_multi(umi_ctx *ctx, const uint64_t *const *d_keys, co
     }
     // every device's shard through the ordinary pipeline on its own stream (a host thread each: the
     // pipeline plans and synchronises), its mask packed to bits into its slot of its gather buffer
-    const int mode = algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY;
+    const int mode = mode_of(algo);
     std::vector<ShardResult> res(n_dev);
     std::vector<std::thread> pool;
     for (uint32_t r = 0; r < n_dev; r++)
@@ -2768,7 +2854,7 @@ int umi_pairs_partial_device(umi_ctx *ctx, const uint64_t *d_keys, const uint64_
     *n_edges_out = 0;
     if (n == 0) return UMI_OK;
     if (!d_keys || !d_freq) return fail(UMI_ERR_ARG, "keys/freq is NULL");
-    const int mode = algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY;
+    const int mode = mode_of(algo);
     hipStream_t s = (hipStream_t)hip_stream;
     settle(ctx); // (a deferred call owns the workspace until its end has been seen)
     Pipeline p(ctx, d_keys, d_nmask, d_freq, bucket_off, n_buckets, (uint32_t)n, umi_len, k,
@@ -2797,14 +2883,14 @@ int umi_collapse_edges_device(umi_ctx *ctx, uint64_t n, const uint64_t *d_edges,
             return fail(UMI_ERR_ARG, "device pointers belong to one device: use a single-device context");
         ctx = ctx->subs[0];
     }
-    if (algo != UMI_ALGO_DIRECTIONAL && algo != UMI_ALGO_ADJACENCY)
+    if (!known_algo(algo))
         return fail(UMI_ERR_ARG, "unknown algo %d", algo);
     if (n >= 0x7FFFFFF0ull || n_edges >= 0x7FFFFFF0ull) return fail(UMI_ERR_ARG, "too many entries/edges");
     settle(ctx);
     if (n == 0) return UMI_OK;
     if (!d_kept || (n_edges && !d_edges)) return fail(UMI_ERR_ARG, "kept/edges is NULL");
     return EdgeCollapse(ctx, (uint32_t)n, (const uint2 *)d_edges, (uint32_t)n_edges,
-                        algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY, d_kept,
+                        mode_of(algo), d_kept,
                         d_root, (hipStream_t)hip_stream)
         .run(stats);
 }
@@ -2829,7 +2915,7 @@ int seq_check(umi_ctx *ctx, int n_words, const uint64_t *bucket_off, const int32
     if (!bucket_off || (n_buckets && !bucket_len)) return fail(UMI_ERR_ARG, "bucket_off/bucket_len is NULL");
     if (n_words < 1 || n_words > SEQ_MAX_WORDS) return fail(UMI_ERR_ARG, "n_words %d outside 1..%d", n_words, SEQ_MAX_WORDS);
     if (k < 0) return fail(UMI_ERR_ARG, "k must be >= 0 (got %d)", k);
-    if (algo != UMI_ALGO_DIRECTIONAL && algo != UMI_ALGO_ADJACENCY) return fail(UMI_ERR_ARG, "unknown algo %d", algo);
+    if (!known_algo(algo)) return fail(UMI_ERR_ARG, "unknown algo %d", algo);
     if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
     for (uint64_t b = 0; b < n_buckets; b++) {
         if (bucket_off[b + 1] < bucket_off[b])
@@ -2860,7 +2946,7 @@ int seq_pipeline(umi_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_nmask, 
     memset(&st, 0, sizeof(st));
     st.n_umis = n;
     st.n_buckets = n_buckets;
-    const int mode = algo == UMI_ALGO_DIRECTIONAL ? MODE_DIRECTIONAL : MODE_ADJACENCY;
+    const int mode = mode_of(algo);
     const int kk = std::min(k, SEQ_MAX_K);
     // groups: k + 1 parts of a deep bucket with parts of SEQ_MIN_PART_BASES bases or more, else one
     std::vector<SeqGroup> groups;

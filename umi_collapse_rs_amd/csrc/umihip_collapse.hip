@@ -445,6 +445,57 @@ hipError_t launch_collapse_finalize(const CollapseDesc &d, hipStream_t s, int ch
     return hipGetLastError();
 }
 
+// ---- connected components (MODE_CLUSTER): the write-out behind the unions ---------------------------
+// Every pair within k was a union, so the forest is the whole answer: parent[v] <= v makes the root of a
+// set its smallest index, which in rank order is the entry the algorithm keeps.  With root[] wanted an
+// entry climbs to its root (the forest does not change any more: the unions ran in the launches before),
+// leaves it in parent[] as the flatten pass does, and writes kept / root; with the mask alone
+// (kept_only) kept[i] = parent[i] == i -- one stream in, one out, the forest left as it is.  No lab[], no
+// list of one-way pairs, no round.  The blocks behind the entries' add up what the segment index's
+// blocks counted (candidates, united pairs), as the directional flatten launch does; their private
+// edge slots are empty, a cluster call has no pair that is not united where it is found or listed flagged.
+namespace {
+__global__ __launch_bounds__(256) void cluster_write_kernel(CollapseArgs a, uint32_t entry_blocks)
+{
+    if (blockIdx.x >= entry_blocks) {
+        const uint32_t s0 = (blockIdx.x - entry_blocks) * 256u + threadIdx.x;
+        const uint2 st = s0 < a.priv_blocks ? a.priv_stat[s0] : make_uint2(0u, 0u);
+        block_count_add(st.x, &a.counters[CNT_CANDIDATES]);
+        block_count_add(st.y, &a.counters[CNT_UF_DIRECT]);
+        return;
+    }
+    unsigned int cnt = 0;
+    collapse_entries(a, entry_blocks, [&](uint32_t i) {
+        uint32_t r = a.parent[i];
+        if (!a.kept_only && r != i) {
+            for (;;) {
+                const uint32_t p = a.parent[r];
+                if (p == r) break;
+                r = p;
+            }
+            a.parent[i] = r; // (a later climb through i ends here; any value on the way up is an ancestor)
+        }
+        const bool kp = r == i;
+        a.kept[i] = kp ? 1 : 0;
+        if (a.root) a.root[i] = r;
+        cnt += kp ? 1u : 0u;
+    });
+    block_count_add(cnt, &a.counters[CNT_KEPT]);
+}
+} // namespace
+
+hipError_t launch_cluster_write(const CollapseDesc &d, hipStream_t s)
+{
+    const bool entries = !(d.n == 0 || (d.ranges && d.n_ranges == 0));
+    const uint32_t entry_blocks = entries ? entries_grid(d, 2048) : 0u;
+    const uint32_t stat_blocks = d.priv_stat && d.priv_blocks ? (d.priv_blocks + 255u) / 256u : 0u;
+    if (entry_blocks + stat_blocks == 0) return hipSuccess;
+    CollapseArgs a = collapse_args(d);
+    a.kept_only = d.kept_only && !d.root;
+    cluster_write_kernel<<<entry_blocks + stat_blocks, 256, 0, s>>>(a, entry_blocks);
+    return hipGetLastError();
+}
+
 namespace {
 __global__ __launch_bounds__(256) void uf_flatten_all_kernel(uint32_t *parent, uint32_t *lab, uint32_t n)
 {

@@ -133,6 +133,10 @@ __attribute__((unused)) __device__ __noinline__ void verify_pair(const uint64_t 
         emit_edge(st, edges, edge_dist, counters, edge_cap, gi, gj, dist, true);
         return;
     }
+    if (mode == MODE_CLUSTER) { // connected components: the pair is a union whatever its entries' freq
+        emit_edge(st, edges, edge_dist, counters, edge_cap, gi | SYM_FLAG, gj, dist, false);
+        return;
+    }
     const int32_t fi = freq[gi], fj = freq[gj];
     bool fwd, bwd;
     if (mode == MODE_DIRECTIONAL) {

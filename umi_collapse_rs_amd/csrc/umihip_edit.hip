@@ -173,6 +173,8 @@ __global__ __launch_bounds__(64) void edit_pair_kernel(PairArgs a, const uint32_
             if (mode == MODE_DIRECTIONAL) { // naive.rs:31 with max_freq = threshold(start) (directional.rs:38-39)
                 fwd = C.freq <= R.thr;
                 bwd = R.freq <= C.thr;
+            } else if (mode == MODE_CLUSTER) { // connected components: a union, nothing to ask of freq
+                fwd = bwd = true;
             } else { // adjacency.rs:56: a root only ever sees entries of larger rank
                 fwd = C.freq <= a.adj_max_freq;
                 bwd = false;

@@ -22,6 +22,7 @@ enum PairMode : int {
     MODE_DIRECTIONAL = 0, // directed edges u->v with freq[v] <= thr[u]   (directional.rs:38-39)
     MODE_ADJACENCY = 1,   // forward edges u->v (u<v) with freq[v] <= max_freq (adjacency.rs:56)
     MODE_NEIGHBOURS = 2,  // undirected (i<j, dist) lists for the DataStruct path
+    MODE_CLUSTER = 3,     // connected components: every pair within k is a symmetric pair, freq takes no part
 };
 
 enum Counter : int {
@@ -528,6 +529,11 @@ hipError_t launch_collapse_round(const CollapseDesc &d, int round, hipStream_t s
 // move a label (changed[check_round])
 hipError_t launch_collapse_finalize(const CollapseDesc &d, hipStream_t s, int check_round = -1);
 // bits[i / 8] bit (i % 8) = kept[i] != 0, for i < n (ceil(n / 8) bytes written)
+// Connected components (MODE_CLUSTER): kept / root / CNT_KEPT straight from the union-find forest in d.parent
+// -- with d.root the entries are flattened on the way, with d.kept_only and no root kept[i] = parent[i] == i and the
+// forest stays as it is; d.lab, d.edges and d.changed are not looked at.  d.priv_stat (may be null): the counts of
+// d.priv_blocks blocks of the segment index's kernels, added to the counters here.
+hipError_t launch_cluster_write(const CollapseDesc &d, hipStream_t s);
 hipError_t launch_pack_mask(const uint8_t *kept, uint64_t n, uint8_t *bits, hipStream_t s);
 
 hipError_t launch_pairs(const PairArgs &a, uint32_t n_tasks, bool big, bool key32, hipStream_t s);

@@ -261,10 +261,10 @@ __device__ __forceinline__ unsigned int fused_write_out(uint32_t start, int n, c
     for (int s = 0; s < RL; s++) {
         const int row = lane + 64 * s;
         if (row < n) {
-            const bool kp = MODE == MODE_DIRECTIONAL ? lab[s] == (uint32_t)row : alive[s] != 0u;
+            const bool kp = MODE != MODE_ADJACENCY ? lab[s] == (uint32_t)row : alive[s] != 0u;
             if (label) label[start + row] = start + lab[s];
             kept[start + row] = kp ? 1 : 0;
-            if (root) root[start + row] = (MODE != MODE_DIRECTIONAL && kp) ? start + row : start + lab[s];
+            if (root) root[start + row] = (MODE == MODE_ADJACENCY && kp) ? start + row : start + lab[s];
             n_kept += kp ? 1u : 0u;
         }
     }
@@ -292,7 +292,7 @@ __device__ __forceinline__ FusedCounts small_bucket_body(const uint64_t *__restr
         key[s] = in_range ? keys[start + r] : 0ull;
         nm[s] = (HAS_N && in_range) ? nmask[start + r] : 0ull;
         fr[s] = in_range ? freq[start + r] : 0x7FFFFFFF;
-        th[s] = in_range ? threshold_of(percentage, fr[s]) : (-0x7FFFFFFF - 1);
+        th[s] = in_range ? (MODE == MODE_CLUSTER ? 0x7FFFFFFF : threshold_of(percentage, fr[s])) : (-0x7FFFFFFF - 1);
     }
     // in[s][h]: bit jj set <=> entry j = 32h+jj may remove row (lane + 64s)
     uint32_t in[RL][H];
@@ -319,8 +319,10 @@ __device__ __forceinline__ FusedCounts small_bucket_body(const uint64_t *__restr
                 bool e = bcx <= lim && (lane + 64 * s) != j;
                 if (MODE == MODE_DIRECTIONAL)
                     e = e && fr[s] <= thj; // naive.rs:31 with max_freq = threshold(start)
-                else
+                else if (MODE == MODE_ADJACENCY)
                     e = e && fr[s] <= adj_max_freq && (lane + 64 * s) > j;
+                // (MODE_CLUSTER: within k and not the row itself -- a symmetric matrix, whose min-label sweeps
+                // below end with every row at the smallest row of its connected component)
                 in[s][h] |= e ? bit : 0u;
             }
         }
@@ -331,7 +333,7 @@ __device__ __forceinline__ FusedCounts small_bucket_body(const uint64_t *__restr
         lab[s] = (uint32_t)(lane + 64 * s);
         alive[s] = 0u;
     }
-    if (MODE == MODE_DIRECTIONAL) {
+    if (MODE != MODE_ADJACENCY) {
         bool changed;
         do { // Gauss-Seidel sweeps in rank order until no label moves
             uint32_t before[RL];
@@ -677,7 +679,9 @@ template <int W> __device__ __forceinline__ uint32_t window12(const uint64_t (&f
     return (uint32_t)v;
 }
 
-template <int RL, bool HAS_N, int K, int W>
+// CLUSTER: connected components -- every source passes every row's freq test (thresholds at the top of the
+// range, in rank order by construction), so the in-edge masks are "within k, not the row itself"
+template <int RL, bool HAS_N, int K, int W, bool CLUSTER = false>
 __device__ __forceinline__ FusedCounts small_bucket_body_dir(const uint64_t *__restrict__ keys,
                                                              const uint64_t *__restrict__ nmask,
                                                              const int32_t *__restrict__ freq,
@@ -702,7 +706,7 @@ __device__ __forceinline__ FusedCounts small_bucket_body_dir(const uint64_t *__r
             fold[s][w] = key[s][w] & ~nm[s][w]; // N folded onto A: the sliced distance never exceeds the exact one
         }
         fr[s] = in_range ? freq[start + r] : 0x7FFFFFFF;
-        th[s] = in_range ? threshold_of(percentage, fr[s]) : (-0x7FFFFFFF - 1);
+        th[s] = in_range ? (CLUSTER ? 0x7FFFFFFF : threshold_of(percentage, fr[s])) : (-0x7FFFFFFF - 1);
         const int left = n - 64 * s;
         vmask[s] = left >= 64 ? ~0ull : (left <= 0 ? 0ull : ((1ull << left) - 1ull));
     }
@@ -812,9 +816,9 @@ __device__ __forceinline__ FusedCounts small_bucket_body_dir(const uint64_t *__r
         unsigned long long todo[RL];
 #pragma unroll
         for (int s = 0; s < RL; s++) {
-            q[s] = 0;
+            q[s] = CLUSTER ? n : 0; // (every source may remove every row: no freq to walk)
             qp[s] = 0;
-            todo[s] = vmask[s];
+            todo[s] = CLUSTER ? 0ull : vmask[s];
         }
         for (;;) {
             int32_t v, tv;
@@ -1006,14 +1010,15 @@ __global__ __launch_bounds__(256) void small_bucket_kernel(const uint64_t *__res
             continue;
         }
         FusedCounts c;
-        if ((KB >= 0 && MODE == MODE_DIRECTIONAL) || W > 1) {
+        if ((KB >= 0 && MODE != MODE_ADJACENCY) || W > 1) {
             constexpr int K = KB >= 0 ? KB : 0;
+            constexpr bool CL = MODE == MODE_CLUSTER;
             if (n <= 64)
-                c = small_bucket_body_dir<1, HAS_N, K, W>(keys, nmask, freq, percentage, start, (int)n, umi_len, label,
-                                                          kept, root);
+                c = small_bucket_body_dir<1, HAS_N, K, W, CL>(keys, nmask, freq, percentage, start, (int)n, umi_len, label,
+                                                              kept, root);
             else
-                c = small_bucket_body_dir<2, HAS_N, K, W>(keys, nmask, freq, percentage, start, (int)n, umi_len, label,
-                                                          kept, root);
+                c = small_bucket_body_dir<2, HAS_N, K, W, CL>(keys, nmask, freq, percentage, start, (int)n, umi_len, label,
+                                                              kept, root);
         } else if (KB >= 0) {
             constexpr int K = KB >= 0 ? KB : 0;
             if (n <= 64)
@@ -1293,7 +1298,10 @@ hipError_t launch_small_buckets(const uint64_t *keys, const uint64_t *nmask, con
     // from the context ("fused_blocks" per CU, default 20).
     const uint32_t blocks = grid_for((uint64_t)n_buckets * 64, 256, max_blocks);
     const int kb = (sliced && k >= 0 && k <= 3) ? k : -1;
-    if (mode == MODE_DIRECTIONAL) {
+    if (mode == MODE_CLUSTER) {
+        if (nmask) launch_small_k<true, MODE_CLUSTER>(kb, blocks, keys, nmask, freq, percentage, bucket_off, n_buckets, fused_max, n_entries, label, kept, root, k, umi_len, adj_max_freq, counters, s);
+        else launch_small_k<false, MODE_CLUSTER>(kb, blocks, keys, nmask, freq, percentage, bucket_off, n_buckets, fused_max, n_entries, label, kept, root, k, umi_len, adj_max_freq, counters, s);
+    } else if (mode == MODE_DIRECTIONAL) {
         if (nmask) launch_small_k<true, MODE_DIRECTIONAL>(kb, blocks, keys, nmask, freq, percentage, bucket_off, n_buckets, fused_max, n_entries, label, kept, root, k, umi_len, adj_max_freq, counters, s);
         else launch_small_k<false, MODE_DIRECTIONAL>(kb, blocks, keys, nmask, freq, percentage, bucket_off, n_buckets, fused_max, n_entries, label, kept, root, k, umi_len, adj_max_freq, counters, s);
     } else {

@@ -707,6 +707,8 @@ __global__ __launch_bounds__(64) void seg_pair_kernel(PairArgs a, SegArgs g, flo
                 if (a.mode == MODE_DIRECTIONAL) { // naive.rs:31 under directional.rs:38-39
                     fwd = fj <= threshold_of(percentage, fi);
                     bwd = fi <= threshold_of(percentage, fj);
+                } else if (a.mode == MODE_CLUSTER) { // connected components: a union, nothing to ask of freq
+                    fwd = bwd = true;
                 } else { // adjacency.rs:56: a root only ever sees entries of larger rank
                     fwd = fj <= a.adj_max_freq;
                     bwd = false;
@@ -906,7 +908,9 @@ __device__ __forceinline__ uint32_t rest_code(uint32_t ck)
     return s;
 }
 
-template <bool HAS_N>
+// CLUSTER: connected components -- every pair within k is united, nothing is asked of freq and no one-way
+// pair exists (the private slots stay empty)
+template <bool HAS_N, bool CLUSTER = false>
 __global__ __launch_bounds__(64) void seg_local_kernel(PairArgs a, SegArgs g, float percentage)
 {
     extern __shared__ uint32_t lds[];
@@ -969,8 +973,8 @@ __global__ __launch_bounds__(64) void seg_local_kernel(PairArgs a, SegArgs g, fl
             }
             const bool near = live && dist <= a.k;
             // naive.rs:31 under directional.rs:38-39
-            const bool fwd = near && fj <= threshold_of(percentage, fi);
-            const bool bwd = near && fi <= threshold_of(percentage, fj);
+            const bool fwd = near && (CLUSTER || fj <= threshold_of(percentage, fi));
+            const bool bwd = near && (CLUSTER || fi <= threshold_of(percentage, fj));
             if (fwd && bwd) { // reachability inside such a set is symmetric: one set
                 n_direct++;
                 lds_union(par, min(pa, pb), max(pa, pb));
@@ -1263,10 +1267,14 @@ int seg_local_blocks_per_cu(bool has_n, uint32_t cap)
 hipError_t launch_seg_local(const PairArgs &a, const SegArgs &g, float percentage, uint32_t n_blocks, hipStream_t s)
 {
     if (g.n_chunks == 0 || n_blocks == 0 || g.local_cap == 0) return hipSuccess;
-    if (g.local_cap > SEG_LOCAL_MAX_CAP || !g.uf_parent || !g.priv_stat || !g.use_ckey || a.mode != MODE_DIRECTIONAL)
+    if (g.local_cap > SEG_LOCAL_MAX_CAP || !g.uf_parent || !g.priv_stat || !g.use_ckey ||
+        (a.mode != MODE_DIRECTIONAL && a.mode != MODE_CLUSTER))
         return hipErrorInvalidValue;
     const size_t lds = seg_local_lds_bytes(g.local_cap);
-    if (a.nmask) seg_local_kernel<true><<<n_blocks, 64, lds, s>>>(a, g, percentage);
+    if (a.mode == MODE_CLUSTER) {
+        if (a.nmask) seg_local_kernel<true, true><<<n_blocks, 64, lds, s>>>(a, g, percentage);
+        else seg_local_kernel<false, true><<<n_blocks, 64, lds, s>>>(a, g, percentage);
+    } else if (a.nmask) seg_local_kernel<true><<<n_blocks, 64, lds, s>>>(a, g, percentage);
     else seg_local_kernel<false><<<n_blocks, 64, lds, s>>>(a, g, percentage);
     return hipGetLastError();
 }

@@ -253,6 +253,8 @@ __global__ __launch_bounds__(64) void seq_pair_kernel(SeqPairArgs a)
             if (a.mode == MODE_DIRECTIONAL) { // naive.rs:31 with max_freq = threshold(start) (directional.rs:38-39)
                 fwd = fj <= tr;
                 bwd = fr <= tj;
+            } else if (a.mode == MODE_CLUSTER) { // connected components: a union, nothing to ask of freq
+                fwd = bwd = true;
             } else { // adjacency.rs:56: a root only ever sees entries of larger rank
                 fwd = fj <= a.adj_max_freq;
                 bwd = false;

@@ -1,6 +1,10 @@
 // `umicollapse`'s command line: the flags (Cli, parse, usage), the refusals that need no input file
 // (validate) and the lists the flags name (read_whitelist).
 //
+// --algo cluster (every mode that takes --algo; umi_tools' --method cluster, STARsolo's 1MM_All at -k 1, what the
+// reference's help calls `cc` and its main() refuses): one UMI per connected component of "within -k", the
+// component's first in rank order; -p is accepted and plays no part (UMI_ALGO_CLUSTER, include/umihip.h).  `cc`
+// itself stays refused with the reference's message.
 // --per-gene [--gene-tag XX] (bam/sam mode, one pass; umi_tools --per-gene / STARsolo's grouping, not the
 // reference's, tests/gene_model.py defines it): reads are grouped by gene -- with --per-cell by (cell, gene) --
 // and not by alignment position (staging.hpp has the rule, umicollapse_main.cpp the pipeline).
@@ -96,7 +100,8 @@ void usage()
               "  -p <PERCENTAGE>          Directional threshold percentage [default: 0.5]\n"
               "      --num-threads <N>    Threads used in reader/writer [default: 1]\n"
               "      --umi_sep <BYTE>     Separator byte value between UMI and read name [default: 95]\n"
-              "      --algo <ALGO>        adj or dir [default: dir]\n"
+              "      --algo <ALGO>        adj, dir or cluster [default: dir]; cluster: one UMI per connected component of\n"
+              "                           \"within k\" (umi_tools' cluster, STARsolo's 1MM_All at -k 1); -p plays no part\n"
               "      --merge <MERGE>      any, avgqual or mapqual [default: mapqual in bam mode, avgqual in fastq mode]\n"
               "      --data <DATA>        accepted; every value gives Naive's result (as in the reference)\n"
               "      --keep-unmapped      Keep unmapped reads\n"
@@ -393,6 +398,7 @@ bool validate(Cli &args)
     if (args.track_clusters && args.paired) die("--tag with --paired is not implemented (the reference never reaches its tagging pass)");
     if (args.algo == "dir") args.algo_id = UMI_ALGO_DIRECTIONAL;
     else if (args.algo == "adj") args.algo_id = UMI_ALGO_ADJACENCY;
+    else if (args.algo == "cluster") args.algo_id = UMI_ALGO_CLUSTER; // (not `cc`: that name stays refused, as below)
     else die("Invalid algorithm combination: " + args.algo + " , " + args.merge + " and " + args.data); // main.rs:86-91
     if (args.merge == "any") args.merge_id = 0;
     else if (args.merge == "avgqual") args.merge_id = 1;

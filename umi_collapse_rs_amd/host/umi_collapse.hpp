@@ -241,6 +241,47 @@ class Adjacency {
     bool track_;
 };
 
+// Connected components of "within k" (UMI_ALGO_CLUSTER; umi_tools' `cluster`, UMICollapse's `cc`, which the
+// reference names and never implements): Directional's root loop with every neighbour admitted whatever its
+// freq -- remove_near(u, k, INT32_MAX), followed transitively -- so a root takes its whole component and the
+// survivor is the component's first UMI in rank order.  percentage is accepted and plays no part.
+class Cluster {
+  public:
+    Cluster(int32_t k, float percentage = 0.5f, bool track_cluster = false) : k_(k), track_(track_cluster) { (void)percentage; }
+
+    template <class R, class D = HipNaive>
+    std::vector<const R *> apply(const UmiReads<R> &reads, ClusterTracker *tracker, size_t umi_length)
+    {
+        UmiFreqMap data_member;
+        for (auto &kv : reads) data_member.emplace_back(kv.first, kv.second->freq);
+        UmiReads<R> umi_freqs(reads);
+        std::stable_sort(umi_freqs.begin(), umi_freqs.end(),
+                         [](const auto &a, const auto &b) { return b.second->freq < a.second->freq; });
+        D data(data_member, umi_length, k_);
+        std::vector<const R *> res;
+        for (auto &entry : umi_freqs) {
+            if (!data.contains(*entry.first)) continue;
+            std::vector<const BitSet *> stack{entry.first};
+            while (!stack.empty()) {
+                const BitSet *start = stack.back();
+                stack.pop_back();
+                auto near = data.remove_near(*start, k_, INT32_MAX);
+                for (const BitSet *v : near) {
+                    if (track_ && tracker) (*tracker)[entry.first].push_back(v);
+                    if (v == start) continue;
+                    stack.push_back(v);
+                }
+            }
+            res.push_back(&entry.second->read);
+        }
+        return res;
+    }
+
+  private:
+    int32_t k_;
+    bool track_;
+};
+
 // The bucket loop src/deduplicate_sam.rs:207-233 as ONE batched call: `buckets` in the
 // order the loop would visit them, each in first-appearance order.  Returns the surviving
 // reads in the reference's output order and fills the loop's counters.

@@ -69,7 +69,9 @@
 // "%%MatrixMarket matrix coordinate integer general", then "G C NNZ", then NNZ lines "row col molecules", counted
 // from 1, by column and then row; reads.mtx, the same with the reads.  The molecules add up to "Number of reads
 // after deduplicating".
-// Not implemented, as in the reference: --algo cc.
+// --algo cluster: connected components of "within -k" (cli.hpp); every pipeline here only forwards the algorithm
+// to the library, so it goes with every flag --algo dir goes with.
+// Not implemented, as in the reference: --algo cc (that spelling stays refused; `cluster` is the mode's name).
 #include "fastq_mode.hpp"
 #include "hiplib.hpp"
 #include "staging.hpp"
