@@ -143,6 +143,9 @@ const char *umi_last_error(void);
  *   "cons_split"     2..2^30 (default 512): umi_consensus_seqs / umi_consensus_bam sum a cluster of at least this many reads in
  *                    pieces over the whole grid instead of by one wave (raised by itself where the deep
  *                    clusters' accumulators, 12 KB each, would pass 512 MB)
+ *   "stats_split"    64..2^30 (default 4096): umi_dedup_stats counts a bucket of at least this many entries in pieces
+ *                    over the whole grid instead of by one wave (raised by itself where the deep buckets' tables,
+ *                    80 bytes per base each, would pass 512 MB)
  * The round-1 tile kernels (bit-sliced masks, key-sorted scan + item walk, range pruning, hook/jump
  * collapse) and their options ("bitslice", "bs_*", "prune", "two_phase", "ovf_capacity") exist in the
  * development build only (make dev: libumihip_dev.so, -DUMIHIP_DEV), as cross-checks. */
@@ -486,6 +489,58 @@ int umi_count_matrix_device(umi_ctx *ctx, const uint8_t *d_kept, const int32_t *
 int umi_count_matrix(umi_ctx *ctx, const uint8_t *kept, const int32_t *freq, const uint64_t *bucket_off,
                      uint64_t n_buckets, const uint32_t *row, const uint32_t *col, uint32_t n_rows, uint32_t n_cols,
                      uint32_t *out_row, uint32_t *out_col, uint32_t *out_molecules, uint64_t *out_reads, uint64_t *nnz);
+
+/* ---- what a batched call did, as tables (the program's --output-stats): family sizes before and after, the mean
+ *      UMI distance of every bucket before and after against a null, and how every UMI sequence is used, on the
+ *      GPU.  No counterpart in the reference; the tables are umi_tools dedup --output-stats's, tests/stats_model.py
+ *      defines them.  Everything is exact integer arithmetic.
+ * in : keys: n_words words per entry, entry-major, umi_len in 1..UMI_MAX_WIDE_UMI_LEN, n_words = ceil(3 * umi_len /
+ *      64); no nmask: code 100 is N.  freq / kept / root: the N = bucket_off[n_buckets] entries as a batched call
+ *      took and wrote them (any byte of kept other than 0 counts as kept).  bucket_off: a HOST array in both forms,
+ *      [n_buckets + 1], starting at 0 and never falling.  hist_bins in 2..2^24.
+ * out: count_pre / count_post [hist_bins]: count_pre[min(freq[i], hist_bins - 1)] counts every entry;
+ *      total[r] = the sum of freq[i] over root[i] == r (64 bits), and count_post[min(total[i], hist_bins - 1)]
+ *      counts every kept entry; the last bin collects everything at or above it.
+ *      dist [4][umi_len + 2], rows 0 pre, 1 pre-null, 2 post, 3 post-null; column j <= umi_len is bin j, column
+ *      umi_len + 1 is "single".  A UMI's letter at base b is the 3-bit code at bits [3b, 3b + 3) of its key read
+ *      as one little-endian integer (000 A, 110 C, 011 G, 101 T, 100 N); two letters differ iff their codes
+ *      differ, so N is a letter of its own (the rule of umi_dedup_batch_edit; for UMIs without N: umi_dist).  A
+ *      set of m UMIs (a multiset for the nulls; equal UMIs are at distance 0) contributes nothing if m = 0, one
+ *      to "single" if m = 1, else one to bin (S + P - 1) / P, S the sum of its pair distances and P = m (m - 1) /
+ *      2: the mean rounded up, where umi_tools' digitize(..., right=True) puts it.  Per non-empty bucket [s, e)
+ *      with m kept entries: pre the UMIs of all its entries, post those of the kept ones, pre-null those of the
+ *      entries pick(i) for i in [s, e), post-null those of pick(i) for i in [s, s + m).  pick(i) draws an entry
+ *      with probability proportional to its reads: x = seed + 0x9E3779B97F4A7C15 * (i + 1) mod 2^64; x ^= x >>
+ *      30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31; t = the high 64 bits of
+ *      x * R, R the sum of all freq; pick(i) = the smallest e with cum[e] > t, cum the inclusive scan of freq.
+ *      The per-UMI table (its five arrays NULL together: left out, n_umis may then be NULL too; else room for N
+ *      rows each): one row per distinct key among the N entries, in ascending order of the key as a little-endian
+ *      integer (word n_words - 1 the most significant; bits from 3 * umi_len up are not looked at).  umi_entry the
+ *      smallest entry that holds the key, times_pre the entries that hold it, reads_pre the sum of their freq,
+ *      times_post the kept entries among them, reads_post the sum of their total[]; *n_umis the rows.  What lies
+ *      behind them is not defined.
+ * n_buckets == 0 or every bucket empty: UMI_OK, the three tables zeroed, *n_umis = 0, nothing else launched.  A
+ * multi-device context uses its first device.  A deferred call (umi_dedup_batch_device_begin) that is out on the
+ * context ends first; its result keeps waiting for umi_dedup_batch_end.
+ * UMI_ERR_ARG: a NULL among ctx and the arrays the call would touch, some but not all of the table's five,
+ * umi_len, n_words or hist_bins out of range, a bucket_off that does not start at 0 or that falls, 2^31 entries or
+ * more (2^30 with the per-UMI table: its sort's index space), a bucket of 2^28 entries or more (S would pass 64
+ * bits at 85 bases) -- all found on the host before anything is launched.  Counted on the device and told after the
+ * call's synchronisation, the outputs then not defined: a code other than the five at a base below umi_len, a
+ * root[i] outside i's bucket or at an entry with kept == 0, a kept entry with root[i] != i.
+ * Option "stats_split" (64..2^30, default 4096): a bucket of at least this many entries is counted in pieces by
+ * the whole grid instead of by one wave; same result.
+ * The _device form takes and leaves everything but bucket_off and n_umis in device memory, works on hip_stream
+ * and synchronises it once, at the end; the plain form copies host arrays in and out around it. */
+int umi_dedup_stats_device(umi_ctx *ctx, const uint64_t *d_keys, int n_words, const int32_t *d_freq, const uint8_t *d_kept,
+                           const uint32_t *d_root, const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, uint64_t seed,
+                           uint32_t hist_bins, uint64_t *d_count_pre, uint64_t *d_count_post, uint64_t *d_dist,
+                           uint32_t *d_umi_entry, uint32_t *d_times_pre, uint64_t *d_reads_pre, uint32_t *d_times_post,
+                           uint64_t *d_reads_post, uint64_t *n_umis, void *hip_stream);
+int umi_dedup_stats(umi_ctx *ctx, const uint64_t *keys, int n_words, const int32_t *freq, const uint8_t *kept,
+                    const uint32_t *root, const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, uint64_t seed,
+                    uint32_t hist_bins, uint64_t *count_pre, uint64_t *count_post, uint64_t *dist, uint32_t *umi_entry,
+                    uint32_t *times_pre, uint64_t *reads_pre, uint32_t *times_post, uint64_t *reads_post, uint64_t *n_umis);
 
 /* ---- batched path: replaces the whole bucket loop
  *      src/deduplicate_sam.rs:207-233 (apply::<UcSAMRead,Naive> per bucket,

@@ -113,6 +113,11 @@ SIGNATURES = {
                                           C.c_void_p]),
     "umi_count_matrix": (C.c_int, [C.c_void_p, _u8p, _i32p, _u64p, C.c_uint64, _u32p, _u32p, C.c_uint32, C.c_uint32,
                                    _u32p, _u32p, _u32p, _u64p, _u64p]),
+    "umi_dedup_stats_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _u64p,
+                                         C.c_uint64, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_void_p]),
+    "umi_dedup_stats": (C.c_int, [C.c_void_p, _u64p, C.c_int, _i32p, _u8p, _u32p, _u64p, C.c_uint64, C.c_int, C.c_uint64,
+                                  C.c_uint32, _u64p, _u64p, _u64p, _u32p, _u32p, _u64p, _u32p, _u64p, _u64p]),
     "umi_dedup_batch": (C.c_int, [C.c_void_p, _u64p, _u64p, _i32p, _u64p, C.c_uint64, C.c_int,
                                   C.c_int, C.c_float, C.c_int, C.c_int32, _u8p, _u32p,
                                   C.POINTER(Stats)]),

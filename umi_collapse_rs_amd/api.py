@@ -457,6 +457,55 @@ class Context:
                                              d_out_reads or None, C.byref(nnz), stream or None))
         return int(nnz.value)
 
+    def dedup_stats(self, keys, freq, kept, root, bucket_off, umi_len, n_words=1, seed=0, hist_bins=65536, per_umi=True):
+        """What a batched call did, as tables (umi_dedup_stats): keys uint64 [N * n_words], freq int32 [N], kept uint8
+        [N] and root uint32 [N] of the call, bucket_off uint64 [n_buckets + 1].  Returns a dict: count_pre / count_post
+        uint64 [hist_bins] (family sizes before and after), dist uint64 [4, umi_len + 2] (rows pre, pre-null, post,
+        post-null; columns the bins 0..umi_len, then "single") and, with per_umi, umi_entry / times_pre / reads_pre /
+        times_post / reads_post, one element per distinct key in ascending key order."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+        freq = np.ascontiguousarray(freq, dtype=np.int32)
+        kept = np.ascontiguousarray(kept, dtype=np.uint8)
+        root = np.ascontiguousarray(root, dtype=np.uint32)
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        n, nb = len(freq), len(bucket_off) - 1
+        if nb < 0 or len(kept) != n or len(root) != n or len(keys) != n * n_words or (nb and int(bucket_off.max()) > n):
+            raise ValueError("keys / freq / kept / root lengths differ, or bucket_off runs past them")
+        count_pre = np.zeros(max(1, hist_bins), np.uint64)
+        count_post = np.zeros(max(1, hist_bins), np.uint64)
+        dist = np.zeros((4, max(1, umi_len) + 2), np.uint64)
+        out = {"count_pre": count_pre, "count_post": count_post, "dist": dist}
+        m = max(1, n)
+        tab = {}
+        if per_umi:
+            tab = {"umi_entry": np.zeros(m, np.uint32), "times_pre": np.zeros(m, np.uint32), "reads_pre": np.zeros(m, np.uint64),
+                   "times_post": np.zeros(m, np.uint32), "reads_post": np.zeros(m, np.uint64)}
+        rows = C.c_uint64(0)
+        check(load().umi_dedup_stats(self._h, ptr(keys, C.c_uint64), n_words, ptr(freq, C.c_int32), ptr(kept, C.c_uint8),
+                                     ptr(root, C.c_uint32), ptr(bucket_off, C.c_uint64), nb, umi_len, seed, hist_bins,
+                                     ptr(count_pre, C.c_uint64), ptr(count_post, C.c_uint64), ptr(dist, C.c_uint64),
+                                     ptr(tab.get("umi_entry"), C.c_uint32), ptr(tab.get("times_pre"), C.c_uint32),
+                                     ptr(tab.get("reads_pre"), C.c_uint64), ptr(tab.get("times_post"), C.c_uint32),
+                                     ptr(tab.get("reads_post"), C.c_uint64), C.byref(rows) if per_umi else None))
+        for name, a in tab.items():
+            out[name] = a[:int(rows.value)]
+        return out
+
+    def dedup_stats_device(self, d_keys, d_freq, d_kept, d_root, bucket_off, umi_len, d_count_pre, d_count_post, d_dist,
+                           n_words=1, seed=0, hist_bins=65536, d_umi_entry=0, d_times_pre=0, d_reads_pre=0, d_times_post=0,
+                           d_reads_post=0, stream=0):
+        """The same on raw device pointers (umi_dedup_stats_device; bucket_off stays on the host): fills the three
+        tables and, where its five arrays are given (room for N elements each), the per-UMI table; returns its rows
+        (0 without it)."""
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        rows = C.c_uint64(0)
+        check(load().umi_dedup_stats_device(self._h, d_keys or None, n_words, d_freq or None, d_kept or None, d_root or None,
+                                            ptr(bucket_off, C.c_uint64), len(bucket_off) - 1, umi_len, seed, hist_bins,
+                                            d_count_pre or None, d_count_post or None, d_dist or None, d_umi_entry or None,
+                                            d_times_pre or None, d_reads_pre or None, d_times_post or None,
+                                            d_reads_post or None, C.byref(rows), stream or None))
+        return int(rows.value)
+
     def stage_reads(self, align_key, umi_bytes, score, umi_len, merge=1, align_key_bits=64):
         """Read staging on the device (host arrays in and out): reads in file order ->
         dict(keys, nmask, freq, rep, bucket_off) in canonical order, the batched path's input

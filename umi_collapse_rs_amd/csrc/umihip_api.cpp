@@ -251,6 +251,11 @@ struct umi_ctx {
     // pinned staging of the non-empty buckets' offsets and numbers
     DevBuf cm_ws, cm_io;
     PinnedBuf cm_h;
+    // family sizes, UMI distances and UMI usage (umi_dedup_stats*): workspace; the host-buffer form's arrays in one
+    // block; pinned staging of the non-empty buckets' offsets, the deep buckets and their pieces
+    DevBuf ds_ws, ds_io;
+    PinnedBuf ds_h;
+    uint32_t stats_split = STATS_SPLIT; // buckets of at least this many entries are counted by the whole grid
     uint32_t cons_split = 512; // clusters of at least this many reads are summed in pieces by the whole grid
     uint64_t *h_boff = nullptr;               // pinned staging of the bucket table
     size_t h_boff_cap = 0;
@@ -2017,9 +2022,10 @@ void umi_ctx_destroy(umi_ctx *ctx)
                       &ctx->cons_ws, &ctx->cons_seq, &ctx->cons_qual, &ctx->cons_off, &ctx->cons_cr,
                       &ctx->corr_ws, &ctx->corr_umi, &ctx->corr_out, &ctx->corr_match, &ctx->corr_best, &ctx->corr_second,
                       &ctx->bc_ws, &ctx->bc_in, &ctx->bc_match, &ctx->bc_status,
-                      &ctx->cm_ws, &ctx->cm_io};
+                      &ctx->cm_ws, &ctx->cm_io, &ctx->ds_ws, &ctx->ds_io};
     for (DevBuf *b : bufs) b->release();
     ctx->cm_h.release();
+    ctx->ds_h.release();
     if (ctx->h_boff) (void)hipHostFree(ctx->h_boff);
     ctx->h_tasks.release();
     ctx->h_plan_alt[0].release();
@@ -2120,6 +2126,9 @@ int umi_ctx_set_option(umi_ctx *ctx, const char *name, int64_t value)
     } else if (!strcmp(name, "cons_split")) {
         if (value < 2 || value > (1ll << 30)) return fail(UMI_ERR_ARG, "cons_split must be in 2..2^30");
         ctx->cons_split = (uint32_t)value;
+    } else if (!strcmp(name, "stats_split")) {
+        if (value < 64 || value > (1ll << 30)) return fail(UMI_ERR_ARG, "stats_split must be in 64..2^30");
+        ctx->stats_split = (uint32_t)value;
     } else if (!strcmp(name, "fused_sliced")) {
         ctx->fused_sliced = value != 0;
     } else if (!strcmp(name, "fused_blocks")) {
@@ -3811,6 +3820,204 @@ int umi_count_matrix(umi_ctx *ctx, const uint8_t *kept, const int32_t *freq, con
         HIP_TRY(hipStreamSynchronize(s));
     }
     *nnz = got;
+    return UMI_OK;
+}
+
+} // extern "C"
+
+// ---- family sizes, UMI distances and UMI usage of a batched call ------------------------------------
+namespace {
+struct DsShape { // what the checks find out
+    uint64_t n = 0;  // entries
+    uint32_t m = 0;  // non-empty buckets
+    bool per_umi = false;
+};
+// what both forms check before a device is looked at (the context last)
+int ds_check(umi_ctx *ctx, const void *keys, int n_words, const void *freq, const void *kept, const void *root,
+             const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, uint32_t hist_bins, const void *count_pre,
+             const void *count_post, const void *dist, const void *umi_entry, const void *times_pre, const void *reads_pre,
+             const void *times_post, const void *reads_post, const uint64_t *n_umis, DsShape *shape)
+{
+    if (!count_pre || !count_post || !dist) return fail(UMI_ERR_ARG, "count_pre, count_post or dist is NULL");
+    const int given = (umi_entry != nullptr) + (times_pre != nullptr) + (reads_pre != nullptr) + (times_post != nullptr) +
+                      (reads_post != nullptr);
+    if (given != 0 && given != 5) return fail(UMI_ERR_ARG, "the five arrays of the per-UMI table are given together or not at all");
+    if (given && !n_umis) return fail(UMI_ERR_ARG, "n_umis is NULL");
+    if (umi_len < 1 || umi_len > UMI_MAX_WIDE_UMI_LEN)
+        return fail(UMI_ERR_ARG, "umi_len %d outside 1..%d", umi_len, UMI_MAX_WIDE_UMI_LEN);
+    if (n_words != (3 * umi_len + 63) / 64) return fail(UMI_ERR_ARG, "n_words must be %d for umi_len %d", (3 * umi_len + 63) / 64, umi_len);
+    if (hist_bins < 2 || hist_bins > (1u << 24)) return fail(UMI_ERR_ARG, "hist_bins %u outside 2..2^24", hist_bins);
+    if (n_buckets && !bucket_off) return fail(UMI_ERR_ARG, "bucket_off is NULL");
+    if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
+    uint64_t m = 0;
+    for (uint64_t b = 0; b < n_buckets; b++) {
+        const uint64_t lo = bucket_off[b], hi = bucket_off[b + 1];
+        if (hi < lo) return fail(UMI_ERR_ARG, "bucket_off is not monotone at bucket %llu", (unsigned long long)b);
+        if (hi - lo >= (1ull << 28))
+            return fail(UMI_ERR_ARG, "bucket %llu has %llu entries, 2^28 or more", (unsigned long long)b, (unsigned long long)(hi - lo));
+        if (hi >= (1ull << 31)) return fail(UMI_ERR_ARG, "%llu entries exceed the 31-bit index space of one call", (unsigned long long)hi);
+        m += hi != lo;
+    }
+    const uint64_t n = n_buckets ? bucket_off[n_buckets] : 0;
+    if (n && (!keys || !freq || !kept || !root)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (given && n >= (1ull << 30)) return fail(UMI_ERR_ARG, "%llu entries exceed the 30-bit index space of the per-UMI table's sort", (unsigned long long)n);
+    if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
+    shape->n = n;
+    shape->m = (uint32_t)m;
+    shape->per_umi = given != 0;
+    return UMI_OK;
+}
+
+// everything on the device; *rows: the per-UMI table's rows
+int ds_run(umi_ctx *ctx, const DsShape &shape, const uint64_t *d_keys, int n_words, const int32_t *d_freq, const uint8_t *d_kept,
+           const uint32_t *d_root, const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, uint64_t seed, uint32_t hist_bins,
+           uint64_t *d_count_pre, uint64_t *d_count_post, uint64_t *d_dist, uint32_t *d_umi_entry, uint32_t *d_times_pre,
+           uint64_t *d_reads_pre, uint32_t *d_times_post, uint64_t *d_reads_post, uint64_t *rows, hipStream_t s)
+{
+    int rc;
+    const uint32_t n = (uint32_t)shape.n, m = shape.m;
+    // the pinned block: the non-empty buckets' offsets | the deep buckets' pieces | their numbers (room for the most
+    // there can be: a deep bucket has at least 64 entries)
+    const size_t deep_max = std::min<size_t>(m, n / 64), tasks_max = n / STATS_PIECE + deep_max;
+    const size_t o_tasks = ((size_t)m + 1) * 8, o_deep = o_tasks + tasks_max * sizeof(StatsTask);
+    if ((rc = ctx->ds_h.reserve(o_deep + deep_max * 4))) return rc;
+    uint64_t *h_off = (uint64_t *)ctx->ds_h.p;
+    {
+        uint32_t k = 0;
+        h_off[0] = 0;
+        for (uint64_t b = 0; b < n_buckets; b++)
+            if (bucket_off[b + 1] != bucket_off[b]) h_off[++k] = bucket_off[b + 1];
+    }
+    StatsCall c;
+    stats_plan(h_off, m, ctx->stats_split, umi_len, &c.split, &c.n_deep, &c.n_tasks);
+    if (c.n_deep > deep_max || c.n_tasks > tasks_max) return fail(UMI_ERR_HIP, "internal: %u deep buckets in %u pieces", c.n_deep, c.n_tasks);
+    if ((rc = ctx->ds_ws.reserve(stats_workspace_bytes(n, m, c.n_deep, c.n_tasks, umi_len, shape.per_umi)))) return rc;
+    c.d_keys = d_keys;
+    c.d_freq = d_freq;
+    c.d_kept = d_kept;
+    c.d_root = d_root;
+    c.h_off = h_off;
+    c.n = n;
+    c.m = m;
+    c.hist_bins = hist_bins;
+    c.n_cus = (uint32_t)ctx->n_cus;
+    c.umi_len = umi_len;
+    c.n_words = n_words;
+    c.seed = seed;
+    c.d_count_pre = d_count_pre;
+    c.d_count_post = d_count_post;
+    c.d_dist = d_dist;
+    c.d_umi_entry = d_umi_entry;
+    c.d_times_pre = d_times_pre;
+    c.d_times_post = d_times_post;
+    c.d_reads_pre = d_reads_pre;
+    c.d_reads_post = d_reads_post;
+    c.h_tasks = (StatsTask *)(ctx->ds_h.p + o_tasks);
+    c.h_deep_j = (uint32_t *)(ctx->ds_h.p + o_deep);
+    c.h_pinned = ctx->h_counters;
+    ctx->h_counters[2] = 0;
+    const int r = stats_on_device(ctx->ds_ws.p, c, s);
+    if (r < 0) return fail(UMI_ERR_HIP, "dedup stats: %s", hipGetErrorString((hipError_t)(-r)));
+    if (ctx->h_counters[0])
+        return fail(UMI_ERR_ARG, "%llu keys hold a code that is none of A, C, G, T, N below base %d",
+                    (unsigned long long)ctx->h_counters[0], umi_len);
+    if (ctx->h_counters[1])
+        return fail(UMI_ERR_ARG, "%llu entries have a root outside their bucket, at an entry that was not kept, or are kept "
+                                 "with another root than themselves", (unsigned long long)ctx->h_counters[1]);
+    *rows = shape.per_umi ? ctx->h_counters[2] : 0;
+    return UMI_OK;
+}
+} // namespace
+
+extern "C" {
+
+int umi_dedup_stats_device(umi_ctx *ctx, const uint64_t *d_keys, int n_words, const int32_t *d_freq, const uint8_t *d_kept,
+                           const uint32_t *d_root, const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, uint64_t seed,
+                           uint32_t hist_bins, uint64_t *d_count_pre, uint64_t *d_count_post, uint64_t *d_dist,
+                           uint32_t *d_umi_entry, uint32_t *d_times_pre, uint64_t *d_reads_pre, uint32_t *d_times_post,
+                           uint64_t *d_reads_post, uint64_t *n_umis, void *hip_stream)
+{
+    DsShape shape;
+    int rc = ds_check(ctx, d_keys, n_words, d_freq, d_kept, d_root, bucket_off, n_buckets, umi_len, hist_bins, d_count_pre,
+                      d_count_post, d_dist, d_umi_entry, d_times_pre, d_reads_pre, d_times_post, d_reads_post, n_umis, &shape);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_count_matrix)
+    if (n_umis) *n_umis = 0;
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
+    if (shape.m == 0) {
+        HIP_TRY(hipMemsetAsync(d_count_pre, 0, (size_t)hist_bins * 8, s));
+        HIP_TRY(hipMemsetAsync(d_count_post, 0, (size_t)hist_bins * 8, s));
+        HIP_TRY(hipMemsetAsync(d_dist, 0, 4 * ((size_t)umi_len + 2) * 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return UMI_OK;
+    }
+    uint64_t rows = 0;
+    rc = ds_run(ctx, shape, d_keys, n_words, d_freq, d_kept, d_root, bucket_off, n_buckets, umi_len, seed, hist_bins, d_count_pre,
+                d_count_post, d_dist, d_umi_entry, d_times_pre, d_reads_pre, d_times_post, d_reads_post, &rows, s);
+    if (rc) return rc;
+    if (n_umis) *n_umis = rows;
+    return UMI_OK;
+}
+
+int umi_dedup_stats(umi_ctx *ctx, const uint64_t *keys, int n_words, const int32_t *freq, const uint8_t *kept, const uint32_t *root,
+                    const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, uint64_t seed, uint32_t hist_bins,
+                    uint64_t *count_pre, uint64_t *count_post, uint64_t *dist, uint32_t *umi_entry, uint32_t *times_pre,
+                    uint64_t *reads_pre, uint32_t *times_post, uint64_t *reads_post, uint64_t *n_umis)
+{
+    DsShape shape;
+    int rc = ds_check(ctx, keys, n_words, freq, kept, root, bucket_off, n_buckets, umi_len, hist_bins, count_pre, count_post, dist,
+                      umi_entry, times_pre, reads_pre, times_post, reads_post, n_umis, &shape);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    if (n_umis) *n_umis = 0;
+    const size_t dist_words = 4 * ((size_t)umi_len + 2);
+    if (shape.m == 0) { // (nothing is launched)
+        memset(count_pre, 0, (size_t)hist_bins * 8);
+        memset(count_post, 0, (size_t)hist_bins * 8);
+        memset(dist, 0, dist_words * 8);
+        return UMI_OK;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx);
+    // the host arrays' device copies in one block: keys | freq | root | the three tables | the per-UMI table | kept
+    const size_t n = (size_t)shape.n, nu = shape.per_umi ? n : 0;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_keys = 0, o_freq = o_keys + up(n * 8 * (size_t)n_words), o_root = o_freq + up(n * 4), o_pre = o_root + up(n * 4),
+                 o_post = o_pre + up((size_t)hist_bins * 8), o_dist = o_post + up((size_t)hist_bins * 8),
+                 o_entry = o_dist + up(dist_words * 8), o_tpre = o_entry + up(nu * 4), o_rpre = o_tpre + up(nu * 4),
+                 o_tpost = o_rpre + up(nu * 8), o_rpost = o_tpost + up(nu * 4), o_kept = o_rpost + up(nu * 8),
+                 total = o_kept + up(n);
+    if ((rc = ctx->ds_io.reserve(total))) return rc;
+    char *d = ctx->ds_io.as<char>();
+    hipStream_t s = ctx->own_stream;
+    HIP_TRY(hipMemcpyAsync(d + o_keys, keys, n * 8 * (size_t)n_words, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_freq, freq, n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_root, root, n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_kept, kept, n, hipMemcpyHostToDevice, s));
+    uint64_t rows = 0;
+    rc = ds_run(ctx, shape, (const uint64_t *)(d + o_keys), n_words, (const int32_t *)(d + o_freq), (const uint8_t *)(d + o_kept),
+                (const uint32_t *)(d + o_root), bucket_off, n_buckets, umi_len, seed, hist_bins, (uint64_t *)(d + o_pre),
+                (uint64_t *)(d + o_post), (uint64_t *)(d + o_dist), shape.per_umi ? (uint32_t *)(d + o_entry) : nullptr,
+                shape.per_umi ? (uint32_t *)(d + o_tpre) : nullptr, shape.per_umi ? (uint64_t *)(d + o_rpre) : nullptr,
+                shape.per_umi ? (uint32_t *)(d + o_tpost) : nullptr, shape.per_umi ? (uint64_t *)(d + o_rpost) : nullptr, &rows, s);
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(count_pre, d + o_pre, (size_t)hist_bins * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(count_post, d + o_post, (size_t)hist_bins * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(dist, d + o_dist, dist_words * 8, hipMemcpyDeviceToHost, s));
+    if (rows) {
+        HIP_TRY(hipMemcpyAsync(umi_entry, d + o_entry, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(times_pre, d + o_tpre, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(reads_pre, d + o_rpre, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(times_post, d + o_tpost, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(reads_post, d + o_rpost, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (n_umis) *n_umis = rows;
     return UMI_OK;
 }
 

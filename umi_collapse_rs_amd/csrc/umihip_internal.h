@@ -461,6 +461,39 @@ int count_matrix_on_device(void *workspace, const uint8_t *d_kept, const int32_t
                            uint64_t *d_out_reads, uint64_t *nnz, uint64_t *bad_ids, uint32_t n_cus, unsigned long long *h_pinned,
                            hipStream_t s);
 
+// ---- family sizes, UMI distances and UMI usage of a batched call (umihip_stats.hip: umi_dedup_stats) ----
+constexpr uint32_t STATS_LANE_MAX = 8;    // a bucket of more entries is a wave's
+constexpr uint32_t STATS_HIST_LDS = 2048; // family-size bins a block counts in LDS; the others by global atomics
+constexpr uint32_t STATS_PIECE = 1024;    // entries of a deep bucket a wave takes at a time
+constexpr uint32_t STATS_SPLIT = 4096;    // option "stats_split": buckets of at least this many entries go to the whole grid
+struct StatsTask {                        // a piece [lo, hi) of deep bucket `deep`
+    uint64_t lo, hi;
+    uint32_t deep, pad;
+};
+// the split that is used (raised by itself where the deep buckets' tables would pass 512 MB), the buckets at or
+// above it and their pieces; h_off: the m + 1 offsets of the m >= 1 non-empty buckets
+void stats_plan(const uint64_t *h_off, uint32_t m, uint32_t split, int umi_len, uint32_t *split_used, uint32_t *n_deep,
+                uint32_t *n_tasks);
+size_t stats_workspace_bytes(uint32_t n, uint32_t m, uint32_t n_deep, uint32_t n_tasks, int umi_len, bool per_umi);
+struct StatsCall {
+    const uint64_t *d_keys;
+    const int32_t *d_freq;
+    const uint8_t *d_kept;
+    const uint32_t *d_root;
+    const uint64_t *h_off; // pinned
+    uint32_t n, m, split, n_deep, n_tasks, hist_bins, n_cus;
+    int umi_len, n_words;
+    uint64_t seed;
+    uint64_t *d_count_pre, *d_count_post, *d_dist;
+    uint32_t *d_umi_entry, *d_times_pre, *d_times_post; // the per-UMI table: all five or none
+    uint64_t *d_reads_pre, *d_reads_post;
+    uint32_t *h_deep_j;          // pinned, [n_deep]
+    StatsTask *h_tasks;          // pinned, [n_tasks]
+    unsigned long long *h_pinned; // 3 pinned words: keys with a bad code, entries with a bad root, rows of the table
+};
+// One synchronisation, at the end.  0 ok; negative: -(hipError_t)
+int stats_on_device(void *workspace, const StatsCall &c, hipStream_t s);
+
 // ---- sort and scan primitives of the staging (umihip_radix.hip) ----
 constexpr int RADIX_BINS = 256, RADIX_MAX_PASSES = 8; // 8-bit digits; a 64-bit key has at most eight
 constexpr int RADIX_HIST_PARTS = 2048;                // blocks of a kernel that counts digits, at most

@@ -14,6 +14,23 @@
 // message of its own: --per-gene with fastq mode, --two-pass, --paired, --keep-unmapped, --tag, --call-consensus
 // or --passthrough; --gene-tag without --per-gene, or not a tag name of two characters; --count-matrix without
 // --per-gene, with --dump-staging, or a DIR that cannot be made.
+// --output-stats PREFIX [--output-stats-seed S] (bam/sam mode, one pass; umi_tools dedup --output-stats, not the
+// reference's, tests/stats_model.py defines it): after the collapse one call to umi_dedup_stats (include/umihip.h)
+// over the staged keys and freq and the collapse's kept[] and root[] -- asked of the collapse for the flag, which alone
+// does not move --stage auto to the host -- and three tab-separated files, uncompressed, lines ended by \n:
+// PREFIX_per_umi_per_position.tsv ("counts instances_pre instances_post": how many entries had that many reads before,
+// how many kept entries stand for that many after; a row per count with a non-zero instance, ascending; hist_bins is
+// min(2^22, 2 + the largest bucket's reads), so below 2^22 nothing reaches the last bin, whose row would read
+// "<hist_bins-1>+"), PREFIX_edit_distance.tsv ("edit_distance unique unique_null <algo> <algo>_null" with --algo's
+// value: per bucket the mean pair distance of its UMIs before and after, rounded up, against a null drawn from the
+// file's UMI usage with seed S [default 0]; rows 0..umi_len, all of them, then Single_UMI) and PREFIX_per_umi.tsv
+// ("UMI times_observed_pre total_counts_pre times_observed_post total_counts_post", a row per distinct UMI in the
+// library's order).  The distances are letter distances whatever --distance says; with a whitelist the corrected UMI
+// is what is counted; with --devices the call runs on the first.  The three files are made here, while the flags
+// are looked at and after every other refusal, so a prefix that cannot be written ends the run with status 101 before
+// the GPU is woken.  Refused likewise, each with a message of its own: fastq mode, --two-pass (its windows never hold
+// the file's UMI usage), --dump-staging, --passthrough, --output-stats-seed without --output-stats or not a whole
+// number in 0..2^64-1.  The output BAM and the summary lines are as without the flag.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -70,6 +87,9 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     bool per_gene = false, gene_tag_given = false; // --per-gene: a bucket is a gene, with --per-cell a (cell, gene) pair
     std::string gene_tag = "GX";                   // --gene-tag XX: the gene's tag
     std::string count_matrix;                      // --count-matrix DIR: molecules per cell and gene, MatrixMarket files
+    std::string output_stats;        // --output-stats PREFIX: three tables on what the deduplication did
+    uint64_t output_stats_seed = 0;  // --output-stats-seed S: the seed of the tables' null
+    bool output_stats_seed_given = false;
     bool edit_distance = false; // --distance edit: -k bounds the Levenshtein distance (umi_dedup_batch_edit)
     // filled in by validate(): --algo as UMI_ALGO_*, --merge as 0 any, 1 avgqual, 2 mapqual, and the two lists
     int algo_id = 0, merge_id = 0;
@@ -159,6 +179,13 @@ void usage()
               "      --count-matrix <DIR> with --per-gene: write the molecules per cell and gene to DIR (made if it is\n"
               "                           not there) as features.tsv, barcodes.tsv, matrix.mtx (molecules) and reads.mtx\n"
               "                           (reads), MatrixMarket coordinate files sorted by cell, then gene, counted on the GPU\n"
+              "      --output-stats <PREFIX> write three tables, counted on the GPU (umi_tools dedup --output-stats):\n"
+              "                           PREFIX_per_umi_per_position.tsv (reads per UMI and position, before and after),\n"
+              "                           PREFIX_edit_distance.tsv (mean UMI distance per position before and after, each\n"
+              "                           against a null drawn from the file's UMI usage; letter distances also with\n"
+              "                           --distance edit) and PREFIX_per_umi.tsv (how every UMI sequence is used)\n"
+              "                           (bam/sam mode, one pass; not with --dump-staging, --passthrough)\n"
+              "      --output-stats-seed <S> with --output-stats: seed of the null, 0..2^64-1 [default: 0]\n"
               "      --device <ID>        GPU to use [default: 0]\n"
               "      --devices <ID,..>    several GPUs of the node: alignment positions are sharded over them");
 }
@@ -228,6 +255,17 @@ Cli parse(int argc, char **argv)
         else if (a == "--per-gene") c.per_gene = true;
         else if (a == "--gene-tag") { c.gene_tag = need(i); c.gene_tag_given = true; } // (looked at by validate)
         else if (a == "--count-matrix") c.count_matrix = need(i);
+        else if (a == "--output-stats") c.output_stats = need(i);
+        else if (a == "--output-stats-seed") {
+            const std::string v = need(i);
+            errno = 0;
+            char *end = nullptr;
+            const unsigned long long w = std::strtoull(v.c_str(), &end, 10);
+            const bool digits = !v.empty() && v.find_first_not_of("0123456789") == std::string::npos;
+            if (!digits || *end != '\0' || errno == ERANGE) die("--output-stats-seed wants a whole number in 0..2^64-1: '" + v + "'");
+            c.output_stats_seed = (uint64_t)w;
+            c.output_stats_seed_given = true;
+        }
         else if (a == "--umi-whitelist") c.umi_whitelist = need(i);
         else if (a == "--whitelist-metrics") c.whitelist_metrics = need(i);
         else if (a == "--whitelist-max-mismatches" || a == "--whitelist-min-distance") {
@@ -327,6 +365,13 @@ void check_edit_length(const Cli &args, size_t umi_length, const std::string &wh
         die("--distance edit takes UMIs of at most 21 bases (" + whose + " " + std::to_string(umi_length) + ")");
 }
 
+// --output-stats: its three files (none without the flag)
+std::vector<std::string> output_stats_paths(const Cli &args)
+{
+    if (args.output_stats.empty()) return {};
+    return {args.output_stats + "_per_umi_per_position.tsv", args.output_stats + "_edit_distance.tsv", args.output_stats + "_per_umi.tsv"};
+}
+
 // The refusals that need nothing but the command line and the lists it names, in the order that decides
 // which message wins when two apply; fills in the defaults and the decoded --algo / --merge.  False: a
 // --mode that is none of bam, sam, fastq, for which nothing happens.
@@ -395,6 +440,14 @@ bool validate(Cli &args)
         if (!args.dump_staging.empty() || args.passthrough) die("--cell-whitelist does not go with --dump-staging or --passthrough");
         args.cell_list = read_whitelist(args.cell_whitelist, args.cell_len, "cell barcode whitelist", "barcode", 32);
     }
+    // --output-stats: likewise (its files are made last, once nothing else refuses the run)
+    if (args.output_stats_seed_given && args.output_stats.empty()) die("--output-stats-seed goes with --output-stats only");
+    if (!args.output_stats.empty()) {
+        if (args.mode == "fastq") die("--output-stats is defined in bam/sam mode only");
+        if (args.two_pass) die("--output-stats does not go with --two-pass (its windows never hold the file's UMI usage)");
+        if (!args.dump_staging.empty()) die("--output-stats does not go with --dump-staging");
+        if (args.passthrough) die("--output-stats does not go with --passthrough");
+    }
     if (args.track_clusters && args.paired) die("--tag with --paired is not implemented (the reference never reaches its tagging pass)");
     if (args.algo == "dir") args.algo_id = UMI_ALGO_DIRECTIONAL;
     else if (args.algo == "adj") args.algo_id = UMI_ALGO_ADJACENCY;
@@ -409,6 +462,11 @@ bool validate(Cli &args)
         struct stat sb;
         if (why != EEXIST || stat(args.count_matrix.c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode))
             die("cannot make the directory " + args.count_matrix + " for --count-matrix: " + std::strerror(why));
+    }
+    for (const std::string &path : output_stats_paths(args)) {
+        FILE *f = std::fopen(path.c_str(), "wb");
+        if (!f) die("cannot make " + path + " for --output-stats: " + std::strerror(errno));
+        std::fclose(f);
     }
     return true;
 }

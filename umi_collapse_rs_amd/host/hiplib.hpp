@@ -15,6 +15,8 @@
 //
 // --count-matrix DIR (with --per-gene): umi_count_matrix, the one library call behind the flag, is resolved only
 // when the flag is given, so that a library without it serves every other run.
+//
+// --output-stats PREFIX: likewise umi_dedup_stats.
 #pragma once
 #include <chrono>
 #include <dlfcn.h>
@@ -77,6 +79,9 @@ struct HipLib {
     // --count-matrix: likewise
     bool want_count = false;
     decltype(&umi_count_matrix) count_matrix = nullptr;
+    // --output-stats: likewise
+    bool want_stats = false;
+    decltype(&umi_dedup_stats) dedup_stats = nullptr;
     // (the HIP runtime the library brings along: device buffers for the arrays above)
     int (*hip_set_device)(int) = nullptr; // (the current device is per thread: the context was made on another)
     int (*hip_malloc)(void **, size_t) = nullptr;
@@ -85,7 +90,7 @@ struct HipLib {
     explicit HipLib(const Cli &args)
         : want_edit(args.edit_distance), want_consensus(args.consensus), want_consensus_bam(args.call_consensus),
           want_correct(!args.whitelist.empty()), want_barcodes(!args.cell_list.empty()),
-          want_count(!args.count_matrix.empty())
+          want_count(!args.count_matrix.empty()), want_stats(!args.output_stats.empty())
     {
     }
     bool load()
@@ -126,6 +131,7 @@ struct HipLib {
         if (want_correct) correct_umis = (decltype(correct_umis))sym("umi_correct_umis");
         if (want_barcodes) correct_barcodes = (decltype(correct_barcodes))sym("umi_correct_barcodes");
         if (want_count) count_matrix = (decltype(count_matrix))sym("umi_count_matrix");
+        if (want_stats) dedup_stats = (decltype(dedup_stats))sym("umi_dedup_stats");
         hip_set_device = (decltype(hip_set_device))sym("hipSetDevice");
         hip_malloc = (decltype(hip_malloc))sym("hipMalloc");
         hip_memcpy = (decltype(hip_memcpy))sym("hipMemcpy");

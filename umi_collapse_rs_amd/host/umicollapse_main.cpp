@@ -69,6 +69,8 @@
 // "%%MatrixMarket matrix coordinate integer general", then "G C NNZ", then NNZ lines "row col molecules", counted
 // from 1, by column and then row; reads.mtx, the same with the reads.  The molecules add up to "Number of reads
 // after deduplicating".
+// --output-stats PREFIX [--output-stats-seed S]: three tables on what the deduplication did, from one call to
+// umi_dedup_stats after the collapse (cli.hpp has the flag's definition and its refusals; output_stats() below).
 // --algo cluster: connected components of "within -k" (cli.hpp); every pipeline here only forwards the algorithm
 // to the library, so it goes with every flag --algo dir goes with.
 // Not implemented, as in the reference: --algo cc (that spelling stays refused; `cluster` is the mode's name).
@@ -123,6 +125,7 @@ struct OnePass {
     const int algo = args.algo_id, merge = args.merge_id;
     const unsigned T = std::max(1u, args.num_threads);
     const bool need_clusters = args.track_clusters || args.call_consensus; // every read's entry, every entry's root
+    const bool need_root = need_clusters || !args.output_stats.empty();    // root[] of the collapse (no host staging for it alone)
 
     umi::bam::File in;
     uint32_t n_rec = 0, chunk = 0; // records; records per thread of the per-read passes
@@ -225,6 +228,7 @@ struct OnePass {
         }
         collapse();
         if (!args.count_matrix.empty()) count_matrix();
+        if (!args.output_stats.empty()) output_stats();
         if (need_clusters) number_clusters();
         select_records();
         if (args.call_consensus) call_consensus();
@@ -752,7 +756,7 @@ struct OnePass {
     {
         lap("to-hot-path");
         kept.assign(n + 1, 0);
-        root.resize(need_clusters ? n + 1 : 0);
+        root.resize(need_root ? n + 1 : 0);
         std::memset(&st, 0, sizeof(st));
         t_gpu0 = t_gpu1 = now_s();
         if (!args.passthrough && n) {
@@ -762,7 +766,7 @@ struct OnePass {
             t_gpu0 = now_s();
             if (lib.dedup(ctx, keys.data(), any_n ? nmask.data() : nullptr, n_words, freq.data(), off.data(), nb,
                           (int)umi_length, args.k, args.percentage, algo, 0 /* adjacency.rs:56 */,
-                          kept.data(), need_clusters ? root.data() : nullptr, &st) != UMI_OK)
+                          kept.data(), need_root ? root.data() : nullptr, &st) != UMI_OK)
                 die(lib.last_error());
             t_gpu1 = now_s();
         }
@@ -812,6 +816,65 @@ struct OnePass {
         write("matrix.mtx", mol);
         write("reads.mtx", rd);
         lap("count matrix");
+    }
+
+    // --output-stats: family sizes, UMI distances and UMI usage in one call over the staged keys and freq and the
+    // collapse's kept[] and root[], then the three files
+    void output_stats()
+    {
+        const size_t L = umi_length;
+        uint64_t most = 0; // the largest bucket's reads: no total is larger
+        for (size_t b = 0; b < nb; b++) {
+            uint64_t reads = 0;
+            for (uint64_t i = off[b]; i < off[b + 1]; i++) reads += (uint64_t)freq[i];
+            most = std::max(most, reads);
+        }
+        const uint32_t bins = (uint32_t)std::min<uint64_t>(1u << 22, 2 + most);
+        std::vector<uint64_t> count_pre(bins, 0), count_post(bins, 0), dist(4 * (L + 2), 0), reads_pre(n + 1), reads_post(n + 1);
+        std::vector<uint32_t> umi_entry(n + 1), times_pre(n + 1), times_post(n + 1);
+        uint64_t rows = 0;
+        if (n) {
+            need_ctx();
+            if (!lib.dedup_stats) die("libumihip.so lacks umi_dedup_stats");
+            if (lib.dedup_stats(ctx, keys.data(), n_words, freq.data(), kept.data(), root.data(), off.data(), nb, (int)L,
+                                args.output_stats_seed, bins, count_pre.data(), count_post.data(), dist.data(), umi_entry.data(),
+                                times_pre.data(), reads_pre.data(), times_post.data(), reads_post.data(), &rows) != UMI_OK)
+                die(lib.last_error());
+        }
+        const std::vector<std::string> paths = output_stats_paths(args);
+        auto write = [&](const std::string &path, const std::string &text) {
+            FILE *f = std::fopen(path.c_str(), "wb");
+            if (!f) die("cannot open " + path);
+            const bool ok = std::fwrite(text.data(), 1, text.size(), f) == text.size();
+            if (std::fclose(f) != 0 || !ok) die("cannot write " + path);
+        };
+        std::string text = "counts\tinstances_pre\tinstances_post\n";
+        for (uint32_t c = 0; c < bins; c++)
+            if (count_pre[c] || count_post[c])
+                text.append(std::to_string(c)).append(c == bins - 1 ? "+" : "").append("\t").append(std::to_string(count_pre[c]))
+                    .append("\t").append(std::to_string(count_post[c])).append("\n");
+        write(paths[0], text);
+        text = "edit_distance\tunique\tunique_null\t" + args.algo + "\t" + args.algo + "_null\n";
+        for (size_t j = 0; j < L + 2; j++) {
+            text.append(j <= L ? std::to_string(j) : std::string("Single_UMI"));
+            for (size_t r = 0; r < 4; r++) text.append("\t").append(std::to_string(dist[r * (L + 2) + j]));
+            text.append("\n");
+        }
+        write(paths[1], text);
+        text = "UMI\ttimes_observed_pre\ttotal_counts_pre\ttimes_observed_post\ttotal_counts_post\n";
+        for (uint64_t j = 0; j < rows; j++) {
+            const uint64_t *k = &keys[(size_t)umi_entry[j] * n_words];
+            for (size_t b = 0; b < L; b++) { // the 3-bit code at bits [3b, 3b + 3) of the key as one little-endian integer
+                const size_t w = 3 * b / 64, sh = 3 * b % 64;
+                uint64_t c = k[w] >> sh;
+                if (sh > 61 && w + 1 < (size_t)n_words) c |= k[w + 1] << (64 - sh);
+                text.push_back("A??GNTC?"[c & 7]);
+            }
+            text.append("\t").append(std::to_string(times_pre[j])).append("\t").append(std::to_string(reads_pre[j])).append("\t")
+                .append(std::to_string(times_post[j])).append("\t").append(std::to_string(reads_post[j])).append("\n");
+        }
+        write(paths[2], text);
+        lap("output stats");
     }
 
     // --tag, --call-consensus: cluster id / size per entry from the root of every entry.  Survivors in index
