@@ -7,13 +7,17 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wextra -Wno-unuse
 
 LIB := $(PKG)/libumihip.so
 OBJDIR := build/obj
-OBJS := $(OBJDIR)/umihip_kernels.o $(OBJDIR)/umihip_seg.o $(OBJDIR)/umihip_collapse.o $(OBJDIR)/umihip_stage.o $(OBJDIR)/umihip_radix.o $(OBJDIR)/umihip_wide.o $(OBJDIR)/umihip_edit.o $(OBJDIR)/umihip_seq.o $(OBJDIR)/umihip_consensus.o $(OBJDIR)/umihip_consensus_bam.o $(OBJDIR)/umihip_correct.o $(OBJDIR)/umihip_barcode.o $(OBJDIR)/umihip_count.o $(OBJDIR)/umihip_stats.o $(OBJDIR)/umihip_api.o
+# the library's translation units, listed once: the kernels (.hip), then the host side (.cpp)
+SRCS := umihip_kernels umihip_seg umihip_collapse umihip_stage umihip_radix umihip_wide umihip_edit umihip_seq \
+        umihip_consensus umihip_consensus_bam umihip_correct umihip_barcode umihip_count umihip_stats \
+        umihip_api umihip_batch umihip_stage_api umihip_seq_api umihip_correct_api umihip_count_api umihip_data
+OBJS := $(patsubst %,$(OBJDIR)/%.o,$(SRCS))
 # development build (make dev): the shipped sources plus the round-1 tile kernels, their key sort
 # and their options (-DUMIHIP_DEV), as libumihip_dev.so; the legacy cross-check tests load it
 DEVDIR := build/obj_dev
 DEVLIB := $(PKG)/libumihip_dev.so
-DEVOBJS := $(DEVDIR)/umihip_kernels.o $(DEVDIR)/umihip_seg.o $(DEVDIR)/umihip_collapse.o $(DEVDIR)/umihip_stage.o $(DEVDIR)/umihip_radix.o $(DEVDIR)/umihip_wide.o $(DEVDIR)/umihip_edit.o $(DEVDIR)/umihip_seq.o $(DEVDIR)/umihip_consensus.o $(DEVDIR)/umihip_consensus_bam.o $(DEVDIR)/umihip_correct.o $(DEVDIR)/umihip_barcode.o $(DEVDIR)/umihip_count.o $(DEVDIR)/umihip_stats.o $(DEVDIR)/umihip_api.o $(DEVDIR)/umihip_legacy.o $(DEVDIR)/umihip_sort.o
-HDRS := $(CSRC)/umihip_internal.h $(CSRC)/umihip_cons_group.h $(CSRC)/umihip_device.h $(CSRC)/umihip_plan.hpp include/umihip.h
+DEVOBJS := $(patsubst %,$(DEVDIR)/%.o,$(SRCS)) $(DEVDIR)/umihip_legacy.o $(DEVDIR)/umihip_sort.o
+HDRS := $(CSRC)/umihip_internal.h $(CSRC)/umihip_cons_group.h $(CSRC)/umihip_device.h $(CSRC)/umihip_plan.hpp $(CSRC)/umihip_host.hpp include/umihip.h
 CLI := $(PKG)/bin/umicollapse
 
 all: $(LIB) oracle cpptest $(CLI)

@@ -1,0 +1,342 @@
+// Tables over a call's result: umi_count_matrix*, umi_dedup_stats*.
+#include "umihip_host.hpp"
+
+#include <algorithm>
+
+using namespace umihip;
+
+// ---- molecules and reads per (column, row) pair ---------------------------------------------------
+namespace {
+// what both forms check before a device is looked at (the context last)
+int cm_check(umi_ctx *ctx, const void *kept, const void *freq, const uint64_t *bucket_off, uint64_t n_buckets, const void *row,
+             const void *col, const void *out_row, const void *out_col, const void *out_molecules, const void *out_reads,
+             const uint64_t *nnz)
+{
+    if (!nnz) return fail(UMI_ERR_ARG, "nnz is NULL");
+    if (n_buckets >= (1ull << 30))
+        return fail(UMI_ERR_ARG, "%llu buckets exceed the 30-bit index space of one call", (unsigned long long)n_buckets);
+    if (n_buckets && !bucket_off) return fail(UMI_ERR_ARG, "bucket_off is NULL");
+    if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
+    if (n_buckets && (!row || !col || !out_row || !out_col || !out_molecules || !out_reads))
+        return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (n_buckets && bucket_off[n_buckets] && (!kept || !freq)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
+    return UMI_OK;
+}
+
+// The table walked once into the pinned staging: its non-empty buckets' offsets (a run of equal offsets is
+// one) and, from the first empty bucket on, their numbers.  *m: the non-empty buckets; *idx: null where
+// nothing was left out.
+int cm_walk(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, uint32_t *m, const uint64_t **off, const uint32_t **idx)
+{
+    int rc;
+    const size_t off_bytes = ((size_t)n_buckets + 1) * 8;
+    if ((rc = ctx->cm_h.reserve(off_bytes + (size_t)n_buckets * 4))) return rc;
+    uint64_t *o = (uint64_t *)ctx->cm_h.p;
+    uint32_t *x = (uint32_t *)(ctx->cm_h.p + off_bytes);
+    uint32_t k = 0;
+    o[0] = 0;
+    for (uint64_t b = 0; b < n_buckets; b++) {
+        const uint64_t lo = bucket_off[b], hi = bucket_off[b + 1];
+        if (hi < lo) return fail(UMI_ERR_ARG, "bucket_off is not monotone at bucket %llu", (unsigned long long)b);
+        if (hi == lo) continue;
+        x[k] = (uint32_t)b;
+        o[++k] = hi;
+    }
+    *m = k;
+    *off = o;
+    *idx = k == n_buckets ? nullptr : x;
+    return UMI_OK;
+}
+
+int cm_run(umi_ctx *ctx, const uint8_t *d_kept, const int32_t *d_freq, uint32_t m, const uint64_t *h_off, const uint32_t *h_idx,
+           const uint32_t *d_row, const uint32_t *d_col, uint32_t n_rows, uint32_t n_cols, uint32_t *d_out_row, uint32_t *d_out_col,
+           uint32_t *d_out_molecules, uint64_t *d_out_reads, uint64_t *nnz, hipStream_t s)
+{
+    int rc;
+    if ((rc = ctx->cm_ws.reserve(count_workspace_bytes(m, h_idx != nullptr)))) return rc;
+    uint64_t bad = 0;
+    const int r = count_matrix_on_device(ctx->cm_ws.p, d_kept, d_freq, h_off, h_idx, m, d_row, d_col, n_rows, n_cols, d_out_row,
+                                         d_out_col, d_out_molecules, d_out_reads, nnz, &bad, (uint32_t)ctx->n_cus, ctx->h_counters, s);
+    if (r < 0) return fail(UMI_ERR_HIP, "count matrix: %s", hipGetErrorString((hipError_t)(-r)));
+    if (bad) {
+        *nnz = 0;
+        return fail(UMI_ERR_ARG, "%llu non-empty buckets have a row id of %u or more, or a column id of %u or more",
+                    (unsigned long long)bad, n_rows, n_cols);
+    }
+    return UMI_OK;
+}
+} // namespace
+
+extern "C" {
+
+int umi_count_matrix_device(umi_ctx *ctx, const uint8_t *d_kept, const int32_t *d_freq, const uint64_t *bucket_off,
+                            uint64_t n_buckets, const uint32_t *d_row, const uint32_t *d_col, uint32_t n_rows, uint32_t n_cols,
+                            uint32_t *d_out_row, uint32_t *d_out_col, uint32_t *d_out_molecules, uint64_t *d_out_reads,
+                            uint64_t *nnz, void *hip_stream)
+{
+    int rc = cm_check(ctx, d_kept, d_freq, bucket_off, n_buckets, d_row, d_col, d_out_row, d_out_col, d_out_molecules, d_out_reads, nnz);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_correct_barcodes)
+    *nnz = 0;
+    if (n_buckets == 0) return UMI_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
+    uint32_t m = 0;
+    const uint64_t *h_off = nullptr;
+    const uint32_t *h_idx = nullptr;
+    if ((rc = cm_walk(ctx, bucket_off, n_buckets, &m, &h_off, &h_idx))) return rc;
+    if (m == 0) return UMI_OK;
+    if (n_rows == 0 || n_cols == 0) return fail(UMI_ERR_ARG, "a matrix of %u rows and %u columns with a non-empty bucket", n_rows, n_cols);
+    return cm_run(ctx, d_kept, d_freq, m, h_off, h_idx, d_row, d_col, n_rows, n_cols, d_out_row, d_out_col, d_out_molecules,
+                  d_out_reads, nnz, (hipStream_t)hip_stream);
+}
+
+int umi_count_matrix(umi_ctx *ctx, const uint8_t *kept, const int32_t *freq, const uint64_t *bucket_off, uint64_t n_buckets,
+                     const uint32_t *row, const uint32_t *col, uint32_t n_rows, uint32_t n_cols, uint32_t *out_row,
+                     uint32_t *out_col, uint32_t *out_molecules, uint64_t *out_reads, uint64_t *nnz)
+{
+    int rc = cm_check(ctx, kept, freq, bucket_off, n_buckets, row, col, out_row, out_col, out_molecules, out_reads, nnz);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    *nnz = 0;
+    if (n_buckets == 0) return UMI_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx);
+    uint32_t m = 0;
+    const uint64_t *h_off = nullptr;
+    const uint32_t *h_idx = nullptr;
+    if ((rc = cm_walk(ctx, bucket_off, n_buckets, &m, &h_off, &h_idx))) return rc;
+    if (m == 0) return UMI_OK;
+    if (n_rows == 0 || n_cols == 0) return fail(UMI_ERR_ARG, "a matrix of %u rows and %u columns with a non-empty bucket", n_rows, n_cols);
+    // the host arrays' device copies in one block: freq | row | col | the four outputs | kept
+    const size_t n = (size_t)bucket_off[n_buckets], nb = (size_t)n_buckets, cap = (size_t)m;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_freq = 0, o_row = o_freq + up(n * 4), o_col = o_row + up(nb * 4), o_orow = o_col + up(nb * 4),
+                 o_ocol = o_orow + up(cap * 4), o_omol = o_ocol + up(cap * 4), o_oreads = o_omol + up(cap * 4),
+                 o_kept = o_oreads + up(cap * 8), total = o_kept + up(n);
+    if ((rc = ctx->cm_io.reserve(total))) return rc;
+    char *d = ctx->cm_io.as<char>();
+    hipStream_t s = ctx->own_stream;
+    HIP_TRY(hipMemcpyAsync(d + o_kept, kept, n, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_freq, freq, n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_row, row, nb * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_col, col, nb * 4, hipMemcpyHostToDevice, s));
+    uint64_t got = 0;
+    rc = cm_run(ctx, (const uint8_t *)(d + o_kept), (const int32_t *)(d + o_freq), m, h_off, h_idx, (const uint32_t *)(d + o_row),
+                (const uint32_t *)(d + o_col), n_rows, n_cols, (uint32_t *)(d + o_orow), (uint32_t *)(d + o_ocol),
+                (uint32_t *)(d + o_omol), (uint64_t *)(d + o_oreads), &got, s);
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    if (got) {
+        HIP_TRY(hipMemcpyAsync(out_row, d + o_orow, (size_t)got * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_col, d + o_ocol, (size_t)got * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_molecules, d + o_omol, (size_t)got * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_reads, d + o_oreads, (size_t)got * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    *nnz = got;
+    return UMI_OK;
+}
+
+} // extern "C"
+
+// ---- family sizes, UMI distances and UMI usage of a batched call ------------------------------------
+namespace {
+struct DsShape { // what the checks find out
+    uint64_t n = 0;  // entries
+    uint32_t m = 0;  // non-empty buckets
+    bool per_umi = false;
+};
+// what both forms check before a device is looked at (the context last)
+int ds_check(umi_ctx *ctx, const void *keys, int n_words, const void *freq, const void *kept, const void *root,
+             const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, uint32_t hist_bins, const void *count_pre,
+             const void *count_post, const void *dist, const void *umi_entry, const void *times_pre, const void *reads_pre,
+             const void *times_post, const void *reads_post, const uint64_t *n_umis, DsShape *shape)
+{
+    if (!count_pre || !count_post || !dist) return fail(UMI_ERR_ARG, "count_pre, count_post or dist is NULL");
+    const int given = (umi_entry != nullptr) + (times_pre != nullptr) + (reads_pre != nullptr) + (times_post != nullptr) +
+                      (reads_post != nullptr);
+    if (given != 0 && given != 5) return fail(UMI_ERR_ARG, "the five arrays of the per-UMI table are given together or not at all");
+    if (given && !n_umis) return fail(UMI_ERR_ARG, "n_umis is NULL");
+    if (umi_len < 1 || umi_len > UMI_MAX_WIDE_UMI_LEN)
+        return fail(UMI_ERR_ARG, "umi_len %d outside 1..%d", umi_len, UMI_MAX_WIDE_UMI_LEN);
+    if (n_words != (3 * umi_len + 63) / 64) return fail(UMI_ERR_ARG, "n_words must be %d for umi_len %d", (3 * umi_len + 63) / 64, umi_len);
+    if (hist_bins < 2 || hist_bins > (1u << 24)) return fail(UMI_ERR_ARG, "hist_bins %u outside 2..2^24", hist_bins);
+    if (n_buckets && !bucket_off) return fail(UMI_ERR_ARG, "bucket_off is NULL");
+    if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
+    uint64_t m = 0;
+    for (uint64_t b = 0; b < n_buckets; b++) {
+        const uint64_t lo = bucket_off[b], hi = bucket_off[b + 1];
+        if (hi < lo) return fail(UMI_ERR_ARG, "bucket_off is not monotone at bucket %llu", (unsigned long long)b);
+        if (hi - lo >= (1ull << 28))
+            return fail(UMI_ERR_ARG, "bucket %llu has %llu entries, 2^28 or more", (unsigned long long)b, (unsigned long long)(hi - lo));
+        if (hi >= (1ull << 31)) return fail(UMI_ERR_ARG, "%llu entries exceed the 31-bit index space of one call", (unsigned long long)hi);
+        m += hi != lo;
+    }
+    const uint64_t n = n_buckets ? bucket_off[n_buckets] : 0;
+    if (n && (!keys || !freq || !kept || !root)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (given && n >= (1ull << 30)) return fail(UMI_ERR_ARG, "%llu entries exceed the 30-bit index space of the per-UMI table's sort", (unsigned long long)n);
+    if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
+    shape->n = n;
+    shape->m = (uint32_t)m;
+    shape->per_umi = given != 0;
+    return UMI_OK;
+}
+
+// everything on the device; *rows: the per-UMI table's rows
+int ds_run(umi_ctx *ctx, const DsShape &shape, const uint64_t *d_keys, int n_words, const int32_t *d_freq, const uint8_t *d_kept,
+           const uint32_t *d_root, const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, uint64_t seed, uint32_t hist_bins,
+           uint64_t *d_count_pre, uint64_t *d_count_post, uint64_t *d_dist, uint32_t *d_umi_entry, uint32_t *d_times_pre,
+           uint64_t *d_reads_pre, uint32_t *d_times_post, uint64_t *d_reads_post, uint64_t *rows, hipStream_t s)
+{
+    int rc;
+    const uint32_t n = (uint32_t)shape.n, m = shape.m;
+    // the pinned block: the non-empty buckets' offsets | the deep buckets' pieces | their numbers (room for the most
+    // there can be: a deep bucket has at least 64 entries)
+    const size_t deep_max = std::min<size_t>(m, n / 64), tasks_max = n / STATS_PIECE + deep_max;
+    const size_t o_tasks = ((size_t)m + 1) * 8, o_deep = o_tasks + tasks_max * sizeof(StatsTask);
+    if ((rc = ctx->ds_h.reserve(o_deep + deep_max * 4))) return rc;
+    uint64_t *h_off = (uint64_t *)ctx->ds_h.p;
+    {
+        uint32_t k = 0;
+        h_off[0] = 0;
+        for (uint64_t b = 0; b < n_buckets; b++)
+            if (bucket_off[b + 1] != bucket_off[b]) h_off[++k] = bucket_off[b + 1];
+    }
+    StatsCall c;
+    stats_plan(h_off, m, ctx->stats_split, umi_len, &c.split, &c.n_deep, &c.n_tasks);
+    if (c.n_deep > deep_max || c.n_tasks > tasks_max) return fail(UMI_ERR_HIP, "internal: %u deep buckets in %u pieces", c.n_deep, c.n_tasks);
+    if ((rc = ctx->ds_ws.reserve(stats_workspace_bytes(n, m, c.n_deep, c.n_tasks, umi_len, shape.per_umi)))) return rc;
+    c.d_keys = d_keys;
+    c.d_freq = d_freq;
+    c.d_kept = d_kept;
+    c.d_root = d_root;
+    c.h_off = h_off;
+    c.n = n;
+    c.m = m;
+    c.hist_bins = hist_bins;
+    c.n_cus = (uint32_t)ctx->n_cus;
+    c.umi_len = umi_len;
+    c.n_words = n_words;
+    c.seed = seed;
+    c.d_count_pre = d_count_pre;
+    c.d_count_post = d_count_post;
+    c.d_dist = d_dist;
+    c.d_umi_entry = d_umi_entry;
+    c.d_times_pre = d_times_pre;
+    c.d_times_post = d_times_post;
+    c.d_reads_pre = d_reads_pre;
+    c.d_reads_post = d_reads_post;
+    c.h_tasks = (StatsTask *)(ctx->ds_h.p + o_tasks);
+    c.h_deep_j = (uint32_t *)(ctx->ds_h.p + o_deep);
+    c.h_pinned = ctx->h_counters;
+    ctx->h_counters[2] = 0;
+    const int r = stats_on_device(ctx->ds_ws.p, c, s);
+    if (r < 0) return fail(UMI_ERR_HIP, "dedup stats: %s", hipGetErrorString((hipError_t)(-r)));
+    if (ctx->h_counters[0])
+        return fail(UMI_ERR_ARG, "%llu keys hold a code that is none of A, C, G, T, N below base %d",
+                    (unsigned long long)ctx->h_counters[0], umi_len);
+    if (ctx->h_counters[1])
+        return fail(UMI_ERR_ARG, "%llu entries have a root outside their bucket, at an entry that was not kept, or are kept "
+                                 "with another root than themselves", (unsigned long long)ctx->h_counters[1]);
+    *rows = shape.per_umi ? ctx->h_counters[2] : 0;
+    return UMI_OK;
+}
+} // namespace
+
+extern "C" {
+
+int umi_dedup_stats_device(umi_ctx *ctx, const uint64_t *d_keys, int n_words, const int32_t *d_freq, const uint8_t *d_kept,
+                           const uint32_t *d_root, const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, uint64_t seed,
+                           uint32_t hist_bins, uint64_t *d_count_pre, uint64_t *d_count_post, uint64_t *d_dist,
+                           uint32_t *d_umi_entry, uint32_t *d_times_pre, uint64_t *d_reads_pre, uint32_t *d_times_post,
+                           uint64_t *d_reads_post, uint64_t *n_umis, void *hip_stream)
+{
+    DsShape shape;
+    int rc = ds_check(ctx, d_keys, n_words, d_freq, d_kept, d_root, bucket_off, n_buckets, umi_len, hist_bins, d_count_pre,
+                      d_count_post, d_dist, d_umi_entry, d_times_pre, d_reads_pre, d_times_post, d_reads_post, n_umis, &shape);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_count_matrix)
+    if (n_umis) *n_umis = 0;
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
+    if (shape.m == 0) {
+        HIP_TRY(hipMemsetAsync(d_count_pre, 0, (size_t)hist_bins * 8, s));
+        HIP_TRY(hipMemsetAsync(d_count_post, 0, (size_t)hist_bins * 8, s));
+        HIP_TRY(hipMemsetAsync(d_dist, 0, 4 * ((size_t)umi_len + 2) * 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return UMI_OK;
+    }
+    uint64_t rows = 0;
+    rc = ds_run(ctx, shape, d_keys, n_words, d_freq, d_kept, d_root, bucket_off, n_buckets, umi_len, seed, hist_bins, d_count_pre,
+                d_count_post, d_dist, d_umi_entry, d_times_pre, d_reads_pre, d_times_post, d_reads_post, &rows, s);
+    if (rc) return rc;
+    if (n_umis) *n_umis = rows;
+    return UMI_OK;
+}
+
+int umi_dedup_stats(umi_ctx *ctx, const uint64_t *keys, int n_words, const int32_t *freq, const uint8_t *kept, const uint32_t *root,
+                    const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, uint64_t seed, uint32_t hist_bins,
+                    uint64_t *count_pre, uint64_t *count_post, uint64_t *dist, uint32_t *umi_entry, uint32_t *times_pre,
+                    uint64_t *reads_pre, uint32_t *times_post, uint64_t *reads_post, uint64_t *n_umis)
+{
+    DsShape shape;
+    int rc = ds_check(ctx, keys, n_words, freq, kept, root, bucket_off, n_buckets, umi_len, hist_bins, count_pre, count_post, dist,
+                      umi_entry, times_pre, reads_pre, times_post, reads_post, n_umis, &shape);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    if (n_umis) *n_umis = 0;
+    const size_t dist_words = 4 * ((size_t)umi_len + 2);
+    if (shape.m == 0) { // (nothing is launched)
+        memset(count_pre, 0, (size_t)hist_bins * 8);
+        memset(count_post, 0, (size_t)hist_bins * 8);
+        memset(dist, 0, dist_words * 8);
+        return UMI_OK;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx);
+    // the host arrays' device copies in one block: keys | freq | root | the three tables | the per-UMI table | kept
+    const size_t n = (size_t)shape.n, nu = shape.per_umi ? n : 0;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_keys = 0, o_freq = o_keys + up(n * 8 * (size_t)n_words), o_root = o_freq + up(n * 4), o_pre = o_root + up(n * 4),
+                 o_post = o_pre + up((size_t)hist_bins * 8), o_dist = o_post + up((size_t)hist_bins * 8),
+                 o_entry = o_dist + up(dist_words * 8), o_tpre = o_entry + up(nu * 4), o_rpre = o_tpre + up(nu * 4),
+                 o_tpost = o_rpre + up(nu * 8), o_rpost = o_tpost + up(nu * 4), o_kept = o_rpost + up(nu * 8),
+                 total = o_kept + up(n);
+    if ((rc = ctx->ds_io.reserve(total))) return rc;
+    char *d = ctx->ds_io.as<char>();
+    hipStream_t s = ctx->own_stream;
+    HIP_TRY(hipMemcpyAsync(d + o_keys, keys, n * 8 * (size_t)n_words, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_freq, freq, n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_root, root, n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_kept, kept, n, hipMemcpyHostToDevice, s));
+    uint64_t rows = 0;
+    rc = ds_run(ctx, shape, (const uint64_t *)(d + o_keys), n_words, (const int32_t *)(d + o_freq), (const uint8_t *)(d + o_kept),
+                (const uint32_t *)(d + o_root), bucket_off, n_buckets, umi_len, seed, hist_bins, (uint64_t *)(d + o_pre),
+                (uint64_t *)(d + o_post), (uint64_t *)(d + o_dist), shape.per_umi ? (uint32_t *)(d + o_entry) : nullptr,
+                shape.per_umi ? (uint32_t *)(d + o_tpre) : nullptr, shape.per_umi ? (uint64_t *)(d + o_rpre) : nullptr,
+                shape.per_umi ? (uint32_t *)(d + o_tpost) : nullptr, shape.per_umi ? (uint64_t *)(d + o_rpost) : nullptr, &rows, s);
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(count_pre, d + o_pre, (size_t)hist_bins * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(count_post, d + o_post, (size_t)hist_bins * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(dist, d + o_dist, dist_words * 8, hipMemcpyDeviceToHost, s));
+    if (rows) {
+        HIP_TRY(hipMemcpyAsync(umi_entry, d + o_entry, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(times_pre, d + o_tpre, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(reads_pre, d + o_rpre, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(times_post, d + o_tpost, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(reads_post, d + o_rpost, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (n_umis) *n_umis = rows;
+    return UMI_OK;
+}
+
+} // extern "C"
