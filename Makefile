@@ -20,7 +20,7 @@ DEVOBJS := $(patsubst %,$(DEVDIR)/%.o,$(SRCS)) $(DEVDIR)/umihip_legacy.o $(DEVDI
 HDRS := $(CSRC)/umihip_internal.h $(CSRC)/umihip_cons_group.h $(CSRC)/umihip_device.h $(CSRC)/umihip_plan.hpp $(CSRC)/umihip_host.hpp include/umihip.h
 CLI := $(PKG)/bin/umicollapse
 
-all: $(LIB) oracle cpptest $(CLI)
+all: $(LIB) oracle cpptest primtest $(CLI)
 
 # one object per translation unit (the rocPRIM sort alone takes ~20 s to compile)
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
@@ -67,9 +67,21 @@ cpptest: $(LIB) oracle tests/cpp/test_host.cpp $(PKG)/host/umi_collapse.hpp
 	g++ -O2 -std=c++17 -Wall -Wextra -o build/test_host tests/cpp/test_host.cpp \
 	    -L$(PKG) -lumihip -Loracle -lumi_oracle -Wl,-rpath,'$$ORIGIN/../$(PKG)' -Wl,-rpath,'$$ORIGIN/../oracle'
 
+# the sort and scan primitives on their own: umihip_radix.o and a program that calls it directly.  The
+# test is compiled to an object first: on one line with -x hip the linker's object would be read as source
+PRIMTEST := build/test_primitives
+$(OBJDIR)/test_primitives.o: tests/cpp/test_primitives.hip tests/cpp/primitives_ref.hpp $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -c -o $@ -x hip $<
+
+$(PRIMTEST): $(OBJDIR)/test_primitives.o $(OBJDIR)/umihip_radix.o
+	$(HIPCC) $(HIPFLAGS) -o $@ $(OBJDIR)/test_primitives.o $(OBJDIR)/umihip_radix.o
+
+primtest: $(PRIMTEST)
+
 clean:
 	rm -f $(LIB) $(DEVLIB) $(CLI)
 	rm -rf build
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all dev oracle asm clean cpptest cli
+.PHONY: all dev oracle asm clean cpptest primtest cli

@@ -499,7 +499,8 @@ constexpr int RADIX_BINS = 256, RADIX_MAX_PASSES = 8; // 8-bit digits; a 64-bit 
 constexpr int RADIX_HIST_PARTS = 2048;                // blocks of a kernel that counts digits, at most
 size_t radix_sort_temp_bytes(uint32_t n);
 // stable sort of (key, value) pairs by bits [begin_bit, end_bit) of the key (n < 2^30); the buffers
-// are used in turn, *result_in_b says where the result lies.  hist_parts > 0: the digit counts were
+// are used in turn, *result_in_b says where the result lies.  temp holds radix_sort_temp_bytes(n)
+// bytes or more, whatever the bit range: less is hipErrorInvalidValue.  hist_parts > 0: the digit counts were
 // taken by the kernel that wrote the keys -- block b of its hist_parts blocks put its counts of pass
 // p (bits [begin_bit + 8p, +8)) and digit d at parts[(b * passes + p) * 256 + d], zeros included,
 // parts being what radix_sort_prepare returned; that call zeroes the sort's temporaries and

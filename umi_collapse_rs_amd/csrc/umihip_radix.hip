@@ -8,8 +8,8 @@
 // alignment and by UMI; here the reads are sorted by (alignment key, UMI) instead and equal
 // neighbours are one entry (umihip_stage.hip).  Integer / byte work on HBM streams, no MFMA.
 //
-// One pass over a tile of 4,096 pairs (256 threads, 16 rounds of 64 pairs per wave):
-//   rank   every key's position among the keys of its digit inside its wave's 1,024 pairs, in
+// One pass over a tile of 4,096 pairs (1,024 threads, 4 rounds of 64 pairs per wave):
+//   rank   every key's position among the keys of its digit inside its wave's 256 pairs, in
 //          order: the lanes of a round that share a digit find each other with eight ballots (one
 //          per bit of the digit), the wave keeps a running count per digit in LDS;
 //   chain  the tile's 256 counts are published, thread d adds up digit d's counts of the tiles before
@@ -352,8 +352,8 @@ hipError_t radix_sort_impl(KeyT *keys_a, KeyT *keys_b, uint32_t *vals_a, uint32_
     if (n == 0 || end_bit <= begin_bit) return hipSuccess;
     if (begin_bit < 0 || end_bit > (int)sizeof(KeyT) * 8 || n > RS_COUNT) return hipErrorInvalidValue;
     const int passes = (end_bit - begin_bit + 7) / 8;
+    if (radix_sort_temp_bytes(n) > temp_bytes) return hipErrorInvalidValue; // (the whole of it, however few the passes)
     const RadixTemp t = radix_carve(temp, n, passes);
-    if (t.total > temp_bytes) return hipErrorInvalidValue;
     const uint32_t tiles = tiles_of(n, RS_TILE);
     if (hist_parts > (uint32_t)RADIX_HIST_PARTS) return hipErrorInvalidValue;
     if (!hist_parts) {
@@ -397,8 +397,8 @@ hipError_t radix_sort_prepare(void *temp, size_t temp_bytes, uint32_t n, int beg
 {
     *hist_parts = nullptr;
     if (n == 0 || end_bit <= begin_bit) return hipSuccess;
+    if (radix_sort_temp_bytes(n) > temp_bytes) return hipErrorInvalidValue;
     const RadixTemp t = radix_carve(temp, n, (end_bit - begin_bit + 7) / 8);
-    if (t.total > temp_bytes) return hipErrorInvalidValue;
     *hist_parts = t.parts;
     return hipMemsetAsync(temp, 0, t.zero_bytes, s);
 }
