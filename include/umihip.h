@@ -460,6 +460,37 @@ int umi_correct_barcodes(umi_ctx *ctx, const uint8_t *bc_ascii, uint64_t n_reads
                          const uint8_t *whitelist_ascii, uint32_t n_wl, int max_mismatches, int32_t *match,
                          uint8_t *status, uint64_t counts[4]);
 
+/* ---- ambiguous cell barcodes decided by posterior (the program's --cell-whitelist-multi): the call above with
+ *      max_mismatches 1, and the reads it leaves ambiguous weighed as STARsolo's 1MM_multi[_pseudocounts] and
+ *      Cell Ranger weigh them.  No counterpart in the reference; tests/barcode_multi_model.py defines the rule.
+ * in : as umi_correct_barcodes, and bc_qual: the barcodes' qualities, bc_len bytes per read beside bc_ascii's,
+ *      Phred + 33, every byte in 33..126; min_posterior_permille in 0..1000; pseudocount in 0..1000.
+ * out: exact, corrected and none are what umi_correct_barcodes gives (a single candidate is accepted whatever
+ *      its count).  exact_reads[e] (uint32 [n_wl], may be NULL): the reads of this call that are exact with
+ *      match e.  For a read with two or more listed barcodes one substitution away (one N: that agree
+ *      everywhere else), candidate e with its mismatch at position p has the weight
+ *        w_e = (exact_reads[e] + pseudocount) * T[min(qual[p] - 33, 40)],  T[q] = round(2^26 * 10^(-q / 10)),
+ *      W is the sum of the weights and e* the candidate of greatest weight, the smallest index on ties.  Where
+ *      W > 0 and 1000 * w_e* >= min_posterior_permille * W the read is UMI_BARCODE_RESOLVED with match = e*;
+ *      otherwise it stays UMI_BARCODE_AMBIGUOUS, match = -1.  All in integers (the comparison in 128 bits):
+ *      the result is exact and the same in every run.  counts (host): the reads of each of the five statuses;
+ *      counts[3] + counts[4] is umi_correct_barcodes' counts[3].
+ * n_reads == 0, a multi-device context and a deferred call that is out: as umi_correct_barcodes.
+ * Refusals as umi_correct_barcodes, and UMI_ERR_ARG: bc_qual NULL with n_reads > 0, min_posterior_permille or
+ * pseudocount outside 0..1000.  UMI_ERR_CHAR: a quality byte outside 33..126, "Unknown character in cell
+ * barcode quality: <byte> (read <index>)", the smallest such read, found beside the barcodes' check before
+ * anything is written; a bad barcode byte of that read or an earlier one is reported in its place.  After any
+ * refusal the outputs are as they were. */
+#define UMI_BARCODE_RESOLVED 4
+int umi_correct_barcodes_multi_device(umi_ctx *ctx, const uint8_t *d_bc_ascii, const uint8_t *d_bc_qual, uint64_t n_reads,
+                                      int bc_len, const uint8_t *whitelist_ascii, uint32_t n_wl,
+                                      int min_posterior_permille, int pseudocount, int32_t *d_match, uint8_t *d_status,
+                                      uint32_t *d_exact_reads, uint64_t counts[5], void *hip_stream);
+int umi_correct_barcodes_multi(umi_ctx *ctx, const uint8_t *bc_ascii, const uint8_t *bc_qual, uint64_t n_reads, int bc_len,
+                               const uint8_t *whitelist_ascii, uint32_t n_wl, int min_posterior_permille,
+                               int pseudocount, int32_t *match, uint8_t *status, uint32_t *exact_reads,
+                               uint64_t counts[5]);
+
 /* ---- molecules and reads per (column, row) pair (the program's --count-matrix): what a batched call kept,
  *      summed over its buckets into the triplets of a sparse matrix, on the GPU.  No counterpart in the
  *      reference; the counting is umi_tools count --per-gene --per-cell's, tests/gene_model.py (count_model)

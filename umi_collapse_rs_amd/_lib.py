@@ -108,6 +108,11 @@ SIGNATURES = {
                                               C.c_void_p, C.c_void_p, _u64p, C.c_void_p]),
     "umi_correct_barcodes": (C.c_int, [C.c_void_p, _u8p, C.c_uint64, C.c_int, _u8p, C.c_uint32, C.c_int, _i32p, _u8p,
                                        _u64p]),
+    "umi_correct_barcodes_multi_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, _u8p,
+                                                    C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    _u64p, C.c_void_p]),
+    "umi_correct_barcodes_multi": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_uint64, C.c_int, _u8p, C.c_uint32, C.c_int,
+                                             C.c_int, _i32p, _u8p, _u32p, _u64p]),
     "umi_count_matrix_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_uint64, C.c_void_p, C.c_void_p,
                                           C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p,
                                           C.c_void_p]),

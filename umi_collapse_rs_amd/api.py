@@ -419,6 +419,42 @@ class Context:
                                                  ptr(counts, C.c_uint64), stream or None))
         return counts
 
+    def correct_barcodes_multi(self, bc_bytes, qual_bytes, bc_len, whitelist, min_posterior_permille=975, pseudocount=0):
+        """correct_barcodes with max_mismatches 1 and the ambiguous reads decided by posterior
+        (umi_correct_barcodes_multi): qual_bytes uint8 [n * bc_len], Phred + 33, beside bc_bytes.  A candidate's
+        weight is (its exact reads in this call + pseudocount) times the chance of an error at the quality of the
+        mismatched base; the heaviest is taken where it holds min_posterior_permille of all the weight.  Returns
+        dict(match int32 [n], status uint8 [n] (... 3 ambiguous, 4 resolved), counts uint64 [5], exact_reads
+        uint32 [n_wl])."""
+        bc_bytes = np.ascontiguousarray(bc_bytes, dtype=np.uint8).reshape(-1)
+        qual_bytes = np.ascontiguousarray(qual_bytes, dtype=np.uint8).reshape(-1)
+        if bc_len < 1 or bc_bytes.size % bc_len:
+            raise ValueError("bc_bytes is not a whole number of barcodes")
+        if qual_bytes.size != bc_bytes.size:
+            raise ValueError("qual_bytes is not of bc_bytes' size")
+        n = bc_bytes.size // bc_len
+        wl, n_wl = self._whitelist_bytes(whitelist, bc_len)
+        m = max(1, n)
+        match, status = np.zeros(m, np.int32), np.zeros(m, np.uint8)
+        counts, exact_reads = np.zeros(5, np.uint64), np.zeros(max(1, n_wl), np.uint32)
+        check(load().umi_correct_barcodes_multi(self._h, ptr(bc_bytes, C.c_uint8), ptr(qual_bytes, C.c_uint8), n, bc_len,
+                                                ptr(wl, C.c_uint8), n_wl, min_posterior_permille, pseudocount,
+                                                ptr(match, C.c_int32), ptr(status, C.c_uint8),
+                                                ptr(exact_reads, C.c_uint32), ptr(counts, C.c_uint64)))
+        return {"match": match[:n], "status": status[:n], "counts": counts, "exact_reads": exact_reads[:n_wl]}
+
+    def correct_barcodes_multi_device(self, d_bc, d_qual, n_reads, bc_len, whitelist, min_posterior_permille, pseudocount,
+                                      d_match, d_status=0, d_exact_reads=0, stream=0):
+        """The same on raw device pointers (umi_correct_barcodes_multi_device; the whitelist stays on the host):
+        fills d_match and, where given, d_status and d_exact_reads (uint32 [n_wl]); returns counts uint64 [5]."""
+        wl, n_wl = self._whitelist_bytes(whitelist, bc_len)
+        counts = np.zeros(5, np.uint64)
+        check(load().umi_correct_barcodes_multi_device(self._h, d_bc or None, d_qual or None, n_reads, bc_len,
+                                                       ptr(wl, C.c_uint8), n_wl, min_posterior_permille, pseudocount,
+                                                       d_match or None, d_status or None, d_exact_reads or None,
+                                                       ptr(counts, C.c_uint64), stream or None))
+        return counts
+
     def count_matrix(self, kept, freq, bucket_off, row, col, n_rows, n_cols):
         """Molecules and reads per (column, row) pair (umi_count_matrix): kept uint8 [N] and freq int32 [N] of a
         batched call, bucket_off uint64 [n_buckets + 1], row / col uint32 [n_buckets] the row (gene) and column

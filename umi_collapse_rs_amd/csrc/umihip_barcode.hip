@@ -39,6 +39,19 @@
 //
 // A pass of its own looks at every read byte first (the smallest read with a byte outside ACGTN is
 // reported and nothing is written); the host looks once, after it and the build.
+//
+// umi_correct_barcodes_multi (the program's --cell-whitelist-multi; after STARsolo's 1MM_multi, tests/
+// barcode_multi_model.py defines it): the ambiguous reads are weighed, not dropped.  Two passes:
+//   1. the lookup above, instantiated with MULTI: an exact read also adds 1 to exact_reads[match] (one
+//      atomic per distinct match of a wave: the lanes that share a match elect a leader, so the reads of a
+//      deep cell cost their wave one atomic and not 64 on one address), and the reads that come out
+//      ambiguous go to a global queue, one atomic per wave trip for the queue's tail;
+//   2. barcode_resolve_kernel, a queued read per wave trip, probes the variants again; a lane that hits
+//      forms w = (exact_reads[idx] + pseudocount) * T[min(q, 40)] from the quality at its position, wave
+//      reductions give W = sum w (64 bits; below 2^57) and the greatest (w, smallest idx), and lane 0
+//      accepts the winner where 1000 w >= permille W, both products in 128 bits.
+// The queue's order depends on scheduling; a read's verdict depends on exact_reads and its own bytes only.
+// The qualities are looked at beside the barcodes, before anything is written (bytes 33..126).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <thread>
@@ -68,7 +81,19 @@ enum BcCtl : int {
     BC_SEEN = 2, // the build met a duplicate
     BC_STATUS0 = 3, // four words: reads exact, corrected, none, ambiguous
     BC_COUNT = 7,
+    // umi_correct_barcodes_multi only
+    BC_QUEUED = 7,   // the length of the queue of ambiguous reads
+    BC_RESOLVED = 8, // reads the second pass resolved
+    BC_BAD_QUAL = 9, // smallest read with a quality byte outside 33..126 (all ones: none)
+    BC_COUNT_MULTI = 10,
 };
+
+// T[q] = round(2^26 * 10^(-q / 10)): the chance of an error at Phred quality q, in units of 2^-26
+__constant__ uint32_t BC_ERR_WEIGHT[41] = {
+    67108864, 53306465, 42342831, 33634106, 26716520, 21221686, 16856984, 13389979, 10636038, 8448505, 6710886,
+    5330647,  4234283,  3363411,  2671652,  2122169,  1685698,  1338998,  1063604,  844851,   671089,  533065,
+    423428,   336341,   267165,   212217,   168570,   133900,   106360,   84485,    67109,    53306,   42343,
+    33634,    26717,    21222,    16857,    13390,    10636,    8449,     6711};
 
 // 0..3 for ACGT, 4 for N, 5 for anything else
 __device__ __forceinline__ uint32_t bc_base_code(uint8_t c)
@@ -162,6 +187,28 @@ __global__ void __launch_bounds__(BC_THREADS) barcode_check_kernel(const uint8_t
     }
 }
 
+// the same over the qualities: the smallest read with a byte outside 33..126
+__global__ void __launch_bounds__(BC_THREADS) barcode_qual_check_kernel(const uint8_t *__restrict__ qual, uint32_t n, int bc_len,
+                                                                        unsigned long long *ctl)
+{
+    __shared__ unsigned int first[BC_WAVES];
+    unsigned int mine = 0xFFFFFFFFu;
+    for (uint64_t i = (uint64_t)blockIdx.x * BC_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BC_THREADS) {
+        const uint8_t *u = qual + (size_t)i * bc_len;
+        bool bad = false;
+        for (int b = 0; b < bc_len; b++) bad = bad || u[b] < 33 || u[b] > 126;
+        if (bad) mine = min(mine, (unsigned int)i);
+    }
+    for (int off = 32; off > 0; off >>= 1) mine = min(mine, (unsigned int)__shfl_down((int)mine, off));
+    if ((threadIdx.x & 63) == 0) first[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned int m = first[0];
+        for (int w = 1; w < BC_WAVES; w++) m = min(m, first[w]);
+        if (m != 0xFFFFFFFFu) atomicMin(&ctl[BC_BAD_QUAL], (unsigned long long)m);
+    }
+}
+
 struct BcArgs {
     const uint8_t *bc;
     int32_t *match;
@@ -169,8 +216,13 @@ struct BcArgs {
     unsigned long long *ctl;
     uint32_t n;
     int bc_len, max_mismatches;
+    // MULTI only
+    uint32_t *exact_reads; // [n_wl], zero at the start
+    uint32_t *queue;       // [n] the ambiguous reads, in any order; its length is ctl[BC_QUEUED]
 };
 
+// MULTI: the first pass of umi_correct_barcodes_multi; without it the code is umi_correct_barcodes' as it was
+template <bool MULTI>
 __global__ void __launch_bounds__(BC_THREADS) barcode_lookup_kernel(const BcTable t, const BcArgs a)
 {
     // per wave: the reads that go on to the variants, as (key, read << 8 | position of the N or 0xFF)
@@ -207,6 +259,16 @@ __global__ void __launch_bounds__(BC_THREADS) barcode_lookup_kernel(const BcTabl
             } else {
                 queued = true;
             }
+            if constexpr (MULTI) {
+                // the lanes of one match add their number with one atomic (a wave of a deep cell's reads: one in all)
+                unsigned long long todo = __ballot(hit != BC_EMPTY);
+                while (todo) { // (wave-uniform; the lanes beyond a.n sit this block out, below)
+                    const uint32_t lead = (uint32_t)__builtin_amdgcn_readlane((int)hit, __ffsll(todo) - 1);
+                    const unsigned long long same = __ballot(hit == lead);
+                    if (lane == __ffsll(todo) - 1) atomicAdd(&a.exact_reads[lead], (uint32_t)__builtin_popcountll(same));
+                    todo &= ~same;
+                }
+            }
         }
         // 2. the others to the wave's queue
         const unsigned long long qmask = __ballot(queued);
@@ -220,6 +282,7 @@ __global__ void __launch_bounds__(BC_THREADS) barcode_lookup_kernel(const BcTabl
         __builtin_amdgcn_wave_barrier(); // (one wave, in lockstep; LDS accesses stay in program order)
         // 3. a queued read at a time, a variant per lane
         const int qn = __builtin_popcountll(qmask);
+        uint32_t amb_n = 0, amb_read = 0; // MULTI: the trip's ambiguous reads, the j-th in lane j
         for (int q = 0; q < qn; q++) {
             const uint64_t k0 = q_key[wave][q], rd = q_read[wave][q]; // (one address for the wave: a broadcast)
             const uint32_t npos = (uint32_t)rd & 0xFFu;
@@ -248,10 +311,95 @@ __global__ void __launch_bounds__(BC_THREADS) barcode_lookup_kernel(const BcTabl
                 cnt[UMI_BARCODE_NONE] += hits == 0;
                 cnt[UMI_BARCODE_AMBIGUOUS] += hits > 1;
             }
+            if constexpr (MULTI) {
+                if (hits > 1) { // (wave-uniform)
+                    if (lane == (int)amb_n) amb_read = (uint32_t)(rd >> 8);
+                    amb_n++;
+                }
+            }
+        }
+        if constexpr (MULTI) {
+            if (amb_n) { // one atomic for the trip's stretch of the global queue
+                unsigned long long base = 0;
+                if (lane == 0) base = atomicAdd(&a.ctl[BC_QUEUED], (unsigned long long)amb_n);
+                const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+                if (lane < (int)amb_n) a.queue[at + lane] = amb_read; // (at most n reads are queued in all)
+            }
         }
         __builtin_amdgcn_wave_barrier(); // (the queue is read before the next trip writes it)
     }
     for (int s = 0; s < 4; s++) block_count_add(cnt[s], &a.ctl[BC_STATUS0 + s]);
+}
+
+struct BcResolveArgs {
+    const uint8_t *bc, *qual;
+    const uint32_t *exact_reads, *queue;
+    int32_t *match;
+    uint8_t *status; // may be null
+    unsigned long long *ctl;
+    int bc_len;
+    uint32_t permille, pseudocount;
+};
+
+// The second pass of umi_correct_barcodes_multi: a queued (ambiguous) read per wave trip, a variant per lane.
+__global__ void __launch_bounds__(BC_THREADS) barcode_resolve_kernel(const BcTable t, const BcResolveArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t qn = (uint32_t)a.ctl[BC_QUEUED];
+    unsigned int resolved = 0;
+    for (uint32_t q = blockIdx.x * BC_WAVES + (threadIdx.x >> 6); q < qn; q += gridDim.x * BC_WAVES) {
+        const uint32_t r = a.queue[q];
+        // (every lane packs the read: one address per load for the wave)
+        const uint8_t *u = a.bc + (size_t)r * a.bc_len;
+        uint64_t k0 = 0;
+        uint32_t npos = 0xFFu;
+        for (int b = 0; b < a.bc_len; b++) {
+            const uint32_t c = bc_base_code(u[b]);
+            k0 |= (uint64_t)(c & 3u) << (2 * b);
+            if (c >> 2) npos = (uint32_t)b;
+        }
+        const int n_var = npos != 0xFFu ? 4 : 3 * a.bc_len;
+        uint64_t w_sum = 0, w_best = 0; // this lane's candidates: at most two (3 L <= 96)
+        uint32_t i_best = BC_EMPTY;
+        for (int v0 = 0; v0 < n_var; v0 += 64) {
+            const int v = v0 + lane;
+            if (v < n_var) {
+                const uint32_t p = npos != 0xFFu ? npos : (uint32_t)(v / 3);
+                const uint64_t var = npos != 0xFFu ? k0 | (uint64_t)v << (2 * npos) : k0 ^ (uint64_t)(1 + v % 3) << (2 * (v / 3));
+                const uint32_t found = bc_probe(t, var);
+                if (found != BC_EMPTY) {
+                    const uint32_t ql = min((uint32_t)a.qual[(size_t)r * a.bc_len + p] - 33u, 40u);
+                    const uint64_t w = (uint64_t)(a.exact_reads[found] + a.pseudocount) * BC_ERR_WEIGHT[ql];
+                    w_sum += w;
+                    if (w > w_best || (w == w_best && found < i_best)) {
+                        w_best = w;
+                        i_best = found;
+                    }
+                }
+            }
+        }
+        // the wave's sum, and its greatest weight with the smallest index among equals
+        for (int off = 32; off > 0; off >>= 1) {
+            w_sum += (uint64_t)__shfl_xor((unsigned long long)w_sum, off);
+            const uint64_t w_o = (uint64_t)__shfl_xor((unsigned long long)w_best, off);
+            const uint32_t i_o = (uint32_t)__shfl_xor((int)i_best, off);
+            if (w_o > w_best || (w_o == w_best && i_o < i_best)) {
+                w_best = w_o;
+                i_best = i_o;
+            }
+        }
+        if (lane == 0) {
+            // 1000 w >= permille W, in 128 bits (W < 2^57, but 1000 W may pass 2^64)
+            const uint64_t l_hi = __umul64hi(1000ull, w_best), l_lo = 1000ull * w_best;
+            const uint64_t r_hi = __umul64hi((uint64_t)a.permille, w_sum), r_lo = (uint64_t)a.permille * w_sum;
+            if (w_sum > 0 && (l_hi > r_hi || (l_hi == r_hi && l_lo >= r_lo))) {
+                a.match[r] = (int32_t)i_best;
+                if (a.status) a.status[r] = UMI_BARCODE_RESOLVED;
+                resolved++;
+            }
+        }
+    }
+    block_count_add(resolved, &a.ctl[BC_RESOLVED]);
 }
 
 inline uint32_t blocks_for(uint64_t n, uint32_t per_block) { return (uint32_t)((n + per_block - 1) / per_block); }
@@ -307,10 +455,26 @@ size_t barcode_workspace_bytes(uint32_t n_wl)
     return 256 + align256((size_t)n_wl * 8) + (size_t)barcode_table_slots(n_wl) * 8;
 }
 
+// ... and behind it exact_reads [n_wl] and the queue of ambiguous reads [n_reads]
+size_t barcode_multi_workspace_bytes(uint32_t n_wl, uint32_t n_reads)
+{
+    return barcode_workspace_bytes(n_wl) + align256((size_t)n_wl * 4) + align256((size_t)n_reads * 4);
+}
+
 int barcode_on_device(void *workspace, const uint8_t *d_bc, uint32_t n_reads, int bc_len, const uint64_t *h_packed, uint32_t n_wl,
                       int max_mismatches, int32_t *d_match, uint8_t *d_status, uint64_t counts[4], uint64_t *bad, uint32_t n_cus,
                       unsigned long long *h_pinned, hipStream_t s)
 {
+    return barcode_multi_on_device(workspace, d_bc, nullptr, n_reads, bc_len, h_packed, n_wl, max_mismatches, 0, 0, d_match,
+                                   d_status, nullptr, counts, bad, n_cus, h_pinned, s);
+}
+
+int barcode_multi_on_device(void *workspace, const uint8_t *d_bc, const uint8_t *d_qual, uint32_t n_reads, int bc_len,
+                            const uint64_t *h_packed, uint32_t n_wl, int max_mismatches, uint32_t permille, uint32_t pseudocount,
+                            int32_t *d_match, uint8_t *d_status, uint32_t *d_exact_reads, uint64_t *counts, uint64_t *bad,
+                            uint32_t n_cus, unsigned long long *h_pinned, hipStream_t s)
+{
+    const bool multi = d_qual != nullptr;
     unsigned long long *ctl = (unsigned long long *)workspace;
     uint64_t *d_keys = (uint64_t *)((char *)workspace + 256);
     const uint32_t slots = barcode_table_slots(n_wl);
@@ -319,8 +483,15 @@ int barcode_on_device(void *workspace, const uint8_t *d_bc, uint32_t n_reads, in
     t.keys = d_keys;
     t.mask = slots - 1;
     t.short_keys = bc_len <= 16;
+    uint32_t *exact_reads = multi ? (uint32_t *)((char *)workspace + barcode_workspace_bytes(n_wl)) : nullptr;
+    uint32_t *queue = multi ? (uint32_t *)((char *)exact_reads + align256((size_t)n_wl * 4)) : nullptr;
     BC_TRY(hipMemsetAsync(ctl, 0xFF, 16, s));
     BC_TRY(hipMemsetAsync(ctl + BC_SEEN, 0, (BC_COUNT - BC_SEEN) * 8, s));
+    if (multi) {
+        BC_TRY(hipMemsetAsync(ctl + BC_QUEUED, 0, 16, s));
+        BC_TRY(hipMemsetAsync(ctl + BC_BAD_QUAL, 0xFF, 8, s));
+        BC_TRY(hipMemsetAsync(exact_reads, 0, (size_t)n_wl * 4, s));
+    }
     BC_TRY(hipMemsetAsync(t.slot, 0xFF, (size_t)slots * 8, s));
     BC_TRY(hipMemcpyAsync(d_keys, h_packed, (size_t)n_wl * 8, hipMemcpyHostToDevice, s));
     const uint32_t wl_grid = std::max(1u, std::min(blocks_for(n_wl, BC_THREADS), n_cus * 8));
@@ -329,7 +500,12 @@ int barcode_on_device(void *workspace, const uint8_t *d_bc, uint32_t n_reads, in
     barcode_check_kernel<<<std::max(1u, std::min(blocks_for(n_reads, BC_THREADS), n_cus * 8)), BC_THREADS, 0, s>>>(d_bc, n_reads,
                                                                                                                   bc_len, ctl);
     BC_TRY(hipGetLastError());
-    BC_TRY(hipMemcpyAsync(h_pinned, ctl, 24, hipMemcpyDeviceToHost, s));
+    if (multi) {
+        barcode_qual_check_kernel<<<std::max(1u, std::min(blocks_for(n_reads, BC_THREADS), n_cus * 8)), BC_THREADS, 0, s>>>(
+            d_qual, n_reads, bc_len, ctl);
+        BC_TRY(hipGetLastError());
+    }
+    BC_TRY(hipMemcpyAsync(h_pinned, ctl, multi ? BC_COUNT_MULTI * 8 : 24, hipMemcpyDeviceToHost, s));
     BC_TRY(hipStreamSynchronize(s));
     if (h_pinned[BC_SEEN]) { // (the list first, as its bytes come before the reads')
         barcode_dup_kernel<<<wl_grid, BC_THREADS, 0, s>>>(t, n_wl, ctl);
@@ -339,9 +515,14 @@ int barcode_on_device(void *workspace, const uint8_t *d_bc, uint32_t n_reads, in
         *bad = h_pinned[BC_DUP];
         return 2;
     }
-    if (h_pinned[BC_BAD] != ~0ull) {
+    // (a bad barcode byte is reported before a bad quality byte of the same or a later read)
+    if (h_pinned[BC_BAD] != ~0ull && (!multi || h_pinned[BC_BAD] <= h_pinned[BC_BAD_QUAL])) {
         *bad = h_pinned[BC_BAD];
         return 1;
+    }
+    if (multi && h_pinned[BC_BAD_QUAL] != ~0ull) {
+        *bad = h_pinned[BC_BAD_QUAL];
+        return 3;
     }
     BcArgs a;
     a.bc = d_bc;
@@ -351,12 +532,41 @@ int barcode_on_device(void *workspace, const uint8_t *d_bc, uint32_t n_reads, in
     a.n = n_reads;
     a.bc_len = bc_len;
     a.max_mismatches = max_mismatches;
+    a.exact_reads = exact_reads;
+    a.queue = queue;
     // every block resident at once where there are that many reads (8 blocks of 4 waves per CU)
-    barcode_lookup_kernel<<<std::max(1u, std::min(blocks_for(n_reads, BC_THREADS), n_cus * 8)), BC_THREADS, 0, s>>>(t, a);
+    const uint32_t grid = std::max(1u, std::min(blocks_for(n_reads, BC_THREADS), n_cus * 8));
+    if (!multi) {
+        barcode_lookup_kernel<false><<<grid, BC_THREADS, 0, s>>>(t, a);
+        BC_TRY(hipGetLastError());
+        BC_TRY(hipMemcpyAsync(h_pinned, ctl, BC_COUNT * 8, hipMemcpyDeviceToHost, s));
+        BC_TRY(hipStreamSynchronize(s));
+        for (int c = 0; c < 4; c++) counts[c] = h_pinned[BC_STATUS0 + c];
+        return 0;
+    }
+    barcode_lookup_kernel<true><<<grid, BC_THREADS, 0, s>>>(t, a);
     BC_TRY(hipGetLastError());
-    BC_TRY(hipMemcpyAsync(h_pinned, ctl, BC_COUNT * 8, hipMemcpyDeviceToHost, s));
+    BcResolveArgs ra;
+    ra.bc = d_bc;
+    ra.qual = d_qual;
+    ra.exact_reads = exact_reads;
+    ra.queue = queue;
+    ra.match = d_match;
+    ra.status = d_status;
+    ra.ctl = ctl;
+    ra.bc_len = bc_len;
+    ra.permille = permille;
+    ra.pseudocount = pseudocount;
+    // (the queue's length is known on the device only: the grid is sized for every read, a wave per read, and
+    // capped as above; a block without a read leaves at once)
+    barcode_resolve_kernel<<<std::max(1u, std::min(blocks_for(n_reads, BC_WAVES), n_cus * 8)), BC_THREADS, 0, s>>>(t, ra);
+    BC_TRY(hipGetLastError());
+    if (d_exact_reads) BC_TRY(hipMemcpyAsync(d_exact_reads, exact_reads, (size_t)n_wl * 4, hipMemcpyDeviceToDevice, s));
+    BC_TRY(hipMemcpyAsync(h_pinned, ctl, BC_COUNT_MULTI * 8, hipMemcpyDeviceToHost, s));
     BC_TRY(hipStreamSynchronize(s));
     for (int c = 0; c < 4; c++) counts[c] = h_pinned[BC_STATUS0 + c];
+    counts[UMI_BARCODE_AMBIGUOUS] -= h_pinned[BC_RESOLVED];
+    counts[UMI_BARCODE_RESOLVED] = h_pinned[BC_RESOLVED];
     return 0;
 }
 

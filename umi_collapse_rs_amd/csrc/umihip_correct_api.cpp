@@ -1,4 +1,4 @@
-// Correction to a fixed list: umi_correct_umis*, umi_correct_barcodes*.
+// Correction to a fixed list: umi_correct_umis*, umi_correct_barcodes*, umi_correct_barcodes_multi*.
 #include "umihip_host.hpp"
 
 #include <algorithm>
@@ -146,14 +146,18 @@ int bc_check(umi_ctx *ctx, const void *bc, uint64_t n_reads, int bc_len, const u
     return UMI_OK;
 }
 
+// (umi_correct_barcodes_multi*: d_qual given, with the two parameters of its rule, d_exact_reads and five counts)
 int bc_run(umi_ctx *ctx, const uint8_t *d_bc_ascii, uint64_t n_reads, int bc_len, const std::vector<uint64_t> &packed,
-           uint32_t n_wl, int max_mismatches, int32_t *d_match, uint8_t *d_status, uint64_t counts[4], hipStream_t s)
+           uint32_t n_wl, int max_mismatches, int32_t *d_match, uint8_t *d_status, uint64_t *counts, hipStream_t s,
+           const uint8_t *d_qual = nullptr, int permille = 0, int pseudocount = 0, uint32_t *d_exact_reads = nullptr)
 {
     int rc;
-    if ((rc = ctx->bc_ws.reserve(barcode_workspace_bytes(n_wl)))) return rc;
+    if ((rc = ctx->bc_ws.reserve(d_qual ? barcode_multi_workspace_bytes(n_wl, (uint32_t)n_reads) : barcode_workspace_bytes(n_wl))))
+        return rc;
     uint64_t bad = 0;
-    const int r = barcode_on_device(ctx->bc_ws.p, d_bc_ascii, (uint32_t)n_reads, bc_len, packed.data(), n_wl, max_mismatches,
-                                    d_match, d_status, counts, &bad, (uint32_t)ctx->n_cus, ctx->h_counters, s);
+    const int r = barcode_multi_on_device(ctx->bc_ws.p, d_bc_ascii, d_qual, (uint32_t)n_reads, bc_len, packed.data(), n_wl,
+                                          max_mismatches, (uint32_t)permille, (uint32_t)pseudocount, d_match, d_status,
+                                          d_exact_reads, counts, &bad, (uint32_t)ctx->n_cus, ctx->h_counters, s);
     if (r == 1) {
         uint8_t u[BARCODE_MAX_LEN];
         HIP_TRY(hipMemcpyAsync(u, d_bc_ascii + (size_t)bad * bc_len, (size_t)bc_len, hipMemcpyDeviceToHost, s));
@@ -162,11 +166,32 @@ int bc_run(umi_ctx *ctx, const uint8_t *d_bc_ascii, uint64_t n_reads, int bc_len
         while (b < bc_len - 1 && (u[b] == 'A' || u[b] == 'T' || u[b] == 'C' || u[b] == 'G' || u[b] == 'N')) b++;
         return fail(UMI_ERR_CHAR, "Unknown character in cell barcode: %u (read %llu)", (unsigned)u[b], (unsigned long long)bad);
     }
+    if (r == 3) {
+        uint8_t u[BARCODE_MAX_LEN];
+        HIP_TRY(hipMemcpyAsync(u, d_qual + (size_t)bad * bc_len, (size_t)bc_len, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        int b = 0;
+        while (b < bc_len - 1 && u[b] >= 33 && u[b] <= 126) b++;
+        return fail(UMI_ERR_CHAR, "Unknown character in cell barcode quality: %u (read %llu)", (unsigned)u[b],
+                    (unsigned long long)bad);
+    }
     if (r == 2)
         return fail(UMI_ERR_ARG, "duplicate entry in the barcode whitelist: entry %llu equals an earlier one",
                     (unsigned long long)bad);
     if (r < 0) return fail(UMI_ERR_HIP, "barcode correction: %s", hipGetErrorString((hipError_t)(-r)));
     return UMI_OK;
+}
+
+// what umi_correct_barcodes_multi* refuses beyond bc_check (which looks at the rest, the context last)
+int bc_multi_check(umi_ctx *ctx, const void *bc, const void *qual, uint64_t n_reads, int bc_len, const uint8_t *whitelist_ascii,
+                   uint32_t n_wl, int min_posterior_permille, int pseudocount, const void *match, const uint64_t *counts,
+                   std::vector<uint64_t> &packed)
+{
+    if (min_posterior_permille < 0 || min_posterior_permille > 1000)
+        return fail(UMI_ERR_ARG, "min_posterior_permille %d outside 0..1000", min_posterior_permille);
+    if (pseudocount < 0 || pseudocount > 1000) return fail(UMI_ERR_ARG, "pseudocount %d outside 0..1000", pseudocount);
+    if (n_reads && !qual) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    return bc_check(ctx, bc, n_reads, bc_len, whitelist_ascii, n_wl, 1, match, counts, packed);
 }
 } // namespace
 
@@ -212,6 +237,58 @@ int umi_correct_barcodes(umi_ctx *ctx, const uint8_t *bc_ascii, uint64_t n_reads
     }
     HIP_TRY(hipMemcpyAsync(match, ctx->bc_match.p, n * 4, hipMemcpyDeviceToHost, s));
     if (status) HIP_TRY(hipMemcpyAsync(status, ctx->bc_status.p, n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return UMI_OK;
+}
+
+int umi_correct_barcodes_multi_device(umi_ctx *ctx, const uint8_t *d_bc_ascii, const uint8_t *d_bc_qual, uint64_t n_reads,
+                                      int bc_len, const uint8_t *whitelist_ascii, uint32_t n_wl, int min_posterior_permille,
+                                      int pseudocount, int32_t *d_match, uint8_t *d_status, uint32_t *d_exact_reads,
+                                      uint64_t counts[5], void *hip_stream)
+{
+    std::vector<uint64_t> packed;
+    int rc = bc_multi_check(ctx, d_bc_ascii, d_bc_qual, n_reads, bc_len, whitelist_ascii, n_wl, min_posterior_permille, pseudocount,
+                            d_match, counts, packed);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    for (int c = 0; c < 5; c++) counts[c] = 0;
+    if (n_reads == 0) return UMI_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx);
+    return bc_run(ctx, d_bc_ascii, n_reads, bc_len, packed, n_wl, 1, d_match, d_status, counts, (hipStream_t)hip_stream, d_bc_qual,
+                  min_posterior_permille, pseudocount, d_exact_reads);
+}
+
+int umi_correct_barcodes_multi(umi_ctx *ctx, const uint8_t *bc_ascii, const uint8_t *bc_qual, uint64_t n_reads, int bc_len,
+                               const uint8_t *whitelist_ascii, uint32_t n_wl, int min_posterior_permille, int pseudocount,
+                               int32_t *match, uint8_t *status, uint32_t *exact_reads, uint64_t counts[5])
+{
+    std::vector<uint64_t> packed;
+    int rc = bc_multi_check(ctx, bc_ascii, bc_qual, n_reads, bc_len, whitelist_ascii, n_wl, min_posterior_permille, pseudocount, match,
+                            counts, packed);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    for (int c = 0; c < 5; c++) counts[c] = 0;
+    if (n_reads == 0) return UMI_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx);
+    const size_t n = (size_t)n_reads, bytes = n * (size_t)bc_len;
+    if ((rc = ctx->bc_in.reserve(bytes)) || (rc = ctx->bc_qual.reserve(bytes)) || (rc = ctx->bc_match.reserve(n * 4)) ||
+        (status && (rc = ctx->bc_status.reserve(n))) || (exact_reads && (rc = ctx->bc_exact.reserve((size_t)n_wl * 4))))
+        return rc;
+    hipStream_t s = ctx->own_stream;
+    HIP_TRY(hipMemcpyAsync(ctx->bc_in.p, bc_ascii, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ctx->bc_qual.p, bc_qual, bytes, hipMemcpyHostToDevice, s));
+    rc = bc_run(ctx, ctx->bc_in.as<uint8_t>(), n_reads, bc_len, packed, n_wl, 1, ctx->bc_match.as<int32_t>(),
+                status ? ctx->bc_status.as<uint8_t>() : nullptr, counts, s, ctx->bc_qual.as<uint8_t>(), min_posterior_permille,
+                pseudocount, exact_reads ? ctx->bc_exact.as<uint32_t>() : nullptr);
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(match, ctx->bc_match.p, n * 4, hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(hipMemcpyAsync(status, ctx->bc_status.p, n, hipMemcpyDeviceToHost, s));
+    if (exact_reads) HIP_TRY(hipMemcpyAsync(exact_reads, ctx->bc_exact.p, (size_t)n_wl * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return UMI_OK;
 }

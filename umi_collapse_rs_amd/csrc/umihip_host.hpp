@@ -255,7 +255,8 @@ struct umi_ctx {
     // correction of UMIs to a fixed list (umi_correct_umis*): workspace; the host-buffer form's arrays
     umihip::DevBuf corr_ws, corr_umi, corr_out, corr_match, corr_best, corr_second;
     // correction of cell barcodes (umi_correct_barcodes*): packed list and index; the host-buffer form's arrays
-    umihip::DevBuf bc_ws, bc_in, bc_match, bc_status;
+    // (bc_qual, bc_exact: umi_correct_barcodes_multi's qualities and exact reads per listed barcode)
+    umihip::DevBuf bc_ws, bc_in, bc_match, bc_status, bc_qual, bc_exact;
     // molecules per (column, row) pair (umi_count_matrix*): workspace; the host-buffer form's arrays in one block;
     // pinned staging of the non-empty buckets' offsets and numbers
     umihip::DevBuf cm_ws, cm_io;

@@ -448,6 +448,16 @@ size_t barcode_workspace_bytes(uint32_t n_wl);
 int barcode_on_device(void *workspace, const uint8_t *d_bc, uint32_t n_reads, int bc_len, const uint64_t *h_packed, uint32_t n_wl,
                       int max_mismatches, int32_t *d_match, uint8_t *d_status, uint64_t counts[4], uint64_t *bad, uint32_t n_cus,
                       unsigned long long *h_pinned, hipStream_t s);
+// umi_correct_barcodes_multi: the same with the qualities beside the barcodes (d_qual given: max_mismatches is 1),
+// the exact reads per listed barcode (d_exact_reads may be null) and the ambiguous reads weighed in a second
+// pass; the workspace holds barcode_multi_workspace_bytes, counts has 5 words and h_pinned 10.  Also 3: a
+// quality byte outside 33..126 (*bad: the smallest such read, and no read up to it has a bad barcode byte).
+// Without d_qual it is barcode_on_device.
+size_t barcode_multi_workspace_bytes(uint32_t n_wl, uint32_t n_reads);
+int barcode_multi_on_device(void *workspace, const uint8_t *d_bc, const uint8_t *d_qual, uint32_t n_reads, int bc_len,
+                            const uint64_t *h_packed, uint32_t n_wl, int max_mismatches, uint32_t permille, uint32_t pseudocount,
+                            int32_t *d_match, uint8_t *d_status, uint32_t *d_exact_reads, uint64_t *counts, uint64_t *bad,
+                            uint32_t n_cus, unsigned long long *h_pinned, hipStream_t s);
 
 // ---- molecules and reads per (column, row) pair (umihip_count.hip: umi_count_matrix) ----
 // h_off (pinned): the m + 1 offsets of the m >= 1 non-empty buckets; h_idx (pinned, null: nothing was left out):

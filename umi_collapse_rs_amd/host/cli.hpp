@@ -31,6 +31,15 @@
 // the GPU is woken.  Refused likewise, each with a message of its own: fastq mode, --two-pass (its windows never hold
 // the file's UMI usage), --dump-staging, --passthrough, --output-stats-seed without --output-stats or not a whole
 // number in 0..2^64-1.  The output BAM and the summary lines are as without the flag.
+// --cell-whitelist-multi [--cell-quality-tag XX] [--cell-whitelist-min-posterior P] [--cell-whitelist-pseudocount N]
+// (with --cell-whitelist; after STARsolo's 1MM_multi[_pseudocounts] and Cell Ranger, tests/barcode_multi_model.py
+// defines it): a barcode one substitution from two or more listed ones is not dropped but weighed -- every
+// candidate by the reads that carry it exactly and by the base quality at the mismatched position, from the tag XX
+// [default: CY] -- and the heaviest is taken where it holds P of the weight [default: 0.975]; N [default: 0, 0..1000]
+// is added to every candidate's reads.  P is read from its text as per-mille and never as a float: 0 or 1, or 0. / 1.
+// and at most three decimals, 0..1.  Refused with status 101 before the GPU is woken, each with a message of its own:
+// any of the four flags without --cell-whitelist, a companion flag without --cell-whitelist-multi,
+// --cell-whitelist-max-mismatches 0 with it, a tag name that is not two characters, a malformed P or N.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -83,6 +92,11 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     std::string cell_whitelist_metrics; // --cell-whitelist-metrics FILE: reads, exact, corrected per listed barcode
     int cell_wl_max_mismatches = 1;     // --cell-whitelist-max-mismatches: 0 or 1
     bool cell_wl_max_given = false;
+    bool cell_wl_multi = false;         // --cell-whitelist-multi: ambiguous barcodes are decided by posterior
+    std::string cell_qual_tag = "CY";   // --cell-quality-tag XX: the barcode's base qualities
+    int cell_wl_min_posterior = 975;    // --cell-whitelist-min-posterior P, per-mille
+    int cell_wl_pseudocount = 0;        // --cell-whitelist-pseudocount N
+    bool cell_qual_tag_given = false, cell_wl_min_posterior_given = false, cell_wl_pseudocount_given = false;
     bool wl_max_given = false, wl_min_given = false;
     bool per_gene = false, gene_tag_given = false; // --per-gene: a bucket is a gene, with --per-cell a (cell, gene) pair
     std::string gene_tag = "GX";                   // --gene-tag XX: the gene's tag
@@ -168,7 +182,14 @@ void usage()
               "                           barcode are dropped; written records keep their own bytes (bam/sam mode, one pass)\n"
               "      --cell-whitelist-max-mismatches <M> 0: listed barcodes only; 1: one substitution allowed [default: 1]\n"
               "      --cell-whitelist-metrics <FILE> write a table: barcode, reads, exact, corrected per listed barcode\n"
-              "                           that took a read, in list order\n"
+              "                           that took a read, in list order (with --cell-whitelist-multi also: resolved)\n"
+              "      --cell-whitelist-multi with --cell-whitelist: a barcode one substitution from two or more listed ones\n"
+              "                           is weighed, not dropped: every candidate by its exact reads and by the base\n"
+              "                           quality at the mismatched position; the heaviest is taken where it holds the\n"
+              "                           minimum posterior (STARsolo 1MM_multi, Cell Ranger)\n"
+              "      --cell-quality-tag <XX> aux tag of the barcode's qualities, type Z, Phred + 33 [default: CY]\n"
+              "      --cell-whitelist-min-posterior <P> 0..1, at most three decimals [default: 0.975]\n"
+              "      --cell-whitelist-pseudocount <N> added to every candidate's exact reads, 0..1000 [default: 0]\n"
               "      --per-gene           deduplicate per gene: reads are grouped by gene (with --per-cell by cell and\n"
               "                           gene) and not by alignment position, so a molecule fragmented at two places\n"
               "                           is kept once; reads without a gene, or assigned to several, are dropped\n"
@@ -280,6 +301,34 @@ Cli parse(int argc, char **argv)
             if (v != "0" && v != "1") die(a + " wants 0 or 1: '" + v + "'");
             c.cell_wl_max_mismatches = v == "1";
             c.cell_wl_max_given = true;
+        }
+        else if (a == "--cell-whitelist-multi") c.cell_wl_multi = true;
+        else if (a == "--cell-quality-tag") {
+            const std::string t = need(i);
+            auto alpha = [](char ch) { return (ch >= 'A' && ch <= 'Z') || (ch >= 'a' && ch <= 'z'); };
+            if (t.size() != 2 || !alpha(t[0]) || !(alpha(t[1]) || (t[1] >= '0' && t[1] <= '9')))
+                die(a + " wants a tag name of two characters, [A-Za-z][A-Za-z0-9]: '" + t + "'");
+            c.cell_qual_tag = t;
+            c.cell_qual_tag_given = true;
+        }
+        else if (a == "--cell-whitelist-min-posterior") { // per-mille from the text: [01] or [01].d{1,3}, at most 1
+            const std::string v = need(i);
+            bool ok = !v.empty() && (v[0] == '0' || v[0] == '1') && (v.size() == 1 || (v[1] == '.' && v.size() >= 3 && v.size() <= 5));
+            int pm = ok ? (v[0] - '0') * 1000 : 0;
+            for (size_t d = 2, unit = 100; ok && d < v.size(); d++, unit /= 10) {
+                ok = v[d] >= '0' && v[d] <= '9';
+                pm += (v[d] - '0') * (int)unit;
+            }
+            if (!ok || pm > 1000) die(a + " wants a number in 0..1 with at most three decimals: '" + v + "'");
+            c.cell_wl_min_posterior = pm;
+            c.cell_wl_min_posterior_given = true;
+        }
+        else if (a == "--cell-whitelist-pseudocount") {
+            const std::string v = need(i);
+            const bool digits = !v.empty() && v.size() <= 4 && v.find_first_not_of("0123456789") == std::string::npos;
+            if (!digits || std::atoi(v.c_str()) > 1000) die(a + " wants a whole number in 0..1000: '" + v + "'");
+            c.cell_wl_pseudocount = std::atoi(v.c_str());
+            c.cell_wl_pseudocount_given = true;
         }
         else if (a == "--consensus") c.consensus = true;
         else if (a == "--consensus-min-reads") {
@@ -433,6 +482,14 @@ bool validate(Cli &args)
     // --cell-whitelist: likewise
     if (args.cell_whitelist.empty() && (args.cell_wl_max_given || !args.cell_whitelist_metrics.empty()))
         die("--cell-whitelist-max-mismatches and --cell-whitelist-metrics go with --cell-whitelist only");
+    const bool multi_companion = args.cell_qual_tag_given || args.cell_wl_min_posterior_given || args.cell_wl_pseudocount_given;
+    if (args.cell_whitelist.empty() && (args.cell_wl_multi || multi_companion))
+        die("--cell-whitelist-multi, --cell-quality-tag, --cell-whitelist-min-posterior and --cell-whitelist-pseudocount go with "
+            "--cell-whitelist only");
+    if (multi_companion && !args.cell_wl_multi)
+        die("--cell-quality-tag, --cell-whitelist-min-posterior and --cell-whitelist-pseudocount go with --cell-whitelist-multi only");
+    if (args.cell_wl_multi && args.cell_wl_max_mismatches == 0)
+        die("--cell-whitelist-multi does not go with --cell-whitelist-max-mismatches 0 (nothing is ambiguous then)");
     if (!args.cell_whitelist.empty()) {
         if (args.mode == "fastq") die("--cell-whitelist does not go with fastq mode (there are no tags there)");
         if (!args.per_cell) die("--cell-whitelist goes with --per-cell only");

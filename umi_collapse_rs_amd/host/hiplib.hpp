@@ -17,6 +17,8 @@
 // when the flag is given, so that a library without it serves every other run.
 //
 // --output-stats PREFIX: likewise umi_dedup_stats.
+//
+// --cell-whitelist-multi: likewise umi_correct_barcodes_multi, in umi_correct_barcodes' place.
 #pragma once
 #include <chrono>
 #include <dlfcn.h>
@@ -76,6 +78,9 @@ struct HipLib {
     // --cell-whitelist: likewise
     bool want_barcodes = false;
     decltype(&umi_correct_barcodes) correct_barcodes = nullptr;
+    // --cell-whitelist-multi: likewise, in its place
+    bool want_barcodes_multi = false;
+    decltype(&umi_correct_barcodes_multi) correct_barcodes_multi = nullptr;
     // --count-matrix: likewise
     bool want_count = false;
     decltype(&umi_count_matrix) count_matrix = nullptr;
@@ -89,7 +94,8 @@ struct HipLib {
     std::string error;
     explicit HipLib(const Cli &args)
         : want_edit(args.edit_distance), want_consensus(args.consensus), want_consensus_bam(args.call_consensus),
-          want_correct(!args.whitelist.empty()), want_barcodes(!args.cell_list.empty()),
+          want_correct(!args.whitelist.empty()), want_barcodes(!args.cell_list.empty() && !args.cell_wl_multi),
+          want_barcodes_multi(!args.cell_list.empty() && args.cell_wl_multi),
           want_count(!args.count_matrix.empty()), want_stats(!args.output_stats.empty())
     {
     }
@@ -130,6 +136,7 @@ struct HipLib {
         if (want_consensus_bam) consensus_bam = (decltype(consensus_bam))sym("umi_consensus_bam");
         if (want_correct) correct_umis = (decltype(correct_umis))sym("umi_correct_umis");
         if (want_barcodes) correct_barcodes = (decltype(correct_barcodes))sym("umi_correct_barcodes");
+        if (want_barcodes_multi) correct_barcodes_multi = (decltype(correct_barcodes_multi))sym("umi_correct_barcodes_multi");
         if (want_count) count_matrix = (decltype(count_matrix))sym("umi_count_matrix");
         if (want_stats) dedup_stats = (decltype(dedup_stats))sym("umi_dedup_stats");
         hip_set_device = (decltype(hip_set_device))sym("hipSetDevice");

@@ -29,6 +29,12 @@
 // order, the merge rule and what is written are as ever.  The summary gains the two lines, "Number of genes"
 // and "Number of (cell, gene) groups" ("Number of gene groups" without --per-cell) and loses "Number of unique
 // alignment positions"; --dump-staging appends every bucket's gene id behind the cell ids.
+//
+// --cell-whitelist-multi (cli.hpp has the flags, umicollapse_main.cpp the call): a read with the cell barcode tag
+// must carry --cell-quality-tag (default CY, type Z) as well -- a read with the one and without the other ends the
+// run with status 101, as a tag of another type does; its length and bytes (33..126) are looked at where the
+// barcode's are.  The summary gains "Number of reads with a resolved cell barcode" after the corrected ones, and
+// write_list_metrics the column `resolved`.
 #pragma once
 #include <string_view>
 #include <unordered_map>
@@ -191,6 +197,7 @@ struct ReadTags {
     const uint8_t *umi = nullptr; // --umi-tag: the value
     size_t umi_len = 0;
     std::string_view cell;        // --per-cell: the barcode, an opaque byte string
+    std::string_view cell_qual;   // --cell-whitelist-multi: its qualities (--cell-quality-tag)
     std::string_view gene;        // --per-gene: the gene, likewise
     bool several_genes = false;   // ... its value lists more than one (';' or ','): the read is dropped
 };
@@ -219,6 +226,13 @@ uint8_t read_tags(const Cli &args, const umi::bam::Record &r, ReadTags &t, std::
         if (look(args.cell_tag, f)) t.cell = std::string_view((const char *)f.value, f.len);
         else miss |= MISS_CELL;
         if (!err.empty()) return 0;
+        if (args.cell_wl_multi && !(miss & MISS_CELL)) { // a read with a barcode carries its qualities
+            if (look(args.cell_qual_tag, f)) t.cell_qual = std::string_view((const char *)f.value, f.len);
+            else if (err.empty())
+                err = "read " + std::string((const char *)r.qname(), r.qname_len()) + " has the cell barcode tag " + args.cell_tag +
+                      " without the quality tag " + args.cell_qual_tag;
+            if (!err.empty()) return 0;
+        }
     }
     if (args.per_gene) {
         std::string_view g;
@@ -320,22 +334,28 @@ void emit_position(std::vector<Entry> &entries, std::vector<uint32_t> &members, 
 }
 
 // --whitelist-metrics / --cell-whitelist-metrics: per listed item, in list order, the reads it took, exact and
-// corrected (status 0: exact); `used_only` leaves out the items that took none
+// corrected (status 0: exact); `used_only` leaves out the items that took none.  `with_resolved`
+// (--cell-whitelist-multi): a fifth column, the reads of status UMI_BARCODE_RESOLVED, counted among `reads` too
 void write_list_metrics(const std::string &path, const char *item, const std::vector<uint8_t> &list, size_t L,
-                        const std::vector<int32_t> &match, const std::vector<uint8_t> &status, bool used_only)
+                        const std::vector<int32_t> &match, const std::vector<uint8_t> &status, bool used_only,
+                        bool with_resolved = false)
 {
     const size_t n_wl = list.size() / L;
-    std::vector<uint64_t> exact(n_wl, 0), corrected(n_wl, 0);
+    std::vector<uint64_t> exact(n_wl, 0), corrected(n_wl, 0), resolved(n_wl, 0);
     for (size_t j = 0; j < match.size(); j++)
-        if (match[j] >= 0) (status[j] == 0 ? exact : corrected)[(size_t)match[j]]++;
+        if (match[j] >= 0)
+            (status[j] == 0 ? exact : with_resolved && status[j] == UMI_BARCODE_RESOLVED ? resolved : corrected)[(size_t)match[j]]++;
     FILE *f = std::fopen(path.c_str(), "wb");
     if (!f) die("cannot open " + path);
-    std::fprintf(f, "%s\treads\texact\tcorrected\n", item);
+    std::fprintf(f, with_resolved ? "%s\treads\texact\tcorrected\tresolved\n" : "%s\treads\texact\tcorrected\n", item);
     for (size_t w = 0; w < n_wl; w++)
-        if (!used_only || exact[w] + corrected[w])
-            std::fprintf(f, "%.*s\t%llu\t%llu\t%llu\n", (int)L, (const char *)&list[w * L],
-                         (unsigned long long)(exact[w] + corrected[w]), (unsigned long long)exact[w],
+        if (!used_only || exact[w] + corrected[w] + resolved[w]) {
+            std::fprintf(f, "%.*s\t%llu\t%llu\t%llu", (int)L, (const char *)&list[w * L],
+                         (unsigned long long)(exact[w] + corrected[w] + resolved[w]), (unsigned long long)exact[w],
                          (unsigned long long)corrected[w]);
+            if (with_resolved) std::fprintf(f, "\t%llu", (unsigned long long)resolved[w]);
+            std::fputc('\n', f);
+        }
     if (std::fclose(f) != 0) die("cannot write " + path);
 }
 
@@ -344,7 +364,7 @@ void write_list_metrics(const std::string &path, const char *item, const std::ve
 struct Summary {
     size_t total_read_count = 0, unmapped = 0, unpaired = 0, chimeric = 0, no_umi_tag = 0, no_cell = 0;
     size_t no_gene = 0, several_genes = 0, n_genes = 0; // --per-gene
-    uint64_t cb_counts[4] = {0, 0, 0, 0}; // --cell-whitelist: exact, corrected, unlisted, ambiguous
+    uint64_t cb_counts[5] = {0, 0, 0, 0, 0}; // --cell-whitelist: exact, corrected, unlisted, ambiguous, (-multi) resolved
     uint64_t wl_counts[3] = {0, 0, 0};    // --umi-whitelist: exact, corrected, uncorrectable
     size_t n_positions = 0, nb = 0, n = 0, max_umi = 0;
     uint64_t n_kept = 0;
@@ -367,6 +387,8 @@ struct Summary {
         }
         if (!args.cell_list.empty()) {
             std::fprintf(stderr, "Number of reads with a corrected cell barcode: %llu\n", (unsigned long long)cb_counts[1]);
+            if (args.cell_wl_multi)
+                std::fprintf(stderr, "Number of reads with a resolved cell barcode: %llu\n", (unsigned long long)cb_counts[4]);
             std::fprintf(stderr, "Number of reads with an unlisted cell barcode: %llu\n", (unsigned long long)cb_counts[2]);
             std::fprintf(stderr, "Number of reads with an ambiguous cell barcode: %llu\n", (unsigned long long)cb_counts[3]);
         }

@@ -38,6 +38,14 @@
 // --passthrough, the two other flags alone, a mismatch bound other than 0 or 1, a list that is empty, of mixed
 // lengths, with a byte outside ACGT (Cell Ranger's "-1" suffix included), with a duplicate, or of more than 32
 // bases.
+// --cell-whitelist-multi (with --cell-whitelist; after STARsolo's 1MM_multi and Cell Ranger, tests/
+// barcode_multi_model.py defines it; cli.hpp has the flags): the one call is umi_correct_barcodes_multi, which
+// also takes the barcodes' qualities -- the value of --cell-quality-tag (CY), gathered beside the barcode; every
+// read with a barcode must carry it, type Z, of the barcode's length, bytes 33..126, else the run ends with status
+// 101 -- and decides a barcode with several listed neighbours by their exact reads and the quality at the
+// mismatch.  Resolved reads are numbered and grouped like corrected ones; the summary gains "Number of reads with
+// a resolved cell barcode", "... an ambiguous cell barcode" counts what stayed ambiguous, and the metrics table
+// gains the column `resolved`.  Without the flag every output and summary line is as before.
 // --call-consensus (bam/sam mode, one pass; not the reference's, tests/bam_consensus_model.py defines it): the
 // same records in the same order, but of each kept record the sequence and the qualities are its cluster's
 // consensus.  A cluster is a kept entry with every entry it removed, as for --tag; its voters are its reads
@@ -148,6 +156,7 @@ struct OnePass {
     std::vector<int64_t> c_min, c_max; // coordinates and (ref, strand) codes seen, per thread
     std::vector<uint64_t> rs_max;
     umi::bgzf::Bytes cell_raw; // --cell-whitelist: per record, a staged read's barcode as the tag has it
+    umi::bgzf::Bytes cell_qual; // --cell-whitelist-multi: ... and its qualities
     std::vector<std::vector<std::string_view>> cell_seen; // --per-cell: per thread, its barcodes in order of appearance
     U64s gkey; // GPU staging with --per-cell: every read's cell id, the group key
     size_t n_cells = 0;
@@ -320,6 +329,7 @@ struct OnePass {
         std::vector<std::string> errors(T);
         std::vector<uint32_t> first_error(T, UINT32_MAX);
         if (!args.cell_list.empty()) cell_raw.resize((size_t)n_rec * args.cell_len);
+        if (args.cell_wl_multi) cell_qual.resize((size_t)n_rec * args.cell_len);
         // --per-cell: every thread numbers the barcodes of its reads in order of appearance; the numbers are
         // made global (first appearance in the file) below.  A few thousand to 10^5 barcodes: the tables stay
         // in cache.
@@ -384,6 +394,23 @@ struct OnePass {
                         continue;
                     }
                     std::memcpy(&cell_raw[(size_t)ri * args.cell_len], tg.cell.data(), args.cell_len);
+                    if (args.cell_wl_multi) { // the qualities beside it: of the barcode's length, bytes 33..126
+                        bool phred = tg.cell_qual.size() == args.cell_len;
+                        for (const char ch : tg.cell_qual) phred = phred && (uint8_t)ch >= 33 && (uint8_t)ch <= 126;
+                        if (!phred) {
+                            ii.state = 2;
+                            if (first_error[t] == UINT32_MAX) {
+                                first_error[t] = ri;
+                                const std::string name((const char *)r.qname(), r.qname_len());
+                                errors[t] = tg.cell_qual.size() != args.cell_len
+                                                ? "cell quality tag " + args.cell_qual_tag + " of read " + name + " holds " +
+                                                      std::to_string(tg.cell_qual.size()) + " bytes, not " + std::to_string(args.cell_len)
+                                                : "Unknown character in cell quality tag " + args.cell_qual_tag + " of read " + name;
+                            }
+                            continue;
+                        }
+                        std::memcpy(&cell_qual[(size_t)ri * args.cell_len], tg.cell_qual.data(), args.cell_len);
+                    }
                 } else if (args.per_cell) {
                     const auto id = cell_ids[t].emplace(tg.cell, (uint32_t)cell_seen[t].size());
                     if (id.second) cell_seen[t].push_back(tg.cell);
@@ -426,7 +453,14 @@ struct OnePass {
         const umi::bgzf::Bytes raw = gather(cand, L, [&](uint32_t ri) { return &cell_raw[(size_t)ri * L]; });
         std::vector<int32_t> cb_match(nc);
         std::vector<uint8_t> cb_status(nc);
-        if (nc) {
+        if (nc && args.cell_wl_multi) { // ambiguous barcodes weighed by their candidates' exact reads and the qualities
+            const umi::bgzf::Bytes qual = gather(cand, L, [&](uint32_t ri) { return &cell_qual[(size_t)ri * L]; });
+            need_ctx();
+            if (lib.correct_barcodes_multi(ctx, raw.data(), qual.data(), nc, (int)L, args.cell_list.data(), (uint32_t)n_wl,
+                                           args.cell_wl_min_posterior, args.cell_wl_pseudocount, cb_match.data(), cb_status.data(),
+                                           nullptr, sum.cb_counts) != UMI_OK)
+                die(lib.last_error());
+        } else if (nc) {
             need_ctx();
             if (lib.correct_barcodes(ctx, raw.data(), nc, (int)L, args.cell_list.data(), (uint32_t)n_wl, args.cell_wl_max_mismatches,
                                      cb_match.data(), cb_status.data(), sum.cb_counts) != UMI_OK)
@@ -450,7 +484,7 @@ struct OnePass {
         }
         n_cells = next_id;
         if (!args.cell_whitelist_metrics.empty()) // per listed barcode that took a read, in list order
-            write_list_metrics(args.cell_whitelist_metrics, "barcode", args.cell_list, L, cb_match, cb_status, true);
+            write_list_metrics(args.cell_whitelist_metrics, "barcode", args.cell_list, L, cb_match, cb_status, true, args.cell_wl_multi);
         lap("cell whitelist");
     }
 
