@@ -128,6 +128,17 @@ const char *umi_last_error(void);
  *                    sub-bucket instead of being compared one by one (0: the tile walk); same result and
  *                    statistics
  *   "seg_probe_min"  2..2048 (default 129): smallest sub-bucket decided by lookups
+ *   "seg_super"      0/1 (default 1): k = 1 without N, on the calls "seg_local" applies to (whatever its value): a run
+ *                    of 4^g adjacent part-0 sub-buckets -- they share all but g bases of their bin code and lie back
+ *                    to back -- is decided as one unit out of LDS by a multi-wave block, so that the pairs that differ
+ *                    in one of those g bases are united there instead of by the pair kernel's global unions (0: the
+ *                    sub-buckets one by one); same result and statistics
+ *   "seg_super_bases" 0..4 (default 0): g; 0 = the largest for which the other bases number at most 8 and the expected
+ *                    run n / 4^(bin bases - g) lies between "seg_super_min" and 3/4 of "seg_super_cap", another
+ *                    value = that g where those conditions hold (else none)
+ *   "seg_super_cap"  2..8192 (default 5632): largest run that kernel takes (LDS: 16 bytes per entry + 16 KB); a larger
+ *                    one goes through the pair kernel whole
+ *   "seg_super_min"  2..8192 (default 1024): smallest expected run the path is planned for
  *   "collapse_kept_only" 0/1 (default 1): a batched directional call without d_root leaves the union-find
  *                    forest unflattened: only the endpoints of the one-way pairs are followed to their
  *                    roots, and the mask is read off parent[] and lab[] (0: flatten as a call with d_root does)

@@ -381,11 +381,20 @@ class Pipeline {
         // bit-sliced tiles keep an overflow list of their own, which that mode's one collapse path does not read)
         const bool dev_tiles = mode != MODE_CLUSTER;
         const bool seg_on = ctx->seg_index && need_pairs && !(ctx->prune && dev_tiles) && !edit;
+        // super-bins of part 0: a call whose part-0 sub-buckets may be united in LDS (as the one-wave local kernel's:
+        // unions on the spot, one device's whole call, 32-bit compare keys), k = 1 (the planner looks), no N mask.
+        // Nothing of "seg_local", "seg_probe" or their sizes in here: no count may move with those
+        SegSuperOpt sup;
+        sup.on = ctx->seg_super && ctx->seg_unite && ctx->seg_ckey && unions_collapse() && n_parts == 1 && ctx->two_phase == 2 &&
+                 key32 && !wide() && !edit && !d_nmask;
+        sup.bases = ctx->seg_super_bases;
+        sup.cap = ctx->seg_super_cap;
+        sup.min = ctx->seg_super_min;
         build_plan(bucket_off, n_buckets, wide() || edit ? 0x7FFFFFFFu : ctx->small_max,
                    ctx->use_bitslice && k <= BS_MAX_K && !wide() && !edit && dev_tiles,
                    plan_umi_len(), fused_max, ctx->prune && dev_tiles, ctx->bs_sorted && ctx->bs_unit == 2 && need_pairs && dev_tiles,
                    ctx->bs_tables && key32 && dev_tiles, ctx->bs_tab_min_run, seg_on ? std::max(ctx->seg_min, 1u) : 0u, k, key32, pl,
-                   &ctx->table_pass);
+                   &ctx->table_pass, sup);
         prune = ctx->prune && dev_tiles && need_pairs && !pl.bs_buckets.empty() && !wide() && !edit;
         keep_my_share(pl.small_tasks);
         keep_my_share(pl.big_tasks);
@@ -414,6 +423,7 @@ class Pipeline {
         const size_t o_segs = place(pl.segs.size() * sizeof(SegDesc));
         const size_t o_chunks = place(pl.seg_chunks.size() * sizeof(SegScanChunk));
         const size_t o_blocks = place(pl.seg_blocks.size() * sizeof(SegBlock));
+        const size_t o_supers = place(pl.seg_supers.size() * sizeof(SegSuper));
         const size_t o_small = place(pl.small_tasks.size() * sizeof(PairTask));
         const size_t o_big = place(pl.big_tasks.size() * sizeof(PairTask));
         const size_t total = std::max<size_t>(off, 64);
@@ -426,6 +436,7 @@ class Pipeline {
             (rc = hp.put(o_segs, pl.segs.data(), pl.segs.size() * sizeof(SegDesc))) ||
             (rc = hp.put(o_chunks, pl.seg_chunks.data(), pl.seg_chunks.size() * sizeof(SegScanChunk))) ||
             (rc = hp.put(o_blocks, pl.seg_blocks.data(), pl.seg_blocks.size() * sizeof(SegBlock))) ||
+            (rc = hp.put(o_supers, pl.seg_supers.data(), pl.seg_supers.size() * sizeof(SegSuper))) ||
             (rc = hp.put(o_small, pl.small_tasks.data(), pl.small_tasks.size() * sizeof(PairTask))) ||
             (rc = hp.put(o_big, pl.big_tasks.data(), pl.big_tasks.size() * sizeof(PairTask))))
             return rc;
@@ -481,12 +492,22 @@ class Pipeline {
             seg.full_umi_len = umi_len;
             seg.use_ckey = key32 && ctx->seg_ckey && pl.seg_max_rest <= 10 ? 1u : 0u;
             seg.col_sliced = ctx->seg_sliced ? 1u : 0u;
+            // super-bins (the planner has set SegDesc::sup_g where the call's shape allows): the same kind of call as
+            // the local kernel's below, whatever "seg_local" says
+            const bool super_on = !pl.seg_supers.empty() && ctx->seg_unite && unions_collapse() && one_sync() && seg.use_ckey &&
+                                  k == 1 && !d_nmask;
+            if (super_on) {
+                seg.super_cap = ctx->seg_super_cap;
+                seg.supers = (const SegSuper *)(d + o_supers);
+                seg.n_supers = (uint32_t)pl.seg_supers.size();
+            }
             // part 0 in LDS: where the pair kernel would unite symmetric pairs on the spot (the batched
             // directional path, one device's whole call) and compares 32-bit compare keys
             if (ctx->seg_local && ctx->seg_unite && unions_collapse() && one_sync() && seg.use_ckey) {
                 seg.local_cap = ctx->seg_local_cap;
                 seg_local_bins = 0;
                 for (const SegDesc &sd : pl.segs) seg_local_bins += 1ull << (2 * sd.nb[0]);
+                if (super_on && pl.seg_plain == 0) seg_local_bins = 0; // (every segment has super-bins: nothing for it)
                 // k = 1 without N: inside a bin every pair within k differs in one base outside the bin's own,
                 // and no two entries agree there (with N folded onto A they could)
                 if (ctx->seg_probe && k == 1 && !d_nmask) {
@@ -810,10 +831,13 @@ class Pipeline {
                 pl.seg_task_cap, ctx->seg_blocks ? ctx->seg_blocks : (uint64_t)ctx->n_cus * std::min(16u, seg_occupancy())));
             // the local kernel's blocks (resident all at once, no more than there are part-0 bins) take
             // the first private slots, the pair kernel's the ones behind them
-            const uint32_t local_blocks = seg.local_cap ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(
+            const uint32_t local_blocks = seg.local_cap && seg_local_bins ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(
                                                               seg_local_bins, (uint64_t)ctx->n_cus * seg_local_occupancy()))
                                                         : 0u;
-            const size_t slots = (size_t)local_blocks + blocks;
+            // ... and the super-bin kernel's waves the ones in between
+            const uint32_t super_blocks = seg.super_cap ? seg_super_blocks(seg.n_supers, (uint32_t)ctx->n_cus) : 0u;
+            const uint32_t super_slots = super_blocks * (seg_super_threads(seg.super_cap) / 64u);
+            const size_t slots = (size_t)local_blocks + super_slots + blocks;
             int rc;
             if ((rc = ctx->seg_priv_edges.reserve(slots * SEG_PRIV_CAP * sizeof(uint2))) ||
                 (rc = ctx->seg_priv_cnt.reserve(slots * 4)) || (rc = ctx->seg_priv_stat.reserve(slots * sizeof(uint2))) ||
@@ -826,16 +850,21 @@ class Pipeline {
             // the slots go to the collapse's flatten launch, which adds up the blocks' counts as well
             const bool slots_to_collapse = seg.uf_parent && unions_collapse();
             seg.priv_stat = slots_to_collapse ? ctx->seg_priv_stat.as<uint2>() : nullptr;
-            if (seg.local_cap && !seg.uf_parent) // (the scan has left the local bins without tasks)
+            if ((seg.local_cap || seg.super_cap) && !seg.uf_parent) // (the scan has left the local bins without tasks)
                 return fail(UMI_ERR_HIP, "internal: part-0 sub-buckets planned for the local kernel without unions");
-            SegArgs pair_seg = seg;
-            pair_seg.priv_edges += (size_t)local_blocks * SEG_PRIV_CAP;
-            pair_seg.priv_cnt += local_blocks;
-            if (pair_seg.priv_stat) pair_seg.priv_stat += local_blocks;
+            SegArgs super_seg = seg;
+            super_seg.priv_edges += (size_t)local_blocks * SEG_PRIV_CAP;
+            super_seg.priv_cnt += local_blocks;
+            if (super_seg.priv_stat) super_seg.priv_stat += local_blocks;
+            SegArgs pair_seg = super_seg;
+            pair_seg.priv_edges += (size_t)super_slots * SEG_PRIV_CAP;
+            pair_seg.priv_cnt += super_slots;
+            if (pair_seg.priv_stat) pair_seg.priv_stat += super_slots;
 
             if (prof) HIP_TRY(hipEventRecord(ctx->ev[7], s));
             // (part 0's plain label stores all land before the pair kernel's first union: stream order)
             if (local_blocks) HIP_TRY(launch_seg_local(a, seg, percentage, local_blocks, s));
+            if (super_blocks) HIP_TRY(launch_seg_super(a, super_seg, percentage, super_blocks, s));
             HIP_TRY(launch_seg_pairs(a, pair_seg, key32, percentage, part, n_parts, blocks, s));
             if (prof) HIP_TRY(hipEventRecord(ctx->ev[8], s));
             seg_timed = true;
@@ -1550,6 +1579,18 @@ int umi_ctx_set_option(umi_ctx *ctx, const char *name, int64_t value)
     } else if (!strcmp(name, "seg_probe_min")) {
         if (value < 2 || value > SEG_LOCAL_MAX_CAP) return fail(UMI_ERR_ARG, "seg_probe_min must be in 2..%u", SEG_LOCAL_MAX_CAP);
         ctx->seg_probe_min = (uint32_t)value;
+    } else if (!strcmp(name, "seg_super")) {
+        if (value != 0 && value != 1) return fail(UMI_ERR_ARG, "seg_super must be 0 or 1");
+        ctx->seg_super = value != 0;
+    } else if (!strcmp(name, "seg_super_bases")) {
+        if (value < 0 || value > SEG_SUPER_MAX_BASES) return fail(UMI_ERR_ARG, "seg_super_bases must be in 0..%d", SEG_SUPER_MAX_BASES);
+        ctx->seg_super_bases = (int)value;
+    } else if (!strcmp(name, "seg_super_cap")) {
+        if (value < 2 || value > SEG_SUPER_MAX_CAP) return fail(UMI_ERR_ARG, "seg_super_cap must be in 2..%u", SEG_SUPER_MAX_CAP);
+        ctx->seg_super_cap = (uint32_t)value;
+    } else if (!strcmp(name, "seg_super_min")) {
+        if (value < 2 || value > SEG_SUPER_MAX_CAP) return fail(UMI_ERR_ARG, "seg_super_min must be in 2..%u", SEG_SUPER_MAX_CAP);
+        ctx->seg_super_min = (uint32_t)value;
     } else if (!strcmp(name, "collapse_kept_only")) {
         ctx->collapse_kept_only = value != 0;
     } else if (!strcmp(name, "seg_local_cap")) {

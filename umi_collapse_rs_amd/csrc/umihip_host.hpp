@@ -221,6 +221,10 @@ struct umi_ctx {
     bool seg_probe = true;   // ... k = 1 without N: their pairs decided by bitmap lookups where at most
                              // SEG_PROBE_MAX_REST bases lie outside the bins (0: the tile walk)
     uint32_t seg_probe_min = umihip::SEG_PROBE_MIN; // smallest sub-bucket decided by lookups
+    bool seg_super = true;   // k = 1 without N: runs of 4^g adjacent part-0 bins decided as one unit in LDS (seg_super_kernel)
+    int seg_super_bases = 0; // ... g (0: the planner's choice, choose_super_bases)
+    uint32_t seg_super_cap = umihip::SEG_SUPER_CAP; // largest super-bin that kernel takes (LDS: 16 bytes per entry + 16 KB)
+    uint32_t seg_super_min = umihip::SEG_SUPER_MIN; // smallest expected super-bin the path is planned for
     int seg_local_occ[2] = {0, 0}; // its resident blocks per CU (without / with N) at seg_local_occ_cap
     uint32_t seg_local_occ_cap = 0;
     bool collapse_kept_only = true; // a batched directional call without root[] skips the forest flatten (umihip_collapse.hip)

@@ -88,6 +88,16 @@ struct SegDesc {
     uint8_t nb[SEG_MAX_PARTS];       // leading bases of part j that index its bins (4^nb bins)
     uint64_t mask[SEG_MAX_PARTS];    // filter-key bits those bases occupy: two entries share the bin of
                                      // part j iff (key_a ^ key_b) & mask[j] == 0
+    uint8_t sup_g;                   // super-bin exponent of part 0 (seg_super_kernel): 4^sup_g adjacent part-0 bins --
+                                     // they share the upper nb[0] - sup_g bases of the bin code and lie back to back in
+                                     // the sub-bucket arrays -- are decided as one unit in LDS; 0: none
+    uint8_t sup_pad[7];              // (zero: the plan's tables are compared byte by byte)
+};
+// One super-bin: the part-0 bins [bin0, bin0 + 4^g) of a segment whose part 0 is indexed by nb bases and leaves
+// rest = umi_len - nb + g bases to tell its entries apart
+struct SegSuper {
+    uint32_t bin0;
+    uint8_t g, nb, rest, pad;
 };
 // An entry in sub-bucket order: everything the pair kernel needs of it, 16 bytes
 struct SegRec32 {
@@ -271,6 +281,15 @@ struct SegArgs {
     // kernel decides its sub-buckets of at least probe_min entries by bitmap lookups instead of the tile walk
     // (SEG_PROBE_MAX_REST, or 0: every sub-bucket is walked)
     uint32_t probe_rest, probe_min;
+    // k = 1, no N in the call: in a segment with SegDesc::sup_g > 0 a super-bin of 2..super_cap entries is "taken" --
+    // seg_super_kernel decides every pair inside it, its part-0 bins get no tile tasks and the pair kernel drops the
+    // hits of the other part that lie inside it; every other super-bin's bins all go to the tiles, and the one-wave
+    // local kernel leaves such a segment alone.  Whether a super-bin is taken is not stored: its entry count is
+    // bin_start[first bin of the next run] - bin_start[its first bin], which the scan and both kernels read.
+    // 0: no super-bins in this call (sup_g is ignored)
+    uint32_t super_cap;
+    const SegSuper *supers;
+    uint32_t n_supers;
 };
 // exclusive scan of the bin counts -> bin_start, task list, counters[CNT_SEG_TASKS / _PAIRS];
 // then every entry of a segment is copied to its position in each part's sub-bucket order
@@ -296,6 +315,22 @@ constexpr uint32_t SEG_LOCAL_CAP = 512; // default cap (LDS: 16 bytes per entry 
 constexpr int SEG_PROBE_MAX_REST = 6;                                       // 4,096 bits: 512 bytes
 constexpr uint32_t SEG_PROBE_WORDS = (1u << (2 * SEG_PROBE_MAX_REST)) / 32; // words of the bitmap
 constexpr uint32_t SEG_PROBE_MIN = 129; // smallest sub-bucket decided by lookups (up to three tiles: the tile walk)
+// Super-bins (see SegArgs::super_cap): LDS is 16 bytes per entry, a 4^8-bit map and its prefix -- one block per CU
+constexpr int SEG_SUPER_MAX_REST = 8;
+constexpr uint32_t SEG_SUPER_WORDS = (1u << (2 * SEG_SUPER_MAX_REST)) / 32; // 2,048
+constexpr int SEG_SUPER_MAX_BASES = 4;                                      // g: a super-bin stays inside a scan chunk
+constexpr uint32_t SEG_SUPER_MAX_CAP = 8192; // (eight records per thread of a 1,024-thread block in registers)
+constexpr uint32_t SEG_SUPER_CAP = 5632;     // default: config 2's largest super-bin (~4,050) with headroom
+constexpr uint32_t SEG_SUPER_MIN = 1024;     // smallest expected super-bin the planner gives the path to
+constexpr uint32_t SEG_SUPER_SMALL = 2048;   // caps up to here: 256-thread blocks
+inline uint32_t seg_super_threads(uint32_t cap) { return cap <= SEG_SUPER_SMALL ? 256u : 1024u; }
+size_t seg_super_lds_bytes(uint32_t cap);
+// private slots (one per wave) the kernel's grid needs: its blocks times its waves per block
+uint32_t seg_super_blocks(uint32_t n_supers, uint32_t n_cus);
+// Every taken super-bin: all pairs inside it by bitmap lookups out of LDS, symmetric ones united in an LDS forest
+// written to g.uf_parent as seg_local_kernel does, one-way ones to the waves' private slots (g.priv_* point at the
+// first of n_blocks * (threads / 64) slots).  A launch of its own ahead of the pair kernel, as launch_seg_local.
+hipError_t launch_seg_super(const PairArgs &a, const SegArgs &g, float percentage, uint32_t n_blocks, hipStream_t s);
 size_t seg_local_lds_bytes(uint32_t cap);
 int seg_local_blocks_per_cu(bool has_n, uint32_t cap);
 hipError_t launch_seg_local(const PairArgs &a, const SegArgs &g, float percentage, uint32_t n_blocks, hipStream_t s);

@@ -42,6 +42,8 @@ struct Plan {
     std::vector<SegDesc> segs;
     std::vector<SegScanChunk> seg_chunks;
     std::vector<SegBlock> seg_blocks; // entry blocks of the counting sort's LDS path
+    std::vector<SegSuper> seg_supers; // super-bins of the segments with sup_g > 0
+    uint64_t seg_plain = 0;           // segments with sup_g == 0 (the one-wave local kernel's)
     uint32_t seg_max_bins = 0;        // most bins any part of any segment has
     int seg_max_rest = 0;             // most bases any part of any segment leaves outside its bins
     int seg_parts = 0;           // k + 1 (0: no segment in this call)
@@ -182,7 +184,32 @@ inline bool seg_index_applies(int umi_len, int k)
 // Segment descriptor of a bucket of n entries: part j covers bases [j L / P, (j+1) L / P); its
 // bins are indexed by its leading bases, as many as keep a sub-bucket around 32-64 entries on
 // uniform keys (more bins than that only add empty ones to scan, fewer add pairs to evaluate).
-inline void plan_segment(Plan &pl, uint64_t s, uint64_t e, int umi_len, int k, bool key32)
+// Super-bins of part 0 (seg_super_kernel): what the call allows.  on: a call whose part-0 sub-buckets may be united
+// in LDS at all (batched directional or cluster path, unions on the spot, one device's whole call, 32-bit filter
+// keys), k = 1, no N mask.  bases: 0 = the planner's choice, 1..4 = that exponent where the conditions hold.
+struct SegSuperOpt {
+    bool on = false;
+    int bases = 0;
+    uint32_t cap = SEG_SUPER_CAP, min = SEG_SUPER_MIN;
+};
+// The exponent g for a segment of n entries whose part 0 is indexed by nb0 bases: the largest g for which the
+// rest-code (the bases outside the shared ones) fits the bitmap and the expected super-bin n / 4^(nb0 - g) lies
+// in min..3/4 cap (the headroom is for uneven bins: a super-bin beyond the cap goes back to the tiles whole).
+inline int choose_super_bases(uint64_t n, int umi_len, int nb0, const SegSuperOpt &o)
+{
+    if (!o.on) return 0;
+    for (int g = std::min(SEG_SUPER_MAX_BASES, nb0); g >= 1; g--) {
+        if (o.bases && g != o.bases) continue;
+        if (umi_len - nb0 + g > SEG_SUPER_MAX_REST) continue;
+        const uint64_t expect = n >> (2 * (nb0 - g));
+        if (expect > (uint64_t)o.cap / 4 * 3 || expect < o.min) continue;
+        return g;
+    }
+    return 0;
+}
+
+inline void plan_segment(Plan &pl, uint64_t s, uint64_t e, int umi_len, int k, bool key32,
+                         const SegSuperOpt &sup = SegSuperOpt())
 {
     const int P = k + 1;
     const uint64_t n = e - s;
@@ -199,6 +226,8 @@ inline void plan_segment(Plan &pl, uint64_t s, uint64_t e, int umi_len, int k, b
         sd.nb[j] = 0;
         sd.mask[j] = 0;
     }
+    sd.sup_g = 0;
+    for (uint8_t &b : sd.sup_pad) b = 0;
     for (int j = 0; j < P; j++) {
         const int b0 = j * umi_len / P, b1 = (j + 1) * umi_len / P;
         const int nb = std::min(b1 - b0, nb_cap);
@@ -215,6 +244,14 @@ inline void plan_segment(Plan &pl, uint64_t s, uint64_t e, int umi_len, int k, b
         pl.seg_max_bins = std::max<uint32_t>(pl.seg_max_bins, (uint32_t)std::min<uint64_t>(bins, 0xFFFFFFFFull));
         pl.seg_max_rest = std::max(pl.seg_max_rest, umi_len - nb);
         pl.seg_task_cap += seg_task_bound(n, bins);
+    }
+    if (k == 1 && key32) sd.sup_g = (uint8_t)choose_super_bases(n, umi_len, sd.nb[0], sup);
+    if (sd.sup_g) { // (k = 1: part 1's first bin follows part 0's last, so every run has a next bin_start word)
+        const uint32_t g = sd.sup_g, nb0 = sd.nb[0];
+        for (uint32_t sb = 0; sb < (1u << (2 * (nb0 - g))); sb++)
+            pl.seg_supers.push_back({sd.bin_off[0] + (sb << (2 * g)), (uint8_t)g, (uint8_t)nb0, (uint8_t)(umi_len - nb0 + g), 0});
+    } else {
+        pl.seg_plain++;
     }
     pl.seg_entries += n;
     for (uint64_t q = s; q < e; q += SEG_BLOCK_ENTRIES)
@@ -337,11 +374,13 @@ inline void scan_table(const uint64_t *__restrict bucket_off, uint64_t n_buckets
 inline void build_plan(const uint64_t *bucket_off, uint64_t n_buckets, uint32_t small_max, bool use_bs,
                 int umi_len, uint32_t fused_max, bool narrow_only, bool cache_prefix, bool tables,
                 uint32_t tab_min_run, uint32_t seg_min, int k, bool key32, Plan &pl,
-                const TablePass *pass = nullptr)
+                const TablePass *pass = nullptr, const SegSuperOpt &sup = SegSuperOpt())
 {
     pl.segs.clear();
     pl.seg_chunks.clear();
     pl.seg_blocks.clear();
+    pl.seg_supers.clear();
+    pl.seg_plain = 0;
     pl.seg_max_bins = 0;
     pl.seg_max_rest = 0;
     pl.seg_parts = 0;
@@ -396,7 +435,7 @@ inline void build_plan(const uint64_t *bucket_off, uint64_t n_buckets, uint32_t 
         if (n <= fused_max) {
             pl.n_pairs_eval += n * n;
         } else if (is_seg) {
-            plan_segment(pl, s, e, umi_len, k, key32);
+            plan_segment(pl, s, e, umi_len, k, key32, sup);
             pl.seg_parts = k + 1;
         } else if (n <= small_max) {
             for (uint64_t r0 = s; r0 < e; r0 += SMALL_ROWS) {

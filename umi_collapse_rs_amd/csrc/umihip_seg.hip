@@ -20,7 +20,7 @@ namespace umihip {
 namespace {
 
 constexpr int SCAN_THREADS = 256;
-constexpr int SCAN_PER_THREAD = SEG_SCAN_CHUNK / SCAN_THREADS; // 16 bins per thread
+constexpr int SCAN_PER_THREAD = SEG_SCAN_CHUNK / SCAN_THREADS; // one bin per thread
 
 // a part whose bins are indexed by nb bases has its sub-buckets decided by lookups (seg_local_kernel)
 __device__ __forceinline__ bool probe_part(const SegArgs &g, uint32_t nb)
@@ -29,10 +29,10 @@ __device__ __forceinline__ bool probe_part(const SegArgs &g, uint32_t nb)
 }
 // (a part-0 sub-bucket the local kernel takes has no tile tasks)
 __device__ __forceinline__ bool local_bin(const SegArgs &g, uint32_t part, uint32_t c) { return part == 0 && c <= g.local_cap; }
-__device__ __forceinline__ uint32_t tasks_of_bin(const SegArgs &g, uint32_t part, uint32_t c)
-{
-    return local_bin(g, part, c) ? 0u : seg_tasks_of_bin(c);
-}
+// a super-bin of n entries is seg_super_kernel's: its bins have no tile tasks either
+__device__ __forceinline__ bool super_taken(const SegArgs &g, uint32_t n) { return n >= 2u && n <= g.super_cap; }
+// super-bin exponent of a segment in this call (wave-uniform)
+__device__ __forceinline__ uint32_t super_bases(const SegArgs &g, uint32_t seg) { return g.super_cap ? g.segs[seg].sup_g : 0u; }
 
 // Exclusive scan of the bin counts -> bin_start, the task list, the pair count: ONE launch, the
 // chunks chained by a decoupled look-back.  A block draws its chunk from a ticket counter (so that
@@ -62,8 +62,27 @@ __global__ __launch_bounds__(SCAN_THREADS) void seg_scan_kernel(SegArgs g, unsig
         const uint32_t b = b_first + q;
         c[q] = b < ch.nbins ? g.bin_cnt[ch.bin0 + b] : 0u;
         mine.x += c[q];
-        mine.y += tasks_of_bin(g, ch.part, c[q]);
     }
+    // bit q: bin q of this thread has no tile tasks -- the local kernel's, or inside a taken super-bin.  A super-bin
+    // is 4^sg adjacent bins, the bins of 4^sg / SCAN_PER_THREAD adjacent threads (one chunk at most)
+    uint32_t no_tasks = 0;
+    const uint32_t sg = ch.part == 0 ? super_bases(g, ch.seg) : 0u; // (block-uniform)
+    if (sg) {
+        static_assert(SCAN_PER_THREAD == 1 || SCAN_PER_THREAD == 4, "a super-bin is whole threads' bins");
+        __shared__ uint32_t tcnt[SCAN_THREADS];
+        tcnt[threadIdx.x] = mine.x;
+        __syncthreads();
+        const uint32_t nthr = (1u << (2 * sg)) / SCAN_PER_THREAD, t0 = threadIdx.x & ~(nthr - 1u);
+        uint32_t n_super = 0;
+        for (uint32_t i = 0; i < nthr; i++) n_super += tcnt[t0 + i];
+        if (super_taken(g, n_super)) no_tasks = (1u << SCAN_PER_THREAD) - 1u;
+    } else {
+#pragma unroll
+        for (int q = 0; q < SCAN_PER_THREAD; q++)
+            if (local_bin(g, ch.part, c[q])) no_tasks |= 1u << q;
+    }
+#pragma unroll
+    for (int q = 0; q < SCAN_PER_THREAD; q++) mine.y += (no_tasks >> q) & 1u ? 0u : seg_tasks_of_bin(c[q]);
     uint2 incl = mine;
     for (int d = 1; d < 64; d <<= 1) {
         const uint32_t ux = __shfl_up(incl.x, d), uy = __shfl_up(incl.y, d);
@@ -129,7 +148,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void seg_scan_kernel(SegArgs g, unsig
         if (b < ch.nbins) {
             g.bin_start[ch.bin0 + b] = off.x;
             g.bin_cnt[ch.bin0 + b] = 0;
-            const uint32_t nt = local_bin(g, ch.part, c[q]) ? 0u : seg_chunks_of(c[q]), e = seg_span_log2(nt), span = 1u << e;
+            const uint32_t nt = (no_tasks >> q) & 1u ? 0u : seg_chunks_of(c[q]), e = seg_span_log2(nt), span = 1u << e;
             const uint32_t where = ch.seg | (ch.part << 24) | (e << 28);
             uint32_t ti = off.y;
             for (uint32_t t = 0; t < nt; t++) {
@@ -642,6 +661,9 @@ __global__ __launch_bounds__(64) void seg_pair_kernel(PairArgs a, SegArgs g, flo
     for (int j = 0; j < SEG_MAX_PARTS - 1; j++) dup_mask[j] = KeyT(0);
     uint32_t have_seg = SEG_NONE, have_part = 0;
     int ck_bases = 0;
+    // a segment with super-bins, tasks of part 1: the filter-key bits of the bases a super-bin shares (as a part-0
+    // bin code they are the super-bin's first bin), the bins of a super-bin, the segment's first part-0 bin
+    uint32_t sup_mask = 0, sup_bins = 0, sup_bin0 = 0;
     const bool sliced = a.k <= 3 && g.col_sliced != 0;
     uint32_t nq = 0; // queued hits (wave-uniform); the queue outlives a task
 
@@ -676,6 +698,11 @@ __global__ __launch_bounds__(64) void seg_pair_kernel(PairArgs a, SegArgs g, flo
                 for (int p = 0; p < SEG_MAX_PARTS - 1; p++)
                     ok = ok && (dup_mask[p] == KeyT(0) || (z & dup_mask[p]) != KeyT(0));
                 if (!ok) continue;
+                // ... and a pair inside a taken super-bin by seg_super_kernel
+                if (sup_bins && ((uint32_t)z & sup_mask) == 0u) {
+                    const uint32_t b = sup_bin0 + ((uint32_t)ra[s].key & sup_mask);
+                    if (super_taken(g, g.bin_start[b + sup_bins] - g.bin_start[b])) continue;
+                }
                 // entry indices in rank order (src/algo/directional.rs:67-72)
                 const bool sw = cb[s].idx < ra[s].idx;
                 const uint32_t gi = sw ? cb[s].idx : ra[s].idx, gj = sw ? ra[s].idx : cb[s].idx;
@@ -785,6 +812,10 @@ __global__ __launch_bounds__(64) void seg_pair_kernel(PairArgs a, SegArgs g, flo
                 have_seg = seg;
                 have_part = my_part;
                 ck_bases = __builtin_amdgcn_readfirstlane(g.umi_len - (int)sd->nb[my_part]); // bases a compare key holds
+                const uint32_t sg = my_part != 0 ? super_bases(g, seg) : 0u;
+                sup_mask = sg ? ((1u << (2 * (sd->nb[0] - sg))) - 1u) << (2 * sg) : 0u;
+                sup_bins = sg ? 1u << (2 * sg) : 0u; // (0: no super-bins here)
+                sup_bin0 = sd->bin_off[0];
             }
             for (uint32_t c0 = col0; c0 < col1; c0 += 64) {
                 // (a task of several tiles -- a sub-bucket beyond 1025 entries: the next 64 columns
@@ -885,6 +916,33 @@ __device__ __forceinline__ void lds_union(uint32_t *par, uint32_t u, uint32_t v)
         } else {
             u = pu;
             pu = lds_ld(&par[u]);
+        }
+    }
+}
+
+// ... by many waves on forests of thousands of positions (seg_super_kernel): a climb also moves the position it
+// leaves under its grandparent (path halving).  Every value a position's word ever holds is an ancestor of it --
+// a root's word only changes by its own compare-and-swap, the halving stores only touch words that have a parent
+// already -- so a stale store costs a step, never a set.
+__device__ __forceinline__ void lds_union_halving(uint32_t *par, uint32_t u, uint32_t v)
+{
+    const uint32_t seen = atomicCAS(&par[v], v, u);
+    if (seen == v || seen == u) return;
+    uint32_t pu = lds_ld(&par[u]), pv = seen;
+    while (pu != pv) {
+        if (pu < pv) {
+            uint32_t t = u; u = v; v = t;
+            t = pu; pu = pv; pv = t;
+        }
+        if (u == pu) {
+            const uint32_t old = atomicCAS(&par[u], u, pv);
+            if (old == u) return;
+            pu = old;
+        } else {
+            const uint32_t up = lds_ld(&par[pu]);
+            if (up != pu) __hip_atomic_store(&par[u], up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            u = pu;
+            pu = up;
         }
     }
 }
@@ -996,7 +1054,7 @@ __global__ __launch_bounds__(64) void seg_local_kernel(PairArgs a, SegArgs g, fl
     for (uint32_t id = blockIdx.x; id < n_ids; id += gridDim.x) {
         const SegScanChunk ch = g.chunks[id / SEG_SCAN_CHUNK];
         const uint32_t bi = id % SEG_SCAN_CHUNK;
-        if (ch.part != 0 || bi >= ch.nbins) continue;
+        if (ch.part != 0 || bi >= ch.nbins || super_bases(g, ch.seg)) continue; // (a segment with super-bins: not this kernel's)
         const uint32_t nb = g.segs[ch.seg].nb[0];
         const uint32_t b = ch.bin0 + bi;
         const uint32_t c = __builtin_amdgcn_readfirstlane(g.bin_cnt[b]); // (the scatter's cursor: the count again)
@@ -1131,6 +1189,227 @@ __global__ __launch_bounds__(64) void seg_local_kernel(PairArgs a, SegArgs g, fl
     for (int off = 32; off > 0; off >>= 1) n_cand += __shfl_down(n_cand, off);
     for (int off = 32; off > 0; off >>= 1) n_direct += __shfl_down(n_direct, off);
     if (lane == 0) g.priv_stat[blockIdx.x] = make_uint2(n_cand, n_direct); // (the flatten launch adds them up)
+}
+
+// ---- super-bins: runs of adjacent part-0 bins in LDS (k = 1, no N in the call) ---------------------------
+// The index orders part-0 bins by their code, so the 4^g bins that share the upper nb - g bases of it lie back to
+// back in the sub-bucket arrays: one super-bin.  A block that holds a whole super-bin in LDS decides every pair
+// that agrees on those shared bases -- a pair inside one of its bins and a pair that differs in one of the g low
+// bases, which would otherwise be part 1's to find and a global union's to join.  An entry is its rest-code (the
+// filter key's 2 bits per base with the shared bases squeezed out, at most SEG_SUPER_MAX_REST bases), the
+// super-bin a bitmap of 4^rest bits; the rest is seg_local_kernel's lookup path with many waves: records read
+// once and kept in registers until the rank of their code is known, 3 * rest single-bit tests per entry for the
+// partners with the larger code, symmetric pairs united in an LDS forest over positions (lds_union_halving: hooks
+// are compare-and-swaps, waves may race), one-way pairs to a private slot per wave, and the local kernel's
+// write-out: label[idx] = smallest entry index of idx's set, the forest flattened by pointer jumping first.  A key twice in the input shows when the map is
+// built: that super-bin's positions are walked pair by pair instead, where equal codes are a hit of distance 0.
+// Which super-bins: those of 2..super_cap entries, read off bin_start as the scan and the pair kernel do.
+constexpr int SUPER_RPT = 8; // records a thread keeps in registers: a block takes SUPER_RPT * its threads
+
+template <bool CLUSTER, int NT>
+__global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, float percentage)
+{
+    extern __shared__ uint32_t lds[];
+    constexpr int NW = NT / 64;
+    constexpr int WPT = (int)SEG_SUPER_WORDS / NT; // words of the bitmap a thread sums for the prefix
+    static_assert(WPT * NT == (int)SEG_SUPER_WORDS && WPT >= 1, "whole words per thread");
+    const uint32_t cap = g.super_cap;
+    uint32_t *sc = lds, *ix = lds + cap, *fr = lds + 2 * cap, *par = lds + 3 * cap; // rest-code, entry index, freq, forest
+    uint32_t *bm = lds + 4 * cap, *pre = bm + SEG_SUPER_WORDS; // the bitmap, set bits before each word
+    __shared__ uint32_t wsum[NW];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6;
+    const int lane = (int)(tid & 63u);
+    const SegRec32 *__restrict__ sub = (const SegRec32 *)g.sub_rec;
+    unsigned int n_cand = 0, n_direct = 0;
+    // one-way pairs: to this wave's private slot, wave-uniform fill level; a slot that is full sends the rest to
+    // the list, one atomic per wave and batch
+    const size_t my_slot = (size_t)blockIdx.x * NW + wave;
+    uint32_t n_out = 0;
+    uint2 *__restrict__ slot = g.priv_edges + my_slot * SEG_PRIV_CAP;
+    auto emit = [&](bool has, uint32_t u, uint32_t v) {
+        const unsigned long long bal = __ballot(has);
+        if (!bal) return;
+        const uint32_t cnt = (uint32_t)__builtin_popcountll(bal);
+        const uint32_t pos = n_out + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1ull));
+        unsigned long long base = 0;
+        if (n_out + cnt > SEG_PRIV_CAP) {
+            const uint32_t first_over = max(n_out, SEG_PRIV_CAP);
+            const int leader = __builtin_ctzll(bal);
+            if (lane == leader) base = atomicAdd(&a.counters[CNT_EDGES], (unsigned long long)(n_out + cnt - first_over));
+            base = __shfl(base, leader);
+            base -= first_over;
+        }
+        if (has) {
+            if (pos < SEG_PRIV_CAP) slot[pos] = make_uint2(u, v);
+            else if (base + pos < a.edge_cap) a.edges[base + pos] = make_uint2(u, v);
+        }
+        n_out += cnt;
+    };
+    // a pair within one substitution at positions pa, pb (the whole wave calls, `has` says which lanes hold one)
+    auto decide = [&](bool has, uint32_t pa, uint32_t pb) {
+        const uint32_t ia = ix[pa], ib = ix[pb];
+        const int32_t fa = (int32_t)fr[pa], fb = (int32_t)fr[pb];
+        // entry indices in rank order (src/algo/directional.rs:67-72)
+        const bool sw = ib < ia;
+        const uint32_t gi = sw ? ib : ia, gj = sw ? ia : ib;
+        const int32_t fi = sw ? fb : fa, fj = sw ? fa : fb;
+        if (has) n_cand++;
+        // naive.rs:31 under directional.rs:38-39
+        const bool fwd = has && (CLUSTER || fj <= threshold_of(percentage, fi));
+        const bool bwd = has && (CLUSTER || fi <= threshold_of(percentage, fj));
+        if (fwd && bwd) { // reachability inside such a set is symmetric: one set
+            n_direct++;
+            lds_union_halving(par, min(pa, pb), max(pa, pb));
+        }
+        emit(fwd != bwd, fwd ? gi : gj, fwd ? gj : gi);
+    };
+
+    for (uint32_t u = blockIdx.x; u < g.n_supers; u += gridDim.x) {
+        const SegSuper su = g.supers[u];
+        const uint32_t start = __builtin_amdgcn_readfirstlane(g.bin_start[su.bin0]);
+        const uint32_t c = __builtin_amdgcn_readfirstlane(g.bin_start[su.bin0 + (1u << (2 * su.g))]) - start;
+        if (!super_taken(g, c)) continue; // (block-uniform)
+        const uint32_t lo_bits = 2u * su.g, hi_shift = 2u * su.nb, rest = su.rest;
+        const uint32_t lo_mask = (1u << lo_bits) - 1u, code_mask = (1u << (2u * rest)) - 1u; // rest <= 8: 16 bits
+        for (uint32_t w = tid; w < SEG_SUPER_WORDS; w += NT) bm[w] = 0u;
+        uint32_t rc[SUPER_RPT], ri[SUPER_RPT], rf[SUPER_RPT], rq[SUPER_RPT];
+#pragma unroll
+        for (int r = 0; r < SUPER_RPT; r++) {
+            const uint32_t p = tid + (uint32_t)r * NT;
+            rc[r] = ri[r] = rf[r] = rq[r] = 0u;
+            if (p < c) {
+                const SegRec32 rec = sub[start + p];
+                rc[r] = ((rec.key & lo_mask) | ((rec.key >> hi_shift) << lo_bits)) & code_mask;
+                ri[r] = rec.idx;
+                rf[r] = (uint32_t)rec.freq;
+            }
+        }
+        __syncthreads();
+        bool twice = false;
+#pragma unroll
+        for (int r = 0; r < SUPER_RPT; r++)
+            if (tid + (uint32_t)r * NT < c) {
+                const uint32_t bit = 1u << (rc[r] & 31u);
+                twice = twice || (atomicOr(&bm[rc[r] >> 5], bit) & bit) != 0u;
+            }
+        const bool dup = __syncthreads_or(twice ? 1 : 0) != 0;
+        if (!dup) {
+            { // set bits before every word: a thread sums WPT words, the block scans the sums
+                uint32_t n_w[WPT], mine = 0;
+#pragma unroll
+                for (int i = 0; i < WPT; i++) mine += n_w[i] = (uint32_t)__builtin_popcount(bm[tid * WPT + i]);
+                uint32_t incl = mine;
+                for (int d = 1; d < 64; d <<= 1) {
+                    const uint32_t up = __shfl_up(incl, d);
+                    if (lane >= d) incl += up;
+                }
+                if (lane == 63) wsum[wave] = incl;
+                __syncthreads();
+                uint32_t before = incl - mine;
+                for (uint32_t w = 0; w < wave; w++) before += wsum[w];
+#pragma unroll
+                for (int i = 0; i < WPT; i++) {
+                    pre[tid * WPT + i] = before;
+                    before += n_w[i];
+                }
+            }
+            __syncthreads();
+            auto rank_of = [&](uint32_t s) { // entries of the super-bin with a smaller rest-code = the position of s's
+                return pre[s >> 5] + (uint32_t)__builtin_popcount(bm[s >> 5] & ((1u << (s & 31u)) - 1u));
+            };
+#pragma unroll
+            for (int r = 0; r < SUPER_RPT; r++)
+                if (tid + (uint32_t)r * NT < c) {
+                    const uint32_t q = rank_of(rc[r]);
+                    rq[r] = q;
+                    sc[q] = rc[r];
+                    ix[q] = ri[r];
+                    fr[q] = rf[r];
+                    par[q] = q;
+                }
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < SUPER_RPT; r++) {
+                if ((uint32_t)r * NT >= c) break; // (block-uniform)
+                const uint32_t s = rc[r];
+                uint32_t m = 0; // bit 3 b + d - 1: the entry with base b changed by d is there, behind this one
+#pragma unroll
+                for (int bb = 0; bb < SEG_SUPER_MAX_REST; bb++) {
+#pragma unroll
+                    for (int d = 1; d <= 3; d++) {
+                        const uint32_t t = s ^ ((uint32_t)d << (2 * bb));
+                        const uint32_t there = (bm[t >> 5] >> (t & 31u)) & 1u;
+                        if ((uint32_t)bb < rest && t > s) m |= there << (3 * bb + d - 1);
+                    }
+                }
+                if (tid + (uint32_t)r * NT >= c) m = 0u;
+                while (__any(m != 0u)) { // one hit per lane and round
+                    const bool has = m != 0u;
+                    uint32_t pb = 0;
+                    if (has) {
+                        const int j = __builtin_ctz(m), bb = j / 3;
+                        m &= m - 1u;
+                        pb = rank_of(s ^ ((uint32_t)(j - 3 * bb + 1) << (2 * bb)));
+                    }
+                    decide(has, has ? rq[r] : 0u, pb);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < SUPER_RPT; r++) {
+                const uint32_t p = tid + (uint32_t)r * NT;
+                if (p < c) {
+                    sc[p] = rc[r];
+                    ix[p] = ri[r];
+                    fr[p] = rf[r];
+                    par[p] = p;
+                }
+            }
+            __syncthreads();
+            // every pair of positions p < q: a thread's own entries against the ones behind them, the wave in step
+#pragma unroll
+            for (int r = 0; r < SUPER_RPT; r++) {
+                if ((uint32_t)r * NT >= c) break; // (block-uniform)
+                const uint32_t p = tid + (uint32_t)r * NT, p_first = p - (uint32_t)lane;
+                const uint32_t s = rc[r];
+                const uint32_t n_it = c > p_first + 1u ? c - 1u - p_first : 0u; // (wave-uniform)
+                for (uint32_t i = 1; i <= n_it; i++) {
+                    const uint32_t q = p + i;
+                    const uint32_t z = s ^ (q < c ? sc[q] : 0u);
+                    const bool hit = p < c && q < c && __builtin_popcount((z | (z >> 1)) & 0x55555555u) <= 1;
+                    if (__any(hit)) decide(hit, hit ? p : 0u, hit ? q : 0u);
+                }
+            }
+        }
+        __syncthreads();
+        // the sets out: root position of every entry (into sc[], free now), the smallest entry index of every
+        // set (fr[] of its root), label[] of every entry
+        // (the forest stands still now, and its chains can be hundreds of positions long: every position jumps to
+        // its grandparent, all together, until none moves -- a handful of rounds instead of a climb per entry)
+        for (;;) {
+            bool moved = false;
+            for (uint32_t p = tid; p < c; p += NT) {
+                const uint32_t q = lds_ld(&par[p]), up = lds_ld(&par[q]);
+                if (up != q) {
+                    __hip_atomic_store(&par[p], up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    moved = true;
+                }
+            }
+            if (!__syncthreads_or(moved ? 1 : 0)) break;
+        }
+        for (uint32_t p = tid; p < c; p += NT) sc[p] = lds_ld(&par[p]);
+        __syncthreads(); // (fr[] was read by the pairs until here)
+        for (uint32_t p = tid; p < c; p += NT) fr[p] = 0xFFFFFFFFu;
+        __syncthreads();
+        for (uint32_t p = tid; p < c; p += NT) atomicMin(&fr[sc[p]], ix[p]);
+        __syncthreads();
+        for (uint32_t p = tid; p < c; p += NT) g.uf_parent[ix[p]] = fr[sc[p]];
+        __syncthreads(); // (the next super-bin's records overwrite these arrays)
+    }
+    if (lane == 0) g.priv_cnt[my_slot] = min(n_out, SEG_PRIV_CAP);
+    for (int off = 32; off > 0; off >>= 1) n_cand += __shfl_down(n_cand, off);
+    for (int off = 32; off > 0; off >>= 1) n_direct += __shfl_down(n_direct, off);
+    if (lane == 0) g.priv_stat[my_slot] = make_uint2(n_cand, n_direct); // (the flatten launch adds them up)
 }
 
 // offsets of the blocks' slots behind what the list holds already (one block), the new total
@@ -1277,6 +1556,40 @@ hipError_t launch_seg_local(const PairArgs &a, const SegArgs &g, float percentag
     } else if (a.nmask) seg_local_kernel<true><<<n_blocks, 64, lds, s>>>(a, g, percentage);
     else seg_local_kernel<false><<<n_blocks, 64, lds, s>>>(a, g, percentage);
     return hipGetLastError();
+}
+
+// (the records and the forest, the bitmap and its prefix: 106,496 bytes at the default cap -- one block to a CU's 160 KB)
+size_t seg_super_lds_bytes(uint32_t cap) { return ((size_t)4 * cap + 2 * SEG_SUPER_WORDS) * sizeof(uint32_t); }
+
+// its persistent grid: one block per CU at most, no more than there are super-bins
+uint32_t seg_super_blocks(uint32_t n_supers, uint32_t n_cus) { return n_supers < n_cus ? n_supers : n_cus; }
+
+template <bool CLUSTER, int NT>
+static hipError_t launch_seg_super_as(const PairArgs &a, const SegArgs &g, float percentage, uint32_t n_blocks, size_t lds,
+                                      hipStream_t s)
+{
+    // (beyond 64 KB of dynamic LDS a kernel has to be told so)
+    const hipError_t e = hipFuncSetAttribute((const void *)seg_super_kernel<CLUSTER, NT>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    seg_super_kernel<CLUSTER, NT><<<n_blocks, NT, lds, s>>>(a, g, percentage);
+    return hipGetLastError();
+}
+
+hipError_t launch_seg_super(const PairArgs &a, const SegArgs &g, float percentage, uint32_t n_blocks, hipStream_t s)
+{
+    if (g.n_supers == 0 || n_blocks == 0 || g.super_cap == 0) return hipSuccess;
+    if (g.super_cap > SEG_SUPER_MAX_CAP || !g.supers || !g.uf_parent || !g.priv_stat || a.nmask || a.k != 1 ||
+        (a.mode != MODE_DIRECTIONAL && a.mode != MODE_CLUSTER))
+        return hipErrorInvalidValue;
+    const size_t lds = seg_super_lds_bytes(g.super_cap);
+    static_assert(SEG_SUPER_SMALL <= 256 * SUPER_RPT && SEG_SUPER_MAX_CAP <= 1024 * SUPER_RPT, "a block holds the cap in registers");
+    const bool small = seg_super_threads(g.super_cap) == 256u;
+    if (a.mode == MODE_CLUSTER)
+        return small ? launch_seg_super_as<true, 256>(a, g, percentage, n_blocks, lds, s)
+                     : launch_seg_super_as<true, 1024>(a, g, percentage, n_blocks, lds, s);
+    return small ? launch_seg_super_as<false, 256>(a, g, percentage, n_blocks, lds, s)
+                 : launch_seg_super_as<false, 1024>(a, g, percentage, n_blocks, lds, s);
 }
 
 // what the pair kernel's blocks still held in their stages when they ended: from their private
