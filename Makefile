@@ -22,6 +22,9 @@ CLI := $(PKG)/bin/umicollapse
 
 all: $(LIB) oracle cpptest primtest $(CLI)
 
+# (the staging's host decisions: read by the staging unit alone)
+$(OBJDIR)/umihip_stage.o $(DEVDIR)/umihip_stage.o: $(CSRC)/umihip_stage_plan.hpp
+
 # one object per translation unit (the rocPRIM sort alone takes ~20 s to compile)
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)

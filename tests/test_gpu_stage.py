@@ -213,7 +213,8 @@ def test_many_tiny_positions_and_few_deep_ones_take_the_sort(ctx):
 def test_local_order_with_64_bit_order_keys():
     """Positions of up to 1,024 entries are ordered by a wave each (no sort): with 32-bit order keys where the
     freq field and the read index fit them together, else with 64-bit ones -- forced here through the
-    environment (it takes 2^24 reads otherwise), in a process of its own: the library reads it once."""
+    environment on inputs that the rule would give 32-bit keys (the rule's own 33-bit cases are in
+    test_gpu_stage_edges.py), in a process of its own: the library reads it once."""
     import os
     import subprocess
     import sys

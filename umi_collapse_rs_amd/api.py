@@ -630,6 +630,20 @@ class Context:
                                                     C.byref(nb), stream or None))
         return int(ne.value), int(nb.value)
 
+    def stage_reads_grouped_wide_device(self, d_align_key, d_group_key, d_umi, d_score, n_reads, umi_len, d_keys,
+                                        d_nmask, d_freq, d_rep, d_bucket_off, merge=1, align_key_bits=64,
+                                        group_key_bits=64, stream=0):
+        """umi_stage_reads_grouped_wide_device (raw device pointers): UMIs of up to 85 bases, keys / nmask
+        ceil(3 * umi_len / 64) words per entry; group_key_bits=0 (d_group_key may then be 0) is the plain
+        umi_stage_reads_wide_device, as in the C ABI.  Returns (n_entries, n_buckets)."""
+        ne, nb = C.c_uint64(0), C.c_uint64(0)
+        check(load().umi_stage_reads_grouped_wide_device(self._h, d_align_key, align_key_bits, d_group_key or None,
+                                                         group_key_bits, d_umi, d_score or None, n_reads, umi_len,
+                                                         (3 * umi_len + 63) // 64, merge, d_keys, d_nmask or None,
+                                                         d_freq, d_rep, d_bucket_off, C.byref(ne), C.byref(nb),
+                                                         stream or None))
+        return int(ne.value), int(nb.value)
+
     def stage_reads_device(self, d_align_key, d_umi, d_score, n_reads, umi_len, d_keys, d_nmask, d_freq,
                            d_rep, d_bucket_off, merge=1, align_key_bits=64, stream=0):
         """The same with everything in device memory (raw pointers); returns (n_entries, n_buckets)."""

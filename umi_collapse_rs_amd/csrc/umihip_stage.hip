@@ -30,6 +30,7 @@
 
 #include "../../include/umihip.h"
 #include "umihip_internal.h"
+#include "umihip_stage_plan.hpp"
 
 namespace umihip {
 
@@ -66,17 +67,8 @@ __device__ __forceinline__ uint32_t encode4(uint32_t w, uint32_t *bad)
 // The sort of the reads only has to bring equal (alignment, UMI) together, so the UMI rides in the
 // composed key at seven bits per three bases (5^3 = 125 letters' worth) instead of nine -- 12 bases:
 // 28 bits, not 36, a radix pass less -- codes 0 3 4 5 6 -> digits 0 1 2 3 4, a group = d0 + 5 d1 +
-// 25 d2, groups in base order from bit 0; a last group of one / two bases takes three / five bits.
-struct Pack5 {
-    int len, bits;
-};
-inline Pack5 pack5_of(int umi_len)
-{
-    Pack5 p;
-    p.len = umi_len;
-    p.bits = 7 * (umi_len / 3) + (umi_len % 3 == 1 ? 3 : umi_len % 3 == 2 ? 5 : 0);
-    return p;
-}
+// 25 d2, groups in base order from bit 0; a last group of one / two bases takes three / five bits
+// (Pack5, pack5_of: umihip_stage_plan.hpp).
 __device__ __forceinline__ uint64_t pack5(uint64_t key3, const Pack5 &p)
 {
     uint64_t out = 0;
@@ -680,7 +672,7 @@ __global__ __launch_bounds__(256) void stage_emit_kernel(const uint32_t *__restr
 // its (max freq - freq, first read) keys go to LDS, every lane counts the keys below its own (all
 // pairs: a position of 60 entries is 60 broadcast reads), and writes its entry where it belongs.  At
 // 10^7 reads in 10^5 positions this replaces the order kernel, three radix passes and the gather.
-constexpr uint32_t LOCAL_MAX = 1024;
+constexpr uint32_t LOCAL_MAX = STAGE_LOCAL_MAX;
 __global__ __launch_bounds__(256) void stage_rank_sizes_kernel(const uint32_t *__restrict__ pos_start,
                                                                const uint32_t *__restrict__ brank_of, uint32_t n_buckets,
                                                                uint64_t *__restrict__ size_by_rank)
@@ -944,13 +936,6 @@ __global__ __launch_bounds__(256) void seq_entry_slot_kernel(const uint32_t *__r
     for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) eor[r] = slot[eor[r]];
 }
 
-inline int bits_for(uint64_t v)
-{
-    int b = 1;
-    while (b < 64 && (v >> b)) b++;
-    return b;
-}
-
 struct Carver {
     char *p;
     size_t off = 0;
@@ -1064,32 +1049,33 @@ int stage_finish(StageBufs &b, uint32_t *va, const uint64_t *composed, Pack5 p5,
     // ---- 3'. every position fits a wave's LDS: ordered where it lies, no sort.  (A wave per position pays
     // where positions hold some tens of entries; a file of singletons -- shallow sequencing -- is 10^7
     // positions of one entry each, a trip to memory per wave and position: the sort below does not care.)
-    if (pmax <= LOCAL_MAX && (uint64_t)E >= 16ull * B) {
+    // (UMIHIP_STAGE_WIDE_ORDER in the environment: the 64-bit order keys of 3' on any input.  The rule alone
+    // takes them from 33 bits of read index and freq on: 2^17 reads with one UMI read 32,768 times.)
+    static const bool force_wide = getenv("UMIHIP_STAGE_WIDE_ORDER") != nullptr;
+    const StageOrderPlan op = stage_order_plan(n, E, B, fmax, pmax, force_wide);
+    if (op.local) {
         uint64_t *size_by_rank = b.keyA, *end_by_rank = b.keyB; // (the read sort's buffers are free)
         stage_rank_sizes_kernel<<<grid_for(B), 256, 0, s>>>(b.pos_start, b.brank_of, B, size_by_rank);
         STAGE_TRY(scan_inclusive_u64(size_by_rank, end_by_rank, B, b.tmp, b.tmp_bytes, s));
-        const int first_bits = bits_for(n - 1);
-        // (UMIHIP_STAGE_WIDE_ORDER: the tests' way to the 64-bit form, which otherwise needs 2^24 reads and a freq to match)
-        static const bool force_wide = getenv("UMIHIP_STAGE_WIDE_ORDER") != nullptr;
-        if (first_bits + bits_for(fmax) <= 32 && !force_wide)
+        if (!op.wide)
             stage_emit_local_kernel<W, uint32_t><<<grid_for((uint64_t)B, 4, 8192), 256, 0, s>>>(
-                b.pos_start, b.brank_of, end_by_rank, E, B, use_score ? 1 : 0, umi_len, fmax, first_bits, p5, one_key ? 1 : 0,
+                b.pos_start, b.brank_of, end_by_rank, E, B, use_score ? 1 : 0, umi_len, fmax, op.first_bits, p5, one_key ? 1 : 0,
                 b.ent_key, b.ent_first, b.head_pos, b.best, d_keys, d_nmask, d_freq, d_rep, d_bucket_off, slot);
         else
             stage_emit_local_kernel<W, uint64_t><<<grid_for((uint64_t)B, 4, 4096), 256, 0, s>>>(
-                b.pos_start, b.brank_of, end_by_rank, E, B, use_score ? 1 : 0, umi_len, fmax, 32, p5, one_key ? 1 : 0,
+                b.pos_start, b.brank_of, end_by_rank, E, B, use_score ? 1 : 0, umi_len, fmax, op.first_bits, p5, one_key ? 1 : 0,
                 b.ent_key, b.ent_first, b.head_pos, b.best, d_keys, d_nmask, d_freq, d_rep, d_bucket_off, slot);
     } else {
         // ... and one stable sort of the entries, taken in that order, by (position rank, max freq - freq).
         // (Everything of the read sort but its order, va, is free by now -- and va's twin and the entry
         // numbers too, in stream order.)
-        const int freq_bits = bits_for(fmax), rank_bits = bits_for(B ? B - 1 : 0), order_bits = std::min(64, freq_bits + rank_bits);
+        const int freq_bits = op.freq_bits, order_bits = op.order_bits;
         uint32_t *ova = va == b.idxA ? b.idxB : b.idxA, *ovb = b.numbers;
         uint32_t *hist = nullptr;
         STAGE_TRY(radix_sort_prepare(b.tmp, b.tmp_bytes, E, 0, order_bits, &hist, s));
         bool ob = false;
         const uint32_t order_blocks = grid_for(E, 256, RADIX_HIST_PARTS);
-        if (order_bits <= 32) {
+        if (!op.key64) {
             uint32_t *oka = (uint32_t *)b.keyA, *okb = (uint32_t *)b.keyB;
             stage_order_kernel<uint32_t><<<order_blocks, 256, 0, s>>>(b.rank_rec, b.tile_sums, b.ent_first, b.ent_bseq, b.brank_of,
                                                                      b.head_pos, b.ent_key, W, E, fmax, freq_bits, oka, ova, b.rec,
@@ -1119,18 +1105,19 @@ int stage_impl(void *workspace, const uint64_t *d_align, int align_bits, const u
                uint64_t *n_buckets_out, unsigned long long *h_pinned4, hipStream_t s)
 {
     StageBufs b = carve(workspace, n, W, group_bits > 0);
-    if (group_bits > 0 && align_bits + group_bits <= 64) {
+    const StageSortPlan sp = stage_sort_plan(W, umi_len, align_bits, group_bits);
+    if (sp.combine) {
         // (alignment and group in one word: from here on the ordinary staging of a wider alignment key)
         stage_group_combine_kernel<<<grid_for(n), 256, 0, s>>>(d_align, align_bits, d_group, group_bits, n, b.gkey);
         d_align = b.gkey;
-        align_bits += group_bits;
-        group_bits = 0;
     }
-    if (group_bits <= 0) d_group = nullptr;
+    align_bits = sp.align_bits;
+    group_bits = sp.group_bits;
+    if (!sp.second_word) d_group = nullptr;
     const int umi_bits = 3 * umi_len;
-    const Pack5 p5 = pack5_of(W == 1 ? umi_len : 1);
-    const bool one_key = W == 1 && !d_group && align_bits + p5.bits <= 64; // the composed sort key fits a word
-    const int composed_bits = align_bits + p5.bits;
+    const Pack5 p5 = sp.p5;
+    const bool one_key = sp.one_key; // the composed sort key fits a word
+    const int composed_bits = sp.composed_bits;
     STAGE_TRY(hipMemsetAsync(b.counters, 0, SC_COUNT * 8, s));
     STAGE_TRY(hipMemsetAsync(b.bfirst, 0xFF, (size_t)n * 4, s)); // (a position per read at most)
     uint32_t *hist = nullptr;
