@@ -451,6 +451,31 @@ def test_edge_list_overflow_is_transparent():
         c.close()
 
 
+@pytest.mark.parametrize("seg_index", [0, 1])
+def test_edge_list_overflow_in_adjacency_mode(seg_index):
+    """Adjacency with max_freq >= 1 stays off the one-synchronisation path, so its overflow is the pair stage's own
+    retry: one bucket of ~2,100 UMIs over 6 free bases (some 9,700 pairs within k = 1, the list's floor is 1,024
+    entries), through the popcount tiles and through the segment index.  The first call does its pair work twice,
+    the second finds the grown list."""
+    import umi_collapse_rs_amd as umi
+    from umi_collapse_rs_amd import synth
+    bases = synth.uniform_reads(seed=8, n_reads=3000, umi_len=12)
+    bases[:, 6:] = 0
+    s = synth.stage(np.zeros(len(bases), dtype=np.int64), synth.bases_to_keys(bases))
+    keys, fr, off = s["keys"], s["freq"], s["bucket_off"]
+    c = umi.Context(0)
+    try:
+        c.set_option("seg_index", seg_index)
+        c.set_option("edge_capacity", 1)
+        st = check_against_oracle(c, keys, np.zeros_like(keys), fr, off, 12, 1, algo=1, amf=2)
+        assert st["n_edges"] > 1024
+        st2 = check_against_oracle(c, keys, np.zeros_like(keys), fr, off, 12, 1, algo=1, amf=2)
+        assert st2["n_edges"] == st["n_edges"] and st2["n_candidates"] == st["n_candidates"]
+        assert st["n_pair_launches"] > st2["n_pair_launches"] > 0
+    finally:
+        c.close()
+
+
 @pytest.mark.parametrize("spin", [0, 1])
 def test_end_of_call_seen_by_the_runtime_or_by_watching_pinned_memory(spin):
     """option spin_wait: the stream's last kernel writes a sequence word behind the control block in pinned

@@ -302,7 +302,7 @@ namespace umihip {
 int check_common(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, int k,
                  int algo, uint64_t *n_out, int max_len = UMI_MAX_UMI_LEN);
 
-// a whole batched call on stream s (lets a deferred call end first)
+// umihip_pipeline.cpp: a whole batched call on stream s (lets a deferred call end first)
 int run_pipeline(umi_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_nmask,
                  const int32_t *d_freq, const uint64_t *bucket_off, uint64_t n_buckets, uint32_t n,
                  int umi_len, int k, float percentage, int mode, int32_t adj_max_freq,

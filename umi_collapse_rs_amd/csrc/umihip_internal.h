@@ -1,4 +1,4 @@
-// Internal interface between the host side (umihip_api.cpp) and the gfx950
+// Internal interface between the host side (umihip_pipeline.cpp) and the gfx950
 // kernels (umihip_kernels.hip).  Not part of the C ABI.
 #pragma once
 

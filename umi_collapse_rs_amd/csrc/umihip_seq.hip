@@ -29,7 +29,7 @@
 // almost always differ elsewhere).  Integer / bitwise work, no MFMA.
 //
 // Edges go to the same list, in the same format, as every other pair kernel's; the collapse and the
-// finalisation behind it are the existing ones (EdgeCollapse, umihip_api.cpp).
+// finalisation behind it are the existing ones (EdgeCollapse, umihip_pipeline.cpp).
 #include <hip/hip_runtime.h>
 
 #include "umihip_internal.h"
