@@ -41,15 +41,18 @@ __global__ __launch_bounds__(256) void uf_union_kernel(const uint2 *__restrict__
 // (identity, then atomicMin) and comp[i] <= i (parents are smaller than children), so an entry that
 // is not the root of its set has lab[comp[i]] <= comp[i] < i and is not kept whatever its root is,
 // and a root is kept iff lab[i] == i: kept[i] = parent[i] == i && lab[i] == i, two streams over the
-// forest as the unions left it.  Only the endpoints of the one-way pairs need their roots: the first
-// round finds them by climbing (read only: no union runs behind the pair kernels in stream order) and
-// writes each pair back to its slot as (root of u, root of v); the rounds after it, the check and the
-// host's continuation read lab[] at the stored endpoints.
+// forest as the unions left it.  Only the endpoints of the one-way pairs need their roots: round 0
+// finds them by climbing (read only: no union runs behind the pair kernels in stream order) and
+// writes each pair to its place in the list as (root of u, root of v); the rounds after it, the check and
+// the host's continuation read lab[] at the stored endpoints.  Round 0 is the launch that gathers the
+// private slots (gather_resolve_hook_kernel): a slot's pair is resolved and hooked by the thread that
+// finds its place, not copied to the list by one launch and read back by the next.  lab[] is the identity
+// when it starts: the entry kernels store it beside label[] (prep_kernel, seg_count_lds_kernel).
 struct CollapseArgs {
     uint32_t *parent;       // in: the forest; out: comp[v] = root of v's set (flat; kept_only: left as it is)
     uint32_t *lab;          // lab[c] = smallest set that reaches set c along one-way pairs
     const uint2 *edges;     // the list (one-way pairs and, flagged, symmetric ones: skipped here);
-                            // kept_only: the resolving round rewrites the one-way pairs in place
+                            // kept_only: round 0 stores the one-way pairs as (root, root)
     uint32_t edge_cap;
     const RangeTask *ranges; // the entries the collapse covers (the fused kernel finished the others); null: all n
     uint32_t n_ranges, n;
@@ -108,63 +111,68 @@ __device__ __forceinline__ void flatten_entry(uint32_t *parent, uint32_t *lab, u
 // to 768 pairs are in tests/test_gpu_deep_chains.py.  Only as many blocks walk the list as it needs
 // (the count is on the device): the fewer waves, the more of a hot word's hooks meet in one wave's
 // registers.
-// Returns whether this thread saw a label to move.  Every lane of a wave makes the same trips.
 //
-// RESOLVE (kept_only's first round): the pair's endpoints are climbed to their roots in the unflattened
-// forest -- both climbs in one loop, two loads in flight per step; plain loads: the forest does not
-// change any more -- and the pair goes back to its own slot as (cu, cv) with one 8-byte store.  Flagged
-// entries and whatever lies at or beyond edge_cap are left alone.  A pair that is resolved a second time
-// stays what it is (a root is its own root).  PER_THREAD: the trips a thread makes when the list is
-// at least as long as the grid covers; each is a chain of dependent loads, and the climbs make it
-// long, so the resolving round spreads the list over more waves than the others.
-template <bool RESOLVE, uint32_t PER_THREAD>
-__device__ __forceinline__ bool one_way_round(const CollapseArgs &a)
+// The hook of one pair between the sets cu -> cv (live: this lane has a pair).  Returns whether the lane
+// saw a label to move.  Every lane of a wave calls it together, and makes the same trips.
+__device__ __forceinline__ bool hook_pair(const CollapseArgs &a, uint32_t cu, uint32_t cv, bool live, HotMin &hot)
+{
+    uint32_t lu = 0;
+    bool todo = false;
+    if (live) {
+        lu = a.lab[cu];
+        todo = lu < a.lab[cv];
+    }
+    wave_atomic_min(a.lab, cv, lu, todo, hot);
+    return todo;
+}
+
+// PER_THREAD: the trips a thread makes when the list is at least as long as the grid covers; each is a
+// chain of dependent loads.
+template <uint32_t PER_THREAD> __device__ __forceinline__ bool one_way_round(const CollapseArgs &a)
 {
     const uint32_t E = list_length(a);
     constexpr uint32_t PER_BLOCK = 256 * PER_THREAD;
     const uint32_t active = min(gridDim.x, (E + PER_BLOCK - 1) / PER_BLOCK);
     bool any = false;
     HotMin hot;
-    auto pair = [&](uint32_t e, uint2 uv) {
-        bool todo = false;
-        uint32_t cv = 0, lu = 0;
-        if (!(uv.x & SYM_FLAG)) {
-            uint32_t cu;
-            if (RESOLVE) {
-                cu = uv.x;
-                cv = uv.y;
-                uint32_t pu = a.parent[cu], pv = a.parent[cv];
-                while (pu != cu || pv != cv) {
-                    if (pu != cu) {
-                        cu = pu;
-                        pu = a.parent[cu];
-                    }
-                    if (pv != cv) {
-                        cv = pv;
-                        pv = a.parent[cv];
-                    }
-                }
-                const_cast<uint2 *>(a.edges)[e] = make_uint2(cu, cv);
-            } else if (a.kept_only) { // resolved by the round before
-                cu = uv.x;
-                cv = uv.y;
-            } else {
-                cu = a.parent[uv.x];
-                cv = a.parent[uv.y];
-            }
-            lu = a.lab[cu];
-            todo = lu < a.lab[cv];
-        }
-        any |= todo;
-        wave_atomic_min(a.lab, cv, lu, todo, hot);
-    };
     if (blockIdx.x < active)
         for (uint32_t e0 = blockIdx.x * blockDim.x; e0 < E; e0 += active * blockDim.x) {
             const uint32_t e = e0 + threadIdx.x;
-            pair(e, e < E ? a.edges[e] : make_uint2(SYM_FLAG, 0u));
+            const uint2 uv = e < E ? a.edges[e] : make_uint2(SYM_FLAG, 0u);
+            const bool live = !(uv.x & SYM_FLAG);
+            // kept_only: the list holds roots (resolve_hook_pair)
+            const uint32_t cu = !live ? 0u : a.kept_only ? uv.x : a.parent[uv.x];
+            const uint32_t cv = !live ? 0u : a.kept_only ? uv.y : a.parent[uv.y];
+            any |= hook_pair(a, cu, cv, live, hot);
         }
     hot_flush(a.lab, hot);
     return any;
+}
+
+// kept_only's round 0, pair by pair: the endpoints of uv are climbed to their roots in the unflattened
+// forest -- both climbs in one loop, two loads in flight per step; plain loads: the forest does not
+// change any more -- the pair goes to slot pos of the list as (cu, cv) with one 8-byte store, and the
+// roots are hooked.  A flagged uv (a symmetric pair of the list, or a lane without a pair) is left alone.
+// A pair that is resolved a second time stays what it is (a root is its own root).
+__device__ __forceinline__ bool resolve_hook_pair(const CollapseArgs &a, uint32_t pos, uint2 uv, HotMin &hot)
+{
+    const bool live = !(uv.x & SYM_FLAG);
+    uint32_t cu = uv.x, cv = uv.y;
+    if (live) {
+        uint32_t pu = a.parent[cu], pv = a.parent[cv];
+        while (pu != cu || pv != cv) {
+            if (pu != cu) {
+                cu = pu;
+                pu = a.parent[cu];
+            }
+            if (pv != cv) {
+                cv = pv;
+                pv = a.parent[cv];
+            }
+        }
+        const_cast<uint2 *>(a.edges)[pos] = make_uint2(cu, cv);
+    }
+    return hook_pair(a, cu, cv, live, hot);
 }
 
 // The same walk without a store: would a round still move a label?  (Rides in the finalize launch as
@@ -177,7 +185,7 @@ __device__ __forceinline__ bool one_way_check(const CollapseArgs &a, uint32_t fi
     for (uint32_t e = me * blockDim.x + threadIdx.x; e < E; e += n_blocks * blockDim.x) {
         const uint2 uv = a.edges[e];
         if (uv.x & SYM_FLAG) continue;
-        any |= a.kept_only ? a.lab[uv.x] < a.lab[uv.y] // (resolved: a resolving round always runs ahead of the check)
+        any |= a.kept_only ? a.lab[uv.x] < a.lab[uv.y] // (resolved: round 0 always runs ahead of the check)
                            : a.lab[a.parent[uv.x]] < a.lab[a.parent[uv.y]];
     }
     return any;
@@ -209,42 +217,59 @@ __device__ __forceinline__ unsigned int finalize_entry(const CollapseArgs &a, ui
 __global__ __launch_bounds__(256) void dag_flat_hook_kernel(CollapseArgs a, int round)
 {
     if (round > 0 && a.changed[round - 1] == 0) return;
-    if (one_way_round<false, 8>(a)) a.changed[round] = 1;
+    if (one_way_round<8>(a)) a.changed[round] = 1;
 }
 
-// kept_only's first round (always runs: the rounds and the check behind it read what it stores)
-constexpr uint32_t RESOLVE_PER_THREAD = 2;
-__global__ __launch_bounds__(256) void dag_resolve_hook_kernel(CollapseArgs a, int round)
+// The private slots to the list, GATHER_SLOTS slots per group (blocks behind the flatten pass's own, in
+// the same launch: was a scan kernel and a move kernel, 11 us).  A block scans its group's counts, adds up
+// the counts of the slots before the group itself (at most 4,096 words), and gives every edge of its
+// slots a position behind what the list holds; the last group says how many there were in all.  Nobody
+// writes CNT_EDGES meanwhile.  RESOLVE (kept_only): the edge does not go to its position as it is -- the
+// thread that would copy it resolves and hooks it there (resolve_hook_pair: the launch is round 0), and
+// sets changed[0] if a label moved.  An edge whose position lies at or beyond edge_cap is neither stored
+// nor hooked (the host sees the count and runs the call again).  The slots hold one-way pairs only.
+// n_sub blocks share a group, block `sub` taking every n_sub-th chunk of GATHER_CHUNK edges: a position of
+// uniform UMIs leaves a few hundred pairs per group, one chunk, and a block without a chunk ends behind
+// the scan of 64 counts; a clustered position leaves some thousand, and one block per group walked them
+// in four and more trips of dependent loads per thread (config 2m took 0.156 ms that way, 0.145 before).
+constexpr uint32_t GATHER_SLOTS = 64; // (a multiple of 64: GATHER_SLOTS / 64 slots per lane of the scan)
+constexpr uint32_t GATHER_CHUNK = 256 * 2; // two pairs per thread, as the list blocks' RESOLVE_PER_THREAD
+constexpr uint32_t GATHER_SPLIT = 8;       // blocks per group of the resolving launch
+template <bool RESOLVE>
+__device__ __forceinline__ void gather_private_edges(const CollapseArgs &a, uint32_t group, uint32_t sub, uint32_t n_sub)
 {
-    if (one_way_round<true, RESOLVE_PER_THREAD>(a)) a.changed[round] = 1;
-}
-
-// The private slots to the list, 64 slots per block (blocks behind the flatten pass's own, in the same
-// launch: was a scan kernel and a move kernel, 11 us).  A block adds up the counts of the slots before
-// its group itself (at most 4,096 words), scans its own 64, and moves its slots' edges behind what the
-// list holds; the last group says how many there were in all.  Nobody writes CNT_EDGES meanwhile.
-constexpr uint32_t GATHER_SLOTS = 64;
-__device__ __forceinline__ void gather_private_edges(const CollapseArgs &a, uint32_t group)
-{
+    constexpr uint32_t PER_LANE = GATHER_SLOTS / 64;
+    static_assert(GATHER_SLOTS % 64 == 0, "the scan deals whole slots to the first wave's lanes");
     __shared__ unsigned long long wsum[4];
     __shared__ uint32_t pre[GATHER_SLOTS + 1];
     const uint32_t s0 = group * GATHER_SLOTS, s1 = min(a.priv_blocks, s0 + GATHER_SLOTS);
-    unsigned long long before = 0;
-    for (uint32_t i = threadIdx.x; i < s0; i += blockDim.x) before += a.priv_cnt[i];
-    for (int o = 32; o > 0; o >>= 1) before += __shfl_down(before, o);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = before;
-    if (threadIdx.x < 64) { // the group's own counts, exclusive
-        const uint32_t c = s0 + threadIdx.x < s1 ? min(a.priv_cnt[s0 + threadIdx.x], SEG_PRIV_CAP) : 0u;
-        uint32_t incl = c;
+    if (threadIdx.x < 64) { // the group's own counts, exclusive: PER_LANE consecutive slots per lane
+        uint32_t c[PER_LANE], sum = 0;
+        unsigned long long cand = 0, direct = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < PER_LANE; q++) {
+            const uint32_t sl = s0 + threadIdx.x * PER_LANE + q;
+            c[q] = sl < s1 ? min(a.priv_cnt[sl], SEG_PRIV_CAP) : 0u;
+            sum += c[q];
+            if (a.priv_stat && sub == 0 && sl < s1) {
+                const uint2 st = a.priv_stat[sl];
+                cand += st.x;
+                direct += st.y;
+            }
+        }
+        uint32_t incl = sum;
         for (int o = 1; o < 64; o <<= 1) {
             const uint32_t up = __shfl_up(incl, o);
             if ((int)threadIdx.x >= o) incl += up;
         }
-        pre[threadIdx.x] = incl - c;
+        uint32_t run = incl - sum;
+#pragma unroll
+        for (uint32_t q = 0; q < PER_LANE; q++) {
+            pre[threadIdx.x * PER_LANE + q] = run;
+            run += c[q];
+        }
         if (threadIdx.x == 63) pre[GATHER_SLOTS] = incl;
-        if (a.priv_stat) { // the blocks' counts: two atomics per group instead of two per block
-            const uint2 st = s0 + threadIdx.x < s1 ? a.priv_stat[s0 + threadIdx.x] : make_uint2(0u, 0u);
-            unsigned long long cand = st.x, direct = st.y;
+        if (a.priv_stat && sub == 0) { // the blocks' counts: two atomics per group instead of two per block
             for (int o = 32; o > 0; o >>= 1) {
                 cand += __shfl_down(cand, o);
                 direct += __shfl_down(direct, o);
@@ -254,32 +279,83 @@ __device__ __forceinline__ void gather_private_edges(const CollapseArgs &a, uint
         }
     }
     __syncthreads();
+    const uint32_t total = pre[GATHER_SLOTS];
+    if (sub != 0 && sub * GATHER_CHUNK >= total) return; // (the whole block: no chunk of this group is its)
+    unsigned long long before = 0;
+    for (uint32_t i = threadIdx.x; i < s0; i += blockDim.x) before += a.priv_cnt[i];
+    for (int o = 32; o > 0; o >>= 1) before += __shfl_down(before, o);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = before;
+    __syncthreads();
     const unsigned long long first = a.counters[CNT_EDGES] + wsum[0] + wsum[1] + wsum[2] + wsum[3];
     uint2 *list = const_cast<uint2 *>(a.edges);
+    bool any = false;
+    HotMin hot;
     // a thread per edge of the group, its slot by bisection of pre[]: a slot holds a handful of edges, and a
     // wave that walks its sixteen slots one after the other makes sixteen dependent trips to memory (with
-    // the flatten's entry part gone from the launch, kept_only, it took 21 us that way and takes 16 so)
-    for (uint32_t t = threadIdx.x; t < pre[GATHER_SLOTS]; t += blockDim.x) {
-        uint32_t lo = 0, hi = GATHER_SLOTS; // pre[lo] <= t < pre[hi]
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (pre[mid] <= t) lo = mid;
-            else hi = mid;
+    // the flatten's entry part gone from the launch, kept_only, it took 21 us that way and takes 16 so).
+    // Whole blocks of threads make each trip (the hook is a wave's business), a lane past the end without a pair
+    for (uint32_t c0 = sub * GATHER_CHUNK; c0 < total; c0 += n_sub * GATHER_CHUNK)
+        for (uint32_t t0 = c0; t0 < min(total, c0 + GATHER_CHUNK); t0 += blockDim.x) {
+            const uint32_t t = t0 + threadIdx.x;
+            const unsigned long long pos = first + t;
+            uint2 uv = make_uint2(SYM_FLAG, 0u);
+            if (t < total && pos < a.edge_cap) {
+                uint32_t lo = 0, hi = GATHER_SLOTS; // pre[lo] <= t < pre[hi]
+                while (hi - lo > 1) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (pre[mid] <= t) lo = mid;
+                    else hi = mid;
+                }
+                uv = a.priv_edges[(size_t)(s0 + lo) * SEG_PRIV_CAP + (t - pre[lo])];
+                if (!RESOLVE) list[pos] = uv;
+            }
+            if (RESOLVE) any |= resolve_hook_pair(a, (uint32_t)pos, uv, hot);
         }
-        const unsigned long long pos = first + t;
-        if (pos < a.edge_cap) list[pos] = a.priv_edges[(size_t)(s0 + lo) * SEG_PRIV_CAP + (t - pre[lo])];
+    if (RESOLVE) {
+        hot_flush(a.lab, hot);
+        if (any) a.changed[0] = 1;
     }
-    if (s1 == a.priv_blocks && threadIdx.x == 0) a.counters[CNT_EDGES_MOVED] = first + pre[GATHER_SLOTS] - a.counters[CNT_EDGES];
+    if (s1 == a.priv_blocks && sub == 0 && threadIdx.x == 0) a.counters[CNT_EDGES_MOVED] = first + total - a.counters[CNT_EDGES];
 }
 
+// kept_only's round 0, one launch behind the unions: lab[] is the identity already (the entry kernels wrote
+// it beside label[]), parent[] is only read.  The first gather_blocks blocks take the private slots'
+// pairs (above: block b is block b / groups of group b % groups, so the blocks with the groups' first
+// chunks start first); the blocks behind them take what the pair kernels appended to the list themselves --
+// CNT_EDGES of them, not list_length(): CNT_EDGES_MOVED is written during this launch -- resolve them in
+// place and hook them, flagged entries skipped, only as many blocks active as that length needs
+// (RESOLVE_PER_THREAD pairs per thread: the climbs make a trip's chain of loads long, so the list is
+// spread over more waves than in the rounds that follow).  The rounds, the check and the
+// host's continuation behind this launch read lab[] at the stored roots.
+constexpr uint32_t RESOLVE_PER_THREAD = 2;
+__global__ __launch_bounds__(256) void gather_resolve_hook_kernel(CollapseArgs a, uint32_t gather_blocks)
+{
+    if (blockIdx.x < gather_blocks) {
+        const uint32_t groups = gather_blocks / GATHER_SPLIT;
+        gather_private_edges<true>(a, blockIdx.x % groups, blockIdx.x / groups, GATHER_SPLIT);
+        return;
+    }
+    const unsigned long long ne = a.counters[CNT_EDGES];
+    const uint32_t E = ne < a.edge_cap ? (uint32_t)ne : a.edge_cap;
+    constexpr uint32_t PER_BLOCK = 256 * RESOLVE_PER_THREAD;
+    const uint32_t me = blockIdx.x - gather_blocks, active = min(gridDim.x - gather_blocks, (E + PER_BLOCK - 1) / PER_BLOCK);
+    if (me >= active) return;
+    bool any = false;
+    HotMin hot;
+    for (uint32_t e0 = me * blockDim.x; e0 < E; e0 += active * blockDim.x) {
+        const uint32_t e = e0 + threadIdx.x;
+        any |= resolve_hook_pair(a, e, e < E ? a.edges[e] : make_uint2(SYM_FLAG, 0u), hot);
+    }
+    hot_flush(a.lab, hot);
+    if (any) a.changed[0] = 1;
+}
+
+// the with-root path: comp[] flat and lab[] = identity by the entry blocks, the private slots moved to the
+// list by the blocks behind them
 __global__ __launch_bounds__(256) void uf_flatten_kernel(CollapseArgs a, uint32_t entry_blocks)
 {
     if (blockIdx.x >= entry_blocks) {
-        gather_private_edges(a, blockIdx.x - entry_blocks);
-        return;
-    }
-    if (a.kept_only) { // lab[] = identity and nothing else: parent[] is neither read nor written
-        collapse_entries(a, entry_blocks, [&](uint32_t i) { a.lab[i] = i; });
+        gather_private_edges<false>(a, blockIdx.x - entry_blocks, 0, 1);
         return;
     }
     if (a.ranges) {
@@ -418,21 +494,22 @@ hipError_t launch_control_to_host(const void *d_ctrl, void *h_ctrl, size_t bytes
 
 hipError_t launch_collapse_flatten(const CollapseDesc &d, hipStream_t s)
 {
+    const uint32_t gather_blocks = d.priv_blocks ? (d.priv_blocks + GATHER_SLOTS - 1) / GATHER_SLOTS : 0u;
+    if (d.kept_only) { // round 0 in the same launch: the slots' pairs where they are gathered, the list's in place
+        const uint32_t list_blocks = grid_of(d.edge_cap, 256 * RESOLVE_PER_THREAD, 4096 / RESOLVE_PER_THREAD);
+        gather_resolve_hook_kernel<<<gather_blocks * GATHER_SPLIT + list_blocks, 256, 0, s>>>(collapse_args(d), gather_blocks * GATHER_SPLIT);
+        return hipGetLastError();
+    }
     const bool entries = !(d.n == 0 || (d.ranges && d.n_ranges == 0));
     const uint32_t entry_blocks = entries ? entries_grid(d, 4096) : 0u;
-    const uint32_t gather_blocks = d.priv_blocks ? (d.priv_blocks + GATHER_SLOTS - 1) / GATHER_SLOTS : 0u;
     if (entry_blocks + gather_blocks == 0) return hipSuccess;
     uf_flatten_kernel<<<entry_blocks + gather_blocks, 256, 0, s>>>(collapse_args(d), entry_blocks);
     return hipGetLastError();
 }
 
-hipError_t launch_collapse_round(const CollapseDesc &d, int round, hipStream_t s, bool resolve)
+hipError_t launch_collapse_round(const CollapseDesc &d, int round, hipStream_t s)
 {
-    if (resolve && d.kept_only)
-        dag_resolve_hook_kernel<<<grid_of(d.edge_cap, 256 * RESOLVE_PER_THREAD, 4096 / RESOLVE_PER_THREAD), 256, 0, s>>>(
-            collapse_args(d), round);
-    else
-        dag_flat_hook_kernel<<<grid_of(d.edge_cap, 256 * 8, 512), 256, 0, s>>>(collapse_args(d), round);
+    dag_flat_hook_kernel<<<grid_of(d.edge_cap, 256 * 8, 512), 256, 0, s>>>(collapse_args(d), round);
     return hipGetLastError();
 }
 

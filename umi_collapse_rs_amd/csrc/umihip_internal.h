@@ -266,6 +266,7 @@ struct SegArgs {
     const int32_t *prep_freq;
     int32_t *prep_thr;
     uint32_t *prep_label;
+    uint32_t *prep_lab;     // lab[i] = i beside label[i] = i (may be null: the collapse's flatten pass writes lab[])
     float prep_percentage;
     unsigned long long *prep_counters;
     int umi_len;            // (keys of several words: 21, the bases of the first word the filter keys hold)
@@ -583,12 +584,14 @@ struct CollapseDesc {
     uint32_t n_ranges, n;
     uint8_t *kept;
     uint32_t *root;
-    bool kept_only = false;  // root is null and only kept[] is wanted: no flatten; the first round resolves the one-way
-                             // pairs' endpoints to roots in place, finalize reads parent[i] and lab[i] only
+    bool kept_only = false;  // root is null and only kept[] is wanted: no flatten; round 0 (the flatten launch) resolves
+                             // the one-way pairs' endpoints to roots, finalize reads parent[i] and lab[i] only.  lab[] must
+                             // be the identity over the entries when the collapse starts (launch_prep, SegArgs::prep_lab)
     unsigned long long *counters;
     uint32_t *changed;       // the rounds' flags in the control block
     // what the segment index's pair kernel left in its blocks' private slots (one-way pairs only: the
-    // symmetric ones were united where they were found); the flatten launch appends them to the list
+    // symmetric ones were united where they were found); the flatten launch appends them to the list (kept_only: as
+    // (root, root), hooked on the way)
     const uint2 *priv_edges = nullptr; // [priv_blocks * SEG_PRIV_CAP]
     const uint32_t *priv_cnt = nullptr;
     const uint2 *priv_stat = nullptr; // (candidates, united pairs) of each such block (null: counted already)
@@ -598,12 +601,13 @@ struct CollapseDesc {
 // h_seq (pinned, may be null): set to seq once the block has arrived
 hipError_t launch_control_to_host(const void *d_ctrl, void *h_ctrl, size_t bytes, hipStream_t s,
                                   unsigned long long *h_seq = nullptr, unsigned long long seq = 0);
-// ... phase by phase: comp[v] = root of v in place and lab[v] = v (kept_only: lab[v] = v alone); round `round`
-// along the one-way pairs (a no-op once round - 1 was quiet); label = lab[comp[v]], kept, root, survivors
+// ... phase by phase: comp[v] = root of v in place and lab[v] = v; round `round` along the one-way pairs (a no-op
+// once round - 1 was quiet); label = lab[comp[v]], kept, root, survivors.
+// kept_only: the flatten launch is round 0 -- every one-way pair, in a private slot or in the list, resolved to
+// (root, root) at its place in the list and hooked, changed[0] set if a label moved -- and the rounds behind it
+// start at 1.
 hipError_t launch_collapse_flatten(const CollapseDesc &d, hipStream_t s);
-// resolve (kept_only; ignored otherwise): this round also rewrites the one-way pairs as (root, root).  The first
-// round behind launch_collapse_flatten must; a later one that does is harmless (a root resolves to itself)
-hipError_t launch_collapse_round(const CollapseDesc &d, int round, hipStream_t s, bool resolve = false);
+hipError_t launch_collapse_round(const CollapseDesc &d, int round, hipStream_t s);
 // check_round >= 0: blocks of their own look, without a store, whether round check_round would still
 // move a label (changed[check_round])
 hipError_t launch_collapse_finalize(const CollapseDesc &d, hipStream_t s, int check_round = -1);

@@ -230,6 +230,14 @@ class Pipeline {
     }
     // the forest of the unions is the result (MODE_CLUSTER) or the first phase of it (MODE_DIRECTIONAL)
     bool unions_collapse() const { return mode == MODE_DIRECTIONAL || mode == MODE_CLUSTER; }
+    // the call's collapse is the mask-only directional one (CollapseDesc::kept_only): its round 0 has no entry pass,
+    // so lab[] = identity is the entry kernels' to store
+    bool mask_only_collapse() const { return d_root == nullptr && ctx->collapse_kept_only; }
+    // (asked before the development build's tiles are cut: every call that may still turn out one_sync())
+    uint32_t *prep_lab() const
+    {
+        return mode == MODE_DIRECTIONAL && n_parts == 1 && ctx->two_phase == 2 && mask_only_collapse() ? ctx->lab.as<uint32_t>() : nullptr;
+    }
 
     int run_stages()
     {
@@ -580,6 +588,7 @@ class Pipeline {
             HIP_TRY(launch_edit_prep(d_keys, d_nmask, d_freq, d_boff(), n_buckets, n, umi_len, percentage,
                                      ctx->fkey.as<uint64_t>(), ctx->planes.as<uint32_t>(), ctx->thr.as<int32_t>(),
                                      ctx->label.as<uint32_t>(), d_cnt, s));
+            if (prep_lab()) HIP_TRY(launch_iota(prep_lab(), n, s)); // (that entry kernel knows no lab[])
             return UMI_OK;
         }
         // With the LDS counting sort the segments' entries are prepared by its count kernel; the
@@ -592,6 +601,7 @@ class Pipeline {
             seg.prep_freq = d_freq;
             seg.prep_thr = ctx->thr.as<int32_t>();
             seg.prep_label = ctx->label.as<uint32_t>();
+            seg.prep_lab = prep_lab();
             seg.prep_percentage = percentage;
             seg.prep_counters = d_cnt;
         }
@@ -599,7 +609,7 @@ class Pipeline {
         for (const RangeTask &r : pl.ranges) other_ranges = other_ranges || r.seg == SEG_NONE;
         HIP_TRY(launch_prep(d_keys, d_nmask, d_freq, d_boff(), n_buckets, d_ranges,
                             (uint32_t)pl.ranges.size(), n, fused_max, plan_umi_len(), percentage, key32, ctx->fkey.p,
-                            ctx->thr.as<int32_t>(), ctx->label.as<uint32_t>(), nullptr, d_cnt,
+                            ctx->thr.as<int32_t>(), ctx->label.as<uint32_t>(), prep_lab(), d_cnt,
                             seg.n_chunks && !seg.blocks ? d_segs : nullptr, pl.seg_parts, seg.bin_cnt, s, fold,
                             !fold || other_ranges, std::max({ctx->seg_min, fused_max + 1, 1u}), n_words, umi_len));
         return UMI_OK;
@@ -1018,7 +1028,7 @@ class Pipeline {
         d.root = d_root;
         // (label[] then holds the unflattened forest when the call ends: nobody reads it across calls, every
         // call's prep / launch_iota writes its entries afresh)
-        d.kept_only = d_root == nullptr && ctx->collapse_kept_only;
+        d.kept_only = mask_only_collapse();
         d.counters = d_cnt;
         d.changed = ctx->d_changed();
         if (priv_blocks_for_collapse) {
@@ -1086,6 +1096,7 @@ class Pipeline {
             HIP_TRY(hipMemsetAsync(&d_cnt[CNT_UF_DIRECT], 0, 2 * sizeof(unsigned long long), s));
             if (!cluster) HIP_TRY(hipMemsetAsync(ctx->d_changed(), 0, CTRL_BYTES - CTRL_FLAGS_OFF, s)); // flags and sync words
             HIP_TRY(launch_iota(d_label, n, s)); // (the fused buckets' entries are finished: their labels are free)
+            if (prep_lab()) HIP_TRY(launch_iota(prep_lab(), n, s)); // (the attempt's round 0 has lowered it)
         }
         st.n_edges = n_edges + n_direct;
         if (cluster)
@@ -1102,9 +1113,10 @@ class Pipeline {
         HIP_TRY(launch_collapse_flatten(cd, s));
         // (the last of them as a check beside the finalize pass: in the common case it would change
         // nothing, and the kept mask stands)
-        // (kept_only: round 0 resolves the one-way pairs' endpoints for the rounds and the check behind it)
+        // (kept_only: the flatten launch is round 0 -- it resolves the one-way pairs' endpoints for the rounds
+        // and the check behind it)
         static_assert(DAG_ROUNDS >= 2, "the check beside finalize needs a resolving round ahead of it");
-        for (int r = 0; r < ahead - 1; r++) HIP_TRY(launch_collapse_round(cd, r, s, r == 0));
+        for (int r = cd.kept_only ? 1 : 0; r < ahead - 1; r++) HIP_TRY(launch_collapse_round(cd, r, s));
         HIP_TRY(launch_collapse_finalize(cd, s, ahead - 1));
         return UMI_OK;
     }

@@ -326,6 +326,7 @@ __global__ __launch_bounds__(SEG_BLOCK_THREADS) void seg_count_lds_kernel(SegArg
             const int32_t f = g.prep_freq[i];
             g.prep_thr[i] = threshold_of(g.prep_percentage, f);
             g.prep_label[i] = i;
+            if (g.prep_lab) g.prep_lab[i] = i; // (the mask-only collapse starts from it: its round 0 has no entry pass)
             const uint64_t k3 = key & ~nm & (g.umi_len >= 21 ? 0x7FFFFFFFFFFFFFFFull : ((1ull << (3 * g.umi_len)) - 1ull));
             store_filter_key(fkey, i, k3, g.umi_len);
             bad += f < 1 ? 1u : 0u;
