@@ -6,7 +6,10 @@ include/umihip.h promises: any other call that needs the context's workspace fir
 call end, whose result then waits for umi_dedup_batch_end (a second begin replaces it); d_kept /
 d_root of the pending call are final in stream order.  Each intervening call X here gets inputs of
 its own and is checked against its own reference, on the pending call's stream and on another one;
-the pending call's outputs, stats and contract verdict are checked after end."""
+the pending call's outputs, stats and contract verdict are checked after end.
+
+Also here: one context taken through every family of host-buffer calls at changing sizes, each result
+compared with the same call on a context of its own."""
 import ctypes as C
 
 import numpy as np
@@ -677,6 +680,157 @@ def _without_n(umi_len):
         assert not m.any()
         keys.append(k); nm.append(m); fr.extend(freq[j] for j in order); off.append(off[-1] + len(umis))
     return np.concatenate(keys), np.concatenate(nm), np.array(fr, np.int32), np.array(off, np.uint64)
+
+
+# ---- one context, every family of host-buffer calls in turn ----------------------------------------------
+# The host-buffer forms lay their arrays into one staging block of the context, afresh per call, and the
+# single-shot device forms share one workspace.  So: the calls below in a row on one context, with about 300
+# items each, then about 70,000 (the block and the workspace grow, every offset moves), then about 300 again
+# (small calls inside a large block), arrays that a call may leave out coming and going.  Every result is,
+# byte for byte, that of the same call on a context of its own.
+
+def _mix_bam_case(rng, n_clusters):
+    """test_gpu_consensus_bam's mixed case with the voters drawn from a pool of families (a family per read
+    would take seconds at 70,000 reads)"""
+    from test_gpu_consensus_bam import Case, family
+    from umi_collapse_rs_amd._lib import UMI_NO_CLUSTER
+    lengths = (36, 75, 100, 151)
+    pool = {L: [family(rng, L, 25, odd_codes=0.02) for _ in range(8)] for L in lengths}
+    reads, clen = [], []
+    for c in range(n_clusters):
+        L = int(lengths[int(rng.integers(0, 4))])
+        clen.append(L)
+        if c % 97 == 5:
+            continue  # a cluster without a voter
+        fam = pool[L][int(rng.integers(0, 8))]
+        for j in rng.integers(0, 25, int(rng.geometric(0.25))):
+            reads.append(fam[int(j)] + (L, c))
+    for _ in range(len(reads) // 9):  # reads that vote nowhere
+        L = int(lengths[int(rng.integers(0, 4))])
+        reads.append(pool[L][0][int(rng.integers(0, 25))] + (L, UMI_NO_CLUSTER))
+    order = rng.permutation(len(reads))
+    return Case([reads[i] for i in order], clen)
+
+
+def _mix_inputs(seed, n, batch_a=None):
+    """the inputs of every call of the sequence, about n items each, from the generators of the calls' own tests"""
+    import barcode_model as bm
+    import barcode_multi_model as mm
+    from umi_collapse_rs_amd import synth
+    rng = np.random.default_rng(seed)
+    inp = dict(a=batch_a if batch_a is not None else staged(rng, n, max(1, n // 25), n_frac=0.002, sort=True),
+               plain=staged(rng, n, max(1, n // 25)))  # (no N: a call without nmask)
+    assert inp["a"][1].any() and not inp["plain"][1].any()
+    wl, pairs = bm.random_list(rng, 5003, 16)
+    inp["bc"] = (wl,) + mm.multi_reads(rng, wl, n, pairs)
+    inp["stage"] = stage_input(seed + 1, n, 24)
+    inp["bam"] = _mix_bam_case(rng, max(1, n // 4))
+    nb = len(inp["a"][3]) - 1
+    inp["rowcol"] = (rng.integers(0, 700, nb).astype(np.uint32), rng.integers(0, 90, nb).astype(np.uint32))
+    few = min(n, 10000)  # (the generator takes a loop per read: a file of 10,000 reads, then the same again)
+    seqs, quals = synth.fastq_reads(seed + 2, few, max(1, few // 3), lengths=[30, 100, 151], err=0.01, n_frac=0.002)
+    inp["fastq"] = (seqs * (n // few), quals * (n // few))
+    return inp
+
+
+# every step: (context, inputs, the earlier results of this run) -> result
+def _m_dedup(c, i, r):
+    keys, nm, fr, off = i["a"]
+    kept, root, st = c.dedup_batch(keys, nm, fr, off, L, k=1)
+    return kept, root, st["n_kept"], st["n_umis"]
+
+
+def _m_barcodes(c, i, r):
+    wl, reads, quals = i["bc"]
+    return c.correct_barcodes_multi(reads, quals, 16, wl)
+
+
+def _m_stage(c, i, r):
+    align, group, umis, score = i["stage"]
+    return c.stage_reads_grouped_wide(align, group, umis, score, 24, merge=1, group_key_bits=8)
+
+
+def _m_bam(c, i, r):
+    case = i["bam"]
+    return c.consensus_bam(case.data, case.seq_pos, case.qual_pos, case.lens, case.cluster, case.clen, want_disagree=True)
+
+
+def _m_count(c, i, r):
+    return c.count_matrix(r["dedup"][0], i["a"][2], i["a"][3], i["rowcol"][0], i["rowcol"][1], 700, 90)
+
+
+def _m_stats(c, i, r):
+    keys, _, fr, off = i["a"]
+    return c.dedup_stats(keys, fr, r["dedup"][0], r["dedup"][1], off, L, seed=7, hist_bins=4096, per_umi=True)
+
+
+def _m_stage_seqs(c, i, r):
+    return c.stage_seqs(i["fastq"][0], i["fastq"][1], merge=1)
+
+
+def _m_dedup_seqs(c, i, r):
+    st = r["stage_seqs"]
+    kept, root, _ = c.dedup_seqs(st["keys"], st["nmask"] if st["any_n"] else None, st["freq"], st["bucket_off"],
+                                 st["bucket_len"], k=1)
+    return kept, root
+
+
+def _m_consensus(c, i, r):
+    return c.consensus_seqs(i["fastq"][0], i["fastq"][1], r["stage_seqs"], r["dedup_seqs"][0], r["dedup_seqs"][1])
+
+
+def _m_dedup_plain(c, i, r):
+    keys, _, fr, off = i["plain"]
+    kept, root, st = c.dedup_batch(keys, None, fr, off, L, k=1, want_root=False)
+    assert root is None
+    return kept, st["n_kept"]
+
+
+MIX = [("dedup", _m_dedup), ("barcodes_multi", _m_barcodes), ("stage_reads_grouped_wide", _m_stage),
+       ("consensus_bam", _m_bam), ("count_matrix", _m_count), ("dedup_stats", _m_stats), ("stage_seqs", _m_stage_seqs),
+       ("dedup_seqs", _m_dedup_seqs), ("consensus_seqs", _m_consensus), ("dedup_plain", _m_dedup_plain)]
+
+
+def _blob(x):
+    """a result as nested tuples of bytes"""
+    if isinstance(x, dict):
+        return tuple((k, _blob(x[k])) for k in sorted(x))
+    if isinstance(x, (list, tuple)):
+        return tuple(_blob(v) for v in x)
+    if isinstance(x, np.ndarray):
+        return (str(x.dtype), x.shape, x.tobytes())
+    return x
+
+
+def _mix_run(inp, ctx_of):
+    """the sequence, step s on the context ctx_of(s) gives; every step sees this run's earlier results"""
+    res = {}
+    for name, step in MIX:
+        c, done = ctx_of(name)
+        try:
+            res[name] = step(c, inp, res)
+        finally:
+            done(c)
+    return res
+
+
+def test_one_context_across_every_family_while_the_staging_block_grows_and_shrinks(batches):
+    import umi_collapse_rs_amd as umi
+    small, large = _mix_inputs(3001, 300), _mix_inputs(3002, 70000, batch_a=batches["a"])
+    assert 200 <= len(small["a"][0]) <= 300 and len(large["a"][0]) >= 50000 and len(large["bam"].lens) >= 60000
+    alone = {}
+    for size, inp in (("small", small), ("large", large)):  # every call on a context of its own
+        alone[size] = _mix_run(inp, lambda name: (umi.Context(0), lambda c: c.close()))
+        assert alone[size]["stage_seqs"]["any_n"] and len(alone[size]["count_matrix"][0]) > 5
+        assert len(alone[size]["dedup_stats"]["umi_entry"]) > 100 and (alone[size]["barcodes_multi"]["counts"][:4] > 0).all()
+    shared = umi.Context(0)
+    try:
+        for size, inp in (("small", small), ("large", large), ("small", small)):
+            got = _mix_run(inp, lambda name: (shared, lambda c: None))
+            for name, _ in MIX:
+                assert _blob(got[name]) == _blob(alone[size][name]), (size, name)
+    finally:
+        shared.close()
 
 
 # ---- the multi-device call's error exit --------------------------------------------------------------

@@ -5,6 +5,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <deque>
 #include <thread>
 
 using namespace umihip;
@@ -125,40 +126,33 @@ int dedup_batch_split(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask,
     const int mode = mode_of(algo);
     std::vector<ShardResult> res(n_dev);
     std::vector<uint64_t> n_edges(n_dev, 0);
+    // every device gets the whole input; the first one's block holds kept and root as well (the collapse below)
+    std::deque<HostIo> io;
+    IoPtr<uint8_t> d_kept;
+    IoPtr<uint32_t> d_root;
     std::vector<std::thread> pool;
-    for (uint32_t r = 0; r < n_dev; r++)
-        pool.emplace_back([&, r] {
-            umi_ctx *sub = ctx->subs[r];
+    for (umi_ctx *sub : ctx->subs) io.emplace_back(sub);
+    for (uint32_t r = 0; r < n_dev; r++) {
+        HostIo *my = &io[r];
+        const auto d_keys = my->in(keys, n * 8), d_nmask = my->in(nmask, n * 8);
+        const auto d_freq = my->in(freq, n * 4);
+        if (r == 0) {
+            d_kept = my->out(kept, n);
+            d_root = my->out(root, n * 4);
+        }
+        pool.emplace_back([&, r, my, d_keys, d_nmask, d_freq] {
             ShardResult &out = res[r];
-            auto fail_here = [&](int rc) {
-                out.rc = rc;
-                out.err = umi_last_error();
-            };
             memset(&out.st, 0, sizeof(out.st));
-            if (hipSetDevice(sub->device) != hipSuccess) {
-                out.rc = UMI_ERR_HIP;
-                out.err = "hipSetDevice failed on a worker thread";
-                return;
-            }
-            settle(sub); // (a deferred call owns the workspace until its end has been seen)
             int rc;
-            if ((rc = sub->in_keys.reserve(n * 8)) || (rc = sub->in_freq.reserve(n * 4)) ||
-                (nmask && (rc = sub->in_nmask.reserve(n * 8))))
-                return fail_here(rc);
-            hipStream_t s = sub->own_stream;
-            hipError_t e = hipMemcpyAsync(sub->in_keys.p, keys, n * 8, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(sub->in_freq.p, freq, n * 4, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess && nmask) e = hipMemcpyAsync(sub->in_nmask.p, nmask, n * 8, hipMemcpyHostToDevice, s);
-            if (e != hipSuccess) {
-                out.rc = UMI_ERR_HIP;
-                out.err = std::string("upload failed: ") + hipGetErrorString(e);
-                return;
+            if ((rc = my->open()) ||
+                (rc = run_pipeline_part(ctx->subs[r], d_keys, d_nmask, d_freq, bucket_off, n_buckets, (uint32_t)n, umi_len, k,
+                                        percentage, mode, adj_max_freq, my->stream(), r, n_dev, &out.st, &n_edges[r]))) {
+                out.rc = rc;
+                out.err = umi_last_error(); // (this thread's message)
             }
-            if ((rc = run_pipeline_part(sub, sub->in_keys.as<uint64_t>(), nmask ? sub->in_nmask.as<uint64_t>() : nullptr,
-                                        sub->in_freq.as<int32_t>(), bucket_off, n_buckets, (uint32_t)n, umi_len, k,
-                                        percentage, mode, adj_max_freq, s, r, n_dev, &out.st, &n_edges[r])))
-                return fail_here(rc);
+            if (rc || r) (void)my->close(); // (here, where its device is current; the first one's stays open for the collapse)
         });
+    }
     for (auto &t : pool) t.join();
     for (uint32_t r = 0; r < n_dev; r++)
         if (res[r].rc) return fail(res[r].rc, "device %d: %s", ctx->subs[r]->device, res[r].err.c_str());
@@ -170,8 +164,7 @@ int dedup_batch_split(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask,
     if (total >= 0x7FFFFFF0ull) return fail(UMI_ERR_NOMEM, "gathered edge list too large");
     HIP_TRY(hipSetDevice(c0->device));
     int rc;
-    if ((rc = c0->out_kept.reserve(n)) || (rc = c0->out_root.reserve(n * 4))) return rc;
-    DevBuf gathered; // (freed on leaving: after the collapse and the blocking downloads behind it)
+    DevBuf gathered; // (freed on leaving: after the collapse and the downloads behind it have been waited for)
     if ((rc = gathered.reserve(std::max<uint64_t>(total, 1) * sizeof(uint2)))) return rc;
     uint64_t at = 0;
     hipError_t e = hipSuccess;
@@ -187,14 +180,9 @@ int dedup_batch_split(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask,
     if (e != hipSuccess) return fail(UMI_ERR_HIP, "edge gather failed: %s", hipGetErrorString(e));
     umi_stats st;
     memset(&st, 0, sizeof(st));
-    rc = collapse_edges(c0, (uint32_t)n, gathered.as<uint2>(), (uint32_t)total, mode, c0->out_kept.as<uint8_t>(),
-                        root ? c0->out_root.as<uint32_t>() : nullptr, c0->own_stream, &st);
-    if (rc == UMI_OK) {
-        e = hipMemcpy(kept, c0->out_kept.p, n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && root) e = hipMemcpy(root, c0->out_root.p, n * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(UMI_ERR_HIP, "download failed: %s", hipGetErrorString(e));
-    }
-    if (rc) return rc;
+    if ((rc = collapse_edges(c0, (uint32_t)n, gathered.as<uint2>(), (uint32_t)total, mode, d_kept, d_root, c0->own_stream, &st)) ||
+        (rc = io[0].fetch(kept, d_kept, n)) || (rc = io[0].fetch(root, d_root, n)) || (rc = io[0].close()))
+        return rc;
     if (stats) {
         umi_stats total_st = res[0].st;
         for (uint32_t r = 1; r < n_dev; r++) merge_stats(total_st, res[r].st);
@@ -258,6 +246,26 @@ int dedup_batch_multi(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask,
     return UMI_OK;
 }
 
+// a checked, non-empty call on one device: its arrays staged, the pipeline, kept and root back
+int dedup_batch_staged(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask, const int32_t *freq,
+                       const uint64_t *bucket_off, uint64_t n_buckets, uint64_t n, int umi_len, int k, float percentage,
+                       int algo, int32_t adj_max_freq, uint8_t *kept, uint32_t *root, umi_stats *stats, int n_words, bool edit)
+{
+    const size_t kb = (size_t)n * 8 * (size_t)n_words;
+    HostIo io(ctx);
+    const auto d_keys = io.in(keys, kb), d_nmask = io.in(nmask, kb);
+    const auto d_freq = io.in(freq, n * 4);
+    const auto d_kept = io.out(kept, n);
+    const auto d_root = io.out(root, n * 4);
+    int rc;
+    if ((rc = io.open()) ||
+        (rc = run_pipeline(ctx, d_keys, d_nmask, d_freq, bucket_off, n_buckets, (uint32_t)n, umi_len, k, percentage,
+                           mode_of(algo), adj_max_freq, d_kept, d_root, io.stream(), stats, nullptr, n_words, false, edit)) ||
+        (rc = io.fetch(kept, d_kept, n)) || (rc = io.fetch(root, d_root, n)))
+        return rc;
+    return io.close();
+}
+
 int dedup_batch_single(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask, const int32_t *freq,
                     const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, int k,
                     float percentage, int algo, int32_t adj_max_freq, uint8_t *kept, uint32_t *root,
@@ -274,29 +282,9 @@ int dedup_batch_single(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask
         }
         return UMI_OK;
     }
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t kb = (size_t)n * 8 * (size_t)n_words;
-    if ((rc = ctx->in_keys.reserve(kb)) || (rc = ctx->in_freq.reserve(n * 4)) ||
-        (rc = ctx->out_kept.reserve(n)) || (rc = ctx->out_root.reserve(n * 4)))
-        return rc;
-    if (nmask && (rc = ctx->in_nmask.reserve(kb))) return rc;
-    hipStream_t s = ctx->own_stream;
-    HIP_TRY(hipMemcpyAsync(ctx->in_keys.p, keys, kb, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ctx->in_freq.p, freq, n * 4, hipMemcpyHostToDevice, s));
-    if (nmask) HIP_TRY(hipMemcpyAsync(ctx->in_nmask.p, nmask, kb, hipMemcpyHostToDevice, s));
-    rc = run_pipeline(ctx, ctx->in_keys.as<uint64_t>(),
-                      nmask ? ctx->in_nmask.as<uint64_t>() : nullptr, ctx->in_freq.as<int32_t>(),
-                      bucket_off, n_buckets, (uint32_t)n, umi_len, k, percentage,
-                      mode_of(algo),
-                      adj_max_freq, ctx->out_kept.as<uint8_t>(),
-                      root ? ctx->out_root.as<uint32_t>() : nullptr, s, stats, nullptr, n_words);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(kept, ctx->out_kept.p, n, hipMemcpyDeviceToHost, s));
-    if (root) HIP_TRY(hipMemcpyAsync(root, ctx->out_root.p, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return UMI_OK;
+    return dedup_batch_staged(ctx, keys, nmask, freq, bucket_off, n_buckets, n, umi_len, k, percentage, algo, adj_max_freq,
+                              kept, root, stats, n_words, false);
 }
-
 
 } // namespace
 
@@ -564,25 +552,8 @@ int umi_dedup_batch_edit(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nma
         }
         return UMI_OK;
     }
-    settle(ctx); // (the staging buffers below are the deferred call's as well)
-    HIP_TRY(hipSetDevice(ctx->device));
-    if ((rc = ctx->in_keys.reserve(n * 8)) || (rc = ctx->in_freq.reserve(n * 4)) || (rc = ctx->out_kept.reserve(n)) ||
-        (rc = ctx->out_root.reserve(n * 4)) || (nmask && (rc = ctx->in_nmask.reserve(n * 8))))
-        return rc;
-    hipStream_t s = ctx->own_stream;
-    HIP_TRY(hipMemcpyAsync(ctx->in_keys.p, keys, n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ctx->in_freq.p, freq, n * 4, hipMemcpyHostToDevice, s));
-    if (nmask) HIP_TRY(hipMemcpyAsync(ctx->in_nmask.p, nmask, n * 8, hipMemcpyHostToDevice, s));
-    rc = run_pipeline(ctx, ctx->in_keys.as<uint64_t>(), nmask ? ctx->in_nmask.as<uint64_t>() : nullptr,
-                      ctx->in_freq.as<int32_t>(), bucket_off, n_buckets, (uint32_t)n, umi_len, k, percentage,
-                      mode_of(algo), adj_max_freq,
-                      ctx->out_kept.as<uint8_t>(), root ? ctx->out_root.as<uint32_t>() : nullptr, s, stats, nullptr, 1,
-                      false, true);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(kept, ctx->out_kept.p, n, hipMemcpyDeviceToHost, s));
-    if (root) HIP_TRY(hipMemcpyAsync(root, ctx->out_root.p, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return UMI_OK;
+    return dedup_batch_staged(ctx, keys, nmask, freq, bucket_off, n_buckets, n, umi_len, k, percentage, algo, adj_max_freq,
+                              kept, root, stats, 1, true);
 }
 
 int umi_dedup_batch_device_begin(umi_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_nmask, const int32_t *d_freq,

@@ -40,10 +40,10 @@ int corr_run(umi_ctx *ctx, const uint8_t *d_umi_ascii, uint64_t n_reads, int umi
              uint8_t *d_second, uint64_t counts[3], hipStream_t s)
 {
     int rc;
-    if ((rc = ctx->corr_ws.reserve(correct_workspace_bytes(n_wl, umi_len)))) return rc;
+    if ((rc = ctx->call_ws.reserve(correct_workspace_bytes(n_wl, umi_len)))) return rc;
     uint64_t bad_read = 0;
     // (a max_mismatches of umi_len or more lets every distance pass; min_distance is compared as it is)
-    const int r = correct_on_device(ctx->corr_ws.p, d_umi_ascii, (uint32_t)n_reads, umi_len, packed.data(), n_wl,
+    const int r = correct_on_device(ctx->call_ws.p, d_umi_ascii, (uint32_t)n_reads, umi_len, packed.data(), n_wl,
                                     std::min(max_mismatches, umi_len), min_distance, d_out_ascii, d_match, d_best, d_second,
                                     counts, &bad_read, (uint32_t)ctx->n_cus, ctx->h_counters, s);
     if (r == 1) {
@@ -91,28 +91,19 @@ int umi_correct_umis(umi_ctx *ctx, const uint8_t *umi_ascii, uint64_t n_reads, i
     if (!ctx->subs.empty()) ctx = ctx->subs[0];
     counts[0] = counts[1] = counts[2] = 0;
     if (n_reads == 0) return UMI_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    settle(ctx);
     const size_t n = (size_t)n_reads, bytes = n * (size_t)umi_len;
-    if ((rc = ctx->corr_umi.reserve(bytes)) || (out_ascii && (rc = ctx->corr_out.reserve(bytes))) ||
-        (rc = ctx->corr_match.reserve(n * 4)) || (best && (rc = ctx->corr_best.reserve(n))) ||
-        (second && (rc = ctx->corr_second.reserve(n))))
+    HostIo io(ctx);
+    const auto d_umi = io.in(umi_ascii, bytes);
+    const auto d_out = io.out(out_ascii, bytes);
+    const auto d_match = io.out(match, n * 4);
+    const auto d_best = io.out(best, n), d_second = io.out(second, n);
+    if ((rc = io.open()) ||
+        (rc = corr_run(ctx, d_umi, n_reads, umi_len, packed, n_wl, max_mismatches, min_distance, d_out, d_match, d_best, d_second,
+                       counts, io.stream())) ||
+        (rc = io.fetch(out_ascii, d_out, bytes)) || (rc = io.fetch(match, d_match, n)) || (rc = io.fetch(best, d_best, n)) ||
+        (rc = io.fetch(second, d_second, n)))
         return rc;
-    hipStream_t s = ctx->own_stream;
-    HIP_TRY(hipMemcpyAsync(ctx->corr_umi.p, umi_ascii, bytes, hipMemcpyHostToDevice, s));
-    rc = corr_run(ctx, ctx->corr_umi.as<uint8_t>(), n_reads, umi_len, packed, n_wl, max_mismatches, min_distance,
-                  out_ascii ? ctx->corr_out.as<uint8_t>() : nullptr, ctx->corr_match.as<int32_t>(),
-                  best ? ctx->corr_best.as<uint8_t>() : nullptr, second ? ctx->corr_second.as<uint8_t>() : nullptr, counts, s);
-    if (rc) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    if (out_ascii) HIP_TRY(hipMemcpyAsync(out_ascii, ctx->corr_out.p, bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(match, ctx->corr_match.p, n * 4, hipMemcpyDeviceToHost, s));
-    if (best) HIP_TRY(hipMemcpyAsync(best, ctx->corr_best.p, n, hipMemcpyDeviceToHost, s));
-    if (second) HIP_TRY(hipMemcpyAsync(second, ctx->corr_second.p, n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return UMI_OK;
+    return io.close();
 }
 
 } // extern "C"
@@ -152,10 +143,10 @@ int bc_run(umi_ctx *ctx, const uint8_t *d_bc_ascii, uint64_t n_reads, int bc_len
            const uint8_t *d_qual = nullptr, int permille = 0, int pseudocount = 0, uint32_t *d_exact_reads = nullptr)
 {
     int rc;
-    if ((rc = ctx->bc_ws.reserve(d_qual ? barcode_multi_workspace_bytes(n_wl, (uint32_t)n_reads) : barcode_workspace_bytes(n_wl))))
+    if ((rc = ctx->call_ws.reserve(d_qual ? barcode_multi_workspace_bytes(n_wl, (uint32_t)n_reads) : barcode_workspace_bytes(n_wl))))
         return rc;
     uint64_t bad = 0;
-    const int r = barcode_multi_on_device(ctx->bc_ws.p, d_bc_ascii, d_qual, (uint32_t)n_reads, bc_len, packed.data(), n_wl,
+    const int r = barcode_multi_on_device(ctx->call_ws.p, d_bc_ascii, d_qual, (uint32_t)n_reads, bc_len, packed.data(), n_wl,
                                           max_mismatches, (uint32_t)permille, (uint32_t)pseudocount, d_match, d_status,
                                           d_exact_reads, counts, &bad, (uint32_t)ctx->n_cus, ctx->h_counters, s);
     if (r == 1) {
@@ -180,6 +171,27 @@ int bc_run(umi_ctx *ctx, const uint8_t *d_bc_ascii, uint64_t n_reads, int bc_len
                     (unsigned long long)bad);
     if (r < 0) return fail(UMI_ERR_HIP, "barcode correction: %s", hipGetErrorString((hipError_t)(-r)));
     return UMI_OK;
+}
+
+// the host-buffer form of both: the reads (and their qualities) staged, bc_run, the results back
+int bc_staged(umi_ctx *ctx, const uint8_t *bc_ascii, const uint8_t *bc_qual, uint64_t n_reads, int bc_len,
+              const std::vector<uint64_t> &packed, uint32_t n_wl, int max_mismatches, int permille, int pseudocount, int32_t *match,
+              uint8_t *status, uint32_t *exact_reads, uint64_t *counts)
+{
+    const size_t n = (size_t)n_reads, bytes = n * (size_t)bc_len;
+    HostIo io(ctx);
+    const auto d_bc = io.in(bc_ascii, bytes), d_qual = io.in(bc_qual, bytes);
+    const auto d_match = io.out(match, n * 4);
+    const auto d_status = io.out(status, n);
+    const auto d_exact = io.out(exact_reads, (size_t)n_wl * 4);
+    int rc;
+    if ((rc = io.open()) ||
+        (rc = bc_run(ctx, d_bc, n_reads, bc_len, packed, n_wl, max_mismatches, d_match, d_status, counts, io.stream(), d_qual,
+                     permille, pseudocount, d_exact)) ||
+        (rc = io.fetch(match, d_match, n)) || (rc = io.fetch(status, d_status, n)) ||
+        (rc = io.fetch(exact_reads, d_exact, (size_t)n_wl)))
+        return rc;
+    return io.close();
 }
 
 // what umi_correct_barcodes_multi* refuses beyond bc_check (which looks at the rest, the context last)
@@ -222,23 +234,7 @@ int umi_correct_barcodes(umi_ctx *ctx, const uint8_t *bc_ascii, uint64_t n_reads
     if (!ctx->subs.empty()) ctx = ctx->subs[0];
     counts[0] = counts[1] = counts[2] = counts[3] = 0;
     if (n_reads == 0) return UMI_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    settle(ctx);
-    const size_t n = (size_t)n_reads, bytes = n * (size_t)bc_len;
-    if ((rc = ctx->bc_in.reserve(bytes)) || (rc = ctx->bc_match.reserve(n * 4)) || (status && (rc = ctx->bc_status.reserve(n))))
-        return rc;
-    hipStream_t s = ctx->own_stream;
-    HIP_TRY(hipMemcpyAsync(ctx->bc_in.p, bc_ascii, bytes, hipMemcpyHostToDevice, s));
-    rc = bc_run(ctx, ctx->bc_in.as<uint8_t>(), n_reads, bc_len, packed, n_wl, max_mismatches, ctx->bc_match.as<int32_t>(),
-                status ? ctx->bc_status.as<uint8_t>() : nullptr, counts, s);
-    if (rc) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(match, ctx->bc_match.p, n * 4, hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(hipMemcpyAsync(status, ctx->bc_status.p, n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return UMI_OK;
+    return bc_staged(ctx, bc_ascii, nullptr, n_reads, bc_len, packed, n_wl, max_mismatches, 0, 0, match, status, nullptr, counts);
 }
 
 int umi_correct_barcodes_multi_device(umi_ctx *ctx, const uint8_t *d_bc_ascii, const uint8_t *d_bc_qual, uint64_t n_reads,
@@ -270,27 +266,8 @@ int umi_correct_barcodes_multi(umi_ctx *ctx, const uint8_t *bc_ascii, const uint
     if (!ctx->subs.empty()) ctx = ctx->subs[0];
     for (int c = 0; c < 5; c++) counts[c] = 0;
     if (n_reads == 0) return UMI_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    settle(ctx);
-    const size_t n = (size_t)n_reads, bytes = n * (size_t)bc_len;
-    if ((rc = ctx->bc_in.reserve(bytes)) || (rc = ctx->bc_qual.reserve(bytes)) || (rc = ctx->bc_match.reserve(n * 4)) ||
-        (status && (rc = ctx->bc_status.reserve(n))) || (exact_reads && (rc = ctx->bc_exact.reserve((size_t)n_wl * 4))))
-        return rc;
-    hipStream_t s = ctx->own_stream;
-    HIP_TRY(hipMemcpyAsync(ctx->bc_in.p, bc_ascii, bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ctx->bc_qual.p, bc_qual, bytes, hipMemcpyHostToDevice, s));
-    rc = bc_run(ctx, ctx->bc_in.as<uint8_t>(), n_reads, bc_len, packed, n_wl, 1, ctx->bc_match.as<int32_t>(),
-                status ? ctx->bc_status.as<uint8_t>() : nullptr, counts, s, ctx->bc_qual.as<uint8_t>(), min_posterior_permille,
-                pseudocount, exact_reads ? ctx->bc_exact.as<uint32_t>() : nullptr);
-    if (rc) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(match, ctx->bc_match.p, n * 4, hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(hipMemcpyAsync(status, ctx->bc_status.p, n, hipMemcpyDeviceToHost, s));
-    if (exact_reads) HIP_TRY(hipMemcpyAsync(exact_reads, ctx->bc_exact.p, (size_t)n_wl * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return UMI_OK;
+    return bc_staged(ctx, bc_ascii, bc_qual, n_reads, bc_len, packed, n_wl, 1, min_posterior_permille, pseudocount, match, status,
+                     exact_reads, counts);
 }
 
 } // extern "C"

@@ -54,9 +54,9 @@ int cm_run(umi_ctx *ctx, const uint8_t *d_kept, const int32_t *d_freq, uint32_t 
            uint32_t *d_out_molecules, uint64_t *d_out_reads, uint64_t *nnz, hipStream_t s)
 {
     int rc;
-    if ((rc = ctx->cm_ws.reserve(count_workspace_bytes(m, h_idx != nullptr)))) return rc;
+    if ((rc = ctx->call_ws.reserve(count_workspace_bytes(m, h_idx != nullptr)))) return rc;
     uint64_t bad = 0;
-    const int r = count_matrix_on_device(ctx->cm_ws.p, d_kept, d_freq, h_off, h_idx, m, d_row, d_col, n_rows, n_cols, d_out_row,
+    const int r = count_matrix_on_device(ctx->call_ws.p, d_kept, d_freq, h_off, h_idx, m, d_row, d_col, n_rows, n_cols, d_out_row,
                                          d_out_col, d_out_molecules, d_out_reads, nnz, &bad, (uint32_t)ctx->n_cus, ctx->h_counters, s);
     if (r < 0) return fail(UMI_ERR_HIP, "count matrix: %s", hipGetErrorString((hipError_t)(-r)));
     if (bad) {
@@ -109,34 +109,21 @@ int umi_count_matrix(umi_ctx *ctx, const uint8_t *kept, const int32_t *freq, con
     if ((rc = cm_walk(ctx, bucket_off, n_buckets, &m, &h_off, &h_idx))) return rc;
     if (m == 0) return UMI_OK;
     if (n_rows == 0 || n_cols == 0) return fail(UMI_ERR_ARG, "a matrix of %u rows and %u columns with a non-empty bucket", n_rows, n_cols);
-    // the host arrays' device copies in one block: freq | row | col | the four outputs | kept
     const size_t n = (size_t)bucket_off[n_buckets], nb = (size_t)n_buckets, cap = (size_t)m;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_freq = 0, o_row = o_freq + up(n * 4), o_col = o_row + up(nb * 4), o_orow = o_col + up(nb * 4),
-                 o_ocol = o_orow + up(cap * 4), o_omol = o_ocol + up(cap * 4), o_oreads = o_omol + up(cap * 4),
-                 o_kept = o_oreads + up(cap * 8), total = o_kept + up(n);
-    if ((rc = ctx->cm_io.reserve(total))) return rc;
-    char *d = ctx->cm_io.as<char>();
-    hipStream_t s = ctx->own_stream;
-    HIP_TRY(hipMemcpyAsync(d + o_kept, kept, n, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_freq, freq, n * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_row, row, nb * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_col, col, nb * 4, hipMemcpyHostToDevice, s));
+    HostIo io(ctx);
+    const auto d_freq = io.in(freq, n * 4);
+    const auto d_row = io.in(row, nb * 4), d_col = io.in(col, nb * 4);
+    const auto d_orow = io.out(out_row, cap * 4), d_ocol = io.out(out_col, cap * 4), d_omol = io.out(out_molecules, cap * 4);
+    const auto d_oreads = io.out(out_reads, cap * 8);
+    const auto d_kept = io.in(kept, n);
     uint64_t got = 0;
-    rc = cm_run(ctx, (const uint8_t *)(d + o_kept), (const int32_t *)(d + o_freq), m, h_off, h_idx, (const uint32_t *)(d + o_row),
-                (const uint32_t *)(d + o_col), n_rows, n_cols, (uint32_t *)(d + o_orow), (uint32_t *)(d + o_ocol),
-                (uint32_t *)(d + o_omol), (uint64_t *)(d + o_oreads), &got, s);
-    if (rc) {
-        (void)hipStreamSynchronize(s);
+    if ((rc = io.open()) ||
+        (rc = cm_run(ctx, d_kept, d_freq, m, h_off, h_idx, d_row, d_col, n_rows, n_cols, d_orow, d_ocol, d_omol, d_oreads, &got,
+                     io.stream())) ||
+        (rc = io.fetch(out_row, d_orow, (size_t)got)) || (rc = io.fetch(out_col, d_ocol, (size_t)got)) ||
+        (rc = io.fetch(out_molecules, d_omol, (size_t)got)) || (rc = io.fetch(out_reads, d_oreads, (size_t)got)) ||
+        (rc = io.close()))
         return rc;
-    }
-    if (got) {
-        HIP_TRY(hipMemcpyAsync(out_row, d + o_orow, (size_t)got * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out_col, d + o_ocol, (size_t)got * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out_molecules, d + o_omol, (size_t)got * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out_reads, d + o_oreads, (size_t)got * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
     *nnz = got;
     return UMI_OK;
 }
@@ -209,7 +196,7 @@ int ds_run(umi_ctx *ctx, const DsShape &shape, const uint64_t *d_keys, int n_wor
     StatsCall c;
     stats_plan(h_off, m, ctx->stats_split, umi_len, &c.split, &c.n_deep, &c.n_tasks);
     if (c.n_deep > deep_max || c.n_tasks > tasks_max) return fail(UMI_ERR_HIP, "internal: %u deep buckets in %u pieces", c.n_deep, c.n_tasks);
-    if ((rc = ctx->ds_ws.reserve(stats_workspace_bytes(n, m, c.n_deep, c.n_tasks, umi_len, shape.per_umi)))) return rc;
+    if ((rc = ctx->call_ws.reserve(stats_workspace_bytes(n, m, c.n_deep, c.n_tasks, umi_len, shape.per_umi)))) return rc;
     c.d_keys = d_keys;
     c.d_freq = d_freq;
     c.d_kept = d_kept;
@@ -234,7 +221,7 @@ int ds_run(umi_ctx *ctx, const DsShape &shape, const uint64_t *d_keys, int n_wor
     c.h_deep_j = (uint32_t *)(ctx->ds_h.p + o_deep);
     c.h_pinned = ctx->h_counters;
     ctx->h_counters[2] = 0;
-    const int r = stats_on_device(ctx->ds_ws.p, c, s);
+    const int r = stats_on_device(ctx->call_ws.p, c, s);
     if (r < 0) return fail(UMI_ERR_HIP, "dedup stats: %s", hipGetErrorString((hipError_t)(-r)));
     if (ctx->h_counters[0])
         return fail(UMI_ERR_ARG, "%llu keys hold a code that is none of A, C, G, T, N below base %d",
@@ -297,44 +284,28 @@ int umi_dedup_stats(umi_ctx *ctx, const uint64_t *keys, int n_words, const int32
         memset(dist, 0, dist_words * 8);
         return UMI_OK;
     }
-    HIP_TRY(hipSetDevice(ctx->device));
-    settle(ctx);
-    // the host arrays' device copies in one block: keys | freq | root | the three tables | the per-UMI table | kept
-    const size_t n = (size_t)shape.n, nu = shape.per_umi ? n : 0;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_keys = 0, o_freq = o_keys + up(n * 8 * (size_t)n_words), o_root = o_freq + up(n * 4), o_pre = o_root + up(n * 4),
-                 o_post = o_pre + up((size_t)hist_bins * 8), o_dist = o_post + up((size_t)hist_bins * 8),
-                 o_entry = o_dist + up(dist_words * 8), o_tpre = o_entry + up(nu * 4), o_rpre = o_tpre + up(nu * 4),
-                 o_tpost = o_rpre + up(nu * 8), o_rpost = o_tpost + up(nu * 4), o_kept = o_rpost + up(nu * 8),
-                 total = o_kept + up(n);
-    if ((rc = ctx->ds_io.reserve(total))) return rc;
-    char *d = ctx->ds_io.as<char>();
-    hipStream_t s = ctx->own_stream;
-    HIP_TRY(hipMemcpyAsync(d + o_keys, keys, n * 8 * (size_t)n_words, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_freq, freq, n * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_root, root, n * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_kept, kept, n, hipMemcpyHostToDevice, s));
+    const size_t n = (size_t)shape.n, hist = (size_t)hist_bins;
+    HostIo io(ctx);
+    const auto d_keys = io.in(keys, n * 8 * (size_t)n_words);
+    const auto d_freq = io.in(freq, n * 4);
+    const auto d_root = io.in(root, n * 4);
+    const auto d_pre = io.out(count_pre, hist * 8), d_post = io.out(count_post, hist * 8), d_dist = io.out(dist, dist_words * 8);
+    // (the per-UMI table: absent as one)
+    const auto d_entry = io.out(umi_entry, n * 4), d_tpre = io.out(times_pre, n * 4);
+    const auto d_rpre = io.out(reads_pre, n * 8);
+    const auto d_tpost = io.out(times_post, n * 4);
+    const auto d_rpost = io.out(reads_post, n * 8);
+    const auto d_kept = io.in(kept, n);
     uint64_t rows = 0;
-    rc = ds_run(ctx, shape, (const uint64_t *)(d + o_keys), n_words, (const int32_t *)(d + o_freq), (const uint8_t *)(d + o_kept),
-                (const uint32_t *)(d + o_root), bucket_off, n_buckets, umi_len, seed, hist_bins, (uint64_t *)(d + o_pre),
-                (uint64_t *)(d + o_post), (uint64_t *)(d + o_dist), shape.per_umi ? (uint32_t *)(d + o_entry) : nullptr,
-                shape.per_umi ? (uint32_t *)(d + o_tpre) : nullptr, shape.per_umi ? (uint64_t *)(d + o_rpre) : nullptr,
-                shape.per_umi ? (uint32_t *)(d + o_tpost) : nullptr, shape.per_umi ? (uint64_t *)(d + o_rpost) : nullptr, &rows, s);
-    if (rc) {
-        (void)hipStreamSynchronize(s);
+    if ((rc = io.open()) ||
+        (rc = ds_run(ctx, shape, d_keys, n_words, d_freq, d_kept, d_root, bucket_off, n_buckets, umi_len, seed, hist_bins, d_pre,
+                     d_post, d_dist, d_entry, d_tpre, d_rpre, d_tpost, d_rpost, &rows, io.stream())) ||
+        (rc = io.fetch(count_pre, d_pre, hist)) || (rc = io.fetch(count_post, d_post, hist)) ||
+        (rc = io.fetch(dist, d_dist, dist_words)) || (rc = io.fetch(umi_entry, d_entry, (size_t)rows)) ||
+        (rc = io.fetch(times_pre, d_tpre, (size_t)rows)) || (rc = io.fetch(reads_pre, d_rpre, (size_t)rows)) ||
+        (rc = io.fetch(times_post, d_tpost, (size_t)rows)) || (rc = io.fetch(reads_post, d_rpost, (size_t)rows)) ||
+        (rc = io.close()))
         return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(count_pre, d + o_pre, (size_t)hist_bins * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(count_post, d + o_post, (size_t)hist_bins * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(dist, d + o_dist, dist_words * 8, hipMemcpyDeviceToHost, s));
-    if (rows) {
-        HIP_TRY(hipMemcpyAsync(umi_entry, d + o_entry, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(times_pre, d + o_tpre, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(reads_pre, d + o_rpre, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(times_post, d + o_tpost, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(reads_post, d + o_rpost, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
     if (n_umis) *n_umis = rows;
     return UMI_OK;
 }

@@ -51,34 +51,24 @@ int umi_data_new_wide(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask,
     d->off.assign((size_t)n + 1, 0);
     if (n >= 2) {
         int rc;
-        HIP_TRY(hipSetDevice(ctx->device));
         const size_t kb = (size_t)n * 8 * (size_t)n_words;
-        if ((rc = ctx->in_keys.reserve(kb)) || (rc = ctx->in_freq.reserve((size_t)n * 4)) ||
-            (nmask && (rc = ctx->in_nmask.reserve(kb))))
-            return rc;
-        hipStream_t s = ctx->own_stream;
         // the neighbour build ignores freq and order; feed ones so that prep's
         // contract check (rank order) does not apply to an unordered map
-        std::vector<int32_t> ones(n, 1);
-        hipError_t e = hipMemcpyAsync(ctx->in_keys.p, keys, kb, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(ctx->in_freq.p, ones.data(), (size_t)n * 4, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess && nmask)
-            e = hipMemcpyAsync(ctx->in_nmask.p, nmask, kb, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s); // `ones` must outlive the copy
-        if (e != hipSuccess) return fail(UMI_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
+        const std::vector<int32_t> ones(n, 1);
+        HostIo io(ctx);
+        const auto d_keys = io.in(keys, kb), d_nmask = io.in(nmask, kb);
+        const auto d_freq = io.in(ones.data(), (size_t)n * 4);
+        if ((rc = io.open()) || (rc = io.close())) return rc; // (closed at once: the copies are done while `ones` lives)
         const uint64_t boff[2] = {0, n};
         umi_stats st;
-        rc = run_pipeline(ctx, ctx->in_keys.as<uint64_t>(),
-                          nmask ? ctx->in_nmask.as<uint64_t>() : nullptr,
-                          ctx->in_freq.as<int32_t>(), boff, 1, n, umi_len, max_edits, 0.0f,
-                          MODE_NEIGHBOURS, 0, nullptr, nullptr, s, &st, nullptr, n_words);
+        rc = run_pipeline(ctx, d_keys, d_nmask, d_freq, boff, 1, n, umi_len, max_edits, 0.0f, MODE_NEIGHBOURS, 0, nullptr,
+                          nullptr, io.stream(), &st, nullptr, n_words);
         if (rc) return rc;
         const size_t E = (size_t)st.n_edges;
         std::vector<uint2> pairs(E);
         std::vector<uint8_t> pd(E);
         if (E) {
-            e = hipMemcpy(pairs.data(), ctx->edges.p, E * sizeof(uint2), hipMemcpyDeviceToHost);
+            hipError_t e = hipMemcpy(pairs.data(), ctx->edges.p, E * sizeof(uint2), hipMemcpyDeviceToHost);
             if (e == hipSuccess) e = hipMemcpy(pd.data(), ctx->edge_dist.p, E, hipMemcpyDeviceToHost);
             if (e != hipSuccess)
                 return fail(UMI_ERR_HIP, "download failed: %s", hipGetErrorString(e));

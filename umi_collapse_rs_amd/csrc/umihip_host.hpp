@@ -1,6 +1,6 @@
 // What the host .cpp files of libumihip.so share: error reporting, the two buffer classes, the
-// RCCL loader, the context, and the few functions one file offers the others.  Host code only:
-// no .hip file includes this.
+// RCCL loader, the context, the few functions one file offers the others, and the staging of a
+// host-buffer call (HostIo).  Host code only: no .hip file includes this.
 #pragma once
 #include "../../include/umihip.h"
 
@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "umihip_internal.h"
+#include "umihip_io_layout.hpp"
 #include "umihip_plan.hpp"
 
 #include <rccl/rccl.h> // (types only: the library itself is opened when the first collective is asked for)
@@ -244,31 +245,16 @@ struct umi_ctx {
     bool prune = false;
     umihip::Plan plan;
     umihip::TablePass table_pass;
-    // staging for the host-buffer entry point
-    umihip::DevBuf in_keys, in_nmask, in_freq, out_kept, out_root;
-    // read staging (umi_stage_reads*): workspace; device copies of the host-buffer form
-    umihip::DevBuf stage_ws, st_align, st_group, st_umi, st_score, st_keys, st_nmask, st_freq, st_rep, st_boff;
-    // ... and of umi_stage_seqs: the text, seq_pos then qual_pos, the lengths, entry_of_read
-    umihip::DevBuf sq_text, sq_pos, sq_len, sq_eor;
+    // the device copies of a host-buffer call's arrays: one block, laid out afresh by every call (HostIo below)
+    umihip::DevBuf io;
+    // the workspace of the single-shot device forms (staging, consensus, correction, count matrix, stats): each
+    // call carves it anew and keeps nothing in it -- settle() leaves one call at a time in the context
+    umihip::DevBuf call_ws;
     // whole-read keys (umi_dedup_seqs*): group table, records and their sort, runs, tile tasks
     umihip::DevBuf seq_groups, seq_ka, seq_kb, seq_va, seq_vb, seq_flag, seq_runid, seq_rs, seq_tend, seq_tmp;
-    // consensus of their clusters (umi_consensus_seqs*): workspace; the host-buffer form's outputs
-    umihip::DevBuf cons_ws, cons_seq, cons_qual, cons_off, cons_cr;
-    // ... of aligned reads (umi_consensus_bam): the host-buffer form's inputs and its other outputs
-    umihip::DevBuf cb_cluster, cb_clen, cb_qoff, cb_disagree;
-    // correction of UMIs to a fixed list (umi_correct_umis*): workspace; the host-buffer form's arrays
-    umihip::DevBuf corr_ws, corr_umi, corr_out, corr_match, corr_best, corr_second;
-    // correction of cell barcodes (umi_correct_barcodes*): packed list and index; the host-buffer form's arrays
-    // (bc_qual, bc_exact: umi_correct_barcodes_multi's qualities and exact reads per listed barcode)
-    umihip::DevBuf bc_ws, bc_in, bc_match, bc_status, bc_qual, bc_exact;
-    // molecules per (column, row) pair (umi_count_matrix*): workspace; the host-buffer form's arrays in one block;
-    // pinned staging of the non-empty buckets' offsets and numbers
-    umihip::DevBuf cm_ws, cm_io;
-    umihip::PinnedBuf cm_h;
-    // family sizes, UMI distances and UMI usage (umi_dedup_stats*): workspace; the host-buffer form's arrays in one
-    // block; pinned staging of the non-empty buckets' offsets, the deep buckets and their pieces
-    umihip::DevBuf ds_ws, ds_io;
-    umihip::PinnedBuf ds_h;
+    // pinned staging of umi_count_matrix* (the non-empty buckets' offsets and numbers) and of umi_dedup_stats*
+    // (the non-empty buckets' offsets, the deep buckets and their pieces)
+    umihip::PinnedBuf cm_h, ds_h;
     uint32_t stats_split = umihip::STATS_SPLIT; // buckets of at least this many entries are counted by the whole grid
     uint32_t cons_split = 512; // clusters of at least this many reads are summed in pieces by the whole grid
     umihip::PinnedBuf h_boff;                 // pinned staging of the bucket table
@@ -321,5 +307,74 @@ int collapse_edges(umi_ctx *ctx, uint32_t n, const uint2 *d_edges, uint32_t n_ed
 // the context's workspace does first
 int finish_pending(umi_ctx *ctx, umi_stats *stats);
 void settle(umi_ctx *ctx);
+
+// a device pointer into the staging block, good once the call's HostIo is open; null for an absent array
+template <typename T> struct IoPtr {
+    const DevBuf *block = nullptr;
+    size_t off = IO_ABSENT;
+    operator T *() const { return (T *)io_at(block->p, off); }
+};
+
+// One host-buffer call on a single-device context: its arrays' device copies are slots of ctx->io.  Declare
+// them, open(), run the device form on stream(), fetch() what came out, close().  However the call ends, the
+// stream has run dry before the caller has its arrays back: what close() did not see to, the destructor does.
+class HostIo {
+    struct Upload {
+        const void *host;
+        size_t off, bytes;
+    };
+    umi_ctx *ctx;
+    IoLayout layout;
+    std::vector<Upload> uploads;
+    bool busy = false; // a copy from or to the caller's memory may be in flight
+
+public:
+    explicit HostIo(umi_ctx *c) : ctx(c) {}
+    HostIo(const HostIo &) = delete;
+    HostIo &operator=(const HostIo &) = delete;
+    ~HostIo()
+    {
+        if (busy) (void)hipStreamSynchronize(ctx->own_stream);
+    }
+    hipStream_t stream() const { return ctx->own_stream; }
+    // an input: `bytes` of `host` are uploaded into a slot of bytes + pad (absent where host is null)
+    template <typename T> IoPtr<T> in(const T *host, size_t bytes, size_t pad = 0)
+    {
+        const IoPtr<T> p{&ctx->io, layout.add(host != nullptr, bytes + pad)};
+        also(p, 0, host, bytes);
+        return p;
+    }
+    // ... one more array into the pad of a slot that is present, `at` bytes from its start
+    template <typename T> void also(IoPtr<T> slot, size_t at, const T *host, size_t bytes)
+    {
+        if (host && bytes) uploads.push_back({host, slot.off + at, bytes});
+    }
+    // an output of this many bytes; the second form is absent where the caller did not ask for the array
+    template <typename T> IoPtr<T> out(size_t bytes) { return {&ctx->io, layout.add(true, bytes)}; }
+    template <typename T> IoPtr<T> out(const T *host, size_t bytes) { return {&ctx->io, layout.add(host != nullptr, bytes)}; }
+    // the device made current, a deferred call let end, the block reserved, the inputs put on the stream
+    int open()
+    {
+        HIP_TRY(hipSetDevice(ctx->device));
+        settle(ctx);
+        if (int rc = ctx->io.reserve(layout.total + 1)) return rc; // (+ 1: a block, and an address, even for no bytes)
+        busy = true;
+        for (const Upload &u : uploads)
+            HIP_TRY(hipMemcpyAsync(ctx->io.as<char>() + u.off, u.host, u.bytes, hipMemcpyHostToDevice, ctx->own_stream));
+        return UMI_OK;
+    }
+    // the first `count` elements of an output to the caller (nothing where host is null)
+    template <typename T> int fetch(T *host, IoPtr<T> from, size_t count)
+    {
+        if (host && count) HIP_TRY(hipMemcpyAsync(host, (T *)from, count * sizeof(T), hipMemcpyDeviceToHost, ctx->own_stream));
+        return UMI_OK;
+    }
+    int close()
+    {
+        busy = false;
+        HIP_TRY(hipStreamSynchronize(ctx->own_stream));
+        return UMI_OK;
+    }
+};
 
 } // namespace umihip

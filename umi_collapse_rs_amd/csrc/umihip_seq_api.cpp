@@ -274,29 +274,18 @@ int umi_dedup_seqs(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask, in
         }
         return UMI_OK;
     }
-    settle(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
     const size_t kb = (size_t)n * 8 * (size_t)n_words;
-    if ((rc = ctx->in_keys.reserve(kb)) || (rc = ctx->in_freq.reserve(n * 4)) || (rc = ctx->out_kept.reserve(n)) ||
-        (rc = ctx->out_root.reserve(n * 4)))
+    HostIo io(ctx);
+    const auto d_keys = io.in(keys, kb), d_nmask = io.in(nmask, kb);
+    const auto d_freq = io.in(freq, n * 4);
+    const auto d_kept = io.out(kept, n);
+    const auto d_root = io.out(root, n * 4);
+    if ((rc = io.open()) ||
+        (rc = seq_pipeline(ctx, d_keys, d_nmask, n_words, d_freq, bucket_off, bucket_len, n_buckets, (uint32_t)n, k, percentage,
+                           algo, adj_max_freq, d_kept, d_root, io.stream(), stats)) ||
+        (rc = io.fetch(kept, d_kept, n)) || (rc = io.fetch(root, d_root, n)))
         return rc;
-    if (nmask && (rc = ctx->in_nmask.reserve(kb))) return rc;
-    hipStream_t s = ctx->own_stream;
-    HIP_TRY(hipMemcpyAsync(ctx->in_keys.p, keys, kb, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ctx->in_freq.p, freq, n * 4, hipMemcpyHostToDevice, s));
-    if (nmask) HIP_TRY(hipMemcpyAsync(ctx->in_nmask.p, nmask, kb, hipMemcpyHostToDevice, s));
-    rc = seq_pipeline(ctx, ctx->in_keys.as<uint64_t>(), nmask ? ctx->in_nmask.as<uint64_t>() : nullptr, n_words,
-                      ctx->in_freq.as<int32_t>(), bucket_off, bucket_len, n_buckets, (uint32_t)n, k, percentage, algo,
-                      adj_max_freq, ctx->out_kept.as<uint8_t>(), root ? ctx->out_root.as<uint32_t>() : nullptr, s,
-                      stats);
-    if (rc) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(kept, ctx->out_kept.p, n, hipMemcpyDeviceToHost, s));
-    if (root) HIP_TRY(hipMemcpyAsync(root, ctx->out_root.p, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return UMI_OK;
+    return io.close();
 }
 
 } // extern "C"
@@ -353,11 +342,11 @@ int umi_consensus_seqs_device(umi_ctx *ctx, const uint8_t *d_text, const uint64_
                     (unsigned long long)n_reads);
     HIP_TRY(hipSetDevice(ctx->device));
     settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
-    if ((rc = ctx->cons_ws.reserve(consensus_workspace_bytes((uint32_t)n_reads, (uint32_t)n_entries, (uint32_t)n_buckets,
+    if ((rc = ctx->call_ws.reserve(consensus_workspace_bytes((uint32_t)n_reads, (uint32_t)n_entries, (uint32_t)n_buckets,
                                                              ctx->cons_split))))
         return rc;
     ConsFault f;
-    const int r = consensus_on_device(ctx->cons_ws.p, d_text, d_seq_pos, d_qual_pos, d_len, (uint32_t)n_reads, d_entry_of_read,
+    const int r = consensus_on_device(ctx->call_ws.p, d_text, d_seq_pos, d_qual_pos, d_len, (uint32_t)n_reads, d_entry_of_read,
                                       d_freq, d_kept, d_root, (uint32_t)n_entries, bucket_off, bucket_len, (uint32_t)n_buckets,
                                       ctx->cons_split, (uint32_t)ctx->n_cus, d_cons_seq, d_cons_qual, d_cons_off,
                                       d_cluster_reads, cons_bytes, &f, ctx->h_counters, (hipStream_t)hip_stream);
@@ -395,8 +384,6 @@ int umi_consensus_seqs(umi_ctx *ctx, const uint8_t *text, const uint64_t *seq_po
         return fail(UMI_ERR_ARG, "a required pointer is NULL");
     *cons_bytes = 0;
     if (n_reads == 0) return UMI_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    settle(ctx);
     // the text that is looked at, and what the consensus may fill: the caller's capacity
     size_t text_bytes = 1, cap = 0;
     for (uint64_t i = 0; i < n_reads; i++) {
@@ -406,42 +393,30 @@ int umi_consensus_seqs(umi_ctx *ctx, const uint8_t *text, const uint64_t *seq_po
         cap += len[i];
     }
     const size_t n = (size_t)n_reads, ne = std::max<size_t>((size_t)n_entries, 1);
-    if ((rc = ctx->sq_text.reserve(text_bytes)) || (rc = ctx->sq_pos.reserve(n * 16)) || (rc = ctx->sq_len.reserve(n * 4)) ||
-        (rc = ctx->sq_eor.reserve(n * 4)) || (rc = ctx->in_freq.reserve(ne * 4)) || (rc = ctx->out_kept.reserve(ne)) ||
-        (rc = ctx->out_root.reserve(ne * 4)) || (rc = ctx->cons_seq.reserve(cap + 8)) || (rc = ctx->cons_qual.reserve(cap + 8)) ||
-        (rc = ctx->cons_off.reserve(ne * 8)) || (rc = ctx->cons_cr.reserve(ne * 4)))
-        return rc;
-    hipStream_t s = ctx->own_stream;
-    uint64_t *d_pos = ctx->sq_pos.as<uint64_t>(); // (seq_pos, then qual_pos)
-    HIP_TRY(hipMemcpyAsync(ctx->sq_text.p, text, text_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_pos, seq_pos, n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_pos + n, qual_pos, n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ctx->sq_len.p, len, n * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ctx->sq_eor.p, entry_of_read, n * 4, hipMemcpyHostToDevice, s));
-    if (n_entries) {
-        HIP_TRY(hipMemcpyAsync(ctx->in_freq.p, freq, n_entries * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(ctx->out_kept.p, kept, n_entries, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(ctx->out_root.p, root, n_entries * 4, hipMemcpyHostToDevice, s));
-    }
-    rc = umi_consensus_seqs_device(ctx, ctx->sq_text.as<uint8_t>(), d_pos, d_pos + n, ctx->sq_len.as<uint32_t>(), n_reads,
-                                   ctx->sq_eor.as<uint32_t>(), ctx->in_freq.as<int32_t>(), ctx->out_kept.as<uint8_t>(),
-                                   ctx->out_root.as<uint32_t>(), n_entries, bucket_off, bucket_len, n_buckets,
-                                   ctx->cons_seq.as<uint8_t>(), ctx->cons_qual.as<uint8_t>(), ctx->cons_off.as<uint64_t>(),
-                                   ctx->cons_cr.as<uint32_t>(), cons_bytes, s);
-    if (rc) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    // what came out, where it is defined: the kept entries' offsets and counts, the bytes in front of cons_bytes
+    // what comes out, where it is defined: the kept entries' offsets and counts, the bytes in front of cons_bytes
     std::vector<uint64_t> off_all((size_t)n_entries);
     std::vector<uint32_t> cr_all((size_t)n_entries);
-    if (*cons_bytes) {
-        HIP_TRY(hipMemcpyAsync(cons_seq, ctx->cons_seq.p, (size_t)*cons_bytes, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(cons_qual, ctx->cons_qual.p, (size_t)*cons_bytes, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipMemcpyAsync(off_all.data(), ctx->cons_off.p, (size_t)n_entries * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(cr_all.data(), ctx->cons_cr.p, (size_t)n_entries * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    HostIo io(ctx);
+    const auto d_text = io.in(text, text_bytes);
+    const auto d_pos = io.in(seq_pos, n * 8, n * 8); // (pad: qual_pos behind seq_pos, from d_pos + n)
+    io.also(d_pos, n * 8, qual_pos, n * 8);
+    const auto d_len = io.in(len, n * 4), d_eor = io.in(entry_of_read, n * 4);
+    // (pads: room for max(n_entries, 1) entries)
+    const auto d_freq = io.in(freq, n_entries * 4, (ne - n_entries) * 4);
+    const auto d_kept = io.in(kept, n_entries, ne - n_entries);
+    const auto d_root = io.in(root, n_entries * 4, (ne - n_entries) * 4);
+    // (+ 8: a whole word behind the consensus bytes, for kernels that touch them a word at a time)
+    const auto d_cons_seq = io.out<uint8_t>(cap + 8), d_cons_qual = io.out<uint8_t>(cap + 8);
+    const auto d_cons_off = io.out<uint64_t>(ne * 8);
+    const auto d_cr = io.out<uint32_t>(ne * 4);
+    if ((rc = io.open()) ||
+        (rc = umi_consensus_seqs_device(ctx, d_text, d_pos, d_pos + n, d_len, n_reads, d_eor, d_freq, d_kept, d_root, n_entries,
+                                        bucket_off, bucket_len, n_buckets, d_cons_seq, d_cons_qual, d_cons_off, d_cr, cons_bytes,
+                                        io.stream())) ||
+        (rc = io.fetch(cons_seq, d_cons_seq, (size_t)*cons_bytes)) || (rc = io.fetch(cons_qual, d_cons_qual, (size_t)*cons_bytes)) ||
+        (rc = io.fetch(off_all.data(), d_cons_off, (size_t)n_entries)) ||
+        (rc = io.fetch(cr_all.data(), d_cr, (size_t)n_entries)) || (rc = io.close()))
+        return rc;
     for (uint64_t e = 0; e < n_entries; e++)
         if (kept[e]) {
             cons_off[e] = off_all[e];
@@ -486,11 +461,11 @@ int umi_consensus_bam_device(umi_ctx *ctx, const uint8_t *d_data, const uint64_t
     if (n_reads == 0 && n_clusters == 0) return UMI_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
-    if ((rc = ctx->cons_ws.reserve(consensus_bam_workspace_bytes((uint32_t)n_reads, (uint32_t)n_clusters, ctx->cons_split))))
+    if ((rc = ctx->call_ws.reserve(consensus_bam_workspace_bytes((uint32_t)n_reads, (uint32_t)n_clusters, ctx->cons_split))))
         return rc;
     ConsBamFault f;
     uint64_t sb = 0, qb = 0;
-    const int r = consensus_bam_on_device(ctx->cons_ws.p, d_data, d_seq_pos, d_qual_pos, d_len, d_cluster, (uint32_t)n_reads,
+    const int r = consensus_bam_on_device(ctx->call_ws.p, d_data, d_seq_pos, d_qual_pos, d_len, d_cluster, (uint32_t)n_reads,
                                           d_cluster_len, (uint32_t)n_clusters, ctx->cons_split, (uint32_t)ctx->n_cus, d_cons_seq,
                                           d_cons_qual, d_seq_off, d_qual_off, d_depth, d_disagree, &sb, &qb, &f,
                                           ctx->h_counters, (hipStream_t)hip_stream);
@@ -522,8 +497,6 @@ int umi_consensus_bam(umi_ctx *ctx, const uint8_t *data, const uint64_t *seq_pos
         return fail(UMI_ERR_ARG, "a required pointer is NULL");
     *seq_bytes = *qual_bytes = 0;
     if (n_reads == 0 && n_clusters == 0) return UMI_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    settle(ctx);
     // what of the data is looked at: the voters' bytes (a voter of a length the device refuses adds nothing);
     // what the consensus may fill (likewise for a cluster that is too long)
     size_t data_bytes = 1, cap_s = 0, cap_q = 0;
@@ -536,40 +509,27 @@ int umi_consensus_bam(umi_ctx *ctx, const uint8_t *data, const uint64_t *seq_pos
         cap_q += L;
     }
     const size_t n = std::max<size_t>((size_t)n_reads, 1), nc = std::max<size_t>((size_t)n_clusters, 1);
-    if ((rc = ctx->sq_text.reserve(data_bytes)) || (rc = ctx->sq_pos.reserve(n * 16)) || (rc = ctx->sq_len.reserve(n * 4)) ||
-        (rc = ctx->cb_cluster.reserve(n * 4)) || (rc = ctx->cb_clen.reserve(nc * 4)) || (rc = ctx->cons_seq.reserve(cap_s + 8)) ||
-        (rc = ctx->cons_qual.reserve(cap_q + 8)) || (rc = ctx->cons_off.reserve(nc * 8)) || (rc = ctx->cb_qoff.reserve(nc * 8)) ||
-        (rc = ctx->cons_cr.reserve(nc * 4)) || (rc = ctx->cb_disagree.reserve(nc * 4)))
+    // (pads of the inputs: room for max(n_reads, 1) reads and max(n_clusters, 1) clusters, a byte of data at least)
+    const size_t nr = (size_t)n_reads, ncl = (size_t)n_clusters;
+    HostIo io(ctx);
+    const auto d_data = io.in(data, nr ? data_bytes : 0, nr ? 0 : 1);
+    const auto d_pos = io.in(seq_pos, nr * 8, n * 16 - nr * 8); // (... and qual_pos behind seq_pos, from d_pos + n)
+    io.also(d_pos, n * 8, qual_pos, nr * 8);
+    const auto d_len = io.in(len, nr * 4, (n - nr) * 4), d_cluster = io.in(cluster, nr * 4, (n - nr) * 4);
+    const auto d_clen = io.in(cluster_len, ncl * 4, (nc - ncl) * 4);
+    // (+ 8: a whole word behind the consensus bytes, for kernels that touch them a word at a time)
+    const auto d_cons_seq = io.out(cons_seq, cap_s + 8), d_cons_qual = io.out(cons_qual, cap_q + 8);
+    const auto d_seq_off = io.out(seq_off, nc * 8), d_qual_off = io.out(qual_off, nc * 8);
+    const auto d_depth = io.out(depth, nc * 4), d_disagree = io.out(disagree, nc * 4);
+    if ((rc = io.open()) ||
+        (rc = umi_consensus_bam_device(ctx, d_data, d_pos, nr ? d_pos + n : nullptr, d_len, d_cluster, n_reads, d_clen, n_clusters, d_cons_seq,
+                                       d_cons_qual, d_seq_off, d_qual_off, d_depth, d_disagree, seq_bytes, qual_bytes,
+                                       io.stream())) ||
+        (rc = io.fetch(cons_seq, d_cons_seq, (size_t)*seq_bytes)) || (rc = io.fetch(cons_qual, d_cons_qual, (size_t)*qual_bytes)) ||
+        (rc = io.fetch(seq_off, d_seq_off, ncl)) || (rc = io.fetch(qual_off, d_qual_off, ncl)) ||
+        (rc = io.fetch(depth, d_depth, ncl)) || (rc = io.fetch(disagree, d_disagree, ncl)))
         return rc;
-    hipStream_t s = ctx->own_stream;
-    uint64_t *d_pos = ctx->sq_pos.as<uint64_t>(); // (seq_pos, then qual_pos)
-    if (n_reads) {
-        HIP_TRY(hipMemcpyAsync(ctx->sq_text.p, data, data_bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_pos, seq_pos, n_reads * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_pos + n, qual_pos, n_reads * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(ctx->sq_len.p, len, n_reads * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(ctx->cb_cluster.p, cluster, n_reads * 4, hipMemcpyHostToDevice, s));
-    }
-    if (n_clusters) HIP_TRY(hipMemcpyAsync(ctx->cb_clen.p, cluster_len, n_clusters * 4, hipMemcpyHostToDevice, s));
-    rc = umi_consensus_bam_device(ctx, ctx->sq_text.as<uint8_t>(), d_pos, d_pos + n, ctx->sq_len.as<uint32_t>(),
-                                  ctx->cb_cluster.as<uint32_t>(), n_reads, ctx->cb_clen.as<uint32_t>(), n_clusters,
-                                  ctx->cons_seq.as<uint8_t>(), ctx->cons_qual.as<uint8_t>(), ctx->cons_off.as<uint64_t>(),
-                                  ctx->cb_qoff.as<uint64_t>(), ctx->cons_cr.as<uint32_t>(),
-                                  disagree ? ctx->cb_disagree.as<uint32_t>() : nullptr, seq_bytes, qual_bytes, s);
-    if (rc) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    if (*seq_bytes) HIP_TRY(hipMemcpyAsync(cons_seq, ctx->cons_seq.p, (size_t)*seq_bytes, hipMemcpyDeviceToHost, s));
-    if (*qual_bytes) HIP_TRY(hipMemcpyAsync(cons_qual, ctx->cons_qual.p, (size_t)*qual_bytes, hipMemcpyDeviceToHost, s));
-    if (n_clusters) {
-        HIP_TRY(hipMemcpyAsync(seq_off, ctx->cons_off.p, (size_t)n_clusters * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(qual_off, ctx->cb_qoff.p, (size_t)n_clusters * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(depth, ctx->cons_cr.p, (size_t)n_clusters * 4, hipMemcpyDeviceToHost, s));
-        if (disagree) HIP_TRY(hipMemcpyAsync(disagree, ctx->cb_disagree.p, (size_t)n_clusters * 4, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    return UMI_OK;
+    return io.close();
 }
 
 } // extern "C"

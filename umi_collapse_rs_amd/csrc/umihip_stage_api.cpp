@@ -28,9 +28,9 @@ int umi_stage_reads_grouped_wide_device(umi_ctx *ctx, const uint64_t *d_align_ke
     HIP_TRY(hipSetDevice(ctx->device));
     settle(ctx);
     int rc;
-    if ((rc = ctx->stage_ws.reserve(stage_workspace_bytes((uint32_t)n_reads, n_words, group_key_bits > 0)))) return rc;
+    if ((rc = ctx->call_ws.reserve(stage_workspace_bytes((uint32_t)n_reads, n_words, group_key_bits > 0)))) return rc;
     hipStream_t s = (hipStream_t)hip_stream; // (NULL = the default stream, as in every device-pointer call)
-    const int r = stage_reads_on_device(ctx->stage_ws.p, d_align_key, align_key_bits, group_key_bits ? d_group_key : nullptr,
+    const int r = stage_reads_on_device(ctx->call_ws.p, d_align_key, align_key_bits, group_key_bits ? d_group_key : nullptr,
                                         group_key_bits, d_umi_ascii, d_score, (uint32_t)n_reads, umi_len, n_words, merge,
                                         d_keys, d_nmask, d_freq, d_rep, d_bucket_off, n_entries, n_buckets, ctx->h_counters, s);
     if (r == 1) return fail(UMI_ERR_CHAR, "Unknown character in UMI sequence");
@@ -84,39 +84,27 @@ int umi_stage_reads_grouped_wide(umi_ctx *ctx, const uint64_t *align_key, int al
     if (group_key_bits < 0 || group_key_bits > 64) return fail(UMI_ERR_ARG, "group_key_bits must be in 0..64");
     if (group_key_bits && n_reads && !group_key) return fail(UMI_ERR_ARG, "group_key is NULL with group_key_bits %d", group_key_bits);
     if (n_reads >= (1ull << 30)) return fail(UMI_ERR_ARG, "%llu reads exceed the 30-bit index space of one staging call", (unsigned long long)n_reads);
-    HIP_TRY(hipSetDevice(ctx->device));
     int rc;
+    // (sizes for max(n, 1) reads: no array without room; the pad of an input is that room beyond its n reads)
     const size_t n = (size_t)n_reads, m = std::max<size_t>(n, 1), kw = 8 * (size_t)n_words;
-    if ((rc = ctx->st_align.reserve(m * 8)) || (rc = ctx->st_umi.reserve(m * (size_t)umi_len)) ||
-        (rc = ctx->st_score.reserve(m * 4)) || (rc = ctx->st_keys.reserve(m * kw)) || (rc = ctx->st_nmask.reserve(m * kw)) ||
-        (rc = ctx->st_freq.reserve(m * 4)) || (rc = ctx->st_rep.reserve(m * 8)) || (rc = ctx->st_boff.reserve((m + 1) * 8)) ||
-        (group_key_bits && (rc = ctx->st_group.reserve(m * 8))))
-        return rc;
-    hipStream_t s = ctx->own_stream;
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(ctx->st_align.p, align_key, n * 8, hipMemcpyHostToDevice, s));
-        if (group_key_bits) HIP_TRY(hipMemcpyAsync(ctx->st_group.p, group_key, n * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(ctx->st_umi.p, umi_ascii, n * (size_t)umi_len, hipMemcpyHostToDevice, s));
-        if (score) HIP_TRY(hipMemcpyAsync(ctx->st_score.p, score, n * 4, hipMemcpyHostToDevice, s));
-    }
-    if ((rc = umi_stage_reads_grouped_wide_device(ctx, ctx->st_align.as<uint64_t>(), align_key_bits,
-                                                  group_key_bits ? ctx->st_group.as<uint64_t>() : nullptr, group_key_bits,
-                                                  ctx->st_umi.as<uint8_t>(), score ? ctx->st_score.as<int32_t>() : nullptr,
-                                                  n_reads, umi_len, n_words, merge, ctx->st_keys.as<uint64_t>(),
-                                                  ctx->st_nmask.as<uint64_t>(), ctx->st_freq.as<int32_t>(),
-                                                  ctx->st_rep.as<uint64_t>(), ctx->st_boff.as<uint64_t>(), n_entries,
-                                                  n_buckets, s)))
+    HostIo io(ctx);
+    const auto d_align = io.in(align_key, n * 8, (m - n) * 8);
+    const auto d_group = io.in(group_key_bits ? group_key : nullptr, n * 8, (m - n) * 8);
+    const auto d_umi = io.in(umi_ascii, n * (size_t)umi_len, (m - n) * (size_t)umi_len);
+    const auto d_score = io.in(score, n * 4, (m - n) * 4);
+    const auto d_keys = io.out<uint64_t>(m * kw), d_nmask = io.out<uint64_t>(m * kw); // (the mask is written, asked for or not)
+    const auto d_freq = io.out<int32_t>(m * 4);
+    const auto d_rep = io.out<uint64_t>(m * 8), d_boff = io.out<uint64_t>((m + 1) * 8);
+    if ((rc = io.open()) ||
+        (rc = umi_stage_reads_grouped_wide_device(ctx, d_align, align_key_bits, d_group, group_key_bits, d_umi, d_score, n_reads,
+                                                  umi_len, n_words, merge, d_keys, d_nmask, d_freq, d_rep, d_boff, n_entries,
+                                                  n_buckets, io.stream())))
         return rc;
     const size_t e = (size_t)*n_entries, b = (size_t)*n_buckets;
-    if (e) {
-        HIP_TRY(hipMemcpyAsync(keys, ctx->st_keys.p, e * kw, hipMemcpyDeviceToHost, s));
-        if (nmask) HIP_TRY(hipMemcpyAsync(nmask, ctx->st_nmask.p, e * kw, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(freq, ctx->st_freq.p, e * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(rep, ctx->st_rep.p, e * 8, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipMemcpyAsync(bucket_off, ctx->st_boff.p, (b + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return UMI_OK;
+    if ((rc = io.fetch(keys, d_keys, e * (size_t)n_words)) || (rc = io.fetch(nmask, d_nmask, e * (size_t)n_words)) ||
+        (rc = io.fetch(freq, d_freq, e)) || (rc = io.fetch(rep, d_rep, e)) || (rc = io.fetch(bucket_off, d_boff, b + 1)))
+        return rc;
+    return io.close();
 }
 
 int umi_stage_reads_wide(umi_ctx *ctx, const uint64_t *align_key, int align_key_bits, const uint8_t *umi_ascii,
@@ -164,9 +152,9 @@ int umi_stage_seqs_device(umi_ctx *ctx, const uint8_t *d_text, const uint64_t *d
     HIP_TRY(hipSetDevice(ctx->device));
     settle(ctx);
     int rc;
-    if ((rc = ctx->stage_ws.reserve(stage_seqs_workspace_bytes((uint32_t)n_reads, n_words)))) return rc;
+    if ((rc = ctx->call_ws.reserve(stage_seqs_workspace_bytes((uint32_t)n_reads, n_words)))) return rc;
     SeqFault fault;
-    const int r = stage_seqs_on_device(ctx->stage_ws.p, d_text, d_seq_pos, d_qual_pos, d_len, (uint32_t)n_reads, n_words, merge,
+    const int r = stage_seqs_on_device(ctx->call_ws.p, d_text, d_seq_pos, d_qual_pos, d_len, (uint32_t)n_reads, n_words, merge,
                                        d_keys, d_nmask, d_freq, d_rep, d_entry_of_read, bucket_off, bucket_len, n_entries,
                                        n_buckets, any_n, &fault, ctx->h_counters, (hipStream_t)hip_stream);
     if (r == 1)
@@ -192,7 +180,6 @@ int umi_stage_seqs(umi_ctx *ctx, const uint8_t *text, const uint64_t *seq_pos, c
     if (n_words < 1 || n_words > SEQ_MAX_WORDS) return fail(UMI_ERR_ARG, "n_words %d outside 1..%d", n_words, SEQ_MAX_WORDS);
     if (merge == 1 && n_reads && !qual_pos) return fail(UMI_ERR_ARG, "merge 1 needs qual_pos");
     if (n_reads >= (1ull << 30)) return fail(UMI_ERR_ARG, "%llu reads exceed the 30-bit index space of one staging call", (unsigned long long)n_reads);
-    HIP_TRY(hipSetDevice(ctx->device));
     // the text that is looked at: up to the end of the last byte of any read (lengths beyond
     // UMI_MAX_SEQ_LEN are refused inside; their first UMI_MAX_SEQ_LEN bytes are what the device reads)
     size_t text_bytes = 1;
@@ -203,34 +190,26 @@ int umi_stage_seqs(umi_ctx *ctx, const uint8_t *text, const uint64_t *seq_pos, c
     }
     int rc;
     const size_t n = (size_t)n_reads, m = std::max<size_t>(n, 1), kw = 8 * (size_t)n_words;
-    if ((rc = ctx->sq_text.reserve(text_bytes)) || (rc = ctx->sq_pos.reserve(m * 16)) || (rc = ctx->sq_len.reserve(m * 4)) ||
-        (rc = ctx->sq_eor.reserve(m * 4)) || (rc = ctx->st_keys.reserve(m * kw)) || (rc = ctx->st_nmask.reserve(m * kw)) ||
-        (rc = ctx->st_freq.reserve(m * 4)) || (rc = ctx->st_rep.reserve(m * 8)))
-        return rc;
-    hipStream_t s = ctx->own_stream;
-    uint64_t *d_pos = ctx->sq_pos.as<uint64_t>(); // (seq_pos, then qual_pos from d_pos + m)
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(ctx->sq_text.p, text, text_bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_pos, seq_pos, n * 8, hipMemcpyHostToDevice, s));
-        if (qual_pos) HIP_TRY(hipMemcpyAsync(d_pos + m, qual_pos, n * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(ctx->sq_len.p, len, n * 4, hipMemcpyHostToDevice, s));
-    }
-    uint32_t *d_eor = entry_of_read ? ctx->sq_eor.as<uint32_t>() : nullptr;
-    if ((rc = umi_stage_seqs_device(ctx, ctx->sq_text.as<uint8_t>(), d_pos, qual_pos ? d_pos + m : nullptr,
-                                    ctx->sq_len.as<uint32_t>(), n_reads, n_words, merge, ctx->st_keys.as<uint64_t>(),
-                                    nmask ? ctx->st_nmask.as<uint64_t>() : nullptr, ctx->st_freq.as<int32_t>(),
-                                    ctx->st_rep.as<uint64_t>(), d_eor, bucket_off, bucket_len, n_entries, n_buckets, any_n, s)))
+    HostIo io(ctx);
+    const auto d_text = io.in(text, n ? text_bytes : 0, n ? 0 : 1); // (pad: a byte of text where there is no read)
+    // (pad: qual_pos behind seq_pos, from d_pos + m -- and, as for every array here, room for max(n, 1) reads)
+    const auto d_pos = io.in(seq_pos, n * 8, m * 16 - n * 8);
+    io.also(d_pos, m * 8, qual_pos, n * 8);
+    const auto d_len = io.in(len, n * 4, (m - n) * 4);
+    const auto d_keys = io.out(keys, m * kw), d_nmask = io.out(nmask, m * kw);
+    const auto d_freq = io.out(freq, m * 4);
+    const auto d_rep = io.out(rep, m * 8);
+    const auto d_eor = io.out(entry_of_read, m * 4);
+    if ((rc = io.open()) ||
+        (rc = umi_stage_seqs_device(ctx, d_text, d_pos, qual_pos && n ? d_pos + m : nullptr, d_len, n_reads, n_words, merge, d_keys,
+                                    d_nmask, d_freq, d_rep, d_eor, bucket_off, bucket_len, n_entries, n_buckets, any_n,
+                                    io.stream())))
         return rc;
     const size_t e = (size_t)*n_entries;
-    if (e) {
-        HIP_TRY(hipMemcpyAsync(keys, ctx->st_keys.p, e * kw, hipMemcpyDeviceToHost, s));
-        if (nmask) HIP_TRY(hipMemcpyAsync(nmask, ctx->st_nmask.p, e * kw, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(freq, ctx->st_freq.p, e * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(rep, ctx->st_rep.p, e * 8, hipMemcpyDeviceToHost, s));
-    }
-    if (d_eor && n) HIP_TRY(hipMemcpyAsync(entry_of_read, d_eor, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return UMI_OK;
+    if ((rc = io.fetch(keys, d_keys, e * (size_t)n_words)) || (rc = io.fetch(nmask, d_nmask, e * (size_t)n_words)) ||
+        (rc = io.fetch(freq, d_freq, e)) || (rc = io.fetch(rep, d_rep, e)) || (rc = io.fetch(entry_of_read, d_eor, n)))
+        return rc;
+    return io.close();
 }
 
 } // extern "C"
