@@ -234,8 +234,9 @@ struct SegArgs {
     int n_parts;            // k + 1
     uint32_t *bin_cnt;      // [n_bins] entries per bin (prep); reused as the scatter cursor
     uint32_t *bin_start;    // [n_bins] first position of the bin in the sub-bucket arrays
-    unsigned long long *scan_state; // [1 + n_chunks] the scan's ticket counter and its chunks' status words
-                                    // (zeroed with bin_cnt: they sit behind it in one block)
+    unsigned long long *scan_state; // [1 + n_chunks + segments] the scan's ticket counter, its chunks' status words
+                                    // and a word per segment (seg_scan_flag_word); zeroed with bin_cnt: they sit
+                                    // behind it in one block
     SegTask *tasks;         // [task_cap]
     uint32_t task_cap;
     void *sub_rec;          // [n_parts * M] entries in sub-bucket order: SegRec32 / SegRec64, one
@@ -291,7 +292,18 @@ struct SegArgs {
     uint32_t super_cap;
     const SegSuper *supers;
     uint32_t n_supers;
+#ifdef UMIHIP_DEV
+    // development build: where seg_super_kernel's blocks add up the time they spend in each of their phases
+    // ([blocks][SEG_SUPER_PHASES] ticks of the 100 MHz clock, zeroed by the host; null: no stamps)
+    unsigned long long *super_stamps;
+#endif
 };
+// seg_super_kernel's phases (development build's stamps): records in, map built, ranks and placement, bit tests,
+// the hit rounds (decide and the unions), pointer jumping, atomicMin, label stores
+constexpr int SEG_SUPER_PHASES = 8;
+// the scan's word of a segment with super-bins, behind the chunks' status words: left 0 where every super-bin of the
+// segment is taken (none lies above the cap), so that a part-1 hit inside a super-bin is seg_super_kernel's for sure
+UMIHIP_HD inline uint32_t seg_scan_flag_word(uint32_t n_chunks, uint32_t seg) { return 1u + n_chunks + seg; }
 // exclusive scan of the bin counts -> bin_start, task list, counters[CNT_SEG_TASKS / _PAIRS];
 // then every entry of a segment is copied to its position in each part's sub-bucket order
 hipError_t launch_seg_build(const SegArgs &g, void *fkey, const int32_t *freq, bool key32,

@@ -375,7 +375,8 @@ class Pipeline {
     size_t seg_bins_bytes() const { return (pl.seg_bins * 4 + 15) & ~(size_t)15; }
     size_t seg_zero_bytes() const
     {
-        return (seg_bins_bytes() + (1 + pl.seg_chunks.size()) * sizeof(unsigned long long) + 15) & ~(size_t)15;
+        // (... and one word per segment: seg_scan_flag_word)
+        return (seg_bins_bytes() + (1 + pl.seg_chunks.size() + pl.segs.size()) * sizeof(unsigned long long) + 15) & ~(size_t)15;
     }
 
     // the plan's tables -- entry ranges, segment descriptors and scan chunks, popcount tile tasks --
@@ -915,7 +916,45 @@ class Pipeline {
             if (prof) HIP_TRY(hipEventRecord(ctx->ev[7], s));
             // (part 0's plain label stores all land before the pair kernel's first union: stream order)
             if (local_blocks) HIP_TRY(launch_seg_local(a, seg, percentage, local_blocks, s));
+#ifdef UMIHIP_DEV
+            // UMIHIP_SUPER_PHASES=<file>: the super-bin kernel's blocks stamp their phases, the call waits for them here
+            // and appends the phases' mean and maximum over the blocks to the file (a measuring run, never a timed one)
+            const char *phase_file = super_blocks ? getenv("UMIHIP_SUPER_PHASES") : nullptr;
+            if (phase_file && *phase_file) {
+                const size_t n_stamps = (size_t)super_blocks * SEG_SUPER_PHASES;
+                HIP_TRY(hipMalloc((void **)&super_seg.super_stamps, n_stamps * sizeof(unsigned long long)));
+                HIP_TRY(hipMemsetAsync(super_seg.super_stamps, 0, n_stamps * sizeof(unsigned long long), s));
+            }
+#endif
             if (super_blocks) HIP_TRY(launch_seg_super(a, super_seg, percentage, super_blocks, s));
+#ifdef UMIHIP_DEV
+            if (super_seg.super_stamps) {
+                std::vector<unsigned long long> ticks((size_t)super_blocks * SEG_SUPER_PHASES);
+                const hipError_t e = hipMemcpyAsync(ticks.data(), super_seg.super_stamps, ticks.size() * sizeof(unsigned long long),
+                                                    hipMemcpyDeviceToHost, s);
+                const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(s) : e;
+                (void)hipFree(super_seg.super_stamps);
+                HIP_TRY(e2);
+                if (FILE *f = fopen(phase_file, "a")) {
+                    static const char *const names[SEG_SUPER_PHASES] = {"records in", "map built", "ranks and placement",
+                        "bit tests (wave 0)", "hit rounds", "pointer jumping", "atomicMin", "label stores"};
+                    fprintf(f, "seg_super_kernel: %u blocks, us per block (100 MHz clock): phase, mean, max\n", super_blocks);
+                    double sum_mean = 0;
+                    for (int i = 0; i < SEG_SUPER_PHASES; i++) {
+                        unsigned long long tot = 0, mx = 0;
+                        for (uint32_t b = 0; b < super_blocks; b++) {
+                            const unsigned long long t = ticks[(size_t)b * SEG_SUPER_PHASES + i];
+                            tot += t;
+                            mx = std::max(mx, t);
+                        }
+                        sum_mean += (double)tot / super_blocks / 100.0;
+                        fprintf(f, "  %-22s %8.2f %8.2f\n", names[i], (double)tot / super_blocks / 100.0, (double)mx / 100.0);
+                    }
+                    fprintf(f, "  %-22s %8.2f\n", "all phases", sum_mean);
+                    fclose(f);
+                }
+            }
+#endif
             HIP_TRY(launch_seg_pairs(a, pair_seg, key32, percentage, part, n_parts, blocks, s));
             if (prof) HIP_TRY(hipEventRecord(ctx->ev[8], s));
             seg_timed = true;

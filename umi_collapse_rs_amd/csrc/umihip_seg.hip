@@ -76,6 +76,9 @@ __global__ __launch_bounds__(SCAN_THREADS) void seg_scan_kernel(SegArgs g, unsig
         uint32_t n_super = 0;
         for (uint32_t i = 0; i < nthr; i++) n_super += tcnt[t0 + i];
         if (super_taken(g, n_super)) no_tasks = (1u << SCAN_PER_THREAD) - 1u;
+        // a super-bin above the cap goes to the tiles: the segment's word says that not all of its super-bins are
+        // taken (the blocks that find one all store the same value; an empty or single entry holds no pair)
+        if (n_super > g.super_cap && threadIdx.x == t0) g.scan_state[seg_scan_flag_word(g.n_chunks, ch.seg)] = 1ull;
     } else {
 #pragma unroll
         for (int q = 0; q < SCAN_PER_THREAD; q++)
@@ -528,9 +531,12 @@ __device__ __forceinline__ uint32_t columns32(KeyT x, KeyT ky, int k, uint32_t l
 // counters "more than l bases differ so far" through v_bitop3: fourteen instructions per base and
 // 64 pairs at k = 1, 84 for the six compared bases of a 12-bp position, where the broadcast loop
 // above takes 320.  Bit j of the result: at most K bases of column j differ from the row.
-template <int K, int NB> __device__ __forceinline__ unsigned long long columns64_sliced(uint32_t x, uint32_t ky)
+// SUP: ... and one of the bases in sup_bases (bit b: base b of the compare key, wave-uniform) is among them -- part 1
+// of a segment whose super-bins are all taken: a pair that agrees on the bases a super-bin shares is not this tile's
+template <int K, int NB, bool SUP = false>
+__device__ __forceinline__ unsigned long long columns64_sliced(uint32_t x, uint32_t ky, uint32_t sup_bases = 0)
 {
-    uint32_t cl[K + 1], ch[K + 1];
+    uint32_t cl[K + 1], ch[K + 1], sl = 0, sh = 0;
 #pragma unroll
     for (int l = 0; l <= K; l++) cl[l] = ch[l] = 0u;
 #pragma unroll
@@ -546,11 +552,29 @@ template <int K, int NB> __device__ __forceinline__ unsigned long long columns64
         }
         cl[0] |= dl;
         ch[0] |= dh;
+        if (SUP && (sup_bases >> b) & 1u) {
+            sl |= dl;
+            sh |= dh;
+        }
     }
+    if (SUP) return (((unsigned long long)(sh & ~ch[K]) << 32) | (sl & ~cl[K]));
     return ~(((unsigned long long)ch[K] << 32) | cl[K]);
 }
-template <int K> __device__ __forceinline__ unsigned long long columns64_sliced_nb(uint32_t x, uint32_t ky, int nb)
+template <int K> __device__ __forceinline__ unsigned long long columns64_sliced_nb(uint32_t x, uint32_t ky, int nb, uint32_t sup_bases)
 {
+    if (K == 1 && sup_bases)
+        switch (nb) {
+        case 1: return columns64_sliced<1, 1, true>(x, ky, sup_bases);
+        case 2: return columns64_sliced<1, 2, true>(x, ky, sup_bases);
+        case 3: return columns64_sliced<1, 3, true>(x, ky, sup_bases);
+        case 4: return columns64_sliced<1, 4, true>(x, ky, sup_bases);
+        case 5: return columns64_sliced<1, 5, true>(x, ky, sup_bases);
+        case 6: return columns64_sliced<1, 6, true>(x, ky, sup_bases);
+        case 7: return columns64_sliced<1, 7, true>(x, ky, sup_bases);
+        case 8: return columns64_sliced<1, 8, true>(x, ky, sup_bases);
+        case 9: return columns64_sliced<1, 9, true>(x, ky, sup_bases);
+        default: return columns64_sliced<1, 10, true>(x, ky, sup_bases);
+        }
     switch (nb) { // (wave-uniform: the bases a compare key holds)
     case 1: return columns64_sliced<K, 1>(x, ky);
     case 2: return columns64_sliced<K, 2>(x, ky);
@@ -564,16 +588,17 @@ template <int K> __device__ __forceinline__ unsigned long long columns64_sliced_
     default: return columns64_sliced<K, 10>(x, ky);
     }
 }
-__device__ __forceinline__ unsigned long long columns64_sliced_k(uint32_t x, uint32_t ky, int k, int nb)
+// (sup_bases: only ever set at k = 1)
+__device__ __forceinline__ unsigned long long columns64_sliced_k(uint32_t x, uint32_t ky, int k, int nb, uint32_t sup_bases = 0)
 {
     switch (k) {
-    case 0: return columns64_sliced_nb<0>(x, ky, nb);
-    case 1: return columns64_sliced_nb<1>(x, ky, nb);
-    case 2: return columns64_sliced_nb<2>(x, ky, nb);
-    default: return columns64_sliced_nb<3>(x, ky, nb);
+    case 0: return columns64_sliced_nb<0>(x, ky, nb, 0u);
+    case 1: return columns64_sliced_nb<1>(x, ky, nb, sup_bases);
+    case 2: return columns64_sliced_nb<2>(x, ky, nb, 0u);
+    default: return columns64_sliced_nb<3>(x, ky, nb, 0u);
     }
 }
-__device__ __forceinline__ unsigned long long columns64_sliced_k(uint64_t, uint64_t, int, int) { return 0ull; } // (never: CK is 32-bit)
+__device__ __forceinline__ unsigned long long columns64_sliced_k(uint64_t, uint64_t, int, int, uint32_t = 0) { return 0ull; } // (never: CK is 32-bit)
 
 // ILP unions per lane, their steps interleaved: a union is a chain of dependent scattered accesses
 // (a load or a compare-and-swap per step, each a trip to the memory side), and a wave waits for
@@ -664,7 +689,9 @@ __global__ __launch_bounds__(64) void seg_pair_kernel(PairArgs a, SegArgs g, flo
     int ck_bases = 0;
     // a segment with super-bins, tasks of part 1: the filter-key bits of the bases a super-bin shares (as a part-0
     // bin code they are the super-bin's first bin), the bins of a super-bin, the segment's first part-0 bin
-    uint32_t sup_mask = 0, sup_bins = 0, sup_bin0 = 0;
+    // sup_tile: every super-bin of the segment is taken (the scan's word) and the tiles are bit-sliced -- the tile itself
+    // leaves out the pairs that agree on these bases of the compare key, and the drain has nothing to ask (sup_bins 0)
+    uint32_t sup_mask = 0, sup_bins = 0, sup_bin0 = 0, sup_tile = 0;
     const bool sliced = a.k <= 3 && g.col_sliced != 0;
     uint32_t nq = 0; // queued hits (wave-uniform); the queue outlives a task
 
@@ -817,6 +844,13 @@ __global__ __launch_bounds__(64) void seg_pair_kernel(PairArgs a, SegArgs g, flo
                 sup_mask = sg ? ((1u << (2 * (sd->nb[0] - sg))) - 1u) << (2 * sg) : 0u;
                 sup_bins = sg ? 1u << (2 * sg) : 0u; // (0: no super-bins here)
                 sup_bin0 = sd->bin_off[0];
+                // (k = 1: part 1's compare key holds all of part 0's bases, base b at place b; a segment that is one
+                // super-bin shares no base: the drain drops every hit of its part 1, as before)
+                sup_tile = 0u;
+                if (CK && sliced && sg && sg < sd->nb[0] && __builtin_amdgcn_readfirstlane((uint32_t)g.scan_state[seg_scan_flag_word(g.n_chunks, seg)]) == 0u) {
+                    sup_tile = ((1u << sd->nb[0]) - 1u) & ~((1u << sg) - 1u);
+                    sup_bins = 0u;
+                }
             }
             for (uint32_t c0 = col0; c0 < col1; c0 += 64) {
                 // (a task of several tiles -- a sub-bucket beyond 1025 entries: the next 64 columns
@@ -827,7 +861,7 @@ __global__ __launch_bounds__(64) void seg_pair_kernel(PairArgs a, SegArgs g, flo
                 const uint32_t nc = min(64u, end - c0);
                 unsigned long long h; // bit j: this lane's row is within k of column j of the tile
                 if (CK && sliced) {
-                    h = columns64_sliced_k(x, ky, a.k, ck_bases);
+                    h = columns64_sliced_k(x, ky, a.k, ck_bases, sup_tile);
                 } else {
                     uint32_t hlo = 0, hhi = 0;
                     hlo = columns32<CK, 0>(x, ky, a.k, lim2);
@@ -1204,8 +1238,21 @@ __global__ __launch_bounds__(64) void seg_local_kernel(PairArgs a, SegArgs g, fl
 // are compare-and-swaps, waves may race), one-way pairs to a private slot per wave, and the local kernel's
 // write-out: label[idx] = smallest entry index of idx's set, the forest flattened by pointer jumping first.  A key twice in the input shows when the map is
 // built: that super-bin's positions are walked pair by pair instead, where equal codes are a hit of distance 0.
+// (Components by rounds of min-label hooking in place of the unions were built and measured: slower)
 // Which super-bins: those of 2..super_cap entries, read off bin_start as the scan and the pair kernel do.
 constexpr int SUPER_RPT = 8; // records a thread keeps in registers: a block takes SUPER_RPT * its threads
+
+#ifdef UMIHIP_DEV
+// development build: the 100 MHz clock once everything this wave has asked of memory and LDS is back
+__device__ __forceinline__ unsigned long long super_clock()
+{
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+#endif
 
 template <bool CLUSTER, int NT>
 __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, float percentage)
@@ -1246,6 +1293,19 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
         }
         n_out += cnt;
     };
+#ifdef UMIHIP_DEV
+    // the time since the block's last stamp goes to phase i (thread 0: behind a barrier that is when the last wave
+    // arrived; between the bit tests and the hit rounds, which no barrier parts, it is the first wave's own time)
+    unsigned long long t_prev = g.super_stamps ? super_clock() : 0ull;
+    auto stamp = [&](int i) {
+        if (!g.super_stamps) return;
+        const unsigned long long now = super_clock();
+        if (tid == 0) g.super_stamps[(size_t)blockIdx.x * SEG_SUPER_PHASES + i] += now - t_prev;
+        t_prev = now;
+    };
+#else
+    auto stamp = [](int) {};
+#endif
     // a pair within one substitution at positions pa, pb (the whole wave calls, `has` says which lanes hold one)
     auto decide = [&](bool has, uint32_t pa, uint32_t pb) {
         const uint32_t ia = ix[pa], ib = ix[pb];
@@ -1286,6 +1346,7 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
             }
         }
         __syncthreads();
+        stamp(0);
         bool twice = false;
 #pragma unroll
         for (int r = 0; r < SUPER_RPT; r++)
@@ -1294,6 +1355,7 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
                 twice = twice || (atomicOr(&bm[rc[r] >> 5], bit) & bit) != 0u;
             }
         const bool dup = __syncthreads_or(twice ? 1 : 0) != 0;
+        stamp(1);
         if (!dup) {
             { // set bits before every word: a thread sums WPT words, the block scans the sums
                 uint32_t n_w[WPT], mine = 0;
@@ -1329,6 +1391,7 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
                     par[q] = q;
                 }
             __syncthreads();
+            stamp(2);
 #pragma unroll
             for (int r = 0; r < SUPER_RPT; r++) {
                 if ((uint32_t)r * NT >= c) break; // (block-uniform)
@@ -1344,6 +1407,7 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
                     }
                 }
                 if (tid + (uint32_t)r * NT >= c) m = 0u;
+                stamp(3);
                 while (__any(m != 0u)) { // one hit per lane and round
                     const bool has = m != 0u;
                     uint32_t pb = 0;
@@ -1354,6 +1418,7 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
                     }
                     decide(has, has ? rq[r] : 0u, pb);
                 }
+                stamp(4);
             }
         } else {
 #pragma unroll
@@ -1367,6 +1432,7 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
                 }
             }
             __syncthreads();
+            stamp(2);
             // every pair of positions p < q: a thread's own entries against the ones behind them, the wave in step
 #pragma unroll
             for (int r = 0; r < SUPER_RPT; r++) {
@@ -1383,6 +1449,7 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
             }
         }
         __syncthreads();
+        stamp(4);
         // the sets out: root position of every entry (into sc[], free now), the smallest entry index of every
         // set (fr[] of its root), label[] of every entry
         // (the forest stands still now, and its chains can be hundreds of positions long: every position jumps to
@@ -1398,14 +1465,17 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
             }
             if (!__syncthreads_or(moved ? 1 : 0)) break;
         }
+        stamp(5);
         for (uint32_t p = tid; p < c; p += NT) sc[p] = lds_ld(&par[p]);
         __syncthreads(); // (fr[] was read by the pairs until here)
         for (uint32_t p = tid; p < c; p += NT) fr[p] = 0xFFFFFFFFu;
         __syncthreads();
         for (uint32_t p = tid; p < c; p += NT) atomicMin(&fr[sc[p]], ix[p]);
         __syncthreads();
+        stamp(6);
         for (uint32_t p = tid; p < c; p += NT) g.uf_parent[ix[p]] = fr[sc[p]];
         __syncthreads(); // (the next super-bin's records overwrite these arrays)
+        stamp(7);
     }
     if (lane == 0) g.priv_cnt[my_slot] = min(n_out, SEG_PRIV_CAP);
     for (int off = 32; off > 0; off >>= 1) n_cand += __shfl_down(n_cand, off);
