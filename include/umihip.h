@@ -532,6 +532,47 @@ int umi_count_matrix(umi_ctx *ctx, const uint8_t *kept, const int32_t *freq, con
                      uint64_t n_buckets, const uint32_t *row, const uint32_t *col, uint32_t n_rows, uint32_t n_cols,
                      uint32_t *out_row, uint32_t *out_col, uint32_t *out_molecules, uint64_t *out_reads, uint64_t *nnz);
 
+/* ---- UMIs a group shows in several buckets (the program's --umi-filtering multi-gene): the molecules of a batched
+ *      call joined across its buckets, on the GPU.  A UMI that one cell shows under two or more genes is a chimera
+ *      or a mis-assignment: only the gene with the most reads keeps it, none where the top count is shared.  The
+ *      rule is Cell Ranger's and STARsolo's --soloUMIfiltering MultiGeneUMI_CR; no counterpart in the reference,
+ *      tests/multigene_model.py (filter_model) defines it.  Everything is exact integer arithmetic.
+ * in : keys: n_words words per entry, entry-major, umi_len in 1..UMI_MAX_WIDE_UMI_LEN, n_words = ceil(3 * umi_len /
+ *      64); no nmask: code 100 (N) is a letter of its own.  freq / kept / root: the N = bucket_off[n_buckets] entries
+ *      as a batched call took and wrote them (any byte of kept other than 0 counts as kept).  bucket_off: a HOST
+ *      array in both forms, [n_buckets + 1], starting at 0 and never falling.  group[b] < n_groups: the group (cell)
+ *      of bucket b; the groups of empty buckets are not looked at.
+ * A molecule is an entry with kept != 0; its UMI is its key's bits below 3 * umi_len (what lies above is not looked
+ * at), its reads are total[r] = the sum of freq[i] over root[i] == r (64 bits).  The molecules of non-empty
+ * buckets with the same (group, UMI) form a run, whatever their buckets are: the library never sees a gene, and two
+ * buckets are two candidates even where a caller gave them the same (cell, gene).  A run of one molecule survives.
+ * In a longer run the molecule whose total is strictly greater than every other's survives and the rest are
+ * removed; where two or more hold the greatest total, all molecules of the run are removed.
+ * out: kept_out[i] = 1 for the surviving molecules, 0 for every other entry.  freq_out (may be NULL): freq[i], or 0
+ *      where root[i] was removed: umi_count_matrix on (kept_out, freq_out) counts the molecules and reads of
+ *      survivors only.  counts[0] the runs of two or more molecules, counts[1] the molecules removed, counts[2]
+ *      the sum of their total.  Only kept_out[0..N) and freq_out[0..N) are written, and they must not be the
+ *      inputs.
+ * n_buckets == 0 or every bucket empty: UMI_OK, counts zeroed, nothing launched, nothing else touched.  A
+ * multi-device context uses its first device.  A deferred call (umi_dedup_batch_device_begin) that is out on the
+ * context ends first; its result keeps waiting for umi_dedup_batch_end.
+ * UMI_ERR_ARG: a NULL among ctx, counts and the arrays the call would touch, umi_len or n_words out of range, a
+ * bucket_off that does not start at 0 or that falls, 2^30 entries or buckets or more, kept_out == kept or freq_out
+ * == freq, n_groups == 0 with a non-empty bucket -- all found on the host before anything is launched.  Counted on
+ * the device and told after the call's synchronisation, the outputs then not defined and counts zeroed: a
+ * non-empty bucket whose group >= n_groups, a root[i] outside i's bucket or at an entry with kept == 0, a kept
+ * entry with root[i] != i.
+ * The _device form takes and leaves everything but bucket_off and counts in device memory, works on hip_stream
+ * and synchronises it once, at the end; the plain form copies host arrays in and out around it. */
+int umi_filter_multigene_device(umi_ctx *ctx, const uint64_t *d_keys, int n_words, int umi_len, const int32_t *d_freq,
+                                const uint8_t *d_kept, const uint32_t *d_root, const uint64_t *bucket_off,
+                                uint64_t n_buckets, const uint32_t *d_group, uint32_t n_groups, uint8_t *d_kept_out,
+                                int32_t *d_freq_out, uint64_t counts[3], void *hip_stream);
+int umi_filter_multigene(umi_ctx *ctx, const uint64_t *keys, int n_words, int umi_len, const int32_t *freq,
+                         const uint8_t *kept, const uint32_t *root, const uint64_t *bucket_off, uint64_t n_buckets,
+                         const uint32_t *group, uint32_t n_groups, uint8_t *kept_out, int32_t *freq_out,
+                         uint64_t counts[3]);
+
 /* ---- what a batched call did, as tables (the program's --output-stats): family sizes before and after, the mean
  *      UMI distance of every bucket before and after against a null, and how every UMI sequence is used, on the
  *      GPU.  No counterpart in the reference; the tables are umi_tools dedup --output-stats's, tests/stats_model.py

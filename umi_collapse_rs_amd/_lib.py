@@ -118,6 +118,11 @@ SIGNATURES = {
                                           C.c_void_p]),
     "umi_count_matrix": (C.c_int, [C.c_void_p, _u8p, _i32p, _u64p, C.c_uint64, _u32p, _u32p, C.c_uint32, C.c_uint32,
                                    _u32p, _u32p, _u32p, _u64p, _u64p]),
+    "umi_filter_multigene_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              _u64p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, _u64p,
+                                              C.c_void_p]),
+    "umi_filter_multigene": (C.c_int, [C.c_void_p, _u64p, C.c_int, C.c_int, _i32p, _u8p, _u32p, _u64p, C.c_uint64, _u32p,
+                                       C.c_uint32, _u8p, _i32p, _u64p]),
     "umi_dedup_stats_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _u64p,
                                          C.c_uint64, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_void_p]),

@@ -493,6 +493,48 @@ class Context:
                                              d_out_reads or None, C.byref(nnz), stream or None))
         return int(nnz.value)
 
+    def filter_multigene(self, keys, freq, kept, root, bucket_off, group, n_groups, umi_len, n_words=1, want_freq=True):
+        """UMIs a group shows in several buckets (umi_filter_multigene): keys uint64 [N * n_words], freq int32 [N], kept
+        uint8 [N] and root uint32 [N] of a batched call, bucket_off uint64 [n_buckets + 1], group uint32 [n_buckets]
+        the group (cell) of every bucket.  Among the kept entries of one group with one UMI only the one with
+        strictly the most reads survives.  Returns (kept_out uint8 [N], freq_out int32 [N] or None, dict of
+        runs, removed and removed_reads)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+        freq = np.ascontiguousarray(freq, dtype=np.int32)
+        kept = np.ascontiguousarray(kept, dtype=np.uint8)
+        root = np.ascontiguousarray(root, dtype=np.uint32)
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        group = np.ascontiguousarray(group, dtype=np.uint32)
+        n, nb = len(freq), len(bucket_off) - 1
+        if nb < 0 or len(group) != nb:
+            raise ValueError("group wants one element per bucket")
+        if len(kept) != n or len(root) != n or len(keys) != n * n_words or (nb and int(bucket_off.max()) > n):
+            raise ValueError("keys / freq / kept / root lengths differ, or bucket_off runs past them")
+        kept_out = np.zeros(n, np.uint8)
+        freq_out = np.zeros(n, np.int32) if want_freq else None
+        counts = np.zeros(3, np.uint64)
+        check(load().umi_filter_multigene(self._h, ptr(keys, C.c_uint64), n_words, umi_len, ptr(freq, C.c_int32),
+                                          ptr(kept, C.c_uint8), ptr(root, C.c_uint32), ptr(bucket_off, C.c_uint64), nb,
+                                          ptr(group, C.c_uint32), n_groups, ptr(kept_out, C.c_uint8),
+                                          ptr(freq_out, C.c_int32), ptr(counts, C.c_uint64)))
+        return kept_out, freq_out, self._multigene_counts(counts)
+
+    @staticmethod
+    def _multigene_counts(counts):
+        return {"runs": int(counts[0]), "removed": int(counts[1]), "removed_reads": int(counts[2])}
+
+    def filter_multigene_device(self, d_keys, d_freq, d_kept, d_root, bucket_off, d_group, n_groups, umi_len, d_kept_out,
+                                d_freq_out=0, n_words=1, stream=0):
+        """The same on raw device pointers (umi_filter_multigene_device; bucket_off stays on the host): fills
+        d_kept_out and, where given, d_freq_out (N elements each) and returns the dict of counts."""
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        counts = np.zeros(3, np.uint64)
+        check(load().umi_filter_multigene_device(self._h, d_keys or None, n_words, umi_len, d_freq or None, d_kept or None,
+                                                 d_root or None, ptr(bucket_off, C.c_uint64), len(bucket_off) - 1,
+                                                 d_group or None, n_groups, d_kept_out or None, d_freq_out or None,
+                                                 ptr(counts, C.c_uint64), stream or None))
+        return self._multigene_counts(counts)
+
     def dedup_stats(self, keys, freq, kept, root, bucket_off, umi_len, n_words=1, seed=0, hist_bins=65536, per_umi=True):
         """What a batched call did, as tables (umi_dedup_stats): keys uint64 [N * n_words], freq int32 [N], kept uint8
         [N] and root uint32 [N] of the call, bucket_off uint64 [n_buckets + 1].  Returns a dict: count_pre / count_post

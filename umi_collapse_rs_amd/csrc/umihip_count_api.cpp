@@ -1,4 +1,4 @@
-// Tables over a call's result: umi_count_matrix*, umi_dedup_stats*.
+// Tables over a call's result, and its filter: umi_count_matrix*, umi_filter_multigene*, umi_dedup_stats*.
 #include "umihip_host.hpp"
 
 #include <algorithm>
@@ -125,6 +125,123 @@ int umi_count_matrix(umi_ctx *ctx, const uint8_t *kept, const int32_t *freq, con
         (rc = io.close()))
         return rc;
     *nnz = got;
+    return UMI_OK;
+}
+
+} // extern "C"
+
+// ---- UMIs a group shows in several buckets ----------------------------------------------------------
+namespace {
+// what both forms check before a device is looked at (the context last)
+int mg_check(umi_ctx *ctx, const void *keys, int n_words, int umi_len, const void *freq, const void *kept, const void *root,
+             const uint64_t *bucket_off, uint64_t n_buckets, const void *group, const void *kept_out, const void *freq_out,
+             const uint64_t *counts)
+{
+    if (!counts) return fail(UMI_ERR_ARG, "counts is NULL");
+    if (umi_len < 1 || umi_len > UMI_MAX_WIDE_UMI_LEN)
+        return fail(UMI_ERR_ARG, "umi_len %d outside 1..%d", umi_len, UMI_MAX_WIDE_UMI_LEN);
+    if (n_words != wide_words(umi_len)) return fail(UMI_ERR_ARG, "n_words must be %d for umi_len %d", wide_words(umi_len), umi_len);
+    if (n_buckets >= (1ull << 30))
+        return fail(UMI_ERR_ARG, "%llu buckets exceed the 30-bit index space of one call", (unsigned long long)n_buckets);
+    if (n_buckets && !bucket_off) return fail(UMI_ERR_ARG, "bucket_off is NULL");
+    if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
+    const uint64_t n = n_buckets ? bucket_off[n_buckets] : 0; // (a table that falls: cm_walk's finding, on its one walk)
+    if (n >= (1ull << 30)) return fail(UMI_ERR_ARG, "%llu entries exceed the 30-bit index space of the call's sort", (unsigned long long)n);
+    if (n && (!keys || !freq || !kept || !root || !group || !kept_out)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (n && (kept_out == kept || (freq_out && freq_out == freq))) return fail(UMI_ERR_ARG, "an output is its own input");
+    if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
+    return UMI_OK;
+}
+
+// everything on the device (the context is the call's device, settled)
+int mg_run(umi_ctx *ctx, const uint64_t *d_keys, int n_words, int umi_len, const int32_t *d_freq, const uint8_t *d_kept,
+           const uint32_t *d_root, uint32_t m, const uint64_t *h_off, const uint32_t *h_idx, const uint32_t *d_group,
+           uint32_t n_groups, uint8_t *d_kept_out, int32_t *d_freq_out, uint64_t counts[3], hipStream_t s)
+{
+    int rc;
+    MultigeneCall c;
+    c.d_keys = d_keys;
+    c.d_freq = d_freq;
+    c.d_kept = d_kept;
+    c.d_root = d_root;
+    c.d_group = d_group;
+    c.h_off = h_off;
+    c.h_idx = h_idx;
+    c.n = (uint32_t)h_off[m];
+    c.m = m;
+    c.n_groups = n_groups;
+    c.n_cus = (uint32_t)ctx->n_cus;
+    c.umi_len = umi_len;
+    c.n_words = n_words;
+    c.d_kept_out = d_kept_out;
+    c.d_freq_out = d_freq_out;
+    c.h_pinned = ctx->h_counters;
+    if ((rc = ctx->call_ws.reserve(multigene_workspace_bytes(c.n, m, h_idx != nullptr)))) return rc;
+    const int r = multigene_on_device(ctx->call_ws.p, c, s);
+    if (r < 0) return fail(UMI_ERR_HIP, "multi-gene filter: %s", hipGetErrorString((hipError_t)(-r)));
+    if (ctx->h_counters[0])
+        return fail(UMI_ERR_ARG, "%llu non-empty buckets have a group id of %u or more", (unsigned long long)ctx->h_counters[0], n_groups);
+    if (ctx->h_counters[1])
+        return fail(UMI_ERR_ARG, "%llu entries have a root outside their bucket, at an entry that was not kept, or are kept "
+                                 "with another root than themselves", (unsigned long long)ctx->h_counters[1]);
+    for (int i = 0; i < 3; i++) counts[i] = ctx->h_counters[2 + i];
+    return UMI_OK;
+}
+} // namespace
+
+extern "C" {
+
+int umi_filter_multigene_device(umi_ctx *ctx, const uint64_t *d_keys, int n_words, int umi_len, const int32_t *d_freq,
+                                const uint8_t *d_kept, const uint32_t *d_root, const uint64_t *bucket_off, uint64_t n_buckets,
+                                const uint32_t *d_group, uint32_t n_groups, uint8_t *d_kept_out, int32_t *d_freq_out,
+                                uint64_t counts[3], void *hip_stream)
+{
+    int rc = mg_check(ctx, d_keys, n_words, umi_len, d_freq, d_kept, d_root, bucket_off, n_buckets, d_group, d_kept_out, d_freq_out, counts);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_count_matrix)
+    counts[0] = counts[1] = counts[2] = 0;
+    if (n_buckets == 0 || bucket_off[n_buckets] == 0) return UMI_OK;
+    if (n_groups == 0) return fail(UMI_ERR_ARG, "no groups with a non-empty bucket");
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
+    uint32_t m = 0;
+    const uint64_t *h_off = nullptr;
+    const uint32_t *h_idx = nullptr;
+    if ((rc = cm_walk(ctx, bucket_off, n_buckets, &m, &h_off, &h_idx))) return rc;
+    return mg_run(ctx, d_keys, n_words, umi_len, d_freq, d_kept, d_root, m, h_off, h_idx, d_group, n_groups, d_kept_out, d_freq_out,
+                  counts, (hipStream_t)hip_stream);
+}
+
+int umi_filter_multigene(umi_ctx *ctx, const uint64_t *keys, int n_words, int umi_len, const int32_t *freq, const uint8_t *kept,
+                         const uint32_t *root, const uint64_t *bucket_off, uint64_t n_buckets, const uint32_t *group,
+                         uint32_t n_groups, uint8_t *kept_out, int32_t *freq_out, uint64_t counts[3])
+{
+    int rc = mg_check(ctx, keys, n_words, umi_len, freq, kept, root, bucket_off, n_buckets, group, kept_out, freq_out, counts);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    counts[0] = counts[1] = counts[2] = 0;
+    if (n_buckets == 0 || bucket_off[n_buckets] == 0) return UMI_OK;
+    if (n_groups == 0) return fail(UMI_ERR_ARG, "no groups with a non-empty bucket");
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx);
+    uint32_t m = 0;
+    const uint64_t *h_off = nullptr;
+    const uint32_t *h_idx = nullptr;
+    if ((rc = cm_walk(ctx, bucket_off, n_buckets, &m, &h_off, &h_idx))) return rc; // (before anything is copied)
+    const size_t n = (size_t)bucket_off[n_buckets], nb = (size_t)n_buckets;
+    HostIo io(ctx);
+    const auto d_keys = io.in(keys, n * 8 * (size_t)n_words);
+    const auto d_freq = io.in(freq, n * 4);
+    const auto d_root = io.in(root, n * 4);
+    const auto d_group = io.in(group, nb * 4);
+    const auto d_fout = io.out(freq_out, n * 4);
+    const auto d_kept = io.in(kept, n);
+    const auto d_kout = io.out(kept_out, n);
+    if ((rc = io.open()) ||
+        (rc = mg_run(ctx, d_keys, n_words, umi_len, d_freq, d_kept, d_root, m, h_off, h_idx, d_group, n_groups, d_kout, d_fout, counts,
+                     io.stream())) ||
+        (rc = io.fetch(kept_out, d_kout, n)) || (rc = io.fetch(freq_out, d_fout, n)) || (rc = io.close()))
+        return rc;
     return UMI_OK;
 }
 

@@ -552,6 +552,27 @@ struct StatsCall {
 // One synchronisation, at the end.  0 ok; negative: -(hipError_t)
 int stats_on_device(void *workspace, const StatsCall &c, hipStream_t s);
 
+// ---- UMIs a group shows in several buckets (umihip_multigene.hip: umi_filter_multigene) ----
+size_t multigene_workspace_bytes(uint32_t n, uint32_t m, bool has_idx);
+struct MultigeneCall {
+    const uint64_t *d_keys;
+    const int32_t *d_freq;
+    const uint8_t *d_kept;
+    const uint32_t *d_root;
+    const uint32_t *d_group; // per bucket of the caller's table
+    const uint64_t *h_off;   // pinned: the m + 1 offsets of the m >= 1 non-empty buckets
+    const uint32_t *h_idx;   // pinned: their numbers in d_group (null: nothing was left out)
+    uint32_t n, m, n_groups, n_cus; // n = h_off[m] entries, 1 <= n < 2^30; n_groups >= 1
+    int umi_len, n_words;
+    uint8_t *d_kept_out;
+    int32_t *d_freq_out; // may be null
+    // 5 pinned words: non-empty buckets with a group out of range, entries with a bad root (either: the outputs are
+    // worthless), runs of two or more molecules, molecules removed, their reads
+    unsigned long long *h_pinned;
+};
+// One synchronisation, at the end.  0 ok; negative: -(hipError_t)
+int multigene_on_device(void *workspace, const MultigeneCall &c, hipStream_t s);
+
 // ---- sort and scan primitives of the staging (umihip_radix.hip) ----
 constexpr int RADIX_BINS = 256, RADIX_MAX_PASSES = 8; // 8-bit digits; a 64-bit key has at most eight
 constexpr int RADIX_HIST_PARTS = 2048;                // blocks of a kernel that counts digits, at most

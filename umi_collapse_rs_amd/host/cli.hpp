@@ -31,6 +31,17 @@
 // the GPU is woken.  Refused likewise, each with a message of its own: fastq mode, --two-pass (its windows never hold
 // the file's UMI usage), --dump-staging, --passthrough, --output-stats-seed without --output-stats or not a whole
 // number in 0..2^64-1.  The output BAM and the summary lines are as without the flag.
+// --umi-filtering none|multi-gene (with --per-gene; Cell Ranger's rule and STARsolo's --soloUMIfiltering
+// MultiGeneUMI_CR, not the reference's, tests/multigene_model.py defines it): none, the default, changes nothing.
+// multi-gene: after every (cell, gene) group has been collapsed, a UMI that one cell -- without --per-cell: the one
+// cell `all` -- still shows under two or more genes is a chimera or a mis-assignment; only the gene with the most reads
+// keeps it, none where the top count is shared.  One call to umi_filter_multigene (include/umihip.h) after the
+// collapse, over the staged keys and freq and the collapse's kept[] and root[] (asked of the collapse for the flag,
+// as --output-stats does); the records written, "Number of reads after deduplicating" and --count-matrix (which
+// leaves out a pair that lost all its molecules) follow the filtered mask, --output-stats keeps describing the
+// collapse.  With --devices the call runs on the first.  The summary gains "UMI filtering: multi-gene" and three
+// counts.  Refused with status 101 before the GPU is woken: any other value, multi-gene without --per-gene, the flag
+// given twice with different values.
 // --cell-whitelist-multi [--cell-quality-tag XX] [--cell-whitelist-min-posterior P] [--cell-whitelist-pseudocount N]
 // (with --cell-whitelist; after STARsolo's 1MM_multi[_pseudocounts] and Cell Ranger, tests/barcode_multi_model.py
 // defines it): a barcode one substitution from two or more listed ones is not dropped but weighed -- every
@@ -104,6 +115,8 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     std::string output_stats;        // --output-stats PREFIX: three tables on what the deduplication did
     uint64_t output_stats_seed = 0;  // --output-stats-seed S: the seed of the tables' null
     bool output_stats_seed_given = false;
+    std::string umi_filtering;       // --umi-filtering none|multi-gene: what is done to the collapsed UMIs across genes
+    bool umi_filtering_given = false, filter_multigene = false; // ... multi-gene (filled in by validate())
     bool edit_distance = false; // --distance edit: -k bounds the Levenshtein distance (umi_dedup_batch_edit)
     // filled in by validate(): --algo as UMI_ALGO_*, --merge as 0 any, 1 avgqual, 2 mapqual, and the two lists
     int algo_id = 0, merge_id = 0;
@@ -207,6 +220,11 @@ void usage()
               "                           --distance edit) and PREFIX_per_umi.tsv (how every UMI sequence is used)\n"
               "                           (bam/sam mode, one pass; not with --dump-staging, --passthrough)\n"
               "      --output-stats-seed <S> with --output-stats: seed of the null, 0..2^64-1 [default: 0]\n"
+              "      --umi-filtering <F>  none or multi-gene [default: none]; multi-gene, with --per-gene: a UMI that a cell\n"
+              "                           shows under several genes after the collapse is kept by the gene with the most\n"
+              "                           reads only, by none where the top count is shared (Cell Ranger, STARsolo's\n"
+              "                           MultiGeneUMI_CR); the records, the summary and --count-matrix follow, decided on\n"
+              "                           the GPU\n"
               "      --device <ID>        GPU to use [default: 0]\n"
               "      --devices <ID,..>    several GPUs of the node: alignment positions are sharded over them");
 }
@@ -286,6 +304,13 @@ Cli parse(int argc, char **argv)
             if (!digits || *end != '\0' || errno == ERANGE) die("--output-stats-seed wants a whole number in 0..2^64-1: '" + v + "'");
             c.output_stats_seed = (uint64_t)w;
             c.output_stats_seed_given = true;
+        }
+        else if (a == "--umi-filtering") {
+            const std::string v = need(i);
+            if (c.umi_filtering_given && c.umi_filtering != v)
+                die("--umi-filtering given twice with different values: '" + c.umi_filtering + "' and '" + v + "'");
+            c.umi_filtering = v;
+            c.umi_filtering_given = true;
         }
         else if (a == "--umi-whitelist") c.umi_whitelist = need(i);
         else if (a == "--whitelist-metrics") c.whitelist_metrics = need(i);
@@ -460,6 +485,11 @@ bool validate(Cli &args)
             die("--gene-tag wants a tag name of two characters, [A-Za-z][A-Za-z0-9]: '" + t + "'");
         if (!args.count_matrix.empty() && !args.dump_staging.empty()) die("--count-matrix does not go with --dump-staging");
     }
+    // --umi-filtering: likewise
+    if (args.umi_filtering_given && args.umi_filtering != "none" && args.umi_filtering != "multi-gene")
+        die("--umi-filtering wants none or multi-gene: '" + args.umi_filtering + "'");
+    args.filter_multigene = args.umi_filtering == "multi-gene";
+    if (args.filter_multigene && !args.per_gene) die("--umi-filtering multi-gene goes with --per-gene only");
     // --distance edit: everything about it that can be refused is, before the GPU is woken
     if (args.edit_distance) {
         if (args.mode == "fastq") die("--distance edit is defined in bam/sam mode only (whole reads are the key in fastq mode)");

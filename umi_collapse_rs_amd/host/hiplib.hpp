@@ -19,6 +19,8 @@
 // --output-stats PREFIX: likewise umi_dedup_stats.
 //
 // --cell-whitelist-multi: likewise umi_correct_barcodes_multi, in umi_correct_barcodes' place.
+//
+// --umi-filtering multi-gene: likewise umi_filter_multigene.
 #pragma once
 #include <chrono>
 #include <dlfcn.h>
@@ -87,6 +89,9 @@ struct HipLib {
     // --output-stats: likewise
     bool want_stats = false;
     decltype(&umi_dedup_stats) dedup_stats = nullptr;
+    // --umi-filtering multi-gene: likewise
+    bool want_multigene = false;
+    decltype(&umi_filter_multigene) filter_multigene = nullptr;
     // (the HIP runtime the library brings along: device buffers for the arrays above)
     int (*hip_set_device)(int) = nullptr; // (the current device is per thread: the context was made on another)
     int (*hip_malloc)(void **, size_t) = nullptr;
@@ -96,7 +101,8 @@ struct HipLib {
         : want_edit(args.edit_distance), want_consensus(args.consensus), want_consensus_bam(args.call_consensus),
           want_correct(!args.whitelist.empty()), want_barcodes(!args.cell_list.empty() && !args.cell_wl_multi),
           want_barcodes_multi(!args.cell_list.empty() && args.cell_wl_multi),
-          want_count(!args.count_matrix.empty()), want_stats(!args.output_stats.empty())
+          want_count(!args.count_matrix.empty()), want_stats(!args.output_stats.empty()),
+          want_multigene(args.filter_multigene)
     {
     }
     bool load()
@@ -139,6 +145,7 @@ struct HipLib {
         if (want_barcodes_multi) correct_barcodes_multi = (decltype(correct_barcodes_multi))sym("umi_correct_barcodes_multi");
         if (want_count) count_matrix = (decltype(count_matrix))sym("umi_count_matrix");
         if (want_stats) dedup_stats = (decltype(dedup_stats))sym("umi_dedup_stats");
+        if (want_multigene) filter_multigene = (decltype(filter_multigene))sym("umi_filter_multigene");
         hip_set_device = (decltype(hip_set_device))sym("hipSetDevice");
         hip_malloc = (decltype(hip_malloc))sym("hipMalloc");
         hip_memcpy = (decltype(hip_memcpy))sym("hipMemcpy");

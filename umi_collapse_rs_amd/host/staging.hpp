@@ -369,6 +369,7 @@ struct Summary {
     size_t n_positions = 0, nb = 0, n = 0, max_umi = 0;
     uint64_t n_kept = 0;
     size_t n_below = 0, n_without = 0; // --call-consensus
+    uint64_t mg_counts[3] = {0, 0, 0}; // --umi-filtering multi-gene: UMIs in several genes of a cell, molecules removed, their reads
     void print(const Cli &args, bool dump_exit = false) const
     {
         if (!dump_exit) {
@@ -410,6 +411,12 @@ struct Summary {
         std::fprintf(stderr, args.track_clusters ? "Number of groups of reads: %llu\n" : "Number of reads after deduplicating: %llu\n",
                      (unsigned long long)n_kept); // :259-266
         if (args.edit_distance) std::fprintf(stderr, "UMI distance: edit\n");
+        if (args.filter_multigene) {
+            std::fprintf(stderr, "UMI filtering: multi-gene\n");
+            std::fprintf(stderr, "Number of UMIs seen in several genes of a cell: %llu\n", (unsigned long long)mg_counts[0]);
+            std::fprintf(stderr, "Number of molecules removed as multi-gene UMIs: %llu\n", (unsigned long long)mg_counts[1]);
+            std::fprintf(stderr, "Number of reads in removed molecules: %llu\n", (unsigned long long)mg_counts[2]);
+        }
         if (args.call_consensus) {
             std::fprintf(stderr, "Number of clusters below --call-consensus-min-reads: %zu\n", n_below);
             std::fprintf(stderr, "Number of clusters without a consensus: %zu\n", n_without);

@@ -79,6 +79,11 @@
 // after deduplicating".
 // --output-stats PREFIX [--output-stats-seed S]: three tables on what the deduplication did, from one call to
 // umi_dedup_stats after the collapse (cli.hpp has the flag's definition and its refusals; output_stats() below).
+// --umi-filtering multi-gene (with --per-gene; cli.hpp has the flag's definition and its refusals): after the collapse
+// one call to umi_filter_multigene, group = the bucket's cell (one group without --per-cell); what it leaves --
+// kept_out, and freq_out for the matrix -- is what the records written, "Number of reads after deduplicating" and
+// --count-matrix see, which leaves out the pairs without a molecule; --output-stats sees the collapse's own kept[]
+// (filter_multigene() below).
 // --algo cluster: connected components of "within -k" (cli.hpp); every pipeline here only forwards the algorithm
 // to the library, so it goes with every flag --algo dir goes with.
 // Not implemented, as in the reference: --algo cc (that spelling stays refused; `cluster` is the mode's name).
@@ -133,7 +138,8 @@ struct OnePass {
     const int algo = args.algo_id, merge = args.merge_id;
     const unsigned T = std::max(1u, args.num_threads);
     const bool need_clusters = args.track_clusters || args.call_consensus; // every read's entry, every entry's root
-    const bool need_root = need_clusters || !args.output_stats.empty();    // root[] of the collapse (no host staging for it alone)
+    const bool need_root = need_clusters || !args.output_stats.empty() || args.filter_multigene; // root[] of the collapse (no host
+                                                                                                 // staging for it alone)
 
     umi::bam::File in;
     uint32_t n_rec = 0, chunk = 0; // records; records per thread of the per-read passes
@@ -180,6 +186,12 @@ struct OnePass {
     std::vector<uint8_t> kept;
     std::vector<uint32_t> root;
     umi_stats st;
+    // --umi-filtering multi-gene: what the filter leaves of kept[] and freq[]; `survivors` is the mask everything
+    // behind the collapse but --output-stats reads (kept[] itself without the flag)
+    std::vector<uint8_t> kept_filtered;
+    I32s freq_filtered;
+    uint64_t n_survivors = 0;
+    const std::vector<uint8_t> &survivors() const { return args.filter_multigene ? kept_filtered : kept; }
     std::vector<uint32_t> cluster_id, cluster_reads; // per entry (of its root): --tag, --call-consensus
     uint32_t n_clusters = 0;
     std::vector<uint32_t> staged_reads; // the staged reads in file order (with the two)
@@ -236,6 +248,7 @@ struct OnePass {
             return 0;
         }
         collapse();
+        if (args.filter_multigene) filter_multigene();
         if (!args.count_matrix.empty()) count_matrix();
         if (!args.output_stats.empty()) output_stats();
         if (need_clusters) number_clusters();
@@ -808,8 +821,28 @@ struct OnePass {
         // a second another 0.1 s, and the process ends below without running destructors)
     }
 
+    // --umi-filtering multi-gene: the molecules of one cell that share their UMI across its genes, decided in one call
+    // over the staged keys and freq and the collapse's kept[] and root[]
+    void filter_multigene()
+    {
+        kept_filtered.assign(n + 1, 0);
+        freq_filtered.assign(n + 1, 0);
+        if (n) {
+            need_ctx();
+            if (!lib.filter_multigene) die("libumihip.so lacks umi_filter_multigene");
+            const std::vector<uint32_t> one_group(args.per_cell ? 0 : nb, 0u);
+            if (lib.filter_multigene(ctx, keys.data(), n_words, (int)umi_length, freq.data(), kept.data(), root.data(), off.data(), nb,
+                                     args.per_cell ? bucket_cell.data() : one_group.data(), args.per_cell ? (uint32_t)n_cells : 1u,
+                                     kept_filtered.data(), freq_filtered.data(), sum.mg_counts) != UMI_OK)
+                die(lib.last_error());
+        }
+        n_survivors = st.n_kept - sum.mg_counts[1];
+        lap("multi-gene filter");
+    }
+
     // --count-matrix: molecules and reads per (cell, gene) in one call over the collapse's kept[] and the staged
-    // freq[], then the four files
+    // freq[] (with --umi-filtering multi-gene: what the filter left of both, and only the pairs that still hold a
+    // molecule), then the four files
     void count_matrix()
     {
         const uint32_t n_rows = (uint32_t)sum.n_genes, n_cols = args.per_cell ? (uint32_t)n_cells : 1u;
@@ -820,9 +853,9 @@ struct OnePass {
             need_ctx();
             if (!lib.count_matrix) die("libumihip.so lacks umi_count_matrix");
             const std::vector<uint32_t> one_column(args.per_cell ? 0 : nb, 0u);
-            if (lib.count_matrix(ctx, kept.data(), freq.data(), off.data(), nb, bucket_gene.data(),
-                                 args.per_cell ? bucket_cell.data() : one_column.data(), n_rows, n_cols, out_row.data(),
-                                 out_col.data(), molecules.data(), reads.data(), &nnz) != UMI_OK)
+            if (lib.count_matrix(ctx, survivors().data(), args.filter_multigene ? freq_filtered.data() : freq.data(), off.data(), nb,
+                                 bucket_gene.data(), args.per_cell ? bucket_cell.data() : one_column.data(), n_rows, n_cols,
+                                 out_row.data(), out_col.data(), molecules.data(), reads.data(), &nnz) != UMI_OK)
                 die(lib.last_error());
         }
         auto write = [&](const char *name, const std::string &text) {
@@ -839,10 +872,13 @@ struct OnePass {
         if (!args.per_cell) text = "all\n";
         for (size_t c = 0; c < n_cols && args.per_cell; c++) text.append(cell_names[c]).append("\n");
         write("barcodes.tsv", text);
+        uint64_t lines = nnz;
+        if (args.filter_multigene) lines = (uint64_t)std::count_if(molecules.begin(), molecules.begin() + nnz, [](uint32_t m) { return m != 0; });
         const std::string head = "%%MatrixMarket matrix coordinate integer general\n" + std::to_string(n_rows) + " " +
-                                 std::to_string(n_cols) + " " + std::to_string(nnz) + "\n";
+                                 std::to_string(n_cols) + " " + std::to_string(lines) + "\n";
         std::string mol = head, rd = head;
         for (uint64_t i = 0; i < nnz; i++) {
+            if (args.filter_multigene && molecules[i] == 0) continue; // (a pair whose molecules were all removed)
             const std::string at = std::to_string(out_row[i] + 1) + " " + std::to_string(out_col[i] + 1) + " ";
             mol.append(at).append(std::to_string(molecules[i])).append("\n");
             rd.append(at).append(std::to_string(reads[i])).append("\n");
@@ -930,8 +966,9 @@ struct OnePass {
     {
         if (args.track_clusters) return;
         if (args.paired) return select_paired();
+        const std::vector<uint8_t> &mask = survivors();
         for (size_t i = 0; i < n; i++)
-            if (kept[i]) out_records.push_back(rep[i]); // :227-231, in rank order per bucket
+            if (mask[i]) out_records.push_back(rep[i]); // :227-231, in rank order per bucket
     }
 
     // UcWriter (:382-459): every written paired record leaves (qname, mate ref, mate pos)
@@ -1145,7 +1182,7 @@ struct OnePass {
     void print_summary()
     {
         const double t_end = now_s();
-        sum.n_kept = st.n_kept;
+        sum.n_kept = args.filter_multigene ? n_survivors : st.n_kept;
         sum.print(args);
         std::fprintf(stderr,
                      "phases: read+inflate %.3f s, staging (%s) %.3f s, gpu init %.3f s, hot path (H2D+GPU+D2H) %.3f s [%llu pairs], write %.3f s\n",
