@@ -418,3 +418,60 @@ def assert_tight_pigeonhole(seqs, pairs, P):
     eq = equal_parts_of_pairs(seqs, pairs, P)
     assert frozenset([P - 1]) in eq, "no pair within k equal in part %d only" % (P - 1)
     assert frozenset([0]) in eq, "no pair within k equal in part 0 only"
+
+
+# ---- inputs for the pair lists themselves (tests/pair_list_model.py) --------------------------------
+# The segment index bins an entry, in every part, by the part's leading bases (plan_segment of umihip_plan.hpp:
+# as many as keep a sub-bucket around 32-64 entries, 2 at the least, the part's length at the most), and a
+# pair is found by every part in whose bin its two entries meet.
+
+def seg_bin_bases(n, L, k):
+    """[(first base, bases that index the bins)] of the k + 1 parts of a bucket of n entries, restated."""
+    P = k + 1
+    cap = max(2, min(12, (int(n).bit_length() - 1 - 4) // 2))
+    b = part_bounds(L, P)
+    return [(b[j], min(b[j + 1] - b[j], cap)) for j in range(P)]
+
+
+def seg_probe_entries(rng, L, k, part_len=None):
+    """dict UMI -> freq of pairs that only one route through the segment index finds, and of pairs that
+    several do.  Per part j a centre and a copy with one substitution at the first base of every other part:
+    distance exactly k, equal on part j, in one bin nowhere else.  Then a centre and a copy that differ in
+    the last base of the last part alone (one bin shared per part: every part finds the pair, the list wants
+    it once) and, for k >= 2, one with a substitution at the first base of every part but the first two.
+    Parts are cut from the first part_len bases.  Frequencies make the pairs symmetric, one-way and
+    not permitted at all in turn (p = 0.5)."""
+    part_len = min(part_len or L, L)
+    P = k + 1
+    b = part_bounds(part_len, P)
+    fr = [(1, 1), (5, 2), (3, 3)]
+    out = {}
+
+    def put(c, sites, t):
+        u = c.copy()
+        for i in sites:
+            u[i] = rng.choice(ALPHA[ALPHA != c[i]])
+        out.setdefault(c.tobytes().decode(), fr[t % 3][0])
+        out.setdefault(u.tobytes().decode(), fr[t % 3][1])
+
+    t = 0
+    for rep in range(3):  # (each kind of pair under each of the three freq relations)
+        for j in range(P):
+            put(rng.choice(ALPHA, L), [b[i] for i in range(P) if i != j], t + rep)
+            t += 1
+        put(rng.choice(ALPHA, L), [b[P] - 1], t + rep)
+        t += 1
+        if k >= 2:
+            put(rng.choice(ALPHA, L), [b[i] for i in range(2, P)], t + rep)
+            t += 1
+    return out
+
+
+def merged_bucket(*parts):
+    """One bucket of several (umis, freq) lists or dicts: the first freq of a UMI holds; rank order."""
+    out = {}
+    for p in parts:
+        for u, f in (p.items() if isinstance(p, dict) else zip(*p)):
+            out.setdefault(u, int(f))
+    umis, freq, _ = canonical(list(out), list(out.values()))
+    return umis, freq
