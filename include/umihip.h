@@ -136,7 +136,8 @@ const char *umi_last_error(void);
  *   "seg_super_bases" 0..4 (default 0): g; 0 = the largest for which the other bases number at most 8 and the expected
  *                    run n / 4^(bin bases - g) lies between "seg_super_min" and 3/4 of "seg_super_cap", another
  *                    value = that g where those conditions hold (else none)
- *   "seg_super_cap"  2..8192 (default 5632): largest run that kernel takes (LDS: 16 bytes per entry + 16 KB); a larger
+ *   "seg_super_cap"  2..8192 (default 5632): largest run that kernel takes (LDS: 16 bytes per entry + 16 KB + a hit queue of 512 bytes
+ *                    per wave -- 155,648 bytes at 8192 with 1,024 threads, 51,200 at 2048 with 256); a larger
  *                    one goes through the pair kernel whole
  *   "seg_super_min"  2..8192 (default 1024): smallest expected run the path is planned for
  *   "collapse_kept_only" 0/1 (default 1): a batched directional call without d_root leaves the union-find

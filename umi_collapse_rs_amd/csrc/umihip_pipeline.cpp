@@ -937,7 +937,7 @@ class Pipeline {
                 HIP_TRY(e2);
                 if (FILE *f = fopen(phase_file, "a")) {
                     static const char *const names[SEG_SUPER_PHASES] = {"records in", "map built", "ranks and placement",
-                        "bit tests (wave 0)", "hit rounds", "pointer jumping", "atomicMin", "label stores"};
+                        "bit tests, pushes (w0)", "drains", "pointer jumping", "atomicMin", "label stores"};
                     fprintf(f, "seg_super_kernel: %u blocks, us per block (100 MHz clock): phase, mean, max\n", super_blocks);
                     double sum_mean = 0;
                     for (int i = 0; i < SEG_SUPER_PHASES; i++) {

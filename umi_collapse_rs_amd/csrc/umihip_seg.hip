@@ -1234,13 +1234,24 @@ __global__ __launch_bounds__(64) void seg_local_kernel(PairArgs a, SegArgs g, fl
 // filter key's 2 bits per base with the shared bases squeezed out, at most SEG_SUPER_MAX_REST bases), the
 // super-bin a bitmap of 4^rest bits; the rest is seg_local_kernel's lookup path with many waves: records read
 // once and kept in registers until the rank of their code is known, 3 * rest single-bit tests per entry for the
-// partners with the larger code, symmetric pairs united in an LDS forest over positions (lds_union_halving: hooks
+// partners with the larger code, the hits queued per wave and decided 64 at a time (SUPER_HITQ below), symmetric
+// pairs united in an LDS forest over positions (lds_union_halving: hooks
 // are compare-and-swaps, waves may race), one-way pairs to a private slot per wave, and the local kernel's
 // write-out: label[idx] = smallest entry index of idx's set, the forest flattened by pointer jumping first.  A key twice in the input shows when the map is
 // built: that super-bin's positions are walked pair by pair instead, where equal codes are a hit of distance 0.
 // (Components by rounds of min-label hooking in place of the unions were built and measured: slower)
 // Which super-bins: those of 2..super_cap entries, read off bin_start as the scan and the pair kernel do.
 constexpr int SUPER_RPT = 8; // records a thread keeps in registers: a block takes SUPER_RPT * its threads
+// The hits are not decided where the bit tests find them -- a trip of that loop has a few lanes of 64 live and
+// pays the whole chain of LDS latencies for them -- but queued per wave and worked off 64 at a time, as
+// seg_local_kernel does it.  A word of the queue: the record's own position (13 bits) | its partner << 13, the
+// partner's rest-code (16 bits; its rank is looked up in the drain) or, in the walk, the partner's position.
+// A wave reads and writes its own queue alone: no block barrier.  A push finds fewer than SUPER_DRAIN_AT hits
+// queued (else the push before it had drained) and adds one per lane at most.
+constexpr uint32_t SUPER_DRAIN_AT = 64;
+constexpr uint32_t SUPER_HITQ = SUPER_DRAIN_AT + 64; // words per wave
+static_assert(SUPER_DRAIN_AT - 1 + 64 <= SUPER_HITQ, "the fullest queue a push can leave");
+static_assert(SEG_SUPER_MAX_CAP <= (1u << 13) && 2 * SEG_SUPER_MAX_REST + 13 <= 32, "a position and a rest-code in one word");
 
 #ifdef UMIHIP_DEV
 // development build: the 100 MHz clock once everything this wave has asked of memory and LDS is back
@@ -1267,6 +1278,7 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
     __shared__ uint32_t wsum[NW];
     const uint32_t tid = threadIdx.x, wave = tid >> 6;
     const int lane = (int)(tid & 63u);
+    uint32_t *hitq = pre + SEG_SUPER_WORDS + wave * SUPER_HITQ; // this wave's hits (seg_super_lds_bytes)
     const SegRec32 *__restrict__ sub = (const SegRec32 *)g.sub_rec;
     unsigned int n_cand = 0, n_direct = 0;
     // one-way pairs: to this wave's private slot, wave-uniform fill level; a slot that is full sends the rest to
@@ -1295,7 +1307,7 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
     };
 #ifdef UMIHIP_DEV
     // the time since the block's last stamp goes to phase i (thread 0: behind a barrier that is when the last wave
-    // arrived; between the bit tests and the hit rounds, which no barrier parts, it is the first wave's own time)
+    // arrived; between the bit tests with their pushes and the drains, which no barrier parts, it is the first wave's own time)
     unsigned long long t_prev = g.super_stamps ? super_clock() : 0ull;
     auto stamp = [&](int i) {
         if (!g.super_stamps) return;
@@ -1323,6 +1335,35 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
             lds_union_halving(par, min(pa, pb), max(pa, pb));
         }
         emit(fwd != bwd, fwd ? gi : gj, fwd ? gj : gi);
+    };
+    auto rank_of = [&](uint32_t s) { // entries of the super-bin with a smaller rest-code = the position of s's
+        return pre[s >> 5] + (uint32_t)__builtin_popcount(bm[s >> 5] & ((1u << (s & 31u)) - 1u));
+    };
+    // the wave's queue: the newest 64 hits decided, one per lane (fewer only in the drain that empties it);
+    // walk (block-uniform): the partner is a position, not a rest-code
+    uint32_t nq = 0; // (wave-uniform)
+    auto drain = [&](bool walk) {
+        const uint32_t n = min(nq, 64u);
+        nq -= n;
+        // (the wave's own stores, in program order on the LDS: the compiler must not move the loads above them)
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const bool has = (uint32_t)lane < n;
+        const uint32_t h = has ? hitq[nq + (uint32_t)lane] : 0u;
+        const uint32_t x = h >> 13;
+        decide(has, h & 0x1FFFu, walk ? x : rank_of(x)); // (an idle lane: position 0 twice, nothing decided)
+        __builtin_amdgcn_wave_barrier(); // (the queue is read before the next push writes it)
+    };
+    // one hit per lane and trip into the queue
+    auto push = [&](bool has, uint32_t h, bool walk) {
+        const unsigned long long bal = __ballot(has);
+        if (has) hitq[nq + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1ull))] = h;
+        nq += (uint32_t)__builtin_popcountll(bal);
+        if (nq >= SUPER_DRAIN_AT) {
+            stamp(3);
+            drain(walk);
+            stamp(4);
+        }
     };
 
     for (uint32_t u = blockIdx.x; u < g.n_supers; u += gridDim.x) {
@@ -1377,9 +1418,6 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
                 }
             }
             __syncthreads();
-            auto rank_of = [&](uint32_t s) { // entries of the super-bin with a smaller rest-code = the position of s's
-                return pre[s >> 5] + (uint32_t)__builtin_popcount(bm[s >> 5] & ((1u << (s & 31u)) - 1u));
-            };
 #pragma unroll
             for (int r = 0; r < SUPER_RPT; r++)
                 if (tid + (uint32_t)r * NT < c) {
@@ -1396,6 +1434,8 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
             for (int r = 0; r < SUPER_RPT; r++) {
                 if ((uint32_t)r * NT >= c) break; // (block-uniform)
                 const uint32_t s = rc[r];
+                // (the compiler puts each load under its test's condition, 24 LDS waits in a row; 17 words loaded by hand
+                // ahead of the tests took 2 us off this phase and 15 more VGPRs, and the step did not show it: DESIGN.md 5a)
                 uint32_t m = 0; // bit 3 b + d - 1: the entry with base b changed by d is there, behind this one
 #pragma unroll
                 for (int bb = 0; bb < SEG_SUPER_MAX_REST; bb++) {
@@ -1407,19 +1447,19 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
                     }
                 }
                 if (tid + (uint32_t)r * NT >= c) m = 0u;
-                stamp(3);
-                while (__any(m != 0u)) { // one hit per lane and round
+                while (__any(m != 0u)) { // one hit per lane and trip
                     const bool has = m != 0u;
-                    uint32_t pb = 0;
+                    uint32_t h = 0;
                     if (has) {
                         const int j = __builtin_ctz(m), bb = j / 3;
                         m &= m - 1u;
-                        pb = rank_of(s ^ ((uint32_t)(j - 3 * bb + 1) << (2 * bb)));
+                        h = rq[r] | ((s ^ ((uint32_t)(j - 3 * bb + 1) << (2 * bb))) << 13);
                     }
-                    decide(has, has ? rq[r] : 0u, pb);
+                    push(has, h, false);
                 }
-                stamp(4);
             }
+            stamp(3);
+            if (nq) drain(false); // (what is left, fewer than 64: the queue is empty for the write-out and the next super-bin)
         } else {
 #pragma unroll
             for (int r = 0; r < SUPER_RPT; r++) {
@@ -1444,9 +1484,11 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
                     const uint32_t q = p + i;
                     const uint32_t z = s ^ (q < c ? sc[q] : 0u);
                     const bool hit = p < c && q < c && __builtin_popcount((z | (z >> 1)) & 0x55555555u) <= 1;
-                    if (__any(hit)) decide(hit, hit ? p : 0u, hit ? q : 0u);
+                    if (__any(hit)) push(hit, p | (q << 13), true);
                 }
             }
+            stamp(3);
+            if (nq) drain(true);
         }
         __syncthreads();
         stamp(4);
@@ -1629,8 +1671,16 @@ hipError_t launch_seg_local(const PairArgs &a, const SegArgs &g, float percentag
     return hipGetLastError();
 }
 
-// (the records and the forest, the bitmap and its prefix: 106,496 bytes at the default cap -- one block to a CU's 160 KB)
-size_t seg_super_lds_bytes(uint32_t cap) { return ((size_t)4 * cap + 2 * SEG_SUPER_WORDS) * sizeof(uint32_t); }
+// (the records and the forest, 16 bytes per entry; the bitmap and its prefix, 16 KB; a hit queue of SUPER_HITQ words per
+// wave, 8 KB for 1,024 threads and 2 KB for 256 -- the kernel lays them out in this order.  1,024 threads: 114,688 bytes
+// at the default cap, 155,648 at SEG_SUPER_MAX_CAP; 256 threads: 51,200 at SEG_SUPER_SMALL.  One block to a CU's 160 KB.)
+size_t seg_super_lds_bytes(uint32_t cap)
+{
+    const uint32_t n_waves = seg_super_threads(cap) / 64u;
+    return ((size_t)4 * cap + 2 * SEG_SUPER_WORDS + (size_t)n_waves * SUPER_HITQ) * sizeof(uint32_t);
+}
+static_assert(((size_t)4 * SEG_SUPER_MAX_CAP + 2 * SEG_SUPER_WORDS + 16 * SUPER_HITQ) * sizeof(uint32_t) + 64 <= 160 * 1024,
+              "the largest block and its wave sums fit a CU's LDS");
 
 // its persistent grid: one block per CU at most, no more than there are super-bins
 uint32_t seg_super_blocks(uint32_t n_supers, uint32_t n_cus) { return n_supers < n_cus ? n_supers : n_cus; }
