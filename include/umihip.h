@@ -574,6 +574,55 @@ int umi_filter_multigene(umi_ctx *ctx, const uint64_t *keys, int n_words, int um
                          const uint32_t *group, uint32_t n_groups, uint8_t *kept_out, int32_t *freq_out,
                          uint64_t counts[3]);
 
+/* ---- cell calling (the program's --cell-filter): which columns of a count matrix are cells, their table, the
+ *      run's summary numbers and the filtered matrix, on the GPU.  The rules are STARsolo's --soloCellFilter
+ *      CellRanger2.2 (Cell Ranger 2.2's knee) and TopCells, and a plain threshold; no counterpart in the reference,
+ *      tests/cells_model.py (call_model) defines them.  Everything is exact integer arithmetic.
+ * in : the nnz triplets (row, col, molecules, reads) as umi_count_matrix leaves them: sorted by col, then row, every
+ *      (col, row) pair once; a triplet may have 0 molecules.
+ * For column c: T[c] the sum of molecules and R[c] the sum of reads (64 bits), G[c] its triplets with molecules > 0.
+ * The candidates are the n columns with T[c] >= 1, S[0..n) their totals in descending order.  A rule yields one
+ * threshold t, and column c is called iff T[c] >= 1 && T[c] >= t: a tie at the threshold is called whole.
+ *   UMI_CELLS_CR22: i = min(n - 1, floor(expect_cells * (1000 - percentile_permille) / 1000)), m = S[i],
+ *                   t = max(1, floor((2 m + max_min_ratio) / (2 max_min_ratio))) -- m / max_min_ratio rounded half up.
+ *                   STARsolo's defaults are 3000, 990 and 10.
+ *   UMI_CELLS_TOP : t = S[min(n - 1, expect_cells - 1)].
+ *   UMI_CELLS_MIN : t = max(1, min_molecules).
+ *   n == 0        : t = 0, nothing is called.
+ * A rule reads only the parameters named in its line; the others are not looked at.
+ * out: per column, n_cols elements each: cell_molecules = T, cell_reads = R, cell_genes = G, called (0 or 1) and
+ *      new_col, the called columns' dense number in ascending col, 0xFFFFFFFF where the column is not called.  The
+ *      filtered triplets (room for nnz each): the triplets of called columns with molecules > 0, in their input
+ *      order, col replaced by new_col; *nnz_out their number; what lies behind is not defined.  counts[0] candidates,
+ *      [1] called, [2] t, [3] m (0 under the other rules), [4] molecules and [5] reads in called columns, [6] all
+ *      molecules, [7] all reads, [8] the median of T and [9] of G over the called columns: the lower median, element
+ *      floor((k - 1) / 2) of the k values in ascending order, 0 for k = 0.
+ * nnz == 0: UMI_OK, the per-column arrays zeroed (new_col all ones), counts zeroed, *nnz_out = 0, nothing launched.
+ * A multi-device context uses its first device.  A deferred call (umi_dedup_batch_device_begin) that is out on the
+ * context ends first; its result keeps waiting for umi_dedup_batch_end.
+ * UMI_ERR_ARG, found on the host before anything is launched: a NULL among ctx, nnz_out, counts and the arrays the
+ * call would touch, nnz or n_cols >= 2^30, n_cols == 0 or n_rows == 0 with nnz > 0, an unknown rule, expect_cells
+ * < 1, percentile_permille outside 0..1000 or max_min_ratio < 1 where the rule reads them.  Counted on the device and
+ * told after the call's one synchronisation, *nnz_out then 0 and the outputs not defined: UMI_ERR_ARG for a triplet
+ * with row >= n_rows or col >= n_cols, UMI_ERR_ORDER for triplets that are not strictly increasing in (col, row).
+ * The _device form takes and leaves everything but nnz_out and counts in device memory, works on hip_stream and
+ * synchronises it once, at the end; the plain form copies host arrays in and out around it. */
+#define UMI_CELLS_CR22 0
+#define UMI_CELLS_TOP 1
+#define UMI_CELLS_MIN 2
+int umi_call_cells_device(umi_ctx *ctx, const uint32_t *d_row, const uint32_t *d_col, const uint32_t *d_molecules,
+                          const uint64_t *d_reads, uint64_t nnz, uint32_t n_rows, uint32_t n_cols, int rule,
+                          int64_t expect_cells, int percentile_permille, int64_t max_min_ratio, int64_t min_molecules,
+                          uint64_t *d_cell_molecules, uint64_t *d_cell_reads, uint32_t *d_cell_genes, uint8_t *d_called,
+                          uint32_t *d_new_col, uint32_t *d_out_row, uint32_t *d_out_col, uint32_t *d_out_molecules,
+                          uint64_t *d_out_reads, uint64_t *nnz_out, uint64_t counts[10], void *hip_stream);
+int umi_call_cells(umi_ctx *ctx, const uint32_t *row, const uint32_t *col, const uint32_t *molecules,
+                   const uint64_t *reads, uint64_t nnz, uint32_t n_rows, uint32_t n_cols, int rule, int64_t expect_cells,
+                   int percentile_permille, int64_t max_min_ratio, int64_t min_molecules, uint64_t *cell_molecules,
+                   uint64_t *cell_reads, uint32_t *cell_genes, uint8_t *called, uint32_t *new_col, uint32_t *out_row,
+                   uint32_t *out_col, uint32_t *out_molecules, uint64_t *out_reads, uint64_t *nnz_out,
+                   uint64_t counts[10]);
+
 /* ---- what a batched call did, as tables (the program's --output-stats): family sizes before and after, the mean
  *      UMI distance of every bucket before and after against a null, and how every UMI sequence is used, on the
  *      GPU.  No counterpart in the reference; the tables are umi_tools dedup --output-stats's, tests/stats_model.py

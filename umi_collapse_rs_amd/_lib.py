@@ -11,6 +11,7 @@ UMI_OK = 0
 UMI_ERR_ARG, UMI_ERR_HIP, UMI_ERR_ORDER, UMI_ERR_NOMEM, UMI_ERR_NODEV, UMI_ERR_CHAR = (
     -1, -2, -3, -4, -5, -6)
 UMI_ALGO_DIRECTIONAL, UMI_ALGO_ADJACENCY, UMI_ALGO_CLUSTER = 0, 1, 2
+UMI_CELLS_CR22, UMI_CELLS_TOP, UMI_CELLS_MIN = 0, 1, 2   # the rules of umi_call_cells
 UMI_MAX_UMI_LEN = 21
 UMI_KERNEL_EDIT_PAIRS = 4     # Stats.kernel_id of umi_dedup_batch_edit (with "profile")
 UMI_MAX_CONS_LEN = 1024       # umi_consensus_bam: bases of a cluster, at most
@@ -123,6 +124,13 @@ SIGNATURES = {
                                               C.c_void_p]),
     "umi_filter_multigene": (C.c_int, [C.c_void_p, _u64p, C.c_int, C.c_int, _i32p, _u8p, _u32p, _u64p, C.c_uint64, _u32p,
                                        C.c_uint32, _u8p, _i32p, _u64p]),
+    "umi_call_cells_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                        C.c_uint32, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, _u64p, _u64p, C.c_void_p]),
+    "umi_call_cells": (C.c_int, [C.c_void_p, _u32p, _u32p, _u32p, _u64p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int,
+                                 C.c_int64, C.c_int, C.c_int64, C.c_int64, _u64p, _u64p, _u32p, _u8p, _u32p, _u32p, _u32p,
+                                 _u32p, _u64p, _u64p, _u64p]),
     "umi_dedup_stats_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _u64p,
                                          C.c_uint64, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_void_p]),

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (UMI_ALGO_ADJACENCY, UMI_ALGO_CLUSTER, UMI_ALGO_DIRECTIONAL, Stats, UmiHipError, check, load, ptr)
+from ._lib import (UMI_ALGO_ADJACENCY, UMI_ALGO_CLUSTER, UMI_ALGO_DIRECTIONAL, UMI_CELLS_CR22, Stats, UmiHipError, check, load, ptr)
 
 
 def to_bitset(umis, umi_len=None):
@@ -534,6 +534,61 @@ class Context:
                                                  d_group or None, n_groups, d_kept_out or None, d_freq_out or None,
                                                  ptr(counts, C.c_uint64), stream or None))
         return self._multigene_counts(counts)
+
+    CELLS_COUNTS = ("candidates", "called", "threshold", "knee", "molecules_in_cells", "reads_in_cells", "molecules", "reads",
+                    "median_molecules", "median_genes")
+
+    def call_cells(self, row, col, molecules, reads, n_rows, n_cols, rule=UMI_CELLS_CR22, expect_cells=3000,
+                   percentile_permille=990, max_min_ratio=10, min_molecules=1):
+        """Which columns of a count matrix are cells (umi_call_cells): the triplets row / col / molecules uint32 [nnz]
+        and reads uint64 [nnz] as count_matrix returns them, sorted by column, then row.  Returns (dict of the
+        per-column arrays cell_molecules, cell_reads uint64, cell_genes uint32, called uint8 and new_col uint32
+        [n_cols], the filtered triplets (row, col, molecules, reads) of the called columns, dict of the counts
+        CELLS_COUNTS)."""
+        row = np.ascontiguousarray(row, dtype=np.uint32)
+        col = np.ascontiguousarray(col, dtype=np.uint32)
+        molecules = np.ascontiguousarray(molecules, dtype=np.uint32)
+        reads = np.ascontiguousarray(reads, dtype=np.uint64)
+        nnz = len(row)
+        if len(col) != nnz or len(molecules) != nnz or len(reads) != nnz:
+            raise ValueError("row / col / molecules / reads lengths differ")
+        per = {"cell_molecules": np.zeros(n_cols, np.uint64), "cell_reads": np.zeros(n_cols, np.uint64),
+               "cell_genes": np.zeros(n_cols, np.uint32), "called": np.zeros(n_cols, np.uint8),
+               "new_col": np.zeros(n_cols, np.uint32)}
+        m = max(1, nnz)
+        o_row, o_col, o_mol = (np.zeros(m, np.uint32) for _ in range(3))
+        o_reads = np.zeros(m, np.uint64)
+        nnz_out = C.c_uint64(0)
+        counts = np.zeros(10, np.uint64)
+        check(load().umi_call_cells(self._h, ptr(row, C.c_uint32), ptr(col, C.c_uint32), ptr(molecules, C.c_uint32),
+                                    ptr(reads, C.c_uint64), nnz, n_rows, n_cols, rule, expect_cells, percentile_permille,
+                                    max_min_ratio, min_molecules, ptr(per["cell_molecules"], C.c_uint64),
+                                    ptr(per["cell_reads"], C.c_uint64), ptr(per["cell_genes"], C.c_uint32),
+                                    ptr(per["called"], C.c_uint8), ptr(per["new_col"], C.c_uint32), ptr(o_row, C.c_uint32),
+                                    ptr(o_col, C.c_uint32), ptr(o_mol, C.c_uint32), ptr(o_reads, C.c_uint64),
+                                    C.byref(nnz_out), ptr(counts, C.c_uint64)))
+        z = int(nnz_out.value)
+        return per, (o_row[:z], o_col[:z], o_mol[:z], o_reads[:z]), self._cells_counts(counts)
+
+    @classmethod
+    def _cells_counts(cls, counts):
+        return {name: int(v) for name, v in zip(cls.CELLS_COUNTS, counts)}
+
+    def call_cells_device(self, d_row, d_col, d_molecules, d_reads, nnz, n_rows, n_cols, d_cell_molecules, d_cell_reads,
+                          d_cell_genes, d_called, d_new_col, d_out_row, d_out_col, d_out_molecules, d_out_reads,
+                          rule=UMI_CELLS_CR22, expect_cells=3000, percentile_permille=990, max_min_ratio=10, min_molecules=1,
+                          stream=0):
+        """The same on raw device pointers (umi_call_cells_device): fills the five per-column arrays (n_cols
+        elements each) and the filtered triplets (room for nnz each); returns (nnz_out, dict of the counts)."""
+        nnz_out = C.c_uint64(0)
+        counts = np.zeros(10, np.uint64)
+        check(load().umi_call_cells_device(self._h, d_row or None, d_col or None, d_molecules or None, d_reads or None, nnz,
+                                           n_rows, n_cols, rule, expect_cells, percentile_permille, max_min_ratio,
+                                           min_molecules, d_cell_molecules or None, d_cell_reads or None,
+                                           d_cell_genes or None, d_called or None, d_new_col or None, d_out_row or None,
+                                           d_out_col or None, d_out_molecules or None, d_out_reads or None,
+                                           C.byref(nnz_out), ptr(counts, C.c_uint64), stream or None))
+        return int(nnz_out.value), self._cells_counts(counts)
 
     def dedup_stats(self, keys, freq, kept, root, bucket_off, umi_len, n_words=1, seed=0, hist_bins=65536, per_umi=True):
         """What a batched call did, as tables (umi_dedup_stats): keys uint64 [N * n_words], freq int32 [N], kept uint8

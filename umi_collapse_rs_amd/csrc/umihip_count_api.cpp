@@ -1,4 +1,4 @@
-// Tables over a call's result, and its filter: umi_count_matrix*, umi_filter_multigene*, umi_dedup_stats*.
+// Tables over a call's result, and its filters: umi_count_matrix*, umi_filter_multigene*, umi_dedup_stats*, umi_call_cells*.
 #include "umihip_host.hpp"
 
 #include <algorithm>
@@ -424,6 +424,171 @@ int umi_dedup_stats(umi_ctx *ctx, const uint64_t *keys, int n_words, const int32
         (rc = io.close()))
         return rc;
     if (n_umis) *n_umis = rows;
+    return UMI_OK;
+}
+
+} // extern "C"
+
+// ---- which columns of a count matrix are cells ------------------------------------------------------
+namespace {
+static_assert(UMI_CELLS_CR22 == CELLS_CR22 && UMI_CELLS_TOP == CELLS_TOP && UMI_CELLS_MIN == CELLS_MIN, "one numbering of the rules");
+
+struct CellsRuleArgs { // what the kernels take of a rule's parameters
+    unsigned long long pick = 0, ratio = 1, min_molecules = 0;
+};
+// what both forms check before a device is looked at (the context last)
+int cc_check(umi_ctx *ctx, const void *row, const void *col, const void *molecules, const void *reads, uint64_t nnz, uint32_t n_rows,
+             uint32_t n_cols, int rule, int64_t expect_cells, int percentile_permille, int64_t max_min_ratio, int64_t min_molecules,
+             const void *cell_molecules, const void *cell_reads, const void *cell_genes, const void *called, const void *new_col,
+             const void *out_row, const void *out_col, const void *out_molecules, const void *out_reads, const uint64_t *nnz_out,
+             const uint64_t *counts, CellsRuleArgs *ra)
+{
+    if (!nnz_out || !counts) return fail(UMI_ERR_ARG, "nnz_out or counts is NULL");
+    if (nnz >= (1ull << 30)) return fail(UMI_ERR_ARG, "%llu triplets exceed the 30-bit index space of one call", (unsigned long long)nnz);
+    if (n_cols >= (1u << 30)) return fail(UMI_ERR_ARG, "%u columns exceed the 30-bit index space of the call's sort", n_cols);
+    if (nnz && (n_rows == 0 || n_cols == 0)) return fail(UMI_ERR_ARG, "a matrix of %u rows and %u columns with a triplet", n_rows, n_cols);
+    if (rule != UMI_CELLS_CR22 && rule != UMI_CELLS_TOP && rule != UMI_CELLS_MIN) return fail(UMI_ERR_ARG, "unknown rule %d", rule);
+    if (rule != UMI_CELLS_MIN && expect_cells < 1) return fail(UMI_ERR_ARG, "expect_cells %lld below 1", (long long)expect_cells);
+    if (rule == UMI_CELLS_CR22 && (percentile_permille < 0 || percentile_permille > 1000))
+        return fail(UMI_ERR_ARG, "percentile_permille %d outside 0..1000", percentile_permille);
+    if (rule == UMI_CELLS_CR22 && max_min_ratio < 1) return fail(UMI_ERR_ARG, "max_min_ratio %lld below 1", (long long)max_min_ratio);
+    if (n_cols && (!cell_molecules || !cell_reads || !cell_genes || !called || !new_col)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (nnz && (!row || !col || !molecules || !reads || !out_row || !out_col || !out_molecules || !out_reads))
+        return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
+    // (the index is the smaller of this and n - 1 < 2^30: 2^40 cells stand for any number above)
+    const unsigned long long cells = (unsigned long long)std::min<int64_t>(std::max<int64_t>(expect_cells, 1), (int64_t)1 << 40);
+    ra->pick = rule == UMI_CELLS_CR22 ? cells * (unsigned long long)(1000 - percentile_permille) / 1000ull : cells - 1ull;
+    ra->ratio = (unsigned long long)std::max<int64_t>(max_min_ratio, 1);
+    ra->min_molecules = (unsigned long long)std::max<int64_t>(min_molecules, 0);
+    return UMI_OK;
+}
+
+// everything on the device (the context is the call's device, settled; nnz >= 1)
+int cc_run(umi_ctx *ctx, const uint32_t *d_row, const uint32_t *d_col, const uint32_t *d_molecules, const uint64_t *d_reads, uint64_t nnz,
+           uint32_t n_rows, uint32_t n_cols, int rule, const CellsRuleArgs &ra, uint64_t *d_cell_molecules, uint64_t *d_cell_reads,
+           uint32_t *d_cell_genes, uint8_t *d_called, uint32_t *d_new_col, uint32_t *d_out_row, uint32_t *d_out_col,
+           uint32_t *d_out_molecules, uint64_t *d_out_reads, uint64_t *nnz_out, uint64_t counts[10], hipStream_t s)
+{
+    int rc;
+    CellsCall c;
+    c.d_row = d_row;
+    c.d_col = d_col;
+    c.d_molecules = d_molecules;
+    c.d_reads = d_reads;
+    c.nnz = (uint32_t)nnz;
+    c.n_rows = n_rows;
+    c.n_cols = n_cols;
+    c.n_cus = (uint32_t)ctx->n_cus;
+    c.rule = rule;
+    c.pick = ra.pick;
+    c.ratio = ra.ratio;
+    c.min_molecules = ra.min_molecules;
+    c.d_cell_molecules = d_cell_molecules;
+    c.d_cell_reads = d_cell_reads;
+    c.d_cell_genes = d_cell_genes;
+    c.d_new_col = d_new_col;
+    c.d_called = d_called;
+    c.d_out_row = d_out_row;
+    c.d_out_col = d_out_col;
+    c.d_out_molecules = d_out_molecules;
+    c.d_out_reads = d_out_reads;
+    c.h_pinned = ctx->h_counters;
+    static_assert(CELLS_CTL_WORDS + 1 <= CNT_COUNT, "the pinned words of the call lie in the control block's mirror");
+    if ((rc = ctx->call_ws.reserve(cells_workspace_bytes(c.nnz, n_cols)))) return rc;
+    const int r = call_cells_on_device(ctx->call_ws.p, c, s);
+    if (r < 0) return fail(UMI_ERR_HIP, "call cells: %s", hipGetErrorString((hipError_t)(-r)));
+    const unsigned long long *h = ctx->h_counters;
+    if (h[0])
+        return fail(UMI_ERR_ARG, "%llu triplets have a row id of %u or more, or a column id of %u or more", h[0], n_rows, n_cols);
+    if (h[1]) return fail(UMI_ERR_ORDER, "%llu triplets are not above their predecessor in (col, row)", h[1]);
+    // candidates, called, t, m, molecules and reads in called columns, all molecules, all reads, the two medians
+    const int from[10] = {2, 9, 5, 6, 7, 8, 3, 4, 10, 11};
+    for (int i = 0; i < 10; i++) counts[i] = h[from[i]];
+    *nnz_out = h[CELLS_CTL_WORDS];
+    return UMI_OK;
+}
+} // namespace
+
+extern "C" {
+
+int umi_call_cells_device(umi_ctx *ctx, const uint32_t *d_row, const uint32_t *d_col, const uint32_t *d_molecules,
+                          const uint64_t *d_reads, uint64_t nnz, uint32_t n_rows, uint32_t n_cols, int rule, int64_t expect_cells,
+                          int percentile_permille, int64_t max_min_ratio, int64_t min_molecules, uint64_t *d_cell_molecules,
+                          uint64_t *d_cell_reads, uint32_t *d_cell_genes, uint8_t *d_called, uint32_t *d_new_col, uint32_t *d_out_row,
+                          uint32_t *d_out_col, uint32_t *d_out_molecules, uint64_t *d_out_reads, uint64_t *nnz_out, uint64_t counts[10],
+                          void *hip_stream)
+{
+    CellsRuleArgs ra;
+    int rc = cc_check(ctx, d_row, d_col, d_molecules, d_reads, nnz, n_rows, n_cols, rule, expect_cells, percentile_permille, max_min_ratio,
+                      min_molecules, d_cell_molecules, d_cell_reads, d_cell_genes, d_called, d_new_col, d_out_row, d_out_col,
+                      d_out_molecules, d_out_reads, nnz_out, counts, &ra);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_count_matrix)
+    *nnz_out = 0;
+    for (int i = 0; i < 10; i++) counts[i] = 0;
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
+    if (nnz == 0) { // (no kernel is launched)
+        if (n_cols == 0) return UMI_OK;
+        HIP_TRY(hipMemsetAsync(d_cell_molecules, 0, (size_t)n_cols * 8, s));
+        HIP_TRY(hipMemsetAsync(d_cell_reads, 0, (size_t)n_cols * 8, s));
+        HIP_TRY(hipMemsetAsync(d_cell_genes, 0, (size_t)n_cols * 4, s));
+        HIP_TRY(hipMemsetAsync(d_called, 0, (size_t)n_cols, s));
+        HIP_TRY(hipMemsetAsync(d_new_col, 0xFF, (size_t)n_cols * 4, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return UMI_OK;
+    }
+    return cc_run(ctx, d_row, d_col, d_molecules, d_reads, nnz, n_rows, n_cols, rule, ra, d_cell_molecules, d_cell_reads, d_cell_genes,
+                  d_called, d_new_col, d_out_row, d_out_col, d_out_molecules, d_out_reads, nnz_out, counts, s);
+}
+
+int umi_call_cells(umi_ctx *ctx, const uint32_t *row, const uint32_t *col, const uint32_t *molecules, const uint64_t *reads,
+                   uint64_t nnz, uint32_t n_rows, uint32_t n_cols, int rule, int64_t expect_cells, int percentile_permille,
+                   int64_t max_min_ratio, int64_t min_molecules, uint64_t *cell_molecules, uint64_t *cell_reads, uint32_t *cell_genes,
+                   uint8_t *called, uint32_t *new_col, uint32_t *out_row, uint32_t *out_col, uint32_t *out_molecules,
+                   uint64_t *out_reads, uint64_t *nnz_out, uint64_t counts[10])
+{
+    CellsRuleArgs ra;
+    int rc = cc_check(ctx, row, col, molecules, reads, nnz, n_rows, n_cols, rule, expect_cells, percentile_permille, max_min_ratio,
+                      min_molecules, cell_molecules, cell_reads, cell_genes, called, new_col, out_row, out_col, out_molecules, out_reads,
+                      nnz_out, counts, &ra);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    *nnz_out = 0;
+    for (int i = 0; i < 10; i++) counts[i] = 0;
+    const size_t nc = (size_t)n_cols, nz = (size_t)nnz;
+    if (nnz == 0) { // (nothing is launched)
+        if (nc) {
+            memset(cell_molecules, 0, nc * 8);
+            memset(cell_reads, 0, nc * 8);
+            memset(cell_genes, 0, nc * 4);
+            memset(called, 0, nc);
+            memset(new_col, 0xFF, nc * 4);
+        }
+        return UMI_OK;
+    }
+    HostIo io(ctx);
+    const auto d_reads = io.in(reads, nz * 8);
+    const auto d_row = io.in(row, nz * 4), d_col = io.in(col, nz * 4), d_mol = io.in(molecules, nz * 4);
+    const auto d_cmol = io.out(cell_molecules, nc * 8), d_creads = io.out(cell_reads, nc * 8);
+    const auto d_oreads = io.out(out_reads, nz * 8);
+    const auto d_cgenes = io.out(cell_genes, nc * 4), d_newcol = io.out(new_col, nc * 4);
+    const auto d_orow = io.out(out_row, nz * 4), d_ocol = io.out(out_col, nz * 4), d_omol = io.out(out_molecules, nz * 4);
+    const auto d_called = io.out(called, nc);
+    uint64_t got = 0;
+    if ((rc = io.open()) ||
+        (rc = cc_run(ctx, d_row, d_col, d_mol, d_reads, nnz, n_rows, n_cols, rule, ra, d_cmol, d_creads, d_cgenes, d_called, d_newcol,
+                     d_orow, d_ocol, d_omol, d_oreads, &got, counts, io.stream())) ||
+        (rc = io.fetch(cell_molecules, d_cmol, nc)) || (rc = io.fetch(cell_reads, d_creads, nc)) ||
+        (rc = io.fetch(cell_genes, d_cgenes, nc)) || (rc = io.fetch(called, d_called, nc)) || (rc = io.fetch(new_col, d_newcol, nc)) ||
+        (rc = io.fetch(out_row, d_orow, (size_t)got)) || (rc = io.fetch(out_col, d_ocol, (size_t)got)) ||
+        (rc = io.fetch(out_molecules, d_omol, (size_t)got)) || (rc = io.fetch(out_reads, d_oreads, (size_t)got)) || (rc = io.close())) {
+        for (int i = 0; i < 10; i++) counts[i] = 0;
+        return rc;
+    }
+    *nnz_out = got;
     return UMI_OK;
 }
 

@@ -573,6 +573,31 @@ struct MultigeneCall {
 // One synchronisation, at the end.  0 ok; negative: -(hipError_t)
 int multigene_on_device(void *workspace, const MultigeneCall &c, hipStream_t s);
 
+// ---- cell calling over the triplets of a count matrix (umihip_cells.hip: umi_call_cells) ----
+constexpr int CELLS_CTL_WORDS = 12; // the control block's words, in h_pinned's order
+enum CellsRule : int { CELLS_CR22 = 0, CELLS_TOP = 1, CELLS_MIN = 2 }; // the values of UMI_CELLS_* (umihip.h)
+size_t cells_workspace_bytes(uint32_t nnz, uint32_t n_cols);
+struct CellsCall {
+    const uint32_t *d_row, *d_col, *d_molecules; // the nnz triplets, sorted by column, then row
+    const uint64_t *d_reads;
+    uint32_t nnz, n_rows, n_cols, n_cus; // 1 <= nnz < 2^30, 1 <= n_cols < 2^30, n_rows >= 1
+    int rule;                            // CELLS_* (= UMI_CELLS_*), known
+    // what the rule's index is the smaller of, beside n - 1: floor(N (1000 - P) / 1000) or N - 1; its ratio (>= 1
+    // where it is read); min_molecules, negative ones as 0
+    unsigned long long pick, ratio, min_molecules;
+    uint64_t *d_cell_molecules, *d_cell_reads; // per column
+    uint32_t *d_cell_genes, *d_new_col;
+    uint8_t *d_called;
+    uint32_t *d_out_row, *d_out_col, *d_out_molecules; // the filtered triplets (capacity nnz)
+    uint64_t *d_out_reads;
+    // CELLS_CTL_WORDS + 1 pinned words: triplets with an id out of range, triplets not above their predecessor
+    // (either: the outputs are worthless), candidates, all molecules, all reads, t, m, molecules and reads in called
+    // columns, called columns, their median molecules and genes; then the filtered triplets
+    unsigned long long *h_pinned;
+};
+// One synchronisation, at the end.  0 ok; negative: -(hipError_t)
+int call_cells_on_device(void *workspace, const CellsCall &c, hipStream_t s);
+
 // ---- sort and scan primitives of the staging (umihip_radix.hip) ----
 constexpr int RADIX_BINS = 256, RADIX_MAX_PASSES = 8; // 8-bit digits; a 64-bit key has at most eight
 constexpr int RADIX_HIST_PARTS = 2048;                // blocks of a kernel that counts digits, at most

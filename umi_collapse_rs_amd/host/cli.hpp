@@ -51,6 +51,25 @@
 // and at most three decimals, 0..1.  Refused with status 101 before the GPU is woken, each with a message of its own:
 // any of the four flags without --cell-whitelist, a companion flag without --cell-whitelist-multi,
 // --cell-whitelist-max-mismatches 0 with it, a tag name that is not two characters, a malformed P or N.
+// --cell-filter cr2.2|top-cells|min-molecules [--expect-cells N] [--cell-filter-percentile P] [--cell-filter-ratio R]
+// [--cell-min-molecules T] (with --per-cell --per-gene --count-matrix DIR and everything those go with; STARsolo's
+// --soloCellFilter CellRanger2.2 N P R and TopCells N, not the reference's, tests/cells_model.py defines it): which of
+// the matrix's columns are cells.  A cell's total is its molecules over all genes; the candidates are the cells with
+// a molecule, S their totals in descending order, and every rule yields one threshold t: a candidate with a total of
+// t or more is called, a tie at t whole.  cr2.2: m = S[min(n - 1, floor(N (1 - P)))], t = max(1, m / R rounded half
+// up) [N 3000, P 0.99, R 10]; top-cells: t = S[min(n - 1, N - 1)], N required; min-molecules: t = T, required.  P is
+// read from its text as per-mille like --cell-whitelist-min-posterior.  One call to umi_call_cells (include/umihip.h)
+// after umi_count_matrix, over the triplets matrix.mtx holds; the four raw files, the BAM and the summary lines
+// before it are as without the flag.  Added: DIR/filtered/ with features.tsv (as raw), barcodes.tsv (the called cells
+// in id order), matrix.mtx and reads.mtx (raw's layout, columns renumbered); DIR/cells.tsv, "barcode reads molecules
+// genes called" tab-separated, a line per candidate cell in id order; and the summary lines "Cell filter", "Number of
+// candidate cells", "Number of cells called", "Molecule threshold", "Number of molecules in called cells", "Number of
+// reads in called cells", "Median molecules per called cell", "Median genes per called cell" (lower medians).
+// DIR/filtered is made here, after DIR.  Refused with status 101 before the GPU is woken and with nothing written,
+// each with a message that names the flag: --cell-filter without --per-cell, --per-gene or --count-matrix, or given
+// twice with different values; an unknown rule; a companion flag without --cell-filter or with a rule that does not
+// read it; top-cells without --expect-cells, min-molecules without --cell-min-molecules; N, R or T below 1; P outside
+// 0..1 or with more than three decimals; a DIR/filtered that cannot be made.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -58,6 +77,7 @@
 #include <cstring>
 #include <string>
 #include <unordered_set>
+#include <utility>
 #include <vector>
 
 #include <cerrno>
@@ -117,6 +137,15 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     bool output_stats_seed_given = false;
     std::string umi_filtering;       // --umi-filtering none|multi-gene: what is done to the collapsed UMIs across genes
     bool umi_filtering_given = false, filter_multigene = false; // ... multi-gene (filled in by validate())
+    std::string cell_filter;         // --cell-filter cr2.2|top-cells|min-molecules: which columns of the matrix are cells
+    bool cell_filter_given = false;
+    int cell_filter_rule = UMI_CELLS_CR22;  // ... as UMI_CELLS_* (filled in by validate())
+    long long expect_cells = 3000;          // --expect-cells N
+    int cell_filter_permille = 990;         // --cell-filter-percentile P, per-mille
+    long long cell_filter_ratio = 10;       // --cell-filter-ratio R
+    long long cell_min_molecules = 1;       // --cell-min-molecules T
+    bool expect_cells_given = false, cell_filter_percentile_given = false, cell_filter_ratio_given = false,
+         cell_min_molecules_given = false;
     bool edit_distance = false; // --distance edit: -k bounds the Levenshtein distance (umi_dedup_batch_edit)
     // filled in by validate(): --algo as UMI_ALGO_*, --merge as 0 any, 1 avgqual, 2 mapqual, and the two lists
     int algo_id = 0, merge_id = 0;
@@ -225,6 +254,16 @@ void usage()
               "                           reads only, by none where the top count is shared (Cell Ranger, STARsolo's\n"
               "                           MultiGeneUMI_CR); the records, the summary and --count-matrix follow, decided on\n"
               "                           the GPU\n"
+              "      --cell-filter <RULE> cr2.2, top-cells or min-molecules, with --per-cell --per-gene --count-matrix: call\n"
+              "                           cells on the GPU by their molecule totals and write DIR/filtered/ (the matrix of\n"
+              "                           the called cells) and DIR/cells.tsv; cr2.2: Cell Ranger 2.2's knee (STARsolo\n"
+              "                           CellRanger2.2 N P R): the total at rank N (1 - P), divided by R; top-cells: the\n"
+              "                           total at rank N (STARsolo TopCells); min-molecules: T; ties at the threshold\n"
+              "                           are called whole\n"
+              "      --expect-cells <N>   with --cell-filter cr2.2 [default: 3000] or top-cells (required), 1 or more\n"
+              "      --cell-filter-percentile <P> with cr2.2: 0..1, at most three decimals [default: 0.99]\n"
+              "      --cell-filter-ratio <R> with cr2.2: 1 or more [default: 10]\n"
+              "      --cell-min-molecules <T> with --cell-filter min-molecules (required): 1 or more\n"
               "      --device <ID>        GPU to use [default: 0]\n"
               "      --devices <ID,..>    several GPUs of the node: alignment positions are sharded over them");
 }
@@ -252,6 +291,18 @@ Cli parse(int argc, char **argv)
         const long long w = std::strtoll(v, &end, 10);
         if (end == v || *end != '\0' || w < least || w > most) die(msg);
         return w;
+    };
+    // a flag's value in 0..1 as per-mille, from the text and never as a float: [01] or [01].d{1,3}, at most 1
+    auto permille = [&](int &i, const std::string &a) -> int {
+        const std::string v = need(i);
+        bool ok = !v.empty() && (v[0] == '0' || v[0] == '1') && (v.size() == 1 || (v[1] == '.' && v.size() >= 3 && v.size() <= 5));
+        int pm = ok ? (v[0] - '0') * 1000 : 0;
+        for (size_t d = 2, unit = 100; ok && d < v.size(); d++, unit /= 10) {
+            ok = v[d] >= '0' && v[d] <= '9';
+            pm += (v[d] - '0') * (int)unit;
+        }
+        if (!ok || pm > 1000) die(a + " wants a number in 0..1 with at most three decimals: '" + v + "'");
+        return pm;
     };
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -336,17 +387,32 @@ Cli parse(int argc, char **argv)
             c.cell_qual_tag = t;
             c.cell_qual_tag_given = true;
         }
-        else if (a == "--cell-whitelist-min-posterior") { // per-mille from the text: [01] or [01].d{1,3}, at most 1
-            const std::string v = need(i);
-            bool ok = !v.empty() && (v[0] == '0' || v[0] == '1') && (v.size() == 1 || (v[1] == '.' && v.size() >= 3 && v.size() <= 5));
-            int pm = ok ? (v[0] - '0') * 1000 : 0;
-            for (size_t d = 2, unit = 100; ok && d < v.size(); d++, unit /= 10) {
-                ok = v[d] >= '0' && v[d] <= '9';
-                pm += (v[d] - '0') * (int)unit;
-            }
-            if (!ok || pm > 1000) die(a + " wants a number in 0..1 with at most three decimals: '" + v + "'");
-            c.cell_wl_min_posterior = pm;
+        else if (a == "--cell-whitelist-min-posterior") {
+            c.cell_wl_min_posterior = permille(i, a);
             c.cell_wl_min_posterior_given = true;
+        }
+        else if (a == "--cell-filter") {
+            const std::string v = need(i);
+            if (c.cell_filter_given && c.cell_filter != v)
+                die("--cell-filter given twice with different values: '" + c.cell_filter + "' and '" + v + "'");
+            c.cell_filter = v;
+            c.cell_filter_given = true;
+        }
+        else if (a == "--expect-cells") {
+            c.expect_cells = number(i, "--expect-cells wants a number of cells, 1 or more", 1);
+            c.expect_cells_given = true;
+        }
+        else if (a == "--cell-filter-percentile") {
+            c.cell_filter_permille = permille(i, a);
+            c.cell_filter_percentile_given = true;
+        }
+        else if (a == "--cell-filter-ratio") {
+            c.cell_filter_ratio = number(i, "--cell-filter-ratio wants a number, 1 or more", 1);
+            c.cell_filter_ratio_given = true;
+        }
+        else if (a == "--cell-min-molecules") {
+            c.cell_min_molecules = number(i, "--cell-min-molecules wants a number of molecules, 1 or more", 1);
+            c.cell_min_molecules_given = true;
         }
         else if (a == "--cell-whitelist-pseudocount") {
             const std::string v = need(i);
@@ -490,6 +556,28 @@ bool validate(Cli &args)
         die("--umi-filtering wants none or multi-gene: '" + args.umi_filtering + "'");
     args.filter_multigene = args.umi_filtering == "multi-gene";
     if (args.filter_multigene && !args.per_gene) die("--umi-filtering multi-gene goes with --per-gene only");
+    // --cell-filter: likewise (its directory is made last, behind --count-matrix's)
+    if (!args.cell_filter_given) {
+        for (const auto &f : {std::make_pair(args.expect_cells_given, "--expect-cells"),
+                              std::make_pair(args.cell_filter_percentile_given, "--cell-filter-percentile"),
+                              std::make_pair(args.cell_filter_ratio_given, "--cell-filter-ratio"),
+                              std::make_pair(args.cell_min_molecules_given, "--cell-min-molecules")})
+            if (f.first) die(std::string(f.second) + " goes with --cell-filter only");
+    } else {
+        const std::string &r = args.cell_filter;
+        if (r == "cr2.2") args.cell_filter_rule = UMI_CELLS_CR22;
+        else if (r == "top-cells") args.cell_filter_rule = UMI_CELLS_TOP;
+        else if (r == "min-molecules") args.cell_filter_rule = UMI_CELLS_MIN;
+        else die("--cell-filter wants cr2.2, top-cells or min-molecules: '" + r + "'");
+        if (!args.per_cell || !args.per_gene || args.count_matrix.empty())
+            die("--cell-filter goes with --per-cell --per-gene --count-matrix DIR only");
+        if (args.expect_cells_given && r == "min-molecules") die("--expect-cells does not go with --cell-filter min-molecules");
+        if (args.cell_filter_percentile_given && r != "cr2.2") die("--cell-filter-percentile goes with --cell-filter cr2.2 only");
+        if (args.cell_filter_ratio_given && r != "cr2.2") die("--cell-filter-ratio goes with --cell-filter cr2.2 only");
+        if (args.cell_min_molecules_given && r != "min-molecules") die("--cell-min-molecules goes with --cell-filter min-molecules only");
+        if (r == "top-cells" && !args.expect_cells_given) die("--cell-filter top-cells wants --expect-cells N");
+        if (r == "min-molecules" && !args.cell_min_molecules_given) die("--cell-filter min-molecules wants --cell-min-molecules T");
+    }
     // --distance edit: everything about it that can be refused is, before the GPU is woken
     if (args.edit_distance) {
         if (args.mode == "fastq") die("--distance edit is defined in bam/sam mode only (whole reads are the key in fastq mode)");
@@ -549,6 +637,15 @@ bool validate(Cli &args)
         struct stat sb;
         if (why != EEXIST || stat(args.count_matrix.c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode))
             die("cannot make the directory " + args.count_matrix + " for --count-matrix: " + std::strerror(why));
+    }
+    if (args.cell_filter_given) {
+        const std::string dir = args.count_matrix + "/filtered";
+        if (mkdir(dir.c_str(), 0777) != 0) {
+            const int why = errno;
+            struct stat sb;
+            if (why != EEXIST || stat(dir.c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode))
+                die("cannot make the directory " + dir + " for --cell-filter: " + std::strerror(why));
+        }
     }
     for (const std::string &path : output_stats_paths(args)) {
         FILE *f = std::fopen(path.c_str(), "wb");

@@ -21,6 +21,8 @@
 // --cell-whitelist-multi: likewise umi_correct_barcodes_multi, in umi_correct_barcodes' place.
 //
 // --umi-filtering multi-gene: likewise umi_filter_multigene.
+//
+// --cell-filter RULE (with --count-matrix): likewise umi_call_cells.
 #pragma once
 #include <chrono>
 #include <dlfcn.h>
@@ -92,6 +94,9 @@ struct HipLib {
     // --umi-filtering multi-gene: likewise
     bool want_multigene = false;
     decltype(&umi_filter_multigene) filter_multigene = nullptr;
+    // --cell-filter: likewise
+    bool want_cells = false;
+    decltype(&umi_call_cells) call_cells = nullptr;
     // (the HIP runtime the library brings along: device buffers for the arrays above)
     int (*hip_set_device)(int) = nullptr; // (the current device is per thread: the context was made on another)
     int (*hip_malloc)(void **, size_t) = nullptr;
@@ -102,7 +107,7 @@ struct HipLib {
           want_correct(!args.whitelist.empty()), want_barcodes(!args.cell_list.empty() && !args.cell_wl_multi),
           want_barcodes_multi(!args.cell_list.empty() && args.cell_wl_multi),
           want_count(!args.count_matrix.empty()), want_stats(!args.output_stats.empty()),
-          want_multigene(args.filter_multigene)
+          want_multigene(args.filter_multigene), want_cells(args.cell_filter_given)
     {
     }
     bool load()
@@ -146,6 +151,7 @@ struct HipLib {
         if (want_count) count_matrix = (decltype(count_matrix))sym("umi_count_matrix");
         if (want_stats) dedup_stats = (decltype(dedup_stats))sym("umi_dedup_stats");
         if (want_multigene) filter_multigene = (decltype(filter_multigene))sym("umi_filter_multigene");
+        if (want_cells) call_cells = (decltype(call_cells))sym("umi_call_cells");
         hip_set_device = (decltype(hip_set_device))sym("hipSetDevice");
         hip_malloc = (decltype(hip_malloc))sym("hipMalloc");
         hip_memcpy = (decltype(hip_memcpy))sym("hipMemcpy");

@@ -370,6 +370,7 @@ struct Summary {
     uint64_t n_kept = 0;
     size_t n_below = 0, n_without = 0; // --call-consensus
     uint64_t mg_counts[3] = {0, 0, 0}; // --umi-filtering multi-gene: UMIs in several genes of a cell, molecules removed, their reads
+    uint64_t cell_counts[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // --cell-filter: umi_call_cells' counts
     void print(const Cli &args, bool dump_exit = false) const
     {
         if (!dump_exit) {
@@ -416,6 +417,17 @@ struct Summary {
             std::fprintf(stderr, "Number of UMIs seen in several genes of a cell: %llu\n", (unsigned long long)mg_counts[0]);
             std::fprintf(stderr, "Number of molecules removed as multi-gene UMIs: %llu\n", (unsigned long long)mg_counts[1]);
             std::fprintf(stderr, "Number of reads in removed molecules: %llu\n", (unsigned long long)mg_counts[2]);
+        }
+        if (args.cell_filter_given) {
+            const unsigned long long *c = (const unsigned long long *)cell_counts;
+            std::fprintf(stderr, "Cell filter: %s\n", args.cell_filter.c_str());
+            std::fprintf(stderr, "Number of candidate cells: %llu\n", c[0]);
+            std::fprintf(stderr, "Number of cells called: %llu\n", c[1]);
+            std::fprintf(stderr, "Molecule threshold: %llu\n", c[2]);
+            std::fprintf(stderr, "Number of molecules in called cells: %llu\n", c[4]);
+            std::fprintf(stderr, "Number of reads in called cells: %llu\n", c[5]);
+            std::fprintf(stderr, "Median molecules per called cell: %llu\n", c[8]);
+            std::fprintf(stderr, "Median genes per called cell: %llu\n", c[9]);
         }
         if (args.call_consensus) {
             std::fprintf(stderr, "Number of clusters below --call-consensus-min-reads: %zu\n", n_below);

@@ -84,6 +84,9 @@
 // kept_out, and freq_out for the matrix -- is what the records written, "Number of reads after deduplicating" and
 // --count-matrix see, which leaves out the pairs without a molecule; --output-stats sees the collapse's own kept[]
 // (filter_multigene() below).
+// --cell-filter RULE (with --per-cell --per-gene --count-matrix DIR; cli.hpp has the flag's definition, its files and
+// its refusals): after umi_count_matrix one call to umi_call_cells over the triplets matrix.mtx holds; DIR/filtered/,
+// DIR/cells.tsv and eight summary lines are added, everything else stays byte for byte (call_cells() below).
 // --algo cluster: connected components of "within -k" (cli.hpp); every pipeline here only forwards the algorithm
 // to the library, so it goes with every flag --algo dir goes with.
 // Not implemented, as in the reference: --algo cc (that spelling stays refused; `cluster` is the mode's name).
@@ -886,6 +889,64 @@ struct OnePass {
         write("matrix.mtx", mol);
         write("reads.mtx", rd);
         lap("count matrix");
+        if (args.cell_filter_given) {
+            if (args.filter_multigene) { // (what matrix.mtx holds: the pairs that still have a molecule)
+                uint64_t w = 0;
+                for (uint64_t i = 0; i < nnz; i++) {
+                    if (molecules[i] == 0) continue;
+                    out_row[w] = out_row[i], out_col[w] = out_col[i], molecules[w] = molecules[i], reads[w] = reads[i];
+                    w++;
+                }
+                nnz = w;
+            }
+            call_cells(n_rows, n_cols, out_row, out_col, molecules, reads, nnz, write);
+        }
+    }
+
+    // --cell-filter: which cells of the matrix are called, in one call over its triplets, then DIR/filtered/'s four
+    // files and DIR/cells.tsv
+    void call_cells(uint32_t n_rows, uint32_t n_cols, const std::vector<uint32_t> &row, const std::vector<uint32_t> &col,
+                    const std::vector<uint32_t> &molecules, const std::vector<uint64_t> &reads, uint64_t nnz,
+                    const std::function<void(const char *, const std::string &)> &write)
+    {
+        std::vector<uint64_t> cell_molecules(n_cols + 1, 0), cell_reads(n_cols + 1, 0), f_reads(nnz + 1);
+        std::vector<uint32_t> cell_genes(n_cols + 1, 0), new_col(n_cols + 1, UINT32_MAX), f_row(nnz + 1), f_col(nnz + 1), f_mol(nnz + 1);
+        std::vector<uint8_t> called(n_cols + 1, 0);
+        uint64_t f_nnz = 0;
+        if (nnz) {
+            need_ctx();
+            if (!lib.call_cells) die("libumihip.so lacks umi_call_cells");
+            if (lib.call_cells(ctx, row.data(), col.data(), molecules.data(), reads.data(), nnz, n_rows, n_cols, args.cell_filter_rule,
+                               args.expect_cells, args.cell_filter_permille, args.cell_filter_ratio, args.cell_min_molecules,
+                               cell_molecules.data(), cell_reads.data(), cell_genes.data(), called.data(), new_col.data(), f_row.data(),
+                               f_col.data(), f_mol.data(), f_reads.data(), &f_nnz, sum.cell_counts) != UMI_OK)
+                die(lib.last_error());
+        }
+        std::string text;
+        for (const std::string_view &g : gene_names) text.append(g).append("\t").append(g).append("\tGene Expression\n");
+        write("filtered/features.tsv", text);
+        text.clear();
+        std::string table = "barcode\treads\tmolecules\tgenes\tcalled\n";
+        for (size_t c = 0; c < n_cols; c++) {
+            if (called[c]) text.append(cell_names[c]).append("\n");
+            if (cell_molecules[c] == 0) continue; // (no candidate)
+            table.append(cell_names[c]).append("\t").append(std::to_string(cell_reads[c])).append("\t");
+            table.append(std::to_string(cell_molecules[c])).append("\t").append(std::to_string(cell_genes[c]));
+            table.append(called[c] ? "\t1\n" : "\t0\n");
+        }
+        write("filtered/barcodes.tsv", text);
+        write("cells.tsv", table);
+        const std::string head = "%%MatrixMarket matrix coordinate integer general\n" + std::to_string(n_rows) + " " +
+                                 std::to_string(sum.cell_counts[1]) + " " + std::to_string(f_nnz) + "\n";
+        std::string mol = head, rd = head;
+        for (uint64_t i = 0; i < f_nnz; i++) {
+            const std::string at = std::to_string(f_row[i] + 1) + " " + std::to_string(f_col[i] + 1) + " ";
+            mol.append(at).append(std::to_string(f_mol[i])).append("\n");
+            rd.append(at).append(std::to_string(f_reads[i])).append("\n");
+        }
+        write("filtered/matrix.mtx", mol);
+        write("filtered/reads.mtx", rd);
+        lap("cell filter");
     }
 
     // --output-stats: family sizes, UMI distances and UMI usage in one call over the staged keys and freq and the
