@@ -9,15 +9,15 @@ LIB := $(PKG)/libumihip.so
 OBJDIR := build/obj
 # the library's translation units, listed once: the kernels (.hip), then the host side (.cpp)
 SRCS := umihip_kernels umihip_seg umihip_collapse umihip_stage umihip_radix umihip_wide umihip_edit umihip_seq \
-        umihip_consensus umihip_consensus_bam umihip_correct umihip_barcode umihip_count umihip_multigene umihip_stats umihip_cells \
-        umihip_api umihip_pipeline umihip_batch umihip_stage_api umihip_seq_api umihip_correct_api umihip_count_api umihip_data
+        umihip_consensus umihip_consensus_bam umihip_correct umihip_barcode umihip_count umihip_multigene umihip_stats umihip_cells umihip_genes \
+        umihip_api umihip_pipeline umihip_batch umihip_stage_api umihip_seq_api umihip_correct_api umihip_count_api umihip_genes_api umihip_data
 OBJS := $(patsubst %,$(OBJDIR)/%.o,$(SRCS))
 # development build (make dev): the shipped sources plus the round-1 tile kernels, their key sort
 # and their options (-DUMIHIP_DEV), as libumihip_dev.so; the legacy cross-check tests load it
 DEVDIR := build/obj_dev
 DEVLIB := $(PKG)/libumihip_dev.so
 DEVOBJS := $(patsubst %,$(DEVDIR)/%.o,$(SRCS)) $(DEVDIR)/umihip_legacy.o $(DEVDIR)/umihip_sort.o
-HDRS := $(CSRC)/umihip_internal.h $(CSRC)/umihip_cons_group.h $(CSRC)/umihip_device.h $(CSRC)/umihip_plan.hpp $(CSRC)/umihip_io_layout.hpp $(CSRC)/umihip_host.hpp include/umihip.h
+HDRS := $(CSRC)/umihip_internal.h $(CSRC)/umihip_cons_group.h $(CSRC)/umihip_device.h $(CSRC)/umihip_plan.hpp $(CSRC)/umihip_io_layout.hpp $(CSRC)/umihip_host.hpp $(CSRC)/umihip_gene_index.hpp include/umihip.h
 CLI := $(PKG)/bin/umicollapse
 
 all: $(LIB) oracle cpptest primtest $(CLI)
@@ -50,7 +50,7 @@ $(DEVLIB): $(DEVOBJS)
 
 dev: $(DEVLIB)
 
-$(CLI): $(LIB) $(PKG)/host/umicollapse_main.cpp $(PKG)/host/cli.hpp $(PKG)/host/hiplib.hpp $(PKG)/host/staging.hpp \
+$(CLI): $(LIB) $(PKG)/host/umicollapse_main.cpp $(PKG)/host/cli.hpp $(PKG)/host/hiplib.hpp $(PKG)/host/staging.hpp $(PKG)/host/annotation.hpp \
         $(PKG)/host/two_pass.hpp $(PKG)/host/fastq_mode.hpp $(PKG)/host/bam.hpp $(PKG)/host/bgzf.hpp $(PKG)/host/fastq.hpp include/umihip.h
 	mkdir -p $(PKG)/bin
 	g++ -O2 -std=c++17 -Wall -Wextra -o $@ $(PKG)/host/umicollapse_main.cpp -lz -lpthread -ldl

@@ -158,6 +158,8 @@ const char *umi_last_error(void);
  *   "stats_split"    64..2^30 (default 4096): umi_dedup_stats counts a bucket of at least this many entries in pieces
  *                    over the whole grid instead of by one wave (raised by itself where the deep buckets' tables,
  *                    80 bytes per base each, would pass 512 MB)
+ *   "gene_top"       0/1 (default 1): umi_assign_genes searches a sampled top of its index in LDS before the
+ *                    index itself (0: the index alone)
  * The round-1 tile kernels (bit-sliced masks, key-sorted scan + item walk, range pruning, hook/jump
  * collapse) and their options ("bitslice", "bs_*", "prune", "two_phase", "ovf_capacity") exist in the
  * development build only (make dev: libumihip_dev.so, -DUMIHIP_DEV), as cross-checks. */
@@ -502,6 +504,57 @@ int umi_correct_barcodes_multi(umi_ctx *ctx, const uint8_t *bc_ascii, const uint
                                const uint8_t *whitelist_ascii, uint32_t n_wl, int min_posterior_permille,
                                int pseudocount, int32_t *match, uint8_t *status, uint32_t *exact_reads,
                                uint64_t counts[5]);
+
+/* ---- reads assigned to genes from an annotation (the program's --gene-annotation), on the GPU.  No counterpart
+ *      in the reference; the rule is featureCounts' default (-t exon -g gene_id -s 0|1|2, minimum overlap 1, no
+ *      -O, single-end) and tests/annotation_model.py defines it:
+ *        Blocks of a read: start at read_pos (0-based) and walk the CIGAR (BAM's words, len << 4 | op).  M, =, X
+ *          and D (0, 7, 8, 2) extend the current block on the reference; N (3) closes the block and skips its
+ *          length; I, S, H and P (1, 4, 5, 6) consume nothing.  Blocks are half-open [s, e); a read without a
+ *          reference-consuming operation has no block.  Op codes 9 to 15 are an error.
+ *        Exons: (ref, start, end, strand, gene), half-open, 0-based, strand '+', '-' or '.'.
+ *        Hits: gene g hits a read when one of its exons is on the read's reference, on an admissible strand, and
+ *          shares at least one base with one of the read's blocks.
+ *        Admissible strand: the read's strand is '-' where read_reverse is not 0 (flag 0x10), else '+'.
+ *          UMI_STRAND_FORWARD: the exon's strand equals the read's; UMI_STRAND_REVERSE: it is the opposite;
+ *          UMI_STRAND_UNSTRANDED: any.  A '.' exon is admissible under all three.
+ *        Result: exactly one gene hits: UMI_GENE_ASSIGNED, gene = its index; none: UMI_GENE_NONE, gene = -1; two
+ *          or more: UMI_GENE_SEVERAL, gene = -1.  Overlapping exons of one gene count as one gene.
+ *      Not built: transcript-level containment (STARsolo's Gene), paired reads, fractional assignment, a minimum
+ *      overlap above 1.
+ * in : the n_exons exons in five HOST arrays in both forms (exon_strand: the ASCII bytes), exon_gene in
+ *      0..n_genes - 1; per read read_ref, read_pos, read_reverse, and its CIGAR words cigar[cigar_off[i] ..
+ *      cigar_off[i + 1]), the reads' words back to back, cigar_off of n_reads + 1 entries (cigar may be NULL
+ *      where there is no word).  The index is built on the host inside the call; the walk and the lookups run on
+ *      the device.  n_exons == 0 is legal: every read is UMI_GENE_NONE.
+ * out: gene int32 [n_reads], status uint8 [n_reads], counts (host): the reads of each status, counts[status].
+ * n_reads == 0: UMI_OK, counts all zero, nothing else touched.  A multi-device context uses its first device.
+ * A deferred call (umi_dedup_batch_device_begin) that is out on the context ends first; its result keeps
+ * waiting for umi_dedup_batch_end.
+ * UMI_ERR_ARG, found on the host before anything is launched: an exon with end <= start, start < 0 or ref < 0,
+ * exon_gene outside 0..n_genes - 1, an unknown exon_strand or strand_mode, a NULL among ctx, counts and the arrays
+ * a positive count asks for, n_reads or n_exons >= 2^30.  Found on the device, told after the call's one
+ * synchronisation, the outputs then not defined: UMI_ERR_ARG for a read_ref < 0 or a CIGAR op code above 8,
+ * UMI_ERR_ORDER for a cigar_off that falls (nothing is read outside cigar[0 .. cigar_off[n_reads])); the message
+ * names the smallest such read.  Option "gene_top" (0/1, default 1): the sampled top of the index in LDS.  The
+ * _device form takes and leaves the per-read arrays in device memory; the plain form copies host arrays in and
+ * out around it. */
+#define UMI_GENE_ASSIGNED 0
+#define UMI_GENE_NONE 1
+#define UMI_GENE_SEVERAL 2
+#define UMI_STRAND_FORWARD 0
+#define UMI_STRAND_REVERSE 1
+#define UMI_STRAND_UNSTRANDED 2
+int umi_assign_genes_device(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end,
+                            const uint8_t *exon_strand, const int32_t *exon_gene, uint64_t n_exons, uint32_t n_genes,
+                            int strand_mode, const int32_t *d_read_ref, const int32_t *d_read_pos,
+                            const uint8_t *d_read_reverse, const uint32_t *d_cigar, const uint64_t *d_cigar_off,
+                            uint64_t n_reads, int32_t *d_gene, uint8_t *d_status, uint64_t counts[3], void *hip_stream);
+int umi_assign_genes(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end,
+                     const uint8_t *exon_strand, const int32_t *exon_gene, uint64_t n_exons, uint32_t n_genes,
+                     int strand_mode, const int32_t *read_ref, const int32_t *read_pos, const uint8_t *read_reverse,
+                     const uint32_t *cigar, const uint64_t *cigar_off, uint64_t n_reads, int32_t *gene, uint8_t *status,
+                     uint64_t counts[3]);
 
 /* ---- molecules and reads per (column, row) pair (the program's --count-matrix): what a batched call kept,
  *      summed over its buckets into the triplets of a sparse matrix, on the GPU.  No counterpart in the

@@ -455,6 +455,61 @@ class Context:
                                                        ptr(counts, C.c_uint64), stream or None))
         return counts
 
+    @staticmethod
+    def _exon_arrays(exons):
+        """exons: a dict of ref, start, end, gene (int32) and strand (uint8, the ASCII bytes of + - .), or a
+        sequence of (ref, start, end, strand, gene) with strand a one-letter str"""
+        if not isinstance(exons, dict):
+            rows = list(exons)
+            exons = {"ref": [e[0] for e in rows], "start": [e[1] for e in rows], "end": [e[2] for e in rows],
+                     "strand": np.frombuffer("".join(e[3] for e in rows).encode("latin-1"), np.uint8),
+                     "gene": [e[4] for e in rows]}
+        a = [np.ascontiguousarray(exons[k], dtype=np.uint8 if k == "strand" else np.int32).reshape(-1)
+             for k in ("ref", "start", "end", "strand", "gene")]
+        if len({len(x) for x in a}) != 1:
+            raise ValueError("the exon arrays differ in length")
+        return a
+
+    def assign_genes(self, exons, n_genes, strand_mode, read_ref, read_pos, read_reverse, cigar, cigar_off):
+        """Reads assigned to genes from an annotation by featureCounts' default rule (umi_assign_genes; the rule is
+        in include/umihip.h): exons as _exon_arrays takes them, strand_mode one of UMI_STRAND_*, per read its
+        reference, 0-based position, strand (not 0: reverse) and CIGAR words cigar[cigar_off[i]:cigar_off[i + 1]]
+        (BAM's, len << 4 | op).  Returns dict(gene int32 [n] (-1 unless assigned), status uint8 [n] (0 assigned,
+        1 none, 2 several), counts uint64 [3], by status)."""
+        ex = self._exon_arrays(exons)
+        read_ref = np.ascontiguousarray(read_ref, dtype=np.int32).reshape(-1)
+        read_pos = np.ascontiguousarray(read_pos, dtype=np.int32).reshape(-1)
+        read_reverse = np.ascontiguousarray(read_reverse, dtype=np.uint8).reshape(-1)
+        cigar = np.ascontiguousarray(cigar, dtype=np.uint32).reshape(-1)
+        cigar_off = np.ascontiguousarray(cigar_off, dtype=np.uint64).reshape(-1)
+        n = len(read_ref)
+        if len(read_pos) != n or len(read_reverse) != n or len(cigar_off) != n + 1:
+            raise ValueError("the read arrays differ in length (cigar_off has one entry more)")
+        if int(cigar_off[-1]) > len(cigar):
+            raise ValueError("cigar_off ends beyond cigar")
+        m = max(1, n)
+        gene, status = np.zeros(m, np.int32), np.zeros(m, np.uint8)
+        counts = np.zeros(3, np.uint64)
+        check(load().umi_assign_genes(self._h, ptr(ex[0], C.c_int32), ptr(ex[1], C.c_int32), ptr(ex[2], C.c_int32),
+                                      ptr(ex[3], C.c_uint8), ptr(ex[4], C.c_int32), len(ex[0]), n_genes, strand_mode,
+                                      ptr(read_ref, C.c_int32), ptr(read_pos, C.c_int32), ptr(read_reverse, C.c_uint8),
+                                      ptr(cigar, C.c_uint32), ptr(cigar_off, C.c_uint64), n, ptr(gene, C.c_int32),
+                                      ptr(status, C.c_uint8), ptr(counts, C.c_uint64)))
+        return {"gene": gene[:n], "status": status[:n], "counts": counts}
+
+    def assign_genes_device(self, exons, n_genes, strand_mode, d_read_ref, d_read_pos, d_read_reverse, d_cigar, d_cigar_off,
+                            n_reads, d_gene, d_status, stream=0):
+        """The same on raw device pointers (umi_assign_genes_device; the exons stay on the host): fills d_gene
+        (int32 [n_reads]) and d_status (uint8 [n_reads]); returns counts uint64 [3]."""
+        ex = self._exon_arrays(exons)
+        counts = np.zeros(3, np.uint64)
+        check(load().umi_assign_genes_device(self._h, ptr(ex[0], C.c_int32), ptr(ex[1], C.c_int32), ptr(ex[2], C.c_int32),
+                                             ptr(ex[3], C.c_uint8), ptr(ex[4], C.c_int32), len(ex[0]), n_genes,
+                                             strand_mode, d_read_ref or None, d_read_pos or None, d_read_reverse or None,
+                                             d_cigar or None, d_cigar_off or None, n_reads, d_gene or None,
+                                             d_status or None, ptr(counts, C.c_uint64), stream or None))
+        return counts
+
     def count_matrix(self, kept, freq, bucket_off, row, col, n_rows, n_cols):
         """Molecules and reads per (column, row) pair (umi_count_matrix): kept uint8 [N] and freq int32 [N] of a
         batched call, bucket_off uint64 [n_buckets + 1], row / col uint32 [n_buckets] the row (gene) and column

@@ -256,6 +256,7 @@ struct umi_ctx {
     // (the non-empty buckets' offsets, the deep buckets and their pieces)
     umihip::PinnedBuf cm_h, ds_h;
     uint32_t stats_split = umihip::STATS_SPLIT; // buckets of at least this many entries are counted by the whole grid
+    bool gene_top = true; // umi_assign_genes: the sampled top of each table in LDS (option "gene_top")
     uint32_t cons_split = 512; // clusters of at least this many reads are summed in pieces by the whole grid
     umihip::PinnedBuf h_boff;                 // pinned staging of the bucket table
     umihip::PinnedBuf h_tasks;                // pinned staging of the bit-sliced tile-task lists

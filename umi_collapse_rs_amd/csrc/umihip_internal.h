@@ -507,6 +507,22 @@ int barcode_multi_on_device(void *workspace, const uint8_t *d_bc, const uint8_t 
                             int32_t *d_match, uint8_t *d_status, uint32_t *d_exact_reads, uint64_t *counts, uint64_t *bad,
                             uint32_t n_cus, unsigned long long *h_pinned, hipStream_t s);
 
+// ---- reads assigned to genes from an annotation (umihip_genes.hip: umi_assign_genes) ----
+// The tables (umihip_gene_index.hpp: one for unstranded, else the exons a read on + and a read on - may hit under
+// "forward"; flip: "reverse", the two change places) are built and sampled on the host and uploaded into the
+// workspace.  One synchronisation, at the end.  h_pinned: 5 pinned words.  0 ok; 1 a read with read_ref < 0 or
+// a CIGAR op code above 8; 2 a cigar_off that falls (*bad: the smallest such read; the outputs are then
+// worthless); negative: -(hipError_t)
+struct GeneTable;
+constexpr int GENE_THREADS = 1024;        // lanes of a block, a read each
+constexpr int GENE_BLOCKS_PER_CU = 2;     // resident blocks per CU: the grid's cap, a stride beyond
+constexpr uint32_t GENE_TOP_CAP = 4096;   // sampled ends of a table in LDS, at most (option "gene_top")
+size_t genes_workspace_bytes(const GeneTable *tables, int n_tables);
+int genes_on_device(void *workspace, const GeneTable *tables, int n_tables, bool flip, bool use_top, const int32_t *d_ref,
+                    const int32_t *d_pos, const uint8_t *d_reverse, const uint32_t *d_cigar, const uint64_t *d_cigar_off,
+                    uint32_t n_reads, int32_t *d_gene, uint8_t *d_status, uint64_t counts[3], uint64_t *bad, uint32_t n_cus,
+                    unsigned long long *h_pinned, hipStream_t s);
+
 // ---- molecules and reads per (column, row) pair (umihip_count.hip: umi_count_matrix) ----
 // h_off (pinned): the m + 1 offsets of the m >= 1 non-empty buckets; h_idx (pinned, null: nothing was left out):
 // their numbers in d_row / d_col.  The outputs take the triplets sorted by column, then row (capacity m);

@@ -1,0 +1,145 @@
+// --gene-annotation FILE (with --per-gene; bam/sam mode, one pass; featureCounts' default rule, not the reference's,
+// tests/annotation_model.py defines it): a read's gene is decided from an annotation file, on the GPU, and not read
+// from a tag -- for files from STAR without solo, minimap2, bowtie2 or any bulk aligner, which write no GX, and in
+// place of the featureCounts -R BAM pass, the sort and the index that umi_tools asks of their users.
+//
+// The rule: a read's blocks are the stretches of its CIGAR's M, =, X and D from its position on, an N closing one
+// and skipping its length (I, S, H, P consume nothing); a gene hits the read when one of its features lies on the
+// read's reference, on an admissible strand, and shares at least one base with a block.  --gene-strand forward (the
+// default: 10x 3' chemistry, featureCounts -s 1): the feature's strand is the read's (- where flag 0x10 is set);
+// reverse (-s 2): the opposite; unstranded (-s 0): any; a feature on '.' is admissible always.  Exactly one gene:
+// the read is that gene's.  None: dropped like a read without a gene tag ("Number of reads outside every gene" takes
+// that line's place).  Two or more: dropped like a read whose tag names several ("Number of reads assigned to several
+// genes").  Overlapping features of one gene are one gene.  One call, umi_assign_genes (include/umihip.h), over every
+// mapped read, after the file is read and before the per-read pass, which then takes the call's verdict where it
+// took the tag's value (staging.hpp, read_tags): the tag is not looked at, and everything behind the gene's id --
+// numbering by first appearance among the staged reads, buckets, collapse, matrix, filters -- is --per-gene's,
+// unchanged.  With --devices the call runs on the first.
+//
+// The file: a GTF, plain or gzip (by its magic bytes), nine tab-separated columns; lines that start with # and
+// empty lines are skipped.  The lines taken are those whose column 3 equals --annotation-feature (default exon;
+// `gene` counts reads over whole gene bodies, introns included, as single-nucleus runs do); the others are skipped
+// silently.  Columns 4 and 5 are 1-based and inclusive, column 7 is the strand.  The gene is the value of
+// --annotation-attribute (default gene_id) in column 9, `key "value";`; features.tsv's second column is the value of
+// gene_name on the gene's first taken line where there is one, else the gene's id.  Column 1 is matched to the BAM
+// header's reference names; lines on a reference the BAM does not have are skipped and counted.  The summary gains
+// "Gene annotation: <genes> genes, <features> features" (those on the BAM's references), "Gene strand: <mode>" and
+// "Number of annotation lines on unknown references".
+//
+// Refused with status 101 before the GPU is woken: without --per-gene; with --gene-tag or --dump-staging; a
+// companion flag without --gene-annotation; an unknown --gene-strand; any of the four flags given twice with
+// different values; a file that cannot be read; a line of fewer than nine columns; on a taken line a start or end
+// that is not a number, a start below 1, an end below the start or above 2^31 - 1, a strand other than + - ., no
+// such attribute, an empty value, or a value with a byte outside 0x21..0x7e or a ; or , (the bytes --per-gene
+// reserves); a file without a taken line.  Everything --per-gene refuses stays refused.
+//
+// Not built: transcript-level containment (STARsolo's Gene: a read inside one transcript's exons), --paired,
+// fractional assignment of a read among several genes, a minimum overlap above 1.
+#pragma once
+#include <unordered_map>
+
+#include "cli.hpp"
+#include "fastq.hpp"
+
+namespace {
+
+// the value of `key` among column 9's attributes, `key "value";` (a bare value is taken up to the ;): false where
+// the key is absent
+bool gtf_attribute(std::string_view attrs, std::string_view key, std::string_view &value)
+{
+    size_t p = 0;
+    while (p < attrs.size()) {
+        while (p < attrs.size() && (attrs[p] == ' ' || attrs[p] == ';')) p++;
+        const size_t k0 = p;
+        while (p < attrs.size() && attrs[p] != ' ' && attrs[p] != ';') p++;
+        const std::string_view k = attrs.substr(k0, p - k0);
+        while (p < attrs.size() && attrs[p] == ' ') p++;
+        std::string_view v;
+        if (p < attrs.size() && attrs[p] == '"') {
+            const size_t v0 = ++p;
+            while (p < attrs.size() && attrs[p] != '"') p++;
+            v = attrs.substr(v0, p - v0);
+            if (p < attrs.size()) p++;
+        } else {
+            const size_t v0 = p;
+            while (p < attrs.size() && attrs[p] != ';') p++;
+            size_t v1 = p;
+            while (v1 > v0 && attrs[v1 - 1] == ' ') v1--;
+            v = attrs.substr(v0, v1 - v0);
+        }
+        if (!k.empty() && k == key) {
+            value = v;
+            return true;
+        }
+    }
+    return false;
+}
+
+void read_annotation(Cli &args)
+{
+    umi::bgzf::Bytes text;
+    try {
+        text = umi::fastq::read_all(args.gene_annotation, args.num_threads);
+    } catch (const std::exception &e) {
+        die("cannot read the gene annotation " + args.gene_annotation + ": " + e.what());
+    }
+    Cli::Annotation &an = args.annotation;
+    std::unordered_map<std::string, uint32_t> ref_of;
+    std::unordered_map<std::string, int32_t> gene_of;
+    const std::string_view all((const char *)text.data(), text.size());
+    size_t line_no = 0;
+    for (size_t p = 0; p < all.size();) {
+        size_t q = all.find('\n', p);
+        if (q == std::string_view::npos) q = all.size();
+        std::string_view line = all.substr(p, q - p);
+        p = q + 1;
+        line_no++;
+        if (!line.empty() && line.back() == '\r') line.remove_suffix(1);
+        if (line.empty() || line[0] == '#') continue;
+        const std::string where = "gene annotation " + args.gene_annotation + ", line " + std::to_string(line_no) + ": ";
+        std::string_view col[9];
+        size_t c = 0, at = 0;
+        for (; c < 9; c++) {
+            const size_t tab = c < 8 ? line.find('\t', at) : std::string_view::npos;
+            col[c] = line.substr(at, tab == std::string_view::npos ? std::string_view::npos : tab - at);
+            if (tab == std::string_view::npos) break;
+            at = tab + 1;
+        }
+        if (c < 8) die(where + "fewer than nine tab-separated columns");
+        if (col[2] != args.annotation_feature) continue;
+        long long se[2];
+        for (int i = 0; i < 2; i++) {
+            const std::string v(col[3 + i]);
+            const bool digits = !v.empty() && v.size() <= 10 && v.find_first_not_of("0123456789") == std::string::npos;
+            if (!digits) die(where + (i ? "the end '" : "the start '") + v + "' is not a number");
+            se[i] = std::atoll(v.c_str());
+        }
+        if (se[0] < 1) die(where + "a start below 1");
+        if (se[1] < se[0]) die(where + "the end " + std::to_string(se[1]) + " lies before the start " + std::to_string(se[0]));
+        if (se[1] > INT32_MAX) die(where + "the end " + std::to_string(se[1]) + " lies beyond 2^31 - 1");
+        if (col[6] != "+" && col[6] != "-" && col[6] != ".") die(where + "the strand '" + std::string(col[6]) + "' is none of + - .");
+        std::string_view id, name;
+        if (!gtf_attribute(col[8], args.annotation_attribute, id)) die(where + "no attribute " + args.annotation_attribute);
+        if (id.empty()) die(where + "the attribute " + args.annotation_attribute + " is empty");
+        for (const char ch : id)
+            if ((uint8_t)ch < 0x21 || (uint8_t)ch > 0x7e || ch == ';' || ch == ',')
+                die(where + "the attribute " + args.annotation_attribute + " holds a byte that a gene's name cannot: " +
+                    std::to_string((unsigned)(uint8_t)ch));
+        const auto g = gene_of.emplace(std::string(id), (int32_t)an.gene_ids.size());
+        if (g.second) {
+            an.gene_ids.emplace_back(id);
+            an.gene_names.emplace_back(gtf_attribute(col[8], "gene_name", name) ? name : std::string_view());
+        }
+        const auto r = ref_of.emplace(std::string(col[0]), (uint32_t)an.refs.size());
+        if (r.second) an.refs.emplace_back(col[0]);
+        an.ref_name.push_back(r.first->second);
+        an.start.push_back((int32_t)(se[0] - 1));
+        an.end.push_back((int32_t)se[1]);
+        an.strand.push_back((uint8_t)col[6][0]);
+        an.gene.push_back(g.first->second);
+    }
+    if (an.gene.empty())
+        die("the gene annotation " + args.gene_annotation + " holds no line of feature type " + args.annotation_feature);
+}
+
+} // namespace

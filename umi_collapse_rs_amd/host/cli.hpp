@@ -70,6 +70,9 @@
 // twice with different values; an unknown rule; a companion flag without --cell-filter or with a rule that does not
 // read it; top-cells without --expect-cells, min-molecules without --cell-min-molecules; N, R or T below 1; P outside
 // 0..1 or with more than three decimals; a DIR/filtered that cannot be made.
+// --gene-annotation FILE [--annotation-feature F] [--annotation-attribute A] [--gene-strand S] (with --per-gene): a
+// read's gene comes from a GTF, decided on the GPU, and not from a tag (annotation.hpp has the flags' definition, the
+// file's reader and every refusal; the flags and the file are looked at here, in validate(), before the GPU is woken).
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -146,6 +149,19 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     long long cell_min_molecules = 1;       // --cell-min-molecules T
     bool expect_cells_given = false, cell_filter_percentile_given = false, cell_filter_ratio_given = false,
          cell_min_molecules_given = false;
+    // --gene-annotation FILE: a read's gene is decided from this GTF (annotation.hpp), not read from --gene-tag
+    std::string gene_annotation, annotation_feature = "exon", annotation_attribute = "gene_id", gene_strand = "forward";
+    bool gene_annotation_given = false, annotation_feature_given = false, annotation_attribute_given = false, gene_strand_given = false;
+    int gene_strand_mode = UMI_STRAND_FORWARD; // --gene-strand as UMI_STRAND_* (filled in by validate())
+    struct Annotation { // the file's taken lines (filled in by validate(): read_annotation)
+        std::vector<std::string> refs;      // the reference names of column 1, in order of first appearance
+        std::vector<uint32_t> ref_name;     // per taken line: its reference, an index into refs
+        std::vector<int32_t> start, end;    // ... half-open, 0-based
+        std::vector<uint8_t> strand;        // ... + - or .
+        std::vector<int32_t> gene;          // ... an index into gene_ids
+        std::vector<std::string> gene_ids;  // the genes in order of first appearance
+        std::vector<std::string> gene_names; // ... and the gene_name of each one's first taken line (empty: none)
+    } annotation;
     bool edit_distance = false; // --distance edit: -k bounds the Levenshtein distance (umi_dedup_batch_edit)
     // filled in by validate(): --algo as UMI_ALGO_*, --merge as 0 any, 1 avgqual, 2 mapqual, and the two lists
     int algo_id = 0, merge_id = 0;
@@ -239,6 +255,17 @@ void usage()
               "                           --call-consensus)\n"
               "      --gene-tag <XX>      aux tag of the gene, type Z [default: GX]; no tag, an empty value, -, or a value\n"
               "                           starting with __ or Unassigned: no gene; a value with ; or , : several genes\n"
+              "      --gene-annotation <FILE> with --per-gene: a read's gene comes from this GTF (plain or gzip) and not from\n"
+              "                           a tag: the one gene whose features share a base with the read's aligned blocks\n"
+              "                           (the CIGAR's M = X D stretches between its N), on an admissible strand; no gene\n"
+              "                           or several: the read is dropped (featureCounts' default rule, decided on the\n"
+              "                           GPU); features.tsv names a gene by its gene_name where the file has one (not\n"
+              "                           with --gene-tag, --dump-staging)\n"
+              "      --annotation-feature <F> the lines taken: column 3 equals F [default: exon]; gene: whole gene bodies,\n"
+              "                           introns included (single-nucleus runs)\n"
+              "      --annotation-attribute <A> the attribute of column 9 that names the gene [default: gene_id]\n"
+              "      --gene-strand <S>    forward, reverse or unstranded [default: forward]: a feature is admissible on the\n"
+              "                           read's strand, on the opposite one, or on either (featureCounts -s 1, 2, 0)\n"
               "      --count-matrix <DIR> with --per-gene: write the molecules per cell and gene to DIR (made if it is\n"
               "                           not there) as features.tsv, barcodes.tsv, matrix.mtx (molecules) and reads.mtx\n"
               "                           (reads), MatrixMarket coordinate files sorted by cell, then gene, counted on the GPU\n"
@@ -344,6 +371,16 @@ Cli parse(int argc, char **argv)
         else if (a == "--per-cell") c.per_cell = true;
         else if (a == "--per-gene") c.per_gene = true;
         else if (a == "--gene-tag") { c.gene_tag = need(i); c.gene_tag_given = true; } // (looked at by validate)
+        else if (a == "--gene-annotation" || a == "--annotation-feature" || a == "--annotation-attribute" || a == "--gene-strand") {
+            const std::string v = need(i);
+            std::string &value = a == "--gene-annotation" ? c.gene_annotation : a == "--annotation-feature" ? c.annotation_feature
+                                 : a == "--annotation-attribute" ? c.annotation_attribute : c.gene_strand;
+            bool &given = a == "--gene-annotation" ? c.gene_annotation_given : a == "--annotation-feature" ? c.annotation_feature_given
+                          : a == "--annotation-attribute" ? c.annotation_attribute_given : c.gene_strand_given;
+            if (given && value != v) die(a + " given twice with different values: '" + value + "' and '" + v + "'");
+            value = v;
+            given = true;
+        }
         else if (a == "--count-matrix") c.count_matrix = need(i);
         else if (a == "--output-stats") c.output_stats = need(i);
         else if (a == "--output-stats-seed") {
@@ -492,6 +529,9 @@ std::vector<uint8_t> read_whitelist(const std::string &path, size_t &umi_len, co
     return list;
 }
 
+// --gene-annotation: the file's taken lines into args.annotation, or the message that ends the run (annotation.hpp)
+void read_annotation(Cli &args);
+
 // the one spelling of --stage's values (each mode asks at its own place among its refusals)
 void check_stage(const Cli &args)
 {
@@ -550,6 +590,24 @@ bool validate(Cli &args)
         if (t.size() != 2 || !alpha(t[0]) || !(alpha(t[1]) || (t[1] >= '0' && t[1] <= '9')))
             die("--gene-tag wants a tag name of two characters, [A-Za-z][A-Za-z0-9]: '" + t + "'");
         if (!args.count_matrix.empty() && !args.dump_staging.empty()) die("--count-matrix does not go with --dump-staging");
+    }
+    // --gene-annotation: likewise, the file included
+    if (!args.gene_annotation_given) {
+        for (const auto &f : {std::make_pair(args.annotation_feature_given, "--annotation-feature"),
+                              std::make_pair(args.annotation_attribute_given, "--annotation-attribute"),
+                              std::make_pair(args.gene_strand_given, "--gene-strand")})
+            if (f.first) die(std::string(f.second) + " goes with --gene-annotation only");
+    } else {
+        if (!args.per_gene) die("--gene-annotation goes with --per-gene only");
+        if (args.gene_tag_given) die("--gene-annotation does not go with --gene-tag (the gene comes from the file, not from a tag)");
+        if (!args.dump_staging.empty()) die("--gene-annotation does not go with --dump-staging (which stops before the GPU)");
+        if (args.gene_strand == "forward") args.gene_strand_mode = UMI_STRAND_FORWARD;
+        else if (args.gene_strand == "reverse") args.gene_strand_mode = UMI_STRAND_REVERSE;
+        else if (args.gene_strand == "unstranded") args.gene_strand_mode = UMI_STRAND_UNSTRANDED;
+        else die("--gene-strand wants forward, reverse or unstranded: '" + args.gene_strand + "'");
+        if (args.annotation_feature.empty()) die("--annotation-feature wants a feature type");
+        if (args.annotation_attribute.empty()) die("--annotation-attribute wants an attribute name");
+        read_annotation(args);
     }
     // --umi-filtering: likewise
     if (args.umi_filtering_given && args.umi_filtering != "none" && args.umi_filtering != "multi-gene")

@@ -23,6 +23,8 @@
 // --umi-filtering multi-gene: likewise umi_filter_multigene.
 //
 // --cell-filter RULE (with --count-matrix): likewise umi_call_cells.
+//
+// --gene-annotation FILE: likewise umi_assign_genes.
 #pragma once
 #include <chrono>
 #include <dlfcn.h>
@@ -97,6 +99,9 @@ struct HipLib {
     // --cell-filter: likewise
     bool want_cells = false;
     decltype(&umi_call_cells) call_cells = nullptr;
+    // --gene-annotation: likewise
+    bool want_genes = false;
+    decltype(&umi_assign_genes) assign_genes = nullptr;
     // (the HIP runtime the library brings along: device buffers for the arrays above)
     int (*hip_set_device)(int) = nullptr; // (the current device is per thread: the context was made on another)
     int (*hip_malloc)(void **, size_t) = nullptr;
@@ -107,7 +112,8 @@ struct HipLib {
           want_correct(!args.whitelist.empty()), want_barcodes(!args.cell_list.empty() && !args.cell_wl_multi),
           want_barcodes_multi(!args.cell_list.empty() && args.cell_wl_multi),
           want_count(!args.count_matrix.empty()), want_stats(!args.output_stats.empty()),
-          want_multigene(args.filter_multigene), want_cells(args.cell_filter_given)
+          want_multigene(args.filter_multigene), want_cells(args.cell_filter_given),
+          want_genes(args.gene_annotation_given)
     {
     }
     bool load()
@@ -152,6 +158,7 @@ struct HipLib {
         if (want_stats) dedup_stats = (decltype(dedup_stats))sym("umi_dedup_stats");
         if (want_multigene) filter_multigene = (decltype(filter_multigene))sym("umi_filter_multigene");
         if (want_cells) call_cells = (decltype(call_cells))sym("umi_call_cells");
+        if (want_genes) assign_genes = (decltype(assign_genes))sym("umi_assign_genes");
         hip_set_device = (decltype(hip_set_device))sym("hipSetDevice");
         hip_malloc = (decltype(hip_malloc))sym("hipMalloc");
         hip_memcpy = (decltype(hip_memcpy))sym("hipMemcpy");

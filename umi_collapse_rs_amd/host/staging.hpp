@@ -30,6 +30,10 @@
 // and "Number of (cell, gene) groups" ("Number of gene groups" without --per-cell) and loses "Number of unique
 // alignment positions"; --dump-staging appends every bucket's gene id behind the cell ids.
 //
+// --gene-annotation (annotation.hpp): the gene is what umi_assign_genes made of the read (AssignedGene below) and
+// the tag is not looked at; a read outside every gene is dropped like one without the tag ("Number of reads outside
+// every gene" in that line's place), one in several genes like one whose tag names several.
+//
 // --cell-whitelist-multi (cli.hpp has the flags, umicollapse_main.cpp the call): a read with the cell barcode tag
 // must carry --cell-quality-tag (default CY, type Z) as well -- a read with the one and without the other ends the
 // run with status 101, as a tag of another type does; its length and bytes (33..126) are looked at where the
@@ -201,7 +205,12 @@ struct ReadTags {
     std::string_view gene;        // --per-gene: the gene, likewise
     bool several_genes = false;   // ... its value lists more than one (';' or ','): the read is dropped
 };
-uint8_t read_tags(const Cli &args, const umi::bam::Record &r, ReadTags &t, std::string &err)
+// --gene-annotation: what umi_assign_genes made of a read (UMI_GENE_*), and the gene's id where it is assigned
+struct AssignedGene {
+    uint8_t status = UMI_GENE_NONE;
+    std::string_view id;
+};
+uint8_t read_tags(const Cli &args, const umi::bam::Record &r, ReadTags &t, std::string &err, const AssignedGene *assigned = nullptr)
 {
     auto look = [&](const std::string &tag, umi::bam::AuxField &f) -> bool {
         const umi::bam::AuxFind got = umi::bam::find_aux(r, tag.c_str(), &f);
@@ -234,7 +243,11 @@ uint8_t read_tags(const Cli &args, const umi::bam::Record &r, ReadTags &t, std::
             if (!err.empty()) return 0;
         }
     }
-    if (args.per_gene) {
+    if (args.per_gene && assigned) { // --gene-annotation: the tag is not looked at
+        if (assigned->status == UMI_GENE_NONE) miss |= MISS_GENE;
+        t.gene = assigned->id;
+        t.several_genes = assigned->status == UMI_GENE_SEVERAL;
+    } else if (args.per_gene) {
         std::string_view g;
         if (look(args.gene_tag, f)) g = std::string_view((const char *)f.value, f.len);
         if (!err.empty()) return 0;
@@ -364,6 +377,7 @@ void write_list_metrics(const std::string &path, const char *item, const std::ve
 struct Summary {
     size_t total_read_count = 0, unmapped = 0, unpaired = 0, chimeric = 0, no_umi_tag = 0, no_cell = 0;
     size_t no_gene = 0, several_genes = 0, n_genes = 0; // --per-gene
+    size_t annotation_genes = 0, annotation_features = 0, annotation_unknown = 0; // --gene-annotation: on the file's references
     uint64_t cb_counts[5] = {0, 0, 0, 0, 0}; // --cell-whitelist: exact, corrected, unlisted, ambiguous, (-multi) resolved
     uint64_t wl_counts[3] = {0, 0, 0};    // --umi-whitelist: exact, corrected, uncorrectable
     size_t n_positions = 0, nb = 0, n = 0, max_umi = 0;
@@ -384,8 +398,13 @@ struct Summary {
         if (!args.umi_tag.empty()) std::fprintf(stderr, "Number of reads without a UMI tag: %zu\n", no_umi_tag);
         if (args.per_cell) std::fprintf(stderr, "Number of reads without a cell barcode: %zu\n", no_cell);
         if (args.per_gene) {
-            std::fprintf(stderr, "Number of reads without a gene tag: %zu\n", no_gene);
+            std::fprintf(stderr, "Number of reads %s: %zu\n", args.gene_annotation_given ? "outside every gene" : "without a gene tag", no_gene);
             std::fprintf(stderr, "Number of reads assigned to several genes: %zu\n", several_genes);
+            if (args.gene_annotation_given) {
+                std::fprintf(stderr, "Gene annotation: %zu genes, %zu features\n", annotation_genes, annotation_features);
+                std::fprintf(stderr, "Gene strand: %s\n", args.gene_strand.c_str());
+                std::fprintf(stderr, "Number of annotation lines on unknown references: %zu\n", annotation_unknown);
+            }
         }
         if (!args.cell_list.empty()) {
             std::fprintf(stderr, "Number of reads with a corrected cell barcode: %llu\n", (unsigned long long)cb_counts[1]);

@@ -87,9 +87,13 @@
 // --cell-filter RULE (with --per-cell --per-gene --count-matrix DIR; cli.hpp has the flag's definition, its files and
 // its refusals): after umi_count_matrix one call to umi_call_cells over the triplets matrix.mtx holds; DIR/filtered/,
 // DIR/cells.tsv and eight summary lines are added, everything else stays byte for byte (call_cells() below).
+// --gene-annotation FILE (with --per-gene; annotation.hpp has the flags' definition, the file's reader and the
+// refusals): one call to umi_assign_genes over every mapped read, after the file is read and before the per-read
+// pass, which takes its verdict in the gene tag's place (assign_genes() below).
 // --algo cluster: connected components of "within -k" (cli.hpp); every pipeline here only forwards the algorithm
 // to the library, so it goes with every flag --algo dir goes with.
 // Not implemented, as in the reference: --algo cc (that spelling stays refused; `cluster` is the mode's name).
+#include "annotation.hpp"
 #include "fastq_mode.hpp"
 #include "hiplib.hpp"
 #include "staging.hpp"
@@ -172,6 +176,29 @@ struct OnePass {
     std::vector<std::string_view> cell_names; // --count-matrix: what barcodes.tsv calls every cell, in id order
     std::vector<std::vector<std::string_view>> gene_seen; // --per-gene: per thread, its genes in order of appearance
     std::vector<std::string_view> gene_names;             // ... and all of them in id order
+    // --gene-annotation: per record what umi_assign_genes made of it (a record the call did not see: none), the id
+    // of every gene of the call, and what features.tsv calls a gene beside its id (its gene_name where it has one)
+    std::vector<uint8_t> assigned_status;
+    std::vector<int32_t> assigned_gene;
+    std::vector<std::string_view> annotation_ids;
+    std::unordered_map<std::string_view, std::string_view> gene_display;
+    const AssignedGene *assigned(uint32_t ri, AssignedGene &a) const
+    {
+        if (!args.gene_annotation_given) return nullptr;
+        a.status = assigned_status[ri];
+        a.id = a.status == UMI_GENE_ASSIGNED ? annotation_ids[(size_t)assigned_gene[ri]] : std::string_view();
+        return &a;
+    }
+    // features.tsv: "<gene>\t<name>\tGene Expression" per gene in id order, the name being the id without an annotation
+    std::string features_text() const
+    {
+        std::string text;
+        for (const std::string_view &g : gene_names) {
+            const auto d = gene_display.find(g);
+            text.append(g).append("\t").append(d == gene_display.end() ? g : d->second).append("\tGene Expression\n");
+        }
+        return text;
+    }
     std::vector<uint32_t> out_records; // the records to write, in order; first those written before dedup (--keep-unmapped, :104-106)
 
     // the staged arrays: unique (position, UMI) entries in canonical order
@@ -232,6 +259,7 @@ struct OnePass {
     int run()
     {
         read_input();
+        if (args.gene_annotation_given) assign_genes();
         choose_staging();
         per_read_pass();
         if (!args.cell_list.empty()) correct_cells();
@@ -281,6 +309,94 @@ struct OnePass {
         chunk = (n_rec + T - 1) / T;
     }
 
+    // --gene-annotation: the file's lines on the BAM's references, every mapped read's reference, position, strand
+    // and CIGAR words gathered (the walk is the device's), one call; what it made of a read is what read_tags sees
+    // in the gene tag's place
+    void assign_genes()
+    {
+        const Cli::Annotation &an = args.annotation;
+        // the BAM header's reference names -> ids (parse() has checked the lengths)
+        std::unordered_map<std::string_view, int32_t> tid_of;
+        {
+            const uint8_t *p = in.data.data();
+            size_t q = 8 + (size_t)umi::bam::rd_i32(p + 4) + 4;
+            for (int32_t r = 0; r < in.n_ref; r++) {
+                const size_t l_name = (size_t)umi::bam::rd_i32(p + q);
+                std::string_view name((const char *)p + q + 4, l_name);
+                if (!name.empty() && name.back() == '\0') name.remove_suffix(1);
+                tid_of.emplace(name, r); // (a name that occurs twice: its first id, as a lookup by name would give)
+                q += 4 + l_name + 4;
+            }
+        }
+        std::vector<int32_t> tid_of_ref(an.refs.size());
+        for (size_t r = 0; r < an.refs.size(); r++) {
+            const auto it = tid_of.find(an.refs[r]);
+            tid_of_ref[r] = it == tid_of.end() ? -1 : it->second;
+        }
+        // the lines on known references, their genes numbered anew by first appearance among them
+        std::vector<int32_t> x_ref, x_start, x_end, x_gene, new_gene(an.gene_ids.size(), -1);
+        std::vector<uint8_t> x_strand;
+        for (size_t i = 0; i < an.gene.size(); i++) {
+            const int32_t tid = tid_of_ref[an.ref_name[i]];
+            if (tid < 0) {
+                sum.annotation_unknown++;
+                continue;
+            }
+            int32_t &g = new_gene[(size_t)an.gene[i]];
+            if (g < 0) {
+                g = (int32_t)annotation_ids.size();
+                const std::string &id = an.gene_ids[(size_t)an.gene[i]], &name = an.gene_names[(size_t)an.gene[i]];
+                annotation_ids.emplace_back(id);
+                gene_display.emplace(id, name.empty() ? std::string_view(id) : std::string_view(name));
+            }
+            x_ref.push_back(tid);
+            x_start.push_back(an.start[i]);
+            x_end.push_back(an.end[i]);
+            x_strand.push_back(an.strand[i]);
+            x_gene.push_back(g);
+        }
+        sum.annotation_genes = annotation_ids.size();
+        sum.annotation_features = x_gene.size();
+        // the reads the call sees: mapped, on a reference
+        std::vector<uint32_t> cand;
+        std::vector<uint64_t> c_off(1, 0);
+        for (uint32_t ri = 0; ri < n_rec; ri++) {
+            const umi::bam::Record &r = in.records[ri];
+            if (r.is_unmapped() || r.tid() < 0) continue;
+            cand.push_back(ri);
+            c_off.push_back(c_off.back() + r.n_cigar());
+        }
+        const size_t nc = cand.size(), per = (nc + T - 1) / T;
+        std::vector<int32_t> r_ref(nc), r_pos(nc), r_gene(nc);
+        std::vector<uint8_t> r_rev(nc), r_status(nc);
+        std::vector<uint32_t> words((size_t)c_off.back() + 1);
+        umi::bgzf::parallel_for(T, T, [&](size_t t) {
+            for (size_t j = t * per; j < std::min(nc, (t + 1) * per); j++) {
+                const umi::bam::Record &r = in.records[cand[j]];
+                r_ref[j] = r.tid();
+                r_pos[j] = r.pos();
+                r_rev[j] = r.is_reverse() ? 1 : 0;
+                std::memcpy(&words[(size_t)c_off[j]], r.cigar(), 4 * (size_t)r.n_cigar());
+            }
+        });
+        assigned_status.assign(n_rec, UMI_GENE_NONE);
+        assigned_gene.assign(n_rec, -1);
+        uint64_t counts[3] = {0, 0, 0};
+        if (nc) {
+            need_ctx();
+            if (!lib.assign_genes) die("libumihip.so lacks umi_assign_genes");
+            if (lib.assign_genes(ctx, x_ref.data(), x_start.data(), x_end.data(), x_strand.data(), x_gene.data(), x_gene.size(),
+                                 (uint32_t)annotation_ids.size(), args.gene_strand_mode, r_ref.data(), r_pos.data(), r_rev.data(),
+                                 words.data(), c_off.data(), nc, r_gene.data(), r_status.data(), counts) != UMI_OK)
+                die(lib.last_error());
+        }
+        for (size_t j = 0; j < nc; j++) {
+            assigned_status[cand[j]] = r_status[j];
+            assigned_gene[cand[j]] = r_gene[j];
+        }
+        lap("gene annotation");
+    }
+
     // the UMI length, and where the reads are staged
     void choose_staging()
     {
@@ -290,7 +406,8 @@ struct OnePass {
                 if (read_state(args, in.records[ri], u, c) == 0) {
                     ReadTags tg;
                     std::string err;
-                    const uint8_t miss = read_tags(args, in.records[ri], tg, err); // (a read without its tags is not staged)
+                    AssignedGene ag;
+                    const uint8_t miss = read_tags(args, in.records[ri], tg, err, assigned(ri, ag)); // (a read without its tags is not staged)
                     if (!err.empty()) die(err);
                     if (miss || tg.several_genes) continue;
                     umi_length = detect_length(args, in.records[ri], tg);
@@ -378,7 +495,8 @@ struct OnePass {
                 std::string err;
                 ReadTags tg;
                 if (!args.umi_tag.empty() || args.per_cell || args.per_gene) {
-                    ii.missing = read_tags(args, r, tg, err);
+                    AssignedGene ag;
+                    ii.missing = read_tags(args, r, tg, err, assigned(ri, ag));
                     if (ii.missing && err.empty()) {
                         ii.state = 6;
                         continue;
@@ -868,8 +986,7 @@ struct OnePass {
             const bool ok = std::fwrite(text.data(), 1, text.size(), f) == text.size();
             if (std::fclose(f) != 0 || !ok) die("cannot write " + path);
         };
-        std::string text;
-        for (const std::string_view &g : gene_names) text.append(g).append("\t").append(g).append("\tGene Expression\n");
+        std::string text = features_text();
         write("features.tsv", text);
         text.clear();
         if (!args.per_cell) text = "all\n";
@@ -922,8 +1039,7 @@ struct OnePass {
                                f_col.data(), f_mol.data(), f_reads.data(), &f_nnz, sum.cell_counts) != UMI_OK)
                 die(lib.last_error());
         }
-        std::string text;
-        for (const std::string_view &g : gene_names) text.append(g).append("\t").append(g).append("\tGene Expression\n");
+        std::string text = features_text();
         write("filtered/features.tsv", text);
         text.clear();
         std::string table = "barcode\treads\tmolecules\tgenes\tcalled\n";
