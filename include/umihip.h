@@ -159,7 +159,9 @@ const char *umi_last_error(void);
  *                    over the whole grid instead of by one wave (raised by itself where the deep buckets' tables,
  *                    80 bytes per base each, would pass 512 MB)
  *   "gene_top"       0/1 (default 1): umi_assign_genes searches a sampled top of its index in LDS before the
- *                    index itself (0: the index alone)
+ *                    index itself (0: the index alone); umi_assign_genes_introns likewise, for both its tiers
+ *   "gene_body_top"  0/1 (default 1): with gene_top 1, umi_assign_genes_introns holds the gene bodies' tops in LDS
+ *                    beside the exons' (0: the exons' alone)
  * The round-1 tile kernels (bit-sliced masks, key-sorted scan + item walk, range pruning, hook/jump
  * collapse) and their options ("bitslice", "bs_*", "prune", "two_phase", "ovf_capacity") exist in the
  * development build only (make dev: libumihip_dev.so, -DUMIHIP_DEV), as cross-checks. */
@@ -555,6 +557,51 @@ int umi_assign_genes(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_
                      int strand_mode, const int32_t *read_ref, const int32_t *read_pos, const uint8_t *read_reverse,
                      const uint32_t *cigar, const uint64_t *cigar_off, uint64_t n_reads, int32_t *gene, uint8_t *status,
                      uint64_t counts[3]);
+
+/* ---- ... with their introns (the program's --gene-introns), on the GPU.  No counterpart in the reference; the
+ *      rules are STARsolo's GeneFull_ExonOverIntron and GeneFull, stated with this project's overlap of one base, and
+ *      tests/intron_model.py defines them.  Blocks of a read, exons, admissible strands and the set E of genes
+ *      that hit a read are umi_assign_genes', unchanged.  New:
+ *        Gene body: the exons of a gene are grouped by (reference, strand as written: '+', '-' or '.').  Each group
+ *          gives one body, [min start, max end) over the group's exons; the minimum and the maximum may come from
+ *          different exons.  A gene with exons on two references, or on '+' and '.', has one body per group.  No
+ *          `gene` or `transcript` line is needed: bodies come from whatever the caller passes as exons.
+ *        B: the genes with a body on the read's reference, on an admissible strand (the exons' rule; a '.' body is
+ *          always admissible), that shares at least one base with one of the read's blocks.  E is a subset of B.
+ *        UMI_INTRONS_EXON_FIRST: |E| = 1: assigned to that gene, tier exon.  |E| >= 2: several.  |E| = 0 and
+ *          |B| = 1: assigned, tier intron.  |E| = 0 and |B| = 0: none.  |E| = 0 and |B| >= 2: several.
+ *        UMI_INTRONS_ALL (plain GeneFull on derived bodies): |B| = 1: assigned, tier exon if E is not empty, else
+ *          intron.  |B| = 0: none.  |B| >= 2: several.
+ *        UMI_INTRONS_OFF: umi_assign_genes' result, every assigned read tier exon.
+ *      The minimum overlap is 1 throughout: a block that starts in an exon and runs into the intron is tier exon.
+ *      Not built: STARsolo's Ex50pAS half-of-the-read rule, antisense counting, spliced / unspliced (velocity)
+ *      matrices, paired reads.
+ * in : umi_assign_genes' arguments, and intron_mode, one of UMI_INTRONS_*.  The bodies are derived and both tiers
+ *      of the index built on the host inside the call; a read is walked against the exons, and again against the
+ *      bodies only where its verdict still depends on them.
+ * out: gene int32 [n_reads] and status uint8 [n_reads] as umi_assign_genes writes them; tier uint8 [n_reads],
+ *      UMI_GENE_TIER_EXON or UMI_GENE_TIER_INTRON, 0 where the read is not assigned; counts (host): the reads
+ *      assigned by an exon, assigned by an intron, none, several.
+ * Everything else is umi_assign_genes' contract: n_reads == 0 (UMI_OK, counts all zero, nothing else touched),
+ * n_exons == 0 (legal: every read is none), the first device of a multi-device context, a deferred call that is out
+ * ends first, and the errors and when they are found, tier among the required pointers; an unknown intron_mode is
+ * UMI_ERR_ARG before anything is launched.  Options "gene_top" and "gene_body_top". */
+#define UMI_INTRONS_OFF 0
+#define UMI_INTRONS_EXON_FIRST 1
+#define UMI_INTRONS_ALL 2
+#define UMI_GENE_TIER_EXON 0
+#define UMI_GENE_TIER_INTRON 1
+int umi_assign_genes_introns_device(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end,
+                                    const uint8_t *exon_strand, const int32_t *exon_gene, uint64_t n_exons, uint32_t n_genes,
+                                    int strand_mode, int intron_mode, const int32_t *d_read_ref, const int32_t *d_read_pos,
+                                    const uint8_t *d_read_reverse, const uint32_t *d_cigar, const uint64_t *d_cigar_off,
+                                    uint64_t n_reads, int32_t *d_gene, uint8_t *d_status, uint8_t *d_tier, uint64_t counts[4],
+                                    void *hip_stream);
+int umi_assign_genes_introns(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end,
+                             const uint8_t *exon_strand, const int32_t *exon_gene, uint64_t n_exons, uint32_t n_genes,
+                             int strand_mode, int intron_mode, const int32_t *read_ref, const int32_t *read_pos,
+                             const uint8_t *read_reverse, const uint32_t *cigar, const uint64_t *cigar_off, uint64_t n_reads,
+                             int32_t *gene, uint8_t *status, uint8_t *tier, uint64_t counts[4]);
 
 /* ---- molecules and reads per (column, row) pair (the program's --count-matrix): what a batched call kept,
  *      summed over its buckets into the triplets of a sparse matrix, on the GPU.  No counterpart in the

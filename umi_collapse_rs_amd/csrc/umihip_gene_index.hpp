@@ -21,9 +21,12 @@
 //
 // Top: every 2^shift-th end (the last end of each chunk of 2^shift segments), at most `cap` of them, small
 // enough for LDS.  A search over the top names the chunk, a search over the chunk's ends the segment.
+//
+// Gene bodies (umi_assign_genes_introns, --gene-introns) are a second tier of the same tables: the end of this file.
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <unordered_map>
 #include <vector>
 
 #if defined(__HIPCC__)
@@ -225,6 +228,69 @@ UMIHIP_HD inline int gene_assign_read(const GeneView &t, const GeneTop *top, uin
     if (found == GENE_HIT_NONE) return GENE_READ_NONE;
     *gene = found;
     return GENE_READ_ASSIGNED;
+}
+
+// ---- the second tier: gene bodies (umi_assign_genes_introns, the program's --gene-introns) ----
+// A gene's lines are grouped by (reference, strand as written); each group gives one body, [the group's smallest
+// start, its largest end).  The bodies are lines like any other: gene_index_build makes their tables with the same
+// `take` per strand class as the exons', and gene_query serves them unchanged.  Bodies nest, so GENE_MULTI segments
+// are the rule here where genes overlap.  Every exon lies inside its group's body: the genes E that hit a read by an
+// exon are among the genes B that hit it by a body.
+constexpr int GENE_INTRONS_OFF = 0, GENE_INTRONS_EXON_FIRST = 1, GENE_INTRONS_ALL = 2; // UMI_INTRONS_*
+constexpr int GENE_TIER_EXON = 0, GENE_TIER_INTRON = 1;                                // UMI_GENE_TIER_*
+
+struct GeneBodies {
+    std::vector<int32_t> ref, start, end, gene;
+    std::vector<uint8_t> strand;
+};
+
+// The bodies of the checked exons (gene_index_build's), in the order their groups first appear.
+inline void gene_bodies_derive(const int32_t *ref, const int32_t *start, const int32_t *end, const uint8_t *strand,
+                               const int32_t *gene, uint64_t n_exons, GeneBodies &b)
+{
+    b = GeneBodies();
+    // (gene and ref are below 2^31, the strand takes two bits: a group is one 64-bit key).  A file names a gene's
+    // lines one after another, so most lines find their group in `last` and not in the map
+    std::unordered_map<uint64_t, size_t> body_of;
+    uint64_t last_key = ~(uint64_t)0;
+    size_t last = 0;
+    for (uint64_t i = 0; i < n_exons; i++) {
+        const uint64_t sc = strand[i] == '+' ? 0 : strand[i] == '-' ? 1 : 2;
+        const uint64_t key = (uint64_t)gene[i] << 33 | (uint64_t)ref[i] << 2 | sc;
+        if (key != last_key) {
+            const auto at = body_of.emplace(key, b.gene.size());
+            if (at.second) {
+                b.ref.push_back(ref[i]);
+                b.start.push_back(start[i]);
+                b.end.push_back(end[i]);
+                b.strand.push_back(strand[i]);
+                b.gene.push_back(gene[i]);
+            }
+            last_key = key;
+            last = at.first->second;
+        }
+        b.start[last] = std::min(b.start[last], start[i]);
+        b.end[last] = std::max(b.end[last], end[i]);
+    }
+}
+
+// A read under --gene-introns: phase 1 is gene_assign_read against the exon table and gives E's verdict; a read
+// whose verdict still depends on B walks its CIGAR again, against the body table.  exon-first: E one gene: that gene,
+// tier exon; E several: several; E empty: B's verdict, tier intron.  all: E several: several (E is in B); else B's
+// verdict, tier exon where E is not empty, else intron.  off: E's verdict.  *tier is GENE_TIER_EXON unless the read is
+// assigned by an intron.  (A bad op code is found by phase 1, which looks at every word.)
+UMIHIP_HD inline int gene_assign_read_tiers(const GeneView &exons, const GeneTop *exon_top, const GeneView &bodies,
+                                            const GeneTop *body_top, int mode, uint32_t ref, int64_t pos, const uint32_t *cigar,
+                                            uint64_t n_cigar, int32_t *gene, int *tier)
+{
+    *tier = GENE_TIER_EXON;
+    int st = gene_assign_read(exons, exon_top, ref, pos, cigar, n_cigar, gene);
+    if (st == GENE_READ_BAD_OP || st == GENE_READ_SEVERAL || mode == GENE_INTRONS_OFF) return st;
+    const bool by_exon = st == GENE_READ_ASSIGNED;
+    if (by_exon && mode == GENE_INTRONS_EXON_FIRST) return st;
+    st = gene_assign_read(bodies, body_top, ref, pos, cigar, n_cigar, gene);
+    if (st == GENE_READ_ASSIGNED && !by_exon) *tier = GENE_TIER_INTRON;
+    return st;
 }
 
 } // namespace umihip

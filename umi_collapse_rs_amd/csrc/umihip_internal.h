@@ -523,6 +523,18 @@ int genes_on_device(void *workspace, const GeneTable *tables, int n_tables, bool
                     uint32_t n_reads, int32_t *d_gene, uint8_t *d_status, uint64_t counts[3], uint64_t *bad, uint32_t n_cus,
                     unsigned long long *h_pinned, hipStream_t s);
 
+// ---- ... with their introns (umihip_gene_introns.hip: umi_assign_genes_introns) ----
+// Two tiers of such tables, the exons' and the gene bodies' (n_tables of each, sampled at GENE_TOP_CAP and at
+// GENE_BODY_TOP_CAP), uploaded alike; mode: UMI_INTRONS_*.  use_body_top counts only with use_top.  h_pinned: 6
+// pinned words.  Returns as genes_on_device; counts: assigned by an exon, by an intron, none, several.
+constexpr uint32_t GENE_BODY_TOP_CAP = 512; // sampled ends of a body table in LDS, at most (option "gene_body_top")
+size_t gene_introns_workspace_bytes(const GeneTable *exons, const GeneTable *bodies, int n_tables);
+int gene_introns_on_device(void *workspace, const GeneTable *exons, const GeneTable *bodies, int n_tables, bool flip, int mode,
+                           bool use_top, bool use_body_top, const int32_t *d_ref, const int32_t *d_pos, const uint8_t *d_reverse,
+                           const uint32_t *d_cigar, const uint64_t *d_cigar_off, uint32_t n_reads, int32_t *d_gene, uint8_t *d_status,
+                           uint8_t *d_tier, uint64_t counts[4], uint64_t *bad, uint32_t n_cus, unsigned long long *h_pinned,
+                           hipStream_t s);
+
 // ---- molecules and reads per (column, row) pair (umihip_count.hip: umi_count_matrix) ----
 // h_off (pinned): the m + 1 offsets of the m >= 1 non-empty buckets; h_idx (pinned, null: nothing was left out):
 // their numbers in d_row / d_col.  The outputs take the triplets sorted by column, then row (capacity m);

@@ -35,6 +35,25 @@
 //
 // Not built: transcript-level containment (STARsolo's Gene: a read inside one transcript's exons), --paired,
 // fractional assignment of a read among several genes, a minimum overlap above 1.
+//
+// --gene-introns off|exon-first|all (with --gene-annotation; default off; tests/intron_model.py defines it): reads in
+// a gene's introns count too, as Cell Ranger 7 counts them by default and as single-nucleus runs need.  A gene's body:
+// its taken lines grouped by reference and strand as written (+, - or .), each group one body from the group's
+// smallest start to its largest end, which may come from different lines; no `gene` or `transcript` line is needed,
+// and bodies come from whatever --annotation-feature takes.  B: the genes with a body on the read's reference, on an
+// admissible strand (the features' rule; a . body always), that shares a base with a block; E, the genes that hit by a
+// feature, is a subset of B.  exon-first (STARsolo's GeneFull_ExonOverIntron, with this program's overlap of one
+// base): one gene in E: that gene, by an exon; two or more: several; E empty: one gene in B: that gene, by an
+// intron; none: none; two or more: several.  all (GeneFull on derived bodies): one gene in B: that gene, by an exon
+// where E is not empty, else by an intron; none: none; two or more: several.  off: the run without the flag, byte
+// for byte.  The minimum overlap is 1 throughout: a block that starts in an exon and runs on into the intron is
+// assigned by the exon.  The one call is umi_assign_genes_introns in umi_assign_genes' place; everything behind the
+// gene's id is --per-gene's, unchanged.  The summary gains, behind "Number of annotation lines on unknown
+// references": "Gene introns: <mode>", "Number of reads assigned by an exon", "Number of reads assigned by an
+// intron" (over every mapped read the call saw).  Refused with status 101 before the GPU is woken: the flag without
+// --gene-annotation; a value other than off, exon-first, all; the flag given twice with different values.
+// Not built: STARsolo's Ex50pAS half-of-the-read rule, antisense counting, spliced / unspliced (velocity) matrices
+// (a read's tier would have to travel through staging), --paired.
 #pragma once
 #include <unordered_map>
 

@@ -73,6 +73,8 @@
 // --gene-annotation FILE [--annotation-feature F] [--annotation-attribute A] [--gene-strand S] (with --per-gene): a
 // read's gene comes from a GTF, decided on the GPU, and not from a tag (annotation.hpp has the flags' definition, the
 // file's reader and every refusal; the flags and the file are looked at here, in validate(), before the GPU is woken).
+// --gene-introns off|exon-first|all (with --gene-annotation) [off]: reads in a gene's introns count too, by
+// umi_assign_genes_introns (annotation.hpp has the rule, the summary lines and the refusals).
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -153,6 +155,10 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     std::string gene_annotation, annotation_feature = "exon", annotation_attribute = "gene_id", gene_strand = "forward";
     bool gene_annotation_given = false, annotation_feature_given = false, annotation_attribute_given = false, gene_strand_given = false;
     int gene_strand_mode = UMI_STRAND_FORWARD; // --gene-strand as UMI_STRAND_* (filled in by validate())
+    // --gene-introns M: off, exon-first or all (annotation.hpp); off and no flag are the same run
+    std::string gene_introns = "off";
+    bool gene_introns_given = false;
+    int gene_introns_mode = UMI_INTRONS_OFF; // as UMI_INTRONS_* (filled in by validate())
     struct Annotation { // the file's taken lines (filled in by validate(): read_annotation)
         std::vector<std::string> refs;      // the reference names of column 1, in order of first appearance
         std::vector<uint32_t> ref_name;     // per taken line: its reference, an index into refs
@@ -266,6 +272,11 @@ void usage()
               "      --annotation-attribute <A> the attribute of column 9 that names the gene [default: gene_id]\n"
               "      --gene-strand <S>    forward, reverse or unstranded [default: forward]: a feature is admissible on the\n"
               "                           read's strand, on the opposite one, or on either (featureCounts -s 1, 2, 0)\n"
+              "      --gene-introns <M>   off, exon-first or all [default: off], with --gene-annotation: a gene's body runs\n"
+              "                           from its first taken line to its last, per reference and strand.  exon-first: a\n"
+              "                           read that hits no exon goes to the one gene whose body it shares a base with\n"
+              "                           (STARsolo's GeneFull_ExonOverIntron, Cell Ranger 7's default); all: every read\n"
+              "                           goes by the bodies alone (GeneFull); no body or several: dropped\n"
               "      --count-matrix <DIR> with --per-gene: write the molecules per cell and gene to DIR (made if it is\n"
               "                           not there) as features.tsv, barcodes.tsv, matrix.mtx (molecules) and reads.mtx\n"
               "                           (reads), MatrixMarket coordinate files sorted by cell, then gene, counted on the GPU\n"
@@ -380,6 +391,13 @@ Cli parse(int argc, char **argv)
             if (given && value != v) die(a + " given twice with different values: '" + value + "' and '" + v + "'");
             value = v;
             given = true;
+        }
+        else if (a == "--gene-introns") {
+            const std::string v = need(i);
+            if (c.gene_introns_given && c.gene_introns != v)
+                die(a + " given twice with different values: '" + c.gene_introns + "' and '" + v + "'");
+            c.gene_introns = v;
+            c.gene_introns_given = true;
         }
         else if (a == "--count-matrix") c.count_matrix = need(i);
         else if (a == "--output-stats") c.output_stats = need(i);
@@ -597,7 +615,12 @@ bool validate(Cli &args)
                               std::make_pair(args.annotation_attribute_given, "--annotation-attribute"),
                               std::make_pair(args.gene_strand_given, "--gene-strand")})
             if (f.first) die(std::string(f.second) + " goes with --gene-annotation only");
+        if (args.gene_introns_given) die("--gene-introns goes with --gene-annotation only");
     } else {
+        if (args.gene_introns == "off") args.gene_introns_mode = UMI_INTRONS_OFF;
+        else if (args.gene_introns == "exon-first") args.gene_introns_mode = UMI_INTRONS_EXON_FIRST;
+        else if (args.gene_introns == "all") args.gene_introns_mode = UMI_INTRONS_ALL;
+        else die("--gene-introns wants off, exon-first or all: '" + args.gene_introns + "'");
         if (!args.per_gene) die("--gene-annotation goes with --per-gene only");
         if (args.gene_tag_given) die("--gene-annotation does not go with --gene-tag (the gene comes from the file, not from a tag)");
         if (!args.dump_staging.empty()) die("--gene-annotation does not go with --dump-staging (which stops before the GPU)");

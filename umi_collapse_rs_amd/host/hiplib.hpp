@@ -25,6 +25,8 @@
 // --cell-filter RULE (with --count-matrix): likewise umi_call_cells.
 //
 // --gene-annotation FILE: likewise umi_assign_genes.
+//
+// --gene-introns exon-first|all: likewise umi_assign_genes_introns, in umi_assign_genes' place.
 #pragma once
 #include <chrono>
 #include <dlfcn.h>
@@ -102,6 +104,9 @@ struct HipLib {
     // --gene-annotation: likewise
     bool want_genes = false;
     decltype(&umi_assign_genes) assign_genes = nullptr;
+    // --gene-introns exon-first|all: likewise, in its place
+    bool want_introns = false;
+    decltype(&umi_assign_genes_introns) assign_genes_introns = nullptr;
     // (the HIP runtime the library brings along: device buffers for the arrays above)
     int (*hip_set_device)(int) = nullptr; // (the current device is per thread: the context was made on another)
     int (*hip_malloc)(void **, size_t) = nullptr;
@@ -113,7 +118,8 @@ struct HipLib {
           want_barcodes_multi(!args.cell_list.empty() && args.cell_wl_multi),
           want_count(!args.count_matrix.empty()), want_stats(!args.output_stats.empty()),
           want_multigene(args.filter_multigene), want_cells(args.cell_filter_given),
-          want_genes(args.gene_annotation_given)
+          want_genes(args.gene_annotation_given && args.gene_introns_mode == UMI_INTRONS_OFF),
+          want_introns(args.gene_annotation_given && args.gene_introns_mode != UMI_INTRONS_OFF)
     {
     }
     bool load()
@@ -159,6 +165,7 @@ struct HipLib {
         if (want_multigene) filter_multigene = (decltype(filter_multigene))sym("umi_filter_multigene");
         if (want_cells) call_cells = (decltype(call_cells))sym("umi_call_cells");
         if (want_genes) assign_genes = (decltype(assign_genes))sym("umi_assign_genes");
+        if (want_introns) assign_genes_introns = (decltype(assign_genes_introns))sym("umi_assign_genes_introns");
         hip_set_device = (decltype(hip_set_device))sym("hipSetDevice");
         hip_malloc = (decltype(hip_malloc))sym("hipMalloc");
         hip_memcpy = (decltype(hip_memcpy))sym("hipMemcpy");

@@ -90,6 +90,8 @@
 // --gene-annotation FILE (with --per-gene; annotation.hpp has the flags' definition, the file's reader and the
 // refusals): one call to umi_assign_genes over every mapped read, after the file is read and before the per-read
 // pass, which takes its verdict in the gene tag's place (assign_genes() below).
+// --gene-introns exon-first|all (with --gene-annotation; annotation.hpp): that one call is umi_assign_genes_introns,
+// whose gene and status are used alike; its counts by tier go into the summary, the tier of a read goes nowhere.
 // --algo cluster: connected components of "within -k" (cli.hpp); every pipeline here only forwards the algorithm
 // to the library, so it goes with every flag --algo dir goes with.
 // Not implemented, as in the reference: --algo cc (that spelling stays refused; `cluster` is the mode's name).
@@ -382,7 +384,19 @@ struct OnePass {
         assigned_status.assign(n_rec, UMI_GENE_NONE);
         assigned_gene.assign(n_rec, -1);
         uint64_t counts[3] = {0, 0, 0};
-        if (nc) {
+        if (nc && args.gene_introns_mode != UMI_INTRONS_OFF) { // --gene-introns: the two-tier call in the plain one's place
+            need_ctx();
+            if (!lib.assign_genes_introns) die("libumihip.so lacks umi_assign_genes_introns");
+            std::vector<uint8_t> r_tier(nc);
+            uint64_t by_tier[4] = {0, 0, 0, 0};
+            if (lib.assign_genes_introns(ctx, x_ref.data(), x_start.data(), x_end.data(), x_strand.data(), x_gene.data(),
+                                         x_gene.size(), (uint32_t)annotation_ids.size(), args.gene_strand_mode,
+                                         args.gene_introns_mode, r_ref.data(), r_pos.data(), r_rev.data(), words.data(),
+                                         c_off.data(), nc, r_gene.data(), r_status.data(), r_tier.data(), by_tier) != UMI_OK)
+                die(lib.last_error());
+            sum.by_exon = by_tier[0];
+            sum.by_intron = by_tier[1];
+        } else if (nc) {
             need_ctx();
             if (!lib.assign_genes) die("libumihip.so lacks umi_assign_genes");
             if (lib.assign_genes(ctx, x_ref.data(), x_start.data(), x_end.data(), x_strand.data(), x_gene.data(), x_gene.size(),
