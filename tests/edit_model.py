@@ -263,3 +263,194 @@ def batch(L, n_frac):
         mats = [edit_matrix(u) for u, _ in buckets]
         _batches[key] = (buckets, mats, pack(buckets))
     return _batches[key]
+
+
+# ---- inputs that put pairs at every distance (tests/test_gpu_edit_distances.py) ------------------------------
+
+LETTERS = "ACGTN"
+PAIR_FREQS = ((2, 1), (1, 1), (3, 3))
+_pairs = {}
+
+
+def _random_string(rng, L, letters=LETTERS):
+    return "".join(letters[c] for c in rng.integers(0, len(letters), L))
+
+
+def adversarial_pairs(L, seed=0):
+    """Ordered pairs (a, b) of distinct strings of length L over ACGTN with every distance 1..L among them, made
+    once per (L, seed) and without repeats.  A family whose members are not symmetric comes in both orders, (a, b)
+    and (b, a): the kernel takes the first entry of a pair as Myers' pattern and the second as its text.
+      substitutions  exactly d of them at d places, d = 1..L, two pairs each of four kinds: among A, C, G, T;
+                     every one to N; every one from N; any letter to any other
+      filter bound   A*L against C*d + A*(L-d) and against A*(L-d) + C*d: L1 of the letter counts is 2 d
+      rotations      by s = 1..L-1, of a random string and of ("ACGT"*6)[:L]: d_E small, d_H large
+      homopolymers   x*L against y*d + x*(L-d) and x*(L-d) + y*d for all 20 ordered letter pairs and d = 1..L
+                     (x = A: code 000, whose match vector has garbage above bit L-1; N: no letter count)
+      alternating    xyxy.. against yxyx.. for all 20 ordered letter pairs
+      reverse        a string against its reverse
+      random         unrelated strings"""
+    if (L, seed) in _pairs:
+        return _pairs[(L, seed)]
+    rng = np.random.default_rng(4100 + 100 * seed + L)
+    out, seen = [], set()
+
+    def add(a, b, both=True):
+        for p in ((a, b), (b, a)) if both else ((a, b),):
+            if p[0] != p[1] and p not in seen:
+                seen.add(p)
+                out.append(p)
+
+    for d in range(1, L + 1):
+        for _ in range(2):
+            at = rng.choice(L, d, replace=False)
+            a = list(_random_string(rng, L, "ACGT"))        # among A, C, G, T
+            b = a[:]
+            for i in at:
+                b[i] = str(rng.choice([c for c in "ACGT" if c != a[i]]))
+            add("".join(a), "".join(b))
+            a = list(_random_string(rng, L, "ACGT"))        # every one to N
+            b = a[:]
+            for i in at:
+                b[i] = "N"
+            add("".join(a), "".join(b))
+            b = list(_random_string(rng, L, "ACGT"))        # every one from N
+            a = b[:]
+            for i in at:
+                a[i] = "N"
+            add("".join(a), "".join(b))
+            a = list(_random_string(rng, L))                # any letter to any other
+            b = a[:]
+            for i in at:
+                b[i] = str(rng.choice([c for c in LETTERS if c != a[i]]))
+            add("".join(a), "".join(b))
+    for d in range(1, L + 1):
+        add("A" * L, "C" * d + "A" * (L - d))
+        add("A" * L, "A" * (L - d) + "C" * d)
+    for base in (_random_string(rng, L), ("ACGT" * 6)[:L]):
+        for s in range(1, L):
+            add(base, base[s:] + base[:s])
+    for x in LETTERS:
+        for y in LETTERS:
+            if x == y:
+                continue
+            for d in range(1, L + 1):
+                add(x * L, y * d + x * (L - d))
+                add(x * L, x * (L - d) + y * d)
+    for x in LETTERS:
+        for y in LETTERS:
+            if x != y:
+                add(((x + y) * 11)[:L], ((y + x) * 11)[:L], both=False)   # (the other order is the pair (y, x))
+    for _ in range(4):
+        a = _random_string(rng, L)
+        add(a, a[::-1])
+    for _ in range(8):
+        add(_random_string(rng, L), _random_string(rng, L))
+    _pairs[(L, seed)] = out
+    return out
+
+
+def pair_buckets(pairs, freqs=PAIR_FREQS):
+    """One bucket of two entries per pair, a first, packed: (keys, nmask, freq, bucket_off).  freqs go round:
+    at p = 0.5 a directional call merges (2, 1) and (1, 1) iff d_E(a, b) <= k (thresholds 1 and 1 against
+    frequencies 1 and 1) and never (3, 3) (threshold 2 < 3 both ways)."""
+    return pack([([a, b], list(freqs[i % len(freqs)])) for i, (a, b) in enumerate(pairs)])
+
+
+def distinct_strings(L):
+    """The strings of adversarial_pairs(L), each once, in order of appearance."""
+    seen = {}
+    for a, b in adversarial_pairs(L):
+        seen.setdefault(a)
+        seen.setdefault(b)
+    return list(seen)
+
+
+def mixed_bucket(L, n, seed):
+    """n distinct strings of adversarial_pairs(L) -- all of them put in an order of the seed's, the first n of
+    that (fewer where there are fewer) -- with frequencies drawn from a short list, in rank order: (umis, freq).
+    Every family is in it, so its pairs spread over all distances and its letter counts over the filter's range."""
+    rng = np.random.default_rng(seed)
+    every = distinct_strings(L)
+    umis = [every[i] for i in rng.permutation(len(every))[:n]]
+    freq = [int(f) for f in rng.choice([1, 1, 2, 3, 5, 9, 20], len(umis))]
+    umis, freq, _ = canonical(umis, freq)
+    return umis, freq
+
+
+def all_strings_bucket(L):
+    """All 5^L strings of length L <= 4 in one bucket, freq 1 each: every pair there is."""
+    import itertools
+    assert L <= 4
+    umis = ["".join(t) for t in itertools.product(LETTERS, repeat=L)]
+    return umis, [1] * len(umis)
+
+
+def count_l1_matrix(umis):
+    """count_l1 of every pair of a bucket."""
+    if not umis:
+        return np.zeros((0, 0), np.int64)
+    a = np.array([np.frombuffer(u.encode(), dtype=np.uint8) for u in umis])
+    cnt = np.stack([(a == ord(c)).sum(1) for c in "ACGT"], 1).astype(np.int64)
+    return np.abs(cnt[:, None, :] - cnt[None, :, :]).sum(-1)
+
+
+def filter_hits(umis, k, l1=None):
+    """Pairs i < j of a bucket that pass the kernel's filter, count_l1 <= 2 min(k, L) (the call clamps k to the
+    length): what umi_stats.n_candidates counts.  l1: the bucket's count_l1_matrix, if at hand."""
+    if len(umis) < 2:
+        return 0
+    l1 = count_l1_matrix(umis) if l1 is None else l1
+    return int(np.triu(l1 <= 2 * min(k, len(umis[0])), 1).sum())
+
+
+def permitted_pairs(d, freq, k, p=0.5, algo=0, amf=0):
+    """Pairs i < j within k that the algorithm permits in at least one direction (what umi_stats.n_edges counts;
+    the rule of seq_reference in tests/test_gpu_large_k.py): directional (0) freq[j] <= thr(freq[i]) or the
+    other way round, adjacency (1) freq[j] <= amf, cluster (2) every pair."""
+    n = len(freq)
+    if n < 2:
+        return 0
+    f = np.array(freq, np.int64)
+    near = np.triu(np.asarray(d) <= k, 1)
+    if algo == 0:
+        thr = np.array([thr_f32(p, int(x)) for x in freq], np.int64)
+        ok = (f[None, :] <= thr[:, None]) | (f[:, None] <= thr[None, :])
+    elif algo == 1:
+        ok = np.broadcast_to(f[None, :] <= amf, (n, n))
+    else:
+        ok = np.ones((n, n), bool)
+    return int((near & ok).sum())
+
+
+def tile_hits(l1, k, L):
+    """Filter hits of every 64 x 64 tile of edit_pair_kernel's walk over one bucket: row tiles start at
+    multiples of 64 from the bucket's start, the column tiles of a row tile start at its first row and step by
+    64, and only pairs with row < column count.  {(row0, col0): hits}."""
+    n = len(l1)
+    hit = np.triu(np.asarray(l1) <= 2 * min(k, L), 1)
+    return {(r0, c0): int(hit[r0:r0 + 64, c0:c0 + 64].sum()) for r0 in range(0, n, 64) for c0 in range(r0, n, 64)}
+
+
+WHOLE_SIZES = (2, 63, 64, 65, 129, 330)
+_whole = {}
+
+
+def whole_batch(L):
+    """One call's buckets for the sweep over every k: a mixed_bucket of every size of WHOLE_SIZES with an empty
+    bucket after each; their distance and count_l1 matrices; the packed call.  Made once per L."""
+    if L not in _whole:
+        buckets = []
+        for n in WHOLE_SIZES:
+            buckets.append(mixed_bucket(L, n, seed=n))
+            buckets.append(([], []))
+        _whole[L] = (buckets, [edit_matrix(u) for u, _ in buckets], [count_l1_matrix(u) for u, _ in buckets], pack(buckets))
+    return _whole[L]
+
+
+def all_strings_batch(L):
+    """all_strings_bucket(L) as a call of its own, in whole_batch's form."""
+    key = ("all", L)
+    if key not in _whole:
+        buckets = [all_strings_bucket(L)]
+        _whole[key] = (buckets, [edit_matrix(u) for u, _ in buckets], [count_l1_matrix(u) for u, _ in buckets], pack(buckets))
+    return _whole[key]
