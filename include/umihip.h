@@ -161,7 +161,10 @@ const char *umi_last_error(void);
  *   "gene_top"       0/1 (default 1): umi_assign_genes searches a sampled top of its index in LDS before the
  *                    index itself (0: the index alone); umi_assign_genes_introns likewise, for both its tiers
  *   "gene_body_top"  0/1 (default 1): with gene_top 1, umi_assign_genes_introns holds the gene bodies' tops in LDS
- *                    beside the exons' (0: the exons' alone)
+ *                    beside the exons' (0: the exons' alone); umi_assign_genes_classes takes both options alike
+ *   "velocity_skip"  0/1 (default 0): 1: umi_velocity_matrix's reads load their molecule's evidence first and leave the
+ *                    atomic out where their bit is set (0: an atomic per read with evidence).  The result is the same;
+ *                    measured, the load costs more than it saves unless a molecule has very many reads
  * The round-1 tile kernels (bit-sliced masks, key-sorted scan + item walk, range pruning, hook/jump
  * collapse) and their options ("bitslice", "bs_*", "prune", "two_phase", "ovf_capacity") exist in the
  * development build only (make dev: libumihip_dev.so, -DUMIHIP_DEV), as cross-checks. */
@@ -574,8 +577,8 @@ int umi_assign_genes(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_
  *          intron.  |B| = 0: none.  |B| >= 2: several.
  *        UMI_INTRONS_OFF: umi_assign_genes' result, every assigned read tier exon.
  *      The minimum overlap is 1 throughout: a block that starts in an exon and runs into the intron is tier exon.
- *      Not built: STARsolo's Ex50pAS half-of-the-read rule, antisense counting, spliced / unspliced (velocity)
- *      matrices, paired reads.
+ *      Not built: STARsolo's Ex50pAS half-of-the-read rule, antisense counting, paired reads.  (Spliced / unspliced
+ *      matrices: umi_assign_genes_classes and umi_velocity_matrix, below.)
  * in : umi_assign_genes' arguments, and intron_mode, one of UMI_INTRONS_*.  The bodies are derived and both tiers
  *      of the index built on the host inside the call; a read is walked against the exons, and again against the
  *      bodies only where its verdict still depends on them.
@@ -602,6 +605,45 @@ int umi_assign_genes_introns(umi_ctx *ctx, const int32_t *exon_ref, const int32_
                              int strand_mode, int intron_mode, const int32_t *read_ref, const int32_t *read_pos,
                              const uint8_t *read_reverse, const uint32_t *cigar, const uint64_t *cigar_off, uint64_t n_reads,
                              int32_t *gene, uint8_t *status, uint8_t *tier, uint64_t counts[4]);
+
+/* ---- ... and the class of every assigned read (the program's --velocity), on the GPU.  A gene-level rule in exact
+ *      integers, NOT velocyto's or STARsolo's transcript-model rule: this project keeps no transcript models.
+ *      tests/velocity_model.py defines it.  A read's blocks, exons, admissible strands, E, B, status, gene and tier
+ *      are umi_assign_genes_introns', unchanged.  New, for an assigned read with gene g:
+ *        Blocks are cut to [0, 2^31), and the empty ones left out: b1 .. bm.  A gap is the stretch between one
+ *          block's end and the next one's start (what N operations skipped).
+ *        cover of an interval [s, e): the number of its positions that lie in an exon of g on the read's reference
+ *          and on an admissible strand.
+ *        UMI_READ_CLASS_INTRONIC: tier intron.  Tier exon: UMI_READ_CLASS_SPANNING where the blocks' summed cover
+ *          is less than their summed length (the read leaves the exons into an intron or past the gene's end);
+ *          otherwise UMI_READ_CLASS_JUNCTION where m >= 2 and some gap has cover < its length (the read skips an
+ *          intron); otherwise UMI_READ_CLASS_EXONIC.  UMI_READ_CLASS_NONE where the read is not assigned.
+ *      The classes are relative to the exons passed: where the caller passes whole genes as exons, every assigned
+ *      read is EXONIC.  Not built: transcript-model rules (velocyto's or STARsolo's own), paired reads.
+ * in : umi_assign_genes_introns' arguments.
+ * out: gene, status, tier and counts[4], bit for bit what umi_assign_genes_introns writes on the same input; cls
+ *      uint8 [n_reads], one of UMI_READ_CLASS_*; class_counts (host) [5]: the reads by class, indexed by
+ *      UMI_READ_CLASS_*.
+ * Everything else is umi_assign_genes_introns' contract (n_reads == 0, n_exons == 0, the first device of a
+ * multi-device context, a deferred call that is out ends first, the errors and when they are found, cls and
+ * class_counts among the required pointers, options "gene_top" and "gene_body_top"). */
+#define UMI_READ_CLASS_NONE 0
+#define UMI_READ_CLASS_EXONIC 1
+#define UMI_READ_CLASS_JUNCTION 2
+#define UMI_READ_CLASS_SPANNING 3
+#define UMI_READ_CLASS_INTRONIC 4
+int umi_assign_genes_classes_device(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end,
+                                    const uint8_t *exon_strand, const int32_t *exon_gene, uint64_t n_exons, uint32_t n_genes,
+                                    int strand_mode, int intron_mode, const int32_t *d_read_ref, const int32_t *d_read_pos,
+                                    const uint8_t *d_read_reverse, const uint32_t *d_cigar, const uint64_t *d_cigar_off,
+                                    uint64_t n_reads, int32_t *d_gene, uint8_t *d_status, uint8_t *d_tier, uint8_t *d_cls,
+                                    uint64_t counts[4], uint64_t class_counts[5], void *hip_stream);
+int umi_assign_genes_classes(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end,
+                             const uint8_t *exon_strand, const int32_t *exon_gene, uint64_t n_exons, uint32_t n_genes,
+                             int strand_mode, int intron_mode, const int32_t *read_ref, const int32_t *read_pos,
+                             const uint8_t *read_reverse, const uint32_t *cigar, const uint64_t *cigar_off, uint64_t n_reads,
+                             int32_t *gene, uint8_t *status, uint8_t *tier, uint8_t *cls, uint64_t counts[4],
+                             uint64_t class_counts[5]);
 
 /* ---- molecules and reads per (column, row) pair (the program's --count-matrix): what a batched call kept,
  *      summed over its buckets into the triplets of a sparse matrix, on the GPU.  No counterpart in the
@@ -632,6 +674,38 @@ int umi_count_matrix_device(umi_ctx *ctx, const uint8_t *d_kept, const int32_t *
 int umi_count_matrix(umi_ctx *ctx, const uint8_t *kept, const int32_t *freq, const uint64_t *bucket_off,
                      uint64_t n_buckets, const uint32_t *row, const uint32_t *col, uint32_t n_rows, uint32_t n_cols,
                      uint32_t *out_row, uint32_t *out_col, uint32_t *out_molecules, uint64_t *out_reads, uint64_t *nnz);
+
+/* ---- spliced, unspliced and ambiguous molecules per (column, row) pair (the program's --velocity): the classes of
+ *      the reads carried to their molecules, and the molecules counted in three layers, on the GPU.
+ *      tests/velocity_model.py defines it.  A molecule is a kept entry r (kept[r] != 0); its reads are the reads i
+ *      with read_entry[i] != UMI_READ_UNSTAGED and root[read_entry[i]] == r.  s: one of them is
+ *      UMI_READ_CLASS_JUNCTION; u: one of them is UMI_READ_CLASS_SPANNING or UMI_READ_CLASS_INTRONIC.  s and not u:
+ *      spliced.  u and not s: unspliced.  Otherwise (both, or neither -- EXONIC reads alone, or no read at all):
+ *      ambiguous.  An entry with kept == 0 counts nowhere.
+ * in : read_entry uint32 [n_reads]: the entry a read was staged into, UMI_READ_UNSTAGED: none, the read is skipped;
+ *      read_class uint8 [n_reads]: umi_assign_genes_classes' cls; kept uint8 [N] and root uint32 [N] of a batched
+ *      call (N = bucket_off[n_buckets]); bucket_off (a HOST array in both forms), row, col, n_rows, n_cols as
+ *      umi_count_matrix takes them.
+ * out: the triplets of umi_count_matrix for the same kept, bucket_off, row and col, in the same order: out_row,
+ *      out_col, and out_spliced, out_unspliced, out_ambiguous (uint32), whose sum is that call's molecules for every
+ *      triplet; *nnz their number.  The five arrays have room for n_buckets triplets.
+ * n_buckets == 0 or every bucket empty: UMI_OK, *nnz = 0, nothing launched.  n_reads == 0 is legal: every molecule is
+ * ambiguous.  A multi-device context uses its first device; a deferred call that is out ends first.
+ * UMI_ERR_ARG: umi_count_matrix's own (NULL pointers, n_buckets >= 2^30, bucket_off, n_rows, n_cols, a row or col
+ * out of range), n_reads >= 2^32, and, found on the device and told after the call's one synchronisation with *nnz
+ * 0 and the outputs not defined, the smallest read named: a read_entry >= N other than UMI_READ_UNSTAGED, a
+ * read_class above 4, a root[read_entry[i]] >= N. */
+#define UMI_READ_UNSTAGED 0xFFFFFFFFu
+int umi_velocity_matrix_device(umi_ctx *ctx, const uint32_t *d_read_entry, const uint8_t *d_read_class, uint64_t n_reads,
+                               const uint8_t *d_kept, const uint32_t *d_root, const uint64_t *bucket_off, uint64_t n_buckets,
+                               const uint32_t *d_row, const uint32_t *d_col, uint32_t n_rows, uint32_t n_cols,
+                               uint32_t *d_out_row, uint32_t *d_out_col, uint32_t *d_out_spliced, uint32_t *d_out_unspliced,
+                               uint32_t *d_out_ambiguous, uint64_t *nnz, void *hip_stream);
+int umi_velocity_matrix(umi_ctx *ctx, const uint32_t *read_entry, const uint8_t *read_class, uint64_t n_reads,
+                        const uint8_t *kept, const uint32_t *root, const uint64_t *bucket_off, uint64_t n_buckets,
+                        const uint32_t *row, const uint32_t *col, uint32_t n_rows, uint32_t n_cols, uint32_t *out_row,
+                        uint32_t *out_col, uint32_t *out_spliced, uint32_t *out_unspliced, uint32_t *out_ambiguous,
+                        uint64_t *nnz);
 
 /* ---- UMIs a group shows in several buckets (the program's --umi-filtering multi-gene): the molecules of a batched
  *      call joined across its buckets, on the GPU.  A UMI that one cell shows under two or more genes is a chimera

@@ -16,6 +16,9 @@ UMI_GENE_ASSIGNED, UMI_GENE_NONE, UMI_GENE_SEVERAL = 0, 1, 2             # the s
 UMI_STRAND_FORWARD, UMI_STRAND_REVERSE, UMI_STRAND_UNSTRANDED = 0, 1, 2  # ... and its strand modes
 UMI_INTRONS_OFF, UMI_INTRONS_EXON_FIRST, UMI_INTRONS_ALL = 0, 1, 2       # the modes of umi_assign_genes_introns
 UMI_GENE_TIER_EXON, UMI_GENE_TIER_INTRON = 0, 1                          # ... and its tiers
+(UMI_READ_CLASS_NONE, UMI_READ_CLASS_EXONIC, UMI_READ_CLASS_JUNCTION, UMI_READ_CLASS_SPANNING,
+ UMI_READ_CLASS_INTRONIC) = 0, 1, 2, 3, 4                                # the classes of umi_assign_genes_classes
+UMI_READ_UNSTAGED = 0xFFFFFFFF                                           # umi_velocity_matrix: a read no entry holds
 UMI_MAX_UMI_LEN = 21
 UMI_KERNEL_EDIT_PAIRS = 4     # Stats.kernel_id of umi_dedup_batch_edit (with "profile")
 UMI_MAX_CONS_LEN = 1024       # umi_consensus_bam: bases of a cluster, at most
@@ -128,6 +131,18 @@ SIGNATURES = {
                                                   C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_void_p]),
     "umi_assign_genes_introns": (C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, _u8p, _i32p, C.c_uint64, C.c_uint32, C.c_int,
                                            C.c_int, _i32p, _i32p, _u8p, _u32p, _u64p, C.c_uint64, _i32p, _u8p, _u8p, _u64p]),
+    "umi_assign_genes_classes_device": (C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, _u8p, _i32p, C.c_uint64, C.c_uint32, C.c_int,
+                                                  C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p, _u64p,
+                                                  C.c_void_p]),
+    "umi_assign_genes_classes": (C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, _u8p, _i32p, C.c_uint64, C.c_uint32, C.c_int,
+                                           C.c_int, _i32p, _i32p, _u8p, _u32p, _u64p, C.c_uint64, _i32p, _u8p, _u8p, _u8p, _u64p,
+                                           _u64p]),
+    "umi_velocity_matrix_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, _u64p,
+                                             C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_void_p]),
+    "umi_velocity_matrix": (C.c_int, [C.c_void_p, _u32p, _u8p, C.c_uint64, _u8p, _u32p, _u64p, C.c_uint64, _u32p, _u32p,
+                                      C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _u32p, _u64p]),
     "umi_count_matrix_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_uint64, C.c_void_p, C.c_void_p,
                                           C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p,
                                           C.c_void_p]),

@@ -551,6 +551,92 @@ class Context:
                                                      d_tier or None, ptr(counts, C.c_uint64), stream or None))
         return counts
 
+    def assign_genes_classes(self, exons, n_genes, strand_mode, intron_mode, read_ref, read_pos, read_reverse, cigar, cigar_off):
+        """Reads assigned to genes with their introns, and the class of every assigned read (umi_assign_genes_classes;
+        the rule is in include/umihip.h): assign_genes_introns' arguments.  Returns its dict and, beside it, cls uint8
+        [n] (UMI_READ_CLASS_*: 0 none, 1 exonic, 2 junction, 3 spanning, 4 intronic) and class_counts uint64 [5]."""
+        ex = self._exon_arrays(exons)
+        read_ref = np.ascontiguousarray(read_ref, dtype=np.int32).reshape(-1)
+        read_pos = np.ascontiguousarray(read_pos, dtype=np.int32).reshape(-1)
+        read_reverse = np.ascontiguousarray(read_reverse, dtype=np.uint8).reshape(-1)
+        cigar = np.ascontiguousarray(cigar, dtype=np.uint32).reshape(-1)
+        cigar_off = np.ascontiguousarray(cigar_off, dtype=np.uint64).reshape(-1)
+        n = len(read_ref)
+        if len(read_pos) != n or len(read_reverse) != n or len(cigar_off) != n + 1:
+            raise ValueError("the read arrays differ in length (cigar_off has one entry more)")
+        if int(cigar_off[-1]) > len(cigar):
+            raise ValueError("cigar_off ends beyond cigar")
+        m = max(1, n)
+        gene, status, tier, cls = np.zeros(m, np.int32), np.zeros(m, np.uint8), np.zeros(m, np.uint8), np.zeros(m, np.uint8)
+        counts, class_counts = np.zeros(4, np.uint64), np.zeros(5, np.uint64)
+        check(load().umi_assign_genes_classes(self._h, ptr(ex[0], C.c_int32), ptr(ex[1], C.c_int32), ptr(ex[2], C.c_int32),
+                                              ptr(ex[3], C.c_uint8), ptr(ex[4], C.c_int32), len(ex[0]), n_genes, strand_mode,
+                                              intron_mode, ptr(read_ref, C.c_int32), ptr(read_pos, C.c_int32),
+                                              ptr(read_reverse, C.c_uint8), ptr(cigar, C.c_uint32), ptr(cigar_off, C.c_uint64),
+                                              n, ptr(gene, C.c_int32), ptr(status, C.c_uint8), ptr(tier, C.c_uint8),
+                                              ptr(cls, C.c_uint8), ptr(counts, C.c_uint64), ptr(class_counts, C.c_uint64)))
+        return {"gene": gene[:n], "status": status[:n], "tier": tier[:n], "cls": cls[:n], "counts": counts,
+                "class_counts": class_counts}
+
+    def assign_genes_classes_device(self, exons, n_genes, strand_mode, intron_mode, d_read_ref, d_read_pos, d_read_reverse,
+                                    d_cigar, d_cigar_off, n_reads, d_gene, d_status, d_tier, d_cls, stream=0):
+        """The same on raw device pointers (umi_assign_genes_classes_device; the exons stay on the host): fills d_gene
+        (int32 [n_reads]), d_status, d_tier and d_cls (uint8 [n_reads]); returns (counts uint64 [4], class_counts
+        uint64 [5])."""
+        ex = self._exon_arrays(exons)
+        counts, class_counts = np.zeros(4, np.uint64), np.zeros(5, np.uint64)
+        check(load().umi_assign_genes_classes_device(self._h, ptr(ex[0], C.c_int32), ptr(ex[1], C.c_int32),
+                                                     ptr(ex[2], C.c_int32), ptr(ex[3], C.c_uint8), ptr(ex[4], C.c_int32),
+                                                     len(ex[0]), n_genes, strand_mode, intron_mode, d_read_ref or None,
+                                                     d_read_pos or None, d_read_reverse or None, d_cigar or None,
+                                                     d_cigar_off or None, n_reads, d_gene or None, d_status or None,
+                                                     d_tier or None, d_cls or None, ptr(counts, C.c_uint64),
+                                                     ptr(class_counts, C.c_uint64), stream or None))
+        return counts, class_counts
+
+    def velocity_matrix(self, read_entry, read_class, kept, root, bucket_off, row, col, n_rows, n_cols):
+        """Spliced, unspliced and ambiguous molecules per (column, row) pair (umi_velocity_matrix): read_entry uint32
+        [n_reads] (UMI_READ_UNSTAGED: the read is skipped) and read_class uint8 [n_reads] (assign_genes_classes' cls),
+        kept uint8 [N] and root uint32 [N] of a batched call, the buckets as count_matrix takes them.  Returns
+        (out_row, out_col, spliced, unspliced, ambiguous), uint32, count_matrix's triplets in its order."""
+        read_entry = np.ascontiguousarray(read_entry, dtype=np.uint32).reshape(-1)
+        read_class = np.ascontiguousarray(read_class, dtype=np.uint8).reshape(-1)
+        kept = np.ascontiguousarray(kept, dtype=np.uint8)
+        root = np.ascontiguousarray(root, dtype=np.uint32)
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        row = np.ascontiguousarray(row, dtype=np.uint32)
+        col = np.ascontiguousarray(col, dtype=np.uint32)
+        nb = len(bucket_off) - 1
+        if nb < 0 or len(row) != nb or len(col) != nb:
+            raise ValueError("row / col want one element per bucket")
+        if len(read_entry) != len(read_class):
+            raise ValueError("read_entry / read_class lengths differ")
+        if len(kept) != len(root) or (nb and int(bucket_off.max()) > len(kept)):
+            raise ValueError("kept / root lengths differ, or bucket_off runs past them")
+        m = max(1, nb)
+        o_row, o_col, o_s, o_u, o_a = (np.zeros(m, np.uint32) for _ in range(5))
+        nnz = C.c_uint64(0)
+        check(load().umi_velocity_matrix(self._h, ptr(read_entry, C.c_uint32), ptr(read_class, C.c_uint8), len(read_entry),
+                                         ptr(kept, C.c_uint8), ptr(root, C.c_uint32), ptr(bucket_off, C.c_uint64), nb,
+                                         ptr(row, C.c_uint32), ptr(col, C.c_uint32), n_rows, n_cols, ptr(o_row, C.c_uint32),
+                                         ptr(o_col, C.c_uint32), ptr(o_s, C.c_uint32), ptr(o_u, C.c_uint32),
+                                         ptr(o_a, C.c_uint32), C.byref(nnz)))
+        z = int(nnz.value)
+        return o_row[:z], o_col[:z], o_s[:z], o_u[:z], o_a[:z]
+
+    def velocity_matrix_device(self, d_read_entry, d_read_class, n_reads, d_kept, d_root, bucket_off, d_row, d_col, n_rows,
+                               n_cols, d_out_row, d_out_col, d_out_spliced, d_out_unspliced, d_out_ambiguous, stream=0):
+        """The same on raw device pointers (umi_velocity_matrix_device; bucket_off stays on the host): fills the five
+        output arrays (room for n_buckets elements each) and returns nnz."""
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        nnz = C.c_uint64(0)
+        check(load().umi_velocity_matrix_device(self._h, d_read_entry or None, d_read_class or None, n_reads, d_kept or None,
+                                                d_root or None, ptr(bucket_off, C.c_uint64), len(bucket_off) - 1,
+                                                d_row or None, d_col or None, n_rows, n_cols, d_out_row or None,
+                                                d_out_col or None, d_out_spliced or None, d_out_unspliced or None,
+                                                d_out_ambiguous or None, C.byref(nnz), stream or None))
+        return int(nnz.value)
+
     def count_matrix(self, kept, freq, bucket_off, row, col, n_rows, n_cols):
         """Molecules and reads per (column, row) pair (umi_count_matrix): kept uint8 [N] and freq int32 [N] of a
         batched call, bucket_off uint64 [n_buckets + 1], row / col uint32 [n_buckets] the row (gene) and column

@@ -1,4 +1,4 @@
-// Tables over a call's result, and its filters: umi_count_matrix*, umi_filter_multigene*, umi_dedup_stats*, umi_call_cells*.
+// Tables over a call's result, and its filters: umi_count_matrix*, umi_velocity_matrix*, umi_filter_multigene*, umi_dedup_stats*, umi_call_cells*.
 #include "umihip_host.hpp"
 
 #include <algorithm>
@@ -123,6 +123,127 @@ int umi_count_matrix(umi_ctx *ctx, const uint8_t *kept, const int32_t *freq, con
         (rc = io.fetch(out_row, d_orow, (size_t)got)) || (rc = io.fetch(out_col, d_ocol, (size_t)got)) ||
         (rc = io.fetch(out_molecules, d_omol, (size_t)got)) || (rc = io.fetch(out_reads, d_oreads, (size_t)got)) ||
         (rc = io.close()))
+        return rc;
+    *nnz = got;
+    return UMI_OK;
+}
+
+} // extern "C"
+
+// ---- spliced, unspliced and ambiguous molecules per (column, row) pair --------------------------------
+namespace {
+// what both forms check before a device is looked at (the context last)
+int vm_check(umi_ctx *ctx, const void *read_entry, const void *read_class, uint64_t n_reads, const void *kept, const void *root,
+             const uint64_t *bucket_off, uint64_t n_buckets, const void *row, const void *col, const void *out_row, const void *out_col,
+             const void *out_spliced, const void *out_unspliced, const void *out_ambiguous, const uint64_t *nnz)
+{
+    if (!nnz) return fail(UMI_ERR_ARG, "nnz is NULL");
+    if (n_buckets >= (1ull << 30))
+        return fail(UMI_ERR_ARG, "%llu buckets exceed the 30-bit index space of one call", (unsigned long long)n_buckets);
+    if (n_reads >= (1ull << 32)) return fail(UMI_ERR_ARG, "%llu reads exceed the 32-bit index space of one call", (unsigned long long)n_reads);
+    if (n_buckets && !bucket_off) return fail(UMI_ERR_ARG, "bucket_off is NULL");
+    if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
+    if (n_buckets && (!row || !col || !out_row || !out_col || !out_spliced || !out_unspliced || !out_ambiguous))
+        return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (n_buckets && bucket_off[n_buckets] && (!kept || !root)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (n_buckets && bucket_off[n_buckets] && n_reads && (!read_entry || !read_class)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (n_buckets && bucket_off[n_buckets] >= (1ull << 32))
+        return fail(UMI_ERR_ARG, "%llu entries exceed the 32-bit index space of root", (unsigned long long)bucket_off[n_buckets]);
+    if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
+    return UMI_OK;
+}
+
+int vm_run(umi_ctx *ctx, const uint32_t *d_read_entry, const uint8_t *d_read_class, uint64_t n_reads, const uint8_t *d_kept,
+           const uint32_t *d_root, uint64_t n, uint32_t m, const uint64_t *h_off, const uint32_t *h_idx, const uint32_t *d_row,
+           const uint32_t *d_col, uint32_t n_rows, uint32_t n_cols, uint32_t *d_out_row, uint32_t *d_out_col, uint32_t *d_out_spliced,
+           uint32_t *d_out_unspliced, uint32_t *d_out_ambiguous, uint64_t *nnz, hipStream_t s)
+{
+    int rc;
+    if ((rc = ctx->call_ws.reserve(velocity_workspace_bytes(n, m, h_idx != nullptr)))) return rc;
+    uint64_t bad = 0, bad_read = 0;
+    int kind = 0;
+    const int r = velocity_matrix_on_device(ctx->call_ws.p, d_read_entry, d_read_class, (uint32_t)n_reads, d_kept, d_root, n, h_off,
+                                            h_idx, m, d_row, d_col, n_rows, n_cols, d_out_row, d_out_col, d_out_spliced,
+                                            d_out_unspliced, d_out_ambiguous, ctx->velocity_skip, nnz, &bad, &kind, &bad_read,
+                                            (uint32_t)ctx->n_cus, ctx->h_counters, s);
+    if (r < 0) return fail(UMI_ERR_HIP, "velocity matrix: %s", hipGetErrorString((hipError_t)(-r)));
+    if (bad || kind) *nnz = 0;
+    if (bad)
+        return fail(UMI_ERR_ARG, "%llu non-empty buckets have a row id of %u or more, or a column id of %u or more",
+                    (unsigned long long)bad, n_rows, n_cols);
+    if (kind == 1)
+        return fail(UMI_ERR_ARG, "read %llu: its read_entry is neither below the %llu entries nor UMI_READ_UNSTAGED",
+                    (unsigned long long)bad_read, (unsigned long long)n);
+    if (kind == 2) return fail(UMI_ERR_ARG, "read %llu: a read_class above 4", (unsigned long long)bad_read);
+    if (kind == 3)
+        return fail(UMI_ERR_ARG, "read %llu: the root of its entry is not below the %llu entries", (unsigned long long)bad_read,
+                    (unsigned long long)n);
+    return UMI_OK;
+}
+} // namespace
+
+extern "C" {
+
+int umi_velocity_matrix_device(umi_ctx *ctx, const uint32_t *d_read_entry, const uint8_t *d_read_class, uint64_t n_reads,
+                               const uint8_t *d_kept, const uint32_t *d_root, const uint64_t *bucket_off, uint64_t n_buckets,
+                               const uint32_t *d_row, const uint32_t *d_col, uint32_t n_rows, uint32_t n_cols,
+                               uint32_t *d_out_row, uint32_t *d_out_col, uint32_t *d_out_spliced, uint32_t *d_out_unspliced,
+                               uint32_t *d_out_ambiguous, uint64_t *nnz, void *hip_stream)
+{
+    int rc = vm_check(ctx, d_read_entry, d_read_class, n_reads, d_kept, d_root, bucket_off, n_buckets, d_row, d_col, d_out_row,
+                      d_out_col, d_out_spliced, d_out_unspliced, d_out_ambiguous, nnz);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_count_matrix)
+    *nnz = 0;
+    if (n_buckets == 0) return UMI_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
+    uint32_t m = 0;
+    const uint64_t *h_off = nullptr;
+    const uint32_t *h_idx = nullptr;
+    if ((rc = cm_walk(ctx, bucket_off, n_buckets, &m, &h_off, &h_idx))) return rc;
+    if (m == 0) return UMI_OK;
+    if (n_rows == 0 || n_cols == 0) return fail(UMI_ERR_ARG, "a matrix of %u rows and %u columns with a non-empty bucket", n_rows, n_cols);
+    return vm_run(ctx, d_read_entry, d_read_class, n_reads, d_kept, d_root, bucket_off[n_buckets], m, h_off, h_idx, d_row, d_col,
+                  n_rows, n_cols, d_out_row, d_out_col, d_out_spliced, d_out_unspliced, d_out_ambiguous, nnz, (hipStream_t)hip_stream);
+}
+
+int umi_velocity_matrix(umi_ctx *ctx, const uint32_t *read_entry, const uint8_t *read_class, uint64_t n_reads,
+                        const uint8_t *kept, const uint32_t *root, const uint64_t *bucket_off, uint64_t n_buckets,
+                        const uint32_t *row, const uint32_t *col, uint32_t n_rows, uint32_t n_cols, uint32_t *out_row,
+                        uint32_t *out_col, uint32_t *out_spliced, uint32_t *out_unspliced, uint32_t *out_ambiguous,
+                        uint64_t *nnz)
+{
+    int rc = vm_check(ctx, read_entry, read_class, n_reads, kept, root, bucket_off, n_buckets, row, col, out_row, out_col, out_spliced,
+                      out_unspliced, out_ambiguous, nnz);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    *nnz = 0;
+    if (n_buckets == 0) return UMI_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx);
+    uint32_t m = 0;
+    const uint64_t *h_off = nullptr;
+    const uint32_t *h_idx = nullptr;
+    if ((rc = cm_walk(ctx, bucket_off, n_buckets, &m, &h_off, &h_idx))) return rc;
+    if (m == 0) return UMI_OK;
+    if (n_rows == 0 || n_cols == 0) return fail(UMI_ERR_ARG, "a matrix of %u rows and %u columns with a non-empty bucket", n_rows, n_cols);
+    const size_t n = (size_t)bucket_off[n_buckets], nb = (size_t)n_buckets, cap = (size_t)m, nr = (size_t)n_reads;
+    HostIo io(ctx);
+    const auto d_entry = io.in(read_entry, nr * 4);
+    const auto d_root = io.in(root, n * 4);
+    const auto d_row = io.in(row, nb * 4), d_col = io.in(col, nb * 4);
+    const auto d_orow = io.out(out_row, cap * 4), d_ocol = io.out(out_col, cap * 4);
+    const auto d_os = io.out(out_spliced, cap * 4), d_ou = io.out(out_unspliced, cap * 4), d_oa = io.out(out_ambiguous, cap * 4);
+    const auto d_class = io.in(read_class, nr);
+    const auto d_kept = io.in(kept, n);
+    uint64_t got = 0;
+    if ((rc = io.open()) ||
+        (rc = vm_run(ctx, d_entry, d_class, n_reads, d_kept, d_root, n, m, h_off, h_idx, d_row, d_col, n_rows, n_cols, d_orow, d_ocol,
+                     d_os, d_ou, d_oa, &got, io.stream())) ||
+        (rc = io.fetch(out_row, d_orow, (size_t)got)) || (rc = io.fetch(out_col, d_ocol, (size_t)got)) ||
+        (rc = io.fetch(out_spliced, d_os, (size_t)got)) || (rc = io.fetch(out_unspliced, d_ou, (size_t)got)) ||
+        (rc = io.fetch(out_ambiguous, d_oa, (size_t)got)) || (rc = io.close()))
         return rc;
     *nnz = got;
     return UMI_OK;

@@ -23,6 +23,7 @@
 // enough for LDS.  A search over the top names the chunk, a search over the chunk's ends the segment.
 //
 // Gene bodies (umi_assign_genes_introns, --gene-introns) are a second tier of the same tables: the end of this file.
+// Behind them: the covered bases of an interval and the class of a read (umi_assign_genes_classes, --velocity).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -291,6 +292,159 @@ UMIHIP_HD inline int gene_assign_read_tiers(const GeneView &exons, const GeneTop
     st = gene_assign_read(bodies, body_top, ref, pos, cigar, n_cigar, gene);
     if (st == GENE_READ_ASSIGNED && !by_exon) *tier = GENE_TIER_INTRON;
     return st;
+}
+
+// ---- covered bases and the class of a read (umi_assign_genes_classes, the program's --velocity) ----
+// cover of [s, e): the positions of it that lie in a kept segment of a table.  Beside the table travels a prefix array,
+// cum[i] = the summed lengths of segments 0 .. i-1 (n + 1 words): cover = cum[hi + 1] - cum[lo] less what the block
+// leaves of segment lo in front of s and of segment hi behind e; lo and hi are gene_query's.  The table, its view and
+// its top are as they were: the array is built and uploaded only by the call that wants classes.
+//
+// The blocks of a read assigned to gene g by an exon touch only segments that carry g's label (otherwise E would be
+// several), so the table's cover of a block is g's.  The stretch an N skipped is another matter: a nested gene's exon
+// may lie in g's intron, and the table's cover of a gap is then an upper bound of g's.  A gap the table covers whole
+// is therefore looked up once more, in g's own exons: GeneOwn holds, per gene, the union of its lines of the table's
+// strand class as disjoint, non-touching intervals in key order (own_off[g] .. own_off[g + 1]); the gap is g's where
+// the interval that holds its first base reaches its end.
+constexpr int GENE_CLASS_NONE = 0, GENE_CLASS_EXONIC = 1, GENE_CLASS_JUNCTION = 2, GENE_CLASS_SPANNING = 3,
+              GENE_CLASS_INTRONIC = 4; // UMI_READ_CLASS_*
+
+inline void gene_cover_prefix(const GeneTable &t, std::vector<uint64_t> &cum)
+{
+    const size_t n = t.end.size();
+    cum.assign(n + 1, 0);
+    for (size_t i = 0; i < n; i++) cum[i + 1] = cum[i] + (t.end[i] - t.start[i]); // (a segment lies on one reference)
+}
+
+// hi: the last segment that starts before key ke, from lo on (start[lo] < ke), found as gene_query finds it
+UMIHIP_HD inline uint32_t gene_last_segment(const GeneView &t, uint32_t lo, uint64_t ke)
+{
+    uint32_t a = lo, step = 1;
+    while (a + step < t.n && t.start[a + step] < ke) {
+        a += step;
+        step <<= 1;
+    }
+    uint32_t b = a + step < t.n ? a + step : t.n;
+    while (b - a > 1) {
+        const uint32_t m = a + (b - a) / 2;
+        if (t.start[m] < ke)
+            a = m;
+        else
+            b = m;
+    }
+    return a;
+}
+
+// the covered bases of [s, e) on reference ref, e > s, 0 <= s, e <= GENE_POS_LIMIT
+UMIHIP_HD inline uint64_t gene_cover(const GeneView &t, const GeneTop *top, const uint64_t *cum, uint32_t ref, uint64_t s, uint64_t e)
+{
+    const uint64_t ks = gene_key(ref, s), ke = gene_key(ref, e);
+    const uint32_t lo = gene_first_segment(t, top, ks);
+    if (lo >= t.n || t.start[lo] >= ke) return 0;
+    const uint32_t hi = gene_last_segment(t, lo, ke);
+    uint64_t c = cum[hi + 1] - cum[lo]; // (segments lo .. hi end behind ks and start before ke: all on ref)
+    const uint64_t first = t.start[lo], last = t.end[hi];
+    if (first < ks) c -= ks - first;
+    if (last > ke) c -= last - ke;
+    return c;
+}
+
+struct GeneOwn {
+    std::vector<uint64_t> start, end; // keys, as the table's
+    std::vector<uint32_t> off;        // [n_genes + 1]
+};
+
+struct GeneOwnView {
+    const uint64_t *start, *end;
+    const uint32_t *off;
+};
+
+// The checked exons (gene_index_build's) whose strand is in `take`, united per gene.
+inline void gene_own_build(const int32_t *ref, const int32_t *start, const int32_t *end, const uint8_t *strand, const int32_t *gene,
+                           uint64_t n_exons, uint32_t n_genes, unsigned take, GeneOwn &o)
+{
+    struct Line {
+        int32_t gene;
+        uint64_t ks, ke;
+    };
+    std::vector<Line> lines;
+    lines.reserve(n_exons);
+    for (uint64_t i = 0; i < n_exons; i++) {
+        const unsigned bit = strand[i] == '+' ? GENE_TAKE_PLUS : strand[i] == '-' ? GENE_TAKE_MINUS : GENE_TAKE_DOT;
+        if (take & bit) lines.push_back({gene[i], gene_key((uint32_t)ref[i], (uint64_t)start[i]), gene_key((uint32_t)ref[i], (uint64_t)end[i])});
+    }
+    std::sort(lines.begin(), lines.end(), [](const Line &a, const Line &b) { return a.gene != b.gene ? a.gene < b.gene : a.ks < b.ks; });
+    o.start.clear();
+    o.end.clear();
+    o.off.assign((size_t)n_genes + 1, 0);
+    int32_t g = -1;
+    for (const Line &l : lines) {
+        // (an end never reaches the next reference's keys: lines that touch lie on one reference)
+        if (l.gene == g && l.ks <= o.end.back()) {
+            o.end.back() = std::max(o.end.back(), l.ke);
+            continue;
+        }
+        g = l.gene;
+        o.start.push_back(l.ks);
+        o.end.push_back(l.ke);
+        o.off[(size_t)g + 1]++;
+    }
+    for (size_t i = 0; i < n_genes; i++) o.off[i + 1] += o.off[i];
+}
+
+// what travels beside an exon table for the classes: its prefix array and its genes' own exons
+struct GeneCover {
+    std::vector<uint64_t> cum;
+    GeneOwn own;
+};
+
+inline GeneOwnView gene_own_view(const GeneOwn &o) { return {o.start.data(), o.end.data(), o.off.data()}; }
+
+// does every base of [s, e), e > s, lie in an exon of gene g
+UMIHIP_HD inline bool gene_own_covers(const GeneOwnView &o, int32_t g, uint32_t ref, uint64_t s, uint64_t e)
+{
+    const uint32_t a = o.off[g], b = o.off[g + 1];
+    const uint32_t i = gene_first_above(o.start, a, b, gene_key(ref, s)); // the first interval that starts behind s
+    return i > a && o.end[i - 1] >= gene_key(ref, e);
+}
+
+// The class of a read that is assigned to gene g with tier exon (its CIGAR has passed gene_assign_read: no bad op
+// code).  The blocks are gene_assign_read's, cut to [0, GENE_POS_LIMIT), the empty ones left out; a gap is the stretch
+// between one block's end and the next one's start.  A block not covered whole: SPANNING.  Otherwise a gap not covered
+// whole by g: JUNCTION.  Otherwise EXONIC.  The gaps are walked only where every block is covered and there are two.
+UMIHIP_HD inline int gene_read_class(const GeneView &t, const GeneTop *top, const uint64_t *cum, const GeneOwnView &own, int32_t g,
+                                     uint32_t ref, int64_t pos, const uint32_t *cigar, uint64_t n_cigar)
+{
+    for (int walk = 0; walk < 2; walk++) {
+        int64_t s = pos, e = pos, prev_end = -1;
+        uint32_t blocks = 0;
+        for (uint64_t c = 0; c <= n_cigar; c++) {
+            uint32_t op = 3, len = 0;
+            if (c < n_cigar) {
+                op = cigar[c] & 15u;
+                len = cigar[c] >> 4;
+            }
+            if (op == 0 || op == 2 || op == 7 || op == 8) {
+                e += len;
+                continue;
+            }
+            if (op != 3) continue;
+            const int64_t bs = s < 0 ? 0 : s, be = e > GENE_POS_LIMIT ? GENE_POS_LIMIT : e;
+            if (be > bs) {
+                blocks++;
+                if (walk == 0) {
+                    if (gene_cover(t, top, cum, ref, (uint64_t)bs, (uint64_t)be) < (uint64_t)(be - bs)) return GENE_CLASS_SPANNING;
+                } else if (prev_end >= 0 && bs > prev_end) {
+                    const uint64_t gs = (uint64_t)prev_end, ge = (uint64_t)bs;
+                    if (gene_cover(t, top, cum, ref, gs, ge) < ge - gs || !gene_own_covers(own, g, ref, gs, ge)) return GENE_CLASS_JUNCTION;
+                }
+                prev_end = be;
+            }
+            s = e = e + len;
+        }
+        if (blocks < 2) break;
+    }
+    return GENE_CLASS_EXONIC;
 }
 
 } // namespace umihip

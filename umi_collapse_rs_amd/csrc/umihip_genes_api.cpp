@@ -245,3 +245,123 @@ int umi_assign_genes_introns(umi_ctx *ctx, const int32_t *exon_ref, const int32_
 }
 
 } // extern "C"
+
+// ---- umi_assign_genes_classes*: umi_assign_genes_introns' checks and index, and beside every exon table its prefix
+// ---- array of covered bases and its genes' own exons; the kernel is umihip_gene_classes.hip's
+
+namespace {
+
+struct ClassIndex {
+    IntronIndex tiers;
+    GeneCover cover[2];
+};
+
+int classes_check(const void *cls, const uint64_t *class_counts, uint64_t n_reads)
+{
+    if (!class_counts) return fail(UMI_ERR_ARG, "class_counts is NULL");
+    if (n_reads && !cls) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    return UMI_OK;
+}
+
+void classes_index(const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end, const uint8_t *exon_strand,
+                   const int32_t *exon_gene, uint64_t n_exons, uint32_t n_genes, int strand_mode, int intron_mode, ClassIndex &ix)
+{
+    introns_index(exon_ref, exon_start, exon_end, exon_strand, exon_gene, n_exons, n_genes, strand_mode, intron_mode, ix.tiers);
+    const int n_tables = ix.tiers.exons.n_tables;
+    const unsigned take[2] = {n_tables == 1 ? GENE_TAKE_PLUS | GENE_TAKE_MINUS | GENE_TAKE_DOT : GENE_TAKE_PLUS | GENE_TAKE_DOT,
+                              GENE_TAKE_MINUS | GENE_TAKE_DOT};
+    for (int t = 0; t < n_tables; t++) {
+        gene_cover_prefix(ix.tiers.exons.tables[t], ix.cover[t].cum);
+        gene_own_build(exon_ref, exon_start, exon_end, exon_strand, exon_gene, n_exons, n_genes, take[t], ix.cover[t].own);
+    }
+}
+
+int classes_run(umi_ctx *ctx, const ClassIndex &ix, int intron_mode, const int32_t *d_ref, const int32_t *d_pos,
+                const uint8_t *d_reverse, const uint32_t *d_cigar, const uint64_t *d_cigar_off, uint64_t n_reads, int32_t *d_gene,
+                uint8_t *d_status, uint8_t *d_tier, uint8_t *d_cls, uint64_t *counts, uint64_t *class_counts, hipStream_t s)
+{
+    int rc;
+    const GeneIndex &ex = ix.tiers.exons;
+    if ((rc = ctx->call_ws.reserve(gene_classes_workspace_bytes(ex.tables, ix.tiers.bodies, ix.cover, ex.n_tables)))) return rc;
+    uint64_t bad = 0;
+    const int r = gene_classes_on_device(ctx->call_ws.p, ex.tables, ix.tiers.bodies, ix.cover, ex.n_tables, ex.flip, intron_mode,
+                                         ctx->gene_top, ctx->gene_body_top, d_ref, d_pos, d_reverse, d_cigar, d_cigar_off,
+                                         (uint32_t)n_reads, d_gene, d_status, d_tier, d_cls, counts, class_counts, &bad,
+                                         (uint32_t)ctx->n_cus, ctx->h_counters, s);
+    if (r == 1)
+        return fail(UMI_ERR_ARG, "read %llu: a negative reference, a CIGAR op code above 8, or CIGAR words without an array",
+                    (unsigned long long)bad);
+    if (r == 2) return fail(UMI_ERR_ORDER, "cigar_off falls at read %llu", (unsigned long long)bad);
+    if (r < 0) return fail(UMI_ERR_HIP, "gene assignment with classes: %s", hipGetErrorString((hipError_t)(-r)));
+    return UMI_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int umi_assign_genes_classes_device(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end,
+                                    const uint8_t *exon_strand, const int32_t *exon_gene, uint64_t n_exons, uint32_t n_genes,
+                                    int strand_mode, int intron_mode, const int32_t *d_read_ref, const int32_t *d_read_pos,
+                                    const uint8_t *d_read_reverse, const uint32_t *d_cigar, const uint64_t *d_cigar_off,
+                                    uint64_t n_reads, int32_t *d_gene, uint8_t *d_status, uint8_t *d_tier, uint8_t *d_cls,
+                                    uint64_t counts[4], uint64_t class_counts[5], void *hip_stream)
+{
+    int rc = classes_check(d_cls, class_counts, n_reads);
+    if (rc) return rc;
+    if ((rc = introns_check(intron_mode, d_tier, n_reads))) return rc;
+    rc = genes_check(ctx, exon_ref, exon_start, exon_end, exon_strand, exon_gene, n_exons, n_genes, strand_mode, d_read_ref, d_read_pos,
+                     d_read_reverse, d_cigar_off, n_reads, d_gene, d_status, counts);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    for (int c = 0; c < 5; c++) class_counts[c] = 0;
+    if (n_reads == 0) return UMI_OK;
+    ClassIndex ix;
+    classes_index(exon_ref, exon_start, exon_end, exon_strand, exon_gene, n_exons, n_genes, strand_mode, intron_mode, ix);
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
+    return classes_run(ctx, ix, intron_mode, d_read_ref, d_read_pos, d_read_reverse, d_cigar, d_cigar_off, n_reads, d_gene, d_status,
+                       d_tier, d_cls, counts, class_counts, (hipStream_t)hip_stream);
+}
+
+int umi_assign_genes_classes(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end,
+                             const uint8_t *exon_strand, const int32_t *exon_gene, uint64_t n_exons, uint32_t n_genes,
+                             int strand_mode, int intron_mode, const int32_t *read_ref, const int32_t *read_pos,
+                             const uint8_t *read_reverse, const uint32_t *cigar, const uint64_t *cigar_off, uint64_t n_reads,
+                             int32_t *gene, uint8_t *status, uint8_t *tier, uint8_t *cls, uint64_t counts[4],
+                             uint64_t class_counts[5])
+{
+    int rc = classes_check(cls, class_counts, n_reads);
+    if (rc) return rc;
+    if ((rc = introns_check(intron_mode, tier, n_reads))) return rc;
+    rc = genes_check(ctx, exon_ref, exon_start, exon_end, exon_strand, exon_gene, n_exons, n_genes, strand_mode, read_ref, read_pos,
+                     read_reverse, cigar_off, n_reads, gene, status, counts);
+    if (rc) return rc;
+    if (n_reads && cigar_off[n_reads] && !cigar) return fail(UMI_ERR_ARG, "cigar is NULL");
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    for (int c = 0; c < 5; c++) class_counts[c] = 0;
+    if (n_reads == 0) return UMI_OK;
+    ClassIndex ix;
+    classes_index(exon_ref, exon_start, exon_end, exon_strand, exon_gene, n_exons, n_genes, strand_mode, intron_mode, ix);
+    const size_t n = (size_t)n_reads, words = (size_t)cigar_off[n_reads];
+    HostIo io(ctx);
+    const auto d_ref = io.in(read_ref, n * 4), d_pos = io.in(read_pos, n * 4);
+    const auto d_reverse = io.in(read_reverse, n);
+    const auto d_cigar = io.in(cigar, words * 4);
+    const auto d_off = io.in(cigar_off, (n + 1) * 8);
+    const auto d_gene = io.out(gene, n * 4);
+    const auto d_status = io.out(status, n);
+    const auto d_tier = io.out(tier, n);
+    const auto d_cls = io.out(cls, n);
+    if ((rc = io.open()) ||
+        (rc = classes_run(ctx, ix, intron_mode, d_ref, d_pos, d_reverse, d_cigar, d_off, n_reads, d_gene, d_status, d_tier, d_cls, counts,
+                          class_counts, io.stream())) ||
+        (rc = io.fetch(gene, d_gene, n)) || (rc = io.fetch(status, d_status, n)) || (rc = io.fetch(tier, d_tier, n)) ||
+        (rc = io.fetch(cls, d_cls, n)))
+        return rc;
+    return io.close();
+}
+
+} // extern "C"

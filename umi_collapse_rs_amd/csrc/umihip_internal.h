@@ -535,6 +535,17 @@ int gene_introns_on_device(void *workspace, const GeneTable *exons, const GeneTa
                            uint8_t *d_tier, uint64_t counts[4], uint64_t *bad, uint32_t n_cus, unsigned long long *h_pinned,
                            hipStream_t s);
 
+// ---- ... and the class of every assigned read (umihip_gene_classes.hip: umi_assign_genes_classes) ----
+// gene_introns_on_device's arguments; beside every exon table its GeneCover (umihip_gene_index.hpp: the prefix array
+// of covered bases and the genes' own exons), uploaded alike.  h_pinned: 9 pinned words.  class_counts: by UMI_READ_CLASS_*.
+struct GeneCover;
+size_t gene_classes_workspace_bytes(const GeneTable *exons, const GeneTable *bodies, const GeneCover *cover, int n_tables);
+int gene_classes_on_device(void *workspace, const GeneTable *exons, const GeneTable *bodies, const GeneCover *cover,
+                           int n_tables, bool flip, int mode, bool use_top, bool use_body_top, const int32_t *d_ref,
+                           const int32_t *d_pos, const uint8_t *d_reverse, const uint32_t *d_cigar, const uint64_t *d_cigar_off,
+                           uint32_t n_reads, int32_t *d_gene, uint8_t *d_status, uint8_t *d_tier, uint8_t *d_cls, uint64_t counts[4],
+                           uint64_t class_counts[5], uint64_t *bad, uint32_t n_cus, unsigned long long *h_pinned, hipStream_t s);
+
 // ---- molecules and reads per (column, row) pair (umihip_count.hip: umi_count_matrix) ----
 // h_off (pinned): the m + 1 offsets of the m >= 1 non-empty buckets; h_idx (pinned, null: nothing was left out):
 // their numbers in d_row / d_col.  The outputs take the triplets sorted by column, then row (capacity m);
@@ -546,6 +557,19 @@ int count_matrix_on_device(void *workspace, const uint8_t *d_kept, const int32_t
                            uint32_t n_cols, uint32_t *d_out_row, uint32_t *d_out_col, uint32_t *d_out_molecules,
                            uint64_t *d_out_reads, uint64_t *nnz, uint64_t *bad_ids, uint32_t n_cus, unsigned long long *h_pinned,
                            hipStream_t s);
+
+// ---- spliced, unspliced and ambiguous molecules per pair (umihip_velocity.hip: umi_velocity_matrix) ----
+// count_matrix_on_device's bucket arguments; n entries (the last offset).  *bad_ids as there; *bad_kind: 0 none, 1 a
+// read_entry out of range, 2 a read_class above 4, 3 a root out of range, of read *bad_read (the smallest read with
+// any of them).  skip_set: a lane loads the evidence word and leaves the atomic out where its bit is set.  One
+// synchronisation, at the end.  h_pinned: 5 pinned words.  0 ok; negative: -(hipError_t)
+size_t velocity_workspace_bytes(uint64_t n, uint32_t m, bool has_idx);
+int velocity_matrix_on_device(void *workspace, const uint32_t *d_read_entry, const uint8_t *d_read_class, uint32_t n_reads,
+                              const uint8_t *d_kept, const uint32_t *d_root, uint64_t n, const uint64_t *h_off, const uint32_t *h_idx,
+                              uint32_t m, const uint32_t *d_row, const uint32_t *d_col, uint32_t n_rows, uint32_t n_cols,
+                              uint32_t *d_out_row, uint32_t *d_out_col, uint32_t *d_out_spliced, uint32_t *d_out_unspliced,
+                              uint32_t *d_out_ambiguous, bool skip_set, uint64_t *nnz, uint64_t *bad_ids, int *bad_kind,
+                              uint64_t *bad_read, uint32_t n_cus, unsigned long long *h_pinned, hipStream_t s);
 
 // ---- family sizes, UMI distances and UMI usage of a batched call (umihip_stats.hip: umi_dedup_stats) ----
 constexpr uint32_t STATS_LANE_MAX = 8;    // a bucket of more entries is a wave's

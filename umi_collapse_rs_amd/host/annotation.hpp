@@ -52,8 +52,36 @@
 // references": "Gene introns: <mode>", "Number of reads assigned by an exon", "Number of reads assigned by an
 // intron" (over every mapped read the call saw).  Refused with status 101 before the GPU is woken: the flag without
 // --gene-annotation; a value other than off, exon-first, all; the flag given twice with different values.
-// Not built: STARsolo's Ex50pAS half-of-the-read rule, antisense counting, spliced / unspliced (velocity) matrices
-// (a read's tier would have to travel through staging), --paired.
+// Not built: STARsolo's Ex50pAS half-of-the-read rule, antisense counting, --paired.
+//
+// --velocity (with --gene-annotation, --gene-introns exon-first|all and --count-matrix DIR; tests/velocity_model.py
+// defines it): the matrix's molecules in three layers -- spliced, unspliced, ambiguous -- what STARsolo's --soloFeatures
+// Velocyto, velocyto and alevin-fry's USA mode give scVelo and its kin.  The rule is at gene level and in exact integers;
+// it is NOT velocyto's or STARsolo's transcript-model rule, for this program keeps no transcript models.  A read's
+// gene, status and tier are --gene-introns', unchanged.  The class of an assigned read with gene g: its blocks are cut
+// to [0, 2^31) and the empty ones left out; the cover of a stretch is the number of its bases in one of g's taken lines
+// on the read's reference and an admissible strand.  Assigned by an intron: intronic.  By an exon: where the blocks are
+// not covered whole, exon-intron (the read leaves the exons, into an intron or past the gene's end); else, where a
+// stretch that an N skipped between two blocks is not covered whole, junction (the read skips an intron); else exonic.
+// A molecule is a kept entry; its reads are the staged reads whose entry's root it is.  With a junction read and no
+// exon-intron or intronic read it is spliced; with an exon-intron or intronic read and no junction read, unspliced;
+// with both kinds, or with exonic reads alone (alevin-fry's A), ambiguous.  A molecule --umi-filtering multi-gene removed
+// counts nowhere.  The classes are relative to the lines taken: under --annotation-feature gene the lines are whole genes, no read
+// is intronic, and every assigned read that stays inside its gene is exonic; this is documented, not refused.
+// The one call over the reads is umi_assign_genes_classes in umi_assign_genes_introns' place (the same gene, status,
+// tier and counts, and a class per read); the flag stages on the host, as --tag does, because the host staging keeps
+// every read's entry; after umi_count_matrix one call to umi_velocity_matrix gives the layers of that matrix's
+// triplets.  Written: DIR/velocity/features.tsv and barcodes.tsv (the raw ones' bytes) and spliced.mtx, unspliced.mtx,
+// ambiguous.mtx, matrix.mtx's layout, each with its non-zero entries alone and its own line count in the header; the
+// three add up to matrix.mtx pair by pair.  With --cell-filter the same five files under DIR/velocity/filtered/ for the
+// called cells, columns renumbered as in DIR/filtered/; the cells are called from the total matrix, as without the flag.
+// The summary gains "Velocity: on", "Number of exonic reads", "Number of junction reads", "Number of exon-intron reads",
+// "Number of intronic reads" (over every mapped read the call saw) and "Number of spliced molecules", "Number of
+// unspliced molecules", "Number of ambiguous molecules" (together "Number of reads after deduplicating").  The BAM, the
+// four raw files, filtered/, cells.tsv and the other summary lines are what --stage host writes without the flag.
+// Refused with status 101 before the GPU is woken: --velocity without --count-matrix, without --gene-annotation, with
+// --gene-introns absent or off, with --stage gpu.  Not built: transcript-model rules (velocyto's or STARsolo's own), a
+// read's entry from the GPU staging, --two-pass, --paired.
 #pragma once
 #include <unordered_map>
 

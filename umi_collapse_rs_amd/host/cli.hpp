@@ -75,6 +75,12 @@
 // file's reader and every refusal; the flags and the file are looked at here, in validate(), before the GPU is woken).
 // --gene-introns off|exon-first|all (with --gene-annotation) [off]: reads in a gene's introns count too, by
 // umi_assign_genes_introns (annotation.hpp has the rule, the summary lines and the refusals).
+// --velocity (with --per-gene --gene-annotation FILE --gene-introns exon-first|all --count-matrix DIR; tests/velocity_model.py
+// defines it): the molecules of the matrix in three layers, spliced, unspliced and ambiguous, as STARsolo's --soloFeatures
+// Velocyto, velocyto and alevin-fry's USA mode write them -- but by a gene-level rule, not by their transcript models,
+// which this project does not keep (annotation.hpp has the rule, the files, the summary lines and what is not built).
+// Refused with status 101 before the GPU is woken: --velocity without --count-matrix, without --gene-annotation, with
+// --gene-introns absent or off, or with --stage gpu (a read's entry is kept by the host staging alone).
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -159,6 +165,7 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     std::string gene_introns = "off";
     bool gene_introns_given = false;
     int gene_introns_mode = UMI_INTRONS_OFF; // as UMI_INTRONS_* (filled in by validate())
+    bool velocity = false; // --velocity: spliced, unspliced and ambiguous matrices beside --count-matrix's
     struct Annotation { // the file's taken lines (filled in by validate(): read_annotation)
         std::vector<std::string> refs;      // the reference names of column 1, in order of first appearance
         std::vector<uint32_t> ref_name;     // per taken line: its reference, an index into refs
@@ -277,6 +284,11 @@ void usage()
               "                           read that hits no exon goes to the one gene whose body it shares a base with\n"
               "                           (STARsolo's GeneFull_ExonOverIntron, Cell Ranger 7's default); all: every read\n"
               "                           goes by the bodies alone (GeneFull); no body or several: dropped\n"
+              "      --velocity           with --gene-annotation, --gene-introns exon-first|all and --count-matrix: write the\n"
+              "                           matrix's molecules in three layers to DIR/velocity (spliced.mtx, unspliced.mtx,\n"
+              "                           ambiguous.mtx, features.tsv, barcodes.tsv) by a gene-level rule: a molecule with a\n"
+              "                           read that skips an intron is spliced, with a read in an intron or over an exon's\n"
+              "                           edge unspliced, with both or neither ambiguous (host staging; not with --stage gpu)\n"
               "      --count-matrix <DIR> with --per-gene: write the molecules per cell and gene to DIR (made if it is\n"
               "                           not there) as features.tsv, barcodes.tsv, matrix.mtx (molecules) and reads.mtx\n"
               "                           (reads), MatrixMarket coordinate files sorted by cell, then gene, counted on the GPU\n"
@@ -399,6 +411,7 @@ Cli parse(int argc, char **argv)
             c.gene_introns = v;
             c.gene_introns_given = true;
         }
+        else if (a == "--velocity") c.velocity = true;
         else if (a == "--count-matrix") c.count_matrix = need(i);
         else if (a == "--output-stats") c.output_stats = need(i);
         else if (a == "--output-stats-seed") {
@@ -632,6 +645,13 @@ bool validate(Cli &args)
         if (args.annotation_attribute.empty()) die("--annotation-attribute wants an attribute name");
         read_annotation(args);
     }
+    // --velocity: likewise (its directories are made last, behind --cell-filter's)
+    if (args.velocity) {
+        if (args.count_matrix.empty()) die("--velocity goes with --count-matrix DIR only");
+        if (!args.gene_annotation_given) die("--velocity goes with --gene-annotation only (a read's class comes from the file's exons)");
+        if (args.gene_introns_mode == UMI_INTRONS_OFF) die("--velocity goes with --gene-introns exon-first or all only");
+        if (args.stage == "gpu") die("--stage gpu does not go with --paired, --tag, --call-consensus, --velocity or --dump-staging");
+    }
     // --umi-filtering: likewise
     if (args.umi_filtering_given && args.umi_filtering != "none" && args.umi_filtering != "multi-gene")
         die("--umi-filtering wants none or multi-gene: '" + args.umi_filtering + "'");
@@ -727,6 +747,17 @@ bool validate(Cli &args)
             if (why != EEXIST || stat(dir.c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode))
                 die("cannot make the directory " + dir + " for --cell-filter: " + std::strerror(why));
         }
+    }
+    if (args.velocity) {
+        std::vector<std::string> dirs{args.count_matrix + "/velocity"};
+        if (args.cell_filter_given) dirs.push_back(args.count_matrix + "/velocity/filtered");
+        for (const std::string &dir : dirs)
+            if (mkdir(dir.c_str(), 0777) != 0) {
+                const int why = errno;
+                struct stat sb;
+                if (why != EEXIST || stat(dir.c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode))
+                    die("cannot make the directory " + dir + " for --velocity: " + std::strerror(why));
+            }
     }
     for (const std::string &path : output_stats_paths(args)) {
         FILE *f = std::fopen(path.c_str(), "wb");

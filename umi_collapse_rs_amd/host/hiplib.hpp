@@ -27,6 +27,8 @@
 // --gene-annotation FILE: likewise umi_assign_genes.
 //
 // --gene-introns exon-first|all: likewise umi_assign_genes_introns, in umi_assign_genes' place.
+//
+// --velocity: likewise umi_assign_genes_classes, in umi_assign_genes_introns' place, and umi_velocity_matrix.
 #pragma once
 #include <chrono>
 #include <dlfcn.h>
@@ -107,6 +109,10 @@ struct HipLib {
     // --gene-introns exon-first|all: likewise, in its place
     bool want_introns = false;
     decltype(&umi_assign_genes_introns) assign_genes_introns = nullptr;
+    // --velocity: likewise, in its place, and the three layers' call
+    bool want_velocity = false;
+    decltype(&umi_assign_genes_classes) assign_genes_classes = nullptr;
+    decltype(&umi_velocity_matrix) velocity_matrix = nullptr;
     // (the HIP runtime the library brings along: device buffers for the arrays above)
     int (*hip_set_device)(int) = nullptr; // (the current device is per thread: the context was made on another)
     int (*hip_malloc)(void **, size_t) = nullptr;
@@ -119,7 +125,8 @@ struct HipLib {
           want_count(!args.count_matrix.empty()), want_stats(!args.output_stats.empty()),
           want_multigene(args.filter_multigene), want_cells(args.cell_filter_given),
           want_genes(args.gene_annotation_given && args.gene_introns_mode == UMI_INTRONS_OFF),
-          want_introns(args.gene_annotation_given && args.gene_introns_mode != UMI_INTRONS_OFF)
+          want_introns(args.gene_annotation_given && args.gene_introns_mode != UMI_INTRONS_OFF && !args.velocity),
+          want_velocity(args.velocity)
     {
     }
     bool load()
@@ -166,6 +173,10 @@ struct HipLib {
         if (want_cells) call_cells = (decltype(call_cells))sym("umi_call_cells");
         if (want_genes) assign_genes = (decltype(assign_genes))sym("umi_assign_genes");
         if (want_introns) assign_genes_introns = (decltype(assign_genes_introns))sym("umi_assign_genes_introns");
+        if (want_velocity) {
+            assign_genes_classes = (decltype(assign_genes_classes))sym("umi_assign_genes_classes");
+            velocity_matrix = (decltype(velocity_matrix))sym("umi_velocity_matrix");
+        }
         hip_set_device = (decltype(hip_set_device))sym("hipSetDevice");
         hip_malloc = (decltype(hip_malloc))sym("hipMalloc");
         hip_memcpy = (decltype(hip_memcpy))sym("hipMemcpy");

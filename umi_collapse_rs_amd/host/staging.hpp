@@ -379,6 +379,8 @@ struct Summary {
     size_t no_gene = 0, several_genes = 0, n_genes = 0; // --per-gene
     size_t annotation_genes = 0, annotation_features = 0, annotation_unknown = 0; // --gene-annotation: on the file's references
     uint64_t by_exon = 0, by_intron = 0; // --gene-introns exon-first|all: the call's reads assigned by either tier
+    uint64_t class_counts[5] = {0, 0, 0, 0, 0}; // --velocity: the call's reads by class (UMI_READ_CLASS_*)
+    uint64_t layers[3] = {0, 0, 0};             // ... and the molecules: spliced, unspliced, ambiguous
     uint64_t cb_counts[5] = {0, 0, 0, 0, 0}; // --cell-whitelist: exact, corrected, unlisted, ambiguous, (-multi) resolved
     uint64_t wl_counts[3] = {0, 0, 0};    // --umi-whitelist: exact, corrected, uncorrectable
     size_t n_positions = 0, nb = 0, n = 0, max_umi = 0;
@@ -453,6 +455,16 @@ struct Summary {
             std::fprintf(stderr, "Number of reads in called cells: %llu\n", c[5]);
             std::fprintf(stderr, "Median molecules per called cell: %llu\n", c[8]);
             std::fprintf(stderr, "Median genes per called cell: %llu\n", c[9]);
+        }
+        if (args.velocity) {
+            std::fprintf(stderr, "Velocity: on\n");
+            std::fprintf(stderr, "Number of exonic reads: %llu\n", (unsigned long long)class_counts[UMI_READ_CLASS_EXONIC]);
+            std::fprintf(stderr, "Number of junction reads: %llu\n", (unsigned long long)class_counts[UMI_READ_CLASS_JUNCTION]);
+            std::fprintf(stderr, "Number of exon-intron reads: %llu\n", (unsigned long long)class_counts[UMI_READ_CLASS_SPANNING]);
+            std::fprintf(stderr, "Number of intronic reads: %llu\n", (unsigned long long)class_counts[UMI_READ_CLASS_INTRONIC]);
+            std::fprintf(stderr, "Number of spliced molecules: %llu\n", (unsigned long long)layers[0]);
+            std::fprintf(stderr, "Number of unspliced molecules: %llu\n", (unsigned long long)layers[1]);
+            std::fprintf(stderr, "Number of ambiguous molecules: %llu\n", (unsigned long long)layers[2]);
         }
         if (args.call_consensus) {
             std::fprintf(stderr, "Number of clusters below --call-consensus-min-reads: %zu\n", n_below);

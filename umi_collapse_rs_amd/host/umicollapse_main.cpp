@@ -92,6 +92,12 @@
 // pass, which takes its verdict in the gene tag's place (assign_genes() below).
 // --gene-introns exon-first|all (with --gene-annotation; annotation.hpp): that one call is umi_assign_genes_introns,
 // whose gene and status are used alike; its counts by tier go into the summary, the tier of a read goes nowhere.
+// --velocity (with --gene-introns exon-first|all and --count-matrix DIR; annotation.hpp has the rule and the files): that
+// one call is umi_assign_genes_classes, whose gene, status and counts are umi_assign_genes_introns' and whose class per
+// read is kept; the reads are staged on the host, which keeps every read's entry as for --tag; after umi_count_matrix one
+// call to umi_velocity_matrix over the reads' entries and classes, the surviving mask, root[] and the buckets' gene and
+// cell gives the three layers of the same triplets, written to DIR/velocity/ (and, for the called cells, to
+// DIR/velocity/filtered/); everything else stays byte for byte what --stage host writes without the flag.
 // --algo cluster: connected components of "within -k" (cli.hpp); every pipeline here only forwards the algorithm
 // to the library, so it goes with every flag --algo dir goes with.
 // Not implemented, as in the reference: --algo cc (that spelling stays refused; `cluster` is the mode's name).
@@ -147,8 +153,9 @@ struct OnePass {
     const int algo = args.algo_id, merge = args.merge_id;
     const unsigned T = std::max(1u, args.num_threads);
     const bool need_clusters = args.track_clusters || args.call_consensus; // every read's entry, every entry's root
-    const bool need_root = need_clusters || !args.output_stats.empty() || args.filter_multigene; // root[] of the collapse (no host
-                                                                                                 // staging for it alone)
+    const bool need_entries = need_clusters || args.velocity;              // every read's entry: the host staging keeps it
+    const bool need_root = need_entries || !args.output_stats.empty() || args.filter_multigene; // root[] of the collapse (no host
+                                                                                                // staging for it alone)
 
     umi::bam::File in;
     uint32_t n_rec = 0, chunk = 0; // records; records per thread of the per-read passes
@@ -182,6 +189,7 @@ struct OnePass {
     // of every gene of the call, and what features.tsv calls a gene beside its id (its gene_name where it has one)
     std::vector<uint8_t> assigned_status;
     std::vector<int32_t> assigned_gene;
+    std::vector<uint8_t> assigned_class; // --velocity: per record its UMI_READ_CLASS_*
     std::vector<std::string_view> annotation_ids;
     std::unordered_map<std::string_view, std::string_view> gene_display;
     const AssignedGene *assigned(uint32_t ri, AssignedGene &a) const
@@ -210,7 +218,7 @@ struct OnePass {
     U64s keys, nmask, off; // keys / nmask: n_words words per entry (not zeroed when sized: the staging call writes them)
     I32s freq;
     std::vector<uint32_t> rep;
-    std::vector<uint32_t> entry_of;    // host staging, --tag / --call-consensus: every staged read's entry
+    std::vector<uint32_t> entry_of;    // host staging, --tag / --call-consensus / --velocity: every staged read's entry
     std::vector<uint32_t> bucket_cell; // --per-cell: every bucket's cell id
     std::vector<uint32_t> bucket_gene; // --per-gene: every bucket's gene id
 
@@ -384,7 +392,22 @@ struct OnePass {
         assigned_status.assign(n_rec, UMI_GENE_NONE);
         assigned_gene.assign(n_rec, -1);
         uint64_t counts[3] = {0, 0, 0};
-        if (nc && args.gene_introns_mode != UMI_INTRONS_OFF) { // --gene-introns: the two-tier call in the plain one's place
+        if (args.velocity) assigned_class.assign(n_rec, UMI_READ_CLASS_NONE);
+        if (nc && args.velocity) { // --velocity: the call that tells the classes too, in the two-tier call's place
+            need_ctx();
+            if (!lib.assign_genes_classes) die("libumihip.so lacks umi_assign_genes_classes");
+            std::vector<uint8_t> r_tier(nc), r_class(nc);
+            uint64_t by_tier[4] = {0, 0, 0, 0};
+            if (lib.assign_genes_classes(ctx, x_ref.data(), x_start.data(), x_end.data(), x_strand.data(), x_gene.data(),
+                                         x_gene.size(), (uint32_t)annotation_ids.size(), args.gene_strand_mode,
+                                         args.gene_introns_mode, r_ref.data(), r_pos.data(), r_rev.data(), words.data(),
+                                         c_off.data(), nc, r_gene.data(), r_status.data(), r_tier.data(), r_class.data(), by_tier,
+                                         sum.class_counts) != UMI_OK)
+                die(lib.last_error());
+            sum.by_exon = by_tier[0];
+            sum.by_intron = by_tier[1];
+            for (size_t j = 0; j < nc; j++) assigned_class[cand[j]] = r_class[j];
+        } else if (nc && args.gene_introns_mode != UMI_INTRONS_OFF) { // --gene-introns: the two-tier call in the plain one's place
             need_ctx();
             if (!lib.assign_genes_introns) die("libumihip.so lacks umi_assign_genes_introns");
             std::vector<uint8_t> r_tier(nc);
@@ -431,10 +454,10 @@ struct OnePass {
         // (where the reads are merged per (position, UMI): on the GPU unless something needs the host's
         // per-read bookkeeping -- decided here because the per-read pass only encodes UMIs for the host path)
         check_stage(args);
-        gpu_stage = args.stage != "host" && !args.passthrough && !args.paired && !need_clusters &&
+        gpu_stage = args.stage != "host" && !args.passthrough && !args.paired && !need_entries &&
                     args.dump_staging.empty() && umi_length >= 1;
         if (args.stage == "gpu" && !gpu_stage)
-            die("--stage gpu does not go with --paired, --tag, --call-consensus or --dump-staging");
+            die("--stage gpu does not go with --paired, --tag, --call-consensus, --velocity or --dump-staging");
     }
 
     // utils/mod.rs:63-83 for every staged read; the first bad character ends the run
@@ -832,7 +855,7 @@ struct OnePass {
             std::vector<Entry> entries;
         };
         std::vector<Shard> shards(args.passthrough ? 0 : T);
-        entry_of.assign(need_clusters ? n_rec : 0, 0); // read -> its entry (--tag, --call-consensus): its shard's number first
+        entry_of.assign(need_entries ? n_rec : 0, 0); // read -> its entry (--tag, --call-consensus, --velocity): its shard's number first
         const KeyHash hasher;
         auto key_of = [&](const ReadInfo &ii) { return AlignKey{ii.coord, ii.ref_strand, ii.tlen, ii.cell, ii.gene}; };
         umi::bgzf::parallel_for(shards.size(), T, [&](size_t t) {
@@ -854,7 +877,7 @@ struct OnePass {
                     b = it->second;
                 }
                 const uint32_t e = add_read(sh.umi_index[b], sh.entries, sh.bucket_entries[b], rkey[ri], rnm[ri], ii.score, ri, merge);
-                if (need_clusters) entry_of[ri] = e;
+                if (need_entries) entry_of[ri] = e;
             }
         });
 
@@ -882,7 +905,7 @@ struct OnePass {
             max_umi = std::max(max_umi, v.size());
         }
         // read -> entry: the shard's number becomes the entry's place in the arrays, once and for every later stage
-        if (need_clusters && !shards.empty())
+        if (need_entries && !shards.empty())
             umi::bgzf::parallel_for(T, T, [&](size_t t) {
                 for (uint32_t ri = (uint32_t)t * chunk; ri < std::min(n_rec, ((uint32_t)t + 1) * chunk); ri++)
                     if (info[ri].state == 0) entry_of[ri] = shards[hasher(key_of(info[ri])) % T].entries[entry_of[ri]].index;
@@ -1020,6 +1043,9 @@ struct OnePass {
         write("matrix.mtx", mol);
         write("reads.mtx", rd);
         lap("count matrix");
+        std::vector<uint32_t> v_row, v_col, layer[3];
+        uint64_t v_nnz = 0;
+        if (args.velocity) velocity_matrix(n_rows, n_cols, v_row, v_col, layer, v_nnz, write);
         if (args.cell_filter_given) {
             if (args.filter_multigene) { // (what matrix.mtx holds: the pairs that still have a molecule)
                 uint64_t w = 0;
@@ -1031,6 +1057,67 @@ struct OnePass {
                 nnz = w;
             }
             call_cells(n_rows, n_cols, out_row, out_col, molecules, reads, nnz, write);
+            if (args.velocity) { // the layers of the called cells, their columns renumbered as DIR/filtered's
+                uint64_t w = 0;
+                for (uint64_t i = 0; i < v_nnz; i++) {
+                    if (called_col[v_col[i]] == UINT32_MAX) continue;
+                    v_row[w] = v_row[i], v_col[w] = called_col[v_col[i]];
+                    for (auto &l : layer) l[w] = l[i];
+                    w++;
+                }
+                write_layers("velocity/filtered/", n_rows, (uint32_t)sum.cell_counts[1], v_row, v_col, layer, w, write);
+            }
+        }
+    }
+
+    // --velocity: the three layers of the matrix's triplets in one call over every read's entry and class, the mask
+    // the matrix was counted from, root[] and the buckets' gene and cell; then DIR/velocity's five files
+    using Write = std::function<void(const char *, const std::string &)>;
+    std::vector<uint32_t> called_col; // --cell-filter: per column its number among the called cells, UINT32_MAX: not called
+    void velocity_matrix(uint32_t n_rows, uint32_t n_cols, std::vector<uint32_t> &v_row, std::vector<uint32_t> &v_col,
+                         std::vector<uint32_t> (&layer)[3], uint64_t &v_nnz, const Write &write)
+    {
+        v_row.assign(nb + 1, 0);
+        v_col.assign(nb + 1, 0);
+        for (auto &l : layer) l.assign(nb + 1, 0);
+        if (nb) {
+            need_ctx();
+            if (!lib.velocity_matrix) die("libumihip.so lacks umi_velocity_matrix");
+            std::vector<uint32_t> read_entry(n_rec);
+            for (uint32_t ri = 0; ri < n_rec; ri++) read_entry[ri] = info[ri].state == 0 ? entry_of[ri] : UMI_READ_UNSTAGED;
+            const std::vector<uint32_t> one_column(args.per_cell ? 0 : nb, 0u);
+            if (lib.velocity_matrix(ctx, read_entry.data(), assigned_class.data(), n_rec, survivors().data(), root.data(), off.data(), nb,
+                                    bucket_gene.data(), args.per_cell ? bucket_cell.data() : one_column.data(), n_rows, n_cols,
+                                    v_row.data(), v_col.data(), layer[0].data(), layer[1].data(), layer[2].data(), &v_nnz) != UMI_OK)
+                die(lib.last_error());
+        }
+        for (int k = 0; k < 3; k++)
+            for (uint64_t i = 0; i < v_nnz; i++) sum.layers[k] += layer[k][i];
+        write_layers("velocity/", n_rows, n_cols, v_row, v_col, layer, v_nnz, write);
+        lap("velocity matrix");
+    }
+
+    // features.tsv and barcodes.tsv as their directory's parent has them, and a layer per file, each with its non-zero entries alone
+    void write_layers(const std::string &dir, uint32_t n_rows, uint32_t n_cols, const std::vector<uint32_t> &row,
+                      const std::vector<uint32_t> &col, const std::vector<uint32_t> (&layer)[3], uint64_t nnz, const Write &write)
+    {
+        const bool filtered = dir != "velocity/";
+        write((dir + "features.tsv").c_str(), features_text());
+        std::string text;
+        if (!args.per_cell) text = "all\n";
+        for (size_t c = 0; c < cell_names.size() && args.per_cell; c++)
+            if (!filtered || called_col[c] != UINT32_MAX) text.append(cell_names[c]).append("\n");
+        write((dir + "barcodes.tsv").c_str(), text);
+        const char *names[3] = {"spliced.mtx", "unspliced.mtx", "ambiguous.mtx"};
+        for (int k = 0; k < 3; k++) {
+            const uint64_t lines = (uint64_t)std::count_if(layer[k].begin(), layer[k].begin() + nnz, [](uint32_t m) { return m != 0; });
+            text = "%%MatrixMarket matrix coordinate integer general\n" + std::to_string(n_rows) + " " + std::to_string(n_cols) + " " +
+                   std::to_string(lines) + "\n";
+            for (uint64_t i = 0; i < nnz; i++)
+                if (layer[k][i])
+                    text.append(std::to_string(row[i] + 1)).append(" ").append(std::to_string(col[i] + 1)).append(" ")
+                        .append(std::to_string(layer[k][i])).append("\n");
+            write((dir + names[k]).c_str(), text);
         }
     }
 
@@ -1076,6 +1163,9 @@ struct OnePass {
         }
         write("filtered/matrix.mtx", mol);
         write("filtered/reads.mtx", rd);
+        called_col.assign(new_col.begin(), new_col.begin() + n_cols);
+        for (size_t c = 0; c < n_cols; c++)
+            if (!called[c]) called_col[c] = UINT32_MAX;
         lap("cell filter");
     }
 
