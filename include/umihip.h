@@ -114,6 +114,10 @@ const char *umi_last_error(void);
  *                    n_pairs_evaluated counts the pairs inside the sub-buckets
  *   "seg_min"        2..2^31, see above
  *   "seg_blocks"     one-wave blocks of the segment index's pair kernel (0 = 16 per CU)
+ *   "grid_cus"       0..the device's CUs (default 0 = the device's): the number of CUs every call sizes its grids
+ *                    from.  A test handle: at 1 a few thousand items send every grid-stride kernel round its loop
+ *                    several times, as half a million do on a whole device.  A value above the device's is
+ *                    refused: the persistent grids must stay resident
  *   "seg_lds"        0/1 (default 1): its counting sort through per-block LDS histograms (0: one atomic
  *                    per entry)
  *   "seg_unite"      0/1 (default 1): symmetric pairs united where the pair kernel finds them (0: through

@@ -80,7 +80,8 @@ int umi_ctx_create(int device_id, umi_ctx **out)
     umi_ctx *ctx = new (std::nothrow) umi_ctx();
     if (!ctx) return fail(UMI_ERR_NOMEM, "out of host memory");
     ctx->device = device_id;
-    ctx->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    ctx->device_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    ctx->n_cus = ctx->device_cus;
     hipError_t err = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking);
     if (err == hipSuccess)
         err = hipHostMalloc((void **)&ctx->h_counters, CTRL_BYTES + 64);
@@ -212,6 +213,10 @@ int umi_ctx_set_option(umi_ctx *ctx, const char *name, int64_t value)
     } else if (!strcmp(name, "seg_blocks")) {
         if (value < 0 || value > (1 << 22)) return fail(UMI_ERR_ARG, "seg_blocks must be in 0..2^22");
         ctx->seg_blocks = (uint32_t)value;
+    } else if (!strcmp(name, "grid_cus")) {
+        if (value < 0 || value > ctx->device_cus)
+            return fail(UMI_ERR_ARG, "grid_cus must be in 0..%d (the device's CUs)", ctx->device_cus);
+        ctx->n_cus = value ? (int)value : ctx->device_cus;
     } else if (!strcmp(name, "seg_min")) {
         if (value < 2 || value > (1ll << 31)) return fail(UMI_ERR_ARG, "seg_min must be in 2..2^31");
         ctx->seg_min = (uint32_t)value;

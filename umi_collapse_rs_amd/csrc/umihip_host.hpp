@@ -240,7 +240,8 @@ struct umi_ctx {
     int plan_flip = 0;
     size_t plan_uploaded = 0;
     const void *plan_uploaded_to = nullptr;
-    int n_cus = 256;
+    int n_cus = 256;     // the CUs every call sizes its grids from: the device's, or option "grid_cus"
+    int device_cus = 256; // the device's own count ("grid_cus" 0 puts it back)
     umihip::DevBuf fkey_sorted, perm, iota, sort_tmp, sample_pos, sample_out; // prune mode
     bool prune = false;
     umihip::Plan plan;
