@@ -9,7 +9,7 @@ LIB := $(PKG)/libumihip.so
 OBJDIR := build/obj
 # the library's translation units, listed once: the kernels (.hip), then the host side (.cpp)
 SRCS := umihip_kernels umihip_seg umihip_collapse umihip_stage umihip_radix umihip_wide umihip_edit umihip_seq \
-        umihip_consensus umihip_consensus_bam umihip_correct umihip_barcode umihip_count umihip_multigene umihip_stats umihip_cells umihip_genes umihip_gene_introns umihip_gene_classes umihip_velocity \
+        umihip_consensus umihip_consensus_bam umihip_correct umihip_barcode umihip_count umihip_multigene umihip_stats umihip_cells umihip_genes umihip_gene_introns umihip_gene_classes umihip_gene_transcripts umihip_velocity \
         umihip_api umihip_pipeline umihip_batch umihip_stage_api umihip_seq_api umihip_correct_api umihip_count_api umihip_genes_api umihip_data
 OBJS := $(patsubst %,$(OBJDIR)/%.o,$(SRCS))
 # development build (make dev): the shipped sources plus the round-1 tile kernels, their key sort
@@ -17,10 +17,10 @@ OBJS := $(patsubst %,$(OBJDIR)/%.o,$(SRCS))
 DEVDIR := build/obj_dev
 DEVLIB := $(PKG)/libumihip_dev.so
 DEVOBJS := $(patsubst %,$(DEVDIR)/%.o,$(SRCS)) $(DEVDIR)/umihip_legacy.o $(DEVDIR)/umihip_sort.o
-HDRS := $(CSRC)/umihip_internal.h $(CSRC)/umihip_cons_group.h $(CSRC)/umihip_device.h $(CSRC)/umihip_plan.hpp $(CSRC)/umihip_io_layout.hpp $(CSRC)/umihip_host.hpp $(CSRC)/umihip_gene_index.hpp include/umihip.h
+HDRS := $(CSRC)/umihip_internal.h $(CSRC)/umihip_cons_group.h $(CSRC)/umihip_device.h $(CSRC)/umihip_plan.hpp $(CSRC)/umihip_io_layout.hpp $(CSRC)/umihip_host.hpp $(CSRC)/umihip_gene_index.hpp $(CSRC)/umihip_transcript_index.hpp include/umihip.h
 CLI := $(PKG)/bin/umicollapse
 
-all: $(LIB) oracle cpptest primtest $(CLI)
+all: $(LIB) oracle cpptest primtest trtest $(CLI)
 
 # (the staging's host decisions: read by the staging unit alone)
 $(OBJDIR)/umihip_stage.o $(DEVDIR)/umihip_stage.o: $(CSRC)/umihip_stage_plan.hpp
@@ -82,9 +82,17 @@ $(PRIMTEST): $(OBJDIR)/test_primitives.o $(OBJDIR)/umihip_radix.o
 
 primtest: $(PRIMTEST)
 
+# the transcript index's lookup on the CPU, a program of its own (tests/test_transcript_index_cpu.py builds it once more, under sanitizers)
+TRTEST := build/test_transcript_index
+$(TRTEST): tests/cpp/test_transcript_index.cpp $(CSRC)/umihip_transcript_index.hpp $(CSRC)/umihip_gene_index.hpp
+	@mkdir -p build
+	g++ -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/test_transcript_index.cpp
+
+trtest: $(TRTEST)
+
 clean:
 	rm -f $(LIB) $(DEVLIB) $(CLI)
 	rm -rf build
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all dev oracle asm clean cpptest primtest cli
+.PHONY: all dev oracle asm clean cpptest primtest trtest cli

@@ -163,7 +163,8 @@ const char *umi_last_error(void);
  *                    over the whole grid instead of by one wave (raised by itself where the deep buckets' tables,
  *                    80 bytes per base each, would pass 512 MB)
  *   "gene_top"       0/1 (default 1): umi_assign_genes searches a sampled top of its index in LDS before the
- *                    index itself (0: the index alone); umi_assign_genes_introns likewise, for both its tiers
+ *                    index itself (0: the index alone); umi_assign_genes_introns likewise, for both its tiers,
+ *                    and umi_assign_genes_transcripts for its distinct exons
  *   "gene_body_top"  0/1 (default 1): with gene_top 1, umi_assign_genes_introns holds the gene bodies' tops in LDS
  *                    beside the exons' (0: the exons' alone); umi_assign_genes_classes takes both options alike
  *   "velocity_skip"  0/1 (default 0): 1: umi_velocity_matrix's reads load their molecule's evidence first and leave the
@@ -529,8 +530,8 @@ int umi_correct_barcodes_multi(umi_ctx *ctx, const uint8_t *bc_ascii, const uint
  *          UMI_STRAND_UNSTRANDED: any.  A '.' exon is admissible under all three.
  *        Result: exactly one gene hits: UMI_GENE_ASSIGNED, gene = its index; none: UMI_GENE_NONE, gene = -1; two
  *          or more: UMI_GENE_SEVERAL, gene = -1.  Overlapping exons of one gene count as one gene.
- *      Not built: transcript-level containment (STARsolo's Gene), paired reads, fractional assignment, a minimum
- *      overlap above 1.
+ *      Transcript-level containment (STARsolo's Gene) is umi_assign_genes_transcripts, below.  Not built: paired
+ *      reads, fractional assignment, a minimum overlap above 1.
  * in : the n_exons exons in five HOST arrays in both forms (exon_strand: the ASCII bytes), exon_gene in
  *      0..n_genes - 1; per read read_ref, read_pos, read_reverse, and its CIGAR words cigar[cigar_off[i] ..
  *      cigar_off[i + 1]), the reads' words back to back, cigar_off of n_reads + 1 entries (cigar may be NULL
@@ -564,6 +565,48 @@ int umi_assign_genes(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_
                      int strand_mode, const int32_t *read_ref, const int32_t *read_pos, const uint8_t *read_reverse,
                      const uint32_t *cigar, const uint64_t *cigar_off, uint64_t n_reads, int32_t *gene, uint8_t *status,
                      uint64_t counts[3]);
+
+/* ---- ... by transcript model (the program's --gene-rule transcript), on the GPU.  No counterpart in the reference;
+ *      the rule is STARsolo's default feature (Gene) and Cell Ranger's transcriptome-compatible reads, and
+ *      tests/transcript_model.py defines it.  Blocks of a read and admissible strands are umi_assign_genes', unchanged
+ *      (a zero-length N closes a block too: two abutting blocks; empty blocks are left out).  New:
+ *        Exons: (ref, start, end, strand, gene, transcript), transcript in 0..n_transcripts - 1.  All exons of one
+ *          transcript share ref, strand and gene.  A transcript's exons are taken in ascending order, whatever order
+ *          they were passed in; those that overlap or abut are united: x_1 < x_2 < ... < x_n, disjoint, at least one
+ *          base between neighbours.
+ *        Fit: a read with blocks b_1 .. b_m fits transcript t when t is on the read's reference and on an admissible
+ *          strand (a '.' transcript always), m >= 1, and there is a j such that b_i lies inside x_{j+i-1} for every i,
+ *          and for every i < m: end(b_i) == end(x_{j+i-1}) and start(b_{i+1}) == start(x_{j+i}).  A D never splits a
+ *          block: a deletion across an intron makes a block that no exon contains.  A read with more blocks than t
+ *          has exons from j on does not fit t.  Coordinates are compared in 64 bits: a block that starts before 0 or
+ *          ends beyond 2^31 - 1 lies in nothing, and nothing wraps.
+ *        Result: G = the genes with a transcript the read fits.  One gene: UMI_GENE_ASSIGNED, gene = its index; none:
+ *          UMI_GENE_NONE, gene = -1; two or more: UMI_GENE_SEVERAL, gene = -1.  Two fitting transcripts of one gene
+ *          are one gene.  G is a subset of the genes that hit the read under umi_assign_genes.
+ *      Not built: a body tier and read classes by transcript model (--gene-introns, --velocity with this rule),
+ *      paired reads, STARsolo's multi-gene modes.
+ * in : umi_assign_genes' arguments, and exon_transcript (HOST, n_exons entries) and n_transcripts (it may lie above the
+ *      transcripts used).  The index is built on the host inside the call; the walks and the lookups run on the device.
+ * out: gene, status and counts[3] as umi_assign_genes writes them.
+ * Everything else is umi_assign_genes' contract: n_reads == 0 (UMI_OK, counts all zero, nothing else touched),
+ * n_exons == 0 (legal: every read is none), the first device of a multi-device context, a deferred call that is out
+ * ends first, the errors and when they are found, the limit of 2^30, options "gene_top" and "grid_cus".  UMI_ERR_ARG
+ * before anything is launched, beside umi_assign_genes' own: exon_transcript NULL with exons, an entry outside
+ * 0..n_transcripts - 1, a transcript whose exons lie on two references, on two strands or in two genes,
+ * n_transcripts >= 2^31. */
+int umi_assign_genes_transcripts_device(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start,
+                                        const int32_t *exon_end, const uint8_t *exon_strand, const int32_t *exon_gene,
+                                        const int32_t *exon_transcript, uint64_t n_exons, uint32_t n_genes,
+                                        uint32_t n_transcripts, int strand_mode, const int32_t *d_read_ref,
+                                        const int32_t *d_read_pos, const uint8_t *d_read_reverse, const uint32_t *d_cigar,
+                                        const uint64_t *d_cigar_off, uint64_t n_reads, int32_t *d_gene, uint8_t *d_status,
+                                        uint64_t counts[3], void *hip_stream);
+int umi_assign_genes_transcripts(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end,
+                                 const uint8_t *exon_strand, const int32_t *exon_gene, const int32_t *exon_transcript,
+                                 uint64_t n_exons, uint32_t n_genes, uint32_t n_transcripts, int strand_mode,
+                                 const int32_t *read_ref, const int32_t *read_pos, const uint8_t *read_reverse,
+                                 const uint32_t *cigar, const uint64_t *cigar_off, uint64_t n_reads, int32_t *gene,
+                                 uint8_t *status, uint64_t counts[3]);
 
 /* ---- ... with their introns (the program's --gene-introns), on the GPU.  No counterpart in the reference; the
  *      rules are STARsolo's GeneFull_ExonOverIntron and GeneFull, stated with this project's overlap of one base, and

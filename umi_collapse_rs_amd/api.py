@@ -510,6 +510,61 @@ class Context:
                                              d_status or None, ptr(counts, C.c_uint64), stream or None))
         return counts
 
+    @staticmethod
+    def _transcript_array(exons, n_exons):
+        """exon_transcript of exons: the dict's "transcript", or the sixth element of every tuple"""
+        tr = exons["transcript"] if isinstance(exons, dict) else [e[5] for e in exons]
+        tr = np.ascontiguousarray(tr, dtype=np.int32).reshape(-1)
+        if len(tr) != n_exons:
+            raise ValueError("the exon arrays differ in length")
+        return tr
+
+    def assign_genes_transcripts(self, exons, n_genes, n_transcripts, strand_mode, read_ref, read_pos, read_reverse, cigar,
+                                 cigar_off):
+        """Reads assigned to genes by transcript model, STARsolo's Gene (umi_assign_genes_transcripts; the rule is in
+        include/umihip.h): assign_genes' arguments, the exons with their transcript -- a dict with "transcript" (int32)
+        beside _exon_arrays' keys, or (ref, start, end, strand, gene, transcript) tuples -- and n_transcripts.  Returns
+        assign_genes' dict."""
+        exons = exons if isinstance(exons, dict) else list(exons)
+        ex = self._exon_arrays(exons)
+        tr = self._transcript_array(exons, len(ex[0]))
+        read_ref = np.ascontiguousarray(read_ref, dtype=np.int32).reshape(-1)
+        read_pos = np.ascontiguousarray(read_pos, dtype=np.int32).reshape(-1)
+        read_reverse = np.ascontiguousarray(read_reverse, dtype=np.uint8).reshape(-1)
+        cigar = np.ascontiguousarray(cigar, dtype=np.uint32).reshape(-1)
+        cigar_off = np.ascontiguousarray(cigar_off, dtype=np.uint64).reshape(-1)
+        n = len(read_ref)
+        if len(read_pos) != n or len(read_reverse) != n or len(cigar_off) != n + 1:
+            raise ValueError("the read arrays differ in length (cigar_off has one entry more)")
+        if int(cigar_off[-1]) > len(cigar):
+            raise ValueError("cigar_off ends beyond cigar")
+        m = max(1, n)
+        gene, status = np.zeros(m, np.int32), np.zeros(m, np.uint8)
+        counts = np.zeros(3, np.uint64)
+        check(load().umi_assign_genes_transcripts(self._h, ptr(ex[0], C.c_int32), ptr(ex[1], C.c_int32), ptr(ex[2], C.c_int32),
+                                                  ptr(ex[3], C.c_uint8), ptr(ex[4], C.c_int32), ptr(tr, C.c_int32), len(ex[0]),
+                                                  n_genes, n_transcripts, strand_mode, ptr(read_ref, C.c_int32),
+                                                  ptr(read_pos, C.c_int32), ptr(read_reverse, C.c_uint8), ptr(cigar, C.c_uint32),
+                                                  ptr(cigar_off, C.c_uint64), n, ptr(gene, C.c_int32), ptr(status, C.c_uint8),
+                                                  ptr(counts, C.c_uint64)))
+        return {"gene": gene[:n], "status": status[:n], "counts": counts}
+
+    def assign_genes_transcripts_device(self, exons, n_genes, n_transcripts, strand_mode, d_read_ref, d_read_pos, d_read_reverse,
+                                        d_cigar, d_cigar_off, n_reads, d_gene, d_status, stream=0):
+        """The same on raw device pointers (umi_assign_genes_transcripts_device; the exons stay on the host): fills
+        d_gene (int32 [n_reads]) and d_status (uint8 [n_reads]); returns counts uint64 [3]."""
+        exons = exons if isinstance(exons, dict) else list(exons)
+        ex = self._exon_arrays(exons)
+        tr = self._transcript_array(exons, len(ex[0]))
+        counts = np.zeros(3, np.uint64)
+        check(load().umi_assign_genes_transcripts_device(self._h, ptr(ex[0], C.c_int32), ptr(ex[1], C.c_int32),
+                                                         ptr(ex[2], C.c_int32), ptr(ex[3], C.c_uint8), ptr(ex[4], C.c_int32),
+                                                         ptr(tr, C.c_int32), len(ex[0]), n_genes, n_transcripts, strand_mode,
+                                                         d_read_ref or None, d_read_pos or None, d_read_reverse or None,
+                                                         d_cigar or None, d_cigar_off or None, n_reads, d_gene or None,
+                                                         d_status or None, ptr(counts, C.c_uint64), stream or None))
+        return counts
+
     def assign_genes_introns(self, exons, n_genes, strand_mode, intron_mode, read_ref, read_pos, read_reverse, cigar, cigar_off):
         """Reads assigned to genes with their introns (umi_assign_genes_introns; the rule is in include/umihip.h):
         assign_genes' arguments and intron_mode, one of UMI_INTRONS_*.  Returns dict(gene int32 [n] (-1 unless

@@ -4,6 +4,7 @@
 
 #include "umihip_gene_index.hpp"
 #include "umihip_host.hpp"
+#include "umihip_transcript_index.hpp"
 
 using namespace umihip;
 
@@ -15,11 +16,11 @@ struct GeneIndex {
     bool flip = false;
 };
 
-// the checks both forms share (the context is looked at last: everything before it is decided without a device)
-int genes_check(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end, const uint8_t *exon_strand,
-                const int32_t *exon_gene, uint64_t n_exons, uint32_t n_genes, int strand_mode, const void *read_ref,
-                const void *read_pos, const void *read_reverse, const void *cigar_off, uint64_t n_reads, const void *gene,
-                const void *status, const uint64_t *counts)
+// the checks both forms share, all but the context's: decided without a device
+int genes_check_arrays(const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end, const uint8_t *exon_strand,
+                       const int32_t *exon_gene, uint64_t n_exons, uint32_t n_genes, int strand_mode, const void *read_ref,
+                       const void *read_pos, const void *read_reverse, const void *cigar_off, uint64_t n_reads, const void *gene,
+                       const void *status, const uint64_t *counts)
 {
     if (!counts) return fail(UMI_ERR_ARG, "counts is NULL");
     if (strand_mode != UMI_STRAND_FORWARD && strand_mode != UMI_STRAND_REVERSE && strand_mode != UMI_STRAND_UNSTRANDED)
@@ -41,6 +42,18 @@ int genes_check(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start
         if (exon_strand[i] != '+' && exon_strand[i] != '-' && exon_strand[i] != '.')
             return fail(UMI_ERR_ARG, "exon %llu: unknown strand %u", (unsigned long long)i, (unsigned)exon_strand[i]);
     }
+    return UMI_OK;
+}
+
+// (the context is looked at last)
+int genes_check(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end, const uint8_t *exon_strand,
+                const int32_t *exon_gene, uint64_t n_exons, uint32_t n_genes, int strand_mode, const void *read_ref,
+                const void *read_pos, const void *read_reverse, const void *cigar_off, uint64_t n_reads, const void *gene,
+                const void *status, const uint64_t *counts)
+{
+    const int rc = genes_check_arrays(exon_ref, exon_start, exon_end, exon_strand, exon_gene, n_exons, n_genes, strand_mode, read_ref,
+                                      read_pos, read_reverse, cigar_off, n_reads, gene, status, counts);
+    if (rc) return rc;
     if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
     return UMI_OK;
 }
@@ -360,6 +373,142 @@ int umi_assign_genes_classes(umi_ctx *ctx, const int32_t *exon_ref, const int32_
                           class_counts, io.stream())) ||
         (rc = io.fetch(gene, d_gene, n)) || (rc = io.fetch(status, d_status, n)) || (rc = io.fetch(tier, d_tier, n)) ||
         (rc = io.fetch(cls, d_cls, n)))
+        return rc;
+    return io.close();
+}
+
+} // extern "C"
+
+// ---- umi_assign_genes_transcripts*: umi_assign_genes' checks, the transcripts' (umihip_transcript_index.hpp), and the
+// ---- transcript tables, one per strand class; the kernel is umihip_gene_transcripts.hip's
+
+namespace {
+
+struct TranscriptIndex {
+    TranscriptTable tables[2];
+    int n_tables = 0;
+    bool flip = false;
+};
+
+// (after genes_check_arrays: every exon is an exon)
+int transcripts_check(const int32_t *exon_ref, const uint8_t *exon_strand, const int32_t *exon_gene, const int32_t *exon_transcript,
+                      uint64_t n_exons, uint32_t n_transcripts)
+{
+    if (n_transcripts >= (1u << 31)) return fail(UMI_ERR_ARG, "n_transcripts %u does not fit a transcript index", n_transcripts);
+    if (n_exons && !exon_transcript) return fail(UMI_ERR_ARG, "a required exon array is NULL");
+    uint64_t bad = 0;
+    switch (transcript_check(exon_ref, exon_strand, exon_gene, exon_transcript, n_exons, n_transcripts, &bad)) {
+    case TR_BAD_RANGE:
+        return fail(UMI_ERR_ARG, "exon %llu: transcript %d outside 0..%u", (unsigned long long)bad, exon_transcript[bad], n_transcripts);
+    case TR_BAD_REF:
+        return fail(UMI_ERR_ARG, "exon %llu: transcript %d lies on two references", (unsigned long long)bad, exon_transcript[bad]);
+    case TR_BAD_STRAND:
+        return fail(UMI_ERR_ARG, "exon %llu: transcript %d lies on two strands", (unsigned long long)bad, exon_transcript[bad]);
+    case TR_BAD_GENE:
+        return fail(UMI_ERR_ARG, "exon %llu: transcript %d lies in two genes", (unsigned long long)bad, exon_transcript[bad]);
+    default:
+        return UMI_OK;
+    }
+}
+
+// both forms' checks, in order: the exons, the transcripts, the context
+int transcripts_check_all(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end,
+                          const uint8_t *exon_strand, const int32_t *exon_gene, const int32_t *exon_transcript, uint64_t n_exons,
+                          uint32_t n_genes, uint32_t n_transcripts, int strand_mode, const void *read_ref, const void *read_pos,
+                          const void *read_reverse, const void *cigar_off, uint64_t n_reads, const void *gene, const void *status,
+                          const uint64_t *counts)
+{
+    int rc = genes_check_arrays(exon_ref, exon_start, exon_end, exon_strand, exon_gene, n_exons, n_genes, strand_mode, read_ref, read_pos,
+                                read_reverse, cigar_off, n_reads, gene, status, counts);
+    if (rc) return rc;
+    if ((rc = transcripts_check(exon_ref, exon_strand, exon_gene, exon_transcript, n_exons, n_transcripts))) return rc;
+    if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
+    return UMI_OK;
+}
+
+void transcripts_index(const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end, const uint8_t *exon_strand,
+                       const int32_t *exon_gene, const int32_t *exon_transcript, uint64_t n_exons, int strand_mode, TranscriptIndex &ix)
+{
+    ix.flip = strand_mode == UMI_STRAND_REVERSE;
+    ix.n_tables = strand_mode == UMI_STRAND_UNSTRANDED ? 1 : 2;
+    const unsigned take[2] = {ix.n_tables == 1 ? GENE_TAKE_PLUS | GENE_TAKE_MINUS | GENE_TAKE_DOT : GENE_TAKE_PLUS | GENE_TAKE_DOT,
+                              GENE_TAKE_MINUS | GENE_TAKE_DOT};
+    for (int t = 0; t < ix.n_tables; t++) {
+        transcript_index_build(exon_ref, exon_start, exon_end, exon_strand, exon_gene, exon_transcript, n_exons, take[t], ix.tables[t]);
+        transcript_index_sample(ix.tables[t], GENE_TOP_CAP);
+    }
+}
+
+int transcripts_run(umi_ctx *ctx, const TranscriptIndex &ix, const int32_t *d_ref, const int32_t *d_pos, const uint8_t *d_reverse,
+                    const uint32_t *d_cigar, const uint64_t *d_cigar_off, uint64_t n_reads, int32_t *d_gene, uint8_t *d_status,
+                    uint64_t *counts, hipStream_t s)
+{
+    int rc;
+    if ((rc = ctx->call_ws.reserve(gene_transcripts_workspace_bytes(ix.tables, ix.n_tables)))) return rc;
+    uint64_t bad = 0;
+    const int r = gene_transcripts_on_device(ctx->call_ws.p, ix.tables, ix.n_tables, ix.flip, ctx->gene_top, d_ref, d_pos, d_reverse,
+                                             d_cigar, d_cigar_off, (uint32_t)n_reads, d_gene, d_status, counts, &bad,
+                                             (uint32_t)ctx->n_cus, ctx->h_counters, s);
+    if (r == 1)
+        return fail(UMI_ERR_ARG, "read %llu: a negative reference, a CIGAR op code above 8, or CIGAR words without an array",
+                    (unsigned long long)bad);
+    if (r == 2) return fail(UMI_ERR_ORDER, "cigar_off falls at read %llu", (unsigned long long)bad);
+    if (r < 0) return fail(UMI_ERR_HIP, "gene assignment by transcripts: %s", hipGetErrorString((hipError_t)(-r)));
+    return UMI_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int umi_assign_genes_transcripts_device(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end,
+                                        const uint8_t *exon_strand, const int32_t *exon_gene, const int32_t *exon_transcript,
+                                        uint64_t n_exons, uint32_t n_genes, uint32_t n_transcripts, int strand_mode,
+                                        const int32_t *d_read_ref, const int32_t *d_read_pos, const uint8_t *d_read_reverse,
+                                        const uint32_t *d_cigar, const uint64_t *d_cigar_off, uint64_t n_reads, int32_t *d_gene,
+                                        uint8_t *d_status, uint64_t counts[3], void *hip_stream)
+{
+    int rc = transcripts_check_all(ctx, exon_ref, exon_start, exon_end, exon_strand, exon_gene, exon_transcript, n_exons, n_genes,
+                                   n_transcripts, strand_mode, d_read_ref, d_read_pos, d_read_reverse, d_cigar_off, n_reads, d_gene,
+                                   d_status, counts);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_assign_genes)
+    counts[0] = counts[1] = counts[2] = 0;
+    if (n_reads == 0) return UMI_OK;
+    TranscriptIndex ix;
+    transcripts_index(exon_ref, exon_start, exon_end, exon_strand, exon_gene, exon_transcript, n_exons, strand_mode, ix);
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
+    return transcripts_run(ctx, ix, d_read_ref, d_read_pos, d_read_reverse, d_cigar, d_cigar_off, n_reads, d_gene, d_status, counts,
+                           (hipStream_t)hip_stream);
+}
+
+int umi_assign_genes_transcripts(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end,
+                                 const uint8_t *exon_strand, const int32_t *exon_gene, const int32_t *exon_transcript, uint64_t n_exons,
+                                 uint32_t n_genes, uint32_t n_transcripts, int strand_mode, const int32_t *read_ref,
+                                 const int32_t *read_pos, const uint8_t *read_reverse, const uint32_t *cigar, const uint64_t *cigar_off,
+                                 uint64_t n_reads, int32_t *gene, uint8_t *status, uint64_t counts[3])
+{
+    int rc = transcripts_check_all(ctx, exon_ref, exon_start, exon_end, exon_strand, exon_gene, exon_transcript, n_exons, n_genes,
+                                   n_transcripts, strand_mode, read_ref, read_pos, read_reverse, cigar_off, n_reads, gene, status, counts);
+    if (rc) return rc;
+    if (n_reads && cigar_off[n_reads] && !cigar) return fail(UMI_ERR_ARG, "cigar is NULL");
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    counts[0] = counts[1] = counts[2] = 0;
+    if (n_reads == 0) return UMI_OK;
+    TranscriptIndex ix;
+    transcripts_index(exon_ref, exon_start, exon_end, exon_strand, exon_gene, exon_transcript, n_exons, strand_mode, ix);
+    const size_t n = (size_t)n_reads, words = (size_t)cigar_off[n_reads];
+    HostIo io(ctx);
+    const auto d_ref = io.in(read_ref, n * 4), d_pos = io.in(read_pos, n * 4);
+    const auto d_reverse = io.in(read_reverse, n);
+    const auto d_cigar = io.in(cigar, words * 4);
+    const auto d_off = io.in(cigar_off, (n + 1) * 8);
+    const auto d_gene = io.out(gene, n * 4);
+    const auto d_status = io.out(status, n);
+    if ((rc = io.open()) ||
+        (rc = transcripts_run(ctx, ix, d_ref, d_pos, d_reverse, d_cigar, d_off, n_reads, d_gene, d_status, counts, io.stream())) ||
+        (rc = io.fetch(gene, d_gene, n)) || (rc = io.fetch(status, d_status, n)))
         return rc;
     return io.close();
 }

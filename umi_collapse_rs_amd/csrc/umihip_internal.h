@@ -546,6 +546,17 @@ int gene_classes_on_device(void *workspace, const GeneTable *exons, const GeneTa
                            uint32_t n_reads, int32_t *d_gene, uint8_t *d_status, uint8_t *d_tier, uint8_t *d_cls, uint64_t counts[4],
                            uint64_t class_counts[5], uint64_t *bad, uint32_t n_cus, unsigned long long *h_pinned, hipStream_t s);
 
+// ---- reads assigned to genes by transcript model (umihip_gene_transcripts.hip: umi_assign_genes_transcripts) ----
+// The tables (umihip_transcript_index.hpp: one per strand class, as genes_on_device's, sampled at GENE_TOP_CAP) are built
+// on the host and uploaded into the workspace.  One synchronisation, at the end.  h_pinned: 5 pinned words.  Returns
+// as genes_on_device.
+struct TranscriptTable;
+size_t gene_transcripts_workspace_bytes(const TranscriptTable *tables, int n_tables);
+int gene_transcripts_on_device(void *workspace, const TranscriptTable *tables, int n_tables, bool flip, bool use_top, const int32_t *d_ref,
+                               const int32_t *d_pos, const uint8_t *d_reverse, const uint32_t *d_cigar, const uint64_t *d_cigar_off,
+                               uint32_t n_reads, int32_t *d_gene, uint8_t *d_status, uint64_t counts[3], uint64_t *bad, uint32_t n_cus,
+                               unsigned long long *h_pinned, hipStream_t s);
+
 // ---- molecules and reads per (column, row) pair (umihip_count.hip: umi_count_matrix) ----
 // h_off (pinned): the m + 1 offsets of the m >= 1 non-empty buckets; h_idx (pinned, null: nothing was left out):
 // their numbers in d_row / d_col.  The outputs take the triplets sorted by column, then row (capacity m);

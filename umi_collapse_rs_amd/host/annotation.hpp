@@ -33,8 +33,34 @@
 // such attribute, an empty value, or a value with a byte outside 0x21..0x7e or a ; or , (the bytes --per-gene
 // reserves); a file without a taken line.  Everything --per-gene refuses stays refused.
 //
-// Not built: transcript-level containment (STARsolo's Gene: a read inside one transcript's exons), --paired,
-// fractional assignment of a read among several genes, a minimum overlap above 1.
+// Transcript-level containment (STARsolo's Gene: a read inside one transcript's exons) is --gene-rule transcript,
+// below.  Not built: --paired, fractional assignment of a read among several genes, a minimum overlap above 1.
+//
+// --gene-rule overlap|transcript (with --gene-annotation; default overlap; tests/transcript_model.py defines transcript):
+// how a read gets its gene from the file.  overlap: the rule above; the run is the run without the flag, byte for byte.
+// transcript (STARsolo's default feature Gene, Cell Ranger's transcriptome-compatible reads, velocyto's models): a read
+// belongs to a gene when it fits one of that gene's transcripts.  A taken line's transcript is the value of
+// --annotation-transcript-attribute (default transcript_id) in column 9; a transcript's identity is (gene, that value,
+// reference, strand as written), so an id that recurs on chrX and chrY, as in older GENCODE PAR entries, is two
+// transcripts.  A transcript's lines are taken in ascending order whatever order the file has them in (minus-strand
+// GTFs list them descending), and lines that overlap or abut are united: exons x_1 < ... < x_n, a base or more between
+// neighbours.  The read's blocks b_1 .. b_m are the rule's above (a zero-length N closes a block too; empty blocks are
+// left out).  The read fits the transcript when the transcript is on its reference and on an admissible strand
+// (--gene-strand's rule; a . transcript always), m >= 1, and there is a j with b_i inside x_{j+i-1} for every i, and for
+// every i < m the block ends where its exon ends and the next block starts where the next exon starts.  A D never
+// splits a block, so a deletion across an intron fits nothing; a read with more blocks than the transcript has exons
+// left does not fit it; a block before 0 or beyond 2^31 - 1 lies in nothing.  G: the genes with a transcript the read
+// fits.  One gene: the read is that gene's.  None: "Number of reads outside every gene".  Two or more: "Number of reads
+// assigned to several genes".  Two fitting transcripts of one gene are one gene.  G is a subset of the overlap rule's
+// genes: a read that hangs one base into an exon from an intron is dropped here and counted there, and a read that fits
+// a transcript of gene A and grazes an exon of an overlapping gene B is A's here and "several" there.  The one call is
+// umi_assign_genes_transcripts in umi_assign_genes' place; everything behind the gene's id is --per-gene's, unchanged.
+// The summary gains, behind "Number of annotation lines on unknown references": "Gene rule: transcript" and "Number of
+// transcripts" (those with a line on the BAM's references).  Refused with status 101 before the GPU is woken: the flag
+// without --gene-annotation; a value other than overlap, transcript; the flag given twice with different values;
+// --annotation-transcript-attribute without --gene-rule transcript; on a taken line no such attribute, an empty value,
+// or a value with a byte outside 0x21..0x7e or a ; or , ; --gene-rule transcript with --gene-introns exon-first|all or
+// with --velocity.  Not built: a gene-body tier and read classes by transcript model (those two combinations), --paired.
 //
 // --gene-introns off|exon-first|all (with --gene-annotation; default off; tests/intron_model.py defines it): reads in
 // a gene's introns count too, as Cell Ranger 7 counts them by default and as single-nucleus runs need.  A gene's body:
@@ -57,7 +83,8 @@
 // --velocity (with --gene-annotation, --gene-introns exon-first|all and --count-matrix DIR; tests/velocity_model.py
 // defines it): the matrix's molecules in three layers -- spliced, unspliced, ambiguous -- what STARsolo's --soloFeatures
 // Velocyto, velocyto and alevin-fry's USA mode give scVelo and its kin.  The rule is at gene level and in exact integers;
-// it is NOT velocyto's or STARsolo's transcript-model rule, for this program keeps no transcript models.  A read's
+// it is NOT velocyto's or STARsolo's transcript-model rule: the transcript models that --gene-rule transcript keeps decide a
+// read's gene, not yet its class.  A read's
 // gene, status and tier are --gene-introns', unchanged.  The class of an assigned read with gene g: its blocks are cut
 // to [0, 2^31) and the empty ones left out; the cover of a stretch is the number of its bases in one of g's taken lines
 // on the read's reference and an admissible strand.  Assigned by an intron: intronic.  By an exon: where the blocks are
@@ -132,7 +159,7 @@ void read_annotation(Cli &args)
     }
     Cli::Annotation &an = args.annotation;
     std::unordered_map<std::string, uint32_t> ref_of;
-    std::unordered_map<std::string, int32_t> gene_of;
+    std::unordered_map<std::string, int32_t> gene_of, transcript_of;
     const std::string_view all((const char *)text.data(), text.size());
     size_t line_no = 0;
     for (size_t p = 0; p < all.size();) {
@@ -184,7 +211,21 @@ void read_annotation(Cli &args)
         an.end.push_back((int32_t)se[1]);
         an.strand.push_back((uint8_t)col[6][0]);
         an.gene.push_back(g.first->second);
+        if (!args.gene_rule_transcript) continue;
+        // the line's transcript: (gene, the attribute's value, reference, strand as written)
+        const std::string &ta = args.annotation_transcript_attribute;
+        std::string_view tv;
+        if (!gtf_attribute(col[8], ta, tv)) die(where + "no attribute " + ta);
+        if (tv.empty()) die(where + "the attribute " + ta + " is empty");
+        for (const char ch : tv)
+            if ((uint8_t)ch < 0x21 || (uint8_t)ch > 0x7e || ch == ';' || ch == ',')
+                die(where + "the attribute " + ta + " holds a byte that a transcript's name cannot: " + std::to_string((unsigned)(uint8_t)ch));
+        std::string key = std::to_string(g.first->second) + '\t' + std::to_string(r.first->second) + '\t' + col[6][0] + '\t';
+        key.append(tv);
+        const auto t = transcript_of.emplace(std::move(key), (int32_t)transcript_of.size());
+        an.transcript.push_back(t.first->second);
     }
+    an.n_transcripts = (uint32_t)transcript_of.size();
     if (an.gene.empty())
         die("the gene annotation " + args.gene_annotation + " holds no line of feature type " + args.annotation_feature);
 }

@@ -75,10 +75,14 @@
 // file's reader and every refusal; the flags and the file are looked at here, in validate(), before the GPU is woken).
 // --gene-introns off|exon-first|all (with --gene-annotation) [off]: reads in a gene's introns count too, by
 // umi_assign_genes_introns (annotation.hpp has the rule, the summary lines and the refusals).
+// --gene-rule overlap|transcript [--annotation-transcript-attribute A] (with --gene-annotation) [overlap]: transcript: a
+// read's gene is the one gene with a transcript the read fits, by umi_assign_genes_transcripts (annotation.hpp has the
+// rule, the summary lines, the refusals and what is not built).
 // --velocity (with --per-gene --gene-annotation FILE --gene-introns exon-first|all --count-matrix DIR; tests/velocity_model.py
 // defines it): the molecules of the matrix in three layers, spliced, unspliced and ambiguous, as STARsolo's --soloFeatures
-// Velocyto, velocyto and alevin-fry's USA mode write them -- but by a gene-level rule, not by their transcript models,
-// which this project does not keep (annotation.hpp has the rule, the files, the summary lines and what is not built).
+// Velocyto, velocyto and alevin-fry's USA mode write them -- but by a gene-level rule, not by their transcript models
+// (those of --gene-rule transcript decide a read's gene, not yet its class; annotation.hpp has the rule, the files, the
+// summary lines and what is not built).
 // Refused with status 101 before the GPU is woken: --velocity without --count-matrix, without --gene-annotation, with
 // --gene-introns absent or off, or with --stage gpu (a read's entry is kept by the host staging alone).
 #pragma once
@@ -166,12 +170,18 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     bool gene_introns_given = false;
     int gene_introns_mode = UMI_INTRONS_OFF; // as UMI_INTRONS_* (filled in by validate())
     bool velocity = false; // --velocity: spliced, unspliced and ambiguous matrices beside --count-matrix's
+    // --gene-rule overlap|transcript (annotation.hpp); overlap and no flag are the same run
+    std::string gene_rule = "overlap", annotation_transcript_attribute = "transcript_id";
+    bool gene_rule_given = false, annotation_transcript_attribute_given = false;
+    bool gene_rule_transcript = false; // ... transcript (filled in by validate())
     struct Annotation { // the file's taken lines (filled in by validate(): read_annotation)
         std::vector<std::string> refs;      // the reference names of column 1, in order of first appearance
         std::vector<uint32_t> ref_name;     // per taken line: its reference, an index into refs
         std::vector<int32_t> start, end;    // ... half-open, 0-based
         std::vector<uint8_t> strand;        // ... + - or .
         std::vector<int32_t> gene;          // ... an index into gene_ids
+        std::vector<int32_t> transcript;    // ... its transcript, numbered by first appearance (--gene-rule transcript alone)
+        uint32_t n_transcripts = 0;
         std::vector<std::string> gene_ids;  // the genes in order of first appearance
         std::vector<std::string> gene_names; // ... and the gene_name of each one's first taken line (empty: none)
     } annotation;
@@ -284,6 +294,13 @@ void usage()
               "                           read that hits no exon goes to the one gene whose body it shares a base with\n"
               "                           (STARsolo's GeneFull_ExonOverIntron, Cell Ranger 7's default); all: every read\n"
               "                           goes by the bodies alone (GeneFull); no body or several: dropped\n"
+              "      --gene-rule <R>      overlap or transcript [default: overlap], with --gene-annotation.  transcript: a read\n"
+              "                           belongs to a gene when it fits one of the gene's transcripts: every block inside\n"
+              "                           an exon, every N from one exon's end to the next one's start (STARsolo's Gene,\n"
+              "                           Cell Ranger's transcriptome-compatible reads); no such gene or several: dropped\n"
+              "                           (not with --gene-introns exon-first|all, --velocity)\n"
+              "      --annotation-transcript-attribute <A> with --gene-rule transcript: the attribute of column 9 that names\n"
+              "                           a line's transcript [default: transcript_id]\n"
               "      --velocity           with --gene-annotation, --gene-introns exon-first|all and --count-matrix: write the\n"
               "                           matrix's molecules in three layers to DIR/velocity (spliced.mtx, unspliced.mtx,\n"
               "                           ambiguous.mtx, features.tsv, barcodes.tsv) by a gene-level rule: a molecule with a\n"
@@ -412,6 +429,14 @@ Cli parse(int argc, char **argv)
             c.gene_introns_given = true;
         }
         else if (a == "--velocity") c.velocity = true;
+        else if (a == "--gene-rule" || a == "--annotation-transcript-attribute") {
+            const std::string v = need(i);
+            std::string &value = a == "--gene-rule" ? c.gene_rule : c.annotation_transcript_attribute;
+            bool &given = a == "--gene-rule" ? c.gene_rule_given : c.annotation_transcript_attribute_given;
+            if (given && value != v) die(a + " given twice with different values: '" + value + "' and '" + v + "'");
+            value = v;
+            given = true;
+        }
         else if (a == "--count-matrix") c.count_matrix = need(i);
         else if (a == "--output-stats") c.output_stats = need(i);
         else if (a == "--output-stats-seed") {
@@ -629,11 +654,23 @@ bool validate(Cli &args)
                               std::make_pair(args.gene_strand_given, "--gene-strand")})
             if (f.first) die(std::string(f.second) + " goes with --gene-annotation only");
         if (args.gene_introns_given) die("--gene-introns goes with --gene-annotation only");
+        if (args.gene_rule_given) die("--gene-rule goes with --gene-annotation only");
+        if (args.annotation_transcript_attribute_given) die("--annotation-transcript-attribute goes with --gene-rule transcript only");
     } else {
+        if (args.gene_rule != "overlap" && args.gene_rule != "transcript") die("--gene-rule wants overlap or transcript: '" + args.gene_rule + "'");
+        args.gene_rule_transcript = args.gene_rule == "transcript";
+        if (args.annotation_transcript_attribute_given && !args.gene_rule_transcript)
+            die("--annotation-transcript-attribute goes with --gene-rule transcript only");
+        if (args.annotation_transcript_attribute.empty()) die("--annotation-transcript-attribute wants an attribute name");
         if (args.gene_introns == "off") args.gene_introns_mode = UMI_INTRONS_OFF;
         else if (args.gene_introns == "exon-first") args.gene_introns_mode = UMI_INTRONS_EXON_FIRST;
         else if (args.gene_introns == "all") args.gene_introns_mode = UMI_INTRONS_ALL;
         else die("--gene-introns wants off, exon-first or all: '" + args.gene_introns + "'");
+        if (args.gene_rule_transcript && args.gene_introns_mode != UMI_INTRONS_OFF)
+            die("--gene-rule transcript does not go with --gene-introns " + args.gene_introns +
+                ". Not built: a gene-body tier beside the transcript models");
+        if (args.gene_rule_transcript && args.velocity)
+            die("--gene-rule transcript does not go with --velocity. Not built: read classes by transcript model");
         if (!args.per_gene) die("--gene-annotation goes with --per-gene only");
         if (args.gene_tag_given) die("--gene-annotation does not go with --gene-tag (the gene comes from the file, not from a tag)");
         if (!args.dump_staging.empty()) die("--gene-annotation does not go with --dump-staging (which stops before the GPU)");

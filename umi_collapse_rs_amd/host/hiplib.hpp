@@ -27,6 +27,7 @@
 // --gene-annotation FILE: likewise umi_assign_genes.
 //
 // --gene-introns exon-first|all: likewise umi_assign_genes_introns, in umi_assign_genes' place.
+// --gene-rule transcript: likewise umi_assign_genes_transcripts, in umi_assign_genes' place.
 //
 // --velocity: likewise umi_assign_genes_classes, in umi_assign_genes_introns' place, and umi_velocity_matrix.
 #pragma once
@@ -106,6 +107,9 @@ struct HipLib {
     // --gene-annotation: likewise
     bool want_genes = false;
     decltype(&umi_assign_genes) assign_genes = nullptr;
+    // --gene-rule transcript: likewise, in its place
+    bool want_transcripts = false;
+    decltype(&umi_assign_genes_transcripts) assign_genes_transcripts = nullptr;
     // --gene-introns exon-first|all: likewise, in its place
     bool want_introns = false;
     decltype(&umi_assign_genes_introns) assign_genes_introns = nullptr;
@@ -124,7 +128,8 @@ struct HipLib {
           want_barcodes_multi(!args.cell_list.empty() && args.cell_wl_multi),
           want_count(!args.count_matrix.empty()), want_stats(!args.output_stats.empty()),
           want_multigene(args.filter_multigene), want_cells(args.cell_filter_given),
-          want_genes(args.gene_annotation_given && args.gene_introns_mode == UMI_INTRONS_OFF),
+          want_genes(args.gene_annotation_given && args.gene_introns_mode == UMI_INTRONS_OFF && !args.gene_rule_transcript),
+          want_transcripts(args.gene_annotation_given && args.gene_rule_transcript),
           want_introns(args.gene_annotation_given && args.gene_introns_mode != UMI_INTRONS_OFF && !args.velocity),
           want_velocity(args.velocity)
     {
@@ -172,6 +177,7 @@ struct HipLib {
         if (want_multigene) filter_multigene = (decltype(filter_multigene))sym("umi_filter_multigene");
         if (want_cells) call_cells = (decltype(call_cells))sym("umi_call_cells");
         if (want_genes) assign_genes = (decltype(assign_genes))sym("umi_assign_genes");
+        if (want_transcripts) assign_genes_transcripts = (decltype(assign_genes_transcripts))sym("umi_assign_genes_transcripts");
         if (want_introns) assign_genes_introns = (decltype(assign_genes_introns))sym("umi_assign_genes_introns");
         if (want_velocity) {
             assign_genes_classes = (decltype(assign_genes_classes))sym("umi_assign_genes_classes");

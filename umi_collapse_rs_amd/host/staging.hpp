@@ -378,6 +378,7 @@ struct Summary {
     size_t total_read_count = 0, unmapped = 0, unpaired = 0, chimeric = 0, no_umi_tag = 0, no_cell = 0;
     size_t no_gene = 0, several_genes = 0, n_genes = 0; // --per-gene
     size_t annotation_genes = 0, annotation_features = 0, annotation_unknown = 0; // --gene-annotation: on the file's references
+    size_t annotation_transcripts = 0; // --gene-rule transcript: the transcripts of the lines on the BAM's references
     uint64_t by_exon = 0, by_intron = 0; // --gene-introns exon-first|all: the call's reads assigned by either tier
     uint64_t class_counts[5] = {0, 0, 0, 0, 0}; // --velocity: the call's reads by class (UMI_READ_CLASS_*)
     uint64_t layers[3] = {0, 0, 0};             // ... and the molecules: spliced, unspliced, ambiguous
@@ -407,6 +408,10 @@ struct Summary {
                 std::fprintf(stderr, "Gene annotation: %zu genes, %zu features\n", annotation_genes, annotation_features);
                 std::fprintf(stderr, "Gene strand: %s\n", args.gene_strand.c_str());
                 std::fprintf(stderr, "Number of annotation lines on unknown references: %zu\n", annotation_unknown);
+                if (args.gene_rule_transcript) {
+                    std::fprintf(stderr, "Gene rule: transcript\n");
+                    std::fprintf(stderr, "Number of transcripts: %zu\n", annotation_transcripts);
+                }
                 if (args.gene_introns_mode != UMI_INTRONS_OFF) {
                     std::fprintf(stderr, "Gene introns: %s\n", args.gene_introns.c_str());
                     std::fprintf(stderr, "Number of reads assigned by an exon: %llu\n", (unsigned long long)by_exon);

@@ -90,6 +90,7 @@
 // --gene-annotation FILE (with --per-gene; annotation.hpp has the flags' definition, the file's reader and the
 // refusals): one call to umi_assign_genes over every mapped read, after the file is read and before the per-read
 // pass, which takes its verdict in the gene tag's place (assign_genes() below).
+// --gene-rule transcript (with --gene-annotation; annotation.hpp): that one call is umi_assign_genes_transcripts.
 // --gene-introns exon-first|all (with --gene-annotation; annotation.hpp): that one call is umi_assign_genes_introns,
 // whose gene and status are used alike; its counts by tier go into the summary, the tier of a read goes nowhere.
 // --velocity (with --gene-introns exon-first|all and --count-matrix DIR; annotation.hpp has the rule and the files): that
@@ -345,6 +346,7 @@ struct OnePass {
         }
         // the lines on known references, their genes numbered anew by first appearance among them
         std::vector<int32_t> x_ref, x_start, x_end, x_gene, new_gene(an.gene_ids.size(), -1);
+        std::vector<int32_t> x_tr, new_tr(an.n_transcripts, -1); // --gene-rule transcript: the lines' transcripts, numbered likewise
         std::vector<uint8_t> x_strand;
         for (size_t i = 0; i < an.gene.size(); i++) {
             const int32_t tid = tid_of_ref[an.ref_name[i]];
@@ -364,6 +366,11 @@ struct OnePass {
             x_end.push_back(an.end[i]);
             x_strand.push_back(an.strand[i]);
             x_gene.push_back(g);
+            if (args.gene_rule_transcript) {
+                int32_t &t = new_tr[(size_t)an.transcript[i]];
+                if (t < 0) t = (int32_t)sum.annotation_transcripts++;
+                x_tr.push_back(t);
+            }
         }
         sum.annotation_genes = annotation_ids.size();
         sum.annotation_features = x_gene.size();
@@ -419,6 +426,14 @@ struct OnePass {
                 die(lib.last_error());
             sum.by_exon = by_tier[0];
             sum.by_intron = by_tier[1];
+        } else if (nc && args.gene_rule_transcript) { // --gene-rule transcript: the transcript-model call in the plain one's place
+            need_ctx();
+            if (!lib.assign_genes_transcripts) die("libumihip.so lacks umi_assign_genes_transcripts");
+            if (lib.assign_genes_transcripts(ctx, x_ref.data(), x_start.data(), x_end.data(), x_strand.data(), x_gene.data(), x_tr.data(),
+                                             x_gene.size(), (uint32_t)annotation_ids.size(), (uint32_t)sum.annotation_transcripts,
+                                             args.gene_strand_mode, r_ref.data(), r_pos.data(), r_rev.data(), words.data(), c_off.data(),
+                                             nc, r_gene.data(), r_status.data(), counts) != UMI_OK)
+                die(lib.last_error());
         } else if (nc) {
             need_ctx();
             if (!lib.assign_genes) die("libumihip.so lacks umi_assign_genes");
