@@ -137,6 +137,11 @@ const char *umi_last_error(void);
  *                    to back -- is decided as one unit out of LDS by a multi-wave block, so that the pairs that differ
  *                    in one of those g bases are united there instead of by the pair kernel's global unions (0: the
  *                    sub-buckets one by one); same result and statistics
+ *   "seg_super_coarse" 0/1 (default 1): where "seg_super" and "seg_lds" apply, the counting sort files a part-0 entry
+ *                    under the first sub-bucket of its run instead of its own -- nothing reads the order inside a
+ *                    run, and a (block, run) costs one atomic and one stretch of stores where the 4^g sub-buckets
+ *                    cost one each; a run above "seg_super_cap" goes through the pair kernel as one sub-bucket, a
+ *                    hit kept only inside a sub-bucket (0: every entry under its own); same result and statistics
  *   "seg_super_bases" 0..4 (default 0): g; 0 = the largest for which the other bases number at most 8 and the expected
  *                    run n / 4^(bin bases - g) lies between "seg_super_min" and 3/4 of "seg_super_cap", another
  *                    value = that g where those conditions hold (else none)

@@ -196,6 +196,9 @@ int umi_ctx_set_option(umi_ctx *ctx, const char *name, int64_t value)
     } else if (!strcmp(name, "seg_super")) {
         if (value != 0 && value != 1) return fail(UMI_ERR_ARG, "seg_super must be 0 or 1");
         ctx->seg_super = value != 0;
+    } else if (!strcmp(name, "seg_super_coarse")) {
+        if (value != 0 && value != 1) return fail(UMI_ERR_ARG, "seg_super_coarse must be 0 or 1");
+        ctx->seg_super_coarse = value != 0;
     } else if (!strcmp(name, "seg_super_bases")) {
         if (value < 0 || value > SEG_SUPER_MAX_BASES) return fail(UMI_ERR_ARG, "seg_super_bases must be in 0..%d", SEG_SUPER_MAX_BASES);
         ctx->seg_super_bases = (int)value;

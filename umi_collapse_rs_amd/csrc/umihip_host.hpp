@@ -223,6 +223,8 @@ struct umi_ctx {
                              // SEG_PROBE_MAX_REST bases lie outside the bins (0: the tile walk)
     uint32_t seg_probe_min = umihip::SEG_PROBE_MIN; // smallest sub-bucket decided by lookups
     bool seg_super = true;   // k = 1 without N: runs of 4^g adjacent part-0 bins decided as one unit in LDS (seg_super_kernel)
+    bool seg_super_coarse = true; // ... and the counting sort files a part-0 entry of such a segment under its run's first
+                                  // bin, not its own (SegArgs::super_coarse; 0 for A/B runs and as the tests' reference)
     int seg_super_bases = 0; // ... g (0: the planner's choice, choose_super_bases)
     uint32_t seg_super_cap = umihip::SEG_SUPER_CAP; // largest super-bin that kernel takes (LDS: 16 bytes per entry + 16 KB)
     uint32_t seg_super_min = umihip::SEG_SUPER_MIN; // smallest expected super-bin the path is planned for

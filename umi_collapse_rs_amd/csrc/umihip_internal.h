@@ -292,6 +292,15 @@ struct SegArgs {
     uint32_t super_cap;
     const SegSuper *supers;
     uint32_t n_supers;
+    // Coarse filing (LDS counting sort only): in a segment with super-bins the count and scatter kernels file a part-0
+    // entry under the first bin of its run -- nobody reads the order of a run's entries by fine bin: seg_super_kernel
+    // places a taken super-bin's records by rest-code, and a run above the cap is one sub-bucket for the tiles, whose
+    // drain keeps a hit only if the two keys agree on all of mask[0].  The run's other bins count 0, so bin_start of
+    // a run's first bin and of the next run's are what they were.  0: every entry under its own bin.
+    uint32_t super_coarse;
+    // ... and the pairs inside the fine bins of such a segment's part 0 (CNT_SEG_PAIRS), which the scan can no longer
+    // see, are counted by seg_super_kernel (0 in the launch of a second attempt: they are counted once)
+    uint32_t super_count_pairs;
 #ifdef UMIHIP_DEV
     // development build: where seg_super_kernel's blocks add up the time they spend in each of their phases
     // ([blocks][SEG_SUPER_PHASES] ticks of the 100 MHz clock, zeroed by the host; null: no stamps)
@@ -299,8 +308,9 @@ struct SegArgs {
 #endif
 };
 // seg_super_kernel's phases (development build's stamps): records in, map built, ranks and placement, bit tests,
-// the hit rounds (decide and the unions), pointer jumping, atomicMin, label stores
-constexpr int SEG_SUPER_PHASES = 8;
+// the hit rounds (decide and the unions), pointer jumping, atomicMin, label stores, the pairs inside the fine bins
+// counted (coarse filing)
+constexpr int SEG_SUPER_PHASES = 9;
 // the scan's word of a segment with super-bins, behind the chunks' status words: left 0 where every super-bin of the
 // segment is taken (none lies above the cap), so that a part-1 hit inside a super-bin is seg_super_kernel's for sure
 UMIHIP_HD inline uint32_t seg_scan_flag_word(uint32_t n_chunks, uint32_t seg) { return 1u + n_chunks + seg; }

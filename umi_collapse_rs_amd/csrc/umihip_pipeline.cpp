@@ -203,6 +203,7 @@ class Pipeline {
     uint32_t priv_blocks_for_collapse = 0; // blocks of the segment index's local and pair kernels whose private edge
                                            // slots the collapse's flatten launch appends to the list (0: appended already)
     uint64_t seg_local_bins = 0; // part-0 bins of the call's segments (the local kernel's grid at most)
+    bool super_pairs_counted = false; // seg_super_kernel has run with SegArgs::super_count_pairs in this call
     umi_stats st;
     unsigned long long *d_cnt = nullptr;
     size_t n_tasks = 0;              // tile tasks of the pair kernels (fused buckets excluded)
@@ -500,6 +501,8 @@ class Pipeline {
                 seg.n_blocks = (uint32_t)pl.seg_blocks.size();
                 seg.lds_bins = pl.seg_max_bins;
                 seg.parts_per_pass = std::max(1u, std::min({4u, (uint32_t)pl.seg_parts, SEG_LDS_BINS / std::max(1u, pl.seg_max_bins)}));
+                // (the per-entry path of the counting sort files by fine bin, prep_kernel's histogram with it)
+                seg.super_coarse = super_on && ctx->seg_super_coarse ? 1u : 0u;
             }
             if (!zero_behind_control) HIP_TRY(hipMemsetAsync(seg.bin_cnt, 0, zero_bytes, s));
         }
@@ -905,6 +908,9 @@ class Pipeline {
             if ((seg.local_cap || seg.super_cap) && !seg.uf_parent) // (the scan has left the local bins without tasks)
                 return fail(UMI_ERR_HIP, "internal: part-0 sub-buckets planned for the local kernel without unions");
             SegArgs super_seg = seg;
+            // (the scan ran once: a second attempt's launch must not count the fine bins' pairs again)
+            super_seg.super_count_pairs = seg.super_coarse && !super_pairs_counted ? 1u : 0u;
+            super_pairs_counted = super_pairs_counted || super_blocks != 0;
             super_seg.priv_edges += (size_t)local_blocks * SEG_PRIV_CAP;
             super_seg.priv_cnt += local_blocks;
             if (super_seg.priv_stat) super_seg.priv_stat += local_blocks;
@@ -937,7 +943,8 @@ class Pipeline {
                 HIP_TRY(e2);
                 if (FILE *f = fopen(phase_file, "a")) {
                     static const char *const names[SEG_SUPER_PHASES] = {"records in", "map built", "ranks and placement",
-                        "bit tests, pushes (w0)", "drains", "pointer jumping", "atomicMin", "label stores"};
+                        "bit tests, pushes (w0)", "drains", "pointer jumping", "atomicMin", "label stores",
+                        "fine-bin pairs counted"};
                     fprintf(f, "seg_super_kernel: %u blocks, us per block (100 MHz clock): phase, mean, max\n", super_blocks);
                     double sum_mean = 0;
                     for (int i = 0; i < SEG_SUPER_PHASES; i++) {

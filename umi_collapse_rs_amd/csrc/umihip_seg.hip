@@ -33,6 +33,8 @@ __device__ __forceinline__ bool local_bin(const SegArgs &g, uint32_t part, uint3
 __device__ __forceinline__ bool super_taken(const SegArgs &g, uint32_t n) { return n >= 2u && n <= g.super_cap; }
 // super-bin exponent of a segment in this call (wave-uniform)
 __device__ __forceinline__ uint32_t super_bases(const SegArgs &g, uint32_t seg) { return g.super_cap ? g.segs[seg].sup_g : 0u; }
+// ... if its part 0 is filed by super-bin (SegArgs::super_coarse), else 0: the bases a run's bins differ in
+__device__ __forceinline__ uint32_t coarse_bases(const SegArgs &g, uint32_t seg) { return g.super_coarse ? super_bases(g, seg) : 0u; }
 
 // Exclusive scan of the bin counts -> bin_start, the task list, the pair count: ONE launch, the
 // chunks chained by a decoupled look-back.  A block draws its chunk from a ticket counter (so that
@@ -160,7 +162,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void seg_scan_kernel(SegArgs g, unsig
                     if (ti < g.task_cap) g.tasks[ti] = SegTask{row0, off.x + c[q], row0 + 1u + 64u * sp, where};
             }
             const uint32_t n_bin_tasks = ti - off.y;
-            pairs += (unsigned long long)c[q] * (c[q] ? c[q] - 1 : 0) / 2;
+            // (filed by super-bin: a bin's count is its whole run's, the pairs inside the fine bins are seg_super_kernel's to count)
+            if (!(sg && g.super_coarse)) pairs += (unsigned long long)c[q] * (c[q] ? c[q] - 1 : 0) / 2;
             off.x += c[q];
             off.y += n_bin_tasks;
         }
@@ -245,9 +248,12 @@ struct SegPass {
     int b0[SEG_PASS_PARTS], nb[SEG_PASS_PARTS];
     uint32_t nbins[SEG_PASS_PARTS], bin_off[SEG_PASS_PARTS];
     uint32_t lds_off[SEG_PASS_PARTS]; // first counter of the part in hist[]
+    uint32_t sh[SEG_PASS_PARTS];   // low bits of the bin code a counter leaves out: 2 * cg for part 0, else 0
     uint32_t total;                // counters of the pass
 };
-__device__ __forceinline__ SegPass seg_pass_of(const SegDesc *__restrict__ sd, int j0, int n_parts, int per_pass)
+// cg (coarse_bases): part 0 is filed by runs of 4^cg bins -- its counters are the runs, dense in LDS (4^cg words
+// apart they would share a handful of banks), and stand for the first bin of their run
+__device__ __forceinline__ SegPass seg_pass_of(const SegDesc *__restrict__ sd, int j0, int n_parts, int per_pass, uint32_t cg)
 {
     SegPass ps;
     ps.np = min(per_pass, n_parts - j0);
@@ -257,7 +263,8 @@ __device__ __forceinline__ SegPass seg_pass_of(const SegDesc *__restrict__ sd, i
         const bool on = q < ps.np;
         ps.b0[q] = on ? sd->b0[j0 + q] : 0;
         ps.nb[q] = on ? sd->nb[j0 + q] : 0;
-        ps.nbins[q] = on ? 1u << (2 * ps.nb[q]) : 0u;
+        ps.sh[q] = on && j0 + q == 0 ? 2u * cg : 0u;
+        ps.nbins[q] = on ? (1u << (2 * ps.nb[q])) >> ps.sh[q] : 0u;
         ps.bin_off[q] = on ? sd->bin_off[j0 + q] : 0u;
         ps.lds_off[q] = ps.total;
         ps.total += ps.nbins[q];
@@ -270,7 +277,7 @@ __device__ __forceinline__ uint32_t seg_pass_global_bin(const SegPass &ps, uint3
     uint32_t gb = 0;
 #pragma unroll
     for (int q = 0; q < SEG_PASS_PARTS; q++)
-        if (q < ps.np && c >= ps.lds_off[q] && c < ps.lds_off[q] + ps.nbins[q]) gb = ps.bin_off[q] + (c - ps.lds_off[q]);
+        if (q < ps.np && c >= ps.lds_off[q] && c < ps.lds_off[q] + ps.nbins[q]) gb = ps.bin_off[q] + ((c - ps.lds_off[q]) << ps.sh[q]);
     return gb;
 }
 
@@ -294,7 +301,7 @@ __device__ __forceinline__ void seg_block_histogram(const SegBlock &blk, const K
             if (i0 + (uint32_t)q * SEG_BLOCK_THREADS < blk.end) {
 #pragma unroll
                 for (int j = 0; j < SEG_PASS_PARTS; j++)
-                    if (j < ps.np) atomicAdd(&hist[ps.lds_off[j] + seg_part_bits(key[q], ps.b0[j], ps.nb[j])], 1u);
+                    if (j < ps.np) atomicAdd(&hist[ps.lds_off[j] + (seg_part_bits(key[q], ps.b0[j], ps.nb[j]) >> ps.sh[j])], 1u);
             }
     }
     __syncthreads();
@@ -316,6 +323,7 @@ __global__ __launch_bounds__(SEG_BLOCK_THREADS) void seg_count_lds_kernel(SegArg
     extern __shared__ uint32_t hist[];
     const SegBlock blk = g.blocks[blockIdx.x];
     const SegDesc *__restrict__ sd = g.segs + blk.seg;
+    const uint32_t cg = coarse_bases(g, blk.seg); // (block-uniform)
     if (g.prep_keys) {
         // the entry kernel's work for this block's entries (prep_kernel, umihip_kernels.hip): filter
         // key, threshold (directional.rs:38), label, and the contract check -- freq >= 1, no N code
@@ -347,7 +355,7 @@ __global__ __launch_bounds__(SEG_BLOCK_THREADS) void seg_count_lds_kernel(SegArg
         __syncthreads(); // the block's filter keys are read back below
     }
     for (int j0 = 0; j0 < g.n_parts; j0 += (int)g.parts_per_pass) {
-        const SegPass ps = seg_pass_of(sd, j0, g.n_parts, (int)g.parts_per_pass);
+        const SegPass ps = seg_pass_of(sd, j0, g.n_parts, (int)g.parts_per_pass, cg);
         seg_block_histogram(blk, fkey, ps, hist);
         for (uint32_t c = threadIdx.x; c < ps.total; c += SEG_BLOCK_THREADS) {
             const uint32_t cnt = hist[c];
@@ -365,9 +373,10 @@ __global__ __launch_bounds__(SEG_BLOCK_THREADS) void seg_scatter_lds_kernel(SegA
     extern __shared__ uint32_t hist[];
     const SegBlock blk = g.blocks[blockIdx.x];
     const SegDesc *__restrict__ sd = g.segs + blk.seg;
+    const uint32_t cg = coarse_bases(g, blk.seg); // (block-uniform)
     Rec *__restrict__ sub = (Rec *)g.sub_rec;
     for (int j0 = 0; j0 < g.n_parts; j0 += (int)g.parts_per_pass) {
-        const SegPass ps = seg_pass_of(sd, j0, g.n_parts, (int)g.parts_per_pass);
+        const SegPass ps = seg_pass_of(sd, j0, g.n_parts, (int)g.parts_per_pass, cg);
         seg_block_histogram(blk, fkey, ps, hist);
         // the block's run inside every bin it has entries for: the counter becomes its first position
         for (uint32_t c = threadIdx.x; c < ps.total; c += SEG_BLOCK_THREADS) {
@@ -398,7 +407,7 @@ __global__ __launch_bounds__(SEG_BLOCK_THREADS) void seg_scatter_lds_kernel(SegA
 #pragma unroll
                     for (int q = 0; q < B; q++)
                         pos[q] = i0 + (uint32_t)q * SEG_BLOCK_THREADS < blk.end
-                                     ? atomicAdd(&hist[ps.lds_off[j] + seg_part_bits(key[q], ps.b0[j], ps.nb[j])], 1u)
+                                     ? atomicAdd(&hist[ps.lds_off[j] + (seg_part_bits(key[q], ps.b0[j], ps.nb[j]) >> ps.sh[j])], 1u)
                                      : 0u;
 #pragma unroll
                     for (int q = 0; q < B; q++) {
@@ -692,6 +701,9 @@ __global__ __launch_bounds__(64) void seg_pair_kernel(PairArgs a, SegArgs g, flo
     // sup_tile: every super-bin of the segment is taken (the scan's word) and the tiles are bit-sliced -- the tile itself
     // leaves out the pairs that agree on these bases of the compare key, and the drain has nothing to ask (sup_bins 0)
     uint32_t sup_mask = 0, sup_bins = 0, sup_bin0 = 0, sup_tile = 0;
+    // tasks of part 0 of a segment filed by super-bin (a run above the cap, one sub-bucket of 4^g fine bins whose
+    // compare keys leave out all of the bin's bases): the part's own mask -- a hit is one only inside a fine bin
+    KeyT coarse_mask = KeyT(0);
     const bool sliced = a.k <= 3 && g.col_sliced != 0;
     uint32_t nq = 0; // queued hits (wave-uniform); the queue outlives a task
 
@@ -721,7 +733,7 @@ __global__ __launch_bounds__(64) void seg_pair_kernel(PairArgs a, SegArgs g, flo
                 uu[s] = uv[s] = 0;
                 if (!live[s]) continue;
                 const KeyT z = ra[s].key ^ cb[s].key;
-                bool ok = true;
+                bool ok = (z & coarse_mask) == KeyT(0); // (two fine bins of one run: no pair of this part)
 #pragma unroll
                 for (int p = 0; p < SEG_MAX_PARTS - 1; p++)
                     ok = ok && (dup_mask[p] == KeyT(0) || (z & dup_mask[p]) != KeyT(0));
@@ -840,6 +852,7 @@ __global__ __launch_bounds__(64) void seg_pair_kernel(PairArgs a, SegArgs g, flo
                 have_seg = seg;
                 have_part = my_part;
                 ck_bases = __builtin_amdgcn_readfirstlane(g.umi_len - (int)sd->nb[my_part]); // bases a compare key holds
+                coarse_mask = my_part == 0 && coarse_bases(g, seg) ? (KeyT)sd->mask[0] : KeyT(0);
                 const uint32_t sg = my_part != 0 ? super_bases(g, seg) : 0u;
                 sup_mask = sg ? ((1u << (2 * (sd->nb[0] - sg))) - 1u) << (2 * sg) : 0u;
                 sup_bins = sg ? 1u << (2 * sg) : 0u; // (0: no super-bins here)
@@ -1231,8 +1244,9 @@ __global__ __launch_bounds__(64) void seg_local_kernel(PairArgs a, SegArgs g, fl
 // back in the sub-bucket arrays: one super-bin.  A block that holds a whole super-bin in LDS decides every pair
 // that agrees on those shared bases -- a pair inside one of its bins and a pair that differs in one of the g low
 // bases, which would otherwise be part 1's to find and a global union's to join.  An entry is its rest-code (the
-// filter key's 2 bits per base with the shared bases squeezed out, at most SEG_SUPER_MAX_REST bases), the
-// super-bin a bitmap of 4^rest bits; the rest is seg_local_kernel's lookup path with many waves: records read
+// filter key's 2 bits per base without the shared bases, at most SEG_SUPER_MAX_REST bases: the bases outside the
+// bins below, the g low bases of the bin code -- the fine bin -- on top, so that the ranks of 4^g codes give the
+// entries per fine bin), the super-bin a bitmap of 4^rest bits; the rest is seg_local_kernel's lookup path with many waves: records read
 // once and kept in registers until the rank of their code is known, 3 * rest single-bit tests per entry for the
 // partners with the larger code, the hits queued per wave and decided 64 at a time (SUPER_HITQ below), symmetric
 // pairs united in an LDS forest over positions (lds_union_halving: hooks
@@ -1251,6 +1265,7 @@ constexpr int SUPER_RPT = 8; // records a thread keeps in registers: a block tak
 constexpr uint32_t SUPER_DRAIN_AT = 64;
 constexpr uint32_t SUPER_HITQ = SUPER_DRAIN_AT + 64; // words per wave
 static_assert(SUPER_DRAIN_AT - 1 + 64 <= SUPER_HITQ, "the fullest queue a push can leave");
+constexpr uint32_t SUPER_FINE = 1u << (2 * SEG_SUPER_MAX_BASES); // fine bins of the largest run (static LDS of the kernel)
 static_assert(SEG_SUPER_MAX_CAP <= (1u << 13) && 2 * SEG_SUPER_MAX_REST + 13 <= 32, "a position and a rest-code in one word");
 
 #ifdef UMIHIP_DEV
@@ -1366,14 +1381,74 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
         }
     };
 
+    // Filed by super-bin (SegArgs::super_count_pairs): the pairs inside the run's fine bins, which the scan counted when
+    // each was a bin of its own.  The fine bin of a record is the low 2g bits of its filter key.  A taken super-bin
+    // reads the counts off the ranks (fine_pairs_ranked below); a run above the cap, which is only passed through
+    // here, and a super-bin with a key twice are counted entry by entry.  fine[]: a counter per
+    // fine bin, SUPER_FINE >> 2g copies of it next to each other (2g = 2, 4, 6, 8: 64, 16, 4, 1) -- a lane adds to the
+    // copy of its number, so that a wave's adds spread over the banks -- then thread t of the first SUPER_FINE takes
+    // word t, the copies of a bin are summed across 1..64 adjacent lanes, c (c - 1) / 2 each, one LDS add per wave.
+    // The block's sum goes to the counter once, as the block's last access: a global atomic issued here would be
+    // waited for at the next barrier (its fence), and all blocks' adds reach the one word together -- served at
+    // ~90 per microsecond, that wait was 1.4 us per block with one add per super-bin and 4.3 us with one per wave.
+    __shared__ uint32_t fine[SUPER_FINE];
+    __shared__ unsigned long long fine_pairs; // (cleared here; first added to behind the barriers of the first super-bin)
+    if (tid == 0) fine_pairs = 0ull;
+    static_assert(SUPER_FINE == 256 && NT >= (int)SUPER_FINE, "at most 64 copies: inside a wave");
+    auto fine_add = [&](uint32_t key, uint32_t lo_bits) {
+        const uint32_t cb = 8u - lo_bits; // log2 of the copies
+        atomicAdd(&fine[((key & ((1u << lo_bits) - 1u)) << cb) | ((uint32_t)lane & ((1u << cb) - 1u))], 1u);
+    };
+    auto fine_pairs_out = [&](uint32_t lo_bits) { // (behind a barrier that has the adds)
+        if (tid >= SUPER_FINE) return; // (whole waves)
+        const uint32_t cb = 8u - lo_bits;
+        uint32_t n = fine[tid];
+#pragma unroll
+        for (uint32_t s = 0; s < 6; s++) {
+            const uint32_t other = __shfl_xor(n, 1 << s);
+            if (s < cb) n += other;
+        }
+        unsigned long long pairs = (tid & ((1u << cb) - 1u)) == 0u ? (unsigned long long)n * (n ? n - 1u : 0u) / 2ull : 0ull;
+        for (int off = 32; off > 0; off >>= 1) pairs += __shfl_down(pairs, off);
+        if (lane == 0 && pairs) atomicAdd(&fine_pairs, pairs);
+    };
+    // ... without a counter where no key stands twice: the fine bin is the top of the rest-code, so fine bin f holds
+    // the entries ranked from rank_of(f << hi_bits) to the next bin's first rank (behind the barrier that has pre[])
+    auto fine_pairs_ranked = [&](uint32_t lo_bits, uint32_t hi_bits, uint32_t c) {
+        if (tid >= SUPER_FINE) return; // (whole waves)
+        unsigned long long pairs = 0ull;
+        if (tid < (1u << lo_bits)) {
+            const uint32_t first = rank_of(tid << hi_bits);
+            const uint32_t next = tid + 1u < (1u << lo_bits) ? rank_of((tid + 1u) << hi_bits) : c; // (4^rest: past the map)
+            const uint32_t n = next - first;
+            pairs = (unsigned long long)n * (n ? n - 1u : 0u) / 2ull;
+        }
+        for (int off = 32; off > 0; off >>= 1) pairs += __shfl_down(pairs, off);
+        if (lane == 0 && pairs) atomicAdd(&fine_pairs, pairs);
+    };
+
     for (uint32_t u = blockIdx.x; u < g.n_supers; u += gridDim.x) {
         const SegSuper su = g.supers[u];
         const uint32_t start = __builtin_amdgcn_readfirstlane(g.bin_start[su.bin0]);
         const uint32_t c = __builtin_amdgcn_readfirstlane(g.bin_start[su.bin0 + (1u << (2 * su.g))]) - start;
-        if (!super_taken(g, c)) continue; // (block-uniform)
         const uint32_t lo_bits = 2u * su.g, hi_shift = 2u * su.nb, rest = su.rest;
-        const uint32_t lo_mask = (1u << lo_bits) - 1u, code_mask = (1u << (2u * rest)) - 1u; // rest <= 8: 16 bits
+        if (!super_taken(g, c)) { // (block-uniform)
+            if (g.super_count_pairs && c >= 2u) { // above the cap, the tiles' own: its keys once more, for that count alone
+                for (uint32_t w = tid; w < SUPER_FINE; w += NT) fine[w] = 0u;
+                __syncthreads();
+                for (uint32_t p = tid; p < c; p += NT) fine_add(sub[start + p].key, lo_bits);
+                __syncthreads();
+                fine_pairs_out(lo_bits);
+                __syncthreads(); // (the next super-bin clears the counters)
+            }
+            continue;
+        }
+        // the rest-code: the bases outside the bins in its low hi_bits, the fine bin above them (rest <= 8: 16 bits)
+        const uint32_t hi_bits = 2u * rest - lo_bits;
+        const uint32_t lo_mask = (1u << lo_bits) - 1u, hi_mask = (1u << hi_bits) - 1u;
         for (uint32_t w = tid; w < SEG_SUPER_WORDS; w += NT) bm[w] = 0u;
+        if (g.super_count_pairs)
+            for (uint32_t w = tid; w < SUPER_FINE; w += NT) fine[w] = 0u;
         uint32_t rc[SUPER_RPT], ri[SUPER_RPT], rf[SUPER_RPT], rq[SUPER_RPT];
 #pragma unroll
         for (int r = 0; r < SUPER_RPT; r++) {
@@ -1381,7 +1456,7 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
             rc[r] = ri[r] = rf[r] = rq[r] = 0u;
             if (p < c) {
                 const SegRec32 rec = sub[start + p];
-                rc[r] = ((rec.key & lo_mask) | ((rec.key >> hi_shift) << lo_bits)) & code_mask;
+                rc[r] = ((rec.key >> hi_shift) & hi_mask) | ((rec.key & lo_mask) << hi_bits);
                 ri[r] = rec.idx;
                 rf[r] = (uint32_t)rec.freq;
             }
@@ -1397,6 +1472,14 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
             }
         const bool dup = __syncthreads_or(twice ? 1 : 0) != 0;
         stamp(1);
+        if (dup && g.super_count_pairs) { // (the map holds fewer bits than there are entries: counted one by one)
+#pragma unroll
+            for (int r = 0; r < SUPER_RPT; r++)
+                if (tid + (uint32_t)r * NT < c) fine_add(rc[r] >> hi_bits, lo_bits);
+            __syncthreads();
+            fine_pairs_out(lo_bits); // (fine[] is next written when the next super-bin clears it, barriers away)
+            stamp(8);
+        }
         if (!dup) {
             { // set bits before every word: a thread sums WPT words, the block scans the sums
                 uint32_t n_w[WPT], mine = 0;
@@ -1418,6 +1501,11 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
                 }
             }
             __syncthreads();
+            if (g.super_count_pairs) { // the fine bins' entries: the ranks of their first codes, one apart
+                stamp(2);
+                fine_pairs_ranked(lo_bits, hi_bits, c);
+                stamp(8);
+            }
 #pragma unroll
             for (int r = 0; r < SUPER_RPT; r++)
                 if (tid + (uint32_t)r * NT < c) {
@@ -1523,6 +1611,10 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
     for (int off = 32; off > 0; off >>= 1) n_cand += __shfl_down(n_cand, off);
     for (int off = 32; off > 0; off >>= 1) n_direct += __shfl_down(n_direct, off);
     if (lane == 0) g.priv_stat[my_slot] = make_uint2(n_cand, n_direct); // (the flatten launch adds them up)
+    if (g.super_count_pairs) {
+        __syncthreads(); // (a block without a super-bin of its own has met no barrier yet)
+        if (tid == 0 && fine_pairs) atomicAdd(&a.counters[CNT_SEG_PAIRS], fine_pairs);
+    }
 }
 
 // offsets of the blocks' slots behind what the list holds already (one block), the new total
@@ -1679,8 +1771,8 @@ size_t seg_super_lds_bytes(uint32_t cap)
     const uint32_t n_waves = seg_super_threads(cap) / 64u;
     return ((size_t)4 * cap + 2 * SEG_SUPER_WORDS + (size_t)n_waves * SUPER_HITQ) * sizeof(uint32_t);
 }
-static_assert(((size_t)4 * SEG_SUPER_MAX_CAP + 2 * SEG_SUPER_WORDS + 16 * SUPER_HITQ) * sizeof(uint32_t) + 64 <= 160 * 1024,
-              "the largest block and its wave sums fit a CU's LDS");
+static_assert(((size_t)4 * SEG_SUPER_MAX_CAP + 2 * SEG_SUPER_WORDS + 16 * SUPER_HITQ + SUPER_FINE) * sizeof(uint32_t) + 64 <= 160 * 1024,
+              "the largest block, its wave sums and its fine-bin counters fit a CU's LDS");
 
 // its persistent grid: one block per CU at most, no more than there are super-bins
 uint32_t seg_super_blocks(uint32_t n_supers, uint32_t n_cus) { return n_supers < n_cus ? n_supers : n_cus; }
