@@ -175,6 +175,8 @@ const char *umi_last_error(void);
  *   "velocity_skip"  0/1 (default 0): 1: umi_velocity_matrix's reads load their molecule's evidence first and leave the
  *                    atomic out where their bit is set (0: an atomic per read with evidence).  The result is the same;
  *                    measured, the load costs more than it saves unless a molecule has very many reads
+ *   "saturation_skip" 0/1 (default 0): 1: umi_saturation_curve's reads load their molecule's word of levels first and
+ *                    leave the atomic out where their bit is set (0: an atomic per counted read).  The curve is the same
  * The round-1 tile kernels (bit-sliced masks, key-sorted scan + item walk, range pruning, hook/jump
  * collapse) and their options ("bitslice", "bs_*", "prune", "two_phase", "ovf_capacity") exist in the
  * development build only (make dev: libumihip_dev.so, -DUMIHIP_DEV), as cross-checks. */
@@ -758,6 +760,47 @@ int umi_velocity_matrix(umi_ctx *ctx, const uint32_t *read_entry, const uint8_t 
                         const uint32_t *row, const uint32_t *col, uint32_t n_rows, uint32_t n_cols, uint32_t *out_row,
                         uint32_t *out_col, uint32_t *out_spliced, uint32_t *out_unspliced, uint32_t *out_ambiguous,
                         uint64_t *nnz);
+
+/* ---- sequencing saturation and median genes / molecules per cell as a function of depth (the program's
+ *      --saturation-curve): nested read subsampling on the GPU.  tests/saturation_model.py defines it.  Everything is
+ *      exact integer arithmetic, the same in every run.  The collapse is the full-depth one: the curve takes kept[] and
+ *      root[] as they are and does NOT collapse again at each depth (what Cell Ranger does from its molecule table).
+ *      Hash of read i (its index in read_entry), mod 2^64:  z = seed + (i + 1) * 0x9E3779B97F4A7C15;
+ *        z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;  z ^= z >> 31;  h = z >> 32.
+ *      Level of a read: lev = (h * L) >> 32, in 0..L-1.  A read is in depth j -- the sample of (j + 1) / L of the reads
+ *        -- when lev <= j; the samples are nested and depth L-1 holds every read.
+ *      A molecule is an entry r with kept[r] != 0; its reads are the reads i with read_entry[i] != UMI_READ_UNSTAGED and
+ *        root[read_entry[i]] == r; its level is the smallest level of its reads, and it is absent at every depth if it
+ *        has none.  A counted read is a read whose root is kept; reads under a root with kept == 0 count nowhere.  A
+ *        molecule belongs to the bucket that holds r.  A pair is a distinct (col, row) among the non-empty buckets
+ *        (several buckets may share one); its level is the smallest level of the molecules of its buckets.
+ *      Selected columns: with cell_mask, those with cell_mask[c] != 0, whether they hold a molecule or not; with
+ *        cell_mask NULL, the columns with a molecule at full depth.  n_sel is their number.
+ * in : read_entry, n_reads, kept, root, bucket_off (a HOST array in both forms), row, col, n_rows, n_cols as
+ *      umi_velocity_matrix takes them; seed; n_levels = L in 1..32; cell_mask uint8 [n_cols] or NULL.
+ * out: curve uint64 [L][8], HOST memory in both forms, row j = depth j, everything cumulative (lev <= j):
+ *      0 reads (counted reads), 1 molecules, 2 pairs, 3 cells (selected columns with a molecule at this depth),
+ *      4 molecules_in_cells and 5 pairs_in_cells (those in selected columns), 6 median_molecules: over all n_sel
+ *      selected columns -- those with none count as 0 -- the lower median (element floor((n_sel - 1) / 2) in
+ *      ascending order) of a column's molecules at this depth, 0 for n_sel = 0; 7 median_genes: the same for a
+ *      column's pairs.  The device form writes nothing else the caller can see.
+ * n_buckets == 0 or every bucket empty: UMI_OK, the curve all zeros, nothing launched, the reads not looked at.  A
+ * multi-device context uses its first device; a deferred call that is out ends first.  Grids come from the context's
+ * CU count (option "grid_cus").  Workspace, bytes: 4 N + 52 m + 56 L n_cols + the temporaries of the library's sort
+ * of max(m, 2 L n_cols) keys and of its scan of m + 4 KB, m the non-empty buckets; the column tables and the median
+ * sort are sized by n_cols, not n_sel (the selected columns are not compacted), and 2 L n_cols < 2^30.
+ * UMI_ERR_ARG, nothing written to curve: n_levels outside 1..32 and n_reads >= 2^32 (both before any HIP call), NULL
+ * pointers, umi_count_matrix's own (n_buckets >= 2^30, bucket_off, n_rows, n_cols, a row or col of a non-empty bucket
+ * out of range), 2 L n_cols >= 2^30, and, found on the device and told after the call's one synchronisation, the
+ * smallest read named: a read_entry >= N other than UMI_READ_UNSTAGED, a root[read_entry[i]] >= N.
+ * Option "saturation_skip" 0/1: see umi_ctx_set_option. */
+int umi_saturation_curve_device(umi_ctx *ctx, const uint32_t *d_read_entry, uint64_t n_reads, const uint8_t *d_kept,
+                                const uint32_t *d_root, const uint64_t *bucket_off, uint64_t n_buckets, const uint32_t *d_row,
+                                const uint32_t *d_col, uint32_t n_rows, uint32_t n_cols, uint64_t seed, int n_levels,
+                                const uint8_t *d_cell_mask, uint64_t *curve, void *hip_stream);
+int umi_saturation_curve(umi_ctx *ctx, const uint32_t *read_entry, uint64_t n_reads, const uint8_t *kept, const uint32_t *root,
+                         const uint64_t *bucket_off, uint64_t n_buckets, const uint32_t *row, const uint32_t *col, uint32_t n_rows,
+                         uint32_t n_cols, uint64_t seed, int n_levels, const uint8_t *cell_mask, uint64_t *curve);
 
 /* ---- UMIs a group shows in several buckets (the program's --umi-filtering multi-gene): the molecules of a batched
  *      call joined across its buckets, on the GPU.  A UMI that one cell shows under two or more genes is a chimera

@@ -19,6 +19,9 @@ UMI_GENE_TIER_EXON, UMI_GENE_TIER_INTRON = 0, 1                          # ... a
 (UMI_READ_CLASS_NONE, UMI_READ_CLASS_EXONIC, UMI_READ_CLASS_JUNCTION, UMI_READ_CLASS_SPANNING,
  UMI_READ_CLASS_INTRONIC) = 0, 1, 2, 3, 4                                # the classes of umi_assign_genes_classes
 UMI_READ_UNSTAGED = 0xFFFFFFFF                                           # umi_velocity_matrix: a read no entry holds
+# the eight columns of umi_saturation_curve's rows
+SATURATION_COLUMNS = ("reads", "molecules", "pairs", "cells", "molecules_in_cells", "pairs_in_cells", "median_molecules",
+                      "median_genes")
 UMI_MAX_UMI_LEN = 21
 UMI_KERNEL_EDIT_PAIRS = 4     # Stats.kernel_id of umi_dedup_batch_edit (with "profile")
 UMI_MAX_CONS_LEN = 1024       # umi_consensus_bam: bases of a cluster, at most
@@ -149,6 +152,11 @@ SIGNATURES = {
                                              C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_void_p]),
     "umi_velocity_matrix": (C.c_int, [C.c_void_p, _u32p, _u8p, C.c_uint64, _u8p, _u32p, _u64p, C.c_uint64, _u32p, _u32p,
                                       C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _u32p, _u64p]),
+    "umi_saturation_curve_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, _u64p, C.c_uint64,
+                                              C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p,
+                                              _u64p, C.c_void_p]),
+    "umi_saturation_curve": (C.c_int, [C.c_void_p, _u32p, C.c_uint64, _u8p, _u32p, _u64p, C.c_uint64, _u32p, _u32p, C.c_uint32,
+                                       C.c_uint32, C.c_uint64, C.c_int, _u8p, _u64p]),
     "umi_count_matrix_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_uint64, C.c_void_p, C.c_void_p,
                                           C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p,
                                           C.c_void_p]),

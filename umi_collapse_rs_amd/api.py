@@ -692,6 +692,46 @@ class Context:
                                                 d_out_ambiguous or None, C.byref(nnz), stream or None))
         return int(nnz.value)
 
+    def saturation_curve(self, read_entry, kept, root, bucket_off, row, col, n_rows, n_cols, n_levels=10, seed=0, cell_mask=None):
+        """Sequencing saturation and medians per cell as a function of depth (umi_saturation_curve; the rule is in
+        include/umihip.h): velocity_matrix's arguments without the classes, n_levels depths, the seed of the reads'
+        hash, cell_mask uint8 [n_cols] or None (every column with a molecule is selected).  Returns uint64
+        [n_levels, 8], row j the sample of (j + 1) / n_levels of the reads, its columns SATURATION_COLUMNS.  The
+        collapse is the full-depth one; nothing is collapsed again per depth."""
+        read_entry = np.ascontiguousarray(read_entry, dtype=np.uint32).reshape(-1)
+        kept = np.ascontiguousarray(kept, dtype=np.uint8)
+        root = np.ascontiguousarray(root, dtype=np.uint32)
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        row = np.ascontiguousarray(row, dtype=np.uint32)
+        col = np.ascontiguousarray(col, dtype=np.uint32)
+        nb = len(bucket_off) - 1
+        if nb < 0 or len(row) != nb or len(col) != nb:
+            raise ValueError("row / col want one element per bucket")
+        if len(kept) != len(root) or (nb and int(bucket_off.max()) > len(kept)):
+            raise ValueError("kept / root lengths differ, or bucket_off runs past them")
+        if cell_mask is not None:
+            cell_mask = np.ascontiguousarray(cell_mask, dtype=np.uint8).reshape(-1)
+            if len(cell_mask) != n_cols:
+                raise ValueError("cell_mask wants one element per column")
+        curve = np.zeros((max(1, min(int(n_levels), 32)), 8), np.uint64)
+        check(load().umi_saturation_curve(self._h, ptr(read_entry, C.c_uint32), len(read_entry), ptr(kept, C.c_uint8),
+                                          ptr(root, C.c_uint32), ptr(bucket_off, C.c_uint64), nb, ptr(row, C.c_uint32),
+                                          ptr(col, C.c_uint32), n_rows, n_cols, int(seed), int(n_levels),
+                                          None if cell_mask is None else ptr(cell_mask, C.c_uint8), ptr(curve, C.c_uint64)))
+        return curve
+
+    def saturation_curve_device(self, d_read_entry, n_reads, d_kept, d_root, bucket_off, d_row, d_col, n_rows, n_cols,
+                                n_levels=10, seed=0, d_cell_mask=0, stream=0):
+        """The same on raw device pointers (umi_saturation_curve_device; bucket_off stays on the host, and the curve
+        comes back in host memory): returns uint64 [n_levels, 8]."""
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        curve = np.zeros((max(1, min(int(n_levels), 32)), 8), np.uint64)
+        check(load().umi_saturation_curve_device(self._h, d_read_entry or None, n_reads, d_kept or None, d_root or None,
+                                                 ptr(bucket_off, C.c_uint64), len(bucket_off) - 1, d_row or None, d_col or None,
+                                                 n_rows, n_cols, int(seed), int(n_levels), d_cell_mask or None,
+                                                 ptr(curve, C.c_uint64), stream or None))
+        return curve
+
     def count_matrix(self, kept, freq, bucket_off, row, col, n_rows, n_cols):
         """Molecules and reads per (column, row) pair (umi_count_matrix): kept uint8 [N] and freq int32 [N] of a
         batched call, bucket_off uint64 [n_buckets + 1], row / col uint32 [n_buckets] the row (gene) and column

@@ -238,6 +238,9 @@ int umi_ctx_set_option(umi_ctx *ctx, const char *name, int64_t value)
     } else if (!strcmp(name, "velocity_skip")) {
         if (value != 0 && value != 1) return fail(UMI_ERR_ARG, "velocity_skip must be 0 or 1");
         ctx->velocity_skip = value != 0;
+    } else if (!strcmp(name, "saturation_skip")) {
+        if (value != 0 && value != 1) return fail(UMI_ERR_ARG, "saturation_skip must be 0 or 1");
+        ctx->saturation_skip = value != 0;
     } else if (!strcmp(name, "fused_sliced")) {
         ctx->fused_sliced = value != 0;
     } else if (!strcmp(name, "fused_blocks")) {

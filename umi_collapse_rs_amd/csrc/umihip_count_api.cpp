@@ -1,4 +1,4 @@
-// Tables over a call's result, and its filters: umi_count_matrix*, umi_velocity_matrix*, umi_filter_multigene*, umi_dedup_stats*, umi_call_cells*.
+// Tables over a call's result, and its filters: umi_count_matrix*, umi_velocity_matrix*, umi_saturation_curve*, umi_filter_multigene*, umi_dedup_stats*, umi_call_cells*.
 #include "umihip_host.hpp"
 
 #include <algorithm>
@@ -26,12 +26,14 @@ int cm_check(umi_ctx *ctx, const void *kept, const void *freq, const uint64_t *b
 
 // The table walked once into the pinned staging: its non-empty buckets' offsets (a run of equal offsets is
 // one) and, from the first empty bucket on, their numbers.  *m: the non-empty buckets; *idx: null where
-// nothing was left out.
-int cm_walk(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, uint32_t *m, const uint64_t **off, const uint32_t **idx)
+// nothing was left out.  extra: pinned bytes of the call's own behind the two, at *extra_at.
+int cm_walk(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, uint32_t *m, const uint64_t **off, const uint32_t **idx,
+            size_t extra = 0, unsigned long long **extra_at = nullptr)
 {
     int rc;
-    const size_t off_bytes = ((size_t)n_buckets + 1) * 8;
-    if ((rc = ctx->cm_h.reserve(off_bytes + (size_t)n_buckets * 4))) return rc;
+    const size_t off_bytes = ((size_t)n_buckets + 1) * 8, tables = (off_bytes + (size_t)n_buckets * 4 + 7) & ~(size_t)7;
+    if ((rc = ctx->cm_h.reserve(tables + extra))) return rc;
+    if (extra_at) *extra_at = (unsigned long long *)(ctx->cm_h.p + tables);
     uint64_t *o = (uint64_t *)ctx->cm_h.p;
     uint32_t *x = (uint32_t *)(ctx->cm_h.p + off_bytes);
     uint32_t k = 0;
@@ -246,6 +248,124 @@ int umi_velocity_matrix(umi_ctx *ctx, const uint32_t *read_entry, const uint8_t 
         (rc = io.fetch(out_ambiguous, d_oa, (size_t)got)) || (rc = io.close()))
         return rc;
     *nnz = got;
+    return UMI_OK;
+}
+
+} // extern "C"
+
+// ---- saturation and medians per depth ---------------------------------------------------------------
+namespace {
+// what both forms check before a device is looked at (the context last)
+int sc_check(umi_ctx *ctx, const void *read_entry, uint64_t n_reads, const void *kept, const void *root, const uint64_t *bucket_off,
+             uint64_t n_buckets, const void *row, const void *col, uint32_t n_cols, int n_levels, const uint64_t *curve)
+{
+    if (!curve) return fail(UMI_ERR_ARG, "curve is NULL");
+    if (n_levels < 1 || n_levels > 32) return fail(UMI_ERR_ARG, "n_levels %d outside 1..32", n_levels);
+    if (n_reads >= (1ull << 32)) return fail(UMI_ERR_ARG, "%llu reads exceed the 32-bit index space of one call", (unsigned long long)n_reads);
+    if (n_buckets >= (1ull << 30))
+        return fail(UMI_ERR_ARG, "%llu buckets exceed the 30-bit index space of one call", (unsigned long long)n_buckets);
+    if (n_buckets && !bucket_off) return fail(UMI_ERR_ARG, "bucket_off is NULL");
+    if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
+    if (n_buckets && (!row || !col)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (n_buckets && bucket_off[n_buckets] && (!kept || !root)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (n_buckets && bucket_off[n_buckets] && n_reads && !read_entry) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (n_buckets && bucket_off[n_buckets] >= (1ull << 32))
+        return fail(UMI_ERR_ARG, "%llu entries exceed the 32-bit index space of root", (unsigned long long)bucket_off[n_buckets]);
+    if (n_buckets && 2ull * (uint64_t)n_levels * n_cols >= (1ull << 30))
+        return fail(UMI_ERR_ARG, "%u columns at %d levels exceed the 30-bit index space of the call's sort", n_cols, n_levels);
+    if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
+    return UMI_OK;
+}
+
+// the device made current, a deferred call let end, the table walked; *m == 0: the curve is all zeros and written
+int sc_begin(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, uint32_t n_rows, uint32_t n_cols, int n_levels,
+             uint64_t *curve, uint32_t *m, const uint64_t **h_off, const uint32_t **h_idx, unsigned long long **h_pinned)
+{
+    int rc;
+    *m = 0;
+    if (n_buckets) {
+        HIP_TRY(hipSetDevice(ctx->device));
+        settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
+        if ((rc = cm_walk(ctx, bucket_off, n_buckets, m, h_off, h_idx, (4 + 8 * (size_t)n_levels) * 8, h_pinned))) return rc;
+    }
+    if (*m == 0) {
+        memset(curve, 0, (size_t)n_levels * 8 * sizeof(uint64_t));
+        return UMI_OK;
+    }
+    if (n_rows == 0 || n_cols == 0) return fail(UMI_ERR_ARG, "a matrix of %u rows and %u columns with a non-empty bucket", n_rows, n_cols);
+    return UMI_OK;
+}
+
+int sc_run(umi_ctx *ctx, const uint32_t *d_read_entry, uint64_t n_reads, const uint8_t *d_kept, const uint32_t *d_root, uint64_t n,
+           uint32_t m, const uint64_t *h_off, const uint32_t *h_idx, const uint32_t *d_row, const uint32_t *d_col, uint32_t n_rows,
+           uint32_t n_cols, uint64_t seed, int n_levels, const uint8_t *d_cell_mask, unsigned long long *h_pinned, uint64_t *curve,
+           hipStream_t s)
+{
+    int rc;
+    if ((rc = ctx->call_ws.reserve(saturation_workspace_bytes(n, m, h_idx != nullptr, n_cols, n_levels)))) return rc;
+    uint64_t bad = 0, bad_read = 0;
+    int kind = 0;
+    const int r = saturation_curve_on_device(ctx->call_ws.p, d_read_entry, (uint32_t)n_reads, d_kept, d_root, n, h_off, h_idx, m, d_row,
+                                             d_col, n_rows, n_cols, seed, n_levels, d_cell_mask, ctx->saturation_skip, &bad, &kind,
+                                             &bad_read, (uint32_t)ctx->n_cus, h_pinned, s);
+    if (r < 0) return fail(UMI_ERR_HIP, "saturation curve: %s", hipGetErrorString((hipError_t)(-r)));
+    if (bad)
+        return fail(UMI_ERR_ARG, "%llu non-empty buckets have a row id of %u or more, or a column id of %u or more",
+                    (unsigned long long)bad, n_rows, n_cols);
+    if (kind == 1)
+        return fail(UMI_ERR_ARG, "read %llu: its read_entry is neither below the %llu entries nor UMI_READ_UNSTAGED",
+                    (unsigned long long)bad_read, (unsigned long long)n);
+    if (kind == 2)
+        return fail(UMI_ERR_ARG, "read %llu: the root of its entry is not below the %llu entries", (unsigned long long)bad_read,
+                    (unsigned long long)n);
+    memcpy(curve, h_pinned + 4, (size_t)n_levels * 8 * sizeof(uint64_t));
+    return UMI_OK;
+}
+} // namespace
+
+extern "C" {
+
+int umi_saturation_curve_device(umi_ctx *ctx, const uint32_t *d_read_entry, uint64_t n_reads, const uint8_t *d_kept,
+                                const uint32_t *d_root, const uint64_t *bucket_off, uint64_t n_buckets, const uint32_t *d_row,
+                                const uint32_t *d_col, uint32_t n_rows, uint32_t n_cols, uint64_t seed, int n_levels,
+                                const uint8_t *d_cell_mask, uint64_t *curve, void *hip_stream)
+{
+    int rc = sc_check(ctx, d_read_entry, n_reads, d_kept, d_root, bucket_off, n_buckets, d_row, d_col, n_cols, n_levels, curve);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_count_matrix)
+    uint32_t m = 0;
+    const uint64_t *h_off = nullptr;
+    const uint32_t *h_idx = nullptr;
+    unsigned long long *h_pinned = nullptr;
+    if ((rc = sc_begin(ctx, bucket_off, n_buckets, n_rows, n_cols, n_levels, curve, &m, &h_off, &h_idx, &h_pinned)) || m == 0) return rc;
+    return sc_run(ctx, d_read_entry, n_reads, d_kept, d_root, bucket_off[n_buckets], m, h_off, h_idx, d_row, d_col, n_rows, n_cols, seed,
+                  n_levels, d_cell_mask, h_pinned, curve, (hipStream_t)hip_stream);
+}
+
+int umi_saturation_curve(umi_ctx *ctx, const uint32_t *read_entry, uint64_t n_reads, const uint8_t *kept, const uint32_t *root,
+                         const uint64_t *bucket_off, uint64_t n_buckets, const uint32_t *row, const uint32_t *col, uint32_t n_rows,
+                         uint32_t n_cols, uint64_t seed, int n_levels, const uint8_t *cell_mask, uint64_t *curve)
+{
+    int rc = sc_check(ctx, read_entry, n_reads, kept, root, bucket_off, n_buckets, row, col, n_cols, n_levels, curve);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    uint32_t m = 0;
+    const uint64_t *h_off = nullptr;
+    const uint32_t *h_idx = nullptr;
+    unsigned long long *h_pinned = nullptr;
+    if ((rc = sc_begin(ctx, bucket_off, n_buckets, n_rows, n_cols, n_levels, curve, &m, &h_off, &h_idx, &h_pinned)) || m == 0) return rc;
+    const size_t n = (size_t)bucket_off[n_buckets], nb = (size_t)n_buckets;
+    HostIo io(ctx);
+    const auto d_entry = io.in(read_entry, (size_t)n_reads * 4);
+    const auto d_root = io.in(root, n * 4);
+    const auto d_row = io.in(row, nb * 4), d_col = io.in(col, nb * 4);
+    const auto d_kept = io.in(kept, n);
+    const auto d_mask = io.in(cell_mask, (size_t)n_cols);
+    if ((rc = io.open()) ||
+        (rc = sc_run(ctx, d_entry, n_reads, d_kept, d_root, n, m, h_off, h_idx, d_row, d_col, n_rows, n_cols, seed, n_levels, d_mask,
+                     h_pinned, curve, io.stream())) ||
+        (rc = io.close()))
+        return rc;
     return UMI_OK;
 }
 

@@ -261,6 +261,7 @@ struct umi_ctx {
     uint32_t stats_split = umihip::STATS_SPLIT; // buckets of at least this many entries are counted by the whole grid
     bool gene_top = true; // umi_assign_genes: the sampled top of each table in LDS (option "gene_top")
     bool velocity_skip = false; // umi_velocity_matrix: a read loads its molecule's evidence and skips the atomic where its bit is set (option "velocity_skip")
+    bool saturation_skip = false; // umi_saturation_curve: likewise for its molecule's word of levels (option "saturation_skip")
     bool gene_body_top = true; //umi_assign_genes_introns: the body tables' tops too (option "gene_body_top"; counts with gene_top)
     uint32_t cons_split = 512; // clusters of at least this many reads are summed in pieces by the whole grid
     umihip::PinnedBuf h_boff;                 // pinned staging of the bucket table

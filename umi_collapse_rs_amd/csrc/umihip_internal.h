@@ -592,6 +592,19 @@ int velocity_matrix_on_device(void *workspace, const uint32_t *d_read_entry, con
                               uint32_t *d_out_ambiguous, bool skip_set, uint64_t *nnz, uint64_t *bad_ids, int *bad_kind,
                               uint64_t *bad_read, uint32_t n_cus, unsigned long long *h_pinned, hipStream_t s);
 
+// ---- saturation and medians per depth (umihip_saturation.hip: umi_saturation_curve) ----
+// velocity_matrix_on_device's read and bucket arguments without the classes; 1 <= n_levels <= 32, 2 n_levels n_cols < 2^30;
+// d_cell_mask may be null.  *bad_ids as there; *bad_kind: 0 none, 1 a read_entry out of range, 2 a root out of range, of
+// read *bad_read.  skip_set: a lane loads its molecule's word and leaves the atomic out where its bit is set.  One
+// synchronisation, at the end.  h_pinned: 4 + 8 n_levels pinned words; the curve lies from word 4 on.  0 ok;
+// negative: -(hipError_t)
+size_t saturation_workspace_bytes(uint64_t n, uint32_t m, bool has_idx, uint32_t n_cols, int n_levels);
+int saturation_curve_on_device(void *workspace, const uint32_t *d_read_entry, uint32_t n_reads, const uint8_t *d_kept,
+                               const uint32_t *d_root, uint64_t n, const uint64_t *h_off, const uint32_t *h_idx, uint32_t m,
+                               const uint32_t *d_row, const uint32_t *d_col, uint32_t n_rows, uint32_t n_cols, uint64_t seed,
+                               int n_levels, const uint8_t *d_cell_mask, bool skip_set, uint64_t *bad_ids, int *bad_kind,
+                               uint64_t *bad_read, uint32_t n_cus, unsigned long long *h_pinned, hipStream_t s);
+
 // ---- family sizes, UMI distances and UMI usage of a batched call (umihip_stats.hip: umi_dedup_stats) ----
 constexpr uint32_t STATS_LANE_MAX = 8;    // a bucket of more entries is a wave's
 constexpr uint32_t STATS_HIST_LDS = 2048; // family-size bins a block counts in LDS; the others by global atomics

@@ -85,6 +85,29 @@
 // summary lines and what is not built).
 // Refused with status 101 before the GPU is woken: --velocity without --count-matrix, without --gene-annotation, with
 // --gene-introns absent or off, or with --stage gpu (a read's entry is kept by the host staging alone).
+// --saturation-curve FILE [--saturation-points L] [--saturation-seed S] (with --per-gene --count-matrix DIR, with or
+// without --per-cell -- without it there is the one column "all" -- and with everything those go with;
+// tests/saturation_model.py defines it, include/umihip.h has the same rule) [L 10, S 0]: sequencing saturation and the
+// median genes and molecules per cell as a function of depth, as Cell Ranger plots them, by nested read subsampling on
+// the GPU.  Read i -- its record's number in the input -- has the hash h = splitmix64(S, i) >> 32 of umihip.h and the
+// level (h * L) >> 32; depth j of 1..L is the reads of a level below j, so a read of one depth is in every deeper one,
+// and depth L is the whole file.  A molecule is there at a depth when one of its reads is; a (cell, gene) pair when one
+// of its molecules is.  The collapse is the full-depth one: the molecules are those of the run, and nothing is
+// collapsed again per depth (what Cell Ranger does from its molecule table).  Reads under a UMI that --umi-filtering
+// multi-gene removed count nowhere.  One call to umi_saturation_curve on the first device, after the matrix and after
+// --cell-filter's call, over every read's entry as --velocity builds it, the mask the matrix was counted from, root[]
+// and the buckets' gene and cell.  The selected cells of the medians and the "in cells" columns are --cell-filter's
+// called cells; without that flag every column with a molecule.
+// FILE: tab-separated, uncompressed, the header "depth reads molecules saturation pairs cells molecules_in_cells
+// pairs_in_cells median_molecules median_genes" and a line per depth; depth is the text j/L; saturation is
+// floor(10000 (reads - molecules) / reads) printed as 0.dddd, 0.0000 where reads is 0, computed in integers; the medians
+// are lower medians over all selected cells, those with nothing at the depth as 0.  The summary gains "Saturation
+// curve: <L> points, seed <S>" and "Sequencing saturation: 0.dddd" (the last line's).  The BAM, every matrix file,
+// cells.tsv, velocity/ and the other summary lines are byte for byte what --stage host writes without the flag.  The
+// flag stages on the host, as --velocity does: --stage auto goes to the host.
+// Refused with status 101 before the GPU is woken: the flag without --count-matrix or with --stage gpu;
+// --saturation-points or --saturation-seed without the flag; L that is not a number in 1..32; S that is not a number in
+// 0..2^64-1; any of the three given twice with different values; a FILE that cannot be created (its parent must exist).
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -170,6 +193,10 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     bool gene_introns_given = false;
     int gene_introns_mode = UMI_INTRONS_OFF; // as UMI_INTRONS_* (filled in by validate())
     bool velocity = false; // --velocity: spliced, unspliced and ambiguous matrices beside --count-matrix's
+    std::string saturation_curve;  // --saturation-curve FILE: saturation and medians per depth (the rule is at the top)
+    int saturation_points = 10;    // --saturation-points L
+    uint64_t saturation_seed = 0;  // --saturation-seed S
+    std::string saturation_points_text, saturation_seed_text; // ... as given, for "given twice"
     // --gene-rule overlap|transcript (annotation.hpp); overlap and no flag are the same run
     std::string gene_rule = "overlap", annotation_transcript_attribute = "transcript_id";
     bool gene_rule_given = false, annotation_transcript_attribute_given = false;
@@ -306,6 +333,12 @@ void usage()
               "                           ambiguous.mtx, features.tsv, barcodes.tsv) by a gene-level rule: a molecule with a\n"
               "                           read that skips an intron is spliced, with a read in an intron or over an exon's\n"
               "                           edge unspliced, with both or neither ambiguous (host staging; not with --stage gpu)\n"
+              "      --saturation-curve <FILE> with --per-gene --count-matrix: write sequencing saturation and the median genes\n"
+              "                           and molecules per cell at L depths to FILE (tab-separated), by nested subsampling\n"
+              "                           of the reads on the GPU; the molecules are the run's own, nothing is collapsed\n"
+              "                           again per depth (host staging; not with --stage gpu)\n"
+              "      --saturation-points <L> with --saturation-curve: depths, 1..32 [default: 10]\n"
+              "      --saturation-seed <S> with --saturation-curve: seed of the reads' hash, 0..2^64-1 [default: 0]\n"
               "      --count-matrix <DIR> with --per-gene: write the molecules per cell and gene to DIR (made if it is\n"
               "                           not there) as features.tsv, barcodes.tsv, matrix.mtx (molecules) and reads.mtx\n"
               "                           (reads), MatrixMarket coordinate files sorted by cell, then gene, counted on the GPU\n"
@@ -436,6 +469,24 @@ Cli parse(int argc, char **argv)
             if (given && value != v) die(a + " given twice with different values: '" + value + "' and '" + v + "'");
             value = v;
             given = true;
+        }
+        else if (a == "--saturation-curve" || a == "--saturation-points" || a == "--saturation-seed") {
+            const std::string v = need(i);
+            std::string &value = a == "--saturation-curve" ? c.saturation_curve : a == "--saturation-points" ? c.saturation_points_text
+                                                                                                           : c.saturation_seed_text;
+            if (!value.empty() && value != v) die(a + " given twice with different values: '" + value + "' and '" + v + "'");
+            if (v.empty()) die(a + " wants a value");
+            value = v;
+            const bool digits = v.find_first_not_of("0123456789") == std::string::npos;
+            errno = 0;
+            const unsigned long long w = digits ? std::strtoull(v.c_str(), nullptr, 10) : 0ull;
+            if (a == "--saturation-points") {
+                if (!digits || errno == ERANGE || w < 1 || w > 32) die("--saturation-points wants a whole number in 1..32: '" + v + "'");
+                c.saturation_points = (int)w;
+            } else if (a == "--saturation-seed") {
+                if (!digits || errno == ERANGE) die("--saturation-seed wants a whole number in 0..2^64-1: '" + v + "'");
+                c.saturation_seed = (uint64_t)w;
+            }
         }
         else if (a == "--count-matrix") c.count_matrix = need(i);
         else if (a == "--output-stats") c.output_stats = need(i);
@@ -689,8 +740,17 @@ bool validate(Cli &args)
         if (args.gene_introns_mode == UMI_INTRONS_OFF) die("--velocity goes with --gene-introns exon-first or all only");
         if (args.stage == "gpu") die("--stage gpu does not go with --paired, --tag, --call-consensus, --velocity or --dump-staging");
     }
+    // --saturation-curve: likewise (its file is made last)
+    if (args.saturation_curve.empty()) {
+        if (!args.saturation_points_text.empty()) die("--saturation-points goes with --saturation-curve only");
+        if (!args.saturation_seed_text.empty()) die("--saturation-seed goes with --saturation-curve only");
+    } else {
+        if (args.count_matrix.empty()) die("--saturation-curve goes with --count-matrix DIR only");
+        if (args.stage == "gpu")
+            die("--stage gpu does not go with --saturation-curve (a read's entry is kept by the host staging alone)");
+    }
     // --umi-filtering: likewise
-    if (args.umi_filtering_given && args.umi_filtering != "none" && args.umi_filtering != "multi-gene")
+    if (args.umi_filtering_given &&args.umi_filtering != "none" && args.umi_filtering != "multi-gene")
         die("--umi-filtering wants none or multi-gene: '" + args.umi_filtering + "'");
     args.filter_multigene = args.umi_filtering == "multi-gene";
     if (args.filter_multigene && !args.per_gene) die("--umi-filtering multi-gene goes with --per-gene only");
@@ -799,6 +859,11 @@ bool validate(Cli &args)
     for (const std::string &path : output_stats_paths(args)) {
         FILE *f = std::fopen(path.c_str(), "wb");
         if (!f) die("cannot make " + path + " for --output-stats: " + std::strerror(errno));
+        std::fclose(f);
+    }
+    if (!args.saturation_curve.empty()) {
+        FILE *f = std::fopen(args.saturation_curve.c_str(), "wb");
+        if (!f) die("cannot make " + args.saturation_curve + " for --saturation-curve: " + std::strerror(errno));
         std::fclose(f);
     }
     return true;

@@ -30,6 +30,8 @@
 // --gene-rule transcript: likewise umi_assign_genes_transcripts, in umi_assign_genes' place.
 //
 // --velocity: likewise umi_assign_genes_classes, in umi_assign_genes_introns' place, and umi_velocity_matrix.
+//
+// --saturation-curve FILE: likewise umi_saturation_curve.
 #pragma once
 #include <chrono>
 #include <dlfcn.h>
@@ -117,6 +119,9 @@ struct HipLib {
     bool want_velocity = false;
     decltype(&umi_assign_genes_classes) assign_genes_classes = nullptr;
     decltype(&umi_velocity_matrix) velocity_matrix = nullptr;
+    // --saturation-curve: likewise
+    bool want_saturation = false;
+    decltype(&umi_saturation_curve) saturation_curve = nullptr;
     // (the HIP runtime the library brings along: device buffers for the arrays above)
     int (*hip_set_device)(int) = nullptr; // (the current device is per thread: the context was made on another)
     int (*hip_malloc)(void **, size_t) = nullptr;
@@ -131,7 +136,7 @@ struct HipLib {
           want_genes(args.gene_annotation_given && args.gene_introns_mode == UMI_INTRONS_OFF && !args.gene_rule_transcript),
           want_transcripts(args.gene_annotation_given && args.gene_rule_transcript),
           want_introns(args.gene_annotation_given && args.gene_introns_mode != UMI_INTRONS_OFF && !args.velocity),
-          want_velocity(args.velocity)
+          want_velocity(args.velocity), want_saturation(!args.saturation_curve.empty())
     {
     }
     bool load()
@@ -183,6 +188,7 @@ struct HipLib {
             assign_genes_classes = (decltype(assign_genes_classes))sym("umi_assign_genes_classes");
             velocity_matrix = (decltype(velocity_matrix))sym("umi_velocity_matrix");
         }
+        if (want_saturation) saturation_curve = (decltype(saturation_curve))sym("umi_saturation_curve");
         hip_set_device = (decltype(hip_set_device))sym("hipSetDevice");
         hip_malloc = (decltype(hip_malloc))sym("hipMalloc");
         hip_memcpy = (decltype(hip_memcpy))sym("hipMemcpy");

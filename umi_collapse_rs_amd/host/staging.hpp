@@ -389,6 +389,15 @@ struct Summary {
     size_t n_below = 0, n_without = 0; // --call-consensus
     uint64_t mg_counts[3] = {0, 0, 0}; // --umi-filtering multi-gene: UMIs in several genes of a cell, molecules removed, their reads
     uint64_t cell_counts[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // --cell-filter: umi_call_cells' counts
+    uint64_t saturation_reads = 0, saturation_molecules = 0; // --saturation-curve: the full depth's counted reads and molecules
+    // floor(10000 (reads - molecules) / reads) as 0.dddd, in integers; 0.0000 for no reads (--saturation-curve)
+    static std::string saturation_text(uint64_t reads, uint64_t molecules)
+    {
+        const unsigned long long v = reads ? (unsigned long long)((unsigned __int128)10000 * (reads - molecules) / reads) : 0ull;
+        char text[32];
+        std::snprintf(text, sizeof text, "%llu.%04llu", v / 10000ull, v % 10000ull);
+        return text;
+    }
     void print(const Cli &args, bool dump_exit = false) const
     {
         if (!dump_exit) {
@@ -470,6 +479,10 @@ struct Summary {
             std::fprintf(stderr, "Number of spliced molecules: %llu\n", (unsigned long long)layers[0]);
             std::fprintf(stderr, "Number of unspliced molecules: %llu\n", (unsigned long long)layers[1]);
             std::fprintf(stderr, "Number of ambiguous molecules: %llu\n", (unsigned long long)layers[2]);
+        }
+        if (!args.saturation_curve.empty()) {
+            std::fprintf(stderr, "Saturation curve: %d points, seed %llu\n", args.saturation_points, (unsigned long long)args.saturation_seed);
+            std::fprintf(stderr, "Sequencing saturation: %s\n", saturation_text(saturation_reads, saturation_molecules).c_str());
         }
         if (args.call_consensus) {
             std::fprintf(stderr, "Number of clusters below --call-consensus-min-reads: %zu\n", n_below);

@@ -99,6 +99,11 @@
 // call to umi_velocity_matrix over the reads' entries and classes, the surviving mask, root[] and the buckets' gene and
 // cell gives the three layers of the same triplets, written to DIR/velocity/ (and, for the called cells, to
 // DIR/velocity/filtered/); everything else stays byte for byte what --stage host writes without the flag.
+// --saturation-curve FILE (with --per-gene --count-matrix DIR; cli.hpp has the rule and the file): the reads are staged on
+// the host, which keeps every read's entry as for --velocity; after umi_count_matrix, and after umi_call_cells where
+// --cell-filter is given, one call to umi_saturation_curve over the reads' entries, the surviving mask, root[], the buckets'
+// gene and cell and the called cells gives every depth's row of FILE; everything else stays byte for byte what --stage
+// host writes without the flag.
 // --algo cluster: connected components of "within -k" (cli.hpp); every pipeline here only forwards the algorithm
 // to the library, so it goes with every flag --algo dir goes with.
 // Not implemented, as in the reference: --algo cc (that spelling stays refused; `cluster` is the mode's name).
@@ -154,7 +159,7 @@ struct OnePass {
     const int algo = args.algo_id, merge = args.merge_id;
     const unsigned T = std::max(1u, args.num_threads);
     const bool need_clusters = args.track_clusters || args.call_consensus; // every read's entry, every entry's root
-    const bool need_entries = need_clusters || args.velocity;              // every read's entry: the host staging keeps it
+    const bool need_entries = need_clusters || args.velocity || !args.saturation_curve.empty(); // every read's entry: the host staging keeps it
     const bool need_root = need_entries || !args.output_stats.empty() || args.filter_multigene; // root[] of the collapse (no host
                                                                                                 // staging for it alone)
 
@@ -1083,6 +1088,49 @@ struct OnePass {
                 write_layers("velocity/filtered/", n_rows, (uint32_t)sum.cell_counts[1], v_row, v_col, layer, w, write);
             }
         }
+        if (!args.saturation_curve.empty()) saturation_curve(n_rows, n_cols);
+    }
+
+    // --saturation-curve: reads, molecules, pairs and the medians of the selected cells at every depth, in one call over
+    // every read's entry (as --velocity builds it: a read's index is its record's number), the mask the matrix was
+    // counted from, root[] and the buckets' gene and cell; the selected cells are --cell-filter's called ones, and
+    // without that flag every column with a molecule.  Then FILE (cli.hpp has its layout)
+    void saturation_curve(uint32_t n_rows, uint32_t n_cols)
+    {
+        const int L = args.saturation_points;
+        std::vector<uint64_t> curve((size_t)L * 8, 0);
+        if (nb) {
+            need_ctx();
+            if (!lib.saturation_curve) die("libumihip.so lacks umi_saturation_curve");
+            std::vector<uint32_t> read_entry(n_rec);
+            for (uint32_t ri = 0; ri < n_rec; ri++) read_entry[ri] = info[ri].state == 0 ? entry_of[ri] : UMI_READ_UNSTAGED;
+            const std::vector<uint32_t> one_column(args.per_cell ? 0 : nb, 0u);
+            std::vector<uint8_t> cell_mask;
+            if (args.cell_filter_given) {
+                cell_mask.assign((size_t)n_cols + 1, 0);
+                for (size_t c = 0; c < called_col.size() && c < n_cols; c++) cell_mask[c] = called_col[c] != UINT32_MAX;
+            }
+            if (lib.saturation_curve(ctx, read_entry.data(), n_rec, survivors().data(), root.data(), off.data(), nb, bucket_gene.data(),
+                                     args.per_cell ? bucket_cell.data() : one_column.data(), n_rows, n_cols, args.saturation_seed, L,
+                                     args.cell_filter_given ? cell_mask.data() : nullptr, curve.data()) != UMI_OK)
+                die(lib.last_error());
+        }
+        std::string text = "depth\treads\tmolecules\tsaturation\tpairs\tcells\tmolecules_in_cells\tpairs_in_cells\tmedian_molecules\tmedian_genes\n";
+        for (int j = 0; j < L; j++) {
+            const uint64_t *c = &curve[(size_t)j * 8];
+            text.append(std::to_string(j + 1)).append("/").append(std::to_string(L)).append("\t");
+            text.append(std::to_string(c[0])).append("\t").append(std::to_string(c[1])).append("\t");
+            text.append(Summary::saturation_text(c[0], c[1]));
+            for (int k = 2; k < 8; k++) text.append("\t").append(std::to_string(c[k]));
+            text.append("\n");
+        }
+        FILE *f = std::fopen(args.saturation_curve.c_str(), "wb");
+        if (!f) die("cannot open " + args.saturation_curve);
+        const bool ok = std::fwrite(text.data(), 1, text.size(), f) == text.size();
+        if (std::fclose(f) != 0 || !ok) die("cannot write " + args.saturation_curve);
+        sum.saturation_reads = curve[(size_t)(L - 1) * 8];
+        sum.saturation_molecules = curve[(size_t)(L - 1) * 8 + 1];
+        lap("saturation curve");
     }
 
     // --velocity: the three layers of the matrix's triplets in one call over every read's entry and class, the mask
