@@ -142,6 +142,14 @@ const char *umi_last_error(void);
  *                    run, and a (block, run) costs one atomic and one stretch of stores where the 4^g sub-buckets
  *                    cost one each; a run above "seg_super_cap" goes through the pair kernel as one sub-bucket, a
  *                    hit kept only inside a sub-bucket (0: every entry under its own); same result and statistics
+ *   "seg_cross"      0/1 (default 1): where "seg_super_coarse" applies, the pairs that differ in one of the bases a run
+ *                    shares are read off the runs' bitmaps -- two such entries agree on every other base, so they are
+ *                    the set bits of the AND of two runs' maps -- and the second partition of the segment is counted
+ *                    but neither filed nor walked (0: through the pair kernel); same result and statistics.  A call
+ *                    that holds a key twice or a run above "seg_super_cap" is done again without the path, and so are
+ *                    the context's later calls until the option is set again
+ *   "seg_cross_map_mb" 0..64 (default 8): the maps of one segment, 4^umi_len / 8 bytes, may take this much (12 and 13
+ *                    bases by default; 64 MB per call)
  *   "seg_super_bases" 0..4 (default 0): g; 0 = the largest for which the other bases number at most 8 and the expected
  *                    run n / 4^(bin bases - g) lies between "seg_super_min" and 3/4 of "seg_super_cap", another
  *                    value = that g where those conditions hold (else none)
@@ -181,6 +189,10 @@ const char *umi_last_error(void);
  * collapse) and their options ("bitslice", "bs_*", "prune", "two_phase", "ovf_capacity") exist in the
  * development build only (make dev: libumihip_dev.so, -DUMIHIP_DEV), as cross-checks. */
 int umi_ctx_set_option(umi_ctx *ctx, const char *name, int64_t value);
+/* What a context has done since it was created, by name (for tests and tuning; the results of a call never depend on it):
+ *   "seg_cross_launches"  attempts of its batched calls in which the kernel of "seg_cross" was launched
+ *   "seg_cross_abandoned" calls that did their pair work again without that path (a key twice, a run above the cap) */
+int umi_ctx_get_counter(const umi_ctx *ctx, const char *name, uint64_t *out);
 /* Version of this header the library was built from (umi_stats grew in 2), for loaders */
 #define UMI_ABI_VERSION 2
 int umi_abi_version(void);

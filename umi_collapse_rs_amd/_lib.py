@@ -59,6 +59,7 @@ SIGNATURES = {
     "umi_ctx_destroy": (None, [C.c_void_p]),
     "umi_last_error": (C.c_char_p, []),
     "umi_ctx_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
+    "umi_ctx_get_counter": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64)]),
     "umi_abi_version": (C.c_int, []),
     "umi_encode_umis": (C.c_int, [_u8p, C.c_uint64, C.c_int, _u64p, _u64p]),
     "umi_encode_umis_wide": (C.c_int, [_u8p, C.c_uint64, C.c_int, C.c_int, _u64p, _u64p]),

@@ -94,6 +94,12 @@ class Context:
     def set_option(self, name, value):
         check(load().umi_ctx_set_option(self._h, name.encode(), int(value)))
 
+    def counter(self, name):
+        """what the context has done since it was created (umi_ctx_get_counter)"""
+        v = C.c_uint64(0)
+        check(load().umi_ctx_get_counter(self._h, name.encode(), C.byref(v)))
+        return int(v.value)
+
     def close(self):
         if getattr(self, "_h", None):
             load().umi_ctx_destroy(self._h)

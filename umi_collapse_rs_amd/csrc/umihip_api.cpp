@@ -118,6 +118,15 @@ void umi_ctx_destroy(umi_ctx *ctx)
     delete ctx;
 }
 
+int umi_ctx_get_counter(const umi_ctx *ctx, const char *name, uint64_t *out)
+{
+    if (!ctx || !name || !out) return fail(UMI_ERR_ARG, "ctx/name/out is NULL");
+    if (!strcmp(name, "seg_cross_launches")) *out = ctx->seg_cross_launches;
+    else if (!strcmp(name, "seg_cross_abandoned")) *out = ctx->seg_cross_abandoned_calls;
+    else return fail(UMI_ERR_ARG, "unknown counter '%s'", name);
+    return UMI_OK;
+}
+
 int umi_ctx_set_option(umi_ctx *ctx, const char *name, int64_t value)
 {
     if (!ctx || !name) return fail(UMI_ERR_ARG, "ctx/name is NULL");
@@ -199,6 +208,13 @@ int umi_ctx_set_option(umi_ctx *ctx, const char *name, int64_t value)
     } else if (!strcmp(name, "seg_super_coarse")) {
         if (value != 0 && value != 1) return fail(UMI_ERR_ARG, "seg_super_coarse must be 0 or 1");
         ctx->seg_super_coarse = value != 0;
+    } else if (!strcmp(name, "seg_cross")) {
+        if (value != 0 && value != 1) return fail(UMI_ERR_ARG, "seg_cross must be 0 or 1");
+        ctx->seg_cross = value != 0;
+        ctx->seg_cross_failed = false; // (armed again)
+    } else if (!strcmp(name, "seg_cross_map_mb")) {
+        if (value < 0 || value > 64) return fail(UMI_ERR_ARG, "seg_cross_map_mb must be in 0..64");
+        ctx->seg_cross_map_mb = (uint32_t)value;
     } else if (!strcmp(name, "seg_super_bases")) {
         if (value < 0 || value > SEG_SUPER_MAX_BASES) return fail(UMI_ERR_ARG, "seg_super_bases must be in 0..%d", SEG_SUPER_MAX_BASES);
         ctx->seg_super_bases = (int)value;

@@ -225,6 +225,13 @@ struct umi_ctx {
     bool seg_super = true;   // k = 1 without N: runs of 4^g adjacent part-0 bins decided as one unit in LDS (seg_super_kernel)
     bool seg_super_coarse = true; // ... and the counting sort files a part-0 entry of such a segment under its run's first
                                   // bin, not its own (SegArgs::super_coarse; 0 for A/B runs and as the tests' reference)
+    bool seg_cross = true;   // ... and the pairs between its super-bins are found by ANDing their rest-code maps: part 1 is
+                             // counted, not filed (SegDesc::cross, seg_cross_kernel)
+    bool seg_cross_failed = false; // a call of this context fell back (a key twice, a run above the cap): its later calls
+                                   // are planned without the path until "seg_cross" is set again
+    uint64_t seg_cross_launches = 0;        // attempts of this context's calls that launched seg_cross_kernel ...
+    uint64_t seg_cross_abandoned_calls = 0; // ... and calls that fell back (umi_ctx_get_counter)
+    uint32_t seg_cross_map_mb = umihip::SEG_CROSS_MAP_MB; // the maps of one segment, 4^umi_len / 8 bytes, at most
     int seg_super_bases = 0; // ... g (0: the planner's choice, choose_super_bases)
     uint32_t seg_super_cap = umihip::SEG_SUPER_CAP; // largest super-bin that kernel takes (LDS: 16 bytes per entry + 16 KB)
     uint32_t seg_super_min = umihip::SEG_SUPER_MIN; // smallest expected super-bin the path is planned for
@@ -238,6 +245,7 @@ struct umi_ctx {
     umihip::DevBuf plan_tables; // ranges, segment descriptors, scan chunks, popcount tile tasks: one upload
     umihip::DevBuf bs_tasks, plane_tasks, planes, tab_rows, tab_items;
     umihip::DevBuf seg_bin_cnt, seg_bin_start, seg_tasks, seg_sub_rec, seg_priv_edges, seg_priv_dist, seg_priv_cnt, seg_priv_stat;
+    umihip::DevBuf seg_cross_maps; // cross segments: the super-bins' rest-code maps, then the u16 prefixes of their words
     umihip::PinnedBuf h_plan_alt[2]; // staging of the plan's tables, in turn; [plan_flip ^ 1] = what plan_tables holds
     int plan_flip = 0;
     size_t plan_uploaded = 0;

@@ -44,7 +44,9 @@ enum Counter : int {
     CNT_UF_DIRECT = 15, // symmetric pairs the segment index's pair kernel united on the spot (not in the list)
     CNT_EDGES_MOVED = 16, // edges the flatten launch moved from the pair kernel's private slots to the list, behind
                           // the CNT_EDGES it found there (the list's length is the sum of the two)
-    CNT_COUNT = 17,
+    CNT_SEG_CROSS_ABANDONED = 17, // a super-bin of a cross segment could not be served (a key twice, a run above the cap):
+                                  // the call's cross pairs are to be found again through part 1 (a plain store of 1)
+    CNT_COUNT = 18,
 };
 // The flags of the collapse rounds ("round r changed a label") sit behind the counters in the
 // same device block, so that one memset clears and one copy reads everything the host looks at.
@@ -81,6 +83,11 @@ constexpr uint32_t SEG_NONE = 0xFFFFFFFFu;
 // (`--data ngram*` of the CLI, src/cli.rs:43-44, never implemented in the Rust port) prunes the
 // same way; the result is Naive's (src/data/naive.rs:26-40), which is all the reference ever runs.
 constexpr int SEG_MAX_PARTS = 8; // k + 1
+#if defined(__HIPCC__)
+#define UMIHIP_HD __host__ __device__
+#else
+#define UMIHIP_HD
+#endif
 struct SegDesc {
     uint32_t start, end;             // global entry range of the bucket
     uint32_t bin_off[SEG_MAX_PARTS]; // first bin of part j in the call's bin array
@@ -91,14 +98,22 @@ struct SegDesc {
     uint8_t sup_g;                   // super-bin exponent of part 0 (seg_super_kernel): 4^sup_g adjacent part-0 bins --
                                      // they share the upper nb[0] - sup_g bases of the bin code and lie back to back in
                                      // the sub-bucket arrays -- are decided as one unit in LDS; 0: none
-    uint8_t sup_pad[7];              // (zero: the plan's tables are compared byte by byte)
+    uint8_t cross;                   // 1: the pairs that differ in a base the super-bins share are found by ANDing the
+                                     // super-bins' rest-code maps (seg_cross_kernel) -- part 1 is counted, not filed
+    uint8_t sup_pad[6];              // (zero: the plan's tables are compared byte by byte)
 };
 // One super-bin: the part-0 bins [bin0, bin0 + 4^g) of a segment whose part 0 is indexed by nb bases and leaves
 // rest = umi_len - nb + g bases to tell its entries apart
 struct SegSuper {
     uint32_t bin0;
-    uint8_t g, nb, rest, pad;
+    uint8_t g, nb, rest, cross; // cross: SegDesc::cross of its segment
+    uint32_t seg;               // its segment
+    uint32_t map0;              // cross: first word of its rest-code map in SegArgs::cross_map (4^rest / 32 words; the
+                                // segment's maps lie back to back in super-bin order)
 };
+static_assert(sizeof(SegSuper) == 16, "no padding: the plan's tables are compared byte by byte");
+// words of a super-bin's rest-code map (rest >= 4: a segment's part 0 takes half the bases at most)
+UMIHIP_HD inline uint32_t seg_cross_words(uint32_t rest) { return rest >= 3u ? 1u << (2u * rest - 5u) : 1u; }
 // An entry in sub-bucket order: everything the pair kernel needs of it, 16 bytes
 struct SegRec32 {
     uint32_t key; // filter key
@@ -132,11 +147,6 @@ struct SegTask {
     uint32_t col0;
     uint32_t where; // segment | part << 24 | e << 28
 };
-#if defined(__HIPCC__)
-#define UMIHIP_HD __host__ __device__
-#else
-#define UMIHIP_HD
-#endif
 UMIHIP_HD inline uint32_t seg_chunks_of(uint32_t c) { return c >= 2 ? (c - 1 + 63) / 64 : 0u; } // nt
 UMIHIP_HD inline uint32_t seg_span_log2(uint32_t nt)
 {
@@ -301,6 +311,12 @@ struct SegArgs {
     // ... and the pairs inside the fine bins of such a segment's part 0 (CNT_SEG_PAIRS), which the scan can no longer
     // see, are counted by seg_super_kernel (0 in the launch of a second attempt: they are counted once)
     uint32_t super_count_pairs;
+    // Cross segments (SegDesc::cross): seg_super_kernel stores every super-bin's rest-code map, the set bits before each
+    // of its words and (entry index, freq) by rank -- the last in the part-1 half of sub_rec, which the scatter leaves
+    // free in such a segment: super-bin at position `start` of part 0, rank r -> the uint2 at
+    // (uint2 *)(sub_rec + bin_start[bin_off[1]]) + (start - bin_start[bin_off[0]]) + r.  seg_cross_kernel reads them.
+    uint32_t *cross_map;
+    uint16_t *cross_pre;
 #ifdef UMIHIP_DEV
     // development build: where seg_super_kernel's blocks add up the time they spend in each of their phases
     // ([blocks][SEG_SUPER_PHASES] ticks of the 100 MHz clock, zeroed by the host; null: no stamps)
@@ -354,6 +370,16 @@ uint32_t seg_super_blocks(uint32_t n_supers, uint32_t n_cus);
 // written to g.uf_parent as seg_local_kernel does, one-way ones to the waves' private slots (g.priv_* point at the
 // first of n_blocks * (threads / 64) slots).  A launch of its own ahead of the pair kernel, as launch_seg_local.
 hipError_t launch_seg_super(const PairArgs &a, const SegArgs &g, float percentage, uint32_t n_blocks, hipStream_t s);
+// The pairs of the cross segments that differ in one base their super-bins share: two such entries have the same
+// rest-code and lie in super-bins whose codes differ in that base, so they are the set bits of the AND of two maps.
+// Persistent one-wave blocks, a private slot and a priv_stat entry each (g.priv_* point at the first of n_blocks
+// slots); symmetric pairs united through g.uf_parent.  Behind launch_seg_super in stream order.  Does nothing in a
+// call whose CNT_SEG_CROSS_ABANDONED is set.
+constexpr uint32_t SEG_CROSS_CHUNKS = SEG_SUPER_WORDS / 64u; // 64-word chunks of the largest map: work items per super-bin
+constexpr int SEG_CROSS_MAX_SHARED = 8;                      // bases a segment's super-bins can share (nb <= 8, g >= 1)
+constexpr uint64_t SEG_CROSS_CALL_BYTES = 64ull << 20;       // maps of one call
+constexpr uint32_t SEG_CROSS_MAP_MB = 8;                     // default "seg_cross_map_mb": maps of one segment (12, 13 bp)
+hipError_t launch_seg_cross(const PairArgs &a, const SegArgs &g, float percentage, uint32_t n_blocks, hipStream_t s);
 size_t seg_local_lds_bytes(uint32_t cap);
 int seg_local_blocks_per_cu(bool has_n, uint32_t cap);
 hipError_t launch_seg_local(const PairArgs &a, const SegArgs &g, float percentage, uint32_t n_blocks, hipStream_t s);

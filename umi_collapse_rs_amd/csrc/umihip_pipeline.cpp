@@ -204,6 +204,7 @@ class Pipeline {
                                            // slots the collapse's flatten launch appends to the list (0: appended already)
     uint64_t seg_local_bins = 0; // part-0 bins of the call's segments (the local kernel's grid at most)
     bool super_pairs_counted = false; // seg_super_kernel has run with SegArgs::super_count_pairs in this call
+    uint32_t launches_before_attempt = 0; // st.n_pair_launches when run_one_sync's attempt in hand began
     umi_stats st;
     unsigned long long *d_cnt = nullptr;
     size_t n_tasks = 0;              // tile tasks of the pair kernels (fused buckets excluded)
@@ -361,6 +362,10 @@ class Pipeline {
         sup.bases = ctx->seg_super_bases;
         sup.cap = ctx->seg_super_cap;
         sup.min = ctx->seg_super_min;
+        // ... and the cross path where part 0 is filed by super-bin (configure_seg takes the bits back if the call turns
+        // out to be none seg_super_kernel runs in)
+        sup.cross = sup.on && ctx->seg_cross && !ctx->seg_cross_failed && ctx->seg_super_coarse && ctx->seg_lds && k == 1;
+        sup.cross_map_mb = ctx->seg_cross_map_mb;
         build_plan(bucket_off, n_buckets, wide() || edit ? 0x7FFFFFFFu : ctx->small_max,
                    ctx->use_bitslice && k <= BS_MAX_K && !wide() && !edit && dev_tiles,
                    plan_umi_len(), fused_max, ctx->prune && dev_tiles, ctx->bs_sorted && ctx->bs_unit == 2 && need_pairs && dev_tiles,
@@ -436,6 +441,32 @@ class Pipeline {
         return UMI_OK;
     }
 
+    // the plan without the cross path: every segment's part 1 is filed and walked again
+    void strip_cross()
+    {
+        for (SegDesc &sd : pl.segs) sd.cross = 0;
+        for (SegSuper &su : pl.seg_supers) {
+            su.cross = 0;
+            su.map0 = 0;
+        }
+        pl.seg_cross = pl.seg_cross_words = 0;
+    }
+    // ... uploaded in place of the one the device holds (same sizes: the tables stay where they are)
+    int upload_stripped_plan()
+    {
+        int rc;
+        strip_cross();
+        if ((rc = upload_plan())) return rc;
+        seg.segs = d_segs;
+        seg.chunks = d_chunks;
+        seg.ranges = d_ranges;
+        if (seg.blocks) seg.blocks = d_seg_blocks;
+        if (seg.supers) seg.supers = d_supers;
+        seg.cross_map = nullptr;
+        seg.cross_pre = nullptr;
+        return UMI_OK;
+    }
+
     // what the segment index's kernels of this call work with (SegArgs over the uploaded tables): its workspace,
     // compare keys, super-bins, the local kernel and its probe, the LDS counting sort; the bin counters cleared
     int configure_seg()
@@ -504,7 +535,19 @@ class Pipeline {
                 // (the per-entry path of the counting sort files by fine bin, prep_kernel's histogram with it)
                 seg.super_coarse = super_on && ctx->seg_super_coarse ? 1u : 0u;
             }
+            if (pl.seg_cross) {
+                // the cross path: a call seg_super_kernel runs in, part 0 filed by super-bin
+                if (!(super_on && seg.super_coarse)) {
+                    if ((rc = upload_stripped_plan())) return rc;
+                } else {
+                    if ((rc = ctx->seg_cross_maps.reserve(pl.seg_cross_words * (sizeof(uint32_t) + sizeof(uint16_t))))) return rc;
+                    seg.cross_map = ctx->seg_cross_maps.as<uint32_t>();
+                    seg.cross_pre = (uint16_t *)(seg.cross_map + pl.seg_cross_words);
+                }
+            }
             if (!zero_behind_control) HIP_TRY(hipMemsetAsync(seg.bin_cnt, 0, zero_bytes, s));
+        } else if (pl.seg_cross) {
+            strip_cross(); // (no kernel of the index runs: nothing on the device reads the bits)
         }
         return UMI_OK;
     }
@@ -893,7 +936,15 @@ class Pipeline {
             // ... and the super-bin kernel's waves the ones in between
             const uint32_t super_blocks = seg.super_cap ? seg_super_blocks(seg.n_supers, (uint32_t)ctx->n_cus) : 0u;
             const uint32_t super_slots = super_blocks * (seg_super_threads(seg.super_cap) / 64u);
-            const size_t slots = (size_t)local_blocks + super_slots + blocks;
+            // ... then the pair kernel's, where a segment is left to it, and the cross kernel's (work items: 64-word
+            // chunks of the super-bins' maps)
+            const uint32_t pair_blocks = pl.seg_cross < pl.segs.size() ? blocks : 0u;
+            const uint32_t cross_blocks = pl.seg_cross && super_blocks
+                                              ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)seg.n_supers * SEG_CROSS_CHUNKS,
+                                                    ctx->seg_blocks ? ctx->seg_blocks : (uint64_t)ctx->n_cus * 16u))
+                                              : 0u;
+            if (pl.seg_cross && !cross_blocks) return fail(UMI_ERR_HIP, "internal: cross segments planned without super-bins");
+            const size_t slots = (size_t)local_blocks + super_slots + pair_blocks + cross_blocks;
             if ((rc = ctx->seg_priv_edges.reserve(slots * SEG_PRIV_CAP * sizeof(uint2))) ||
                 (rc = ctx->seg_priv_cnt.reserve(slots * 4)) || (rc = ctx->seg_priv_stat.reserve(slots * sizeof(uint2))) ||
                 (mode == MODE_NEIGHBOURS && (rc = ctx->seg_priv_dist.reserve((size_t)blocks * SEG_PRIV_CAP))))
@@ -962,14 +1013,22 @@ class Pipeline {
                 }
             }
 #endif
-            HIP_TRY(launch_seg_pairs(a, pair_seg, key32, percentage, part, n_parts, blocks, s));
+            if (pair_blocks) HIP_TRY(launch_seg_pairs(a, pair_seg, key32, percentage, part, n_parts, pair_blocks, s));
+            if (cross_blocks) {
+                SegArgs cross_seg = pair_seg;
+                cross_seg.priv_edges += (size_t)pair_blocks * SEG_PRIV_CAP;
+                cross_seg.priv_cnt += pair_blocks;
+                cross_seg.priv_stat += pair_blocks; // (cross segments: the slots go to the collapse)
+                HIP_TRY(launch_seg_cross(a, cross_seg, percentage, cross_blocks, s));
+                ctx->seg_cross_launches++;
+            }
             if (prof) HIP_TRY(hipEventRecord(ctx->ev[8], s));
             seg_timed = true;
             // what the blocks still hold in their private slots: one-way pairs only when the symmetric
             // ones were united where they were found, and then the collapse's flatten launch moves them
             // to the list (collapse_desc); else two small launches here, ahead of the list's unions
             priv_blocks_for_collapse = slots_to_collapse ? (uint32_t)slots : 0u;
-            if (!priv_blocks_for_collapse) HIP_TRY(launch_seg_edge_append(a, seg, blocks, s));
+            if (!priv_blocks_for_collapse) HIP_TRY(launch_seg_edge_append(a, seg, pair_blocks, s));
             st.n_pair_launches += 1;
         }
         if ((rc = enqueue_legacy_tiles(a))) return rc;
@@ -1108,7 +1167,8 @@ class Pipeline {
         // one-way pairs down a freq ladder) takes five or six where a uniform one takes three, and each look
         // of the host in between costs a wait and a second finalize pass
         const int ahead = std::min(std::max(ctx->dag_rounds_ahead, DAG_ROUNDS), MAX_ROUNDS_PER_SYNC);
-        for (int attempt = 0;; attempt++) {
+        for (int attempt = 0;;) { // (attempt: the edge list's retries)
+            launches_before_attempt = st.n_pair_launches;
             if (have_pairs) {
                 uint64_t ovf_cap = 0;
                 if ((rc = reserve_lists(cap, ovf_cap))) return rc;
@@ -1136,8 +1196,19 @@ class Pipeline {
             }
             if ((rc = read_control())) return rc;
             if ((rc = note_pair_counters())) return rc;
-            if (n_edges <= cap || !have_pairs) break;
-            if ((rc = grow_edge_list(cap, attempt))) return rc;
+            // a super-bin the cross path could not serve (a key twice, a run above the cap): the pair work again without
+            // the path, everything the attempt has counted or united reset as for the edge list's retry
+            const bool abandoned = have_pairs && pl.seg_cross && ctx->h_counters[CNT_SEG_CROSS_ABANDONED] != 0;
+            // (an abandoned attempt's edge count is a part of the call's: the list grows by the next attempt's, as it
+            // does in a call without the path)
+            const bool over = have_pairs && !abandoned && n_edges > cap;
+            if (!abandoned && !over) break;
+            if (over) {
+                if ((rc = grow_edge_list(cap, attempt++))) return rc;
+            } else {
+                HIP_TRY(hipMemsetAsync(&d_cnt[CNT_EDGES], 0, 2 * sizeof(unsigned long long), s));
+            }
+            if (abandoned && (rc = drop_cross())) return rc;
             HIP_TRY(hipMemsetAsync(&d_cnt[CNT_KEPT], 0, sizeof(unsigned long long), s));
             HIP_TRY(hipMemsetAsync(&d_cnt[CNT_UF_DIRECT], 0, 2 * sizeof(unsigned long long), s));
             if (!cluster) HIP_TRY(hipMemsetAsync(ctx->d_changed(), 0, CTRL_BYTES - CTRL_FLAGS_OFF, s)); // flags and sync words
@@ -1150,6 +1221,26 @@ class Pipeline {
         else if ((rc = directional_rounds_end(have_pairs, ahead)))
             return rc;
         return finish_stats();
+    }
+
+    // The cross path's fallback: the context plans without it from now on ("seg_cross" arms it again), the plan's
+    // cross bits are cleared, and the index is built again with part 1 -- the entries are prepared, so the count kernel
+    // only counts.  The abandoned attempt's launch is not one of the call's.
+    int drop_cross()
+    {
+        int rc;
+        ctx->seg_cross_failed = true;
+        if ((rc = upload_stripped_plan())) return rc;
+        seg.prep_keys = nullptr;
+        HIP_TRY(hipMemsetAsync(seg.bin_cnt, 0, seg_zero_bytes(), s));
+        static_assert(CNT_SEG_PAIRS == CNT_SEG_TASKS + 1, "one fill");
+        HIP_TRY(hipMemsetAsync(&d_cnt[CNT_SEG_TASKS], 0, 2 * sizeof(unsigned long long), s));
+        HIP_TRY(hipMemsetAsync(&d_cnt[CNT_SEG_CROSS_ABANDONED], 0, sizeof(unsigned long long), s));
+        HIP_TRY(launch_seg_build(seg, ctx->fkey.p, d_freq, key32, d_cnt, s));
+        super_pairs_counted = false;
+        st.n_pair_launches = launches_before_attempt; // (every pair launch of the attempt: the tiles of mid-size buckets too)
+        ctx->seg_cross_abandoned_calls++;
+        return UMI_OK;
     }
 
     // the directional collapse behind the unions: forest flattened, ahead - 1 rounds, finalize with the check round

@@ -44,6 +44,8 @@ struct Plan {
     std::vector<SegBlock> seg_blocks; // entry blocks of the counting sort's LDS path
     std::vector<SegSuper> seg_supers; // super-bins of the segments with sup_g > 0
     uint64_t seg_plain = 0;           // segments with sup_g == 0 (the one-wave local kernel's)
+    uint64_t seg_cross = 0;           // segments with SegDesc::cross
+    uint64_t seg_cross_words = 0;     // words of their super-bins' rest-code maps
     uint32_t seg_max_bins = 0;        // most bins any part of any segment has
     int seg_max_rest = 0;             // most bases any part of any segment leaves outside its bins
     int seg_parts = 0;           // k + 1 (0: no segment in this call)
@@ -191,6 +193,10 @@ struct SegSuperOpt {
     bool on = false;
     int bases = 0;
     uint32_t cap = SEG_SUPER_CAP, min = SEG_SUPER_MIN;
+    // the cross path (SegDesc::cross): the caller says whether the call is one it may run in -- option "seg_cross", a
+    // call seg_super_kernel runs in, part 0 filed by super-bin by the LDS counting sort
+    bool cross = false;
+    uint32_t cross_map_mb = SEG_CROSS_MAP_MB; // rest-code maps of one segment, MB at most
 };
 // The exponent g for a segment of n entries whose part 0 is indexed by nb0 bases: the largest g for which the
 // rest-code (the bases outside the shared ones) fits the bitmap and the expected super-bin n / 4^(nb0 - g) lies
@@ -206,6 +212,18 @@ inline int choose_super_bases(uint64_t n, int umi_len, int nb0, const SegSuperOp
         return g;
     }
     return 0;
+}
+
+// Does a segment of umi_len bases with super-bin exponent sup_g find its cross pairs -- those that differ in one of the
+// bases its super-bins share -- by ANDing the super-bins' rest-code maps?  The maps of a segment are 4^umi_len bits
+// whatever g is: they must fit "seg_cross_map_mb", and those of a call (used_bytes so far) SEG_CROSS_CALL_BYTES.
+// (sup_g > 0 already says k = 1, 32-bit keys, no N mask; a segment of one super-bin, g = nb0, has no such pair and
+// qualifies like any other.)
+inline bool choose_cross(int umi_len, int sup_g, const SegSuperOpt &o, uint64_t used_bytes = 0)
+{
+    if (!o.on || !o.cross || sup_g <= 0 || umi_len > 16) return false;
+    const uint64_t bytes = (1ull << (2 * umi_len)) / 8;
+    return bytes <= ((uint64_t)o.cross_map_mb << 20) && used_bytes + bytes <= SEG_CROSS_CALL_BYTES;
 }
 
 inline void plan_segment(Plan &pl, uint64_t s, uint64_t e, int umi_len, int k, bool key32,
@@ -227,6 +245,7 @@ inline void plan_segment(Plan &pl, uint64_t s, uint64_t e, int umi_len, int k, b
         sd.mask[j] = 0;
     }
     sd.sup_g = 0;
+    sd.cross = 0;
     for (uint8_t &b : sd.sup_pad) b = 0;
     for (int j = 0; j < P; j++) {
         const int b0 = j * umi_len / P, b1 = (j + 1) * umi_len / P;
@@ -247,9 +266,17 @@ inline void plan_segment(Plan &pl, uint64_t s, uint64_t e, int umi_len, int k, b
     }
     if (k == 1 && key32) sd.sup_g = (uint8_t)choose_super_bases(n, umi_len, sd.nb[0], sup);
     if (sd.sup_g) { // (k = 1: part 1's first bin follows part 0's last, so every run has a next bin_start word)
-        const uint32_t g = sd.sup_g, nb0 = sd.nb[0];
+        const uint32_t g = sd.sup_g, nb0 = sd.nb[0], rest = (uint32_t)umi_len - nb0 + g;
+        // (seg_cross_words shifts by 2 rest - 5: part 0 holds half the bases at most and g >= 1, so rest >= 4 wherever the
+        // segment index applies; a shorter rest-code has no map)
+        sd.cross = rest >= 3 && choose_cross(umi_len, sd.sup_g, sup, pl.seg_cross_words * 4) ? 1 : 0;
         for (uint32_t sb = 0; sb < (1u << (2 * (nb0 - g))); sb++)
-            pl.seg_supers.push_back({sd.bin_off[0] + (sb << (2 * g)), (uint8_t)g, (uint8_t)nb0, (uint8_t)(umi_len - nb0 + g), 0});
+            pl.seg_supers.push_back({sd.bin_off[0] + (sb << (2 * g)), (uint8_t)g, (uint8_t)nb0, (uint8_t)rest, sd.cross, seg,
+                                     sd.cross ? (uint32_t)pl.seg_cross_words + sb * seg_cross_words(rest) : 0u});
+        if (sd.cross) {
+            pl.seg_cross++;
+            pl.seg_cross_words += (uint64_t)seg_cross_words(rest) << (2 * (nb0 - g));
+        }
     } else {
         pl.seg_plain++;
     }
@@ -381,6 +408,7 @@ inline void build_plan(const uint64_t *bucket_off, uint64_t n_buckets, uint32_t 
     pl.seg_blocks.clear();
     pl.seg_supers.clear();
     pl.seg_plain = 0;
+    pl.seg_cross = pl.seg_cross_words = 0;
     pl.seg_max_bins = 0;
     pl.seg_max_rest = 0;
     pl.seg_parts = 0;

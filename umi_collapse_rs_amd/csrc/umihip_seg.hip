@@ -86,6 +86,9 @@ __global__ __launch_bounds__(SCAN_THREADS) void seg_scan_kernel(SegArgs g, unsig
         for (int q = 0; q < SCAN_PER_THREAD; q++)
             if (local_bin(g, ch.part, c[q])) no_tasks |= 1u << q;
     }
+    // a cross segment has no tile tasks at all: seg_super_kernel and seg_cross_kernel decide its pairs between them (a
+    // super-bin they cannot serve sends the whole call back through the index: CNT_SEG_CROSS_ABANDONED)
+    if (g.segs[ch.seg].cross) no_tasks = (1u << SCAN_PER_THREAD) - 1u; // (block-uniform)
 #pragma unroll
     for (int q = 0; q < SCAN_PER_THREAD; q++) mine.y += (no_tasks >> q) & 1u ? 0u : seg_tasks_of_bin(c[q]);
     uint2 incl = mine;
@@ -375,8 +378,10 @@ __global__ __launch_bounds__(SEG_BLOCK_THREADS) void seg_scatter_lds_kernel(SegA
     const SegDesc *__restrict__ sd = g.segs + blk.seg;
     const uint32_t cg = coarse_bases(g, blk.seg); // (block-uniform)
     Rec *__restrict__ sub = (Rec *)g.sub_rec;
-    for (int j0 = 0; j0 < g.n_parts; j0 += (int)g.parts_per_pass) {
-        const SegPass ps = seg_pass_of(sd, j0, g.n_parts, (int)g.parts_per_pass, cg);
+    // (a cross segment files part 0 alone: nobody reads its part 1, whose positions hold seg_super_kernel's ranks)
+    const int n_parts = sd->cross ? 1 : g.n_parts; // (block-uniform)
+    for (int j0 = 0; j0 < n_parts; j0 += (int)g.parts_per_pass) {
+        const SegPass ps = seg_pass_of(sd, j0, n_parts, (int)g.parts_per_pass, cg);
         seg_block_histogram(blk, fkey, ps, hist);
         // the block's run inside every bin it has entries for: the counter becomes its first position
         for (uint32_t c = threadIdx.x; c < ps.total; c += SEG_BLOCK_THREADS) {
@@ -1432,6 +1437,31 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
         const uint32_t start = __builtin_amdgcn_readfirstlane(g.bin_start[su.bin0]);
         const uint32_t c = __builtin_amdgcn_readfirstlane(g.bin_start[su.bin0 + (1u << (2 * su.g))]) - start;
         const uint32_t lo_bits = 2u * su.g, hi_shift = 2u * su.nb, rest = su.rest;
+        // cross segment: where this super-bin's map, prefix and ranks go (SegArgs::cross_map)
+        uint32_t *__restrict__ x_map = nullptr;
+        uint16_t *__restrict__ x_pre = nullptr;
+        uint2 *__restrict__ x_rec = nullptr;
+        if (su.cross) {
+            const SegDesc *__restrict__ sd = g.segs + su.seg;
+            x_map = g.cross_map + su.map0;
+            x_pre = g.cross_pre + su.map0;
+            x_rec = (uint2 *)((SegRec32 *)g.sub_rec + g.bin_start[sd->bin_off[1]]) + (start - g.bin_start[sd->bin_off[0]]);
+        }
+        if (su.cross && c < 2u) { // empty or a single entry: no pair inside, but its map has partners -- no phase chain for it
+            uint32_t code = 0xFFFFFFFFu;
+            if (c == 1u) {
+                const SegRec32 rec = sub[start];
+                const uint32_t hb = 2u * rest - lo_bits;
+                code = ((rec.key >> hi_shift) & ((1u << hb) - 1u)) | ((rec.key & ((1u << lo_bits) - 1u)) << hb);
+                if (tid == 0) {
+                    x_pre[code >> 5] = 0;
+                    x_rec[0] = make_uint2(rec.idx, (uint32_t)rec.freq);
+                }
+            }
+            for (uint32_t w = tid; w < seg_cross_words(rest); w += NT) x_map[w] = w == (code >> 5) ? 1u << (code & 31u) : 0u;
+            continue;
+        }
+        if (su.cross && c > cap && tid == 0) a.counters[CNT_SEG_CROSS_ABANDONED] = 1ull; // (a plain store: every block writes 1)
         if (!super_taken(g, c)) { // (block-uniform)
             if (g.super_count_pairs && c >= 2u) { // above the cap, the tiles' own: its keys once more, for that count alone
                 for (uint32_t w = tid; w < SUPER_FINE; w += NT) fine[w] = 0u;
@@ -1472,6 +1502,7 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
             }
         const bool dup = __syncthreads_or(twice ? 1 : 0) != 0;
         stamp(1);
+        if (dup && su.cross && tid == 0) a.counters[CNT_SEG_CROSS_ABANDONED] = 1ull; // (no rank per code here)
         if (dup && g.super_count_pairs) { // (the map holds fewer bits than there are entries: counted one by one)
 #pragma unroll
             for (int r = 0; r < SUPER_RPT; r++)
@@ -1518,6 +1549,13 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
                 }
             __syncthreads();
             stamp(2);
+            if (su.cross) { // what seg_cross_kernel reads: plain coalesced stores, nothing waits for them
+                for (uint32_t w = tid; w < seg_cross_words(rest); w += NT) {
+                    x_map[w] = bm[w];
+                    x_pre[w] = (uint16_t)pre[w];
+                }
+                for (uint32_t p = tid; p < c; p += NT) x_rec[p] = make_uint2(ix[p], fr[p]);
+            }
 #pragma unroll
             for (int r = 0; r < SUPER_RPT; r++) {
                 if ((uint32_t)r * NT >= c) break; // (block-uniform)
@@ -1615,6 +1653,164 @@ __global__ __launch_bounds__(NT) void seg_super_kernel(PairArgs a, SegArgs g, fl
         __syncthreads(); // (a block without a super-bin of its own has met no barrier yet)
         if (tid == 0 && fine_pairs) atomicAdd(&a.counters[CNT_SEG_PAIRS], fine_pairs);
     }
+}
+
+// ---- cross segments: the pairs between super-bins (k = 1, no N in the call) -------------------------------
+// A pair that seg_super_kernel does not see differs in one of the nb - g bases a super-bin shares, and in nothing
+// else: the two entries have the same rest-code and lie in super-bins S and S' = S ^ (d << 2 b), d = 1..3, b one of
+// those bases.  seg_super_kernel has left every super-bin's rest-code map, so these pairs are the set bits of
+// map_S[w] & map_S'[w] -- a word AND where part 1 of the index would file every entry again and walk its bins' tiles.
+// A pair is found once, from its smaller super-bin code.
+// One wave per block, persistent.  Work items are computed: (super-bin, 64-word chunk of its map), SEG_CROSS_CHUNKS
+// per super-bin whatever the map's length (the chunks past its end are skipped), a block takes a contiguous run of
+// them -- mostly one super-bin's, whose hits share a queue.  Lane = word: the lane's own word, then the same word of
+// every partner with the larger code, all loads issued before the first is looked at.  A hit is one queue word (word
+// index, bit, partner number); 64 at a time they are decided as seg_super_kernel's are: both ranks from the prefix
+// and the bits below, the two (entry index, freq) records, rank order, the freq predicate both ways; a symmetric pair
+// is united through uf_parent, a one-way pair goes to the block's private slot.
+constexpr uint32_t CROSS_DRAIN_AT = 64;
+constexpr uint32_t CROSS_HITQ = CROSS_DRAIN_AT + 64;
+constexpr int CROSS_MAX_PARTNERS = 3 * SEG_CROSS_MAX_SHARED;
+static_assert(SEG_SUPER_WORDS <= (1u << 11) && CROSS_MAX_PARTNERS <= 32, "word index, bit and partner number in one queue word");
+
+template <bool CLUSTER>
+__global__ __launch_bounds__(64) void seg_cross_kernel(PairArgs a, SegArgs g, float percentage)
+{
+    __shared__ uint32_t hitq[CROSS_HITQ]; // word index | bit << 11 | partner number << 16
+    const int lane = threadIdx.x;
+    unsigned int n_cand = 0, n_direct = 0;
+    uint32_t n_out = 0; // (wave-uniform)
+    uint2 *__restrict__ slot = g.priv_edges + (size_t)blockIdx.x * SEG_PRIV_CAP;
+    // one-way pairs: to this block's private slot; a slot that is full sends the rest to the list, one atomic per
+    // wave and batch (seg_super_kernel's emit)
+    auto emit = [&](bool has, uint32_t u, uint32_t v) {
+        const unsigned long long bal = __ballot(has);
+        if (!bal) return;
+        const uint32_t cnt = (uint32_t)__builtin_popcountll(bal);
+        const uint32_t pos = n_out + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1ull));
+        unsigned long long base = 0;
+        if (n_out + cnt > SEG_PRIV_CAP) {
+            const uint32_t first_over = max(n_out, SEG_PRIV_CAP);
+            const int leader = __builtin_ctzll(bal);
+            if (lane == leader) base = atomicAdd(&a.counters[CNT_EDGES], (unsigned long long)(n_out + cnt - first_over));
+            base = __shfl(base, leader);
+            base -= first_over;
+        }
+        if (has) {
+            if (pos < SEG_PRIV_CAP) slot[pos] = make_uint2(u, v);
+            else if (base + pos < a.edge_cap) a.edges[base + pos] = make_uint2(u, v);
+        }
+        n_out += cnt;
+    };
+    // the super-bin in hand (wave-uniform): its code inside the segment, the segment's first map word, its map's words,
+    // its own first map word, where the segment's ranks lie and how many, its first part-0 position and bin
+    uint32_t have_u = 0xFFFFFFFFu, sb = 0, seg_map0 = 0, W = 0, my_map0 = 0, my_rec0 = 0, seg_entries = 1, seg_pos0 = 0, seg_bin0 = 0;
+    uint32_t n_shared = 0, g2 = 0;
+    const uint2 *__restrict__ seg_rec = nullptr;
+    uint32_t nq = 0; // (wave-uniform)
+    // the newest 64 hits of the queue, one per lane (fewer only in the drain that empties it)
+    auto drain = [&]() {
+        const uint32_t n = min(nq, 64u);
+        nq -= n;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const bool has = (uint32_t)lane < n;
+        const uint32_t h = has ? hitq[nq + (uint32_t)lane] : 0u;
+        const uint32_t w = h & 0x7FFu, bit = (h >> 11) & 31u, pn = h >> 16;
+        const uint32_t b = pn / 3u, d = pn - 3u * b + 1u;
+        const uint32_t sbp = has ? sb ^ (d << (2u * b)) : sb; // (an idle lane: this super-bin twice, nothing decided)
+        const uint32_t wa_at = my_map0 + w, wb_at = seg_map0 + sbp * W + w;
+        const uint32_t wa = g.cross_map[wa_at], wb = g.cross_map[wb_at];
+        const uint32_t pa = g.cross_pre[wa_at], pb = g.cross_pre[wb_at];
+        const uint32_t start_b = g.bin_start[seg_bin0 + (sbp << g2)];
+        const uint32_t below = (1u << bit) - 1u;
+        // (a rank is below its super-bin's count by construction; the clamp keeps a load inside the segment whatever it reads)
+        const uint32_t ra = min(my_rec0 + pa + (uint32_t)__builtin_popcount(wa & below), seg_entries - 1u);
+        const uint32_t rb = min(start_b - seg_pos0 + pb + (uint32_t)__builtin_popcount(wb & below), seg_entries - 1u);
+        const uint2 ea = seg_rec[ra], eb = seg_rec[rb];
+        const uint32_t ia = ea.x, ib = eb.x;
+        const int32_t fa = (int32_t)ea.y, fb = (int32_t)eb.y;
+        // entry indices in rank order (src/algo/directional.rs:67-72)
+        const bool sw = ib < ia;
+        const uint32_t gi = sw ? ib : ia, gj = sw ? ia : ib;
+        const int32_t fi = sw ? fb : fa, fj = sw ? fa : fb;
+        const bool ok = has && gi != gj && gj < a.n_entries;
+        if (ok) n_cand++;
+        // naive.rs:31 under directional.rs:38-39
+        const bool fwd = ok && (CLUSTER || fj <= threshold_of(percentage, fi));
+        const bool bwd = ok && (CLUSTER || fi <= threshold_of(percentage, fj));
+        uint32_t uu[1] = {gi}, uv[1] = {gj};
+        bool unite[1] = {fwd && bwd}; // reachability inside such a set is symmetric: one set
+        if (unite[0]) n_direct++;
+        uf_union_multi<1>(g.uf_parent, uu, uv, unite);
+        emit(fwd != bwd, fwd ? gi : gj, fwd ? gj : gi);
+        __builtin_amdgcn_wave_barrier(); // (the queue is read before the next push writes it)
+    };
+
+    // (a super-bin that could not be served has left no map: the host does this call's cross pairs again through part 1)
+    const bool abandoned = a.counters[CNT_SEG_CROSS_ABANDONED] != 0ull;
+    const uint32_t n_items = abandoned ? 0u : g.n_supers * SEG_CROSS_CHUNKS;
+    const uint32_t per = (n_items + gridDim.x - 1u) / gridDim.x;
+    const uint32_t it0 = min(n_items, blockIdx.x * per), it1 = min(n_items, it0 + per);
+    for (uint32_t it = it0; it < it1; it++) {
+        const uint32_t u = it / SEG_CROSS_CHUNKS, chunk = it % SEG_CROSS_CHUNKS;
+        if (u != have_u) { // (wave-uniform)
+            while (nq) drain(); // the queued hits belong to the super-bin in hand
+            have_u = u;
+            const SegSuper su = g.supers[u];
+            W = 0u;
+            if (su.cross) {
+                const SegDesc *__restrict__ sd = g.segs + su.seg;
+                g2 = 2u * su.g;
+                n_shared = (uint32_t)su.nb - su.g;
+                seg_bin0 = sd->bin_off[0];
+                sb = (su.bin0 - seg_bin0) >> g2;
+                W = seg_cross_words(su.rest);
+                my_map0 = su.map0;
+                seg_map0 = su.map0 - sb * W;
+                seg_pos0 = g.bin_start[seg_bin0];
+                my_rec0 = g.bin_start[su.bin0] - seg_pos0;
+                seg_entries = max(1u, sd->end - sd->start);
+                seg_rec = (const uint2 *)((const SegRec32 *)g.sub_rec + g.bin_start[sd->bin_off[1]]);
+            }
+        }
+        const uint32_t w = chunk * 64u + (uint32_t)lane;
+        if (chunk * 64u >= W) continue; // (past the map's end, or no cross segment's super-bin)
+        const bool live = w < W;
+        const uint32_t mine = live ? g.cross_map[my_map0 + w] : 0u;
+        uint32_t m[CROSS_MAX_PARTNERS];
+#pragma unroll
+        for (int b = 0; b < SEG_CROSS_MAX_SHARED; b++) {
+#pragma unroll
+            for (int d = 1; d <= 3; d++) {
+                const uint32_t sbp = sb ^ ((uint32_t)d << (2 * b));
+                const bool there = (uint32_t)b < n_shared && sbp > sb; // (wave-uniform)
+                m[3 * b + d - 1] = there && live ? g.cross_map[seg_map0 + sbp * W + w] : 0u;
+            }
+        }
+        for (uint32_t pn = 0; pn < 3u * n_shared; pn++) { // (wave-uniform)
+            uint32_t mp = 0;
+#pragma unroll
+            for (int q = 0; q < CROSS_MAX_PARTNERS; q++) mp = pn == (uint32_t)q ? m[q] : mp; // (no indexed registers)
+            uint32_t x = mine & mp;
+            while (__any(x != 0u)) { // one hit per lane and trip
+                const bool has = x != 0u;
+                const unsigned long long bal = __ballot(has);
+                if (has) {
+                    const uint32_t bit = (uint32_t)__builtin_ctz(x);
+                    x &= x - 1u;
+                    hitq[nq + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1ull))] = w | (bit << 11) | (pn << 16);
+                }
+                nq += (uint32_t)__builtin_popcountll(bal);
+                if (nq >= CROSS_DRAIN_AT) drain();
+            }
+        }
+    }
+    while (nq) drain();
+    if (lane == 0) g.priv_cnt[blockIdx.x] = min(n_out, SEG_PRIV_CAP);
+    for (int off = 32; off > 0; off >>= 1) n_cand += __shfl_down(n_cand, off);
+    for (int off = 32; off > 0; off >>= 1) n_direct += __shfl_down(n_direct, off);
+    if (lane == 0) g.priv_stat[blockIdx.x] = make_uint2(n_cand, n_direct); // (the flatten launch adds them up)
 }
 
 // offsets of the blocks' slots behind what the list holds already (one block), the new total
@@ -1803,6 +1999,17 @@ hipError_t launch_seg_super(const PairArgs &a, const SegArgs &g, float percentag
                      : launch_seg_super_as<true, 1024>(a, g, percentage, n_blocks, lds, s);
     return small ? launch_seg_super_as<false, 256>(a, g, percentage, n_blocks, lds, s)
                  : launch_seg_super_as<false, 1024>(a, g, percentage, n_blocks, lds, s);
+}
+
+hipError_t launch_seg_cross(const PairArgs &a, const SegArgs &g, float percentage, uint32_t n_blocks, hipStream_t s)
+{
+    if (g.n_supers == 0 || n_blocks == 0) return hipSuccess;
+    if (!g.supers || !g.cross_map || !g.cross_pre || !g.uf_parent || !g.priv_stat || a.nmask || a.k != 1 || g.n_parts != 2 ||
+        g.n_supers > 0xFFFFFFFFu / SEG_CROSS_CHUNKS || (a.mode != MODE_DIRECTIONAL && a.mode != MODE_CLUSTER))
+        return hipErrorInvalidValue;
+    if (a.mode == MODE_CLUSTER) seg_cross_kernel<true><<<n_blocks, 64, 0, s>>>(a, g, percentage);
+    else seg_cross_kernel<false><<<n_blocks, 64, 0, s>>>(a, g, percentage);
+    return hipGetLastError();
 }
 
 // what the pair kernel's blocks still held in their stages when they ended: from their private
