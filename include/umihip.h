@@ -602,7 +602,7 @@ int umi_assign_genes(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_
  *        Result: G = the genes with a transcript the read fits.  One gene: UMI_GENE_ASSIGNED, gene = its index; none:
  *          UMI_GENE_NONE, gene = -1; two or more: UMI_GENE_SEVERAL, gene = -1.  Two fitting transcripts of one gene
  *          are one gene.  G is a subset of the genes that hit the read under umi_assign_genes.
- *      Not built: a body tier and read classes by transcript model (--gene-introns, --velocity with this rule),
+ *      A body tier and read classes by transcript model: umi_assign_genes_transcripts_classes, below.  Not built:
  *      paired reads, STARsolo's multi-gene modes.
  * in : umi_assign_genes' arguments, and exon_transcript (HOST, n_exons entries) and n_transcripts (it may lie above the
  *      transcripts used).  The index is built on the host inside the call; the walks and the lookups run on the device.
@@ -685,7 +685,8 @@ int umi_assign_genes_introns(umi_ctx *ctx, const int32_t *exon_ref, const int32_
  *          otherwise UMI_READ_CLASS_JUNCTION where m >= 2 and some gap has cover < its length (the read skips an
  *          intron); otherwise UMI_READ_CLASS_EXONIC.  UMI_READ_CLASS_NONE where the read is not assigned.
  *      The classes are relative to the exons passed: where the caller passes whole genes as exons, every assigned
- *      read is EXONIC.  Not built: transcript-model rules (velocyto's or STARsolo's own), paired reads.
+ *      read is EXONIC.  Classes by transcript model: umi_assign_genes_transcripts_classes, below.  Not built:
+ *      velocyto's or STARsolo's own rules, paired reads.
  * in : umi_assign_genes_introns' arguments.
  * out: gene, status, tier and counts[4], bit for bit what umi_assign_genes_introns writes on the same input; cls
  *      uint8 [n_reads], one of UMI_READ_CLASS_*; class_counts (host) [5]: the reads by class, indexed by
@@ -710,6 +711,61 @@ int umi_assign_genes_classes(umi_ctx *ctx, const int32_t *exon_ref, const int32_
                              const uint8_t *read_reverse, const uint32_t *cigar, const uint64_t *cigar_off, uint64_t n_reads,
                              int32_t *gene, uint8_t *status, uint8_t *tier, uint8_t *cls, uint64_t counts[4],
                              uint64_t class_counts[5]);
+
+/* ---- ... by transcript model, with the gene bodies behind it and the class of every assigned read (the program's
+ *      --transcript-introns), on the GPU.  No counterpart in the reference.  Stated after Cell Ranger 7's counting with
+ *      introns (a read is tried against the transcript models first and falls back to the gene body) and velocyto's /
+ *      STARsolo Velocyto's classes, not claimed equal to them: no intron validation, no per-model logic across a
+ *      molecule's reads.  Exact integers; tests/transcript_intron_model.py defines it.
+ *        Blocks, admissible strands, fit and G (the genes with a transcript the read fits) are
+ *          umi_assign_genes_transcripts', unchanged; m is the number of non-empty blocks.  Bodies and B (the genes whose
+ *          admissible body on the read's reference shares a base with a block) are umi_assign_genes_introns', derived
+ *          from the same lines, grouped per gene by reference and strand as written; E is umi_assign_genes'.
+ *          G is a subset of E, E of B.
+ *        UMI_INTRONS_EXON_FIRST: |G| = 1: assigned to it, tier transcript (UMI_GENE_TIER_EXON).  |G| >= 2: several.
+ *          |G| = 0 and |B| = 1: assigned, tier body (UMI_GENE_TIER_INTRON).  |G| = 0 and |B| = 0: none.  |G| = 0 and
+ *          |B| >= 2: several.
+ *        UMI_INTRONS_ALL: |B| = 1: assigned to it, tier transcript where G is not empty, else body.  |B| = 0: none.
+ *          |B| >= 2: several.
+ *        UMI_INTRONS_OFF: umi_assign_genes_transcripts' gene and status, every assigned read tier transcript.
+ *        Class of an assigned read with gene g.  Tier transcript: UMI_READ_CLASS_JUNCTION where m >= 2, else
+ *          UMI_READ_CLASS_EXONIC (every gap of a fitting read is an intron of a transcript it fits).  Tier body: the
+ *          blocks are cut to [0, 2^31), the empty ones left out; c is the summed cover of the blocks by g's
+ *          admissible exon lines on the reference (umi_assign_genes_classes' cover).  c == 0:
+ *          UMI_READ_CLASS_INTRONIC.  0 < c < the summed length: UMI_READ_CLASS_SPANNING.  c == the summed length:
+ *          UMI_READ_CLASS_JUNCTION where a gap is not covered whole by g's own exons (a spliced read of an isoform
+ *          the annotation does not have is spliced evidence), else UMI_READ_CLASS_EXONIC (two abutting blocks after a
+ *          zero-length N, an N inside an exon).  Not assigned: UMI_READ_CLASS_NONE.
+ *      Where it differs from umi_assign_genes_classes: a read spliced over an intron that another isoform of the gene
+ *      retains is EXONIC there (the long exon line covers the gap) and JUNCTION here (it fits the spliced isoform).
+ *      Not built: paired reads, Ex50pAS, antisense counting.
+ * in : umi_assign_genes_transcripts' arguments, and intron_mode, one of UMI_INTRONS_*.  The three indices (transcripts,
+ *      bodies and, for the classes, the exons' overlap table with its covers) are built on the host inside the call.
+ * out: gene, status and tier as umi_assign_genes_introns writes them; counts (host) [4]: the reads assigned by a
+ *      transcript, by a body, none, several; cls uint8 [n_reads] and class_counts (host) [5] as umi_assign_genes_classes
+ *      writes them.  cls and class_counts may both be NULL: no class is computed, and the overlap table and its covers
+ *      are neither built nor uploaded; gene, status, tier and counts are the same.  One of the two NULL alone is
+ *      UMI_ERR_ARG.
+ * Everything else is umi_assign_genes_transcripts' contract (n_reads == 0, n_exons == 0, the first device of a
+ * multi-device context, a deferred call that is out ends first, the limit of 2^30, the transcript errors, the errors
+ * and when they are found, tier among the required pointers); an unknown intron_mode is UMI_ERR_ARG before anything is
+ * launched.  Options "gene_top", "gene_body_top" and "grid_cus". */
+int umi_assign_genes_transcripts_classes_device(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start,
+                                                const int32_t *exon_end, const uint8_t *exon_strand, const int32_t *exon_gene,
+                                                const int32_t *exon_transcript, uint64_t n_exons, uint32_t n_genes,
+                                                uint32_t n_transcripts, int strand_mode, int intron_mode,
+                                                const int32_t *d_read_ref, const int32_t *d_read_pos,
+                                                const uint8_t *d_read_reverse, const uint32_t *d_cigar,
+                                                const uint64_t *d_cigar_off, uint64_t n_reads, int32_t *d_gene,
+                                                uint8_t *d_status, uint8_t *d_tier, uint8_t *d_cls, uint64_t counts[4],
+                                                uint64_t class_counts[5], void *hip_stream);
+int umi_assign_genes_transcripts_classes(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start,
+                                         const int32_t *exon_end, const uint8_t *exon_strand, const int32_t *exon_gene,
+                                         const int32_t *exon_transcript, uint64_t n_exons, uint32_t n_genes,
+                                         uint32_t n_transcripts, int strand_mode, int intron_mode, const int32_t *read_ref,
+                                         const int32_t *read_pos, const uint8_t *read_reverse, const uint32_t *cigar,
+                                         const uint64_t *cigar_off, uint64_t n_reads, int32_t *gene, uint8_t *status,
+                                         uint8_t *tier, uint8_t *cls, uint64_t counts[4], uint64_t class_counts[5]);
 
 /* ---- molecules and reads per (column, row) pair (the program's --count-matrix): what a batched call kept,
  *      summed over its buckets into the triplets of a sparse matrix, on the GPU.  No counterpart in the

@@ -148,6 +148,13 @@ SIGNATURES = {
     "umi_assign_genes_transcripts": (C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, _u8p, _i32p, _i32p, C.c_uint64, C.c_uint32,
                                                C.c_uint32, C.c_int, _i32p, _i32p, _u8p, _u32p, _u64p, C.c_uint64, _i32p, _u8p,
                                                _u64p]),
+    "umi_assign_genes_transcripts_classes_device": (C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, _u8p, _i32p, _i32p, C.c_uint64,
+                                                              C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                              C.c_void_p, C.c_void_p, _u64p, _u64p, C.c_void_p]),
+    "umi_assign_genes_transcripts_classes": (C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, _u8p, _i32p, _i32p, C.c_uint64, C.c_uint32,
+                                                       C.c_uint32, C.c_int, C.c_int, _i32p, _i32p, _u8p, _u32p, _u64p, C.c_uint64,
+                                                       _i32p, _u8p, _u8p, _u8p, _u64p, _u64p]),
     "umi_velocity_matrix_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, _u64p,
                                              C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_void_p]),

@@ -655,6 +655,57 @@ class Context:
                                                      ptr(class_counts, C.c_uint64), stream or None))
         return counts, class_counts
 
+    def assign_genes_transcripts_classes(self, exons, n_genes, n_transcripts, strand_mode, intron_mode, read_ref, read_pos,
+                                         read_reverse, cigar, cigar_off, classes=True):
+        """Reads assigned to genes by transcript model, with the gene bodies behind it and the class of every assigned
+        read (umi_assign_genes_transcripts_classes; the rule is in include/umihip.h): assign_genes_transcripts' arguments
+        and intron_mode, one of UMI_INTRONS_*.  Returns assign_genes_classes' dict; counts: assigned by a transcript, by a
+        body, none, several.  classes=False: no class is computed, and the dict has neither cls nor class_counts."""
+        exons = exons if isinstance(exons, dict) else list(exons)
+        ex = self._exon_arrays(exons)
+        tr = self._transcript_array(exons, len(ex[0]))
+        read_ref = np.ascontiguousarray(read_ref, dtype=np.int32).reshape(-1)
+        read_pos = np.ascontiguousarray(read_pos, dtype=np.int32).reshape(-1)
+        read_reverse = np.ascontiguousarray(read_reverse, dtype=np.uint8).reshape(-1)
+        cigar = np.ascontiguousarray(cigar, dtype=np.uint32).reshape(-1)
+        cigar_off = np.ascontiguousarray(cigar_off, dtype=np.uint64).reshape(-1)
+        n = len(read_ref)
+        if len(read_pos) != n or len(read_reverse) != n or len(cigar_off) != n + 1:
+            raise ValueError("the read arrays differ in length (cigar_off has one entry more)")
+        if int(cigar_off[-1]) > len(cigar):
+            raise ValueError("cigar_off ends beyond cigar")
+        m = max(1, n)
+        gene, status, tier, cls = np.zeros(m, np.int32), np.zeros(m, np.uint8), np.zeros(m, np.uint8), np.zeros(m, np.uint8)
+        counts, class_counts = np.zeros(4, np.uint64), np.zeros(5, np.uint64)
+        check(load().umi_assign_genes_transcripts_classes(
+            self._h, ptr(ex[0], C.c_int32), ptr(ex[1], C.c_int32), ptr(ex[2], C.c_int32), ptr(ex[3], C.c_uint8), ptr(ex[4], C.c_int32),
+            ptr(tr, C.c_int32), len(ex[0]), n_genes, n_transcripts, strand_mode, intron_mode, ptr(read_ref, C.c_int32),
+            ptr(read_pos, C.c_int32), ptr(read_reverse, C.c_uint8), ptr(cigar, C.c_uint32), ptr(cigar_off, C.c_uint64), n,
+            ptr(gene, C.c_int32), ptr(status, C.c_uint8), ptr(tier, C.c_uint8), ptr(cls, C.c_uint8) if classes else None,
+            ptr(counts, C.c_uint64), ptr(class_counts, C.c_uint64) if classes else None))
+        out = {"gene": gene[:n], "status": status[:n], "tier": tier[:n], "counts": counts}
+        if classes:
+            out["cls"], out["class_counts"] = cls[:n], class_counts
+        return out
+
+    def assign_genes_transcripts_classes_device(self, exons, n_genes, n_transcripts, strand_mode, intron_mode, d_read_ref,
+                                                d_read_pos, d_read_reverse, d_cigar, d_cigar_off, n_reads, d_gene, d_status,
+                                                d_tier, d_cls, stream=0, classes=True):
+        """The same on raw device pointers (umi_assign_genes_transcripts_classes_device; the exons stay on the host): fills
+        d_gene (int32 [n_reads]), d_status, d_tier and d_cls (uint8 [n_reads]); returns (counts uint64 [4], class_counts
+        uint64 [5]).  classes=False: d_cls is not passed on and not written, and class_counts is None."""
+        exons = exons if isinstance(exons, dict) else list(exons)
+        ex = self._exon_arrays(exons)
+        tr = self._transcript_array(exons, len(ex[0]))
+        counts, class_counts = np.zeros(4, np.uint64), np.zeros(5, np.uint64) if classes else None
+        check(load().umi_assign_genes_transcripts_classes_device(
+            self._h, ptr(ex[0], C.c_int32), ptr(ex[1], C.c_int32), ptr(ex[2], C.c_int32), ptr(ex[3], C.c_uint8), ptr(ex[4], C.c_int32),
+            ptr(tr, C.c_int32), len(ex[0]), n_genes, n_transcripts, strand_mode, intron_mode, d_read_ref or None, d_read_pos or None,
+            d_read_reverse or None, d_cigar or None, d_cigar_off or None, n_reads, d_gene or None, d_status or None, d_tier or None,
+            (d_cls or None) if classes else None, ptr(counts, C.c_uint64), ptr(class_counts, C.c_uint64) if classes else None,
+            stream or None))
+        return counts, class_counts
+
     def velocity_matrix(self, read_entry, read_class, kept, root, bucket_off, row, col, n_rows, n_cols):
         """Spliced, unspliced and ambiguous molecules per (column, row) pair (umi_velocity_matrix): read_entry uint32
         [n_reads] (UMI_READ_UNSTAGED: the read is skipped) and read_class uint8 [n_reads] (assign_genes_classes' cls),

@@ -514,3 +514,141 @@ int umi_assign_genes_transcripts(umi_ctx *ctx, const int32_t *exon_ref, const in
 }
 
 } // extern "C"
+
+// ---- umi_assign_genes_transcripts_classes*: umi_assign_genes_transcripts' checks and tables, the gene bodies' (as
+// ---- umi_assign_genes_introns derives them) and, where classes are asked for, the exons' overlap tables with their
+// ---- covers (as umi_assign_genes_classes builds them, not sampled); the kernel is umihip_gene_transcript_classes.hip's
+
+namespace {
+
+struct TranscriptClassIndex {
+    TranscriptIndex transcripts;
+    GeneTable bodies[2], exons[2];
+    GeneCover cover[2];
+    bool classes = false;
+};
+
+// (cls and class_counts come or go together)
+int transcript_classes_check(int intron_mode, const void *tier, const void *cls, const uint64_t *class_counts, uint64_t n_reads)
+{
+    if ((cls == nullptr) != (class_counts == nullptr)) return fail(UMI_ERR_ARG, "cls and class_counts are given together or not at all");
+    return introns_check(intron_mode, tier, n_reads);
+}
+
+void transcript_classes_index(const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end, const uint8_t *exon_strand,
+                              const int32_t *exon_gene, const int32_t *exon_transcript, uint64_t n_exons, uint32_t n_genes, int strand_mode,
+                              int intron_mode, bool classes, TranscriptClassIndex &ix)
+{
+    transcripts_index(exon_ref, exon_start, exon_end, exon_strand, exon_gene, exon_transcript, n_exons, strand_mode, ix.transcripts);
+    ix.classes = classes;
+    const int n_tables = ix.transcripts.n_tables;
+    GeneBodies b; // (off: no read looks at a body, and the body tables stay empty)
+    if (intron_mode != UMI_INTRONS_OFF) gene_bodies_derive(exon_ref, exon_start, exon_end, exon_strand, exon_gene, n_exons, b);
+    const unsigned take[2] = {n_tables == 1 ? GENE_TAKE_PLUS | GENE_TAKE_MINUS | GENE_TAKE_DOT : GENE_TAKE_PLUS | GENE_TAKE_DOT,
+                              GENE_TAKE_MINUS | GENE_TAKE_DOT};
+    for (int t = 0; t < n_tables; t++) {
+        gene_index_build(b.ref.data(), b.start.data(), b.end.data(), b.strand.data(), b.gene.data(), b.gene.size(), n_genes, take[t],
+                         ix.bodies[t]);
+        gene_index_sample(ix.bodies[t], GENE_BODY_TOP_CAP);
+        // (off: no read is assigned by a body, and none looks at the overlap table)
+        if (!classes) continue;
+        gene_index_build(exon_ref, exon_start, exon_end, exon_strand, exon_gene, intron_mode != UMI_INTRONS_OFF ? n_exons : 0, n_genes,
+                         take[t], ix.exons[t]);
+        gene_cover_prefix(ix.exons[t], ix.cover[t].cum);
+        gene_own_build(exon_ref, exon_start, exon_end, exon_strand, exon_gene, intron_mode != UMI_INTRONS_OFF ? n_exons : 0, n_genes, take[t],
+                       ix.cover[t].own);
+    }
+}
+
+int transcript_classes_run(umi_ctx *ctx, const TranscriptClassIndex &ix, int intron_mode, const int32_t *d_ref, const int32_t *d_pos,
+                           const uint8_t *d_reverse, const uint32_t *d_cigar, const uint64_t *d_cigar_off, uint64_t n_reads,
+                           int32_t *d_gene, uint8_t *d_status, uint8_t *d_tier, uint8_t *d_cls, uint64_t *counts, uint64_t *class_counts,
+                           hipStream_t s)
+{
+    int rc;
+    const TranscriptIndex &tr = ix.transcripts;
+    const GeneCover *cover = ix.classes ? ix.cover : nullptr;
+    if ((rc = ctx->call_ws.reserve(gene_transcript_classes_workspace_bytes(tr.tables, ix.bodies, ix.exons, cover, tr.n_tables, (uint32_t)n_reads)))) return rc;
+    uint64_t bad = 0;
+    const int r = gene_transcript_classes_on_device(ctx->call_ws.p, tr.tables, ix.bodies, ix.exons, cover, tr.n_tables, tr.flip, intron_mode,
+                                                    ctx->gene_top, ctx->gene_body_top, d_ref, d_pos, d_reverse, d_cigar, d_cigar_off,
+                                                    (uint32_t)n_reads, d_gene, d_status, d_tier, d_cls, counts, class_counts, &bad,
+                                                    (uint32_t)ctx->n_cus, ctx->h_counters, s);
+    if (r == 1)
+        return fail(UMI_ERR_ARG, "read %llu: a negative reference, a CIGAR op code above 8, or CIGAR words without an array",
+                    (unsigned long long)bad);
+    if (r == 2) return fail(UMI_ERR_ORDER, "cigar_off falls at read %llu", (unsigned long long)bad);
+    if (r < 0) return fail(UMI_ERR_HIP, "gene assignment by transcripts with classes: %s", hipGetErrorString((hipError_t)(-r)));
+    return UMI_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int umi_assign_genes_transcripts_classes_device(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end,
+                                                const uint8_t *exon_strand, const int32_t *exon_gene, const int32_t *exon_transcript,
+                                                uint64_t n_exons, uint32_t n_genes, uint32_t n_transcripts, int strand_mode,
+                                                int intron_mode, const int32_t *d_read_ref, const int32_t *d_read_pos,
+                                                const uint8_t *d_read_reverse, const uint32_t *d_cigar, const uint64_t *d_cigar_off,
+                                                uint64_t n_reads, int32_t *d_gene, uint8_t *d_status, uint8_t *d_tier, uint8_t *d_cls,
+                                                uint64_t counts[4], uint64_t class_counts[5], void *hip_stream)
+{
+    int rc = transcript_classes_check(intron_mode, d_tier, d_cls, class_counts, n_reads);
+    if (rc) return rc;
+    rc = transcripts_check_all(ctx, exon_ref, exon_start, exon_end, exon_strand, exon_gene, exon_transcript, n_exons, n_genes, n_transcripts,
+                               strand_mode, d_read_ref, d_read_pos, d_read_reverse, d_cigar_off, n_reads, d_gene, d_status, counts);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_assign_genes)
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    for (int c = 0; class_counts && c < 5; c++) class_counts[c] = 0;
+    if (n_reads == 0) return UMI_OK;
+    TranscriptClassIndex ix;
+    transcript_classes_index(exon_ref, exon_start, exon_end, exon_strand, exon_gene, exon_transcript, n_exons, n_genes, strand_mode,
+                             intron_mode, d_cls != nullptr, ix);
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
+    return transcript_classes_run(ctx, ix, intron_mode, d_read_ref, d_read_pos, d_read_reverse, d_cigar, d_cigar_off, n_reads, d_gene,
+                                  d_status, d_tier, d_cls, counts, class_counts, (hipStream_t)hip_stream);
+}
+
+int umi_assign_genes_transcripts_classes(umi_ctx *ctx, const int32_t *exon_ref, const int32_t *exon_start, const int32_t *exon_end,
+                                         const uint8_t *exon_strand, const int32_t *exon_gene, const int32_t *exon_transcript,
+                                         uint64_t n_exons, uint32_t n_genes, uint32_t n_transcripts, int strand_mode, int intron_mode,
+                                         const int32_t *read_ref, const int32_t *read_pos, const uint8_t *read_reverse,
+                                         const uint32_t *cigar, const uint64_t *cigar_off, uint64_t n_reads, int32_t *gene,
+                                         uint8_t *status, uint8_t *tier, uint8_t *cls, uint64_t counts[4], uint64_t class_counts[5])
+{
+    int rc = transcript_classes_check(intron_mode, tier, cls, class_counts, n_reads);
+    if (rc) return rc;
+    rc = transcripts_check_all(ctx, exon_ref, exon_start, exon_end, exon_strand, exon_gene, exon_transcript, n_exons, n_genes, n_transcripts,
+                               strand_mode, read_ref, read_pos, read_reverse, cigar_off, n_reads, gene, status, counts);
+    if (rc) return rc;
+    if (n_reads && cigar_off[n_reads] && !cigar) return fail(UMI_ERR_ARG, "cigar is NULL");
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    for (int c = 0; class_counts && c < 5; c++) class_counts[c] = 0;
+    if (n_reads == 0) return UMI_OK;
+    TranscriptClassIndex ix;
+    transcript_classes_index(exon_ref, exon_start, exon_end, exon_strand, exon_gene, exon_transcript, n_exons, n_genes, strand_mode,
+                             intron_mode, cls != nullptr, ix);
+    const size_t n = (size_t)n_reads, words = (size_t)cigar_off[n_reads];
+    HostIo io(ctx);
+    const auto d_ref = io.in(read_ref, n * 4), d_pos = io.in(read_pos, n * 4);
+    const auto d_reverse = io.in(read_reverse, n);
+    const auto d_cigar = io.in(cigar, words * 4);
+    const auto d_off = io.in(cigar_off, (n + 1) * 8);
+    const auto d_gene = io.out(gene, n * 4);
+    const auto d_status = io.out(status, n);
+    const auto d_tier = io.out(tier, n);
+    const auto d_cls = io.out(cls, n); // (absent, and null, where no class is asked for)
+    if ((rc = io.open()) ||
+        (rc = transcript_classes_run(ctx, ix, intron_mode, d_ref, d_pos, d_reverse, d_cigar, d_off, n_reads, d_gene, d_status, d_tier,
+                                     d_cls, counts, class_counts, io.stream())) ||
+        (rc = io.fetch(gene, d_gene, n)) || (rc = io.fetch(status, d_status, n)) || (rc = io.fetch(tier, d_tier, n)) ||
+        (rc = io.fetch(cls, d_cls, n)))
+        return rc;
+    return io.close();
+}
+
+} // extern "C"

@@ -593,6 +593,22 @@ int gene_transcripts_on_device(void *workspace, const TranscriptTable *tables, i
                                uint32_t n_reads, int32_t *d_gene, uint8_t *d_status, uint64_t counts[3], uint64_t *bad, uint32_t n_cus,
                                unsigned long long *h_pinned, hipStream_t s);
 
+// ---- ... with the gene bodies behind the transcripts, and classes (umihip_gene_transcript_classes.hip:
+// ---- umi_assign_genes_transcripts_classes) ----
+// Per strand class a transcript table (sampled at GENE_TOP_CAP), a body table (at GENE_BODY_TOP_CAP) and, where classes
+// are asked for (cover != null), the exons' overlap table (not sampled: searched from global memory) with its GeneCover.
+// cover null: exons, d_cls and class_counts are not looked at.  mode: UMI_INTRONS_*.  Two kernels, the second over a queue
+// of n_reads words in the workspace; one synchronisation, at the end.  h_pinned: 9 pinned words.  Returns
+// as genes_on_device; counts: assigned by a transcript, by a body, none, several; class_counts: by UMI_READ_CLASS_*.
+size_t gene_transcript_classes_workspace_bytes(const TranscriptTable *transcripts, const GeneTable *bodies, const GeneTable *exons,
+                                               const GeneCover *cover, int n_tables, uint32_t n_reads);
+int gene_transcript_classes_on_device(void *workspace, const TranscriptTable *transcripts, const GeneTable *bodies, const GeneTable *exons,
+                                      const GeneCover *cover, int n_tables, bool flip, int mode, bool use_top, bool use_body_top,
+                                      const int32_t *d_ref, const int32_t *d_pos, const uint8_t *d_reverse, const uint32_t *d_cigar,
+                                      const uint64_t *d_cigar_off, uint32_t n_reads, int32_t *d_gene, uint8_t *d_status, uint8_t *d_tier,
+                                      uint8_t *d_cls, uint64_t counts[4], uint64_t *class_counts, uint64_t *bad, uint32_t n_cus,
+                                      unsigned long long *h_pinned, hipStream_t s);
+
 // ---- molecules and reads per (column, row) pair (umihip_count.hip: umi_count_matrix) ----
 // h_off (pinned): the m + 1 offsets of the m >= 1 non-empty buckets; h_idx (pinned, null: nothing was left out):
 // their numbers in d_row / d_col.  The outputs take the triplets sorted by column, then row (capacity m);

@@ -27,6 +27,9 @@
 // p + m <= stop, the CIGAR is walked again from behind the first block, block i against instance p + i: both ends
 // equal for a middle block, start equal and end <= for the last.  The first gene seen is kept; a second one ends the
 // query: several.  An instance whose gene is the one already seen is not walked.
+//
+// Behind the lookup: the gene bodies behind the transcripts and the class of a read (umi_assign_genes_transcripts_classes,
+// the program's --transcript-introns): the end of this file; tests/cpp/test_transcript_tiers.cpp runs it on the CPU.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -227,11 +230,13 @@ UMIHIP_HD inline bool transcript_rest_fits(const TranscriptView &t, uint32_t p, 
 
 // A read: GENE_READ_* and *gene (-1 unless assigned); GENE_READ_BAD_OP at an op code above 8.  Coordinates are kept in
 // 64 bits: a block that starts before 0 or ends behind 2^31 - 1 lies in no exon, and the read fits nothing.
-// steps (may be null): the distinct exons the walk back looked at are added to it.
+// steps (may be null): the distinct exons the walk back looked at are added to it.  blocks (may be null): m, the
+// number of the read's non-empty blocks, whatever the verdict (0 at a bad op code).
 UMIHIP_HD inline int transcript_assign_read(const TranscriptView &t, const GeneTop *top, uint32_t ref, int64_t pos, const uint32_t *cigar,
-                                            uint64_t n_cigar, int32_t *gene, uint64_t *steps)
+                                            uint64_t n_cigar, int32_t *gene, uint64_t *steps, uint64_t *blocks = nullptr)
 {
     *gene = -1;
+    if (blocks) *blocks = 0;
     // the first walk: every op code, the number of non-empty blocks, the first of them and the walk's state behind it
     uint64_t m = 0;
     int64_t s = pos, e = pos, s1 = 0, e1 = 0;
@@ -258,6 +263,7 @@ UMIHIP_HD inline int transcript_assign_read(const TranscriptView &t, const GeneT
         }
         s = e = e + len;
     }
+    if (blocks) *blocks = m;
     if (m == 0 || outside) return GENE_READ_NONE;
     const uint64_t ks = gene_key(ref, (uint64_t)s1), ke = gene_key(ref, (uint64_t)e1);
     int32_t found = GENE_HIT_NONE;
@@ -286,6 +292,114 @@ UMIHIP_HD inline int transcript_assign_read(const TranscriptView &t, const GeneT
     if (found == GENE_HIT_NONE) return GENE_READ_NONE;
     *gene = found;
     return GENE_READ_ASSIGNED;
+}
+
+// ---- transcripts first, gene bodies behind them, and the class of a read (umi_assign_genes_transcripts_classes, the
+// ---- program's --transcript-introns) ----
+// G: the genes with a transcript the read fits (transcript_assign_read).  B: the genes whose body shares a base with a
+// block (gene_assign_read against the body table, umihip_gene_index.hpp).  G is in E, the overlap rule's set, and E
+// is in B.  exon-first: G one gene: that gene, tier transcript (GENE_TIER_EXON); G several: several; G empty: B's
+// verdict, tier body (GENE_TIER_INTRON).  all: G several: several (G is in B); else B's verdict, tier transcript where
+// G is not empty, else body.  off: G's verdict.
+//
+// Class of an assigned read.  Tier transcript: JUNCTION where m >= 2, else EXONIC -- every gap of a fitting read is an
+// intron of a transcript it fits, nothing is looked up.  Tier body, gene g: the blocks cut to [0, GENE_POS_LIMIT); c
+// the summed cover of the blocks by g's exon lines.  B = {g} gives E in {g}: every segment of the overlap table that a
+// block touches carries g's label (another gene's exon there would put that gene into E, and so into B), so the
+// table's cover of a block is g's -- the argument umihip_gene_index.hpp makes for tier exon.  c == 0: INTRONIC; c below
+// the summed length: SPANNING; else the gaps decide as gene_read_class has them: one that the table or g's own exons
+// do not cover whole: JUNCTION (the read is spliced, by an isoform the annotation does not have), else EXONIC.
+struct TrCoverView {
+    GeneView exons; // the overlap table of the strand class, searched without a top
+    const uint64_t *cum;
+    GeneOwnView own;
+};
+
+// The class of a read assigned to gene g by a body (its CIGAR has passed transcript_assign_read: no bad op code).  One
+// walk for the summed cover; the gaps are walked only where the cover is whole and there are two blocks.
+UMIHIP_HD inline int transcript_body_class(const TrCoverView &v, int32_t g, uint32_t ref, int64_t pos, const uint32_t *cigar,
+                                           uint64_t n_cigar)
+{
+    uint64_t covered = 0, length = 0;
+    uint32_t blocks = 0;
+    for (int walk = 0; walk < 2; walk++) {
+        int64_t s = pos, e = pos, prev_end = -1;
+        for (uint64_t c = 0; c <= n_cigar; c++) {
+            uint32_t op = 3, len = 0; // (behind the last word: the open block is closed)
+            if (c < n_cigar) {
+                op = cigar[c] & 15u;
+                len = cigar[c] >> 4;
+            }
+            if (op == 0 || op == 2 || op == 7 || op == 8) {
+                e += len;
+                continue;
+            }
+            if (op != 3) continue;
+            const int64_t bs = s < 0 ? 0 : s, be = e > GENE_POS_LIMIT ? GENE_POS_LIMIT : e;
+            if (be > bs) {
+                if (walk == 0) {
+                    blocks++;
+                    covered += gene_cover(v.exons, nullptr, v.cum, ref, (uint64_t)bs, (uint64_t)be);
+                    length += (uint64_t)(be - bs);
+                } else if (prev_end >= 0 && bs > prev_end) {
+                    const uint64_t gs = (uint64_t)prev_end, ge = (uint64_t)bs;
+                    if (gene_cover(v.exons, nullptr, v.cum, ref, gs, ge) < ge - gs || !gene_own_covers(v.own, g, ref, gs, ge))
+                        return GENE_CLASS_JUNCTION;
+                }
+                prev_end = be;
+            }
+            s = e = e + len;
+        }
+        if (covered == 0) return GENE_CLASS_INTRONIC;
+        if (covered < length) return GENE_CLASS_SPANNING;
+        if (blocks < 2) break;
+    }
+    return GENE_CLASS_EXONIC;
+}
+
+// A read under --transcript-introns, in three phases.  Phase 1 is transcript_assign_read, which looks at every word
+// and so finds a bad op code; it also gives m.  Phase 2, gene_assign_read against the bodies, runs only where the
+// verdict still depends on B (transcript_needs_bodies).  Phase 3, the body tier's class, runs only for a read that a
+// body assigned, and only where classes are asked for (cover given; cover null: *cls is not written).
+
+// does the verdict of a read with phase 1's verdict st still depend on B
+UMIHIP_HD inline bool transcript_needs_bodies(int mode, int st)
+{
+    if (st == GENE_READ_ASSIGNED) return mode == GENE_INTRONS_ALL;
+    return st == GENE_READ_NONE && mode != GENE_INTRONS_OFF;
+}
+
+// the class of a read that a transcript assigned
+UMIHIP_HD inline int transcript_fit_class(bool spliced) { return spliced ? GENE_CLASS_JUNCTION : GENE_CLASS_EXONIC; }
+
+// Phases 2 and 3 of a read that needs them (its CIGAR has passed phase 1).  fits: phase 1 assigned it; spliced: m >= 2.
+UMIHIP_HD inline int transcript_assign_read_bodies(const GeneView &bodies, const GeneTop *body_top, const TrCoverView *cover, bool fits,
+                                                   bool spliced, uint32_t ref, int64_t pos, const uint32_t *cigar, uint64_t n_cigar,
+                                                   int32_t *gene, int *tier, int *cls)
+{
+    const int st = gene_assign_read(bodies, body_top, ref, pos, cigar, n_cigar, gene);
+    *tier = st == GENE_READ_ASSIGNED && !fits ? GENE_TIER_INTRON : GENE_TIER_EXON;
+    if (cover)
+        *cls = st != GENE_READ_ASSIGNED ? GENE_CLASS_NONE
+               : fits                   ? transcript_fit_class(spliced)
+                                        : transcript_body_class(*cover, *gene, ref, pos, cigar, n_cigar);
+    return st;
+}
+
+// The three phases of one read: GENE_READ_*, *gene, *tier (GENE_TIER_EXON unless the read is assigned by a body), *cls.
+UMIHIP_HD inline int transcript_assign_read_tiers(const TranscriptView &t, const GeneTop *top, const GeneView &bodies, const GeneTop *body_top,
+                                                  const TrCoverView *cover, int mode, uint32_t ref, int64_t pos, const uint32_t *cigar,
+                                                  uint64_t n_cigar, int32_t *gene, int *tier, int *cls)
+{
+    *tier = GENE_TIER_EXON;
+    if (cover) *cls = GENE_CLASS_NONE;
+    uint64_t m = 0;
+    const int st = transcript_assign_read(t, top, ref, pos, cigar, n_cigar, gene, nullptr, &m);
+    if (st == GENE_READ_BAD_OP) return st;
+    if (transcript_needs_bodies(mode, st))
+        return transcript_assign_read_bodies(bodies, body_top, cover, st == GENE_READ_ASSIGNED, m >= 2, ref, pos, cigar, n_cigar, gene, tier, cls);
+    if (cover && st == GENE_READ_ASSIGNED) *cls = transcript_fit_class(m >= 2);
+    return st;
 }
 
 } // namespace umihip

@@ -59,8 +59,28 @@
 // transcripts" (those with a line on the BAM's references).  Refused with status 101 before the GPU is woken: the flag
 // without --gene-annotation; a value other than overlap, transcript; the flag given twice with different values;
 // --annotation-transcript-attribute without --gene-rule transcript; on a taken line no such attribute, an empty value,
-// or a value with a byte outside 0x21..0x7e or a ; or , ; --gene-rule transcript with --gene-introns exon-first|all or
-// with --velocity.  Not built: a gene-body tier and read classes by transcript model (those two combinations), --paired.
+// or a value with a byte outside 0x21..0x7e or a ; or , ; --gene-rule transcript with --gene-introns exon-first|all, or
+// with --velocity and no --transcript-introns exon-first|all.  Not built: --paired.
+//
+// --transcript-introns off|exon-first|all (with --gene-rule transcript; default off; tests/transcript_intron_model.py
+// defines it): the gene bodies behind the transcript models, as Cell Ranger 7 counts with introns, and read classes by
+// transcript model.  G is --gene-rule transcript's set, B --gene-introns' (the bodies derived from the same lines); G is
+// in B.  exon-first: one gene in G: that gene, by a transcript; two or more: several; G empty: one gene in B: that gene,
+// by a gene body; none: none; two or more: several.  all: one gene in B: that gene, by a transcript where G is not
+// empty, else by a body; none: none; two or more: several.  off: the run without the flag, byte for byte.  It is another
+// rule than --gene-introns, whose first tier is the overlap set E: a read that hangs a base into an exon is "by an exon"
+// there and "by a gene body" here.  With --velocity the class of an assigned read comes from the same call: by a
+// transcript: junction where the read has two blocks or more, else exonic; by a body: intronic where no base of its
+// blocks lies in one of its gene's lines, exon-intron where some do, and where all do, junction where a stretch an N
+// skipped is not covered whole by the gene's own lines (a splice the annotation does not have), else exonic.  So a read
+// spliced over an intron that another isoform retains is a junction read here, and exonic under the gene-level rule.
+// Stated after velocyto and STARsolo's Velocyto, not claimed equal to them: no intron validation, no per-model logic
+// across a molecule's reads.  The one call is umi_assign_genes_transcripts_classes in umi_assign_genes_transcripts'
+// place; molecules, layers and files are --velocity's, unchanged.  The summary gains, in "Gene introns"' place:
+// "Transcript introns: <mode>", "Number of reads assigned by a transcript", "Number of reads assigned by a gene body".
+// Refused with status 101 before the GPU is woken: the flag without --gene-rule transcript; a value other than off,
+// exon-first, all; the flag given twice with different values; the flag together with --gene-introns.
+// Not built: --paired, Ex50pAS, antisense counting, --two-pass.
 //
 // --gene-introns off|exon-first|all (with --gene-annotation; default off; tests/intron_model.py defines it): reads in
 // a gene's introns count too, as Cell Ranger 7 counts them by default and as single-nucleus runs need.  A gene's body:
@@ -83,8 +103,7 @@
 // --velocity (with --gene-annotation, --gene-introns exon-first|all and --count-matrix DIR; tests/velocity_model.py
 // defines it): the matrix's molecules in three layers -- spliced, unspliced, ambiguous -- what STARsolo's --soloFeatures
 // Velocyto, velocyto and alevin-fry's USA mode give scVelo and its kin.  The rule is at gene level and in exact integers;
-// it is NOT velocyto's or STARsolo's transcript-model rule: the transcript models that --gene-rule transcript keeps decide a
-// read's gene, not yet its class.  A read's
+// it is NOT velocyto's or STARsolo's transcript-model rule (classes by transcript model: --transcript-introns, above).  A read's
 // gene, status and tier are --gene-introns', unchanged.  The class of an assigned read with gene g: its blocks are cut
 // to [0, 2^31) and the empty ones left out; the cover of a stretch is the number of its bases in one of g's taken lines
 // on the read's reference and an admissible strand.  Assigned by an intron: intronic.  By an exon: where the blocks are
@@ -107,8 +126,8 @@
 // unspliced molecules", "Number of ambiguous molecules" (together "Number of reads after deduplicating").  The BAM, the
 // four raw files, filtered/, cells.tsv and the other summary lines are what --stage host writes without the flag.
 // Refused with status 101 before the GPU is woken: --velocity without --count-matrix, without --gene-annotation, with
-// --gene-introns absent or off, with --stage gpu.  Not built: transcript-model rules (velocyto's or STARsolo's own), a
-// read's entry from the GPU staging, --two-pass, --paired.
+// --gene-introns absent or off (with --gene-rule transcript: --transcript-introns absent or off), with --stage gpu.  Not
+// built: velocyto's or STARsolo's own rules, a read's entry from the GPU staging, --two-pass, --paired.
 #pragma once
 #include <unordered_map>
 

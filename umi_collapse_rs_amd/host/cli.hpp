@@ -78,13 +78,26 @@
 // --gene-rule overlap|transcript [--annotation-transcript-attribute A] (with --gene-annotation) [overlap]: transcript: a
 // read's gene is the one gene with a transcript the read fits, by umi_assign_genes_transcripts (annotation.hpp has the
 // rule, the summary lines, the refusals and what is not built).
+// --transcript-introns off|exon-first|all (with --gene-rule transcript, and with everything that goes with it) [off;
+// tests/transcript_intron_model.py defines it]: exon-first: a read that fits a transcript of one gene is that gene's, and
+// a read that fits none falls back to the gene bodies (Cell Ranger 7's counting with introns); all: the bodies decide, and
+// the fit names the tier; off: the run without the flag, byte for byte.  The one call is
+// umi_assign_genes_transcripts_classes.  The summary gains, in "Gene introns"' place, "Transcript introns: <mode>",
+// "Number of reads assigned by a transcript" and "Number of reads assigned by a gene body".  With exon-first or all,
+// --velocity goes with --gene-rule transcript: a read's class comes from the same call (a read that fits is a junction
+// read where it has two blocks, else exonic; a read a body assigned is classed by the cover of its gene's exons), the
+// staging is the host's as ever, and the layers are umi_velocity_matrix's, unchanged.
+// Refused with status 101 before the GPU is woken: the flag without --gene-rule transcript; a value other than the
+// three; the flag twice with different values; the flag together with --gene-introns (whose tiers are the overlap
+// rule's: another rule).
 // --velocity (with --per-gene --gene-annotation FILE --gene-introns exon-first|all --count-matrix DIR; tests/velocity_model.py
 // defines it): the molecules of the matrix in three layers, spliced, unspliced and ambiguous, as STARsolo's --soloFeatures
 // Velocyto, velocyto and alevin-fry's USA mode write them -- but by a gene-level rule, not by their transcript models
-// (those of --gene-rule transcript decide a read's gene, not yet its class; annotation.hpp has the rule, the files, the
-// summary lines and what is not built).
+// (with --gene-rule transcript the classes come by transcript model, under --transcript-introns exon-first|all, above;
+// annotation.hpp has the rule, the files, the summary lines and what is not built).
 // Refused with status 101 before the GPU is woken: --velocity without --count-matrix, without --gene-annotation, with
-// --gene-introns absent or off, or with --stage gpu (a read's entry is kept by the host staging alone).
+// --gene-introns absent or off (with --gene-rule transcript: --transcript-introns absent or off), or with --stage gpu (a
+// read's entry is kept by the host staging alone).
 // --saturation-curve FILE [--saturation-points L] [--saturation-seed S] (with --per-gene --count-matrix DIR, with or
 // without --per-cell -- without it there is the one column "all" -- and with everything those go with;
 // tests/saturation_model.py defines it, include/umihip.h has the same rule) [L 10, S 0]: sequencing saturation and the
@@ -192,6 +205,10 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     std::string gene_introns = "off";
     bool gene_introns_given = false;
     int gene_introns_mode = UMI_INTRONS_OFF; // as UMI_INTRONS_* (filled in by validate())
+    // --transcript-introns M (with --gene-rule transcript): off, exon-first or all; off and no flag are the same run
+    std::string transcript_introns = "off";
+    bool transcript_introns_given = false;
+    int transcript_introns_mode = UMI_INTRONS_OFF; // as UMI_INTRONS_* (filled in by validate())
     bool velocity = false; // --velocity: spliced, unspliced and ambiguous matrices beside --count-matrix's
     std::string saturation_curve;  // --saturation-curve FILE: saturation and medians per depth (the rule is at the top)
     int saturation_points = 10;    // --saturation-points L
@@ -325,7 +342,12 @@ void usage()
               "                           belongs to a gene when it fits one of the gene's transcripts: every block inside\n"
               "                           an exon, every N from one exon's end to the next one's start (STARsolo's Gene,\n"
               "                           Cell Ranger's transcriptome-compatible reads); no such gene or several: dropped\n"
-              "                           (not with --gene-introns exon-first|all, --velocity)\n"
+              "                           (not with --gene-introns exon-first|all; with --velocity only under\n"
+              "                           --transcript-introns exon-first|all)\n"
+              "      --transcript-introns <M> off, exon-first or all [default: off], with --gene-rule transcript.  exon-first:\n"
+              "                           a read that fits no transcript falls back to the gene bodies; all: the bodies\n"
+              "                           decide, the fit names the tier.  Makes --velocity go with --gene-rule transcript:\n"
+              "                           a read's class comes by transcript model (not with --gene-introns)\n"
               "      --annotation-transcript-attribute <A> with --gene-rule transcript: the attribute of column 9 that names\n"
               "                           a line's transcript [default: transcript_id]\n"
               "      --velocity           with --gene-annotation, --gene-introns exon-first|all and --count-matrix: write the\n"
@@ -460,6 +482,13 @@ Cli parse(int argc, char **argv)
                 die(a + " given twice with different values: '" + c.gene_introns + "' and '" + v + "'");
             c.gene_introns = v;
             c.gene_introns_given = true;
+        }
+        else if (a == "--transcript-introns") {
+            const std::string v = need(i);
+            if (c.transcript_introns_given && c.transcript_introns != v)
+                die(a + " given twice with different values: '" + c.transcript_introns + "' and '" + v + "'");
+            c.transcript_introns = v;
+            c.transcript_introns_given = true;
         }
         else if (a == "--velocity") c.velocity = true;
         else if (a == "--gene-rule" || a == "--annotation-transcript-attribute") {
@@ -707,6 +736,7 @@ bool validate(Cli &args)
         if (args.gene_introns_given) die("--gene-introns goes with --gene-annotation only");
         if (args.gene_rule_given) die("--gene-rule goes with --gene-annotation only");
         if (args.annotation_transcript_attribute_given) die("--annotation-transcript-attribute goes with --gene-rule transcript only");
+        if (args.transcript_introns_given) die("--transcript-introns goes with --gene-rule transcript only");
     } else {
         if (args.gene_rule != "overlap" && args.gene_rule != "transcript") die("--gene-rule wants overlap or transcript: '" + args.gene_rule + "'");
         args.gene_rule_transcript = args.gene_rule == "transcript";
@@ -717,11 +747,20 @@ bool validate(Cli &args)
         else if (args.gene_introns == "exon-first") args.gene_introns_mode = UMI_INTRONS_EXON_FIRST;
         else if (args.gene_introns == "all") args.gene_introns_mode = UMI_INTRONS_ALL;
         else die("--gene-introns wants off, exon-first or all: '" + args.gene_introns + "'");
+        if (args.transcript_introns_given && !args.gene_rule_transcript) die("--transcript-introns goes with --gene-rule transcript only");
+        if (args.transcript_introns == "off") args.transcript_introns_mode = UMI_INTRONS_OFF;
+        else if (args.transcript_introns == "exon-first") args.transcript_introns_mode = UMI_INTRONS_EXON_FIRST;
+        else if (args.transcript_introns == "all") args.transcript_introns_mode = UMI_INTRONS_ALL;
+        else die("--transcript-introns wants off, exon-first or all: '" + args.transcript_introns + "'");
+        if (args.transcript_introns_given && args.gene_introns_given)
+            die("--transcript-introns does not go with --gene-introns (the one falls back from the transcript models, the other from the "
+                "overlap rule's exons: two rules)");
         if (args.gene_rule_transcript && args.gene_introns_mode != UMI_INTRONS_OFF)
-            die("--gene-rule transcript does not go with --gene-introns " + args.gene_introns +
-                ". Not built: a gene-body tier beside the transcript models");
-        if (args.gene_rule_transcript && args.velocity)
-            die("--gene-rule transcript does not go with --velocity. Not built: read classes by transcript model");
+            die("--gene-rule transcript does not go with --gene-introns " + args.gene_introns + " (the gene bodies behind the transcript "
+                "models are --transcript-introns " + args.gene_introns + "). Not built: the overlap rule's exon tier beside the transcript models");
+        if (args.gene_rule_transcript && args.velocity && args.transcript_introns_mode == UMI_INTRONS_OFF)
+            die("--gene-rule transcript does not go with --velocity unless --transcript-introns exon-first or all is given. Not built: read "
+                "classes by transcript model without the gene bodies behind it");
         if (!args.per_gene) die("--gene-annotation goes with --per-gene only");
         if (args.gene_tag_given) die("--gene-annotation does not go with --gene-tag (the gene comes from the file, not from a tag)");
         if (!args.dump_staging.empty()) die("--gene-annotation does not go with --dump-staging (which stops before the GPU)");
@@ -737,7 +776,8 @@ bool validate(Cli &args)
     if (args.velocity) {
         if (args.count_matrix.empty()) die("--velocity goes with --count-matrix DIR only");
         if (!args.gene_annotation_given) die("--velocity goes with --gene-annotation only (a read's class comes from the file's exons)");
-        if (args.gene_introns_mode == UMI_INTRONS_OFF) die("--velocity goes with --gene-introns exon-first or all only");
+        if (args.gene_introns_mode == UMI_INTRONS_OFF && args.transcript_introns_mode == UMI_INTRONS_OFF)
+            die("--velocity goes with --gene-introns exon-first or all only");
         if (args.stage == "gpu") die("--stage gpu does not go with --paired, --tag, --call-consensus, --velocity or --dump-staging");
     }
     // --saturation-curve: likewise (its file is made last)

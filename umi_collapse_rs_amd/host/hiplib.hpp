@@ -31,6 +31,9 @@
 //
 // --velocity: likewise umi_assign_genes_classes, in umi_assign_genes_introns' place, and umi_velocity_matrix.
 //
+// --transcript-introns exon-first|all (with --gene-rule transcript): likewise umi_assign_genes_transcripts_classes, in
+// umi_assign_genes_transcripts' place; with --velocity it tells the classes too, and umi_assign_genes_classes is not asked for.
+//
 // --saturation-curve FILE: likewise umi_saturation_curve.
 #pragma once
 #include <chrono>
@@ -112,11 +115,14 @@ struct HipLib {
     // --gene-rule transcript: likewise, in its place
     bool want_transcripts = false;
     decltype(&umi_assign_genes_transcripts) assign_genes_transcripts = nullptr;
+    // --transcript-introns exon-first|all: likewise, in its place
+    bool want_transcript_classes = false;
+    decltype(&umi_assign_genes_transcripts_classes) assign_genes_transcripts_classes = nullptr;
     // --gene-introns exon-first|all: likewise, in its place
     bool want_introns = false;
     decltype(&umi_assign_genes_introns) assign_genes_introns = nullptr;
-    // --velocity: likewise, in its place, and the three layers' call
-    bool want_velocity = false;
+    // --velocity: likewise, in its place (not under --transcript-introns, whose call tells the classes), and the three layers' call
+    bool want_velocity = false, want_gene_classes = false;
     decltype(&umi_assign_genes_classes) assign_genes_classes = nullptr;
     decltype(&umi_velocity_matrix) velocity_matrix = nullptr;
     // --saturation-curve: likewise
@@ -134,9 +140,11 @@ struct HipLib {
           want_count(!args.count_matrix.empty()), want_stats(!args.output_stats.empty()),
           want_multigene(args.filter_multigene), want_cells(args.cell_filter_given),
           want_genes(args.gene_annotation_given && args.gene_introns_mode == UMI_INTRONS_OFF && !args.gene_rule_transcript),
-          want_transcripts(args.gene_annotation_given && args.gene_rule_transcript),
+          want_transcripts(args.gene_annotation_given && args.gene_rule_transcript && args.transcript_introns_mode == UMI_INTRONS_OFF),
+          want_transcript_classes(args.gene_annotation_given && args.gene_rule_transcript && args.transcript_introns_mode != UMI_INTRONS_OFF),
           want_introns(args.gene_annotation_given && args.gene_introns_mode != UMI_INTRONS_OFF && !args.velocity),
-          want_velocity(args.velocity), want_saturation(!args.saturation_curve.empty())
+          want_velocity(args.velocity), want_gene_classes(args.velocity && args.transcript_introns_mode == UMI_INTRONS_OFF),
+          want_saturation(!args.saturation_curve.empty())
     {
     }
     bool load()
@@ -183,9 +191,11 @@ struct HipLib {
         if (want_cells) call_cells = (decltype(call_cells))sym("umi_call_cells");
         if (want_genes) assign_genes = (decltype(assign_genes))sym("umi_assign_genes");
         if (want_transcripts) assign_genes_transcripts = (decltype(assign_genes_transcripts))sym("umi_assign_genes_transcripts");
+        if (want_transcript_classes)
+            assign_genes_transcripts_classes = (decltype(assign_genes_transcripts_classes))sym("umi_assign_genes_transcripts_classes");
         if (want_introns) assign_genes_introns = (decltype(assign_genes_introns))sym("umi_assign_genes_introns");
         if (want_velocity) {
-            assign_genes_classes = (decltype(assign_genes_classes))sym("umi_assign_genes_classes");
+            if (want_gene_classes) assign_genes_classes = (decltype(assign_genes_classes))sym("umi_assign_genes_classes");
             velocity_matrix = (decltype(velocity_matrix))sym("umi_velocity_matrix");
         }
         if (want_saturation) saturation_curve = (decltype(saturation_curve))sym("umi_saturation_curve");

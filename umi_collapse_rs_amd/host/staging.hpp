@@ -421,6 +421,11 @@ struct Summary {
                     std::fprintf(stderr, "Gene rule: transcript\n");
                     std::fprintf(stderr, "Number of transcripts: %zu\n", annotation_transcripts);
                 }
+                if (args.transcript_introns_mode != UMI_INTRONS_OFF) {
+                    std::fprintf(stderr, "Transcript introns: %s\n", args.transcript_introns.c_str());
+                    std::fprintf(stderr, "Number of reads assigned by a transcript: %llu\n", (unsigned long long)by_exon);
+                    std::fprintf(stderr, "Number of reads assigned by a gene body: %llu\n", (unsigned long long)by_intron);
+                }
                 if (args.gene_introns_mode != UMI_INTRONS_OFF) {
                     std::fprintf(stderr, "Gene introns: %s\n", args.gene_introns.c_str());
                     std::fprintf(stderr, "Number of reads assigned by an exon: %llu\n", (unsigned long long)by_exon);

@@ -91,6 +91,9 @@
 // refusals): one call to umi_assign_genes over every mapped read, after the file is read and before the per-read
 // pass, which takes its verdict in the gene tag's place (assign_genes() below).
 // --gene-rule transcript (with --gene-annotation; annotation.hpp): that one call is umi_assign_genes_transcripts.
+// --transcript-introns exon-first|all (with --gene-rule transcript; annotation.hpp): that one call is
+// umi_assign_genes_transcripts_classes -- a read that fits no transcript falls back to the gene bodies -- and with
+// --velocity its classes feed umi_velocity_matrix.
 // --gene-introns exon-first|all (with --gene-annotation; annotation.hpp): that one call is umi_assign_genes_introns,
 // whose gene and status are used alike; its counts by tier go into the summary, the tier of a read goes nowhere.
 // --velocity (with --gene-introns exon-first|all and --count-matrix DIR; annotation.hpp has the rule and the files): that
@@ -405,7 +408,24 @@ struct OnePass {
         assigned_gene.assign(n_rec, -1);
         uint64_t counts[3] = {0, 0, 0};
         if (args.velocity) assigned_class.assign(n_rec, UMI_READ_CLASS_NONE);
-        if (nc && args.velocity) { // --velocity: the call that tells the classes too, in the two-tier call's place
+        if (nc && args.transcript_introns_mode != UMI_INTRONS_OFF) { // --transcript-introns: transcripts first, bodies behind; --velocity: the classes too
+            need_ctx();
+            if (!lib.assign_genes_transcripts_classes) die("libumihip.so lacks umi_assign_genes_transcripts_classes");
+            std::vector<uint8_t> r_tier(nc), r_class(args.velocity ? nc : 0);
+            uint64_t by_tier[4] = {0, 0, 0, 0};
+            if (lib.assign_genes_transcripts_classes(ctx, x_ref.data(), x_start.data(), x_end.data(), x_strand.data(), x_gene.data(),
+                                                     x_tr.data(), x_gene.size(), (uint32_t)annotation_ids.size(),
+                                                     (uint32_t)sum.annotation_transcripts, args.gene_strand_mode,
+                                                     args.transcript_introns_mode, r_ref.data(), r_pos.data(), r_rev.data(), words.data(),
+                                                     c_off.data(), nc, r_gene.data(), r_status.data(), r_tier.data(),
+                                                     args.velocity ? r_class.data() : nullptr, by_tier,
+                                                     args.velocity ? sum.class_counts : nullptr) != UMI_OK)
+                die(lib.last_error());
+            sum.by_exon = by_tier[0];
+            sum.by_intron = by_tier[1];
+            if (args.velocity)
+                for (size_t j = 0; j < nc; j++) assigned_class[cand[j]] = r_class[j];
+        } else if (nc && args.velocity) { // --velocity: the call that tells the classes too, in the two-tier call's place
             need_ctx();
             if (!lib.assign_genes_classes) die("libumihip.so lacks umi_assign_genes_classes");
             std::vector<uint8_t> r_tier(nc), r_class(nc);
