@@ -9,7 +9,7 @@ LIB := $(PKG)/libumihip.so
 OBJDIR := build/obj
 # the library's translation units, listed once: the kernels (.hip), then the host side (.cpp)
 SRCS := umihip_kernels umihip_seg umihip_collapse umihip_stage umihip_radix umihip_wide umihip_edit umihip_seq \
-        umihip_consensus umihip_consensus_bam umihip_correct umihip_barcode umihip_count umihip_multigene umihip_stats umihip_cells umihip_genes umihip_gene_introns umihip_gene_classes umihip_gene_transcripts umihip_gene_transcript_classes umihip_velocity umihip_saturation \
+        umihip_consensus umihip_consensus_bam umihip_correct umihip_barcode umihip_count umihip_multigene umihip_stats umihip_cells umihip_genes umihip_gene_introns umihip_gene_classes umihip_gene_transcripts umihip_gene_transcript_classes umihip_velocity umihip_saturation umihip_junctions \
         umihip_api umihip_pipeline umihip_batch umihip_stage_api umihip_seq_api umihip_correct_api umihip_count_api umihip_genes_api umihip_data
 OBJS := $(patsubst %,$(OBJDIR)/%.o,$(SRCS))
 # development build (make dev): the shipped sources plus the round-1 tile kernels, their key sort
@@ -17,10 +17,10 @@ OBJS := $(patsubst %,$(OBJDIR)/%.o,$(SRCS))
 DEVDIR := build/obj_dev
 DEVLIB := $(PKG)/libumihip_dev.so
 DEVOBJS := $(patsubst %,$(DEVDIR)/%.o,$(SRCS)) $(DEVDIR)/umihip_legacy.o $(DEVDIR)/umihip_sort.o
-HDRS := $(CSRC)/umihip_internal.h $(CSRC)/umihip_cons_group.h $(CSRC)/umihip_device.h $(CSRC)/umihip_plan.hpp $(CSRC)/umihip_io_layout.hpp $(CSRC)/umihip_host.hpp $(CSRC)/umihip_gene_index.hpp $(CSRC)/umihip_transcript_index.hpp include/umihip.h
+HDRS := $(CSRC)/umihip_internal.h $(CSRC)/umihip_cons_group.h $(CSRC)/umihip_device.h $(CSRC)/umihip_plan.hpp $(CSRC)/umihip_io_layout.hpp $(CSRC)/umihip_host.hpp $(CSRC)/umihip_gene_index.hpp $(CSRC)/umihip_transcript_index.hpp $(CSRC)/umihip_junction_walk.hpp include/umihip.h
 CLI := $(PKG)/bin/umicollapse
 
-all: $(LIB) oracle cpptest primtest trtest $(CLI)
+all: $(LIB) oracle cpptest primtest trtest jntest $(CLI)
 
 # (the staging's host decisions: read by the staging unit alone)
 $(OBJDIR)/umihip_stage.o $(DEVDIR)/umihip_stage.o: $(CSRC)/umihip_stage_plan.hpp
@@ -90,9 +90,17 @@ $(TRTEST): tests/cpp/test_transcript_index.cpp $(CSRC)/umihip_transcript_index.h
 
 trtest: $(TRTEST)
 
+# the junction walk on the CPU, a program of its own (tests/test_junction_model_cpu.py builds it once more, under sanitizers)
+JNTEST := build/test_junction_walk
+$(JNTEST): tests/cpp/test_junction_walk.cpp $(CSRC)/umihip_junction_walk.hpp
+	@mkdir -p build
+	g++ -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/test_junction_walk.cpp
+
+jntest: $(JNTEST)
+
 clean:
 	rm -f $(LIB) $(DEVLIB) $(CLI)
 	rm -rf build
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all dev oracle asm clean cpptest primtest trtest cli
+.PHONY: all dev oracle asm clean cpptest primtest trtest jntest cli

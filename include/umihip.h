@@ -870,6 +870,62 @@ int umi_saturation_curve(umi_ctx *ctx, const uint32_t *read_entry, uint64_t n_re
                          const uint64_t *bucket_off, uint64_t n_buckets, const uint32_t *row, const uint32_t *col, uint32_t n_rows,
                          uint32_t n_cols, uint64_t seed, int n_levels, const uint8_t *cell_mask, uint64_t *curve);
 
+/* ---- molecules and reads per (column, splice junction) pair (the program's --junction-matrix): a count matrix whose
+ *      rows are the splice junctions of the reads' CIGARs, on the GPU.  The matrix is what STARsolo's --soloFeatures SJ
+ *      writes, with two differences stated below; tests/junction_model.py defines it.  Exact integer arithmetic.
+ *        Blocks of a read are umi_assign_genes_transcripts' blocks, unchanged: start at read_pos, M, =, X and D extend
+ *          the current block, an N of any length, 0 included, closes it and skips its length, I, S, H and P consume
+ *          nothing, empty blocks are left out, op codes 9 to 15 are an error.
+ *        A junction of a read is the stretch [e, s) between two consecutive non-empty blocks: the end of one, the start
+ *          of the next.  It counts where 0 <= e < s <= 2^31 - 1.  So several N with only I, S, H or P between them are
+ *          one junction; a leading, a trailing or a zero-length N gives none; a D never makes one.  Positions are
+ *          computed in 64 bits, and a gap that reaches beyond 2^31 - 1 is left out.  Positions only grow along a read:
+ *          a read has a given junction at most once.  The junction's identity is (ref, e, s) = (ref, start, end).
+ *          It has NO strand: there is no genome here to read a motif from (STARsolo tells the strand by the motif).
+ *        A molecule is an entry r with kept[r] != 0; its reads are the reads i with read_entry[i] !=
+ *          UMI_READ_UNSTAGED and root[read_entry[i]] == r (umi_velocity_matrix' statement).  A molecule supports a
+ *          junction when one of its reads has it.  Reads under a root with kept == 0 -- what umi_filter_multigene
+ *          removed -- count nowhere, and unstaged reads contribute no junction.  The collapse is the call's own:
+ *          NOTHING is collapsed again per junction (STARsolo's SJ dedups UMIs per cell and junction).
+ *        The column of a molecule is col[b] of the bucket b that holds r.
+ * in : read_ref, read_pos int32 [n_reads], cigar, cigar_off as umi_assign_genes takes them; read_entry uint32
+ *      [n_reads]; kept uint8 [N] and root uint32 [N] of a batched call (N = bucket_off[n_buckets]); bucket_off (a HOST
+ *      array in both forms); col uint32 [n_buckets], n_cols; capacity: the elements every output array has room for.
+ *      The read_ref and the CIGAR words of a read that is unstaged or under a root that is not kept are not looked at.
+ * out: the junction table jn_ref, jn_start, jn_end (int32): the distinct junctions of counted reads, sorted by (ref,
+ *      start, end) ascending and numbered in that order, counts[2] of them.  The triplets out_jn, out_col (uint32),
+ *      out_molecules (uint32), out_reads (uint64): one per distinct (col, junction), sorted by col, then junction,
+ *      counts[3] of them; molecules = the distinct molecules of that column that support the junction, reads = the
+ *      reads under kept roots of that column that have it.  counts (HOST, 4 words): 0 the counted reads with a
+ *      junction, 1 the junction occurrences (the sum of reads over the triplets), 2 the junctions, 3 the triplets.
+ * n_buckets == 0, every bucket empty or n_reads == 0: UMI_OK, counts all zero, nothing launched.  A multi-device
+ * context uses its first device; a deferred call that is out ends first.  Grids come from the context's CU count
+ * (option "grid_cus").  The stream is synchronised twice: once when the occurrences have been counted -- their number
+ * T sizes the sorts and the workspace, and an error ends the call there with nothing written to the outputs -- and once
+ * at the end.  Workspace, bytes: 16 n_reads + 12 m (m the non-empty buckets) and 48 T, and the temporaries of the
+ * library's sort and scan.
+ * UMI_ERR_ARG before any HIP call: NULL pointers the call would touch (counts always; every array where there are reads
+ * and entries), n_reads >= 2^32, n_buckets >= 2^30, N >= 2^32, a bucket_off that does not start at 0 or that falls,
+ * n_cols == 0 with a non-empty bucket.  Found on the device and told after the first synchronisation, the smallest
+ * such read named and the outputs not defined: UMI_ERR_ARG for a read_ref < 0, a CIGAR op code above 8, a read_entry >=
+ * N other than UMI_READ_UNSTAGED, a root[read_entry[i]] >= N; UMI_ERR_ORDER for a cigar_off that falls (nothing is
+ * read outside cigar[0 .. cigar_off[n_reads])); UMI_ERR_ARG for a col >= n_cols of a non-empty bucket.
+ * UMI_ERR_ARG where T exceeds capacity or reaches 2^30: counts[1] then holds T, the other counts 0, so the caller can
+ * size the arrays and call again; nothing is written to the outputs.  The number of N words among the CIGARs is an upper
+ * bound of T. */
+int umi_junction_matrix_device(umi_ctx *ctx, const int32_t *d_read_ref, const int32_t *d_read_pos, const uint32_t *d_cigar,
+                               const uint64_t *d_cigar_off, const uint32_t *d_read_entry, uint64_t n_reads,
+                               const uint8_t *d_kept, const uint32_t *d_root, const uint64_t *bucket_off, uint64_t n_buckets,
+                               const uint32_t *d_col, uint32_t n_cols, uint64_t capacity, int32_t *d_jn_ref,
+                               int32_t *d_jn_start, int32_t *d_jn_end, uint32_t *d_out_jn, uint32_t *d_out_col,
+                               uint32_t *d_out_molecules, uint64_t *d_out_reads, uint64_t counts[4], void *hip_stream);
+int umi_junction_matrix(umi_ctx *ctx, const int32_t *read_ref, const int32_t *read_pos, const uint32_t *cigar,
+                        const uint64_t *cigar_off, const uint32_t *read_entry, uint64_t n_reads, const uint8_t *kept,
+                        const uint32_t *root, const uint64_t *bucket_off, uint64_t n_buckets, const uint32_t *col,
+                        uint32_t n_cols, uint64_t capacity, int32_t *jn_ref, int32_t *jn_start, int32_t *jn_end,
+                        uint32_t *out_jn, uint32_t *out_col, uint32_t *out_molecules, uint64_t *out_reads,
+                        uint64_t counts[4]);
+
 /* ---- UMIs a group shows in several buckets (the program's --umi-filtering multi-gene): the molecules of a batched
  *      call joined across its buckets, on the GPU.  A UMI that one cell shows under two or more genes is a chimera
  *      or a mis-assignment: only the gene with the most reads keeps it, none where the top count is shared.  The

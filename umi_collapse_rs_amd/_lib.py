@@ -165,6 +165,12 @@ SIGNATURES = {
                                               _u64p, C.c_void_p]),
     "umi_saturation_curve": (C.c_int, [C.c_void_p, _u32p, C.c_uint64, _u8p, _u32p, _u64p, C.c_uint64, _u32p, _u32p, C.c_uint32,
                                        C.c_uint32, C.c_uint64, C.c_int, _u8p, _u64p]),
+    "umi_junction_matrix_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                             C.c_void_p, C.c_void_p, _u64p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             _u64p, C.c_void_p]),
+    "umi_junction_matrix": (C.c_int, [C.c_void_p, _i32p, _i32p, _u32p, _u64p, _u32p, C.c_uint64, _u8p, _u32p, _u64p, C.c_uint64,
+                                      _u32p, C.c_uint32, C.c_uint64, _i32p, _i32p, _i32p, _u32p, _u32p, _u32p, _u64p, _u64p]),
     "umi_count_matrix_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_uint64, C.c_void_p, C.c_void_p,
                                           C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p,
                                           C.c_void_p]),

@@ -749,6 +749,68 @@ class Context:
                                                 d_out_ambiguous or None, C.byref(nnz), stream or None))
         return int(nnz.value)
 
+    def junction_matrix(self, read_ref, read_pos, cigar, cigar_off, read_entry, kept, root, bucket_off, col, n_cols,
+                        capacity=None):
+        """Molecules and reads per (column, splice junction) pair (umi_junction_matrix; the rule is in
+        include/umihip.h): per read read_ref, read_pos (int32), its CIGAR words cigar[cigar_off[i] .. cigar_off[i + 1])
+        and read_entry uint32 (UMI_READ_UNSTAGED: the read is skipped); kept uint8 [N] and root uint32 [N] of a batched
+        call, bucket_off uint64 [n_buckets + 1], col uint32 [n_buckets].  capacity: the junction occurrences the outputs
+        have room for (None: the N words among the CIGARs, an upper bound).  Returns ((jn_ref, jn_start, jn_end) int32,
+        the junction table in the order of (ref, start, end); (out_jn, out_col, molecules uint32, reads uint64), sorted
+        by column, then junction; counts uint64 [4]: spliced reads counted, occurrences, junctions, triplets).  The
+        collapse is the call's own; nothing is collapsed again per junction, and a junction has no strand."""
+        read_ref = np.ascontiguousarray(read_ref, dtype=np.int32).reshape(-1)
+        read_pos = np.ascontiguousarray(read_pos, dtype=np.int32).reshape(-1)
+        cigar = np.ascontiguousarray(cigar, dtype=np.uint32).reshape(-1)
+        cigar_off = np.ascontiguousarray(cigar_off, dtype=np.uint64).reshape(-1)
+        read_entry = np.ascontiguousarray(read_entry, dtype=np.uint32).reshape(-1)
+        kept = np.ascontiguousarray(kept, dtype=np.uint8)
+        root = np.ascontiguousarray(root, dtype=np.uint32)
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        col = np.ascontiguousarray(col, dtype=np.uint32)
+        nb, nr = len(bucket_off) - 1, len(read_ref)
+        if nb < 0 or len(col) != nb:
+            raise ValueError("col wants one element per bucket")
+        if len(read_pos) != nr or len(read_entry) != nr or len(cigar_off) != nr + 1:
+            raise ValueError("read_ref / read_pos / read_entry / cigar_off lengths differ")
+        if len(kept) != len(root) or (nb and int(bucket_off.max()) > len(kept)):
+            raise ValueError("kept / root lengths differ, or bucket_off runs past them")
+        if capacity is None:
+            capacity = int(np.count_nonzero((cigar & 15) == 3))
+        cap = max(1, int(capacity))
+        if len(cigar) == 0:
+            cigar = np.zeros(1, np.uint32)
+        jn = [np.zeros(cap, np.int32) for _ in range(3)]
+        o_jn, o_col, o_mol = (np.zeros(cap, np.uint32) for _ in range(3))
+        o_reads = np.zeros(cap, np.uint64)
+        counts = np.zeros(4, np.uint64)
+        self.junction_counts = counts  # (what a refused call found: counts[1] = the occurrences a capacity has to hold)
+        check(load().umi_junction_matrix(self._h, ptr(read_ref, C.c_int32), ptr(read_pos, C.c_int32), ptr(cigar, C.c_uint32),
+                                         ptr(cigar_off, C.c_uint64), ptr(read_entry, C.c_uint32), nr, ptr(kept, C.c_uint8),
+                                         ptr(root, C.c_uint32), ptr(bucket_off, C.c_uint64), nb, ptr(col, C.c_uint32), n_cols,
+                                         int(capacity), ptr(jn[0], C.c_int32), ptr(jn[1], C.c_int32), ptr(jn[2], C.c_int32),
+                                         ptr(o_jn, C.c_uint32), ptr(o_col, C.c_uint32), ptr(o_mol, C.c_uint32),
+                                         ptr(o_reads, C.c_uint64), ptr(counts, C.c_uint64)))
+        j, z = int(counts[2]), int(counts[3])
+        return (jn[0][:j], jn[1][:j], jn[2][:j]), (o_jn[:z], o_col[:z], o_mol[:z], o_reads[:z]), counts
+
+    def junction_matrix_device(self, d_read_ref, d_read_pos, d_cigar, d_cigar_off, d_read_entry, n_reads, d_kept, d_root,
+                               bucket_off, d_col, n_cols, capacity, d_jn_ref, d_jn_start, d_jn_end, d_out_jn, d_out_col,
+                               d_out_molecules, d_out_reads, stream=0):
+        """The same on raw device pointers (umi_junction_matrix_device; bucket_off stays on the host): fills the seven
+        output arrays (room for `capacity` elements each) and returns counts uint64 [4].  Where the call is refused,
+        self.junction_counts[1] holds the occurrences a capacity has to hold."""
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        counts = np.zeros(4, np.uint64)
+        self.junction_counts = counts
+        check(load().umi_junction_matrix_device(self._h, d_read_ref or None, d_read_pos or None, d_cigar or None,
+                                                d_cigar_off or None, d_read_entry or None, n_reads, d_kept or None,
+                                                d_root or None, ptr(bucket_off, C.c_uint64), len(bucket_off) - 1, d_col or None,
+                                                n_cols, int(capacity), d_jn_ref or None, d_jn_start or None, d_jn_end or None,
+                                                d_out_jn or None, d_out_col or None, d_out_molecules or None,
+                                                d_out_reads or None, ptr(counts, C.c_uint64), stream or None))
+        return counts
+
     def saturation_curve(self, read_entry, kept, root, bucket_off, row, col, n_rows, n_cols, n_levels=10, seed=0, cell_mask=None):
         """Sequencing saturation and medians per cell as a function of depth (umi_saturation_curve; the rule is in
         include/umihip.h): velocity_matrix's arguments without the classes, n_levels depths, the seed of the reads'

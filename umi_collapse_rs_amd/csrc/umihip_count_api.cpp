@@ -371,6 +371,160 @@ int umi_saturation_curve(umi_ctx *ctx, const uint32_t *read_entry, uint64_t n_re
 
 } // extern "C"
 
+// ---- molecules and reads per (column, splice junction) pair --------------------------------------------
+namespace {
+// what both forms check before a device is looked at (the context last)
+int jm_check(umi_ctx *ctx, const void *read_ref, const void *read_pos, const void *cigar, const void *cigar_off, const void *read_entry,
+             uint64_t n_reads, const void *kept, const void *root, const uint64_t *bucket_off, uint64_t n_buckets, const void *col,
+             const void *jn_ref, const void *jn_start, const void *jn_end, const void *out_jn, const void *out_col,
+             const void *out_molecules, const void *out_reads, const uint64_t *counts)
+{
+    if (!counts) return fail(UMI_ERR_ARG, "counts is NULL");
+    if (n_buckets >= (1ull << 30))
+        return fail(UMI_ERR_ARG, "%llu buckets exceed the 30-bit index space of one call", (unsigned long long)n_buckets);
+    if (n_reads >= (1ull << 32)) return fail(UMI_ERR_ARG, "%llu reads exceed the 32-bit index space of one call", (unsigned long long)n_reads);
+    if (n_buckets && !bucket_off) return fail(UMI_ERR_ARG, "bucket_off is NULL");
+    if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
+    if (n_buckets && bucket_off[n_buckets] && n_reads) {
+        if (!col || !kept || !root) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+        if (!read_ref || !read_pos || !cigar || !cigar_off || !read_entry) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+        if (!jn_ref || !jn_start || !jn_end || !out_jn || !out_col || !out_molecules || !out_reads)
+            return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    }
+    if (n_buckets && bucket_off[n_buckets] >= (1ull << 32))
+        return fail(UMI_ERR_ARG, "%llu entries exceed the 32-bit index space of root", (unsigned long long)bucket_off[n_buckets]);
+    if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
+    return UMI_OK;
+}
+
+// the device made current, a deferred call let end, the table walked; *m == 0: nothing to do
+int jm_begin(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, uint64_t n_reads, uint32_t n_cols, uint32_t *m,
+             const uint64_t **h_off, const uint32_t **h_idx)
+{
+    int rc;
+    *m = 0;
+    if (n_buckets == 0 || n_reads == 0) return UMI_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
+    if ((rc = cm_walk(ctx, bucket_off, n_buckets, m, h_off, h_idx))) return rc;
+    if (*m && n_cols == 0) return fail(UMI_ERR_ARG, "a matrix of no columns with a non-empty bucket");
+    return UMI_OK;
+}
+
+int jm_run(umi_ctx *ctx, const int32_t *d_ref, const int32_t *d_pos, const uint32_t *d_cigar, const uint64_t *d_cigar_off,
+           const uint32_t *d_read_entry, uint64_t n_reads, const uint8_t *d_kept, const uint32_t *d_root, uint64_t n, uint32_t m,
+           const uint64_t *h_off, const uint32_t *h_idx, const uint32_t *d_col, uint32_t n_cols, uint64_t capacity, int32_t *d_jn_ref,
+           int32_t *d_jn_start, int32_t *d_jn_end, uint32_t *d_out_jn, uint32_t *d_out_col, uint32_t *d_out_molecules,
+           uint64_t *d_out_reads, uint64_t counts[4], hipStream_t s)
+{
+    int rc;
+    if ((rc = ctx->call_ws.reserve(junction_count_workspace_bytes((uint32_t)n_reads, m, h_idx != nullptr)))) return rc;
+    JunctionCounted got;
+    int r = junction_count_on_device(ctx->call_ws.p, d_ref, d_pos, d_cigar, d_cigar_off, d_read_entry, (uint32_t)n_reads, d_kept, d_root, n,
+                                     h_off, h_idx, m, d_col, n_cols, &got, (uint32_t)ctx->n_cus, ctx->h_counters, s);
+    if (r < 0) return fail(UMI_ERR_HIP, "junction matrix: %s", hipGetErrorString((hipError_t)(-r)));
+    const unsigned long long at = (unsigned long long)got.bad_read;
+    switch (got.bad_kind) {
+    case 1: return fail(UMI_ERR_ORDER, "read %llu: cigar_off falls", at);
+    case 2:
+        return fail(UMI_ERR_ARG, "read %llu: its read_entry is neither below the %llu entries nor UMI_READ_UNSTAGED", at,
+                    (unsigned long long)n);
+    case 3: return fail(UMI_ERR_ARG, "read %llu: the root of its entry is not below the %llu entries", at, (unsigned long long)n);
+    case 4: return fail(UMI_ERR_ARG, "read %llu: read_ref < 0", at);
+    case 5: return fail(UMI_ERR_ARG, "read %llu: a CIGAR op code above 8", at);
+    default: break;
+    }
+    if (got.bad_cols)
+        return fail(UMI_ERR_ARG, "%llu non-empty buckets have a column id of %u or more", (unsigned long long)got.bad_cols, n_cols);
+    if (got.occurrences > capacity || got.occurrences >= (1ull << 30)) {
+        counts[1] = got.occurrences;
+        return fail(UMI_ERR_ARG, "%llu junction occurrences exceed the capacity of %llu, or the 30-bit index space of one call",
+                    (unsigned long long)got.occurrences, (unsigned long long)capacity);
+    }
+    if (got.occurrences == 0) return UMI_OK;
+    if ((rc = ctx->jn_ws.reserve(junction_fill_workspace_bytes((uint32_t)got.occurrences)))) return rc;
+    uint64_t junctions = 0, nnz = 0;
+    r = junction_fill_on_device(ctx->call_ws.p, ctx->jn_ws.p, d_ref, d_pos, d_cigar, d_cigar_off, d_read_entry, (uint32_t)n_reads, d_kept,
+                                d_root, n, m, h_idx != nullptr, n_cols, got, d_jn_ref, d_jn_start, d_jn_end, d_out_jn, d_out_col,
+                                d_out_molecules, d_out_reads, &junctions, &nnz, (uint32_t)ctx->n_cus, ctx->h_counters, s);
+    if (r < 0) return fail(UMI_ERR_HIP, "junction matrix: %s", hipGetErrorString((hipError_t)(-r)));
+    counts[0] = got.spliced;
+    counts[1] = got.occurrences;
+    counts[2] = junctions;
+    counts[3] = nnz;
+    return UMI_OK;
+}
+} // namespace
+
+extern "C" {
+
+int umi_junction_matrix_device(umi_ctx *ctx, const int32_t *d_read_ref, const int32_t *d_read_pos, const uint32_t *d_cigar,
+                               const uint64_t *d_cigar_off, const uint32_t *d_read_entry, uint64_t n_reads, const uint8_t *d_kept,
+                               const uint32_t *d_root, const uint64_t *bucket_off, uint64_t n_buckets, const uint32_t *d_col,
+                               uint32_t n_cols, uint64_t capacity, int32_t *d_jn_ref, int32_t *d_jn_start, int32_t *d_jn_end,
+                               uint32_t *d_out_jn, uint32_t *d_out_col, uint32_t *d_out_molecules, uint64_t *d_out_reads,
+                               uint64_t counts[4], void *hip_stream)
+{
+    int rc = jm_check(ctx, d_read_ref, d_read_pos, d_cigar, d_cigar_off, d_read_entry, n_reads, d_kept, d_root, bucket_off, n_buckets,
+                      d_col, d_jn_ref, d_jn_start, d_jn_end, d_out_jn, d_out_col, d_out_molecules, d_out_reads, counts);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_count_matrix)
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    uint32_t m = 0;
+    const uint64_t *h_off = nullptr;
+    const uint32_t *h_idx = nullptr;
+    if ((rc = jm_begin(ctx, bucket_off, n_buckets, n_reads, n_cols, &m, &h_off, &h_idx)) || m == 0) return rc;
+    return jm_run(ctx, d_read_ref, d_read_pos, d_cigar, d_cigar_off, d_read_entry, n_reads, d_kept, d_root, bucket_off[n_buckets], m,
+                  h_off, h_idx, d_col, n_cols, capacity, d_jn_ref, d_jn_start, d_jn_end, d_out_jn, d_out_col, d_out_molecules,
+                  d_out_reads, counts, (hipStream_t)hip_stream);
+}
+
+int umi_junction_matrix(umi_ctx *ctx, const int32_t *read_ref, const int32_t *read_pos, const uint32_t *cigar,
+                        const uint64_t *cigar_off, const uint32_t *read_entry, uint64_t n_reads, const uint8_t *kept,
+                        const uint32_t *root, const uint64_t *bucket_off, uint64_t n_buckets, const uint32_t *col, uint32_t n_cols,
+                        uint64_t capacity, int32_t *jn_ref, int32_t *jn_start, int32_t *jn_end, uint32_t *out_jn, uint32_t *out_col,
+                        uint32_t *out_molecules, uint64_t *out_reads, uint64_t counts[4])
+{
+    int rc = jm_check(ctx, read_ref, read_pos, cigar, cigar_off, read_entry, n_reads, kept, root, bucket_off, n_buckets, col, jn_ref,
+                      jn_start, jn_end, out_jn, out_col, out_molecules, out_reads, counts);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    uint32_t m = 0;
+    const uint64_t *h_off = nullptr;
+    const uint32_t *h_idx = nullptr;
+    if ((rc = jm_begin(ctx, bucket_off, n_buckets, n_reads, n_cols, &m, &h_off, &h_idx)) || m == 0) return rc;
+    const size_t n = (size_t)bucket_off[n_buckets], nb = (size_t)n_buckets, nr = (size_t)n_reads;
+    const size_t cap = (size_t)std::min<uint64_t>(capacity, (1ull << 30) - 1), words = (size_t)cigar_off[n_reads];
+    HostIo io(ctx);
+    const auto d_off = io.in(cigar_off, (nr + 1) * 8);
+    const auto d_oreads = io.out(out_reads, cap * 8);
+    const auto d_ref = io.in(read_ref, nr * 4), d_pos = io.in(read_pos, nr * 4);
+    const auto d_cigar = io.in(cigar, words * 4, 4); // (a slot, and an address, even for no word)
+    const auto d_entry = io.in(read_entry, nr * 4);
+    const auto d_root = io.in(root, n * 4);
+    const auto d_col = io.in(col, nb * 4);
+    const auto d_jref = io.out(jn_ref, cap * 4), d_jstart = io.out(jn_start, cap * 4), d_jend = io.out(jn_end, cap * 4);
+    const auto d_ojn = io.out(out_jn, cap * 4), d_ocol = io.out(out_col, cap * 4), d_omol = io.out(out_molecules, cap * 4);
+    const auto d_kept = io.in(kept, n);
+    uint64_t got[4] = {0, 0, 0, 0};
+    if ((rc = io.open()) ||
+        (rc = jm_run(ctx, d_ref, d_pos, d_cigar, d_off, d_entry, n_reads, d_kept, d_root, n, m, h_off, h_idx, d_col, n_cols, capacity,
+                     d_jref, d_jstart, d_jend, d_ojn, d_ocol, d_omol, d_oreads, got, io.stream()))) {
+        counts[1] = got[1]; // (the occurrences a larger capacity has to hold)
+        return rc;
+    }
+    if ((rc = io.fetch(jn_ref, d_jref, (size_t)got[2])) || (rc = io.fetch(jn_start, d_jstart, (size_t)got[2])) ||
+        (rc = io.fetch(jn_end, d_jend, (size_t)got[2])) || (rc = io.fetch(out_jn, d_ojn, (size_t)got[3])) ||
+        (rc = io.fetch(out_col, d_ocol, (size_t)got[3])) || (rc = io.fetch(out_molecules, d_omol, (size_t)got[3])) ||
+        (rc = io.fetch(out_reads, d_oreads, (size_t)got[3])) || (rc = io.close()))
+        return rc;
+    for (int k = 0; k < 4; k++) counts[k] = got[k];
+    return UMI_OK;
+}
+
+} // extern "C"
+
 // ---- UMIs a group shows in several buckets ----------------------------------------------------------
 namespace {
 // what both forms check before a device is looked at (the context last)

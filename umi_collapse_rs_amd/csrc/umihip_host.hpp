@@ -261,6 +261,8 @@ struct umi_ctx {
     // the workspace of the single-shot device forms (staging, consensus, correction, count matrix, stats): each
     // call carves it anew and keeps nothing in it -- settle() leaves one call at a time in the context
     umihip::DevBuf call_ws;
+    // umi_junction_matrix*: the workspace of its second half, sized by the occurrences its first half counted in call_ws
+    umihip::DevBuf jn_ws;
     // whole-read keys (umi_dedup_seqs*): group table, records and their sort, runs, tile tasks
     umihip::DevBuf seq_groups, seq_ka, seq_kb, seq_va, seq_vb, seq_flag, seq_runid, seq_rs, seq_tend, seq_tmp;
     // pinned staging of umi_count_matrix* (the non-empty buckets' offsets and numbers) and of umi_dedup_stats*

@@ -647,6 +647,32 @@ int saturation_curve_on_device(void *workspace, const uint32_t *d_read_entry, ui
                                int n_levels, const uint8_t *d_cell_mask, bool skip_set, uint64_t *bad_ids, int *bad_kind,
                                uint64_t *bad_read, uint32_t n_cus, unsigned long long *h_pinned, hipStream_t s);
 
+// ---- molecules and reads per (column, splice junction) pair (umihip_junctions.hip: umi_junction_matrix) ----
+// Two halves, each with one synchronisation at its end: the sorts of the second take the occurrences T as a host
+// argument.  junction_count_on_device: count_matrix_on_device's bucket arguments without the rows, the reads'
+// ref, pos, CIGAR words and entries; *got: what the host decides on.  bad_kind: 0 none, 1 a falling cigar_off, 2 a
+// read_entry out of range, 3 a root out of range, 4 a read_ref < 0, 5 an op code above 8, of read bad_read (the
+// smallest read with any of them).  h_pinned: 10 pinned words.  junction_fill_on_device: runs only where got has no
+// error and 1 <= got.occurrences < 2^30; workspace1 is the first half's, untouched since; workspace2 holds
+// junction_fill_workspace_bytes(T); the outputs have room for T.  0 ok; -(hipError_t).
+struct JunctionCounted {
+    uint64_t bad_cols, bad_read, spliced, occurrences, max_ref, max_pos;
+    int bad_kind;
+};
+size_t junction_count_workspace_bytes(uint32_t n_reads, uint32_t m, bool has_idx);
+size_t junction_fill_workspace_bytes(uint32_t t);
+int junction_count_on_device(void *workspace, const int32_t *d_ref, const int32_t *d_pos, const uint32_t *d_cigar,
+                             const uint64_t *d_cigar_off, const uint32_t *d_read_entry, uint32_t n_reads, const uint8_t *d_kept,
+                             const uint32_t *d_root, uint64_t n, const uint64_t *h_off, const uint32_t *h_idx, uint32_t m,
+                             const uint32_t *d_col, uint32_t n_cols, JunctionCounted *got, uint32_t n_cus, unsigned long long *h_pinned,
+                             hipStream_t s);
+int junction_fill_on_device(void *workspace1, void *workspace2, const int32_t *d_ref, const int32_t *d_pos, const uint32_t *d_cigar,
+                            const uint64_t *d_cigar_off, const uint32_t *d_read_entry, uint32_t n_reads, const uint8_t *d_kept,
+                            const uint32_t *d_root, uint64_t n, uint32_t m, bool has_idx, uint32_t n_cols, const JunctionCounted &got,
+                            int32_t *d_jn_ref, int32_t *d_jn_start, int32_t *d_jn_end, uint32_t *d_out_jn, uint32_t *d_out_col,
+                            uint32_t *d_out_molecules, uint64_t *d_out_reads, uint64_t *junctions, uint64_t *nnz, uint32_t n_cus,
+                            unsigned long long *h_pinned, hipStream_t s);
+
 // ---- family sizes, UMI distances and UMI usage of a batched call (umihip_stats.hip: umi_dedup_stats) ----
 constexpr uint32_t STATS_LANE_MAX = 8;    // a bucket of more entries is a wave's
 constexpr uint32_t STATS_HIST_LDS = 2048; // family-size bins a block counts in LDS; the others by global atomics

@@ -121,6 +121,36 @@
 // Refused with status 101 before the GPU is woken: the flag without --count-matrix or with --stage gpu;
 // --saturation-points or --saturation-seed without the flag; L that is not a number in 1..32; S that is not a number in
 // 0..2^64-1; any of the three given twice with different values; a FILE that cannot be created (its parent must exist).
+// --junction-matrix (no argument; with --per-gene --count-matrix DIR, with or without --per-cell -- without it there is the
+// one column "all" -- and with everything those go with: GX tags or --gene-annotation under any rule, --umi-filtering
+// multi-gene, --cell-filter, --velocity, --saturation-curve, --output-stats, both whitelists, -k, --algo, --distance edit,
+// --devices; tests/junction_model.py defines it, include/umihip.h has the same rule): a count matrix whose rows are splice
+// junctions instead of genes, what STARsolo's --soloFeatures SJ writes.  A junction of a read is the stretch between two
+// consecutive non-empty blocks of its CIGAR (blocks as --gene-rule transcript walks them: M, =, X and D extend a block,
+// an N of any length closes it, I, S, H and P consume nothing), where it is at least one base long and ends at or
+// before 2^31 - 1: several N with only I, S, H or P between them are one junction, a leading, trailing or zero-length
+// N gives none, a D never makes one.  Its identity is (reference, start, end); it has no strand, because there is no
+// genome here to read a motif from.  A molecule of the run -- a surviving UMI of a (cell, gene) -- supports a junction
+// when one of its reads has it.  The collapse is the run's own: nothing is collapsed again per junction, which is not
+// what STARsolo's SJ does (it dedups UMIs per cell and junction).  Reads the run did not stage (no gene, several genes,
+// no barcode, no UMI) contribute no junction, and reads under a UMI that --umi-filtering multi-gene removed count
+// nowhere.  One call to umi_junction_matrix on the first device, after the matrix and after --cell-filter's call, over
+// the staged reads' reference, position, CIGAR words and entry (as --velocity builds it), the mask the matrix was
+// counted from, root[] and the buckets' cell; its capacity is the number of N words among those reads, an upper bound.
+// DIR/junctions/: features.tsv, a line "<reference name>\t<start + 1>\t<end>" per junction -- the intron's first and
+// last base, 1-based -- sorted by (reference id, start, end); barcodes.tsv, the raw file's bytes; matrix.mtx, the
+// molecules, laid out like the raw matrix.mtx, "junction cell count" sorted by cell, then junction; reads.mtx, the
+// reads under surviving UMIs that have the junction.  With --cell-filter also DIR/junctions/filtered/, the same four
+// files for the called cells: columns renumbered as in DIR/filtered/, junctions with no entry left dropped and the rest
+// renumbered; the cells are called from the gene matrix exactly as without the flag.  The summary gains, behind every
+// other line, "Junction matrix: on", "Number of spliced reads counted", "Number of junction occurrences", "Number of
+// distinct junctions" and "Number of (cell, junction) pairs".  The BAM, every other file and the other summary lines are
+// byte for byte what --stage host writes without the flag.  The flag stages on the host, as --velocity does: --stage auto
+// goes to the host.
+// Refused with status 101 before the GPU is woken: the flag without --count-matrix or with --stage gpu; a DIR/junctions
+// or DIR/junctions/filtered that cannot be made.  Not built: junction strand and motif, an annotated / novel column
+// from the GTF, junctions of reads outside every gene, per-junction UMI collapse as STARsolo does it, --two-pass,
+// --paired, a read's entry from the GPU staging.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -210,6 +240,7 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
     bool transcript_introns_given = false;
     int transcript_introns_mode = UMI_INTRONS_OFF; // as UMI_INTRONS_* (filled in by validate())
     bool velocity = false; // --velocity: spliced, unspliced and ambiguous matrices beside --count-matrix's
+    bool junction_matrix = false;  // --junction-matrix: molecules per cell and splice junction beside --count-matrix's
     std::string saturation_curve;  // --saturation-curve FILE: saturation and medians per depth (the rule is at the top)
     int saturation_points = 10;    // --saturation-points L
     uint64_t saturation_seed = 0;  // --saturation-seed S
@@ -359,6 +390,11 @@ void usage()
               "                           and molecules per cell at L depths to FILE (tab-separated), by nested subsampling\n"
               "                           of the reads on the GPU; the molecules are the run's own, nothing is collapsed\n"
               "                           again per depth (host staging; not with --stage gpu)\n"
+              "      --junction-matrix    with --per-gene --count-matrix: write the molecules per cell and splice junction to\n"
+              "                           DIR/junctions (features.tsv: reference, first and last base of the intron;\n"
+              "                           barcodes.tsv, matrix.mtx, reads.mtx); junctions come from the CIGARs of the reads\n"
+              "                           the run staged, have no strand, and nothing is collapsed again per junction\n"
+              "                           (host staging; not with --stage gpu)\n"
               "      --saturation-points <L> with --saturation-curve: depths, 1..32 [default: 10]\n"
               "      --saturation-seed <S> with --saturation-curve: seed of the reads' hash, 0..2^64-1 [default: 0]\n"
               "      --count-matrix <DIR> with --per-gene: write the molecules per cell and gene to DIR (made if it is\n"
@@ -491,6 +527,7 @@ Cli parse(int argc, char **argv)
             c.transcript_introns_given = true;
         }
         else if (a == "--velocity") c.velocity = true;
+        else if (a == "--junction-matrix") c.junction_matrix = true;
         else if (a == "--gene-rule" || a == "--annotation-transcript-attribute") {
             const std::string v = need(i);
             std::string &value = a == "--gene-rule" ? c.gene_rule : c.annotation_transcript_attribute;
@@ -789,6 +826,11 @@ bool validate(Cli &args)
         if (args.stage == "gpu")
             die("--stage gpu does not go with --saturation-curve (a read's entry is kept by the host staging alone)");
     }
+    // --junction-matrix: likewise (its directories are made last)
+    if (args.junction_matrix) {
+        if (args.count_matrix.empty()) die("--junction-matrix goes with --count-matrix DIR only");
+        if (args.stage == "gpu") die("--stage gpu does not go with --junction-matrix");
+    }
     // --umi-filtering: likewise
     if (args.umi_filtering_given &&args.umi_filtering != "none" && args.umi_filtering != "multi-gene")
         die("--umi-filtering wants none or multi-gene: '" + args.umi_filtering + "'");
@@ -894,6 +936,17 @@ bool validate(Cli &args)
                 struct stat sb;
                 if (why != EEXIST || stat(dir.c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode))
                     die("cannot make the directory " + dir + " for --velocity: " + std::strerror(why));
+            }
+    }
+    if (args.junction_matrix) {
+        std::vector<std::string> dirs{args.count_matrix + "/junctions"};
+        if (args.cell_filter_given) dirs.push_back(args.count_matrix + "/junctions/filtered");
+        for (const std::string &dir : dirs)
+            if (mkdir(dir.c_str(), 0777) != 0) {
+                const int why = errno;
+                struct stat sb;
+                if (why != EEXIST || stat(dir.c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode))
+                    die("cannot make the directory " + dir + " for --junction-matrix: " + std::strerror(why));
             }
     }
     for (const std::string &path : output_stats_paths(args)) {

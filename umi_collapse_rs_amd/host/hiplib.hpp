@@ -35,6 +35,8 @@
 // umi_assign_genes_transcripts' place; with --velocity it tells the classes too, and umi_assign_genes_classes is not asked for.
 //
 // --saturation-curve FILE: likewise umi_saturation_curve.
+//
+// --junction-matrix: likewise umi_junction_matrix.
 #pragma once
 #include <chrono>
 #include <dlfcn.h>
@@ -128,6 +130,9 @@ struct HipLib {
     // --saturation-curve: likewise
     bool want_saturation = false;
     decltype(&umi_saturation_curve) saturation_curve = nullptr;
+    // --junction-matrix: likewise
+    bool want_junctions = false;
+    decltype(&umi_junction_matrix) junction_matrix = nullptr;
     // (the HIP runtime the library brings along: device buffers for the arrays above)
     int (*hip_set_device)(int) = nullptr; // (the current device is per thread: the context was made on another)
     int (*hip_malloc)(void **, size_t) = nullptr;
@@ -144,7 +149,7 @@ struct HipLib {
           want_transcript_classes(args.gene_annotation_given && args.gene_rule_transcript && args.transcript_introns_mode != UMI_INTRONS_OFF),
           want_introns(args.gene_annotation_given && args.gene_introns_mode != UMI_INTRONS_OFF && !args.velocity),
           want_velocity(args.velocity), want_gene_classes(args.velocity && args.transcript_introns_mode == UMI_INTRONS_OFF),
-          want_saturation(!args.saturation_curve.empty())
+          want_saturation(!args.saturation_curve.empty()), want_junctions(args.junction_matrix)
     {
     }
     bool load()
@@ -199,6 +204,7 @@ struct HipLib {
             velocity_matrix = (decltype(velocity_matrix))sym("umi_velocity_matrix");
         }
         if (want_saturation) saturation_curve = (decltype(saturation_curve))sym("umi_saturation_curve");
+        if (want_junctions) junction_matrix = (decltype(junction_matrix))sym("umi_junction_matrix");
         hip_set_device = (decltype(hip_set_device))sym("hipSetDevice");
         hip_malloc = (decltype(hip_malloc))sym("hipMalloc");
         hip_memcpy = (decltype(hip_memcpy))sym("hipMemcpy");

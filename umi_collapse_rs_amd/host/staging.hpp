@@ -390,6 +390,7 @@ struct Summary {
     uint64_t mg_counts[3] = {0, 0, 0}; // --umi-filtering multi-gene: UMIs in several genes of a cell, molecules removed, their reads
     uint64_t cell_counts[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // --cell-filter: umi_call_cells' counts
     uint64_t saturation_reads = 0, saturation_molecules = 0; // --saturation-curve: the full depth's counted reads and molecules
+    uint64_t junction_counts[4] = {0, 0, 0, 0}; // --junction-matrix: umi_junction_matrix' counts
     // floor(10000 (reads - molecules) / reads) as 0.dddd, in integers; 0.0000 for no reads (--saturation-curve)
     static std::string saturation_text(uint64_t reads, uint64_t molecules)
     {
@@ -492,6 +493,13 @@ struct Summary {
         if (args.call_consensus) {
             std::fprintf(stderr, "Number of clusters below --call-consensus-min-reads: %zu\n", n_below);
             std::fprintf(stderr, "Number of clusters without a consensus: %zu\n", n_without);
+        }
+        if (args.junction_matrix) {
+            std::fprintf(stderr, "Junction matrix: on\n");
+            std::fprintf(stderr, "Number of spliced reads counted: %llu\n", (unsigned long long)junction_counts[0]);
+            std::fprintf(stderr, "Number of junction occurrences: %llu\n", (unsigned long long)junction_counts[1]);
+            std::fprintf(stderr, "Number of distinct junctions: %llu\n", (unsigned long long)junction_counts[2]);
+            std::fprintf(stderr, "Number of (cell, junction) pairs: %llu\n", (unsigned long long)junction_counts[3]);
         }
     }
 };

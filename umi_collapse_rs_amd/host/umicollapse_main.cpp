@@ -107,6 +107,10 @@
 // --cell-filter is given, one call to umi_saturation_curve over the reads' entries, the surviving mask, root[], the buckets'
 // gene and cell and the called cells gives every depth's row of FILE; everything else stays byte for byte what --stage
 // host writes without the flag.
+// --junction-matrix (with --per-gene --count-matrix DIR; cli.hpp has the rule and the files): the reads are staged on the
+// host likewise; behind the calls above one call to umi_junction_matrix over the staged reads' reference, position, CIGAR
+// words and entry, the surviving mask, root[] and the buckets' cell gives the junction table and its triplets, written to
+// DIR/junctions/ (and, for the called cells, to DIR/junctions/filtered/); everything else stays byte for byte likewise.
 // --algo cluster: connected components of "within -k" (cli.hpp); every pipeline here only forwards the algorithm
 // to the library, so it goes with every flag --algo dir goes with.
 // Not implemented, as in the reference: --algo cc (that spelling stays refused; `cluster` is the mode's name).
@@ -162,7 +166,7 @@ struct OnePass {
     const int algo = args.algo_id, merge = args.merge_id;
     const unsigned T = std::max(1u, args.num_threads);
     const bool need_clusters = args.track_clusters || args.call_consensus; // every read's entry, every entry's root
-    const bool need_entries = need_clusters || args.velocity || !args.saturation_curve.empty(); // every read's entry: the host staging keeps it
+    const bool need_entries = need_clusters || args.velocity || !args.saturation_curve.empty() || args.junction_matrix; // every read's entry: the host staging keeps it
     const bool need_root = need_entries || !args.output_stats.empty() || args.filter_multigene; // root[] of the collapse (no host
                                                                                                 // staging for it alone)
 
@@ -1109,6 +1113,111 @@ struct OnePass {
             }
         }
         if (!args.saturation_curve.empty()) saturation_curve(n_rows, n_cols);
+        if (args.junction_matrix) junction_matrix(n_cols, write);
+    }
+
+    // --junction-matrix: molecules and reads per (cell, junction) in one call over the staged reads' reference, position,
+    // CIGAR words and entry, the mask the matrix was counted from, root[] and the buckets' cell; then DIR/junctions' four
+    // files and, for the called cells, DIR/junctions/filtered's (cli.hpp has the rule and the files)
+    void junction_matrix(uint32_t n_cols, const std::function<void(const char *, const std::string &)> &write)
+    {
+        std::vector<uint32_t> cand;
+        std::vector<uint64_t> c_off(1, 0);
+        uint64_t capacity = 0; // the N words among them: no read has more junctions than N words
+        for (uint32_t ri = 0; ri < n_rec; ri++) {
+            const umi::bam::Record &r = in.records[ri];
+            if (info[ri].state != 0 || r.is_unmapped() || r.tid() < 0) continue;
+            cand.push_back(ri);
+            c_off.push_back(c_off.back() + r.n_cigar());
+        }
+        const size_t nc = cand.size();
+        std::vector<int32_t> r_ref(nc + 1), r_pos(nc + 1);
+        std::vector<uint32_t> r_entry(nc + 1), words((size_t)c_off.back() + 1);
+        for (size_t j = 0; j < nc; j++) {
+            const umi::bam::Record &r = in.records[cand[j]];
+            r_ref[j] = r.tid();
+            r_pos[j] = r.pos();
+            r_entry[j] = entry_of[cand[j]];
+            std::memcpy(&words[(size_t)c_off[j]], r.cigar(), 4 * (size_t)r.n_cigar());
+            for (uint64_t w = c_off[j]; w < c_off[j + 1]; w++) capacity += (words[(size_t)w] & 15u) == 3u;
+        }
+        const size_t cap = (size_t)capacity + 1;
+        std::vector<int32_t> jn_ref(cap), jn_start(cap), jn_end(cap);
+        std::vector<uint32_t> o_jn(cap), o_col(cap), o_mol(cap);
+        std::vector<uint64_t> o_reads(cap);
+        uint64_t *counts = sum.junction_counts;
+        if (nb && nc) {
+            need_ctx();
+            if (!lib.junction_matrix) die("libumihip.so lacks umi_junction_matrix");
+            const std::vector<uint32_t> one_column(args.per_cell ? 0 : nb, 0u);
+            if (lib.junction_matrix(ctx, r_ref.data(), r_pos.data(), words.data(), c_off.data(), r_entry.data(), nc, survivors().data(),
+                                    root.data(), off.data(), nb, args.per_cell ? bucket_cell.data() : one_column.data(), n_cols, capacity,
+                                    jn_ref.data(), jn_start.data(), jn_end.data(), o_jn.data(), o_col.data(), o_mol.data(),
+                                    o_reads.data(), counts) != UMI_OK)
+                die(lib.last_error());
+        }
+        // the references' names, from the header
+        std::vector<std::string_view> ref_names;
+        {
+            const uint8_t *p = in.data.data();
+            size_t q = 8 + (size_t)umi::bam::rd_i32(p + 4) + 4;
+            for (int32_t r = 0; r < in.n_ref; r++) {
+                const size_t l_name = (size_t)umi::bam::rd_i32(p + q);
+                std::string_view name((const char *)p + q + 4, l_name);
+                if (!name.empty() && name.back() == '\0') name.remove_suffix(1);
+                ref_names.push_back(name);
+                q += 4 + l_name + 4;
+            }
+        }
+        // a directory's four files: the junctions `rows` of the table in this order, the triplets [0, nnz) with their
+        // junctions numbered by `row_of`
+        auto files = [&](const std::string &dir, const std::vector<uint32_t> &rows, const std::vector<uint32_t> &row_of, uint32_t cols,
+                         bool filtered, uint64_t nnz) {
+            std::string text;
+            for (const uint32_t j : rows) {
+                const int32_t ref = jn_ref[j];
+                text.append(ref < (int32_t)ref_names.size() ? ref_names[(size_t)ref] : std::string_view("*")).append("\t");
+                text.append(std::to_string((int64_t)jn_start[j] + 1)).append("\t").append(std::to_string(jn_end[j])).append("\n");
+            }
+            write((dir + "features.tsv").c_str(), text);
+            text.clear();
+            if (!args.per_cell) text = "all\n";
+            for (size_t c = 0; c < cell_names.size() && args.per_cell; c++)
+                if (!filtered || called_col[c] != UINT32_MAX) text.append(cell_names[c]).append("\n");
+            write((dir + "barcodes.tsv").c_str(), text);
+            const std::string head = "%%MatrixMarket matrix coordinate integer general\n" + std::to_string(rows.size()) + " " +
+                                     std::to_string(cols) + " " + std::to_string(nnz) + "\n";
+            std::string mol = head, rd = head;
+            for (uint64_t i = 0; i < nnz; i++) {
+                const std::string at = std::to_string(row_of[o_jn[i]] + 1) + " " + std::to_string(o_col[i] + 1) + " ";
+                mol.append(at).append(std::to_string(o_mol[i])).append("\n");
+                rd.append(at).append(std::to_string(o_reads[i])).append("\n");
+            }
+            write((dir + "matrix.mtx").c_str(), mol);
+            write((dir + "reads.mtx").c_str(), rd);
+        };
+        const size_t n_jn = (size_t)counts[2];
+        std::vector<uint32_t> rows(n_jn), row_of(n_jn + 1, 0);
+        for (size_t j = 0; j < n_jn; j++) rows[j] = row_of[j] = (uint32_t)j;
+        files("junctions/", rows, row_of, n_cols, false, counts[3]);
+        if (args.cell_filter_given) { // the called cells: their columns as DIR/filtered's, the junctions they still have
+            std::vector<uint8_t> used(n_jn + 1, 0);
+            uint64_t w = 0;
+            for (uint64_t i = 0; i < counts[3]; i++) {
+                if (o_col[i] >= called_col.size() || called_col[o_col[i]] == UINT32_MAX) continue;
+                o_jn[w] = o_jn[i], o_col[w] = called_col[o_col[i]], o_mol[w] = o_mol[i], o_reads[w] = o_reads[i];
+                used[o_jn[w]] = 1;
+                w++;
+            }
+            rows.clear();
+            for (size_t j = 0; j < n_jn; j++)
+                if (used[j]) {
+                    row_of[j] = (uint32_t)rows.size();
+                    rows.push_back((uint32_t)j);
+                }
+            files("junctions/filtered/", rows, row_of, (uint32_t)sum.cell_counts[1], true, w);
+        }
+        lap("junction matrix");
     }
 
     // --saturation-curve: reads, molecules, pairs and the medians of the selected cells at every depth, in one call over
