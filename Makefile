@@ -17,7 +17,7 @@ OBJS := $(patsubst %,$(OBJDIR)/%.o,$(SRCS))
 DEVDIR := build/obj_dev
 DEVLIB := $(PKG)/libumihip_dev.so
 DEVOBJS := $(patsubst %,$(DEVDIR)/%.o,$(SRCS)) $(DEVDIR)/umihip_legacy.o $(DEVDIR)/umihip_sort.o
-HDRS := $(CSRC)/umihip_internal.h $(CSRC)/umihip_cons_group.h $(CSRC)/umihip_device.h $(CSRC)/umihip_plan.hpp $(CSRC)/umihip_io_layout.hpp $(CSRC)/umihip_host.hpp $(CSRC)/umihip_gene_index.hpp $(CSRC)/umihip_transcript_index.hpp $(CSRC)/umihip_junction_walk.hpp include/umihip.h
+HDRS := $(CSRC)/umihip_internal.h $(CSRC)/umihip_cons_group.h $(CSRC)/umihip_device.h $(CSRC)/umihip_plan.hpp $(CSRC)/umihip_io_layout.hpp $(CSRC)/umihip_host.hpp $(CSRC)/umihip_gene_index.hpp $(CSRC)/umihip_transcript_index.hpp $(CSRC)/umihip_junction_walk.hpp $(CSRC)/umihip_pair_table.h include/umihip.h
 CLI := $(PKG)/bin/umicollapse
 
 all: $(LIB) oracle cpptest primtest trtest jntest $(CLI)

@@ -47,6 +47,10 @@ One kernel a source file at a time (seven builds; the tests of this file that tu
 The first deep input left cons_deep_kernel's mutant green: half of 8,322 reads call the same bases with capped
 qualities.  The deepest cluster now votes A over C at one base by a margin of 7 (grid_trip_inputs.CONS_CLOSE_MARGIN),
 which any read left out moves.
+
+Kernel names since: count_heads_kernel, velocity_heads_kernel, saturation_heads_kernel and mg_heads_key_kernel are one
+kernel, pair_heads_kernel<256> (csrc/umihip_pair_table.h).  It loops grid-stride; of its callers only the saturation
+curve launches it under the cap, the others in one trip as before, so none of the rows above is another kernel's now.
 """
 import numpy as np
 import pytest

@@ -5,30 +5,31 @@
 
 using namespace umihip;
 
-// ---- molecules and reads per (column, row) pair ---------------------------------------------------
+// ---- what the calls over a bucket table share ---------------------------------------------------------
 namespace {
-// what both forms check before a device is looked at (the context last)
-int cm_check(umi_ctx *ctx, const void *kept, const void *freq, const uint64_t *bucket_off, uint64_t n_buckets, const void *row,
-             const void *col, const void *out_row, const void *out_col, const void *out_molecules, const void *out_reads,
-             const uint64_t *nnz)
+// the first device of a multi-device context (as umi_correct_barcodes)
+umi_ctx *first_device(umi_ctx *ctx) { return ctx->subs.empty() ? ctx : ctx->subs[0]; }
+
+// what every *_check asks of the table itself (limit: the call files buckets by a 30-bit index)
+int check_bucket_table(const uint64_t *bucket_off, uint64_t n_buckets, bool limit = true)
 {
-    if (!nnz) return fail(UMI_ERR_ARG, "nnz is NULL");
-    if (n_buckets >= (1ull << 30))
+    if (limit && n_buckets >= (1ull << 30))
         return fail(UMI_ERR_ARG, "%llu buckets exceed the 30-bit index space of one call", (unsigned long long)n_buckets);
     if (n_buckets && !bucket_off) return fail(UMI_ERR_ARG, "bucket_off is NULL");
     if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
-    if (n_buckets && (!row || !col || !out_row || !out_col || !out_molecules || !out_reads))
-        return fail(UMI_ERR_ARG, "a required pointer is NULL");
-    if (n_buckets && bucket_off[n_buckets] && (!kept || !freq)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
-    if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
     return UMI_OK;
 }
 
-// The table walked once into the pinned staging: its non-empty buckets' offsets (a run of equal offsets is
-// one) and, from the first empty bucket on, their numbers.  *m: the non-empty buckets; *idx: null where
-// nothing was left out.  extra: pinned bytes of the call's own behind the two, at *extra_at.
-int cm_walk(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, uint32_t *m, const uint64_t **off, const uint32_t **idx,
-            size_t extra = 0, unsigned long long **extra_at = nullptr)
+// A table as the device code takes it, in the pinned staging: the m non-empty buckets' m + 1 offsets (a run of
+// equal offsets is one) and, from the first empty bucket on, their numbers (null where nothing was left out).
+struct BucketTable {
+    uint32_t m = 0;
+    const uint64_t *off = nullptr;
+    const uint32_t *idx = nullptr;
+};
+
+// The table walked once into the pinned staging.  extra: pinned bytes of the call's own behind it, at *extra_at.
+int cm_walk(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, BucketTable *t, size_t extra, unsigned long long **extra_at)
 {
     int rc;
     const size_t off_bytes = ((size_t)n_buckets + 1) * 8, tables = (off_bytes + (size_t)n_buckets * 4 + 7) & ~(size_t)7;
@@ -45,20 +46,56 @@ int cm_walk(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, uint32
         x[k] = (uint32_t)b;
         o[++k] = hi;
     }
-    *m = k;
-    *off = o;
-    *idx = k == n_buckets ? nullptr : x;
+    t->m = k;
+    t->off = o;
+    t->idx = k == n_buckets ? nullptr : x;
     return UMI_OK;
 }
 
-int cm_run(umi_ctx *ctx, const uint8_t *d_kept, const int32_t *d_freq, uint32_t m, const uint64_t *h_off, const uint32_t *h_idx,
-           const uint32_t *d_row, const uint32_t *d_col, uint32_t n_rows, uint32_t n_cols, uint32_t *d_out_row, uint32_t *d_out_col,
+// What a call does first once it has to touch its device (n_buckets >= 1): the device made current, a deferred call
+// let end (its counters lie in the pinned block this call reads through), the table walked.
+int table_begin(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, BucketTable *t, size_t extra = 0,
+                unsigned long long **extra_at = nullptr)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    settle(ctx);
+    return cm_walk(ctx, bucket_off, n_buckets, t, extra, extra_at);
+}
+// ... and a matrix of no rows or no columns refused where a bucket is not empty
+int matrix_begin(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, uint32_t n_rows, uint32_t n_cols, BucketTable *t,
+                 size_t extra = 0, unsigned long long **extra_at = nullptr)
+{
+    if (int rc = table_begin(ctx, bucket_off, n_buckets, t, extra, extra_at)) return rc;
+    if (t->m && (n_rows == 0 || n_cols == 0))
+        return fail(UMI_ERR_ARG, "a matrix of %u rows and %u columns with a non-empty bucket", n_rows, n_cols);
+    return UMI_OK;
+}
+} // namespace
+
+// ---- molecules and reads per (column, row) pair ---------------------------------------------------
+namespace {
+// what both forms check before a device is looked at (the context last)
+int cm_check(umi_ctx *ctx, const void *kept, const void *freq, const uint64_t *bucket_off, uint64_t n_buckets, const void *row,
+             const void *col, const void *out_row, const void *out_col, const void *out_molecules, const void *out_reads,
+             const uint64_t *nnz)
+{
+    if (!nnz) return fail(UMI_ERR_ARG, "nnz is NULL");
+    if (int rc = check_bucket_table(bucket_off, n_buckets)) return rc;
+    if (n_buckets && (!row || !col || !out_row || !out_col || !out_molecules || !out_reads))
+        return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (n_buckets && bucket_off[n_buckets] && (!kept || !freq)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
+    if (!ctx) return fail(UMI_ERR_ARG, "ctx is NULL");
+    return UMI_OK;
+}
+
+int cm_run(umi_ctx *ctx, const uint8_t *d_kept, const int32_t *d_freq, const BucketTable &t, const uint32_t *d_row,
+           const uint32_t *d_col, uint32_t n_rows, uint32_t n_cols, uint32_t *d_out_row, uint32_t *d_out_col,
            uint32_t *d_out_molecules, uint64_t *d_out_reads, uint64_t *nnz, hipStream_t s)
 {
     int rc;
-    if ((rc = ctx->call_ws.reserve(count_workspace_bytes(m, h_idx != nullptr)))) return rc;
+    if ((rc = ctx->call_ws.reserve(count_workspace_bytes(t.m, t.idx != nullptr)))) return rc;
     uint64_t bad = 0;
-    const int r = count_matrix_on_device(ctx->call_ws.p, d_kept, d_freq, h_off, h_idx, m, d_row, d_col, n_rows, n_cols, d_out_row,
+    const int r = count_matrix_on_device(ctx->call_ws.p, d_kept, d_freq, t.off, t.idx, t.m, d_row, d_col, n_rows, n_cols, d_out_row,
                                          d_out_col, d_out_molecules, d_out_reads, nnz, &bad, (uint32_t)ctx->n_cus, ctx->h_counters, s);
     if (r < 0) return fail(UMI_ERR_HIP, "count matrix: %s", hipGetErrorString((hipError_t)(-r)));
     if (bad) {
@@ -79,18 +116,12 @@ int umi_count_matrix_device(umi_ctx *ctx, const uint8_t *d_kept, const int32_t *
 {
     int rc = cm_check(ctx, d_kept, d_freq, bucket_off, n_buckets, d_row, d_col, d_out_row, d_out_col, d_out_molecules, d_out_reads, nnz);
     if (rc) return rc;
-    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_correct_barcodes)
+    ctx = first_device(ctx);
     *nnz = 0;
     if (n_buckets == 0) return UMI_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
-    uint32_t m = 0;
-    const uint64_t *h_off = nullptr;
-    const uint32_t *h_idx = nullptr;
-    if ((rc = cm_walk(ctx, bucket_off, n_buckets, &m, &h_off, &h_idx))) return rc;
-    if (m == 0) return UMI_OK;
-    if (n_rows == 0 || n_cols == 0) return fail(UMI_ERR_ARG, "a matrix of %u rows and %u columns with a non-empty bucket", n_rows, n_cols);
-    return cm_run(ctx, d_kept, d_freq, m, h_off, h_idx, d_row, d_col, n_rows, n_cols, d_out_row, d_out_col, d_out_molecules,
+    BucketTable t;
+    if ((rc = matrix_begin(ctx, bucket_off, n_buckets, n_rows, n_cols, &t)) || t.m == 0) return rc;
+    return cm_run(ctx, d_kept, d_freq, t, d_row, d_col, n_rows, n_cols, d_out_row, d_out_col, d_out_molecules,
                   d_out_reads, nnz, (hipStream_t)hip_stream);
 }
 
@@ -100,18 +131,12 @@ int umi_count_matrix(umi_ctx *ctx, const uint8_t *kept, const int32_t *freq, con
 {
     int rc = cm_check(ctx, kept, freq, bucket_off, n_buckets, row, col, out_row, out_col, out_molecules, out_reads, nnz);
     if (rc) return rc;
-    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    ctx = first_device(ctx);
     *nnz = 0;
     if (n_buckets == 0) return UMI_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    settle(ctx);
-    uint32_t m = 0;
-    const uint64_t *h_off = nullptr;
-    const uint32_t *h_idx = nullptr;
-    if ((rc = cm_walk(ctx, bucket_off, n_buckets, &m, &h_off, &h_idx))) return rc;
-    if (m == 0) return UMI_OK;
-    if (n_rows == 0 || n_cols == 0) return fail(UMI_ERR_ARG, "a matrix of %u rows and %u columns with a non-empty bucket", n_rows, n_cols);
-    const size_t n = (size_t)bucket_off[n_buckets], nb = (size_t)n_buckets, cap = (size_t)m;
+    BucketTable t;
+    if ((rc = matrix_begin(ctx, bucket_off, n_buckets, n_rows, n_cols, &t)) || t.m == 0) return rc;
+    const size_t n = (size_t)bucket_off[n_buckets], nb = (size_t)n_buckets, cap = (size_t)t.m;
     HostIo io(ctx);
     const auto d_freq = io.in(freq, n * 4);
     const auto d_row = io.in(row, nb * 4), d_col = io.in(col, nb * 4);
@@ -120,7 +145,7 @@ int umi_count_matrix(umi_ctx *ctx, const uint8_t *kept, const int32_t *freq, con
     const auto d_kept = io.in(kept, n);
     uint64_t got = 0;
     if ((rc = io.open()) ||
-        (rc = cm_run(ctx, d_kept, d_freq, m, h_off, h_idx, d_row, d_col, n_rows, n_cols, d_orow, d_ocol, d_omol, d_oreads, &got,
+        (rc = cm_run(ctx, d_kept, d_freq, t, d_row, d_col, n_rows, n_cols, d_orow, d_ocol, d_omol, d_oreads, &got,
                      io.stream())) ||
         (rc = io.fetch(out_row, d_orow, (size_t)got)) || (rc = io.fetch(out_col, d_ocol, (size_t)got)) ||
         (rc = io.fetch(out_molecules, d_omol, (size_t)got)) || (rc = io.fetch(out_reads, d_oreads, (size_t)got)) ||
@@ -140,11 +165,10 @@ int vm_check(umi_ctx *ctx, const void *read_entry, const void *read_class, uint6
              const void *out_spliced, const void *out_unspliced, const void *out_ambiguous, const uint64_t *nnz)
 {
     if (!nnz) return fail(UMI_ERR_ARG, "nnz is NULL");
-    if (n_buckets >= (1ull << 30))
-        return fail(UMI_ERR_ARG, "%llu buckets exceed the 30-bit index space of one call", (unsigned long long)n_buckets);
-    if (n_reads >= (1ull << 32)) return fail(UMI_ERR_ARG, "%llu reads exceed the 32-bit index space of one call", (unsigned long long)n_reads);
-    if (n_buckets && !bucket_off) return fail(UMI_ERR_ARG, "bucket_off is NULL");
-    if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
+    // (the reads' limit is told between the table's: after too many buckets, before a table that is missing)
+    if (n_buckets < (1ull << 30) && n_reads >= (1ull << 32))
+        return fail(UMI_ERR_ARG, "%llu reads exceed the 32-bit index space of one call", (unsigned long long)n_reads);
+    if (int rc = check_bucket_table(bucket_off, n_buckets)) return rc;
     if (n_buckets && (!row || !col || !out_row || !out_col || !out_spliced || !out_unspliced || !out_ambiguous))
         return fail(UMI_ERR_ARG, "a required pointer is NULL");
     if (n_buckets && bucket_off[n_buckets] && (!kept || !root)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
@@ -156,16 +180,16 @@ int vm_check(umi_ctx *ctx, const void *read_entry, const void *read_class, uint6
 }
 
 int vm_run(umi_ctx *ctx, const uint32_t *d_read_entry, const uint8_t *d_read_class, uint64_t n_reads, const uint8_t *d_kept,
-           const uint32_t *d_root, uint64_t n, uint32_t m, const uint64_t *h_off, const uint32_t *h_idx, const uint32_t *d_row,
-           const uint32_t *d_col, uint32_t n_rows, uint32_t n_cols, uint32_t *d_out_row, uint32_t *d_out_col, uint32_t *d_out_spliced,
+           const uint32_t *d_root, uint64_t n, const BucketTable &t, const uint32_t *d_row, const uint32_t *d_col, uint32_t n_rows,
+           uint32_t n_cols, uint32_t *d_out_row, uint32_t *d_out_col, uint32_t *d_out_spliced,
            uint32_t *d_out_unspliced, uint32_t *d_out_ambiguous, uint64_t *nnz, hipStream_t s)
 {
     int rc;
-    if ((rc = ctx->call_ws.reserve(velocity_workspace_bytes(n, m, h_idx != nullptr)))) return rc;
+    if ((rc = ctx->call_ws.reserve(velocity_workspace_bytes(n, t.m, t.idx != nullptr)))) return rc;
     uint64_t bad = 0, bad_read = 0;
     int kind = 0;
-    const int r = velocity_matrix_on_device(ctx->call_ws.p, d_read_entry, d_read_class, (uint32_t)n_reads, d_kept, d_root, n, h_off,
-                                            h_idx, m, d_row, d_col, n_rows, n_cols, d_out_row, d_out_col, d_out_spliced,
+    const int r = velocity_matrix_on_device(ctx->call_ws.p, d_read_entry, d_read_class, (uint32_t)n_reads, d_kept, d_root, n, t.off,
+                                            t.idx, t.m, d_row, d_col, n_rows, n_cols, d_out_row, d_out_col, d_out_spliced,
                                             d_out_unspliced, d_out_ambiguous, ctx->velocity_skip, nnz, &bad, &kind, &bad_read,
                                             (uint32_t)ctx->n_cus, ctx->h_counters, s);
     if (r < 0) return fail(UMI_ERR_HIP, "velocity matrix: %s", hipGetErrorString((hipError_t)(-r)));
@@ -195,18 +219,12 @@ int umi_velocity_matrix_device(umi_ctx *ctx, const uint32_t *d_read_entry, const
     int rc = vm_check(ctx, d_read_entry, d_read_class, n_reads, d_kept, d_root, bucket_off, n_buckets, d_row, d_col, d_out_row,
                       d_out_col, d_out_spliced, d_out_unspliced, d_out_ambiguous, nnz);
     if (rc) return rc;
-    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_count_matrix)
+    ctx = first_device(ctx);
     *nnz = 0;
     if (n_buckets == 0) return UMI_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
-    uint32_t m = 0;
-    const uint64_t *h_off = nullptr;
-    const uint32_t *h_idx = nullptr;
-    if ((rc = cm_walk(ctx, bucket_off, n_buckets, &m, &h_off, &h_idx))) return rc;
-    if (m == 0) return UMI_OK;
-    if (n_rows == 0 || n_cols == 0) return fail(UMI_ERR_ARG, "a matrix of %u rows and %u columns with a non-empty bucket", n_rows, n_cols);
-    return vm_run(ctx, d_read_entry, d_read_class, n_reads, d_kept, d_root, bucket_off[n_buckets], m, h_off, h_idx, d_row, d_col,
+    BucketTable t;
+    if ((rc = matrix_begin(ctx, bucket_off, n_buckets, n_rows, n_cols, &t)) || t.m == 0) return rc;
+    return vm_run(ctx, d_read_entry, d_read_class, n_reads, d_kept, d_root, bucket_off[n_buckets], t, d_row, d_col,
                   n_rows, n_cols, d_out_row, d_out_col, d_out_spliced, d_out_unspliced, d_out_ambiguous, nnz, (hipStream_t)hip_stream);
 }
 
@@ -219,18 +237,12 @@ int umi_velocity_matrix(umi_ctx *ctx, const uint32_t *read_entry, const uint8_t 
     int rc = vm_check(ctx, read_entry, read_class, n_reads, kept, root, bucket_off, n_buckets, row, col, out_row, out_col, out_spliced,
                       out_unspliced, out_ambiguous, nnz);
     if (rc) return rc;
-    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    ctx = first_device(ctx);
     *nnz = 0;
     if (n_buckets == 0) return UMI_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    settle(ctx);
-    uint32_t m = 0;
-    const uint64_t *h_off = nullptr;
-    const uint32_t *h_idx = nullptr;
-    if ((rc = cm_walk(ctx, bucket_off, n_buckets, &m, &h_off, &h_idx))) return rc;
-    if (m == 0) return UMI_OK;
-    if (n_rows == 0 || n_cols == 0) return fail(UMI_ERR_ARG, "a matrix of %u rows and %u columns with a non-empty bucket", n_rows, n_cols);
-    const size_t n = (size_t)bucket_off[n_buckets], nb = (size_t)n_buckets, cap = (size_t)m, nr = (size_t)n_reads;
+    BucketTable t;
+    if ((rc = matrix_begin(ctx, bucket_off, n_buckets, n_rows, n_cols, &t)) || t.m == 0) return rc;
+    const size_t n = (size_t)bucket_off[n_buckets], nb = (size_t)n_buckets, cap = (size_t)t.m, nr = (size_t)n_reads;
     HostIo io(ctx);
     const auto d_entry = io.in(read_entry, nr * 4);
     const auto d_root = io.in(root, n * 4);
@@ -241,7 +253,7 @@ int umi_velocity_matrix(umi_ctx *ctx, const uint32_t *read_entry, const uint8_t 
     const auto d_kept = io.in(kept, n);
     uint64_t got = 0;
     if ((rc = io.open()) ||
-        (rc = vm_run(ctx, d_entry, d_class, n_reads, d_kept, d_root, n, m, h_off, h_idx, d_row, d_col, n_rows, n_cols, d_orow, d_ocol,
+        (rc = vm_run(ctx, d_entry, d_class, n_reads, d_kept, d_root, n, t, d_row, d_col, n_rows, n_cols, d_orow, d_ocol,
                      d_os, d_ou, d_oa, &got, io.stream())) ||
         (rc = io.fetch(out_row, d_orow, (size_t)got)) || (rc = io.fetch(out_col, d_ocol, (size_t)got)) ||
         (rc = io.fetch(out_spliced, d_os, (size_t)got)) || (rc = io.fetch(out_unspliced, d_ou, (size_t)got)) ||
@@ -262,10 +274,7 @@ int sc_check(umi_ctx *ctx, const void *read_entry, uint64_t n_reads, const void 
     if (!curve) return fail(UMI_ERR_ARG, "curve is NULL");
     if (n_levels < 1 || n_levels > 32) return fail(UMI_ERR_ARG, "n_levels %d outside 1..32", n_levels);
     if (n_reads >= (1ull << 32)) return fail(UMI_ERR_ARG, "%llu reads exceed the 32-bit index space of one call", (unsigned long long)n_reads);
-    if (n_buckets >= (1ull << 30))
-        return fail(UMI_ERR_ARG, "%llu buckets exceed the 30-bit index space of one call", (unsigned long long)n_buckets);
-    if (n_buckets && !bucket_off) return fail(UMI_ERR_ARG, "bucket_off is NULL");
-    if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
+    if (int rc = check_bucket_table(bucket_off, n_buckets)) return rc;
     if (n_buckets && (!row || !col)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
     if (n_buckets && bucket_off[n_buckets] && (!kept || !root)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
     if (n_buckets && bucket_off[n_buckets] && n_reads && !read_entry) return fail(UMI_ERR_ARG, "a required pointer is NULL");
@@ -277,35 +286,26 @@ int sc_check(umi_ctx *ctx, const void *read_entry, uint64_t n_reads, const void 
     return UMI_OK;
 }
 
-// the device made current, a deferred call let end, the table walked; *m == 0: the curve is all zeros and written
+// the table walked, with the pinned block of the call's own behind it; t->m == 0: the curve is all zeros and written
 int sc_begin(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, uint32_t n_rows, uint32_t n_cols, int n_levels,
-             uint64_t *curve, uint32_t *m, const uint64_t **h_off, const uint32_t **h_idx, unsigned long long **h_pinned)
+             uint64_t *curve, BucketTable *t, unsigned long long **h_pinned)
 {
     int rc;
-    *m = 0;
-    if (n_buckets) {
-        HIP_TRY(hipSetDevice(ctx->device));
-        settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
-        if ((rc = cm_walk(ctx, bucket_off, n_buckets, m, h_off, h_idx, (4 + 8 * (size_t)n_levels) * 8, h_pinned))) return rc;
-    }
-    if (*m == 0) {
-        memset(curve, 0, (size_t)n_levels * 8 * sizeof(uint64_t));
-        return UMI_OK;
-    }
-    if (n_rows == 0 || n_cols == 0) return fail(UMI_ERR_ARG, "a matrix of %u rows and %u columns with a non-empty bucket", n_rows, n_cols);
+    if (n_buckets && (rc = matrix_begin(ctx, bucket_off, n_buckets, n_rows, n_cols, t, (4 + 8 * (size_t)n_levels) * 8, h_pinned)))
+        return rc;
+    if (t->m == 0) memset(curve, 0, (size_t)n_levels * 8 * sizeof(uint64_t));
     return UMI_OK;
 }
 
 int sc_run(umi_ctx *ctx, const uint32_t *d_read_entry, uint64_t n_reads, const uint8_t *d_kept, const uint32_t *d_root, uint64_t n,
-           uint32_t m, const uint64_t *h_off, const uint32_t *h_idx, const uint32_t *d_row, const uint32_t *d_col, uint32_t n_rows,
-           uint32_t n_cols, uint64_t seed, int n_levels, const uint8_t *d_cell_mask, unsigned long long *h_pinned, uint64_t *curve,
-           hipStream_t s)
+           const BucketTable &t, const uint32_t *d_row, const uint32_t *d_col, uint32_t n_rows, uint32_t n_cols, uint64_t seed,
+           int n_levels, const uint8_t *d_cell_mask, unsigned long long *h_pinned, uint64_t *curve, hipStream_t s)
 {
     int rc;
-    if ((rc = ctx->call_ws.reserve(saturation_workspace_bytes(n, m, h_idx != nullptr, n_cols, n_levels)))) return rc;
+    if ((rc = ctx->call_ws.reserve(saturation_workspace_bytes(n, t.m, t.idx != nullptr, n_cols, n_levels)))) return rc;
     uint64_t bad = 0, bad_read = 0;
     int kind = 0;
-    const int r = saturation_curve_on_device(ctx->call_ws.p, d_read_entry, (uint32_t)n_reads, d_kept, d_root, n, h_off, h_idx, m, d_row,
+    const int r = saturation_curve_on_device(ctx->call_ws.p, d_read_entry, (uint32_t)n_reads, d_kept, d_root, n, t.off, t.idx, t.m, d_row,
                                              d_col, n_rows, n_cols, seed, n_levels, d_cell_mask, ctx->saturation_skip, &bad, &kind,
                                              &bad_read, (uint32_t)ctx->n_cus, h_pinned, s);
     if (r < 0) return fail(UMI_ERR_HIP, "saturation curve: %s", hipGetErrorString((hipError_t)(-r)));
@@ -332,13 +332,11 @@ int umi_saturation_curve_device(umi_ctx *ctx, const uint32_t *d_read_entry, uint
 {
     int rc = sc_check(ctx, d_read_entry, n_reads, d_kept, d_root, bucket_off, n_buckets, d_row, d_col, n_cols, n_levels, curve);
     if (rc) return rc;
-    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_count_matrix)
-    uint32_t m = 0;
-    const uint64_t *h_off = nullptr;
-    const uint32_t *h_idx = nullptr;
+    ctx = first_device(ctx);
+    BucketTable t;
     unsigned long long *h_pinned = nullptr;
-    if ((rc = sc_begin(ctx, bucket_off, n_buckets, n_rows, n_cols, n_levels, curve, &m, &h_off, &h_idx, &h_pinned)) || m == 0) return rc;
-    return sc_run(ctx, d_read_entry, n_reads, d_kept, d_root, bucket_off[n_buckets], m, h_off, h_idx, d_row, d_col, n_rows, n_cols, seed,
+    if ((rc = sc_begin(ctx, bucket_off, n_buckets, n_rows, n_cols, n_levels, curve, &t, &h_pinned)) || t.m == 0) return rc;
+    return sc_run(ctx, d_read_entry, n_reads, d_kept, d_root, bucket_off[n_buckets], t, d_row, d_col, n_rows, n_cols, seed,
                   n_levels, d_cell_mask, h_pinned, curve, (hipStream_t)hip_stream);
 }
 
@@ -348,12 +346,10 @@ int umi_saturation_curve(umi_ctx *ctx, const uint32_t *read_entry, uint64_t n_re
 {
     int rc = sc_check(ctx, read_entry, n_reads, kept, root, bucket_off, n_buckets, row, col, n_cols, n_levels, curve);
     if (rc) return rc;
-    if (!ctx->subs.empty()) ctx = ctx->subs[0];
-    uint32_t m = 0;
-    const uint64_t *h_off = nullptr;
-    const uint32_t *h_idx = nullptr;
+    ctx = first_device(ctx);
+    BucketTable t;
     unsigned long long *h_pinned = nullptr;
-    if ((rc = sc_begin(ctx, bucket_off, n_buckets, n_rows, n_cols, n_levels, curve, &m, &h_off, &h_idx, &h_pinned)) || m == 0) return rc;
+    if ((rc = sc_begin(ctx, bucket_off, n_buckets, n_rows, n_cols, n_levels, curve, &t, &h_pinned)) || t.m == 0) return rc;
     const size_t n = (size_t)bucket_off[n_buckets], nb = (size_t)n_buckets;
     HostIo io(ctx);
     const auto d_entry = io.in(read_entry, (size_t)n_reads * 4);
@@ -362,7 +358,7 @@ int umi_saturation_curve(umi_ctx *ctx, const uint32_t *read_entry, uint64_t n_re
     const auto d_kept = io.in(kept, n);
     const auto d_mask = io.in(cell_mask, (size_t)n_cols);
     if ((rc = io.open()) ||
-        (rc = sc_run(ctx, d_entry, n_reads, d_kept, d_root, n, m, h_off, h_idx, d_row, d_col, n_rows, n_cols, seed, n_levels, d_mask,
+        (rc = sc_run(ctx, d_entry, n_reads, d_kept, d_root, n, t, d_row, d_col, n_rows, n_cols, seed, n_levels, d_mask,
                      h_pinned, curve, io.stream())) ||
         (rc = io.close()))
         return rc;
@@ -380,11 +376,10 @@ int jm_check(umi_ctx *ctx, const void *read_ref, const void *read_pos, const voi
              const void *out_molecules, const void *out_reads, const uint64_t *counts)
 {
     if (!counts) return fail(UMI_ERR_ARG, "counts is NULL");
-    if (n_buckets >= (1ull << 30))
-        return fail(UMI_ERR_ARG, "%llu buckets exceed the 30-bit index space of one call", (unsigned long long)n_buckets);
-    if (n_reads >= (1ull << 32)) return fail(UMI_ERR_ARG, "%llu reads exceed the 32-bit index space of one call", (unsigned long long)n_reads);
-    if (n_buckets && !bucket_off) return fail(UMI_ERR_ARG, "bucket_off is NULL");
-    if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
+    // (the reads' limit is told between the table's: after too many buckets, before a table that is missing)
+    if (n_buckets < (1ull << 30) && n_reads >= (1ull << 32))
+        return fail(UMI_ERR_ARG, "%llu reads exceed the 32-bit index space of one call", (unsigned long long)n_reads);
+    if (int rc = check_bucket_table(bucket_off, n_buckets)) return rc;
     if (n_buckets && bucket_off[n_buckets] && n_reads) {
         if (!col || !kept || !root) return fail(UMI_ERR_ARG, "a required pointer is NULL");
         if (!read_ref || !read_pos || !cigar || !cigar_off || !read_entry) return fail(UMI_ERR_ARG, "a required pointer is NULL");
@@ -397,31 +392,27 @@ int jm_check(umi_ctx *ctx, const void *read_ref, const void *read_pos, const voi
     return UMI_OK;
 }
 
-// the device made current, a deferred call let end, the table walked; *m == 0: nothing to do
-int jm_begin(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, uint64_t n_reads, uint32_t n_cols, uint32_t *m,
-             const uint64_t **h_off, const uint32_t **h_idx)
+// the table walked; t->m == 0: nothing to do
+int jm_begin(umi_ctx *ctx, const uint64_t *bucket_off, uint64_t n_buckets, uint64_t n_reads, uint32_t n_cols, BucketTable *t)
 {
     int rc;
-    *m = 0;
     if (n_buckets == 0 || n_reads == 0) return UMI_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
-    if ((rc = cm_walk(ctx, bucket_off, n_buckets, m, h_off, h_idx))) return rc;
-    if (*m && n_cols == 0) return fail(UMI_ERR_ARG, "a matrix of no columns with a non-empty bucket");
+    if ((rc = table_begin(ctx, bucket_off, n_buckets, t))) return rc;
+    if (t->m && n_cols == 0) return fail(UMI_ERR_ARG, "a matrix of no columns with a non-empty bucket");
     return UMI_OK;
 }
 
 int jm_run(umi_ctx *ctx, const int32_t *d_ref, const int32_t *d_pos, const uint32_t *d_cigar, const uint64_t *d_cigar_off,
-           const uint32_t *d_read_entry, uint64_t n_reads, const uint8_t *d_kept, const uint32_t *d_root, uint64_t n, uint32_t m,
-           const uint64_t *h_off, const uint32_t *h_idx, const uint32_t *d_col, uint32_t n_cols, uint64_t capacity, int32_t *d_jn_ref,
+           const uint32_t *d_read_entry, uint64_t n_reads, const uint8_t *d_kept, const uint32_t *d_root, uint64_t n,
+           const BucketTable &t, const uint32_t *d_col, uint32_t n_cols, uint64_t capacity, int32_t *d_jn_ref,
            int32_t *d_jn_start, int32_t *d_jn_end, uint32_t *d_out_jn, uint32_t *d_out_col, uint32_t *d_out_molecules,
            uint64_t *d_out_reads, uint64_t counts[4], hipStream_t s)
 {
     int rc;
-    if ((rc = ctx->call_ws.reserve(junction_count_workspace_bytes((uint32_t)n_reads, m, h_idx != nullptr)))) return rc;
+    if ((rc = ctx->call_ws.reserve(junction_count_workspace_bytes((uint32_t)n_reads, t.m, t.idx != nullptr)))) return rc;
     JunctionCounted got;
     int r = junction_count_on_device(ctx->call_ws.p, d_ref, d_pos, d_cigar, d_cigar_off, d_read_entry, (uint32_t)n_reads, d_kept, d_root, n,
-                                     h_off, h_idx, m, d_col, n_cols, &got, (uint32_t)ctx->n_cus, ctx->h_counters, s);
+                                     t.off, t.idx, t.m, d_col, n_cols, &got, (uint32_t)ctx->n_cus, ctx->h_counters, s);
     if (r < 0) return fail(UMI_ERR_HIP, "junction matrix: %s", hipGetErrorString((hipError_t)(-r)));
     const unsigned long long at = (unsigned long long)got.bad_read;
     switch (got.bad_kind) {
@@ -445,7 +436,7 @@ int jm_run(umi_ctx *ctx, const int32_t *d_ref, const int32_t *d_pos, const uint3
     if ((rc = ctx->jn_ws.reserve(junction_fill_workspace_bytes((uint32_t)got.occurrences)))) return rc;
     uint64_t junctions = 0, nnz = 0;
     r = junction_fill_on_device(ctx->call_ws.p, ctx->jn_ws.p, d_ref, d_pos, d_cigar, d_cigar_off, d_read_entry, (uint32_t)n_reads, d_kept,
-                                d_root, n, m, h_idx != nullptr, n_cols, got, d_jn_ref, d_jn_start, d_jn_end, d_out_jn, d_out_col,
+                                d_root, n, t.m, t.idx != nullptr, n_cols, got, d_jn_ref, d_jn_start, d_jn_end, d_out_jn, d_out_col,
                                 d_out_molecules, d_out_reads, &junctions, &nnz, (uint32_t)ctx->n_cus, ctx->h_counters, s);
     if (r < 0) return fail(UMI_ERR_HIP, "junction matrix: %s", hipGetErrorString((hipError_t)(-r)));
     counts[0] = got.spliced;
@@ -468,14 +459,12 @@ int umi_junction_matrix_device(umi_ctx *ctx, const int32_t *d_read_ref, const in
     int rc = jm_check(ctx, d_read_ref, d_read_pos, d_cigar, d_cigar_off, d_read_entry, n_reads, d_kept, d_root, bucket_off, n_buckets,
                       d_col, d_jn_ref, d_jn_start, d_jn_end, d_out_jn, d_out_col, d_out_molecules, d_out_reads, counts);
     if (rc) return rc;
-    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_count_matrix)
+    ctx = first_device(ctx);
     counts[0] = counts[1] = counts[2] = counts[3] = 0;
-    uint32_t m = 0;
-    const uint64_t *h_off = nullptr;
-    const uint32_t *h_idx = nullptr;
-    if ((rc = jm_begin(ctx, bucket_off, n_buckets, n_reads, n_cols, &m, &h_off, &h_idx)) || m == 0) return rc;
-    return jm_run(ctx, d_read_ref, d_read_pos, d_cigar, d_cigar_off, d_read_entry, n_reads, d_kept, d_root, bucket_off[n_buckets], m,
-                  h_off, h_idx, d_col, n_cols, capacity, d_jn_ref, d_jn_start, d_jn_end, d_out_jn, d_out_col, d_out_molecules,
+    BucketTable t;
+    if ((rc = jm_begin(ctx, bucket_off, n_buckets, n_reads, n_cols, &t)) || t.m == 0) return rc;
+    return jm_run(ctx, d_read_ref, d_read_pos, d_cigar, d_cigar_off, d_read_entry, n_reads, d_kept, d_root, bucket_off[n_buckets], t,
+                  d_col, n_cols, capacity, d_jn_ref, d_jn_start, d_jn_end, d_out_jn, d_out_col, d_out_molecules,
                   d_out_reads, counts, (hipStream_t)hip_stream);
 }
 
@@ -488,12 +477,10 @@ int umi_junction_matrix(umi_ctx *ctx, const int32_t *read_ref, const int32_t *re
     int rc = jm_check(ctx, read_ref, read_pos, cigar, cigar_off, read_entry, n_reads, kept, root, bucket_off, n_buckets, col, jn_ref,
                       jn_start, jn_end, out_jn, out_col, out_molecules, out_reads, counts);
     if (rc) return rc;
-    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    ctx = first_device(ctx);
     counts[0] = counts[1] = counts[2] = counts[3] = 0;
-    uint32_t m = 0;
-    const uint64_t *h_off = nullptr;
-    const uint32_t *h_idx = nullptr;
-    if ((rc = jm_begin(ctx, bucket_off, n_buckets, n_reads, n_cols, &m, &h_off, &h_idx)) || m == 0) return rc;
+    BucketTable t;
+    if ((rc = jm_begin(ctx, bucket_off, n_buckets, n_reads, n_cols, &t)) || t.m == 0) return rc;
     const size_t n = (size_t)bucket_off[n_buckets], nb = (size_t)n_buckets, nr = (size_t)n_reads;
     const size_t cap = (size_t)std::min<uint64_t>(capacity, (1ull << 30) - 1), words = (size_t)cigar_off[n_reads];
     HostIo io(ctx);
@@ -509,7 +496,7 @@ int umi_junction_matrix(umi_ctx *ctx, const int32_t *read_ref, const int32_t *re
     const auto d_kept = io.in(kept, n);
     uint64_t got[4] = {0, 0, 0, 0};
     if ((rc = io.open()) ||
-        (rc = jm_run(ctx, d_ref, d_pos, d_cigar, d_off, d_entry, n_reads, d_kept, d_root, n, m, h_off, h_idx, d_col, n_cols, capacity,
+        (rc = jm_run(ctx, d_ref, d_pos, d_cigar, d_off, d_entry, n_reads, d_kept, d_root, n, t, d_col, n_cols, capacity,
                      d_jref, d_jstart, d_jend, d_ojn, d_ocol, d_omol, d_oreads, got, io.stream()))) {
         counts[1] = got[1]; // (the occurrences a larger capacity has to hold)
         return rc;
@@ -536,10 +523,7 @@ int mg_check(umi_ctx *ctx, const void *keys, int n_words, int umi_len, const voi
     if (umi_len < 1 || umi_len > UMI_MAX_WIDE_UMI_LEN)
         return fail(UMI_ERR_ARG, "umi_len %d outside 1..%d", umi_len, UMI_MAX_WIDE_UMI_LEN);
     if (n_words != wide_words(umi_len)) return fail(UMI_ERR_ARG, "n_words must be %d for umi_len %d", wide_words(umi_len), umi_len);
-    if (n_buckets >= (1ull << 30))
-        return fail(UMI_ERR_ARG, "%llu buckets exceed the 30-bit index space of one call", (unsigned long long)n_buckets);
-    if (n_buckets && !bucket_off) return fail(UMI_ERR_ARG, "bucket_off is NULL");
-    if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
+    if (int rc = check_bucket_table(bucket_off, n_buckets)) return rc;
     const uint64_t n = n_buckets ? bucket_off[n_buckets] : 0; // (a table that falls: cm_walk's finding, on its one walk)
     if (n >= (1ull << 30)) return fail(UMI_ERR_ARG, "%llu entries exceed the 30-bit index space of the call's sort", (unsigned long long)n);
     if (n && (!keys || !freq || !kept || !root || !group || !kept_out)) return fail(UMI_ERR_ARG, "a required pointer is NULL");
@@ -550,7 +534,7 @@ int mg_check(umi_ctx *ctx, const void *keys, int n_words, int umi_len, const voi
 
 // everything on the device (the context is the call's device, settled)
 int mg_run(umi_ctx *ctx, const uint64_t *d_keys, int n_words, int umi_len, const int32_t *d_freq, const uint8_t *d_kept,
-           const uint32_t *d_root, uint32_t m, const uint64_t *h_off, const uint32_t *h_idx, const uint32_t *d_group,
+           const uint32_t *d_root, const BucketTable &t, const uint32_t *d_group,
            uint32_t n_groups, uint8_t *d_kept_out, int32_t *d_freq_out, uint64_t counts[3], hipStream_t s)
 {
     int rc;
@@ -560,10 +544,10 @@ int mg_run(umi_ctx *ctx, const uint64_t *d_keys, int n_words, int umi_len, const
     c.d_kept = d_kept;
     c.d_root = d_root;
     c.d_group = d_group;
-    c.h_off = h_off;
-    c.h_idx = h_idx;
-    c.n = (uint32_t)h_off[m];
-    c.m = m;
+    c.h_off = t.off;
+    c.h_idx = t.idx;
+    c.n = (uint32_t)t.off[t.m];
+    c.m = t.m;
     c.n_groups = n_groups;
     c.n_cus = (uint32_t)ctx->n_cus;
     c.umi_len = umi_len;
@@ -571,7 +555,7 @@ int mg_run(umi_ctx *ctx, const uint64_t *d_keys, int n_words, int umi_len, const
     c.d_kept_out = d_kept_out;
     c.d_freq_out = d_freq_out;
     c.h_pinned = ctx->h_counters;
-    if ((rc = ctx->call_ws.reserve(multigene_workspace_bytes(c.n, m, h_idx != nullptr)))) return rc;
+    if ((rc = ctx->call_ws.reserve(multigene_workspace_bytes(c.n, t.m, t.idx != nullptr)))) return rc;
     const int r = multigene_on_device(ctx->call_ws.p, c, s);
     if (r < 0) return fail(UMI_ERR_HIP, "multi-gene filter: %s", hipGetErrorString((hipError_t)(-r)));
     if (ctx->h_counters[0])
@@ -593,18 +577,14 @@ int umi_filter_multigene_device(umi_ctx *ctx, const uint64_t *d_keys, int n_word
 {
     int rc = mg_check(ctx, d_keys, n_words, umi_len, d_freq, d_kept, d_root, bucket_off, n_buckets, d_group, d_kept_out, d_freq_out, counts);
     if (rc) return rc;
-    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_count_matrix)
+    ctx = first_device(ctx);
     counts[0] = counts[1] = counts[2] = 0;
     if (n_buckets == 0 || bucket_off[n_buckets] == 0) return UMI_OK;
     if (n_groups == 0) return fail(UMI_ERR_ARG, "no groups with a non-empty bucket");
-    HIP_TRY(hipSetDevice(ctx->device));
-    settle(ctx); // (a deferred call's counters lie in the pinned block this call reads through)
-    uint32_t m = 0;
-    const uint64_t *h_off = nullptr;
-    const uint32_t *h_idx = nullptr;
-    if ((rc = cm_walk(ctx, bucket_off, n_buckets, &m, &h_off, &h_idx))) return rc;
-    return mg_run(ctx, d_keys, n_words, umi_len, d_freq, d_kept, d_root, m, h_off, h_idx, d_group, n_groups, d_kept_out, d_freq_out,
-                  counts, (hipStream_t)hip_stream);
+    BucketTable t;
+    if ((rc = table_begin(ctx, bucket_off, n_buckets, &t))) return rc;
+    return mg_run(ctx, d_keys, n_words, umi_len, d_freq, d_kept, d_root, t, d_group, n_groups, d_kept_out, d_freq_out, counts,
+                  (hipStream_t)hip_stream);
 }
 
 int umi_filter_multigene(umi_ctx *ctx, const uint64_t *keys, int n_words, int umi_len, const int32_t *freq, const uint8_t *kept,
@@ -613,16 +593,12 @@ int umi_filter_multigene(umi_ctx *ctx, const uint64_t *keys, int n_words, int um
 {
     int rc = mg_check(ctx, keys, n_words, umi_len, freq, kept, root, bucket_off, n_buckets, group, kept_out, freq_out, counts);
     if (rc) return rc;
-    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    ctx = first_device(ctx);
     counts[0] = counts[1] = counts[2] = 0;
     if (n_buckets == 0 || bucket_off[n_buckets] == 0) return UMI_OK;
     if (n_groups == 0) return fail(UMI_ERR_ARG, "no groups with a non-empty bucket");
-    HIP_TRY(hipSetDevice(ctx->device));
-    settle(ctx);
-    uint32_t m = 0;
-    const uint64_t *h_off = nullptr;
-    const uint32_t *h_idx = nullptr;
-    if ((rc = cm_walk(ctx, bucket_off, n_buckets, &m, &h_off, &h_idx))) return rc; // (before anything is copied)
+    BucketTable t;
+    if ((rc = table_begin(ctx, bucket_off, n_buckets, &t))) return rc; // (before anything is copied)
     const size_t n = (size_t)bucket_off[n_buckets], nb = (size_t)n_buckets;
     HostIo io(ctx);
     const auto d_keys = io.in(keys, n * 8 * (size_t)n_words);
@@ -633,8 +609,7 @@ int umi_filter_multigene(umi_ctx *ctx, const uint64_t *keys, int n_words, int um
     const auto d_kept = io.in(kept, n);
     const auto d_kout = io.out(kept_out, n);
     if ((rc = io.open()) ||
-        (rc = mg_run(ctx, d_keys, n_words, umi_len, d_freq, d_kept, d_root, m, h_off, h_idx, d_group, n_groups, d_kout, d_fout, counts,
-                     io.stream())) ||
+        (rc = mg_run(ctx, d_keys, n_words, umi_len, d_freq, d_kept, d_root, t, d_group, n_groups, d_kout, d_fout, counts, io.stream())) ||
         (rc = io.fetch(kept_out, d_kout, n)) || (rc = io.fetch(freq_out, d_fout, n)) || (rc = io.close()))
         return rc;
     return UMI_OK;
@@ -664,8 +639,8 @@ int ds_check(umi_ctx *ctx, const void *keys, int n_words, const void *freq, cons
         return fail(UMI_ERR_ARG, "umi_len %d outside 1..%d", umi_len, UMI_MAX_WIDE_UMI_LEN);
     if (n_words != (3 * umi_len + 63) / 64) return fail(UMI_ERR_ARG, "n_words must be %d for umi_len %d", (3 * umi_len + 63) / 64, umi_len);
     if (hist_bins < 2 || hist_bins > (1u << 24)) return fail(UMI_ERR_ARG, "hist_bins %u outside 2..2^24", hist_bins);
-    if (n_buckets && !bucket_off) return fail(UMI_ERR_ARG, "bucket_off is NULL");
-    if (n_buckets && bucket_off[0] != 0) return fail(UMI_ERR_ARG, "bucket_off[0] must be 0");
+    // (any number of buckets: it is the entries that are limited, below)
+    if (int rc = check_bucket_table(bucket_off, n_buckets, false)) return rc;
     uint64_t m = 0;
     for (uint64_t b = 0; b < n_buckets; b++) {
         const uint64_t lo = bucket_off[b], hi = bucket_off[b + 1];
@@ -758,7 +733,7 @@ int umi_dedup_stats_device(umi_ctx *ctx, const uint64_t *d_keys, int n_words, co
     int rc = ds_check(ctx, d_keys, n_words, d_freq, d_kept, d_root, bucket_off, n_buckets, umi_len, hist_bins, d_count_pre,
                       d_count_post, d_dist, d_umi_entry, d_times_pre, d_reads_pre, d_times_post, d_reads_post, n_umis, &shape);
     if (rc) return rc;
-    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_count_matrix)
+    ctx = first_device(ctx);
     if (n_umis) *n_umis = 0;
     hipStream_t s = (hipStream_t)hip_stream;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -787,7 +762,7 @@ int umi_dedup_stats(umi_ctx *ctx, const uint64_t *keys, int n_words, const int32
     int rc = ds_check(ctx, keys, n_words, freq, kept, root, bucket_off, n_buckets, umi_len, hist_bins, count_pre, count_post, dist,
                       umi_entry, times_pre, reads_pre, times_post, reads_post, n_umis, &shape);
     if (rc) return rc;
-    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    ctx = first_device(ctx);
     if (n_umis) *n_umis = 0;
     const size_t dist_words = 4 * ((size_t)umi_len + 2);
     if (shape.m == 0) { // (nothing is launched)
@@ -919,7 +894,7 @@ int umi_call_cells_device(umi_ctx *ctx, const uint32_t *d_row, const uint32_t *d
                       min_molecules, d_cell_molecules, d_cell_reads, d_cell_genes, d_called, d_new_col, d_out_row, d_out_col,
                       d_out_molecules, d_out_reads, nnz_out, counts, &ra);
     if (rc) return rc;
-    if (!ctx->subs.empty()) ctx = ctx->subs[0]; // (the first device of a multi-device context, as umi_count_matrix)
+    ctx = first_device(ctx);
     *nnz_out = 0;
     for (int i = 0; i < 10; i++) counts[i] = 0;
     hipStream_t s = (hipStream_t)hip_stream;
@@ -950,7 +925,7 @@ int umi_call_cells(umi_ctx *ctx, const uint32_t *row, const uint32_t *col, const
                       min_molecules, cell_molecules, cell_reads, cell_genes, called, new_col, out_row, out_col, out_molecules, out_reads,
                       nnz_out, counts, &ra);
     if (rc) return rc;
-    if (!ctx->subs.empty()) ctx = ctx->subs[0];
+    ctx = first_device(ctx);
     *nnz_out = 0;
     for (int i = 0; i < 10; i++) counts[i] = 0;
     const size_t nc = (size_t)n_cols, nz = (size_t)nnz;

@@ -21,6 +21,7 @@
 #include "../../include/umihip.h"
 #include "umihip_gene_index.hpp"
 #include "umihip_internal.h"
+#include "umihip_pair_table.h"
 
 namespace umihip {
 
@@ -31,20 +32,12 @@ static_assert(GENE_CLASS_NONE == UMI_READ_CLASS_NONE && GENE_CLASS_EXONIC == UMI
 
 namespace {
 
-#define GENE_TRY(expr)                           \
-    do {                                         \
-        const hipError_t e__ = (expr);           \
-        if (e__ != hipSuccess) return -(int)e__; \
-    } while (0)
-
 enum ClassCtl : int {
     CLASS_BAD_ARG = 0,   // smallest read with read_ref < 0 or a bad op code (all ones: none)
     CLASS_BAD_ORDER = 1, // smallest read whose cigar_off falls (all ones: none)
     CLASS_COUNT0 = 2,    // seven words: reads assigned by an exon, by an intron, none, several; exonic, junction, spanning
     CLASS_CTL_COUNT = 9,
 };
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct ClassDevTable {
     GeneView view;
@@ -156,10 +149,10 @@ int upload(const GeneTable &h, char *&p, ClassDevTable &d, hipStream_t s)
     uint64_t *d_top = (uint64_t *)p;
     p += align256(h.top.size() * 8 + 8);
     if (n) {
-        GENE_TRY(hipMemcpyAsync(d_start, h.start.data(), n * 8, hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(d_end, h.end.data(), n * 8, hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(d_seg, h.seg.data(), n * sizeof(GeneSeg), hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(d_top, h.top.data(), h.top.size() * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(d_start, h.start.data(), n * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(d_end, h.end.data(), n * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(d_seg, h.seg.data(), n * sizeof(GeneSeg), hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(d_top, h.top.data(), h.top.size() * 8, hipMemcpyHostToDevice, s));
     }
     d = {{d_start, d_end, d_seg, (uint32_t)n}, d_top, (uint32_t)h.top.size(), h.top_shift, nullptr, {nullptr, nullptr, nullptr}};
     return 0;
@@ -179,12 +172,12 @@ int upload_cover(const GeneCover &c, char *&p, ClassDevTable &d, hipStream_t s)
     p += align256(m * 8 + 8);
     uint32_t *d_off = (uint32_t *)p;
     p += align256(o.off.size() * 4 + 8);
-    GENE_TRY(hipMemcpyAsync(d_cum, cum.data(), cum.size() * 8, hipMemcpyHostToDevice, s));
+    UMIHIP_TRY_NEG(hipMemcpyAsync(d_cum, cum.data(), cum.size() * 8, hipMemcpyHostToDevice, s));
     if (m) {
-        GENE_TRY(hipMemcpyAsync(d_start, o.start.data(), m * 8, hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(d_end, o.end.data(), m * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(d_start, o.start.data(), m * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(d_end, o.end.data(), m * 8, hipMemcpyHostToDevice, s));
     }
-    GENE_TRY(hipMemcpyAsync(d_off, o.off.data(), o.off.size() * 4, hipMemcpyHostToDevice, s));
+    UMIHIP_TRY_NEG(hipMemcpyAsync(d_off, o.off.data(), o.off.size() * 4, hipMemcpyHostToDevice, s));
     d.cum = d_cum;
     d.own = {d_start, d_end, d_off};
     return 0;
@@ -206,8 +199,8 @@ int gene_classes_on_device(void *workspace, const GeneTable *exons, const GeneTa
                            uint64_t class_counts[5], uint64_t *bad, uint32_t n_cus, unsigned long long *h_pinned, hipStream_t s)
 {
     unsigned long long *ctl = (unsigned long long *)workspace;
-    GENE_TRY(hipMemsetAsync(ctl, 0xFF, CLASS_COUNT0 * 8, s));
-    GENE_TRY(hipMemsetAsync(ctl + CLASS_COUNT0, 0, 7 * 8, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(ctl, 0xFF, CLASS_COUNT0 * 8, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(ctl + CLASS_COUNT0, 0, 7 * 8, s));
     ClassDevTable dev_exon[2], dev_body[2];
     char *p = (char *)workspace + 256;
     for (int t = 0; t < n_tables; t++) {
@@ -244,9 +237,9 @@ int gene_classes_on_device(void *workspace, const GeneTable *exons, const GeneTa
         gene_classes_kernel<true, false><<<grid, GENE_THREADS, 0, s>>>(a);
     else
         gene_classes_kernel<false, false><<<grid, GENE_THREADS, 0, s>>>(a);
-    GENE_TRY(hipGetLastError());
-    GENE_TRY(hipMemcpyAsync(h_pinned, ctl, CLASS_CTL_COUNT * 8, hipMemcpyDeviceToHost, s));
-    GENE_TRY(hipStreamSynchronize(s));
+    UMIHIP_TRY_NEG(hipGetLastError());
+    UMIHIP_TRY_NEG(hipMemcpyAsync(h_pinned, ctl, CLASS_CTL_COUNT * 8, hipMemcpyDeviceToHost, s));
+    UMIHIP_TRY_NEG(hipStreamSynchronize(s));
     if (h_pinned[CLASS_BAD_ORDER] != ~0ull && h_pinned[CLASS_BAD_ORDER] <= h_pinned[CLASS_BAD_ARG]) {
         *bad = h_pinned[CLASS_BAD_ORDER];
         return 2;
@@ -263,7 +256,5 @@ int gene_classes_on_device(void *workspace, const GeneTable *exons, const GeneTa
     class_counts[GENE_CLASS_INTRONIC] = counts[1];
     return 0;
 }
-
-#undef GENE_TRY
 
 } // namespace umihip

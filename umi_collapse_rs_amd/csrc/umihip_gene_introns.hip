@@ -21,6 +21,7 @@
 #include "../../include/umihip.h"
 #include "umihip_gene_index.hpp"
 #include "umihip_internal.h"
+#include "umihip_pair_table.h"
 
 namespace umihip {
 
@@ -32,20 +33,12 @@ static_assert((2 * (size_t)GENE_TOP_CAP + 2 * (size_t)GENE_BODY_TOP_CAP) * 8 * G
 
 namespace {
 
-#define GENE_TRY(expr)                           \
-    do {                                         \
-        const hipError_t e__ = (expr);           \
-        if (e__ != hipSuccess) return -(int)e__; \
-    } while (0)
-
 enum IntronCtl : int {
     INTRON_BAD_ARG = 0,   // smallest read with read_ref < 0 or a bad op code (all ones: none)
     INTRON_BAD_ORDER = 1, // smallest read whose cigar_off falls (all ones: none)
     INTRON_COUNT0 = 2,    // four words: reads assigned by an exon, by an intron, none, several
     INTRON_CTL_COUNT = 6,
 };
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct IntronDevTable {
     GeneView view;
@@ -140,10 +133,10 @@ int upload(const GeneTable &h, char *&p, IntronDevTable &d, hipStream_t s)
     uint64_t *d_top = (uint64_t *)p;
     p += align256(h.top.size() * 8 + 8);
     if (n) {
-        GENE_TRY(hipMemcpyAsync(d_start, h.start.data(), n * 8, hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(d_end, h.end.data(), n * 8, hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(d_seg, h.seg.data(), n * sizeof(GeneSeg), hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(d_top, h.top.data(), h.top.size() * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(d_start, h.start.data(), n * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(d_end, h.end.data(), n * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(d_seg, h.seg.data(), n * sizeof(GeneSeg), hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(d_top, h.top.data(), h.top.size() * 8, hipMemcpyHostToDevice, s));
     }
     d = {{d_start, d_end, d_seg, (uint32_t)n}, d_top, (uint32_t)h.top.size(), h.top_shift};
     return 0;
@@ -165,8 +158,8 @@ int gene_introns_on_device(void *workspace, const GeneTable *exons, const GeneTa
                            hipStream_t s)
 {
     unsigned long long *ctl = (unsigned long long *)workspace;
-    GENE_TRY(hipMemsetAsync(ctl, 0xFF, INTRON_COUNT0 * 8, s));
-    GENE_TRY(hipMemsetAsync(ctl + INTRON_COUNT0, 0, 4 * 8, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(ctl, 0xFF, INTRON_COUNT0 * 8, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(ctl + INTRON_COUNT0, 0, 4 * 8, s));
     IntronDevTable dev_exon[2], dev_body[2];
     char *p = (char *)workspace + 256;
     for (int t = 0; t < n_tables; t++) {
@@ -200,9 +193,9 @@ int gene_introns_on_device(void *workspace, const GeneTable *exons, const GeneTa
         gene_introns_kernel<true, false><<<grid, GENE_THREADS, 0, s>>>(a);
     else
         gene_introns_kernel<false, false><<<grid, GENE_THREADS, 0, s>>>(a);
-    GENE_TRY(hipGetLastError());
-    GENE_TRY(hipMemcpyAsync(h_pinned, ctl, INTRON_CTL_COUNT * 8, hipMemcpyDeviceToHost, s));
-    GENE_TRY(hipStreamSynchronize(s));
+    UMIHIP_TRY_NEG(hipGetLastError());
+    UMIHIP_TRY_NEG(hipMemcpyAsync(h_pinned, ctl, INTRON_CTL_COUNT * 8, hipMemcpyDeviceToHost, s));
+    UMIHIP_TRY_NEG(hipStreamSynchronize(s));
     if (h_pinned[INTRON_BAD_ORDER] != ~0ull && h_pinned[INTRON_BAD_ORDER] <= h_pinned[INTRON_BAD_ARG]) {
         *bad = h_pinned[INTRON_BAD_ORDER];
         return 2;
@@ -214,7 +207,5 @@ int gene_introns_on_device(void *workspace, const GeneTable *exons, const GeneTa
     for (int c = 0; c < 4; c++) counts[c] = h_pinned[INTRON_COUNT0 + c];
     return 0;
 }
-
-#undef GENE_TRY
 
 } // namespace umihip

@@ -32,6 +32,7 @@
 
 #include "../../include/umihip.h"
 #include "umihip_internal.h"
+#include "umihip_pair_table.h"
 #include "umihip_transcript_index.hpp"
 
 namespace umihip {
@@ -43,12 +44,6 @@ static_assert(2 * (size_t)GENE_TOP_CAP * 8 * GENE_BLOCKS_PER_CU <= 160 * 1024, "
 
 namespace {
 
-#define GENE_TRY(expr)                           \
-    do {                                         \
-        const hipError_t e__ = (expr);           \
-        if (e__ != hipSuccess) return -(int)e__; \
-    } while (0)
-
 enum TcCtl : int {
     TC_BAD_ARG = 0,   // smallest read with read_ref < 0 or a bad op code (all ones: none)
     TC_BAD_ORDER = 1, // smallest read whose cigar_off falls (all ones: none)
@@ -56,8 +51,6 @@ enum TcCtl : int {
     TC_CTL_COUNT = 9, // (what the host reads)
     TC_QUEUE_N = 9,   // the reads queued for the second pass
 };
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct TcTrTable {
     TranscriptView view;
@@ -261,15 +254,15 @@ int upload_transcripts(const TranscriptTable &h, char *&p, TcTrTable &d, hipStre
     const size_t ni = h.x.size(), nd = h.start.size();
     char *base = p;
     if (nd) {
-        GENE_TRY(hipMemcpyAsync(base + l.x, h.x.data(), ni * sizeof(TrExon), hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(base + l.of, h.of.data(), ni * sizeof(TrOf), hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(base + l.start, h.start.data(), nd * 8, hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(base + l.end, h.end.data(), nd * 8, hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(base + l.dmax, h.dmax.data(), nd * 8, hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(base + l.label, h.label.data(), nd * 4, hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(base + l.off, h.off.data(), (nd + 1) * 4, hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(base + l.inst, h.inst.data(), ni * 4, hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(base + l.top, h.top.data(), h.top.size() * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.x, h.x.data(), ni * sizeof(TrExon), hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.of, h.of.data(), ni * sizeof(TrOf), hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.start, h.start.data(), nd * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.end, h.end.data(), nd * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.dmax, h.dmax.data(), nd * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.label, h.label.data(), nd * 4, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.off, h.off.data(), (nd + 1) * 4, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.inst, h.inst.data(), ni * 4, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.top, h.top.data(), h.top.size() * 8, hipMemcpyHostToDevice, s));
     }
     d = {{(const TrExon *)(base + l.x), (const TrOf *)(base + l.of), (const uint64_t *)(base + l.start), (const uint64_t *)(base + l.end),
           (const uint64_t *)(base + l.dmax), (const int32_t *)(base + l.label), (const uint32_t *)(base + l.off),
@@ -306,10 +299,10 @@ int upload_table(const GeneTable &h, char *&p, TcBodyTable &d, hipStream_t s)
     uint64_t *d_top = (uint64_t *)p;
     p += align256(h.top.size() * 8 + 8);
     if (n) {
-        GENE_TRY(hipMemcpyAsync(d_start, h.start.data(), n * 8, hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(d_end, h.end.data(), n * 8, hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(d_seg, h.seg.data(), n * sizeof(GeneSeg), hipMemcpyHostToDevice, s));
-        if (!h.top.empty()) GENE_TRY(hipMemcpyAsync(d_top, h.top.data(), h.top.size() * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(d_start, h.start.data(), n * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(d_end, h.end.data(), n * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(d_seg, h.seg.data(), n * sizeof(GeneSeg), hipMemcpyHostToDevice, s));
+        if (!h.top.empty()) UMIHIP_TRY_NEG(hipMemcpyAsync(d_top, h.top.data(), h.top.size() * 8, hipMemcpyHostToDevice, s));
     }
     d = {{d_start, d_end, d_seg, (uint32_t)n}, d_top, (uint32_t)h.top.size(), h.top_shift};
     return 0;
@@ -329,12 +322,12 @@ int upload_cover(const GeneCover &c, char *&p, TrCoverView &d, hipStream_t s)
     p += align256(m * 8 + 8);
     uint32_t *d_off = (uint32_t *)p;
     p += align256(o.off.size() * 4 + 8);
-    if (!cum.empty()) GENE_TRY(hipMemcpyAsync(d_cum, cum.data(), cum.size() * 8, hipMemcpyHostToDevice, s));
+    if (!cum.empty()) UMIHIP_TRY_NEG(hipMemcpyAsync(d_cum, cum.data(), cum.size() * 8, hipMemcpyHostToDevice, s));
     if (m) {
-        GENE_TRY(hipMemcpyAsync(d_start, o.start.data(), m * 8, hipMemcpyHostToDevice, s));
-        GENE_TRY(hipMemcpyAsync(d_end, o.end.data(), m * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(d_start, o.start.data(), m * 8, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(d_end, o.end.data(), m * 8, hipMemcpyHostToDevice, s));
     }
-    if (!o.off.empty()) GENE_TRY(hipMemcpyAsync(d_off, o.off.data(), o.off.size() * 4, hipMemcpyHostToDevice, s));
+    if (!o.off.empty()) UMIHIP_TRY_NEG(hipMemcpyAsync(d_off, o.off.data(), o.off.size() * 4, hipMemcpyHostToDevice, s));
     d.cum = d_cum;
     d.own = {d_start, d_end, d_off};
     return 0;
@@ -375,8 +368,8 @@ int gene_transcript_classes_on_device(void *workspace, const TranscriptTable *tr
 {
     const bool classes = cover != nullptr;
     unsigned long long *ctl = (unsigned long long *)workspace;
-    GENE_TRY(hipMemsetAsync(ctl, 0xFF, TC_COUNT0 * 8, s));
-    GENE_TRY(hipMemsetAsync(ctl + TC_COUNT0, 0, 8 * 8, s)); // (the counts and the queue's length)
+    UMIHIP_TRY_NEG(hipMemsetAsync(ctl, 0xFF, TC_COUNT0 * 8, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(ctl + TC_COUNT0, 0, 8 * 8, s)); // (the counts and the queue's length)
     TcTrTable dev_tr[2];
     TcBodyTable dev_body[2], dev_exon[2];
     TrCoverView dev_cover[2];
@@ -422,9 +415,9 @@ int gene_transcript_classes_on_device(void *workspace, const TranscriptTable *tr
         launch<true>(use_top, use_body_top, mode != GENE_INTRONS_OFF, grid, a, s);
     else
         launch<false>(use_top, use_body_top, mode != GENE_INTRONS_OFF, grid, a, s);
-    GENE_TRY(hipGetLastError());
-    GENE_TRY(hipMemcpyAsync(h_pinned, ctl, TC_CTL_COUNT * 8, hipMemcpyDeviceToHost, s));
-    GENE_TRY(hipStreamSynchronize(s));
+    UMIHIP_TRY_NEG(hipGetLastError());
+    UMIHIP_TRY_NEG(hipMemcpyAsync(h_pinned, ctl, TC_CTL_COUNT * 8, hipMemcpyDeviceToHost, s));
+    UMIHIP_TRY_NEG(hipStreamSynchronize(s));
     if (h_pinned[TC_BAD_ORDER] != ~0ull && h_pinned[TC_BAD_ORDER] <= h_pinned[TC_BAD_ARG]) {
         *bad = h_pinned[TC_BAD_ORDER];
         return 2;
@@ -444,7 +437,5 @@ int gene_transcript_classes_on_device(void *workspace, const TranscriptTable *tr
     }
     return 0;
 }
-
-#undef GENE_TRY
 
 } // namespace umihip

@@ -24,6 +24,7 @@
 
 #include "../../include/umihip.h"
 #include "umihip_internal.h"
+#include "umihip_pair_table.h"
 #include "umihip_transcript_index.hpp"
 
 namespace umihip {
@@ -34,20 +35,12 @@ static_assert(2 * (size_t)GENE_TOP_CAP * 8 * GENE_BLOCKS_PER_CU <= 160 * 1024, "
 
 namespace {
 
-#define GENE_TRY(expr)                           \
-    do {                                         \
-        const hipError_t e__ = (expr);           \
-        if (e__ != hipSuccess) return -(int)e__; \
-    } while (0)
-
 enum TrCtl : int {
     TR_CTL_BAD_ARG = 0,   // smallest read with read_ref < 0 or a bad op code (all ones: none)
     TR_CTL_BAD_ORDER = 1, // smallest read whose cigar_off falls (all ones: none)
     TR_CTL_STATUS0 = 2,   // three words: reads assigned, none, several
     TR_CTL_COUNT = 5,
 };
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct TrDevTable {
     TranscriptView view;
@@ -151,8 +144,8 @@ int gene_transcripts_on_device(void *workspace, const TranscriptTable *tables, i
                                unsigned long long *h_pinned, hipStream_t s)
 {
     unsigned long long *ctl = (unsigned long long *)workspace;
-    GENE_TRY(hipMemsetAsync(ctl, 0xFF, TR_CTL_STATUS0 * 8, s));
-    GENE_TRY(hipMemsetAsync(ctl + TR_CTL_STATUS0, 0, 3 * 8, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(ctl, 0xFF, TR_CTL_STATUS0 * 8, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(ctl + TR_CTL_STATUS0, 0, 3 * 8, s));
     TrDevTable dev[2];
     char *base = (char *)workspace + 256;
     for (int t = 0; t < n_tables; t++) {
@@ -160,15 +153,15 @@ int gene_transcripts_on_device(void *workspace, const TranscriptTable *tables, i
         const TrLayout l = layout_of(h);
         const size_t ni = h.x.size(), nd = h.start.size();
         if (nd) {
-            GENE_TRY(hipMemcpyAsync(base + l.x, h.x.data(), ni * sizeof(TrExon), hipMemcpyHostToDevice, s));
-            GENE_TRY(hipMemcpyAsync(base + l.of, h.of.data(), ni * sizeof(TrOf), hipMemcpyHostToDevice, s));
-            GENE_TRY(hipMemcpyAsync(base + l.start, h.start.data(), nd * 8, hipMemcpyHostToDevice, s));
-            GENE_TRY(hipMemcpyAsync(base + l.end, h.end.data(), nd * 8, hipMemcpyHostToDevice, s));
-            GENE_TRY(hipMemcpyAsync(base + l.dmax, h.dmax.data(), nd * 8, hipMemcpyHostToDevice, s));
-            GENE_TRY(hipMemcpyAsync(base + l.label, h.label.data(), nd * 4, hipMemcpyHostToDevice, s));
-            GENE_TRY(hipMemcpyAsync(base + l.off, h.off.data(), (nd + 1) * 4, hipMemcpyHostToDevice, s));
-            GENE_TRY(hipMemcpyAsync(base + l.inst, h.inst.data(), ni * 4, hipMemcpyHostToDevice, s));
-            GENE_TRY(hipMemcpyAsync(base + l.top, h.top.data(), h.top.size() * 8, hipMemcpyHostToDevice, s));
+            UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.x, h.x.data(), ni * sizeof(TrExon), hipMemcpyHostToDevice, s));
+            UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.of, h.of.data(), ni * sizeof(TrOf), hipMemcpyHostToDevice, s));
+            UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.start, h.start.data(), nd * 8, hipMemcpyHostToDevice, s));
+            UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.end, h.end.data(), nd * 8, hipMemcpyHostToDevice, s));
+            UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.dmax, h.dmax.data(), nd * 8, hipMemcpyHostToDevice, s));
+            UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.label, h.label.data(), nd * 4, hipMemcpyHostToDevice, s));
+            UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.off, h.off.data(), (nd + 1) * 4, hipMemcpyHostToDevice, s));
+            UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.inst, h.inst.data(), ni * 4, hipMemcpyHostToDevice, s));
+            UMIHIP_TRY_NEG(hipMemcpyAsync(base + l.top, h.top.data(), h.top.size() * 8, hipMemcpyHostToDevice, s));
         }
         dev[t] = {{(const TrExon *)(base + l.x), (const TrOf *)(base + l.of), (const uint64_t *)(base + l.start),
                    (const uint64_t *)(base + l.end), (const uint64_t *)(base + l.dmax), (const int32_t *)(base + l.label),
@@ -198,9 +191,9 @@ int gene_transcripts_on_device(void *workspace, const TranscriptTable *tables, i
         gene_transcripts_kernel<true><<<grid, GENE_THREADS, 0, s>>>(a);
     else
         gene_transcripts_kernel<false><<<grid, GENE_THREADS, 0, s>>>(a);
-    GENE_TRY(hipGetLastError());
-    GENE_TRY(hipMemcpyAsync(h_pinned, ctl, TR_CTL_COUNT * 8, hipMemcpyDeviceToHost, s));
-    GENE_TRY(hipStreamSynchronize(s));
+    UMIHIP_TRY_NEG(hipGetLastError());
+    UMIHIP_TRY_NEG(hipMemcpyAsync(h_pinned, ctl, TR_CTL_COUNT * 8, hipMemcpyDeviceToHost, s));
+    UMIHIP_TRY_NEG(hipStreamSynchronize(s));
     if (h_pinned[TR_CTL_BAD_ORDER] != ~0ull && h_pinned[TR_CTL_BAD_ORDER] <= h_pinned[TR_CTL_BAD_ARG]) {
         *bad = h_pinned[TR_CTL_BAD_ORDER];
         return 2;
@@ -212,7 +205,5 @@ int gene_transcripts_on_device(void *workspace, const TranscriptTable *tables, i
     for (int c = 0; c < 3; c++) counts[c] = h_pinned[TR_CTL_STATUS0 + c];
     return 0;
 }
-
-#undef GENE_TRY
 
 } // namespace umihip

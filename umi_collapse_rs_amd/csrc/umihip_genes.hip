@@ -23,6 +23,7 @@
 #include "../../include/umihip.h"
 #include "umihip_gene_index.hpp"
 #include "umihip_internal.h"
+#include "umihip_pair_table.h"
 
 namespace umihip {
 
@@ -31,20 +32,12 @@ static_assert(GENE_READ_ASSIGNED == UMI_GENE_ASSIGNED && GENE_READ_NONE == UMI_G
 
 namespace {
 
-#define GENE_TRY(expr)                           \
-    do {                                         \
-        const hipError_t e__ = (expr);           \
-        if (e__ != hipSuccess) return -(int)e__; \
-    } while (0)
-
 enum GeneCtl : int {
     GENE_BAD_ARG = 0,   // smallest read with read_ref < 0 or a bad op code (all ones: none)
     GENE_BAD_ORDER = 1, // smallest read whose cigar_off falls (all ones: none)
     GENE_STATUS0 = 2,   // three words: reads assigned, none, several
     GENE_CTL_COUNT = 5,
 };
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct GeneDevTable {
     GeneView view;
@@ -130,8 +123,8 @@ int genes_on_device(void *workspace, const GeneTable *tables, int n_tables, bool
                     unsigned long long *h_pinned, hipStream_t s)
 {
     unsigned long long *ctl = (unsigned long long *)workspace;
-    GENE_TRY(hipMemsetAsync(ctl, 0xFF, GENE_STATUS0 * 8, s));
-    GENE_TRY(hipMemsetAsync(ctl + GENE_STATUS0, 0, 3 * 8, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(ctl, 0xFF, GENE_STATUS0 * 8, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(ctl + GENE_STATUS0, 0, 3 * 8, s));
     GeneDevTable dev[2];
     char *p = (char *)workspace + 256;
     for (int t = 0; t < n_tables; t++) {
@@ -146,10 +139,10 @@ int genes_on_device(void *workspace, const GeneTable *tables, int n_tables, bool
         uint64_t *d_top = (uint64_t *)p;
         p += align256(h.top.size() * 8 + 8);
         if (n) {
-            GENE_TRY(hipMemcpyAsync(d_start, h.start.data(), n * 8, hipMemcpyHostToDevice, s));
-            GENE_TRY(hipMemcpyAsync(d_end, h.end.data(), n * 8, hipMemcpyHostToDevice, s));
-            GENE_TRY(hipMemcpyAsync(d_seg, h.seg.data(), n * sizeof(GeneSeg), hipMemcpyHostToDevice, s));
-            GENE_TRY(hipMemcpyAsync(d_top, h.top.data(), h.top.size() * 8, hipMemcpyHostToDevice, s));
+            UMIHIP_TRY_NEG(hipMemcpyAsync(d_start, h.start.data(), n * 8, hipMemcpyHostToDevice, s));
+            UMIHIP_TRY_NEG(hipMemcpyAsync(d_end, h.end.data(), n * 8, hipMemcpyHostToDevice, s));
+            UMIHIP_TRY_NEG(hipMemcpyAsync(d_seg, h.seg.data(), n * sizeof(GeneSeg), hipMemcpyHostToDevice, s));
+            UMIHIP_TRY_NEG(hipMemcpyAsync(d_top, h.top.data(), h.top.size() * 8, hipMemcpyHostToDevice, s));
         }
         dev[t] = {{d_start, d_end, d_seg, (uint32_t)n}, d_top, (uint32_t)h.top.size(), h.top_shift};
     }
@@ -173,9 +166,9 @@ int genes_on_device(void *workspace, const GeneTable *tables, int n_tables, bool
         gene_assign_kernel<true><<<grid, GENE_THREADS, 0, s>>>(a);
     else
         gene_assign_kernel<false><<<grid, GENE_THREADS, 0, s>>>(a);
-    GENE_TRY(hipGetLastError());
-    GENE_TRY(hipMemcpyAsync(h_pinned, ctl, GENE_CTL_COUNT * 8, hipMemcpyDeviceToHost, s));
-    GENE_TRY(hipStreamSynchronize(s));
+    UMIHIP_TRY_NEG(hipGetLastError());
+    UMIHIP_TRY_NEG(hipMemcpyAsync(h_pinned, ctl, GENE_CTL_COUNT * 8, hipMemcpyDeviceToHost, s));
+    UMIHIP_TRY_NEG(hipStreamSynchronize(s));
     if (h_pinned[GENE_BAD_ORDER] != ~0ull && h_pinned[GENE_BAD_ORDER] <= h_pinned[GENE_BAD_ARG]) {
         *bad = h_pinned[GENE_BAD_ORDER];
         return 2;
@@ -187,7 +180,5 @@ int genes_on_device(void *workspace, const GeneTable *tables, int n_tables, bool
     for (int c = 0; c < 3; c++) counts[c] = h_pinned[GENE_STATUS0 + c];
     return 0;
 }
-
-#undef GENE_TRY
 
 } // namespace umihip

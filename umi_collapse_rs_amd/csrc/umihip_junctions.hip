@@ -35,17 +35,12 @@
 
 #include "../../include/umihip.h"
 #include "umihip_internal.h"
+#include "umihip_pair_table.h"
 #include "umihip_junction_walk.hpp"
 
 namespace umihip {
 
 namespace {
-
-#define JN_TRY(expr)                             \
-    do {                                         \
-        const hipError_t e__ = (expr);           \
-        if (e__ != hipSuccess) return -(int)e__; \
-    } while (0)
 
 constexpr int JN_THREADS = 256;
 constexpr uint32_t JN_BLOCKS_PER_CU = 16;
@@ -63,15 +58,6 @@ enum JnCtl : int {
     JN_CTL_COUNT = 9,
 };
 enum JnCtl2 : int { JN2_JUNCTIONS = 0, JN2_NNZ = 1, JN2_COUNT = 2 };
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline uint32_t blocks_for(uint64_t n, uint32_t per) { return (uint32_t)std::max<uint64_t>(1, (n + per - 1) / per); }
-inline int bits_of(uint64_t v)
-{
-    int b = 0;
-    while (b < 64 && (v >> b)) b++;
-    return b;
-}
 
 struct JnWs1 {
     unsigned long long *ctl;
@@ -371,20 +357,20 @@ int junction_count_on_device(void *workspace, const int32_t *d_ref, const int32_
                              hipStream_t s)
 {
     const JnWs1 w = jn_carve1(workspace, n_reads, m, h_idx != nullptr);
-    JN_TRY(hipMemsetAsync(w.ctl, 0, JN_CTL_COUNT * 8, s));
-    JN_TRY(hipMemsetAsync(w.ctl + JN_BAD_ORDER, 0xFF, 5 * 8, s));
-    JN_TRY(hipMemcpyAsync(w.off, h_off, ((size_t)m + 1) * 8, hipMemcpyHostToDevice, s));
-    if (h_idx) JN_TRY(hipMemcpyAsync(w.idx, h_idx, (size_t)m * 4, hipMemcpyHostToDevice, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(w.ctl, 0, JN_CTL_COUNT * 8, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(w.ctl + JN_BAD_ORDER, 0xFF, 5 * 8, s));
+    UMIHIP_TRY_NEG(hipMemcpyAsync(w.off, h_off, ((size_t)m + 1) * 8, hipMemcpyHostToDevice, s));
+    if (h_idx) UMIHIP_TRY_NEG(hipMemcpyAsync(w.idx, h_idx, (size_t)m * 4, hipMemcpyHostToDevice, s));
     junction_cols_kernel<<<std::min(blocks_for(m, JN_THREADS), n_cus * JN_BLOCKS_PER_CU), JN_THREADS, 0, s>>>(w.idx, d_col, m, n_cols,
                                                                                                             w.bcol, w.ctl);
-    JN_TRY(hipGetLastError());
+    UMIHIP_TRY_NEG(hipGetLastError());
     const JnReads a{d_ref, d_pos, d_cigar, d_cigar_off, d_read_entry, n_reads, d_kept, d_root, n};
     junction_count_kernel<<<std::min(blocks_for(n_reads, JN_THREADS), n_cus * JN_BLOCKS_PER_CU), JN_THREADS, 0, s>>>(a, w.cnt, w.ctl);
-    JN_TRY(hipGetLastError());
-    JN_TRY(scan_inclusive_u64(w.cnt, w.incl, n_reads, w.scan_tmp, w.scan_bytes, s));
-    JN_TRY(hipMemcpyAsync(h_pinned, w.ctl, JN_CTL_COUNT * 8, hipMemcpyDeviceToHost, s));
-    JN_TRY(hipMemcpyAsync(h_pinned + JN_CTL_COUNT, w.incl + (n_reads - 1), 8, hipMemcpyDeviceToHost, s));
-    JN_TRY(hipStreamSynchronize(s));
+    UMIHIP_TRY_NEG(hipGetLastError());
+    UMIHIP_TRY_NEG(scan_inclusive_u64(w.cnt, w.incl, n_reads, w.scan_tmp, w.scan_bytes, s));
+    UMIHIP_TRY_NEG(hipMemcpyAsync(h_pinned, w.ctl, JN_CTL_COUNT * 8, hipMemcpyDeviceToHost, s));
+    UMIHIP_TRY_NEG(hipMemcpyAsync(h_pinned + JN_CTL_COUNT, w.incl + (n_reads - 1), 8, hipMemcpyDeviceToHost, s));
+    UMIHIP_TRY_NEG(hipStreamSynchronize(s));
     got->bad_cols = h_pinned[JN_BAD_COLS];
     got->bad_kind = 0;
     got->bad_read = ~0ull;
@@ -416,35 +402,35 @@ int junction_fill_on_device(void *workspace1, void *workspace2, const int32_t *d
     const JnReads a{d_ref, d_pos, d_cigar, d_cigar_off, d_read_entry, n_reads, d_kept, d_root, n};
     junction_fill_kernel<<<std::min(blocks_for(n_reads, JN_THREADS), n_cus * JN_BLOCKS_PER_CU), JN_THREADS, 0, s>>>(
         a, w1.cnt, w1.incl, w1.off, w1.bcol, m, eb, t, w.lo, w.ka, w.va, w.ref, w.mol, w.col);
-    JN_TRY(hipGetLastError());
+    UMIHIP_TRY_NEG(hipGetLastError());
     // the junctions in the order of (ref, start, end): the key word, then the ref
     bool in_b = false;
-    JN_TRY(radix_sort_pairs_u64(w.ka, w.kb, w.va, w.vb, t, 0, 2 * eb, w.radix_tmp, w.radix_bytes, &in_b, s));
+    UMIHIP_TRY_NEG(radix_sort_pairs_u64(w.ka, w.kb, w.va, w.vb, t, 0, 2 * eb, w.radix_tmp, w.radix_bytes, &in_b, s));
     uint64_t *kx = in_b ? w.kb : w.ka, *ky = in_b ? w.ka : w.kb;
     uint32_t *vx = in_b ? w.vb : w.va, *vy = in_b ? w.va : w.vb;
     if (rb) {
         junction_gather_kernel<<<grid_t, JN_THREADS, 0, s>>>(vx, w.ref, t, kx);
-        JN_TRY(hipGetLastError());
-        JN_TRY(radix_sort_pairs_u64(kx, ky, vx, vy, t, 0, rb, w.radix_tmp, w.radix_bytes, &in_b, s));
+        UMIHIP_TRY_NEG(hipGetLastError());
+        UMIHIP_TRY_NEG(radix_sort_pairs_u64(kx, ky, vx, vy, t, 0, rb, w.radix_tmp, w.radix_bytes, &in_b, s));
         if (in_b) {
             std::swap(kx, ky);
             std::swap(vx, vy);
         }
     }
     junction_heads_kernel<<<grid_t, JN_THREADS, 0, s>>>(vx, w.lo, w.ref, t, ky);
-    JN_TRY(hipGetLastError());
-    JN_TRY(scan_inclusive_u64(ky, kx, t, w.scan_tmp, w.scan_bytes, s)); // (the sorted keys have served: the numbers lie over them)
+    UMIHIP_TRY_NEG(hipGetLastError());
+    UMIHIP_TRY_NEG(scan_inclusive_u64(ky, kx, t, w.scan_tmp, w.scan_bytes, s)); // (the sorted keys have served: the numbers lie over them)
     junction_table_kernel<<<grid_t, JN_THREADS, 0, s>>>(vx, kx, w.lo, w.ref, t, eb, w.jid, d_jn_ref, d_jn_start, d_jn_end, w.ctl);
-    JN_TRY(hipGetLastError());
+    UMIHIP_TRY_NEG(hipGetLastError());
     // the occurrences in the order of (column, junction, molecule): by molecule, then, stable, by the pair
     junction_molkey_kernel<<<grid_t, JN_THREADS, 0, s>>>(w.mol, t, w.ka, w.va);
-    JN_TRY(hipGetLastError());
-    JN_TRY(radix_sort_pairs_u64(w.ka, w.kb, w.va, w.vb, t, 0, nb, w.radix_tmp, w.radix_bytes, &in_b, s));
+    UMIHIP_TRY_NEG(hipGetLastError());
+    UMIHIP_TRY_NEG(radix_sort_pairs_u64(w.ka, w.kb, w.va, w.vb, t, 0, nb, w.radix_tmp, w.radix_bytes, &in_b, s));
     kx = in_b ? w.kb : w.ka, ky = in_b ? w.ka : w.kb;
     vx = in_b ? w.vb : w.va, vy = in_b ? w.va : w.vb;
     junction_pairkey_kernel<<<grid_t, JN_THREADS, 0, s>>>(vx, w.col, w.jid, t, jb, kx);
-    JN_TRY(hipGetLastError());
-    JN_TRY(radix_sort_pairs_u64(kx, ky, vx, vy, t, 0, jb + cb, w.radix_tmp, w.radix_bytes, &in_b, s));
+    UMIHIP_TRY_NEG(hipGetLastError());
+    UMIHIP_TRY_NEG(radix_sort_pairs_u64(kx, ky, vx, vy, t, 0, jb + cb, w.radix_tmp, w.radix_bytes, &in_b, s));
     if (in_b) {
         std::swap(kx, ky);
         std::swap(vx, vy);
@@ -452,19 +438,17 @@ int junction_fill_on_device(void *workspace1, void *workspace2, const int32_t *d
     uint64_t *incl = w.lo;       // (the key words have served)
     uint32_t *head_pos = w.jid;  // (the numbers are in the pair keys)
     junction_pair_heads_kernel<<<grid_t, JN_THREADS, 0, s>>>(kx, vx, w.mol, t, ky);
-    JN_TRY(hipGetLastError());
-    JN_TRY(scan_inclusive_u64(ky, incl, t, w.scan_tmp, w.scan_bytes, s));
+    UMIHIP_TRY_NEG(hipGetLastError());
+    UMIHIP_TRY_NEG(scan_inclusive_u64(ky, incl, t, w.scan_tmp, w.scan_bytes, s));
     junction_pair_slots_kernel<<<grid_t, JN_THREADS, 0, s>>>(kx, incl, t, jb, head_pos, d_out_jn, d_out_col, w.ctl);
-    JN_TRY(hipGetLastError());
+    UMIHIP_TRY_NEG(hipGetLastError());
     junction_pair_counts_kernel<<<grid_t, JN_THREADS, 0, s>>>(head_pos, incl, t, w.ctl, d_out_molecules, d_out_reads);
-    JN_TRY(hipGetLastError());
-    JN_TRY(hipMemcpyAsync(h_pinned, w.ctl, JN2_COUNT * 8, hipMemcpyDeviceToHost, s));
-    JN_TRY(hipStreamSynchronize(s));
+    UMIHIP_TRY_NEG(hipGetLastError());
+    UMIHIP_TRY_NEG(hipMemcpyAsync(h_pinned, w.ctl, JN2_COUNT * 8, hipMemcpyDeviceToHost, s));
+    UMIHIP_TRY_NEG(hipStreamSynchronize(s));
     *junctions = h_pinned[JN2_JUNCTIONS];
     *nnz = h_pinned[JN2_NNZ];
     return 0;
 }
-
-#undef JN_TRY
 
 } // namespace umihip

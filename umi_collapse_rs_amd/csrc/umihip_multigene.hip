@@ -41,25 +41,17 @@
 #include <algorithm>
 
 #include "umihip_internal.h"
+#include "umihip_pair_table.h"
 
 namespace umihip {
 
 namespace {
-
-#define MG_TRY(expr)                             \
-    do {                                         \
-        const hipError_t e__ = (expr);           \
-        if (e__ != hipSuccess) return -(int)e__; \
-    } while (0)
 
 constexpr int MG_THREADS = 256;
 // the control block's words
 constexpr int MG_BAD_GROUPS = 0, MG_BAD_ROOTS = 1, MG_RUNS = 2, MG_REMOVED = 3, MG_REMOVED_READS = 4;
 // the walk's flags of a sorted entry
 constexpr uint32_t MG_MOL = 1u, MG_MULTI = 2u, MG_HEAD = 4u;
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline uint32_t blocks_for(uint64_t n, uint32_t per) { return (uint32_t)std::max<uint64_t>(1, (n + per - 1) / per); }
 
 struct MgWs {
     unsigned long long *ctl;
@@ -75,30 +67,24 @@ struct MgWs {
 MgWs mg_carve(void *ws, uint32_t n, uint32_t m, bool has_idx)
 {
     MgWs w;
-    char *p = (char *)ws;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        char *at = p + o;
-        o += align256(bytes);
-        return at;
-    };
-    w.ctl = (unsigned long long *)take(256);
-    w.off = (uint64_t *)take(((size_t)m + 1) * 8);
-    w.idx = has_idx ? (uint32_t *)take((size_t)m * 4) : nullptr;
-    w.total = (unsigned long long *)take((size_t)n * 8);
-    w.runmax = (unsigned long long *)take((size_t)n * 8);
-    w.eg = (uint32_t *)take((size_t)n * 4);
-    w.ties = (uint32_t *)take((size_t)n * 4);
-    w.ka = (uint64_t *)take((size_t)n * 8);
-    w.kb = (uint64_t *)take((size_t)n * 8);
-    w.incl = (uint64_t *)take((size_t)n * 8);
-    w.va = (uint32_t *)take((size_t)n * 4);
-    w.vb = (uint32_t *)take((size_t)n * 4);
+    Carver c(ws);
+    w.ctl = c.take<unsigned long long>(256);
+    w.off = c.take<uint64_t>(((size_t)m + 1) * 8);
+    w.idx = has_idx ? c.take<uint32_t>((size_t)m * 4) : nullptr;
+    w.total = c.take<unsigned long long>((size_t)n * 8);
+    w.runmax = c.take<unsigned long long>((size_t)n * 8);
+    w.eg = c.take<uint32_t>((size_t)n * 4);
+    w.ties = c.take<uint32_t>((size_t)n * 4);
+    w.ka = c.take<uint64_t>((size_t)n * 8);
+    w.kb = c.take<uint64_t>((size_t)n * 8);
+    w.incl = c.take<uint64_t>((size_t)n * 8);
+    w.va = c.take<uint32_t>((size_t)n * 4);
+    w.vb = c.take<uint32_t>((size_t)n * 4);
     w.radix_bytes = radix_sort_temp_bytes(n);
-    w.radix_tmp = take(w.radix_bytes);
+    w.radix_tmp = c.take(w.radix_bytes);
     w.scan_bytes = scan_temp_bytes(n);
-    w.scan_tmp = take(w.scan_bytes);
-    w.bytes = o;
+    w.scan_tmp = c.take(w.scan_bytes);
+    w.bytes = c.o;
     return w;
 }
 
@@ -200,11 +186,6 @@ __global__ __launch_bounds__(MG_THREADS) void mg_word_kernel(const uint64_t *__r
     if (!order) out_val[i] = e;
 }
 
-__global__ __launch_bounds__(MG_THREADS) void mg_heads_key_kernel(const uint64_t *__restrict__ key, uint32_t n, uint64_t *__restrict__ flag)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * MG_THREADS + threadIdx.x;
-    if (i < n) flag[i] = i == 0 || key[i] != key[i - 1] ? 1ull : 0ull;
-}
 __global__ __launch_bounds__(MG_THREADS) void mg_heads_wide_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ eg,
                                                                    const uint8_t *__restrict__ kept, int W, MgMasks um,
                                                                    const uint32_t *__restrict__ order, uint32_t n,
@@ -221,26 +202,6 @@ __global__ __launch_bounds__(MG_THREADS) void mg_heads_wide_kernel(const uint64_
     flag[i] = head ? 1ull : 0ull;
 }
 
-// what a lane of the three walks knows of its sorted entry's run: its number (from 1; 0 past the end) and whether
-// the run ends at this entry
-struct MgRun {
-    uint64_t slot1;
-    bool valid, head, last;
-};
-__device__ __forceinline__ MgRun mg_run_of(const uint64_t *__restrict__ incl, uint64_t i, uint32_t n)
-{
-    const int lane = (int)(threadIdx.x & 63u);
-    MgRun r;
-    r.valid = i < n;
-    r.slot1 = r.valid ? incl[i] : 0ull;
-    uint64_t prev = __shfl_up(r.slot1, 1), next = __shfl_down(r.slot1, 1);
-    if (lane == 0) prev = r.valid && i > 0 ? incl[i - 1] : 0ull;
-    if (lane == 63) next = i + 1 < n ? incl[i + 1] : 0ull;
-    r.head = r.valid && r.slot1 != prev; // (run numbers start at 1: the first entry differs from 0)
-    r.last = r.valid && (i + 1 >= n || next != r.slot1);
-    return r;
-}
-
 // key_ts: the last sort's keys, whose bit mol_bit says "no molecule"; the totals of the runs longer than one are
 // written over them, in sorted order (a lane reads its own word first)
 __global__ __launch_bounds__(MG_THREADS) void mg_max_kernel(const uint32_t *__restrict__ order, const uint64_t *__restrict__ incl,
@@ -249,8 +210,7 @@ __global__ __launch_bounds__(MG_THREADS) void mg_max_kernel(const uint32_t *__re
                                                             unsigned long long *runmax)
 {
     const uint64_t i = (uint64_t)blockIdx.x * MG_THREADS + threadIdx.x;
-    const int lane = (int)(threadIdx.x & 63u);
-    const MgRun r = mg_run_of(incl, i, n);
+    const WaveRuns r(incl, i, n);
     const bool mol = r.valid && ((key_ts[i] >> mol_bit) & 1ull) == 0ull;
     const bool multi = mol && !(r.head && r.last); // (a run holds molecules only or none: the molecule bit is part of the key)
     unsigned long long t = 0;
@@ -260,12 +220,8 @@ __global__ __launch_bounds__(MG_THREADS) void mg_max_kernel(const uint32_t *__re
         vf[i] = (mol ? MG_MOL : 0u) | (multi ? MG_MULTI : 0u) | (r.head ? MG_HEAD : 0u);
     }
     unsigned long long v = multi ? t : 0ull;
-    for (int d = 1; d < 64; d <<= 1) { // inclusive max scan inside runs
-        const unsigned long long uv = __shfl_up(v, d);
-        const uint64_t us = __shfl_up(r.slot1, d);
-        if (lane >= d && us == r.slot1) v = max(v, uv);
-    }
-    if (multi && (r.last || lane == 63)) atomicMax(runmax + (r.slot1 - 1), v); // the run's last lane in this wave
+    r.scan([](unsigned long long x, unsigned long long y) { return max(x, y); }, v);
+    if (multi && r.tail()) atomicMax(runmax + r.slot(), v);
 }
 
 __global__ __launch_bounds__(MG_THREADS) void mg_ties_kernel(const uint64_t *__restrict__ incl, const unsigned long long *__restrict__ ts,
@@ -274,16 +230,11 @@ __global__ __launch_bounds__(MG_THREADS) void mg_ties_kernel(const uint64_t *__r
                                                              uint32_t *ties)
 {
     const uint64_t i = (uint64_t)blockIdx.x * MG_THREADS + threadIdx.x;
-    const int lane = (int)(threadIdx.x & 63u);
-    const MgRun r = mg_run_of(incl, i, n);
+    const WaveRuns r(incl, i, n);
     const bool multi = r.valid && (vf[i] & MG_MULTI) != 0u;
-    uint32_t c = multi && ts[i] == runmax[r.slot1 - 1] ? 1u : 0u;
-    for (int d = 1; d < 64; d <<= 1) { // inclusive sum scan inside runs
-        const uint32_t uc = __shfl_up(c, d);
-        const uint64_t us = __shfl_up(r.slot1, d);
-        if (lane >= d && us == r.slot1) c += uc;
-    }
-    if (multi && (r.last || lane == 63) && c) atomicAdd(ties + (r.slot1 - 1), c);
+    uint32_t c = multi && ts[i] == runmax[r.slot()] ? 1u : 0u;
+    r.scan([](uint32_t x, uint32_t y) { return x + y; }, c);
+    if (multi && r.tail() && c) atomicAdd(ties + r.slot(), c);
 }
 
 // (grid-stride, the counts kept in registers: a block adds to the control block once -- a wave's worth of atomics
@@ -355,12 +306,12 @@ int multigene_on_device(void *workspace, const MultigeneCall &c, hipStream_t s)
         const int bits = std::min(64, std::max(0, 3 * L - 64 * wd));
         um.wm[wd] = bits == 64 ? ~0ull : (1ull << bits) - 1ull;
     }
-    MG_TRY(hipMemsetAsync(w.ctl, 0, 256, s));
-    MG_TRY(hipMemsetAsync(w.total, 0, (size_t)n * 8, s));
-    MG_TRY(hipMemsetAsync(w.runmax, 0, (size_t)n * 8, s)); // (the runs' words are added up in place)
-    MG_TRY(hipMemsetAsync(w.ties, 0, (size_t)n * 4, s));
-    MG_TRY(hipMemcpyAsync(w.off, c.h_off, ((size_t)m + 1) * 8, hipMemcpyHostToDevice, s));
-    if (c.h_idx) MG_TRY(hipMemcpyAsync(w.idx, c.h_idx, (size_t)m * 4, hipMemcpyHostToDevice, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(w.ctl, 0, 256, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(w.total, 0, (size_t)n * 8, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(w.runmax, 0, (size_t)n * 8, s)); // (the runs' words are added up in place)
+    UMIHIP_TRY_NEG(hipMemsetAsync(w.ties, 0, (size_t)n * 4, s));
+    UMIHIP_TRY_NEG(hipMemcpyAsync(w.off, c.h_off, ((size_t)m + 1) * 8, hipMemcpyHostToDevice, s));
+    if (c.h_idx) UMIHIP_TRY_NEG(hipMemcpyAsync(w.idx, c.h_idx, (size_t)m * 4, hipMemcpyHostToDevice, s));
     const uint32_t per_entry = blocks_for(n, MG_THREADS);
     MgEntryArgs a;
     a.keys = c.d_keys;
@@ -384,7 +335,7 @@ int multigene_on_device(void *workspace, const MultigeneCall &c, hipStream_t s)
     a.val = w.va;
     a.kept_out = c.d_kept_out;
     mg_entry_kernel<<<std::min(per_entry, c.n_cus * 8), MG_THREADS, 0, s>>>(a);
-    MG_TRY(hipGetLastError());
+    UMIHIP_TRY_NEG(hipGetLastError());
     uint64_t *ka = w.ka, *kb = w.kb;
     uint32_t *va = w.va, *vb = w.vb;
     auto sort_by = [&](int bits) {
@@ -397,37 +348,35 @@ int multigene_on_device(void *workspace, const MultigeneCall &c, hipStream_t s)
         return e;
     };
     if (composed) {
-        MG_TRY(sort_by(3 * L + gb + 1));
-        mg_heads_key_kernel<<<per_entry, MG_THREADS, 0, s>>>(ka, n, kb);
-        MG_TRY(hipGetLastError());
+        UMIHIP_TRY_NEG(sort_by(3 * L + gb + 1));
+        pair_heads_kernel<MG_THREADS><<<per_entry, MG_THREADS, 0, s>>>(ka, n, kb);
+        UMIHIP_TRY_NEG(hipGetLastError());
     } else {
         for (int wd = 0; wd <= W; wd++) { // (stable sorts, the least significant word first)
             const int bits = wd < W ? std::min(64, 3 * L - 64 * wd) : gb + 1;
             mg_word_kernel<<<per_entry, MG_THREADS, 0, s>>>(c.d_keys, w.eg, c.d_kept, W, wd, wd < W ? um.wm[wd] : 0ull, gb,
                                                             wd ? va : nullptr, n, ka, va);
-            MG_TRY(hipGetLastError());
-            MG_TRY(sort_by(bits));
+            UMIHIP_TRY_NEG(hipGetLastError());
+            UMIHIP_TRY_NEG(sort_by(bits));
         }
         mg_heads_wide_kernel<<<per_entry, MG_THREADS, 0, s>>>(c.d_keys, w.eg, c.d_kept, W, um, va, n, kb);
-        MG_TRY(hipGetLastError());
+        UMIHIP_TRY_NEG(hipGetLastError());
     }
-    MG_TRY(scan_inclusive_u64(kb, w.incl, n, w.scan_tmp, w.scan_bytes, s));
+    UMIHIP_TRY_NEG(scan_inclusive_u64(kb, w.incl, n, w.scan_tmp, w.scan_bytes, s));
     unsigned long long *ts = (unsigned long long *)ka; // (the sorted keys have been compared: the totals take their place)
     mg_max_kernel<<<per_entry, MG_THREADS, 0, s>>>(va, w.incl, w.total, composed ? 3 * L + gb : gb, n, ts, vb, w.runmax);
-    MG_TRY(hipGetLastError());
+    UMIHIP_TRY_NEG(hipGetLastError());
     mg_ties_kernel<<<per_entry, MG_THREADS, 0, s>>>(w.incl, ts, vb, w.runmax, n, w.ties);
-    MG_TRY(hipGetLastError());
+    UMIHIP_TRY_NEG(hipGetLastError());
     mg_write_kernel<<<std::min(per_entry, c.n_cus * 8), MG_THREADS, 0, s>>>(va, w.incl, ts, vb, w.runmax, w.ties, n, c.d_kept_out, w.ctl);
-    MG_TRY(hipGetLastError());
+    UMIHIP_TRY_NEG(hipGetLastError());
     if (c.d_freq_out) {
         mg_freq_kernel<<<per_entry, MG_THREADS, 0, s>>>(c.d_freq, c.d_root, c.d_kept_out, n, c.d_freq_out);
-        MG_TRY(hipGetLastError());
+        UMIHIP_TRY_NEG(hipGetLastError());
     }
-    MG_TRY(hipMemcpyAsync(c.h_pinned, w.ctl, 5 * 8, hipMemcpyDeviceToHost, s));
-    MG_TRY(hipStreamSynchronize(s));
+    UMIHIP_TRY_NEG(hipMemcpyAsync(c.h_pinned, w.ctl, 5 * 8, hipMemcpyDeviceToHost, s));
+    UMIHIP_TRY_NEG(hipStreamSynchronize(s));
     return 0;
 }
-
-#undef MG_TRY
 
 } // namespace umihip

@@ -5,7 +5,7 @@
 // The collapse is the full-depth one: nothing is collapsed again per depth.  No counterpart in the reference;
 // tests/saturation_model.py defines it.  Integer work on HBM streams, 64-lane waves, no MFMA.
 //
-// The bucket table is walked on the host exactly as for umi_count_matrix (umihip_count.hip): the m non-empty buckets.
+// The pair-table pipeline ("The pair-table pipeline"; umihip_pair_table.h) with these parts of its own:
 //
 //   scatter    a lane per read: its level's bit is OR-ed onto its molecule's word of a zeroed array, a word per entry, at
 //              root[read_entry[i]] -- an integer OR, so the result does not depend on the order; the molecule's level
@@ -13,13 +13,11 @@
 //              level go through the block's LDS histogram and one atomicAdd per bin and block.  With option
 //              "saturation_skip" a lane loads the word first and leaves the atomic out where its bit is set already.
 //              A read_entry or root out of range goes to the control block by atomicMin, and nothing is written for it.
-//   molecules  umi_velocity_matrix's walk: a bucket of up to SAT_SMALL entries is its lane's, a larger one is queued in
-//              LDS and taken by a wave, 64 entries at a time, their levels counted by ballots.  Molecules per level
-//              through the block's LDS histogram; a molecule adds 1 to its (level, column) count; every bucket
-//              writes its smallest level, its sort key column << rb | row and its number.
-//   pairs      the library's radix sort of the buckets by key, run heads, their scan, and a segmented minimum over the
-//              wave that ends in an atomicMin per run and wave (a minimum: no order).  Then a lane per pair: pairs per
-//              level, and 1 onto the pair's (level, column) count.
+//   molecules  the bucket walk: a bucket's lane takes its entries one by one, a queued bucket's wave 64 entries at a
+//              time, their levels counted by ballots.  Molecules per level through the block's LDS histogram; a
+//              molecule adds 1 to its (level, column) count; every bucket writes its smallest level.
+//   pairs      the runs' scan takes the minimum and ends in an atomicMin per run and wave (a minimum: no order).  Then
+//              a lane per pair: pairs per level, and 1 onto the pair's (level, column) count.
 //   columns    a lane per column walks its at most L counts of either table: whether it is selected, its first level,
 //              the molecules and pairs of selected columns per level, and for every depth the column's cumulative
 //              molecules and pairs as sort keys depth << 33 | count (a column that is not selected: count 2^32, behind
@@ -39,18 +37,13 @@
 
 #include "../../include/umihip.h"
 #include "umihip_internal.h"
+#include "umihip_pair_table.h"
 
 namespace umihip {
 
 namespace {
 
-#define SAT_TRY(expr)                            \
-    do {                                         \
-        const hipError_t e__ = (expr);           \
-        if (e__ != hipSuccess) return -(int)e__; \
-    } while (0)
-
-constexpr int SAT_THREADS = 256, SAT_WAVES = SAT_THREADS / 64;
+constexpr int SAT_THREADS = 256;
 constexpr uint32_t SAT_SMALL = 32;       // a bucket of more entries is a wave's (umihip_velocity.hip's VEL_SMALL)
 constexpr uint32_t SAT_NONE = 32;        // the level of what has no read
 constexpr uint32_t SAT_LDS_TABLE = 4096; // words of a block's own (level, column) table
@@ -64,63 +57,42 @@ enum SatCtl : int {
     SAT_N_SEL = 3,     // selected columns
     SAT_CTL_COUNT = 4, // then six histograms of SAT_NONE bins, in the curve's order of columns 0..5
 };
+static_assert(SAT_BAD_IDS == 0, "the bucket walk counts into ctl[0]");
 enum SatHist : int { H_READS = 0, H_MOLECULES = 1, H_PAIRS = 2, H_CELLS = 3, H_MOLECULES_IN = 4, H_PAIRS_IN = 5, H_COUNT = 6 };
 constexpr size_t SAT_CTL_BYTES = (SAT_CTL_COUNT + H_COUNT * SAT_NONE) * 8, SAT_CURVE_WORDS = SAT_NONE * 8;
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-struct SatWs {
-    unsigned long long *ctl; // the control words, then the histograms
+struct SatWs : PairTableWs { // (ctl: the control words, then the histograms)
     unsigned long long *curve;
-    uint32_t *levels; // [n] a word per entry: the levels of the reads of the molecule it roots
-    uint64_t *off;
-    uint32_t *idx;
-    uint64_t *ka, *kb;
-    uint32_t *va, *vb;
-    uint32_t *blev;         // [m] a bucket's smallest level
-    uint32_t *plev, *pcol;  // [m] a pair's smallest level and its column, by slot
+    uint32_t *levels;        // [n] a word per entry: the levels of the reads of the molecule it roots
+    uint32_t *blev;          // [m] a bucket's smallest level
+    uint32_t *plev, *pcol;   // [m] a pair's smallest level and its column, by slot
     uint32_t *tab_m, *tab_p; // [L][n_cols] molecules and pairs of a column at a level
-    uint64_t *mka, *mkb;    // [2 L n_cols] the median keys
+    uint64_t *mka, *mkb;     // [2 L n_cols] the median keys
     uint32_t *mva, *mvb;
-    void *radix_tmp, *scan_tmp;
-    size_t levels_bytes, tab_bytes, radix_bytes, scan_bytes, total;
+    size_t levels_bytes, tab_bytes, total;
 };
 SatWs sat_carve(void *ws, uint64_t n, uint32_t m, bool has_idx, uint32_t n_cols, int n_levels)
 {
     SatWs w;
-    char *p = (char *)ws;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        char *at = p + o;
-        o += align256(bytes);
-        return at;
-    };
+    Carver c(ws);
     const size_t cells = (size_t)n_levels * n_cols;
-    w.ctl = (unsigned long long *)take(SAT_CTL_BYTES);
-    w.curve = (unsigned long long *)take(SAT_CURVE_WORDS * 8);
+    w.ctl = c.take<unsigned long long>(SAT_CTL_BYTES);
+    w.curve = c.take<unsigned long long>(SAT_CURVE_WORDS * 8);
     w.levels_bytes = (size_t)n * 4;
-    w.levels = (uint32_t *)take(w.levels_bytes);
-    w.off = (uint64_t *)take(((size_t)m + 1) * 8);
-    w.idx = has_idx ? (uint32_t *)take((size_t)m * 4) : nullptr;
-    w.ka = (uint64_t *)take((size_t)m * 8);
-    w.kb = (uint64_t *)take((size_t)m * 8);
-    w.va = (uint32_t *)take((size_t)m * 4);
-    w.vb = (uint32_t *)take((size_t)m * 4);
-    w.blev = (uint32_t *)take((size_t)m * 4);
-    w.plev = (uint32_t *)take((size_t)m * 4);
-    w.pcol = (uint32_t *)take((size_t)m * 4);
+    w.levels = c.take<uint32_t>(w.levels_bytes);
+    w.carve_buckets(c, m, has_idx);
+    w.blev = c.take<uint32_t>((size_t)m * 4);
+    w.plev = c.take<uint32_t>((size_t)m * 4);
+    w.pcol = c.take<uint32_t>((size_t)m * 4);
     w.tab_bytes = cells * 4;
-    w.tab_m = (uint32_t *)take(w.tab_bytes);
-    w.tab_p = (uint32_t *)take(w.tab_bytes);
-    w.mka = (uint64_t *)take(2 * cells * 8);
-    w.mkb = (uint64_t *)take(2 * cells * 8);
-    w.mva = (uint32_t *)take(2 * cells * 4);
-    w.mvb = (uint32_t *)take(2 * cells * 4);
-    w.radix_bytes = std::max(radix_sort_temp_bytes(m), radix_sort_temp_bytes((uint32_t)(2 * cells)));
-    w.radix_tmp = take(w.radix_bytes);
-    w.scan_bytes = scan_temp_bytes(m);
-    w.scan_tmp = take(w.scan_bytes);
-    w.total = o;
+    w.tab_m = c.take<uint32_t>(w.tab_bytes);
+    w.tab_p = c.take<uint32_t>(w.tab_bytes);
+    w.mka = c.take<uint64_t>(2 * cells * 8);
+    w.mkb = c.take<uint64_t>(2 * cells * 8);
+    w.mva = c.take<uint32_t>(2 * cells * 4);
+    w.mvb = c.take<uint32_t>(2 * cells * 4);
+    w.carve_temps(c, m, std::max(radix_sort_temp_bytes(m), radix_sort_temp_bytes((uint32_t)(2 * cells))));
+    w.total = c.o;
     return w;
 }
 
@@ -188,63 +160,39 @@ __device__ __forceinline__ void sat_table_flush(const uint32_t *lds, uint32_t wo
 }
 
 struct SatArgs {
+    PairTable t;
     const uint8_t *kept;
     const uint32_t *levels;
-    const uint64_t *off;
-    const uint32_t *idx; // may be null
-    const uint32_t *row, *col;
-    uint32_t n_rows, n_cols, m, n_levels, lds_words; // lds_words: L n_cols where the block's table is in LDS, else 0
-    int rb;
-    uint64_t *key;
-    uint32_t *val, *blev, *tab_m;
-    unsigned long long *ctl;
+    uint32_t n_levels, lds_words; // lds_words: L n_cols where the block's table is in LDS, else 0
+    uint32_t *blev, *tab_m;
 };
 
 __global__ __launch_bounds__(SAT_THREADS) void saturation_molecules_kernel(SatArgs a)
 {
-    __shared__ uint32_t queue[SAT_THREADS];
-    __shared__ uint32_t queued;
     __shared__ uint32_t hist[SAT_NONE];
     __shared__ uint32_t lds_table[SAT_LDS_TABLE];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
     if (tid < SAT_NONE) hist[tid] = 0;
     sat_table_clear(lds_table, a.lds_words);
-    const SatTable table{a.lds_words ? lds_table : nullptr, a.tab_m, a.n_cols};
-    for (uint64_t base = (uint64_t)blockIdx.x * SAT_THREADS; base < a.m; base += (uint64_t)gridDim.x * SAT_THREADS) {
-        if (tid == 0) queued = 0;
-        __syncthreads();
-        const uint64_t j = base + tid;
-        if (j < a.m) {
-            const uint64_t lo = a.off[j], hi = a.off[j + 1];
-            const uint32_t b = a.idx ? a.idx[j] : (uint32_t)j;
-            const uint32_t row = a.row[b], col = a.col[b];
-            const bool bad = row >= a.n_rows || col >= a.n_cols;
-            if (bad) atomicAdd(a.ctl + SAT_BAD_IDS, 1ull);
-            a.key[j] = bad ? 0ull : ((uint64_t)col << a.rb) | row;
-            a.val[j] = (uint32_t)j;
-            if (hi - lo <= SAT_SMALL) {
-                uint32_t least = SAT_NONE;
-                for (uint64_t e = lo; e < hi; e++) {
-                    const uint32_t w = a.levels[e];
-                    if (!a.kept[e] || !w) continue;
-                    const uint32_t lev = (uint32_t)__ffs((int)w) - 1u;
-                    least = min(least, lev);
-                    atomicAdd(&hist[lev], 1u);
-                    if (!bad) table.add(lev, col, 1u);
-                }
-                a.blev[j] = least;
-            } else {
-                queue[atomicAdd(&queued, 1u)] = tid;
+    const SatTable table{a.lds_words ? lds_table : nullptr, a.tab_m, a.t.n_cols};
+    pair_bucket_walk<SAT_THREADS, SAT_SMALL>( // (its first barrier is the cleared tables' too)
+        a.t,
+        [&](uint64_t j, uint64_t lo, uint64_t hi, uint32_t col, bool bad) {
+            uint32_t least = SAT_NONE;
+            for (uint64_t e = lo; e < hi; e++) {
+                const uint32_t w = a.levels[e];
+                if (!a.kept[e] || !w) continue;
+                const uint32_t lev = (uint32_t)__ffs((int)w) - 1u;
+                least = min(least, lev);
+                atomicAdd(&hist[lev], 1u);
+                if (!bad) table.add(lev, col, 1u);
             }
-        }
-        __syncthreads();
-        const uint32_t nq = queued;
-        for (uint32_t t = wave; t < nq; t += SAT_WAVES) {
-            const uint64_t jb = base + queue[t];
-            const uint64_t lo = a.off[jb], hi = a.off[jb + 1];
-            const uint32_t b = a.idx ? a.idx[jb] : (uint32_t)jb;
-            const uint32_t col = a.col[b];
-            const bool bad = a.row[b] >= a.n_rows || col >= a.n_cols;
+            a.blev[j] = least;
+        },
+        [&](uint64_t jb, uint64_t lo, uint64_t hi) {
+            const uint32_t b = a.t.idx ? a.t.idx[jb] : (uint32_t)jb;
+            const uint32_t col = a.t.col[b];
+            const bool bad = a.t.row[b] >= a.t.n_rows || col >= a.t.n_cols;
             uint32_t mine = 0; // lane l: the bucket's molecules of level l
             for (uint64_t e0 = lo; e0 < hi; e0 += 64) {
                 const uint64_t e = e0 + lane;
@@ -264,19 +212,10 @@ __global__ __launch_bounds__(SAT_THREADS) void saturation_molecules_kernel(SatAr
                 if (!bad) table.add(lane, col, mine);
             }
             if (lane == 0) a.blev[jb] = have ? (uint32_t)__ffsll((unsigned long long)have) - 1u : SAT_NONE;
-        }
-        __syncthreads(); // (the queue is the next round's as well)
-    }
+        });
     __syncthreads();
-    if (tid < a.n_levels && hist[tid]) atomicAdd(a.ctl + SAT_CTL_COUNT + H_MOLECULES * SAT_NONE + tid, (unsigned long long)hist[tid]);
+    if (tid < a.n_levels && hist[tid]) atomicAdd(a.t.ctl + SAT_CTL_COUNT + H_MOLECULES * SAT_NONE + tid, (unsigned long long)hist[tid]);
     sat_table_flush(lds_table, a.lds_words, a.tab_m);
-}
-
-__global__ __launch_bounds__(SAT_THREADS) void saturation_heads_kernel(const uint64_t *__restrict__ key, uint32_t m,
-                                                                       uint64_t *__restrict__ flag)
-{
-    for (uint64_t i = (uint64_t)blockIdx.x * SAT_THREADS + threadIdx.x; i < m; i += (uint64_t)gridDim.x * SAT_THREADS)
-        flag[i] = i == 0 || key[i] != key[i - 1] ? 1ull : 0ull;
 }
 
 // plev[] holds all ones on entry
@@ -285,24 +224,13 @@ __global__ __launch_bounds__(SAT_THREADS) void saturation_pair_min_kernel(const 
                                                                           const uint32_t *__restrict__ blev, uint32_t m, int rb,
                                                                           uint32_t *plev, uint32_t *__restrict__ pcol)
 {
-    const int lane = (int)(threadIdx.x & 63u);
     for (uint64_t base = (uint64_t)blockIdx.x * SAT_THREADS; base < m; base += (uint64_t)gridDim.x * SAT_THREADS) {
         const uint64_t i = base + threadIdx.x;
-        const bool valid = i < m;
-        const uint64_t slot1 = valid ? incl[i] : 0ull; // the slot, counted from 1
-        uint64_t prev = __shfl_up(slot1, 1), next = __shfl_down(slot1, 1);
-        if (lane == 0) prev = valid && i > 0 ? incl[i - 1] : 0ull;
-        if (lane == 63) next = i + 1 < m ? incl[i + 1] : 0ull;
-        const bool head = valid && slot1 != prev;
-        const bool last = valid && (i + 1 >= m || next != slot1);
-        uint32_t v = valid ? blev[val[i]] : SAT_NONE;
-        for (int d = 1; d < 64; d <<= 1) { // inclusive minimum inside runs of one slot
-            const uint32_t uv = __shfl_up(v, d);
-            const uint64_t uslot = __shfl_up(slot1, d);
-            if (lane >= d && uslot == slot1) v = min(v, uv);
-        }
-        if (head) pcol[slot1 - 1] = (uint32_t)(key[i] >> rb);
-        if (valid && (last || lane == 63)) atomicMin(plev + (slot1 - 1), v); // the run's last lane in this wave
+        const WaveRuns run(incl, i, m);
+        uint32_t v = run.valid ? blev[val[i]] : SAT_NONE;
+        run.scan([](uint32_t x, uint32_t y) { return min(x, y); }, v);
+        if (run.head) pcol[run.slot()] = (uint32_t)(key[i] >> rb);
+        if (run.tail()) atomicMin(plev + run.slot(), v);
     }
 }
 
@@ -388,8 +316,6 @@ __global__ __launch_bounds__(64) void saturation_curve_kernel(const unsigned lon
     }
 }
 
-inline uint32_t blocks_for(uint64_t n, uint32_t per) { return (uint32_t)std::max<uint64_t>(1, (n + per - 1) / per); }
-
 } // namespace
 
 size_t saturation_workspace_bytes(uint64_t n, uint32_t m, bool has_idx, uint32_t n_cols, int n_levels)
@@ -404,74 +330,49 @@ int saturation_curve_on_device(void *workspace, const uint32_t *d_read_entry, ui
                                uint64_t *bad_read, uint32_t n_cus, unsigned long long *h_pinned, hipStream_t s)
 {
     const SatWs w = sat_carve(workspace, n, m, h_idx != nullptr, n_cols, n_levels);
-    auto bits = [](uint64_t v) {
-        int b = 0;
-        while (v >> b) b++;
-        return b;
-    };
-    const int rb = bits(n_rows - 1), cb = bits(n_cols - 1);
+    const int rb = bits_of(n_rows - 1), cb = bits_of(n_cols - 1);
+    int r;
     const uint32_t L = (uint32_t)n_levels, cells = L * n_cols;
     const uint32_t lds_words = cells <= SAT_LDS_TABLE ? cells : 0u;
-    SAT_TRY(hipMemsetAsync(w.ctl, 0, SAT_CTL_BYTES, s));
-    SAT_TRY(hipMemsetAsync(w.ctl + SAT_BAD_ENTRY, 0xFF, 2 * 8, s));
-    SAT_TRY(hipMemsetAsync(w.levels, 0, w.levels_bytes, s));
-    SAT_TRY(hipMemsetAsync(w.plev, 0xFF, (size_t)m * 4, s));
-    SAT_TRY(hipMemsetAsync(w.tab_m, 0, w.tab_bytes, s));
-    SAT_TRY(hipMemsetAsync(w.tab_p, 0, w.tab_bytes, s));
-    SAT_TRY(hipMemcpyAsync(w.off, h_off, ((size_t)m + 1) * 8, hipMemcpyHostToDevice, s));
-    if (h_idx) SAT_TRY(hipMemcpyAsync(w.idx, h_idx, (size_t)m * 4, hipMemcpyHostToDevice, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(w.ctl, 0, SAT_CTL_BYTES, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(w.ctl + SAT_BAD_ENTRY, 0xFF, 2 * 8, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(w.levels, 0, w.levels_bytes, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(w.plev, 0xFF, (size_t)m * 4, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(w.tab_m, 0, w.tab_bytes, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(w.tab_p, 0, w.tab_bytes, s));
+    if ((r = pair_table_upload(w, h_off, h_idx, m, s))) return r;
     if (n_reads) {
         const uint32_t grid = std::min(blocks_for(n_reads, SAT_THREADS), n_cus * 16);
         if (skip_set)
             saturation_scatter_kernel<true><<<grid, SAT_THREADS, 0, s>>>(d_read_entry, n_reads, d_kept, d_root, n, seed, L, w.levels, w.ctl);
         else
             saturation_scatter_kernel<false><<<grid, SAT_THREADS, 0, s>>>(d_read_entry, n_reads, d_kept, d_root, n, seed, L, w.levels, w.ctl);
-        SAT_TRY(hipGetLastError());
+        UMIHIP_TRY_NEG(hipGetLastError());
     }
-    SatArgs a;
-    a.kept = d_kept;
-    a.levels = w.levels;
-    a.off = w.off;
-    a.idx = w.idx;
-    a.row = d_row;
-    a.col = d_col;
-    a.n_rows = n_rows;
-    a.n_cols = n_cols;
-    a.m = m;
-    a.n_levels = L;
-    a.lds_words = lds_words;
-    a.rb = rb;
-    a.key = w.ka;
-    a.val = w.va;
-    a.blev = w.blev;
-    a.tab_m = w.tab_m;
-    a.ctl = w.ctl;
+    const SatArgs a{{w.off, w.idx, d_row, d_col, n_rows, n_cols, m, rb, w.ka, w.va, w.ctl},
+                    d_kept, w.levels, L, lds_words, w.blev, w.tab_m};
     const uint32_t per_bucket_grid = std::min(blocks_for(m, SAT_THREADS), n_cus * 4); // (a block flushes its table at its end)
     saturation_molecules_kernel<<<per_bucket_grid, SAT_THREADS, 0, s>>>(a);
-    SAT_TRY(hipGetLastError());
-    bool in_b = false;
-    SAT_TRY(radix_sort_pairs_u64(w.ka, w.kb, w.va, w.vb, m, 0, rb + cb, w.radix_tmp, w.radix_bytes, &in_b, s));
-    const uint64_t *keys = in_b ? w.kb : w.ka;
-    const uint32_t *vals = in_b ? w.vb : w.va;
-    uint64_t *flag = in_b ? w.ka : w.kb, *incl = w.off; // (the offsets have been read)
-    saturation_heads_kernel<<<std::min(blocks_for(m, SAT_THREADS), n_cus * 8), SAT_THREADS, 0, s>>>(keys, m, flag);
-    SAT_TRY(hipGetLastError());
-    SAT_TRY(scan_inclusive_u64(flag, incl, m, w.scan_tmp, w.scan_bytes, s));
-    saturation_pair_min_kernel<<<std::min(blocks_for(m, SAT_THREADS), n_cus * 8), SAT_THREADS, 0, s>>>(keys, vals, incl, w.blev, m, rb, w.plev,
-                                                                                                     w.pcol);
-    SAT_TRY(hipGetLastError());
+    UMIHIP_TRY_NEG(hipGetLastError());
+    const uint64_t *keys;
+    const uint32_t *vals;
+    uint64_t *incl;
+    const uint32_t capped_grid = std::min(blocks_for(m, SAT_THREADS), n_cus * 8);
+    if ((r = pair_table_sort_and_number<SAT_THREADS>(w, m, rb + cb, capped_grid, s, &keys, &vals, &incl))) return r;
+    saturation_pair_min_kernel<<<capped_grid, SAT_THREADS, 0, s>>>(keys, vals, incl, w.blev, m, rb, w.plev, w.pcol);
+    UMIHIP_TRY_NEG(hipGetLastError());
     saturation_pairs_kernel<<<per_bucket_grid, SAT_THREADS, 0, s>>>(w.plev, w.pcol, incl + (m - 1), L, n_cols, lds_words, w.tab_p, w.ctl);
-    SAT_TRY(hipGetLastError());
+    UMIHIP_TRY_NEG(hipGetLastError());
     saturation_columns_kernel<<<std::min(blocks_for(n_cols, SAT_THREADS), n_cus * 8), SAT_THREADS, 0, s>>>(w.tab_m, w.tab_p, d_cell_mask, n_cols, L,
                                                                                                          w.mka, w.mva, w.ctl);
-    SAT_TRY(hipGetLastError());
+    UMIHIP_TRY_NEG(hipGetLastError());
     bool med_in_b = false;
-    SAT_TRY(radix_sort_pairs_u64(w.mka, w.mkb, w.mva, w.mvb, 2 * cells, 0, SAT_COUNT_BITS + 6, w.radix_tmp, w.radix_bytes, &med_in_b, s));
+    UMIHIP_TRY_NEG(radix_sort_pairs_u64(w.mka, w.mkb, w.mva, w.mvb, 2 * cells, 0, SAT_COUNT_BITS + 6, w.radix_tmp, w.radix_bytes, &med_in_b, s));
     saturation_curve_kernel<<<1, 64, 0, s>>>(w.ctl, med_in_b ? w.mkb : w.mka, n_cols, L, w.curve);
-    SAT_TRY(hipGetLastError());
-    SAT_TRY(hipMemcpyAsync(h_pinned, w.ctl, SAT_CTL_COUNT * 8, hipMemcpyDeviceToHost, s));
-    SAT_TRY(hipMemcpyAsync(h_pinned + SAT_CTL_COUNT, w.curve, (size_t)L * 8 * 8, hipMemcpyDeviceToHost, s));
-    SAT_TRY(hipStreamSynchronize(s));
+    UMIHIP_TRY_NEG(hipGetLastError());
+    UMIHIP_TRY_NEG(hipMemcpyAsync(h_pinned, w.ctl, SAT_CTL_COUNT * 8, hipMemcpyDeviceToHost, s));
+    UMIHIP_TRY_NEG(hipMemcpyAsync(h_pinned + SAT_CTL_COUNT, w.curve, (size_t)L * 8 * 8, hipMemcpyDeviceToHost, s));
+    UMIHIP_TRY_NEG(hipStreamSynchronize(s));
     *bad_ids = h_pinned[SAT_BAD_IDS];
     *bad_kind = 0;
     *bad_read = ~0ull;
@@ -482,7 +383,5 @@ int saturation_curve_on_device(void *workspace, const uint32_t *d_read_entry, ui
         }
     return 0;
 }
-
-#undef SAT_TRY
 
 } // namespace umihip

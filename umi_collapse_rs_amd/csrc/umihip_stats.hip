@@ -27,7 +27,7 @@
 //            bucket's global table (atomics, from the wave's LDS table), a wave per bucket to finish.
 //   post     per kept entry: total[] to the family sizes after.
 //   per UMI  (optional) a stable radix_sort_pairs_u64 per key word, word 0 first, carrying the entry; heads, a
-//            scan, and segmented sums over the wave as in umihip_count.hip.
+//            scan, and the runs' sums over the wave (umihip_pair_table.h: WaveRuns).
 //
 // One synchronisation, at the end.  Bytes moved per entry without the per-UMI table: keys 8 W read three times
 // (entry, bucket, and gathered through the draw), freq 4 x 2, kept 1 x 3, root 4, cum 8 written and ~log2(N)
@@ -37,24 +37,16 @@
 #include <algorithm>
 
 #include "umihip_internal.h"
+#include "umihip_pair_table.h"
 
 namespace umihip {
 
 namespace {
 
-#define STATS_TRY(expr)                          \
-    do {                                         \
-        const hipError_t e__ = (expr);           \
-        if (e__ != hipSuccess) return -(int)e__; \
-    } while (0)
-
 constexpr int ST_THREADS = 256, ST_WAVES = ST_THREADS / 64;
 constexpr int ST_CELLS = 20;   // per base: 5 letters x 4 sets (0 pre, 1 pre-null, 2 post, 3 post-null)
 constexpr int ST_MAX_LEN = 85;
 constexpr int ST_TAB = ST_MAX_LEN * ST_CELLS;
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline uint32_t blocks_for(uint64_t n, uint32_t per) { return (uint32_t)std::max<uint64_t>(1, (n + per - 1) / per); }
 
 struct StatsWs {
     unsigned long long *ctl;   // [0] keys with a code that is no letter, [1] entries whose root[] breaks the contract
@@ -72,38 +64,32 @@ struct StatsWs {
 StatsWs stats_carve(void *ws, uint32_t n, uint32_t m, uint32_t g, uint32_t n_tasks, int L, bool per_umi)
 {
     StatsWs w;
-    char *p = (char *)ws;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        char *at = p + o;
-        o += align256(bytes);
-        return at;
-    };
-    w.ctl = (unsigned long long *)take(256); // (total[] right behind it: bad_roots)
-    w.total = (unsigned long long *)take((size_t)n * 8);
-    w.f64 = (uint64_t *)take((size_t)n * 8);
-    w.cum = (uint64_t *)take((size_t)n * 8);
-    w.picked = (uint32_t *)take((size_t)n * 4);
-    w.off = (uint64_t *)take(((size_t)m + 1) * 8);
-    w.tasks = (StatsTask *)take((size_t)n_tasks * sizeof(StatsTask));
-    w.deep_j = (uint32_t *)take((size_t)g * 4);
-    w.deep_kept = (uint32_t *)take((size_t)g * 4);
-    w.deep_tab = (uint32_t *)take((size_t)g * (size_t)L * ST_CELLS * 4);
+    Carver c(ws);
+    w.ctl = c.take<unsigned long long>(256); // (total[] right behind it: bad_roots)
+    w.total = c.take<unsigned long long>((size_t)n * 8);
+    w.f64 = c.take<uint64_t>((size_t)n * 8);
+    w.cum = c.take<uint64_t>((size_t)n * 8);
+    w.picked = c.take<uint32_t>((size_t)n * 4);
+    w.off = c.take<uint64_t>(((size_t)m + 1) * 8);
+    w.tasks = c.take<StatsTask>((size_t)n_tasks * sizeof(StatsTask));
+    w.deep_j = c.take<uint32_t>((size_t)g * 4);
+    w.deep_kept = c.take<uint32_t>((size_t)g * 4);
+    w.deep_tab = c.take<uint32_t>((size_t)g * (size_t)L * ST_CELLS * 4);
     w.ka = w.kb = nullptr;
     w.va = w.vb = nullptr;
     w.radix_tmp = nullptr;
     w.radix_bytes = 0;
     if (per_umi) {
-        w.ka = (uint64_t *)take((size_t)n * 8);
-        w.kb = (uint64_t *)take((size_t)n * 8);
-        w.va = (uint32_t *)take((size_t)n * 4);
-        w.vb = (uint32_t *)take((size_t)n * 4);
+        w.ka = c.take<uint64_t>((size_t)n * 8);
+        w.kb = c.take<uint64_t>((size_t)n * 8);
+        w.va = c.take<uint32_t>((size_t)n * 4);
+        w.vb = c.take<uint32_t>((size_t)n * 4);
         w.radix_bytes = radix_sort_temp_bytes(n);
-        w.radix_tmp = take(w.radix_bytes);
+        w.radix_tmp = c.take(w.radix_bytes);
     }
     w.scan_bytes = scan_temp_bytes(n);
-    w.scan_tmp = take(w.scan_bytes);
-    w.total_bytes = o;
+    w.scan_tmp = c.take(w.scan_bytes);
+    w.total_bytes = c.o;
     return w;
 }
 
@@ -550,8 +536,8 @@ __global__ __launch_bounds__(ST_THREADS) void stats_heads_kernel(const uint64_t 
     }
     flag[i] = head ? 1ull : 0ull;
 }
-// a lane per sorted entry; an inclusive scan inside runs of one slot over the wave leaves a run's sums in its
-// last lane there: stored where the run begins and ends inside the wave, added by atomics where it crosses an edge
+// a lane per sorted entry: a run's sums are stored where the run begins and ends inside the wave, added by atomics
+// where it crosses an edge
 __global__ __launch_bounds__(ST_THREADS) void stats_umi_sum_kernel(const uint32_t *__restrict__ order, const uint64_t *__restrict__ incl,
                                                                    const int32_t *__restrict__ freq, const uint8_t *__restrict__ kept,
                                                                    const unsigned long long *__restrict__ total, uint32_t n,
@@ -560,17 +546,10 @@ __global__ __launch_bounds__(ST_THREADS) void stats_umi_sum_kernel(const uint32_
                                                                    unsigned long long *reads_post)
 {
     const uint64_t i = (uint64_t)blockIdx.x * ST_THREADS + threadIdx.x;
-    const int lane = (int)(threadIdx.x & 63u);
-    const bool valid = i < n;
-    const uint64_t slot1 = valid ? incl[i] : 0ull; // the slot, counted from 1
-    uint64_t prev = __shfl_up(slot1, 1), next = __shfl_down(slot1, 1);
-    if (lane == 0) prev = valid && i > 0 ? incl[i - 1] : 0ull;
-    if (lane == 63) next = i + 1 < n ? incl[i + 1] : 0ull;
-    const bool head = valid && slot1 != prev;
-    const bool last = valid && (i + 1 >= n || next != slot1);
+    const WaveRuns run(incl, i, n);
     uint32_t e = 0, tpre = 0, tpost = 0;
     unsigned long long rpre = 0, rpost = 0;
-    if (valid) {
+    if (run.valid) {
         e = order[i];
         tpre = 1;
         rpre = (unsigned long long)(long long)freq[e];
@@ -579,31 +558,19 @@ __global__ __launch_bounds__(ST_THREADS) void stats_umi_sum_kernel(const uint32_
             rpost = total[e];
         }
     }
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t u1 = __shfl_up(tpre, d), u3 = __shfl_up(tpost, d);
-        const unsigned long long u2 = __shfl_up(rpre, d), u4 = __shfl_up(rpost, d);
-        const uint64_t us = __shfl_up(slot1, d);
-        if (lane >= d && us == slot1) {
-            tpre += u1;
-            rpre += u2;
-            tpost += u3;
-            rpost += u4;
-        }
-    }
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long upto = lane == 63 ? ~0ull : (2ull << lane) - 1ull;
-    if (head) umi_entry[slot1 - 1] = e; // (the sorts are stable: the run's first is its smallest entry)
-    if (valid && (last || lane == 63)) {
-        if (last && (heads & upto)) {
-            times_pre[slot1 - 1] = tpre;
-            reads_pre[slot1 - 1] = rpre;
-            times_post[slot1 - 1] = tpost;
-            reads_post[slot1 - 1] = rpost;
+    run.scan([](auto x, auto y) { return x + y; }, tpre, rpre, tpost, rpost);
+    if (run.head) umi_entry[run.slot()] = e; // (the sorts are stable: the run's first is its smallest entry)
+    if (run.tail()) {
+        if (run.whole()) {
+            times_pre[run.slot()] = tpre;
+            reads_pre[run.slot()] = rpre;
+            times_post[run.slot()] = tpost;
+            reads_post[run.slot()] = rpost;
         } else {
-            atomicAdd(times_pre + (slot1 - 1), tpre);
-            atomicAdd(reads_pre + (slot1 - 1), rpre);
-            atomicAdd(times_post + (slot1 - 1), tpost);
-            atomicAdd(reads_post + (slot1 - 1), rpost);
+            atomicAdd(times_pre + run.slot(), tpre);
+            atomicAdd(reads_pre + run.slot(), rpre);
+            atomicAdd(times_post + run.slot(), tpost);
+            atomicAdd(reads_post + run.slot(), rpost);
         }
     }
 }
@@ -658,25 +625,25 @@ int stats_on_device(void *workspace, const StatsCall &c, hipStream_t s)
             h_deep_j[g++] = j;
         }
     }
-    STATS_TRY(hipMemsetAsync(w.ctl, 0, 256, s));
-    STATS_TRY(hipMemsetAsync(w.total, 0, (size_t)n * 8, s));
-    STATS_TRY(hipMemsetAsync(c.d_count_pre, 0, (size_t)c.hist_bins * 8, s));
-    STATS_TRY(hipMemsetAsync(c.d_count_post, 0, (size_t)c.hist_bins * 8, s));
-    STATS_TRY(hipMemsetAsync(c.d_dist, 0, dist_words * 8, s));
-    STATS_TRY(hipMemcpyAsync(w.off, c.h_off, ((size_t)m + 1) * 8, hipMemcpyHostToDevice, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(w.ctl, 0, 256, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(w.total, 0, (size_t)n * 8, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(c.d_count_pre, 0, (size_t)c.hist_bins * 8, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(c.d_count_post, 0, (size_t)c.hist_bins * 8, s));
+    UMIHIP_TRY_NEG(hipMemsetAsync(c.d_dist, 0, dist_words * 8, s));
+    UMIHIP_TRY_NEG(hipMemcpyAsync(w.off, c.h_off, ((size_t)m + 1) * 8, hipMemcpyHostToDevice, s));
     if (c.n_deep) {
-        STATS_TRY(hipMemcpyAsync(w.deep_j, h_deep_j, (size_t)c.n_deep * 4, hipMemcpyHostToDevice, s));
-        STATS_TRY(hipMemcpyAsync(w.tasks, h_tasks, (size_t)c.n_tasks * sizeof(StatsTask), hipMemcpyHostToDevice, s));
-        STATS_TRY(hipMemsetAsync(w.deep_kept, 0, (size_t)c.n_deep * 4, s));
-        STATS_TRY(hipMemsetAsync(w.deep_tab, 0, (size_t)c.n_deep * (size_t)L * ST_CELLS * 4, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(w.deep_j, h_deep_j, (size_t)c.n_deep * 4, hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemcpyAsync(w.tasks, h_tasks, (size_t)c.n_tasks * sizeof(StatsTask), hipMemcpyHostToDevice, s));
+        UMIHIP_TRY_NEG(hipMemsetAsync(w.deep_kept, 0, (size_t)c.n_deep * 4, s));
+        UMIHIP_TRY_NEG(hipMemsetAsync(w.deep_tab, 0, (size_t)c.n_deep * (size_t)L * ST_CELLS * 4, s));
     }
     const uint32_t grid_cap = c.n_cus * 8;
     stats_entry_kernel<<<std::min(blocks_for(n, ST_THREADS), grid_cap), ST_THREADS, 0, s>>>(
         c.d_keys, c.d_freq, n, L, W, c.hist_bins, w.f64, (unsigned long long *)c.d_count_pre, w.ctl);
-    STATS_TRY(hipGetLastError());
-    STATS_TRY(scan_inclusive_u64(w.f64, w.cum, n, w.scan_tmp, w.scan_bytes, s));
+    UMIHIP_TRY_NEG(hipGetLastError());
+    UMIHIP_TRY_NEG(scan_inclusive_u64(w.f64, w.cum, n, w.scan_tmp, w.scan_bytes, s));
     stats_pick_kernel<<<blocks_for(n, ST_THREADS), ST_THREADS, 0, s>>>(w.cum, n, c.seed, w.picked);
-    STATS_TRY(hipGetLastError());
+    UMIHIP_TRY_NEG(hipGetLastError());
     StatsArgs a;
     a.keys = c.d_keys;
     a.freq = c.d_freq;
@@ -704,24 +671,24 @@ int stats_on_device(void *workspace, const StatsCall &c, hipStream_t s)
     }
     if (n_lane) {
         stats_lane_kernel<<<std::min(blocks_for(m, ST_THREADS), grid_cap), ST_THREADS, 0, s>>>(a);
-        STATS_TRY(hipGetLastError());
+        UMIHIP_TRY_NEG(hipGetLastError());
     }
     if (n_wave) {
         stats_wave_kernel<<<std::min(blocks_for(m, ST_THREADS), grid_cap), ST_THREADS, 0, s>>>(a);
-        STATS_TRY(hipGetLastError());
+        UMIHIP_TRY_NEG(hipGetLastError());
     }
     if (c.n_deep) {
         const uint32_t blocks = std::min(blocks_for(c.n_tasks, ST_WAVES), grid_cap);
         stats_deep_roots_kernel<<<blocks, ST_THREADS, 0, s>>>(a, w.tasks, c.n_tasks, w.deep_j, w.deep_kept);
-        STATS_TRY(hipGetLastError());
+        UMIHIP_TRY_NEG(hipGetLastError());
         stats_deep_count_kernel<<<blocks, ST_THREADS, 0, s>>>(a, w.tasks, c.n_tasks, w.deep_j, w.deep_kept, w.deep_tab);
-        STATS_TRY(hipGetLastError());
+        UMIHIP_TRY_NEG(hipGetLastError());
         stats_deep_finish_kernel<<<c.n_deep, 64, 0, s>>>(a, w.deep_j, w.deep_kept, w.deep_tab, c.n_deep);
-        STATS_TRY(hipGetLastError());
+        UMIHIP_TRY_NEG(hipGetLastError());
     }
     stats_post_kernel<<<std::min(blocks_for(n, ST_THREADS), grid_cap), ST_THREADS, 0, s>>>(c.d_kept, w.total, n, c.hist_bins,
                                                                                           (unsigned long long *)c.d_count_post);
-    STATS_TRY(hipGetLastError());
+    UMIHIP_TRY_NEG(hipGetLastError());
     if (per_umi) {
         UmiMasks um;
         for (int wd = 0; wd < 4; wd++) {
@@ -733,9 +700,9 @@ int stats_on_device(void *workspace, const StatsCall &c, hipStream_t s)
         for (int wd = 0; wd < W; wd++) {
             const int bits = std::min(64, 3 * L - 64 * wd);
             stats_word_kernel<<<blocks_for(n, ST_THREADS), ST_THREADS, 0, s>>>(c.d_keys, W, wd, um.wm[wd], wd ? va : nullptr, n, ka, va);
-            STATS_TRY(hipGetLastError());
+            UMIHIP_TRY_NEG(hipGetLastError());
             bool in_b = false;
-            STATS_TRY(radix_sort_pairs_u64(ka, kb, va, vb, n, 0, bits, w.radix_tmp, w.radix_bytes, &in_b, s));
+            UMIHIP_TRY_NEG(radix_sort_pairs_u64(ka, kb, va, vb, n, 0, bits, w.radix_tmp, w.radix_bytes, &in_b, s));
             if (in_b) {
                 std::swap(ka, kb);
                 std::swap(va, vb);
@@ -743,23 +710,21 @@ int stats_on_device(void *workspace, const StatsCall &c, hipStream_t s)
         }
         uint64_t *flag = w.f64, *incl = w.cum; // (the draws have been made)
         stats_heads_kernel<<<blocks_for(n, ST_THREADS), ST_THREADS, 0, s>>>(c.d_keys, W, um, va, n, flag);
-        STATS_TRY(hipGetLastError());
-        STATS_TRY(scan_inclusive_u64(flag, incl, n, w.scan_tmp, w.scan_bytes, s));
-        STATS_TRY(hipMemsetAsync(c.d_times_pre, 0, (size_t)n * 4, s)); // (a run that crosses a wave is added up in place)
-        STATS_TRY(hipMemsetAsync(c.d_reads_pre, 0, (size_t)n * 8, s));
-        STATS_TRY(hipMemsetAsync(c.d_times_post, 0, (size_t)n * 4, s));
-        STATS_TRY(hipMemsetAsync(c.d_reads_post, 0, (size_t)n * 8, s));
+        UMIHIP_TRY_NEG(hipGetLastError());
+        UMIHIP_TRY_NEG(scan_inclusive_u64(flag, incl, n, w.scan_tmp, w.scan_bytes, s));
+        UMIHIP_TRY_NEG(hipMemsetAsync(c.d_times_pre, 0, (size_t)n * 4, s)); // (a run that crosses a wave is added up in place)
+        UMIHIP_TRY_NEG(hipMemsetAsync(c.d_reads_pre, 0, (size_t)n * 8, s));
+        UMIHIP_TRY_NEG(hipMemsetAsync(c.d_times_post, 0, (size_t)n * 4, s));
+        UMIHIP_TRY_NEG(hipMemsetAsync(c.d_reads_post, 0, (size_t)n * 8, s));
         stats_umi_sum_kernel<<<blocks_for(n, ST_THREADS), ST_THREADS, 0, s>>>(
             va, incl, c.d_freq, c.d_kept, w.total, n, c.d_umi_entry, c.d_times_pre, (unsigned long long *)c.d_reads_pre,
             c.d_times_post, (unsigned long long *)c.d_reads_post);
-        STATS_TRY(hipGetLastError());
-        STATS_TRY(hipMemcpyAsync(c.h_pinned + 2, incl + (n - 1), 8, hipMemcpyDeviceToHost, s));
+        UMIHIP_TRY_NEG(hipGetLastError());
+        UMIHIP_TRY_NEG(hipMemcpyAsync(c.h_pinned + 2, incl + (n - 1), 8, hipMemcpyDeviceToHost, s));
     }
-    STATS_TRY(hipMemcpyAsync(c.h_pinned, w.ctl, 16, hipMemcpyDeviceToHost, s));
-    STATS_TRY(hipStreamSynchronize(s));
+    UMIHIP_TRY_NEG(hipMemcpyAsync(c.h_pinned, w.ctl, 16, hipMemcpyDeviceToHost, s));
+    UMIHIP_TRY_NEG(hipStreamSynchronize(s));
     return 0;
 }
-
-#undef STATS_TRY
 
 } // namespace umihip
