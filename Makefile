@@ -8,9 +8,9 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wextra -Wno-unuse
 LIB := $(PKG)/libumihip.so
 OBJDIR := build/obj
 # the library's translation units, listed once: the kernels (.hip), then the host side (.cpp)
-SRCS := umihip_kernels umihip_seg umihip_collapse umihip_stage umihip_radix umihip_wide umihip_edit umihip_seq \
+SRCS := umihip_kernels umihip_seg umihip_collapse umihip_stage umihip_radix umihip_wide umihip_edit umihip_cr umihip_seq \
         umihip_consensus umihip_consensus_bam umihip_correct umihip_barcode umihip_count umihip_multigene umihip_stats umihip_cells umihip_genes umihip_gene_introns umihip_gene_classes umihip_gene_transcripts umihip_gene_transcript_classes umihip_velocity umihip_saturation umihip_junctions \
-        umihip_api umihip_pipeline umihip_batch umihip_stage_api umihip_seq_api umihip_correct_api umihip_count_api umihip_genes_api umihip_data
+        umihip_api umihip_pipeline umihip_batch umihip_stage_api umihip_seq_api umihip_correct_api umihip_count_api umihip_genes_api umihip_cr_api umihip_data
 OBJS := $(patsubst %,$(OBJDIR)/%.o,$(SRCS))
 # development build (make dev): the shipped sources plus the round-1 tile kernels, their key sort
 # and their options (-DUMIHIP_DEV), as libumihip_dev.so; the legacy cross-check tests load it

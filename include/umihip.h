@@ -175,6 +175,8 @@ const char *umi_last_error(void);
  *   "stats_split"    64..2^30 (default 4096): umi_dedup_stats counts a bucket of at least this many entries in pieces
  *                    over the whole grid instead of by one wave (raised by itself where the deep buckets' tables,
  *                    80 bytes per base each, would pass 512 MB)
+ *   "cr_small_max"   0..1024 (default 128): umi_dedup_batch_cr decides a bucket of at most this many entries with one
+ *                    lane per entry, a larger one from the list of neighbour pairs (0: every bucket from the list)
  *   "gene_top"       0/1 (default 1): umi_assign_genes searches a sampled top of its index in LDS before the
  *                    index itself (0: the index alone); umi_assign_genes_introns likewise, for both its tiers,
  *                    and umi_assign_genes_transcripts for its distinct exons
@@ -1155,6 +1157,49 @@ int umi_dedup_batch_edit_device(umi_ctx *ctx, const uint64_t *d_keys, const uint
                                 const int32_t *d_freq, const uint64_t *bucket_off, uint64_t n_buckets,
                                 int umi_len, int k, float percentage, int algo, int32_t adj_max_freq,
                                 uint8_t *d_kept, uint32_t *d_root, void *hip_stream, umi_stats *stats);
+
+/* ---- the batched call by Cell Ranger's one-mismatch correction (umihip_cr.hip).  No counterpart in the
+ *      reference; the rule is stated after Cell Ranger's correct_umi loop and STARsolo's --soloUMIdedup 1MM_CR and
+ *      is not claimed byte-equal to either program.  It is not transitive, so no k and percentage of the other
+ *      algorithms reaches it; this is a call of its own, not a fourth `algo` (umi_dedup_batch*(algo = 3) stays
+ *      UMI_ERR_ARG).  Exact integers and letters; tests/cr_model.py states it twice in plain Python.
+ *      Inside one bucket of distinct UMIs of umi_len letters over A C G T N, with freq:
+ *        candidates  t is a candidate for s when the two differ at exactly one base p and t[p] is one of A C G T
+ *                    (the loop substitutes the four nucleotides at every position and looks the result up): an N
+ *                    in s may be replaced, an N is never substituted in;
+ *        target      target(s) = the maximum of {s} and its candidates under (freq, then the UMI as a byte string,
+ *                    A < C < G < N < T): a higher count wins, among equal counts the lexicographically largest
+ *                    string, s itself included (the sequential loop's `value > count or (value == count and
+ *                    corrected < test)`);
+ *        molecules   a UMI is a molecule iff it is some UMI's target, its own included: for a -> b, b -> c both b
+ *                    and c are molecules.
+ *      kept[i] = 1 iff entry i is a target.  root[i] (may be NULL) = i where kept[i], else target(i), which is kept
+ *      by construction: kept[i] implies root[i] == i, and kept[root[i]] -- the contract umi_count_matrix,
+ *      umi_filter_multigene, umi_dedup_stats, the velocity, saturation and junction calls check, so they take the
+ *      result unchanged.  target[i] (may be NULL) = the raw target, which may be a kept entry whose own target lies
+ *      elsewhere.  Difference from Cell Ranger: the reads of a kept UMI that Cell Ranger would itself correct stay
+ *      with that UMI under root[]; molecule counts are the same, reads per molecule in such chains are not.
+ *      The distance is fixed at one substitution: no k, no percentage, no adj_max_freq.
+ *      Keys are one word, umi_len 1..UMI_MAX_UMI_LEN; code 100 in a key is N, so nmask may be NULL whatever the
+ *      keys hold (where it is given, a key with code 100 at a base it does not cover is UMI_ERR_ORDER).  Entries of
+ *      a bucket in rank order and freq >= 1 as for umi_dedup_batch (UMI_ERR_ORDER).  UMI_ERR_ARG: umi_len above
+ *      21, a multi-device context, 2^31 entries or more, NULL keys / freq / kept with entries present.  No entries:
+ *      UMI_OK.  A deferred call that is out on the context ends first.
+ *      Option "cr_small_max" (0..1024, default 128): a bucket of at most this many entries is decided by a kernel
+ *      with one lane per entry that walks the bucket and keeps its best (count, string, index) in registers; a
+ *      larger one through the list of pairs within one substitution that the pipeline of umi_data_new leaves,
+ *      resolved by three passes that do not depend on the list's order (best count, best string at that count,
+ *      the one index that has it).  Same bytes on either path.
+ *      umi_stats: n_umis, n_buckets, max_bucket, n_kept, n_pairs as for the other calls; n_edges = the unordered
+ *      pairs of one bucket at exactly one mismatching base, admissible or not, on both paths; ms_* under "profile"
+ *      (ms_pairs: the small buckets' kernel and the pipeline; ms_collapse: the list's resolution).
+ *      The symbols are additive: UMI_ABI_VERSION stays 2. */
+int umi_dedup_batch_cr(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask, const int32_t *freq,
+                       const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, uint8_t *kept, uint32_t *root,
+                       uint32_t *target, umi_stats *stats);
+int umi_dedup_batch_cr_device(umi_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_nmask, const int32_t *d_freq,
+                              const uint64_t *bucket_off, uint64_t n_buckets, int umi_len, uint8_t *d_kept,
+                              uint32_t *d_root, uint32_t *d_target, void *hip_stream, umi_stats *stats);
 
 /* The kept mask as one bit per entry (bit i % 8 of byte i / 8; ceil(n / 8) bytes at d_bits), packed
  * on the device and enqueued on hip_stream: what a one-process-per-GPU host all-gathers over RCCL

@@ -207,6 +207,10 @@ SIGNATURES = {
                                               C.c_uint64, C.c_int, C.c_int, C.c_float, C.c_int,
                                               C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.POINTER(Stats)]),
+    "umi_dedup_batch_cr": (C.c_int, [C.c_void_p, _u64p, _u64p, _i32p, _u64p, C.c_uint64, C.c_int, _u8p, _u32p, _u32p,
+                                     C.POINTER(Stats)]),
+    "umi_dedup_batch_cr_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_uint64, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     "umi_dedup_batch_device_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_void_p,
                                                C.c_uint64, C.c_int, C.c_int, C.c_float, C.c_int,
                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

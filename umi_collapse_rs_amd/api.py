@@ -157,6 +157,32 @@ class Context:
                                           C.byref(st)))
         return kept, root, st.as_dict()
 
+    def dedup_batch_cr(self, keys, nmask, freq, bucket_off, umi_len, want_root=True, want_target=False):
+        """Cell Ranger's one-mismatch correction (umi_dedup_batch_cr): every UMI goes to the best of itself and
+        its one-mismatch neighbours by (count, string), and every target is a molecule -- not transitive, no k,
+        no percentage.  One-word keys, umi_len <= 21; nmask may be None whatever the keys hold.  Returns
+        (kept u8[N], root u32[N] or None, stats dict), with want_target (kept, root, target u32[N], stats)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        freq = np.ascontiguousarray(freq, dtype=np.int32)
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        nm = None if nmask is None else np.ascontiguousarray(nmask, dtype=np.uint64)
+        n = len(keys)
+        if len(freq) != n or (nm is not None and len(nm) != n):
+            raise ValueError("keys/nmask/freq lengths differ")
+        if len(bucket_off) < 1 or (len(bucket_off) > 1 and int(bucket_off[-1]) != n):
+            raise ValueError("bucket_off[-1] must equal len(keys)")
+        kept = np.zeros(n, dtype=np.uint8)
+        root = np.zeros(n, dtype=np.uint32) if want_root else None
+        target = np.zeros(n, dtype=np.uint32) if want_target else None
+        st = Stats()
+        check(load().umi_dedup_batch_cr(self._h, ptr(keys, C.c_uint64), ptr(nm, C.c_uint64), ptr(freq, C.c_int32),
+                                        ptr(bucket_off, C.c_uint64), len(bucket_off) - 1, umi_len,
+                                        ptr(kept, C.c_uint8), ptr(root, C.c_uint32), ptr(target, C.c_uint32),
+                                        C.byref(st)))
+        if want_target:
+            return kept, root, target, st.as_dict()
+        return kept, root, st.as_dict()
+
     def dedup_batch_wide(self, keys, nmask, freq, bucket_off, umi_len, k=1, percentage=0.5,
                          algo=UMI_ALGO_DIRECTIONAL, adj_max_freq=0, want_root=True):
         """Batched call for keys of several words (umi_len > 21): keys / nmask uint64 [N, n_words]."""
@@ -1171,6 +1197,15 @@ class Context:
                                                  stream or None, C.byref(st)))
         return st.as_dict()
 
+    def dedup_batch_cr_device(self, d_keys, d_nmask, d_freq, bucket_off, umi_len, d_kept, d_root=0, d_target=0,
+                              stream=0):
+        """umi_dedup_batch_cr_device: dedup_batch_cr on device pointers (d_root and d_target may be 0)."""
+        bucket_off = np.ascontiguousarray(bucket_off, dtype=np.uint64)
+        st = Stats()
+        check(load().umi_dedup_batch_cr_device(self._h, d_keys, d_nmask or None, d_freq, ptr(bucket_off, C.c_uint64),
+                                               len(bucket_off) - 1, umi_len, d_kept, d_root or None, d_target or None,
+                                               stream or None, C.byref(st)))
+        return st.as_dict()
 
     def dedup_batch_device_begin(self, d_keys, d_nmask, d_freq, bucket_off, umi_len, d_kept, d_root=0,
                                  k=1, percentage=0.5, algo=UMI_ALGO_DIRECTIONAL, adj_max_freq=0,

@@ -242,6 +242,9 @@ int umi_ctx_set_option(umi_ctx *ctx, const char *name, int64_t value)
     } else if (!strcmp(name, "cons_split")) {
         if (value < 2 || value > (1ll << 30)) return fail(UMI_ERR_ARG, "cons_split must be in 2..2^30");
         ctx->cons_split = (uint32_t)value;
+    } else if (!strcmp(name, "cr_small_max")) {
+        if (value < 0 || value > CR_SMALL_MAX_CAP) return fail(UMI_ERR_ARG, "cr_small_max must be in 0..%u", CR_SMALL_MAX_CAP);
+        ctx->cr_small_max = (uint32_t)value;
     } else if (!strcmp(name, "stats_split")) {
         if (value < 64 || value > (1ll << 30)) return fail(UMI_ERR_ARG, "stats_split must be in 64..2^30");
         ctx->stats_split = (uint32_t)value;

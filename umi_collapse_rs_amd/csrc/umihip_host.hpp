@@ -273,6 +273,11 @@ struct umi_ctx {
     bool velocity_skip = false; // umi_velocity_matrix: a read loads its molecule's evidence and skips the atomic where its bit is set (option "velocity_skip")
     bool saturation_skip = false; // umi_saturation_curve: likewise for its molecule's word of levels (option "saturation_skip")
     bool gene_body_top = true; //umi_assign_genes_introns: the body tables' tops too (option "gene_body_top"; counts with gene_top)
+    // umi_dedup_batch_cr*: buckets of at most cr_small_max entries are decided a lane per entry, the others from the
+    // neighbour list (option "cr_small_max"); its device table, and its workspace (counters, span, target, the larger
+    // buckets' compact arrays and best words), carved anew by every call
+    uint32_t cr_small_max = umihip::CR_SMALL_MAX;
+    umihip::DevBuf cr_boff, cr_ws;
     uint32_t cons_split = 512; // clusters of at least this many reads are summed in pieces by the whole grid
     umihip::PinnedBuf h_boff;                 // pinned staging of the bucket table
     umihip::PinnedBuf h_tasks;                // pinned staging of the bit-sliced tile-task lists

@@ -399,6 +399,47 @@ hipError_t launch_edit_prep(const uint64_t *keys, const uint64_t *nmask, const i
 // LDS queue of its hits, exact Levenshtein distance of each; permitted pairs to the edge list
 hipError_t launch_edit_pairs(const PairArgs &a, const uint32_t *counts, uint32_t n_tasks, int umi_len, hipStream_t s);
 
+// ---- one-mismatch correction after Cell Ranger (umihip_cr.hip: umi_dedup_batch_cr): one-word keys, umi_len 1..21
+// The call's own counters, eight words of device memory zeroed by the host
+enum CrCounter : int {
+    CR_BAD = 0,         // freq < 1, an N code a given nmask does not cover, a bucket outside the arrays
+    CR_RISES = 1,       // entries whose freq is above their predecessor's ...
+    CR_START_RISES = 2, // ... of which sit at the start of a bucket
+    CR_HAS_N = 3,       // entries with an N
+    CR_PAIRS = 4,       // unordered pairs of one bucket at exactly one mismatching base
+    CR_KEPT = 5,
+    CR_COUNT = 8,
+};
+constexpr uint32_t CR_SMALL_MAX_CAP = 1024; // option "cr_small_max" at most: a lane's place in its bucket is 10 bits
+constexpr uint32_t CR_SMALL_MAX = 128;      // its default
+constexpr uint32_t CR_GATHER_CHUNK = 4096;  // entries of one gather task
+struct CrGatherTask {
+    uint32_t src, dst, len; // entries [src, src + len) of the call become [dst, dst + len) of the compact arrays
+};
+// every entry: freq >= 1, rises, N codes (nmask may be null: code 100 is N)
+hipError_t launch_cr_check(const uint64_t *keys, const uint64_t *nmask, const int32_t *freq, uint32_t n, int umi_len,
+                           unsigned long long *counters, uint32_t n_cus, hipStream_t s);
+// every bucket: the rise at its start, and for a bucket of 1..small_max entries span[i] = (i - start) | size << 10 for
+// its entries (the other entries' words are not written: the host zeroes span[] where there are any)
+hipError_t launch_cr_spans(const uint64_t *d_bucket_off, uint64_t n_buckets, uint32_t n, uint32_t small_max,
+                           const int32_t *freq, uint32_t *span, unsigned long long *counters, uint32_t n_cus, hipStream_t s);
+// the small buckets, a lane per entry: target[i], kept[target[i]] = 1 (kept[] zeroed before), CR_PAIRS
+hipError_t launch_cr_small(const uint64_t *keys, const int32_t *freq, const uint32_t *span, uint32_t n, int umi_len,
+                           uint32_t *target, uint8_t *kept, unsigned long long *counters, uint32_t n_cus, hipStream_t s);
+// the larger buckets' entries into compact arrays (gidx: where each came from)
+hipError_t launch_cr_gather(const CrGatherTask *tasks, uint32_t n_tasks, const uint64_t *keys, const int32_t *freq,
+                            uint64_t *ckeys, int32_t *cfreq, uint32_t *gidx, hipStream_t s);
+hipError_t launch_cr_nmask(const uint64_t *ckeys, uint32_t nl, int umi_len, uint64_t *nmask, uint32_t n_cus, hipStream_t s);
+// ... resolved from the (i, j) list of the pipeline's MODE_NEIGHBOURS at k = 1 over the compact arrays: best count,
+// best string among the candidates at that count, the one index that has it; then kept[target] = 1.  gidx null: the
+// compact arrays are the call's.  best_f [nl], best_k [nl]: workspace
+hipError_t launch_cr_resolve(const uint2 *edges, uint32_t n_edges, const uint64_t *ckeys, const int32_t *cfreq, uint32_t nl,
+                             int umi_len, const uint32_t *gidx, int32_t *best_f, unsigned long long *best_k, uint32_t *target,
+                             uint8_t *kept, unsigned long long *counters, uint32_t n_cus, hipStream_t s);
+// root[i] = i where kept[i], else target[i] (root may be null); CR_KEPT
+hipError_t launch_cr_finish(const uint8_t *kept, const uint32_t *target, uint32_t n, uint32_t *root,
+                            unsigned long long *counters, uint32_t n_cus, hipStream_t s);
+
 // ---- whole-read keys (umihip_seq.hip): reads of up to 256 bases, 1..12 words per key, stride words apart
 constexpr int SEQ_MAX_WORDS = 12;
 constexpr uint32_t SEQ_TILE = 64;           // rows / columns of a pair task

@@ -261,6 +261,7 @@ struct Cli { // src/cli.rs:7-77 (same flags, same defaults)
         std::vector<std::string> gene_names; // ... and the gene_name of each one's first taken line (empty: none)
     } annotation;
     bool edit_distance = false; // --distance edit: -k bounds the Levenshtein distance (umi_dedup_batch_edit)
+    bool algo_cr = false;       // --algo cr: Cell Ranger's one-mismatch correction (umi_dedup_batch_cr); filled in by validate()
     // filled in by validate(): --algo as UMI_ALGO_*, --merge as 0 any, 1 avgqual, 2 mapqual, and the two lists
     int algo_id = 0, merge_id = 0;
     std::vector<uint8_t> whitelist, cell_list; // the listed UMIs / barcodes back to back
@@ -290,8 +291,12 @@ void usage()
               "  -p <PERCENTAGE>          Directional threshold percentage [default: 0.5]\n"
               "      --num-threads <N>    Threads used in reader/writer [default: 1]\n"
               "      --umi_sep <BYTE>     Separator byte value between UMI and read name [default: 95]\n"
-              "      --algo <ALGO>        adj, dir or cluster [default: dir]; cluster: one UMI per connected component of\n"
-              "                           \"within k\" (umi_tools' cluster, STARsolo's 1MM_All at -k 1); -p plays no part\n"
+              "      --algo <ALGO>        adj, dir or cluster [default: dir], or cr; cluster: one UMI per connected component of\n"
+              "                           \"within k\" (umi_tools' cluster, STARsolo's 1MM_All at -k 1); -p plays no part;\n"
+              "                           cr: Cell Ranger's one-mismatch correction (STARsolo's 1MM_CR) -- every UMI goes to\n"
+              "                           the best of itself and its one-mismatch neighbours by (reads, string), every target\n"
+              "                           is a molecule, nothing is transitive; -k 1 only, -p plays no part (bam/sam mode,\n"
+              "                           one pass, one GPU, UMIs of at most 21 bases)\n"
               "      --merge <MERGE>      any, avgqual or mapqual [default: mapqual in bam mode, avgqual in fastq mode]\n"
               "      --data <DATA>        accepted; every value gives Naive's result (as in the reference)\n"
               "      --keep-unmapped      Keep unmapped reads\n"
@@ -716,6 +721,8 @@ void check_edit_length(const Cli &args, size_t umi_length, const std::string &wh
 {
     if (args.edit_distance && umi_length > UMI_MAX_UMI_LEN)
         die("--distance edit takes UMIs of at most 21 bases (" + whose + " " + std::to_string(umi_length) + ")");
+    if (args.algo_cr && umi_length > UMI_MAX_UMI_LEN) // (--algo cr: one-word keys as well)
+        die("--algo cr takes UMIs of at most 21 bases (" + whose + " " + std::to_string(umi_length) + ")");
 }
 
 // --output-stats: its three files (none without the flag)
@@ -858,6 +865,16 @@ bool validate(Cli &args)
         if (r == "top-cells" && !args.expect_cells_given) die("--cell-filter top-cells wants --expect-cells N");
         if (r == "min-molecules" && !args.cell_min_molecules_given) die("--cell-filter min-molecules wants --cell-min-molecules T");
     }
+    // --algo cr: everything about it that can be refused is, before the GPU is woken
+    args.algo_cr = args.algo == "cr";
+    if (args.algo_cr) {
+        if (args.mode == "fastq") die("--algo cr is defined in bam/sam mode only (whole reads are the key in fastq mode)");
+        if (args.two_pass) die("--algo cr does not go with --two-pass");
+        if (args.devices.size() > 1) die("--algo cr runs on one GPU: --devices takes one id with it");
+        if (args.edit_distance) die("--algo cr does not go with --distance edit (its distance is one substitution)");
+        if (args.k != 1) die("--algo cr corrects at one mismatch: -k " + std::to_string(args.k) + " does not go with it");
+        check_edit_length(args, args.umi_length, "-u");
+    }
     // --distance edit: everything about it that can be refused is, before the GPU is woken
     if (args.edit_distance) {
         if (args.mode == "fastq") die("--distance edit is defined in bam/sam mode only (whole reads are the key in fastq mode)");
@@ -907,6 +924,7 @@ bool validate(Cli &args)
     if (args.algo == "dir") args.algo_id = UMI_ALGO_DIRECTIONAL;
     else if (args.algo == "adj") args.algo_id = UMI_ALGO_ADJACENCY;
     else if (args.algo == "cluster") args.algo_id = UMI_ALGO_CLUSTER; // (not `cc`: that name stays refused, as below)
+    else if (args.algo_cr) args.algo_id = UMI_ALGO_DIRECTIONAL; // (a call of its own, HipLib::dedup: the id plays no part)
     else die("Invalid algorithm combination: " + args.algo + " , " + args.merge + " and " + args.data); // main.rs:86-91
     if (args.merge == "any") args.merge_id = 0;
     else if (args.merge == "avgqual") args.merge_id = 1;

@@ -74,11 +74,16 @@ struct HipLib {
     // --distance edit: resolved only when the flag is given, like --consensus below; one-word keys only
     bool want_edit = false;
     decltype(&umi_dedup_batch_edit) dedup_batch_edit = nullptr;
-    // the batched call of the run: by the distance --distance names
+    // --algo cr: likewise; one-word keys only, no -k and no -p
+    bool want_cr = false;
+    decltype(&umi_dedup_batch_cr) dedup_batch_cr = nullptr;
+    // the batched call of the run: by the rule --algo names and the distance --distance names
     int dedup(umi_ctx *ctx, const uint64_t *keys, const uint64_t *nmask, int n_words, const int32_t *freq, const uint64_t *off,
               uint64_t nb, int umi_len, int k, float percentage, int algo, int32_t adj_max_freq, uint8_t *kept, uint32_t *root,
               umi_stats *st) const
     {
+        if (want_cr) // (n_words is 1: a UMI length above 21 has been refused)
+            return dedup_batch_cr(ctx, keys, nmask, freq, off, nb, umi_len, kept, root, nullptr, st);
         if (want_edit) // (n_words is 1: a UMI length above 21 has been refused)
             return dedup_batch_edit(ctx, keys, nmask, freq, off, nb, umi_len, k, percentage, algo, adj_max_freq, kept, root, st);
         return dedup_batch(ctx, keys, nmask, n_words, freq, off, nb, umi_len, k, percentage, algo, adj_max_freq, kept, root, st);
@@ -139,7 +144,7 @@ struct HipLib {
     int (*hip_memcpy)(void *, const void *, size_t, int) = nullptr; // kind: 1 host to device, 2 device to host
     std::string error;
     explicit HipLib(const Cli &args)
-        : want_edit(args.edit_distance), want_consensus(args.consensus), want_consensus_bam(args.call_consensus),
+        : want_edit(args.edit_distance), want_cr(args.algo_cr), want_consensus(args.consensus), want_consensus_bam(args.call_consensus),
           want_correct(!args.whitelist.empty()), want_barcodes(!args.cell_list.empty() && !args.cell_wl_multi),
           want_barcodes_multi(!args.cell_list.empty() && args.cell_wl_multi),
           want_count(!args.count_matrix.empty()), want_stats(!args.output_stats.empty()),
@@ -182,6 +187,7 @@ struct HipLib {
         stage_seqs_device = (decltype(stage_seqs_device))sym("umi_stage_seqs_device");
         dedup_seqs_device = (decltype(dedup_seqs_device))sym("umi_dedup_seqs_device");
         if (want_edit) dedup_batch_edit = (decltype(dedup_batch_edit))sym("umi_dedup_batch_edit");
+        if (want_cr) dedup_batch_cr = (decltype(dedup_batch_cr))sym("umi_dedup_batch_cr");
         if (want_consensus) {
             consensus_seqs = (decltype(consensus_seqs))sym("umi_consensus_seqs");
             consensus_seqs_device = (decltype(consensus_seqs_device))sym("umi_consensus_seqs_device");

@@ -459,6 +459,7 @@ struct Summary {
         std::fprintf(stderr, args.track_clusters ? "Number of groups of reads: %llu\n" : "Number of reads after deduplicating: %llu\n",
                      (unsigned long long)n_kept); // :259-266
         if (args.edit_distance) std::fprintf(stderr, "UMI distance: edit\n");
+        if (args.algo_cr) std::fprintf(stderr, "UMI correction: cr\n");
         if (args.filter_multigene) {
             std::fprintf(stderr, "UMI filtering: multi-gene\n");
             std::fprintf(stderr, "Number of UMIs seen in several genes of a cell: %llu\n", (unsigned long long)mg_counts[0]);

@@ -113,6 +113,11 @@
 // DIR/junctions/ (and, for the called cells, to DIR/junctions/filtered/); everything else stays byte for byte likewise.
 // --algo cluster: connected components of "within -k" (cli.hpp); every pipeline here only forwards the algorithm
 // to the library, so it goes with every flag --algo dir goes with.
+// --algo cr: Cell Ranger's one-mismatch correction (cli.hpp; include/umihip.h has the rule, tests/cr_model.py defines
+// it): the one-pass bam/sam pipeline's batched call is umi_dedup_batch_cr (HipLib::dedup), whose kept[] and root[] keep
+// the contract of the other algorithms, so everything behind the collapse -- the matrix, the filters, the statistics,
+// --tag, --call-consensus -- runs as it is.  -k 1 only, -p plays no part; the summary gains "UMI correction: cr".
+// Refused before the GPU is woken: fastq mode, --two-pass, several --devices, --distance edit, UMIs of more than 21 bases.
 // Not implemented, as in the reference: --algo cc (that spelling stays refused; `cluster` is the mode's name).
 #include "annotation.hpp"
 #include "fastq_mode.hpp"
